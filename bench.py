@@ -54,6 +54,29 @@ def cpu_baseline(n, m, sampler, y):
 
 FSTAR_TOL = 1e-9       # tolerance of every f* comparison (north star: posterior means within 1e-8 relative)
 
+# --dump-outputs: the state one MCMC iteration hands a caller (gpirtMCMC stores theta, beta and f of every iteration and
+# accumulates the IRFs from f*).  At most DUMP_MAX_VALUES float64 values per array (8 MB; 32 MB for all four): f at the
+# metric size (8192 x 1024, 64 MB) is written as a sample at fixed, seeded positions of its column-major flattening.
+DUMP_NAMES = ("theta", "beta", "fstar", "f")
+DUMP_MAX_VALUES = 1 << 20
+DUMP_SAMPLE_SEED = 20240
+
+
+def snapshot_outputs(ss):
+    """Host copies of DUMP_NAMES after the last step of `ss` (item-sharded arrays gathered over the ranks: a collective)."""
+    import numpy as np
+    out = {}
+    for name in DUMP_NAMES:
+        full = ss.engine.get(name) if name == "theta" else ss.gather(name)      # theta is replicated on every rank
+        a = np.asarray(full, dtype=np.float64).ravel(order="F")
+        sampled = a.size > DUMP_MAX_VALUES
+        if sampled:
+            a = a[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, DUMP_MAX_VALUES, replace=False))]
+        else:
+            a = np.asfortranarray(full, dtype=np.float64)
+        out[name] = (a, {"shape": list(full.shape), "sampled_values": int(a.size) if sampled else None})
+    return out
+
 
 def _roof_entry(prof, bound, peak, unit, kernel):
     """One more roofline entry from the library's event pairs: (ms, launches, flops, bytes) of a kernel class."""
@@ -118,6 +141,10 @@ def main():
                     help="N > 1: skip rank 0's single-GPU run of the full problem (item_shard_speedup / whole_iteration_speedup)")
     ap.add_argument("--no-alt-forms", action="store_true",
                     help="skip the extra (untimed for `value`) runs with the other draw_fstar forms")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step -- theta, beta, f* and f, "
+                         "float64 -- as DIR/<name>.npy (an array above %d values is written as a fixed, seeded sample of them), "
+                         "to compare two builds output for output" % DUMP_MAX_VALUES)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--single-device", action="store_true",
@@ -126,6 +153,8 @@ def main():
                          "still get that, four do not (the hang guard fires and the run fails loudly), so with more than two "
                          "ranks the rehearsal factors with the launch-per-step panel (GPIRT_PANEL=2)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -226,6 +255,8 @@ def main():
     ss.init()
     ss.engine.check()
     dt, prof = timed_run(ss)
+    # taken before anything else runs on the sampler (the lowrank check below draws f* again)
+    dumped = snapshot_outputs(ss) if args.dump_outputs else None
 
     # ---- self-certification of the opt-in low-rank form, in this run, on the state the timed steps ended in: the same
     # draw_fstar (same theta, f, L, mu_star, same RNG keys) with every one of the 1001 grid columns solved
@@ -270,6 +301,7 @@ def main():
             form = "fused"
             ss = chk
             dt, prof = timed_run(ss)
+            dumped = snapshot_outputs(ss) if args.dump_outputs else None
         else:
             del chk, c
 
@@ -575,6 +607,14 @@ def main():
             except Exception as e:      # the baseline is a reported extra; never lose the GPU line
                 out["cpu_baseline"] = {"value": None, "unit": "iterations/s", "cores": 1, "kind": "port",
                                        "sample": f"failed: {e!r}"}
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, (a, _) in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            out["dump_outputs"] = {"dir": args.dump_outputs, "form": form, "dtype": "float64",
+                                   "arrays": {name: meta for name, (_, meta) in dumped.items()},
+                                   "sample": f"sampled_values set: values at positions numpy.random.default_rng({DUMP_SAMPLE_SEED})"
+                                             ".choice(size, sampled_values, replace=False), sorted, of the column-major array"}
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
