@@ -62,6 +62,7 @@ int ensure_work(gpirt_handle_t h, size_t bytes)
     hipError_t e = hipMalloc(&h->d_work, bytes);
     if (e != hipSuccess) { set_error("hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return GPIRT_E_ALLOC; }
     h->work_bytes = bytes;
+    GP_HIP(poison_fresh(h, h->d_work, bytes, h->stream));
     return 0;
 }
 
@@ -161,8 +162,9 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 102; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 103; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
+                                            // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -431,6 +433,18 @@ int gpirt_debug_rs_mispredict(gpirt_handle_t h, int every)
     return 0;
 }
 
+// Tests only: every floating buffer a sampler on this handle allocates from now on, and every floating workspace the handle
+// (or its side handle) grows, starts as 0xFF bytes -- a quiet NaN in fp64 and fp32 (poison_fresh, common.h) -- so that a read
+// of memory nothing wrote changes the numbers or raises a named error instead of depending on what the allocator hands out.
+// Integer, flag, ticket and counter buffers are never poisoned.
+int gpirt_debug_poison_allocs(gpirt_handle_t h, int on)
+{
+    GP_ARG(h != nullptr && on >= 0);
+    h->poison_allocs = on ? 1 : 0;
+    if (h->aux) h->aux->poison_allocs = h->poison_allocs;
+    return 0;
+}
+
 // Debug: pass number `pass` of every replayed draw_f on this handle leaves in-kernel time stamps in the sampler's "rs_trace"
 // array (128 64-bit words, 100 MHz wall clock: tools/rs_trace.py); pass < 0 switches it off.
 int gpirt_debug_rs_trace(gpirt_handle_t h, int pass)
@@ -596,13 +610,19 @@ int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double*
                  const double* d_mu, int64_t n, int64_t m, uint64_t seed, uint32_t iter, int* d_k_out)
 {
     GP_ARG(h && d_f && d_y && d_L && d_mu && n >= 0 && m >= 0 && ldl >= n);
-    // workspace: Z (n x m) | NU (n x m) | err
+    // workspace: Z (n x m) | NU (n x m) | err, bad y
     const size_t nm = (size_t)n * (size_t)m;
     GP_TRY(ensure_work(h, (2 * nm + 8) * sizeof(double)));
     double* Z = h->d_work;
     double* NU = Z + nm;
     int* err = reinterpret_cast<int*>(NU + nm);
-    GP_HIP(hipMemsetAsync(err, 0, sizeof(int), h->stream));
+    GP_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), h->stream));
+    // the slice kernels take y as +1, -1 or NaN (a missing response; rng_ess.hip folds y into f, nu and mu for n <= 16384):
+    // anything else is refused before f is touched
+    GP_TRY(launch_check_y(h->stream, d_y, (int64_t)nm, err + 1));
+    GP_HIP(hipMemcpyAsync(h->h_info, err + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GP_HIP(hipStreamSynchronize(h->stream));
+    if (*h->h_info != 0) { set_error("draw_f: y must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
     GP_TRY(launch_item_uniforms(h->stream, seed, iter, GPIRT_ST_F_Z, 0, m, n, Z, true));
     GP_TRY(launch_gemm(h, h->stream, false, false, TRI_A_LOWER, n, m, n, 1.0, d_L, ldl, Z, n, 0.0, NU, n));
     EssArgs a{};

@@ -136,6 +136,7 @@ struct gpirt_handle_s {
     int          rs_trace_pass = -1;      // debug (gpirt_debug_rs_trace): the pass of every replayed draw_f whose kernels stamp their phases
     int          rs_mispredict = 0;       // debug (gpirt_debug_rs_mispredict): the replay's predictor is off by one at every n-th item
     int          rs_cand_limit = 0;       // debug (gpirt_debug_rs_cand_limit): candidates the replay's draw_f may use (0: all)
+    int          poison_allocs = 0;       // debug (gpirt_debug_poison_allocs): floating buffers allocated from now on start as NaN
     long long    trip_guard_at = -1;      // debug (gpirt_debug_trip_guard): the factorisation with this count raises the
                                           //   guard word and poisons its result behind itself, as an expiry would leave it
     bool         panel_attr_set = false;  // dynamic-LDS attribute of panel_ll_kernel set on this device
@@ -157,6 +158,14 @@ struct gpirt_handle_s {
 namespace gpirt {
 
 int  ensure_work(gpirt_handle_t h, size_t bytes);   // grows h->d_work (syncs when it reallocates)
+
+// gpirt_debug_poison_allocs: a floating buffer allocated while the flag is on is filled with 0xFF bytes (a quiet NaN in fp64
+// and fp32) on the stream that first uses it, so that a read of memory nothing wrote shows as a wrong number or a named error.
+// Integer, flag, ticket and counter buffers are never poisoned: kernels spin or take tickets on them.
+inline hipError_t poison_fresh(gpirt_handle_t h, void* p, size_t bytes, hipStream_t stream)
+{
+    return h->poison_allocs ? hipMemsetAsync(p, 0xFF, bytes, stream) : hipSuccess;
+}
 
 // ---------------------------------------------------------------- device math --------------
 typedef double d4 __attribute__((ext_vector_type(4)));

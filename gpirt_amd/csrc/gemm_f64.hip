@@ -829,6 +829,7 @@ int launch_gemm(gpirt_handle_t h, hipStream_t stream, bool ta, bool tb, int tri,
                 h->d_splitk = nullptr; h->splitk_bytes = 0;
                 GP_HIP(hipMalloc(&h->d_splitk, need));
                 h->splitk_bytes = need;
+                GP_HIP(poison_fresh(h, h->d_splitk, need, stream));
             }
             GemmParams q = p;
             q.C = h->d_splitk; q.ldc = M; q.sC = M * N; q.beta = 0.0; q.ksplit = -S;
@@ -854,6 +855,7 @@ int launch_gemm(gpirt_handle_t h, hipStream_t stream, bool ta, bool tb, int tri,
                 h->d_splitk = nullptr; h->splitk_bytes = 0;
                 GP_HIP(hipMalloc(&h->d_splitk, need));
                 h->splitk_bytes = need;
+                GP_HIP(poison_fresh(h, h->d_splitk, need, stream));
             }
             return launch_gemm_splitk(stream, ta, tb, M, N, K, alpha, A, lda, B, ldb, h->d_splitk, M, M * N, split,
                                       C, ldc, beta);

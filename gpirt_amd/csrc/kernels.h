@@ -276,5 +276,7 @@ int create_side_handle(gpirt_handle_t* out, int device);
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);
 int launch_axpy_irf(hipStream_t stream, double* acc, const double* fstar, int64_t count);
 int launch_advance_pos(hipStream_t stream, uint64_t* pos, uint64_t delta);
+// *bad = 1 if any of the `total` responses is not +1, -1 or NaN (bad is not cleared here)
+int launch_check_y(hipStream_t stream, const double* y, int64_t total, int* bad);
 
 }  // namespace gpirt

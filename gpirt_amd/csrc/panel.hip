@@ -586,6 +586,7 @@ int panel_workspaces(gpirt_handle_t h, hipStream_t stream, int64_t n)
         const int64_t blocks = need < 160 ? 160 : need;
         GP_HIP(hipMalloc(&h->d_winv, (size_t)blocks * 1024 * sizeof(double)));
         h->winv_blocks = blocks;
+        GP_HIP(poison_fresh(h, h->d_winv, (size_t)blocks * 1024 * sizeof(double), stream));
     }
     if (!h->panel_attr_set) {
         GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(panel_ll_kernel),

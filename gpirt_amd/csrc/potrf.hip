@@ -372,6 +372,7 @@ int launch_potrf_lower(gpirt_handle_t h, hipStream_t stream, double* A, int64_t 
                         const size_t want = need + need / 4;
                         GP_HIP(hipMalloc(&h->d_defer_ws, want));
                         h->defer_ws_bytes = want;
+                        GP_HIP(poison_fresh(h, h->d_defer_ws, want, stream));
                     }
                     ProfPair pp;
                     GP_TRY(prof_begin(h, stream, pp));

@@ -759,8 +759,10 @@ __global__ __launch_bounds__(320) void rs3_slice_kernel(Rs3Args a)
 // registers, so the (2 + k) likelihood passes of a column touch memory once; arithmetic is identical
 // to ess_kernel (same per-element expression, same reduction tree).
 // FOLD (n up to 16384: 16 entries per lane of 1024, four wavefronts per SIMD at 128 registers): y is +-1 or NaN, so y ((f c + nu s) + mu) = ((y f) c + (y nu) s) + (y mu)
-// bit for bit (a sign change is exact and rounding is symmetric) -- the lane keeps THREE arrays, y f, y nu, y mu (NaN in
-// y mu = a missing response), 96 registers instead of 128, and reads f and nu once more at the end to write f'.
+// bit for bit (a sign change is exact and rounding is symmetric; gpirt_draw_f and gpirt_sampler_create refuse any other y) --
+// the lane keeps THREE arrays, y f, y nu, y mu, 96 registers instead of 128, a bit mask of its observed rows (a NaN in mu or f
+// at an observed row must reach the sums and fail the item, as in the other kernels), and reads f and nu once more at the end
+// to write f'.
 template <int EPT, int NTH, bool FAST, bool FOLD = false>
 __global__ __launch_bounds__(NTH) void ess_kernel_reg(EssArgs a)
 {
@@ -785,6 +787,8 @@ __global__ __launch_bounds__(NTH) void ess_kernel_reg(EssArgs a)
     const double* mj = a.mu + j * n;
     const uint32_t item = a.item0 + (uint32_t)j;
     double F[EPT], V[EPT], M[EPT], Y[EPT];          // (FOLD: Y stays unused and costs no register)
+    static_assert(!FOLD || EPT <= 32, "FOLD keeps one bit per entry");
+    uint32_t live = 0;                              // FOLD: bit e = entry e is an observed row
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int64_t i = threadIdx.x + NTH * e;
@@ -794,14 +798,14 @@ __global__ __launch_bounds__(NTH) void ess_kernel_reg(EssArgs a)
         V[e] = in ? nj[i] : 0.0;
         M[e] = in ? mj[i] : 0.0;
         Y[e] = FOLD ? 0.0 : yy;
-        if (FOLD) { F[e] *= yy; V[e] *= yy; M[e] *= yy; }
+        if (FOLD) { F[e] *= yy; V[e] *= yy; M[e] *= yy; if (yy == yy) live |= 1u << e; }
     }
     // the argument of one term, and whether the row counts.  (Macros, not lambdas: a lambda that captures the arrays by
     // reference put them into scratch memory -- 164 registers + 432 bytes of scratch per lane instead of 237 registers, and the
     // kernel ran 330-450 instead of 140-205 us at 8192 x 1024.)
 #define ESS_ARG0(e) (FOLD ? F[e] + M[e] : Y[e] * (F[e] + M[e]))
 #define ESS_ARGP(e, c_, s_) (FOLD ? (F[e] * (c_) + V[e] * (s_)) + M[e] : Y[e] * ((F[e] * (c_) + V[e] * (s_)) + M[e]))
-#define ESS_LIVE(e) (FOLD ? M[e] == M[e] : Y[e] == Y[e])
+#define ESS_LIVE(e) (FOLD ? ((live >> (e)) & 1u) != 0 : Y[e] == Y[e])
     uint32_t uidx = 0;
     double acc = 0.0;
     // ll(f) of the current state, the other half of the slice level (:28-29) -- in full precision when it is needed: with the
@@ -903,6 +907,15 @@ __global__ __launch_bounds__(NTH) void ess_kernel_reg(EssArgs a)
 #undef ESS_LIVE
 
 __global__ void advance_pos_kernel(uint64_t* pos, uint64_t delta) { *pos += delta; }
+
+// *bad = 1 if any response is not +1, -1 or NaN
+__global__ void check_y_kernel(const double* __restrict__ y, int64_t total, int* bad)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = y[i];
+        if (!(v == 1.0 || v == -1.0 || v != v)) *bad = 1;
+    }
+}
 
 }  // namespace
 
@@ -1037,6 +1050,16 @@ int launch_ll_term_probe(hipStream_t stream, const double* a, int64_t n, double*
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(ll_term_probe_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a, n, out, fast);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_check_y(hipStream_t stream, const double* y, int64_t total, int* bad)
+{
+    if (total <= 0) return 0;
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(check_y_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, y, total, bad);
     GP_HIP(hipGetLastError());
     return 0;
 }

@@ -36,8 +36,10 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 
 // L -> single-precision tiles in the order the predictor's products read them: tile (row group rg of 32 rows, oct ko of 8
 // columns) = 1 KiB, lane l = (row rg 32 + (l & 31), columns 8 ko + 4 (l >> 5) .. + 3) as one float4: a wave's step is one
-// contiguous kilobyte, its steps follow each other in memory.  Rows and columns past the matrix are zeros; the strict upper
-// triangle of L holds zeros (gpirt_sampler_create).  Only the tiles a product reads are written.
+// contiguous kilobyte, its steps follow each other in memory.  Rows and columns past the matrix are written as zeros; the strict
+// upper triangle of L holds zeros (gpirt_sampler_create).  Octs wholly right of the row group's last row are never written:
+// the dense products stop at the diagonal, but the structured pass (rs3p_products_lr_kernel) reads all the octs of the
+// diagonal part, so they hold the zeros Lt32 is cleared to at creation.
 // diag_only: just the octs of the 512-column part that holds the row group's diagonal (all the structured pass reads, rs_lr.hip)
 __global__ __launch_bounds__(256) void rs32_tile_kernel(const double* __restrict__ L, int64_t n, int64_t ldl, int64_t nk8, float* __restrict__ Lt, int diag_only)
 {

@@ -17,6 +17,7 @@
 
 #include <stdlib.h>
 #include <new>
+#include <type_traits>
 #include <string>
 #include <vector>
 
@@ -142,8 +143,10 @@ struct gpirt_sampler_s {
 
 namespace {
 
+// numbers = false: a double-typed buffer that holds integer words (the fixed-point indicators and counters of theta_fixed.hip),
+// never poisoned (poison_fresh)
 template <typename T>
-int dalloc(gpirt_sampler_s* s, T** p, size_t count)
+int dalloc(gpirt_sampler_s* s, T** p, size_t count, bool numbers = true)
 {
     void* q = nullptr;
     const size_t bytes = (count ? count : 1) * sizeof(T);
@@ -154,6 +157,12 @@ int dalloc(gpirt_sampler_s* s, T** p, size_t count)
     }
     s->allocs.push_back(q);
     *p = reinterpret_cast<T*>(q);
+    if (std::is_same<T, double>::value || std::is_same<T, float>::value) {
+        if (numbers && poison_fresh(s->h, q, bytes, s->h->stream) != hipSuccess) {
+            set_error("hipMemsetAsync(%zu bytes) failed", bytes);
+            return GPIRT_E_HIP;
+        }
+    }
     return 0;
 }
 
@@ -453,6 +462,7 @@ int do_draw_f(gpirt_sampler_s* s)
     // the normals draw_f can reach: m items of 2n + 2 uniforms + their rejections (the window's own slack, stream_window)
     GP_TRY(launch_rs3_begin(st, a, (uint64_t)m * (2ull * (uint64_t)n + 2ull) + 512ull * (uint64_t)m + 4096ull));
     int64_t pass = 0, done = 0;
+    int64_t one_phase = 0;                      // passes of the one-phase replay: the draw's progress bound counts these alone
     bool topped = false;
     // Predict + verify (rs_predict.hip; GPIRT_RS_PREDICT=2: every pass in fp64, the one-phase replay).  The predictor's
     // passes leave predicted starts; phase B computes every item at its predicted start exactly and commits, in order, what
@@ -475,7 +485,10 @@ int do_draw_f(gpirt_sampler_s* s)
     while (done < m) {
         const int64_t left = m - done;
         int64_t count = (left + RS3_SLOTS - 1) / RS3_SLOTS + left / 40 + 2;
-        if (pass > 4 * m + 64) { set_error("R-stream replay: draw_f made no progress"); return GPIRT_E_NUMERIC; }   // (a pass resolves >= 1 item)
+        // (a one-phase pass resolves >= 1 item.  A predicted round enqueues spare passes -- ~0.375 per item left + 4 -- and may
+        // commit a single item behind a misprediction, so its passes do not count: a round that commits nothing hands over to
+        // the one-phase replay below, hence at most m predicted rounds)
+        if (one_phase > 4 * m + 64) { set_error("R-stream replay: draw_f made no progress"); return GPIRT_E_NUMERIC; }
         if (predict) {
             // (a slice loop that rejects 16 points in a row costs a pass of its own.)  How many passes a draw needs is a property
             // of the chain's state and moves slowly: the predictor counts its real passes (rs_ctl[3]) and the next draw enqueues
@@ -523,7 +536,7 @@ int do_draw_f(gpirt_sampler_s* s)
             GP_TRY(launch_rs_commit(st, v, s->anchor, s->pos, s->rs_ctl, s->flags, s->f, s->ess_k));
         } else {
         if (!tiles64) { GP_TRY(launch_rs_tiles(st, s->L, n, s->ldl, s->Lt)); tiles64 = true; }
-        for (int64_t q = 0; q < count; ++q, ++pass) {
+        for (int64_t q = 0; q < count; ++q, ++pass, ++one_phase) {
             s->rs_tag += 1ull << 20;
             a.tag = s->rs_tag;
             a.trace = (h->rs_trace_pass >= 0 && pass == h->rs_trace_pass) ? s->rs_trace : nullptr;
@@ -919,6 +932,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
 {
     GP_ARG(out && h && h_y && h_theta0 && h_pm && h_ps && h_step && n > 0 && m > 0);
     *out = nullptr;
+    for (int64_t i = 0; i < n * m; ++i) {          // (the slice kernels fold y into f, nu and mu: rng_ess.hip)
+        const double v = h_y[i];
+        if (!(v == 1.0 || v == -1.0 || v != v)) { set_error("y must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
+    }
     gpirt_sampler_s* s = new (std::nothrow) gpirt_sampler_s();
     if (!s) { set_error("out of host memory"); return GPIRT_E_ALLOC; }
     s->h = h; s->n = n; s->m = m; s->N = GPIRT_NGRID;
@@ -939,7 +956,9 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
 #define GP_A(p, cnt) do { rc = dalloc(s, &(p), (size_t)(cnt)); if (rc) { gpirt_sampler_destroy(s); return rc; } } while (0)
     GP_A(s->y, n * m);       GP_A(s->Ypm, n * 2 * m);  GP_A(s->theta, n);       GP_A(s->theta_new, n);
     s->tfd = tf_dims(n, m, N);
-    GP_A(s->tf_y8, tf_y8_bytes(s->tfd) / 8 + 2); GP_A(s->tf_gq, tf_gq_bytes(s->tfd) / 8 + 2); GP_A(s->tf_aux, tf_aux_bytes(s->tfd) / 8 + 2);
+#define GP_AI(p, cnt) do { rc = dalloc(s, &(p), (size_t)(cnt), false); if (rc) { gpirt_sampler_destroy(s); return rc; } } while (0)
+    GP_AI(s->tf_y8, tf_y8_bytes(s->tfd) / 8 + 2); GP_AI(s->tf_gq, tf_gq_bytes(s->tfd) / 8 + 2); GP_AI(s->tf_aux, tf_aux_bytes(s->tfd) / 8 + 2);
+#undef GP_AI
     GP_A(s->f, n * m);       GP_A(s->Z, n * m);        GP_A(s->NU, n * (m > 1 + TRMV_SPLIT ? m : 1 + TRMV_SPLIT));   GP_A(s->beta, 2 * m);   // (NU: >= 1 + TRMV_SPLIT columns, launch_trmv_lower's parts)
     s->kr = s->opt.kstar_rank;
     if (s->kr != 0 && (!s->opt.fstar_fused || s->kr < 16 || s->kr > 128 || (s->kr % 16) != 0)) {
@@ -1006,6 +1025,9 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
             hipMemsetAsync(s->anchor, 0, 4 * sizeof(uint64_t), st);
             const size_t partsP = (size_t)((n + RS3P_KC - 1) / RS3P_KC);
             GP_A(s->Lt32, rs32_tile_floats(n));   GP_A(s->rs_part32, partsP * RS3_CAND * (size_t)n);
+            // (the octs right of a row group's diagonal are never written by rs32_tile_kernel, but the structured pass reads
+            // its diagonal part whole: they must hold zeros from the start)
+            hipMemsetAsync(s->Lt32, 0, sizeof(float) * rs32_tile_floats(n), st);
             GP_A(s->anchorP, 8);     GP_A(s->rs_ctl, 8);     GP_A(s->rs_posP, 2);
             GP_A(s->rs_dec_part, (size_t)RS3_CAND * 8 * 17 + 8);  GP_A(s->rs_dec_rec, (size_t)RS3_CAND * 20 + 8);  GP_A(s->rs_dec_ticket, 32 * 9);      // the top word + one per row part, 128 bytes apart
             hipMemsetAsync(s->rs_dec_ticket, 0, 32 * 9 * sizeof(unsigned), st);
@@ -1131,6 +1153,7 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
             h->aux->cfg = h->cfg;
         }
         s->haux = h->aux;
+        s->haux->poison_allocs = h->poison_allocs;       // (gpirt_debug_poison_allocs: the side handle's workspaces too)
         if (
             hipEventCreateWithFlags(&s->ev_trmm, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s->ev_prep, hipEventDisableTiming) != hipSuccess ||
@@ -1301,6 +1324,8 @@ int gpirt_sampler_set_theta_block(gpirt_sampler_t s, const double* y_block, int6
     GP_B(s->logpost_blk, N * n_block + 2);       GP_B(s->fstar_full, N * m_total + 2);
     GP_B(s->theta_stage, s->n + 1);              GP_B(yb, n_block * m_total + 1);
     s->tfd_blk = tf_dims(n_block, m_total, N);
+#undef GP_B
+#define GP_B(p, cnt) do { rc = dalloc(s, &(p), (size_t)(cnt), false); if (rc) return rc; } while (0)
     GP_B(s->tf_y8_blk, tf_y8_bytes(s->tfd_blk) / 8 + 2); GP_B(s->tf_gq_blk, tf_gq_bytes(s->tfd_blk) / 8 + 2);
     GP_B(s->tf_aux_blk, tf_aux_bytes(s->tfd_blk) / 8 + 2);
 #undef GP_B

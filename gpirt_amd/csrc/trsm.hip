@@ -350,6 +350,7 @@ int trsm_inverses_reserve(gpirt_handle_t h, hipStream_t stream, int64_t n, int64
             if (h->d_trsm_winv) GP_HIP(hipFree(h->d_trsm_winv));
             h->d_trsm_winv = nullptr; h->trsm_winv_bytes = 0;
             GP_HIP(hipMalloc(&h->d_trsm_winv, wbytes));
+            GP_HIP(poison_fresh(h, h->d_trsm_winv, wbytes, stream));
             GP_HIP(hipMemsetAsync(h->d_trsm_winv, 0, wbytes, stream));   // upper-right quarters stay zero for good
             GP_HIP(hipStreamSynchronize(stream));
             h->trsm_winv_bytes = wbytes;
@@ -359,6 +360,7 @@ int trsm_inverses_reserve(gpirt_handle_t h, hipStream_t stream, int64_t n, int64
             h->d_trsm_tmp = nullptr; h->trsm_tmp_bytes = 0;
             GP_HIP(hipMalloc(&h->d_trsm_tmp, tbytes));
             h->trsm_tmp_bytes = tbytes;
+            GP_HIP(poison_fresh(h, h->d_trsm_tmp, tbytes, stream));
         }
     }
     if (thin && npair >= 2) {
@@ -369,6 +371,7 @@ int trsm_inverses_reserve(gpirt_handle_t h, hipStream_t stream, int64_t n, int64
             h->d_trsm_wquad = nullptr; h->trsm_wquad_bytes = 0;
             GP_HIP(hipMalloc(&h->d_trsm_wquad, qbytes));
             h->trsm_wquad_bytes = qbytes;
+            GP_HIP(poison_fresh(h, h->d_trsm_wquad, qbytes, stream));
         }
     }
     return 0;
@@ -483,6 +486,7 @@ int launch_trsm_lower(gpirt_handle_t h, hipStream_t stream, const double* L, int
             h->d_trsm_tmp = nullptr; h->trsm_tmp_bytes = 0;
             GP_HIP(hipMalloc(&h->d_trsm_tmp, tb));
             h->trsm_tmp_bytes = tb;
+            GP_HIP(poison_fresh(h, h->d_trsm_tmp, tb, stream));
         }
     }
     const bool use_quads = winv && thin && h->trsm_quads > 0;

@@ -60,7 +60,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -95,6 +95,10 @@ int         gpirt_debug_rs_cand_limit(gpirt_handle_t h, int limit);
  * verifies all items exactly afterwards; every > 0 makes the predictor wrong on purpose at every
  * every-th item, so the verification's discard-and-resume path runs.  The draws must not change. */
 int         gpirt_debug_rs_mispredict(gpirt_handle_t h, int every);
+/* Tests only: on != 0 fills every floating buffer a sampler created on h allocates, and every floating workspace h or its side
+ * handle grows, with 0xFF bytes (a quiet NaN in fp64 and fp32) at allocation, so that a kernel reading memory nothing wrote
+ * shows in the results.  Integer, flag, ticket and counter buffers are never poisoned.  0 switches it off for later allocations. */
+int         gpirt_debug_poison_allocs(gpirt_handle_t h, int on);
 /* Debug: pass number `pass` (0-based; < 0: none) of every R-stream draw_f on this handle leaves the in-kernel time stamps of
  * its two kernels in the sampler's "rs_trace" array (gpirt_sampler_get, 128 64-bit words, 100 MHz): tools/rs_trace.py. */
 int         gpirt_debug_rs_trace(gpirt_handle_t h, int pass);
@@ -199,7 +203,8 @@ int gpirt_ll_bar(gpirt_handle_t h, const double* d_f, const double* d_y, const d
 
 /* draw_f(): src/draw-f.cpp:64-73 under GPIRT_RNG_ITEM: Z ~ N(0,1) from (seed, iter) sub-streams,
  * nu = L Z as one trmm, then one elliptical-slice update per column (ess(), :21-60).
- * In place on d_f (n x m).  d_k_out (m ints, may be NULL) receives the rejection counts. */
+ * In place on d_f (n x m).  d_k_out (m ints, may be NULL) receives the rejection counts.  d_y holds +1, -1 or NaN (a missing
+ * response); any other value is refused with GPIRT_E_ARG before d_f is touched. */
 int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double* d_L, int64_t ldl,
                  const double* d_mu, int64_t n, int64_t m, uint64_t seed, uint32_t iter,
                  int* d_k_out);
@@ -295,7 +300,8 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0,
                double* h_beta_draws, double* h_f_draws, double* h_irfs);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
- * put a collective between stages).  State lives on the device. */
+ * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
+ * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
 int gpirt_sampler_create(gpirt_sampler_t* s, gpirt_handle_t h, const double* h_y, int64_t n,
                          int64_t m, const double* h_theta0, const double* h_prior_means,
                          const double* h_prior_sds, const double* h_step_sizes,

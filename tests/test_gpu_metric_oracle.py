@@ -12,6 +12,19 @@ all host cores (tests/_oracle_parallel.py), stage by stage from the device's own
   draw_beta   src/draw-beta.cpp:3-41    1e-12
   K + chol    src/gpirtMCMC.cpp:76-78   max|L - L_oracle| <= 1e-9 (blocked host potrf; measured ~5e-13)
 The north star asks for 1e-8 relative on posterior means; every bound here is ten times tighter.
+
+The same at the default contract, R's single stream (the R-stream replay: predict-and-verify draw_f with the rank-64
+structured predictor, about 300 predictor passes per draw), one iteration driven by step() and every stage's reference started
+from the device's state and from the oracle's generator where the stage before left it (tests/_rstream_oracle.py):
+
+  draw_f      sequential oracle             rejection counts EXACT, f <= 1e-9 * max(1, max|f|)
+  draw_fstar  s, mean on all cores; the     s abs 1e-9; f* <= 1e-9 * max(1, max|f*|)
+              noise in R's order (:23-29)
+  draw_theta  respondent blocks on copies   EXACT
+              of the generator (:27)
+  draw_beta   sequential oracle             1e-12; the generator handed back at the oracle's position
+Each stage's draws start where the oracle's generator stands after the stage before: a stage that consumed a different
+number of uniforms than the reference fails the next one, the last one fails the position check.
 """
 import time
 
@@ -117,3 +130,70 @@ def test_metric_size_iteration_stage_by_stage_against_the_oracle(handle, oracle,
               "s %.2e; mean %.2e, f* %.2e as written, %.2e fused, %.2e lowrank (max|f*| %.1f); theta exact; "
               "beta %.1e; L %.2e" % (cores, time.perf_counter() - t0, rep["ess_mean_k"], rep["f"], rep["s"], rep["mean"],
                                      rep["fstar"], rep["fstar_fused"], rep["fstar_lowrank"], scale, rep["beta"], rep["L"]))
+
+
+def test_metric_size_r_stream_iteration_against_the_oracle(handle, oracle, capsys):
+    from gpirt_amd.ops import RStream
+    from gpirt_amd.sampler import Sampler
+    from gpirt_amd.synthetic import make_responses
+    from tests import _oracle_parallel as P
+    from tests import _rstream_oracle as R
+    n, m, seed = 8192, 1024, 20240
+    y, th0 = make_responses(n, m, seed=20240)
+    rs = RStream(seed)
+    s = Sampler(handle, y, th0, rng="reference", rstream=rs, theta_stabilise=True)
+    s.init()
+    for _ in range(2):
+        s.step()
+    s.check()
+    stats0 = s.get("rs_stats")
+    assert stats0[2] == 0, stats0                         # (the predictor never stalled into the one-phase replay)
+    it = s.iteration + 1
+    state0 = rs.state()
+    theta0, f0, beta0, mu0, mu_star0 = (s.get(k) for k in ("theta", "f", "beta", "mu", "mu_star"))
+    kk = (theta0 + 5.0) / 0.01
+    assert np.abs(kk - np.rint(kk)).max() < 1e-9          # grid-valued: the structured predictor's steady state
+    L0 = np.tril(s.get("L"))
+    s.step(); s.check()
+    f1, k_dev, fs1, s_dev, theta1, beta1 = (s.get(k) for k in ("f", "ess_k", "fstar", "s", "theta", "beta"))
+    stats1 = s.get("rs_stats")
+    state1 = rs.state()
+    s.close()
+    assert stats1[2] == 0, stats1
+    cores = P.host_cores()
+    t0 = time.perf_counter()
+    r = R.rstream_at(state0)
+    rep = {"mispredictions": int(stats1[1] - stats0[1]), "passes": int(stats1[3] - stats0[3])}
+
+    # ---- draw_f: the sequential oracle on the device's f, L, mu -------------------------------------------------
+    f_ref, k_ref = oracle.draw_f(r, f0, y, L0, mu0, it=it)
+    rep["ess_mismatch"] = int(np.count_nonzero(k_dev != k_ref))
+    rep["ess_mean_k"] = float(k_ref.mean())
+    rep["f"] = float(np.abs(f1 - f_ref).max())
+    assert rep["ess_mismatch"] == 0, rep
+    assert rep["f"] <= 1e-9 * max(1.0, float(np.abs(f_ref).max())), rep
+
+    # ---- draw_fstar on the device's f ----------------------------------------------------------------------------
+    fs_ref, s_ref, _ = R.draw_fstar(r, it, f1, theta0, L0, mu_star0, cores)
+    scale = max(1.0, float(np.abs(fs_ref).max()))
+    rep["s"] = float(np.abs(s_dev - s_ref).max())
+    rep["fstar"] = float(np.abs(fs1 - fs_ref).max())
+    assert rep["s"] <= 1e-9, rep
+    assert rep["fstar"] <= 1e-9 * scale, rep
+
+    # ---- draw_theta on the device's f* ---------------------------------------------------------------------------
+    th_ref, deg = R.draw_theta(r, it, y, fs1, True, cores)
+    rep["theta_mismatch"] = int(np.count_nonzero(theta1 != th_ref))
+    assert deg == 0 and rep["theta_mismatch"] == 0, rep
+
+    # ---- draw_beta on the device's theta and f -------------------------------------------------------------------
+    pm, ps, st = np.zeros((2, m)), np.full((2, m), 3.0), np.full((2, m), 0.1)
+    b_ref = oracle.draw_beta(r, beta0, theta1, y, f1, pm, ps, st, it=it)
+    rep["beta"] = float(np.abs(beta1 - b_ref).max())
+    assert rep["beta"] <= 1e-12, rep
+    assert R.same_position(r, state1), "the generator after the iteration is not where the oracle's stands"
+    with capsys.disabled():
+        print("\n[M 8192x1024 R stream vs oracle, %.0f s on %d cores] ESS counts exact (mean k %.2f); max|df| %.2e; s %.2e; "
+              "f* %.2e (max|f*| %.1f); theta exact; beta %.1e; generator position exact; %d mispredictions, %d predictor "
+              "passes" % (time.perf_counter() - t0, cores, rep["ess_mean_k"], rep["f"], rep["s"], rep["fstar"], scale,
+                          rep["beta"], rep["mispredictions"], rep["passes"]))

@@ -314,6 +314,94 @@ def test_draw_f_item_rng_beyond_8192_rows(handle, oracle, n, m):
     assert np.abs(to_host(out) - ref).max() <= 1e-9
 
 
+def _block_factor(theta, block=512):
+    """A valid Cholesky factor without a LAPACK factorisation at 16k: L of the block-diagonal SE kernel (+ jitter), blocks of
+    512 rows (the last one ragged)."""
+    n = len(theta)
+    L = np.zeros((n, n), order="F")
+    for b in range(0, n, block):
+        t = theta[b:b + block]
+        K = np.exp(-0.5 * (t[:, None] - t[None, :]) ** 2)
+        K[np.diag_indices(len(t))] += 1e-3
+        L[b:b + block, b:b + block] = np.linalg.cholesky(K)
+    return L
+
+
+@pytest.mark.parametrize("n", [2048, 2049, 8192, 8193, 16384, 16385])
+def test_draw_f_item_rng_at_the_size_class_edges(handle, oracle, n):
+    """The item-keyed slice kernel comes in four size classes (rng_ess.hip, launch_ess): n <= 2048 and <= 8192 keep f, nu,
+    mu and y in registers, n <= 16384 keeps y f, y nu and y mu (FOLD), beyond that the columns stay in memory.  At both sides
+    of each edge, with missing responses in every column and a column with a single observed row: counts exact and f to 1e-9
+    against the oracle, screened (the default) and with the likelihood as written (GPIRT_LL_EXACT=1: other instances).  Then
+    the failure edges, in every class: a NaN in mu at a row with a response is GPIRT_E_NUMERIC (FOLD once skipped such a row
+    as if the response were missing), and a y outside {+1, -1, NaN} is refused with GPIRT_E_ARG before anything runs."""
+    from gpirt_amd import _lib
+    from gpirt_amd.ops import to_device, to_host
+    m, seed, it = 3, 91, 3
+    rng = np.random.default_rng(n)
+    theta = _theta_grid(n, n + 1)
+    y = np.where(rng.random((n, m)) < 0.5, 1.0, -1.0)
+    y[rng.random((n, m)) < 0.07] = np.nan                  # missing responses in every column
+    y[:, 1] = np.nan
+    y[n // 3, 1] = 1.0                                     # a column with one observed row
+    y = np.asfortranarray(y)
+    f = np.asfortranarray(rng.standard_normal((n, m)))
+    beta = np.vstack([rng.uniform(-1, 1, m), rng.uniform(0.5, 2, m)])
+    mu = np.asfortranarray(beta[0][None, :] + theta[:, None] * beta[1][None, :])
+    L = _block_factor(theta)
+    ref, kref = oracle.draw_f(oracle.ItemStream(seed), f, y, L, mu, it=it)
+    Ld, yd, mud = to_device(L), to_device(y), to_device(mu)
+    for exact in (0, 1):
+        with handle.config("GPIRT_LL_EXACT", exact):
+            out, k = handle.draw_f(to_device(f), yd, Ld, mud, seed, it)
+        assert np.array_equal(k.cpu().numpy(), kref), (n, exact, k.cpu().numpy(), kref)
+        assert np.abs(to_host(out) - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max()), (n, exact)
+    # a NaN in mu where the response is observed: the slice loop cannot decide, a named error (never a skipped row)
+    i = int(np.flatnonzero(~np.isnan(y[:, 2]))[-1])
+    mu_bad = mu.copy()
+    mu_bad[i, 2] = np.nan
+    for exact in (0, 1):
+        with handle.config("GPIRT_LL_EXACT", exact):
+            with pytest.raises(_lib.GpirtError) as e:
+                handle.draw_f(to_device(f), yd, Ld, to_device(mu_bad), seed, it)
+        assert e.value.code == _lib.E_NUMERIC, (n, exact, str(e.value))
+    # a NaN in mu where the response is missing is what a missing response means: no error, same draws as above
+    j = int(np.flatnonzero(np.isnan(y[:, 0]))[0])
+    mu_miss = mu.copy()
+    mu_miss[j, 0] = np.nan
+    out, k = handle.draw_f(to_device(f), yd, Ld, to_device(mu_miss), seed, it)
+    assert np.array_equal(k.cpu().numpy(), kref)
+    assert np.abs(to_host(out) - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
+    # y must be +1, -1 or NaN: refused before f is touched
+    for v in (0.5, 2.0, 0.0, np.inf):
+        y_bad = y.copy()
+        y_bad[i, 2] = v
+        fd = to_device(f)
+        with pytest.raises(_lib.GpirtError) as e:
+            handle.draw_f(fd, to_device(y_bad), Ld, mud, seed, it)
+        assert e.value.code == _lib.E_ARG, (n, v, str(e.value))
+        assert np.array_equal(to_host(fd), f), (n, v)
+
+
+@pytest.mark.parametrize("rng_kind", ["item", "reference"])
+def test_sampler_refuses_responses_outside_plus_minus_one(handle, rng_kind):
+    """The slice kernels take y as +1, -1 or NaN (a missing response; rng_ess.hip folds y into f, nu and mu): anything else
+    is refused at sampler creation with GPIRT_E_ARG, not sampled with a likelihood the reference never defines."""
+    from gpirt_amd import Sampler, _lib
+    from gpirt_amd.ops import RStream
+    from gpirt_amd.synthetic import make_responses
+    y, th0 = make_responses(100, 4, seed=2)
+    for v in (0.5, 2.0, 0.0, -np.inf):
+        y_bad = y.copy()
+        y_bad[17, 3] = v
+        kw = dict(rng="reference", rstream=RStream(3)) if rng_kind == "reference" else dict(rng="item", seed=3)
+        with pytest.raises(_lib.GpirtError) as e:
+            Sampler(handle, y_bad, th0, **kw)
+        assert e.value.code == _lib.E_ARG, (v, str(e.value))
+    s = Sampler(handle, y, th0, **(dict(rng="reference", rstream=RStream(3)) if rng_kind == "reference" else dict(rng="item", seed=3)))
+    s.close()
+
+
 @pytest.mark.parametrize("fused", [False, True])
 def test_draw_fstar_item_rng(handle, oracle, fused):
     from gpirt_amd.ops import to_device, to_host
