@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # GPIRT_HIP_LIBRARY: test hook -- another build of the same library (tests/test_gpu_fences.py loads the fenced variant)
 LIB_PATH = os.environ.get("GPIRT_HIP_LIBRARY") or os.path.join(HERE, "libgpirt_hip.so")
@@ -19,11 +21,37 @@ ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
+# posterior summaries (include/gpirt_hip.h GPIRT_SUM_*): part bits, and the order of the totals
+SUM_THETA_BETA, SUM_F, SUM_PRED, SUM_WAIC = 1, 2, 4, 8
+SUM_PARTS = {"theta_beta": SUM_THETA_BETA, "f": SUM_F, "pred": SUM_PRED, "waic": SUM_WAIC}
+SUM_TOTALS = ("lppd", "p_waic", "elpd_waic", "waic", "se_elpd_waic", "n_obs", "draws", "elpd_mean", "elpd_ss")
+
+
+def summary_parts(spec) -> int:
+    """GPIRT_SUM_* bits from an int, one part name or an iterable of them ("theta_beta", "f", "pred", "waic")."""
+    if isinstance(spec, (int, np.integer)) and not isinstance(spec, bool):
+        return int(spec)
+    if isinstance(spec, str):
+        spec = (spec,)
+    bits = 0
+    for name in spec:
+        if name not in SUM_PARTS:
+            raise ValueError(f"unknown summary part {name!r} (one of {sorted(SUM_PARTS)})")
+        bits |= SUM_PARTS[name]
+    return bits
+
 
 class GpirtError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"[gpirt {code}] {msg}")
         self.code = code
+
+
+class Summary(C.Structure):
+    """gpirt_summary (include/gpirt_hip.h): the parts wanted, a host pointer per output (NULL: not wanted), the totals."""
+    _fields_ = [("parts", C.c_int), ("reserved", C.c_int)] + [
+        (f"h_{k}", C.POINTER(C.c_double)) for k in ("p_yes", "lppd", "p_waic", "f_mean", "f_var", "theta_mean", "theta_var",
+                                                     "beta_mean", "beta_var")] + [("totals", C.c_double * len(SUM_TOTALS))]
 
 
 class Options(C.Structure):
@@ -106,6 +134,12 @@ SIGNATURES = {
     "gpirt_fast_options": (None, [C.POINTER(Options)]),
     "gpirt_mcmc": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _vp,
                            TICK_FN, _vp, _dp, _dp, _dp, _dp]),
+    "gpirt_mcmc_summary": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _vp,
+                                   TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary)]),
+    "gpirt_sampler_summary_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
+    "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),
     "gpirt_sampler_create": (_i32, [C.POINTER(_vp), _vp, _dp, _i64, _i64, _dp, _dp, _dp, _dp,
                                      C.POINTER(Options), _vp]),
     "gpirt_sampler_destroy": (_i32, [_vp]),

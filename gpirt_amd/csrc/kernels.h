@@ -271,6 +271,28 @@ int report_panel_guard(gpirt_handle_t h, const int* info_words, hipStream_t stre
 // api.hip
 int create_side_handle(gpirt_handle_t* out, int device);
 
+// summary.hip: posterior summaries accumulated one draw at a time (gpirt_sampler_summary_*, gpirt_mcmc_summary)
+struct SummaryState {
+    int parts = 0;                    // GPIRT_SUM_* (0: off)
+    int64_t n = 0, m = 0, draws = 0;
+    double *tb_mean = nullptr, *tb_m2 = nullptr;                          // theta (n) then beta (2 x m): Welford
+    double *lse = nullptr, *ll_mean = nullptr, *ll_m2 = nullptr;          // WAIC: log sum_s exp(ll_s), Welford of ll
+    double *p_sum = nullptr;                                              // PRED: sum_s P(y = 1)
+    double *f_mean = nullptr, *f_m2 = nullptr;                            // F: Welford of f
+    double *out = nullptr, *part = nullptr, *tot = nullptr;              // a finished array, block partials, the totals
+    std::vector<void*> allocs;
+};
+int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts);     // zeroed accumulators
+void summary_free(SummaryState* s);
+// adds one draw; f, mu, y are n x m (16-byte aligned), theta n, beta 2 x m
+int launch_summary_accumulate(hipStream_t stream, SummaryState* s, const double* theta, const double* beta, const double* f,
+                              const double* mu, const double* y);
+// the finished array `name` (p_yes, lppd, p_waic, f_mean, f_var, theta_mean, theta_var, beta_mean, beta_var) into s->out
+int launch_summary_finish(hipStream_t stream, const SummaryState* s, const char* name, const double* y, double** d_out,
+                          int64_t* count);
+// the totals (GPIRT_SUM_T_*) into s->tot
+int launch_summary_totals(hipStream_t stream, const SummaryState* s, const double* y);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

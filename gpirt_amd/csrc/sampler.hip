@@ -139,6 +139,7 @@ struct gpirt_sampler_s {
     double stage_ms[ST_COUNT] = {};
     std::vector<void*> allocs;
     std::vector<double> host_tmp;
+    SummaryState sum;                 // posterior summaries (gpirt_sampler_summary_enable; parts == 0: off)
 };
 
 namespace {
@@ -1197,6 +1198,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     if (s->ev_zfill) hipEventDestroy(s->ev_zfill);
     if (s->ev_beta) hipEventDestroy(s->ev_beta);
     for (void* p : s->allocs) hipFree(p);
+    summary_free(&s->sum);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -1420,6 +1422,49 @@ int gpirt_sampler_accumulate_irf(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised);
     return launch_axpy_irf(s->h->stream, s->irf_sum, s->fstar, s->N * s->m);     // :103
+}
+
+// ---- posterior summaries (summary.hip) on the stage API ---------------------------------------------------------------
+int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts)
+{
+    GP_ARG(s && s->initialised);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a summary kernel still running on the old accumulators
+    summary_free(&s->sum);
+    if (parts == 0) return 0;
+    const int rc = summary_alloc(&s->sum, s->n, s->m, parts | GPIRT_SUM_THETA_BETA);
+    if (rc) summary_free(&s->sum);
+    return rc;
+}
+
+int gpirt_sampler_summary_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
+    GP_TRY(beta_sync(s));                     // draw_beta (beta, mu) may still be deferred to the sampler's own stream
+    return launch_summary_accumulate(s->h->stream, &s->sum, s->theta, s->beta, s->f, s->mu, s->y);
+}
+
+int gpirt_sampler_summary_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count)
+{
+    GP_ARG(s && name && h_out && count >= 0);
+    if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
+    double* d = nullptr; int64_t c = 0;
+    GP_TRY(launch_summary_finish(s->h->stream, &s->sum, name, s->y, &d, &c));
+    GP_ARG(count <= c);
+    GP_HIP(hipMemcpyAsync(h_out, d, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_summary_totals(gpirt_sampler_t s, double* h_totals)
+{
+    GP_ARG(s && h_totals);
+    if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
+    GP_TRY(launch_summary_totals(s->h->stream, &s->sum, s->y));
+    GP_HIP(hipMemcpyAsync(h_totals, s->sum.tot, sizeof(double) * GPIRT_SUM_NTOTALS, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
 }
 
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
@@ -1646,13 +1691,14 @@ long long gpirt_debug_take_mcmc_trip(void);
 static int g_last_mcmc_fallbacks = 0;
 int gpirt_debug_last_mcmc_fallbacks(void) { return g_last_mcmc_fallbacks; }
 
-int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int S_it, int B_it,
-               const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts,
-               gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
-               double* h_beta_draws, double* h_f_draws, double* h_irfs)
+// The loop of gpirt_mcmc and gpirt_mcmc_summary (arguments checked by the callers).  sm != NULL: the draws' pointers may be
+// NULL (not stored) and every sampling iteration's state is added to the summaries -- under the item RNG from its checkpoint
+// once that is verified (start_store), so that a rollback cannot count an iteration twice.
+static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int S_it, int B_it,
+                    const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts,
+                    gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
+                    double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* sm)
 {
-    GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && h_theta_draws && h_beta_draws && h_f_draws && h_irfs);
-    GP_ARG(n > 0 && m > 0 && S_it >= 0 && B_it >= 0);
     gpirt_options o;
     if (opts) o = *opts; else gpirt_default_options(&o);
     gpirt_handle_t h = nullptr;
@@ -1664,18 +1710,38 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
     const int64_t N = s->N;
     const int total = S_it + B_it;
     const bool replay = stream_mode(s);
+    const bool summarise = sm && sm->parts;
     std::vector<double> th((size_t)n);
     auto store_sync = [&](int slot) -> int {
         // theta_draws.row(slot), beta_draws.slice(slot), f_draws.slice(slot): :53-55, :99-101
-        GP_TRY(gpirt_sampler_get(s, "theta", th.data(), n));
-        for (int64_t i = 0; i < n; ++i) h_theta_draws[slot + i * (int64_t)(S_it + 1)] = th[(size_t)i];
-        GP_TRY(gpirt_sampler_get(s, "beta", h_beta_draws + (int64_t)slot * 2 * m, 2 * m));
-        GP_TRY(gpirt_sampler_get(s, "f", h_f_draws + (int64_t)slot * n * m, n * m));
+        if (h_theta_draws) {
+            GP_TRY(gpirt_sampler_get(s, "theta", th.data(), n));
+            for (int64_t i = 0; i < n; ++i) h_theta_draws[slot + i * (int64_t)(S_it + 1)] = th[(size_t)i];
+        }
+        if (h_beta_draws) GP_TRY(gpirt_sampler_get(s, "beta", h_beta_draws + (int64_t)slot * 2 * m, 2 * m));
+        if (h_f_draws) GP_TRY(gpirt_sampler_get(s, "f", h_f_draws + (int64_t)slot * n * m, n * m));
+        return 0;
+    };
+    // the summaries out of the sampler (before it is destroyed)
+    auto summary_out = [&]() -> int {
+        if (!sm) return 0;
+        for (int k = 0; k < GPIRT_SUM_NTOTALS; ++k) sm->totals[k] = (double)NAN;
+        sm->totals[GPIRT_SUM_T_DRAWS] = (double)s->sum.draws;
+        if (!summarise) return 0;
+        const struct { const char* name; double* p; int64_t c; } outs[] = {
+            { "p_yes", sm->h_p_yes, n * m }, { "lppd", sm->h_lppd, n * m }, { "p_waic", sm->h_p_waic, n * m },
+            { "f_mean", sm->h_f_mean, n * m }, { "f_var", sm->h_f_var, n * m }, { "theta_mean", sm->h_theta_mean, n },
+            { "theta_var", sm->h_theta_var, n }, { "beta_mean", sm->h_beta_mean, 2 * m }, { "beta_var", sm->h_beta_var, 2 * m },
+        };
+        for (const auto& e : outs)
+            if (e.p) GP_TRY(gpirt_sampler_summary_get(s, e.name, e.p, e.c));
+        if (sm->parts & GPIRT_SUM_WAIC) GP_TRY(gpirt_sampler_summary_totals(s, sm->totals));
         return 0;
     };
     rc = gpirt_sampler_init(s);
     if (!rc) rc = gpirt_sampler_check(s);
     if (!rc) rc = store_sync(0);
+    if (!rc && summarise) rc = gpirt_sampler_summary_enable(s, sm->parts);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -1688,9 +1754,11 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
             if (!rc && it >= B_it) {
                 rc = gpirt_sampler_accumulate_irf(s);                          // :103
                 if (!rc) rc = store_sync(it - B_it + 1);
+                if (!rc && summarise) rc = gpirt_sampler_summary_accumulate(s);   // consumes nothing of R's stream
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
+        if (!rc) rc = summary_out();
         g_last_mcmc_fallbacks = h->guard_fallbacks;
         gpirt_sampler_destroy(s);
         gpirt_destroy(h);
@@ -1711,7 +1779,10 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
     // on -- the same draws as an undisturbed run (counter-based RNG keyed by the iteration; L equal to rounding).  Only a
     // second expiry without progress ends the call.
     constexpr int NS = 3;
-    const size_t ck_doubles = (size_t)n + 2 * (size_t)m + 2 * (size_t)(n * m) + 3 * (size_t)(N * m);
+    // every part of a slot starts on a 16-byte boundary (the summaries' kernel reads f and mu of a slot two doubles a lane)
+    auto even = [](size_t c) { return (c + 1) & ~(size_t)1; };
+    const size_t off_beta = even((size_t)n), off_f = off_beta + even((size_t)(2 * m)), off_mu = off_f + even((size_t)(n * m));
+    const size_t ck_doubles = off_mu + even((size_t)(n * m)) + 3 * even((size_t)(N * m));
     double* ck[NS] = { nullptr, nullptr, nullptr };
     hipEvent_t ev_flags[NS] = {}, ev_copied[NS] = {};
     bool copy_pending[NS] = { false, false, false };
@@ -1745,7 +1816,7 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
         double* d = ck[q];
         for (const Part& pt : parts()) {
             if (hipMemcpyAsync(d, pt.p, pt.cnt * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail_hip("checkpoint");
-            d += pt.cnt;
+            d += even(pt.cnt);
         }
         if (hipMemcpyAsync(h_poll + 16 * q, h->d_info, 8 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(h_poll + 16 * q + 8, s->flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1757,7 +1828,8 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
         if (!copy_pending[q]) return 0;
         if (hipEventSynchronize(ev_copied[q]) != hipSuccess) return fail_hip("draw copy");
         const int slot = copy_slot[q];
-        for (int64_t i = 0; i < n; ++i) h_theta_draws[slot + i * (int64_t)(S_it + 1)] = th_stage[q][(size_t)i];
+        if (h_theta_draws)
+            for (int64_t i = 0; i < n; ++i) h_theta_draws[slot + i * (int64_t)(S_it + 1)] = th_stage[q][(size_t)i];
         copy_pending[q] = false;
         return 0;
     };
@@ -1765,9 +1837,13 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
         const int q = k % NS, slot = k - B_it;
         GP_TRY(finish_store(q));
         const double* d = ck[q];
-        if (hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess ||
-            hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + n, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess ||
-            hipMemcpyAsync(h_f_draws + (int64_t)slot * n * m, d + n + 2 * m, sizeof(double) * (size_t)(n * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess ||
+        // the summaries read the slot on the compute stream: ordered before save_ckpt(k + 3) overwrites it, which the host
+        // enqueues only once checkpoint k + 1 is verified
+        if (summarise) GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y));
+        if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
+        if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
+            (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
+            (h_f_draws && hipMemcpyAsync(h_f_draws + (int64_t)slot * n * m, d + off_f, sizeof(double) * (size_t)(n * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             hipEventRecord(ev_copied[q], copy_stream) != hipSuccess)
             return fail_hip("draw copy");
         copy_pending[q] = true; copy_slot[q] = slot;
@@ -1782,7 +1858,7 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
         const double* d = ck[k % NS];
         for (const Part& pt : parts()) {
             if (hipMemcpyAsync(pt.p, d, pt.cnt * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail_hip("rollback");
-            d += pt.cnt;
+            d += even(pt.cnt);
         }
         if (hipMemsetAsync(s->flags, 0, 4 * sizeof(int), st) != hipSuccess) return fail_hip("rollback");
         s->iter = k;
@@ -1840,10 +1916,39 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, 
     }
     if (h_poll) hipHostFree(h_poll);
     if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
+    if (!rc) rc = summary_out();
     g_last_mcmc_fallbacks = h->guard_fallbacks;
     gpirt_sampler_destroy(s);
     gpirt_destroy(h);
     return rc;
+}
+
+int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int S_it, int B_it,
+               const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts,
+               gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
+               double* h_beta_draws, double* h_f_draws, double* h_irfs)
+{
+    GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && h_theta_draws && h_beta_draws && h_f_draws && h_irfs);
+    GP_ARG(n > 0 && m > 0 && S_it >= 0 && B_it >= 0);
+    return mcmc_run(h_y, n, m, h_theta0, S_it, B_it, h_pm, h_ps, h_step, opts, rs, tick, tick_ctx, h_theta_draws,
+                    h_beta_draws, h_f_draws, h_irfs, nullptr);
+}
+
+int gpirt_mcmc_summary(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int S_it, int B_it,
+                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts,
+                       gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
+                       double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* summary)
+{
+    GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && h_irfs && summary);
+    GP_ARG(n > 0 && m > 0 && S_it >= 0 && B_it >= 0);
+    const int parts = summary->parts;
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0 && summary->reserved == 0);
+    GP_ARG(!((summary->h_p_yes) && !(parts & GPIRT_SUM_PRED)));
+    GP_ARG(!((summary->h_lppd || summary->h_p_waic) && !(parts & GPIRT_SUM_WAIC)));
+    GP_ARG(!((summary->h_f_mean || summary->h_f_var) && !(parts & GPIRT_SUM_F)));
+    GP_ARG(!((summary->h_theta_mean || summary->h_theta_var || summary->h_beta_mean || summary->h_beta_var) && parts == 0));
+    return mcmc_run(h_y, n, m, h_theta0, S_it, B_it, h_pm, h_ps, h_step, opts, rs, tick, tick_ctx, h_theta_draws,
+                    h_beta_draws, h_f_draws, h_irfs, summary);
 }
 
 }  // extern "C"

@@ -223,7 +223,63 @@ class ShardedSampler:
         """All ranks receive the full (column-concatenated) array `name` of item-sharded state.  Tensor collectives on
         the host copies (no pickling: `f` is 64 MiB per rank at the metric size): shards are padded to the largest
         item count so that one flat all-gather serves unequal partitions too."""
-        local = np.ascontiguousarray(self.engine.get(name).T)     # (m_local, rows)
+        return self._gather_columns(self.engine.get(name))
+
+    # -- posterior summaries (include/gpirt_hip.h gpirt_sampler_summary_*): each rank accumulates its own item columns;
+    # theta's moments are the same on every rank
+    def summary_enable(self, parts):
+        self.engine.summary_enable(parts)
+
+    def summary_accumulate(self):
+        self.engine.summary_accumulate()
+
+    def summary_gather(self, name: str):
+        """The full pointwise summary `name` (p_yes, lppd, p_waic, f_mean, f_var, beta_mean, beta_var) on every rank;
+        theta_mean / theta_var are the local ones (identical on every rank)."""
+        local = self.engine.summary_get(name)
+        if name.startswith("theta_"):
+            return local
+        return self._gather_columns(local)
+
+    def summary_totals(self) -> dict:
+        """WAIC totals of the whole problem: sums of lppd, p_waic and n_obs over the ranks; the elpd spread combined by
+        Chan's formula from each rank's (n_obs, mean, sum of squared deviations); one all-gather of three numbers a rank."""
+        t = self.engine.summary_totals()
+        if self.world == 1:
+            return t
+        import torch
+        dev = getattr(self.engine, "torch_device", torch.device("cpu"))
+        if self.dist.get_backend() == "gloo":
+            dev = torch.device("cpu")
+        keys = ("lppd", "p_waic", "n_obs", "elpd_mean", "elpd_ss")
+        mine = torch.tensor([[t[k] for k in keys]], dtype=torch.float64, device=dev)
+        full = torch.empty((self.world, len(keys)), dtype=torch.float64, device=dev)
+        if hasattr(self.dist, "all_gather_into_tensor"):
+            self.dist.all_gather_into_tensor(full, mine)
+        else:
+            parts = [torch.empty_like(mine) for _ in range(self.world)]
+            self.dist.all_gather(parts, mine)
+            full = torch.cat(parts, dim=0)
+        rows = full.cpu().numpy()
+        lppd = float(sum(r[0] for r in rows))                 # rank order: the same sums on every rank
+        p_waic = float(sum(r[1] for r in rows))
+        n, mean, ss = 0.0, 0.0, 0.0
+        for r in rows:                                        # Chan et al.: pairwise combination of (count, mean, M2)
+            nb, mb, sb = float(r[2]), float(r[3]), float(r[4])
+            if nb == 0:
+                continue
+            tot = n + nb
+            delta = mb - mean
+            mean = mean + delta * (nb / tot)
+            ss = ss + sb + delta * delta * (n * nb / tot)
+            n = tot
+        elpd = lppd - p_waic
+        return dict(lppd=lppd, p_waic=p_waic, elpd_waic=elpd, waic=-2.0 * elpd,
+                    se_elpd_waic=float(np.sqrt(n * (ss / (n - 1.0)))) if n > 1 else float("nan"),
+                    n_obs=n, draws=t["draws"], elpd_mean=mean, elpd_ss=ss)
+
+    def _gather_columns(self, arr):
+        local = np.ascontiguousarray(arr.T)                       # (m_local, rows)
         if self.world == 1:
             return np.asfortranarray(local.T)
         import torch

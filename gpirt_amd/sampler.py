@@ -43,7 +43,7 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
 def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_prior_means=None,
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
-              progress=False, preset=None):
+              progress=False, preset=None, summaries=None, store_draws=True):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -56,6 +56,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       the mean as (L^-1 k*)^T (L^-1 f), and K(theta, theta*) through its exact rank-r Chebyshev factorisation.
     preset="fast": the library's throughput preset, gpirt_fast_options() (R: options(gpirt.hip.preset = "fast")) --
       item-keyed RNG with this call's `seed`, theta_stabilise, fstar_fused, kstar_rank = 64; what bench.py times.
+    summaries: posterior summaries accumulated on the device over the S sampling iterations (include/gpirt_hip.h
+      GPIRT_SUM_*): part names ("waic", "pred", "f", "theta_beta") or their bits.  The result then has a "summary" entry:
+      the arrays of those parts (theta / beta moments always) and "totals" (a dict; WAIC's, with "waic").
+    store_draws: True, False, or a subset of ("theta", "beta", "f"); a draw that is not stored comes back as None.  With
+      summaries and no stored f a long chain at 8192 x 1024 needs O(n m) host memory instead of n m 8 bytes per iteration.
     """
     from .ops import RStream
 
@@ -86,9 +91,17 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     if theta0.shape != (n,):
         raise ValueError("theta_init must have one value per respondent")
     S, B = int(sample_iterations), int(burn_iterations)
-    th = np.empty((S + 1, n), order="F")
-    be = np.empty((2, m, S + 1), order="F")
-    ff = np.empty((n, m, S + 1), order="F")
+    if store_draws is True:
+        keep = {"theta", "beta", "f"}
+    elif store_draws is False or store_draws is None:
+        keep = set()
+    else:
+        keep = {store_draws} if isinstance(store_draws, str) else set(store_draws)
+        if not keep <= {"theta", "beta", "f"}:
+            raise ValueError("store_draws must be True, False or a subset of ('theta', 'beta', 'f')")
+    th = np.empty((S + 1, n), order="F") if "theta" in keep else None
+    be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
+    ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
     irf = np.empty((NGRID, m), order="F")
     if preset == "fast":
         o = _lib.fast_options()
@@ -103,14 +116,48 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         return 0
 
     cb = _lib.TICK_FN(_tick)
-    rc = lib.gpirt_mcmc(_ptr(y), n, m, _ptr(theta0), S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                        rs.ptr if rs is not None else None, cb, None, _ptr(th), _ptr(be), _ptr(ff), _ptr(irf))
+    if summaries is None and len(keep) == 3:
+        rc = lib.gpirt_mcmc(_ptr(y), n, m, _ptr(theta0), S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                            rs.ptr if rs is not None else None, cb, None, _ptr(th), _ptr(be), _ptr(ff), _ptr(irf))
+    else:
+        parts = _lib.summary_parts(summaries if summaries is not None else 0)
+        sm = _lib.Summary()
+        sm.parts = parts
+        arrays = _summary_arrays(parts, n, m)
+        for k, a in arrays.items():
+            setattr(sm, "h_" + k, _ptr(a))
+        opt = lambda a: _ptr(a) if a is not None else None           # noqa: E731
+        rc = lib.gpirt_mcmc_summary(_ptr(y), n, m, _ptr(theta0), S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                    rs.ptr if rs is not None else None, cb, None, opt(th), opt(be), opt(ff), _ptr(irf),
+                                    C.byref(sm))
     if progress:
         print("\r100.000 % complete")
     if rc > 0:
         raise RuntimeError("chol(): decomposition failed")           # what arma::chol throws
     check(rc)
-    return dict(theta=th, beta=be, f=ff, IRFs=irf)
+    out = dict(theta=th, beta=be, f=ff, IRFs=irf)
+    if summaries is not None:
+        out["summary"] = dict(arrays, totals=_totals(sm.totals))
+    return out
+
+
+def _summary_arrays(parts: int, n: int, m: int) -> dict:
+    """host arrays of every output of the summary parts `parts` (theta / beta moments with any part)"""
+    names = []
+    if parts:
+        names += ["theta_mean", "theta_var", "beta_mean", "beta_var"]
+    if parts & _lib.SUM_PRED:
+        names += ["p_yes"]
+    if parts & _lib.SUM_WAIC:
+        names += ["lppd", "p_waic"]
+    if parts & _lib.SUM_F:
+        names += ["f_mean", "f_var"]
+    shape = {"theta_mean": (n,), "theta_var": (n,), "beta_mean": (2, m), "beta_var": (2, m)}
+    return {k: np.empty(shape.get(k, (n, m)), order="F") for k in names}
+
+
+def _totals(raw) -> dict:
+    return {k: float(raw[i]) for i, k in enumerate(_lib.SUM_TOTALS)}
 
 
 class Sampler:
@@ -301,6 +348,36 @@ class Sampler:
     def finish_irfs(self, sample_iterations: int) -> np.ndarray:
         out = np.empty((NGRID, self.m), order="F")
         check(self.lib.gpirt_sampler_finish_irfs(self._s, int(sample_iterations), _ptr(out)))
+        return out
+
+    # -- posterior summaries accumulated on the device (include/gpirt_hip.h gpirt_sampler_summary_*)
+    def summary_enable(self, parts):
+        """Allocate and zero the accumulators of `parts` (names or GPIRT_SUM_* bits; 0 / () frees them)."""
+        self._sum_parts = _lib.summary_parts(parts)
+        check(self.lib.gpirt_sampler_summary_enable(self._s, self._sum_parts))
+
+    def summary_accumulate(self):
+        """Add the current state (after a sampling iteration's step) as one draw."""
+        self._call("gpirt_sampler_summary_accumulate")
+
+    def summary_get(self, name: str) -> np.ndarray:
+        shape = {"theta_mean": (self.n,), "theta_var": (self.n,), "beta_mean": (2, self.m), "beta_var": (2, self.m)}.get(
+            name, (self.n, self.m))
+        out = np.empty(shape, order="F")
+        check(self.lib.gpirt_sampler_summary_get(self._s, name.encode(), _ptr(out), out.size))
+        return out
+
+    def summary_totals(self) -> dict:
+        raw = (C.c_double * len(_lib.SUM_TOTALS))()
+        check(self.lib.gpirt_sampler_summary_totals(self._s, raw))
+        return _totals(raw)
+
+    def summary(self) -> dict:
+        """Every array of the enabled parts, plus "totals" (with GPIRT_SUM_WAIC)."""
+        parts = getattr(self, "_sum_parts", 0)
+        out = {k: self.summary_get(k) for k in _summary_arrays(parts, self.n, self.m)}
+        if parts & _lib.SUM_WAIC:
+            out["totals"] = self.summary_totals()
         return out
 
     def enable_timing(self, on=True):

@@ -60,7 +60,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -299,6 +299,62 @@ int gpirt_mcmc(const double* h_y, int64_t n, int64_t m, const double* h_theta0,
                gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
                double* h_beta_draws, double* h_f_draws, double* h_irfs);
 
+/* ------------------------------------------------------ posterior summaries ------------- */
+/* Summaries of a chain accumulated on the device, one draw at a time, in O(n m) memory however long the chain (the stored
+ * f draws of gpirt_mcmc take n m 8 bytes per iteration).  Parts (bits of `parts`):
+ *   GPIRT_SUM_THETA_BETA  theta_mean / theta_var (n), beta_mean / beta_var (2 x m); always on when any part is
+ *   GPIRT_SUM_F           f_mean / f_var (n x m)
+ *   GPIRT_SUM_PRED        p_yes (n x m): mean over the draws of P(y = 1) = plogis(f + mu); for a missing cell the
+ *                         held-out prediction
+ *   GPIRT_SUM_WAIC        lppd, p_waic (n x m; NaN where y is missing) and the totals below
+ * For cell (i, j) of draw s, ll = -softplus(-y g) with g = f + mu (src/log-likelihood.cpp:25-37);
+ * lppd_ij = log(mean_s exp(ll_s)) (a running logaddexp), p_waic_ij = var_s(ll_s) (ddof = 1, Welford).  Every variance and
+ * p_waic is NaN with fewer than two draws.  A draw is the state at the end of a sampling iteration (slot s >= 1 of the
+ * stored draws); burn-in and the initial state never enter. */
+#define GPIRT_SUM_THETA_BETA 1
+#define GPIRT_SUM_F          2
+#define GPIRT_SUM_PRED       4
+#define GPIRT_SUM_WAIC       8
+/* totals[] over the observed cells (GPIRT_SUM_WAIC): sums of lppd_ij and p_waic_ij, elpd_waic = lppd - p_waic,
+ * waic = -2 elpd_waic, se_elpd_waic = sqrt(n_obs var(elpd_ij)) (ddof = 1, as the loo package), n_obs, draws, and the
+ * mean and sum of squared deviations of elpd_ij (what shards combine exactly by Chan's formula) */
+#define GPIRT_SUM_T_LPPD         0
+#define GPIRT_SUM_T_P_WAIC       1
+#define GPIRT_SUM_T_ELPD_WAIC    2
+#define GPIRT_SUM_T_WAIC         3
+#define GPIRT_SUM_T_SE_ELPD_WAIC 4
+#define GPIRT_SUM_T_N_OBS        5
+#define GPIRT_SUM_T_DRAWS        6
+#define GPIRT_SUM_T_ELPD_MEAN    7
+#define GPIRT_SUM_T_ELPD_SS      8
+#define GPIRT_SUM_NTOTALS        9
+
+/* What gpirt_mcmc_summary returns besides the IRFs: the parts wanted, a HOST pointer per output (NULL: not wanted; a
+ * pointer to a part that is off is refused) and the totals (written when GPIRT_SUM_WAIC is on). */
+typedef struct gpirt_summary {
+    int      parts;
+    int      reserved;        /* must be 0 */
+    double*  h_p_yes;         /* n x m */
+    double*  h_lppd;          /* n x m */
+    double*  h_p_waic;        /* n x m */
+    double*  h_f_mean;        /* n x m */
+    double*  h_f_var;         /* n x m */
+    double*  h_theta_mean;    /* n */
+    double*  h_theta_var;     /* n */
+    double*  h_beta_mean;     /* 2 x m */
+    double*  h_beta_var;      /* 2 x m */
+    double   totals[GPIRT_SUM_NTOTALS];
+} gpirt_summary;
+
+/* gpirt_mcmc with summaries: same inputs, the same chain (draws, IRFs and R's stream bit-identical to gpirt_mcmc's);
+ * h_theta_draws, h_beta_draws and h_f_draws may each be NULL (not stored), h_irfs is required.  GPIRT_RNG_ITEM: each draw
+ * is added from its checkpoint once that is verified, so a hang-guard rollback never counts an iteration twice. */
+int gpirt_mcmc_summary(const double* h_y, int64_t n, int64_t m, const double* h_theta0,
+                       int sample_iterations, int burn_iterations, const double* h_prior_means,
+                       const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts,
+                       gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
+                       double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* summary);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
@@ -347,6 +403,14 @@ int gpirt_sampler_panel_copy_part(gpirt_sampler_t s, int64_t p, int half, double
 int gpirt_sampler_adopt_factor(gpirt_sampler_t s, int rows_with_L);
 int gpirt_sampler_skip_factor(gpirt_sampler_t s);
 int gpirt_sampler_accumulate_irf(gpirt_sampler_t s);     /* :103 */
+/* Posterior summaries on the stage API: summary_enable allocates and zeroes the accumulators of `parts` (0 frees them);
+ * summary_accumulate adds the CURRENT state as one draw (call it after the step of a sampling iteration); summary_get
+ * finishes one array ("p_yes", "lppd", "p_waic", "f_mean", "f_var", "theta_mean", "theta_var", "beta_mean", "beta_var";
+ * count <= its size) and copies it out; summary_totals writes GPIRT_SUM_NTOTALS doubles (needs GPIRT_SUM_WAIC). */
+int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts);
+int gpirt_sampler_summary_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_summary_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count);
+int gpirt_sampler_summary_totals(gpirt_sampler_t s, double* h_totals);
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter);
 /* Sets the completed-iteration counter (the GPIRT_RNG_ITEM sub-streams are keyed by it): lets a second sampler
  * replay a stage of another one's iteration on copied state (bench.py's in-run check of the draw_fstar forms). */
