@@ -24,6 +24,7 @@ E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -
 # posterior summaries (include/gpirt_hip.h GPIRT_SUM_*): part bits, and the order of the totals
 SUM_THETA_BETA, SUM_F, SUM_PRED, SUM_WAIC = 1, 2, 4, 8
 SUM_PARTS = {"theta_beta": SUM_THETA_BETA, "f": SUM_F, "pred": SUM_PRED, "waic": SUM_WAIC}
+SUM_DIAG = 16                     # split-R-hat / batch-means ESS accumulators (Sampler.summary_enable(..., planned_draws=S))
 SUM_TOTALS = ("lppd", "p_waic", "elpd_waic", "waic", "se_elpd_waic", "n_obs", "draws", "elpd_mean", "elpd_ss")
 
 
@@ -52,6 +53,31 @@ class Summary(C.Structure):
     _fields_ = [("parts", C.c_int), ("reserved", C.c_int)] + [
         (f"h_{k}", C.POINTER(C.c_double)) for k in ("p_yes", "lppd", "p_waic", "f_mean", "f_var", "theta_mean", "theta_var",
                                                      "beta_mean", "beta_var")] + [("totals", C.c_double * len(SUM_TOTALS))]
+
+
+DIAG_BLOCKS = ("theta", "beta", "f")
+DIAG_SCALARS = ("max_rhat", "min_ess", "n_rhat_high", "n_rhat_nan", "n_ess_nan")
+CHAIN_SEED_GAMMA, CHAIN_SEED_M1, CHAIN_SEED_M2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+_M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def chain_seed(seed: int, c: int) -> int:
+    """gpirt_chain_seed: chain 0 keeps `seed`; chain c >= 1 takes the splitmix64 finaliser of seed + c GAMMA."""
+    seed = int(seed) & _M64
+    if c <= 0:
+        return seed
+    z = (seed + c * CHAIN_SEED_GAMMA) & _M64
+    z = ((z ^ (z >> 30)) * CHAIN_SEED_M1) & _M64
+    z = ((z ^ (z >> 27)) * CHAIN_SEED_M2) & _M64
+    return z ^ (z >> 31)
+
+
+class Diag(C.Structure):
+    """gpirt_diag (include/gpirt_hip.h): host pointers of R-hat / ESS / MCSE per block (NULL: not wanted), the reflection
+    flags, the per-block scalars and reserved words."""
+    _fields_ = [(f"h_{b}_{k}", C.POINTER(C.c_double)) for b in DIAG_BLOCKS for k in ("rhat", "ess", "mcse")] + [
+        ("reflected", C.POINTER(C.c_int)), ("scalars", (C.c_double * len(DIAG_SCALARS)) * len(DIAG_BLOCKS)),
+        ("reserved", C.c_int64 * 4)]
 
 
 class Options(C.Structure):
@@ -137,6 +163,14 @@ SIGNATURES = {
     "gpirt_mcmc_summary": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _vp,
                                    TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary)]),
     "gpirt_sampler_summary_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_summary_enable_planned": (_i32, [_vp, _i32, _i64]),
+    "gpirt_summary_state_bytes": (_i32, [_i64, _i64, _i32, C.POINTER(_i64)]),
+    "gpirt_sampler_summary_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_chain_seed": (_u64, [_u64, _i32]),
+    "gpirt_chains_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, _dp, C.POINTER(Summary),
+                                     C.POINTER(Diag)]),
+    "gpirt_mcmc_chains": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

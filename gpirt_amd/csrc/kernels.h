@@ -271,18 +271,36 @@ int report_panel_guard(gpirt_handle_t h, const int* info_words, hipStream_t stre
 // api.hip
 int create_side_handle(gpirt_handle_t* out, int device);
 
-// summary.hip: posterior summaries accumulated one draw at a time (gpirt_sampler_summary_*, gpirt_mcmc_summary)
+// summary.hip: posterior summaries accumulated one draw at a time (gpirt_sampler_summary_*, gpirt_mcmc_summary), and the
+// combination of several chains' accumulators (gpirt_chains_combine)
+constexpr int SUM_LAYOUT_VERSION = 1;
+constexpr int SUM_HEADER_WORDS = 8;       // int64: n, m, parts, planned S, draws, layout version, grid points, 0
+// offsets in doubles from the start of a state block (-1: the part is off); every one is even (16-byte aligned)
+struct SumLayout {
+    int64_t tb_mean = -1, tb_m2 = -1, lse = -1, ll_mean = -1, ll_m2 = -1, y = -1, p_sum = -1, f_mean = -1, f_m2 = -1, irf = -1;
+    int64_t dtb[7] = { -1, -1, -1, -1, -1, -1, -1 };    // DIAG of theta / beta: half 1 (mean, M2), half 2 (mean, M2), batch sum,
+    int64_t df[7] = { -1, -1, -1, -1, -1, -1, -1 };     // batch means (mean, M2); df: the same of f (DIAG and F)
+    int64_t total = 0;
+};
+enum { DG_H1_MEAN, DG_H1_M2, DG_H2_MEAN, DG_H2_M2, DG_BSUM, DG_BM_MEAN, DG_BM_M2 };
+SumLayout summary_layout(int64_t n, int64_t m, int parts);
 struct SummaryState {
     int parts = 0;                    // GPIRT_SUM_* (0: off)
-    int64_t n = 0, m = 0, draws = 0;
+    int64_t n = 0, m = 0, draws = 0, planned = 0;
+    double* block = nullptr;          // the accumulators: ONE device block (SumLayout), header first
+    SumLayout lay;
     double *tb_mean = nullptr, *tb_m2 = nullptr;                          // theta (n) then beta (2 x m): Welford
     double *lse = nullptr, *ll_mean = nullptr, *ll_m2 = nullptr;          // WAIC: log sum_s exp(ll_s), Welford of ll
+    double *y = nullptr;                                                  // WAIC: a copy of y (the missing cells' mask)
     double *p_sum = nullptr;                                              // PRED: sum_s P(y = 1)
     double *f_mean = nullptr, *f_m2 = nullptr;                            // F: Welford of f
+    double *irf = nullptr;                                                // a copy of the sampler's irf_sum (N x m)
+    double *dtb[7] = {}, *df[7] = {};                                     // DIAG (SumLayout)
     double *out = nullptr, *part = nullptr, *tot = nullptr;              // a finished array, block partials, the totals
     std::vector<void*> allocs;
 };
-int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts);     // zeroed accumulators
+// zeroed accumulators; planned: the draw count S fixed for GPIRT_SUM_DIAG (0 without it)
+int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t planned = 0);
 void summary_free(SummaryState* s);
 // adds one draw; f, mu, y are n x m (16-byte aligned), theta n, beta 2 x m
 int launch_summary_accumulate(hipStream_t stream, SummaryState* s, const double* theta, const double* beta, const double* f,
@@ -292,6 +310,11 @@ int launch_summary_finish(hipStream_t stream, const SummaryState* s, const char*
                           int64_t* count);
 // the totals (GPIRT_SUM_T_*) into s->tot
 int launch_summary_totals(hipStream_t stream, const SummaryState* s, const double* y);
+// the header words and the IRF sum into the block (irf_sum: the sampler's, N x m); the block is then self-contained
+int summary_seal(hipStream_t stream, SummaryState* s, const double* irf_sum, int64_t N);
+// gpirt_chains_combine on h's stream (arguments as in include/gpirt_hip.h)
+int chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align, double* h_irfs,
+                   gpirt_summary* pooled, gpirt_diag* diag);
 
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi

@@ -1429,12 +1429,38 @@ int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts)
 {
     GP_ARG(s && s->initialised);
     GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0);
+    return gpirt_sampler_summary_enable_planned(s, parts, 0);
+}
+
+int gpirt_sampler_summary_enable_planned(gpirt_sampler_t s, int parts, int64_t planned_draws)
+{
+    GP_ARG(s && s->initialised);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) == 0);
+    GP_ARG(planned_draws >= 0 && (!(parts & GPIRT_SUM_DIAG) || planned_draws >= 1));
     GP_HIP(hipStreamSynchronize(s->h->stream));        // a summary kernel still running on the old accumulators
     summary_free(&s->sum);
     if (parts == 0) return 0;
-    const int rc = summary_alloc(&s->sum, s->n, s->m, parts | GPIRT_SUM_THETA_BETA);
+    const int rc = summary_alloc(&s->sum, s->n, s->m, parts | GPIRT_SUM_THETA_BETA, planned_draws);
     if (rc) summary_free(&s->sum);
     return rc;
+}
+
+int gpirt_summary_state_bytes(int64_t n, int64_t m, int parts, int64_t* bytes)
+{
+    GP_ARG(n > 0 && m > 0 && bytes);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) == 0);
+    *bytes = summary_layout(n, m, parts | GPIRT_SUM_THETA_BETA).total * (int64_t)sizeof(double);
+    return 0;
+}
+
+int gpirt_sampler_summary_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
+    GP_TRY(summary_seal(s->h->stream, &s->sum, s->irf_sum, s->N));
+    *d_state = s->sum.block;
+    *bytes = s->sum.lay.total * (int64_t)sizeof(double);
+    return 0;
 }
 
 int gpirt_sampler_summary_accumulate(gpirt_sampler_t s)
@@ -1691,22 +1717,40 @@ long long gpirt_debug_take_mcmc_trip(void);
 static int g_last_mcmc_fallbacks = 0;
 int gpirt_debug_last_mcmc_fallbacks(void) { return g_last_mcmc_fallbacks; }
 
-// The loop of gpirt_mcmc and gpirt_mcmc_summary (arguments checked by the callers).  sm != NULL: the draws' pointers may be
-// NULL (not stored) and every sampling iteration's state is added to the summaries -- under the item RNG from its checkpoint
-// once that is verified (start_store), so that a rollback cannot count an iteration twice.
+// One chain of gpirt_mcmc_chains: run on the caller's handle, with the GPIRT_SUM_DIAG accumulators planned for the chain's
+// S draws; the sampler's summary state (sealed: header and IRF sum) is moved to *keep before the sampler goes.  The tick
+// sees (base + it, ticks).
+struct ChainRun {
+    gpirt_handle_t h;
+    SummaryState* keep;
+    int base, ticks;
+};
+
+// The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
+// sm != NULL: the draws' pointers may be NULL (not stored) and every sampling iteration's state is added to the summaries --
+// under the item RNG from its checkpoint once that is verified (start_store), so that a rollback cannot count an iteration
+// twice.
 static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int S_it, int B_it,
                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts,
                     gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
-                    double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* sm)
+                    double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* sm, const ChainRun* cr = nullptr)
 {
     gpirt_options o;
     if (opts) o = *opts; else gpirt_default_options(&o);
     gpirt_handle_t h = nullptr;
-    GP_TRY(gpirt_create_own_stream(&h, o.device));
-    { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
+    if (cr) h = cr->h;
+    else {
+        GP_TRY(gpirt_create_own_stream(&h, o.device));
+        const long long trip = gpirt_debug_take_mcmc_trip();
+        if (trip > 0) h->trip_guard_at = trip;
+    }
+    auto drop_handle = [&]() { if (!cr) gpirt_destroy(h); };
+    auto ticked = [&](int it, int total) -> bool {
+        return tick && (cr ? tick(tick_ctx, cr->base + it, cr->ticks) : tick(tick_ctx, it, total));
+    };
     gpirt_sampler_t s = nullptr;
     int rc = gpirt_sampler_create(&s, h, h_y, n, m, h_theta0, h_pm, h_ps, h_step, &o, rs);
-    if (rc) { gpirt_destroy(h); return rc; }
+    if (rc) { drop_handle(); return rc; }
     const int64_t N = s->N;
     const int total = S_it + B_it;
     const bool replay = stream_mode(s);
@@ -1724,6 +1768,12 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     };
     // the summaries out of the sampler (before it is destroyed)
     auto summary_out = [&]() -> int {
+        if (cr) {                               // the chain's state outlives its sampler until the combine
+            GP_TRY(summary_seal(h->stream, &s->sum, s->irf_sum, N));
+            *cr->keep = std::move(s->sum);
+            s->sum = SummaryState{};
+            return 0;
+        }
         if (!sm) return 0;
         for (int k = 0; k < GPIRT_SUM_NTOTALS; ++k) sm->totals[k] = (double)NAN;
         sm->totals[GPIRT_SUM_T_DRAWS] = (double)s->sum.draws;
@@ -1741,14 +1791,15 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     rc = gpirt_sampler_init(s);
     if (!rc) rc = gpirt_sampler_check(s);
     if (!rc) rc = store_sync(0);
-    if (!rc && summarise) rc = gpirt_sampler_summary_enable(s, sm->parts);
+    if (!rc && summarise)
+        rc = cr ? gpirt_sampler_summary_enable_planned(s, sm->parts | GPIRT_SUM_DIAG, S_it) : gpirt_sampler_summary_enable(s, sm->parts);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
         // host): check, repair a hang-guard expiry in place (gpirt_sampler_check: nothing has read the new L yet) and store,
         // synchronously.
         for (int it = 0; it < total && !rc; ++it) {
-            if (tick && tick(tick_ctx, it, total)) { set_error("interrupted"); rc = GPIRT_E_INTERRUPT; break; }
+            if (ticked(it, total)) { set_error("interrupted"); rc = GPIRT_E_INTERRUPT; break; }
             rc = gpirt_sampler_step(s);
             if (!rc) rc = gpirt_sampler_check(s);
             if (!rc && it >= B_it) {
@@ -1761,7 +1812,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (!rc) rc = summary_out();
         g_last_mcmc_fallbacks = h->guard_fallbacks;
         gpirt_sampler_destroy(s);
-        gpirt_destroy(h);
+        drop_handle();
         return rc;
     }
 
@@ -1871,7 +1922,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && hipEventSynchronize(ev_flags[0]) != hipSuccess) rc = fail_hip("hipEventSynchronize");
     while (!rc && verified < total) {
         if (it < total && verified >= it - 1) {
-            if (tick && tick(tick_ctx, it, total)) { set_error("interrupted"); rc = GPIRT_E_INTERRUPT; break; }
+            if (ticked(it, total)) { set_error("interrupted"); rc = GPIRT_E_INTERRUPT; break; }
             h->cfg.panel = (it < fallback_until) ? 2 : panel_mode;          // iterations lost to a guard expiry are repeated on the fallback panel
             if (h->aux) h->aux->cfg.panel = h->cfg.panel;
             rc = gpirt_sampler_step(s);
@@ -1919,7 +1970,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc) rc = summary_out();
     g_last_mcmc_fallbacks = h->guard_fallbacks;
     gpirt_sampler_destroy(s);
-    gpirt_destroy(h);
+    drop_handle();
     return rc;
 }
 
@@ -1949,6 +2000,73 @@ int gpirt_mcmc_summary(const double* h_y, int64_t n, int64_t m, const double* h_
     GP_ARG(!((summary->h_theta_mean || summary->h_theta_var || summary->h_beta_mean || summary->h_beta_var) && parts == 0));
     return mcmc_run(h_y, n, m, h_theta0, S_it, B_it, h_pm, h_ps, h_step, opts, rs, tick, tick_ctx, h_theta_draws,
                     h_beta_draws, h_f_draws, h_irfs, summary);
+}
+
+// ---- several chains ---------------------------------------------------------------------------------------------------
+uint64_t gpirt_chain_seed(uint64_t seed, int c)
+{
+    if (c <= 0) return seed;
+    uint64_t z = seed + (uint64_t)c * GPIRT_CHAIN_SEED_GAMMA;
+    z = (z ^ (z >> 30)) * GPIRT_CHAIN_SEED_M1;
+    z = (z ^ (z >> 27)) * GPIRT_CHAIN_SEED_M2;
+    return z ^ (z >> 31);
+}
+
+int gpirt_chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
+                         double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag)
+{
+    return chains_combine(h, chains, d_states, signs, align, h_irfs, pooled, diag);
+}
+
+int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                      const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag)
+{
+    GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
+    GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
+    if (opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_chains needs GPIRT_RNG_ITEM (each chain keys its draws by gpirt_chain_seed)");
+        return GPIRT_E_ARG;
+    }
+    // the pooled outputs are checked now, before any chain runs (the combine checks them again against the states)
+    const int parts = pooled->parts | GPIRT_SUM_THETA_BETA;
+    {
+        GP_ARG((pooled->parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0 && pooled->reserved == 0);
+        GP_ARG(!(pooled->h_p_yes && !(parts & GPIRT_SUM_PRED)));
+        GP_ARG(!((pooled->h_lppd || pooled->h_p_waic) && !(parts & GPIRT_SUM_WAIC)));
+        GP_ARG(!((pooled->h_f_mean || pooled->h_f_var) && !(parts & GPIRT_SUM_F)));
+    }
+    if (diag) {
+        GP_ARG(diag->reserved[0] == 0 && diag->reserved[1] == 0 && diag->reserved[2] == 0 && diag->reserved[3] == 0);
+        GP_ARG((parts & GPIRT_SUM_F) || !(diag->h_f_rhat || diag->h_f_ess || diag->h_f_mcse));
+    }
+    gpirt_handle_t h = nullptr;
+    GP_TRY(gpirt_create_own_stream(&h, opts->device));
+    { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
+    std::vector<SummaryState> keep((size_t)chains);
+    const int total = S_it + B_it;
+    int rc = 0;
+    for (int c = 0; c < chains && !rc; ++c) {
+        gpirt_options o = *opts;
+        o.seed = gpirt_chain_seed(opts->seed, c);
+        gpirt_summary sm{};
+        sm.parts = parts;
+        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total };
+        std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
+        rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, nullptr, tick, tick_ctx,
+                      h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
+                      h_beta_draws ? h_beta_draws + (int64_t)c * 2 * m * (S_it + 1) : nullptr,
+                      h_f_draws ? h_f_draws + (int64_t)c * n * m * (S_it + 1) : nullptr, irf_c.data(), &sm, &cr);
+    }
+    if (!rc) {
+        std::vector<const void*> st((size_t)chains);
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
+        rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag);
+    }
+    for (auto& k : keep) summary_free(&k);
+    gpirt_destroy(h);
+    return rc;
 }
 
 }  // extern "C"

@@ -8,6 +8,12 @@
 // summary_accumulate_kernel is one streaming pass: f, mu and y read once, each accumulator read and written once, 16 bytes
 // per lane; theta and beta (n + 2m values) ride in the same launch.  The totals are reduced in a fixed order (block partials,
 // then one block), without atomics: bit-identical from run to run.
+//
+// GPIRT_SUM_DIAG adds, in the same pass, the split-half and batch-means accumulators of split-R-hat and a batch-means ESS
+// (summary_diag_accumulate_kernel).  Every accumulator of a chain lives in ONE device block (header, arrays, y, the IRF sum),
+// and chains_combine pools C such blocks -- Chan's formula, a logaddexp over chains, the theta -> -theta reflection applied
+// to the means -- into a state of C S draws that the finish and totals kernels read as they read one chain's
+// (include/gpirt_hip.h).
 #include "common.h"
 #include "kernels.h"
 
@@ -125,6 +131,139 @@ __global__ __launch_bounds__(SUM_THREADS) void summary_accumulate_kernel(SumArgs
     }
 }
 
+// GPIRT_SUM_DIAG: which accumulators draw d touches depends on d only (uniform over the grid).  half: 0 none, 1 or 2 (hd = the
+// draw's count within that half); batch: 0 past the a b batched draws, 1 add to the batch sum, 2 add and close batch bk of
+// size bd (its mean enters the Welford of the batch means, the sum restarts at 0).  The pointers are the draw's half's.
+struct DiagArgs {
+    double *t_hm, *t_h2, *t_bs, *t_bmm, *t_bm2;      // theta / beta (n + 2m)
+    double *f_hm, *f_h2, *f_bs, *f_bmm, *f_bm2;      // f (n x m; with F)
+    double hd, bd, bk;
+    int half, batch;
+};
+
+__device__ __forceinline__ void diag_value(const DiagArgs& g, double x, double& hm, double& h2, double& bs, double& bmm,
+                                           double& bm2)
+{
+    if (g.half) welford(hm, h2, x, g.hd);
+    if (g.batch == 2) { welford(bmm, bm2, (bs + x) / g.bd, g.bk); bs = 0.0; }
+    else if (g.batch == 1) bs += x;
+}
+
+template <bool DIAG>
+__device__ __forceinline__ void diag_load2(const DiagArgs& g, double* hmp, double* h2p, double* bsp, double* bmmp,
+                                           double* bm2p, int64_t q, double2& hm, double2& h2, double2& bs, double2& bmm,
+                                           double2& bm2)
+{
+    if (!DIAG) return;
+    if (g.half) { hm = reinterpret_cast<const double2*>(hmp)[q]; h2 = reinterpret_cast<const double2*>(h2p)[q]; }
+    if (g.batch) bs = reinterpret_cast<const double2*>(bsp)[q];
+    if (g.batch == 2) { bmm = reinterpret_cast<const double2*>(bmmp)[q]; bm2 = reinterpret_cast<const double2*>(bm2p)[q]; }
+}
+
+template <bool DIAG>
+__device__ __forceinline__ void diag_store2(const DiagArgs& g, double* hmp, double* h2p, double* bsp, double* bmmp,
+                                            double* bm2p, int64_t q, const double2& hm, const double2& h2, const double2& bs,
+                                            const double2& bmm, const double2& bm2)
+{
+    if (!DIAG) return;
+    if (g.half) { reinterpret_cast<double2*>(hmp)[q] = hm; reinterpret_cast<double2*>(h2p)[q] = h2; }
+    if (g.batch) reinterpret_cast<double2*>(bsp)[q] = bs;
+    if (g.batch == 2) { reinterpret_cast<double2*>(bmmp)[q] = bmm; reinterpret_cast<double2*>(bm2p)[q] = bm2; }
+}
+
+// one value of an array without a vector form (the odd last cell, theta and beta)
+template <bool DIAG>
+__device__ __forceinline__ void diag_scalar(const DiagArgs& g, double* hmp, double* h2p, double* bsp, double* bmmp, double* bm2p,
+                                            int64_t i, double x)
+{
+    if (!DIAG) return;
+    double hm = 0, h2 = 0, bs = 0, bmm = 0, bm2 = 0;
+    if (g.half) { hm = hmp[i]; h2 = h2p[i]; }
+    if (g.batch) bs = bsp[i];
+    if (g.batch == 2) { bmm = bmmp[i]; bm2 = bm2p[i]; }
+    diag_value(g, x, hm, h2, bs, bmm, bm2);
+    if (g.half) { hmp[i] = hm; h2p[i] = h2; }
+    if (g.batch) bsp[i] = bs;
+    if (g.batch == 2) { bmmp[i] = bmm; bm2p[i] = bm2; }
+}
+
+// summary_accumulate_kernel with the GPIRT_SUM_DIAG accumulators (split halves, batch means) added in the same pass -- f's
+// only with F --, so f is still read once.  (The kernel above is kept as it was: its instances' code does not move.)
+template <bool WAIC, bool PRED, bool F, bool DIAG>
+__device__ __forceinline__ void accumulate_body(const SumArgs& a, const DiagArgs& g, int64_t draw)
+{
+    const double d = (double)draw;
+    const bool first = draw == 1;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    constexpr bool FD = DIAG && F;
+    if (WAIC || PRED || F) {
+        const int64_t pairs = a.cells >> 1;
+        const double2* f2p = reinterpret_cast<const double2*>(a.f);
+        const double2* m2p = reinterpret_cast<const double2*>(a.mu);
+        const double2* y2p = reinterpret_cast<const double2*>(a.y);
+        for (int64_t q = tid; q < pairs; q += stride) {
+            const double2 fv = f2p[q], mv = m2p[q], yv = y2p[q];
+            double2 lse{}, lm{}, l2{}, ps{}, fm{}, fq{};
+            double2 hm{}, h2{}, bs{}, bmm{}, bm2{};
+            if (WAIC) {
+                lse = reinterpret_cast<const double2*>(a.lse)[q];
+                lm = reinterpret_cast<const double2*>(a.ll_mean)[q];
+                l2 = reinterpret_cast<const double2*>(a.ll_m2)[q];
+            }
+            if (PRED) ps = reinterpret_cast<const double2*>(a.p_sum)[q];
+            if (F) {
+                fm = reinterpret_cast<const double2*>(a.f_mean)[q];
+                fq = reinterpret_cast<const double2*>(a.f_m2)[q];
+            }
+            diag_load2<FD>(g, g.f_hm, g.f_h2, g.f_bs, g.f_bmm, g.f_bm2, q, hm, h2, bs, bmm, bm2);
+            accumulate_cell<WAIC, PRED, F>(a, fv.x, mv.x, yv.x, lse.x, lm.x, l2.x, ps.x, fm.x, fq.x, d, first);
+            accumulate_cell<WAIC, PRED, F>(a, fv.y, mv.y, yv.y, lse.y, lm.y, l2.y, ps.y, fm.y, fq.y, d, first);
+            if (FD) {
+                diag_value(g, fv.x, hm.x, h2.x, bs.x, bmm.x, bm2.x);
+                diag_value(g, fv.y, hm.y, h2.y, bs.y, bmm.y, bm2.y);
+            }
+            if (WAIC) {
+                reinterpret_cast<double2*>(a.lse)[q] = lse;
+                reinterpret_cast<double2*>(a.ll_mean)[q] = lm;
+                reinterpret_cast<double2*>(a.ll_m2)[q] = l2;
+            }
+            if (PRED) reinterpret_cast<double2*>(a.p_sum)[q] = ps;
+            if (F) {
+                reinterpret_cast<double2*>(a.f_mean)[q] = fm;
+                reinterpret_cast<double2*>(a.f_m2)[q] = fq;
+            }
+            diag_store2<FD>(g, g.f_hm, g.f_h2, g.f_bs, g.f_bmm, g.f_bm2, q, hm, h2, bs, bmm, bm2);
+        }
+        if ((a.cells & 1) && tid == 0) {
+            const int64_t c = a.cells - 1;
+            double lse = 0, lm = 0, l2 = 0, ps = 0, fm = 0, fq = 0;
+            if (WAIC) { lse = a.lse[c]; lm = a.ll_mean[c]; l2 = a.ll_m2[c]; }
+            if (PRED) ps = a.p_sum[c];
+            if (F) { fm = a.f_mean[c]; fq = a.f_m2[c]; }
+            accumulate_cell<WAIC, PRED, F>(a, a.f[c], a.mu[c], a.y[c], lse, lm, l2, ps, fm, fq, d, first);
+            if (WAIC) { a.lse[c] = lse; a.ll_mean[c] = lm; a.ll_m2[c] = l2; }
+            if (PRED) a.p_sum[c] = ps;
+            if (F) { a.f_mean[c] = fm; a.f_m2[c] = fq; }
+            diag_scalar<FD>(g, g.f_hm, g.f_h2, g.f_bs, g.f_bmm, g.f_bm2, c, a.f[c]);
+        }
+    }
+    const int64_t tb = a.n + 2 * a.m;
+    for (int64_t i = tid; i < tb; i += stride) {
+        const double x = i < a.n ? a.theta[i] : a.beta[i - a.n];
+        double mean = a.tb_mean[i], m2 = a.tb_m2[i];
+        welford(mean, m2, x, d);
+        a.tb_mean[i] = mean; a.tb_m2[i] = m2;
+        diag_scalar<DIAG>(g, g.t_hm, g.t_h2, g.t_bs, g.t_bmm, g.t_bm2, i, x);
+    }
+}
+
+// the same pass with the GPIRT_SUM_DIAG accumulators
+template <bool WAIC, bool PRED, bool F>
+__global__ __launch_bounds__(SUM_THREADS) void summary_diag_accumulate_kernel(SumArgs a, DiagArgs g, int64_t draw)
+{
+    accumulate_body<WAIC, PRED, F, true>(a, g, draw);
+}
+
 // out[i] = src[i] * scale + shift, NaN where the response is missing (y != nullptr)
 __global__ __launch_bounds__(SUM_THREADS) void summary_finish_kernel(const double* __restrict__ src, const double* __restrict__ y,
                                                                      int64_t count, double scale, double shift,
@@ -211,9 +350,60 @@ void launch_acc(hipStream_t st, const SumArgs& a, int64_t draw)
                        draw);
 }
 
+template <bool W, bool P, bool F>
+void launch_diag_acc(hipStream_t st, const SumArgs& a, const DiagArgs& g, int64_t draw)
+{
+    const int64_t work = (W || P || F) ? (a.cells >> 1) : a.n + 2 * a.m;
+    const int64_t tb = a.n + 2 * a.m;
+    hipLaunchKernelGGL((summary_diag_accumulate_kernel<W, P, F>), dim3(grid_cap(work > tb ? work : tb)), dim3(SUM_THREADS), 0,
+                       st, a, g, draw);
+}
+
+int64_t isqrt(int64_t S)
+{
+    int64_t b = (int64_t)sqrt((double)S);
+    while (b > 1 && b * b > S) --b;
+    while ((b + 1) * (b + 1) <= S) ++b;
+    return b < 1 ? 1 : b;
+}
+
+// DiagArgs of draw d (1-based) of a chain of S planned draws
+DiagArgs diag_step(const SummaryState* s, int64_t d)
+{
+    DiagArgs g{};
+    const int64_t S = s->planned, hN = S / 2, b = isqrt(S), nb = S / b;
+    if (d <= hN) { g.half = 1; g.hd = (double)d; }
+    else if (d > S - hN) { g.half = 2; g.hd = (double)(d - (S - hN)); }
+    if (d <= nb * b) { g.batch = d % b == 0 ? 2 : 1; g.bd = (double)b; g.bk = (double)(d / b); }
+    const int h0 = g.half == 2 ? DG_H2_MEAN : DG_H1_MEAN, h1 = g.half == 2 ? DG_H2_M2 : DG_H1_M2;
+    g.t_hm = s->dtb[h0]; g.t_h2 = s->dtb[h1]; g.t_bs = s->dtb[DG_BSUM]; g.t_bmm = s->dtb[DG_BM_MEAN]; g.t_bm2 = s->dtb[DG_BM_M2];
+    g.f_hm = s->df[h0]; g.f_h2 = s->df[h1]; g.f_bs = s->df[DG_BSUM]; g.f_bmm = s->df[DG_BM_MEAN]; g.f_bm2 = s->df[DG_BM_M2];
+    return g;
+}
+
 }  // namespace
 
-int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts)
+SumLayout summary_layout(int64_t n, int64_t m, int parts)
+{
+    SumLayout L;
+    const int64_t cells = n * m, tb = n + 2 * m;
+    int64_t at = SUM_HEADER_WORDS;
+    auto take = [&](int64_t count) { const int64_t o = at; at += (count + 1) & ~(int64_t)1; return o; };
+    L.tb_mean = take(tb); L.tb_m2 = take(tb);
+    if (parts & GPIRT_SUM_WAIC) { L.lse = take(cells); L.ll_mean = take(cells); L.ll_m2 = take(cells); L.y = take(cells); }
+    if (parts & GPIRT_SUM_PRED) L.p_sum = take(cells);
+    if (parts & GPIRT_SUM_F) { L.f_mean = take(cells); L.f_m2 = take(cells); }
+    L.irf = take((int64_t)GPIRT_NGRID * m);
+    if (parts & GPIRT_SUM_DIAG) {
+        for (int k = 0; k < 7; ++k) L.dtb[k] = take(tb);
+        if (parts & GPIRT_SUM_F)
+            for (int k = 0; k < 7; ++k) L.df[k] = take(cells);
+    }
+    L.total = at;
+    return L;
+}
+
+int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t planned)
 {
     const size_t cells = (size_t)(n * m), tb = (size_t)(n + 2 * m);
     auto get = [&](double** p, size_t count) -> int {
@@ -222,11 +412,15 @@ int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts)
         GP_HIP(hipMemset(*p, 0, count * sizeof(double)));
         return 0;
     };
-    s->n = n; s->m = m; s->parts = parts; s->draws = 0;
-    GP_TRY(get(&s->tb_mean, tb)); GP_TRY(get(&s->tb_m2, tb));
-    if (parts & GPIRT_SUM_WAIC) { GP_TRY(get(&s->lse, cells)); GP_TRY(get(&s->ll_mean, cells)); GP_TRY(get(&s->ll_m2, cells)); }
-    if (parts & GPIRT_SUM_PRED) GP_TRY(get(&s->p_sum, cells));
-    if (parts & GPIRT_SUM_F) { GP_TRY(get(&s->f_mean, cells)); GP_TRY(get(&s->f_m2, cells)); }
+    s->n = n; s->m = m; s->parts = parts; s->draws = 0; s->planned = planned;
+    s->lay = summary_layout(n, m, parts);
+    GP_TRY(get(&s->block, (size_t)s->lay.total));
+    auto at = [&](int64_t off) { return off < 0 ? nullptr : s->block + off; };
+    const SumLayout& L = s->lay;
+    s->tb_mean = at(L.tb_mean); s->tb_m2 = at(L.tb_m2);
+    s->lse = at(L.lse); s->ll_mean = at(L.ll_mean); s->ll_m2 = at(L.ll_m2); s->y = at(L.y);
+    s->p_sum = at(L.p_sum); s->f_mean = at(L.f_mean); s->f_m2 = at(L.f_m2); s->irf = at(L.irf);
+    for (int k = 0; k < 7; ++k) { s->dtb[k] = at(L.dtb[k]); s->df[k] = at(L.df[k]); }
     GP_TRY(get(&s->out, cells > tb ? cells : tb));
     GP_TRY(get(&s->part, (size_t)SUM_TOTAL_BLOCKS * 4));
     GP_TRY(get(&s->tot, GPIRT_SUM_NTOTALS));
@@ -246,6 +440,11 @@ int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* the
         set_error("summary: f, mu and y must be 16-byte aligned");
         return GPIRT_E_ARG;
     }
+    const bool diag = s->parts & GPIRT_SUM_DIAG;
+    if (diag && s->draws >= s->planned) {
+        set_error("summary: all %lld planned draws are in (gpirt_sampler_summary_enable_planned)", (long long)s->planned);
+        return GPIRT_E_ARG;
+    }
     SumArgs a{};
     a.f = f; a.mu = mu; a.y = y; a.theta = theta; a.beta = beta;
     a.lse = s->lse; a.ll_mean = s->ll_mean; a.ll_m2 = s->ll_m2; a.p_sum = s->p_sum; a.f_mean = s->f_mean; a.f_m2 = s->f_m2;
@@ -253,6 +452,24 @@ int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* the
     a.cells = s->n * s->m; a.n = s->n; a.m = s->m;
     const int64_t draw = s->draws + 1;
     const bool w = s->parts & GPIRT_SUM_WAIC, p = s->parts & GPIRT_SUM_PRED, fo = s->parts & GPIRT_SUM_F;
+    if (draw == 1 && s->y)       // the missing cells travel with the block (gpirt_chains_combine masks by them)
+        GP_HIP(hipMemcpyAsync(s->y, y, sizeof(double) * (size_t)(s->n * s->m), hipMemcpyDeviceToDevice, st));
+    if (diag) {
+        const DiagArgs g = diag_step(s, draw);
+        switch ((w ? 4 : 0) | (p ? 2 : 0) | (fo ? 1 : 0)) {
+            case 0: launch_diag_acc<false, false, false>(st, a, g, draw); break;
+            case 1: launch_diag_acc<false, false, true>(st, a, g, draw); break;
+            case 2: launch_diag_acc<false, true, false>(st, a, g, draw); break;
+            case 3: launch_diag_acc<false, true, true>(st, a, g, draw); break;
+            case 4: launch_diag_acc<true, false, false>(st, a, g, draw); break;
+            case 5: launch_diag_acc<true, false, true>(st, a, g, draw); break;
+            case 6: launch_diag_acc<true, true, false>(st, a, g, draw); break;
+            default: launch_diag_acc<true, true, true>(st, a, g, draw); break;
+        }
+        GP_HIP(hipGetLastError());
+        s->draws = draw;
+        return 0;
+    }
     switch ((w ? 4 : 0) | (p ? 2 : 0) | (fo ? 1 : 0)) {
         case 0: launch_acc<false, false, false>(st, a, draw); break;
         case 1: launch_acc<false, false, true>(st, a, draw); break;
@@ -265,6 +482,17 @@ int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* the
     }
     GP_HIP(hipGetLastError());
     s->draws = draw;
+    return 0;
+}
+
+int summary_seal(hipStream_t st, SummaryState* s, const double* irf_sum, int64_t N)
+{
+    int64_t hdr[SUM_HEADER_WORDS];
+    hdr[0] = s->n; hdr[1] = s->m; hdr[2] = s->parts; hdr[3] = s->planned; hdr[4] = s->draws; hdr[5] = SUM_LAYOUT_VERSION;
+    hdr[6] = N; hdr[7] = 0;
+    GP_HIP(hipMemcpyAsync(s->block, hdr, SUM_HEADER_WORDS * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    GP_HIP(hipMemcpyAsync(s->irf, irf_sum, sizeof(double) * (size_t)(N * s->m), hipMemcpyDeviceToDevice, st));
+    GP_HIP(hipStreamSynchronize(st));       // hdr is on this stack
     return 0;
 }
 
@@ -326,6 +554,331 @@ int launch_summary_totals(hipStream_t st, const SummaryState* s, const double* y
         GP_HIP(hipGetLastError());
         hipLaunchKernelGGL(summary_reduce_kernel, dim3(1), dim3(SUM_THREADS), 0, st, s->part, SUM_TOTAL_BLOCKS, pass, S, s->tot);
         GP_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// ---- several chains: gpirt_chains_combine ----------------------------------------------------------------------------
+namespace {
+
+struct CombArgs {
+    const double* const* st;          // C state blocks (SumLayout)
+    const double* sgn;                // C signs: -1 reflects the chain's theta and beta slope means
+    SumLayout L;
+    int C, parts;
+    int64_t n, tb, cells;
+    double S, b, a, N;                // draws per chain, batch size and count, half length
+    double *tb_mean, *tb_m2, *lse, *ll_mean, *ll_m2, *p_sum, *f_mean, *f_m2;    // the pooled accumulators (draws C S)
+    double *rhat, *ess, *mcse;        // tb values, then (DIAG and F) the cells
+};
+
+// (mean, M2) of cnt draws += (mc, m2c) of S more: Chan et al.'s pairwise update, the first chain taken as it is
+__device__ __forceinline__ void chan(double& mean, double& m2, double& cnt, double mc, double m2c, double S)
+{
+    if (cnt == 0.0) { mean = mc; m2 = m2c; cnt = S; return; }
+    const double nn = cnt + S, delta = mc - mean;
+    mean += delta * (S / nn);
+    m2 += m2c + delta * delta * (cnt * S / nn);
+    cnt = nn;
+}
+
+// split-R-hat, batch-means ESS and MCSE of one value (include/gpirt_hip.h GPIRT_SUM_DIAG), chains in order
+__device__ __forceinline__ void diag_of(const CombArgs& a, const int64_t* off, int64_t m2off, int64_t i, bool flip, double& rhat,
+                                        double& ess, double& mcse)
+{
+    double hc = 0.0, hmean = 0.0, hss = 0.0, w = 0.0, lam = 0.0, sig = 0.0;
+    for (int c = 0; c < a.C; ++c) {
+        const double* base = a.st[c];
+        const double sg = flip ? a.sgn[c] : 1.0;
+        hc += 1.0; welford(hmean, hss, sg * base[off[DG_H1_MEAN] + i], hc);
+        hc += 1.0; welford(hmean, hss, sg * base[off[DG_H2_MEAN] + i], hc);
+        w += base[off[DG_H1_M2] + i] / (a.N - 1.0) + base[off[DG_H2_M2] + i] / (a.N - 1.0);
+        lam += base[m2off + i] / (a.S - 1.0);
+        sig += base[off[DG_BM_M2] + i] * (a.b / (a.a - 1.0));
+    }
+    const double M = 2.0 * a.C, B = a.N / (M - 1.0) * hss, W = w / M;
+    const double varp = (a.N - 1.0) / a.N * W + B / a.N;
+    if (a.S < 4.0) rhat = (double)NAN;
+    else if (W > 0.0) rhat = sqrt(varp / W);
+    else rhat = B > 0.0 ? (double)INFINITY : (double)NAN;
+    if (a.a < 2.0 || a.S < 2.0) { ess = (double)NAN; mcse = (double)NAN; return; }
+    const double CS = a.C * a.S, lm = lam / a.C, sm = sig / a.C;
+    ess = CS * lm / sm;
+    mcse = sqrt(sm / CS);
+}
+
+template <bool DIAG>
+__global__ __launch_bounds__(SUM_THREADS) void chains_combine_kernel(CombArgs a)
+{
+    const bool anycell = a.parts & (GPIRT_SUM_WAIC | GPIRT_SUM_PRED | GPIRT_SUM_F);
+    const int64_t total = a.tb + (anycell ? a.cells : 0);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < a.tb) {
+            const bool flip = i < a.n || ((i - a.n) & 1);          // theta, and row 1 (the slope) of the 2 x m beta
+            double mean = 0.0, m2 = 0.0, cnt = 0.0;
+            for (int c = 0; c < a.C; ++c) {
+                const double* base = a.st[c];
+                chan(mean, m2, cnt, (flip ? a.sgn[c] : 1.0) * base[a.L.tb_mean + i], base[a.L.tb_m2 + i], a.S);
+            }
+            a.tb_mean[i] = mean; a.tb_m2[i] = m2;
+            if (DIAG) diag_of(a, a.L.dtb, a.L.tb_m2, i, flip, a.rhat[i], a.ess[i], a.mcse[i]);
+            continue;
+        }
+        const int64_t q = i - a.tb;
+        if (a.parts & GPIRT_SUM_WAIC) {
+            double lse = 0.0, mean = 0.0, m2 = 0.0, cnt = 0.0;
+            for (int c = 0; c < a.C; ++c) {
+                const double* base = a.st[c];
+                lse = logaddexp(lse, base[a.L.lse + q], c == 0);
+                chan(mean, m2, cnt, base[a.L.ll_mean + q], base[a.L.ll_m2 + q], a.S);
+            }
+            a.lse[q] = lse; a.ll_mean[q] = mean; a.ll_m2[q] = m2;
+        }
+        if (a.parts & GPIRT_SUM_PRED) {
+            double ps = 0.0;
+            for (int c = 0; c < a.C; ++c) ps += a.st[c][a.L.p_sum + q];
+            a.p_sum[q] = ps;
+        }
+        if (a.parts & GPIRT_SUM_F) {
+            double mean = 0.0, m2 = 0.0, cnt = 0.0;
+            for (int c = 0; c < a.C; ++c) chan(mean, m2, cnt, a.st[c][a.L.f_mean + q], a.st[c][a.L.f_m2 + q], a.S);
+            a.f_mean[q] = mean; a.f_m2[q] = m2;
+            if (DIAG) diag_of(a, a.L.df, a.L.f_m2, q, false, a.rhat[i], a.ess[i], a.mcse[i]);
+        }
+    }
+}
+
+// dots[c] = sum_i thetabar_c,i thetabar_0,i over the n theta means, one block per chain, in a fixed order
+__global__ __launch_bounds__(SUM_THREADS) void chains_dot_kernel(const double* const* st, int64_t off, int64_t n,
+                                                                  double* __restrict__ dots)
+{
+    __shared__ double sh[1][SUM_THREADS];
+    const double* x = st[blockIdx.x] + off;
+    const double* x0 = st[0] + off;
+    double v[1] = { 0.0 };
+    for (int64_t i = threadIdx.x; i < n; i += SUM_THREADS) v[0] += x[i] * x0[i];
+    block_sum<1>(v, sh);
+    if (threadIdx.x == 0) dots[blockIdx.x] = v[0];
+}
+
+// the summed IRF sums, a reflected chain's reversed along the grid (k -> N - 1 - k)
+__global__ __launch_bounds__(SUM_THREADS) void chains_irf_kernel(const double* const* st, const double* __restrict__ sgn, int C,
+                                                                  int64_t off, int64_t N, int64_t m, double* __restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N * m; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = i % N, j = i / N;
+        double v = 0.0;
+        for (int c = 0; c < C; ++c) v += st[c][off + (sgn[c] < 0.0 ? (N - 1 - k) + j * N : i)];
+        out[i] = v;
+    }
+}
+
+constexpr int DG_SCAL_BLOCKS = 256;
+
+// per-block scalars (GPIRT_DIAG_*) of a range of values: partials [max rhat, min ess, # rhat > 1.01, # NaN rhat, # NaN ess]
+__global__ __launch_bounds__(SUM_THREADS) void diag_scalars_kernel(const double* __restrict__ rhat, const double* __restrict__ ess,
+                                                                   int64_t count, int fold, double* __restrict__ part)
+{
+    __shared__ double sh[GPIRT_DIAG_NSCALARS][SUM_THREADS];
+    double v[GPIRT_DIAG_NSCALARS] = { -(double)INFINITY, (double)INFINITY, 0.0, 0.0, 0.0 };
+    if (fold) {                                           // one block: the partials of the first pass
+        for (int64_t b = threadIdx.x; b < count; b += SUM_THREADS) {
+            const double* p = part + b * GPIRT_DIAG_NSCALARS;
+            v[0] = fmax(v[0], p[0]); v[1] = fmin(v[1], p[1]); v[2] += p[2]; v[3] += p[3]; v[4] += p[4];
+        }
+    } else {
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+            const double r = rhat[i], e = ess[i];
+            if (r != r) v[3] += 1.0; else { v[0] = fmax(v[0], r); if (r > 1.01) v[2] += 1.0; }
+            if (e != e) v[4] += 1.0; else v[1] = fmin(v[1], e);
+        }
+    }
+    const int t = threadIdx.x;
+    for (int k = 0; k < GPIRT_DIAG_NSCALARS; ++k) sh[k][t] = v[k];
+    __syncthreads();
+    for (int w = SUM_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            sh[0][t] = fmax(sh[0][t], sh[0][t + w]);
+            sh[1][t] = fmin(sh[1][t], sh[1][t + w]);
+            for (int k = 2; k < GPIRT_DIAG_NSCALARS; ++k) sh[k][t] += sh[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        double* o = fold ? part + (int64_t)DG_SCAL_BLOCKS * GPIRT_DIAG_NSCALARS : part + (int64_t)blockIdx.x * GPIRT_DIAG_NSCALARS;
+        for (int k = 0; k < GPIRT_DIAG_NSCALARS; ++k) o[k] = sh[k][0];
+    }
+}
+
+// the pooled outputs of gpirt_summary: the checks of gpirt_mcmc_summary with the parts the states carry
+int pooled_args_ok(const gpirt_summary* p, int have)
+{
+    const int parts = p->parts;
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0 && p->reserved == 0);
+    GP_ARG((parts & ~have) == 0);
+    GP_ARG(!((p->h_p_yes) && !(parts & GPIRT_SUM_PRED)));
+    GP_ARG(!((p->h_lppd || p->h_p_waic) && !(parts & GPIRT_SUM_WAIC)));
+    GP_ARG(!((p->h_f_mean || p->h_f_var) && !(parts & GPIRT_SUM_F)));
+    return 0;
+}
+
+struct DevFree {
+    std::vector<void*> p;
+    ~DevFree() { for (void* q : p) hipFree(q); }
+};
+
+}  // namespace
+
+int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const int* signs, int align, double* h_irfs,
+                   gpirt_summary* pooled, gpirt_diag* diag)
+{
+    GP_ARG(h && C >= 1 && d_states);
+    hipStream_t st = h->stream;
+    std::vector<int64_t> hd((size_t)C * SUM_HEADER_WORDS);
+    for (int c = 0; c < C; ++c) {
+        GP_ARG(d_states[c] && ((uintptr_t)d_states[c] & 15) == 0);
+        GP_HIP(hipMemcpyAsync(&hd[(size_t)c * SUM_HEADER_WORDS], d_states[c], SUM_HEADER_WORDS * sizeof(int64_t),
+                              hipMemcpyDeviceToHost, st));
+    }
+    GP_HIP(hipStreamSynchronize(st));
+    const int64_t* h0 = hd.data();
+    for (int c = 1; c < C; ++c)
+        if (memcmp(h0, &hd[(size_t)c * SUM_HEADER_WORDS], SUM_HEADER_WORDS * sizeof(int64_t)) != 0) {
+            set_error("chain %d's state header (n, m, parts, planned draws, draws, layout) differs from chain 0's", c);
+            return GPIRT_E_ARG;
+        }
+    const int64_t n = h0[0], m = h0[1], planned = h0[3], draws = h0[4];
+    const int parts = (int)h0[2];
+    if (h0[5] != SUM_LAYOUT_VERSION || h0[6] != GPIRT_NGRID || n <= 0 || m <= 0 || draws < 0 ||
+        (parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) != 0 ||
+        !(parts & GPIRT_SUM_THETA_BETA)) {
+        set_error("not a summary state block of this library (layout %lld)", (long long)h0[5]);
+        return GPIRT_E_ARG;
+    }
+    const bool dg = parts & GPIRT_SUM_DIAG, fo = parts & GPIRT_SUM_F;
+    if (dg && draws != planned) {
+        set_error("diagnostics need all %lld planned draws (%lld are in)", (long long)planned, (long long)draws);
+        return GPIRT_E_ARG;
+    }
+    if (pooled) GP_TRY(pooled_args_ok(pooled, parts & ~GPIRT_SUM_DIAG));
+    if (diag) {
+        GP_ARG(dg);
+        GP_ARG(diag->reserved[0] == 0 && diag->reserved[1] == 0 && diag->reserved[2] == 0 && diag->reserved[3] == 0);
+        GP_ARG(fo || !(diag->h_f_rhat || diag->h_f_ess || diag->h_f_mcse));
+    }
+    const SumLayout L = summary_layout(n, m, parts);
+    const int64_t cells = n * m, tb = n + 2 * m, N = GPIRT_NGRID;
+    std::vector<double> sg((size_t)C, 1.0);
+    DevFree tmp;
+    double* d_ptrs = nullptr;                    // C block pointers, C signs, C dots
+    GP_HIP(hipMalloc(&d_ptrs, sizeof(double) * 3 * (size_t)C));
+    tmp.p.push_back(d_ptrs);
+    const double* const* d_st = reinterpret_cast<const double* const*>(d_ptrs);
+    double* d_sg = d_ptrs + C;
+    double* d_dot = d_ptrs + 2 * C;
+    GP_HIP(hipMemcpyAsync(d_ptrs, d_states, sizeof(void*) * (size_t)C, hipMemcpyHostToDevice, st));
+    if (signs) {
+        for (int c = 0; c < C; ++c) {
+            GP_ARG(signs[c] == 1 || signs[c] == -1);
+            sg[(size_t)c] = (double)signs[c];
+        }
+    } else if (align && C > 1) {
+        hipLaunchKernelGGL(chains_dot_kernel, dim3(C), dim3(SUM_THREADS), 0, st, d_st, L.tb_mean, n, d_dot);
+        GP_HIP(hipGetLastError());
+        std::vector<double> dots((size_t)C);
+        GP_HIP(hipMemcpyAsync(dots.data(), d_dot, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, st));
+        GP_HIP(hipStreamSynchronize(st));
+        for (int c = 1; c < C; ++c) sg[(size_t)c] = dots[(size_t)c] < 0.0 ? -1.0 : 1.0;
+    }
+    GP_HIP(hipMemcpyAsync(d_sg, sg.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, st));
+
+    SummaryState P;                              // the pooled accumulators: a chain of C S draws
+    struct Free { SummaryState* s; ~Free() { summary_free(s); } } pfree{ &P };
+    GP_TRY(summary_alloc(&P, n, m, parts & ~GPIRT_SUM_DIAG));
+    P.draws = (int64_t)C * draws;
+    const int64_t nd = dg ? tb + (fo ? cells : 0) : 0;
+    double* d_diag = nullptr;
+    if (dg) {
+        GP_HIP(hipMalloc(&d_diag, sizeof(double) * (size_t)(3 * nd + (DG_SCAL_BLOCKS + 1) * GPIRT_DIAG_NSCALARS)));
+        tmp.p.push_back(d_diag);
+    }
+    CombArgs a{};
+    a.st = d_st; a.sgn = d_sg; a.L = L; a.C = C; a.parts = parts; a.n = n; a.tb = tb; a.cells = cells;
+    const int64_t S = dg ? planned : draws, b = dg ? isqrt(planned) : 1;
+    a.S = (double)S; a.b = (double)b; a.a = (double)(S / b); a.N = (double)(S / 2);
+    a.tb_mean = P.tb_mean; a.tb_m2 = P.tb_m2; a.lse = P.lse; a.ll_mean = P.ll_mean; a.ll_m2 = P.ll_m2; a.p_sum = P.p_sum;
+    a.f_mean = P.f_mean; a.f_m2 = P.f_m2;
+    if (dg) { a.rhat = d_diag; a.ess = d_diag + nd; a.mcse = d_diag + 2 * nd; }
+    const bool anycell = parts & (GPIRT_SUM_WAIC | GPIRT_SUM_PRED | GPIRT_SUM_F);
+    const int64_t work = tb + (anycell ? cells : 0);
+    if (dg) hipLaunchKernelGGL(chains_combine_kernel<true>, dim3(grid_cap(work)), dim3(SUM_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(chains_combine_kernel<false>, dim3(grid_cap(work)), dim3(SUM_THREADS), 0, st, a);
+    GP_HIP(hipGetLastError());
+
+    const double* y0 = L.y >= 0 ? static_cast<const double*>(d_states[0]) + L.y : nullptr;
+    auto fetch = [&](const char* name, double* h_out) -> int {
+        if (!h_out) return 0;
+        double* d = nullptr; int64_t cnt = 0;
+        GP_TRY(launch_summary_finish(st, &P, name, y0, &d, &cnt));
+        GP_HIP(hipMemcpyAsync(h_out, d, sizeof(double) * (size_t)cnt, hipMemcpyDeviceToHost, st));
+        GP_HIP(hipStreamSynchronize(st));          // P.out is reused by the next array
+        return 0;
+    };
+    if (pooled) {
+        for (int k = 0; k < GPIRT_SUM_NTOTALS; ++k) pooled->totals[k] = (double)NAN;
+        pooled->totals[GPIRT_SUM_T_DRAWS] = (double)P.draws;
+        GP_TRY(fetch("p_yes", pooled->h_p_yes)); GP_TRY(fetch("lppd", pooled->h_lppd)); GP_TRY(fetch("p_waic", pooled->h_p_waic));
+        GP_TRY(fetch("f_mean", pooled->h_f_mean)); GP_TRY(fetch("f_var", pooled->h_f_var));
+        GP_TRY(fetch("theta_mean", pooled->h_theta_mean)); GP_TRY(fetch("theta_var", pooled->h_theta_var));
+        GP_TRY(fetch("beta_mean", pooled->h_beta_mean)); GP_TRY(fetch("beta_var", pooled->h_beta_var));
+        if (pooled->parts & GPIRT_SUM_WAIC) {
+            GP_TRY(launch_summary_totals(st, &P, y0));
+            GP_HIP(hipMemcpyAsync(pooled->totals, P.tot, sizeof(double) * GPIRT_SUM_NTOTALS, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (diag) {
+        const struct { double* p; int64_t at, cnt; } outs[] = {
+            { diag->h_theta_rhat, 0, n }, { diag->h_theta_ess, nd, n }, { diag->h_theta_mcse, 2 * nd, n },
+            { diag->h_beta_rhat, n, 2 * m }, { diag->h_beta_ess, nd + n, 2 * m }, { diag->h_beta_mcse, 2 * nd + n, 2 * m },
+            { diag->h_f_rhat, tb, cells }, { diag->h_f_ess, nd + tb, cells }, { diag->h_f_mcse, 2 * nd + tb, cells },
+        };
+        for (const auto& o : outs)
+            if (o.p) GP_HIP(hipMemcpyAsync(o.p, d_diag + o.at, sizeof(double) * (size_t)o.cnt, hipMemcpyDeviceToHost, st));
+        double* part = d_diag + 3 * nd;
+        const int64_t range[GPIRT_DIAG_NBLOCKS][2] = { { 0, n }, { n, 2 * m }, { tb, fo ? cells : 0 } };
+        for (int blk = 0; blk < GPIRT_DIAG_NBLOCKS; ++blk) {
+            double* sc = diag->scalars[blk];
+            const int64_t cnt = range[blk][1];
+            if (cnt == 0) {
+                sc[GPIRT_DIAG_MAX_RHAT] = sc[GPIRT_DIAG_MIN_ESS] = (double)NAN;
+                sc[GPIRT_DIAG_N_RHAT_HIGH] = sc[GPIRT_DIAG_N_RHAT_NAN] = sc[GPIRT_DIAG_N_ESS_NAN] = 0.0;
+                continue;
+            }
+            const double* r = d_diag + range[blk][0];
+            hipLaunchKernelGGL(diag_scalars_kernel, dim3(DG_SCAL_BLOCKS), dim3(SUM_THREADS), 0, st, r, r + nd, cnt, 0, part);
+            hipLaunchKernelGGL(diag_scalars_kernel, dim3(1), dim3(SUM_THREADS), 0, st, r, r + nd, (int64_t)DG_SCAL_BLOCKS, 1, part);
+            GP_HIP(hipGetLastError());
+            GP_HIP(hipMemcpyAsync(sc, part + (int64_t)DG_SCAL_BLOCKS * GPIRT_DIAG_NSCALARS, sizeof(double) * GPIRT_DIAG_NSCALARS,
+                                  hipMemcpyDeviceToHost, st));
+            GP_HIP(hipStreamSynchronize(st));
+            if (sc[GPIRT_DIAG_N_RHAT_NAN] == (double)cnt) sc[GPIRT_DIAG_MAX_RHAT] = (double)NAN;
+            if (sc[GPIRT_DIAG_N_ESS_NAN] == (double)cnt) sc[GPIRT_DIAG_MIN_ESS] = (double)NAN;
+        }
+        if (diag->reflected)
+            for (int c = 0; c < C; ++c) diag->reflected[c] = sg[(size_t)c] < 0.0 ? 1 : 0;
+    }
+    if (h_irfs) {
+        double* d_irf = nullptr;                 // N x m: more than P.out holds when n < N
+        GP_HIP(hipMalloc(&d_irf, sizeof(double) * (size_t)(N * m)));
+        tmp.p.push_back(d_irf);
+        hipLaunchKernelGGL(chains_irf_kernel, dim3(grid_cap(N * m)), dim3(SUM_THREADS), 0, st, d_st, d_sg, C, L.irf, N, m, d_irf);
+        GP_HIP(hipGetLastError());
+        GP_HIP(hipMemcpyAsync(h_irfs, d_irf, sizeof(double) * (size_t)(N * m), hipMemcpyDeviceToHost, st));
+    }
+    GP_HIP(hipStreamSynchronize(st));
+    if (h_irfs) {
+        const double inv = 1.0 / ((double)C * (double)S);
+        for (int64_t i = 0; i < N * m; ++i) h_irfs[i] = 1.0 / (1.0 + exp(-(h_irfs[i] * inv)));
     }
     return 0;
 }

@@ -43,7 +43,7 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
 def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_prior_means=None,
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
-              progress=False, preset=None, summaries=None, store_draws=True):
+              progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -61,6 +61,12 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       the arrays of those parts (theta / beta moments always) and "totals" (a dict; WAIC's, with "waic").
     store_draws: True, False, or a subset of ("theta", "beta", "f"); a draw that is not stored comes back as None.  With
       summaries and no stored f a long chain at 8192 x 1024 needs O(n m) host memory instead of n m 8 bytes per iteration.
+    chains: C chains one after another (gpirt_mcmc_chains; the item RNG only, chain c seeded gpirt_chain_seed(seed, c)).
+      The draws come back stacked per chain (theta C x (S+1) x n, beta C x 2 x m x (S+1), f C x n x m x (S+1)), "summary"
+      is pooled over the chains and "diagnostics" holds split-R-hat, the batch-means ESS and the MCSE of every theta, beta
+      (and with "f" in summaries, f) value, their per-block scalars and the chains reflected by the theta -> -theta
+      alignment (align=False: none).  theta_init may be (C, n); by default chain 0 starts at RStream(seed).rnorm(n) as
+      today and chain c at RStream(chain_seed(seed, c) & 0xFFFFFFFF).rnorm(n).  chains=None: one chain, as before.
     """
     from .ops import RStream
 
@@ -79,6 +85,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         rng = "item"
     elif preset is not None:
         raise ValueError(f"unknown preset {preset!r}")
+    if chains is not None:
+        if rng == "reference":
+            raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
+        return _mcmc_chains(y, int(chains), sample_iterations, burn_iterations, pm, ps, st, theta_init, seed, preset,
+                            theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws, align)
     rs = None
     if rng == "reference":
         rs = rstream if rstream is not None else RStream(seed)
@@ -91,14 +102,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     if theta0.shape != (n,):
         raise ValueError("theta_init must have one value per respondent")
     S, B = int(sample_iterations), int(burn_iterations)
-    if store_draws is True:
-        keep = {"theta", "beta", "f"}
-    elif store_draws is False or store_draws is None:
-        keep = set()
-    else:
-        keep = {store_draws} if isinstance(store_draws, str) else set(store_draws)
-        if not keep <= {"theta", "beta", "f"}:
-            raise ValueError("store_draws must be True, False or a subset of ('theta', 'beta', 'f')")
+    keep = _keep(store_draws)
     th = np.empty((S + 1, n), order="F") if "theta" in keep else None
     be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
     ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
@@ -139,6 +143,77 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     if summaries is not None:
         out["summary"] = dict(arrays, totals=_totals(sm.totals))
     return out
+
+
+def _keep(store_draws) -> set:
+    if store_draws is True:
+        return {"theta", "beta", "f"}
+    if store_draws is False or store_draws is None:
+        return set()
+    keep = {store_draws} if isinstance(store_draws, str) else set(store_draws)
+    if not keep <= {"theta", "beta", "f"}:
+        raise ValueError("store_draws must be True, False or a subset of ('theta', 'beta', 'f')")
+    return keep
+
+
+def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device,
+                 progress, summaries, store_draws, align):
+    """gpirtMCMC(chains=C): gpirt_mcmc_chains (include/gpirt_hip.h)."""
+    from . import chains as CH
+    lib = _lib.load()
+    n, m = y.shape
+    S, B = int(S), int(B)
+    if nc < 1:
+        raise ValueError("chains must be >= 1")
+    if theta_init is None:
+        th0 = CH.default_inits(n, nc, seed)
+    else:
+        t = np.asarray(theta_init, dtype=np.float64)
+        th0 = np.broadcast_to(t, (nc, n)) if t.shape == (n,) else t
+        if th0.shape != (nc, n):
+            raise ValueError("theta_init must be (n,) or (chains, n)")
+    th0 = np.ascontiguousarray(th0)                                  # n x C column-major: chain c's column at c n
+    keep = _keep(store_draws)
+    # chain-major blocks, each in gpirt_mcmc's layout; the returned arrays are views with the chain first
+    th = np.empty((nc, n, S + 1)) if "theta" in keep else None
+    be = np.empty((nc, S + 1, m, 2)) if "beta" in keep else None
+    ff = np.empty((nc, S + 1, m, n)) if "f" in keep else None
+    irf = np.empty((NGRID, m), order="F")
+    if preset == "fast":
+        o = _lib.fast_options()
+        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        o.device = -1 if device is None else int(device)
+    else:
+        o = _options("item", seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
+    parts = _lib.summary_parts(summaries if summaries is not None else 0) | _lib.SUM_THETA_BETA
+    sm = _lib.Summary()
+    sm.parts = parts
+    arrays = _summary_arrays(parts, n, m)
+    for k, a in arrays.items():
+        setattr(sm, "h_" + k, _ptr(a))
+    d, darr = CH.diag_struct(parts, n, m, nc)
+
+    def _tick(ctx, it, total):
+        if progress:
+            print("\r%6.3f %% complete" % (100.0 * it / max(total, 1)), end="", flush=True)
+        return 0
+
+    cb = _lib.TICK_FN(_tick)
+    opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
+    rc = lib.gpirt_mcmc_chains(_ptr(y), n, m, _ptr(th0), nc, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                               int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d))
+    if progress:
+        print("\r100.000 % complete")
+    if rc > 0:
+        raise RuntimeError("chol(): decomposition failed")
+    check(rc)
+    summary = dict(arrays)
+    if parts & _lib.SUM_WAIC:
+        summary["totals"] = _totals(sm.totals)
+    return dict(theta=th.transpose(0, 2, 1) if th is not None else None,
+                beta=be.transpose(0, 3, 2, 1) if be is not None else None,
+                f=ff.transpose(0, 3, 2, 1) if ff is not None else None,
+                IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr))
 
 
 def _summary_arrays(parts: int, n: int, m: int) -> dict:
@@ -351,10 +426,29 @@ class Sampler:
         return out
 
     # -- posterior summaries accumulated on the device (include/gpirt_hip.h gpirt_sampler_summary_*)
-    def summary_enable(self, parts):
-        """Allocate and zero the accumulators of `parts` (names or GPIRT_SUM_* bits; 0 / () frees them)."""
+    def summary_enable(self, parts, planned_draws=None):
+        """Allocate and zero the accumulators of `parts` (names or GPIRT_SUM_* bits; 0 / () frees them).  planned_draws: the
+        chain's draw count S, fixed now -- the only way to turn on GPIRT_SUM_DIAG (split-R-hat / ESS, gpirt_amd.chains)."""
         self._sum_parts = _lib.summary_parts(parts)
-        check(self.lib.gpirt_sampler_summary_enable(self._s, self._sum_parts))
+        if planned_draws is None:
+            check(self.lib.gpirt_sampler_summary_enable(self._s, self._sum_parts))
+        else:
+            check(self.lib.gpirt_sampler_summary_enable_planned(self._s, self._sum_parts, int(planned_draws)))
+
+    def summary_state(self):
+        """Torch view (float64, on the device) of the ONE block that holds every accumulator of the summaries, its header
+        and the IRF sum refreshed: what gpirt_amd.chains.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_summary_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<f8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
 
     def summary_accumulate(self):
         """Add the current state (after a sampling iteration's step) as one draw."""
@@ -374,7 +468,7 @@ class Sampler:
 
     def summary(self) -> dict:
         """Every array of the enabled parts, plus "totals" (with GPIRT_SUM_WAIC)."""
-        parts = getattr(self, "_sum_parts", 0)
+        parts = getattr(self, "_sum_parts", 0) & ~_lib.SUM_DIAG
         out = {k: self.summary_get(k) for k in _summary_arrays(parts, self.n, self.m)}
         if parts & _lib.SUM_WAIC:
             out["totals"] = self.summary_totals()

@@ -60,7 +60,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -354,6 +354,80 @@ int gpirt_mcmc_summary(const double* h_y, int64_t n, int64_t m, const double* h_
                        const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts,
                        gpirt_rstream_t rs, gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws,
                        double* h_beta_draws, double* h_f_draws, double* h_irfs, gpirt_summary* summary);
+
+/* ------------------------------------------------------ several chains, convergence diagnostics ------------- */
+/* GPIRT_SUM_DIAG: per theta (n), beta (2 x m) and, with GPIRT_SUM_F, f cell (n x m), the accumulators of split-R-hat and a
+ * batch-means ESS for a chain of S planned draws (gpirt_sampler_summary_enable_planned; the only way to turn it on):
+ * Welford moments of half 1 (draws 1..floor(S/2)) and half 2 (draws S-floor(S/2)+1..S; with S odd the middle draw is in
+ * neither), and of the means of a = floor(S/b) batches of b = floor(sqrt(S)) draws (draws 1..a b).  The ESS is the
+ * batch-means one, NOT the rank-normalised ESS of Vehtari et al. (2021): rank normalisation needs every draw.
+ * Split-R-hat (BDA3) over M = 2C half-chains of N = floor(S/2) draws: B = N/(M-1) sum_j (xbar_j - xbar)^2,
+ * W = mean_j s_j^2 (ddof 1), var+ = (N-1)/N W + B/N, Rhat = sqrt(var+ / W); W = 0 gives +inf if B > 0 and NaN otherwise,
+ * S < 4 gives NaN.  ESS = C S mean_c(lambda_c^2) / mean_c(sigma_c^2) with lambda_c^2 the chain's variance (ddof 1) and
+ * sigma_c^2 = b/(a-1) sum_k (Ybar_ck - Ybar_c)^2 (Ybar_c: the mean of the chain's batch means); MCSE of the pooled mean =
+ * sqrt(mean_c(sigma_c^2) / (C S)); a < 2 gives NaN. */
+#define GPIRT_SUM_DIAG       16
+/* chain c's GPIRT_RNG_ITEM seed: chain 0 uses seed; chain c >= 1 the splitmix64 finaliser of seed + c GAMMA:
+ * z = (z ^ (z >> 30)) M1; z = (z ^ (z >> 27)) M2; z ^ (z >> 31) */
+#define GPIRT_CHAIN_SEED_GAMMA 0x9E3779B97F4A7C15ULL
+#define GPIRT_CHAIN_SEED_M1    0xBF58476D1CE4E5B9ULL
+#define GPIRT_CHAIN_SEED_M2    0x94D049BB133111EBULL
+uint64_t gpirt_chain_seed(uint64_t seed, int c);
+
+/* per-block scalars of gpirt_diag: blocks theta, beta, f; NaN values are left out of the max / min and counted apart
+ * (a block whose every value is NaN, or f without GPIRT_SUM_F, has NaN max / min) */
+#define GPIRT_DIAG_THETA      0
+#define GPIRT_DIAG_BETA       1
+#define GPIRT_DIAG_F          2
+#define GPIRT_DIAG_NBLOCKS    3
+#define GPIRT_DIAG_MAX_RHAT   0
+#define GPIRT_DIAG_MIN_ESS    1
+#define GPIRT_DIAG_N_RHAT_HIGH 2   /* R-hat > 1.01 (+inf included) */
+#define GPIRT_DIAG_N_RHAT_NAN 3
+#define GPIRT_DIAG_N_ESS_NAN  4
+#define GPIRT_DIAG_NSCALARS   5
+typedef struct gpirt_diag {
+    double*  h_theta_rhat;    /* n; every pointer may be NULL (not wanted) */
+    double*  h_theta_ess;
+    double*  h_theta_mcse;
+    double*  h_beta_rhat;     /* 2 x m */
+    double*  h_beta_ess;
+    double*  h_beta_mcse;
+    double*  h_f_rhat;        /* n x m (needs GPIRT_SUM_F) */
+    double*  h_f_ess;
+    double*  h_f_mcse;
+    int*     reflected;       /* C flags: 1 where the chain was reflected (theta -> -theta) */
+    double   scalars[GPIRT_DIAG_NBLOCKS][GPIRT_DIAG_NSCALARS];
+    int64_t  reserved[4];     /* must be 0 */
+} gpirt_diag;
+
+/* The accumulators of a sampler's summaries live in ONE contiguous, 16-byte-aligned device block: a header of 8 int64
+ * (n, m, parts, planned S, draws done, layout version, grid points, 0), then the arrays, a copy of y (GPIRT_SUM_WAIC: the
+ * missing cells) and of the chain's IRF sum (1001 x m).  It can be copied anywhere -- another process, another GPU -- and
+ * combined there.  summary_state refreshes the header and the IRF sum and returns the block (valid until the summaries are
+ * enabled again or the sampler is destroyed). */
+int gpirt_sampler_summary_enable_planned(gpirt_sampler_t s, int parts, int64_t planned_draws);
+int gpirt_summary_state_bytes(int64_t n, int64_t m, int parts, int64_t* bytes);
+int gpirt_sampler_summary_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+/* Combine C chains' state blocks (device pointers on h's device; headers identical, GPIRT_SUM_DIAG states complete):
+ * pooled moments (Chan's formula in chain order), p_yes, lppd (logaddexp over chains), p_waic and the totals as
+ * gpirt_mcmc_summary fills `pooled` (pooled->parts: a subset of the states' parts); the diagnostics into diag (needs
+ * GPIRT_SUM_DIAG; may be NULL); the pooled IRFs plogis(sum_c irf_sum_c / (C S)) into h_irfs (1001 x m, may be NULL).
+ * Reflection theta -> -theta (a mode of the likelihood with symmetric priors): signs (C values of +1 / -1) forces it;
+ * signs == NULL and align != 0 reflects chain c >= 1 when sum_i thetabar_c,i thetabar_0,i < 0.  A reflected chain enters
+ * with its theta means and beta slope (row 1) means negated and its IRF sum reversed along the grid; f, p_yes and WAIC are
+ * unchanged.  No atomics: bit-identical from run to run. */
+int gpirt_chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
+                         double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag);
+/* C chains one after another on one handle (GPIRT_RNG_ITEM only), each the gpirt_mcmc_summary loop with
+ * seed = gpirt_chain_seed(opts->seed, c) and column c of h_theta0 (n x C), then gpirt_chains_combine with align.  The
+ * draws (each may be NULL) are chain-major: chain c's gpirt_mcmc layout at offset c (S+1) n, c 2 m (S+1), c n m (S+1).
+ * tick sees (c total + it, C total), total = S + B. */
+int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                      int sample_iterations, int burn_iterations, const double* h_prior_means,
+                      const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
