@@ -25,6 +25,13 @@ E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -
 SUM_THETA_BETA, SUM_F, SUM_PRED, SUM_WAIC = 1, 2, 4, 8
 SUM_PARTS = {"theta_beta": SUM_THETA_BETA, "f": SUM_F, "pred": SUM_PRED, "waic": SUM_WAIC}
 SUM_DIAG = 16                     # split-R-hat / batch-means ESS accumulators (Sampler.summary_enable(..., planned_draws=S))
+# quantiles (gpirt_amd.quantiles): theta histograms, IRF bands -- parts of a summary state, not of gpirt_summary.parts
+SUM_THETA_HIST, SUM_IRF_BAND = 32, 128
+SUM_PARTS.update(diag=SUM_DIAG, theta_hist=SUM_THETA_HIST, irf_band=SUM_IRF_BAND)     # "diag": with planned_draws only
+SUM_POOLED = SUM_THETA_BETA | SUM_F | SUM_PRED | SUM_WAIC      # the parts gpirt_summary (a pooled or one chain's) can carry
+IRF_BINS = 256
+QNT_SCALARS = ("max_rhat", "n_rhat_high", "n_rhat_nan", "theta_off_grid", "irf_nan", "draws", "irf_count_min",
+               "irf_count_max")
 SUM_TOTALS = ("lppd", "p_waic", "elpd_waic", "waic", "se_elpd_waic", "n_obs", "draws", "elpd_mean", "elpd_ss")
 
 
@@ -78,6 +85,15 @@ class Diag(C.Structure):
     _fields_ = [(f"h_{b}_{k}", C.POINTER(C.c_double)) for b in DIAG_BLOCKS for k in ("rhat", "ess", "mcse")] + [
         ("reflected", C.POINTER(C.c_int)), ("scalars", (C.c_double * len(DIAG_SCALARS)) * len(DIAG_BLOCKS)),
         ("reserved", C.c_int64 * 4)]
+
+
+class Quantiles(C.Structure):
+    """gpirt_quantiles (include/gpirt_hip.h): the probabilities, a host pointer per output (NULL: not wanted), the C
+    reflection flags, the scalars and reserved words."""
+    _fields_ = [("nprobs", C.c_int), ("reserved0", C.c_int), ("probs", C.POINTER(C.c_double))] + [
+        (k, C.POINTER(C.c_double)) for k in ("theta_q", "theta_median", "theta_mode", "theta_hist", "theta_rhat_bulk",
+                                             "theta_rhat_tail", "theta_rhat", "irf_q", "irf_p_mean")] + [
+        ("reflected", C.POINTER(C.c_int)), ("scalars", C.c_double * len(QNT_SCALARS)), ("reserved", C.c_int64 * 4)]
 
 
 class Options(C.Structure):
@@ -171,6 +187,11 @@ SIGNATURES = {
                                      C.POINTER(Diag)]),
     "gpirt_mcmc_chains": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                   TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag)]),
+    "gpirt_irf_band_edges": (_i32, [_dp]),
+    "gpirt_summary_quantiles": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, C.POINTER(Quantiles)]),
+    "gpirt_mcmc_quantiles": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                     TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                     C.POINTER(Quantiles)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

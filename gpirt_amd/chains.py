@@ -71,7 +71,7 @@ def combine(handle, states, align=True, signs=None, summaries=None) -> dict:
     tensors = [s.summary_state() if hasattr(s, "summary_state") else s for s in states]
     hdr = state_header(tensors[0])
     n, m, parts = hdr["n"], hdr["m"], hdr["parts"]
-    want = (parts & ~_lib.SUM_DIAG) if summaries is None else _lib.summary_parts(summaries) | _lib.SUM_THETA_BETA
+    want = (parts & _lib.SUM_POOLED) if summaries is None else _lib.summary_parts(summaries) | _lib.SUM_THETA_BETA
     sm = _lib.Summary()
     sm.parts = want
     arrays = _summary_arrays(want, n, m)

@@ -284,6 +284,18 @@ struct SumLayout {
 };
 enum { DG_H1_MEAN, DG_H1_M2, DG_H2_MEAN, DG_H2_M2, DG_BSUM, DG_BM_MEAN, DG_BM_M2 };
 SumLayout summary_layout(int64_t n, int64_t m, int parts);
+// GPIRT_SUM_THETA_HIST / GPIRT_SUM_IRF_BAND: their arrays follow SumLayout's (offsets in doubles, -1: off; a uint32 array
+// takes half a double per count, every array padded to 16 bytes).  total: the whole block.
+struct QntLayout {
+    int64_t th_hist[3] = { -1, -1, -1 };    // whole chain, half 1, half 2 (DIAG): uint32 n x GPIRT_NGRID, respondent-major
+    int64_t th_off = -1;                     // uint32 n: draws off the grid
+    int64_t psum = -1;                       // double GPIRT_NGRID x m: sum of plogis(f*)
+    int64_t band_nan = -1;                   // uint32 GPIRT_NGRID x m
+    int64_t band = -1;                       // uint32 GPIRT_IRF_BINS x (GPIRT_NGRID x m): bin-major, the f* cell fastest
+    int64_t total = 0;
+};
+QntLayout quantile_layout(int64_t n, int64_t m, int parts);
+void irf_band_edges(double* out);          // GPIRT_IRF_BINS - 1 edges logit(b / 256)
 struct SummaryState {
     int parts = 0;                    // GPIRT_SUM_* (0: off)
     int64_t n = 0, m = 0, draws = 0, planned = 0;
@@ -296,15 +308,24 @@ struct SummaryState {
     double *f_mean = nullptr, *f_m2 = nullptr;                            // F: Welford of f
     double *irf = nullptr;                                                // a copy of the sampler's irf_sum (N x m)
     double *dtb[7] = {}, *df[7] = {};                                     // DIAG (SumLayout)
+    QntLayout qlay;                                                       // THETA_HIST / IRF_BAND (and the block's size)
+    uint32_t *th_hist[3] = {}, *th_off = nullptr;                         // THETA_HIST: whole chain, halves; off the grid
+    uint32_t *band = nullptr, *band_nan = nullptr;                        // IRF_BAND: bins, NaN draws
+    double *psum = nullptr, *edges = nullptr;                             // IRF_BAND: sum of plogis(f*); the bin edges
     double *out = nullptr, *part = nullptr, *tot = nullptr;              // a finished array, block partials, the totals
     std::vector<void*> allocs;
 };
 // zeroed accumulators; planned: the draw count S fixed for GPIRT_SUM_DIAG (0 without it)
 int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t planned = 0);
 void summary_free(SummaryState* s);
-// adds one draw; f, mu, y are n x m (16-byte aligned), theta n, beta 2 x m
+// adds one draw; f, mu, y are n x m (16-byte aligned), theta n, beta 2 x m, fstar GPIRT_NGRID x m (GPIRT_SUM_IRF_BAND)
 int launch_summary_accumulate(hipStream_t stream, SummaryState* s, const double* theta, const double* beta, const double* f,
-                              const double* mu, const double* y);
+                              const double* mu, const double* y, const double* fstar = nullptr);
+// GPIRT_SUM_THETA_HIST / IRF_BAND arrays of summary_get by name (*found = false: not one of theirs), copied to h_out
+int summary_hist_get(hipStream_t stream, const SummaryState* s, const char* name, double* h_out, int64_t count, bool* found);
+// gpirt_summary_quantiles on h's stream
+int summary_quantiles(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
+                      gpirt_quantiles* q);
 // the finished array `name` (p_yes, lppd, p_waic, f_mean, f_var, theta_mean, theta_var, beta_mean, beta_var) into s->out
 int launch_summary_finish(hipStream_t stream, const SummaryState* s, const char* name, const double* y, double** d_out,
                           int64_t* count);

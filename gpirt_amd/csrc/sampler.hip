@@ -1428,14 +1428,16 @@ int gpirt_sampler_accumulate_irf(gpirt_sampler_t s)
 int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts)
 {
     GP_ARG(s && s->initialised);
-    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) == 0);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_THETA_HIST |
+                      GPIRT_SUM_IRF_BAND)) == 0);
     return gpirt_sampler_summary_enable_planned(s, parts, 0);
 }
 
 int gpirt_sampler_summary_enable_planned(gpirt_sampler_t s, int parts, int64_t planned_draws)
 {
     GP_ARG(s && s->initialised);
-    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) == 0);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG |
+                      GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND)) == 0);
     GP_ARG(planned_draws >= 0 && (!(parts & GPIRT_SUM_DIAG) || planned_draws >= 1));
     GP_HIP(hipStreamSynchronize(s->h->stream));        // a summary kernel still running on the old accumulators
     summary_free(&s->sum);
@@ -1448,8 +1450,9 @@ int gpirt_sampler_summary_enable_planned(gpirt_sampler_t s, int parts, int64_t p
 int gpirt_summary_state_bytes(int64_t n, int64_t m, int parts, int64_t* bytes)
 {
     GP_ARG(n > 0 && m > 0 && bytes);
-    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) == 0);
-    *bytes = summary_layout(n, m, parts | GPIRT_SUM_THETA_BETA).total * (int64_t)sizeof(double);
+    GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG |
+                      GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND)) == 0);
+    *bytes = quantile_layout(n, m, parts | GPIRT_SUM_THETA_BETA).total * (int64_t)sizeof(double);
     return 0;
 }
 
@@ -1459,7 +1462,7 @@ int gpirt_sampler_summary_state(gpirt_sampler_t s, void** d_state, int64_t* byte
     if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
     GP_TRY(summary_seal(s->h->stream, &s->sum, s->irf_sum, s->N));
     *d_state = s->sum.block;
-    *bytes = s->sum.lay.total * (int64_t)sizeof(double);
+    *bytes = s->sum.qlay.total * (int64_t)sizeof(double);
     return 0;
 }
 
@@ -1468,13 +1471,16 @@ int gpirt_sampler_summary_accumulate(gpirt_sampler_t s)
     GP_ARG(s && s->initialised);
     if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
     GP_TRY(beta_sync(s));                     // draw_beta (beta, mu) may still be deferred to the sampler's own stream
-    return launch_summary_accumulate(s->h->stream, &s->sum, s->theta, s->beta, s->f, s->mu, s->y);
+    return launch_summary_accumulate(s->h->stream, &s->sum, s->theta, s->beta, s->f, s->mu, s->y, s->fstar);
 }
 
 int gpirt_sampler_summary_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count)
 {
     GP_ARG(s && name && h_out && count >= 0);
     if (!s->sum.parts) { set_error("summaries are not enabled (gpirt_sampler_summary_enable)"); return GPIRT_E_ARG; }
+    bool hist = false;
+    GP_TRY(summary_hist_get(s->h->stream, &s->sum, name, h_out, count, &hist));
+    if (hist) return 0;
     double* d = nullptr; int64_t c = 0;
     GP_TRY(launch_summary_finish(s->h->stream, &s->sum, name, s->y, &d, &c));
     GP_ARG(count <= c);
@@ -1834,6 +1840,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     auto even = [](size_t c) { return (c + 1) & ~(size_t)1; };
     const size_t off_beta = even((size_t)n), off_f = off_beta + even((size_t)(2 * m)), off_mu = off_f + even((size_t)(n * m));
     const size_t ck_doubles = off_mu + even((size_t)(n * m)) + 3 * even((size_t)(N * m));
+    const size_t off_fstar = off_mu + even((size_t)(n * m)) + even((size_t)(N * m));      // the slot's f*, after mu*
     double* ck[NS] = { nullptr, nullptr, nullptr };
     hipEvent_t ev_flags[NS] = {}, ev_copied[NS] = {};
     bool copy_pending[NS] = { false, false, false };
@@ -1890,7 +1897,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         const double* d = ck[q];
         // the summaries read the slot on the compute stream: ordered before save_ckpt(k + 3) overwrites it, which the host
         // enqueues only once checkpoint k + 1 is verified
-        if (summarise) GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y));
+        if (summarise)
+            GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y, d + off_fstar));
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2018,17 +2026,18 @@ int gpirt_chains_combine(gpirt_handle_t h, int chains, const void* const* d_stat
     return chains_combine(h, chains, d_states, signs, align, h_irfs, pooled, diag);
 }
 
-int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+// gpirt_mcmc_chains and gpirt_mcmc_quantiles: the arguments checked as gpirt_mcmc_chains checks them, C chains one after
+// another on one handle (chain c: seed gpirt_chain_seed(seed, c), column c of h_theta0; rs != NULL: R's stream, one chain),
+// each state keeping pooled->parts | extra (with DIAG planned for S), then gpirt_chains_combine with align and, with q,
+// gpirt_summary_quantiles of the same states.  One loop, so the quantiles' chains are gpirt_mcmc_chains's chains.
+static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag)
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
+                      gpirt_quantiles* q)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
-    if (opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_chains needs GPIRT_RNG_ITEM (each chain keys its draws by gpirt_chain_seed)");
-        return GPIRT_E_ARG;
-    }
     // the pooled outputs are checked now, before any chain runs (the combine checks them again against the states)
     const int parts = pooled->parts | GPIRT_SUM_THETA_BETA;
     {
@@ -2041,6 +2050,12 @@ int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(diag->reserved[0] == 0 && diag->reserved[1] == 0 && diag->reserved[2] == 0 && diag->reserved[3] == 0);
         GP_ARG((parts & GPIRT_SUM_F) || !(diag->h_f_rhat || diag->h_f_ess || diag->h_f_mcse));
     }
+    if (q) {
+        GP_ARG(q->reserved0 == 0 && q->reserved[0] == 0 && q->reserved[1] == 0 && q->reserved[2] == 0 && q->reserved[3] == 0);
+        GP_ARG(q->nprobs >= 0 && (q->nprobs == 0 || q->probs));
+        for (int p = 0; p < q->nprobs; ++p) GP_ARG(q->probs[p] >= 0.0 && q->probs[p] <= 1.0);
+        GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
+    }
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
@@ -2051,22 +2066,63 @@ int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_t
         gpirt_options o = *opts;
         o.seed = gpirt_chain_seed(opts->seed, c);
         gpirt_summary sm{};
-        sm.parts = parts;
+        sm.parts = parts | extra;
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
-        rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, nullptr, tick, tick_ctx,
+        rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
                       h_beta_draws ? h_beta_draws + (int64_t)c * 2 * m * (S_it + 1) : nullptr,
                       h_f_draws ? h_f_draws + (int64_t)c * n * m * (S_it + 1) : nullptr, irf_c.data(), &sm, &cr);
     }
-    if (!rc) {
-        std::vector<const void*> st((size_t)chains);
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
-        rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag);
-    }
+    std::vector<const void*> st((size_t)chains);
+    for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
+    if (!rc) rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag);
+    if (!rc && q) rc = summary_quantiles(h, chains, st.data(), nullptr, align, q);
     for (auto& k : keep) summary_free(&k);
     gpirt_destroy(h);
     return rc;
+}
+
+int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                      const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag)
+{
+    GP_ARG(opts);
+    if (opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_chains needs GPIRT_RNG_ITEM (each chain keys its draws by gpirt_chain_seed)");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, 0, nullptr, nullptr);
+}
+
+// ---- quantiles --------------------------------------------------------------------------------------------------------
+int gpirt_irf_band_edges(double* out)
+{
+    GP_ARG(out);
+    irf_band_edges(out);
+    return 0;
+}
+
+int gpirt_summary_quantiles(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
+                            gpirt_quantiles* q)
+{
+    return summary_quantiles(h, chains, d_states, signs, align, q);
+}
+
+int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                         const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                         gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                         double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q)
+{
+    GP_ARG(opts && q);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_quantiles needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND, rs, q);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 #include "common.h"
 #include "kernels.h"
 
+#include <algorithm>
+
 namespace gpirt {
 
 namespace {
@@ -381,6 +383,84 @@ DiagArgs diag_step(const SummaryState* s, int64_t d)
     return g;
 }
 
+// ---- GPIRT_SUM_THETA_HIST / GPIRT_SUM_IRF_BAND: the histograms of a draw -------------------------------------------------
+constexpr int NG = GPIRT_NGRID;
+
+struct HistArgs {
+    const double* theta; const double* fstar; const double* edges;
+    uint32_t *th_all, *th_half, *th_off;     // th_half: the draw's DIAG half (nullptr: in neither, or no DIAG)
+    uint32_t *band, *band_nan;
+    double* psum;
+    int64_t n, nm;
+};
+
+__device__ __forceinline__ double plogis(double x)
+{
+    const double e = exp(-fabs(x));
+    return x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+}
+
+// One lane owns one f* cell, or one respondent, of the draw: every counter it increments is its own -- no atomics, the same
+// counts from run to run.  A cell's value goes in bin #{b : e_b <= x} (a binary search over the 255 edges in LDS); the bins
+// are bin-major with the cell fastest, so neighbouring grid points, which mostly share a bin, share cache lines.
+template <bool TH, bool BAND>
+__global__ __launch_bounds__(SUM_THREADS) void summary_hist_accumulate_kernel(HistArgs a)
+{
+    __shared__ double e[GPIRT_IRF_BINS];
+    if (BAND) {
+        for (int b = threadIdx.x; b < GPIRT_IRF_BINS - 1; b += SUM_THREADS) e[b] = a.edges[b];
+        __syncthreads();
+    }
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    if (BAND)
+        for (int64_t c = tid; c < a.nm; c += stride) {
+            const double x = a.fstar[c];
+            a.psum[c] += plogis(x);
+            if (x != x) { a.band_nan[c] += 1u; continue; }
+            int b = 0;
+            for (int step = GPIRT_IRF_BINS / 2; step > 0; step >>= 1)
+                if (b + step <= GPIRT_IRF_BINS - 1 && e[b + step - 1] <= x) b += step;
+            a.band[(int64_t)b * a.nm + c] += 1u;
+        }
+    if (TH)
+        for (int64_t i = tid; i < a.n; i += stride) {
+            const double t = a.theta[i];
+            const double k = rint((t + 5.0) * 100.0);
+            if (!(k >= 0.0 && k <= (double)(NG - 1) && -5.0 + k * 0.01 == t)) { a.th_off[i] += 1u; continue; }
+            const int64_t at = i * NG + (int64_t)k;
+            a.th_all[at] += 1u;
+            if (a.th_half) a.th_half[at] += 1u;
+        }
+}
+
+template <bool TH, bool BAND>
+void launch_hist_t(hipStream_t st, const HistArgs& a)
+{
+    const int64_t work = BAND ? (a.nm > a.n ? a.nm : a.n) : a.n;
+    hipLaunchKernelGGL((summary_hist_accumulate_kernel<TH, BAND>), dim3(grid_cap(work)), dim3(SUM_THREADS), 0, st, a);
+}
+
+// the histogram launch of draw d (1-based), after the moments' own
+int launch_hist(hipStream_t st, const SummaryState* s, const double* theta, const double* fstar, int64_t d)
+{
+    const bool th = s->parts & GPIRT_SUM_THETA_HIST, band = s->parts & GPIRT_SUM_IRF_BAND;
+    if (!th && !band) return 0;
+    HistArgs a{};
+    a.theta = theta; a.fstar = fstar; a.edges = s->edges;
+    a.th_all = s->th_hist[0]; a.th_off = s->th_off; a.band = s->band; a.band_nan = s->band_nan; a.psum = s->psum;
+    a.n = s->n; a.nm = (int64_t)NG * s->m;
+    if (th && (s->parts & GPIRT_SUM_DIAG)) {              // DIAG's halves: draws 1..floor(S/2) and the last floor(S/2)
+        const int64_t S = s->planned, hN = S / 2;
+        if (d <= hN) a.th_half = s->th_hist[1];
+        else if (d > S - hN) a.th_half = s->th_hist[2];
+    }
+    if (th && band) launch_hist_t<true, true>(st, a);
+    else if (th) launch_hist_t<true, false>(st, a);
+    else launch_hist_t<false, true>(st, a);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // namespace
 
 SumLayout summary_layout(int64_t n, int64_t m, int parts)
@@ -403,6 +483,31 @@ SumLayout summary_layout(int64_t n, int64_t m, int parts)
     return L;
 }
 
+QntLayout quantile_layout(int64_t n, int64_t m, int parts)
+{
+    QntLayout Q;
+    int64_t at = summary_layout(n, m, parts).total;
+    auto take_u32 = [&](int64_t count) { const int64_t o = at; const int64_t w = (count + 1) / 2; at += (w + 1) & ~(int64_t)1; return o; };
+    if (parts & GPIRT_SUM_THETA_HIST) {
+        Q.th_hist[0] = take_u32(n * NG);
+        if (parts & GPIRT_SUM_DIAG) { Q.th_hist[1] = take_u32(n * NG); Q.th_hist[2] = take_u32(n * NG); }
+        Q.th_off = take_u32(n);
+    }
+    if (parts & GPIRT_SUM_IRF_BAND) {
+        const int64_t nm = (int64_t)NG * m;
+        Q.psum = at; at += (nm + 1) & ~(int64_t)1;
+        Q.band_nan = take_u32(nm);
+        Q.band = take_u32(nm * GPIRT_IRF_BINS);
+    }
+    Q.total = at;
+    return Q;
+}
+
+void irf_band_edges(double* out)
+{
+    for (int b = 1; b < GPIRT_IRF_BINS; ++b) out[b - 1] = log((double)b) - log((double)(GPIRT_IRF_BINS - b));
+}
+
 int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t planned)
 {
     const size_t cells = (size_t)(n * m), tb = (size_t)(n + 2 * m);
@@ -414,13 +519,24 @@ int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t plan
     };
     s->n = n; s->m = m; s->parts = parts; s->draws = 0; s->planned = planned;
     s->lay = summary_layout(n, m, parts);
-    GP_TRY(get(&s->block, (size_t)s->lay.total));
+    s->qlay = quantile_layout(n, m, parts);
+    GP_TRY(get(&s->block, (size_t)s->qlay.total));
     auto at = [&](int64_t off) { return off < 0 ? nullptr : s->block + off; };
+    auto atu = [&](int64_t off) { return off < 0 ? nullptr : reinterpret_cast<uint32_t*>(s->block + off); };
     const SumLayout& L = s->lay;
     s->tb_mean = at(L.tb_mean); s->tb_m2 = at(L.tb_m2);
     s->lse = at(L.lse); s->ll_mean = at(L.ll_mean); s->ll_m2 = at(L.ll_m2); s->y = at(L.y);
     s->p_sum = at(L.p_sum); s->f_mean = at(L.f_mean); s->f_m2 = at(L.f_m2); s->irf = at(L.irf);
     for (int k = 0; k < 7; ++k) { s->dtb[k] = at(L.dtb[k]); s->df[k] = at(L.df[k]); }
+    const QntLayout& Q = s->qlay;
+    for (int k = 0; k < 3; ++k) s->th_hist[k] = atu(Q.th_hist[k]);
+    s->th_off = atu(Q.th_off); s->band = atu(Q.band); s->band_nan = atu(Q.band_nan); s->psum = at(Q.psum);
+    if (parts & GPIRT_SUM_IRF_BAND) {
+        double e[GPIRT_IRF_BINS - 1];
+        irf_band_edges(e);
+        GP_TRY(get(&s->edges, GPIRT_IRF_BINS));
+        GP_HIP(hipMemcpy(s->edges, e, sizeof(e), hipMemcpyHostToDevice));
+    }
     GP_TRY(get(&s->out, cells > tb ? cells : tb));
     GP_TRY(get(&s->part, (size_t)SUM_TOTAL_BLOCKS * 4));
     GP_TRY(get(&s->tot, GPIRT_SUM_NTOTALS));
@@ -434,10 +550,14 @@ void summary_free(SummaryState* s)
 }
 
 int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* theta, const double* beta, const double* f,
-                              const double* mu, const double* y)
+                              const double* mu, const double* y, const double* fstar)
 {
     if ((((uintptr_t)f | (uintptr_t)mu | (uintptr_t)y) & 15) != 0) {
         set_error("summary: f, mu and y must be 16-byte aligned");
+        return GPIRT_E_ARG;
+    }
+    if ((s->parts & GPIRT_SUM_IRF_BAND) && !fstar) {
+        set_error("summary: GPIRT_SUM_IRF_BAND needs f*");
         return GPIRT_E_ARG;
     }
     const bool diag = s->parts & GPIRT_SUM_DIAG;
@@ -467,6 +587,7 @@ int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* the
             default: launch_diag_acc<true, true, true>(st, a, g, draw); break;
         }
         GP_HIP(hipGetLastError());
+        GP_TRY(launch_hist(st, s, theta, fstar, draw));
         s->draws = draw;
         return 0;
     }
@@ -481,6 +602,7 @@ int launch_summary_accumulate(hipStream_t st, SummaryState* s, const double* the
         default: launch_acc<true, true, true>(st, a, draw); break;
     }
     GP_HIP(hipGetLastError());
+    GP_TRY(launch_hist(st, s, theta, fstar, draw));
     s->draws = draw;
     return 0;
 }
@@ -554,6 +676,40 @@ int launch_summary_totals(hipStream_t st, const SummaryState* s, const double* y
         GP_HIP(hipGetLastError());
         hipLaunchKernelGGL(summary_reduce_kernel, dim3(1), dim3(SUM_THREADS), 0, st, s->part, SUM_TOTAL_BLOCKS, pass, S, s->tot);
         GP_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int summary_hist_get(hipStream_t st, const SummaryState* s, const char* name, double* h_out, int64_t count, bool* found)
+{
+    const int64_t nh = s->n * NG, nm = (int64_t)NG * s->m;
+    const struct { const char* k; const void* p; int64_t c; bool u32; } tab[] = {
+        { "theta_hist", s->th_hist[0], nh, true }, { "theta_hist_h1", s->th_hist[1], nh, true },
+        { "theta_hist_h2", s->th_hist[2], nh, true }, { "theta_off_grid", s->th_off, s->n, true },
+        { "irf_p_mean", s->psum, nm, false }, { "irf_band", s->band, nm * GPIRT_IRF_BINS, true },
+        { "irf_nan", s->band_nan, nm, true },
+    };
+    *found = false;
+    for (const auto& e : tab) {
+        if (strcmp(e.k, name) != 0) continue;
+        *found = true;
+        if (!e.p) {
+            set_error("summary '%s' was not enabled (GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND; the halves need GPIRT_SUM_DIAG)", name);
+            return GPIRT_E_ARG;
+        }
+        GP_ARG(count <= e.c);
+        if (e.u32) {
+            std::vector<uint32_t> tmp((size_t)count);
+            GP_HIP(hipMemcpyAsync(tmp.data(), e.p, sizeof(uint32_t) * (size_t)count, hipMemcpyDeviceToHost, st));
+            GP_HIP(hipStreamSynchronize(st));
+            for (int64_t i = 0; i < count; ++i) h_out[i] = (double)tmp[(size_t)i];
+        } else {                                  // the mean of plogis(f*) over the draws
+            GP_HIP(hipMemcpyAsync(h_out, e.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, st));
+            GP_HIP(hipStreamSynchronize(st));
+            const double T = (double)s->draws;
+            for (int64_t i = 0; i < count; ++i) h_out[i] = s->draws >= 1 ? h_out[i] / T : (double)NAN;
+        }
+        return 0;
     }
     return 0;
 }
@@ -727,14 +883,13 @@ struct DevFree {
     ~DevFree() { for (void* q : p) hipFree(q); }
 };
 
-}  // namespace
+constexpr int POOLED_PARTS = GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC;
+constexpr int STATE_PARTS = POOLED_PARTS | GPIRT_SUM_DIAG | GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND;
 
-int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const int* signs, int align, double* h_irfs,
-                   gpirt_summary* pooled, gpirt_diag* diag)
+// the C headers of d_states (identical) into hd; checks that they are this library's
+int read_headers(hipStream_t st, int C, const void* const* d_states, std::vector<int64_t>& hd)
 {
-    GP_ARG(h && C >= 1 && d_states);
-    hipStream_t st = h->stream;
-    std::vector<int64_t> hd((size_t)C * SUM_HEADER_WORDS);
+    hd.assign((size_t)C * SUM_HEADER_WORDS, 0);
     for (int c = 0; c < C; ++c) {
         GP_ARG(d_states[c] && ((uintptr_t)d_states[c] & 15) == 0);
         GP_HIP(hipMemcpyAsync(&hd[(size_t)c * SUM_HEADER_WORDS], d_states[c], SUM_HEADER_WORDS * sizeof(int64_t),
@@ -747,20 +902,53 @@ int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const i
             set_error("chain %d's state header (n, m, parts, planned draws, draws, layout) differs from chain 0's", c);
             return GPIRT_E_ARG;
         }
-    const int64_t n = h0[0], m = h0[1], planned = h0[3], draws = h0[4];
-    const int parts = (int)h0[2];
-    if (h0[5] != SUM_LAYOUT_VERSION || h0[6] != GPIRT_NGRID || n <= 0 || m <= 0 || draws < 0 ||
-        (parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG)) != 0 ||
-        !(parts & GPIRT_SUM_THETA_BETA)) {
+    if (h0[5] != SUM_LAYOUT_VERSION || h0[6] != GPIRT_NGRID || h0[0] <= 0 || h0[1] <= 0 || h0[4] < 0 ||
+        (h0[2] & ~(int64_t)STATE_PARTS) != 0 || !(h0[2] & GPIRT_SUM_THETA_BETA)) {
         set_error("not a summary state block of this library (layout %lld)", (long long)h0[5]);
         return GPIRT_E_ARG;
     }
+    return 0;
+}
+
+// The chains' signs, gpirt_chains_combine's decision: forced, or chain c >= 1 reflected when sum_i thetabar_c,i thetabar_0,i
+// < 0 (align); sg holds C ones on entry.  d_st: the C block pointers on the device, d_dot C doubles of workspace.
+int chain_signs(hipStream_t st, int C, const double* const* d_st, int64_t tb_mean, int64_t n, const int* signs, int align,
+                double* d_dot, std::vector<double>& sg)
+{
+    if (signs) {
+        for (int c = 0; c < C; ++c) {
+            GP_ARG(signs[c] == 1 || signs[c] == -1);
+            sg[(size_t)c] = (double)signs[c];
+        }
+    } else if (align && C > 1) {
+        hipLaunchKernelGGL(chains_dot_kernel, dim3(C), dim3(SUM_THREADS), 0, st, d_st, tb_mean, n, d_dot);
+        GP_HIP(hipGetLastError());
+        std::vector<double> dots((size_t)C);
+        GP_HIP(hipMemcpyAsync(dots.data(), d_dot, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, st));
+        GP_HIP(hipStreamSynchronize(st));
+        for (int c = 1; c < C; ++c) sg[(size_t)c] = dots[(size_t)c] < 0.0 ? -1.0 : 1.0;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const int* signs, int align, double* h_irfs,
+                   gpirt_summary* pooled, gpirt_diag* diag)
+{
+    GP_ARG(h && C >= 1 && d_states);
+    hipStream_t st = h->stream;
+    std::vector<int64_t> hd;
+    GP_TRY(read_headers(st, C, d_states, hd));       // states with THETA_HIST / IRF_BAND too: their arrays come last
+    const int64_t* h0 = hd.data();
+    const int64_t n = h0[0], m = h0[1], planned = h0[3], draws = h0[4];
+    const int parts = (int)h0[2];
     const bool dg = parts & GPIRT_SUM_DIAG, fo = parts & GPIRT_SUM_F;
     if (dg && draws != planned) {
         set_error("diagnostics need all %lld planned draws (%lld are in)", (long long)planned, (long long)draws);
         return GPIRT_E_ARG;
     }
-    if (pooled) GP_TRY(pooled_args_ok(pooled, parts & ~GPIRT_SUM_DIAG));
+    if (pooled) GP_TRY(pooled_args_ok(pooled, parts & POOLED_PARTS));
     if (diag) {
         GP_ARG(dg);
         GP_ARG(diag->reserved[0] == 0 && diag->reserved[1] == 0 && diag->reserved[2] == 0 && diag->reserved[3] == 0);
@@ -777,24 +965,12 @@ int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const i
     double* d_sg = d_ptrs + C;
     double* d_dot = d_ptrs + 2 * C;
     GP_HIP(hipMemcpyAsync(d_ptrs, d_states, sizeof(void*) * (size_t)C, hipMemcpyHostToDevice, st));
-    if (signs) {
-        for (int c = 0; c < C; ++c) {
-            GP_ARG(signs[c] == 1 || signs[c] == -1);
-            sg[(size_t)c] = (double)signs[c];
-        }
-    } else if (align && C > 1) {
-        hipLaunchKernelGGL(chains_dot_kernel, dim3(C), dim3(SUM_THREADS), 0, st, d_st, L.tb_mean, n, d_dot);
-        GP_HIP(hipGetLastError());
-        std::vector<double> dots((size_t)C);
-        GP_HIP(hipMemcpyAsync(dots.data(), d_dot, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, st));
-        GP_HIP(hipStreamSynchronize(st));
-        for (int c = 1; c < C; ++c) sg[(size_t)c] = dots[(size_t)c] < 0.0 ? -1.0 : 1.0;
-    }
+    GP_TRY(chain_signs(st, C, d_st, L.tb_mean, n, signs, align, d_dot, sg));
     GP_HIP(hipMemcpyAsync(d_sg, sg.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, st));
 
     SummaryState P;                              // the pooled accumulators: a chain of C S draws
     struct Free { SummaryState* s; ~Free() { summary_free(s); } } pfree{ &P };
-    GP_TRY(summary_alloc(&P, n, m, parts & ~GPIRT_SUM_DIAG));
+    GP_TRY(summary_alloc(&P, n, m, parts & POOLED_PARTS));
     P.draws = (int64_t)C * draws;
     const int64_t nd = dg ? tb + (fo ? cells : 0) : 0;
     double* d_diag = nullptr;
@@ -880,6 +1056,374 @@ int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const i
         const double inv = 1.0 / ((double)C * (double)S);
         for (int64_t i = 0; i < N * m; ++i) h_irfs[i] = 1.0 / (1.0 + exp(-(h_irfs[i] * inv)));
     }
+    return 0;
+}
+
+// ---- quantiles: gpirt_summary_quantiles ------------------------------------------------------------------------------
+namespace {
+
+struct QArgs {
+    const double* const* st;          // C state blocks
+    const double* sgn;                // C signs: -1 reverses the chain's grid index (k -> NG - 1 - k)
+    QntLayout Q;
+    int C, nprobs;
+    int64_t n, nm, T, hN;             // pooled draws C S, half length floor(S / 2)
+    const int64_t* rank;              // nprobs + 1: max(ceil(q T), 1) of each prob, then the median's
+    const double* tq;                 // nprobs: q T
+    const int64_t* order;             // nprobs: the probabilities' indices in ascending order of q T
+    double *theta_q, *median, *mode, *hist, *bulk, *tail, *rhat, *off;     // device, nullptr: not wanted
+    double *irf_q, *p_mean, *part;
+};
+
+constexpr int QPER = (NG + SUM_THREADS - 1) / SUM_THREADS;     // grid points a lane scans, contiguous
+
+__device__ __forceinline__ uint32_t th_count(const QArgs& a, int c, int64_t off, int64_t i, int k)
+{
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(a.st[c] + off) + i * NG;
+    return h[a.sgn[c] < 0.0 ? NG - 1 - k : k];
+}
+
+// Half (c, off)'s count at index t of the ranked variable: grid point t (s2 < 0), or the folded distance d = 2t + (s2 & 1)
+// from the median s2 / 2 in half-grid units -- grid points (s2 + d) / 2 and (s2 - d) / 2, one point at d = 0
+__device__ __forceinline__ long long split_count(const QArgs& a, int c, int64_t off, int64_t i, int t, int s2)
+{
+    if (s2 < 0) return th_count(a, c, off, i, t);
+    const int kp = (s2 + 1) / 2 + t, km = s2 / 2 - t;
+    long long v = kp < NG ? (long long)th_count(a, c, off, i, kp) : 0;
+    if (km >= 0 && km != kp) v += th_count(a, c, off, i, km);
+    return v;
+}
+
+// cum[k] = v[0] + ... + v[k] over the NG entries (LDS): each lane sums QPER contiguous entries, a Hillis-Steele scan of
+// the lane sums, then the lane's entries; every lane returns with cum complete
+__device__ __forceinline__ void scan_counts(const long long* v, long long* cum, long long* sh)
+{
+    const int t = threadIdx.x, k0 = t * QPER;
+    long long run = 0;
+    for (int u = 0; u < QPER; ++u)
+        if (k0 + u < NG) run += v[k0 + u];
+    sh[t] = run;
+    __syncthreads();
+    for (int w = 1; w < SUM_THREADS; w <<= 1) {
+        const long long add = t >= w ? sh[t - w] : 0;
+        __syncthreads();
+        sh[t] += add;
+        __syncthreads();
+    }
+    long long base = t ? sh[t - 1] : 0;
+    for (int u = 0; u < QPER; ++u)
+        if (k0 + u < NG) { base += v[k0 + u]; cum[k0 + u] = base; }
+    __syncthreads();
+}
+
+// the block's sum of x in a fixed order (block_sum's tree), in every lane
+__device__ __forceinline__ double block_total(double x, double (*sh)[SUM_THREADS])
+{
+    const int t = threadIdx.x;
+    sh[0][t] = x;
+    __syncthreads();
+    for (int w = SUM_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) sh[0][t] += sh[0][t + w];
+        __syncthreads();
+    }
+    const double v = sh[0][0];
+    __syncthreads();                  // sh is written again by the next sum
+    return v;
+}
+
+// Rank-normalised split-R-hat of respondent i from the 2C halves' counts (s2 < 0: bulk; else the tail, folded about
+// s2 / 2): ranks with ties averaged over the T' split draws, r = cum_(t-1) + (count_t + 1) / 2, z = Phi^-1((r - 3/8) /
+// (T' + 1/4)); each half's mean and variance (ddof 1) from its counts, streamed from the blocks; the BDA3 formula of
+// diag_of with its W = 0 rules.
+__device__ __forceinline__ double rank_rhat(const QArgs& a, int64_t i, int s2, long long* sc, long long* cum, double* z, long long* shl,
+                            double (*shd)[SUM_THREADS])
+{
+    for (int t = threadIdx.x; t < NG; t += SUM_THREADS) {
+        long long v = 0;
+        for (int c = 0; c < a.C; ++c) v += split_count(a, c, a.Q.th_hist[1], i, t, s2) + split_count(a, c, a.Q.th_hist[2], i, t, s2);
+        sc[t] = v;
+    }
+    __syncthreads();
+    scan_counts(sc, cum, shl);
+    const double Tp = (double)(2 * a.C * a.hN);
+    for (int t = threadIdx.x; t < NG; t += SUM_THREADS) {
+        const double r = (double)(cum[t] - sc[t]) + ((double)sc[t] + 1.0) * 0.5;
+        z[t] = sc[t] ? normcdfinv((r - 0.375) / (Tp + 0.25)) : 0.0;
+    }
+    __syncthreads();
+    const double N = (double)a.hN;
+    double hc = 0.0, hmean = 0.0, hss = 0.0, w = 0.0;
+    for (int c = 0; c < a.C; ++c)
+        for (int h = 1; h <= 2; ++h) {
+            const int64_t off = a.Q.th_hist[h];
+            double s = 0.0;
+            for (int t = threadIdx.x; t < NG; t += SUM_THREADS) s += (double)split_count(a, c, off, i, t, s2) * z[t];
+            const double mean = block_total(s, shd) / N;
+            double q = 0.0;
+            for (int t = threadIdx.x; t < NG; t += SUM_THREADS) {
+                const double d = z[t] - mean;
+                q += (double)split_count(a, c, off, i, t, s2) * d * d;
+            }
+            w += block_total(q, shd) / (N - 1.0);
+            hc += 1.0; welford(hmean, hss, mean, hc);
+        }
+    if (a.hN < 2) return (double)NAN;                      // S < 4
+    const double M = 2.0 * a.C, B = N / (M - 1.0) * hss, W = w / M;
+    const double varp = (N - 1.0) / N * W + B / N;
+    if (W > 0.0) return sqrt(varp / W);
+    return B > 0.0 ? (double)INFINITY : (double)NAN;
+}
+
+// One work-group per respondent: the pooled counts, their quantiles, median, mode and (with the halves) the bulk and tail
+// R-hat.  LDS: the pooled and split counts, their prefix sums and the scores, about 45 KB; the 2C halves stream from the
+// blocks, so C does not bound it.
+__global__ __launch_bounds__(SUM_THREADS) void quantile_theta_kernel(QArgs a)
+{
+    __shared__ long long cnt[NG], cum[NG], sc[NG], scum[NG], shl[SUM_THREADS];
+    __shared__ double z[NG], shd[1][SUM_THREADS];
+    __shared__ int shk[SUM_THREADS], kq[2];
+    const int64_t i = blockIdx.x;
+    const int t = threadIdx.x;
+    for (int k = t; k < NG; k += SUM_THREADS) {
+        long long v = 0;
+        for (int c = 0; c < a.C; ++c) v += th_count(a, c, a.Q.th_hist[0], i, k);
+        cnt[k] = v;
+        if (a.hist) a.hist[i * NG + k] = (double)v;
+    }
+    double offc = 0.0;
+    for (int c = 0; c < a.C; ++c) offc += (double)reinterpret_cast<const uint32_t*>(a.st[c] + a.Q.th_off)[i];
+    if (t == 0) a.off[i] = offc;
+    if (offc > 0.0) {                                       // a draw off the grid: no quantity of this respondent is exact
+        for (int p = t; p < a.nprobs; p += SUM_THREADS)
+            if (a.theta_q) a.theta_q[p + (int64_t)a.nprobs * i] = (double)NAN;
+        if (t == 0) {
+            if (a.median) a.median[i] = (double)NAN;
+            if (a.mode) a.mode[i] = (double)NAN;
+            if (a.rhat) { a.rhat[i] = (double)NAN; if (a.bulk) a.bulk[i] = (double)NAN; if (a.tail) a.tail[i] = (double)NAN; }
+        }
+        return;
+    }
+    __syncthreads();
+    scan_counts(cnt, cum, shl);
+    // order statistics: grid point k holds ranks cum_(k-1) + 1 .. cum_k
+    const int64_t rlo = (a.T + 1) / 2, rhi = a.T / 2 + 1;   // R's median: the two middle order statistics
+    long long best = -1;
+    int bk = 0;
+    for (int k = t; k < NG; k += SUM_THREADS) {
+        const long long lo = k ? cum[k - 1] : 0, hi = cum[k];
+        if (cnt[k] > best) { best = cnt[k]; bk = k; }
+        if (lo == hi) continue;
+        const double v = -5.0 + (double)k * 0.01;
+        if (a.theta_q)
+            for (int p = 0; p < a.nprobs; ++p)
+                if (lo < a.rank[p] && a.rank[p] <= hi) a.theta_q[p + (int64_t)a.nprobs * i] = v;
+        if (a.median && lo < a.rank[a.nprobs] && a.rank[a.nprobs] <= hi) a.median[i] = v;
+        if (lo < rlo && rlo <= hi) kq[0] = k;
+        if (lo < rhi && rhi <= hi) kq[1] = k;
+    }
+    shl[t] = best; shk[t] = bk;                             // the mode: the largest count, the lowest grid point on a tie
+    __syncthreads();
+    for (int w = SUM_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w && (shl[t + w] > shl[t] || (shl[t + w] == shl[t] && shk[t + w] < shk[t]))) { shl[t] = shl[t + w]; shk[t] = shk[t + w]; }
+        __syncthreads();
+    }
+    if (t == 0 && a.mode) a.mode[i] = -5.0 + (double)shk[0] * 0.01;
+    __syncthreads();
+    if (!a.rhat) return;
+    const double bulk = rank_rhat(a, i, -1, sc, scum, z, shl, shd);
+    const double tail = rank_rhat(a, i, kq[0] + kq[1], sc, scum, z, shl, shd);
+    if (t == 0) {
+        if (a.bulk) a.bulk[i] = bulk;
+        if (a.tail) a.tail[i] = tail;
+        a.rhat[i] = (bulk != bulk || tail != tail) ? (double)NAN : fmax(bulk, tail);
+    }
+}
+
+// the block's min (mx = false) or max of x, in every lane
+__device__ __forceinline__ double block_extreme(double x, bool mx, double (*sh)[SUM_THREADS])
+{
+    const int t = threadIdx.x;
+    sh[0][t] = x;
+    __syncthreads();
+    for (int w = SUM_THREADS / 2; w > 0; w >>= 1) {
+        if (t < w) sh[0][t] = mx ? fmax(sh[0][t], sh[0][t + w]) : fmin(sh[0][t], sh[0][t + w]);
+        __syncthreads();
+    }
+    const double v = sh[0][0];
+    __syncthreads();
+    return v;
+}
+
+// One lane per f* cell: E[P], then ONE pass over the pooled band (a reflected chain's cell read at the mirrored grid
+// point), each bin of each chain read once, that resolves the probabilities in ascending order of q T (a.order) -- the
+// first bin with a draw whose cumulative count reaches t -- and counts the cell's draws.  Block partials: the NaN draws,
+// the least and the most draws of a cell (bins + NaN).
+__global__ __launch_bounds__(SUM_THREADS) void quantile_irf_kernel(QArgs a)
+{
+    __shared__ double sh[1][SUM_THREADS];
+    double nan_all = 0.0, cnt_min = (double)INFINITY, cnt_max = -(double)INFINITY;
+    const double T = (double)a.T;
+    for (int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; cell < a.nm; cell += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = cell % NG, mirror = cell - k + (NG - 1 - k);
+        double nanc = 0.0, ps = 0.0;
+        for (int c = 0; c < a.C; ++c) {
+            const int64_t src = a.sgn[c] < 0.0 ? mirror : cell;
+            nanc += (double)reinterpret_cast<const uint32_t*>(a.st[c] + a.Q.band_nan)[src];
+            ps += a.st[c][a.Q.psum + src];
+        }
+        nan_all += nanc;
+        if (a.p_mean) a.p_mean[cell] = ps / T;
+        int pi = 0;                                          // the next probability, in ascending order of q T
+        double cum = 0.0;
+        for (int b = 0; b < GPIRT_IRF_BINS; ++b) {
+            double cb = 0.0;
+            for (int c = 0; c < a.C; ++c)
+                cb += (double)reinterpret_cast<const uint32_t*>(a.st[c] + a.Q.band)[(int64_t)b * a.nm + (a.sgn[c] < 0.0 ? mirror : cell)];
+            if (cb > 0.0)
+                for (; pi < a.nprobs && cum + cb >= a.tq[a.order[pi]]; ++pi) {
+                    const int64_t p = a.order[pi];
+                    if (a.irf_q)
+                        a.irf_q[p + (int64_t)a.nprobs * cell] =
+                            nanc == 0.0 ? ((double)b + (a.tq[p] - cum) / cb) / (double)GPIRT_IRF_BINS : (double)NAN;
+                }
+            cum += cb;
+        }
+        for (; pi < a.nprobs; ++pi)
+            if (a.irf_q) a.irf_q[a.order[pi] + (int64_t)a.nprobs * cell] = (double)NAN;
+        cnt_min = fmin(cnt_min, cum + nanc);
+        cnt_max = fmax(cnt_max, cum + nanc);
+    }
+    const double v0 = block_total(nan_all, sh), v1 = block_extreme(cnt_min, false, sh), v2 = block_extreme(cnt_max, true, sh);
+    if (threadIdx.x == 0) { a.part[3 * (int64_t)blockIdx.x] = v0; a.part[3 * (int64_t)blockIdx.x + 1] = v1; a.part[3 * (int64_t)blockIdx.x + 2] = v2; }
+}
+
+}  // namespace
+
+int summary_quantiles(gpirt_handle_t h, int C, const void* const* d_states, const int* signs, int align, gpirt_quantiles* q)
+{
+    GP_ARG(h && C >= 1 && d_states && q);
+    GP_ARG(q->reserved0 == 0 && q->reserved[0] == 0 && q->reserved[1] == 0 && q->reserved[2] == 0 && q->reserved[3] == 0);
+    GP_ARG(q->nprobs >= 0 && (q->nprobs == 0 || q->probs));
+    for (int p = 0; p < q->nprobs; ++p) GP_ARG(q->probs[p] >= 0.0 && q->probs[p] <= 1.0);
+    hipStream_t st = h->stream;
+    std::vector<int64_t> hd;
+    GP_TRY(read_headers(st, C, d_states, hd));
+    const int64_t n = hd[0], m = hd[1], planned = hd[3], draws = hd[4];
+    const int parts = (int)hd[2];
+    const bool th = parts & GPIRT_SUM_THETA_HIST, band = parts & GPIRT_SUM_IRF_BAND, dg = parts & GPIRT_SUM_DIAG;
+    const bool rh = th && dg;
+    GP_ARG(th || !(q->theta_q || q->theta_median || q->theta_mode || q->theta_hist));
+    GP_ARG(rh || !(q->theta_rhat_bulk || q->theta_rhat_tail || q->theta_rhat));
+    GP_ARG(band || !(q->irf_q || q->irf_p_mean));
+    if (dg && draws != planned) {
+        set_error("the R-hat needs all %lld planned draws (%lld are in)", (long long)planned, (long long)draws);
+        return GPIRT_E_ARG;
+    }
+    if (draws < 1) { set_error("quantiles need draws (the states hold none)"); return GPIRT_E_ARG; }
+    const int64_t T = (int64_t)C * draws;
+    if (T >= ((int64_t)1 << 32)) { set_error("C S = %lld draws: the pooled counts are limited to 2^32", (long long)T); return GPIRT_E_ARG; }
+    const SumLayout L = summary_layout(n, m, parts);
+    const QntLayout Q = quantile_layout(n, m, parts);
+    const int64_t nm = (int64_t)NG * m, np = q->nprobs;
+
+    DevFree tmp;
+    auto dalloc = [&](double** p, int64_t count) -> int {
+        GP_HIP(hipMalloc(p, sizeof(double) * (size_t)(count < 1 ? 1 : count)));
+        tmp.p.push_back(*p);
+        return 0;
+    };
+    double* d_ptrs = nullptr;                    // C block pointers, C signs, C dots
+    GP_TRY(dalloc(&d_ptrs, 3 * (int64_t)C));
+    const double* const* d_st = reinterpret_cast<const double* const*>(d_ptrs);
+    GP_HIP(hipMemcpyAsync(d_ptrs, d_states, sizeof(void*) * (size_t)C, hipMemcpyHostToDevice, st));
+    std::vector<double> sg((size_t)C, 1.0);
+    GP_TRY(chain_signs(st, C, d_st, L.tb_mean, n, signs, align, d_ptrs + 2 * C, sg));
+    GP_HIP(hipMemcpyAsync(d_ptrs + C, sg.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, st));
+
+    std::vector<int64_t> rk((size_t)np + 1);     // max(ceil(q T), 1), then the median's; q T
+    std::vector<double> tq((size_t)np + 1, 0.0);
+    for (int64_t p = 0; p <= np; ++p) {
+        const double qq = p < np ? q->probs[p] : 0.5;
+        const int64_t r = (int64_t)ceil(qq * (double)T);
+        rk[(size_t)p] = r < 1 ? 1 : r;
+        tq[(size_t)p] = qq * (double)T;
+    }
+    std::vector<int64_t> order((size_t)np + 1);
+    for (int64_t p = 0; p <= np; ++p) order[(size_t)p] = p;
+    std::stable_sort(order.begin(), order.begin() + np, [&](int64_t x, int64_t y) { return tq[(size_t)x] < tq[(size_t)y]; });
+    double *d_rk = nullptr, *d_tq = nullptr, *d_order = nullptr;
+    GP_TRY(dalloc(&d_rk, np + 1)); GP_TRY(dalloc(&d_tq, np + 1)); GP_TRY(dalloc(&d_order, np + 1));
+    GP_HIP(hipMemcpyAsync(d_rk, rk.data(), sizeof(int64_t) * (size_t)(np + 1), hipMemcpyHostToDevice, st));
+    GP_HIP(hipMemcpyAsync(d_tq, tq.data(), sizeof(double) * (size_t)(np + 1), hipMemcpyHostToDevice, st));
+    GP_HIP(hipMemcpyAsync(d_order, order.data(), sizeof(int64_t) * (size_t)(np + 1), hipMemcpyHostToDevice, st));
+
+    QArgs a{};
+    a.st = d_st; a.sgn = d_ptrs + C; a.Q = Q; a.C = C; a.nprobs = (int)np;
+    a.n = n; a.nm = nm; a.T = T; a.hN = planned / 2;
+    a.rank = reinterpret_cast<const int64_t*>(d_rk); a.tq = d_tq; a.order = reinterpret_cast<const int64_t*>(d_order);
+    struct Out { double* host; double** dev; int64_t count; };
+    std::vector<Out> outs;
+    auto want = [&](double* host, double** dev, int64_t count, bool always) -> int {
+        if (!host && !always) return 0;
+        GP_TRY(dalloc(dev, count));
+        if (host) outs.push_back({ host, dev, count });
+        return 0;
+    };
+    std::vector<double> off_h, rhat_h, part_h;
+    if (th) {
+        GP_TRY(want(np ? q->theta_q : nullptr, &a.theta_q, np * n, false));
+        GP_TRY(want(q->theta_median, &a.median, n, false));
+        GP_TRY(want(q->theta_mode, &a.mode, n, false));
+        GP_TRY(want(q->theta_hist, &a.hist, NG * n, false));
+        off_h.resize((size_t)n);
+        GP_TRY(want(off_h.data(), &a.off, n, true));
+        if (rh) {
+            GP_TRY(want(q->theta_rhat_bulk, &a.bulk, n, false));
+            GP_TRY(want(q->theta_rhat_tail, &a.tail, n, false));
+            rhat_h.resize((size_t)n);
+            GP_TRY(want(rhat_h.data(), &a.rhat, n, true));
+        }
+        hipLaunchKernelGGL(quantile_theta_kernel, dim3((unsigned)n), dim3(SUM_THREADS), 0, st, a);
+        GP_HIP(hipGetLastError());
+    }
+    if (band) {
+        GP_TRY(want(np ? q->irf_q : nullptr, &a.irf_q, np * nm, false));
+        GP_TRY(want(q->irf_p_mean, &a.p_mean, nm, false));
+        const int blocks = grid_cap(nm);
+        part_h.resize(3 * (size_t)blocks);
+        GP_TRY(want(part_h.data(), &a.part, 3 * (int64_t)blocks, true));
+        hipLaunchKernelGGL(quantile_irf_kernel, dim3(blocks), dim3(SUM_THREADS), 0, st, a);
+        GP_HIP(hipGetLastError());
+    }
+    for (const Out& o : outs)
+        GP_HIP(hipMemcpyAsync(o.host, *o.dev, sizeof(double) * (size_t)o.count, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+
+    double* sc = q->scalars;
+    sc[GPIRT_QNT_DRAWS] = (double)T;
+    sc[GPIRT_QNT_MAX_RHAT] = (double)NAN;
+    sc[GPIRT_QNT_N_RHAT_HIGH] = sc[GPIRT_QNT_N_RHAT_NAN] = 0.0;
+    if (rh && q->theta_rhat) memcpy(q->theta_rhat, rhat_h.data(), sizeof(double) * (size_t)n);
+    if (rh)
+        for (double r : rhat_h) {
+            if (r != r) { sc[GPIRT_QNT_N_RHAT_NAN] += 1.0; continue; }
+            if (!(sc[GPIRT_QNT_MAX_RHAT] >= r)) sc[GPIRT_QNT_MAX_RHAT] = r;
+            if (r > 1.01) sc[GPIRT_QNT_N_RHAT_HIGH] += 1.0;
+        }
+    double off = 0.0, nan = 0.0;
+    for (double v : off_h) off += v;
+    double cmin = band ? (double)INFINITY : (double)NAN, cmax = band ? -(double)INFINITY : (double)NAN;
+    for (size_t b = 0; b < part_h.size(); b += 3) {
+        nan += part_h[b];
+        cmin = fmin(cmin, part_h[b + 1]);
+        cmax = fmax(cmax, part_h[b + 2]);
+    }
+    sc[GPIRT_QNT_THETA_OFF_GRID] = th ? off : (double)NAN;
+    sc[GPIRT_QNT_IRF_NAN] = band ? nan : (double)NAN;
+    sc[GPIRT_QNT_IRF_COUNT_MIN] = cmin;
+    sc[GPIRT_QNT_IRF_COUNT_MAX] = cmax;
+    if (q->reflected)
+        for (int c = 0; c < C; ++c) q->reflected[c] = sg[(size_t)c] < 0.0 ? 1 : 0;
     return 0;
 }
 

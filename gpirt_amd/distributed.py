@@ -30,6 +30,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
+
 
 def item_range(m: int, rank: int, world: int):
     """Contiguous block partition of the item columns."""
@@ -226,8 +228,12 @@ class ShardedSampler:
         return self._gather_columns(self.engine.get(name))
 
     # -- posterior summaries (include/gpirt_hip.h gpirt_sampler_summary_*): each rank accumulates its own item columns;
-    # theta's moments are the same on every rank
+    # theta's moments are the same on every rank.  The quantile parts ("theta_hist", "irf_band", gpirt_amd.quantiles) are
+    # not offered here: each rank's f* band would cover its own items only and would have to be gathered.
     def summary_enable(self, parts):
+        bits = _lib.summary_parts(parts)
+        if bits & (_lib.SUM_THETA_HIST | _lib.SUM_IRF_BAND):
+            raise ValueError("ShardedSampler: the quantile parts (theta_hist, irf_band) are not offered for item shards")
         self.engine.summary_enable(parts)
 
     def summary_accumulate(self):

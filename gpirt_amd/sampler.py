@@ -43,7 +43,7 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
 def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_prior_means=None,
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
-              progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True):
+              progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -67,6 +67,13 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       (and with "f" in summaries, f) value, their per-block scalars and the chains reflected by the theta -> -theta
       alignment (align=False: none).  theta_init may be (C, n); by default chain 0 starts at RStream(seed).rnorm(n) as
       today and chain c at RStream(chain_seed(seed, c) & 0xFFFFFFFF).rnorm(n).  chains=None: one chain, as before.
+    quantiles: probabilities, e.g. (0.025, 0.5, 0.975) (gpirt_mcmc_quantiles, gpirt_amd.quantiles): every chain also
+      keeps theta histograms and IRF bands on the device (and the DIAG accumulators), for chains=None too; rng="reference"
+      runs one chain, the chain gpirt_mcmc_summary runs.  The result gains "summary" and "diagnostics" as with chains and
+      "quantiles": probs, theta (len(probs) x n, exact), theta_median, theta_mode, theta_hist, theta_rhat (the
+      rank-normalised bulk / tail / max), irf (len(probs) x 1001 x m, in probability, within 1/256), irf_p_mean (E[P]),
+      reflected and scalars.  Memory: the band is 1001 x m x 256 x 4 bytes per chain on the device (1.05 GB at
+      m = 1024), theta's histograms 3 x 1001 x n x 4 bytes.  quantiles=None leaves every other path as it is.
     """
     from .ops import RStream
 
@@ -85,6 +92,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         rng = "item"
     elif preset is not None:
         raise ValueError(f"unknown preset {preset!r}")
+    if quantiles is not None:
+        return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
+                               preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
+                               align, quantiles)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -214,6 +225,84 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
                 beta=be.transpose(0, 3, 2, 1) if be is not None else None,
                 f=ff.transpose(0, 3, 2, 1) if ff is not None else None,
                 IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr))
+
+
+def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
+                    kstar_rank, device, progress, summaries, store_draws, align, probs):
+    """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
+    gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them."""
+    from . import chains as CH
+    from . import quantiles as Q
+    from .ops import RStream
+    lib = _lib.load()
+    n, m = y.shape
+    S, B = int(S), int(B)
+    one = nc is None
+    C_ = 1 if one else int(nc)
+    if C_ < 1:
+        raise ValueError("chains must be >= 1")
+    rs = None
+    if rng == "reference":
+        if C_ != 1:
+            raise ValueError("rng='reference' runs one chain; several chains need the item RNG")
+        rs = rstream if rstream is not None else RStream(seed)
+    if theta_init is None:
+        th0 = rs.rnorm(n)[None, :] if rs is not None else CH.default_inits(n, C_, seed)
+    else:
+        t = np.asarray(theta_init, dtype=np.float64)
+        th0 = np.broadcast_to(t, (C_, n)) if t.shape == (n,) else t
+        if th0.shape != (C_, n):
+            raise ValueError("theta_init must be (n,) or (chains, n)")
+    th0 = np.ascontiguousarray(th0)
+    keep = _keep(store_draws)
+    if one:
+        th = np.empty((S + 1, n), order="F") if "theta" in keep else None
+        be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
+        ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
+    else:
+        th = np.empty((C_, n, S + 1)) if "theta" in keep else None
+        be = np.empty((C_, S + 1, m, 2)) if "beta" in keep else None
+        ff = np.empty((C_, S + 1, m, n)) if "f" in keep else None
+    irf = np.empty((NGRID, m), order="F")
+    if preset == "fast":
+        o = _lib.fast_options()
+        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        o.device = -1 if device is None else int(device)
+    else:
+        o = _options(rng, seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
+    parts = _lib.summary_parts(summaries if summaries is not None else 0) | _lib.SUM_THETA_BETA
+    sm = _lib.Summary()
+    sm.parts = parts
+    arrays = _summary_arrays(parts, n, m)
+    for k, a in arrays.items():
+        setattr(sm, "h_" + k, _ptr(a))
+    d, darr = CH.diag_struct(parts, n, m, C_)
+    q, qarr = Q.quantiles_struct(probs, n, m, C_)
+
+    def _tick(ctx, it, total):
+        if progress:
+            print("\r%6.3f %% complete" % (100.0 * it / max(total, 1)), end="", flush=True)
+        return 0
+
+    cb = _lib.TICK_FN(_tick)
+    opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
+    rc = lib.gpirt_mcmc_quantiles(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                  rs.ptr if rs is not None else None, C.byref(q))
+    if progress:
+        print("\r100.000 % complete")
+    if rc > 0:
+        raise RuntimeError("chol(): decomposition failed")
+    check(rc)
+    summary = dict(arrays)
+    if parts & _lib.SUM_WAIC:
+        summary["totals"] = _totals(sm.totals)
+    if not one:
+        th = th.transpose(0, 2, 1) if th is not None else None
+        be = be.transpose(0, 3, 2, 1) if be is not None else None
+        ff = ff.transpose(0, 3, 2, 1) if ff is not None else None
+    return dict(theta=th, beta=be, f=ff, IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr),
+                quantiles=Q.quantiles_result(q, qarr))
 
 
 def _summary_arrays(parts: int, n: int, m: int) -> dict:
@@ -428,7 +517,9 @@ class Sampler:
     # -- posterior summaries accumulated on the device (include/gpirt_hip.h gpirt_sampler_summary_*)
     def summary_enable(self, parts, planned_draws=None):
         """Allocate and zero the accumulators of `parts` (names or GPIRT_SUM_* bits; 0 / () frees them).  planned_draws: the
-        chain's draw count S, fixed now -- the only way to turn on GPIRT_SUM_DIAG (split-R-hat / ESS, gpirt_amd.chains)."""
+        chain's draw count S, fixed now -- the only way to turn on GPIRT_SUM_DIAG (split-R-hat / ESS, gpirt_amd.chains).
+        ("theta_hist", "diag") with planned_draws also keeps DIAG's half histograms of theta: the rank-normalised R-hat
+        of gpirt_amd.quantiles."""
         self._sum_parts = _lib.summary_parts(parts)
         if planned_draws is None:
             check(self.lib.gpirt_sampler_summary_enable(self._s, self._sum_parts))
@@ -455,11 +546,15 @@ class Sampler:
         self._call("gpirt_sampler_summary_accumulate")
 
     def summary_get(self, name: str) -> np.ndarray:
-        shape = {"theta_mean": (self.n,), "theta_var": (self.n,), "beta_mean": (2, self.m), "beta_var": (2, self.m)}.get(
-            name, (self.n, self.m))
+        """One finished array; with "theta_hist" / "irf_band" on also theta_hist, theta_hist_h1, theta_hist_h2 (1001 x n
+        counts), theta_off_grid (n), irf_p_mean, irf_nan (1001 x m) and irf_band (256 x 1001 x m)."""
+        n, m = self.n, self.m
+        shape = {"theta_mean": (n,), "theta_var": (n,), "beta_mean": (2, m), "beta_var": (2, m), "theta_hist": (NGRID, n),
+                 "theta_hist_h1": (NGRID, n), "theta_hist_h2": (NGRID, n), "theta_off_grid": (n,),
+                 "irf_p_mean": (NGRID, m), "irf_nan": (NGRID, m), "irf_band": (NGRID, m, _lib.IRF_BINS)}.get(name, (n, m))
         out = np.empty(shape, order="F")
         check(self.lib.gpirt_sampler_summary_get(self._s, name.encode(), _ptr(out), out.size))
-        return out
+        return out.transpose(2, 0, 1) if name == "irf_band" else out
 
     def summary_totals(self) -> dict:
         raw = (C.c_double * len(_lib.SUM_TOTALS))()
@@ -468,7 +563,7 @@ class Sampler:
 
     def summary(self) -> dict:
         """Every array of the enabled parts, plus "totals" (with GPIRT_SUM_WAIC)."""
-        parts = getattr(self, "_sum_parts", 0) & ~_lib.SUM_DIAG
+        parts = getattr(self, "_sum_parts", 0) & _lib.SUM_POOLED
         out = {k: self.summary_get(k) for k in _summary_arrays(parts, self.n, self.m)}
         if parts & _lib.SUM_WAIC:
             out["totals"] = self.summary_totals()

@@ -429,6 +429,78 @@ int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag);
 
+/* ------------------------------------------------------ quantiles: theta intervals, IRF bands, rank R-hat --- */
+/* Two more parts of a summary state (gpirt_sampler_summary_enable(_planned), gpirt_summary_state_bytes; NOT of
+ * gpirt_summary.parts, which has no place for their outputs).  Their arrays follow every other array of the state block.
+ * GPIRT_SUM_THETA_HIST: per respondent, uint32 counts over the GPIRT_NGRID grid points of all draws (a theta draw is a grid
+ * point, -5 + 0.01 k); with GPIRT_SUM_DIAG also the counts of half 1 and half 2 (DIAG's halves).  A draw whose theta is not
+ * bit for bit -5 + 0.01 k, k = rint((theta + 5) 100), NaN included, goes in no histogram and is counted per respondent.
+ * GPIRT_SUM_IRF_BAND: per f* cell (grid point k, item j), uint32 counts over GPIRT_IRF_BINS bins that cut the probability
+ * scale evenly -- x goes in bin #{b : e_b <= x} with the 255 edges e_b = logit(b / 256) of gpirt_irf_band_edges --, a NaN
+ * count per cell, and the running sum of plogis(f*) (the posterior mean IRF E[P], not plogis(E f*)). */
+#define GPIRT_SUM_THETA_HIST 32
+#define GPIRT_SUM_IRF_BAND   128
+#define GPIRT_IRF_BINS       256
+/* the GPIRT_IRF_BINS - 1 edges e_b = logit(b / 256), b = 1..255, in fp64, increasing (out[0] = e_1) */
+int gpirt_irf_band_edges(double* out);
+
+/* per-call scalars of gpirt_quantiles */
+#define GPIRT_QNT_MAX_RHAT       0   /* over the respondents whose R-hat is not NaN (NaN if none) */
+#define GPIRT_QNT_N_RHAT_HIGH    1   /* R-hat > 1.01 (+inf included) */
+#define GPIRT_QNT_N_RHAT_NAN     2
+#define GPIRT_QNT_THETA_OFF_GRID 3   /* theta draws not on the grid, over every chain and respondent (should be 0) */
+#define GPIRT_QNT_IRF_NAN        4   /* f* draws that were NaN, over every chain and cell */
+#define GPIRT_QNT_DRAWS          5   /* T = C S */
+#define GPIRT_QNT_IRF_COUNT_MIN  6   /* the least and the most draws a pooled f* cell holds (bins + NaN): T both when */
+#define GPIRT_QNT_IRF_COUNT_MAX  7   /* no draw was lost or counted twice */
+#define GPIRT_QNT_NSCALARS       8
+/* What gpirt_summary_quantiles / gpirt_mcmc_quantiles return: a HOST pointer per output (NULL: not wanted; an output
+ * whose part the states lack is refused).  T = C S pooled draws, a reflected chain entering with its grid index
+ * reversed (k -> 1000 - k, for theta and for f*'s grid axis).
+ * theta_q (nprobs x n): the ceil(q T)-th smallest pooled draw (1-based; q = 0: the smallest), theta_median the same for
+ * q = 0.5, theta_mode the most frequent grid point (the lowest on a tie), theta_hist (1001 x n) the pooled counts;
+ * NaN (the histogram: as counted) for a respondent with a draw off the grid.  (Needs GPIRT_SUM_THETA_HIST.)
+ * theta_rhat_bulk / _tail / theta_rhat (n; needs GPIRT_SUM_DIAG too): the rank-normalised split-R-hat of Vehtari et al.
+ * (2021), exact from the half histograms.  Bulk: the 2C halves' T' = 2C floor(S/2) draws ranked with ties averaged,
+ * z = Phi^-1((r - 3/8) / (T' + 1/4)), the BDA3 R-hat of GPIRT_SUM_DIAG on z.  Tail: the same on |theta - median| (R's
+ * median of all T draws).  theta_rhat = max(bulk, tail), NaN if either is.
+ * irf_q (nprobs x 1001 x m; needs GPIRT_SUM_IRF_BAND): in probability, t = q T, b = the first bin with a draw whose
+ * cumulative count is >= t (one pass over a cell's bins, the probabilities in ascending order), (b + (t - cum_(b-1)) / count_b) / 256: within 1 / 256 of the ceil(q T)-th smallest
+ * plogis(f*) draw (NaN for a cell with a NaN draw).  irf_p_mean (1001 x m): the mean of plogis(f*) over the T draws.
+ * reflected: C flags, as gpirt_diag's. */
+typedef struct gpirt_quantiles {
+    int            nprobs;
+    int            reserved0;       /* must be 0 */
+    const double*  probs;           /* nprobs values in [0, 1] */
+    double*        theta_q;
+    double*        theta_median;    /* n */
+    double*        theta_mode;      /* n */
+    double*        theta_hist;      /* 1001 x n */
+    double*        theta_rhat_bulk; /* n */
+    double*        theta_rhat_tail; /* n */
+    double*        theta_rhat;      /* n */
+    double*        irf_q;
+    double*        irf_p_mean;      /* 1001 x m */
+    int*           reflected;       /* C */
+    double         scalars[GPIRT_QNT_NSCALARS];
+    int64_t        reserved[4];     /* must be 0 */
+} gpirt_quantiles;
+/* Quantiles of C >= 1 chains' state blocks (as gpirt_chains_combine: device pointers on h's device, identical headers;
+ * states with GPIRT_SUM_DIAG complete).  The reflection is gpirt_chains_combine's decision for the same states, signs and
+ * align.  C S must be < 2^32.  No atomics: bit-identical from run to run. */
+int gpirt_summary_quantiles(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
+                            gpirt_quantiles* q);
+/* gpirt_mcmc_chains with the quantiles (library version 106): every chain also keeps GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND (and
+ * GPIRT_SUM_DIAG with S planned); draws, IRFs, pooled and diag are bit-identical to gpirt_mcmc_chains's.  rs != NULL
+ * (GPIRT_RNG_RSTREAM, chains = 1): the chain is gpirt_mcmc_summary's -- draws, IRFs and R's stream position bit-identical
+ * -- with the quantiles of its one state.  q is required; pooled->parts as gpirt_mcmc_chains's. */
+int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                         int sample_iterations, int burn_iterations, const double* h_prior_means,
+                         const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                         gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                         double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                         gpirt_rstream_t rs, gpirt_quantiles* q);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
@@ -480,7 +552,9 @@ int gpirt_sampler_accumulate_irf(gpirt_sampler_t s);     /* :103 */
 /* Posterior summaries on the stage API: summary_enable allocates and zeroes the accumulators of `parts` (0 frees them);
  * summary_accumulate adds the CURRENT state as one draw (call it after the step of a sampling iteration); summary_get
  * finishes one array ("p_yes", "lppd", "p_waic", "f_mean", "f_var", "theta_mean", "theta_var", "beta_mean", "beta_var";
- * count <= its size) and copies it out; summary_totals writes GPIRT_SUM_NTOTALS doubles (needs GPIRT_SUM_WAIC). */
+ * GPIRT_SUM_THETA_HIST: "theta_hist", "theta_hist_h1", "theta_hist_h2" (1001 x n, counts as doubles; the halves need
+ * GPIRT_SUM_DIAG), "theta_off_grid" (n); GPIRT_SUM_IRF_BAND: "irf_p_mean" (1001 x m), "irf_band" (1001 x m x 256: the
+ * bin last), "irf_nan" (1001 x m); count <= its size) and copies it out; summary_totals writes GPIRT_SUM_NTOTALS doubles (needs GPIRT_SUM_WAIC). */
 int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts);
 int gpirt_sampler_summary_accumulate(gpirt_sampler_t s);
 int gpirt_sampler_summary_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count);
