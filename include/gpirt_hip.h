@@ -365,7 +365,8 @@ int gpirt_mcmc_summary(const double* h_y, int64_t n, int64_t m, const double* h_
  * W = mean_j s_j^2 (ddof 1), var+ = (N-1)/N W + B/N, Rhat = sqrt(var+ / W); W = 0 gives +inf if B > 0 and NaN otherwise,
  * S < 4 gives NaN.  ESS = C S mean_c(lambda_c^2) / mean_c(sigma_c^2) with lambda_c^2 the chain's variance (ddof 1) and
  * sigma_c^2 = b/(a-1) sum_k (Ybar_ck - Ybar_c)^2 (Ybar_c: the mean of the chain's batch means); MCSE of the pooled mean =
- * sqrt(mean_c(sigma_c^2) / (C S)); a < 2 gives NaN. */
+ * sqrt(mean_c(sigma_c^2) / (C S)); a < 2 gives NaN.  Batch means all equal (mean_c(sigma_c^2) = 0) give MCSE 0 and
+ * ESS = x / 0: +inf where the chains vary (mean_c(lambda_c^2) > 0), NaN where every draw is equal. */
 #define GPIRT_SUM_DIAG       16
 /* chain c's GPIRT_RNG_ITEM seed: chain 0 uses seed; chain c >= 1 the splitmix64 finaliser of seed + c GAMMA:
  * z = (z ^ (z >> 30)) M1; z = (z ^ (z >> 27)) M2; z ^ (z >> 31) */
@@ -457,8 +458,9 @@ int gpirt_irf_band_edges(double* out);
 /* What gpirt_summary_quantiles / gpirt_mcmc_quantiles return: a HOST pointer per output (NULL: not wanted; an output
  * whose part the states lack is refused).  T = C S pooled draws, a reflected chain entering with its grid index
  * reversed (k -> 1000 - k, for theta and for f*'s grid axis).
- * theta_q (nprobs x n): the ceil(q T)-th smallest pooled draw (1-based; q = 0: the smallest), theta_median the same for
- * q = 0.5, theta_mode the most frequent grid point (the lowest on a tie), theta_hist (1001 x n) the pooled counts;
+ * theta_q (nprobs x n): the ceil(q T)-th smallest pooled draw (1-based; q = 0: the smallest; q T, here and below, is
+ * the fp64 product), theta_median the same for q = 0.5, theta_mode the most frequent grid point (the lowest on a
+ * tie), theta_hist (1001 x n) the pooled counts;
  * NaN (the histogram: as counted) for a respondent with a draw off the grid.  (Needs GPIRT_SUM_THETA_HIST.)
  * theta_rhat_bulk / _tail / theta_rhat (n; needs GPIRT_SUM_DIAG too): the rank-normalised split-R-hat of Vehtari et al.
  * (2021), exact from the half histograms.  Bulk: the 2C halves' T' = 2C floor(S/2) draws ranked with ties averaged,
@@ -466,7 +468,8 @@ int gpirt_irf_band_edges(double* out);
  * median of all T draws).  theta_rhat = max(bulk, tail), NaN if either is.
  * irf_q (nprobs x 1001 x m; needs GPIRT_SUM_IRF_BAND): in probability, t = q T, b = the first bin with a draw whose
  * cumulative count is >= t (one pass over a cell's bins, the probabilities in ascending order), (b + (t - cum_(b-1)) / count_b) / 256: within 1 / 256 of the ceil(q T)-th smallest
- * plogis(f*) draw (NaN for a cell with a NaN draw).  irf_p_mean (1001 x m): the mean of plogis(f*) over the T draws.
+ * plogis(f*) draw (NaN for a cell with a NaN draw).  irf_p_mean (1001 x m): the mean of plogis(f*) over the T draws
+ * (NaN for a cell with a NaN draw: the NaN enters the sum).
  * reflected: C flags, as gpirt_diag's. */
 typedef struct gpirt_quantiles {
     int            nprobs;

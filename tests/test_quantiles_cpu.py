@@ -78,6 +78,13 @@ def test_band_edges(lib):
     assert np.abs(plogis(e) - np.arange(1, 256) / 256.0).max() <= 1e-15
     assert e[127] == 0.0
     assert lib.gpirt_irf_band_edges(None) != 0
+    # within 4 ulp of the correctly rounded logit(b / 256) (log(b) - log(256 - b) was up to 109 ulp off near b = 128)
+    import math
+    import mpmath
+    with mpmath.workprec(200):
+        exact = [float(mpmath.log(mpmath.mpf(b) / (256 - b))) for b in range(1, 256)]
+    for b, (got, want) in enumerate(zip(e, exact), 1):
+        assert abs(got - want) <= 4 * math.ulp(want), (b, got, want)
 
 
 def _mcmc_q(lib, chains=2, rng_item=True, rs=None, q=None, pooled_parts=None, probs=(0.1, 0.9)):
