@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GPIRT_HIP_LIBRARY") or os.path.join(HERE, "libgpirt_h
 NGRID = 1001
 RNG_RSTREAM, RNG_ITEM = 0, 1
 ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3, 4, 5, 6, 7
+ST_PPC = 8                        # the replicate of the posterior predictive checks (gpirt_amd.ppc)
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
@@ -94,6 +95,18 @@ class Quantiles(C.Structure):
         (k, C.POINTER(C.c_double)) for k in ("theta_q", "theta_median", "theta_mode", "theta_hist", "theta_rhat_bulk",
                                              "theta_rhat_tail", "theta_rhat", "irf_q", "irf_p_mean")] + [
         ("reflected", C.POINTER(C.c_int)), ("scalars", C.c_double * len(QNT_SCALARS)), ("reserved", C.c_int64 * 4)]
+
+
+# posterior predictive checks (include/gpirt_hip.h GPIRT_PPC_*): the fields of a unit, in order
+PPC_FIELDS = ("n_obs", "obs_yes", "rep_yes_mean", "rep_yes_var", "yes_ge", "yes_gt", "dev_obs_mean", "dev_rep_mean", "dev_ge",
+              "correct_mean", "nonfinite", "draws", "rep_yes_sum", "rep_yes_sumsq", "correct_sum")
+
+
+class Ppc(C.Structure):
+    """gpirt_ppc (include/gpirt_hip.h): a host pointer per field for the items (m) and the respondents (n) (NULL: not
+    wanted), the whole matrix's fields and reserved words."""
+    _fields_ = [("item", C.POINTER(C.c_double) * len(PPC_FIELDS)), ("respondent", C.POINTER(C.c_double) * len(PPC_FIELDS)),
+                ("totals", C.c_double * len(PPC_FIELDS)), ("reserved", C.c_int64 * 4)]
 
 
 class Options(C.Structure):
@@ -192,6 +205,15 @@ SIGNATURES = {
     "gpirt_mcmc_quantiles": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                      TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                      C.POINTER(Quantiles)]),
+    "gpirt_sampler_ppc_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ppc_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_ppc_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
+    "gpirt_sampler_ppc_totals": (_i32, [_vp, _dp]),
+    "gpirt_sampler_ppc_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Ppc)]),
+    "gpirt_mcmc_ppc": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                               C.POINTER(Quantiles), C.POINTER(Ppc)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

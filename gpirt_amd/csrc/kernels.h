@@ -337,6 +337,41 @@ int summary_seal(hipStream_t stream, SummaryState* s, const double* irf_sum, int
 int chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align, double* h_irfs,
                    gpirt_summary* pooled, gpirt_diag* diag);
 
+// ppc.hip: posterior predictive checks accumulated one draw at a time (gpirt_sampler_ppc_*, gpirt_mcmc_ppc).  The state is ONE
+// device block of 8-byte words: a header of 8 int64 (n, m, draws, layout version, item0, 0, 0, 0), then PPC_NARRAYS arrays of
+// ppc_stride(n, m) words each, unit k = item k (k < m), respondent k - m (k < m + n) or the whole matrix (k = m + n).
+constexpr int PPC_LAYOUT_VERSION = 1;
+constexpr int PPC_HEADER_WORDS = 8;
+enum { PPC_N_OBS, PPC_OBS_YES, PPC_SUM_R, PPC_SUM_R2, PPC_YES_GE, PPC_YES_GT, PPC_DEV_GE, PPC_CORRECT, PPC_NONFINITE,   // uint64
+       PPC_DEV_OBS, PPC_DEV_REP,                                                                                        // double sums
+       PPC_NARRAYS };
+int64_t ppc_stride(int64_t n, int64_t m);           // n + m + 1 units, padded to an even count
+int64_t ppc_state_words(int64_t n, int64_t m);
+struct PpcState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
+    int strips = 0, rblocks = 0;
+    uint64_t* block = nullptr;                        // header + accumulators
+    double *rowd = nullptr, *cold = nullptr;          // a draw's partials: [strip][3][n], [row block][3][m]
+    uint32_t *rowi = nullptr, *coli = nullptr;        //   ... their packed counts
+    double* unit_d = nullptr; uint64_t* unit_i = nullptr;     // the items' sums of a draw ([3][m]), for the total
+    std::vector<void*> allocs;
+};
+// zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written
+int ppc_alloc(hipStream_t stream, PpcState* s, int64_t n, int64_t m, int64_t item0, const double* y);
+void ppc_free(PpcState* s);
+// adds the replicate of one draw: f, mu, y n x m on the device; iter = the completed-iteration counter of that state
+int launch_ppc_accumulate(hipStream_t stream, PpcState* s, const double* f, const double* mu, const double* y, uint64_t seed,
+                          uint32_t iter);
+int ppc_seal(hipStream_t stream, PpcState* s);      // refreshes the header (synchronises)
+int ppc_fetch(hipStream_t stream, PpcState* s, std::vector<uint64_t>& host);     // seals and copies the block to the host
+int ppc_field_index(const char* name);              // GPIRT_PPC_* of a field name, -1 if unknown
+// finished values from a block on the host
+void ppc_fill(const uint64_t* blk, int fld, bool respondents, double* out, int64_t count);
+void ppc_fill_totals(const uint64_t* blk, double* out);
+void ppc_fill_struct(const uint64_t* blk, gpirt_ppc* out);
+int ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

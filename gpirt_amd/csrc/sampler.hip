@@ -140,6 +140,7 @@ struct gpirt_sampler_s {
     std::vector<void*> allocs;
     std::vector<double> host_tmp;
     SummaryState sum;                 // posterior summaries (gpirt_sampler_summary_enable; parts == 0: off)
+    PpcState ppc;                     // posterior predictive checks (gpirt_sampler_ppc_enable; on == false: off)
 };
 
 namespace {
@@ -1199,6 +1200,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     if (s->ev_beta) hipEventDestroy(s->ev_beta);
     for (void* p : s->allocs) hipFree(p);
     summary_free(&s->sum);
+    ppc_free(&s->ppc);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -1499,6 +1501,72 @@ int gpirt_sampler_summary_totals(gpirt_sampler_t s, double* h_totals)
     return 0;
 }
 
+// ---- posterior predictive checks (ppc.hip) on the stage API -----------------------------------------------------------
+static int ppc_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on) return 0;
+    set_error("the posterior predictive checks are not enabled (gpirt_sampler_ppc_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_ppc_enable(gpirt_sampler_t s, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    ppc_free(&s->ppc);
+    if (!on) return 0;
+    const int rc = ppc_alloc(s->h->stream, &s->ppc, s->n, s->m, s->opt.item0, s->y);
+    if (rc) ppc_free(&s->ppc);
+    return rc;
+}
+
+int gpirt_sampler_ppc_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(ppc_needs_on(s));
+    GP_TRY(beta_sync(s));                     // draw_beta (mu) may still be deferred to the sampler's own stream
+    return launch_ppc_accumulate(s->h->stream, &s->ppc, s->f, s->mu, s->y, s->opt.seed, (uint32_t)s->iter);
+}
+
+int gpirt_sampler_ppc_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count)
+{
+    GP_ARG(s && name && h_out && count >= 0);
+    GP_TRY(ppc_needs_on(s));
+    const bool item = strncmp(name, "item_", 5) == 0, resp = strncmp(name, "respondent_", 11) == 0;
+    const int fld = item ? ppc_field_index(name + 5) : resp ? ppc_field_index(name + 11) : -1;
+    if (fld < 0) { set_error("unknown PPC field '%s'", name); return GPIRT_E_ARG; }
+    GP_ARG(count <= (item ? s->m : s->n));
+    std::vector<uint64_t> host;
+    GP_TRY(ppc_fetch(s->h->stream, &s->ppc, host));
+    ppc_fill(host.data(), fld, resp, h_out, count);
+    return 0;
+}
+
+int gpirt_sampler_ppc_totals(gpirt_sampler_t s, double* h_totals)
+{
+    GP_ARG(s && h_totals);
+    GP_TRY(ppc_needs_on(s));
+    std::vector<uint64_t> host;
+    GP_TRY(ppc_fetch(s->h->stream, &s->ppc, host));
+    ppc_fill_totals(host.data(), h_totals);
+    return 0;
+}
+
+int gpirt_sampler_ppc_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(ppc_needs_on(s));
+    GP_TRY(ppc_seal(s->h->stream, &s->ppc));
+    *d_state = s->ppc.block;
+    *bytes = ppc_state_words(s->n, s->m) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out)
+{
+    return ppc_combine(h, chains, d_states, out);
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -1730,6 +1798,7 @@ struct ChainRun {
     gpirt_handle_t h;
     SummaryState* keep;
     int base, ticks;
+    PpcState* keep_ppc;               // gpirt_mcmc_ppc: the chain also accumulates the PPC; its state outlives the sampler here
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -1778,6 +1847,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
             GP_TRY(summary_seal(h->stream, &s->sum, s->irf_sum, N));
             *cr->keep = std::move(s->sum);
             s->sum = SummaryState{};
+            if (cr->keep_ppc) {
+                GP_TRY(ppc_seal(h->stream, &s->ppc));
+                *cr->keep_ppc = std::move(s->ppc);
+                s->ppc = PpcState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -1799,6 +1873,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc) rc = store_sync(0);
     if (!rc && summarise)
         rc = cr ? gpirt_sampler_summary_enable_planned(s, sm->parts | GPIRT_SUM_DIAG, S_it) : gpirt_sampler_summary_enable(s, sm->parts);
+    const bool ppc = cr && cr->keep_ppc;
+    if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -1812,6 +1888,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 rc = gpirt_sampler_accumulate_irf(s);                          // :103
                 if (!rc) rc = store_sync(it - B_it + 1);
                 if (!rc && summarise) rc = gpirt_sampler_summary_accumulate(s);   // consumes nothing of R's stream
+                if (!rc && ppc) rc = gpirt_sampler_ppc_accumulate(s);             // nor does the replicate (counter-based)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -1899,6 +1976,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         // enqueues only once checkpoint k + 1 is verified
         if (summarise)
             GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y, d + off_fstar));
+        if (ppc)                                // the slot holds the state after k iterations
+            GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k));
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2034,7 +2113,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
-                      gpirt_quantiles* q)
+                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2056,10 +2135,12 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         for (int p = 0; p < q->nprobs; ++p) GP_ARG(q->probs[p] >= 0.0 && q->probs[p] <= 1.0);
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
     }
+    if (ppc) GP_ARG(ppc->reserved[0] == 0 && ppc->reserved[1] == 0 && ppc->reserved[2] == 0 && ppc->reserved[3] == 0);
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
     std::vector<SummaryState> keep((size_t)chains);
+    std::vector<PpcState> keep_ppc(ppc ? (size_t)chains : 0);
     const int total = S_it + B_it;
     int rc = 0;
     for (int c = 0; c < chains && !rc; ++c) {
@@ -2067,7 +2148,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         o.seed = gpirt_chain_seed(opts->seed, c);
         gpirt_summary sm{};
         sm.parts = parts | extra;
-        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total };
+        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2078,7 +2159,12 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
     if (!rc) rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag);
     if (!rc && q) rc = summary_quantiles(h, chains, st.data(), nullptr, align, q);
+    if (!rc && ppc) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].block;
+        rc = ppc_combine(h, chains, st.data(), ppc);
+    }
     for (auto& k : keep) summary_free(&k);
+    for (auto& k : keep_ppc) ppc_free(&k);
     gpirt_destroy(h);
     return rc;
 }
@@ -2123,6 +2209,23 @@ int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* 
     }
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND, rs, q);
+}
+
+// ---- posterior predictive checks ------------------------------------------------------------------------------------
+int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                   const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                   gpirt_ppc* ppc)
+{
+    GP_ARG(opts && ppc);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_ppc needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc);
 }
 
 }  // extern "C"

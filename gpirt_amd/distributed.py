@@ -239,6 +239,13 @@ class ShardedSampler:
     def summary_accumulate(self):
         self.engine.summary_accumulate()
 
+    # -- posterior predictive checks (gpirt_amd.ppc): not offered for item shards -- a respondent's statistics run over ALL
+    # items and would need one all-reduce per draw.  The replicate's uniforms are keyed by the global item index
+    # (item0 + j), so a later sharded form replicates exactly what one GPU does.
+    def ppc_enable(self, on=True):
+        raise ValueError("ShardedSampler: posterior predictive checks are not offered for item shards "
+                         "(the respondents' statistics would need an all-reduce per draw)")
+
     def summary_gather(self, name: str):
         """The full pointwise summary `name` (p_yes, lppd, p_waic, f_mean, f_var, beta_mean, beta_var) on every rank;
         theta_mean / theta_var are the local ones (identical on every rank)."""

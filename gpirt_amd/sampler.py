@@ -43,7 +43,8 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
 def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_prior_means=None,
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
-              progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None):
+              progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
+              ppc=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -74,6 +75,15 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       rank-normalised bulk / tail / max), irf (len(probs) x 1001 x m, in probability, within 1/256), irf_p_mean (E[P]),
       reflected and scalars.  Memory: the band is 1001 x m x 256 x 4 bytes per chain on the device (1.05 GB at
       m = 1024), theta's histograms 3 x 1001 x n x 4 bytes.  quantiles=None leaves every other path as it is.
+    ppc: True adds posterior predictive checks (gpirt_mcmc_ppc, gpirt_amd.ppc): after every sampling iteration the
+      device replicates the response matrix from that draw and compares the yes count and the deviance of the replicate
+      with the data's, per item, per respondent and overall, in O(n + m) memory.  The result gains "ppc": "item" and
+      "respondent" (dicts of arrays: n_obs, obs_yes, rep_yes_mean, rep_yes_var, yes_ge, yes_gt, dev_obs_mean,
+      dev_rep_mean, dev_ge, correct_mean, nonfinite, draws and the derived ppp_yes, ppp_yes_mid, ppp_dev) and "totals",
+      and -- the call runs gpirt_mcmc_chains's or gpirt_mcmc_quantiles's chains -- "summary" and "diagnostics" as with
+      chains (draws stacked per chain only with chains given).  The chain itself is untouched: the replicate draws from
+      the counter-based generator under both RNG contracts and consumes nothing of R's stream.  ppc=None leaves every
+      other path as it is.
     """
     from .ops import RStream
 
@@ -92,10 +102,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         rng = "item"
     elif preset is not None:
         raise ValueError(f"unknown preset {preset!r}")
-    if quantiles is not None:
+    if quantiles is not None or ppc:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles)
+                               align, quantiles, bool(ppc))
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -228,10 +238,12 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
-                    kstar_rank, device, progress, summaries, store_draws, align, probs):
+                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
-    gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them."""
+    gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
+    with the posterior predictive checks (probs may then be None: no quantiles)."""
     from . import chains as CH
+    from . import ppc as P
     from . import quantiles as Q
     from .ops import RStream
     lib = _lib.load()
@@ -277,7 +289,9 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     for k, a in arrays.items():
         setattr(sm, "h_" + k, _ptr(a))
     d, darr = CH.diag_struct(parts, n, m, C_)
-    q, qarr = Q.quantiles_struct(probs, n, m, C_)
+    q, qarr = Q.quantiles_struct(probs, n, m, C_) if probs is not None else (None, None)
+    if with_ppc:
+        pp, parr = P.struct(n, m)
 
     def _tick(ctx, it, total):
         if progress:
@@ -286,9 +300,14 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    rc = lib.gpirt_mcmc_quantiles(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                  rs.ptr if rs is not None else None, C.byref(q))
+    if with_ppc:
+        rc = lib.gpirt_mcmc_ppc(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp))
+    else:
+        rc = lib.gpirt_mcmc_quantiles(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                      int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm),
+                                      C.byref(d), rs.ptr if rs is not None else None, C.byref(q))
     if progress:
         print("\r100.000 % complete")
     if rc > 0:
@@ -301,8 +320,12 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         th = th.transpose(0, 2, 1) if th is not None else None
         be = be.transpose(0, 3, 2, 1) if be is not None else None
         ff = ff.transpose(0, 3, 2, 1) if ff is not None else None
-    return dict(theta=th, beta=be, f=ff, IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr),
-                quantiles=Q.quantiles_result(q, qarr))
+    out = dict(theta=th, beta=be, f=ff, IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr))
+    if q is not None:
+        out["quantiles"] = Q.quantiles_result(q, qarr)
+    if with_ppc:
+        out["ppc"] = P.result(pp, parr)
+    return out
 
 
 def _summary_arrays(parts: int, n: int, m: int) -> dict:
@@ -567,6 +590,52 @@ class Sampler:
         out = {k: self.summary_get(k) for k in _summary_arrays(parts, self.n, self.m)}
         if parts & _lib.SUM_WAIC:
             out["totals"] = self.summary_totals()
+        return out
+
+    # -- posterior predictive checks accumulated on the device (include/gpirt_hip.h gpirt_sampler_ppc_*, gpirt_amd.ppc)
+    def ppc_enable(self, on=True):
+        """Allocate and zero the PPC accumulators and count n_obs / obs_yes on the device (on=False frees them)."""
+        check(self.lib.gpirt_sampler_ppc_enable(self._s, int(bool(on))))
+
+    def ppc_accumulate(self):
+        """Add the replicate of the current state (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_ppc_accumulate")
+
+    def ppc_get(self, name: str) -> np.ndarray:
+        """One finished field: "item_<field>" (m values) or "respondent_<field>" (n), field one of _lib.PPC_FIELDS."""
+        out = np.empty(self.m if name.startswith("item_") else self.n)
+        check(self.lib.gpirt_sampler_ppc_get(self._s, name.encode(), _ptr(out), out.size))
+        return out
+
+    def ppc_totals(self) -> dict:
+        raw = (C.c_double * len(_lib.PPC_FIELDS))()
+        check(self.lib.gpirt_sampler_ppc_totals(self._s, raw))
+        return {k: float(raw[i]) for i, k in enumerate(_lib.PPC_FIELDS)}
+
+    def ppc_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the PPC accumulators, its header refreshed: what
+        gpirt_amd.ppc.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc(self) -> dict:
+        """Every field of the items and the respondents, the derived ppp_* values and "totals" (gpirt_amd.ppc.result's shape)."""
+        from . import ppc as P
+        out = {}
+        tot = self.ppc_totals()
+        for unit in ("item", "respondent"):
+            d = {k: self.ppc_get(f"{unit}_{k}") for k in _lib.PPC_FIELDS}
+            out[unit] = P.derive(d)
+        out["totals"] = {k: float(v) for k, v in P.derive(dict(tot)).items()}
         return out
 
     def enable_timing(self, on=True):

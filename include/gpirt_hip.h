@@ -53,14 +53,15 @@ enum { GPIRT_RNG_RSTREAM = 0, GPIRT_RNG_ITEM = 1 };
 /* stage ids of the GPIRT_RNG_ITEM contract */
 enum {
     GPIRT_ST_INIT_F = 1, GPIRT_ST_INIT_BETA = 2, GPIRT_ST_F_Z = 3, GPIRT_ST_F_ESS = 4,
-    GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7
+    GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
+    GPIRT_ST_PPC = 8      /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
 };
 
 typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -503,6 +504,88 @@ int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* 
                          gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
                          double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
                          gpirt_rstream_t rs, gpirt_quantiles* q);
+
+/* ------------------------------------------------------ posterior predictive checks: items, respondents, the whole matrix --- */
+/* Does the model fit these items and these respondents?  For sampling draw s, the state after that iteration's step gives
+ *   g_ij = f_ij + mu_ij,  p_ij = plogis(g_ij)  (the arithmetic of GPIRT_SUM_PRED: e = exp(-|g|), p = 1 / (1 + e) for
+ *   g >= 0 and e / (1 + e) otherwise),  O = the observed cells, those whose y_ij is not NaN.
+ * The replicate is yrep_ij = +1 if u_ij < p_ij, else -1, with
+ *   u_ij = the item-RNG uniform of (seed, iter, GPIRT_ST_PPC, item0 + j, i)
+ * -- what gpirt_item_uniforms(h, seed, iter, GPIRT_ST_PPC, item0, m, n, .) writes at [i + j n].  iter is the sampler's
+ * completed-iteration counter at the time of the call, seed the chain's opts->seed (chain c of several:
+ * gpirt_chain_seed(seed, c)).  The uniforms are keyed by the GLOBAL item index and the respondent: they depend neither on
+ * the launch geometry nor on a sharding of the items.  The replicate uses the counter-based generator under BOTH RNG
+ * contracts: with GPIRT_RNG_RSTREAM it consumes nothing of R's stream, and under either contract the chain is untouched.
+ * Per unit -- item j over i in O_j, respondent i over j in O_i, and the whole matrix over O -- and draw:
+ *   R = #{yrep = +1},  T = #{y = +1} (fixed; counted on the device at enable),
+ *   D(z) = 2 sum softplus(-z g), the deviance of z = y or z = yrep, softplus(a) = log1p(exp(-|a|)) + max(a, 0),
+ *   Delta = sum over the cells with yrep != y of y g.  softplus(a) - softplus(-a) = a, so D(yrep) - D(y) = 2 Delta in exact
+ *   algebra; D(yrep) >= D(y) is DECIDED as Delta >= 0: exactly 0 when nothing flipped, no cancellation of two large sums,
+ *   correct = #{(g > 0) == (y = +1)}, the correctly classified cells (PCP and APRE follow from it).
+ * Fields of a unit (GPIRT_PPC_*; every one a double on the way out, counts included):
+ *   n_obs, obs_yes = T, rep_yes_mean and rep_yes_var = the mean and the variance (ddof 1) of R over the draws, from the
+ *   exact integer sums rep_yes_sum = sum R and rep_yes_sumsq = sum R^2 (uint64): mean = sum R / S,
+ *   var = (S sum R^2 - (sum R)^2) / (S (S - 1)) with the numerator exact and rounded once;
+ *   yes_ge = #{s : R >= T}, yes_gt = #{s : R > T} (the host derives ppp_yes = yes_ge / S and the mid-p value
+ *   (yes_ge + yes_gt) / 2S); dev_obs_mean, dev_rep_mean = the means of D(y), D(yrep); dev_ge = #{s : Delta >= 0};
+ *   correct_mean = correct_sum / S; nonfinite; draws.
+ * A non-finite g in an observed cell makes that draw count in `nonfinite` of its row, its column and the whole matrix, and
+ * enter NO other accumulator of those three units; S above is the unit's draws - nonfinite, the draws that entered.  A
+ * unit with no observed cell has NaN means and every count 0; so has a mean with S = 0, and the variance with S < 2.
+ * No floating-point atomics: every double sum is reduced in a fixed order (rows in blocks of 256 in order, items in
+ * strips of 32 in order, draws in order), so two runs give bit-identical states.
+ * Pooling C chains adds the integer sums and counts and adds the double sums in chain order.  The reflection
+ * theta -> -theta maps f(theta) to f(-theta) and leaves f_ij + mu_ij of every cell as it is: every PPC output is unchanged
+ * by it, so the pooling takes no signs and no alignment. */
+#define GPIRT_PPC_N_OBS          0
+#define GPIRT_PPC_OBS_YES        1
+#define GPIRT_PPC_REP_YES_MEAN   2
+#define GPIRT_PPC_REP_YES_VAR    3
+#define GPIRT_PPC_YES_GE         4
+#define GPIRT_PPC_YES_GT         5
+#define GPIRT_PPC_DEV_OBS_MEAN   6
+#define GPIRT_PPC_DEV_REP_MEAN   7
+#define GPIRT_PPC_DEV_GE         8
+#define GPIRT_PPC_CORRECT_MEAN   9
+#define GPIRT_PPC_NONFINITE      10
+#define GPIRT_PPC_DRAWS          11   /* every draw accumulated (pooled: over the chains) */
+#define GPIRT_PPC_REP_YES_SUM    12
+#define GPIRT_PPC_REP_YES_SUMSQ  13
+#define GPIRT_PPC_CORRECT_SUM    14
+#define GPIRT_PPC_NFIELDS        15
+/* HOST pointers per field (NULL: not wanted): item[fld] m values, respondent[fld] n values; totals[fld] is always written */
+typedef struct gpirt_ppc {
+    double*  item[GPIRT_PPC_NFIELDS];
+    double*  respondent[GPIRT_PPC_NFIELDS];
+    double   totals[GPIRT_PPC_NFIELDS];
+    int64_t  reserved[4];     /* must be 0 */
+} gpirt_ppc;
+/* Stage API.  ppc_enable(on != 0) allocates and zeroes the accumulators and counts n_obs and obs_yes (0 frees them);
+ * ppc_accumulate adds the replicate of the CURRENT state as one draw (call it after the step of a sampling iteration);
+ * ppc_get finishes one field by name -- "item_" or "respondent_" and the lower-case name of a GPIRT_PPC_* field, e.g.
+ * "item_yes_ge" (count <= m or n) --, ppc_totals writes the GPIRT_PPC_NFIELDS fields of the whole matrix.
+ * The accumulators live in ONE device block of 8-byte words, apart from the summaries' block: a header of 8 int64 (n, m,
+ * draws done, layout version, item0, 0, 0, 0), then 11 arrays of n + m + 1 words (padded to an even count), unit k =
+ * item k, respondent k - m, the whole matrix last: uint64 n_obs, obs_yes, sum R, sum R^2, yes_ge, yes_gt, dev_ge, correct
+ * sum, nonfinite, then the double sums of D(y) and D(yrep).  ppc_state refreshes the header and returns the block (valid
+ * until ppc_enable is called again or the sampler is destroyed); gpirt_ppc_combine pools C such blocks (device pointers
+ * on h's device; the same n, m, item0 and response matrix). */
+int gpirt_sampler_ppc_enable(gpirt_sampler_t s, int on);
+int gpirt_sampler_ppc_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_ppc_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count);
+int gpirt_sampler_ppc_totals(gpirt_sampler_t s, double* h_totals);
+int gpirt_sampler_ppc_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out);
+/* gpirt_mcmc_quantiles with the checks (library version 107): the same chains -- draws, IRFs, pooled, diag, the
+ * quantiles and R's stream position bit-identical --, each accumulating the PPC after every sampling iteration's
+ * summaries, pooled into ppc (required).  q may be NULL: the chains are then gpirt_mcmc_chains's (no histograms, no bands),
+ * and rs != NULL with chains = 1 runs gpirt_mcmc_summary's chain. */
+int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                   int sample_iterations, int burn_iterations, const double* h_prior_means,
+                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
