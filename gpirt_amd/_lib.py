@@ -109,6 +109,23 @@ class Ppc(C.Structure):
                 ("totals", C.c_double * len(PPC_FIELDS)), ("reserved", C.c_int64 * 4)]
 
 
+# rank posteriors (include/gpirt_hip.h gpirt_ranks)
+RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
+
+
+class Ranks(C.Structure):
+    """gpirt_ranks (include/gpirt_hip.h): the probabilities, the pivots (in: as given; out: closed and sorted), host
+    pointers per output (NULL: not wanted) and the counts."""
+    _fields_ = [("probs", C.POINTER(C.c_double)), ("nprobs", C.c_int), ("n_pivots", C.c_int),
+                ("pivots", C.c_int64 * RANK_MAX_PIVOTS_CLOSED), ("pairwise", C.c_int), ("reserved0", C.c_int),
+                ("rank_mean", C.POINTER(C.c_double)), ("rank_var", C.POINTER(C.c_double)), ("rank_q", C.POINTER(C.c_double)),
+                ("p_pivot", C.POINTER(C.c_double)), ("pivot_share", C.POINTER(C.c_double)),
+                ("rank2_sum", C.POINTER(C.c_uint64)), ("rank2_sumsq", C.POINTER(C.c_uint64)),
+                ("rank_hist", C.POINTER(C.c_uint32)), ("pivot_cover", C.POINTER(C.c_uint32)), ("lt", C.POINTER(C.c_uint32)),
+                ("draws", C.c_int64), ("skipped", C.c_int64), ("B", C.c_int64), ("w", C.c_int64),
+                ("rank_bin_width", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -214,6 +231,14 @@ SIGNATURES = {
     "gpirt_mcmc_ppc": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                C.POINTER(Quantiles), C.POINTER(Ppc)]),
+    "gpirt_sampler_rank_enable": (_i32, [_vp, C.POINTER(C.c_int64), _i32, _i32]),
+    "gpirt_sampler_rank_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_rank_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_rank_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_rank_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Ranks)]),
+    "gpirt_mcmc_ranks": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

@@ -335,7 +335,7 @@ int launch_summary_totals(hipStream_t stream, const SummaryState* s, const doubl
 int summary_seal(hipStream_t stream, SummaryState* s, const double* irf_sum, int64_t N);
 // gpirt_chains_combine on h's stream (arguments as in include/gpirt_hip.h)
 int chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align, double* h_irfs,
-                   gpirt_summary* pooled, gpirt_diag* diag);
+                   gpirt_summary* pooled, gpirt_diag* diag, int* signs_out = nullptr);     // signs_out: the C signs it decided
 
 // ppc.hip: posterior predictive checks accumulated one draw at a time (gpirt_sampler_ppc_*, gpirt_mcmc_ppc).  The state is ONE
 // device block of 8-byte words: a header of 8 int64 (n, m, draws, layout version, item0, 0, 0, 0), then PPC_NARRAYS arrays of
@@ -371,6 +371,34 @@ void ppc_fill(const uint64_t* blk, int fld, bool respondents, double* out, int64
 void ppc_fill_totals(const uint64_t* blk, double* out);
 void ppc_fill_struct(const uint64_t* blk, gpirt_ppc* out);
 int ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out);
+
+// ranks.hip: rank posteriors accumulated one theta draw at a time (gpirt_sampler_rank_*, gpirt_mcmc_ranks).  The state is ONE
+// device block of 8-byte words: a header of RANK_HEADER_WORDS int64 (n, counted draws, skipped draws, layout version, B, w,
+// the closed pivots' count, the pairwise flag, then the closed pivots, sorted, in 32 words), uint64 rank2_sum[n] and
+// rank2_sumsq[n], double pivot_share[np][n], uint32 pivot_cover[np][n], uint32 rank_hist[n][B] (each padded to a whole word)
+// and, with the pairwise flag, on a 16-byte boundary uint32 lt[n][ld], ld = n rounded up to 4 (the padding stays 0).  The
+// header's two draw counters are kept by the kernel itself (the device decides whether a draw is skipped).
+constexpr int RANK_LAYOUT_VERSION = 1;
+constexpr int RANK_HEADER_WORDS = 8 + GPIRT_RANK_MAX_PIVOTS_CLOSED;
+struct RankState {
+    bool on = false, pairwise = false;
+    int64_t n = 0, B = 0, w = 0, pad = 0, ld = 0;
+    int np = 0;
+    int64_t piv[GPIRT_RANK_MAX_PIVOTS_CLOSED] = {};
+    uint64_t* block = nullptr;
+    uint16_t* kidx = nullptr;                         // the last draw's grid indices, zero padded to ld (+ 8)
+    uint32_t* ctl = nullptr;                          // [0]: 1 if the last draw counted
+    std::vector<void*> allocs;
+};
+void rank_bins(int64_t n, int64_t* B, int64_t* w, int64_t* pad);      // the histogram's bins over R2 = 2 .. 2n
+// the sorted closure of the pivots under q <-> n + 1 - q (n_pivots = 0: the median position(s)); returns its size (<= 32)
+int rank_close_pivots(int64_t n, const int64_t* pivots, int n_pivots, int64_t* closed);
+int64_t rank_state_words(const RankState* s);
+int rank_alloc(hipStream_t stream, RankState* s, int64_t n, const int64_t* pivots, int n_pivots, int pairwise);
+void rank_free(RankState* s);
+int launch_rank_accumulate(hipStream_t stream, RankState* s, const double* theta);    // theta: n doubles on the device
+int rank_get(hipStream_t stream, RankState* s, const char* name, void* h_out, int64_t bytes);
+int rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out);
 
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi

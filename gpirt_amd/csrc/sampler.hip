@@ -141,6 +141,7 @@ struct gpirt_sampler_s {
     std::vector<double> host_tmp;
     SummaryState sum;                 // posterior summaries (gpirt_sampler_summary_enable; parts == 0: off)
     PpcState ppc;                     // posterior predictive checks (gpirt_sampler_ppc_enable; on == false: off)
+    RankState rank;                   // rank posteriors (gpirt_sampler_rank_enable; on == false: off)
 };
 
 namespace {
@@ -1201,6 +1202,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     for (void* p : s->allocs) hipFree(p);
     summary_free(&s->sum);
     ppc_free(&s->ppc);
+    rank_free(&s->rank);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -1567,6 +1569,54 @@ int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states,
     return ppc_combine(h, chains, d_states, out);
 }
 
+// ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
+static int rank_needs_on(gpirt_sampler_t s)
+{
+    if (s->rank.on) return 0;
+    set_error("the rank posteriors are not enabled (gpirt_sampler_rank_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_rank_enable(gpirt_sampler_t s, const int64_t* pivots, int n_pivots, int pairwise)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    rank_free(&s->rank);
+    if (!pivots && n_pivots < 0) return 0;
+    const int rc = rank_alloc(s->h->stream, &s->rank, s->n, pivots, n_pivots, pairwise);
+    if (rc) rank_free(&s->rank);
+    return rc;
+}
+
+int gpirt_sampler_rank_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(rank_needs_on(s));
+    return launch_rank_accumulate(s->h->stream, &s->rank, s->theta);
+}
+
+int gpirt_sampler_rank_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(rank_needs_on(s));
+    return rank_get(s->h->stream, &s->rank, name, h_out, bytes);
+}
+
+int gpirt_sampler_rank_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(rank_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the header's counters are the kernel's
+    *d_state = s->rank.block;
+    *bytes = rank_state_words(&s->rank) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out)
+{
+    return rank_combine(h, chains, d_states, signs, out);
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -1799,6 +1849,8 @@ struct ChainRun {
     SummaryState* keep;
     int base, ticks;
     PpcState* keep_ppc;               // gpirt_mcmc_ppc: the chain also accumulates the PPC; its state outlives the sampler here
+    RankState* keep_rank;             // gpirt_mcmc_ranks: ... and the rank posteriors (the state names pivots and pairwise)
+    const gpirt_ranks* ranks;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -1852,6 +1904,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_ppc = std::move(s->ppc);
                 s->ppc = PpcState{};
             }
+            if (cr->keep_rank) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_rank = std::move(s->rank);
+                s->rank = RankState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -1875,6 +1932,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         rc = cr ? gpirt_sampler_summary_enable_planned(s, sm->parts | GPIRT_SUM_DIAG, S_it) : gpirt_sampler_summary_enable(s, sm->parts);
     const bool ppc = cr && cr->keep_ppc;
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
+    const bool ranks = cr && cr->keep_rank;
+    if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -1889,6 +1948,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc) rc = store_sync(it - B_it + 1);
                 if (!rc && summarise) rc = gpirt_sampler_summary_accumulate(s);   // consumes nothing of R's stream
                 if (!rc && ppc) rc = gpirt_sampler_ppc_accumulate(s);             // nor does the replicate (counter-based)
+                if (!rc && ranks) rc = gpirt_sampler_rank_accumulate(s);          // the ranks draw nothing at all
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -1978,6 +2038,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
             GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y, d + off_fstar));
         if (ppc)                                // the slot holds the state after k iterations
             GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k));
+        if (ranks) GP_TRY(launch_rank_accumulate(h->stream, &s->rank, d));      // the slot's theta
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2113,7 +2174,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
-                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr)
+                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2136,11 +2197,30 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
     }
     if (ppc) GP_ARG(ppc->reserved[0] == 0 && ppc->reserved[1] == 0 && ppc->reserved[2] == 0 && ppc->reserved[3] == 0);
+    if (ranks) {
+        GP_ARG(ranks->reserved0 == 0 && ranks->reserved[0] == 0 && ranks->reserved[1] == 0 && ranks->reserved[2] == 0 && ranks->reserved[3] == 0);
+        GP_ARG(ranks->nprobs >= 0 && (ranks->nprobs == 0 || ranks->probs));
+        for (int p = 0; p < ranks->nprobs; ++p) GP_ARG(ranks->probs[p] >= 0.0 && ranks->probs[p] <= 1.0);
+        GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
+        if (n > GPIRT_RANK_MAX_N) { set_error("rank posteriors: n = %lld is beyond %d respondents", (long long)n, GPIRT_RANK_MAX_N); return GPIRT_E_ARG; }
+        if (ranks->n_pivots < 0 || ranks->n_pivots > GPIRT_RANK_MAX_PIVOTS) {
+            set_error("rank posteriors: %d pivots given, at most %d are taken", ranks->n_pivots, GPIRT_RANK_MAX_PIVOTS);
+            return GPIRT_E_ARG;
+        }
+        for (int p = 0; p < ranks->n_pivots; ++p)
+            if (ranks->pivots[p] < 1 || ranks->pivots[p] > n) {
+                set_error("rank posteriors: pivot %lld is outside 1..%lld", (long long)ranks->pivots[p], (long long)n);
+                return GPIRT_E_ARG;
+            }
+        GP_ARG(!(ranks->lt && !ranks->pairwise));
+    }
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
     std::vector<SummaryState> keep((size_t)chains);
     std::vector<PpcState> keep_ppc(ppc ? (size_t)chains : 0);
+    std::vector<RankState> keep_rank(ranks ? (size_t)chains : 0);
+    const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
     for (int c = 0; c < chains && !rc; ++c) {
@@ -2148,7 +2228,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         o.seed = gpirt_chain_seed(opts->seed, c);
         gpirt_summary sm{};
         sm.parts = parts | extra;
-        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr };
+        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
+                           ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2157,14 +2238,20 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     }
     std::vector<const void*> st((size_t)chains);
     for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
-    if (!rc) rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag);
+    std::vector<int> sg((size_t)chains, 1);
+    if (!rc) rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag, sg.data());
     if (!rc && q) rc = summary_quantiles(h, chains, st.data(), nullptr, align, q);
     if (!rc && ppc) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].block;
         rc = ppc_combine(h, chains, st.data(), ppc);
     }
     for (auto& k : keep) summary_free(&k);
+    if (!rc && ranks) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_rank[(size_t)c].block;
+        rc = rank_combine(h, chains, st.data(), sg.data(), ranks);
+    }
     for (auto& k : keep_ppc) ppc_free(&k);
+    for (auto& k : keep_rank) rank_free(&k);
     gpirt_destroy(h);
     return rc;
 }
@@ -2226,6 +2313,23 @@ int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_thet
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc);
+}
+
+// ---- rank posteriors ------------------------------------------------------------------------------------------------------
+int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                     gpirt_ppc* ppc, gpirt_ranks* ranks)
+{
+    GP_ARG(opts && ranks);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_ranks needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks);
 }
 
 }  // extern "C"

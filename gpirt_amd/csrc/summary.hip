@@ -937,7 +937,7 @@ int chain_signs(hipStream_t st, int C, const double* const* d_st, int64_t tb_mea
 }  // namespace
 
 int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const int* signs, int align, double* h_irfs,
-                   gpirt_summary* pooled, gpirt_diag* diag)
+                   gpirt_summary* pooled, gpirt_diag* diag, int* signs_out)
 {
     GP_ARG(h && C >= 1 && d_states);
     hipStream_t st = h->stream;
@@ -969,6 +969,8 @@ int chains_combine(gpirt_handle_t h, int C, const void* const* d_states, const i
     double* d_dot = d_ptrs + 2 * C;
     GP_HIP(hipMemcpyAsync(d_ptrs, d_states, sizeof(void*) * (size_t)C, hipMemcpyHostToDevice, st));
     GP_TRY(chain_signs(st, C, d_st, L.tb_mean, n, signs, align, d_dot, sg));
+    if (signs_out)
+        for (int c = 0; c < C; ++c) signs_out[c] = sg[(size_t)c] < 0.0 ? -1 : 1;
     GP_HIP(hipMemcpyAsync(d_sg, sg.data(), sizeof(double) * (size_t)C, hipMemcpyHostToDevice, st));
 
     SummaryState P;                              // the pooled accumulators: a chain of C S draws

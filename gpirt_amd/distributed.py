@@ -246,6 +246,16 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: posterior predictive checks are not offered for item shards "
                          "(the respondents' statistics would need an all-reduce per draw)")
 
+    # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
+    def rank_enable(self, on=True, pivots="median", pairwise=False):
+        self.engine.rank_enable(on, pivots, pairwise)
+
+    def rank_accumulate(self):
+        self.engine.rank_accumulate()
+
+    def ranks(self, probs=(0.025, 0.5, 0.975)):
+        return self.engine.ranks(probs)
+
     def summary_gather(self, name: str):
         """The full pointwise summary `name` (p_yes, lppd, p_waic, f_mean, f_var, beta_mean, beta_var) on every rank;
         theta_mean / theta_var are the local ones (identical on every rank)."""

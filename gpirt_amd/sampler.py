@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None):
+              ppc=None, ranks=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -84,6 +84,17 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       chains (draws stacked per chain only with chains given).  The chain itself is untouched: the replicate draws from
       the counter-based generator under both RNG contracts and consumes nothing of R's stream.  ppc=None leaves every
       other path as it is.
+    ranks: True, or dict(pivots="median", pairwise=False, probs=(0.025, 0.5, 0.975)), adds the rank posteriors
+      (gpirt_mcmc_ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
+      the smallest; ties take the mid-rank) and accumulates, in "ranks": rank_mean, rank_var, rank_quantiles
+      (len(probs) x n, a rank-histogram bin's upper edge; exact for n <= 512), rank_bin_width, order (argsort of
+      rank_mean), pivots (the positions asked for -- "median" and / or positions in 1..n, at most 16 --, closed under
+      q <-> n + 1 - q and sorted), p_pivot and pivot_cover (len(pivots) x n), p_less (n x n, P(theta_i < theta_j)) or
+      None, draws, skipped_draws (a draw with any theta off the grid is skipped whole), and the raw rank2_sum,
+      rank2_sumsq, rank_hist, pivot_share, lt.  Memory with pairwise=True: 4 n^2 bytes per chain on the device (268 MB
+      at n = 8192).  Chains are pooled with the reflection "diagnostics" reports.  Nothing is drawn: the chain is
+      untouched under both RNG contracts.  "summary" and "diagnostics" come as with ppc.  ranks=None leaves every other
+      path as it is.
     """
     from .ops import RStream
 
@@ -102,10 +113,19 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         rng = "item"
     elif preset is not None:
         raise ValueError(f"unknown preset {preset!r}")
-    if quantiles is not None or ppc:
+    if ranks is not None and ranks is not False:
+        if ranks is not True and not isinstance(ranks, dict):
+            raise ValueError("ranks must be None, False, True or a dict(pivots=..., pairwise=..., probs=...)")
+        ranks = dict(ranks) if isinstance(ranks, dict) else {}
+        unknown = set(ranks) - {"pivots", "pairwise", "probs"}
+        if unknown:
+            raise ValueError(f"ranks: unknown keys {sorted(unknown)}")
+    else:
+        ranks = None
+    if quantiles is not None or ppc or ranks is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc))
+                               align, quantiles, bool(ppc), ranks)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -238,11 +258,13 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
-                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False):
+                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
-    with the posterior predictive checks (probs may then be None: no quantiles)."""
+    with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
+    same chains with the rank posteriors (with or without the checks)."""
     from . import chains as CH
+    from . import ranks as RK
     from . import ppc as P
     from . import quantiles as Q
     from .ops import RStream
@@ -292,6 +314,9 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     q, qarr = Q.quantiles_struct(probs, n, m, C_) if probs is not None else (None, None)
     if with_ppc:
         pp, parr = P.struct(n, m)
+    if ranks is not None:
+        rk, rkarr = RK.struct(n, ranks.get("pivots", "median"), ranks.get("probs", RK.DEFAULT_PROBS),
+                              bool(ranks.get("pairwise", False)))
 
     def _tick(ctx, it, total):
         if progress:
@@ -300,7 +325,12 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if with_ppc:
+    if ranks is not None:
+        rc = lib.gpirt_mcmc_ranks(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
+                                  C.byref(pp) if with_ppc else None, C.byref(rk))
+    elif with_ppc:
         rc = lib.gpirt_mcmc_ppc(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
                                 int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
                                 rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp))
@@ -325,6 +355,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["quantiles"] = Q.quantiles_result(q, qarr)
     if with_ppc:
         out["ppc"] = P.result(pp, parr)
+    if ranks is not None:
+        out["ranks"] = RK.result(rk, rkarr)
     return out
 
 
@@ -637,6 +669,61 @@ class Sampler:
             out[unit] = P.derive(d)
         out["totals"] = {k: float(v) for k, v in P.derive(dict(tot)).items()}
         return out
+
+    # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
+    def rank_enable(self, on=True, pivots="median", pairwise=False):
+        """Allocate and zero the rank accumulators for `pivots` ("median" and / or positions in 1..n, at most 16; the
+        library closes the set under q <-> n + 1 - q); pairwise=True keeps lt (4 n^2 bytes).  on=False frees them."""
+        if not on:
+            check(self.lib.gpirt_sampler_rank_enable(self._s, None, -1, 0))
+            return
+        from . import ranks as RK
+        given, _ = RK.close_pivots(self.n, pivots)
+        arr = (C.c_int64 * max(len(given), 1))(*given)
+        check(self.lib.gpirt_sampler_rank_enable(self._s, arr, len(given), int(bool(pairwise))))
+
+    def rank_accumulate(self):
+        """Add the ranks of the current theta (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_rank_accumulate")
+
+    def rank_get(self, name: str) -> np.ndarray:
+        """One array by name: rank2_sum, rank2_sumsq (uint64, n), rank_hist (uint32, n x B), pivot_cover (uint32, P x n),
+        pivot_share, p_pivot (P x n), rank_mean, rank_var (n), pivots (int64, P), lt (uint32, n x n),
+        counts (int64: draws, skipped, B, w, P)."""
+        c = np.zeros(5, dtype=np.int64)
+        check(self.lib.gpirt_sampler_rank_get(self._s, b"counts", c.ctypes.data, c.nbytes))     # the header alone
+        n, B, P = self.n, int(c[2]), int(c[4])
+        shapes = dict(counts=((5,), np.int64), rank2_sum=((n,), np.uint64), rank2_sumsq=((n,), np.uint64),
+                      rank_hist=((n, B), np.uint32), pivot_cover=((P, n), np.uint32), pivot_share=((P, n), np.float64),
+                      p_pivot=((P, n), np.float64), rank_mean=((n,), np.float64), rank_var=((n,), np.float64),
+                      pivots=((P,), np.int64), lt=((n, n), np.uint32))
+        if name == "counts":
+            return c
+        shape, dt = shapes.get(name, ((0,), np.float64))
+        out = np.empty(shape, dtype=dt)
+        check(self.lib.gpirt_sampler_rank_get(self._s, name.encode(), out.ctypes.data, out.nbytes))
+        return out
+
+    def rank_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the rank accumulators: what
+        gpirt_amd.ranks.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_rank_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ranks(self, probs=(0.025, 0.5, 0.975)) -> dict:
+        """Every finished output of this sampler's accumulators (gpirt_amd.ranks.result's shape): gpirt_rank_combine
+        over its own state, nothing reflected."""
+        from . import ranks as RK
+        return RK.combine(self.handle, [self], probs=probs)
 
     def enable_timing(self, on=True):
         check(self.lib.gpirt_sampler_enable_timing(self._s, int(on)))

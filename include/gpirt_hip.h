@@ -61,7 +61,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -586,6 +586,86 @@ int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_thet
                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
                    double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
                    gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc);
+
+/* ------------------------------------------------------ rank posteriors: rank intervals, pivots, pairwise order --------- */
+/* Who is where in the order?  Joint functionals of one theta draw, accumulated without storing it (library version 108).
+ * Per draw: the grid index k_i of every respondent, k = rint((theta + 5) 100) where theta is bit for bit -5 + 0.01 k (the
+ * rule of GPIRT_SUM_THETA_HIST).  If ANY respondent is off the grid (NaN included) the whole draw is skipped: `skipped`
+ * rises by one and nothing else changes.  Otherwise, with S the number of counted draws so far,
+ *   less_i = #{j : k_j < k_i},  eq_i = #{j : k_j = k_i} (i itself included),
+ *   R2_i = 2 less_i + eq_i + 1 in [2, 2n]: twice the mid-rank, rank 1 the smallest theta.
+ * Per respondent: rank2_sum = sum R2 and rank2_sumsq = sum R2^2 (uint64); rank_mean = rank2_sum / (2 S),
+ *   rank_var = (S sum R2^2 - (sum R2)^2) / (4 S (S - 1)) (ddof 1; the numerator exact in 128 bits, rounded once; NaN for S < 2).
+ *   rank_hist: n x B uint32 (respondent-major) over R2, symmetric under R2 -> 2n + 2 - R2: w = the smallest odd width with
+ *   ceil((2n - 1) / w) <= 1025, B = ceil((2n - 1) / w), plus one if that is even (B w is odd), pad = (B w - (2n - 1)) / 2,
+ *   bin = (R2 - 2 + pad) / w.  For n <= 512, w = 1 and the histogram is the exact distribution of twice the mid-rank.
+ *   rank_q[p]: the max(1, ceil(probs[p] S))-th smallest R2 of the S draws, reported as its bin's upper edge in rank units,
+ *   (2 - pad + (bin + 1) w - 1) / 2; rank_bin_width = w / 2.
+ * Pivots: up to GPIRT_RANK_MAX_PIVOTS ordinal positions q in 1..n (none given: the median, (n + 1) / 2 for odd n, n / 2 and
+ *   n / 2 + 1 for even n); the library closes the set under q <-> n + 1 - q and keeps it sorted (at most 32 positions).
+ *   Respondent i covers q in a draw when less_i < q <= less_i + eq_i.  pivot_cover[q][i] (uint32) counts those draws,
+ *   pivot_share[q][i] (double) adds 1.0 / eq_i for each of them, in draw order; p_pivot = pivot_share / S.
+ * Pairwise (optional): lt[i][j] = #{draws : k_i < k_j}, uint32, n x n, zero diagonal; P(theta_i < theta_j) = lt / S, ties
+ *   are S - lt[i][j] - lt[j][i].  MEMORY: 4 n^2 bytes per chain on the device, 268 MB at n = 8192, 1.07 GB at 16384.
+ * All accumulators are integers or per-respondent double sums in draw order: neither the launch geometry nor the device
+ * can change a bit of them, and two runs give bit-identical states.  Nothing is drawn: the chain is untouched under both
+ * RNG contracts.  n <= GPIRT_RANK_MAX_N.
+ * Pooling C chains (gpirt_rank_combine) adds the integers and adds the shares in chain order.  A chain with sign -1 (the
+ * theta -> -theta reflection gpirt_chains_combine decided, or the caller's) is reflected EXACTLY first:
+ *   rank2_sum -> S (2n + 2) - rank2_sum,  rank2_sumsq -> sum (2n + 2 - R2)^2 = S (2n + 2)^2 - 2 (2n + 2) rank2_sum + rank2_sumsq,
+ *   rank_hist's bins reversed, pivot q <-> n + 1 - q, lt -> lt^T.  signs = NULL reflects nothing. */
+#define GPIRT_RANK_MAX_PIVOTS         16      /* positions the caller may give */
+#define GPIRT_RANK_MAX_PIVOTS_CLOSED  32      /* ... and their closure under q <-> n + 1 - q */
+#define GPIRT_RANK_MAX_N              16384
+/* HOST pointers (NULL: not wanted).  P = n_pivots on the way out (the closed set), B and w as above. */
+typedef struct gpirt_ranks {
+    const double* probs;          /* in: nprobs probabilities in [0, 1] for rank_q */
+    int       nprobs;
+    int       n_pivots;           /* in (gpirt_mcmc_ranks): the positions given in pivots[], 0 = the median; out: P */
+    int64_t   pivots[GPIRT_RANK_MAX_PIVOTS_CLOSED];     /* in: the first n_pivots; out: the closed set, sorted */
+    int       pairwise;           /* in (gpirt_mcmc_ranks): keep lt */
+    int       reserved0;          /* must be 0 */
+    double*   rank_mean;          /* n */
+    double*   rank_var;           /* n */
+    double*   rank_q;             /* nprobs x n */
+    double*   p_pivot;            /* P x n */
+    double*   pivot_share;        /* P x n */
+    uint64_t* rank2_sum;          /* n */
+    uint64_t* rank2_sumsq;        /* n */
+    uint32_t* rank_hist;          /* n x B */
+    uint32_t* pivot_cover;        /* P x n */
+    uint32_t* lt;                 /* n x n (the states must hold the pairwise counters) */
+    int64_t   draws, skipped, B, w;       /* out: counted and skipped draws (pooled: over the chains), the bins */
+    double    rank_bin_width;             /* out: w / 2 */
+    int64_t   reserved[4];        /* must be 0 */
+} gpirt_ranks;
+/* Stage API.  rank_enable(pivots, n_pivots, pairwise) allocates and zeroes the accumulators (pivots = NULL and
+ * n_pivots < 0: frees them; n_pivots = 0: the median); more than GPIRT_RANK_MAX_PIVOTS positions or one outside 1..n is
+ * GPIRT_E_ARG.  rank_accumulate adds the CURRENT theta as one draw (call it after the step of a sampling iteration).
+ * rank_get copies one array by name to the host, `bytes` its exact size: "rank2_sum", "rank2_sumsq" (uint64, n),
+ * "rank_hist" (uint32, n x B), "pivot_cover" (uint32, P x n), "pivot_share", "p_pivot" (double, P x n), "rank_mean",
+ * "rank_var" (double, n), "pivots" (int64, P), "lt" (uint32, n x n, dense), "counts" (int64: draws, skipped, B, w, P).
+ * rank_state returns the ONE device block, apart from the summaries' and the PPC's (valid until rank_enable is called again
+ * or the sampler is destroyed): a header of 40 int64 -- n, counted draws, skipped draws, layout version (1), B, w, P, the
+ * pairwise flag, then the closed pivots in 32 words -- then uint64 rank2_sum[n], rank2_sumsq[n], double pivot_share[P][n],
+ * uint32 pivot_cover[P][n] and rank_hist[n][B] (each padded to 8 bytes) and, with the flag, on a 16-byte boundary uint32
+ * lt[n][ld], ld = n rounded up to 4 (padding 0).  gpirt_rank_combine pools C such blocks (device pointers on h's device;
+ * the same n and pivots; with out->lt every state must hold lt) into out, whose probs / nprobs it reads. */
+int gpirt_sampler_rank_enable(gpirt_sampler_t s, const int64_t* pivots, int n_pivots, int pairwise);
+int gpirt_sampler_rank_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_rank_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_rank_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out);
+/* gpirt_mcmc_ppc with the rank posteriors: the same chains -- draws, IRFs, pooled, diag, the quantiles, the PPC and R's
+ * stream position bit-identical --, each accumulating its theta after every sampling iteration's summaries (under the item
+ * RNG from the verified checkpoint, so a hang-guard rollback counts no draw twice), pooled into ranks (required) with the
+ * signs gpirt_chains_combine decided (align = 0 or one chain: none).  q and ppc may be NULL. */
+int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                     int sample_iterations, int burn_iterations, const double* h_prior_means,
+                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
