@@ -126,6 +126,22 @@ class Ranks(C.Structure):
                 ("rank_bin_width", C.c_double), ("reserved", C.c_int64 * 4)]
 
 
+# scoring new respondents (include/gpirt_hip.h gpirt_score)
+SCORE_MAX_N = 16384
+
+
+class Score(C.Structure):
+    """gpirt_score (include/gpirt_hip.h): the probabilities, host pointers per output (NULL: not wanted) and the totals."""
+    _fields_ = [("probs", C.POINTER(C.c_double)), ("nprobs", C.c_int), ("reserved0", C.c_int),
+                ("grid_post", C.POINTER(C.c_double)), ("theta_mean", C.POINTER(C.c_double)),
+                ("theta_sd", C.POINTER(C.c_double)), ("theta_quantiles", C.POINTER(C.c_double)),
+                ("theta_map", C.POINTER(C.c_double)), ("lpd", C.POINTER(C.c_double)), ("loglik_mean", C.POINTER(C.c_double)),
+                ("post_sum", C.POINTER(C.c_double)), ("lpd_acc", C.POINTER(C.c_double)), ("ll_sum", C.POINTER(C.c_double)),
+                ("n_obs", C.POINTER(C.c_int64)), ("draws", C.POINTER(C.c_int64)), ("nonfinite", C.POINTER(C.c_int64)),
+                ("n_new", C.c_int64), ("m", C.c_int64), ("lpd_total", C.c_double), ("se_lpd_total", C.c_double),
+                ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -239,6 +255,14 @@ SIGNATURES = {
     "gpirt_mcmc_ranks": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks)]),
+    "gpirt_sampler_score_enable": (_i32, [_vp, _dp, _i64]),
+    "gpirt_sampler_score_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_score_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_score_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_score_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Score)]),
+    "gpirt_mcmc_score": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

@@ -400,6 +400,34 @@ int launch_rank_accumulate(hipStream_t stream, RankState* s, const double* theta
 int rank_get(hipStream_t stream, RankState* s, const char* name, void* h_out, int64_t bytes);
 int rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out);
 
+// score.hip: scoring respondents who were not in the fit, one f* draw at a time (gpirt_sampler_score_*, gpirt_mcmc_score).  The
+// state is ONE device block of 8-byte words: a header of SCORE_HEADER_WORDS int64 (n_new, m, layout version, N, 0, 0, 0, 0),
+// int64 draws[n_new], nonfinite[n_new], n_obs[n_new], double lpd_acc[n_new] (starts at -inf), ll_sum[n_new] and
+// post_sum[n_new][N] (k fastest).  Beside it the state owns everything the product launchers need at n_new: the packed y_new
+// in both forms (Ypm for the fp64 GEMM, y8 for the int8 kernel), the terms and digit planes, and the product itself.
+constexpr int SCORE_LAYOUT_VERSION = 1;
+constexpr int SCORE_HEADER_WORDS = 8;
+struct ScoreState {
+    bool on = false;
+    int64_t n = 0, m = 0;
+    TfDims tfd{};
+    uint64_t* block = nullptr;
+    double *Ypm = nullptr, *Gpm = nullptr, *T = nullptr, *fclean = nullptr, *logprior = nullptr;
+    void *y8 = nullptr, *gq = nullptr, *aux = nullptr;
+    int* flags = nullptr;                             // [0] a NaN in this draw's f*, [1 + j] in item j, [1 + m + r] r answered one
+    double lse_prior = 0.0;                           // logsumexp_k(logprior)
+    std::vector<void*> allocs;
+};
+int64_t score_state_words(const ScoreState* s);
+// refuses n_new outside 1..GPIRT_SCORE_MAX_N and values other than +1, -1, NaN before anything is allocated; h_y_new is
+// n_new x m, column-major
+int score_alloc(hipStream_t stream, ScoreState* s, const double* h_y_new, int64_t n_new, int64_t m);
+void score_free(ScoreState* s);
+// the product of (y_new, f*) as draw_theta launches it (h: its configuration and the GEMM's workspace), then the accumulation
+int launch_score_accumulate(gpirt_handle_t h, hipStream_t stream, ScoreState* s, const double* fstar);   // fstar: N x m on the device
+int score_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, int64_t bytes);
+int score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

@@ -142,6 +142,7 @@ struct gpirt_sampler_s {
     SummaryState sum;                 // posterior summaries (gpirt_sampler_summary_enable; parts == 0: off)
     PpcState ppc;                     // posterior predictive checks (gpirt_sampler_ppc_enable; on == false: off)
     RankState rank;                   // rank posteriors (gpirt_sampler_rank_enable; on == false: off)
+    ScoreState score;                 // scoring new respondents (gpirt_sampler_score_enable; on == false: off)
 };
 
 namespace {
@@ -1203,6 +1204,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     summary_free(&s->sum);
     ppc_free(&s->ppc);
     rank_free(&s->rank);
+    score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -1617,6 +1619,68 @@ int gpirt_rank_combine(gpirt_handle_t h, int chains, const void* const* d_states
     return rank_combine(h, chains, d_states, signs, out);
 }
 
+// ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
+static int score_needs_on(gpirt_sampler_t s)
+{
+    if (s->score.on) return 0;
+    set_error("scoring is not enabled (gpirt_sampler_score_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_score_enable(gpirt_sampler_t s, const double* h_y_new, int64_t n_new)
+{
+    GP_ARG(s && s->initialised);
+    if (h_y_new && n_new != 0) {                        // every refusal before the old state is touched
+        if (n_new < 1 || n_new > GPIRT_SCORE_MAX_N) {
+            set_error("scoring: n_new = %lld is outside 1..%d", (long long)n_new, GPIRT_SCORE_MAX_N);
+            return GPIRT_E_ARG;
+        }
+        if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
+            set_error("scoring is not offered for item shards (a new respondent's product runs over all items)");
+            return GPIRT_E_ARG;
+        }
+        for (int64_t g = 0; g < n_new * s->m; ++g) {
+            const double v = h_y_new[g];
+            if (!(v == 1.0 || v == -1.0 || v != v)) { set_error("scoring: y_new must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
+        }
+    }
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    score_free(&s->score);
+    if (!h_y_new || n_new == 0) return 0;
+    const int rc = score_alloc(s->h->stream, &s->score, h_y_new, n_new, s->m);
+    if (rc) score_free(&s->score);
+    return rc;
+}
+
+int gpirt_sampler_score_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(score_needs_on(s));
+    return launch_score_accumulate(s->h, s->h->stream, &s->score, s->fstar);
+}
+
+int gpirt_sampler_score_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(score_needs_on(s));
+    return score_get(s->h->stream, &s->score, name, h_out, bytes);
+}
+
+int gpirt_sampler_score_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(score_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    *d_state = s->score.block;
+    *bytes = score_state_words(&s->score) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out)
+{
+    return score_combine(h, chains, d_states, signs, out);
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -1851,6 +1915,9 @@ struct ChainRun {
     PpcState* keep_ppc;               // gpirt_mcmc_ppc: the chain also accumulates the PPC; its state outlives the sampler here
     RankState* keep_rank;             // gpirt_mcmc_ranks: ... and the rank posteriors (the state names pivots and pairwise)
     const gpirt_ranks* ranks;
+    ScoreState* keep_score;           // gpirt_mcmc_score: ... and the scores of y_new (n_new x m on the host)
+    const double* y_new;
+    int64_t n_new;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -1909,6 +1976,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_rank = std::move(s->rank);
                 s->rank = RankState{};
             }
+            if (cr->keep_score) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_score = std::move(s->score);
+                s->score = ScoreState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -1934,6 +2006,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
     const bool ranks = cr && cr->keep_rank;
     if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
+    const bool score = cr && cr->keep_score;
+    if (!rc && score) rc = gpirt_sampler_score_enable(s, cr->y_new, cr->n_new);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -1949,6 +2023,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc && summarise) rc = gpirt_sampler_summary_accumulate(s);   // consumes nothing of R's stream
                 if (!rc && ppc) rc = gpirt_sampler_ppc_accumulate(s);             // nor does the replicate (counter-based)
                 if (!rc && ranks) rc = gpirt_sampler_rank_accumulate(s);          // the ranks draw nothing at all
+                if (!rc && score) rc = gpirt_sampler_score_accumulate(s);         // nor does the scoring (the live f*)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -2039,6 +2114,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (ppc)                                // the slot holds the state after k iterations
             GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k));
         if (ranks) GP_TRY(launch_rank_accumulate(h->stream, &s->rank, d));      // the slot's theta
+        if (score) GP_TRY(launch_score_accumulate(h, h->stream, &s->score, d + off_fstar));   // the slot's f*
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2174,7 +2250,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
-                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr)
+                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
+                      const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2214,12 +2291,26 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
             }
         GP_ARG(!(ranks->lt && !ranks->pairwise));
     }
+    if (score) {
+        GP_ARG(score->reserved0 == 0 && score->reserved[0] == 0 && score->reserved[1] == 0 && score->reserved[2] == 0 && score->reserved[3] == 0);
+        GP_ARG(score->nprobs >= 0 && (score->nprobs == 0 || score->probs));
+        for (int p = 0; p < score->nprobs; ++p) GP_ARG(score->probs[p] >= 0.0 && score->probs[p] <= 1.0);
+        if (!h_y_new || n_new < 1 || n_new > GPIRT_SCORE_MAX_N) {
+            set_error("scoring: n_new = %lld is outside 1..%d", (long long)n_new, GPIRT_SCORE_MAX_N);
+            return GPIRT_E_ARG;
+        }
+        for (int64_t g = 0; g < n_new * m; ++g) {
+            const double v = h_y_new[g];
+            if (!(v == 1.0 || v == -1.0 || v != v)) { set_error("scoring: y_new must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
+        }
+    }
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
     std::vector<SummaryState> keep((size_t)chains);
     std::vector<PpcState> keep_ppc(ppc ? (size_t)chains : 0);
     std::vector<RankState> keep_rank(ranks ? (size_t)chains : 0);
+    std::vector<ScoreState> keep_score(score ? (size_t)chains : 0);
     const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
@@ -2229,7 +2320,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         gpirt_summary sm{};
         sm.parts = parts | extra;
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
-                           ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in };
+                           ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
+                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2250,8 +2342,13 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_rank[(size_t)c].block;
         rc = rank_combine(h, chains, st.data(), sg.data(), ranks);
     }
+    if (!rc && score) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].block;
+        rc = score_combine(h, chains, st.data(), sg.data(), score);
+    }
     for (auto& k : keep_ppc) ppc_free(&k);
     for (auto& k : keep_rank) rank_free(&k);
+    for (auto& k : keep_score) score_free(&k);
     gpirt_destroy(h);
     return rc;
 }
@@ -2330,6 +2427,23 @@ int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_th
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks);
+}
+
+// ---- scoring new respondents ------------------------------------------------------------------------------------------------
+int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score)
+{
+    GP_ARG(opts && score);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_score needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score);
 }
 
 }  // extern "C"

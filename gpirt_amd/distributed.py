@@ -256,6 +256,11 @@ class ShardedSampler:
     def ranks(self, probs=(0.025, 0.5, 0.975)):
         return self.engine.ranks(probs)
 
+    # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
+    def score_enable(self, y_new):
+        raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "
+                         "product runs over all items, and each rank holds its own f* columns)")
+
     def summary_gather(self, name: str):
         """The full pointwise summary `name` (p_yes, lppd, p_waic, f_mean, f_var, beta_mean, beta_var) on every rank;
         theta_mean / theta_var are the local ones (identical on every rank)."""

@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None, ranks=None):
+              ppc=None, ranks=None, score=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -95,6 +95,16 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       at n = 8192).  Chains are pooled with the reflection "diagnostics" reports.  Nothing is drawn: the chain is
       untouched under both RNG contracts.  "summary" and "diagnostics" come as with ppc.  ranks=None leaves every other
       path as it is.
+    score: y_new (n_new x m), or dict(data=y_new, probs=(0.025, 0.5, 0.975)), scores respondents who are NOT in the fit
+      (gpirt_mcmc_score, gpirt_amd.score): y_new is coded +1 / -1 / NaN over the prepared data's m item columns (after
+      unanimous items were dropped; another width is a ValueError), 1 <= n_new <= 16384.  After every sampling iteration
+      the device forms, from that draw's f*, each new respondent's normalised posterior over the theta grid and the log
+      marginal likelihood of their answers, and accumulates them; "score" holds grid_post (n_new x 1001), theta_mean,
+      theta_sd, theta_quantiles (len(probs) x n_new), theta_map, lpd (the log pointwise predictive density of the
+      respondent's answers), loglik_mean, n_obs, lpd_total, se_lpd_total, draws, nonfinite (a draw whose log-posterior is
+      not finite for a respondent is skipped for that respondent alone) and the raw post_sum, lpd_acc, ll_sum.  Chains are
+      pooled with the reflection "diagnostics" reports.  Nothing is drawn: the chain is untouched under both RNG contracts.
+      "summary" and "diagnostics" come as with ranks.  score=None leaves every other path as it is.
     """
     from .ops import RStream
 
@@ -122,10 +132,20 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
             raise ValueError(f"ranks: unknown keys {sorted(unknown)}")
     else:
         ranks = None
-    if quantiles is not None or ppc or ranks is not None:
+    if score is not None:
+        from . import score as SC
+        if isinstance(score, dict):
+            unknown = set(score) - {"data", "probs"}
+            if unknown or "data" not in score:
+                raise ValueError(f"score: a dict needs data=y_new and may give probs (unknown keys {sorted(unknown)})")
+            score = dict(data=score["data"], probs=score.get("probs", SC.DEFAULT_PROBS))
+        else:
+            score = dict(data=score, probs=SC.DEFAULT_PROBS)
+        score["data"] = np.asfortranarray(SC.check_y_new(score["data"], y.shape[1]))
+    if quantiles is not None or ppc or ranks is not None or score is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks)
+                               align, quantiles, bool(ppc), ranks, score)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -258,11 +278,13 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
-                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None):
+                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
+                    score=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
-    same chains with the rank posteriors (with or without the checks)."""
+    same chains with the rank posteriors (with or without the checks).  score (dict(data, probs)): gpirt_mcmc_score, the
+    same chains scoring the new respondents `data` (with or without the checks and the ranks)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -325,7 +347,15 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if ranks is not None:
+    if score is not None:
+        from . import score as SC
+        sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
+        rc = lib.gpirt_mcmc_score(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
+                                  C.byref(pp) if with_ppc else None, C.byref(rk) if ranks is not None else None,
+                                  _ptr(score["data"]), score["data"].shape[0], C.byref(sc))
+    elif ranks is not None:
         rc = lib.gpirt_mcmc_ranks(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
                                   int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
                                   rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
@@ -357,6 +387,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["ppc"] = P.result(pp, parr)
     if ranks is not None:
         out["ranks"] = RK.result(rk, rkarr)
+    if score is not None:
+        out["score"] = SC.result(sc, scarr)
     return out
 
 
@@ -724,6 +756,61 @@ class Sampler:
         over its own state, nothing reflected."""
         from . import ranks as RK
         return RK.combine(self.handle, [self], probs=probs)
+
+    # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
+    def score_enable(self, y_new):
+        """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the
+        accumulators; y_new=None frees them."""
+        if y_new is None:
+            check(self.lib.gpirt_sampler_score_enable(self._s, None, 0))
+            self._score_n = 0
+            return
+        from . import score as SC
+        y = np.asfortranarray(SC.check_y_new(y_new, self.m))
+        check(self.lib.gpirt_sampler_score_enable(self._s, _ptr(y), y.shape[0]))
+        self._score_n = y.shape[0]
+
+    def score_accumulate(self):
+        """Score the new respondents under the current f* (after a sampling iteration's step) as one draw; the chain is
+        untouched."""
+        self._call("gpirt_sampler_score_accumulate")
+
+    def score_get(self, name: str) -> np.ndarray:
+        """One array by name: draws, nonfinite, n_obs (int64, n_new), lpd_acc, ll_sum, lpd, loglik_mean, theta_mean,
+        theta_sd, theta_map (n_new), post_sum, grid_post (n_new x 1001), product (1001 x n_new, column-major: T of the
+        last score_accumulate)."""
+        n = getattr(self, "_score_n", 0)
+        if name in ("draws", "nonfinite", "n_obs"):
+            out = np.empty(n, dtype=np.int64)
+        elif name in ("post_sum", "grid_post"):
+            out = np.empty((n, NGRID))
+        elif name == "product":
+            out = np.empty((NGRID, n), order="F")
+        else:
+            out = np.empty(n)
+        check(self.lib.gpirt_sampler_score_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def score_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the score accumulators: what
+        gpirt_amd.score.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_score_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def score(self, probs=(0.025, 0.5, 0.975)) -> dict:
+        """Every finished output of this sampler's accumulators (gpirt_amd.score.result's shape): gpirt_score_combine over
+        its own state, nothing reflected."""
+        from . import score as SC
+        return SC.combine(self.handle, [self], probs=probs)
 
     def enable_timing(self, on=True):
         check(self.lib.gpirt_sampler_enable_timing(self._s, int(on)))

@@ -61,7 +61,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -666,6 +666,87 @@ int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_th
                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
                      double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
                      gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks);
+
+/* ------------------------------------------------------ scoring new respondents: theta posterior and predictive density -- */
+/* What does the fitted model say about a respondent who was NOT in the fit (library version 109)?  y_new is n_new x m,
+ * column-major, coded +1 / -1 / NaN, over the SAME m item columns as the sampler's y (after unanimous items were dropped),
+ * 1 <= n_new <= GPIRT_SCORE_MAX_N; any other value or size is GPIRT_E_ARG before anything is touched.  Per counted draw of
+ * f* (which carries mu*) and new respondent r, with N = GPIRT_NGRID and theta*_k = -5 + 0.01 k:
+ *   T[k, r]  = sum_j over observed cells of -log(1 + exp(-+ f*[k, j])), the product gpirt_debug_theta_logpost documents: in
+ *     exact fixed point on the int8 matrix cores (with its own hand-over to the fp64 product when |f*| > 709 or f* is not
+ *     finite), or with GPIRT_THETA_FIXED=2 as the fp64 GEMM.  In the fp64 form a term that overflows (the formula as
+ *     written gives -inf for |f*| > ~709.8) is held at -1e300, which is finite.  A NaN cell f*[k, j] makes T[k, r] NaN for
+ *     the respondents who answered item j and ONLY for them (the library keeps it out of the product and flags them).
+ *   lp[k]    = logprior[k] + T[k, r], logprior[k] = log dnorm(theta*_k) = -(log sqrt(2 pi) + 0.5 theta*_k^2) as draw_theta adds it.
+ *   M = max_k lp[k], Z = sum_k exp(lp[k] - M), w_k = exp(lp[k] - M) / Z: always stabilised, whatever theta_stabilise says.
+ *   post_sum[r][k] += w_k: the Rao-Blackwellised grid posterior, the mean over draws of P(theta_new = theta*_k | f*, y_new).
+ *   l = M + log Z - logsumexp_k(logprior): the log of sum_k pi_k prod_j P(y_rj | theta*_k) under the normalised grid prior pi.
+ *   lpd_acc[r] = logaddexp(lpd_acc[r], l) (from -inf, as WAIC's lppd), ll_sum[r] += l, draws[r] += 1.
+ * If any lp[k] of respondent r is not finite in a draw, that draw is skipped for r alone: nonfinite[r] += 1 and nothing
+ * else of r changes.  A respondent with no observed cell has T = 0: its posterior is the prior and l = 0.
+ * Finished on the host from the integers and sums (sums over k in k order; NaN where draws[r] = 0):
+ *   grid_post = post_sum / draws[r];  theta_mean = sum_k theta*_k grid_post[k],  theta_sd = sqrt(sum_k (theta*_k - mean)^2
+ *   grid_post[k]);  theta_quantiles[p] = the smallest grid point whose cumulative grid_post is >= probs[p] (the last one if
+ *   none is);  theta_map = the lowest grid point of maximal grid_post;  lpd = lpd_acc - log draws[r];  loglik_mean =
+ *   ll_sum / draws[r];  lpd_total = sum_r lpd,  se_lpd_total = sqrt(n_new var_r lpd) (ddof 1; NaN for n_new < 2).
+ * Nothing is drawn: the chain, the IRFs and R's stream position are what they are without scoring, under both RNG
+ * contracts.  All accumulators are per-respondent sums in draw order formed by one wave in a fixed order: two runs give
+ * bit-identical states.
+ * Pooling C chains (gpirt_score_combine) adds the counters, adds post_sum and ll_sum in chain order and combines lpd_acc by
+ * logaddexp in chain order.  A chain with sign -1 (the theta -> -theta reflection gpirt_chains_combine decided, or the
+ * caller's) enters with post_sum[r][k] <-> post_sum[r][1000 - k]; l is taken as it is (the prior is symmetric, so l does not
+ * depend on the labelling).  signs = NULL reflects nothing. */
+#define GPIRT_SCORE_MAX_N  16384
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_score {
+    const double* probs;          /* in: nprobs probabilities in [0, 1] for theta_quantiles */
+    int       nprobs;
+    int       reserved0;          /* must be 0 */
+    double*   grid_post;          /* n_new x GPIRT_NGRID (k fastest) */
+    double*   theta_mean;         /* n_new */
+    double*   theta_sd;           /* n_new */
+    double*   theta_quantiles;    /* nprobs x n_new */
+    double*   theta_map;          /* n_new */
+    double*   lpd;                /* n_new */
+    double*   loglik_mean;        /* n_new */
+    double*   post_sum;           /* n_new x GPIRT_NGRID */
+    double*   lpd_acc;            /* n_new */
+    double*   ll_sum;             /* n_new */
+    int64_t*  n_obs;              /* n_new */
+    int64_t*  draws;              /* n_new */
+    int64_t*  nonfinite;          /* n_new */
+    int64_t   n_new, m;           /* out */
+    double    lpd_total, se_lpd_total;    /* out */
+    int64_t   reserved[4];        /* must be 0 */
+} gpirt_score;
+/* Stage API.  score_enable(h_y_new, n_new) packs y_new (a HOST array) and allocates the state (h_y_new = NULL or n_new = 0:
+ * scoring off, the state freed).  score_accumulate adds the CURRENT f* as one draw (call it after the step of a sampling
+ * iteration).  score_get copies one array by name to the host, `bytes` its exact size: "draws", "nonfinite", "n_obs" (int64,
+ * n_new), "lpd_acc", "ll_sum", "lpd", "loglik_mean", "theta_mean", "theta_sd", "theta_map" (double, n_new), "post_sum",
+ * "grid_post" (double, n_new x N) and "product" (double, N x n_new, k fastest: T of the last score_accumulate).
+ * score_state returns the ONE device block, apart from the summaries', the PPC's and the ranks' (valid until score_enable is
+ * called again or the sampler is destroyed): a header of 8 int64 -- n_new, m, layout version (1), N, 0, 0, 0, 0 -- then int64
+ * draws[n_new], nonfinite[n_new], n_obs[n_new], double lpd_acc[n_new] (-inf before the first draw), ll_sum[n_new] and
+ * post_sum[n_new][N].  gpirt_score_combine pools C such blocks (device pointers on h's device; the same n_new, m and
+ * n_obs) into out, whose probs / nprobs it reads.  Item shards are refused by score_enable: a new respondent's product runs
+ * over all items. */
+int gpirt_sampler_score_enable(gpirt_sampler_t s, const double* h_y_new, int64_t n_new);
+int gpirt_sampler_score_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_score_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_score_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out);
+/* gpirt_mcmc_ranks with scoring: the same chains -- draws, IRFs, pooled, diag, the quantiles, the PPC, the ranks and R's
+ * stream position bit-identical --, each accumulating its f* after every sampling iteration's summaries (under the item RNG
+ * from the verified checkpoint, so a hang-guard rollback counts no draw twice; under R's stream from the live state), pooled
+ * into score (required) with the signs gpirt_chains_combine decided (align = 0 or one chain: none).  q, ppc and ranks may
+ * be NULL. */
+int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                     int sample_iterations, int burn_iterations, const double* h_prior_means,
+                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                     const double* h_y_new, int64_t n_new, gpirt_score* score);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
