@@ -142,6 +142,19 @@ class Score(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+# predicting the new respondents' unseen answers (include/gpirt_hip.h gpirt_score_predict)
+PREDICT_MAX_TOP = 16
+
+
+class ScorePredict(C.Structure):
+    """gpirt_score_predict (include/gpirt_hip.h): top, host pointers per output (NULL: not wanted) and the counters."""
+    _fields_ = [("top", C.c_int), ("reserved0", C.c_int), ("p_yes", C.POINTER(C.c_double)), ("info", C.POINTER(C.c_double)),
+                ("next_items", C.POINTER(C.c_int64)), ("next_info", C.POINTER(C.c_double)),
+                ("pred_sum", C.POINTER(C.c_double)), ("info_sum", C.POINTER(C.c_double)),
+                ("n_new", C.c_int64), ("m", C.c_int64), ("pred_draws", C.c_int64), ("pred_skipped", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -263,6 +276,14 @@ SIGNATURES = {
     "gpirt_mcmc_score": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score)]),
+    "gpirt_sampler_score_predict_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_score_predict_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_score_predict_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_score_predict_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(ScorePredict)]),
+    "gpirt_mcmc_predict": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                   TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                   C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                   C.POINTER(ScorePredict)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

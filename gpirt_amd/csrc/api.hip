@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 109; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 110; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -174,6 +174,8 @@ int gpirt_version(void) { return 109; }     // 101: gpirt_options names kernel_f
                                             // 107: posterior predictive checks (ppc.hip: gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc)
                                             // 108: rank posteriors (ranks.hip: gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks)
                                             // 109: scoring new respondents (score.hip: gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score)
+                                            // 110: predicting new respondents' unseen answers and the next item to ask (predict.hip:
+                                            //      gpirt_sampler_score_predict_*, gpirt_score_predict_combine, gpirt_mcmc_predict)
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -407,6 +407,24 @@ int rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, cons
 // in both forms (Ypm for the fp64 GEMM, y8 for the int8 kernel), the terms and digit planes, and the product itself.
 constexpr int SCORE_LAYOUT_VERSION = 1;
 constexpr int SCORE_HEADER_WORDS = 8;
+// predict.hip: the new respondents' UNSEEN answers (gpirt_sampler_score_predict_*, gpirt_mcmc_predict), an add-on to a score
+// state.  Its accumulators are ONE device block of 8-byte words of their own: a header of PRED_HEADER_WORDS int64 (n_new, m,
+// layout version, N, pred_draws, pred_skipped, 0, PRED_TAG -- the two counters are kept by the epilogue kernel; the tag tells
+// the block from a score block, whose header starts alike), the answered-mask of
+// y_new packed 64 cells a word (cell g = r + j n_new: bit g % 64 of word g / 64), double pred_sum[m][n_new] and
+// info_sum[m][n_new] (r fastest).  Beside it: the last draw's weights W (Np x n_new, k fastest, Np = 1024: the padding rows
+// stay zero), the operand tables B = [P | H] (Np x 2m) and the product C = W^T B (n_new x 2m).
+constexpr int PRED_LAYOUT_VERSION = 1;
+constexpr int PRED_HEADER_WORDS = 8;
+constexpr int64_t PRED_TAG = 0x44455250;              // "PRED"
+struct PredState {
+    bool on = false;
+    int64_t n = 0, m = 0;
+    uint64_t* block = nullptr;
+    double *W = nullptr, *B = nullptr, *C = nullptr;
+    int* go = nullptr;                                // 1: this draw's f* holds no NaN (written by the weights' launch)
+    std::vector<void*> allocs;
+};
 struct ScoreState {
     bool on = false;
     int64_t n = 0, m = 0;
@@ -416,6 +434,8 @@ struct ScoreState {
     void *y8 = nullptr, *gq = nullptr, *aux = nullptr;
     int* flags = nullptr;                             // [0] a NaN in this draw's f*, [1 + j] in item j, [1 + m + r] r answered one
     double lse_prior = 0.0;                           // logsumexp_k(logprior)
+    std::vector<uint64_t> answered;                   // host: the answered-mask of y_new, packed as a predict state block holds it
+    PredState pred;                                   // predicting the unseen answers (predict.hip; on == false: off)
     std::vector<void*> allocs;
 };
 int64_t score_state_words(const ScoreState* s);
@@ -427,6 +447,14 @@ void score_free(ScoreState* s);
 int launch_score_accumulate(gpirt_handle_t h, hipStream_t stream, ScoreState* s, const double* fstar);   // fstar: N x m on the device
 int score_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, int64_t bytes);
 int score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out);
+// predict.hip
+int64_t pred_state_words(int64_t n_new, int64_t m);
+int pred_alloc(hipStream_t stream, ScoreState* s);    // needs s->on; the block's header and mask are written
+void pred_free(PredState* p);
+// after score_accumulate_kernel has stored this draw's weights and go-flag: the operands, the contraction, the epilogue
+int launch_pred_accumulate(gpirt_handle_t h, hipStream_t stream, ScoreState* s);
+int pred_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, int64_t bytes);
+int pred_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out);
 
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi

@@ -1681,6 +1681,48 @@ int gpirt_score_combine(gpirt_handle_t h, int chains, const void* const* d_state
     return score_combine(h, chains, d_states, signs, out);
 }
 
+// ---- predicting the new respondents' unseen answers (predict.hip): an add-on to the score state --------------------------------
+static int predict_needs_on(gpirt_sampler_t s)
+{
+    if (s->score.pred.on) return 0;
+    set_error("prediction is not enabled (gpirt_sampler_score_predict_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_score_predict_enable(gpirt_sampler_t s, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) GP_TRY(score_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    pred_free(&s->score.pred);
+    if (!on) return 0;
+    const int rc = pred_alloc(s->h->stream, &s->score);
+    if (rc) pred_free(&s->score.pred);
+    return rc;
+}
+
+int gpirt_sampler_score_predict_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(predict_needs_on(s));
+    return pred_get(s->h->stream, &s->score, name, h_out, bytes);
+}
+
+int gpirt_sampler_score_predict_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(predict_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the header's counters are the kernel's
+    *d_state = s->score.pred.block;
+    *bytes = pred_state_words(s->score.pred.n, s->score.pred.m) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_score_predict_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out)
+{
+    return pred_combine(h, chains, d_states, out);
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -1918,6 +1960,7 @@ struct ChainRun {
     ScoreState* keep_score;           // gpirt_mcmc_score: ... and the scores of y_new (n_new x m on the host)
     const double* y_new;
     int64_t n_new;
+    bool predict;                     // gpirt_mcmc_predict: the score state also predicts the unseen answers (it travels inside keep_score)
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2008,6 +2051,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
     const bool score = cr && cr->keep_score;
     if (!rc && score) rc = gpirt_sampler_score_enable(s, cr->y_new, cr->n_new);
+    if (!rc && score && cr->predict) rc = gpirt_sampler_score_predict_enable(s, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2251,7 +2295,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
-                      const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr)
+                      const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
+                      gpirt_score_predict* predict = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2304,6 +2349,14 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
             if (!(v == 1.0 || v == -1.0 || v != v)) { set_error("scoring: y_new must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
         }
     }
+    if (predict) {
+        GP_ARG(score);
+        GP_ARG(predict->reserved0 == 0 && predict->reserved[0] == 0 && predict->reserved[1] == 0 && predict->reserved[2] == 0 && predict->reserved[3] == 0);
+        if (predict->top < 1 || predict->top > GPIRT_PREDICT_MAX_TOP) {
+            set_error("prediction: top = %d is outside 1..%d", predict->top, GPIRT_PREDICT_MAX_TOP);
+            return GPIRT_E_ARG;
+        }
+    }
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
@@ -2321,7 +2374,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         sm.parts = parts | extra;
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
-                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new };
+                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2345,6 +2398,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     if (!rc && score) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].block;
         rc = score_combine(h, chains, st.data(), sg.data(), score);
+    }
+    if (!rc && predict) {                                    // (no signs: both sums run over the whole grid)
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].pred.block;
+        rc = pred_combine(h, chains, st.data(), predict);
     }
     for (auto& k : keep_ppc) ppc_free(&k);
     for (auto& k : keep_rank) rank_free(&k);
@@ -2444,6 +2501,24 @@ int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_th
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score);
+}
+
+// ---- predicting the new respondents' unseen answers ----------------------------------------------------------------------------
+int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                       gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                       gpirt_score_predict* predict)
+{
+    GP_ARG(opts && score && predict);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_predict needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict);
 }
 
 }  // extern "C"

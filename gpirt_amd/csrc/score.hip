@@ -78,6 +78,8 @@ struct ScoreArgs {
     int64_t n;
     int64_t* draws; int64_t* nonfinite;
     double* lpd_acc; double* ll_sum; double* post_sum;
+    // WEIGHTS instantiation only (predict.hip): this draw's w_k to W[r ldw + k], and go = "no NaN in this draw's f*"
+    double* W; int64_t ldw; const int* nan_flag; int* go;
 };
 
 __device__ __forceinline__ double wave_max(double v)
@@ -94,10 +96,15 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// WEIGHTS = false is the scorer as it always was; true also keeps what it used to throw away: the value added to post_sum
+// goes to W as well (the same register, so the score block's bits do not depend on the flag), and one lane of the launch
+// turns flags[0] into the go-flag of the prediction's conditional launches.
+template <bool WEIGHTS>
 __global__ __launch_bounds__(SC_THREADS) void score_accumulate_kernel(ScoreArgs a)
 {
     const int lane = (int)(threadIdx.x & 63);
     const int64_t r = (int64_t)blockIdx.x * SC_WAVES + (threadIdx.x >> 6);
+    if (WEIGHTS && blockIdx.x == 0 && threadIdx.x == 0) *a.go = (*a.nan_flag == 0) ? 1 : 0;
     if (r >= a.n) return;                                // (a whole wave: nothing below waits for another wave)
     const double* __restrict__ T = a.T + r * NG;
     double* __restrict__ post = a.post_sum + r * NG;
@@ -129,7 +136,11 @@ __global__ __launch_bounds__(SC_THREADS) void score_accumulate_kernel(ScoreArgs 
 #pragma unroll
     for (int i = 0; i < SC_PER_LANE; ++i) {
         const int k = lane + 64 * i;
-        if (k < NG) post[k] += lp[i] / Z;
+        if (k < NG) {
+            const double w = lp[i] / Z;
+            post[k] += w;
+            if (WEIGHTS) a.W[r * a.ldw + k] = w;
+        }
     }
     if (lane == 0) {
         const double l = M + log(Z) - a.lse_prior;
@@ -312,6 +323,9 @@ int score_alloc(hipStream_t st, ScoreState* s, const double* h_y_new, int64_t n_
         hi[L.n_obs + r] = c;
         hd[L.lpd_acc + r] = -INFINITY;
     }
+    s->answered.assign((size_t)((n_new * m + 63) / 64), 0);                  // (host only: what a predict state block carries)
+    for (int64_t g = 0; g < n_new * m; ++g)
+        if (h_y_new[g] == h_y_new[g]) s->answered[(size_t)(g >> 6)] |= (uint64_t)1 << (g & 63);
     double lp[NG];
     score_logprior(lp, &s->lse_prior);
     GP_HIP(hipMemcpyAsync(s->block, head.data(), sizeof(uint64_t) * head.size(), hipMemcpyHostToDevice, st));
@@ -328,6 +342,7 @@ int score_alloc(hipStream_t st, ScoreState* s, const double* h_y_new, int64_t n_
 
 void score_free(ScoreState* s)
 {
+    pred_free(&s->pred);
     for (void* p : s->allocs) hipFree(p);
     *s = ScoreState{};
 }
@@ -358,9 +373,16 @@ int launch_score_accumulate(gpirt_handle_t h, hipStream_t st, ScoreState* s, con
     a.lpd_acc = reinterpret_cast<double*>(s->block + L.lpd_acc);
     a.ll_sum = reinterpret_cast<double*>(s->block + L.ll_sum);
     a.post_sum = reinterpret_cast<double*>(s->block + L.post_sum);
-    hipLaunchKernelGGL(score_accumulate_kernel, dim3((unsigned)((n + SC_WAVES - 1) / SC_WAVES)), dim3(SC_THREADS), 0, st, a);
+    const dim3 grid((unsigned)((n + SC_WAVES - 1) / SC_WAVES));
+    if (!s->pred.on) {
+        hipLaunchKernelGGL(score_accumulate_kernel<false>, grid, dim3(SC_THREADS), 0, st, a);
+        GP_HIP(hipGetLastError());
+        return 0;
+    }
+    a.W = s->pred.W; a.ldw = Np; a.nan_flag = s->flags; a.go = s->pred.go;
+    hipLaunchKernelGGL(score_accumulate_kernel<true>, grid, dim3(SC_THREADS), 0, st, a);
     GP_HIP(hipGetLastError());
-    return 0;
+    return launch_pred_accumulate(h, st, s);
 }
 
 int score_get(hipStream_t st, ScoreState* s, const char* name, void* h_out, int64_t bytes)

@@ -261,6 +261,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "
                          "product runs over all items, and each rank holds its own f* columns)")
 
+    def score_predict_enable(self, top=5, on=True):
+        raise ValueError("ShardedSampler: predicting new respondents' answers is not offered for item shards (it is an "
+                         "add-on to scoring, whose product runs over all items)")
+
     def summary_gather(self, name: str):
         """The full pointwise summary `name` (p_yes, lppd, p_waic, f_mean, f_var, beta_mean, beta_var) on every rank;
         theta_mean / theta_var are the local ones (identical on every rank)."""

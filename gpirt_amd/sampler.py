@@ -105,6 +105,13 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       not finite for a respondent is skipped for that respondent alone) and the raw post_sum, lpd_acc, ll_sum.  Chains are
       pooled with the reflection "diagnostics" reports.  Nothing is drawn: the chain is untouched under both RNG contracts.
       "summary" and "diagnostics" come as with ranks.  score=None leaves every other path as it is.
+      dict(data=y_new, predict=True, top=5) also predicts the answers those respondents have NOT given
+      (gpirt_mcmc_predict): "score" gains "predict" with p_yes (n_new x m: P(y_rj = +1 | y_new[r, :]), for every item),
+      info (n_new x m: the expected information, in nats, that the answer to item j carries about theta_r -- the mutual
+      information under each draw, averaged over the draws; valid for non-monotone items), next_items and next_info
+      (n_new x top: each respondent's UNANSWERED items by decreasing info, padded with -1 / NaN; 1 <= top <= 16), pred_draws,
+      pred_skipped (a draw whose f* holds a NaN cell is skipped whole for the prediction) and the raw pred_sum, info_sum.
+      Without predict the score= argument behaves exactly as before, and the scores themselves do not depend on it.
     """
     from .ops import RStream
 
@@ -135,12 +142,16 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     if score is not None:
         from . import score as SC
         if isinstance(score, dict):
-            unknown = set(score) - {"data", "probs"}
+            unknown = set(score) - {"data", "probs", "predict", "top"}
             if unknown or "data" not in score:
-                raise ValueError(f"score: a dict needs data=y_new and may give probs (unknown keys {sorted(unknown)})")
-            score = dict(data=score["data"], probs=score.get("probs", SC.DEFAULT_PROBS))
+                raise ValueError(f"score: a dict needs data=y_new and may give probs, predict and top (unknown keys "
+                                 f"{sorted(unknown)})")
+            if "top" in score and not score.get("predict"):
+                raise ValueError("score: top needs predict=True")
+            score = dict(data=score["data"], probs=score.get("probs", SC.DEFAULT_PROBS), predict=bool(score.get("predict")),
+                         top=SC.check_top(score.get("top", SC.DEFAULT_TOP)))
         else:
-            score = dict(data=score, probs=SC.DEFAULT_PROBS)
+            score = dict(data=score, probs=SC.DEFAULT_PROBS, predict=False, top=SC.DEFAULT_TOP)
         score["data"] = np.asfortranarray(SC.check_y_new(score["data"], y.shape[1]))
     if quantiles is not None or ppc or ranks is not None or score is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
@@ -350,11 +361,16 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     if score is not None:
         from . import score as SC
         sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
-        rc = lib.gpirt_mcmc_score(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
-                                  C.byref(pp) if with_ppc else None, C.byref(rk) if ranks is not None else None,
-                                  _ptr(score["data"]), score["data"].shape[0], C.byref(sc))
+        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
+                C.byref(pp) if with_ppc else None, C.byref(rk) if ranks is not None else None,
+                _ptr(score["data"]), score["data"].shape[0], C.byref(sc))
+        if score.get("predict"):
+            pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
+            rc = lib.gpirt_mcmc_predict(*args, C.byref(pr))
+        else:
+            rc = lib.gpirt_mcmc_score(*args)
     elif ranks is not None:
         rc = lib.gpirt_mcmc_ranks(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
                                   int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
@@ -389,6 +405,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["ranks"] = RK.result(rk, rkarr)
     if score is not None:
         out["score"] = SC.result(sc, scarr)
+        if score.get("predict"):
+            out["score"]["predict"] = SC.predict_result(pr, prarr)
     return out
 
 
@@ -811,6 +829,52 @@ class Sampler:
         its own state, nothing reflected."""
         from . import score as SC
         return SC.combine(self.handle, [self], probs=probs)
+
+    # -- predicting the new respondents' unseen answers (include/gpirt_hip.h gpirt_sampler_score_predict_*, gpirt_amd.score)
+    def score_predict_enable(self, top=5, on=True):
+        """Allocate and zero the prediction accumulators on a sampler whose score_enable is on: from then on every
+        score_accumulate also adds that draw's P(y_rj = +1) and next-item information for every new respondent and item.
+        top (1..16): how many unanswered items score_predict() lists per respondent.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_score_predict_enable(self._s, 0))
+            return
+        from . import score as SC
+        self._predict_top = SC.check_top(top)
+        check(self.lib.gpirt_sampler_score_predict_enable(self._s, 1))
+
+    def score_predict_get(self, name: str) -> np.ndarray:
+        """One array by name: pred_sum, info_sum, p_yes, info (n_new x m), counts (int64: pred_draws, pred_skipped),
+        weights (1001 x n_new, column-major: W of the last draw that counted)."""
+        n = getattr(self, "_score_n", 0)
+        if name == "counts":
+            out = np.empty(2, dtype=np.int64)
+        elif name == "weights":
+            out = np.empty((NGRID, n), order="F")
+        else:
+            out = np.empty((n, self.m), order="F")
+        check(self.lib.gpirt_sampler_score_predict_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def score_predict_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the prediction accumulators: what
+        gpirt_amd.score.predict_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_score_predict_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def score_predict(self, top=None) -> dict:
+        """Every finished output of this sampler's prediction accumulators (gpirt_amd.score.predict_result's shape):
+        gpirt_score_predict_combine over its own state; top defaults to score_predict_enable's."""
+        from . import score as SC
+        return SC.predict_combine(self.handle, [self], top=getattr(self, "_predict_top", SC.DEFAULT_TOP) if top is None else top)
 
     def enable_timing(self, on=True):
         check(self.lib.gpirt_sampler_enable_timing(self._s, int(on)))

@@ -8,6 +8,12 @@ chain --, normalises lp[k] = log dnorm(theta*_k) + T[k, r] over the grid and acc
 marginal likelihood l (ll_sum) and its running logaddexp (lpd_acc).  `struct` / `result` wrap the C struct, `combine`
 pools chains' state blocks (a chain with sign -1 enters with its grid axis reversed), and `from_draws` is the NumPy
 statement of the header over stored f* draws, with T summed in extended precision so that it is the more accurate side.
+
+Predicting the UNSEEN answers (include/gpirt_hip.h, "predicting new respondents' unseen answers"; csrc/predict.hip) is an
+add-on to the same state: per draw q[r, j] = sum_k w_k plogis(f*[k, j]) and the mutual information g[r, j] between the
+unseen answer and theta_r, accumulated into pred_sum and info_sum.  `predict_struct` / `predict_result` wrap
+gpirt_score_predict, `predict_combine` pools chains' predict state blocks, and `predict_from_draws` is the NumPy statement:
+the weights `accumulate` forms, the two contractions over the grid in extended precision.
 """
 from __future__ import annotations
 
@@ -16,9 +22,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import NGRID, SCORE_MAX_N, check
+from ._lib import NGRID, PREDICT_MAX_TOP, SCORE_MAX_N, check
 
 DEFAULT_PROBS = (0.025, 0.5, 0.975)
+DEFAULT_TOP = 5
 LN_SQRT_2PI = 0.918938533204672741780329736406
 HELD = 1e300          # the finite value an overflowed term -log(1 + exp(x)) = -inf is held at (csrc/stages.hip)
 
@@ -225,4 +232,172 @@ def from_draws(y_new, fstar_draws, probs=DEFAULT_PROBS, signs=None, return_produ
     out = finish(pool(chains, signs), probs)
     if return_products:
         out["products"] = [c["products"] for c in chains]
+    return out
+
+
+# ------------------------------------------------------------------------- predicting the unseen answers: the device ---
+def check_top(top) -> int:
+    """top as an int in 1..16, ValueError otherwise"""
+    t = int(top)
+    if t != top or not 1 <= t <= PREDICT_MAX_TOP:
+        raise ValueError(f"top = {top!r} is outside 1..{PREDICT_MAX_TOP}")
+    return t
+
+
+def predict_struct(n_new: int, m: int, top=DEFAULT_TOP):
+    """A gpirt_score_predict asking for every output, and the host arrays behind it (column-major, as y_new is)."""
+    n, m, top = int(n_new), int(m), check_top(top)
+    arrays = dict(p_yes=np.empty((n, m), order="F"), info=np.empty((n, m), order="F"),
+                  next_items=np.empty((n, top), dtype=np.int64, order="F"), next_info=np.empty((n, top), order="F"),
+                  pred_sum=np.empty((n, m), order="F"), info_sum=np.empty((n, m), order="F"))
+    r = _lib.ScorePredict()
+    for k, a in arrays.items():
+        setattr(r, k, a.ctypes.data_as(dict(r._fields_)[k]))
+    r.top = top
+    return r, arrays
+
+
+def predict_result(r, arrays) -> dict:
+    """The "predict" dict of gpirtMCMC(score=dict(..., predict=True)), Sampler.score_predict() and predict_combine()."""
+    out = dict(arrays)
+    out["pred_draws"] = int(r.pred_draws)
+    out["pred_skipped"] = int(r.pred_skipped)
+    return out
+
+
+def predict_state_header(state) -> dict:
+    """The header of a predict state block (a device tensor of int64): n_new, m, version, N, pred_draws, pred_skipped."""
+    w = state[:8].cpu().numpy().view(np.int64)
+    return dict(n_new=int(w[0]), m=int(w[1]), version=int(w[2]), N=int(w[3]), pred_draws=int(w[4]), pred_skipped=int(w[5]))
+
+
+def predict_combine(handle, states, top=DEFAULT_TOP) -> dict:
+    """gpirt_score_predict_combine over the predict state blocks `states` (device tensors, or Samplers with
+    score_predict_enable() on, all on handle's device): pred_sum, info_sum and the two counters added in chain order;
+    blocks with another n_new, m or answered-mask are refused.  Nothing is reflected: both sums run over the whole grid."""
+    lib = _lib.load()
+    top = check_top(top)
+    tensors = [s.score_predict_state() if hasattr(s, "score_predict_state") else s for s in states]
+    hdr = predict_state_header(tensors[0])
+    r, arrays = predict_struct(hdr["n_new"], hdr["m"], top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    check(lib.gpirt_score_predict_combine(handle.ptr, nc, ptrs, C.byref(r)))
+    return predict_result(r, arrays)
+
+
+# -------------------------------------------------------------------------- predicting the unseen answers: NumPy -------
+def plogis_entropy(fstar):
+    """(P, H) of the header, the formulas as written in fp64: plogis(f*) and its binary entropy in nats (exactly 0 once
+    exp(-|f*|) underflows)."""
+    f = np.asarray(fstar, dtype=np.float64)
+    a = np.abs(f)
+    e = np.exp(-a)
+    l, s_ = np.log1p(e), e / (1.0 + e)
+    with np.errstate(invalid="ignore"):
+        P = np.where(f >= 0.0, 1.0 / (1.0 + e), s_)
+        H = np.where(e == 0.0, 0.0, l + np.where(e == 0.0, 0.0, a) * s_)
+    return P, H
+
+
+def binary_entropy(q):
+    """h(q) = -(q log q + (1 - q) log1p(-q)), q clamped to [0, 1], 0 log 0 = 0"""
+    q = np.clip(np.asarray(q, dtype=np.float64), 0.0, 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a = np.where(q > 0.0, q * np.log(np.where(q > 0.0, q, 1.0)), 0.0)
+        b = np.where(q < 1.0, (1.0 - q) * np.log1p(-np.where(q < 1.0, q, 0.0)), 0.0)
+    return -(a + b)
+
+
+def draw_weights(y_new, fstar, T=None) -> np.ndarray:
+    """w (1001, n_new) of one NaN-free f* draw: the weights `accumulate` forms, from the long-double `product`"""
+    if T is None:
+        T = product(y_new, fstar)
+    lp = logprior()[:, None] + T
+    e = np.exp(lp - lp.max(axis=0)[None, :])
+    return e / e.sum(axis=0)[None, :]
+
+
+def next_items(info, y_new, top=DEFAULT_TOP):
+    """(next_items, next_info), both (n_new, top): each respondent's UNANSWERED items by decreasing info, ties to the lowest
+    j, an item whose info is NaN never listed; padded with -1 / NaN."""
+    top = check_top(top)
+    info = np.asarray(info, dtype=np.float64)
+    y = np.asarray(y_new, dtype=np.float64)
+    n = y.shape[0]
+    items = np.full((n, top), -1, dtype=np.int64)
+    vals = np.full((n, top), np.nan)
+    for r in range(n):
+        cand = np.flatnonzero(np.isnan(y[r]) & ~np.isnan(info[r]))
+        order = cand[np.argsort(-info[r, cand], kind="stable")][:top]
+        items[r, :order.size] = order
+        vals[r, :order.size] = info[r, order]
+    return items, vals
+
+
+def _contract(wl, X):
+    """wl @ X in numpy.longdouble (no BLAS there: the columns are shared among a few threads; the same bits either way)"""
+    X = X.astype(np.longdouble)
+    if wl.shape[0] * X.size < 1 << 24:
+        return (wl @ X).astype(np.float64)
+    from concurrent.futures import ThreadPoolExecutor
+    cols = np.array_split(np.arange(X.shape[1]), 16)
+    with ThreadPoolExecutor(8) as ex:
+        parts = list(ex.map(lambda c: wl @ X[:, c], cols))
+    return np.concatenate(parts, axis=1).astype(np.float64)
+
+
+def predict_accumulate(y_new, fstar_draws, return_draws=False) -> dict:
+    """One chain's prediction accumulators from its f* draws (S, 1001, m): pred_sum, info_sum (n_new, m), pred_draws,
+    pred_skipped.  Per counted draw the contractions q = W^T P and Hbar = W^T H run in numpy.longdouble and are rounded
+    once; with return_draws, "q", "Hbar", "weights" and "products" list them per counted draw."""
+    y = check_y_new(y_new)
+    f = np.asarray(fstar_draws, dtype=np.float64)
+    n, m = y.shape
+    acc = dict(pred_sum=np.zeros((n, m)), info_sum=np.zeros((n, m)), pred_draws=0, pred_skipped=0)
+    if return_draws:
+        acc.update(q=[], Hbar=[], weights=[], products=[])
+    for fd in f:
+        if np.isnan(fd).any():
+            acc["pred_skipped"] += 1
+            continue
+        T = product(y, fd)
+        w = draw_weights(y, fd, T)
+        P, H = plogis_entropy(fd)
+        wl = w.astype(np.longdouble).T
+        q, hbar = _contract(wl, P), _contract(wl, H)
+        acc["pred_sum"] += q
+        acc["info_sum"] += binary_entropy(q) - hbar
+        acc["pred_draws"] += 1
+        if return_draws:
+            acc["q"].append(q); acc["Hbar"].append(hbar); acc["weights"].append(w); acc["products"].append(T)
+    return acc
+
+
+def predict_from_draws(y_new, fstar_draws, top=DEFAULT_TOP, return_draws=False) -> dict:
+    """What the device accumulates and gpirt_score_predict_combine reports, from stored draws fstar_draws (C, S, 1001, m)
+    (or (S, 1001, m): one chain): each chain accumulated on its own, the sums and counters added in chain order.  Returns
+    predict_result()'s keys (and, with return_draws, per chain the lists "q", "Hbar", "weights" and "products")."""
+    top = check_top(top)
+    f = np.asarray(fstar_draws, dtype=np.float64)
+    if f.ndim == 3:
+        f = f[None]
+    if f.ndim != 4 or f.shape[2] != NGRID:
+        raise ValueError("fstar_draws must be (C, S, 1001, m) or (S, 1001, m)")
+    y = check_y_new(y_new, f.shape[3])
+    chains = [predict_accumulate(y, fc, return_draws) for fc in f]
+    pred_sum, info_sum = np.array(chains[0]["pred_sum"]), np.array(chains[0]["info_sum"])
+    for c in chains[1:]:
+        pred_sum = pred_sum + c["pred_sum"]
+        info_sum = info_sum + c["info_sum"]
+    draws = sum(c["pred_draws"] for c in chains)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S = float(draws) if draws > 0 else np.nan
+        p_yes, info = pred_sum / S, info_sum / S
+    items, vals = next_items(info, y, top)
+    out = dict(p_yes=p_yes, info=info, next_items=items, next_info=vals, pred_sum=pred_sum, info_sum=info_sum,
+               pred_draws=draws, pred_skipped=sum(c["pred_skipped"] for c in chains))
+    if return_draws:
+        for k in ("q", "Hbar", "weights", "products"):
+            out[k] = [c[k] for c in chains]
     return out

@@ -61,7 +61,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine, gpirt_mcmc_predict); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -747,6 +747,81 @@ int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_th
                      double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
                      gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
                      const double* h_y_new, int64_t n_new, gpirt_score* score);
+
+/* ---------------------------------------------- predicting new respondents' unseen answers and ranking the next item to ask -- */
+/* How would a respondent who was NOT in the fit answer item j, and which unanswered item is expected to say most about their
+ * theta (library version 110)?  An add-on to scoring: it can only be enabled on a sampler whose score_enable is on, and it
+ * accumulates inside the same score_accumulate call.  Both answers are joint functionals of ONE draw -- that draw's grid
+ * weights times that draw's f* --, so neither grid_post nor the IRFs determine them; they are accumulated draw by draw without
+ * storing f*.  With N = GPIRT_NGRID, theta*_k = -5 + 0.01 k and w_k respondent r's normalised weights of this draw exactly as
+ * the scoring block above defines them:
+ * Per cell f = f*[k, j], with a = |f|, e = exp(-a), l = log1p(e), s = e / (1 + e):
+ *   P[k, j] = f >= 0 ? 1 / (1 + e) : s          plogis(f), stable in both tails
+ *   H[k, j] = e == 0 ? 0 : l + a s              the binary entropy of P in nats: symmetric in f, log 2 at 0, exactly 0 once
+ *                                               exp(-|f|) underflows (+-inf included)
+ * Per draw and respondent r, for EVERY item j (the respondent's own answered items included; the caller masks what they like):
+ *   q[r, j]    = sum_k w_k P[k, j]              P(y_rj = +1 | this draw, y_new[r, :])
+ *   Hbar[r, j] = sum_k w_k H[k, j]
+ *   g[r, j]    = h(q) - Hbar                    the mutual information between the unseen answer and theta_r under this draw;
+ *                                               h(q) = -(q log q + (1 - q) log1p(-q)) with q clamped to [0, 1] for the entropy
+ *                                               only and 0 log 0 = 0; g is NOT clamped (it is >= 0 up to rounding)
+ *   pred_sum[r, j] += q,  info_sum[r, j] += g.
+ * The two sums over k are one fp64 matrix-core product C (n_new x 2m) = W^T [P | H] in a fixed order.
+ * A draw whose f* holds ANY NaN cell is skipped whole for prediction: pred_skipped += 1 and nothing else changes (scoring
+ * itself still skips only the respondents who answered the marked item).  In a NaN-free draw every respondent's
+ * log-posterior is finite (an overflowed term is held at -1e300), so ONE counter pred_draws serves all respondents.  +-inf
+ * cells are fine: P is 0 or 1 and H is 0.
+ * Finished on the host: p_yes = pred_sum / pred_draws, info = info_sum / pred_draws (nats), NaN everywhere if pred_draws = 0;
+ * next_items[r, t], t < top (1 <= top <= GPIRT_PREDICT_MAX_TOP, the Python default is 5), holds r's UNANSWERED items by
+ * decreasing info, ties to the lowest j (an item whose info is NaN is never listed), padded with -1; next_info[r, t] their
+ * info, NaN where padded.
+ * Pooling C chains (gpirt_score_predict_combine) adds pred_sum, info_sum, pred_draws and pred_skipped in chain order and
+ * refuses blocks with another n_new, m or answered-mask.  The theta -> -theta reflection changes nothing here (both sums
+ * run over the whole grid), so there is no signs argument.
+ * Nothing is drawn: the chain, the IRFs, R's stream position and THE SCORE STATE BLOCK are bit for bit what they are without
+ * prediction.  The accumulation order is fixed (each cell is owned by one thread, no atomics): two runs give bit-identical
+ * states.  Item shards stay refused, as for score_enable.
+ * Device memory per state: pred_sum and info_sum 16 n_new m bytes and the per-draw product C as much again, the per-draw
+ * weights 8 Np n_new bytes (Np = 1024), the operand tables 16 Np m bytes: at n_new = 16384, m = 1024 about 268 MB + 268 MB +
+ * 134 MB + 17 MB. */
+#define GPIRT_PREDICT_MAX_TOP  16
+/* HOST pointers (NULL: not wanted); every n_new x . array is column-major (r fastest), as y_new is. */
+typedef struct gpirt_score_predict {
+    int       top;                /* in: 1..GPIRT_PREDICT_MAX_TOP */
+    int       reserved0;          /* must be 0 */
+    double*   p_yes;              /* n_new x m */
+    double*   info;               /* n_new x m */
+    int64_t*  next_items;         /* n_new x top */
+    double*   next_info;          /* n_new x top */
+    double*   pred_sum;           /* n_new x m */
+    double*   info_sum;           /* n_new x m */
+    int64_t   n_new, m;           /* out */
+    int64_t   pred_draws, pred_skipped;   /* out */
+    int64_t   reserved[4];        /* must be 0 */
+} gpirt_score_predict;
+/* Stage API.  score_predict_enable(on != 0) allocates and zeroes the state on a sampler with score_enable on (GPIRT_E_ARG
+ * without; on = 0 frees it; score_enable called again frees it too).  From then on every score_accumulate also adds the draw
+ * to the prediction.  score_predict_get copies one array by name to the host, `bytes` its exact size: "pred_sum", "info_sum",
+ * "p_yes", "info" (double, n_new x m), "counts" (int64: pred_draws, pred_skipped) and "weights" (double, N x n_new, k
+ * fastest: W of the last draw that counted).  score_predict_state returns the ONE device block, apart from the score block:
+ * a header of 8 int64 -- n_new, m, layout version (1), N, pred_draws, pred_skipped, 0, the tag 0x44455250 ("PRED": a score
+ * block's header starts alike) --, the answered-mask of y_new
+ * packed 64 cells a word (cell g = r + j n_new: bit g % 64 of word g / 64; ceil(n_new m / 64) words), then double
+ * pred_sum[m][n_new] and info_sum[m][n_new]. */
+int gpirt_sampler_score_predict_enable(gpirt_sampler_t s, int on);
+int gpirt_sampler_score_predict_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_score_predict_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_score_predict_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out);
+/* gpirt_mcmc_score with prediction (predict is required): the same chains and the same score, every chain also accumulating
+ * the prediction inside its score_accumulate -- under the item RNG from the verified checkpoint, so a hang-guard rollback
+ * counts no draw twice --, pooled into predict. */
+int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                       int sample_iterations, int burn_iterations, const double* h_prior_means,
+                       const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                       double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                       gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                       const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
