@@ -12,6 +12,9 @@
 // that the written form commits and this one does not: at most 1.2e-16 ABSOLUTE per term (for a > 37 the written form
 // returns 0, this one e^-a).  Overflow: the written form gives +inf for a < -709.78 (exp overflows), this one -a; the
 // slice then compares a huge finite number instead of -inf with log_y and rejects all the same.  NaN stays NaN.
+// The CURRENT state is the other side of that: with an observed row at a < -709.78 the written ll(f) is -inf, log_y with it,
+// and the reference accepts the first finite trial point; this form keeps ll(f) finite and the slice goes on shrinking.
+// GPIRT_LL_EXACT=1 follows the reference there as well (tests/test_gpu_draw_f_constructed.py).
 #pragma once
 #include <math.h>
 

@@ -266,9 +266,14 @@ typedef struct gpirt_options {
     int      kernel_fp32;     /* 1: K(theta, theta) is built with single-precision exp() before the fp64 factorisation
                                * (BASELINE config C5; parity then only statistical) */
     int      kstar_rank;      /* r (16..128, multiple of 16; needs fstar_fused): draw_fstar works with the rank-r Chebyshev
-                               * factorisation K(theta, theta*) = K(theta, c) V^T of src/draw-fstar.cpp:17 (exact to 1.3e-15
-                               * for r >= 56) and solves r + m right-hand sides instead of 1001 + m; 0 = every grid column
-                               * is solved */
+                               * factorisation K(theta, theta*) = K(theta, c) V^T of src/draw-fstar.cpp:17 and solves r + m
+                               * right-hand sides instead of 1001 + m; 0 = every grid column is solved.  max |K(theta, c) V^T -
+                               * K(theta, theta*)| over the grid, in long double with V as stored (tests/test_stage_exact_cpu.py):
+                               *   r = 16: 4.6e-3    r = 32: 3.8e-8    r = 48: 8.7e-15    r = 64 .. 128: 1.1e-16 .. 1.3e-16
+                               * r = 16 and r = 32 are APPROXIMATIONS of K* (f* moves by that error times ||S^-1 f||_1); from
+                               * r = 48 on the form is exact to rounding.  At r = 16 the error lifts ||L^-1 k*|| above 1 at
+                               * about a fifth of the grid points: s = 1 - sqrt(q) < 0 there and R::rnorm's rule makes f* NaN
+                               * (tests/test_gpu_fstar_ranks.py): r = 16 is not usable for a chain */
     int      reserved[5];     /* must be 0.  (Up to version 100 kernel_fp32 and kstar_rank were the unnamed slots
                                * reserved[1] and reserved[2] of an int reserved[8] at this offset: same layout, same size.) */
 } gpirt_options;
