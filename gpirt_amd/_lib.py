@@ -109,6 +109,25 @@ class Ppc(C.Structure):
                 ("totals", C.c_double * len(PPC_FIELDS)), ("reserved", C.c_int64 * 4)]
 
 
+# pairwise item checks (include/gpirt_hip.h GPIRT_PAIRS_*): the finished m x m fields in order, the six uint32 counters
+PAIRS_FIELDS = ("n_co", "obs_n11", "obs_n10", "obs_n01", "obs_n00", "rep_n11_mean", "rep_n11_var", "rep_n10_mean",
+                "rep_n01_mean", "rep_n00_mean", "agree_obs", "agree_rep_mean", "log_or_obs", "ppp_n11", "ppp_n11_mid",
+                "ppp_agree", "ppp_agree_mid", "ppp_or", "ppp_or_mid")
+PAIRS_SUMS = ("sum_n11", "sumsq_n11", "sum_n1")
+PAIRS_COUNTS = ("n11_ge", "n11_gt", "agree_ge", "agree_gt", "or_ge", "or_gt")
+PAIRS_MAX_TOP, PAIRS_MAX_N = 64, 65534
+
+
+class PpcPairs(C.Structure):
+    """gpirt_ppc_pairs (include/gpirt_hip.h): top, host pointers per output (NULL: not wanted) and the counters."""
+    _fields_ = [("top", C.c_int), ("reserved0", C.c_int), ("field", C.POINTER(C.c_double) * len(PAIRS_FIELDS)),
+                ("sum_n11", C.POINTER(C.c_uint64)), ("sumsq_n11", C.POINTER(C.c_uint64)), ("sum_n1", C.POINTER(C.c_uint64)),
+                ("count", C.POINTER(C.c_uint32) * len(PAIRS_COUNTS)), ("extreme_pairs", C.POINTER(C.c_int64)),
+                ("extreme_ppp_or_mid", C.POINTER(C.c_double)), ("extreme_log_or_obs", C.POINTER(C.c_double)),
+                ("n", C.c_int64), ("m", C.c_int64), ("pair_draws", C.c_int64), ("pair_skipped", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -284,6 +303,14 @@ SIGNATURES = {
                                    TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                    C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                    C.POINTER(ScorePredict)]),
+    "gpirt_sampler_ppc_pairs_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ppc_pairs_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_pairs_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_pairs_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcPairs)]),
+    "gpirt_mcmc_pairs": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

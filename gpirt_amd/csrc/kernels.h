@@ -347,6 +347,38 @@ enum { PPC_N_OBS, PPC_OBS_YES, PPC_SUM_R, PPC_SUM_R2, PPC_YES_GE, PPC_YES_GT, PP
        PPC_NARRAYS };
 int64_t ppc_stride(int64_t n, int64_t m);           // n + m + 1 units, padded to an even count
 int64_t ppc_state_words(int64_t n, int64_t m);
+// ppc_pairs.hip: the pairwise item checks (gpirt_sampler_ppc_pairs_*, gpirt_mcmc_pairs), an add-on to a PPC state.  Its
+// accumulators are ONE device block of 8-byte words of their own: a header of PAIR_HEADER_WORDS int64 (n, m, layout version,
+// pair_draws, pair_skipped, item0, 0, PAIR_TAG -- the two counters are kept by pair_update_kernel), the constant tables int32
+// n_co, o11, o1 (m x m, pair (a, b) at [a m + b]), then uint64 sum_n11, sumsq_n11, sum_n1 and uint32 n11_ge, n11_gt, agree_ge,
+// agree_gt, or_ge, or_gt, every array padded to 16 bytes.  Beside it: the 0 / 1 byte operands O8, Y8 (built once) and two planes
+// of rep8 (ctl[0] names the plane of the last counted draw; the replicate writes the other one), the per-draw tables r11 and
+// r1, and the control words ctl[0] = plane, ctl[1] = this draw holds a non-finite g.
+constexpr int PAIR_LAYOUT_VERSION = 1;
+constexpr int PAIR_HEADER_WORDS = 8;
+constexpr int64_t PAIR_TAG = 0x52494150;              // "PAIR"
+enum { PAIR_N_CO, PAIR_O11, PAIR_O1, PAIR_SUM_N11, PAIR_SUMSQ_N11, PAIR_SUM_N1, PAIR_N11_GE, PAIR_N11_GT, PAIR_AGREE_GE,
+       PAIR_AGREE_GT, PAIR_OR_GE, PAIR_OR_GT, PAIR_NARRAYS };
+struct PairLayout { int64_t off[PAIR_NARRAYS]; int64_t words; };      // offsets in 8-byte words from the start of the block
+PairLayout pair_layout(int64_t m);
+struct PairState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0;
+    int64_t iblocks = 0, ksteps = 0, plane = 0;       // the operands: item blocks of 32, k-steps of 32 respondents, bytes of one
+    uint64_t* block = nullptr;
+    unsigned char *O8 = nullptr, *Y8 = nullptr, *rep8 = nullptr;
+    int *r11 = nullptr, *r1 = nullptr;
+    int* ctl = nullptr;
+    std::vector<void*> allocs;
+};
+int64_t pair_state_words(int64_t m);
+int pair_alloc(hipStream_t stream, PairState* p, int64_t n, int64_t m, int64_t item0, const double* y);
+void pair_free(PairState* p);
+// after the replicate pass has left this draw's bytes and its non-finite word: the products, then the decisions
+int launch_pair_accumulate(hipStream_t stream, PairState* p);
+int pair_get(hipStream_t stream, PairState* p, const char* name, void* h_out, int64_t bytes);
+int pair_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -355,6 +387,7 @@ struct PpcState {
     double *rowd = nullptr, *cold = nullptr;          // a draw's partials: [strip][3][n], [row block][3][m]
     uint32_t *rowi = nullptr, *coli = nullptr;        //   ... their packed counts
     double* unit_d = nullptr; uint64_t* unit_i = nullptr;     // the items' sums of a draw ([3][m]), for the total
+    PairState pairs;                                  // the pairwise item checks (ppc_pairs.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written

@@ -32,8 +32,24 @@ struct PpcArgs {
     uint64_t seed; uint32_t iter, item0;
     double* rowd; uint32_t* rowi;        // [strip][3][n], [strip][n]: Delta, D(y), D(yrep); the packed counts
     double* cold; uint32_t* coli;        // [row block][3][m], [row block][m]
+    // the pairwise checks (ppc_pairs.hip; read by the BYTES instance only): the replicate's 0 / 1 bytes in the product's
+    // operand layout, written into the plane *cur does NOT name, and the word that tells of a non-finite g in an observed cell
+    unsigned char* rep8; const int* cur; int64_t plane, ksteps; int* bad;
 };
 
+// the BYTES instance's staging area, [PPC_STRIP][PPC_THREADS] bytes of dynamic LDS (the plain instance asks for none and
+// never names it)
+constexpr int PPC_STAGE_BYTES = PPC_STRIP * PPC_THREADS;
+__device__ __forceinline__ unsigned char* ppc_byte_stage()
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ppc_sb[];
+    return ppc_sb;
+}
+
+// BYTES: the same pass also leaves rep[i, j] = [yrep = +1] of the observed cells as bytes for pair_counts_kernel -- strip s is
+// item block s of that layout, a work-group's 256 respondents are its k-steps 8 rb .. 8 rb + 7 -- through 8 KiB of dynamic LDS, so that
+// the stores are the layout's 16-byte pieces.  The instance without BYTES is the kernel as it was before the pairs existed.
+template <bool BYTES>
 __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
 {
     __shared__ double sd[4][PPC_STRIP][3];
@@ -68,6 +84,10 @@ __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
             }
         }
         rD += cD; rO += cO; rR += cR; rI += cI;
+        if constexpr (BYTES) {
+            ppc_byte_stage()[jj * PPC_THREADS + threadIdx.x] = (unsigned char)(cI & PK_R);
+            if (cI & PK_NONFINITE) *a.bad = 1;                // (every writer stores the same word)
+        }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             cD += __shfl_down(cD, off, 64);
@@ -90,6 +110,17 @@ __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
         for (int q = 0; q < 3; ++q)
             a.cold[base + q * a.m] = (sd[0][jj][q] + sd[1][jj][q]) + (sd[2][jj][q] + sd[3][jj][q]);
         a.coli[(int64_t)rb * a.m + j0 + jj] = (si[0][jj] + si[1][jj]) + (si[2][jj] + si[3][jj]);
+    }
+    if constexpr (BYTES) {
+        // piece p = (k-step kk of the work-group, lane L = item jj + 32 x the half of the k-step): 16 respondents of one item
+        unsigned char* dst = a.rep8 + (int64_t)(*a.cur ^ 1) * a.plane + ((int64_t)strip * a.ksteps + (int64_t)rb * 8) * 1024;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int p = (int)threadIdx.x + q * PPC_THREADS, kk = p >> 6, L = p & 63, jj = L & 31;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (jj < w) v = *reinterpret_cast<const uint4*>(ppc_byte_stage() + jj * PPC_THREADS + kk * 32 + (L >> 5) * 16);
+            *reinterpret_cast<uint4*>(dst + (int64_t)p * 16) = v;
+        }
     }
 }
 
@@ -271,6 +302,7 @@ int ppc_alloc(hipStream_t st, PpcState* s, int64_t n, int64_t m, int64_t item0, 
 
 void ppc_free(PpcState* s)
 {
+    pair_free(&s->pairs);
     for (void* p : s->allocs) hipFree(p);
     *s = PpcState{};
 }
@@ -281,7 +313,14 @@ int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const do
     PpcArgs a{};
     a.f = f; a.mu = mu; a.y = y; a.n = s->n; a.m = s->m; a.seed = seed; a.iter = iter; a.item0 = (uint32_t)s->item0;
     a.rowd = s->rowd; a.rowi = s->rowi; a.cold = s->cold; a.coli = s->coli;
-    hipLaunchKernelGGL(ppc_replicate_kernel, dim3((unsigned)s->rblocks, (unsigned)s->strips), dim3(PPC_THREADS), 0, st, a);
+    const dim3 grid((unsigned)s->rblocks, (unsigned)s->strips);
+    if (s->pairs.on) {
+        PairState* p = &s->pairs;
+        a.rep8 = p->rep8; a.cur = p->ctl; a.plane = p->plane; a.ksteps = p->ksteps; a.bad = p->ctl + 1;
+        GP_HIP(hipMemsetAsync(p->ctl + 1, 0, sizeof(int), st));
+        hipLaunchKernelGGL(ppc_replicate_kernel<true>, grid, dim3(PPC_THREADS), PPC_STAGE_BYTES, st, a);
+    } else
+        hipLaunchKernelGGL(ppc_replicate_kernel<false>, grid, dim3(PPC_THREADS), 0, st, a);
     GP_HIP(hipGetLastError());
     PpcUnitArgs u{};
     u.rowd = s->rowd; u.rowi = s->rowi; u.cold = s->cold; u.coli = s->coli;
@@ -293,6 +332,7 @@ int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const do
     hipLaunchKernelGGL(ppc_total_kernel, dim3(1), dim3(PPC_THREADS), 0, st, u);
     GP_HIP(hipGetLastError());
     s->draws += 1;
+    if (s->pairs.on) GP_TRY(launch_pair_accumulate(st, &s->pairs));
     return 0;
 }
 

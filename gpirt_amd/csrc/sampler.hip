@@ -1571,6 +1571,48 @@ int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states,
     return ppc_combine(h, chains, d_states, out);
 }
 
+// ---- pairwise item checks (ppc_pairs.hip): an add-on to the PPC state ----------------------------------------------------
+static int pairs_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.pairs.on) return 0;
+    set_error("the pairwise item checks are not enabled (gpirt_sampler_ppc_pairs_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_ppc_pairs_enable(gpirt_sampler_t s, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    pair_free(&s->ppc.pairs);
+    if (!on) return 0;
+    GP_TRY(ppc_needs_on(s));
+    const int rc = pair_alloc(s->h->stream, &s->ppc.pairs, s->n, s->m, s->opt.item0, s->y);
+    if (rc) pair_free(&s->ppc.pairs);
+    return rc;
+}
+
+int gpirt_sampler_ppc_pairs_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(pairs_needs_on(s));
+    return pair_get(s->h->stream, &s->ppc.pairs, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_pairs_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(pairs_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.pairs.block;
+    *bytes = pair_state_words(s->m) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_pairs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out)
+{
+    return pair_combine(h, chains, d_states, out);
+}
+
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
 static int rank_needs_on(gpirt_sampler_t s)
 {
@@ -1961,6 +2003,7 @@ struct ChainRun {
     const double* y_new;
     int64_t n_new;
     bool predict;                     // gpirt_mcmc_predict: the score state also predicts the unseen answers (it travels inside keep_score)
+    bool pairs;                       // gpirt_mcmc_pairs: the PPC state also checks the item pairs (it travels inside keep_ppc)
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2047,6 +2090,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         rc = cr ? gpirt_sampler_summary_enable_planned(s, sm->parts | GPIRT_SUM_DIAG, S_it) : gpirt_sampler_summary_enable(s, sm->parts);
     const bool ppc = cr && cr->keep_ppc;
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
+    if (!rc && ppc && cr->pairs) rc = gpirt_sampler_ppc_pairs_enable(s, 1);
     const bool ranks = cr && cr->keep_rank;
     if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
     const bool score = cr && cr->keep_score;
@@ -2296,7 +2340,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
-                      gpirt_score_predict* predict = nullptr)
+                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2357,6 +2401,15 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
             return GPIRT_E_ARG;
         }
     }
+    if (pairs) {
+        GP_ARG(ppc);
+        GP_ARG(pairs->reserved0 == 0 && pairs->reserved[0] == 0 && pairs->reserved[1] == 0 && pairs->reserved[2] == 0 && pairs->reserved[3] == 0);
+        if (pairs->top < 1 || pairs->top > GPIRT_PAIRS_MAX_TOP) {
+            set_error("pairwise PPC: top = %d is outside 1..%d", pairs->top, GPIRT_PAIRS_MAX_TOP);
+            return GPIRT_E_ARG;
+        }
+        if (n > GPIRT_PAIRS_MAX_N) { set_error("pairwise PPC: n = %lld is beyond %d respondents", (long long)n, GPIRT_PAIRS_MAX_N); return GPIRT_E_ARG; }
+    }
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
@@ -2374,7 +2427,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         sm.parts = parts | extra;
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
-                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr };
+                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2389,6 +2442,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     if (!rc && ppc) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].block;
         rc = ppc_combine(h, chains, st.data(), ppc);
+    }
+    if (!rc && pairs) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].pairs.block;
+        rc = pair_combine(h, chains, st.data(), pairs);
     }
     for (auto& k : keep) summary_free(&k);
     if (!rc && ranks) {
@@ -2519,6 +2576,24 @@ int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict);
+}
+
+// ---- the pairwise item checks ---------------------------------------------------------------------------------------------------
+int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs)
+{
+    GP_ARG(opts && ppc && pairs);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_pairs needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs);
 }
 
 }  // extern "C"

@@ -246,6 +246,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: posterior predictive checks are not offered for item shards "
                          "(the respondents' statistics would need an all-reduce per draw)")
 
+    def ppc_pairs_enable(self, top=20, on=True):
+        raise ValueError("ShardedSampler: the pairwise item checks are not offered for item shards "
+                         "(a pair's table runs over two shards' replicates)")
+
     # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         self.engine.rank_enable(on, pivots, pairwise)

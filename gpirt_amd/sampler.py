@@ -84,6 +84,14 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       chains (draws stacked per chain only with chains given).  The chain itself is untouched: the replicate draws from
       the counter-based generator under both RNG contracts and consumes nothing of R's stream.  ppc=None leaves every
       other path as it is.
+      ppc=dict(pairs=True, top=20) also checks every PAIR of items (gpirt_mcmc_pairs): "ppc" gains "pairs" with, per
+      ordered pair (a, b) as m x m arrays, the observed 2 x 2 table over the co-observed respondents (n_co, obs_n11,
+      obs_n10, obs_n01, obs_n00), the replicates' (rep_n11_mean, rep_n11_var, rep_n10_mean, rep_n01_mean, rep_n00_mean),
+      agree_obs / agree_rep_mean, log_or_obs and the posterior predictive p-values ppp_n11, ppp_agree, ppp_or with their
+      mid-p forms; "extreme" lists the `top` (1..64) pairs a < b whose ppp_or_mid lies farthest from 0.5 -- the pairs whose
+      dependence the one-dimensional model does not reproduce; pair_draws, pair_skipped (a draw with a non-finite g in an
+      observed cell is skipped whole for the pairs) and the raw sums and counts.  Memory: 68 bytes per ordered pair on the
+      device (71 MB at m = 1024) plus the int8 operands; n <= 65534.  ppc=True is exactly as without it.
     ranks: True, or dict(pivots="median", pairwise=False, probs=(0.025, 0.5, 0.975)), adds the rank posteriors
       (gpirt_mcmc_ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
       the smallest; ties take the mid-rank) and accumulates, in "ranks": rank_mean, rank_var, rank_quantiles
@@ -153,10 +161,21 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         else:
             score = dict(data=score, probs=SC.DEFAULT_PROBS, predict=False, top=SC.DEFAULT_TOP)
         score["data"] = np.asfortranarray(SC.check_y_new(score["data"], y.shape[1]))
+    pairs = None
+    if isinstance(ppc, dict):
+        from . import ppc as P
+        unknown = set(ppc) - {"pairs", "top"}
+        if unknown:
+            raise ValueError(f"ppc: a dict may give pairs and top (unknown keys {sorted(unknown)})")
+        if "top" in ppc and not ppc.get("pairs"):
+            raise ValueError("ppc: top needs pairs=True")
+        if ppc.get("pairs"):
+            pairs = dict(top=P.check_pairs_top(ppc.get("top", P.DEFAULT_PAIRS_TOP)))
+        ppc = True
     if quantiles is not None or ppc or ranks is not None or score is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score)
+                               align, quantiles, bool(ppc), ranks, score, pairs)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -290,12 +309,13 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None):
+                    score=None, pairs=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
     same chains with the rank posteriors (with or without the checks).  score (dict(data, probs)): gpirt_mcmc_score, the
-    same chains scoring the new respondents `data` (with or without the checks and the ranks)."""
+    same chains scoring the new respondents `data` (with or without the checks and the ranks).  pairs (dict(top)):
+    gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -358,7 +378,23 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if score is not None:
+    if pairs is not None:
+        pq, pqarr = P.pairs_struct(m, pairs["top"])
+        sc = pr = None
+        if score is not None:
+            from . import score as SC
+            sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
+            if score.get("predict"):
+                pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
+        rc = lib.gpirt_mcmc_pairs(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp),
+                                  C.byref(rk) if ranks is not None else None,
+                                  _ptr(score["data"]) if score is not None else None,
+                                  score["data"].shape[0] if score is not None else 0,
+                                  C.byref(sc) if sc is not None else None, C.byref(pr) if pr is not None else None,
+                                  C.byref(pq))
+    elif score is not None:
         from . import score as SC
         sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
         args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
@@ -401,6 +437,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["quantiles"] = Q.quantiles_result(q, qarr)
     if with_ppc:
         out["ppc"] = P.result(pp, parr)
+        if pairs is not None:
+            out["ppc"]["pairs"] = P.pairs_result(pq, pqarr)
     if ranks is not None:
         out["ranks"] = RK.result(rk, rkarr)
     if score is not None:
@@ -719,6 +757,59 @@ class Sampler:
             out[unit] = P.derive(d)
         out["totals"] = {k: float(v) for k, v in P.derive(dict(tot)).items()}
         return out
+
+    # -- pairwise item checks inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_pairs_*, gpirt_amd.ppc)
+    def ppc_pairs_enable(self, top=20, on=True):
+        """Allocate and zero the pairwise accumulators on a sampler whose ppc_enable is on and form the constants n_co, o11,
+        o1: from then on every ppc_accumulate also adds that draw's replicate to every item pair's 2 x 2 table statistics.
+        top (1..64): how many extreme pairs ppc_pairs() lists.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_pairs_enable(self._s, 0))
+            return
+        from . import ppc as P
+        self._pairs_top = P.check_pairs_top(top)
+        check(self.lib.gpirt_sampler_ppc_pairs_enable(self._s, 1))
+
+    def ppc_pairs_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.PAIRS_FIELDS; float64 m x m), sum_n11, sumsq_n11, sum_n1 (uint64),
+        n11_ge, n11_gt, agree_ge, agree_gt, or_ge, or_gt (uint32), counts (int64: pair_draws, pair_skipped) and, of the last
+        counted draw, rep (int8, n x m) and r11, r1 (int32, m x m).  Pair (a, b) is at [a, b]."""
+        m = self.m
+        if name == "counts":
+            out = np.empty(2, dtype=np.int64)
+        elif name == "rep":
+            out = np.empty((self.n, m), dtype=np.int8, order="F")
+        elif name in ("r11", "r1"):
+            out = np.empty((m, m), dtype=np.int32)
+        elif name in _lib.PAIRS_SUMS:
+            out = np.empty((m, m), dtype=np.uint64)
+        elif name in _lib.PAIRS_COUNTS:
+            out = np.empty((m, m), dtype=np.uint32)
+        else:
+            out = np.empty((m, m))
+        check(self.lib.gpirt_sampler_ppc_pairs_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def ppc_pairs_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the pairwise accumulators: what
+        gpirt_amd.ppc.pairs_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_pairs_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_pairs(self, top=None) -> dict:
+        """Every finished output of this sampler's pairwise accumulators (gpirt_amd.ppc.pairs_result's shape):
+        gpirt_ppc_pairs_combine over its own state; top defaults to ppc_pairs_enable's."""
+        from . import ppc as P
+        return P.pairs_combine(self.handle, [self], top=getattr(self, "_pairs_top", P.DEFAULT_PAIRS_TOP) if top is None else top)
 
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):

@@ -828,6 +828,117 @@ int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_
                        gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
                        const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict);
 
+/* ------------------------------------------------------------- pairwise item checks: joint counts and odds ratios of item pairs -- */
+/* Does the model's one latent dimension hold (library version 111)?  Given theta, answers to different items are independent;
+ * a second dimension or a pair of near-duplicate items leaves every item's yes count well replicated and shows only in how
+ * items co-occur.  The check is the posterior predictive distribution of each item pair's 2 x 2 table and of its odds ratio.
+ * An add-on to the PPC: it can only be enabled on a sampler whose ppc_enable is on, and it accumulates inside the same
+ * ppc_accumulate call, from the same replicate.  With n respondents and m items:
+ *   O[i, j]   = 1 where y_ij is observed
+ *   Y[i, j]   = [y_ij = +1]
+ *   rep[i, j] = [yrep_ij = +1] O[i, j], yrep EXACTLY the replicate ppc_accumulate forms for that draw: the same p arithmetic
+ *               and the same uniform item_uniform(seed, iter, GPIRT_ST_PPC, item0 + j, i).  No second stream, nothing else drawn.
+ * Constants, formed once at enable: n_co = O^T O, o11 = Y^T Y, o1 = Y^T O.  Per draw: r11 = rep^T rep, r1 = rep^T O.  All are
+ * m x m and exact int32 counts (products of 0 / 1 bytes on the int8 matrix cores).
+ * For x in {o, r} the 2 x 2 table of the pair (a, b), a != b, over the co-observed respondents is
+ *   t11 = x11[a, b],  t10 = x1[a, b] - x11[a, b],  t01 = x1[b, a] - x11[a, b],  t00 = n_co[a, b] - t11 - t10 - t01.
+ * Per COUNTED draw and ordered pair with n_co > 0, everything in integers:
+ *   sum_n11 += r11,  sumsq_n11 += r11^2,  sum_n1[a, b] += r1[a, b] (not symmetric)                    uint64
+ *   n11_ge / n11_gt     += [r11 >= / > o11]                                                           uint32
+ *   agree_ge / agree_gt += [r11 + r00 >= / > o11 + o00]
+ *   or_ge / or_gt       += [lhs >= / > rhs], the odds ratios with the half-count correction compared by cross-multiplication,
+ *                          without a division:  lhs = (2 r11 + 1)(2 r00 + 1)(2 o10 + 1)(2 o01 + 1),
+ *                                               rhs = (2 o11 + 1)(2 o00 + 1)(2 r10 + 1)(2 r01 + 1);
+ *                          both are <= (n + 1)^4, exact in uint64 for n <= GPIRT_PAIRS_MAX_N = 65534 (ppc_pairs_enable returns
+ *                          GPIRT_E_ARG above that).
+ * The diagonal and the pairs with n_co = 0 keep every counter at 0 and finish as NaN (n_co itself is reported everywhere).
+ * A draw with a non-finite g in ANY observed cell is skipped whole for the pairs: pair_skipped += 1 and nothing else changes
+ * (as pred_skipped works); the PPC's own per-unit `nonfinite` rule is untouched.  Otherwise pair_draws += 1.
+ * Finished on the host as m x m doubles, pair (a, b) at [a m + b], with S = pair_draws (GPIRT_PAIRS_* below):
+ *   n_co; obs_n11, obs_n10, obs_n01, obs_n00;
+ *   rep_n11_mean = sum_n11 / S and rep_n11_var = (S sumsq_n11 - sum_n11^2) / (S (S - 1)), the numerator in exact integers,
+ *   rounded once (NaN for S < 2);
+ *   rep_n10_mean, rep_n01_mean, rep_n00_mean: (sum_n1[a, b] - sum_n11) / S, (sum_n1[b, a] - sum_n11) / S and
+ *   (S n_co + sum_n11 - sum_n1[a, b] - sum_n1[b, a]) / S, each numerator an exact integer;
+ *   agree_obs = (o11 + o00) / n_co and agree_rep_mean = (S n_co + 2 sum_n11 - sum_n1[a, b] - sum_n1[b, a]) / (S n_co);
+ *   log_or_obs = log(((2 o11 + 1)(2 o00 + 1)) / ((2 o10 + 1)(2 o01 + 1))): one division of two exact integers, one log;
+ *   ppp_n11, ppp_agree, ppp_or = ge / S and their mid-p forms ppp_*_mid = (ge + gt) / 2S.  Everything NaN for S = 0.
+ *   extreme: the `top` pairs a < b by decreasing |ppp_or_mid - 0.5|, ties to the lowest (a, b) (a pair whose ppp_or_mid is NaN
+ *   is never listed); 1 <= top <= GPIRT_PAIRS_MAX_TOP, the Python default is 20: their indices, ppp_or_mid and log_or_obs,
+ *   padded with -1 / NaN.
+ * Pooling C chains (gpirt_ppc_pairs_combine) adds every array and both counters and refuses blocks with another n, m or
+ * n_co (o11 and o1 are compared too).  The theta -> -theta reflection changes nothing, so there is no signs argument.
+ * There are no atomics: each ordered pair is owned by one thread, so two runs give a bit-identical state.  Nothing is drawn:
+ * the chain, the IRFs, R's stream position and THE PPC STATE BLOCK are bit for bit what they are without the pairs.  Item
+ * shards stay refused, as for ppc_enable.
+ * Device memory per state: 48 bytes of accumulators per ordered pair (3 uint64 + 6 uint32), 12 of constants and 8 of per-draw
+ * tables: about 71 MB at m = 1024 and 1.1 GB at m = 4096.  The n x m int8 operands are extra: O, Y and two planes of rep,
+ * padded to 128 items and 256 respondents (34 MB at 8192 x 1024). */
+#define GPIRT_PAIRS_MAX_TOP  64
+#define GPIRT_PAIRS_MAX_N    65534
+#define GPIRT_PAIRS_N_CO            0
+#define GPIRT_PAIRS_OBS_N11         1
+#define GPIRT_PAIRS_OBS_N10         2
+#define GPIRT_PAIRS_OBS_N01         3
+#define GPIRT_PAIRS_OBS_N00         4
+#define GPIRT_PAIRS_REP_N11_MEAN    5
+#define GPIRT_PAIRS_REP_N11_VAR     6
+#define GPIRT_PAIRS_REP_N10_MEAN    7
+#define GPIRT_PAIRS_REP_N01_MEAN    8
+#define GPIRT_PAIRS_REP_N00_MEAN    9
+#define GPIRT_PAIRS_AGREE_OBS       10
+#define GPIRT_PAIRS_AGREE_REP_MEAN  11
+#define GPIRT_PAIRS_LOG_OR_OBS      12
+#define GPIRT_PAIRS_PPP_N11         13
+#define GPIRT_PAIRS_PPP_N11_MID     14
+#define GPIRT_PAIRS_PPP_AGREE       15
+#define GPIRT_PAIRS_PPP_AGREE_MID   16
+#define GPIRT_PAIRS_PPP_OR          17
+#define GPIRT_PAIRS_PPP_OR_MID      18
+#define GPIRT_PAIRS_NFIELDS         19
+/* HOST pointers (NULL: not wanted); every m x m array holds the pair (a, b) at [a m + b]. */
+typedef struct gpirt_ppc_pairs {
+    int        top;                            /* in: 1..GPIRT_PAIRS_MAX_TOP */
+    int        reserved0;                      /* must be 0 */
+    double*    field[GPIRT_PAIRS_NFIELDS];     /* m x m each */
+    uint64_t*  sum_n11;                        /* m x m */
+    uint64_t*  sumsq_n11;
+    uint64_t*  sum_n1;
+    uint32_t*  count[6];                       /* m x m each: n11_ge, n11_gt, agree_ge, agree_gt, or_ge, or_gt */
+    int64_t*   extreme_pairs;                  /* top x 2: a, b */
+    double*    extreme_ppp_or_mid;             /* top */
+    double*    extreme_log_or_obs;             /* top */
+    int64_t    n, m;                           /* out */
+    int64_t    pair_draws, pair_skipped;       /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_ppc_pairs;
+/* Stage API.  ppc_pairs_enable(on != 0) allocates and zeroes the state on a sampler with ppc_enable on (GPIRT_E_ARG without,
+ * and for n > GPIRT_PAIRS_MAX_N; on = 0 frees it; ppc_enable called again frees it too) and forms the constants.  From then on
+ * every ppc_accumulate also adds the draw to the pairs.  ppc_pairs_get copies one array by name to the host, `bytes` its exact
+ * size: every finished field by the lower-case name of its GPIRT_PAIRS_* index (double, m x m), "sum_n11", "sumsq_n11",
+ * "sum_n1" (uint64), "n11_ge", "n11_gt", "agree_ge", "agree_gt", "or_ge", "or_gt" (uint32), "counts" (int64: pair_draws,
+ * pair_skipped), and of the last COUNTED draw "rep" (int8, n x m, column-major as y is) and "r11", "r1" (int32, m x m).
+ * ppc_pairs_state returns the ONE device block, apart from the PPC block: a header of 8 int64 -- n, m, layout version (1),
+ * pair_draws, pair_skipped, item0, 0, the tag 0x52494150 ("PAIR") --, then the constant tables int32 n_co, o11, o1, then the
+ * accumulators uint64 sum_n11, sumsq_n11, sum_n1 and uint32 n11_ge, n11_gt, agree_ge, agree_gt, or_ge, or_gt; every array is
+ * m x m and starts on a 16-byte boundary. */
+int gpirt_sampler_ppc_pairs_enable(gpirt_sampler_t s, int on);
+int gpirt_sampler_ppc_pairs_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_pairs_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_pairs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out);
+/* gpirt_mcmc_predict with the pairwise checks (ppc and pairs are required; score and predict may be NULL, with y_new NULL and
+ * n_new 0; predict needs score): the same chains and the same PPC, every chain also accumulating the pairs inside its
+ * ppc_accumulate -- under the item RNG from the verified checkpoint, so a hang-guard rollback counts no draw twice --, pooled
+ * into pairs. */
+int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                     int sample_iterations, int burn_iterations, const double* h_prior_means,
+                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                     gpirt_ppc_pairs* pairs);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
