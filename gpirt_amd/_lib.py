@@ -128,6 +128,32 @@ class PpcPairs(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+# theta-binned item fit (include/gpirt_hip.h GPIRT_BINS_*): the finished fields per (bin, item), per item and per bin, in
+# order; the raw arrays of the state block with their dtypes and shapes ("c": B x m, "i": m, "b": B)
+BINS_CELL_FIELDS = ("obs_rate", "rep_rate", "exp_rate", "z_mean", "ppp_cell", "ppp_cell_mid", "n_mean")
+BINS_ITEM_FIELDS = ("ppp_chi2", "ppp_chi2_mid", "chi2_obs_mean", "chi2_rep_mean")
+BINS_BIN_FIELDS = ("occupancy", "bin_lo", "bin_hi")
+BINS_RAW = (("sum_n", "u8", "c"), ("sum_t", "u8", "c"), ("sum_r", "u8", "c"), ("sum_e", "f8", "c"), ("sum_z", "f8", "c"),
+            ("cell_ge", "u4", "c"), ("cell_gt", "u4", "c"), ("cell_empty", "u4", "c"), ("chi_ge", "u4", "i"),
+            ("chi_gt", "u4", "i"), ("chi_obs_sum", "f8", "i"), ("chi_rep_sum", "f8", "i"), ("occ_sum", "u8", "b"))
+BINS_MAX_H, BINS_MAX_TOP, BINS_TAG = 15, 64, 0x534E4942
+
+
+class PpcBins(C.Structure):
+    """gpirt_ppc_bins (include/gpirt_hip.h): top, the cuts, host pointers per output (NULL: not wanted) and the counters."""
+    _fields_ = [("top", C.c_int), ("h", C.c_int), ("cuts", C.c_int * (BINS_MAX_H + 1)),
+                ("cell", C.POINTER(C.c_double) * len(BINS_CELL_FIELDS)), ("item", C.POINTER(C.c_double) * len(BINS_ITEM_FIELDS)),
+                ("bin", C.POINTER(C.c_double) * len(BINS_BIN_FIELDS)),
+                ("sum_n", C.POINTER(C.c_uint64)), ("sum_t", C.POINTER(C.c_uint64)), ("sum_r", C.POINTER(C.c_uint64)),
+                ("sum_e", C.POINTER(C.c_double)), ("sum_z", C.POINTER(C.c_double)),
+                ("cell_count", C.POINTER(C.c_uint32) * 3), ("chi_count", C.POINTER(C.c_uint32) * 2),
+                ("chi_obs_sum", C.POINTER(C.c_double)), ("chi_rep_sum", C.POINTER(C.c_double)),
+                ("occ_sum", C.POINTER(C.c_uint64)), ("worst_items", C.POINTER(C.c_int64)),
+                ("worst_ppp_chi2_mid", C.POINTER(C.c_double)), ("worst_chi2_obs_mean", C.POINTER(C.c_double)),
+                ("n", C.c_int64), ("m", C.c_int64), ("B", C.c_int64), ("bin_draws", C.c_int64), ("bin_skipped", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -311,6 +337,14 @@ SIGNATURES = {
                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                  C.POINTER(ScorePredict), C.POINTER(PpcPairs)]),
+    "gpirt_sampler_ppc_bins_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int), _i32]),
+    "gpirt_sampler_ppc_bins_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_bins_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_bins_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(PpcBins)]),
+    "gpirt_mcmc_bins": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

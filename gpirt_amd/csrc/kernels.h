@@ -379,6 +379,51 @@ int launch_pair_accumulate(hipStream_t stream, PairState* p);
 int pair_get(hipStream_t stream, PairState* p, const char* name, void* h_out, int64_t bytes);
 int pair_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out);
 
+// ppc_bins.hip: the theta-binned item fit (gpirt_sampler_ppc_bins_*, gpirt_mcmc_bins), an add-on to a PPC state.  Its
+// accumulators are ONE device block of 8-byte words of their own: a header of BIN_HEADER_WORDS int64 (n, m, layout version,
+// bin_draws, bin_skipped, item0, B, BIN_TAG -- the two counters are kept by bin_update_kernel), BIN_CUT_WORDS int64 with the
+// cuts, then the arrays of BinLayout, cell (b, j) at [b m + j], every array padded to 16 bytes.  Beside it: this draw's bins
+// (uint8 per respondent, BIN_NONE off the grid), the last counted draw's, n_b, the control words ctl[0] = a theta is off the
+// grid, ctl[1] = this draw holds a non-finite g in an observed cell, the replicate pass's partial tables per block of 256
+// respondents ([row block][item][bin]: the packed counts N | T << 10 | R << 20, E and V) and the last counted draw's tables.
+constexpr int BIN_LAYOUT_VERSION = 1;
+constexpr int BIN_HEADER_WORDS = 8;
+constexpr int BIN_CUT_WORDS = 16;
+constexpr int64_t BIN_TAG = 0x534E4942;               // "BINS"
+constexpr unsigned char BIN_NONE = 0xFF;
+enum { BIN_SUM_N, BIN_SUM_T, BIN_SUM_R,                              // uint64, B x m
+       BIN_SUM_E, BIN_SUM_Z,                                         // double, B x m
+       BIN_CELL_GE, BIN_CELL_GT, BIN_CELL_EMPTY,                     // uint32, B x m
+       BIN_CHI_GE, BIN_CHI_GT,                                       // uint32, m
+       BIN_CHI_OBS, BIN_CHI_REP,                                     // double, m
+       BIN_OCC,                                                      // uint64, B
+       BIN_NARRAYS };
+struct BinLayout { int64_t off[BIN_NARRAYS]; int64_t words; };       // offsets in 8-byte words from the start of the block
+BinLayout bin_layout(int64_t m, int64_t B);
+struct BinState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0;
+    int h = 0, B = 0, rblocks = 0;
+    int cuts[GPIRT_BINS_MAX_H + 1] = {};
+    uint64_t* block = nullptr;
+    unsigned char *bin_cur = nullptr, *bin_last = nullptr;            // [n]
+    uint32_t* nb = nullptr;                                           // [32]: this draw's n_b
+    int* ctl = nullptr;
+    uint32_t* part_i = nullptr; double *part_e = nullptr, *part_v = nullptr;      // [row block][m][B]
+    int32_t* tab_i = nullptr; double* tab_d = nullptr;                // the last counted draw: [3][B][m] N, T, R; [2][B][m] E, V
+    std::vector<void*> allocs;
+};
+int64_t bin_state_words(int64_t m, int64_t B);
+int bin_check_cuts(int h, const int* cuts);          // GPIRT_E_ARG (with the message) unless 1 <= d_1 < ... < d_h <= 499, 1 <= h <= 15
+int bin_alloc(hipStream_t stream, BinState* p, int64_t n, int64_t m, int64_t item0, int rblocks, int h, const int* cuts);
+void bin_free(BinState* p);
+// before the replicate pass: this draw's bins, n_b and ctl[0] from theta (n doubles on the device); clears ctl[1]
+int launch_bin_assign(hipStream_t stream, BinState* p, const double* theta);
+// after the replicate pass has left this draw's partial tables and ctl[1]: the tables, the decisions, the accumulators
+int launch_bin_update(hipStream_t stream, BinState* p);
+int bin_get(hipStream_t stream, BinState* p, const char* name, void* h_out, int64_t bytes);
+int bin_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -388,14 +433,16 @@ struct PpcState {
     uint32_t *rowi = nullptr, *coli = nullptr;        //   ... their packed counts
     double* unit_d = nullptr; uint64_t* unit_i = nullptr;     // the items' sums of a draw ([3][m]), for the total
     PairState pairs;                                  // the pairwise item checks (ppc_pairs.hip; on == false: off)
+    BinState bins;                                    // the theta-binned item fit (ppc_bins.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written
 int ppc_alloc(hipStream_t stream, PpcState* s, int64_t n, int64_t m, int64_t item0, const double* y);
 void ppc_free(PpcState* s);
-// adds the replicate of one draw: f, mu, y n x m on the device; iter = the completed-iteration counter of that state
+// adds the replicate of one draw: f, mu, y n x m on the device; iter = the completed-iteration counter of that state;
+// theta (n, on the device) is read only with the bins on
 int launch_ppc_accumulate(hipStream_t stream, PpcState* s, const double* f, const double* mu, const double* y, uint64_t seed,
-                          uint32_t iter);
+                          uint32_t iter, const double* theta);
 int ppc_seal(hipStream_t stream, PpcState* s);      // refreshes the header (synchronises)
 int ppc_fetch(hipStream_t stream, PpcState* s, std::vector<uint64_t>& host);     // seals and copies the block to the host
 int ppc_field_index(const char* name);              // GPIRT_PPC_* of a field name, -1 if unknown
@@ -412,6 +459,14 @@ int ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt
 // and, with the pairwise flag, on a 16-byte boundary uint32 lt[n][ld], ld = n rounded up to 4 (the padding stays 0).  The
 // header's two draw counters are kept by the kernel itself (the device decides whether a draw is skipped).
 constexpr int RANK_LAYOUT_VERSION = 1;
+// the rule of quantiles.grid_index and of summary_hist_accumulate_kernel: k where theta is bit for bit -5 + 0.01 k, else -1
+// (ranks.hip and ppc_bins.hip)
+__device__ __forceinline__ int grid_index(double t)
+{
+    const double k = rint((t + 5.0) * 100.0);
+    if (!(k >= 0.0 && k <= (double)(GPIRT_NGRID - 1) && -5.0 + k * 0.01 == t)) return -1;
+    return (int)k;
+}
 constexpr int RANK_HEADER_WORDS = 8 + GPIRT_RANK_MAX_PIVOTS_CLOSED;
 struct RankState {
     bool on = false, pairwise = false;

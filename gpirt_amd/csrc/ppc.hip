@@ -35,7 +35,24 @@ struct PpcArgs {
     // the pairwise checks (ppc_pairs.hip; read by the BYTES instance only): the replicate's 0 / 1 bytes in the product's
     // operand layout, written into the plane *cur does NOT name, and the word that tells of a non-finite g in an observed cell
     unsigned char* rep8; const int* cur; int64_t plane, ksteps; int* bad;
+    // the theta-binned item fit (ppc_bins.hip; read by the BINS instances only): this draw's bin of every respondent, the
+    // partial tables [row block][item][bin] and the word that tells of a non-finite g in an observed cell
+    const unsigned char* bin; int B; uint32_t* bpi; double* bpe; double* bpv; int* bbad;
 };
+
+// the BINS instances' staging area: a work-group's 256 cells of one item (E's and V's terms, the flags 1 = observed,
+// 2 = y = +1, 4 = rep = 1), the respondents' bins, and the four waves' partial sums per bin
+struct PpcBinStage {
+    double e[PPC_THREADS], v[PPC_THREADS];
+    unsigned char flag[PPC_THREADS], bin[PPC_THREADS];
+    double pe[4][32], pv[4][32];
+    uint32_t pi[4][32];
+};
+__device__ __forceinline__ PpcBinStage* ppc_bin_stage()
+{
+    __shared__ PpcBinStage ppc_bs;
+    return &ppc_bs;
+}
 
 // the BYTES instance's staging area, [PPC_STRIP][PPC_THREADS] bytes of dynamic LDS (the plain instance asks for none and
 // never names it)
@@ -49,7 +66,11 @@ __device__ __forceinline__ unsigned char* ppc_byte_stage()
 // BYTES: the same pass also leaves rep[i, j] = [yrep = +1] of the observed cells as bytes for pair_counts_kernel -- strip s is
 // item block s of that layout, a work-group's 256 respondents are its k-steps 8 rb .. 8 rb + 7 -- through 8 KiB of dynamic LDS, so that
 // the stores are the layout's 16-byte pieces.  The instance without BYTES is the kernel as it was before the pairs existed.
-template <bool BYTES>
+// BINS: the same pass also leaves, per item and bin of theta, N, T, R, E and V over the work-group's 256 respondents (ppc_bins.hip):
+// a lane stages its cell's p and p q in LDS; lane b < B of every wave then sums the cells of bin b among its wave's 64 rows
+// in row order, and lane 32 + b of wave 0 adds the four waves' sums in wave order: every double in a fixed order, g read once.
+// The instances without BINS are the kernels as they were before the bins existed.
+template <bool BYTES, bool BINS>
 __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
 {
     __shared__ double sd[4][PPC_STRIP][3];
@@ -62,9 +83,12 @@ __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double rD = 0.0, rO = 0.0, rR = 0.0;
     uint32_t rI = 0;
+    if constexpr (BINS) ppc_bin_stage()->bin[threadIdx.x] = live ? a.bin[i] : BIN_NONE;     // (the loop's first barrier follows)
     for (int jj = 0; jj < w; ++jj) {
         double cD = 0.0, cO = 0.0, cR = 0.0;
         uint32_t cI = 0;
+        [[maybe_unused]] double bE = 0.0, bV = 0.0;
+        [[maybe_unused]] unsigned bF = 0;
         if (live) {
             const int64_t c = i + (j0 + jj) * a.n;
             const double yv = a.y[c], g = a.f[c] + a.mu[c];
@@ -80,6 +104,11 @@ __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
                     cR = 2.0 * (l1 + fmax(-yr * g, 0.0));
                     if (yr != yv) cD = yv * g;
                     cI = (yr > 0.0 ? PK_R : 0u) + (((g > 0.0) == (yv > 0.0)) ? PK_CORRECT : 0u);
+                    if constexpr (BINS) {
+                        const double q = g >= 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e);
+                        bE = p; bV = p * q;
+                        bF = 1u | (yv > 0.0 ? 2u : 0u) | (yr > 0.0 ? 4u : 0u);
+                    }
                 }
             }
         }
@@ -87,6 +116,32 @@ __global__ __launch_bounds__(PPC_THREADS) void ppc_replicate_kernel(PpcArgs a)
         if constexpr (BYTES) {
             ppc_byte_stage()[jj * PPC_THREADS + threadIdx.x] = (unsigned char)(cI & PK_R);
             if (cI & PK_NONFINITE) *a.bad = 1;                // (every writer stores the same word)
+        }
+        if constexpr (BINS) {
+            PpcBinStage* bs = ppc_bin_stage();
+            if (cI & PK_NONFINITE) *a.bbad = 1;
+            bs->e[threadIdx.x] = bE; bs->v[threadIdx.x] = bV; bs->flag[threadIdx.x] = (unsigned char)bF;
+            __syncthreads();
+            if (lane < a.B) {
+                double E = 0.0, V = 0.0;
+                uint32_t pk = 0;
+                for (int r = wv * 64; r < wv * 64 + 64; ++r) {
+                    const unsigned fl = bs->flag[r];
+                    if (bs->bin[r] == lane && (fl & 1u)) {
+                        E += bs->e[r]; V += bs->v[r];
+                        pk += 1u + ((fl >> 1) & 1u) * PK_CORRECT + ((fl >> 2) & 1u) * PK_NONFINITE;      // N | T << 10 | R << 20
+                    }
+                }
+                bs->pe[wv][lane] = E; bs->pv[wv][lane] = V; bs->pi[wv][lane] = pk;
+            }
+            __syncthreads();
+            if (wv == 0 && lane >= 32 && lane - 32 < a.B) {
+                const int b = lane - 32;
+                const int64_t at = ((int64_t)rb * a.m + j0 + jj) * a.B + b;
+                a.bpe[at] = ((bs->pe[0][b] + bs->pe[1][b]) + bs->pe[2][b]) + bs->pe[3][b];
+                a.bpv[at] = ((bs->pv[0][b] + bs->pv[1][b]) + bs->pv[2][b]) + bs->pv[3][b];
+                a.bpi[at] = bs->pi[0][b] + bs->pi[1][b] + bs->pi[2][b] + bs->pi[3][b];
+            }
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -303,24 +358,35 @@ int ppc_alloc(hipStream_t st, PpcState* s, int64_t n, int64_t m, int64_t item0, 
 void ppc_free(PpcState* s)
 {
     pair_free(&s->pairs);
+    bin_free(&s->bins);
     for (void* p : s->allocs) hipFree(p);
     *s = PpcState{};
 }
 
 int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const double* mu, const double* y, uint64_t seed,
-                          uint32_t iter)
+                          uint32_t iter, const double* theta)
 {
     PpcArgs a{};
     a.f = f; a.mu = mu; a.y = y; a.n = s->n; a.m = s->m; a.seed = seed; a.iter = iter; a.item0 = (uint32_t)s->item0;
     a.rowd = s->rowd; a.rowi = s->rowi; a.cold = s->cold; a.coli = s->coli;
     const dim3 grid((unsigned)s->rblocks, (unsigned)s->strips);
+    const bool bins = s->bins.on;
+    if (bins) {
+        BinState* b = &s->bins;
+        GP_ARG(theta);
+        GP_TRY(launch_bin_assign(st, b, theta));
+        a.bin = b->bin_cur; a.B = b->B; a.bpi = b->part_i; a.bpe = b->part_e; a.bpv = b->part_v; a.bbad = b->ctl + 1;
+    }
     if (s->pairs.on) {
         PairState* p = &s->pairs;
         a.rep8 = p->rep8; a.cur = p->ctl; a.plane = p->plane; a.ksteps = p->ksteps; a.bad = p->ctl + 1;
         GP_HIP(hipMemsetAsync(p->ctl + 1, 0, sizeof(int), st));
-        hipLaunchKernelGGL(ppc_replicate_kernel<true>, grid, dim3(PPC_THREADS), PPC_STAGE_BYTES, st, a);
-    } else
-        hipLaunchKernelGGL(ppc_replicate_kernel<false>, grid, dim3(PPC_THREADS), 0, st, a);
+        if (bins) hipLaunchKernelGGL((ppc_replicate_kernel<true, true>), grid, dim3(PPC_THREADS), PPC_STAGE_BYTES, st, a);
+        else hipLaunchKernelGGL((ppc_replicate_kernel<true, false>), grid, dim3(PPC_THREADS), PPC_STAGE_BYTES, st, a);
+    } else if (bins)
+        hipLaunchKernelGGL((ppc_replicate_kernel<false, true>), grid, dim3(PPC_THREADS), 0, st, a);
+    else
+        hipLaunchKernelGGL((ppc_replicate_kernel<false, false>), grid, dim3(PPC_THREADS), 0, st, a);
     GP_HIP(hipGetLastError());
     PpcUnitArgs u{};
     u.rowd = s->rowd; u.rowi = s->rowi; u.cold = s->cold; u.coli = s->coli;
@@ -333,6 +399,7 @@ int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const do
     GP_HIP(hipGetLastError());
     s->draws += 1;
     if (s->pairs.on) GP_TRY(launch_pair_accumulate(st, &s->pairs));
+    if (bins) GP_TRY(launch_bin_update(st, &s->bins));
     return 0;
 }
 

@@ -27,7 +27,6 @@ namespace gpirt {
 
 namespace {
 
-constexpr int NG = GPIRT_NGRID;
 constexpr int RK_THREADS = 256;
 constexpr int RK_BINS = 1024;            // 1001 bins, padded to 4 per lane
 constexpr int PW_ROWS = 32;              // rows of a pairwise tile
@@ -45,14 +44,6 @@ struct RankArgs {
     uint32_t* hist;                      // [n][B]
     uint16_t* kidx; uint32_t* ctl;       // the draw's indices and ctl[0] = 1 if the draw counted, for the pairwise pass
 };
-
-// the rule of quantiles.grid_index and of summary_hist_accumulate_kernel: k where theta is bit for bit -5 + 0.01 k, else -1
-__device__ __forceinline__ int grid_index(double t)
-{
-    const double k = rint((t + 5.0) * 100.0);
-    if (!(k >= 0.0 && k <= (double)(NG - 1) && -5.0 + k * 0.01 == t)) return -1;
-    return (int)k;
-}
 
 __global__ __launch_bounds__(RK_THREADS) void rank_accumulate_kernel(RankArgs a)
 {

@@ -1529,7 +1529,7 @@ int gpirt_sampler_ppc_accumulate(gpirt_sampler_t s)
     GP_ARG(s && s->initialised);
     GP_TRY(ppc_needs_on(s));
     GP_TRY(beta_sync(s));                     // draw_beta (mu) may still be deferred to the sampler's own stream
-    return launch_ppc_accumulate(s->h->stream, &s->ppc, s->f, s->mu, s->y, s->opt.seed, (uint32_t)s->iter);
+    return launch_ppc_accumulate(s->h->stream, &s->ppc, s->f, s->mu, s->y, s->opt.seed, (uint32_t)s->iter, s->theta);
 }
 
 int gpirt_sampler_ppc_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count)
@@ -1611,6 +1611,48 @@ int gpirt_sampler_ppc_pairs_state(gpirt_sampler_t s, void** d_state, int64_t* by
 int gpirt_ppc_pairs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out)
 {
     return pair_combine(h, chains, d_states, out);
+}
+
+// ---- theta-binned item fit (ppc_bins.hip): an add-on to the PPC state ------------------------------------------------------
+static int bins_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.bins.on) return 0;
+    set_error("the theta-binned item fit is not enabled (gpirt_sampler_ppc_bins_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_ppc_bins_enable(gpirt_sampler_t s, int h, const int* cuts, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    bin_free(&s->ppc.bins);
+    if (!on) return 0;
+    GP_TRY(ppc_needs_on(s));
+    const int rc = bin_alloc(s->h->stream, &s->ppc.bins, s->n, s->m, s->opt.item0, s->ppc.rblocks, h, cuts);
+    if (rc) bin_free(&s->ppc.bins);
+    return rc;
+}
+
+int gpirt_sampler_ppc_bins_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(bins_needs_on(s));
+    return bin_get(s->h->stream, &s->ppc.bins, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_bins_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(bins_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.bins.block;
+    *bytes = bin_state_words(s->m, s->ppc.bins.B) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_bins_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out)
+{
+    return bin_combine(h, chains, d_states, signs, out);
 }
 
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
@@ -2004,6 +2046,7 @@ struct ChainRun {
     int64_t n_new;
     bool predict;                     // gpirt_mcmc_predict: the score state also predicts the unseen answers (it travels inside keep_score)
     bool pairs;                       // gpirt_mcmc_pairs: the PPC state also checks the item pairs (it travels inside keep_ppc)
+    const gpirt_ppc_bins* bins;       // gpirt_mcmc_bins: ... and the theta-binned item fit with these cuts (inside keep_ppc too)
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2091,6 +2134,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     const bool ppc = cr && cr->keep_ppc;
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
     if (!rc && ppc && cr->pairs) rc = gpirt_sampler_ppc_pairs_enable(s, 1);
+    if (!rc && ppc && cr->bins) rc = gpirt_sampler_ppc_bins_enable(s, cr->bins->h, cr->bins->cuts, 1);
     const bool ranks = cr && cr->keep_rank;
     if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
     const bool score = cr && cr->keep_score;
@@ -2200,7 +2244,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (summarise)
             GP_TRY(launch_summary_accumulate(h->stream, &s->sum, d, d + off_beta, d + off_f, d + off_mu, s->y, d + off_fstar));
         if (ppc)                                // the slot holds the state after k iterations
-            GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k));
+            GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k, d));    // (d: the slot's theta)
         if (ranks) GP_TRY(launch_rank_accumulate(h->stream, &s->rank, d));      // the slot's theta
         if (score) GP_TRY(launch_score_accumulate(h, h->stream, &s->score, d + off_fstar));   // the slot's f*
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
@@ -2340,7 +2384,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
-                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr)
+                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2410,6 +2454,16 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         }
         if (n > GPIRT_PAIRS_MAX_N) { set_error("pairwise PPC: n = %lld is beyond %d respondents", (long long)n, GPIRT_PAIRS_MAX_N); return GPIRT_E_ARG; }
     }
+    if (bins) {
+        GP_ARG(ppc);
+        GP_ARG(bins->reserved[0] == 0 && bins->reserved[1] == 0 && bins->reserved[2] == 0 && bins->reserved[3] == 0);
+        if (bins->top < 1 || bins->top > GPIRT_BINS_MAX_TOP) {
+            set_error("theta-binned PPC: top = %d is outside 1..%d", bins->top, GPIRT_BINS_MAX_TOP);
+            return GPIRT_E_ARG;
+        }
+        GP_TRY(bin_check_cuts(bins->h, bins->cuts));
+    }
+    const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
@@ -2427,7 +2481,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         sm.parts = parts | extra;
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
-                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr };
+                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
+                           bins ? &bins_in : nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2446,6 +2501,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     if (!rc && pairs) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].pairs.block;
         rc = pair_combine(h, chains, st.data(), pairs);
+    }
+    if (!rc && bins) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].bins.block;
+        rc = bin_combine(h, chains, st.data(), sg.data(), bins);
     }
     for (auto& k : keep) summary_free(&k);
     if (!rc && ranks) {
@@ -2594,6 +2653,24 @@ int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_th
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs);
+}
+
+// ---- the theta-binned item fit ---------------------------------------------------------------------------------------------------
+int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                    const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                    double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                    gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                    gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins)
+{
+    GP_ARG(opts && ppc && bins);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_bins needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins);
 }
 
 }  // extern "C"

@@ -250,6 +250,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the pairwise item checks are not offered for item shards "
                          "(a pair's table runs over two shards' replicates)")
 
+    def ppc_bins_enable(self, cuts=None, top=20, on=True):
+        raise ValueError("ShardedSampler: the theta-binned item fit is not offered for item shards "
+                         "(it is an add-on to the posterior predictive checks, which are not offered either)")
+
     # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         self.engine.rank_enable(on, pivots, pairwise)

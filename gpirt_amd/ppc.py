@@ -11,6 +11,11 @@ The pairwise item checks ("pairwise item checks" in the header; csrc/ppc_pairs.h
 `pairs_result` wrap gpirt_ppc_pairs, `pairs_combine` pools chains' state blocks, `pairs_from_rep` is the NumPy statement of
 the header over stored replicates (int64 matmuls, Python-integer cross products) and `pairs_from_draws` builds those
 replicates from stored g draws.
+The theta-binned item fit ("theta-binned item fit" in the header; csrc/ppc_bins.hip) is the second add-on: `check_cuts`,
+`bin_of_index`, `bins_struct` / `bins_result` wrap gpirt_ppc_bins, `bins_combine` pools chains' state blocks with their
+reflection signs, `bins_from_rep` is the NumPy statement of the header over stored theta, g and replicates (integers exact,
+E, V and X2 in np.longdouble, the chi-square decisions as (lo, hi) brackets from `bins_bounds`) and `bins_from_draws` builds
+the replicates from stored g draws.
 ShardedSampler is not covered: the respondents' statistics would need one all-reduce per draw.  The keying of the
 uniforms by the global item index keeps that possible.
 """
@@ -21,7 +26,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import PAIRS_COUNTS, PAIRS_FIELDS, PAIRS_SUMS, PPC_FIELDS, ST_PPC, check
+from ._lib import (BINS_BIN_FIELDS, BINS_CELL_FIELDS, BINS_ITEM_FIELDS, BINS_RAW, PAIRS_COUNTS, PAIRS_FIELDS, PAIRS_SUMS,
+                   PPC_FIELDS, ST_PPC, check)
 
 _dp = C.POINTER(C.c_double)
 INT_FIELDS = ("n_obs", "obs_yes", "yes_ge", "yes_gt", "dev_ge", "nonfinite", "rep_yes_sum", "rep_yes_sumsq", "correct_sum")
@@ -264,6 +270,327 @@ def pairs_from_draws(y, g_draws, seed, iters, top=DEFAULT_PAIRS_TOP, item0=0):
         reps.append(obs & (u < p))
     rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
     return pairs_from_rep(y, rep, top, skipped), gap
+
+
+# ------------------------------------------------------------------------------------ theta-binned item fit: device ---
+DEFAULT_CUTS = (14, 43, 76, 122)          # nine bins of equal N(0, 1) probability, snapped to the grid
+DEFAULT_BINS_TOP = 20
+_BIN_DTYPES = {"u8": np.uint64, "f8": np.float64, "u4": np.uint32}
+
+
+def check_cuts(cuts) -> tuple:
+    """The cuts as a tuple of ints (hundredths of theta): 1 <= d_1 < ... < d_h <= 499, 1 <= h <= 15.  Takes ints, or theta
+    values that round to whole hundredths within 1e-9; anything else is a ValueError."""
+    try:
+        raw = list(cuts)
+    except TypeError:
+        raise ValueError("bins: the cuts must be a sequence of integers (hundredths of theta) or theta values") from None
+    if not 1 <= len(raw) <= _lib.BINS_MAX_H:
+        raise ValueError(f"bins: 1..{_lib.BINS_MAX_H} cuts are taken, {len(raw)} given")
+    out = []
+    for c in raw:
+        if isinstance(c, (bool, np.bool_)):
+            raise ValueError("bins: a cut must be a number")
+        if isinstance(c, (int, np.integer)):
+            d = int(c)
+        elif isinstance(c, (float, np.floating)):
+            d = round(float(c) * 100.0) if np.isfinite(c) else None
+            if d is None or abs(float(c) * 100.0 - d) > 1e-9 * 100.0:
+                raise ValueError(f"bins: the cut {c!r} is not a whole hundredth of theta")
+        else:
+            raise ValueError(f"bins: the cut {c!r} is not a number")
+        if not 1 <= d <= 499:
+            raise ValueError(f"bins: the cut {c!r} is outside 0.01..4.99 (1..499 hundredths)")
+        out.append(d)
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("bins: the cuts must be strictly increasing")
+    return tuple(out)
+
+
+def check_bins_top(top) -> int:
+    t = int(top)
+    if t != top or not 1 <= t <= _lib.BINS_MAX_TOP:
+        raise ValueError(f"bins: top must be an integer in 1..{_lib.BINS_MAX_TOP}")
+    return t
+
+
+def bin_of_index(k, cuts):
+    """The header's rule: the bin of grid index k (0..1000) under the cuts d (ints): a = |k - 500|, l = #{t : a >= d_t},
+    bin = h + l if k >= 500 else h - l."""
+    k = np.asarray(k, dtype=np.int64)
+    d = np.asarray(cuts, dtype=np.int64)
+    l = (np.abs(k - 500)[..., None] >= d).sum(axis=-1)
+    return np.where(k >= 500, len(d) + l, len(d) - l)
+
+
+def bin_edges(cuts):
+    """(bin_lo, bin_hi) in theta of the B = 2h + 1 bins."""
+    d = [c / 100.0 for c in cuts] + [5.0]
+    h = len(cuts)
+    lo = [-d[h - b] for b in range(h)] + [-d[0]] + [d[l - 1] for l in range(1, h + 1)]
+    hi = [-d[h - b - 1] for b in range(h)] + [d[0]] + [d[l] for l in range(1, h + 1)]
+    return np.array(lo), np.array(hi)
+
+
+def _bins_shape(kind, m, B):
+    return {"c": (B, m), "i": (m,), "b": (B,)}[kind]
+
+
+def bins_struct(m: int, cuts=DEFAULT_CUTS, top=DEFAULT_BINS_TOP):
+    """A gpirt_ppc_bins with the cuts and host arrays for every output, and those arrays (kept alive by the caller)."""
+    cuts = check_cuts(cuts)
+    B = 2 * len(cuts) + 1
+    p = _lib.PpcBins()
+    p.top = check_bins_top(top)
+    p.h = len(cuts)
+    for q, d in enumerate(cuts):
+        p.cuts[q] = d
+    arr = {}
+    for group, names, shape in (("cell", BINS_CELL_FIELDS, (B, m)), ("item", BINS_ITEM_FIELDS, (m,)), ("bin", BINS_BIN_FIELDS, (B,))):
+        for k, name in enumerate(names):
+            arr[name] = np.empty(shape)
+            getattr(p, group)[k] = arr[name].ctypes.data_as(_dp)
+    counts = {"cell_ge": ("cell_count", 0), "cell_gt": ("cell_count", 1), "cell_empty": ("cell_count", 2),
+              "chi_ge": ("chi_count", 0), "chi_gt": ("chi_count", 1)}
+    for name, dt, kind in BINS_RAW:
+        arr[name] = np.empty(_bins_shape(kind, m, B), dtype=_BIN_DTYPES[dt])
+        ptr = arr[name].ctypes.data_as(C.POINTER({"u8": C.c_uint64, "f8": C.c_double, "u4": C.c_uint32}[dt]))
+        if name in counts:
+            getattr(p, counts[name][0])[counts[name][1]] = ptr
+        else:
+            setattr(p, name, ptr)
+    arr["worst_items"] = np.empty(p.top, dtype=np.int64)
+    p.worst_items = arr["worst_items"].ctypes.data_as(C.POINTER(C.c_int64))
+    for name in ("worst_ppp_chi2_mid", "worst_chi2_obs_mean"):
+        arr[name] = np.empty(p.top)
+        setattr(p, name, arr[name].ctypes.data_as(_dp))
+    return p, arr
+
+
+def bins_result(p, arr) -> dict:
+    """The "bins" dict of gpirtMCMC(ppc=dict(bins=True)), Sampler.ppc_bins() and bins_combine(): every array of the header by
+    name (cell (b, j) at [b, j]), "cuts", "worst" (dict: items, ppp_chi2_mid, chi2_obs_mean) and the counters."""
+    out = {k: v for k, v in arr.items() if not k.startswith("worst_")}
+    out["worst"] = dict(items=arr["worst_items"], ppp_chi2_mid=arr["worst_ppp_chi2_mid"], chi2_obs_mean=arr["worst_chi2_obs_mean"])
+    out["cuts"] = np.array([p.cuts[q] for q in range(p.h)], dtype=np.int64)
+    out.update(n=int(p.n), m=int(p.m), B=int(p.B), bin_draws=int(p.bin_draws), bin_skipped=int(p.bin_skipped))
+    return out
+
+
+def bins_state_header(state) -> dict:
+    """The header of a theta-binned state block (a device tensor): its 8 int64 words and the cuts."""
+    w = state[:24].cpu().numpy().view(np.int64)
+    B = int(w[6])
+    return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), bin_draws=int(w[3]), bin_skipped=int(w[4]), item0=int(w[5]),
+                B=B, tag=int(w[7]), cuts=tuple(int(x) for x in w[8:8 + max((B - 1) // 2, 0)]))
+
+
+def bins_combine(handle, states, signs=None, top=DEFAULT_BINS_TOP) -> dict:
+    """gpirt_ppc_bins_combine over the theta-binned state blocks `states` (device tensors, or Samplers with ppc_bins_enable()
+    on, all on handle's device): the integers added, the doubles added in chain order; a chain whose sign is -1 enters with
+    its bin axis reversed.  Blocks with another n, m, item0 or cuts are refused."""
+    lib = _lib.load()
+    tensors = [s.ppc_bins_state() if hasattr(s, "ppc_bins_state") else s for s in states]
+    hdr = bins_state_header(tensors[0])
+    if hdr["tag"] != _lib.BINS_TAG:
+        raise ValueError("bins_combine: the first state is not a theta-binned PPC state block")
+    p, arr = bins_struct(hdr["m"], hdr["cuts"], top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    sg = None
+    if signs is not None:
+        if len(signs) != nc:
+            raise ValueError("bins_combine: one sign per state")
+        sg = (C.c_int * nc)(*[int(x) for x in signs])
+    check(lib.gpirt_ppc_bins_combine(handle.ptr, nc, ptrs, sg, C.byref(p)))
+    return bins_result(p, arr)
+
+
+# ------------------------------------------------------------------------------------- theta-binned item fit: NumPy ---
+_EPS = float(np.finfo(np.float64).eps)
+# relative gaps between any two fp64 evaluations of the header's arithmetic (exp within 1 ulp, 1 + e and the division
+# rounded once each: p and q within 4 eps of the true value, so two evaluations within 8 eps; p q within 2 * 9 + 2 eps)
+BINS_P_GAP = 8.0 * _EPS
+BINS_PQ_GAP = 20.0 * _EPS
+
+
+def bins_bounds(N, E, V, Cs=()):
+    """Bounds on how far an fp64 evaluation of a bin's E = sum p, V = sum p q (N terms, any fixed order: at most N eps of the
+    sum of the positive terms) and of (C - E) / sqrt(V), (C - E)^2 / V for the counts C in Cs may lie from the values
+    given: (dE, dV, [dz_C ...], [dterm_C ...]).  Derived from the precision of the format alone; first order terms with 1 %
+    on top for the higher ones."""
+    N = np.asarray(N, dtype=np.float64)
+    E = np.asarray(E, dtype=np.float64)
+    V = np.asarray(V, dtype=np.float64)
+    dE = (BINS_P_GAP + N * _EPS) * E
+    aV = BINS_PQ_GAP + N * _EPS
+    dV = aV * V
+    dz, dt = [], []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for Cc in Cs:
+            d = np.abs(np.asarray(Cc, dtype=np.float64) - E)
+            dd = dE + _EPS * d
+            ok = V > 0
+            z = np.where(ok, d / np.sqrt(np.where(ok, V, 1.0)), 0.0)
+            term = z * z
+            dz.append(np.where(ok, 1.01 * (dd / np.sqrt(np.where(ok, V, 1.0)) + z * (0.5 * aV + 2.0 * _EPS)), 0.0))
+            dt.append(np.where(ok, 1.01 * ((2.0 * d * dd + dd * dd) / np.where(ok, V, 1.0) + term * (aV + 4.0 * _EPS)), 0.0))
+    return dE, dV, dz, dt
+
+
+def bins_from_rep(y, theta_draws, g_draws, rep_draws, cuts=DEFAULT_CUTS, top=DEFAULT_BINS_TOP, signs=None) -> dict:
+    """The header's theta-binned item fit from stored draws: y (n x m; NaN = missing), theta_draws (S, n), g_draws (S, n, m)
+    the draws of g = f + mu, rep_draws (S, n, m) with rep != 0 where yrep = +1 (cells where y is missing are masked out
+    here).  signs: None, or one of +1 / -1 per draw (its chain's reflection sign): a draw with -1 enters with its bin axis
+    reversed, as gpirt_ppc_bins_combine pools it.  A draw with a theta off the grid or a non-finite g in an observed cell is
+    skipped.  Returns bins_result's dict with the integers exact and E, V, z and X2 summed in np.longdouble, and
+      chi_ge, chi_gt     (lo, hi) brackets: an (item, draw) whose |X2(R) - X2(T)| is at most the sum of the two bounds of
+                         bins_bounds is undecided (an integer tie R_b = T_b in every bin is decided: ge, not gt);
+      "undecided", "decisions"   those cases and all (item, counted draw) cases;
+      "bounds"           dict of the accumulated bounds of sum_e, sum_z, chi_obs_sum, chi_rep_sum;
+      "last"             dict(bin, tN, tT, tR, tE, tV, dE, dV) of the last counted draw (None without one)."""
+    cuts = check_cuts(cuts)
+    top = check_bins_top(top)
+    from .quantiles import grid_index
+    y = np.asarray(y, dtype=np.float64)
+    n, m = y.shape
+    theta_draws = np.asarray(theta_draws, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    rep_draws = np.asarray(rep_draws)
+    S = theta_draws.shape[0]
+    assert theta_draws.shape == (S, n) and g_draws.shape == (S, n, m) and rep_draws.shape == (S, n, m)
+    sg = np.ones(S, dtype=np.int64) if signs is None else np.broadcast_to(np.asarray(signs, dtype=np.int64), (S,))
+    assert np.isin(sg, (1, -1)).all()
+    h, B = len(cuts), 2 * len(cuts) + 1
+    obs = ~np.isnan(y)
+    yes = obs & (y > 0)
+    ld = np.longdouble
+    zi = lambda *sh: np.zeros(sh, dtype=np.int64)        # noqa: E731
+    acc = dict(sum_n=zi(B, m), sum_t=zi(B, m), sum_r=zi(B, m), cell_ge=zi(B, m), cell_gt=zi(B, m), cell_empty=zi(B, m),
+               occ_sum=zi(B), sum_e=np.zeros((B, m), dtype=ld), sum_z=np.zeros((B, m), dtype=ld),
+               chi_obs_sum=np.zeros(m, dtype=ld), chi_rep_sum=np.zeros(m, dtype=ld))
+    bnd = dict(sum_e=np.zeros((B, m)), sum_z=np.zeros((B, m)), chi_obs_sum=np.zeros(m), chi_rep_sum=np.zeros(m))
+    absz = np.zeros((B, m))
+    chi = dict(ge_lo=zi(m), ge_hi=zi(m), gt_lo=zi(m), gt_hi=zi(m))
+    draws = skipped = undecided = 0
+    last = None
+    for s in range(S):
+        k = grid_index(theta_draws[s])
+        g = g_draws[s]
+        if (k < 0).any() or not np.isfinite(g[obs]).all():
+            skipped += 1
+            continue
+        draws += 1
+        bins = bin_of_index(k, cuts)
+        onehot = (bins[None, :] == np.arange(B)[:, None])            # B x n
+        oh = onehot.astype(np.int64)
+        rep = obs & (rep_draws[s] != 0)
+        Nn, T, R = oh @ obs.astype(np.int64), oh @ yes.astype(np.int64), oh @ rep.astype(np.int64)
+        gz = np.where(obs, g, 0.0)
+        p, e = _plogis(gz)
+        q = np.where(gz >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+        pl, vl = np.where(obs, p, 0.0).astype(ld), np.where(obs, p * q, 0.0).astype(ld)
+        E = np.stack([pl[onehot[b]].sum(axis=0) for b in range(B)])
+        V = np.stack([vl[onehot[b]].sum(axis=0) for b in range(B)])
+        Ed, Vd = E.astype(np.float64), V.astype(np.float64)
+        dE, dV, (dzT, _), (dtT, dtR) = bins_bounds(Nn, Ed, Vd, (T, R))
+        live = Nn > 0
+        pos = live & (V > 0)
+        Vs = np.where(pos, V, ld(1))
+        z = np.where(pos, (T - E) / np.sqrt(Vs), ld(0))
+        tT = np.where(pos, (T - E) ** 2 / Vs, ld(0))
+        tR = np.where(pos, (R - E) ** 2 / Vs, ld(0))
+        x2T, x2R = tT.sum(axis=0), tR.sum(axis=0)
+        bT = np.where(pos, dtT, 0.0).sum(axis=0) + B * _EPS * x2T.astype(np.float64)
+        bR = np.where(pos, dtR, 0.0).sum(axis=0) + B * _EPS * x2R.astype(np.float64)
+        tie = (np.where(live, R, 0) == np.where(live, T, 0)).all(axis=0)
+        gap = (x2R - x2T).astype(np.float64)
+        open_ = ~tie & (np.abs(gap) <= bT + bR)
+        undecided += int(open_.sum())
+        chi["ge_lo"] += tie | (~open_ & (gap >= 0)); chi["ge_hi"] += tie | open_ | (gap >= 0)
+        chi["gt_lo"] += ~tie & ~open_ & (gap > 0); chi["gt_hi"] += ~tie & (open_ | (gap > 0))
+        flip = (lambda a: a[::-1]) if sg[s] < 0 else (lambda a: a)
+        acc["sum_n"] += flip(Nn); acc["sum_t"] += flip(np.where(live, T, 0)); acc["sum_r"] += flip(np.where(live, R, 0))
+        acc["cell_ge"] += flip(live & (R >= T)); acc["cell_gt"] += flip(live & (R > T)); acc["cell_empty"] += flip(~live)
+        acc["occ_sum"] += flip(oh.sum(axis=1))
+        acc["sum_e"] += flip(np.where(live, E, ld(0))); acc["sum_z"] += flip(z)
+        acc["chi_obs_sum"] += x2T; acc["chi_rep_sum"] += x2R
+        bnd["sum_e"] += flip(np.where(live, dE, 0.0)); bnd["sum_z"] += flip(np.where(pos, dzT, 0.0))
+        absz += flip(np.abs(z).astype(np.float64))
+        bnd["chi_obs_sum"] += bT; bnd["chi_rep_sum"] += bR
+        last = dict(bin=bins.astype(np.uint8), tN=Nn.astype(np.int32), tT=T.astype(np.int32), tR=R.astype(np.int32), tE=Ed, tV=Vd,
+                    dE=dE, dV=dV)
+    # the accumulation over the draws (and, pooled, over the chains): one rounding per addition
+    f64 = {k: acc[k].astype(np.float64) for k in ("sum_e", "sum_z", "chi_obs_sum", "chi_rep_sum")}
+    bnd["sum_e"] += (draws + 1) * _EPS * f64["sum_e"]
+    bnd["sum_z"] += (draws + 1) * _EPS * absz
+    bnd["chi_obs_sum"] += (draws + 1) * _EPS * f64["chi_obs_sum"]
+    bnd["chi_rep_sum"] += (draws + 1) * _EPS * f64["chi_rep_sum"]
+    out = dict(sum_n=acc["sum_n"].astype(np.uint64), sum_t=acc["sum_t"].astype(np.uint64), sum_r=acc["sum_r"].astype(np.uint64),
+               cell_ge=acc["cell_ge"].astype(np.uint32), cell_gt=acc["cell_gt"].astype(np.uint32),
+               cell_empty=acc["cell_empty"].astype(np.uint32), occ_sum=acc["occ_sum"].astype(np.uint64), **f64)
+    out["chi_ge"] = (chi["ge_lo"], chi["ge_hi"])
+    out["chi_gt"] = (chi["gt_lo"], chi["gt_hi"])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sN = np.where(acc["sum_n"] > 0, acc["sum_n"], np.nan).astype(np.float64)
+        Sc = draws - acc["cell_empty"]
+        Sc = np.where(Sc > 0, Sc, np.nan).astype(np.float64)
+        Sd = float(draws) if draws > 0 else np.nan
+        out["obs_rate"] = acc["sum_t"] / sN
+        out["rep_rate"] = acc["sum_r"] / sN
+        out["exp_rate"] = f64["sum_e"] / sN
+        out["z_mean"] = f64["sum_z"] / Sc
+        out["ppp_cell"] = acc["cell_ge"] / Sc
+        out["ppp_cell_mid"] = (acc["cell_ge"] + acc["cell_gt"]) / (2.0 * Sc)
+        out["n_mean"] = acc["sum_n"] / Sd
+        # the finished chi-square fields from the brackets' lower ends (equal to the upper ones unless "undecided" > 0)
+        out["ppp_chi2"] = chi["ge_lo"] / Sd
+        out["ppp_chi2_mid"] = (chi["ge_lo"] + chi["gt_lo"]) / (2.0 * Sd)
+        out["chi2_obs_mean"] = f64["chi_obs_sum"] / Sd
+        out["chi2_rep_mean"] = f64["chi_rep_sum"] / Sd
+        out["occupancy"] = acc["occ_sum"] / Sd
+    out["bin_lo"], out["bin_hi"] = bin_edges(cuts)
+    out["cuts"] = np.array(cuts, dtype=np.int64)
+    out["worst"] = bins_worst(out["ppp_chi2_mid"], out["chi2_obs_mean"], top)
+    out.update(n=n, m=m, B=B, bin_draws=draws, bin_skipped=skipped, undecided=undecided, decisions=draws * m, bounds=bnd, last=last)
+    return out
+
+
+def bins_worst(ppp_chi2_mid, chi2_obs_mean, top=DEFAULT_BINS_TOP) -> dict:
+    """The `top` items by increasing ppp_chi2_mid, ties to the lowest j, NaN never listed; padded with -1 / NaN."""
+    top = check_bins_top(top)
+    mid = np.asarray(ppp_chi2_mid, dtype=np.float64)
+    js = np.flatnonzero(~np.isnan(mid))
+    order = js[np.argsort(mid[js], kind="stable")][:top]
+    w = dict(items=np.full(top, -1, dtype=np.int64), ppp_chi2_mid=np.full(top, np.nan), chi2_obs_mean=np.full(top, np.nan))
+    w["items"][:len(order)] = order
+    w["ppp_chi2_mid"][:len(order)] = mid[order]
+    w["chi2_obs_mean"][:len(order)] = np.asarray(chi2_obs_mean, dtype=np.float64)[order]
+    return w
+
+
+def bins_from_draws(y, theta_draws, g_draws, seed, iters, cuts=DEFAULT_CUTS, top=DEFAULT_BINS_TOP, item0=0, signs=None):
+    """bins_from_rep over the replicates of stored draws, built as pairs_from_draws builds them: rep = [u < plogis(g)] with
+    replicate_uniforms' u at the completed-iteration counters `iters`.  Returns (result, min |u - p| over the observed cells
+    of the draws with finite g): a cell that close to its uniform may replicate either way under another evaluation of
+    plogis."""
+    y = np.asarray(y, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    n, m = y.shape
+    obs = ~np.isnan(y)
+    reps, gap = [], np.inf
+    for s, it in enumerate(iters):
+        g = g_draws[s]
+        if not np.isfinite(g[obs]).all():
+            reps.append(np.zeros((n, m), dtype=bool))    # (bins_from_rep skips the draw)
+            continue
+        p, _ = _plogis(np.where(obs, g, 0.0))
+        u = replicate_uniforms(seed, int(it), n, m, item0)
+        if obs.any():
+            gap = min(gap, float(np.abs(u - p)[obs].min()))
+        reps.append(obs & (u < p))
+    rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
+    return bins_from_rep(y, theta_draws, g_draws, rep, cuts, top, signs), gap
 
 
 # ------------------------------------------------------------------------------------------------------- NumPy -------

@@ -92,6 +92,15 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       dependence the one-dimensional model does not reproduce; pair_draws, pair_skipped (a draw with a non-finite g in an
       observed cell is skipped whole for the pairs) and the raw sums and counts.  Memory: 68 bytes per ordered pair on the
       device (71 MB at m = 1024) plus the int8 operands; n <= 65534.  ppc=True is exactly as without it.
+      ppc=dict(bins=True, bins_top=20) (or bins=(d_1, ..., d_h), the positive cut points as hundredths of theta or theta
+      values; True = gpirt_amd.ppc.DEFAULT_CUTS, nine bins of equal N(0, 1) probability) also checks every item's
+      response curve along theta (gpirt_mcmc_bins): each draw groups the respondents by the bin of their theta, and "ppc"
+      gains "bins" with, per (bin, item) as B x m arrays, obs_rate (the empirical IRF), rep_rate, exp_rate, z_mean,
+      ppp_cell, ppp_cell_mid and n_mean; per item ppp_chi2, ppp_chi2_mid, chi2_obs_mean and chi2_rep_mean (the binned
+      chi-square of the data against the replicates'); per bin occupancy, bin_lo, bin_hi; "worst" lists the `bins_top`
+      (1..64) items with the smallest ppp_chi2_mid -- the items whose curve the data contradict; bin_draws, bin_skipped (a
+      draw with a theta off the grid or a non-finite g in an observed cell is skipped whole) and the raw sums and counts.
+      pairs and bins may be asked for together.
     ranks: True, or dict(pivots="median", pairwise=False, probs=(0.025, 0.5, 0.975)), adds the rank posteriors
       (gpirt_mcmc_ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
       the smallest; ties take the mid-rank) and accumulates, in "ranks": rank_mean, rank_var, rank_quantiles
@@ -161,21 +170,28 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         else:
             score = dict(data=score, probs=SC.DEFAULT_PROBS, predict=False, top=SC.DEFAULT_TOP)
         score["data"] = np.asfortranarray(SC.check_y_new(score["data"], y.shape[1]))
-    pairs = None
+    pairs = bins = None
     if isinstance(ppc, dict):
         from . import ppc as P
-        unknown = set(ppc) - {"pairs", "top"}
+        unknown = set(ppc) - {"pairs", "top", "bins", "bins_top"}
         if unknown:
-            raise ValueError(f"ppc: a dict may give pairs and top (unknown keys {sorted(unknown)})")
+            raise ValueError(f"ppc: a dict may give pairs, top, bins and bins_top (unknown keys {sorted(unknown)})")
         if "top" in ppc and not ppc.get("pairs"):
             raise ValueError("ppc: top needs pairs=True")
         if ppc.get("pairs"):
             pairs = dict(top=P.check_pairs_top(ppc.get("top", P.DEFAULT_PAIRS_TOP)))
+        want_bins = ppc.get("bins")
+        want_bins = want_bins is not None and want_bins is not False
+        if "bins_top" in ppc and not want_bins:
+            raise ValueError("ppc: bins_top needs bins=True or bins=cuts")
+        if want_bins:
+            bins = dict(cuts=P.check_cuts(P.DEFAULT_CUTS if ppc["bins"] is True else ppc["bins"]),
+                        top=P.check_bins_top(ppc.get("bins_top", P.DEFAULT_BINS_TOP)))
         ppc = True
     if quantiles is not None or ppc or ranks is not None or score is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -309,13 +325,15 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None):
+                    score=None, pairs=None, bins=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
     same chains with the rank posteriors (with or without the checks).  score (dict(data, probs)): gpirt_mcmc_score, the
     same chains scoring the new respondents `data` (with or without the checks and the ranks).  pairs (dict(top)):
-    gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else)."""
+    gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else).  bins
+    (dict(cuts, top)): gpirt_mcmc_bins, the same chains with the theta-binned item fit inside the PPC (with or without the
+    pairs and everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -378,22 +396,29 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if pairs is not None:
-        pq, pqarr = P.pairs_struct(m, pairs["top"])
+    if pairs is not None or bins is not None:
+        pq = bq = None
+        if pairs is not None:
+            pq, pqarr = P.pairs_struct(m, pairs["top"])
+        if bins is not None:
+            bq, bqarr = P.bins_struct(m, bins["cuts"], bins["top"])
         sc = pr = None
         if score is not None:
             from . import score as SC
             sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
             if score.get("predict"):
                 pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
-        rc = lib.gpirt_mcmc_pairs(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp),
-                                  C.byref(rk) if ranks is not None else None,
-                                  _ptr(score["data"]) if score is not None else None,
-                                  score["data"].shape[0] if score is not None else 0,
-                                  C.byref(sc) if sc is not None else None, C.byref(pr) if pr is not None else None,
-                                  C.byref(pq))
+        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp),
+                C.byref(rk) if ranks is not None else None,
+                _ptr(score["data"]) if score is not None else None,
+                score["data"].shape[0] if score is not None else 0,
+                C.byref(sc) if sc is not None else None, C.byref(pr) if pr is not None else None)
+        if bq is not None:
+            rc = lib.gpirt_mcmc_bins(*args, C.byref(pq) if pq is not None else None, C.byref(bq))
+        else:
+            rc = lib.gpirt_mcmc_pairs(*args, C.byref(pq))
     elif score is not None:
         from . import score as SC
         sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
@@ -439,6 +464,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["ppc"] = P.result(pp, parr)
         if pairs is not None:
             out["ppc"]["pairs"] = P.pairs_result(pq, pqarr)
+        if bins is not None:
+            out["ppc"]["bins"] = P.bins_result(bq, bqarr)
     if ranks is not None:
         out["ranks"] = RK.result(rk, rkarr)
     if score is not None:
@@ -810,6 +837,71 @@ class Sampler:
         gpirt_ppc_pairs_combine over its own state; top defaults to ppc_pairs_enable's."""
         from . import ppc as P
         return P.pairs_combine(self.handle, [self], top=getattr(self, "_pairs_top", P.DEFAULT_PAIRS_TOP) if top is None else top)
+
+    # -- theta-binned item fit inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_bins_*, gpirt_amd.ppc)
+    def ppc_bins_enable(self, cuts=None, top=20, on=True):
+        """Allocate and zero the theta-binned accumulators on a sampler whose ppc_enable is on: from then on every
+        ppc_accumulate also groups the respondents by the bin of that draw's theta and adds the replicate's and the data's yes
+        counts, E and V per (bin, item).  cuts: the positive cut points (hundredths of theta, or theta values; default
+        gpirt_amd.ppc.DEFAULT_CUTS); top (1..64): how many items ppc_bins() lists as worst.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_bins_enable(self._s, 0, None, 0))
+            self._bins_cuts = ()
+            return
+        from . import ppc as P
+        cuts = P.check_cuts(P.DEFAULT_CUTS if cuts is None else cuts)
+        self._bins_top = P.check_bins_top(top)
+        check(self.lib.gpirt_sampler_ppc_bins_enable(self._s, len(cuts), (C.c_int * len(cuts))(*cuts), 1))
+        self._bins_cuts = cuts
+
+    def ppc_bins_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.BINS_CELL_FIELDS: float64 B x m; BINS_ITEM_FIELDS: m; BINS_BIN_FIELDS: B),
+        a raw array of _lib.BINS_RAW, cuts (int64), counts (int64: bin_draws, bin_skipped) and, of the last counted draw, bin
+        (uint8, n), tN, tT, tR (int32, B x m) and tE, tV (float64, B x m).  Cell (b, j) is at [b, j]."""
+        from . import ppc as P
+        m, B = self.m, 2 * len(getattr(self, "_bins_cuts", ())) + 1      # (not enabled: the library refuses the call)
+        raw = {r[0]: r for r in _lib.BINS_RAW}
+        if name == "counts":
+            out = np.empty(2, dtype=np.int64)
+        elif name == "cuts":
+            out = np.empty(max((B - 1) // 2, 1), dtype=np.int64)
+        elif name == "bin":
+            out = np.empty(self.n, dtype=np.uint8)
+        elif name in ("tN", "tT", "tR"):
+            out = np.empty((B, m), dtype=np.int32)
+        elif name.lower() in raw:
+            _, dt, kind = raw[name.lower()]
+            out = np.empty(P._bins_shape(kind, m, B), dtype=P._BIN_DTYPES[dt])
+        elif name in _lib.BINS_ITEM_FIELDS:
+            out = np.empty(m)
+        elif name in _lib.BINS_BIN_FIELDS:
+            out = np.empty(B)
+        else:
+            out = np.empty((B, m))
+        check(self.lib.gpirt_sampler_ppc_bins_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def ppc_bins_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the theta-binned accumulators: what
+        gpirt_amd.ppc.bins_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_bins_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_bins(self, top=None, sign=1) -> dict:
+        """Every finished output of this sampler's theta-binned accumulators (gpirt_amd.ppc.bins_result's shape):
+        gpirt_ppc_bins_combine over its own state; top defaults to ppc_bins_enable's, sign = -1 reverses the bin axis."""
+        from . import ppc as P
+        return P.bins_combine(self.handle, [self], signs=[sign],
+                              top=getattr(self, "_bins_top", P.DEFAULT_BINS_TOP) if top is None else top)
 
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):

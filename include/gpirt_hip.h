@@ -939,6 +939,126 @@ int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_th
                      const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
                      gpirt_ppc_pairs* pairs);
 
+/* ------------------------------------------------------------- theta-binned item fit: empirical IRFs and chi-square per item -- */
+/* Does an item's response function have the right SHAPE along theta (library version 112)?  An item's yes count is reproduced by
+ * almost any model with an intercept; whether the curve is right in the tails shows only when the respondents are grouped by
+ * where a draw puts them on the theta axis and, group by group, the yes answers are compared with what the model expects there
+ * (Yen's Q1 / Orlando and Thissen's S-X2 as posterior predictive discrepancies, Sinharay 2006).  An add-on to the PPC as the
+ * pairs are: enabled on a sampler whose ppc_enable is on, accumulated inside the same ppc_accumulate call from the same
+ * replicate; O, Y and rep as in the pairs section, p the PPC's p = plogis(g), q = plogis(-g) by the same arithmetic with the
+ * branches swapped (e = exp(-|g|); g >= 0: p = 1 / (1 + e), q = e / (1 + e); else p = e / (1 + e), q = 1 / (1 + e)).
+ * Cuts and bins.  The cuts are h integers 1 <= d_1 < ... < d_h <= 499, 1 <= h <= GPIRT_BINS_MAX_H = 15: hundredths of theta,
+ * the positive cut points.  They give B = 2h + 1 <= 31 bins.  A respondent whose theta is the grid point k (bit for bit
+ * -5 + 0.01 k, the rule of the rank posteriors and the theta histograms) has a = |k - 500|, l = #{t : a >= d_t} and
+ *   bin = h + l if k >= 500, else h - l.
+ * Bin h is the centre bin |theta| < d_1 / 100; theta -> -theta maps bin b to B - 1 - b exactly.  The Python default is
+ * (14, 43, 76, 122): nine bins of equal N(0, 1) probability, snapped to the grid.
+ * Per draw and (bin b, item j), over the cells i in b with y_ij observed: the exact integers N = #cells, T = #{y = +1},
+ * R = #{rep = 1} and, in fp64, E = sum p_ij, V = sum p_ij q_ij; n_b = #{i in b}.
+ * Per COUNTED draw:
+ *   cell (b, j) with N > 0:  cell_ge / cell_gt += [R >= / > T] (uint32); sum_N, sum_T, sum_R += N, T, R (uint64); sum_E += E;
+ *                            sum_z += (T - E) / sqrt(V), added only where V > 0 (double);
+ *                with N = 0: cell_empty += 1 (uint32) and nothing else;
+ *   item j:  X2(C) = sum_b ((double)C_b - E_b)^2 / V_b over the bins with N_b > 0 and V_b > 0, summed in increasing b.
+ *            If R_b = T_b in every bin -- decided on the integers, before any floating point -- the draw counts in chi_ge and
+ *            not in chi_gt; otherwise chi_ge / chi_gt += [X2(R) >= / > X2(T)] (uint32).  chi_obs_sum += X2(T),
+ *            chi_rep_sum += X2(R) (double), in every counted draw;
+ *   bin b:   occ_sum[b] += n_b (uint64).
+ * A draw is skipped whole for the bins when any theta is off the grid (NaN included) or g is non-finite in any observed cell:
+ * bin_skipped += 1 and nothing else changes; any other draw adds 1 to bin_draws.  The PPC's and the pairs' own rules are
+ * untouched.
+ * Finished on the host with S = bin_draws, B x m arrays with cell (b, j) at [b m + j] (GPIRT_BINS_CELL_*):
+ *   obs_rate = sum_T / sum_N (the empirical IRF), rep_rate = sum_R / sum_N, exp_rate = sum_E / sum_N,
+ *   z_mean = sum_z / (S - cell_empty), ppp_cell = cell_ge / (S - cell_empty), ppp_cell_mid = (cell_ge + cell_gt) / 2 (S - cell_empty),
+ *   n_mean = sum_N / S;
+ * per item (GPIRT_BINS_ITEM_*): ppp_chi2 = chi_ge / S, ppp_chi2_mid = (chi_ge + chi_gt) / 2S, chi2_obs_mean = chi_obs_sum / S,
+ * chi2_rep_mean = chi_rep_sum / S; per bin (GPIRT_BINS_BIN_*): occupancy = occ_sum / S and the bin's edges in theta bin_lo,
+ * bin_hi (bin h + l, l >= 1: [d_l, d_(l+1)) / 100 with the last one closed at 5; bin h - l its mirror image; the centre bin
+ * (-d_1, d_1) / 100).  Everything is NaN where its denominator is 0.
+ *   worst: the `top` (1..GPIRT_BINS_MAX_TOP, the Python default is 20) items by increasing ppp_chi2_mid, ties to the lowest j,
+ *   NaN never listed: their indices, ppp_chi2_mid and chi2_obs_mean, padded with -1 / NaN.
+ * Determinism: no floating-point atomics; every double is reduced in a fixed order (the 64 rows of a wave in row order, the four
+ * waves of a 256-row block in order, the row blocks in order, the bins in increasing b), so two runs give a bit-identical state
+ * block.  The only atomics are integer LDS (vector) atomics that count n_b.
+ * Pooling C chains (gpirt_ppc_bins_combine) adds the integers and adds the doubles in chain order; a chain with sign -1 enters
+ * with its bin axis reversed (cell (b, j) as (B - 1 - b, j), occ_sum too), which is exact by the symmetry above.  signs = NULL:
+ * all +1.  Blocks with another n, m, item0 or cuts are refused.
+ * Nothing is drawn: with the bins on, the chain, the IRFs, R's stream position, the PPC state block and the pairs state block are
+ * bit for bit what they are without.  Item shards stay refused, as for ppc_enable.
+ * Device memory per state: 52 B m bytes of accumulators, 28 B m of the last draw's tables and 20 B m per block of 256
+ * respondents of per-draw partial tables (at 8192 x 1024: 0.7 MB + 5.9 MB for B = 9, 2.5 MB + 20 MB for B = 31). */
+#define GPIRT_BINS_MAX_H     15
+#define GPIRT_BINS_MAX_B     31
+#define GPIRT_BINS_MAX_TOP   64
+#define GPIRT_BINS_CELL_OBS_RATE       0
+#define GPIRT_BINS_CELL_REP_RATE       1
+#define GPIRT_BINS_CELL_EXP_RATE       2
+#define GPIRT_BINS_CELL_Z_MEAN         3
+#define GPIRT_BINS_CELL_PPP_CELL       4
+#define GPIRT_BINS_CELL_PPP_CELL_MID   5
+#define GPIRT_BINS_CELL_N_MEAN         6
+#define GPIRT_BINS_CELL_NFIELDS        7
+#define GPIRT_BINS_ITEM_PPP_CHI2       0
+#define GPIRT_BINS_ITEM_PPP_CHI2_MID   1
+#define GPIRT_BINS_ITEM_CHI2_OBS_MEAN  2
+#define GPIRT_BINS_ITEM_CHI2_REP_MEAN  3
+#define GPIRT_BINS_ITEM_NFIELDS        4
+#define GPIRT_BINS_BIN_OCCUPANCY       0
+#define GPIRT_BINS_BIN_LO              1
+#define GPIRT_BINS_BIN_HI              2
+#define GPIRT_BINS_BIN_NFIELDS         3
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_ppc_bins {
+    int        top;                            /* in: 1..GPIRT_BINS_MAX_TOP */
+    int        h;                              /* in (gpirt_mcmc_bins): the number of cuts; out: the states' */
+    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_bins) / out: d_1 .. d_h, the rest 0 */
+    double*    cell[GPIRT_BINS_CELL_NFIELDS];  /* B x m each */
+    double*    item[GPIRT_BINS_ITEM_NFIELDS];  /* m each */
+    double*    bin[GPIRT_BINS_BIN_NFIELDS];    /* B each */
+    uint64_t*  sum_n;                          /* B x m */
+    uint64_t*  sum_t;
+    uint64_t*  sum_r;
+    double*    sum_e;
+    double*    sum_z;
+    uint32_t*  cell_count[3];                  /* B x m each: cell_ge, cell_gt, cell_empty */
+    uint32_t*  chi_count[2];                   /* m each: chi_ge, chi_gt */
+    double*    chi_obs_sum;                    /* m */
+    double*    chi_rep_sum;
+    uint64_t*  occ_sum;                        /* B */
+    int64_t*   worst_items;                    /* top */
+    double*    worst_ppp_chi2_mid;             /* top */
+    double*    worst_chi2_obs_mean;            /* top */
+    int64_t    n, m, B;                        /* out */
+    int64_t    bin_draws, bin_skipped;         /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_ppc_bins;
+/* Stage API.  ppc_bins_enable(h, cuts, on != 0) allocates and zeroes the state on a sampler with ppc_enable on (GPIRT_E_ARG
+ * without, and for cuts that break the rule above; on = 0 frees it, cuts may then be NULL; ppc_enable called again frees it too).
+ * From then on every ppc_accumulate also adds the draw to the bins.  ppc_bins_get copies one array by name to the host, `bytes`
+ * its exact size: every finished array by the lower-case name above (double; B x m, m or B), "cuts" (int64, h), the raw
+ * "sum_n", "sum_t", "sum_r", "occ_sum" (uint64), "sum_e", "sum_z", "chi_obs_sum", "chi_rep_sum" (double), "cell_ge", "cell_gt",
+ * "cell_empty", "chi_ge", "chi_gt" (uint32), "counts" (int64: bin_draws, bin_skipped) and, of the last COUNTED draw, "bin"
+ * (uint8, n), "tN", "tT", "tR" (int32, B x m) and "tE", "tV" (double, B x m).
+ * ppc_bins_state returns the ONE device block, apart from the PPC's and the pairs': a header of 8 int64 -- n, m, layout version
+ * (1), bin_draws, bin_skipped, item0, B, the tag 0x534E4942 ("BINS") --, then 16 int64 that hold the cuts d_1 .. d_h (the rest
+ * 0), then uint64 sum_n, sum_t, sum_r, double sum_e, sum_z, uint32 cell_ge, cell_gt, cell_empty (B x m each), uint32 chi_ge,
+ * chi_gt, double chi_obs_sum, chi_rep_sum (m each) and uint64 occ_sum (B); every array starts on a 16-byte boundary. */
+int gpirt_sampler_ppc_bins_enable(gpirt_sampler_t s, int h, const int* cuts, int on);
+int gpirt_sampler_ppc_bins_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_bins_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_bins_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out);
+/* gpirt_mcmc_pairs with the theta-binned item fit (ppc and bins are required, bins->h and bins->cuts given; pairs may be NULL):
+ * every chain also accumulates the bins inside its ppc_accumulate -- under the item RNG from the verified checkpoint, as the
+ * pairs do --, pooled into bins with the reflection signs that the chains' alignment decides. */
+int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                    int sample_iterations, int burn_iterations, const double* h_prior_means,
+                    const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                    double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                    gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                    const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                    gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
