@@ -200,6 +200,21 @@ class ScorePredict(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+# IRF shape posteriors (include/gpirt_hip.h GPIRT_SHAPE_*): the raw arrays of a state block in order, with their dtypes
+SHAPE_MAX_TOLS, SHAPE_MAX_TOP, SHAPE_TAG = 4, 64, 0x50414853
+SHAPE_RAW = (("cls", "u4"), ("peak_hist", "u4"), ("valley_hist", "u4"), ("cross_first_hist", "u4"), ("cross_last_hist", "u4"),
+             ("cross_count", "u4"), ("draws", "u4"), ("nonfinite", "u4"), ("slope", "f8"), ("info_sum", "f8"), ("ti_sum", "f8"),
+             ("ti_sumsq", "f8"), ("rel", "f8"))
+
+
+class Shape(C.Structure):
+    """gpirt_shape (include/gpirt_hip.h): the window and tolerances, a host pointer per raw array (NULL: not wanted) and
+    the counters."""
+    _fields_ = [("k_half", C.c_int), ("n_tols", C.c_int), ("tols", C.c_double * SHAPE_MAX_TOLS),
+                ("raw", C.c_void_p * len(SHAPE_RAW)), ("n", C.c_int64), ("m", C.c_int64), ("info_draws", C.c_int64),
+                ("info_skipped", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -345,6 +360,16 @@ SIGNATURES = {
                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins)]),
+    "gpirt_sampler_shape_enable": (_i32, [_vp, _i32, _dp, _i32, _i32]),
+    "gpirt_sampler_shape_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_shape_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_shape_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_shape_state_bytes": (_i32, [_i64, C.POINTER(_i64)]),
+    "gpirt_shape_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Shape)]),
+    "gpirt_mcmc_shape": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

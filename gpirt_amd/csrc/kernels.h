@@ -544,6 +544,35 @@ int launch_pred_accumulate(gpirt_handle_t h, hipStream_t stream, ScoreState* s);
 int pred_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, int64_t bytes);
 int pred_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out);
 
+// shape.hip: shape posteriors of the item response curves, one curve draw at a time (gpirt_sampler_shape_*, gpirt_mcmc_shape;
+// include/gpirt_hip.h, "IRF shape posteriors").  The state is ONE device block of 8-byte words: a header of SHAPE_HEADER_WORDS
+// int64 (tag, layout version, n, m, k_half, n_tols, the four tolerances' bits, info_draws, info_skipped, 0, 0, 0, 0 -- the two
+// counters are kept by the kernels), then the GPIRT_SHAPE_* arrays in order, each on a 16-byte boundary.  Beside it the state
+// owns gbar (N x m, ld N: what draw_fstar's epilogue stores as mean_out), the draw's information I (as gbar), TI and the
+// reliability's terms (1024 each), the grid weights w and a byte per item that tells of a skipped column.
+constexpr int SHAPE_LAYOUT_VERSION = 1;
+constexpr int SHAPE_HEADER_WORDS = 16;
+constexpr int64_t SHAPE_TAG = 0x50414853;             // "SHAP"
+struct ShapeLayout { int64_t off[GPIRT_SHAPE_NARRAYS]; int64_t words; };
+ShapeLayout shape_layout(int64_t m);
+struct ShapeState {
+    bool on = false;
+    int64_t n = 0, m = 0;
+    int k_half = 0, n_tols = 0;
+    double tols[GPIRT_SHAPE_MAX_TOLS] = {};
+    uint64_t* block = nullptr;
+    double *gbar = nullptr, *info = nullptr, *ti = nullptr, *term = nullptr, *w = nullptr;
+    unsigned char* bad = nullptr;                     // [m]: 1 where the last draw's column held a non-finite g
+    std::vector<void*> allocs;
+};
+// refuses k_half outside 1..500, n_tols outside 1..GPIRT_SHAPE_MAX_TOLS and a negative or non-finite tolerance, with a message
+int shape_check(int k_half, const double* tols, int n_tols);
+int shape_alloc(hipStream_t stream, ShapeState* s, int64_t n, int64_t m, int k_half, const double* tols, int n_tols);
+void shape_free(ShapeState* s);
+int launch_shape_accumulate(hipStream_t stream, ShapeState* s, const double* gbar);   // gbar: N x m (ld N) on the device
+int shape_get(hipStream_t stream, ShapeState* s, const char* name, void* h_out, int64_t bytes);
+int shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

@@ -142,6 +142,7 @@ struct gpirt_sampler_s {
     SummaryState sum;                 // posterior summaries (gpirt_sampler_summary_enable; parts == 0: off)
     PpcState ppc;                     // posterior predictive checks (gpirt_sampler_ppc_enable; on == false: off)
     RankState rank;                   // rank posteriors (gpirt_sampler_rank_enable; on == false: off)
+    ShapeState shape;                 // IRF shape posteriors (gpirt_sampler_shape_enable; on: draw_fstar also stores gbar)
     ScoreState score;                 // scoring new respondents (gpirt_sampler_score_enable; on == false: off)
 };
 
@@ -657,6 +658,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
         a.mean = s->mean; a.mu_star = s->mu_star; a.s = s->s; a.out = s->fstar; a.N = N; a.m = m;
         a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0; a.err = s->flags;
         if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; a.off_scratch = s->fstar_off; }
+        if (s->shape.on) a.mean_out = s->shape.gbar;          // the draw's smooth curve, for the shape posteriors
         return launch_fstar_epilogue(st, a);
     }
     GP_HIP(hipMemcpyAsync(W, s->f, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToDevice, st));
@@ -687,6 +689,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
     a.mean = s->mean; a.mu_star = s->mu_star; a.s = s->s; a.out = s->fstar; a.N = N; a.m = m;
     a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0; a.err = s->flags;
     if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; a.off_scratch = s->fstar_off; }
+    if (s->shape.on) a.mean_out = s->shape.gbar;
     return launch_fstar_epilogue(st, a);                                                      // :26-28
 }
 
@@ -1204,6 +1207,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     summary_free(&s->sum);
     ppc_free(&s->ppc);
     rank_free(&s->rank);
+    shape_free(&s->shape);
     score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -1703,6 +1707,62 @@ int gpirt_rank_combine(gpirt_handle_t h, int chains, const void* const* d_states
     return rank_combine(h, chains, d_states, signs, out);
 }
 
+// ---- IRF shape posteriors (shape.hip) on the stage API -------------------------------------------------------------------
+static int shape_needs_on(gpirt_sampler_t s)
+{
+    if (s->shape.on) return 0;
+    set_error("the shape posteriors are not enabled (gpirt_sampler_shape_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_shape_enable(gpirt_sampler_t s, int k_half, const double* tols, int n_tols, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) GP_TRY(shape_check(k_half, tols, n_tols));  // refused before the old state goes
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators or storing gbar
+    shape_free(&s->shape);
+    if (!on) return 0;
+    const int rc = shape_alloc(s->h->stream, &s->shape, s->n, s->m, k_half, tols, n_tols);
+    if (rc) shape_free(&s->shape);
+    return rc;
+}
+
+int gpirt_sampler_shape_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(shape_needs_on(s));
+    return launch_shape_accumulate(s->h->stream, &s->shape, s->shape.gbar);
+}
+
+int gpirt_sampler_shape_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(shape_needs_on(s));
+    return shape_get(s->h->stream, &s->shape, name, h_out, bytes);
+}
+
+int gpirt_sampler_shape_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(shape_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the header's counters are the kernels'
+    *d_state = s->shape.block;
+    *bytes = shape_layout(s->m).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_shape_state_bytes(int64_t m, int64_t* bytes)
+{
+    GP_ARG(m > 0 && bytes);
+    *bytes = shape_layout(m).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out)
+{
+    return shape_combine(h, chains, d_states, signs, out);
+}
+
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
 static int score_needs_on(gpirt_sampler_t s)
 {
@@ -1864,6 +1924,7 @@ static int lookup(gpirt_sampler_t s, const char* name, void** p, int64_t* count)
         { "y", s->y, n * m }, { "rs_trace", s->rs_trace, s->rs_trace ? 128 : 0 },
         { "rs_stats", s->rs_ctl, s->rs_ctl ? 8 : 0 },     // 64-bit words: [first item not committed, mispredictions found, ...]
         { "fstar_full", s->fstar_full, s->fstar_full ? N * s->blk_m : 0 }, { "theta_stage", s->theta_stage, s->theta_stage ? n : 0 },
+        { "gbar", s->shape.gbar, s->shape.on ? N * m : 0 },       // the curve draw_fstar's epilogue stored (shape posteriors on)
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { *p = e.p; *count = e.c; return 0; }
@@ -2047,6 +2108,8 @@ struct ChainRun {
     bool predict;                     // gpirt_mcmc_predict: the score state also predicts the unseen answers (it travels inside keep_score)
     bool pairs;                       // gpirt_mcmc_pairs: the PPC state also checks the item pairs (it travels inside keep_ppc)
     const gpirt_ppc_bins* bins;       // gpirt_mcmc_bins: ... and the theta-binned item fit with these cuts (inside keep_ppc too)
+    ShapeState* keep_shape;           // gpirt_mcmc_shape: ... and the IRF shape posteriors (window and tolerances in `shape`)
+    const gpirt_shape* shape;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2110,6 +2173,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_score = std::move(s->score);
                 s->score = ScoreState{};
             }
+            if (cr->keep_shape) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_shape = std::move(s->shape);
+                s->shape = ShapeState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -2140,6 +2208,9 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     const bool score = cr && cr->keep_score;
     if (!rc && score) rc = gpirt_sampler_score_enable(s, cr->y_new, cr->n_new);
     if (!rc && score && cr->predict) rc = gpirt_sampler_score_predict_enable(s, 1);
+    // (gbar holds a curve from the first step's draw_fstar on; no draw is accumulated before that)
+    const bool shape = cr && cr->keep_shape;
+    if (!rc && shape) rc = gpirt_sampler_shape_enable(s, cr->shape->k_half, cr->shape->tols, cr->shape->n_tols, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2156,6 +2227,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc && ppc) rc = gpirt_sampler_ppc_accumulate(s);             // nor does the replicate (counter-based)
                 if (!rc && ranks) rc = gpirt_sampler_rank_accumulate(s);          // the ranks draw nothing at all
                 if (!rc && score) rc = gpirt_sampler_score_accumulate(s);         // nor does the scoring (the live f*)
+                if (!rc && shape) rc = gpirt_sampler_shape_accumulate(s);         // nor the shapes (the step's gbar)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -2183,7 +2255,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     // every part of a slot starts on a 16-byte boundary (the summaries' kernel reads f and mu of a slot two doubles a lane)
     auto even = [](size_t c) { return (c + 1) & ~(size_t)1; };
     const size_t off_beta = even((size_t)n), off_f = off_beta + even((size_t)(2 * m)), off_mu = off_f + even((size_t)(n * m));
-    const size_t ck_doubles = off_mu + even((size_t)(n * m)) + 3 * even((size_t)(N * m));
+    const size_t off_gbar = off_mu + even((size_t)(n * m)) + 3 * even((size_t)(N * m));   // with the shapes on: gbar, last
+    const size_t ck_doubles = off_gbar + (shape ? even((size_t)(N * m)) : 0);
     const size_t off_fstar = off_mu + even((size_t)(n * m)) + even((size_t)(N * m));      // the slot's f*, after mu*
     double* ck[NS] = { nullptr, nullptr, nullptr };
     hipEvent_t ev_flags[NS] = {}, ev_copied[NS] = {};
@@ -2206,9 +2279,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     }
     struct Part { double* p; size_t cnt; };
     auto parts = [&]() {
-        return std::vector<Part>{ { s->theta, (size_t)n }, { s->beta, (size_t)(2 * m) }, { s->f, (size_t)(n * m) },
-                                  { s->mu, (size_t)(n * m) }, { s->mu_star, (size_t)(N * m) }, { s->fstar, (size_t)(N * m) },
-                                  { s->irf_sum, (size_t)(N * m) } };
+        std::vector<Part> v{ { s->theta, (size_t)n }, { s->beta, (size_t)(2 * m) }, { s->f, (size_t)(n * m) },
+                             { s->mu, (size_t)(n * m) }, { s->mu_star, (size_t)(N * m) }, { s->fstar, (size_t)(N * m) },
+                             { s->irf_sum, (size_t)(N * m) } };
+        if (shape) v.push_back(Part{ s->shape.gbar, (size_t)(N * m) });
+        return v;
     };
     auto save_ckpt = [&](int k) -> int {                    // state after k iterations -> slot k % NS, on the compute stream
         const int q = k % NS;
@@ -2247,6 +2322,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
             GP_TRY(launch_ppc_accumulate(h->stream, &s->ppc, d + off_f, d + off_mu, s->y, s->opt.seed, (uint32_t)k, d));    // (d: the slot's theta)
         if (ranks) GP_TRY(launch_rank_accumulate(h->stream, &s->rank, d));      // the slot's theta
         if (score) GP_TRY(launch_score_accumulate(h, h->stream, &s->score, d + off_fstar));   // the slot's f*
+        if (shape) GP_TRY(launch_shape_accumulate(h->stream, &s->shape, d + off_gbar));       // the slot's gbar
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2384,7 +2460,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
-                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr)
+                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
+                      gpirt_shape* shape = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2463,7 +2540,13 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         }
         GP_TRY(bin_check_cuts(bins->h, bins->cuts));
     }
+    if (shape) {
+        GP_ARG(shape->reserved[0] == 0 && shape->reserved[1] == 0 && shape->reserved[2] == 0 && shape->reserved[3] == 0);
+        GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
+        GP_TRY(shape_check(shape->k_half, shape->tols, shape->n_tols));
+    }
     const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
+    const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
@@ -2471,6 +2554,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     std::vector<PpcState> keep_ppc(ppc ? (size_t)chains : 0);
     std::vector<RankState> keep_rank(ranks ? (size_t)chains : 0);
     std::vector<ScoreState> keep_score(score ? (size_t)chains : 0);
+    std::vector<ShapeState> keep_shape(shape ? (size_t)chains : 0);
     const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
@@ -2482,7 +2566,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
                            score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
-                           bins ? &bins_in : nullptr };
+                           bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2519,6 +2603,11 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].pred.block;
         rc = pred_combine(h, chains, st.data(), predict);
     }
+    if (!rc && shape) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].block;
+        rc = shape_combine(h, chains, st.data(), sg.data(), shape);
+    }
+    for (auto& k : keep_shape) shape_free(&k);
     for (auto& k : keep_ppc) ppc_free(&k);
     for (auto& k : keep_rank) rank_free(&k);
     for (auto& k : keep_score) score_free(&k);
@@ -2671,6 +2760,24 @@ int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_the
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins);
+}
+
+// ---- the IRF shape posteriors ---------------------------------------------------------------------------------------------------
+int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape)
+{
+    GP_ARG(opts && shape);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_shape needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape);
 }
 
 }  // extern "C"

@@ -264,6 +264,11 @@ class ShardedSampler:
     def ranks(self, probs=(0.025, 0.5, 0.975)):
         return self.engine.ranks(probs)
 
+    # -- shape posteriors of the item response curves (gpirt_amd.shape): the test information runs over ALL items
+    def shape_enable(self, window=3.0, tols=(0.0, 0.25, 1.0), on=True):
+        raise ValueError("ShardedSampler: the shape posteriors are not offered for item shards (the test information and "
+                         "the reliability of a draw run over all items, and each rank holds its own columns)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None, ranks=None, score=None):
+              ppc=None, ranks=None, score=None, shape=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -129,6 +129,19 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       (n_new x top: each respondent's UNANSWERED items by decreasing info, padded with -1 / NaN; 1 <= top <= 16), pred_draws,
       pred_skipped (a draw whose f* holds a NaN cell is skipped whole for the prediction) and the raw pred_sum, info_sum.
       Without predict the score= argument behaves exactly as before, and the scores themselves do not depend on it.
+    shape: True, or dict(window=3.0, tols=(0.0, 0.25, 1.0), probs=(0.025, 0.5, 0.975), top=20), adds the shape posteriors of
+      the item response curves (gpirt_mcmc_shape, gpirt_amd.shape): after every sampling iteration the device reads that
+      draw's smooth curve g = k*^T S^-1 f + mu* (what draw_fstar draws f* around) and accumulates, per item, inside
+      |theta| <= window (0.01..5.0): p_nonmonotone, p_increasing, p_decreasing, p_flat (len(tols) x m: the draw's largest fall
+      and rise against each tolerance, in logits; at most 4), peak_quantiles and valley_quantiles (len(probs) x m, theta of
+      the argmax / argmin), p_peak_interior, crossings (4 x m: P(0, 1, 2, >= 3 crossings of P = 1/2)), difficulty_quantiles
+      (the first crossing), slope_max_mean, slope_min_mean (and _sd), and over the whole grid item_info (1001 x m, the mean
+      Fisher information), test_info_mean, test_info_sd, sem (1001), reliability_mean, reliability_sd; "nonmonotone" lists the
+      `top` (1..64) items most often non-monotone at the largest tolerance (items, p).  draws / nonfinite count per item (a
+      curve with any non-finite value is skipped), info_draws / info_skipped per draw; the raw accumulators come with it.
+      Memory at m = 1024: 24 MB of accumulators per chain plus 8 MB each for the curve and the draw's information.  Nothing is
+      drawn: the chain is untouched under both RNG contracts.  Reflected chains are reflected exactly on their accumulators.
+      shape=None leaves every other path as it is.
     """
     from .ops import RStream
 
@@ -170,6 +183,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         else:
             score = dict(data=score, probs=SC.DEFAULT_PROBS, predict=False, top=SC.DEFAULT_TOP)
         score["data"] = np.asfortranarray(SC.check_y_new(score["data"], y.shape[1]))
+    if shape is not None and shape is not False:
+        from . import shape as SH
+        shape = SH.parse(shape)
+    else:
+        shape = None
     pairs = bins = None
     if isinstance(ppc, dict):
         from . import ppc as P
@@ -188,10 +206,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
             bins = dict(cuts=P.check_cuts(P.DEFAULT_CUTS if ppc["bins"] is True else ppc["bins"]),
                         top=P.check_bins_top(ppc.get("bins_top", P.DEFAULT_BINS_TOP)))
         ppc = True
-    if quantiles is not None or ppc or ranks is not None or score is not None:
+    if quantiles is not None or ppc or ranks is not None or score is not None or shape is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -325,7 +343,7 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None):
+                    score=None, pairs=None, bins=None, shape=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
@@ -333,7 +351,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     same chains scoring the new respondents `data` (with or without the checks and the ranks).  pairs (dict(top)):
     gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else).  bins
     (dict(cuts, top)): gpirt_mcmc_bins, the same chains with the theta-binned item fit inside the PPC (with or without the
-    pairs and everything else)."""
+    pairs and everything else).  shape (gpirt_amd.shape.parse's dict): gpirt_mcmc_shape, the same chains with the shape
+    posteriors of the item response curves (with or without everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -396,7 +415,28 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if pairs is not None or bins is not None:
+    if shape is not None:
+        from . import shape as SH
+        from . import score as SC
+        sh, sharr = SH.struct(m, shape["k_half"], shape["tols"])
+        pq = bq = sc = pr = None
+        if pairs is not None:
+            pq, pqarr = P.pairs_struct(m, pairs["top"])
+        if bins is not None:
+            bq, bqarr = P.bins_struct(m, bins["cuts"], bins["top"])
+        if score is not None:
+            sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
+            if score.get("predict"):
+                pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
+        ref = lambda x: C.byref(x) if x is not None else None            # noqa: E731
+        rc = lib.gpirt_mcmc_shape(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                                  rs.ptr if rs is not None else None, ref(q), C.byref(pp) if with_ppc else None,
+                                  C.byref(rk) if ranks is not None else None,
+                                  _ptr(score["data"]) if score is not None else None,
+                                  score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq),
+                                  C.byref(sh))
+    elif pairs is not None or bins is not None:
         pq = bq = None
         if pairs is not None:
             pq, pqarr = P.pairs_struct(m, pairs["top"])
@@ -472,6 +512,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["score"] = SC.result(sc, scarr)
         if score.get("predict"):
             out["score"]["predict"] = SC.predict_result(pr, prarr)
+    if shape is not None:
+        out["shape"] = SH.result(sh, sharr, shape["probs"], shape["top"])
     return out
 
 
@@ -635,7 +677,7 @@ class Sampler:
         check(self.lib.gpirt_sampler_set_iteration(self._s, int(it)))
 
     _SHAPES = {"theta": "n", "f": "nm", "beta": "2m", "mu": "nm", "mu_star": "Nm", "fstar": "Nm", "L": "nn",
-               "logpost": "Nn", "irf_sum": "Nm", "s": "N", "mean": "Nm", "nu": "nm", "z": "nm", "y": "nm"}
+               "logpost": "Nn", "irf_sum": "Nm", "s": "N", "mean": "Nm", "nu": "nm", "z": "nm", "y": "nm", "gbar": "Nm"}
 
     def _shape(self, name):
         n, m, N = self.n, self.m, NGRID
@@ -957,6 +999,64 @@ class Sampler:
         over its own state, nothing reflected."""
         from . import ranks as RK
         return RK.combine(self.handle, [self], probs=probs)
+
+    # -- shape posteriors of the item response curves (include/gpirt_hip.h gpirt_sampler_shape_*, gpirt_amd.shape)
+    def shape_enable(self, window=3.0, tols=(0.0, 0.25, 1.0), on=True):
+        """Allocate and zero the shape accumulators for the window |theta| <= window (0.01..5.0) and up to 4 tolerances
+        (logits, >= 0); from the next draw_fstar on the sampler array "gbar" holds the draw's smooth curve.  on=False frees
+        them."""
+        if not on:
+            check(self.lib.gpirt_sampler_shape_enable(self._s, 0, None, 0, 0))
+            self._shape_ntols = 0
+            return
+        from . import shape as SH
+        k_half, tols = SH.check_window(window), SH.check_tols(tols)
+        check(self.lib.gpirt_sampler_shape_enable(self._s, k_half, (C.c_double * len(tols))(*tols), len(tols), 1))
+        self._shape_ntols = len(tols)
+
+    def shape_accumulate(self):
+        """Add the current "gbar" (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_shape_accumulate")
+
+    def shape_get(self, name: str) -> np.ndarray:
+        """One array by name, in gpirt_amd.shape's layout ([k, j] arrays as 1001 x m): cls (n_tols x 4 x m), peak_hist,
+        valley_hist, cross_first_hist, cross_last_hist (uint32), cross_count (4 x m), draws, nonfinite (m), slope (4 x m),
+        info_sum, ti_sum, ti_sumsq, rel (2), counts (int64: info_draws, info_skipped), tols, and of the last draw info
+        (1001 x m) and ti (1001)."""
+        from . import shape as SH
+        m, nt = self.m, getattr(self, "_shape_ntols", 0)                 # (not enabled: the library refuses the call)
+        dts = dict(_lib.SHAPE_RAW)
+        if name in dts:
+            out = np.empty(SH._raw_shape(name, m), dtype=np.dtype(dts[name]))
+        elif name == "counts":
+            out = np.empty(2, dtype=np.int64)
+        else:
+            out = np.empty({"tols": (_lib.SHAPE_MAX_TOLS,), "info": (m, NGRID), "ti": (NGRID,)}.get(name, (0,)))
+        check(self.lib.gpirt_sampler_shape_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        if name == "tols":
+            return out[:nt]
+        return out.T if name == "info" else SH._public(name, out, nt)
+
+    def shape_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the shape accumulators: what
+        gpirt_amd.shape.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_shape_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def shape(self, probs=(0.025, 0.5, 0.975), top=20, sign=1) -> dict:
+        """Every finished output of this sampler's accumulators (gpirt_amd.shape.finish's dict): gpirt_shape_combine over
+        its own state; sign = -1 reflects it."""
+        from . import shape as SH
+        return SH.combine(self.handle, [self], signs=[sign], probs=probs, top=top)
 
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):

@@ -1059,6 +1059,112 @@ int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_the
                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
                     gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins);
 
+/* ------------------------------------------------------ IRF shape posteriors: monotonicity, peaks, information --------- */
+/* The posterior mean curve and its pointwise bands do not say what SHAPE an item's response curve has: whether it is monotone,
+ * where it peaks, where it crosses P = 1/2, how steep it is, how much Fisher information it carries.  Those are joint
+ * functionals of one curve in one draw.  The stored f* is white noise around the draw's smooth curve (draw_fstar draws every
+ * grid point independently about the conditional mean), so the curve of a draw is that mean itself,
+ *   g[k, j] = (k*^T S^-1 f)[k, j] + mu*[k, j],   k = 0 .. 1000 (theta_k = -5 + 0.01 k),
+ * the one fp64 sum draw_fstar's epilogue forms anyway.  With the shape accumulators on, the epilogue also stores it in the
+ * sampler array "gbar" (N x m, leading dimension 1001; gpirt_sampler_get / _set / _devptr know it): the mu* that draw_fstar
+ * used, not the one draw_beta leaves later in the step.
+ * The window W = [k_lo, k_hi] = [500 - k_half, 500 + k_half], 1 <= k_half <= 500, is symmetric about theta = 0.  Per draw and
+ * item j, all in fp64 on the same g:
+ *   extremes   kmax / kmin = argmax / argmin of g over W, the lowest k on ties (+0 and -0 tie): peak_hist[kmax, j] += 1,
+ *              valley_hist[kmin, j] += 1;
+ *   monotone   DD = max over k <= l in W of g[k] - g[l] (the largest fall: prefix max minus g, maximised), DU = max over
+ *              k <= l in W of g[l] - g[k] (the largest rise); both are >= 0 and, being max, min and ONE subtraction, have the
+ *              same bits in any evaluation order.  For each of the n_tols <= GPIRT_SHAPE_MAX_TOLS tolerances t >= 0 (logits) the
+ *              draw is GPIRT_SHAPE_CLS_FLAT (DD <= t and DU <= t), _INCREASING (DD <= t < DU), _DECREASING (DU <= t < DD) or
+ *              _NONMONOTONE (both > t): cls[t, class, j] += 1;
+ *   crossings  sgn(x) = (x >= 0); c = #{k in [k_lo, k_hi - 1] : sgn(g[k]) != sgn(g[k + 1])}; cross_count[min(c, 3), j] += 1 and,
+ *              for c >= 1, cross_first_hist[k, j] += 1 at the lowest such k and cross_last_hist[k, j] += 1 at the highest;
+ *   slopes     d_k = g[k + 1] - g[k], k in [k_lo, k_hi - 1]; slope_max = (max d_k) / 0.01, slope_min = (min d_k) / 0.01; their
+ *              sums and sums of squares per item in draw order (slope[0..3, j]: max sum, max sumsq, min sum, min sumsq);
+ *   information, over the WHOLE grid: I[k, j] = (e / ((1 + e) (1 + e))) (g' g'), e = exp(-|g[k]|),
+ *              g' = (g[k + 1] - g[k - 1]) / 0.02, at the ends (g[1] - g[0]) / 0.01 and (g[1000] - g[999]) / 0.01;
+ *              info_sum[k, j] += I.
+ * An item whose column holds ANY non-finite g (inside W or not) is skipped for that draw in all of the above: nonfinite[j] += 1;
+ * otherwise draws[j] += 1.
+ * Per draw, over all items: TI[k] = sum_j I[k, j] in ascending j; ti_sum[k] += TI, ti_sumsq[k] += TI TI; the marginal
+ * reliability rho = sum_k w_k TI_k / (TI_k + 1) (prior variance 1), w_k = exp(-theta_k theta_k / 2) / sum of the same with
+ * theta_k the double -5 + 0.01 k, the sum in ascending k; rho is reduced in a fixed order (lane t of 256 adds its terms
+ * k = 4t .. 4t + 3 in order, the 256 partial sums are added in ascending t); rel[0] += rho, rel[1] += rho rho.  A draw in which any item
+ * was skipped adds 1 to info_skipped and nothing to ti_sum, ti_sumsq and rel; any other adds 1 to info_draws.
+ * Every accumulator cell is owned by one thread: no atomics, a fixed order, bit-identical state blocks from run to run.
+ * Arrays indexed [k, j] are stored item-major: cell (k, j) at [j 1001 + k].  cls is [GPIRT_SHAPE_MAX_TOLS][4][m] (the slots
+ * beyond n_tols stay 0), cross_count [4][m], slope [4][m].
+ * Pooling C chains (gpirt_shape_combine) adds the integers and adds the doubles in chain order.  A chain with sign -1 (theta ->
+ * -theta) is reflected ON ITS ACCUMULATORS, exactly because W is symmetric: the k axis of the four histograms, of info_sum,
+ * ti_sum and ti_sumsq is reversed (k -> 1000 - k; the crossing histograms hold pair indices: k -> 999 - k), cross_first_hist
+ * and cross_last_hist swap, increasing and decreasing swap, (slope_max, slope_min) becomes (-slope_min, -slope_max) (sums
+ * negated and swapped, sums of squares swapped), rel is kept.  The argmax / argmin tie rule (the lowest k) is applied BEFORE the
+ * reflection: a reflected chain's tied draw lands on the mirror image of its lowest tied k, not on the lowest tied k of the
+ * mirrored curve.  signs = NULL: all +1.  Blocks with another m, k_half or other tolerances are refused.
+ * Nothing is drawn: with the accumulators on, the chain, the IRFs, R's stream position and every other block's state are bit for
+ * bit what they are without.
+ * Device memory per state at m = 1024: four uint32 histograms and info_sum, 24 MB, plus 8 MB each for gbar and the draw's I. */
+#define GPIRT_SHAPE_MAX_TOLS          4
+#define GPIRT_SHAPE_CLS_FLAT          0
+#define GPIRT_SHAPE_CLS_INCREASING    1
+#define GPIRT_SHAPE_CLS_DECREASING    2
+#define GPIRT_SHAPE_CLS_NONMONOTONE   3
+/* the raw arrays of a state block, in the block's order */
+#define GPIRT_SHAPE_CLS               0       /* uint32 [4][4][m] */
+#define GPIRT_SHAPE_PEAK_HIST         1       /* uint32 [m][1001] */
+#define GPIRT_SHAPE_VALLEY_HIST       2
+#define GPIRT_SHAPE_CROSS_FIRST_HIST  3
+#define GPIRT_SHAPE_CROSS_LAST_HIST   4
+#define GPIRT_SHAPE_CROSS_COUNT       5       /* uint32 [4][m] */
+#define GPIRT_SHAPE_DRAWS             6       /* uint32 [m] */
+#define GPIRT_SHAPE_NONFINITE         7       /* uint32 [m] */
+#define GPIRT_SHAPE_SLOPE             8       /* double [4][m] */
+#define GPIRT_SHAPE_INFO_SUM          9       /* double [m][1001] */
+#define GPIRT_SHAPE_TI_SUM            10      /* double [1001] */
+#define GPIRT_SHAPE_TI_SUMSQ          11      /* double [1001] */
+#define GPIRT_SHAPE_REL               12      /* double [2]: sum rho, sum rho^2 */
+#define GPIRT_SHAPE_NARRAYS           13
+/* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
+typedef struct gpirt_shape {
+    int        k_half;                         /* in (gpirt_mcmc_shape): 1..500; out: the states' */
+    int        n_tols;                         /* in (gpirt_mcmc_shape): 1..GPIRT_SHAPE_MAX_TOLS; out: the states' */
+    double     tols[GPIRT_SHAPE_MAX_TOLS];     /* in (gpirt_mcmc_shape) / out: the first n_tols, each >= 0 and finite */
+    void*      raw[GPIRT_SHAPE_NARRAYS];
+    int64_t    n, m;                           /* out */
+    int64_t    info_draws, info_skipped;       /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_shape;
+/* Stage API.  shape_enable(k_half, tols, n_tols, on != 0) allocates and zeroes the state and the "gbar" array (GPIRT_E_ARG with a
+ * message for k_half outside 1..500, n_tols outside 1..GPIRT_SHAPE_MAX_TOLS, a negative or non-finite tolerance; on = 0 frees
+ * both, tols may then be NULL).  "gbar" holds a curve from the next draw_fstar on (zeros until then).  shape_accumulate adds the
+ * CURRENT gbar as one draw (call it after the step of a sampling iteration).  shape_get copies one array by name to the host,
+ * `bytes` its exact size: the lower-case names of the raw arrays ("cls", "peak_hist", "valley_hist", "cross_first_hist",
+ * "cross_last_hist", "cross_count", "draws", "nonfinite", "slope", "info_sum", "ti_sum", "ti_sumsq", "rel"), "counts" (int64:
+ * info_draws, info_skipped), "tols" (double, GPIRT_SHAPE_MAX_TOLS) and, of the last draw, "info" (double [m][1001], stale for
+ * a skipped item) and "ti" (double [1001], stale after a skipped draw).
+ * shape_state returns the ONE device block (valid until shape_enable is called again or the sampler goes): a header of 16 int64
+ * -- the tag 0x50414853 ("SHAP"), the layout version (1), n, m, k_half, n_tols, the four tolerances' bits, info_draws,
+ * info_skipped, 0, 0, 0, 0 -- then the raw arrays in the order above, every array starting on a 16-byte boundary;
+ * gpirt_shape_state_bytes gives its size. */
+int gpirt_sampler_shape_enable(gpirt_sampler_t s, int k_half, const double* tols, int n_tols, int on);
+int gpirt_sampler_shape_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_shape_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_shape_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_shape_state_bytes(int64_t m, int64_t* bytes);
+int gpirt_shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out);
+/* gpirt_mcmc_bins with the shape posteriors (shape is required, k_half, n_tols and tols given; everything from q on may be
+ * NULL, pairs and bins need ppc as before): every chain also accumulates its curves after each sampling iteration -- under the
+ * item RNG from the verified checkpoint, which then carries gbar --, pooled into shape with the reflection signs that the
+ * chains' alignment decides. */
+int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                     int sample_iterations, int burn_iterations, const double* h_prior_means,
+                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                     gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
