@@ -215,6 +215,20 @@ class Shape(C.Structure):
                 ("info_skipped", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# sum-score posteriors (include/gpirt_hip.h GPIRT_SUMSCORE_*): the raw arrays of a state block in order, with their dtypes
+SUMSCORE_MAX_ITEMS, SUMSCORE_TAG = 4096, 0x43534D53
+SUMSCORE_RAW = (("joint_sum", "f8"), ("pi_sum", "f8"), ("pi_sumsq", "f8"), ("tcc_sum", "f8"), ("tcc_sumsq", "f8"), ("var_sum", "f8"),
+                ("rel", "f8"), ("mask", "u1"), ("w", "f8"), ("last", "f8"), ("last_pi", "f8"))
+
+
+class Sumscore(C.Structure):
+    """gpirt_sumscore (include/gpirt_hip.h): the form's mask (in), a host pointer per raw array (NULL: not wanted) and the
+    counters."""
+    _fields_ = [("items", C.c_void_p), ("raw", C.c_void_p * len(SUMSCORE_RAW)), ("m", C.c_int64), ("M", C.c_int64),
+                ("draws", C.c_int64), ("skipped", C.c_int64), ("rel_draws", C.c_int64), ("rel_skipped", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -370,6 +384,18 @@ SIGNATURES = {
                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                  C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape)]),
+    "gpirt_sampler_sumscore_enable": (_i32, [_vp, _vp, _i32]),
+    "gpirt_sampler_sumscore_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_sumscore_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_sumscore_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_sumscore_state_bytes": (_i32, [_i64, _i64, C.POINTER(_i64)]),
+    "gpirt_sumscore_grid_weights": (_i32, [_dp]),
+    "gpirt_sumscore_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Sumscore)]),
+    "gpirt_mcmc_sumscore": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
+                                 C.POINTER(Sumscore)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

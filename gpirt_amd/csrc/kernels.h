@@ -573,6 +573,34 @@ int launch_shape_accumulate(hipStream_t stream, ShapeState* s, const double* gba
 int shape_get(hipStream_t stream, ShapeState* s, const char* name, void* h_out, int64_t bytes);
 int shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out);
 
+// sumscore.hip: posteriors of the sum score on a form of M items, one f* draw at a time (gpirt_sampler_sumscore_*,
+// gpirt_mcmc_sumscore; include/gpirt_hip.h, "Sum-score posteriors").  The state is ONE device block of 8-byte words: a header of
+// SUMSCORE_HEADER_WORDS int64 (tag, layout version, m, M, N = 1001, draws, skipped, rel_draws, rel_skipped, 0 ... -- the four
+// counters are kept by the kernels), then the GPIRT_SUMSCORE_* arrays in order, each on a 16-byte boundary.  Beside it the state
+// owns the draw's table of (p, q) (1001 x steps pairs, steps = M rounded up to 32), T and V of the draw (1024 each), the form's
+// column indices and the draw's skip word.
+constexpr int SUMSCORE_LAYOUT_VERSION = 1;
+constexpr int SUMSCORE_HEADER_WORDS = 16;
+constexpr int64_t SUMSCORE_TAG = 0x43534d53;          // "SMSC"
+struct SumscoreLayout { int64_t off[GPIRT_SUMSCORE_NARRAYS]; int64_t words; };
+SumscoreLayout sumscore_layout(int64_t m, int64_t M);
+struct SumscoreState {
+    bool on = false;
+    int64_t m = 0, M = 0, steps = 0;
+    uint64_t* block = nullptr;
+    double *tab = nullptr, *T = nullptr, *V = nullptr;
+    int *cols = nullptr, *ctl = nullptr;
+    std::vector<void*> allocs;
+};
+// mask: m bytes (non-zero: the item is in the form) or NULL (all m); refuses an empty form and M > GPIRT_SUMSCORE_MAX_ITEMS
+int sumscore_check(int64_t m, const unsigned char* mask, int64_t* M_out);
+void sumscore_grid_weights(double* w);                // 1001 doubles (host)
+int sumscore_alloc(hipStream_t stream, SumscoreState* s, int64_t m, const unsigned char* mask);
+void sumscore_free(SumscoreState* s);
+int launch_sumscore_accumulate(hipStream_t stream, SumscoreState* s, const double* fstar);   // fstar: N x m (ld N) on the device
+int sumscore_get(hipStream_t stream, SumscoreState* s, const char* name, void* h_out, int64_t bytes);
+int sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_sumscore* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

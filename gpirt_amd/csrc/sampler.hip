@@ -144,6 +144,7 @@ struct gpirt_sampler_s {
     RankState rank;                   // rank posteriors (gpirt_sampler_rank_enable; on == false: off)
     ShapeState shape;                 // IRF shape posteriors (gpirt_sampler_shape_enable; on: draw_fstar also stores gbar)
     ScoreState score;                 // scoring new respondents (gpirt_sampler_score_enable; on == false: off)
+    SumscoreState sumscore;           // sum-score posteriors (gpirt_sampler_sumscore_enable; on == false: off)
 };
 
 namespace {
@@ -1208,6 +1209,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     ppc_free(&s->ppc);
     rank_free(&s->rank);
     shape_free(&s->shape);
+    sumscore_free(&s->sumscore);
     score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -1763,6 +1765,69 @@ int gpirt_shape_combine(gpirt_handle_t h, int chains, const void* const* d_state
     return shape_combine(h, chains, d_states, signs, out);
 }
 
+// ---- sum-score posteriors (sumscore.hip) on the stage API -----------------------------------------------------------------
+static int sumscore_needs_on(gpirt_sampler_t s)
+{
+    if (s->sumscore.on) return 0;
+    set_error("the sum-score posteriors are not enabled (gpirt_sampler_sumscore_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_sumscore_enable(gpirt_sampler_t s, const unsigned char* items_mask, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) GP_TRY(sumscore_check(s->m, items_mask, nullptr));   // refused before the old state goes
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // a kernel still running on the old accumulators
+    sumscore_free(&s->sumscore);
+    if (!on) return 0;
+    const int rc = sumscore_alloc(s->h->stream, &s->sumscore, s->m, items_mask);
+    if (rc) sumscore_free(&s->sumscore);
+    return rc;
+}
+
+int gpirt_sampler_sumscore_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(sumscore_needs_on(s));
+    return launch_sumscore_accumulate(s->h->stream, &s->sumscore, s->fstar);
+}
+
+int gpirt_sampler_sumscore_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(sumscore_needs_on(s));
+    return sumscore_get(s->h->stream, &s->sumscore, name, h_out, bytes);
+}
+
+int gpirt_sampler_sumscore_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(sumscore_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // the header's counters are the kernels'
+    *d_state = s->sumscore.block;
+    *bytes = sumscore_layout(s->m, s->sumscore.M).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_sumscore_state_bytes(int64_t m, int64_t M, int64_t* bytes)
+{
+    GP_ARG(m > 0 && M >= 1 && M <= m && M <= GPIRT_SUMSCORE_MAX_ITEMS && bytes);
+    *bytes = sumscore_layout(m, M).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_sumscore_grid_weights(double* h_w)
+{
+    GP_ARG(h_w);
+    sumscore_grid_weights(h_w);
+    return 0;
+}
+
+int gpirt_sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_sumscore* out)
+{
+    return sumscore_combine(h, chains, d_states, signs, out);
+}
+
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
 static int score_needs_on(gpirt_sampler_t s)
 {
@@ -2110,6 +2175,8 @@ struct ChainRun {
     const gpirt_ppc_bins* bins;       // gpirt_mcmc_bins: ... and the theta-binned item fit with these cuts (inside keep_ppc too)
     ShapeState* keep_shape;           // gpirt_mcmc_shape: ... and the IRF shape posteriors (window and tolerances in `shape`)
     const gpirt_shape* shape;
+    SumscoreState* keep_sumscore;     // gpirt_mcmc_sumscore: ... and the sum-score posteriors (the form's mask in `sumscore`)
+    const gpirt_sumscore* sumscore;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2178,6 +2245,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_shape = std::move(s->shape);
                 s->shape = ShapeState{};
             }
+            if (cr->keep_sumscore) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_sumscore = std::move(s->sumscore);
+                s->sumscore = SumscoreState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -2211,6 +2283,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     // (gbar holds a curve from the first step's draw_fstar on; no draw is accumulated before that)
     const bool shape = cr && cr->keep_shape;
     if (!rc && shape) rc = gpirt_sampler_shape_enable(s, cr->shape->k_half, cr->shape->tols, cr->shape->n_tols, 1);
+    const bool sumscore = cr && cr->keep_sumscore;
+    if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, cr->sumscore->items, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2228,6 +2302,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc && ranks) rc = gpirt_sampler_rank_accumulate(s);          // the ranks draw nothing at all
                 if (!rc && score) rc = gpirt_sampler_score_accumulate(s);         // nor does the scoring (the live f*)
                 if (!rc && shape) rc = gpirt_sampler_shape_accumulate(s);         // nor the shapes (the step's gbar)
+                if (!rc && sumscore) rc = gpirt_sampler_sumscore_accumulate(s);   // nor the sum scores (the live f*)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -2323,6 +2398,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (ranks) GP_TRY(launch_rank_accumulate(h->stream, &s->rank, d));      // the slot's theta
         if (score) GP_TRY(launch_score_accumulate(h, h->stream, &s->score, d + off_fstar));   // the slot's f*
         if (shape) GP_TRY(launch_shape_accumulate(h->stream, &s->shape, d + off_gbar));       // the slot's gbar
+        if (sumscore) GP_TRY(launch_sumscore_accumulate(h->stream, &s->sumscore, d + off_fstar));   // the slot's f*
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2461,7 +2537,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
                       gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
-                      gpirt_shape* shape = nullptr)
+                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2545,6 +2621,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
         GP_TRY(shape_check(shape->k_half, shape->tols, shape->n_tols));
     }
+    if (sumscore) {
+        GP_ARG(sumscore->reserved[0] == 0 && sumscore->reserved[1] == 0 && sumscore->reserved[2] == 0 && sumscore->reserved[3] == 0);
+        GP_TRY(sumscore_check(m, sumscore->items, nullptr));
+    }
     const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
     const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
     gpirt_handle_t h = nullptr;
@@ -2555,6 +2635,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     std::vector<RankState> keep_rank(ranks ? (size_t)chains : 0);
     std::vector<ScoreState> keep_score(score ? (size_t)chains : 0);
     std::vector<ShapeState> keep_shape(shape ? (size_t)chains : 0);
+    std::vector<SumscoreState> keep_sumscore(sumscore ? (size_t)chains : 0);
     const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
@@ -2566,7 +2647,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
                            score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
-                           bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in };
+                           bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
+                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2607,7 +2689,12 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].block;
         rc = shape_combine(h, chains, st.data(), sg.data(), shape);
     }
+    if (!rc && sumscore) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_sumscore[(size_t)c].block;
+        rc = sumscore_combine(h, chains, st.data(), sg.data(), sumscore);
+    }
     for (auto& k : keep_shape) shape_free(&k);
+    for (auto& k : keep_sumscore) sumscore_free(&k);
     for (auto& k : keep_ppc) ppc_free(&k);
     for (auto& k : keep_rank) rank_free(&k);
     for (auto& k : keep_score) score_free(&k);
@@ -2778,6 +2865,25 @@ int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_th
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape);
+}
+
+// ---- the sum-score posteriors -----------------------------------------------------------------------------------------------------
+int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                        const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                        gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                        double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                        gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                        gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
+                        gpirt_sumscore* sumscore)
+{
+    GP_ARG(opts && sumscore);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_sumscore needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore);
 }
 
 }  // extern "C"

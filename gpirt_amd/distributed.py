@@ -269,6 +269,11 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the shape posteriors are not offered for item shards (the test information and "
                          "the reliability of a draw run over all items, and each rank holds its own columns)")
 
+    # -- sum-score posteriors (gpirt_amd.sumscore): the recursion of a draw runs over ALL items of the form
+    def sumscore_enable(self, items=None, on=True):
+        raise ValueError("ShardedSampler: the sum-score posteriors are not offered for item shards (the recursion runs over "
+                         "all items of the form, and each rank holds its own f* columns)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

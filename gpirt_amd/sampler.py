@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None, ranks=None, score=None, shape=None):
+              ppc=None, ranks=None, score=None, shape=None, sumscore=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -142,6 +142,20 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       Memory at m = 1024: 24 MB of accumulators per chain plus 8 MB each for the curve and the draw's information.  Nothing is
       drawn: the chain is untouched under both RNG contracts.  Reflected chains are reflected exactly on their accumulators.
       shape=None leaves every other path as it is.
+    sumscore: True, or dict(items=None, probs=(0.025, 0.5, 0.975)), adds the posteriors of the SUM SCORE S = number of yes
+      answers on a form of items (gpirt_mcmc_sumscore, gpirt_amd.sumscore): after every sampling iteration the device runs
+      the Lord-Wingersky recursion over the form's items at every grid point of that draw's f*.  items: None (all items),
+      column indices or a boolean mask over the PREPARED data's columns (after unanimous items were dropped); at most 4096
+      items; a wrong index or an empty form is a ValueError.  "sumscore" holds score_dist, score_dist_sd, score_cdf (M + 1: the
+      score distribution the model implies for a N(0, 1) population), post ((M + 1) x 1001: p(theta_k | S = s, data), the
+      pooled joint normalised once -- not score='s mean of per-draw posteriors), theta_eap, theta_sd, theta_quantiles
+      (len(probs) x (M + 1)), theta_map (the conversion table; NaN for a score without mass), score_given_theta (1001 x
+      (M + 1)), tcc_mean, tcc_sd, csem (1001: the expected score along theta, its posterior sd, the predictive sd of the
+      score at theta), reliability_mean, reliability_sd (the model-based counterpart of Cronbach's alpha), n_complete,
+      obs_hist, exp_count (over the respondents who answered every item of the form), draws, skipped (a draw whose f* holds a
+      NaN in a form column is skipped whole), rel_draws, rel_skipped, items and the raw accumulators.  Memory at M = 1024:
+      33 MB per chain.  Nothing is drawn: the chain is untouched under both RNG contracts.  sumscore=None leaves every other
+      path as it is.
     """
     from .ops import RStream
 
@@ -188,6 +202,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         shape = SH.parse(shape)
     else:
         shape = None
+    if sumscore is not None and sumscore is not False:
+        from . import sumscore as SS
+        sumscore = SS.parse(sumscore, m)
+    else:
+        sumscore = None
     pairs = bins = None
     if isinstance(ppc, dict):
         from . import ppc as P
@@ -206,10 +225,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
             bins = dict(cuts=P.check_cuts(P.DEFAULT_CUTS if ppc["bins"] is True else ppc["bins"]),
                         top=P.check_bins_top(ppc.get("bins_top", P.DEFAULT_BINS_TOP)))
         ppc = True
-    if quantiles is not None or ppc or ranks is not None or score is not None or shape is not None:
+    if quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -343,7 +362,7 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None, shape=None):
+                    score=None, pairs=None, bins=None, shape=None, sumscore=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
@@ -352,7 +371,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else).  bins
     (dict(cuts, top)): gpirt_mcmc_bins, the same chains with the theta-binned item fit inside the PPC (with or without the
     pairs and everything else).  shape (gpirt_amd.shape.parse's dict): gpirt_mcmc_shape, the same chains with the shape
-    posteriors of the item response curves (with or without everything else)."""
+    posteriors of the item response curves (with or without everything else).  sumscore (gpirt_amd.sumscore.parse's dict):
+    gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -415,10 +435,15 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if shape is not None:
+    if shape is not None or sumscore is not None:
         from . import shape as SH
         from . import score as SC
-        sh, sharr = SH.struct(m, shape["k_half"], shape["tols"])
+        sh = ss = None
+        if shape is not None:
+            sh, sharr = SH.struct(m, shape["k_half"], shape["tols"])
+        if sumscore is not None:
+            from . import sumscore as SS
+            ss, ssarr = SS.struct(m, int(sumscore["mask"].sum()), sumscore["mask"])
         pq = bq = sc = pr = None
         if pairs is not None:
             pq, pqarr = P.pairs_struct(m, pairs["top"])
@@ -429,13 +454,16 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
             if score.get("predict"):
                 pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
         ref = lambda x: C.byref(x) if x is not None else None            # noqa: E731
-        rc = lib.gpirt_mcmc_shape(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                  rs.ptr if rs is not None else None, ref(q), C.byref(pp) if with_ppc else None,
-                                  C.byref(rk) if ranks is not None else None,
-                                  _ptr(score["data"]) if score is not None else None,
-                                  score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq),
-                                  C.byref(sh))
+        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
+                rs.ptr if rs is not None else None, ref(q), C.byref(pp) if with_ppc else None,
+                C.byref(rk) if ranks is not None else None,
+                _ptr(score["data"]) if score is not None else None,
+                score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq))
+        if ss is not None:
+            rc = lib.gpirt_mcmc_sumscore(*args, ref(sh), C.byref(ss))
+        else:
+            rc = lib.gpirt_mcmc_shape(*args, C.byref(sh))
     elif pairs is not None or bins is not None:
         pq = bq = None
         if pairs is not None:
@@ -514,6 +542,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
             out["score"]["predict"] = SC.predict_result(pr, prarr)
     if shape is not None:
         out["shape"] = SH.result(sh, sharr, shape["probs"], shape["top"])
+    if sumscore is not None:
+        out["sumscore"] = SS.result(ss, ssarr, sumscore["probs"], y)
     return out
 
 
@@ -1057,6 +1087,60 @@ class Sampler:
         its own state; sign = -1 reflects it."""
         from . import shape as SH
         return SH.combine(self.handle, [self], signs=[sign], probs=probs, top=top)
+
+    # -- sum-score posteriors (include/gpirt_hip.h gpirt_sampler_sumscore_*, gpirt_amd.sumscore)
+    def sumscore_enable(self, items=None, on=True):
+        """Allocate and zero the sum-score accumulators for the form `items` (None: all m items; column indices or a boolean
+        mask; 1..4096 items -- a wrong index, an empty form and a longer one are ValueErrors).  on=False frees them."""
+        if not on:
+            check(self.lib.gpirt_sampler_sumscore_enable(self._s, None, 0))
+            self._sumscore_M = 0
+            return
+        from . import sumscore as SS
+        mask = SS.form_mask(items, self.m)
+        check(self.lib.gpirt_sampler_sumscore_enable(self._s, C.c_void_p(mask.ctypes.data), 1))
+        self._sumscore_M = int(mask.sum())
+
+    def sumscore_accumulate(self):
+        """Add the current "fstar" (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_sumscore_accumulate")
+
+    def sumscore_get(self, name: str) -> np.ndarray:
+        """One array by name: joint_sum, last (1001 x (M + 1)), pi_sum, pi_sumsq, last_pi (M + 1), tcc_sum, tcc_sumsq, var_sum,
+        w (1001), rel (2), mask (uint8, m), counts (int64: draws, skipped, rel_draws, rel_skipped), and of the last counted
+        draw tcc and var (1001)."""
+        from . import sumscore as SS
+        m, M = self.m, getattr(self, "_sumscore_M", 0)                   # (not enabled: the library refuses the call)
+        dts = dict(_lib.SUMSCORE_RAW)
+        if name in dts:
+            out = np.empty(SS._raw_shape(name, m, M), dtype=np.dtype(dts[name]))
+        elif name == "counts":
+            out = np.empty(4, dtype=np.int64)
+        else:
+            out = np.empty({"tcc": (NGRID,), "var": (NGRID,)}.get(name, (0,)))
+        check(self.lib.gpirt_sampler_sumscore_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def sumscore_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the sum-score accumulators: what
+        gpirt_amd.sumscore.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_sumscore_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def sumscore(self, probs=(0.025, 0.5, 0.975), sign=1, y=None) -> dict:
+        """Every finished output of this sampler's accumulators (gpirt_amd.sumscore.finish's dict): gpirt_sumscore_combine
+        over its own state; sign = -1 reverses its k axis; y (the data): also the observed score histogram."""
+        from . import sumscore as SS
+        return SS.combine(self.handle, [self], signs=[sign], probs=probs, y=y)
 
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):

@@ -1165,6 +1165,103 @@ int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_th
                      const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
                      gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape);
 
+/* ------------------------------------------------------ Sum-score posteriors: score table, TCC, reliability ------------ */
+/* Everything above looks at one item, a pair of items or one respondent with a known answer pattern.  The statistic an IRT user
+ * meets first is the SUM SCORE S = the number of yes answers on a set of items: which score distribution the model implies,
+ * what theta is given only that somebody scored s, the expected score along theta (the test characteristic curve, TCC), how
+ * reliable the score is.  Each is a joint functional of ALL items' curves in one draw (the score given theta is a
+ * Poisson-binomial over the items; forming it from the mean curves gives the wrong spread: a mean of a product is not a
+ * product of means), and none can be had by enumerating answer patterns beyond some twenty items.  Library version 114.
+ * A FORM is a non-empty set of item columns: all m, or those a mask of m bytes names; M is its size, 1 <= M <=
+ * GPIRT_SUMSCORE_MAX_ITEMS.  Per draw, over the grid theta*_k = -5 + 0.01 k (k = 0 .. 1000), from the draw's f* (N x m, carrying
+ * mu*), the form's items taken in ascending column j, all in fp64:
+ *   p[k, j] = 1 / (1 + exp(-f*[k, j])),  q[k, j] = 1 / (1 + exp(+f*[k, j])): each formed on its own, q is never 1 - p, so that
+ *             both keep their relative accuracy in the tails; f* = +-inf gives exactly 0 and 1 (so does |f*| = 800: exp overflows
+ *             to inf, 1 / inf = 0);
+ *   A[k, .]   starts as A[k, 0] = 1, A[k, s > 0] = 0; for each item A[k, s] <- A[k, s] q + A[k, s - 1] p (two products, one sum).
+ *             The result is A[k, s] = P(S = s | theta*_k, this draw), s = 0 .. M (the Lord-Wingersky recursion);
+ *   w_k       the N(0, 1) density on the grid, normalised: theta_k the double -5 + 0.01 k, exp(-theta_k theta_k / 2) and the sum
+ *             (ascending k) in long double on the host, the quotient rounded ONCE to double and stored in the state;
+ *   pi[s]     = sum_k w_k A[k, s], ascending k: the draw's score distribution for a N(0, 1) population;
+ *   T[k]      = sum_j p[k, j] (the TCC), V[k] = sum_j p[k, j] q[k, j] (the score's variance at theta_k), ascending j;
+ *   rho       = 1 - (sum_k w_k V[k]) / (sum_k w_k (V[k] + T[k] T[k]) - (sum_k w_k T[k])^2), the three sums in ascending k: the
+ *             reliability of the sum score, the model-based counterpart of Cronbach's alpha.
+ * A draw whose f* holds a NaN in a form column is skipped WHOLE (`skipped` += 1, nothing else changes; the decision is made on
+ * the device before anything is touched); a NaN in a column outside the form is ignored.  Every other draw adds 1 to `draws`.  A
+ * counted draw whose total variance (rho's denominator) is not > 0 adds nothing to rel and 1 to `rel_skipped`; any other adds 1
+ * to `rel_draws`.
+ * The accumulators:
+ *   joint_sum[k, s] += w_k A[k, s]       (1001 x (M + 1), cell (k, s) at [k (M + 1) + s])
+ *   pi_sum[s] += pi[s], pi_sumsq[s] += pi[s] pi[s];  tcc_sum[k] += T[k], tcc_sumsq[k] += T[k] T[k], var_sum[k] += V[k];
+ *   rel[0] += rho, rel[1] += rho rho;  last = A and last_pi = pi of the last counted draw.
+ * THE JOINT, NOT THE RATIO.  For somebody new with theta ~ N(0, 1) of whom only the score s is known,
+ * p(theta_k | s, data) is proportional to E_draws[w_k A[k, s]]: the block keeps the joint and it is normalised ONCE at the end.
+ * This differs on purpose from the scorer above, which keeps the mean of per-draw normalised posteriors.  Nothing is normalised
+ * per draw, and pooling chains is plain addition.
+ * NO RESCALING.  Every A[k, s] is a sum of non-negative products of factors <= 1, and a partial product is never smaller than a
+ * final one: whatever underflows on the way belongs to a probability below the smallest normal double.  There is no cancellation
+ * anywhere, so the error is relative (a few M eps) plus an absolute floor of (M + 1) 2^-1021.
+ * Every accumulator cell is owned by one thread: no atomics, a fixed order, bit-identical state blocks from run to run.
+ * Pooling C chains (gpirt_sumscore_combine) adds the doubles and the counters in chain order.  A chain with sign -1 (theta ->
+ * -theta) enters with the k axis of joint_sum, tcc_sum, tcc_sumsq, var_sum (and last) reversed; pi_sum, pi_sumsq and rel are kept
+ * as they are (a reflected chain's sums over k ran in the other order; as with the shape posteriors they are not redone).  last
+ * and last_pi are the last state's.  signs = NULL: all +1.  States with another m, another form or other grid weights are
+ * refused.
+ * Nothing is drawn: with the accumulators on, the chain, the IRFs, R's stream position and every other block's state are bit for
+ * bit what they are without.
+ * Device memory per state at M = 1024: joint_sum and last 8.2 MB each, the draw's (p, q) table 16.4 MB. */
+#define GPIRT_SUMSCORE_MAX_ITEMS      4096
+/* the raw arrays of a state block, in the block's order */
+#define GPIRT_SUMSCORE_JOINT_SUM      0       /* double [1001][M + 1] */
+#define GPIRT_SUMSCORE_PI_SUM         1       /* double [M + 1] */
+#define GPIRT_SUMSCORE_PI_SUMSQ       2       /* double [M + 1] */
+#define GPIRT_SUMSCORE_TCC_SUM        3       /* double [1001] */
+#define GPIRT_SUMSCORE_TCC_SUMSQ      4       /* double [1001] */
+#define GPIRT_SUMSCORE_VAR_SUM        5       /* double [1001] */
+#define GPIRT_SUMSCORE_REL            6       /* double [2]: sum rho, sum rho^2 */
+#define GPIRT_SUMSCORE_MASK           7       /* unsigned char [m]: 1 where the item is in the form */
+#define GPIRT_SUMSCORE_W              8       /* double [1001]: the grid weights */
+#define GPIRT_SUMSCORE_LAST           9       /* double [1001][M + 1] */
+#define GPIRT_SUMSCORE_LAST_PI        10      /* double [M + 1] */
+#define GPIRT_SUMSCORE_NARRAYS        11
+/* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
+typedef struct gpirt_sumscore {
+    const unsigned char* items;                /* in (gpirt_mcmc_sumscore): m bytes, non-zero = in the form; NULL: all m items */
+    void*      raw[GPIRT_SUMSCORE_NARRAYS];
+    int64_t    m, M;                           /* out */
+    int64_t    draws, skipped, rel_draws, rel_skipped;   /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_sumscore;
+/* Stage API.  sumscore_enable(items_mask, on != 0) allocates and zeroes the state for the form the mask names (m bytes, non-zero
+ * = in the form; NULL: all m items); GPIRT_E_ARG with a message for an empty form and for M > GPIRT_SUMSCORE_MAX_ITEMS, the old
+ * state is then kept; on = 0 frees it.  sumscore_accumulate adds the CURRENT f* (the sampler array "fstar") as one draw.
+ * sumscore_get copies one array by name to the host, `bytes` its exact size: the lower-case names of the raw arrays
+ * ("joint_sum", "pi_sum", "pi_sumsq", "tcc_sum", "tcc_sumsq", "var_sum", "rel", "mask", "w", "last", "last_pi"), "counts" (int64:
+ * draws, skipped, rel_draws, rel_skipped) and, of the last counted draw, "tcc" and "var" (double [1001]).
+ * sumscore_state returns the ONE device block (valid until sumscore_enable is called again or the sampler goes): a header of 16
+ * int64 -- the tag 0x43534d53 ("SMSC"), the layout version (1), m, M, N = 1001, draws, skipped, rel_draws, rel_skipped, 0 ... --
+ * then the raw arrays in the order above, every array starting on a 16-byte boundary; gpirt_sumscore_state_bytes gives its
+ * size.  gpirt_sumscore_grid_weights writes the 1001 weights w_k (host only; no device is needed). */
+int gpirt_sampler_sumscore_enable(gpirt_sampler_t s, const unsigned char* items_mask, int on);
+int gpirt_sampler_sumscore_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_sumscore_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_sumscore_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_sumscore_state_bytes(int64_t m, int64_t M, int64_t* bytes);
+int gpirt_sumscore_grid_weights(double* h_w);
+int gpirt_sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_sumscore* out);
+/* gpirt_mcmc_shape with the sum-score posteriors (sumscore is required, items given or NULL; everything from q on, shape
+ * included, may be NULL; pairs and bins need ppc as before): every chain also accumulates its f* after each sampling iteration
+ * -- under the item RNG from the verified checkpoint's f*, under R's stream right after the step --, pooled into sumscore with
+ * the reflection signs that the chains' alignment decides. */
+int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                        int sample_iterations, int burn_iterations, const double* h_prior_means,
+                        const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                        gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                        double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                        gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                        const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                        gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
