@@ -154,6 +154,33 @@ class PpcBins(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+# group-wise item fit (include/gpirt_hip.h GPIRT_DIF_*): the finished fields per (group, bin, item), per (group, item) and per
+# (focal group, item; row 0 NaN), in order; the raw arrays of the state block with their dtypes and shapes ("c": G x B x m,
+# "o": G x B, "g": G x m)
+DIF_CELL_FIELDS = ("obs_rate", "rep_rate", "exp_rate")
+DIF_GROUP_FIELDS = ("ppp_yes", "ppp_yes_mid", "ppp_chi2", "ppp_chi2_mid", "chi2_obs_mean", "chi2_rep_mean")
+DIF_FOCAL_FIELDS = ("mh_log_or_obs_mean", "mh_log_or_rep_mean", "mh_delta_obs_mean", "ppp_mh", "ppp_mh_mid", "mh_undefined",
+                    "std_obs_mean", "std_rep_mean", "std_undefined")
+DIF_RAW = (("sum_n", "u8", "c"), ("sum_t", "u8", "c"), ("sum_r", "u8", "c"), ("sum_e", "f8", "c"), ("occ_sum", "u8", "o"),
+           ("yes_ge", "u4", "g"), ("yes_gt", "u4", "g"), ("chi_ge", "u4", "g"), ("chi_gt", "u4", "g"), ("mh_ge", "u4", "g"),
+           ("mh_gt", "u4", "g"), ("mh_undefined_count", "u4", "g"), ("std_undefined_count", "u4", "g"),
+           ("chi_obs_sum", "f8", "g"), ("chi_rep_sum", "f8", "g"), ("mh_log_obs_sum", "f8", "g"), ("mh_log_rep_sum", "f8", "g"),
+           ("std_obs_sum", "f8", "g"), ("std_rep_sum", "f8", "g"))
+DIF_MAX_G, DIF_MAX_N, DIF_MAX_TOP, DIF_TAG, DIF_NSTATS = 4, 65534, 64, 0x31464944, 8
+
+
+class PpcDif(C.Structure):
+    """gpirt_ppc_dif (include/gpirt_hip.h): top, the groups, the cuts, host pointers per output (NULL: not wanted), counters."""
+    _fields_ = [("top", C.c_int), ("G", C.c_int), ("h", C.c_int), ("cuts", C.c_int * (BINS_MAX_H + 1)), ("reserved0", C.c_int),
+                ("groups", C.POINTER(C.c_int32)),
+                ("cell", C.POINTER(C.c_double) * len(DIF_CELL_FIELDS)), ("occupancy", C.POINTER(C.c_double)),
+                ("group", C.POINTER(C.c_double) * len(DIF_GROUP_FIELDS)), ("focal", C.POINTER(C.c_double) * len(DIF_FOCAL_FIELDS)),
+                ("raw", C.c_void_p * len(DIF_RAW)), ("flagged_items", C.POINTER(C.c_int64)),
+                ("flagged_groups", C.POINTER(C.c_int64)), ("flagged_ppp_mh_mid", C.POINTER(C.c_double)),
+                ("n", C.c_int64), ("m", C.c_int64), ("B", C.c_int64), ("dif_draws", C.c_int64), ("dif_skipped", C.c_int64),
+                ("group_size", C.c_int64 * DIF_MAX_G), ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -396,6 +423,15 @@ SIGNATURES = {
                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                  C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
                                  C.POINTER(Sumscore)]),
+    "gpirt_sampler_ppc_dif_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int), _i32]),
+    "gpirt_sampler_ppc_dif_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_dif_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_dif_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(PpcDif)]),
+    "gpirt_mcmc_dif": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                               C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                               C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
+                               C.POINTER(Sumscore), C.POINTER(PpcDif)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

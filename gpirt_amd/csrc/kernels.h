@@ -424,6 +424,55 @@ int launch_bin_update(hipStream_t stream, BinState* p);
 int bin_get(hipStream_t stream, BinState* p, const char* name, void* h_out, int64_t bytes);
 int bin_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out);
 
+// ppc_dif.hip: the group-wise item fit (gpirt_sampler_ppc_dif_*, gpirt_mcmc_dif), an add-on to a PPC state.  Its accumulators
+// are ONE device block of 8-byte words of their own: a header of DIF_HEADER_WORDS int64 (n, m, layout version, dif_draws,
+// dif_skipped, item0, B, DIF_TAG -- the two counters are kept by dif_update_kernel), DIF_CUT_WORDS int64 with the cuts,
+// DIF_GROUP_WORDS int64 (G, the groups' sizes), the n group codes as int8, then the arrays of DifLayout, cell (g, b, j) at
+// [(g B + b) m + j] and (g, j) at [g m + j], every array padded to 16 bytes.  Beside it: this draw's cells (uint8 per
+// respondent, DIF_NONE left out or off the grid), the last counted draw's, the cells' occupancy, the control words ctl[0] = a
+// theta is off the grid, ctl[1] = a non-finite g in an observed cell of a grouped respondent, this draw's tables [3][G B][m]
+// (N | T << 16 | R << 32, E and V in units of 2^-44; zero between draws: dif_update_kernel clears what it has read), the last
+// counted draw's tables and statistics.
+constexpr int DIF_LAYOUT_VERSION = 1;
+constexpr int DIF_HEADER_WORDS = 8;
+constexpr int DIF_CUT_WORDS = 16;
+constexpr int DIF_GROUP_WORDS = 8;
+constexpr int64_t DIF_TAG = 0x31464944;               // "DIF1"
+constexpr unsigned char DIF_NONE = 0xFF;
+constexpr int DIF_NSTATS = 8;
+enum { DIF_SUM_N, DIF_SUM_T, DIF_SUM_R,                              // uint64, G x B x m
+       DIF_SUM_E,                                                    // double, G x B x m
+       DIF_OCC,                                                      // uint64, G x B
+       DIF_YES_GE, DIF_YES_GT, DIF_CHI_GE, DIF_CHI_GT, DIF_MH_GE, DIF_MH_GT, DIF_MH_UNDEF, DIF_STD_UNDEF,      // uint32, G x m
+       DIF_CHI_OBS, DIF_CHI_REP, DIF_MH_LOG_OBS, DIF_MH_LOG_REP, DIF_STD_OBS, DIF_STD_REP,                      // double, G x m
+       DIF_NARRAYS };
+static_assert(DIF_NARRAYS == GPIRT_DIF_NRAW, "gpirt_ppc_dif::raw");
+struct DifLayout { int64_t groups; int64_t off[DIF_NARRAYS]; int64_t words; };     // offsets in 8-byte words
+DifLayout dif_layout(int64_t n, int64_t m, int64_t G, int64_t B);
+struct DifState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0;
+    int G = 0, h = 0, B = 0;
+    int cuts[GPIRT_BINS_MAX_H + 1] = {};
+    uint64_t* block = nullptr;
+    unsigned char *cell_cur = nullptr, *cell_last = nullptr;          // [n]
+    uint32_t* occ = nullptr;                                          // [128]: this draw's members per cell
+    int* ctl = nullptr;
+    uint64_t *tab = nullptr, *tab_last = nullptr;                     // [3][G B][m]
+    double* stat_last = nullptr;                                      // [DIF_NSTATS][G][m]
+    std::vector<void*> allocs;
+};
+int dif_check_groups(int64_t n, int G, const int32_t* groups, int64_t* sizes);      // GPIRT_E_ARG with the message
+int dif_alloc(hipStream_t stream, DifState* p, int64_t n, int64_t m, int64_t item0, int G, const int32_t* groups, int h,
+              const int* cuts);
+void dif_free(DifState* p);
+// one draw: the cells from theta, the tables from f, mu, y and the PPC's uniforms, then the statistics and the accumulators
+int launch_dif_accumulate(hipStream_t stream, DifState* p, const double* f, const double* mu, const double* y, uint64_t seed,
+                          uint32_t iter, const double* theta);
+int64_t dif_state_words(const DifState* p);
+int dif_get(hipStream_t stream, DifState* p, const char* name, void* h_out, int64_t bytes);
+int dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -434,13 +483,14 @@ struct PpcState {
     double* unit_d = nullptr; uint64_t* unit_i = nullptr;     // the items' sums of a draw ([3][m]), for the total
     PairState pairs;                                  // the pairwise item checks (ppc_pairs.hip; on == false: off)
     BinState bins;                                    // the theta-binned item fit (ppc_bins.hip; on == false: off)
+    DifState dif;                                     // the group-wise item fit (ppc_dif.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written
 int ppc_alloc(hipStream_t stream, PpcState* s, int64_t n, int64_t m, int64_t item0, const double* y);
 void ppc_free(PpcState* s);
 // adds the replicate of one draw: f, mu, y n x m on the device; iter = the completed-iteration counter of that state;
-// theta (n, on the device) is read only with the bins on
+// theta (n, on the device) is read only with the bins or the group-wise fit on
 int launch_ppc_accumulate(hipStream_t stream, PpcState* s, const double* f, const double* mu, const double* y, uint64_t seed,
                           uint32_t iter, const double* theta);
 int ppc_seal(hipStream_t stream, PpcState* s);      // refreshes the header (synchronises)

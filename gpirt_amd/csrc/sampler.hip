@@ -1661,6 +1661,48 @@ int gpirt_ppc_bins_combine(gpirt_handle_t h, int chains, const void* const* d_st
     return bin_combine(h, chains, d_states, signs, out);
 }
 
+// ---- group-wise item fit (ppc_dif.hip): an add-on to the PPC state ----------------------------------------------------------
+static int dif_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.dif.on) return 0;
+    set_error("the group-wise item fit is not enabled (gpirt_sampler_ppc_dif_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_ppc_dif_enable(gpirt_sampler_t s, int G, const int32_t* groups, int h, const int* cuts, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    dif_free(&s->ppc.dif);
+    if (!on) return 0;
+    GP_TRY(ppc_needs_on(s));
+    const int rc = dif_alloc(s->h->stream, &s->ppc.dif, s->n, s->m, s->opt.item0, G, groups, h, cuts);
+    if (rc) dif_free(&s->ppc.dif);
+    return rc;
+}
+
+int gpirt_sampler_ppc_dif_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(dif_needs_on(s));
+    return dif_get(s->h->stream, &s->ppc.dif, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_dif_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(dif_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.dif.block;
+    *bytes = dif_state_words(&s->ppc.dif) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out)
+{
+    return dif_combine(h, chains, d_states, signs, out);
+}
+
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
 static int rank_needs_on(gpirt_sampler_t s)
 {
@@ -2177,6 +2219,7 @@ struct ChainRun {
     const gpirt_shape* shape;
     SumscoreState* keep_sumscore;     // gpirt_mcmc_sumscore: ... and the sum-score posteriors (the form's mask in `sumscore`)
     const gpirt_sumscore* sumscore;
+    const gpirt_ppc_dif* dif;         // gpirt_mcmc_dif: ... and the group-wise item fit with these groups and cuts (inside keep_ppc)
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2275,6 +2318,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
     if (!rc && ppc && cr->pairs) rc = gpirt_sampler_ppc_pairs_enable(s, 1);
     if (!rc && ppc && cr->bins) rc = gpirt_sampler_ppc_bins_enable(s, cr->bins->h, cr->bins->cuts, 1);
+    if (!rc && ppc && cr->dif) rc = gpirt_sampler_ppc_dif_enable(s, cr->dif->G, cr->dif->groups, cr->dif->h, cr->dif->cuts, 1);
     const bool ranks = cr && cr->keep_rank;
     if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
     const bool score = cr && cr->keep_score;
@@ -2537,7 +2581,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
                       gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
-                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr)
+                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2625,7 +2669,18 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(sumscore->reserved[0] == 0 && sumscore->reserved[1] == 0 && sumscore->reserved[2] == 0 && sumscore->reserved[3] == 0);
         GP_TRY(sumscore_check(m, sumscore->items, nullptr));
     }
+    if (dif) {
+        GP_ARG(ppc);
+        GP_ARG(dif->reserved0 == 0 && dif->reserved[0] == 0 && dif->reserved[1] == 0 && dif->reserved[2] == 0 && dif->reserved[3] == 0);
+        if (dif->top < 1 || dif->top > GPIRT_DIF_MAX_TOP) {
+            set_error("group-wise PPC: top = %d is outside 1..%d", dif->top, GPIRT_DIF_MAX_TOP);
+            return GPIRT_E_ARG;
+        }
+        GP_TRY(dif_check_groups(n, dif->G, dif->groups, nullptr));
+        GP_TRY(bin_check_cuts(dif->h, dif->cuts));
+    }
     const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
+    const gpirt_ppc_dif dif_in = dif ? *dif : gpirt_ppc_dif{};
     const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
@@ -2648,7 +2703,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
                            score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
                            bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
-                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore };
+                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2671,6 +2726,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     if (!rc && bins) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].bins.block;
         rc = bin_combine(h, chains, st.data(), sg.data(), bins);
+    }
+    if (!rc && dif) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].dif.block;
+        rc = dif_combine(h, chains, st.data(), sg.data(), dif);
     }
     for (auto& k : keep) summary_free(&k);
     if (!rc && ranks) {
@@ -2884,6 +2943,25 @@ int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore);
+}
+
+// ---- the group-wise item fit --------------------------------------------------------------------------------------------------------
+int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                   const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                   gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                   gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
+                   gpirt_sumscore* sumscore, gpirt_ppc_dif* dif)
+{
+    GP_ARG(opts && ppc && dif);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_dif needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif);
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@ The theta-binned item fit ("theta-binned item fit" in the header; csrc/ppc_bins.
 reflection signs, `bins_from_rep` is the NumPy statement of the header over stored theta, g and replicates (integers exact,
 E, V and X2 in np.longdouble, the chi-square decisions as (lo, hi) brackets from `bins_bounds`) and `bins_from_draws` builds
 the replicates from stored g draws.
+The group-wise item fit ("group-wise item fit" in the header; csrc/ppc_dif.hip) is the third add-on: see the section at the end
+of this module.
 ShardedSampler is not covered: the respondents' statistics would need one all-reduce per draw.  The keying of the
 uniforms by the global item index keeps that possible.
 """
@@ -731,3 +733,342 @@ def from_draws(y, g_draws, seed, iters, item0=0) -> dict:
     out["undecided"] = dict(cells=und_cells, comparisons=und_cmp)
     out["comparisons"] = n_cmp
     return out
+
+
+# ------------------------------------------------------------------------------------------ group-wise item fit (DIF) ---
+# ("group-wise item fit" in the header; csrc/ppc_dif.hip) the third add-on: `check_groups`, `dif_struct` / `dif_result` wrap
+# gpirt_ppc_dif, `dif_combine` pools chains' state blocks with their reflection signs, `dif_tables` / `dif_draw_stats` /
+# `dif_from_tables` are the NumPy statement of the header -- integer tables, then fp64 operations in the header's order, so the
+# same tables give the same bits --, `dif_from_rep` runs it over stored theta, g and replicates, `dif_from_draws` builds the
+# replicates with this module's Philox.
+DEFAULT_DIF_TOP = 20
+DIF_FIX = 2.0 ** 44
+
+
+def check_groups(groups, n: int):
+    """(codes as int32 (n,), G): -1 = left out, 0 = the reference group, 1 .. G - 1 the focal groups, 2 <= G <= 4, no gap in
+    the codes, no empty group; n <= 65534.  Anything else is a ValueError that says which."""
+    if n > _lib.DIF_MAX_N:
+        raise ValueError(f"dif: n = {n} is beyond {_lib.DIF_MAX_N} respondents")
+    g = np.asarray(groups)
+    if g.ndim != 1 or g.shape[0] != n:
+        raise ValueError(f"dif: groups must hold one code per respondent ({n}), got shape {g.shape}")
+    if g.dtype == bool or not (np.issubdtype(g.dtype, np.integer) or (np.issubdtype(g.dtype, np.floating) and np.isfinite(g).all()
+                                                                       and (g == np.rint(g)).all())):
+        raise ValueError("dif: the group codes must be integers")
+    g = g.astype(np.int64)
+    if ((g < -1) | (g >= _lib.DIF_MAX_G)).any():
+        bad = g[(g < -1) | (g >= _lib.DIF_MAX_G)][0]
+        raise ValueError(f"dif: the group code {int(bad)} is outside -1..{_lib.DIF_MAX_G - 1}")
+    G = int(g.max()) + 1
+    if G < 2:
+        raise ValueError("dif: a reference group 0 and at least one focal group 1 are needed")
+    for c in range(G):
+        if not (g == c).any():
+            raise ValueError(f"dif: group {c} has no member (the codes 0..{G - 1} must all be used)")
+    return np.ascontiguousarray(g, dtype=np.int32), G
+
+
+def check_dif_top(top) -> int:
+    t = int(top)
+    if t != top or not 1 <= t <= _lib.DIF_MAX_TOP:
+        raise ValueError(f"dif: top must be an integer in 1..{_lib.DIF_MAX_TOP}")
+    return t
+
+
+def _dif_shape(kind, m, G, B):
+    return {"c": (G, B, m), "o": (G, B), "g": (G, m)}[kind]
+
+
+def dif_struct(m: int, G: int, cuts=DEFAULT_CUTS, top=DEFAULT_DIF_TOP, groups=None):
+    """A gpirt_ppc_dif with the cuts (and the group codes, for gpirt_mcmc_dif) and host arrays for every output, and those
+    arrays (kept alive by the caller)."""
+    cuts = check_cuts(cuts)
+    B = 2 * len(cuts) + 1
+    p = _lib.PpcDif()
+    p.top = check_dif_top(top)
+    p.G, p.h = int(G), len(cuts)
+    for q, d in enumerate(cuts):
+        p.cuts[q] = d
+    arr = {}
+    if groups is not None:
+        arr["_groups"] = np.ascontiguousarray(groups, dtype=np.int32)
+        p.groups = arr["_groups"].ctypes.data_as(C.POINTER(C.c_int32))
+    for grp, names, shape in (("cell", _lib.DIF_CELL_FIELDS, (G, B, m)), ("group", _lib.DIF_GROUP_FIELDS, (G, m)),
+                              ("focal", _lib.DIF_FOCAL_FIELDS, (G, m))):
+        for k, name in enumerate(names):
+            arr[name] = np.empty(shape)
+            getattr(p, grp)[k] = arr[name].ctypes.data_as(_dp)
+    arr["occupancy"] = np.empty((G, B))
+    p.occupancy = arr["occupancy"].ctypes.data_as(_dp)
+    for k, (name, dt, kind) in enumerate(_lib.DIF_RAW):
+        arr[name] = np.empty(_dif_shape(kind, m, G, B), dtype=_BIN_DTYPES[dt])
+        p.raw[k] = arr[name].ctypes.data
+    for name in ("flagged_items", "flagged_groups"):
+        arr[name] = np.empty(p.top, dtype=np.int64)
+        setattr(p, name, arr[name].ctypes.data_as(C.POINTER(C.c_int64)))
+    arr["flagged_ppp_mh_mid"] = np.empty(p.top)
+    p.flagged_ppp_mh_mid = arr["flagged_ppp_mh_mid"].ctypes.data_as(_dp)
+    return p, arr
+
+
+def dif_result(p, arr) -> dict:
+    """The "dif" dict of gpirtMCMC(ppc=dict(dif=...)), Sampler.ppc_dif() and dif_combine(): every array of the header by name
+    (cell (g, b, j) at [g, b, j]; the focal arrays indexed by the group code, row 0 NaN), "cuts", "flagged" (dict: items,
+    groups, ppp_mh_mid) and the counters."""
+    out = {k: v for k, v in arr.items() if not k.startswith("flagged_") and not k.startswith("_")}
+    out["flagged"] = dict(items=arr["flagged_items"], groups=arr["flagged_groups"], ppp_mh_mid=arr["flagged_ppp_mh_mid"])
+    out["cuts"] = np.array([p.cuts[q] for q in range(p.h)], dtype=np.int64)
+    out.update(n=int(p.n), m=int(p.m), B=int(p.B), G=int(p.G), dif_draws=int(p.dif_draws), dif_skipped=int(p.dif_skipped),
+               group_size=np.array([p.group_size[g] for g in range(p.G)], dtype=np.int64))
+    return out
+
+
+def dif_state_header(state) -> dict:
+    """The header of a group-wise state block (a device tensor): its 8 int64 words, the cuts, G and the groups' sizes."""
+    w = state[:32].cpu().numpy().view(np.int64)
+    B, G = int(w[6]), int(w[24])
+    return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), dif_draws=int(w[3]), dif_skipped=int(w[4]), item0=int(w[5]),
+                B=B, tag=int(w[7]), cuts=tuple(int(x) for x in w[8:8 + max((B - 1) // 2, 0)]), G=G,
+                group_size=tuple(int(x) for x in w[25:25 + max(min(G, 4), 0)]))
+
+
+def dif_combine(handle, states, signs=None, top=DEFAULT_DIF_TOP) -> dict:
+    """gpirt_ppc_dif_combine over the group-wise state blocks `states` (device tensors, or Samplers with ppc_dif_enable() on,
+    all on handle's device): the integers added, the doubles added in chain order; a chain whose sign is -1 enters with the bin
+    axis of its tables reversed.  Blocks with another n, m, item0, groups or cuts are refused."""
+    lib = _lib.load()
+    tensors = [s.ppc_dif_state() if hasattr(s, "ppc_dif_state") else s for s in states]
+    hdr = dif_state_header(tensors[0])
+    if hdr["tag"] != _lib.DIF_TAG or not 2 <= hdr["G"] <= _lib.DIF_MAX_G:
+        raise ValueError("dif_combine: the first state is not a group-wise PPC state block")
+    p, arr = dif_struct(hdr["m"], hdr["G"], hdr["cuts"], top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    sg = None
+    if signs is not None:
+        if len(signs) != nc:
+            raise ValueError("dif_combine: one sign per state")
+        sg = (C.c_int * nc)(*[int(x) for x in signs])
+    check(lib.gpirt_ppc_dif_combine(handle.ptr, nc, ptrs, sg, C.byref(p)))
+    return dif_result(p, arr)
+
+
+def dif_fix(x):
+    """rint(x 2^44) as uint64: a term of E or V in the header's fixed point"""
+    return np.rint(np.asarray(x, dtype=np.float64) * DIF_FIX).astype(np.uint64)
+
+
+def dif_cells(theta, groups, cuts, B):
+    """(cell (uint8, n; 255 = left out or off the grid), any theta off the grid) of one draw"""
+    from .quantiles import grid_index
+    k = grid_index(np.asarray(theta, dtype=np.float64))
+    ok = (k >= 0) & (groups >= 0)
+    cell = np.where(ok, groups.astype(np.int64) * B + bin_of_index(np.where(k >= 0, k, 500), cuts), 255).astype(np.uint8)
+    return cell, bool((k < 0).any())
+
+
+def dif_tables(y, cell, g, rep, GB):
+    """One draw's integer tables (GB x m each): N, T, R (int64) and the fixed-point E, V (uint64), over the observed cells of
+    the respondents whose cell is not 255; g must be finite there."""
+    y = np.asarray(y, dtype=np.float64)
+    m = y.shape[1]
+    obs = ~np.isnan(y) & (cell != 255)[:, None]
+    gz = np.where(obs, g, 0.0)
+    p, e = _plogis(gz)
+    q = np.where(gz >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+    ef, vf = np.where(obs, dif_fix(p), 0).astype(np.uint64), np.where(obs, dif_fix(p * q), 0).astype(np.uint64)
+    N, T, R = (np.zeros((GB, m), dtype=np.int64) for _ in range(3))
+    E, V = (np.zeros((GB, m), dtype=np.uint64) for _ in range(2))
+    yes, rp = obs & (y > 0), obs & (np.asarray(rep) != 0)
+    for c in np.unique(cell[cell != 255]):
+        rows = cell == c
+        N[c], T[c], R[c] = obs[rows].sum(axis=0), yes[rows].sum(axis=0), rp[rows].sum(axis=0)
+        E[c], V[c] = ef[rows].sum(axis=0, dtype=np.uint64), vf[rows].sum(axis=0, dtype=np.uint64)
+    return N, T, R, E, V
+
+
+def dif_draw_stats(N, T, R, Ef, Vf, G, B) -> dict:
+    """The header's statistics of one draw from its tables (G B x m, or G x B x m): fp64 conversions, products, divisions and
+    additions in the header's order, the sums in increasing b.  Returns "stats" (8 x G x m: num(T), den(T), num(R), den(R),
+    STD(T), STD(R), X2(T), X2(R); NaN as the device leaves it), the bool decisions yes_ge, yes_gt, chi_ge, chi_gt (G x m),
+    mh_def, mh_ge, mh_gt, std_def (G x m, row 0 False) and log_obs, log_rep (G x m, 0 where undefined)."""
+    m = np.asarray(N).shape[-1]
+    N, T, R = (np.asarray(a, dtype=np.int64).reshape(G, B, m) for a in (N, T, R))
+    E = np.asarray(Ef, dtype=np.uint64).reshape(G, B, m).astype(np.float64) * (1.0 / DIF_FIX)
+    V = np.asarray(Vf, dtype=np.uint64).reshape(G, B, m).astype(np.float64) * (1.0 / DIF_FIX)
+
+    def serial(terms):                                   # (..., B, m) -> (..., m): 0.0 + t_0 + t_1 + ... in increasing b
+        s = np.zeros(terms.shape[:-2] + (m,))
+        for b in range(B):
+            s = s + terms[..., b, :]
+        return s
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pos = (N > 0) & (V > 0.0)
+        Vs = np.where(pos, V, 1.0)
+        dT, dR = T.astype(np.float64) - E, R.astype(np.float64) - E
+        x2T = serial(np.where(pos, dT * dT / Vs, 0.0))
+        x2R = serial(np.where(pos, dR * dR / Vs, 0.0))
+        Rg, Tg = R.sum(axis=1), T.sum(axis=1)
+        tie = (R == T).all(axis=1)
+        out = dict(yes_ge=Rg >= Tg, yes_gt=Rg > Tg, chi_ge=tie | (x2R >= x2T), chi_gt=~tie & (x2R > x2T))
+        stats = np.full((8, G, m), np.nan)
+        stats[6], stats[7] = x2T, x2R
+        z = lambda: np.zeros((G, m), dtype=bool)         # noqa: E731
+        out.update(mh_def=z(), mh_ge=z(), mh_gt=z(), std_def=z(), log_obs=np.zeros((G, m)), log_rep=np.zeros((G, m)))
+        for f in range(1, G):
+            common = (N[0] > 0) & (N[f] > 0)
+            nb = np.where(common, N[0] + N[f], 1).astype(np.float64)
+            n0, nf = np.where(common, N[0], 1).astype(np.float64), np.where(common, N[f], 1).astype(np.float64)
+            sums = []
+            for Cc in (T, R):
+                num = serial(np.where(common, (Cc[0] * (N[f] - Cc[f])).astype(np.float64) / nb, 0.0))
+                den = serial(np.where(common, ((N[0] - Cc[0]) * Cc[f]).astype(np.float64) / nb, 0.0))
+                sd = serial(np.where(common, nf * (Cc[f].astype(np.float64) / nf - Cc[0].astype(np.float64) / n0), 0.0))
+                sums.append((num, den, sd))
+            nsum = serial(np.where(common, nf, 0.0))
+            (numT, denT, sT), (numR, denR, sR) = sums
+            stats[0, f], stats[1, f], stats[2, f], stats[3, f] = numT, denT, numR, denR
+            ok = (numT != 0) & (denT != 0) & (numR != 0) & (denR != 0)
+            lhs, rhs = numR * denT, numT * denR
+            out["mh_def"][f], out["mh_ge"][f], out["mh_gt"][f] = ok, ok & (lhs >= rhs), ok & (lhs > rhs)
+            out["log_obs"][f] = np.where(ok, np.log(np.where(ok, numT / np.where(ok, denT, 1.0), 1.0)), 0.0)
+            out["log_rep"][f] = np.where(ok, np.log(np.where(ok, numR / np.where(ok, denR, 1.0), 1.0)), 0.0)
+            sok = nsum > 0
+            out["std_def"][f] = sok
+            stats[4, f] = np.where(sok, sT / np.where(sok, nsum, 1.0), np.nan)
+            stats[5, f] = np.where(sok, sR / np.where(sok, nsum, 1.0), np.nan)
+    out["stats"] = stats
+    return out
+
+
+def dif_flagged(ppp_mh_mid, top=DEFAULT_DIF_TOP) -> dict:
+    """The `top` (focal group, item) pairs by decreasing |ppp_mh_mid - 0.5|, ties to the lowest (group, item), NaN never
+    listed; padded with -1 / NaN."""
+    top = check_dif_top(top)
+    mid = np.asarray(ppp_mh_mid, dtype=np.float64)
+    G, m = mid.shape
+    flat = mid[1:].ravel()
+    at = np.flatnonzero(~np.isnan(flat))
+    order = at[np.argsort(-np.abs(flat[at] - 0.5), kind="stable")][:top]
+    w = dict(items=np.full(top, -1, dtype=np.int64), groups=np.full(top, -1, dtype=np.int64), ppp_mh_mid=np.full(top, np.nan))
+    w["items"][:len(order)] = order % m
+    w["groups"][:len(order)] = order // m + 1
+    w["ppp_mh_mid"][:len(order)] = flat[order]
+    return w
+
+
+def dif_from_tables(draws, G, B, m, top=DEFAULT_DIF_TOP, signs=None, skipped=0, group_size=None) -> dict:
+    """The header's accumulators and finished fields from the COUNTED draws' tables: draws = a list of dicts with N, T, R, E, V
+    (G B x m; E and V the fixed-point uint64) and occ (G B members per cell).  signs: None, or +1 / -1 per draw: a draw with -1
+    enters the (group, bin, item) tables and occ_sum with its bin axis reversed; its counters and per-draw sums stay.  Returns
+    dif_result's dict; "log_terms" (G x m) counts the log terms behind mh_log_*_sum, for a bound on them."""
+    S = len(draws)
+    sg = np.ones(S, dtype=np.int64) if signs is None else np.broadcast_to(np.asarray(signs, dtype=np.int64), (S,))
+    zi = lambda *sh: np.zeros(sh, dtype=np.int64)        # noqa: E731
+    acc = dict(sum_n=zi(G, B, m), sum_t=zi(G, B, m), sum_r=zi(G, B, m), sum_e=np.zeros((G, B, m)), occ_sum=zi(G, B))
+    for k in ("yes_ge", "yes_gt", "chi_ge", "chi_gt", "mh_ge", "mh_gt", "mh_undefined_count", "std_undefined_count"):
+        acc[k] = zi(G, m)
+    for k in ("chi_obs_sum", "chi_rep_sum", "mh_log_obs_sum", "mh_log_rep_sum", "std_obs_sum", "std_rep_sum"):
+        acc[k] = np.zeros((G, m))
+    focal = np.arange(G)[:, None] > 0
+    last = None
+    for s, d in enumerate(draws):
+        st = dif_draw_stats(d["N"], d["T"], d["R"], d["E"], d["V"], G, B)
+        flip = (lambda a: a[:, ::-1]) if sg[s] < 0 else (lambda a: a)
+        r3 = lambda a, dt: np.asarray(a).reshape(G, B, m).astype(dt)      # noqa: E731
+        acc["sum_n"] += flip(r3(d["N"], np.int64)); acc["sum_t"] += flip(r3(d["T"], np.int64)); acc["sum_r"] += flip(r3(d["R"], np.int64))
+        acc["sum_e"] = acc["sum_e"] + flip(r3(d["E"], np.uint64).astype(np.float64) * (1.0 / DIF_FIX))
+        acc["occ_sum"] += flip(np.asarray(d["occ"], dtype=np.int64).reshape(G, B))
+        for k in ("yes_ge", "yes_gt", "chi_ge", "chi_gt", "mh_ge", "mh_gt"):
+            acc[k] += st[k]
+        acc["mh_undefined_count"] += focal & ~st["mh_def"]
+        acc["std_undefined_count"] += focal & ~st["std_def"]
+        acc["chi_obs_sum"] = acc["chi_obs_sum"] + st["stats"][6]
+        acc["chi_rep_sum"] = acc["chi_rep_sum"] + st["stats"][7]
+        acc["mh_log_obs_sum"] = acc["mh_log_obs_sum"] + st["log_obs"]
+        acc["mh_log_rep_sum"] = acc["mh_log_rep_sum"] + st["log_rep"]
+        acc["std_obs_sum"] = acc["std_obs_sum"] + np.where(st["std_def"], st["stats"][4], 0.0)
+        acc["std_rep_sum"] = acc["std_rep_sum"] + np.where(st["std_def"], st["stats"][5], 0.0)
+        last = dict(tN=r3(d["N"], np.int32), tT=r3(d["T"], np.int32), tR=r3(d["R"], np.int32), tE=r3(d["E"], np.uint64),
+                    tV=r3(d["V"], np.uint64), stats=st["stats"], cell=d.get("cell"))
+    dts = {name: _BIN_DTYPES[dt] for name, dt, _ in _lib.DIF_RAW}
+    out = {k: v.astype(dts[k]) for k, v in acc.items()}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sN = np.where(acc["sum_n"] > 0, acc["sum_n"], np.nan).astype(np.float64)
+        Sd = float(S) if S > 0 else np.nan
+        out["obs_rate"], out["rep_rate"], out["exp_rate"] = acc["sum_t"] / sN, acc["sum_r"] / sN, acc["sum_e"] / sN
+        out["occupancy"] = acc["occ_sum"] / Sd
+        out["ppp_yes"], out["ppp_yes_mid"] = acc["yes_ge"] / Sd, (acc["yes_ge"] + acc["yes_gt"]) / (2.0 * Sd)
+        out["ppp_chi2"], out["ppp_chi2_mid"] = acc["chi_ge"] / Sd, (acc["chi_ge"] + acc["chi_gt"]) / (2.0 * Sd)
+        out["chi2_obs_mean"], out["chi2_rep_mean"] = acc["chi_obs_sum"] / Sd, acc["chi_rep_sum"] / Sd
+        Sm = S - acc["mh_undefined_count"]
+        Sm = np.where(focal & (Sm > 0), Sm, np.nan).astype(np.float64)
+        Ss = S - acc["std_undefined_count"]
+        Ss = np.where(focal & (Ss > 0), Ss, np.nan).astype(np.float64)
+        rows = np.where(focal, 1.0, np.nan)
+        out["mh_log_or_obs_mean"], out["mh_log_or_rep_mean"] = acc["mh_log_obs_sum"] / Sm, acc["mh_log_rep_sum"] / Sm
+        out["mh_delta_obs_mean"] = -2.35 * out["mh_log_or_obs_mean"]
+        out["ppp_mh"], out["ppp_mh_mid"] = acc["mh_ge"] / Sm, (acc["mh_ge"] + acc["mh_gt"]) / (2.0 * Sm)
+        out["mh_undefined"], out["std_undefined"] = acc["mh_undefined_count"] * rows, acc["std_undefined_count"] * rows
+        out["std_obs_mean"], out["std_rep_mean"] = acc["std_obs_sum"] / Ss, acc["std_rep_sum"] / Ss
+    out["flagged"] = dif_flagged(out["ppp_mh_mid"], top)
+    out["log_terms"] = np.where(focal, S - acc["mh_undefined_count"], 0)
+    out.update(n=None, m=m, B=B, G=G, dif_draws=S, dif_skipped=int(skipped), last=last,
+               group_size=None if group_size is None else np.asarray(group_size, dtype=np.int64))
+    return out
+
+
+def dif_from_rep(y, theta_draws, g_draws, rep_draws, groups, cuts=DEFAULT_CUTS, top=DEFAULT_DIF_TOP, signs=None) -> dict:
+    """The header's group-wise item fit from stored draws: y (n x m; NaN = missing), theta_draws (S, n), g_draws (S, n, m) the
+    draws of g = f + mu, rep_draws (S, n, m) with rep != 0 where yrep = +1, groups (n codes), signs as in dif_from_tables (one
+    per draw).  A draw with a theta off the grid, or a non-finite g in an observed cell of a grouped respondent, is skipped.
+    Returns dif_from_tables' dict, "cuts" and "n" filled in."""
+    cuts = check_cuts(cuts)
+    y = np.asarray(y, dtype=np.float64)
+    n, m = y.shape
+    groups, G = check_groups(groups, n)
+    theta_draws = np.asarray(theta_draws, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    S = theta_draws.shape[0]
+    assert theta_draws.shape == (S, n) and g_draws.shape == (S, n, m) and np.asarray(rep_draws).shape == (S, n, m)
+    sg = np.ones(S, dtype=np.int64) if signs is None else np.broadcast_to(np.asarray(signs, dtype=np.int64), (S,))
+    B = 2 * len(cuts) + 1
+    obs = ~np.isnan(y) & (groups >= 0)[:, None]
+    draws, keep_sg, skipped = [], [], 0
+    for s in range(S):
+        cell, off = dif_cells(theta_draws[s], groups, cuts, B)
+        if off or not np.isfinite(g_draws[s][obs]).all():
+            skipped += 1
+            continue
+        N, T, R, E, V = dif_tables(y, cell, g_draws[s], rep_draws[s], G * B)
+        draws.append(dict(N=N, T=T, R=R, E=E, V=V, occ=np.bincount(cell[cell != 255], minlength=G * B), cell=cell))
+        keep_sg.append(sg[s])
+    out = dif_from_tables(draws, G, B, m, top, keep_sg if draws else None, skipped,
+                          [int((groups == c).sum()) for c in range(G)])
+    out["n"], out["cuts"] = n, np.array(cuts, dtype=np.int64)
+    return out
+
+
+def dif_from_draws(y, theta_draws, g_draws, seed, iters, groups, cuts=DEFAULT_CUTS, top=DEFAULT_DIF_TOP, item0=0, signs=None):
+    """dif_from_rep over the replicates of stored draws, built as bins_from_draws builds them: rep = [u < plogis(g)] with
+    replicate_uniforms' u at the completed-iteration counters `iters`.  Returns (result, min |u - p| over the observed cells
+    of the draws with finite g): a cell that close to its uniform may replicate either way under another evaluation of
+    plogis."""
+    y = np.asarray(y, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    n, m = y.shape
+    obs = ~np.isnan(y)
+    reps, gap = [], np.inf
+    for s, it in enumerate(iters):
+        with np.errstate(invalid="ignore"):
+            gz = np.where(obs & np.isfinite(g_draws[s]), g_draws[s], 0.0)
+        p, _ = _plogis(gz)
+        u = replicate_uniforms(seed, int(it), n, m, item0)
+        fin = obs & np.isfinite(g_draws[s])
+        if fin.any():
+            gap = min(gap, float(np.abs(u - p)[fin].min()))
+        reps.append(obs & (u < p))
+    rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
+    return dif_from_rep(y, theta_draws, g_draws, rep, groups, cuts, top, signs), gap

@@ -101,6 +101,15 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       (1..64) items with the smallest ppp_chi2_mid -- the items whose curve the data contradict; bin_draws, bin_skipped (a
       draw with a theta off the grid or a non-finite g in an observed cell is skipped whole) and the raw sums and counts.
       pairs and bins may be asked for together.
+      ppc=dict(dif=groups) or dif=dict(groups=g, cuts=None, top=20) also checks measurement invariance (gpirt_mcmc_dif):
+      groups holds one code per row of the prepared data (-1 = left out, 0 = the reference group, 1..G-1 the focal groups,
+      G <= 4).  Each draw stratifies the respondents by the bin of their theta (cuts as for bins; None = DEFAULT_CUTS), and
+      "ppc" gains "dif" with the group-wise empirical IRFs obs_rate, rep_rate, exp_rate (G x B x m) and occupancy (G x B);
+      per (group, item) ppp_yes, ppp_yes_mid, ppp_chi2, ppp_chi2_mid, chi2_obs_mean, chi2_rep_mean; per (focal group, item),
+      indexed by the group code with row 0 NaN, the Mantel-Haenszel mh_log_or_obs_mean, mh_log_or_rep_mean,
+      mh_delta_obs_mean (the ETS delta scale), ppp_mh, ppp_mh_mid, mh_undefined and the standardised P-difference
+      std_obs_mean, std_rep_mean; "flagged" lists the `top` (1..64) (item, focal group) pairs whose ppp_mh_mid lies farthest
+      from 0.5; dif_draws, dif_skipped, group_size and the raw sums and counts.  n <= 65534.  It composes with pairs and bins.
     ranks: True, or dict(pivots="median", pairwise=False, probs=(0.025, 0.5, 0.975)), adds the rank posteriors
       (gpirt_mcmc_ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
       the smallest; ties take the mid-rank) and accumulates, in "ranks": rank_mean, rank_var, rank_quantiles
@@ -207,12 +216,12 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         sumscore = SS.parse(sumscore, m)
     else:
         sumscore = None
-    pairs = bins = None
+    pairs = bins = dif = None
     if isinstance(ppc, dict):
         from . import ppc as P
-        unknown = set(ppc) - {"pairs", "top", "bins", "bins_top"}
+        unknown = set(ppc) - {"pairs", "top", "bins", "bins_top", "dif"}
         if unknown:
-            raise ValueError(f"ppc: a dict may give pairs, top, bins and bins_top (unknown keys {sorted(unknown)})")
+            raise ValueError(f"ppc: a dict may give pairs, top, bins, bins_top and dif (unknown keys {sorted(unknown)})")
         if "top" in ppc and not ppc.get("pairs"):
             raise ValueError("ppc: top needs pairs=True")
         if ppc.get("pairs"):
@@ -224,11 +233,19 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         if want_bins:
             bins = dict(cuts=P.check_cuts(P.DEFAULT_CUTS if ppc["bins"] is True else ppc["bins"]),
                         top=P.check_bins_top(ppc.get("bins_top", P.DEFAULT_BINS_TOP)))
+        if ppc.get("dif") is not None and ppc.get("dif") is not False:
+            dif = ppc["dif"] if isinstance(ppc["dif"], dict) else dict(groups=ppc["dif"])
+            unknown = set(dif) - {"groups", "cuts", "top"}
+            if unknown or "groups" not in dif:
+                raise ValueError(f"ppc: dif takes groups, cuts and top (unknown keys {sorted(unknown)})")
+            codes, G = P.check_groups(dif["groups"], y.shape[0])
+            dif = dict(groups=codes, G=G, cuts=P.check_cuts(P.DEFAULT_CUTS if dif.get("cuts") is None else dif["cuts"]),
+                       top=P.check_dif_top(dif.get("top", P.DEFAULT_DIF_TOP)))
         ppc = True
     if quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None:
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -362,7 +379,7 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None, shape=None, sumscore=None):
+                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
@@ -372,7 +389,9 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     (dict(cuts, top)): gpirt_mcmc_bins, the same chains with the theta-binned item fit inside the PPC (with or without the
     pairs and everything else).  shape (gpirt_amd.shape.parse's dict): gpirt_mcmc_shape, the same chains with the shape
     posteriors of the item response curves (with or without everything else).  sumscore (gpirt_amd.sumscore.parse's dict):
-    gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else)."""
+    gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else).  dif
+    (dict(groups, G, cuts, top)): gpirt_mcmc_dif, the same chains with the group-wise item fit inside the PPC (with or without
+    everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -435,7 +454,7 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if shape is not None or sumscore is not None:
+    if shape is not None or sumscore is not None or dif is not None:
         from . import shape as SH
         from . import score as SC
         sh = ss = None
@@ -460,7 +479,10 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
                 C.byref(rk) if ranks is not None else None,
                 _ptr(score["data"]) if score is not None else None,
                 score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq))
-        if ss is not None:
+        if dif is not None:
+            df, dfarr = P.dif_struct(m, dif["G"], dif["cuts"], dif["top"], groups=dif["groups"])
+            rc = lib.gpirt_mcmc_dif(*args, ref(sh), ref(ss), C.byref(df))
+        elif ss is not None:
             rc = lib.gpirt_mcmc_sumscore(*args, ref(sh), C.byref(ss))
         else:
             rc = lib.gpirt_mcmc_shape(*args, C.byref(sh))
@@ -534,6 +556,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
             out["ppc"]["pairs"] = P.pairs_result(pq, pqarr)
         if bins is not None:
             out["ppc"]["bins"] = P.bins_result(bq, bqarr)
+        if dif is not None:
+            out["ppc"]["dif"] = P.dif_result(df, dfarr)
     if ranks is not None:
         out["ranks"] = RK.result(rk, rkarr)
     if score is not None:
@@ -974,6 +998,84 @@ class Sampler:
         from . import ppc as P
         return P.bins_combine(self.handle, [self], signs=[sign],
                               top=getattr(self, "_bins_top", P.DEFAULT_BINS_TOP) if top is None else top)
+
+    # -- group-wise item fit inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_dif_*, gpirt_amd.ppc)
+    def ppc_dif_enable(self, groups=None, cuts=None, top=20, on=True):
+        """Allocate and zero the group-wise accumulators on a sampler whose ppc_enable is on: from then on every ppc_accumulate
+        also stratifies the respondents by (group, bin of that draw's theta) and adds the Mantel-Haenszel, standardised
+        difference, yes-count and chi-square statistics of the data and of the replicate.  groups: one code per respondent
+        (-1 = left out, 0 = reference, 1..G-1 focal); cuts as for ppc_bins_enable; top (1..64): how many (item, group) pairs
+        ppc_dif() flags.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_dif_enable(self._s, 0, None, 0, None, 0))
+            self._dif_shape = None
+            return
+        from . import ppc as P
+        codes, G = P.check_groups(groups, self.n)
+        cuts = P.check_cuts(P.DEFAULT_CUTS if cuts is None else cuts)
+        self._dif_top = P.check_dif_top(top)
+        check(self.lib.gpirt_sampler_ppc_dif_enable(self._s, G, codes.ctypes.data_as(C.POINTER(C.c_int32)), len(cuts),
+                                                    (C.c_int * len(cuts))(*cuts), 1))
+        self._dif_shape = (G, 2 * len(cuts) + 1)
+
+    def ppc_dif_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.DIF_CELL_FIELDS: float64 G x B x m; occupancy: G x B; DIF_GROUP_FIELDS and
+        DIF_FOCAL_FIELDS: G x m), a raw array of _lib.DIF_RAW, cuts (int64), counts (int64: dif_draws, dif_skipped), groups
+        (int8, n), group_size (int64, 4) and, of the last counted draw, cell (uint8, n), tN, tT, tR (int32, G x B x m), tE, tV
+        (uint64, the fixed-point sums) and stats (float64, 8 x G x m)."""
+        from . import ppc as P
+        m = self.m
+        G, B = getattr(self, "_dif_shape", None) or (2, 3)           # (not enabled: the library refuses the call)
+        raw = {r[0]: r for r in _lib.DIF_RAW}
+        if name == "counts":
+            out = np.empty(2, dtype=np.int64)
+        elif name == "cuts":
+            out = np.empty((B - 1) // 2, dtype=np.int64)
+        elif name == "group_size":
+            out = np.empty(_lib.DIF_MAX_G, dtype=np.int64)
+        elif name == "groups":
+            out = np.empty(self.n, dtype=np.int8)
+        elif name == "cell":
+            out = np.empty(self.n, dtype=np.uint8)
+        elif name in ("tN", "tT", "tR"):
+            out = np.empty((G, B, m), dtype=np.int32)
+        elif name in ("tE", "tV"):
+            out = np.empty((G, B, m), dtype=np.uint64)
+        elif name == "stats":
+            out = np.empty((_lib.DIF_NSTATS, G, m))
+        elif name.lower() in raw:
+            _, dt, kind = raw[name.lower()]
+            out = np.empty(P._dif_shape(kind, m, G, B), dtype=P._BIN_DTYPES[dt])
+        elif name in _lib.DIF_CELL_FIELDS:
+            out = np.empty((G, B, m))
+        elif name == "occupancy":
+            out = np.empty((G, B))
+        else:
+            out = np.empty((G, m))
+        check(self.lib.gpirt_sampler_ppc_dif_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def ppc_dif_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the group-wise accumulators: what
+        gpirt_amd.ppc.dif_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_dif_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_dif(self, top=None, sign=1) -> dict:
+        """Every finished output of this sampler's group-wise accumulators (gpirt_amd.ppc.dif_result's shape):
+        gpirt_ppc_dif_combine over its own state; top defaults to ppc_dif_enable's, sign = -1 reverses the bin axis."""
+        from . import ppc as P
+        return P.dif_combine(self.handle, [self], signs=[sign],
+                             top=getattr(self, "_dif_top", P.DEFAULT_DIF_TOP) if top is None else top)
 
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):

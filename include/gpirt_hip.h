@@ -1262,6 +1262,112 @@ int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h
                         const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
                         gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore);
 
+/* ------------------------------------------------------------- group-wise item fit (DIF): Mantel-Haenszel per item ------------ */
+/* Given theta, does an answer still depend on WHO the respondent is (library version 115)?  Differential item functioning: the
+ * respondents are stratified by the bin of a draw's theta (the cuts, the bins and grid_index's rule of the theta-binned item fit
+ * above) and, stratum by stratum, a focal group's answers to an item are compared with the reference group's -- the
+ * Mantel-Haenszel common odds ratio (Holland and Thayer 1988) and the standardised P-difference (Dorans and Kulick 1986) as
+ * posterior predictive discrepancies.  A third add-on to the PPC: enabled on a sampler whose ppc_enable is on, accumulated inside
+ * the same ppc_accumulate call by a pass of its own that forms the PPC's replicate again, bit for bit (the same expression for p,
+ * the same item_uniform(seed, iter, GPIRT_ST_PPC, item0 + j, i)); nothing is drawn.
+ * Groups.  One code per respondent: -1 = left out, 0 = the reference group, 1 .. G - 1 the focal groups,
+ * 2 <= G <= GPIRT_DIF_MAX_G = 4, every group with at least one member; n <= GPIRT_DIF_MAX_N = 65534.  A respondent's cell in a
+ * draw is c = group B + bin (uint8; 255 = left out or theta off the grid).
+ * Per draw and (group g, bin b, item j), over the observed cells of the respondents in (g, b): the integers N = #cells,
+ * T = #{y = +1}, R = #{rep = 1}, and E = sum rint(p 2^44), V = sum rint(p q 2^44) as uint64 (below 2^60): every term rounded once,
+ * the sums exact, so the tables do not depend on the order of summation and integer atomics (LDS and global) form them
+ * deterministically.  E and V below stand for (double)E_fix 2^-44 and (double)V_fix 2^-44.
+ * Per COUNTED draw, every statistic in fp64 from those integer tables, without contraction -- conversions, products, divisions and
+ * additions only, summed in increasing b --, so the same tables give the same bits anywhere:
+ *   cell (g, b, j): sum_n, sum_t, sum_r += N, T, R (uint64); sum_e += E (double); occ_sum[g, b] += #{i in (g, b)};
+ *   group g, item j: R_g = sum_b R, T_g = sum_b T: yes_ge / yes_gt += [R_g >= / > T_g];
+ *            X2_g(C) = sum_b ((double)C - E)^2 / V over the bins with N > 0 and V > 0.  If R = T in every bin of the group the
+ *            draw counts in chi_ge and not in chi_gt, else chi_ge / chi_gt += [X2_g(R) >= / > X2_g(T)]; chi_obs_sum += X2_g(T),
+ *            chi_rep_sum += X2_g(R);
+ *   focal f = 1 .. G - 1 against group 0, item j, over the bins with N_0 > 0 and N_f > 0, n_b = N_0 + N_f, for C in {T, R}:
+ *            num(C) = sum_b (double)(C_0 (N_f - C_f)) / n_b, den(C) = sum_b (double)((N_0 - C_0) C_f) / n_b, alpha = num / den.
+ *            If any of num(T), den(T), num(R), den(R) is 0: mh_undefined += 1 and nothing else of the MH block; otherwise
+ *            mh_ge / mh_gt += [num(R) den(T) >= / > num(T) den(R)], mh_log_obs_sum += log(num(T) / den(T)),
+ *            mh_log_rep_sum += log(num(R) / den(R)).
+ *            STD(C) = (sum_b N_f (C_f / N_f - C_0 / N_0)) / sum_b N_f; without a common bin std_undefined += 1, otherwise
+ *            std_obs_sum += STD(T), std_rep_sum += STD(R).
+ * A draw is skipped whole when any theta is off the grid or g is non-finite in an observed cell of a grouped respondent:
+ * dif_skipped += 1 and nothing else changes; any other draw adds 1 to dif_draws.  The host never synchronises for it.
+ * Finished on the host with S = dif_draws (NaN where a denominator is 0): G x B x m arrays, cell (g, b, j) at [(g B + b) m + j]
+ * (GPIRT_DIF_CELL_*): obs_rate = sum_t / sum_n, rep_rate = sum_r / sum_n, exp_rate = sum_e / sum_n; occupancy = occ_sum / S
+ * (G x B); G x m arrays (GPIRT_DIF_GROUP_*): ppp_yes = yes_ge / S, ppp_yes_mid = (yes_ge + yes_gt) / 2S, ppp_chi2, ppp_chi2_mid
+ * likewise, chi2_obs_mean, chi2_rep_mean; G x m arrays whose row 0 is NaN (GPIRT_DIF_FOCAL_*), with S' = S - mh_undefined and
+ * S" = S - std_undefined: mh_log_or_obs_mean = mh_log_obs_sum / S', mh_log_or_rep_mean, mh_delta_obs_mean = -2.35
+ * mh_log_or_obs_mean (the ETS delta scale), ppp_mh = mh_ge / S', ppp_mh_mid = (mh_ge + mh_gt) / 2S', mh_undefined,
+ * std_obs_mean = std_obs_sum / S", std_rep_mean, std_undefined.
+ *   flagged: the `top` (1..GPIRT_DIF_MAX_TOP, the Python default is 20) (focal group, item) pairs by decreasing
+ *   |ppp_mh_mid - 0.5|, ties to the lowest (group, item), NaN never listed: items, groups, ppp_mh_mid, padded with -1 / NaN.
+ * Determinism: no floating-point atomics anywhere; the only atomics add integers.  Two runs give a byte-identical state block.
+ * Pooling C chains (gpirt_ppc_dif_combine) adds the integers and adds the doubles in chain order; a chain with sign -1 enters with
+ * the bin axis of the (group, bin, item) tables and of occ_sum reversed (exact: the bins are symmetric); every counter and
+ * per-draw sum is kept as the chain decided it.  Blocks with another n, m, item0, G, group vector or cuts are refused.
+ * With the block on, the chain, the IRFs, R's stream position and the PPC, pairs and bins state blocks are bit for bit what they
+ * are without.  Item shards stay refused.
+ * The raw arrays (GPIRT_DIF_NRAW, in the state block's order): uint64 sum_n, sum_t, sum_r, double sum_e (G B m), uint64 occ_sum
+ * (G B), uint32 yes_ge, yes_gt, chi_ge, chi_gt, mh_ge, mh_gt, mh_undefined_count, std_undefined_count (G m), double chi_obs_sum, chi_rep_sum,
+ * mh_log_obs_sum, mh_log_rep_sum, std_obs_sum, std_rep_sum (G m; the rows of group 0 of the focal arrays stay 0). */
+#define GPIRT_DIF_MAX_G      4
+#define GPIRT_DIF_MAX_N      65534
+#define GPIRT_DIF_MAX_TOP    64
+#define GPIRT_DIF_CELL_NFIELDS   3      /* obs_rate, rep_rate, exp_rate */
+#define GPIRT_DIF_GROUP_NFIELDS  6      /* ppp_yes, ppp_yes_mid, ppp_chi2, ppp_chi2_mid, chi2_obs_mean, chi2_rep_mean */
+#define GPIRT_DIF_FOCAL_NFIELDS  9      /* mh_log_or_obs_mean, mh_log_or_rep_mean, mh_delta_obs_mean, ppp_mh, ppp_mh_mid,
+                                           mh_undefined, std_obs_mean, std_rep_mean, std_undefined */
+#define GPIRT_DIF_NRAW           19
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_ppc_dif {
+    int        top;                            /* in: 1..GPIRT_DIF_MAX_TOP */
+    int        G;                              /* in (gpirt_mcmc_dif): the number of groups; out: the states' */
+    int        h;                              /* in (gpirt_mcmc_dif): the number of cuts; out: the states' */
+    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_dif) / out: d_1 .. d_h, the rest 0 */
+    int        reserved0;                      /* must be 0 */
+    const int32_t* groups;                     /* in (gpirt_mcmc_dif): n codes in -1 .. G - 1 */
+    double*    cell[GPIRT_DIF_CELL_NFIELDS];   /* G x B x m each */
+    double*    occupancy;                      /* G x B */
+    double*    group[GPIRT_DIF_GROUP_NFIELDS]; /* G x m each */
+    double*    focal[GPIRT_DIF_FOCAL_NFIELDS]; /* G x m each, row 0 NaN */
+    void*      raw[GPIRT_DIF_NRAW];            /* the raw arrays, in the order and with the types above */
+    int64_t*   flagged_items;                  /* top */
+    int64_t*   flagged_groups;                 /* top */
+    double*    flagged_ppp_mh_mid;             /* top */
+    int64_t    n, m, B;                        /* out */
+    int64_t    dif_draws, dif_skipped;         /* out */
+    int64_t    group_size[GPIRT_DIF_MAX_G];    /* out: the members of each group (0 beyond G) */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_ppc_dif;
+/* Stage API.  ppc_dif_enable(G, groups, h, cuts, on != 0) allocates and zeroes the state on a sampler with ppc_enable on
+ * (GPIRT_E_ARG, with a message, without it, for n > GPIRT_DIF_MAX_N, for G outside 2..4, a code outside -1 .. G - 1, an empty group
+ * and for cuts that break the bins' rule; on = 0 frees it, groups and cuts may then be NULL; ppc_enable called again frees it
+ * too).  From then on every ppc_accumulate also adds the draw to the block.  ppc_dif_get copies one array by name to the host,
+ * `bytes` its exact size: every finished array by the lower-case name above (double), the raw arrays by theirs, "counts" (int64:
+ * dif_draws, dif_skipped), "cuts" (int64, h), "groups" (int8, n), "group_size" (int64, 4) and, of the last COUNTED draw, "cell"
+ * (uint8, n), "tN", "tT", "tR" (int32, G x B x m), "tE", "tV" (the raw uint64 fixed-point sums, G x B x m) and "stats" (double,
+ * 8 x G x m: num(T), den(T), num(R), den(R), STD(T), STD(R) -- NaN for group 0, the STDs NaN without a common bin --, X2_g(T), X2_g(R)).
+ * ppc_dif_state returns the ONE device block of its own: a header of 8 int64 -- n, m, layout version (1), dif_draws, dif_skipped,
+ * item0, B, the tag 0x31464944 ("DIF1") --, 16 int64 with the cuts d_1 .. d_h (the rest 0), 8 int64 G, group_size[0..3], 0, 0, 0,
+ * the n group codes as int8, then the raw arrays in the order above; every array starts on a 16-byte boundary. */
+int gpirt_sampler_ppc_dif_enable(gpirt_sampler_t s, int G, const int32_t* groups, int h, const int* cuts, int on);
+int gpirt_sampler_ppc_dif_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_dif_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out);
+/* gpirt_mcmc_sumscore with the group-wise item fit (ppc and dif are required, dif->G, groups, h and cuts given; everything else from
+ * q on may be NULL): every chain also accumulates the block inside its ppc_accumulate -- under the item RNG from the verified
+ * checkpoint, as the pairs and the bins do --, pooled into dif with the reflection signs that the chains' alignment decides. */
+int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                   int sample_iterations, int burn_iterations, const double* h_prior_means,
+                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                   const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                   gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
+                   gpirt_ppc_dif* dif);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
