@@ -256,6 +256,22 @@ class Sumscore(C.Structure):
                 ("reserved", C.c_int64 * 4)]
 
 
+# two-form score equating (include/gpirt_hip.h GPIRT_EQUATE_*): the raw arrays of a state block in order, with their dtypes
+EQUATE_MAX_ITEMS, EQUATE_TAG, EQUATE_MAX_CUTS = 2048, 0x45545145, 8
+EQUATE_RAW = (("joint_sum", "f8"), ("pix_sum", "f8"), ("pix_sumsq", "f8"), ("piy_sum", "f8"), ("piy_sumsq", "f8"), ("eyx_sum", "f8"),
+              ("eyx_sumsq", "f8"), ("exy_sum", "f8"), ("exy_sumsq", "f8"), ("corr", "f8"), ("corr_terms", "f8"), ("mask_x", "u1"),
+              ("mask_y", "u1"), ("w", "f8"), ("last_joint", "f8"), ("last_pix", "f8"), ("last_piy", "f8"), ("last_eyx", "f8"),
+              ("last_exy", "f8"))
+
+
+class Equate(C.Structure):
+    """gpirt_equate (include/gpirt_hip.h): the two forms' masks (in), a host pointer per raw array (NULL: not wanted) and the
+    counters."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("raw", C.c_void_p * len(EQUATE_RAW)), ("m", C.c_int64), ("Mx", C.c_int64),
+                ("My", C.c_int64), ("draws", C.c_int64), ("skipped", C.c_int64), ("corr_draws", C.c_int64),
+                ("corr_skipped", C.c_int64), ("eq_clamped", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -432,6 +448,17 @@ SIGNATURES = {
                                C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
                                C.POINTER(Sumscore), C.POINTER(PpcDif)]),
+    "gpirt_sampler_equate_enable": (_i32, [_vp, _vp, _vp, _i32]),
+    "gpirt_sampler_equate_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_equate_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_equate_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_equate_state_bytes": (_i32, [_i64, _i64, _i64, C.POINTER(_i64)]),
+    "gpirt_equate_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Equate)]),
+    "gpirt_mcmc_equate": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                  C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
+                                  C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

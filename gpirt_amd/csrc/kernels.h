@@ -650,6 +650,43 @@ void sumscore_free(SumscoreState* s);
 int launch_sumscore_accumulate(hipStream_t stream, SumscoreState* s, const double* fstar);   // fstar: N x m (ld N) on the device
 int sumscore_get(hipStream_t stream, SumscoreState* s, const char* name, void* h_out, int64_t bytes);
 int sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_sumscore* out);
+// one form's recursion for other blocks (equate.hip), the very kernels of launch_sumscore_accumulate: the (p, q) table of the
+// form's columns (1001 x steps pairs, steps = sumscore_steps(M); a NaN raises ctl[0]), then the rows A (`last`, 1001 x (M + 1)),
+// `joint` += w_k A (NULL: not kept), T and V; then pi in sumscore_pi_kernel's order.  All do nothing once ctl[0] is set.
+int64_t sumscore_steps(int64_t M);
+int launch_sumscore_table(hipStream_t stream, const double* fstar, const int* cols, int M, int steps, double* tab, int* ctl);
+int launch_sumscore_rows(hipStream_t stream, const double* tab, int M, int steps, const double* w, const int* ctl, double* last,
+                         double* joint, double* T, double* V);
+int launch_sumscore_pi(hipStream_t stream, const double* last, const double* w, int M, const int* ctl, double* last_pi,
+                       double* pi_sum, double* pi_sumsq);
+
+// equate.hip: the joint distribution of the sum scores on two disjoint forms, one f* draw at a time (gpirt_sampler_equate_*,
+// gpirt_mcmc_equate; include/gpirt_hip.h, "Two-form score equating").  The state is ONE device block of 8-byte words: a header of
+// EQUATE_HEADER_WORDS int64 (tag, layout version, m, M_X, M_Y, N = 1001, draws, skipped, corr_draws, corr_skipped, eq_clamped,
+// 0 ... -- the five counters are kept by the kernels), then the GPIRT_EQUATE_* arrays in order, each on a 16-byte boundary.  Beside
+// it the state owns each form's (p, q) table, A_X, its weighted copy and A_Y (1024 x (M + 1) each: the rows beyond 1001 are the
+// product's zero padding), T and V of both forms, the forms' column indices and the control words (skip, go).
+constexpr int EQUATE_LAYOUT_VERSION = 1;
+constexpr int EQUATE_HEADER_WORDS = 16;
+constexpr int64_t EQUATE_TAG = 0x45545145;            // "EQTE"
+struct EquateLayout { int64_t off[GPIRT_EQUATE_NARRAYS]; int64_t words; };
+EquateLayout equate_layout(int64_t m, int64_t Mx, int64_t My);
+struct EquateState {
+    bool on = false;
+    int64_t m = 0, Mx = 0, My = 0, steps_x = 0, steps_y = 0;
+    uint64_t* block = nullptr;
+    double *tab_x = nullptr, *tab_y = nullptr, *AX = nullptr, *WX = nullptr, *AY = nullptr, *TV = nullptr;
+    int *cols_x = nullptr, *cols_y = nullptr, *ctl = nullptr;
+    std::vector<void*> allocs;
+};
+// both masks: m bytes; refuses a missing mask, an overlap (naming the first shared column), an empty form and more than
+// GPIRT_EQUATE_MAX_ITEMS items in a form
+int equate_check(int64_t m, const unsigned char* mask_x, const unsigned char* mask_y, int64_t* Mx_out, int64_t* My_out);
+int equate_alloc(hipStream_t stream, EquateState* s, int64_t m, const unsigned char* mask_x, const unsigned char* mask_y);
+void equate_free(EquateState* s);
+int launch_equate_accumulate(gpirt_handle_t h, hipStream_t stream, EquateState* s, const double* fstar);   // fstar: N x m (ld N)
+int equate_get(hipStream_t stream, EquateState* s, const char* name, void* h_out, int64_t bytes);
+int equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out);
 
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi

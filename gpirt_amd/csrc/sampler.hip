@@ -145,6 +145,7 @@ struct gpirt_sampler_s {
     ShapeState shape;                 // IRF shape posteriors (gpirt_sampler_shape_enable; on: draw_fstar also stores gbar)
     ScoreState score;                 // scoring new respondents (gpirt_sampler_score_enable; on == false: off)
     SumscoreState sumscore;           // sum-score posteriors (gpirt_sampler_sumscore_enable; on == false: off)
+    EquateState equate;               // two-form score equating (gpirt_sampler_equate_enable; on == false: off)
 };
 
 namespace {
@@ -1210,6 +1211,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     rank_free(&s->rank);
     shape_free(&s->shape);
     sumscore_free(&s->sumscore);
+    equate_free(&s->equate);
     score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -1870,6 +1872,62 @@ int gpirt_sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_st
     return sumscore_combine(h, chains, d_states, signs, out);
 }
 
+// ---- two-form score equating (equate.hip) on the stage API ----------------------------------------------------------------
+static int equate_needs_on(gpirt_sampler_t s)
+{
+    if (s->equate.on) return 0;
+    set_error("the score equating is not enabled (gpirt_sampler_equate_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_equate_enable(gpirt_sampler_t s, const unsigned char* mask_x, const unsigned char* mask_y, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) GP_TRY(equate_check(s->m, mask_x, mask_y, nullptr, nullptr));   // refused before the old state goes
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // a kernel still running on the old accumulators
+    equate_free(&s->equate);
+    if (!on) return 0;
+    const int rc = equate_alloc(s->h->stream, &s->equate, s->m, mask_x, mask_y);
+    if (rc) equate_free(&s->equate);
+    return rc;
+}
+
+int gpirt_sampler_equate_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(equate_needs_on(s));
+    return launch_equate_accumulate(s->h, s->h->stream, &s->equate, s->fstar);
+}
+
+int gpirt_sampler_equate_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(equate_needs_on(s));
+    return equate_get(s->h->stream, &s->equate, name, h_out, bytes);
+}
+
+int gpirt_sampler_equate_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(equate_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // the header's counters are the kernels'
+    *d_state = s->equate.block;
+    *bytes = equate_layout(s->m, s->equate.Mx, s->equate.My).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_equate_state_bytes(int64_t m, int64_t Mx, int64_t My, int64_t* bytes)
+{
+    GP_ARG(m > 0 && Mx >= 1 && My >= 1 && Mx + My <= m && Mx <= GPIRT_EQUATE_MAX_ITEMS && My <= GPIRT_EQUATE_MAX_ITEMS && bytes);
+    *bytes = equate_layout(m, Mx, My).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out)
+{
+    return equate_combine(h, chains, d_states, out);
+}
+
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
 static int score_needs_on(gpirt_sampler_t s)
 {
@@ -2220,6 +2278,8 @@ struct ChainRun {
     SumscoreState* keep_sumscore;     // gpirt_mcmc_sumscore: ... and the sum-score posteriors (the form's mask in `sumscore`)
     const gpirt_sumscore* sumscore;
     const gpirt_ppc_dif* dif;         // gpirt_mcmc_dif: ... and the group-wise item fit with these groups and cuts (inside keep_ppc)
+    EquateState* keep_equate;         // gpirt_mcmc_equate: ... and the two-form score equating (the forms' masks in `equate`)
+    const gpirt_equate* equate;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2293,6 +2353,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_sumscore = std::move(s->sumscore);
                 s->sumscore = SumscoreState{};
             }
+            if (cr->keep_equate) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_equate = std::move(s->equate);
+                s->equate = EquateState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -2329,6 +2394,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && shape) rc = gpirt_sampler_shape_enable(s, cr->shape->k_half, cr->shape->tols, cr->shape->n_tols, 1);
     const bool sumscore = cr && cr->keep_sumscore;
     if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, cr->sumscore->items, 1);
+    const bool equate = cr && cr->keep_equate;
+    if (!rc && equate) rc = gpirt_sampler_equate_enable(s, cr->equate->x, cr->equate->y, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2347,6 +2414,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc && score) rc = gpirt_sampler_score_accumulate(s);         // nor does the scoring (the live f*)
                 if (!rc && shape) rc = gpirt_sampler_shape_accumulate(s);         // nor the shapes (the step's gbar)
                 if (!rc && sumscore) rc = gpirt_sampler_sumscore_accumulate(s);   // nor the sum scores (the live f*)
+                if (!rc && equate) rc = gpirt_sampler_equate_accumulate(s);       // nor the equating (the live f*)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -2443,6 +2511,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (score) GP_TRY(launch_score_accumulate(h, h->stream, &s->score, d + off_fstar));   // the slot's f*
         if (shape) GP_TRY(launch_shape_accumulate(h->stream, &s->shape, d + off_gbar));       // the slot's gbar
         if (sumscore) GP_TRY(launch_sumscore_accumulate(h->stream, &s->sumscore, d + off_fstar));   // the slot's f*
+        if (equate) GP_TRY(launch_equate_accumulate(h, h->stream, &s->equate, d + off_fstar));      // the slot's f*
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2581,7 +2650,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
                       gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
-                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr)
+                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr,
+                      gpirt_equate* equate = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2679,6 +2749,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_TRY(dif_check_groups(n, dif->G, dif->groups, nullptr));
         GP_TRY(bin_check_cuts(dif->h, dif->cuts));
     }
+    if (equate) {
+        GP_ARG(equate->reserved[0] == 0 && equate->reserved[1] == 0 && equate->reserved[2] == 0 && equate->reserved[3] == 0);
+        GP_TRY(equate_check(m, equate->x, equate->y, nullptr, nullptr));
+    }
     const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
     const gpirt_ppc_dif dif_in = dif ? *dif : gpirt_ppc_dif{};
     const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
@@ -2691,6 +2765,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     std::vector<ScoreState> keep_score(score ? (size_t)chains : 0);
     std::vector<ShapeState> keep_shape(shape ? (size_t)chains : 0);
     std::vector<SumscoreState> keep_sumscore(sumscore ? (size_t)chains : 0);
+    std::vector<EquateState> keep_equate(equate ? (size_t)chains : 0);
     const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
@@ -2703,7 +2778,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                            ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
                            score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
                            bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
-                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr };
+                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr,
+                           equate ? &keep_equate[(size_t)c] : nullptr, equate };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2753,7 +2829,12 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         rc = sumscore_combine(h, chains, st.data(), sg.data(), sumscore);
     }
     for (auto& k : keep_shape) shape_free(&k);
+    if (!rc && equate) {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_equate[(size_t)c].block;
+        rc = equate_combine(h, chains, st.data(), equate);
+    }
     for (auto& k : keep_sumscore) sumscore_free(&k);
+    for (auto& k : keep_equate) equate_free(&k);
     for (auto& k : keep_ppc) ppc_free(&k);
     for (auto& k : keep_rank) rank_free(&k);
     for (auto& k : keep_score) score_free(&k);
@@ -2962,6 +3043,25 @@ int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_thet
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif);
+}
+
+// ---- the two-form score equating ------------------------------------------------------------------------------------------------------
+int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                      const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                      gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                      gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
+                      gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate)
+{
+    GP_ARG(opts && equate);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_equate needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate);
 }
 
 }  // extern "C"

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64) void sumscore_row_kernel(const double2* __restr
     for (int s = lane; s <= M; s += 64) {                         // s <= M < 64 R
         const double a = row[s];
         last[at + s] = a;
-        joint[at + s] += wk * a;
+        if (joint) joint[at + s] += wk * a;                       // (NULL: a caller that keeps no weighted copy, equate.hip's form Y)
     }
     if (lane == 0) { T[k] = Tk; V[k] = Vk; }
 }
@@ -282,6 +282,8 @@ int sumscore_check(int64_t m, const unsigned char* mask, int64_t* M_out)
     return 0;
 }
 
+int64_t sumscore_steps(int64_t M) { return (M + SS_STEP_PAD - 1) / SS_STEP_PAD * SS_STEP_PAD; }
+
 void sumscore_free(SumscoreState* p)
 {
     for (void* q : p->allocs) hipFree(q);
@@ -294,7 +296,7 @@ int sumscore_alloc(hipStream_t st, SumscoreState* p, int64_t m, const unsigned c
     GP_TRY(sumscore_check(m, mask, &M));
     const SumscoreLayout L = sumscore_layout(m, M);
     p->m = m; p->M = M;
-    p->steps = (M + SS_STEP_PAD - 1) / SS_STEP_PAD * SS_STEP_PAD;
+    p->steps = sumscore_steps(M);
     auto get = [&](void** q, size_t bytes) -> int {
         GP_HIP(hipMalloc(q, bytes));
         p->allocs.push_back(*q);
@@ -325,28 +327,48 @@ int sumscore_alloc(hipStream_t st, SumscoreState* p, int64_t m, const unsigned c
     return 0;
 }
 
+int launch_sumscore_table(hipStream_t st, const double* fstar, const int* cols, int M, int steps, double* tab, int* ctl)
+{
+    hipLaunchKernelGGL(sumscore_table_kernel, dim3((SS_N + SS_TILE_K - 1) / SS_TILE_K, (unsigned)(steps / SS_TILE_J)), dim3(256), 0, st,
+                       fstar, cols, M, steps, reinterpret_cast<double2*>(tab), ctl);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sumscore_rows(hipStream_t st, const double* tab_, int M, int steps, const double* w, const int* ctl, double* last,
+                         double* joint, double* T, double* V)
+{
+    const double2* tab = reinterpret_cast<const double2*>(tab_);
+    if (M + 1 <= 17 * 64)
+        hipLaunchKernelGGL(sumscore_row_kernel<17>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, ctl, last, joint, T, V);
+    else if (M + 1 <= 33 * 64)
+        hipLaunchKernelGGL(sumscore_row_kernel<33>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, ctl, last, joint, T, V);
+    else
+        hipLaunchKernelGGL(sumscore_row_kernel<65>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, ctl, last, joint, T, V);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sumscore_pi(hipStream_t st, const double* last, const double* w, int M, const int* ctl, double* last_pi, double* pi_sum,
+                       double* pi_sumsq)
+{
+    hipLaunchKernelGGL(sumscore_pi_kernel, dim3((unsigned)((M + 1 + SS_PI_THREADS - 1) / SS_PI_THREADS)), dim3(SS_PI_THREADS), 0, st,
+                       last, w, M, ctl, last_pi, pi_sum, pi_sumsq);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
 int launch_sumscore_accumulate(hipStream_t st, SumscoreState* p, const double* fstar)
 {
     const SumscoreLayout L = sumscore_layout(p->m, p->M);
     auto f64 = [&](int k) { return reinterpret_cast<double*>(p->block + L.off[k]); };
     const int M = (int)p->M, steps = (int)p->steps;
-    double2* tab = reinterpret_cast<double2*>(p->tab);
     const double* w = f64(GPIRT_SUMSCORE_W);
     GP_HIP(hipMemsetAsync(p->ctl, 0, sizeof(int), st));
-    hipLaunchKernelGGL(sumscore_table_kernel, dim3((SS_N + SS_TILE_K - 1) / SS_TILE_K, (unsigned)(steps / SS_TILE_J)), dim3(256), 0, st,
-                       fstar, p->cols, M, steps, tab, p->ctl);
-    GP_HIP(hipGetLastError());
+    GP_TRY(launch_sumscore_table(st, fstar, p->cols, M, steps, p->tab, p->ctl));
     double *last = f64(GPIRT_SUMSCORE_LAST), *joint = f64(GPIRT_SUMSCORE_JOINT_SUM);
-    if (M + 1 <= 17 * 64)
-        hipLaunchKernelGGL(sumscore_row_kernel<17>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, p->ctl, last, joint, p->T, p->V);
-    else if (M + 1 <= 33 * 64)
-        hipLaunchKernelGGL(sumscore_row_kernel<33>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, p->ctl, last, joint, p->T, p->V);
-    else
-        hipLaunchKernelGGL(sumscore_row_kernel<65>, dim3(SS_N), dim3(64), 0, st, tab, M, steps, w, p->ctl, last, joint, p->T, p->V);
-    GP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(sumscore_pi_kernel, dim3((unsigned)((M + 1 + SS_PI_THREADS - 1) / SS_PI_THREADS)), dim3(SS_PI_THREADS), 0, st,
-                       last, w, M, p->ctl, f64(GPIRT_SUMSCORE_LAST_PI), f64(GPIRT_SUMSCORE_PI_SUM), f64(GPIRT_SUMSCORE_PI_SUMSQ));
-    GP_HIP(hipGetLastError());
+    GP_TRY(launch_sumscore_rows(st, p->tab, M, steps, w, p->ctl, last, joint, p->T, p->V));
+    GP_TRY(launch_sumscore_pi(st, last, w, M, p->ctl, f64(GPIRT_SUMSCORE_LAST_PI), f64(GPIRT_SUMSCORE_PI_SUM), f64(GPIRT_SUMSCORE_PI_SUMSQ)));
     hipLaunchKernelGGL(sumscore_fin_kernel, dim3(1), dim3(SS_FIN_THREADS), 0, st, p->T, p->V, w, p->ctl, f64(GPIRT_SUMSCORE_TCC_SUM),
                        f64(GPIRT_SUMSCORE_TCC_SUMSQ), f64(GPIRT_SUMSCORE_VAR_SUM), f64(GPIRT_SUMSCORE_REL),
                        reinterpret_cast<int64_t*>(p->block));

@@ -278,6 +278,11 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the sum-score posteriors are not offered for item shards (the recursion runs over "
                          "all items of the form, and each rank holds its own f* columns)")
 
+    # -- two-form score equating (gpirt_amd.equate): both forms' recursions run over items that live on different ranks
+    def equate_enable(self, x=None, y=None, on=True):
+        raise ValueError("ShardedSampler: the score equating is not offered for item shards (each form's recursion runs over "
+                         "all of its items, and each rank holds its own f* columns)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

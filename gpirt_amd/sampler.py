@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None, ranks=None, score=None, shape=None, sumscore=None):
+              ppc=None, ranks=None, score=None, shape=None, sumscore=None, equate=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -165,6 +165,19 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       NaN in a form column is skipped whole), rel_draws, rel_skipped, items and the raw accumulators.  Memory at M = 1024:
       33 MB per chain.  Nothing is drawn: the chain is untouched under both RNG contracts.  sumscore=None leaves every other
       path as it is.
+    equate: dict(x=items_x, y=items_y, probs=(0.025, 0.5, 0.975), cuts=((cx, cy), ...)) relates the sum scores on TWO disjoint
+      forms (gpirt_mcmc_equate, gpirt_amd.equate): after every sampling iteration the device runs the sum-score recursion once
+      per form and contracts the two score tables over the grid in one fp64 matrix-core product, the draw's joint distribution
+      of (S_X, S_Y) for a N(0, 1) population.  x, y: column indices or boolean masks over the PREPARED data's columns, each
+      non-empty, at most 2048 items, no column in both; cuts: up to 8 pairs of pass marks (a score >= the cut passes).  "equate"
+      holds joint ((M_X + 1) x (M_Y + 1)), x_dist, x_dist_sd, y_dist, y_dist_sd, the equipercentile equivalents y_of_x_mean,
+      y_of_x_sd (M_X + 1: an X score on Y's scale, posterior mean and sd over draws), x_of_y_mean, x_of_y_sd, the concordance
+      y_given_x ((M_X + 1) x (M_Y + 1)), y_given_x_mean, y_given_x_quantiles (len(probs) x (M_X + 1)), x_given_y, x_given_y_mean,
+      x_given_y_quantiles (rows of the pooled joint normalised once; NaN for a score without mass), corr_mean, corr_sd (the
+      correlation of the two scores, per draw), agreement, kappa (per cut, from the pooled joint), draws, skipped (a draw whose
+      f* holds a NaN in a column of either form is skipped whole), corr_draws, corr_skipped, eq_clamped, x_items, y_items and
+      the raw accumulators.  Memory at M_X = M_Y = 1024: 75 MB per chain.  Nothing is drawn: the chain is untouched under both
+      RNG contracts.  equate=None leaves every other path as it is.
     """
     from .ops import RStream
 
@@ -216,6 +229,9 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         sumscore = SS.parse(sumscore, m)
     else:
         sumscore = None
+    if equate is not None:
+        from . import equate as EQ
+        equate = EQ.parse(equate, m)
     pairs = bins = dif = None
     if isinstance(ppc, dict):
         from . import ppc as P
@@ -242,10 +258,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
             dif = dict(groups=codes, G=G, cuts=P.check_cuts(P.DEFAULT_CUTS if dif.get("cuts") is None else dif["cuts"]),
                        top=P.check_dif_top(dif.get("top", P.DEFAULT_DIF_TOP)))
         ppc = True
-    if quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None:
+    if (quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None
+            or equate is not None):
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif, equate)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -379,7 +396,7 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None):
+                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None, equate=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
@@ -391,7 +408,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     posteriors of the item response curves (with or without everything else).  sumscore (gpirt_amd.sumscore.parse's dict):
     gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else).  dif
     (dict(groups, G, cuts, top)): gpirt_mcmc_dif, the same chains with the group-wise item fit inside the PPC (with or without
-    everything else)."""
+    everything else).  equate (gpirt_amd.equate.parse's dict): gpirt_mcmc_equate, the same chains with the two-form score equating
+    (with or without everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -454,7 +472,7 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if shape is not None or sumscore is not None or dif is not None:
+    if shape is not None or sumscore is not None or dif is not None or equate is not None:
         from . import shape as SH
         from . import score as SC
         sh = ss = None
@@ -479,8 +497,14 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
                 C.byref(rk) if ranks is not None else None,
                 _ptr(score["data"]) if score is not None else None,
                 score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq))
+        df = None
         if dif is not None:
             df, dfarr = P.dif_struct(m, dif["G"], dif["cuts"], dif["top"], groups=dif["groups"])
+        if equate is not None:
+            from . import equate as EQ
+            eq, eqarr = EQ.struct(m, int(equate["mask_x"].sum()), int(equate["mask_y"].sum()), equate["mask_x"], equate["mask_y"])
+            rc = lib.gpirt_mcmc_equate(*args, ref(sh), ref(ss), ref(df), C.byref(eq))
+        elif dif is not None:
             rc = lib.gpirt_mcmc_dif(*args, ref(sh), ref(ss), C.byref(df))
         elif ss is not None:
             rc = lib.gpirt_mcmc_sumscore(*args, ref(sh), C.byref(ss))
@@ -568,6 +592,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["shape"] = SH.result(sh, sharr, shape["probs"], shape["top"])
     if sumscore is not None:
         out["sumscore"] = SS.result(ss, ssarr, sumscore["probs"], y)
+    if equate is not None:
+        out["equate"] = EQ.result(eq, eqarr, equate["probs"], equate["cuts"])
     return out
 
 
@@ -1243,6 +1269,60 @@ class Sampler:
         over its own state; sign = -1 reverses its k axis; y (the data): also the observed score histogram."""
         from . import sumscore as SS
         return SS.combine(self.handle, [self], signs=[sign], probs=probs, y=y)
+
+    # -- two-form score equating (include/gpirt_hip.h gpirt_sampler_equate_*, gpirt_amd.equate)
+    def equate_enable(self, x=None, y=None, on=True):
+        """Allocate and zero the equating accumulators for the disjoint forms `x` and `y` (column indices or boolean masks;
+        1..2048 items each -- an empty form, a longer one and a column in both are ValueErrors).  on=False frees them."""
+        if not on:
+            check(self.lib.gpirt_sampler_equate_enable(self._s, None, None, 0))
+            self._equate_M = (0, 0)
+            return
+        from . import equate as EQ
+        mx, my = EQ.form_masks(x, y, self.m)
+        check(self.lib.gpirt_sampler_equate_enable(self._s, C.c_void_p(mx.ctypes.data), C.c_void_p(my.ctypes.data), 1))
+        self._equate_M = (int(mx.sum()), int(my.sum()))
+
+    def equate_accumulate(self):
+        """Add the current "fstar" (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_equate_accumulate")
+
+    def equate_get(self, name: str) -> np.ndarray:
+        """One array by name: joint_sum, last_joint ((M_X + 1) x (M_Y + 1)), pix_sum, pix_sumsq, last_pix, eyx_sum, eyx_sumsq,
+        last_eyx (M_X + 1), piy_sum, piy_sumsq, last_piy, exy_sum, exy_sumsq, last_exy (M_Y + 1), corr (2), corr_terms (5), w
+        (1001), mask_x, mask_y (uint8, m) and counts (int64: draws, skipped, corr_draws, corr_skipped, eq_clamped)."""
+        from . import equate as EQ
+        Mx, My = getattr(self, "_equate_M", (0, 0))                      # (not enabled: the library refuses the call)
+        dts = dict(_lib.EQUATE_RAW)
+        if name in dts:
+            out = np.empty(EQ._raw_shape(name, self.m, Mx, My), dtype=np.dtype(dts[name]))
+        elif name == "counts":
+            out = np.empty(5, dtype=np.int64)
+        else:
+            out = np.empty(0)
+        check(self.lib.gpirt_sampler_equate_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def equate_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the equating accumulators: what
+        gpirt_amd.equate.combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_equate_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def equate(self, probs=(0.025, 0.5, 0.975), cuts=None) -> dict:
+        """Every finished output of this sampler's accumulators (gpirt_amd.equate.finish's dict): gpirt_equate_combine over
+        its own state."""
+        from . import equate as EQ
+        return EQ.combine(self.handle, [self], probs=probs, cuts=cuts)
 
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):

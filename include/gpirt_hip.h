@@ -1368,6 +1368,114 @@ int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_thet
                    gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
                    gpirt_ppc_dif* dif);
 
+/* ------------------------------------------------------ Two-form score equating: joint table, concordance ------------- */
+/* The sum-score section answers every question about ONE form's score.  This one is about TWO forms at once: how scores on
+ * form X and form Y relate (IRT observed-score equating), what somebody who scored s on X scores on Y (the concordance table),
+ * how well the two forms agree on a pass / fail decision, how two subscores correlate.  All follow from the joint distribution
+ * of the two scores for the N(0, 1) population, per draw
+ *     J[s, t] = sum_k w_k P(S_X = s | theta_k) P(S_Y = t | theta_k),
+ * a product of two recursions under ONE draw integrated over theta: a mean of a product is not a product of means, so neither
+ * two sum-score states (they keep the marginals) nor the IRFs determine it.  Library version 116.
+ * The two FORMS are non-empty DISJOINT sets of item columns, each named by a mask of m bytes; 1 <= M_X, M_Y <=
+ * GPIRT_EQUATE_MAX_ITEMS.  They must be disjoint because only then do the scores factorise given theta (anchor designs are out
+ * of scope; so is true-score equating: a GP-IRT test characteristic curve need not be monotone, so it has no inverse).
+ * Per draw, with the grid, the weights w_k (gpirt_sumscore_grid_weights, stored in the state), p, q and the recursion of the
+ * sum-score section, each form's items in ascending column order, all in fp64:
+ *   A_X[k, s], T_X[k], V_X[k] and A_Y[k, t], T_Y[k], V_Y[k]   exactly as the sum-score section forms A, T and V for each form;
+ *   pi_X[s]   = sum_k w_k A_X[k, s], ascending k (the sum-score pi); pi_Y[t] likewise;
+ *   J[s, t]   = sum_k (w_k A_X[k, s]) A_Y[k, t]: the weighted left operand is rounded once, the contraction is ONE product
+ *               through the library's fp64 matrix-core GEMM, never split along k, so its order is fixed and the result is the
+ *               same from run to run; both operands are padded along k to 1024 with zero rows, which add exact zeros.  The order
+ *               of summation inside the product is the GEMM core's: any order of 1001 non-negative terms;
+ *   F_X, F_Y  the cumulative sums of pi_X, pi_Y in ascending score;
+ *   e_YX[s]   the equipercentile equivalent of the X score s on Y's scale (Kolen and Brennan's percentile-rank form), s = 0 ..
+ *               M_X: P = F_X[s - 1] + pi_X[s] / 2 (F[-1] = 0), t* the smallest t with F_Y[t] > P,
+ *               e_YX[s] = (t* - 0.5) + (P - F_Y[t* - 1]) / pi_Y[t*]; if no t qualifies e_YX[s] = M_Y + 0.5 and `eq_clamped`
+ *               counts the cell.  e_XY[t], t = 0 .. M_Y, is the same with the roles swapped;
+ *   r         with a_X = sum_k w_k T_X[k], b_X = sum_k w_k (V_X[k] + T_X[k] T_X[k]), a_Y and b_Y likewise and c = sum_k w_k
+ *               (T_X[k] T_Y[k]), the five sums in ascending k: r = (c - a_X a_Y) / sqrt((b_X - a_X a_X) (b_Y - a_Y a_Y)), the
+ *               correlation of the two scores.
+ * A draw whose f* holds a NaN in a column of EITHER form is skipped WHOLE (`skipped` += 1, nothing else changes; the decision is
+ * made on the device before anything is touched); a NaN in a column outside both forms is ignored; +-inf is fine (a point mass).
+ * Every other draw adds 1 to `draws`.  A counted draw whose two variances b - a a are not both > 0 adds nothing to corr and 1 to
+ * `corr_skipped`; any other adds 1 to `corr_draws`.
+ * The accumulators:
+ *   joint_sum[s, t] += J[s, t]           ((M_X + 1) x (M_Y + 1), cell (s, t) at [s (M_Y + 1) + t])
+ *   pix_sum[s] += pi_X[s], pix_sumsq[s] += pi_X[s]^2;  piy_sum, piy_sumsq likewise
+ *   eyx_sum[s] += e_YX[s], eyx_sumsq[s] += e_YX[s]^2 (M_X + 1);  exy_sum, exy_sumsq (M_Y + 1)
+ *   corr[0] += r, corr[1] += r r;  corr_terms = (a_X, b_X, a_Y, b_Y, c) of the last counted draw
+ *   last_joint, last_pix, last_piy, last_eyx, last_exy = J, pi_X, pi_Y, e_YX, e_XY of the last counted draw.
+ * THE JOINT, NOT THE RATIO, as in the sum-score section: the concordance P(S_Y = t | S_X = s), its mean and quantiles, the
+ * decision agreement and kappa at a pair of cut scores are linear in the joint or a ratio of it; the host computes them from the
+ * pooled joint_sum, normalised once.  A row without mass gives NaN.
+ * Every accumulator cell is owned by one thread: no atomics, a fixed order, byte-identical state blocks from run to run.
+ * REFLECTION.  theta -> -theta changes none of these quantities: every sum runs over the whole symmetric grid.  So
+ * gpirt_equate_combine takes no signs; pooling C chains adds the doubles and the counters in chain order, and the last_* arrays
+ * and corr_terms are the last state's.  States with another m, other forms or other grid weights are refused.
+ * Nothing is drawn: with the accumulators on, the chain, the IRFs, R's stream position and every other block's state are bit for
+ * bit what they are without.
+ * Device memory per state at M_X = M_Y = 1024: joint_sum and last_joint 8.4 MB each, the two A tables and the weighted copy
+ * 8.4 MB each, the two (p, q) tables 16.4 MB each. */
+#define GPIRT_EQUATE_MAX_ITEMS        2048
+/* the raw arrays of a state block, in the block's order */
+#define GPIRT_EQUATE_JOINT_SUM        0       /* double [M_X + 1][M_Y + 1] */
+#define GPIRT_EQUATE_PIX_SUM          1       /* double [M_X + 1] */
+#define GPIRT_EQUATE_PIX_SUMSQ        2       /* double [M_X + 1] */
+#define GPIRT_EQUATE_PIY_SUM          3       /* double [M_Y + 1] */
+#define GPIRT_EQUATE_PIY_SUMSQ        4       /* double [M_Y + 1] */
+#define GPIRT_EQUATE_EYX_SUM          5       /* double [M_X + 1] */
+#define GPIRT_EQUATE_EYX_SUMSQ        6       /* double [M_X + 1] */
+#define GPIRT_EQUATE_EXY_SUM          7       /* double [M_Y + 1] */
+#define GPIRT_EQUATE_EXY_SUMSQ        8       /* double [M_Y + 1] */
+#define GPIRT_EQUATE_CORR             9       /* double [2]: sum r, sum r^2 */
+#define GPIRT_EQUATE_CORR_TERMS       10      /* double [5]: a_X, b_X, a_Y, b_Y, c of the last counted draw */
+#define GPIRT_EQUATE_MASK_X           11      /* unsigned char [m]: 1 where the item is in form X */
+#define GPIRT_EQUATE_MASK_Y           12      /* unsigned char [m] */
+#define GPIRT_EQUATE_W                13      /* double [1001]: the grid weights */
+#define GPIRT_EQUATE_LAST_JOINT       14      /* double [M_X + 1][M_Y + 1] */
+#define GPIRT_EQUATE_LAST_PIX         15      /* double [M_X + 1] */
+#define GPIRT_EQUATE_LAST_PIY         16      /* double [M_Y + 1] */
+#define GPIRT_EQUATE_LAST_EYX         17      /* double [M_X + 1] */
+#define GPIRT_EQUATE_LAST_EXY         18      /* double [M_Y + 1] */
+#define GPIRT_EQUATE_NARRAYS          19
+/* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
+typedef struct gpirt_equate {
+    const unsigned char* x;                    /* in (gpirt_mcmc_equate): m bytes, non-zero = in form X */
+    const unsigned char* y;                    /* in (gpirt_mcmc_equate): m bytes, non-zero = in form Y */
+    void*      raw[GPIRT_EQUATE_NARRAYS];
+    int64_t    m, Mx, My;                      /* out */
+    int64_t    draws, skipped, corr_draws, corr_skipped, eq_clamped;   /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_equate;
+/* Stage API.  equate_enable(mask_x, mask_y, on != 0) allocates and zeroes the state for the two forms (m bytes each, non-zero =
+ * in the form); GPIRT_E_ARG with a message for a missing mask, an overlap (the first shared column is named), an empty form and
+ * more than GPIRT_EQUATE_MAX_ITEMS items, the old state is then kept; on = 0 frees it.  equate_accumulate adds the CURRENT f*
+ * (the sampler array "fstar") as one draw.  equate_get copies one array by name to the host, `bytes` its exact size: the
+ * lower-case names of the raw arrays ("joint_sum", "pix_sum", ..., "last_exy") and "counts" (int64: draws, skipped, corr_draws,
+ * corr_skipped, eq_clamped).  equate_state returns the ONE device block (valid until equate_enable is called again or the
+ * sampler goes): a header of 16 int64 -- the tag 0x45545145 ("EQTE"), the layout version (1), m, M_X, M_Y, N = 1001, draws,
+ * skipped, corr_draws, corr_skipped, eq_clamped, 0 ... -- then the raw arrays in the order above, every array starting on a
+ * 16-byte boundary; gpirt_equate_state_bytes gives its size. */
+int gpirt_sampler_equate_enable(gpirt_sampler_t s, const unsigned char* mask_x, const unsigned char* mask_y, int on);
+int gpirt_sampler_equate_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_equate_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_equate_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_equate_state_bytes(int64_t m, int64_t Mx, int64_t My, int64_t* bytes);
+int gpirt_equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out);
+/* gpirt_mcmc_dif with the score equating (equate is required, both masks given; everything from q on, dif included, may be NULL;
+ * pairs, bins and dif need ppc as before): every chain also accumulates its f* after each sampling iteration -- under the item
+ * RNG from the verified checkpoint's f*, under R's stream right after the step --, pooled into equate in chain order (no signs:
+ * see REFLECTION above). */
+int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                      int sample_iterations, int burn_iterations, const double* h_prior_means,
+                      const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                      double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                      gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                      const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                      gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
+                      gpirt_ppc_dif* dif, gpirt_equate* equate);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
