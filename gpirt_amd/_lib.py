@@ -272,6 +272,25 @@ class Equate(C.Structure):
                 ("corr_skipped", C.c_int64), ("eq_clamped", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# PSIS-LOO (include/gpirt_hip.h GPIRT_LOO_*): the raw arrays of a state block in order, the pointwise outputs and the totals
+LOO_MAX_TAIL, LOO_MAX_TOP, LOO_TAG, LOO_KEY_MAX = 1024, 64, 0x4F4F4C50, 700.0
+LOO_RAW = (("keys", "f8"), ("evicted_sum", "f8"), ("evicted_sumsq", "f8"), ("p_sum", "f8"), ("count", "i4"), ("nonfinite", "i4"),
+           ("y", "i1"))
+LOO_POINTWISE = ("pareto_k", "elpd_loo", "n_eff", "lppd", "p_loo", "loo_p_yes")
+LOO_TOTALS = ("elpd_loo", "se_elpd_loo", "p_loo", "looic", "se_looic", "n_obs", "lppd", "k_threshold", "k_good", "k_bad",
+              "k_very_bad", "unsmoothed", "cells_incomplete", "elpd_mean")
+
+
+class Loo(C.Structure):
+    """gpirt_loo (include/gpirt_hip.h): tail and top (in), a host pointer per array (NULL: not wanted), the totals and the
+    counters."""
+    _fields_ = [("tail", C.c_int64), ("top", C.c_int64), ("raw", C.c_void_p * len(LOO_RAW)),
+                ("pointwise", C.c_void_p * len(LOO_POINTWISE)), ("item_elpd_loo", C.c_void_p),
+                ("respondent_elpd_loo", C.c_void_p), ("worst_index", C.c_void_p), ("worst_k", C.c_void_p),
+                ("totals", C.c_double * len(LOO_TOTALS)), ("n", C.c_int64), ("m", C.c_int64), ("T", C.c_int64), ("M", C.c_int64),
+                ("draws", C.c_int64), ("chains", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -459,6 +478,18 @@ SIGNATURES = {
                                   C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                   C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
                                   C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate)]),
+    "gpirt_sampler_loo_enable": (_i32, [_vp, _i64, _i32, _i32]),
+    "gpirt_sampler_loo_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_loo_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_loo_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_loo_tail_length": (_i32, [_i64, _i32, C.POINTER(_i64)]),
+    "gpirt_loo_state_bytes": (_i32, [_i64, _i64, _i64, C.POINTER(_i64)]),
+    "gpirt_loo_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Loo)]),
+    "gpirt_mcmc_loo": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                               C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                               C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
+                               C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate), C.POINTER(Loo)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

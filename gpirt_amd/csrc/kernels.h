@@ -688,6 +688,30 @@ int launch_equate_accumulate(gpirt_handle_t h, hipStream_t stream, EquateState* 
 int equate_get(hipStream_t stream, EquateState* s, const char* name, void* h_out, int64_t bytes);
 int equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out);
 
+// loo.hip: PSIS-LOO without stored draws (gpirt_sampler_loo_*, gpirt_mcmc_loo; include/gpirt_hip.h, "PSIS-LOO").  The state is
+// ONE device block of 8-byte words: a header of LOO_HEADER_WORDS int64 (tag, layout version, n, m, T, M, draws, chains, 0 ...
+// -- draws and chains are kept by the kernels), then the GPIRT_LOO_* arrays in order, each on a 16-byte boundary: the per-cell
+// min-heaps of the K = M + 1 largest keys (slot-major), the evicted sums, p_sum, the counters and a copy of y as bytes.
+constexpr int LOO_LAYOUT_VERSION = 1;
+constexpr int LOO_HEADER_WORDS = 16;
+constexpr int64_t LOO_TAG = 0x4F4F4C50;               // "PLOO"
+struct LooLayout { int64_t off[GPIRT_LOO_NARRAYS]; int64_t words; };
+LooLayout loo_layout(int64_t n, int64_t m, int64_t M);
+struct LooState {
+    bool on = false;
+    int64_t n = 0, m = 0, T = 0, M = 0;
+    uint64_t* block = nullptr;
+};
+// M from T and `tail` (0: the rule); refuses a tail outside 5 .. GPIRT_LOO_MAX_TAIL, M > GPIRT_LOO_MAX_TAIL and M >= T
+int loo_tail_length(int64_t T, int tail, int64_t* M_out);
+int loo_alloc(hipStream_t stream, LooState* s, int64_t n, int64_t m, int64_t T, int64_t M, const double* d_y);   // d_y: n x m
+void loo_free(LooState* s);
+int launch_loo_accumulate(hipStream_t stream, LooState* s, const double* f, const double* mu);    // f, mu: n x m on the device
+// `from`'s kept keys, sums and counters into `into` (both blocks of the same n, m, M: the callers check)
+int launch_loo_merge(hipStream_t stream, uint64_t* into, const uint64_t* from, int64_t n, int64_t m, int64_t M);
+int loo_get(hipStream_t stream, LooState* s, const char* name, void* h_out, int64_t bytes);
+int loo_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_loo* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

@@ -146,6 +146,7 @@ struct gpirt_sampler_s {
     ScoreState score;                 // scoring new respondents (gpirt_sampler_score_enable; on == false: off)
     SumscoreState sumscore;           // sum-score posteriors (gpirt_sampler_sumscore_enable; on == false: off)
     EquateState equate;               // two-form score equating (gpirt_sampler_equate_enable; on == false: off)
+    LooState loo;                     // PSIS-LOO (gpirt_sampler_loo_enable; on == false: off)
 };
 
 namespace {
@@ -1212,6 +1213,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     shape_free(&s->shape);
     sumscore_free(&s->sumscore);
     equate_free(&s->equate);
+    loo_free(&s->loo);
     score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -1928,6 +1930,69 @@ int gpirt_equate_combine(gpirt_handle_t h, int chains, const void* const* d_stat
     return equate_combine(h, chains, d_states, out);
 }
 
+// ---- PSIS-LOO (loo.hip) on the stage API -----------------------------------------------------------------------------------
+static int loo_needs_on(gpirt_sampler_t s)
+{
+    if (s->loo.on) return 0;
+    set_error("PSIS-LOO is not enabled (gpirt_sampler_loo_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_loo_enable(gpirt_sampler_t s, int64_t planned_total_draws, int tail, int on)
+{
+    GP_ARG(s && s->initialised);
+    int64_t M = 0;
+    if (on) GP_TRY(loo_tail_length(planned_total_draws, tail, &M));   // refused before the old state goes
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // a kernel still running on the old accumulators
+    loo_free(&s->loo);
+    if (!on) return 0;
+    const int rc = loo_alloc(s->h->stream, &s->loo, s->n, s->m, planned_total_draws, M, s->y);
+    if (rc) loo_free(&s->loo);
+    return rc;
+}
+
+int gpirt_sampler_loo_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(loo_needs_on(s));
+    return launch_loo_accumulate(s->h->stream, &s->loo, s->f, s->mu);
+}
+
+int gpirt_sampler_loo_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(loo_needs_on(s));
+    return loo_get(s->h->stream, &s->loo, name, h_out, bytes);
+}
+
+int gpirt_sampler_loo_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(loo_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // the header's counters are the kernels'
+    *d_state = s->loo.block;
+    *bytes = loo_layout(s->n, s->m, s->loo.M).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_loo_tail_length(int64_t T, int tail, int64_t* M)
+{
+    GP_ARG(M);
+    return loo_tail_length(T, tail, M);
+}
+
+int gpirt_loo_state_bytes(int64_t n, int64_t m, int64_t M, int64_t* bytes)
+{
+    GP_ARG(n > 0 && m > 0 && M >= 0 && M <= GPIRT_LOO_MAX_TAIL && bytes);
+    *bytes = loo_layout(n, m, M).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_loo_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_loo* out)
+{
+    return loo_combine(h, chains, d_states, out);
+}
+
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
 static int score_needs_on(gpirt_sampler_t s)
 {
@@ -2280,6 +2345,9 @@ struct ChainRun {
     const gpirt_ppc_dif* dif;         // gpirt_mcmc_dif: ... and the group-wise item fit with these groups and cuts (inside keep_ppc)
     EquateState* keep_equate;         // gpirt_mcmc_equate: ... and the two-form score equating (the forms' masks in `equate`)
     const gpirt_equate* equate;
+    LooState* keep_loo;               // gpirt_mcmc_loo: ... and PSIS-LOO (T = loo_T draws over all chains, `loo_tail` as given)
+    int64_t loo_T;
+    int loo_tail;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2358,6 +2426,11 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 *cr->keep_equate = std::move(s->equate);
                 s->equate = EquateState{};
             }
+            if (cr->keep_loo) {
+                GP_HIP(hipStreamSynchronize(h->stream));
+                *cr->keep_loo = s->loo;
+                s->loo = LooState{};
+            }
             return 0;
         }
         if (!sm) return 0;
@@ -2396,6 +2469,8 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, cr->sumscore->items, 1);
     const bool equate = cr && cr->keep_equate;
     if (!rc && equate) rc = gpirt_sampler_equate_enable(s, cr->equate->x, cr->equate->y, 1);
+    const bool loo = cr && cr->keep_loo;
+    if (!rc && loo) rc = gpirt_sampler_loo_enable(s, cr->loo_T, cr->loo_tail, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2415,6 +2490,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
                 if (!rc && shape) rc = gpirt_sampler_shape_accumulate(s);         // nor the shapes (the step's gbar)
                 if (!rc && sumscore) rc = gpirt_sampler_sumscore_accumulate(s);   // nor the sum scores (the live f*)
                 if (!rc && equate) rc = gpirt_sampler_equate_accumulate(s);       // nor the equating (the live f*)
+                if (!rc && loo) rc = gpirt_sampler_loo_accumulate(s);             // nor PSIS-LOO (the live f and mu)
             }
         }
         if (!rc) rc = gpirt_sampler_finish_irfs(s, S_it, h_irfs);
@@ -2512,6 +2588,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
         if (shape) GP_TRY(launch_shape_accumulate(h->stream, &s->shape, d + off_gbar));       // the slot's gbar
         if (sumscore) GP_TRY(launch_sumscore_accumulate(h->stream, &s->sumscore, d + off_fstar));   // the slot's f*
         if (equate) GP_TRY(launch_equate_accumulate(h, h->stream, &s->equate, d + off_fstar));      // the slot's f*
+        if (loo) GP_TRY(launch_loo_accumulate(h->stream, &s->loo, d + off_f, d + off_mu));          // the slot's f and mu
         if (!h_theta_draws && !h_beta_draws && !h_f_draws) return 0;
         if ((h_theta_draws && hipMemcpyAsync(th_stage[q].data(), d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
             (h_beta_draws && hipMemcpyAsync(h_beta_draws + (int64_t)slot * 2 * m, d + off_beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, copy_stream) != hipSuccess) ||
@@ -2651,7 +2728,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
                       gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
                       gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr,
-                      gpirt_equate* equate = nullptr)
+                      gpirt_equate* equate = nullptr, gpirt_loo* loo = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2753,6 +2830,12 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(equate->reserved[0] == 0 && equate->reserved[1] == 0 && equate->reserved[2] == 0 && equate->reserved[3] == 0);
         GP_TRY(equate_check(m, equate->x, equate->y, nullptr, nullptr));
     }
+    int64_t loo_M = 0;
+    if (loo) {
+        GP_ARG(loo->reserved[0] == 0 && loo->reserved[1] == 0 && loo->reserved[2] == 0 && loo->reserved[3] == 0);
+        GP_ARG(loo->top >= 1 && loo->top <= GPIRT_LOO_MAX_TOP && loo->tail >= 0 && loo->tail <= GPIRT_LOO_MAX_TAIL);
+        GP_TRY(loo_tail_length((int64_t)chains * S_it, (int)loo->tail, &loo_M));
+    }
     const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
     const gpirt_ppc_dif dif_in = dif ? *dif : gpirt_ppc_dif{};
     const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
@@ -2766,6 +2849,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     std::vector<ShapeState> keep_shape(shape ? (size_t)chains : 0);
     std::vector<SumscoreState> keep_sumscore(sumscore ? (size_t)chains : 0);
     std::vector<EquateState> keep_equate(equate ? (size_t)chains : 0);
+    LooState loo_pool, loo_chain;                                      // the pooled state and the chain that just finished
     const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
     const int total = S_it + B_it;
     int rc = 0;
@@ -2779,12 +2863,18 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                            score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
                            bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
                            sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr,
-                           equate ? &keep_equate[(size_t)c] : nullptr, equate };
+                           equate ? &keep_equate[(size_t)c] : nullptr, equate,
+                           loo ? (c == 0 ? &loo_pool : &loo_chain) : nullptr, (int64_t)chains * S_it, loo ? (int)loo->tail : 0 };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
                       h_beta_draws ? h_beta_draws + (int64_t)c * 2 * m * (S_it + 1) : nullptr,
                       h_f_draws ? h_f_draws + (int64_t)c * n * m * (S_it + 1) : nullptr, irf_c.data(), &sm, &cr);
+        if (loo && c > 0) {                                  // pooled in chain order; the chain's state goes at once
+            if (!rc && loo_chain.block) rc = launch_loo_merge(h->stream, loo_pool.block, loo_chain.block, n, m, loo_M);
+            if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { set_error("LOO merge: the stream failed"); rc = GPIRT_E_HIP; }
+            loo_free(&loo_chain);
+        }
     }
     std::vector<const void*> st((size_t)chains);
     for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
@@ -2833,6 +2923,11 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_equate[(size_t)c].block;
         rc = equate_combine(h, chains, st.data(), equate);
     }
+    if (!rc && loo) {
+        const void* one = loo_pool.block;
+        rc = loo_combine(h, 1, &one, loo);
+    }
+    loo_free(&loo_pool);
     for (auto& k : keep_sumscore) sumscore_free(&k);
     for (auto& k : keep_equate) equate_free(&k);
     for (auto& k : keep_ppc) ppc_free(&k);
@@ -3062,6 +3157,25 @@ int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_t
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate);
+}
+
+// ---- PSIS-LOO -------------------------------------------------------------------------------------------------------------------------
+int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                   const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                   gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                   gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
+                   gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo)
+{
+    GP_ARG(opts && loo);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_loo needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate, loo);
 }
 
 }  // extern "C"

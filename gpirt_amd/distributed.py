@@ -283,6 +283,12 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the score equating is not offered for item shards (each form's recursion runs over "
                          "all of its items, and each rank holds its own f* columns)")
 
+    # -- PSIS-LOO (gpirt_amd.loo): the cells are local to an item shard, but the totals, the respondent sums and the worst cells
+    # run over all items and are not pooled across ranks here
+    def loo_enable(self, planned_draws=None, tail=None, on=True):
+        raise ValueError("ShardedSampler: PSIS-LOO is not offered for item shards (the totals, the respondent sums and the "
+                         "worst cells run over all items; each rank holds its own columns)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

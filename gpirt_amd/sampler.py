@@ -44,7 +44,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
               progress=False, preset=None, summaries=None, store_draws=True, chains=None, align=True, quantiles=None,
-              ppc=None, ranks=None, score=None, shape=None, sumscore=None, equate=None):
+              ppc=None, ranks=None, score=None, shape=None, sumscore=None, equate=None, loo=None):
     """Drop-in for the reference's gpirtMCMC() (R/gpirtMCMC.R:85-105) on one MI355X.
 
     Positional arguments, defaults and the returned dict (theta (S+1) x n, beta 2 x m x (S+1),
@@ -178,6 +178,16 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       f* holds a NaN in a column of either form is skipped whole), corr_draws, corr_skipped, eq_clamped, x_items, y_items and
       the raw accumulators.  Memory at M_X = M_Y = 1024: 75 MB per chain.  Nothing is drawn: the chain is untouched under both
       RNG contracts.  equate=None leaves every other path as it is.
+    loo: True or dict(tail=None, top=20) adds PSIS-LOO (gpirt_mcmc_loo, gpirt_amd.loo): after every sampling iteration the device
+      enters each observed cell's key -y (f + mu) into the cell's heap of the M + 1 largest keys, T = chains x sample_iterations,
+      M = min(T // 5, ceil(3 sqrt(T))) or `tail` (5 .. 1024); at the end one wave per cell fits the generalised Pareto tail.
+      "loo" holds the totals elpd_loo, se_elpd_loo, p_loo, looic, se_looic, n_obs, lppd, k_threshold, k_good, k_bad, k_very_bad,
+      unsmoothed, cells_incomplete; pointwise (pareto_k, elpd_loo, n_eff, lppd, p_loo, loo_p_yes, n x m each, NaN for a missing or
+      an incomplete cell); item_elpd_loo (m), respondent_elpd_loo (n); worst (the `top` cells with the largest pareto_k: index,
+      row, col, pareto_k); raw (the pooled state: tail = the kept keys descending, keys, evicted_sum, evicted_sumsq, p_sum, count,
+      nonfinite, y) and T, M, draws, chains.  gpirt_amd.loo.compare(a["loo"], b["loo"]) is the elpd difference of two models
+      with its standard error.  Memory: (8 (M + 1) + 32) bytes per cell and state, two states while chains are pooled.  Nothing
+      is drawn: the chain is untouched under both RNG contracts.  loo=None leaves every other path as it is.
     """
     from .ops import RStream
 
@@ -232,6 +242,12 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     if equate is not None:
         from . import equate as EQ
         equate = EQ.parse(equate, m)
+    if loo is not None and loo is not False:
+        from . import loo as LO
+        loo = LO.parse(loo)
+        LO.tail_length((1 if chains is None else int(chains)) * int(sample_iterations), loo["tail"])
+    else:
+        loo = None
     pairs = bins = dif = None
     if isinstance(ppc, dict):
         from . import ppc as P
@@ -259,10 +275,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
                        top=P.check_dif_top(dif.get("top", P.DEFAULT_DIF_TOP)))
         ppc = True
     if (quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None
-            or equate is not None):
+            or equate is not None or loo is not None):
         return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
                                preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif, equate)
+                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif, equate, loo)
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -396,7 +412,7 @@ def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabil
 
 def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
                     kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None, equate=None):
+                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None, equate=None, loo=None):
     """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
     gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
     with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
@@ -409,7 +425,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
     gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else).  dif
     (dict(groups, G, cuts, top)): gpirt_mcmc_dif, the same chains with the group-wise item fit inside the PPC (with or without
     everything else).  equate (gpirt_amd.equate.parse's dict): gpirt_mcmc_equate, the same chains with the two-form score equating
-    (with or without everything else)."""
+    (with or without everything else).  loo (gpirt_amd.loo.parse's dict): gpirt_mcmc_loo, the same chains with PSIS-LOO (with or
+    without everything else)."""
     from . import chains as CH
     from . import ranks as RK
     from . import ppc as P
@@ -472,7 +489,7 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
 
     cb = _lib.TICK_FN(_tick)
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if shape is not None or sumscore is not None or dif is not None or equate is not None:
+    if shape is not None or sumscore is not None or dif is not None or equate is not None or loo is not None:
         from . import shape as SH
         from . import score as SC
         sh = ss = None
@@ -500,9 +517,15 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         df = None
         if dif is not None:
             df, dfarr = P.dif_struct(m, dif["G"], dif["cuts"], dif["top"], groups=dif["groups"])
+        eq = None
         if equate is not None:
             from . import equate as EQ
             eq, eqarr = EQ.struct(m, int(equate["mask_x"].sum()), int(equate["mask_y"].sum()), equate["mask_x"], equate["mask_y"])
+        if loo is not None:
+            from . import loo as LO
+            lo, loarr = LO.struct(n, m, LO.tail_length(C_ * S, loo["tail"]), loo["top"], loo["tail"])
+            rc = lib.gpirt_mcmc_loo(*args, ref(sh), ref(ss), ref(df), ref(eq), C.byref(lo))
+        elif equate is not None:
             rc = lib.gpirt_mcmc_equate(*args, ref(sh), ref(ss), ref(df), C.byref(eq))
         elif dif is not None:
             rc = lib.gpirt_mcmc_dif(*args, ref(sh), ref(ss), C.byref(df))
@@ -594,6 +617,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         out["sumscore"] = SS.result(ss, ssarr, sumscore["probs"], y)
     if equate is not None:
         out["equate"] = EQ.result(eq, eqarr, equate["probs"], equate["cuts"])
+    if loo is not None:
+        out["loo"] = LO.result(lo, loarr)
     return out
 
 
@@ -1323,6 +1348,63 @@ class Sampler:
         its own state."""
         from . import equate as EQ
         return EQ.combine(self.handle, [self], probs=probs, cuts=cuts)
+
+    # -- PSIS-LOO (include/gpirt_hip.h gpirt_sampler_loo_*, gpirt_amd.loo)
+    def loo_enable(self, planned_draws=None, tail=None, on=True):
+        """Allocate and zero the LOO state for `planned_draws` draws pooled over ALL chains (T) and the tail rule, or `tail`
+        (5 .. 1024) keys; a bad tail, a tail of more than 1024 keys and one that T draws cannot fill are ValueErrors.  on=False
+        frees it."""
+        if not on:
+            check(self.lib.gpirt_sampler_loo_enable(self._s, 0, 0, 0))
+            self._loo_M = None
+            return
+        from . import loo as LO
+        M = LO.tail_length(planned_draws, tail)
+        check(self.lib.gpirt_sampler_loo_enable(self._s, int(planned_draws), 0 if tail is None else int(tail), 1))
+        self._loo_M = M
+
+    def loo_accumulate(self):
+        """Enter the current f + mu (after a sampling iteration's step) as one draw; the chain is untouched."""
+        self._call("gpirt_sampler_loo_accumulate")
+
+    def loo_get(self, name: str) -> np.ndarray:
+        """One array by name: keys (K x n x m, each cell's min-heap, slot 0 the smallest kept key), evicted_sum, evicted_sumsq,
+        p_sum (n x m), count, nonfinite (int32), y (int8), counts (int64: n, m, T, M, draws, chains) and tail: the kept keys in
+        descending order per cell (K x n x m, NaN where fewer than K keys are held)."""
+        from . import loo as LO
+        if name == "tail":
+            return LO.sorted_tail(self.loo_get("keys"), self.loo_get("count"))
+        M = getattr(self, "_loo_M", None) or 0                           # (not enabled: the library refuses the call)
+        dts = dict(_lib.LOO_RAW)
+        if name in dts:
+            out = np.empty(LO._raw_shape(name, self.n, self.m, M), dtype=np.dtype(dts[name]))
+        elif name == "counts":
+            out = np.empty(6, dtype=np.int64)
+        else:
+            out = np.empty(0)
+        check(self.lib.gpirt_sampler_loo_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        if name == "keys":
+            return out.transpose(0, 2, 1)
+        return out.T if name in dts else out
+
+    def loo_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the LOO state: what gpirt_amd.loo.combine pools."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_loo_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def loo(self, top=20) -> dict:
+        """Every finished output of this sampler's state (gpirt_amd.loo.result's dict): gpirt_loo_combine over it alone."""
+        from . import loo as LO
+        return LO.combine(self.handle, [self], top=top)
 
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):

@@ -1476,6 +1476,135 @@ int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_t
                       gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
                       gpirt_ppc_dif* dif, gpirt_equate* equate);
 
+/* ------------------------------------------------------ PSIS-LOO: pointwise elpd, Pareto k, model comparison ----------- */
+/* Leave-one-out cross-validation by Pareto-smoothed importance sampling (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson,
+ * Gelman, Yao and Gabry 2024) for every observed cell, without stored draws.  Library version 117.
+ * For an observed cell (i, j) and a draw s, with the sampler's own arrays f and mu:
+ *   g = f + mu (one fp64 add, as WAIC forms it), a = y g, the KEY kappa_s = -a (exact: a product with +-1 and a sign);
+ *   the importance ratio r_s = 1 / p(y | draw) = 1 + exp(kappa_s), and p_s = 1 / r_s.
+ * T is the number of draws that will be pooled (chains times draws per chain), fixed when the state is made.  The tail length
+ * is M = min(floor(T / 5), ceil(3 sqrt(T))) unless `tail` (5 .. GPIRT_LOO_MAX_TAIL) replaces the rule; M > GPIRT_LOO_MAX_TAIL
+ * and M >= T are argument errors that say so.  K = M + 1.
+ * PER DRAW AND CELL a state keeps
+ *   keys          the K largest keys entered so far (equal keys are interchangeable: the kept multiset is unique), as a binary
+ *                 min-heap per cell, slot-major (slot z of cell c at [z cells + c], c = i + j n), the smallest kept key in slot 0;
+ *   evicted_sum, evicted_sumsq   the sums of r and r^2 over every key that is not, or is no longer, kept, added in draw order at
+ *                 the moment the key is refused (it does not exceed the smallest kept key) or pushed out (the smallest kept key
+ *                 leaves for a larger one): the non-tail sum is never formed by subtraction;
+ *   p_sum         the sum of p_s;
+ *   count, nonfinite   a draw whose g is not finite in the cell, or whose key exceeds GPIRT_LOO_KEY_MAX = 700, is not entered
+ *                 and adds 1 to `nonfinite`; every other draw adds 1 to `count`.  A missing cell (y NaN) keeps nothing.
+ * One thread owns a cell: no atomics, a fixed order, byte-identical state blocks from run to run.
+ * POOLING.  The keys kept by the next chain's state are entered into the pooled heap in slot order, by the same rule; its
+ * evicted sums are added first, then r and r^2 of whatever the pooled heap refuses or pushes out; p_sum and the counters add.
+ * theta -> -theta does not change g, so pooling takes no signs.  States of another n, m, T, M or y are refused.
+ * FINISHING, per cell.  A cell with count == T and nonfinite == 0 is finished; any other observed cell gets NaN outputs and is
+ * counted in `cells_incomplete`.
+ *   1. The kept keys in ascending order: the smallest is the cutoff kappa_c, the other M are the tail kappa_(1) <= ... <=
+ *      kappa_(M) = kmax.
+ *   2. x_z = exp(kappa_(z) - kmax) - exp(kappa_c - kmax), the exceedances in units of exp(kmax) (the "1 +" cancels).
+ *   3. M < 5 or x_M <= 0: the cell is UNSMOOTHED (pareto_k = NaN, the raw ratios are used, counted in `unsmoothed`).
+ *   4. Else the generalised Pareto fit of Zhang and Stephens (2009) as PSIS uses it: mgrid = 30 + floor(sqrt(M)), x* = x at the
+ *      1-based position floor(M / 4 + 0.5); for j = 1 .. mgrid
+ *        theta_j = 1 / x_M + (1 - sqrt(mgrid / (j - 0.5))) / (3 x*),   k_j = mean_z log1p(-theta_j x_z),
+ *        l_j = M (log(-theta_j / k_j) - k_j - 1),   w_j = 1 / sum_i exp(l_i - l_j);
+ *      theta^ = sum_j theta_j w_j, k = mean_z log1p(-theta^ x_z), sigma = -k / theta^, then k <- (k M + 5) / (M + 10).
+ *      A fit whose k or sigma is not finite (x* = 0: a quarter of the tail ties with the cutoff) leaves the cell unsmoothed too.
+ *   5. q_z = sigma expm1(-k log1p(-(z - 1/2) / M)) / k + exp(kappa_c - kmax), capped at 1 (the largest raw ratio);
+ *      w~_z = exp(-kmax) + q_z (unsmoothed: w~_z = rho_z), and the raw rho_z = exp(-kmax) + exp(kappa_(z) - kmax).
+ *   6. With E = evicted_sum + r(kappa_c), E2 = evicted_sumsq + r(kappa_c)^2, W = E exp(-kmax) + sum_z w~_z:
+ *        elpd_loo  = log((T - M) + sum_z w~_z / rho_z) - log(W) - kmax      (W is in units of exp(kmax));
+ *        n_eff     = W^2 / ((E2 exp(-kmax)) exp(-kmax) + sum_z w~_z^2);
+ *        lppd      = log(p_sum / T);   p_loo = lppd - elpd_loo;
+ *        loo_p_yes = exp(elpd_loo) for a yes cell, 1 - exp(elpd_loo) for a no cell.
+ *      The sums over z are 64 interleaved partial sums (z = 1 + lane, 65 + lane, ...) added in lane order.
+ * TOTALS over the finished cells (block partials reduced in a fixed order): elpd_loo, se_elpd_loo = sqrt(N var) (ddof 1),
+ * p_loo, looic = -2 elpd_loo, se_looic = 2 se_elpd_loo, n_obs = N, lppd, k_threshold = min(1 - 1 / log10(T), 0.7), and the
+ * counts k_good (k <= threshold), k_bad (threshold < k <= 1), k_very_bad (k > 1), unsmoothed, cells_incomplete.
+ * item_elpd_loo (m) and respondent_elpd_loo (n) are sums over the finished cells of a column / a row.  worst: the `top` cells
+ * with the largest pareto_k, ties to the lowest column-major index; index -1 and k NaN where fewer cells have a k.
+ * Nothing is drawn: with the accumulators on, the chain, the IRFs, R's stream position and every other block's state are bit
+ * for bit what they are without.
+ * Device memory per state: (8 K + 32) bytes per cell, plus one byte per cell for the copy of y. */
+#define GPIRT_LOO_MAX_TAIL            1024
+#define GPIRT_LOO_MAX_TOP             64
+#define GPIRT_LOO_KEY_MAX             700.0
+/* the raw arrays of a state block, in the block's order */
+#define GPIRT_LOO_KEYS                0       /* double [K][n m]: the heaps, slot-major */
+#define GPIRT_LOO_EVICTED_SUM         1       /* double [n m] */
+#define GPIRT_LOO_EVICTED_SUMSQ       2       /* double [n m] */
+#define GPIRT_LOO_P_SUM               3       /* double [n m] */
+#define GPIRT_LOO_COUNT               4       /* int32 [n m] */
+#define GPIRT_LOO_NONFINITE           5       /* int32 [n m] */
+#define GPIRT_LOO_Y                   6       /* signed char [n m]: +1, -1, 0 for a missing cell */
+#define GPIRT_LOO_NARRAYS             7
+/* the pointwise outputs (double [n m] each, NaN for a missing or an incomplete cell) */
+#define GPIRT_LOO_PW_PARETO_K         0
+#define GPIRT_LOO_PW_ELPD_LOO         1
+#define GPIRT_LOO_PW_N_EFF            2
+#define GPIRT_LOO_PW_LPPD             3
+#define GPIRT_LOO_PW_P_LOO            4
+#define GPIRT_LOO_PW_LOO_P_YES        5
+#define GPIRT_LOO_NPOINTWISE          6
+/* totals */
+#define GPIRT_LOO_T_ELPD_LOO          0
+#define GPIRT_LOO_T_SE_ELPD_LOO       1
+#define GPIRT_LOO_T_P_LOO             2
+#define GPIRT_LOO_T_LOOIC             3
+#define GPIRT_LOO_T_SE_LOOIC          4
+#define GPIRT_LOO_T_N_OBS             5
+#define GPIRT_LOO_T_LPPD              6
+#define GPIRT_LOO_T_K_THRESHOLD       7
+#define GPIRT_LOO_T_K_GOOD            8
+#define GPIRT_LOO_T_K_BAD             9
+#define GPIRT_LOO_T_K_VERY_BAD        10
+#define GPIRT_LOO_T_UNSMOOTHED        11
+#define GPIRT_LOO_T_CELLS_INCOMPLETE  12
+#define GPIRT_LOO_T_ELPD_MEAN         13
+#define GPIRT_LOO_NTOTALS             14
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_loo {
+    int64_t    tail;                           /* in (gpirt_mcmc_loo): 0 = the rule, else 5 .. GPIRT_LOO_MAX_TAIL */
+    int64_t    top;                            /* in: 1 .. GPIRT_LOO_MAX_TOP, the length of worst_index / worst_k */
+    void*      raw[GPIRT_LOO_NARRAYS];         /* the pooled raw arrays, each of the size and type named above */
+    double*    pointwise[GPIRT_LOO_NPOINTWISE];
+    double*    item_elpd_loo;                  /* m */
+    double*    respondent_elpd_loo;            /* n */
+    int64_t*   worst_index;                    /* top */
+    double*    worst_k;                        /* top */
+    double     totals[GPIRT_LOO_NTOTALS];      /* out */
+    int64_t    n, m, T, M, draws, chains;      /* out: draws = accumulate calls pooled, chains = states pooled */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_loo;
+/* Stage API.  loo_enable(planned_total_draws = T >= 1, tail = 0 or 5 .. 1024, on != 0) allocates and zeroes the state (a bad
+ * tail, M > GPIRT_LOO_MAX_TAIL and M >= T are GPIRT_E_ARG with a message, the old state is then kept); on = 0 frees it.
+ * loo_accumulate enters the CURRENT f + mu as one draw.  loo_get copies one array by name to the host, `bytes` its exact size:
+ * "keys", "evicted_sum", "evicted_sumsq", "p_sum", "count", "nonfinite", "y" and "counts" (int64: n, m, T, M, draws, chains).
+ * loo_state returns the ONE device block (valid until loo_enable is called again or the sampler goes): a header of 16 int64 --
+ * the tag 0x4F4F4C50 ("PLOO"), the layout version (1), n, m, T, M, draws, chains, 0 ... -- then the raw arrays in the order
+ * above, every array starting on a 16-byte boundary; gpirt_loo_state_bytes gives its size.  gpirt_loo_combine pools the states
+ * in order on the device (one pooled copy beside the callers' states; none for one state) and finishes. */
+int gpirt_sampler_loo_enable(gpirt_sampler_t s, int64_t planned_total_draws, int tail, int on);
+int gpirt_sampler_loo_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_loo_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_loo_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_loo_tail_length(int64_t T, int tail, int64_t* M);
+int gpirt_loo_state_bytes(int64_t n, int64_t m, int64_t M, int64_t* bytes);
+int gpirt_loo_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_loo* out);
+/* gpirt_mcmc_equate with PSIS-LOO (loo is required; everything from q on, equate included, may be NULL; pairs, bins and dif need
+ * ppc as before): T = chains x sample_iterations; every chain also enters its f + mu after each sampling iteration -- under the
+ * item RNG from the verified checkpoint's f and mu, under R's stream right after the step --; each finished chain is merged into
+ * the pooled state and freed (at most two states are alive), then the pooled state is finished into loo. */
+int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                   int sample_iterations, int burn_iterations, const double* h_prior_means,
+                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                   const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                   gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
+                   gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
