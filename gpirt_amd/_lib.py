@@ -291,6 +291,19 @@ class Loo(C.Structure):
                 ("draws", C.c_int64), ("chains", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# Item-pair IRF order posteriors (include/gpirt_hip.h GPIRT_ORDER_*): the raw arrays of a state block in order, with their dtypes
+ORDER_MAX_M, ORDER_MAX_TOP, ORDER_TAG = 4096, 64, 0x5244524F
+ORDER_RAW = (("above", "u4"), ("cross", "u4"), ("easier", "u4"), ("depth_sum", "f8"), ("easiness", "f8"), ("set_counts", "u8"))
+
+
+class ShapeOrder(C.Structure):
+    """gpirt_shape_order (include/gpirt_hip.h): top (in), the window and tolerances, a host pointer per raw array (NULL: not
+    wanted), the worst pairs and the counters."""
+    _fields_ = [("top", C.c_int), ("k_half", C.c_int), ("n_tols", C.c_int), ("tols", C.c_double * SHAPE_MAX_TOLS),
+                ("raw", C.c_void_p * len(ORDER_RAW)), ("worst_a", C.c_void_p), ("worst_b", C.c_void_p), ("n_worst", C.c_int64),
+                ("n", C.c_int64), ("m", C.c_int64), ("draws", C.c_int64), ("skipped", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -490,6 +503,16 @@ SIGNATURES = {
                                C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
                                C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
                                C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate), C.POINTER(Loo)]),
+    "gpirt_sampler_shape_order_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_shape_order_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_shape_order_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_shape_order_state_bytes": (_i32, [_i64, _i32, C.POINTER(_i64)]),
+    "gpirt_shape_order_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(ShapeOrder)]),
+    "gpirt_mcmc_order": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
+                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
+                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
+                                 C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate), C.POINTER(Loo), C.POINTER(ShapeOrder)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 117; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 118; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -190,6 +190,8 @@ int gpirt_version(void) { return 117; }     // 101: gpirt_options names kernel_f
                                             //      gpirt_equate_combine, gpirt_mcmc_equate)
                                             // 117: PSIS-LOO (loo.hip: gpirt_sampler_loo_*, gpirt_loo_tail_length, gpirt_loo_state_bytes,
                                             //      gpirt_loo_combine, gpirt_mcmc_loo)
+                                            // 118: item-pair IRF order posteriors (order.hip: gpirt_sampler_shape_order_*,
+                                            //      gpirt_shape_order_state_bytes, gpirt_shape_order_combine, gpirt_mcmc_order)
 
 const char* gpirt_last_error(void) { return g_err; }
 

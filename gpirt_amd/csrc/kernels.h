@@ -605,6 +605,24 @@ constexpr int SHAPE_HEADER_WORDS = 16;
 constexpr int64_t SHAPE_TAG = 0x50414853;             // "SHAP"
 struct ShapeLayout { int64_t off[GPIRT_SHAPE_NARRAYS]; int64_t words; };
 ShapeLayout shape_layout(int64_t m);
+// order.hip: item-pair order posteriors on top of the shape block (gpirt_sampler_shape_order_*, gpirt_mcmc_order;
+// include/gpirt_hip.h, "Item-pair IRF order posteriors").  ONE device block of 8-byte words: a header of ORDER_HEADER_WORDS
+// int64 (tag, layout version, n, m, k_half, n_tols, the four tolerances' bits, draws, skipped, 0, 0, 0, 0 -- the two counters
+// are kept by the finishing kernel), then the GPIRT_ORDER_* arrays in order, each on a 16-byte boundary.  Beside it the work
+// arrays of the last counted draw (u: m x m, e: m, ncross: GPIRT_SHAPE_MAX_TOLS int64) and the tiles' crossing partials.
+constexpr int ORDER_LAYOUT_VERSION = 1;
+constexpr int ORDER_HEADER_WORDS = 16;
+constexpr int64_t ORDER_TAG = 0x5244524F;             // "ORDR"
+struct OrderLayout { int64_t off[GPIRT_ORDER_NARRAYS]; int64_t words; };
+OrderLayout order_layout(int64_t m, int n_tols);
+struct OrderState {
+    bool on = false;
+    uint64_t* block = nullptr;
+    double *u = nullptr, *e = nullptr;
+    int64_t* ncross = nullptr;
+    uint32_t* tile_part = nullptr;                    // [tiles][GPIRT_SHAPE_MAX_TOLS]: unordered crossing pairs of a tile
+    std::vector<void*> allocs;
+};
 struct ShapeState {
     bool on = false;
     int64_t n = 0, m = 0;
@@ -614,6 +632,7 @@ struct ShapeState {
     double *gbar = nullptr, *info = nullptr, *ti = nullptr, *term = nullptr, *w = nullptr;
     unsigned char* bad = nullptr;                     // [m]: 1 where the last draw's column held a non-finite g
     std::vector<void*> allocs;
+    OrderState order;                                 // the pair block (order.on: launch_shape_accumulate also runs its kernels)
 };
 // refuses k_half outside 1..500, n_tols outside 1..GPIRT_SHAPE_MAX_TOLS and a negative or non-finite tolerance, with a message
 int shape_check(int k_half, const double* tols, int n_tols);
@@ -622,6 +641,12 @@ void shape_free(ShapeState* s);
 int launch_shape_accumulate(hipStream_t stream, ShapeState* s, const double* gbar);   // gbar: N x m (ld N) on the device
 int shape_get(hipStream_t stream, ShapeState* s, const char* name, void* h_out, int64_t bytes);
 int shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out);
+// the pair block of a shape state that is on: order_alloc refuses m outside 2..GPIRT_ORDER_MAX_M with a message
+int order_alloc(hipStream_t stream, ShapeState* s);
+void order_free(OrderState* o);
+int launch_order_accumulate(hipStream_t stream, ShapeState* s, const double* gbar);   // after the shape's kernels: reads s->bad
+int order_get(hipStream_t stream, ShapeState* s, const char* name, void* h_out, int64_t bytes);
+int order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out);
 
 // sumscore.hip: posteriors of the sum score on a form of M items, one f* draw at a time (gpirt_sampler_sumscore_*,
 // gpirt_mcmc_sumscore; include/gpirt_hip.h, "Sum-score posteriors").  The state is ONE device block of 8-byte words: a header of

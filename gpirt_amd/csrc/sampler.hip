@@ -1993,6 +1993,64 @@ int gpirt_loo_combine(gpirt_handle_t h, int chains, const void* const* d_states,
     return loo_combine(h, chains, d_states, out);
 }
 
+// ---- item-pair order posteriors (order.hip) on top of the shape block ------------------------------------------------------
+static int order_needs_on(gpirt_sampler_t s)
+{
+    if (s->shape.on && s->shape.order.on) return 0;
+    set_error("the order posteriors are not enabled (gpirt_sampler_shape_order_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_shape_order_enable(gpirt_sampler_t s, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) {                                           // refused before the old block goes
+        if (!s->shape.on) {
+            set_error("the order posteriors need the shape posteriors (gpirt_sampler_shape_enable first)");
+            return GPIRT_E_ARG;
+        }
+        if (s->m < 2 || s->m > GPIRT_ORDER_MAX_M) {
+            set_error("order posteriors: m = %lld items, 2..%d are taken", (long long)s->m, GPIRT_ORDER_MAX_M);
+            return GPIRT_E_ARG;
+        }
+    }
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    order_free(&s->shape.order);
+    if (!on) return 0;
+    const int rc = order_alloc(s->h->stream, &s->shape);
+    if (rc) order_free(&s->shape.order);
+    return rc;
+}
+
+int gpirt_sampler_shape_order_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(order_needs_on(s));
+    return order_get(s->h->stream, &s->shape, name, h_out, bytes);
+}
+
+int gpirt_sampler_shape_order_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(order_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the header's counters are the kernels'
+    *d_state = s->shape.order.block;
+    *bytes = order_layout(s->m, s->shape.n_tols).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_shape_order_state_bytes(int64_t m, int n_tols, int64_t* bytes)
+{
+    GP_ARG(m >= 2 && m <= GPIRT_ORDER_MAX_M && n_tols >= 1 && n_tols <= GPIRT_SHAPE_MAX_TOLS && bytes);
+    *bytes = order_layout(m, n_tols).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_shape_order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out)
+{
+    return order_combine(h, chains, d_states, out);
+}
+
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------
 static int score_needs_on(gpirt_sampler_t s)
 {
@@ -2348,6 +2406,7 @@ struct ChainRun {
     LooState* keep_loo;               // gpirt_mcmc_loo: ... and PSIS-LOO (T = loo_T draws over all chains, `loo_tail` as given)
     int64_t loo_T;
     int loo_tail;
+    bool order;                       // gpirt_mcmc_order: the shape state also holds the pair block (it travels inside keep_shape)
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2469,6 +2528,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, cr->sumscore->items, 1);
     const bool equate = cr && cr->keep_equate;
     if (!rc && equate) rc = gpirt_sampler_equate_enable(s, cr->equate->x, cr->equate->y, 1);
+    if (!rc && shape && cr->order) rc = gpirt_sampler_shape_order_enable(s, 1);
     const bool loo = cr && cr->keep_loo;
     if (!rc && loo) rc = gpirt_sampler_loo_enable(s, cr->loo_T, cr->loo_tail, 1);
 
@@ -2728,7 +2788,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                       const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
                       gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
                       gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr,
-                      gpirt_equate* equate = nullptr, gpirt_loo* loo = nullptr)
+                      gpirt_equate* equate = nullptr, gpirt_loo* loo = nullptr, gpirt_shape_order* order = nullptr)
 {
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
@@ -2830,6 +2890,21 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(equate->reserved[0] == 0 && equate->reserved[1] == 0 && equate->reserved[2] == 0 && equate->reserved[3] == 0);
         GP_TRY(equate_check(m, equate->x, equate->y, nullptr, nullptr));
     }
+    if (order) {
+        GP_ARG(order->reserved[0] == 0 && order->reserved[1] == 0 && order->reserved[2] == 0 && order->reserved[3] == 0);
+        if (!shape) {
+            set_error("gpirt_mcmc_order: the order posteriors need the shape posteriors (shape is NULL)");
+            return GPIRT_E_ARG;
+        }
+        if (m < 2 || m > GPIRT_ORDER_MAX_M) {
+            set_error("order posteriors: m = %lld items, 2..%d are taken", (long long)m, GPIRT_ORDER_MAX_M);
+            return GPIRT_E_ARG;
+        }
+        if (order->top < 1 || order->top > GPIRT_ORDER_MAX_TOP) {
+            set_error("gpirt_mcmc_order: top = %d is outside 1..%d", order->top, GPIRT_ORDER_MAX_TOP);
+            return GPIRT_E_ARG;
+        }
+    }
     int64_t loo_M = 0;
     if (loo) {
         GP_ARG(loo->reserved[0] == 0 && loo->reserved[1] == 0 && loo->reserved[2] == 0 && loo->reserved[3] == 0);
@@ -2864,7 +2939,8 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
                            bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
                            sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr,
                            equate ? &keep_equate[(size_t)c] : nullptr, equate,
-                           loo ? (c == 0 ? &loo_pool : &loo_chain) : nullptr, (int64_t)chains * S_it, loo ? (int)loo->tail : 0 };
+                           loo ? (c == 0 ? &loo_pool : &loo_chain) : nullptr, (int64_t)chains * S_it, loo ? (int)loo->tail : 0,
+                           order != nullptr };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
         rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
@@ -2913,6 +2989,10 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     if (!rc && shape) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].block;
         rc = shape_combine(h, chains, st.data(), sg.data(), shape);
+    }
+    if (!rc && order) {                                    // no signs: the pair block is the same under theta -> -theta
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].order.block;
+        rc = order_combine(h, chains, st.data(), order);
     }
     if (!rc && sumscore) {
         for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_sumscore[(size_t)c].block;
@@ -3176,6 +3256,26 @@ int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_thet
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
                       h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
                       ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate, loo);
+}
+
+// ---- the item-pair order posteriors -------------------------------------------------------------------------------------------------
+int gpirt_mcmc_order(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
+                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
+                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
+                     gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo,
+                     gpirt_shape_order* order)
+{
+    GP_ARG(opts && order);
+    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_order needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+        return GPIRT_E_ARG;
+    }
+    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
+                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order);
 }
 
 }  // extern "C"

@@ -310,6 +310,7 @@ int shape_check(int k_half, const double* tols, int n_tols)
 
 void shape_free(ShapeState* p)
 {
+    order_free(&p->order);
     for (void* q : p->allocs) hipFree(q);
     *p = ShapeState{};
 }
@@ -373,6 +374,7 @@ int launch_shape_accumulate(hipStream_t st, ShapeState* p, const double* gbar)
     hipLaunchKernelGGL(shape_rel_kernel, dim3(1), dim3(SH_THREADS), 0, st, p->term, ctl, f64(GPIRT_SHAPE_REL),
                        reinterpret_cast<int64_t*>(p->block));
     GP_HIP(hipGetLastError());
+    if (p->order.on) GP_TRY(launch_order_accumulate(st, p, gbar));    // the pair block, on the same curves and bad[]
     return 0;
 }
 

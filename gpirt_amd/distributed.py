@@ -289,6 +289,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: PSIS-LOO is not offered for item shards (the totals, the respondent sums and the "
                          "worst cells run over all items; each rank holds its own columns)")
 
+    def shape_order_enable(self, on=True):
+        raise ValueError("ShardedSampler: the item-pair order posteriors are not offered for item shards (a pair's two curves "
+                         "may live on two ranks, and the shape posteriors they sit on are not offered either)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

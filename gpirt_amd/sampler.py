@@ -150,7 +150,11 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       curve with any non-finite value is skipped), info_draws / info_skipped per draw; the raw accumulators come with it.
       Memory at m = 1024: 24 MB of accumulators per chain plus 8 MB each for the curve and the draw's information.  Nothing is
       drawn: the chain is untouched under both RNG contracts.  Reflected chains are reflected exactly on their accumulators.
-      shape=None leaves every other path as it is.
+      shape=None leaves every other path as it is.  Two more keys, order=True and order_top=20 (1..64), add the item-pair order
+      posteriors as out["shape"]["order"] (gpirt_mcmc_order, gpirt_amd.shape.order_finish): per tolerance and ordered pair of
+      items p_above, p_cross, p_tied (curve a above b on the whole window, crossing it, neither), p_easier, depth_mean,
+      easiness_mean / _sd, rank_mean, order, cross_items_mean, p_iio, cross_pairs_mean / _sd, worst (the order_top pairs that
+      cross most often at the largest tolerance), draws, skipped and the raw arrays; 2 <= m <= 4096, 46 MB per chain at m = 1024.
     sumscore: True, or dict(items=None, probs=(0.025, 0.5, 0.975)), adds the posteriors of the SUM SCORE S = number of yes
       answers on a form of items (gpirt_mcmc_sumscore, gpirt_amd.sumscore): after every sampling iteration the device runs
       the Lord-Wingersky recursion over the form's items at every grid point of that draw's f*.  items: None (all items),
@@ -521,9 +525,14 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         if equate is not None:
             from . import equate as EQ
             eq, eqarr = EQ.struct(m, int(equate["mask_x"].sum()), int(equate["mask_y"].sum()), equate["mask_x"], equate["mask_y"])
+        lo = None
         if loo is not None:
             from . import loo as LO
             lo, loarr = LO.struct(n, m, LO.tail_length(C_ * S, loo["tail"]), loo["top"], loo["tail"])
+        if shape is not None and shape["order"]:
+            od, odarr = SH.order_struct(m, len(shape["tols"]), shape["order_top"])
+            rc = lib.gpirt_mcmc_order(*args, ref(sh), ref(ss), ref(df), ref(eq), ref(lo), C.byref(od))
+        elif loo is not None:
             rc = lib.gpirt_mcmc_loo(*args, ref(sh), ref(ss), ref(df), ref(eq), C.byref(lo))
         elif equate is not None:
             rc = lib.gpirt_mcmc_equate(*args, ref(sh), ref(ss), ref(df), C.byref(eq))
@@ -613,6 +622,8 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
             out["score"]["predict"] = SC.predict_result(pr, prarr)
     if shape is not None:
         out["shape"] = SH.result(sh, sharr, shape["probs"], shape["top"])
+        if shape["order"]:
+            out["shape"]["order"] = SH.order_result(od, odarr)
     if sumscore is not None:
         out["sumscore"] = SS.result(ss, ssarr, sumscore["probs"], y)
     if equate is not None:
@@ -1219,6 +1230,51 @@ class Sampler:
         if name == "tols":
             return out[:nt]
         return out.T if name == "info" else SH._public(name, out, nt)
+
+    # -- item-pair order posteriors on top of the shape block (include/gpirt_hip.h gpirt_sampler_shape_order_*, gpirt_amd.shape)
+    def shape_order_enable(self, on=True):
+        """Allocate and zero the item-pair order block beside the shape accumulators (after shape_enable(); 2 <= m <= 4096):
+        from then on shape_accumulate() also runs the order kernels on the same curves.  on=False frees it; shape_enable()
+        drops it with the shape state."""
+        check(self.lib.gpirt_sampler_shape_order_enable(self._s, 1 if on else 0))
+
+    def shape_order_get(self, name: str) -> np.ndarray:
+        """One array by name: above, cross (n_tols x m x m, uint32), easier (m x m), depth_sum (m x m), easiness (2 x m),
+        set_counts (3 x n_tols, uint64: iio_draws, cross_pairs_sum, cross_pairs_sumsq), counts (int64: draws, skipped) and, of
+        the last counted draw, u (m x m), e (m) and ncross (n_tols, int64)."""
+        from . import shape as SH
+        m, nt = self.m, getattr(self, "_shape_ntols", 0)                 # (not enabled: the library refuses the call)
+        dts = dict(_lib.ORDER_RAW)
+        if name in dts:
+            out = np.empty(SH._order_raw_shape(name, m, nt), dtype=np.dtype(dts[name]))
+        elif name in ("counts", "ncross"):
+            out = np.empty(2 if name == "counts" else _lib.SHAPE_MAX_TOLS, dtype=np.int64)
+        else:
+            out = np.empty({"u": (m, m), "e": (m,)}.get(name, (0,)))
+        check(self.lib.gpirt_sampler_shape_order_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        if name == "ncross":
+            return out[:nt]
+        return out[:, :nt] if name == "set_counts" else out
+
+    def shape_order_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the order accumulators: what
+        gpirt_amd.shape.order_combine pools."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_shape_order_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def shape_order(self, top=20) -> dict:
+        """Every finished output of this sampler's order block (gpirt_amd.shape.order_finish's dict)."""
+        from . import shape as SH
+        return SH.order_combine(self.handle, [self], top=top)
 
     def shape_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the shape accumulators: what

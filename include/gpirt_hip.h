@@ -1605,6 +1605,79 @@ int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_thet
                    gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
                    gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo);
 
+/* ------------------------------------------------------ Item-pair IRF order posteriors: dominance and crossings -------- */
+/* The shape posteriors say, item by item, whether a curve is monotone.  Whether the curves of two items INTERSECT -- whether the
+ * items have an invariant ordering (Sijtsma and Junker 1996) -- is a joint functional of two smooth curves gbar[:, a] and
+ * gbar[:, b] of one draw.  This block sits on top of the shape block: it reads the same gbar, the same window W = [k_lo, k_hi],
+ * the same tolerances and the bad[] flags the shape's item kernel writes.  2 <= m <= GPIRT_ORDER_MAX_M.
+ * Per counted draw, in fp64 (comparing P_a with P_b is comparing g_a with g_b, plogis being monotone):
+ *   U[a, b] = max over k in W of fl(g[k, a] - g[k, b]), a != b; the minimum over W is L = -U[b, a] exactly (fl(x - y) = -fl(y - x)).
+ *   For each tolerance t and ordered pair (a, b):  cross[t, a, b] += 1 where U > t and L < -t (symmetric);
+ *   above[t, a, b] += 1 where U > t and L >= -t (a above b); where U <= t and L < -t it is above[t, b, a] that gains; the
+ *   remainder is tied.  depth_sum[a, b] += min(max(U, 0), max(-L, 0)): the depth of the crossing in logits, symmetric, added
+ *   in draw order.  All of it is max, min, comparisons and ONE subtraction: the same bits in any order.
+ *   Easiness e_j = sum over the WHOLE grid of w_k / (1 + exp(-g[k, j])), w the shape block's normalised N(0, 1) weights; lane t
+ *   of 256 adds its k = 4t .. 4t + 3 in order, the 256 partial sums are added in ascending t.  easiness[0, j] += e_j,
+ *   easiness[1, j] += e_j e_j; easier[a, b] += 1 where e_a > e_b (the device's own e).
+ *   n_cross[t] = the unordered pairs that cross at t in this draw: set_counts[0, t] += (n_cross == 0) (iio_draws),
+ *   set_counts[1, t] += n_cross, set_counts[2, t] += n_cross n_cross (uint64).
+ * A draw in which ANY item's curve holds a non-finite value anywhere on the grid is skipped whole (inf - inf would poison a row
+ * of pairs): skipped += 1 and nothing else changes; otherwise draws += 1.  The diagonal cells are never touched (0).
+ * One owner per cell, no atomics: the state is byte-identical from run to run.  theta -> -theta changes nothing here (W and w
+ * are symmetric), so pooling chains is plain addition in chain order.
+ * Device memory per state: (8 n_tols + 12) m m bytes of accumulators and 8 m m for u: 38 MB + 8 MB = 46 MB at m = 1024 with
+ * three tolerances, 0.60 GB + 0.13 GB = 0.74 GB at m = 4096. */
+#define GPIRT_ORDER_MAX_M        4096
+#define GPIRT_ORDER_MAX_TOP      64
+/* the raw arrays of a state block, in the block's order */
+#define GPIRT_ORDER_ABOVE        0       /* uint32 [n_tols][m][m] */
+#define GPIRT_ORDER_CROSS        1       /* uint32 [n_tols][m][m] */
+#define GPIRT_ORDER_EASIER       2       /* uint32 [m][m] */
+#define GPIRT_ORDER_DEPTH_SUM    3       /* double [m][m] */
+#define GPIRT_ORDER_EASINESS     4       /* double [2][m]: sum e, sum e^2 */
+#define GPIRT_ORDER_SET_COUNTS   5       /* uint64 [3][GPIRT_SHAPE_MAX_TOLS]: iio_draws, cross_pairs_sum, cross_pairs_sumsq */
+#define GPIRT_ORDER_NARRAYS      6
+/* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
+typedef struct gpirt_shape_order {
+    int        top;                            /* in: 1..GPIRT_ORDER_MAX_TOP, the length of worst_a / worst_b */
+    int        k_half, n_tols;                 /* out: the states' */
+    double     tols[GPIRT_SHAPE_MAX_TOLS];     /* out */
+    void*      raw[GPIRT_ORDER_NARRAYS];
+    int64_t*   worst_a;                        /* top: the pairs a < b with the largest cross count at the largest tolerance, */
+    int64_t*   worst_b;                        /*      ties to the lowest (a, b); -1 beyond n_worst */
+    int64_t    n_worst;                        /* out: min(top, m (m - 1) / 2) */
+    int64_t    n, m, draws, skipped;           /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_shape_order;
+/* Stage API.  shape_order_enable(on != 0) allocates and zeroes the block beside a shape state that is on (GPIRT_E_ARG with a
+ * message when the shape posteriors are off or m is outside 2..GPIRT_ORDER_MAX_M; on = 0 frees it).  gpirt_sampler_shape_enable
+ * drops the block with the shape state it belongs to.  From then on gpirt_sampler_shape_accumulate also runs the order kernels,
+ * behind the shape's own, on the same gbar.  shape_order_get copies one array by name, `bytes` its exact size: "above", "cross",
+ * "easier", "depth_sum", "easiness", "set_counts", "counts" (int64: draws, skipped) and, of the last counted draw, "u" (double
+ * [m][m], the diagonal 0), "e" (double [m]) and "ncross" (int64 [GPIRT_SHAPE_MAX_TOLS]).  shape_order_state returns the ONE device
+ * block: a header of 16 int64 -- the tag 0x5244524F ("ORDR"), the layout version (1), n, m, k_half, n_tols, the four tolerances'
+ * bits, draws, skipped, 0, 0, 0, 0 -- then the raw arrays in the order above, every array starting on a 16-byte boundary;
+ * gpirt_shape_order_state_bytes gives its size.  gpirt_shape_order_combine adds the integers and adds the doubles in chain order;
+ * states with another m, window or tolerances than state 0 are refused. */
+int gpirt_sampler_shape_order_enable(gpirt_sampler_t s, int on);
+int gpirt_sampler_shape_order_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_shape_order_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_shape_order_state_bytes(int64_t m, int n_tols, int64_t* bytes);
+int gpirt_shape_order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out);
+/* gpirt_mcmc_loo with the order posteriors (order and shape are required; everything else from q on may be NULL as before):
+ * every chain's shape accumulation also runs the order kernels -- under the item RNG from the verified checkpoint's gbar --,
+ * pooled into order without signs.  The chain, the IRFs, R's stream position and every other block's state, the shape block
+ * included, are bit for bit what they are without. */
+int gpirt_mcmc_order(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                     int sample_iterations, int burn_iterations, const double* h_prior_means,
+                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
+                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
+                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
+                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
+                     gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
+                     gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo, gpirt_shape_order* order);
+
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any
  * other value is refused with GPIRT_E_ARG (gpirt_mcmc creates its sampler here). */
