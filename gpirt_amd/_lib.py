@@ -304,6 +304,17 @@ class ShapeOrder(C.Structure):
                 ("n", C.c_int64), ("m", C.c_int64), ("draws", C.c_int64), ("skipped", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+class Run(C.Structure):
+    """gpirt_run (include/gpirt_hip.h): what gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs -- R's stream (NULL: the
+    item RNG) and one pointer per analysis (NULL: not wanted)."""
+    _fields_ = [("rs", C.c_void_p), ("quantiles", C.POINTER(Quantiles)), ("ppc", C.POINTER(Ppc)), ("ranks", C.POINTER(Ranks)),
+                ("h_y_new", C.POINTER(C.c_double)), ("n_new", C.c_int64), ("score", C.POINTER(Score)),
+                ("predict", C.POINTER(ScorePredict)), ("pairs", C.POINTER(PpcPairs)), ("bins", C.POINTER(PpcBins)),
+                ("shape", C.POINTER(Shape)), ("sumscore", C.POINTER(Sumscore)), ("dif", C.POINTER(PpcDif)),
+                ("equate", C.POINTER(Equate)), ("loo", C.POINTER(Loo)), ("order", C.POINTER(ShapeOrder)),
+                ("reserved", C.c_void_p * 8)]
+
+
 class Options(C.Structure):
     _fields_ = [
         ("rng_kind", C.c_int),
@@ -395,70 +406,44 @@ SIGNATURES = {
                                      C.POINTER(Diag)]),
     "gpirt_mcmc_chains": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
                                   TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag)]),
+    "gpirt_mcmc_run": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
+                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), C.POINTER(Run)]),
     "gpirt_irf_band_edges": (_i32, [_dp]),
     "gpirt_summary_quantiles": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _i32, C.POINTER(Quantiles)]),
-    "gpirt_mcmc_quantiles": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                     TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                     C.POINTER(Quantiles)]),
     "gpirt_sampler_ppc_enable": (_i32, [_vp, _i32]),
     "gpirt_sampler_ppc_accumulate": (_i32, [_vp]),
     "gpirt_sampler_ppc_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_ppc_totals": (_i32, [_vp, _dp]),
     "gpirt_sampler_ppc_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Ppc)]),
-    "gpirt_mcmc_ppc": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                               C.POINTER(Quantiles), C.POINTER(Ppc)]),
     "gpirt_sampler_rank_enable": (_i32, [_vp, C.POINTER(C.c_int64), _i32, _i32]),
     "gpirt_sampler_rank_accumulate": (_i32, [_vp]),
     "gpirt_sampler_rank_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_rank_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_rank_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Ranks)]),
-    "gpirt_mcmc_ranks": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks)]),
     "gpirt_sampler_score_enable": (_i32, [_vp, _dp, _i64]),
     "gpirt_sampler_score_accumulate": (_i32, [_vp]),
     "gpirt_sampler_score_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_score_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_score_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Score)]),
-    "gpirt_mcmc_score": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score)]),
     "gpirt_sampler_score_predict_enable": (_i32, [_vp, _i32]),
     "gpirt_sampler_score_predict_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_score_predict_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_score_predict_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(ScorePredict)]),
-    "gpirt_mcmc_predict": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                   TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                   C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                   C.POINTER(ScorePredict)]),
     "gpirt_sampler_ppc_pairs_enable": (_i32, [_vp, _i32]),
     "gpirt_sampler_ppc_pairs_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_pairs_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_pairs_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcPairs)]),
-    "gpirt_mcmc_pairs": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs)]),
     "gpirt_sampler_ppc_bins_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int), _i32]),
     "gpirt_sampler_ppc_bins_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_bins_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_bins_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(PpcBins)]),
-    "gpirt_mcmc_bins": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins)]),
     "gpirt_sampler_shape_enable": (_i32, [_vp, _i32, _dp, _i32, _i32]),
     "gpirt_sampler_shape_accumulate": (_i32, [_vp]),
     "gpirt_sampler_shape_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_shape_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_shape_state_bytes": (_i32, [_i64, C.POINTER(_i64)]),
     "gpirt_shape_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Shape)]),
-    "gpirt_mcmc_shape": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape)]),
     "gpirt_sampler_sumscore_enable": (_i32, [_vp, _vp, _i32]),
     "gpirt_sampler_sumscore_accumulate": (_i32, [_vp]),
     "gpirt_sampler_sumscore_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
@@ -466,31 +451,16 @@ SIGNATURES = {
     "gpirt_sumscore_state_bytes": (_i32, [_i64, _i64, C.POINTER(_i64)]),
     "gpirt_sumscore_grid_weights": (_i32, [_dp]),
     "gpirt_sumscore_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Sumscore)]),
-    "gpirt_mcmc_sumscore": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
-                                 C.POINTER(Sumscore)]),
     "gpirt_sampler_ppc_dif_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), _i32, C.POINTER(C.c_int), _i32]),
     "gpirt_sampler_ppc_dif_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_dif_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_dif_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(PpcDif)]),
-    "gpirt_mcmc_dif": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                               C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                               C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
-                               C.POINTER(Sumscore), C.POINTER(PpcDif)]),
     "gpirt_sampler_equate_enable": (_i32, [_vp, _vp, _vp, _i32]),
     "gpirt_sampler_equate_accumulate": (_i32, [_vp]),
     "gpirt_sampler_equate_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_equate_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_equate_state_bytes": (_i32, [_i64, _i64, _i64, C.POINTER(_i64)]),
     "gpirt_equate_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Equate)]),
-    "gpirt_mcmc_equate": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                  TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                  C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                  C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
-                                  C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate)]),
     "gpirt_sampler_loo_enable": (_i32, [_vp, _i64, _i32, _i32]),
     "gpirt_sampler_loo_accumulate": (_i32, [_vp]),
     "gpirt_sampler_loo_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
@@ -498,21 +468,11 @@ SIGNATURES = {
     "gpirt_loo_tail_length": (_i32, [_i64, _i32, C.POINTER(_i64)]),
     "gpirt_loo_state_bytes": (_i32, [_i64, _i64, _i64, C.POINTER(_i64)]),
     "gpirt_loo_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(Loo)]),
-    "gpirt_mcmc_loo": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                               TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                               C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                               C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
-                               C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate), C.POINTER(Loo)]),
     "gpirt_sampler_shape_order_enable": (_i32, [_vp, _i32]),
     "gpirt_sampler_shape_order_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_shape_order_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_shape_order_state_bytes": (_i32, [_i64, _i32, C.POINTER(_i64)]),
     "gpirt_shape_order_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(ShapeOrder)]),
-    "gpirt_mcmc_order": (_i32, [_dp, _i64, _i64, _dp, _i32, _i32, _i32, _dp, _dp, _dp, C.POINTER(Options), _i32,
-                                 TICK_FN, _vp, _dp, _dp, _dp, _dp, C.POINTER(Summary), C.POINTER(Diag), _vp,
-                                 C.POINTER(Quantiles), C.POINTER(Ppc), C.POINTER(Ranks), _dp, _i64, C.POINTER(Score),
-                                 C.POINTER(ScorePredict), C.POINTER(PpcPairs), C.POINTER(PpcBins), C.POINTER(Shape),
-                                 C.POINTER(Sumscore), C.POINTER(PpcDif), C.POINTER(Equate), C.POINTER(Loo), C.POINTER(ShapeOrder)]),
     "gpirt_sampler_summary_accumulate": (_i32, [_vp]),
     "gpirt_sampler_summary_get": (_i32, [_vp, C.c_char_p, _dp, _i64]),
     "gpirt_sampler_summary_totals": (_i32, [_vp, _dp]),

@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 118; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 119; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -170,28 +170,30 @@ int gpirt_version(void) { return 118; }     // 101: gpirt_options names kernel_f
                                             //      gpirt_mcmc_chains, gpirt_chain_seed)
                                             // 106: quantiles -- theta histograms, IRF bands, rank-normalised R-hat
                                             //      (GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND, gpirt_summary_quantiles,
-                                            //      gpirt_mcmc_quantiles, gpirt_irf_band_edges)
-                                            // 107: posterior predictive checks (ppc.hip: gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc)
-                                            // 108: rank posteriors (ranks.hip: gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks)
-                                            // 109: scoring new respondents (score.hip: gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score)
+                                            //      gpirt_irf_band_edges)
+                                            // 107: posterior predictive checks (ppc.hip: gpirt_sampler_ppc_*, gpirt_ppc_combine)
+                                            // 108: rank posteriors (ranks.hip: gpirt_sampler_rank_*, gpirt_rank_combine)
+                                            // 109: scoring new respondents (score.hip: gpirt_sampler_score_*, gpirt_score_combine)
                                             // 110: predicting new respondents' unseen answers and the next item to ask (predict.hip:
-                                            //      gpirt_sampler_score_predict_*, gpirt_score_predict_combine, gpirt_mcmc_predict)
+                                            //      gpirt_sampler_score_predict_*, gpirt_score_predict_combine)
                                             // 111: pairwise item checks of the PPC (ppc_pairs.hip: gpirt_sampler_ppc_pairs_*,
-                                            //      gpirt_ppc_pairs_combine, gpirt_mcmc_pairs)
+                                            //      gpirt_ppc_pairs_combine)
                                             // 112: theta-binned item fit of the PPC (ppc_bins.hip: gpirt_sampler_ppc_bins_*,
-                                            //      gpirt_ppc_bins_combine, gpirt_mcmc_bins)
+                                            //      gpirt_ppc_bins_combine)
                                             // 113: IRF shape posteriors (shape.hip: gpirt_sampler_shape_*, gpirt_shape_state_bytes,
-                                            //      gpirt_shape_combine, gpirt_mcmc_shape; the sampler array "gbar")
+                                            //      gpirt_shape_combine; the sampler array "gbar")
                                             // 114: sum-score posteriors (sumscore.hip: gpirt_sampler_sumscore_*, gpirt_sumscore_state_bytes,
-                                            //      gpirt_sumscore_grid_weights, gpirt_sumscore_combine, gpirt_mcmc_sumscore)
+                                            //      gpirt_sumscore_grid_weights, gpirt_sumscore_combine)
                                             // 115: group-wise item fit of the PPC (ppc_dif.hip: gpirt_sampler_ppc_dif_*,
-                                            //      gpirt_ppc_dif_combine, gpirt_mcmc_dif)
+                                            //      gpirt_ppc_dif_combine)
                                             // 116: two-form score equating (equate.hip: gpirt_sampler_equate_*, gpirt_equate_state_bytes,
-                                            //      gpirt_equate_combine, gpirt_mcmc_equate)
+                                            //      gpirt_equate_combine)
                                             // 117: PSIS-LOO (loo.hip: gpirt_sampler_loo_*, gpirt_loo_tail_length, gpirt_loo_state_bytes,
-                                            //      gpirt_loo_combine, gpirt_mcmc_loo)
+                                            //      gpirt_loo_combine)
                                             // 118: item-pair IRF order posteriors (order.hip: gpirt_sampler_shape_order_*,
-                                            //      gpirt_shape_order_state_bytes, gpirt_shape_order_combine, gpirt_mcmc_order)
+                                            //      gpirt_shape_order_state_bytes, gpirt_shape_order_combine)
+                                            // 119: gpirt_mcmc_run with a gpirt_run (sampler.hip) replaces the whole-call entries that 106 to 118
+                                            //      added one per analysis, each the one before with one more parameter
 
 const char* gpirt_last_error(void) { return g_err; }
 

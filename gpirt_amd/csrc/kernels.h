@@ -337,7 +337,7 @@ int summary_seal(hipStream_t stream, SummaryState* s, const double* irf_sum, int
 int chains_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align, double* h_irfs,
                    gpirt_summary* pooled, gpirt_diag* diag, int* signs_out = nullptr);     // signs_out: the C signs it decided
 
-// ppc.hip: posterior predictive checks accumulated one draw at a time (gpirt_sampler_ppc_*, gpirt_mcmc_ppc).  The state is ONE
+// ppc.hip: posterior predictive checks accumulated one draw at a time (gpirt_sampler_ppc_*, gpirt_run.ppc).  The state is ONE
 // device block of 8-byte words: a header of 8 int64 (n, m, draws, layout version, item0, 0, 0, 0), then PPC_NARRAYS arrays of
 // ppc_stride(n, m) words each, unit k = item k (k < m), respondent k - m (k < m + n) or the whole matrix (k = m + n).
 constexpr int PPC_LAYOUT_VERSION = 1;
@@ -347,7 +347,7 @@ enum { PPC_N_OBS, PPC_OBS_YES, PPC_SUM_R, PPC_SUM_R2, PPC_YES_GE, PPC_YES_GT, PP
        PPC_NARRAYS };
 int64_t ppc_stride(int64_t n, int64_t m);           // n + m + 1 units, padded to an even count
 int64_t ppc_state_words(int64_t n, int64_t m);
-// ppc_pairs.hip: the pairwise item checks (gpirt_sampler_ppc_pairs_*, gpirt_mcmc_pairs), an add-on to a PPC state.  Its
+// ppc_pairs.hip: the pairwise item checks (gpirt_sampler_ppc_pairs_*, gpirt_run.pairs), an add-on to a PPC state.  Its
 // accumulators are ONE device block of 8-byte words of their own: a header of PAIR_HEADER_WORDS int64 (n, m, layout version,
 // pair_draws, pair_skipped, item0, 0, PAIR_TAG -- the two counters are kept by pair_update_kernel), the constant tables int32
 // n_co, o11, o1 (m x m, pair (a, b) at [a m + b]), then uint64 sum_n11, sumsq_n11, sum_n1 and uint32 n11_ge, n11_gt, agree_ge,
@@ -379,7 +379,7 @@ int launch_pair_accumulate(hipStream_t stream, PairState* p);
 int pair_get(hipStream_t stream, PairState* p, const char* name, void* h_out, int64_t bytes);
 int pair_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out);
 
-// ppc_bins.hip: the theta-binned item fit (gpirt_sampler_ppc_bins_*, gpirt_mcmc_bins), an add-on to a PPC state.  Its
+// ppc_bins.hip: the theta-binned item fit (gpirt_sampler_ppc_bins_*, gpirt_run.bins), an add-on to a PPC state.  Its
 // accumulators are ONE device block of 8-byte words of their own: a header of BIN_HEADER_WORDS int64 (n, m, layout version,
 // bin_draws, bin_skipped, item0, B, BIN_TAG -- the two counters are kept by bin_update_kernel), BIN_CUT_WORDS int64 with the
 // cuts, then the arrays of BinLayout, cell (b, j) at [b m + j], every array padded to 16 bytes.  Beside it: this draw's bins
@@ -424,7 +424,7 @@ int launch_bin_update(hipStream_t stream, BinState* p);
 int bin_get(hipStream_t stream, BinState* p, const char* name, void* h_out, int64_t bytes);
 int bin_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out);
 
-// ppc_dif.hip: the group-wise item fit (gpirt_sampler_ppc_dif_*, gpirt_mcmc_dif), an add-on to a PPC state.  Its accumulators
+// ppc_dif.hip: the group-wise item fit (gpirt_sampler_ppc_dif_*, gpirt_run.dif), an add-on to a PPC state.  Its accumulators
 // are ONE device block of 8-byte words of their own: a header of DIF_HEADER_WORDS int64 (n, m, layout version, dif_draws,
 // dif_skipped, item0, B, DIF_TAG -- the two counters are kept by dif_update_kernel), DIF_CUT_WORDS int64 with the cuts,
 // DIF_GROUP_WORDS int64 (G, the groups' sizes), the n group codes as int8, then the arrays of DifLayout, cell (g, b, j) at
@@ -502,7 +502,7 @@ void ppc_fill_totals(const uint64_t* blk, double* out);
 void ppc_fill_struct(const uint64_t* blk, gpirt_ppc* out);
 int ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out);
 
-// ranks.hip: rank posteriors accumulated one theta draw at a time (gpirt_sampler_rank_*, gpirt_mcmc_ranks).  The state is ONE
+// ranks.hip: rank posteriors accumulated one theta draw at a time (gpirt_sampler_rank_*, gpirt_run.ranks).  The state is ONE
 // device block of 8-byte words: a header of RANK_HEADER_WORDS int64 (n, counted draws, skipped draws, layout version, B, w,
 // the closed pivots' count, the pairwise flag, then the closed pivots, sorted, in 32 words), uint64 rank2_sum[n] and
 // rank2_sumsq[n], double pivot_share[np][n], uint32 pivot_cover[np][n], uint32 rank_hist[n][B] (each padded to a whole word)
@@ -538,14 +538,14 @@ int launch_rank_accumulate(hipStream_t stream, RankState* s, const double* theta
 int rank_get(hipStream_t stream, RankState* s, const char* name, void* h_out, int64_t bytes);
 int rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out);
 
-// score.hip: scoring respondents who were not in the fit, one f* draw at a time (gpirt_sampler_score_*, gpirt_mcmc_score).  The
+// score.hip: scoring respondents who were not in the fit, one f* draw at a time (gpirt_sampler_score_*, gpirt_run.score).  The
 // state is ONE device block of 8-byte words: a header of SCORE_HEADER_WORDS int64 (n_new, m, layout version, N, 0, 0, 0, 0),
 // int64 draws[n_new], nonfinite[n_new], n_obs[n_new], double lpd_acc[n_new] (starts at -inf), ll_sum[n_new] and
 // post_sum[n_new][N] (k fastest).  Beside it the state owns everything the product launchers need at n_new: the packed y_new
 // in both forms (Ypm for the fp64 GEMM, y8 for the int8 kernel), the terms and digit planes, and the product itself.
 constexpr int SCORE_LAYOUT_VERSION = 1;
 constexpr int SCORE_HEADER_WORDS = 8;
-// predict.hip: the new respondents' UNSEEN answers (gpirt_sampler_score_predict_*, gpirt_mcmc_predict), an add-on to a score
+// predict.hip: the new respondents' UNSEEN answers (gpirt_sampler_score_predict_*, gpirt_run.predict), an add-on to a score
 // state.  Its accumulators are ONE device block of 8-byte words of their own: a header of PRED_HEADER_WORDS int64 (n_new, m,
 // layout version, N, pred_draws, pred_skipped, 0, PRED_TAG -- the two counters are kept by the epilogue kernel; the tag tells
 // the block from a score block, whose header starts alike), the answered-mask of
@@ -594,7 +594,7 @@ int launch_pred_accumulate(gpirt_handle_t h, hipStream_t stream, ScoreState* s);
 int pred_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, int64_t bytes);
 int pred_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out);
 
-// shape.hip: shape posteriors of the item response curves, one curve draw at a time (gpirt_sampler_shape_*, gpirt_mcmc_shape;
+// shape.hip: shape posteriors of the item response curves, one curve draw at a time (gpirt_sampler_shape_*, gpirt_run.shape;
 // include/gpirt_hip.h, "IRF shape posteriors").  The state is ONE device block of 8-byte words: a header of SHAPE_HEADER_WORDS
 // int64 (tag, layout version, n, m, k_half, n_tols, the four tolerances' bits, info_draws, info_skipped, 0, 0, 0, 0 -- the two
 // counters are kept by the kernels), then the GPIRT_SHAPE_* arrays in order, each on a 16-byte boundary.  Beside it the state
@@ -605,7 +605,7 @@ constexpr int SHAPE_HEADER_WORDS = 16;
 constexpr int64_t SHAPE_TAG = 0x50414853;             // "SHAP"
 struct ShapeLayout { int64_t off[GPIRT_SHAPE_NARRAYS]; int64_t words; };
 ShapeLayout shape_layout(int64_t m);
-// order.hip: item-pair order posteriors on top of the shape block (gpirt_sampler_shape_order_*, gpirt_mcmc_order;
+// order.hip: item-pair order posteriors on top of the shape block (gpirt_sampler_shape_order_*, gpirt_run.order;
 // include/gpirt_hip.h, "Item-pair IRF order posteriors").  ONE device block of 8-byte words: a header of ORDER_HEADER_WORDS
 // int64 (tag, layout version, n, m, k_half, n_tols, the four tolerances' bits, draws, skipped, 0, 0, 0, 0 -- the two counters
 // are kept by the finishing kernel), then the GPIRT_ORDER_* arrays in order, each on a 16-byte boundary.  Beside it the work
@@ -649,7 +649,7 @@ int order_get(hipStream_t stream, ShapeState* s, const char* name, void* h_out, 
 int order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out);
 
 // sumscore.hip: posteriors of the sum score on a form of M items, one f* draw at a time (gpirt_sampler_sumscore_*,
-// gpirt_mcmc_sumscore; include/gpirt_hip.h, "Sum-score posteriors").  The state is ONE device block of 8-byte words: a header of
+// gpirt_run.sumscore; include/gpirt_hip.h, "Sum-score posteriors").  The state is ONE device block of 8-byte words: a header of
 // SUMSCORE_HEADER_WORDS int64 (tag, layout version, m, M, N = 1001, draws, skipped, rel_draws, rel_skipped, 0 ... -- the four
 // counters are kept by the kernels), then the GPIRT_SUMSCORE_* arrays in order, each on a 16-byte boundary.  Beside it the state
 // owns the draw's table of (p, q) (1001 x steps pairs, steps = M rounded up to 32), T and V of the draw (1024 each), the form's
@@ -686,7 +686,7 @@ int launch_sumscore_pi(hipStream_t stream, const double* last, const double* w, 
                        double* pi_sum, double* pi_sumsq);
 
 // equate.hip: the joint distribution of the sum scores on two disjoint forms, one f* draw at a time (gpirt_sampler_equate_*,
-// gpirt_mcmc_equate; include/gpirt_hip.h, "Two-form score equating").  The state is ONE device block of 8-byte words: a header of
+// gpirt_run.equate; include/gpirt_hip.h, "Two-form score equating").  The state is ONE device block of 8-byte words: a header of
 // EQUATE_HEADER_WORDS int64 (tag, layout version, m, M_X, M_Y, N = 1001, draws, skipped, corr_draws, corr_skipped, eq_clamped,
 // 0 ... -- the five counters are kept by the kernels), then the GPIRT_EQUATE_* arrays in order, each on a 16-byte boundary.  Beside
 // it the state owns each form's (p, q) table, A_X, its weighted copy and A_Y (1024 x (M + 1) each: the rows beyond 1001 are the
@@ -713,7 +713,7 @@ int launch_equate_accumulate(gpirt_handle_t h, hipStream_t stream, EquateState* 
 int equate_get(hipStream_t stream, EquateState* s, const char* name, void* h_out, int64_t bytes);
 int equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out);
 
-// loo.hip: PSIS-LOO without stored draws (gpirt_sampler_loo_*, gpirt_mcmc_loo; include/gpirt_hip.h, "PSIS-LOO").  The state is
+// loo.hip: PSIS-LOO without stored draws (gpirt_sampler_loo_*, gpirt_run.loo; include/gpirt_hip.h, "PSIS-LOO").  The state is
 // ONE device block of 8-byte words: a header of LOO_HEADER_WORDS int64 (tag, layout version, n, m, T, M, draws, chains, 0 ...
 // -- draws and chains are kept by the kernels), then the GPIRT_LOO_* arrays in order, each on a 16-byte boundary: the per-cell
 // min-heaps of the K = M + 1 largest keys (slot-major), the evicted sums, p_sum, the counters and a copy of y as bytes.

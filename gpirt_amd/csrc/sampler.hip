@@ -932,6 +932,15 @@ inline void mark(gpirt_sampler_s* s, int idx)
     if (s->timing) hipEventRecord(s->ev[idx], s->h->stream);
 }
 
+// every word of a struct's reserved[] is zero (NULL)
+template <typename T, size_t N>
+bool all_zero(const T (&r)[N])
+{
+    for (const T& v : r)
+        if (v) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2380,33 +2389,28 @@ long long gpirt_debug_take_mcmc_trip(void);
 static int g_last_mcmc_fallbacks = 0;
 int gpirt_debug_last_mcmc_fallbacks(void) { return g_last_mcmc_fallbacks; }
 
-// One chain of gpirt_mcmc_chains: run on the caller's handle, with the GPIRT_SUM_DIAG accumulators planned for the chain's
-// S draws; the sampler's summary state (sealed: header and IRF sum) is moved to *keep before the sampler goes.  The tick
-// sees (base + it, ticks).
+// What one chain of chains_run leaves behind for the combines: its states, moved out of the sampler before that goes.  The
+// pair, bin and group states travel inside ppc, the prediction inside score, the order posteriors' pair block inside shape.
+struct ChainKeep {
+    SummaryState sum;                 // sealed: header and IRF sum
+    PpcState ppc;
+    RankState rank;
+    ScoreState score;
+    ShapeState shape;
+    SumscoreState sumscore;
+    EquateState equate;
+    LooState loo;
+};
+
+// One chain of chains_run: run on the caller's handle, with the GPIRT_SUM_DIAG accumulators planned for the chain's S draws
+// and the analyses that `run` names (never NULL; its in/out structs as they were on entry), each accumulated beside the
+// summaries and handed to *keep.  The tick sees (base + it, ticks); PSIS-LOO plans its tail for all chains' `draws`.
 struct ChainRun {
     gpirt_handle_t h;
-    SummaryState* keep;
     int base, ticks;
-    PpcState* keep_ppc;               // gpirt_mcmc_ppc: the chain also accumulates the PPC; its state outlives the sampler here
-    RankState* keep_rank;             // gpirt_mcmc_ranks: ... and the rank posteriors (the state names pivots and pairwise)
-    const gpirt_ranks* ranks;
-    ScoreState* keep_score;           // gpirt_mcmc_score: ... and the scores of y_new (n_new x m on the host)
-    const double* y_new;
-    int64_t n_new;
-    bool predict;                     // gpirt_mcmc_predict: the score state also predicts the unseen answers (it travels inside keep_score)
-    bool pairs;                       // gpirt_mcmc_pairs: the PPC state also checks the item pairs (it travels inside keep_ppc)
-    const gpirt_ppc_bins* bins;       // gpirt_mcmc_bins: ... and the theta-binned item fit with these cuts (inside keep_ppc too)
-    ShapeState* keep_shape;           // gpirt_mcmc_shape: ... and the IRF shape posteriors (window and tolerances in `shape`)
-    const gpirt_shape* shape;
-    SumscoreState* keep_sumscore;     // gpirt_mcmc_sumscore: ... and the sum-score posteriors (the form's mask in `sumscore`)
-    const gpirt_sumscore* sumscore;
-    const gpirt_ppc_dif* dif;         // gpirt_mcmc_dif: ... and the group-wise item fit with these groups and cuts (inside keep_ppc)
-    EquateState* keep_equate;         // gpirt_mcmc_equate: ... and the two-form score equating (the forms' masks in `equate`)
-    const gpirt_equate* equate;
-    LooState* keep_loo;               // gpirt_mcmc_loo: ... and PSIS-LOO (T = loo_T draws over all chains, `loo_tail` as given)
-    int64_t loo_T;
-    int loo_tail;
-    bool order;                       // gpirt_mcmc_order: the shape state also holds the pair block (it travels inside keep_shape)
+    int64_t draws;
+    const gpirt_run* run;
+    ChainKeep* keep;
 };
 
 // The loop of gpirt_mcmc, gpirt_mcmc_summary and each chain of gpirt_mcmc_chains (arguments checked by the callers).
@@ -2438,6 +2442,12 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     const int total = S_it + B_it;
     const bool replay = stream_mode(s);
     const bool summarise = sm && sm->parts;
+    // a chain of chains_run also accumulates what its run names (chains_run has checked it: predict only with score; pairs,
+    // bins and dif only with ppc; order only with shape)
+    const gpirt_run none{};
+    const gpirt_run& run = cr ? *cr->run : none;
+    const bool ppc = run.ppc, ranks = run.ranks, score = run.score, shape = run.shape, sumscore = run.sumscore,
+               equate = run.equate, loo = run.loo;
     std::vector<double> th((size_t)n);
     auto store_sync = [&](int slot) -> int {
         // theta_draws.row(slot), beta_draws.slice(slot), f_draws.slice(slot): :53-55, :99-101
@@ -2451,43 +2461,30 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     };
     // the summaries out of the sampler (before it is destroyed)
     auto summary_out = [&]() -> int {
-        if (cr) {                               // the chain's state outlives its sampler until the combine
+        if (cr) {                               // the chain's states outlive its sampler until the combines
+            ChainKeep& k = *cr->keep;
+            auto hand_over = [&](auto& kept, auto& live) -> int {      // once the stream has finished the last accumulate
+                GP_HIP(hipStreamSynchronize(h->stream));
+                kept = std::move(live);
+                live = {};
+                return 0;
+            };
             GP_TRY(summary_seal(h->stream, &s->sum, s->irf_sum, N));
-            *cr->keep = std::move(s->sum);
+            k.sum = std::move(s->sum);
             s->sum = SummaryState{};
-            if (cr->keep_ppc) {
+            if (ppc) {
                 GP_TRY(ppc_seal(h->stream, &s->ppc));
-                *cr->keep_ppc = std::move(s->ppc);
+                k.ppc = std::move(s->ppc);
                 s->ppc = PpcState{};
             }
-            if (cr->keep_rank) {
+            if (ranks) GP_TRY(hand_over(k.rank, s->rank));
+            if (score) GP_TRY(hand_over(k.score, s->score));
+            if (shape) GP_TRY(hand_over(k.shape, s->shape));
+            if (sumscore) GP_TRY(hand_over(k.sumscore, s->sumscore));
+            if (equate) GP_TRY(hand_over(k.equate, s->equate));
+            if (loo) {
                 GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_rank = std::move(s->rank);
-                s->rank = RankState{};
-            }
-            if (cr->keep_score) {
-                GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_score = std::move(s->score);
-                s->score = ScoreState{};
-            }
-            if (cr->keep_shape) {
-                GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_shape = std::move(s->shape);
-                s->shape = ShapeState{};
-            }
-            if (cr->keep_sumscore) {
-                GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_sumscore = std::move(s->sumscore);
-                s->sumscore = SumscoreState{};
-            }
-            if (cr->keep_equate) {
-                GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_equate = std::move(s->equate);
-                s->equate = EquateState{};
-            }
-            if (cr->keep_loo) {
-                GP_HIP(hipStreamSynchronize(h->stream));
-                *cr->keep_loo = s->loo;
+                k.loo = s->loo;
                 s->loo = LooState{};
             }
             return 0;
@@ -2511,26 +2508,19 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
     if (!rc) rc = store_sync(0);
     if (!rc && summarise)
         rc = cr ? gpirt_sampler_summary_enable_planned(s, sm->parts | GPIRT_SUM_DIAG, S_it) : gpirt_sampler_summary_enable(s, sm->parts);
-    const bool ppc = cr && cr->keep_ppc;
     if (!rc && ppc) rc = gpirt_sampler_ppc_enable(s, 1);
-    if (!rc && ppc && cr->pairs) rc = gpirt_sampler_ppc_pairs_enable(s, 1);
-    if (!rc && ppc && cr->bins) rc = gpirt_sampler_ppc_bins_enable(s, cr->bins->h, cr->bins->cuts, 1);
-    if (!rc && ppc && cr->dif) rc = gpirt_sampler_ppc_dif_enable(s, cr->dif->G, cr->dif->groups, cr->dif->h, cr->dif->cuts, 1);
-    const bool ranks = cr && cr->keep_rank;
-    if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, cr->ranks->pivots, cr->ranks->n_pivots, cr->ranks->pairwise);
-    const bool score = cr && cr->keep_score;
-    if (!rc && score) rc = gpirt_sampler_score_enable(s, cr->y_new, cr->n_new);
-    if (!rc && score && cr->predict) rc = gpirt_sampler_score_predict_enable(s, 1);
+    if (!rc && run.pairs) rc = gpirt_sampler_ppc_pairs_enable(s, 1);
+    if (!rc && run.bins) rc = gpirt_sampler_ppc_bins_enable(s, run.bins->h, run.bins->cuts, 1);
+    if (!rc && run.dif) rc = gpirt_sampler_ppc_dif_enable(s, run.dif->G, run.dif->groups, run.dif->h, run.dif->cuts, 1);
+    if (!rc && ranks) rc = gpirt_sampler_rank_enable(s, run.ranks->pivots, run.ranks->n_pivots, run.ranks->pairwise);
+    if (!rc && score) rc = gpirt_sampler_score_enable(s, run.h_y_new, run.n_new);
+    if (!rc && run.predict) rc = gpirt_sampler_score_predict_enable(s, 1);
     // (gbar holds a curve from the first step's draw_fstar on; no draw is accumulated before that)
-    const bool shape = cr && cr->keep_shape;
-    if (!rc && shape) rc = gpirt_sampler_shape_enable(s, cr->shape->k_half, cr->shape->tols, cr->shape->n_tols, 1);
-    const bool sumscore = cr && cr->keep_sumscore;
-    if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, cr->sumscore->items, 1);
-    const bool equate = cr && cr->keep_equate;
-    if (!rc && equate) rc = gpirt_sampler_equate_enable(s, cr->equate->x, cr->equate->y, 1);
-    if (!rc && shape && cr->order) rc = gpirt_sampler_shape_order_enable(s, 1);
-    const bool loo = cr && cr->keep_loo;
-    if (!rc && loo) rc = gpirt_sampler_loo_enable(s, cr->loo_T, cr->loo_tail, 1);
+    if (!rc && shape) rc = gpirt_sampler_shape_enable(s, run.shape->k_half, run.shape->tols, run.shape->n_tols, 1);
+    if (!rc && sumscore) rc = gpirt_sampler_sumscore_enable(s, run.sumscore->items, 1);
+    if (!rc && equate) rc = gpirt_sampler_equate_enable(s, run.equate->x, run.equate->y, 1);
+    if (!rc && run.order) rc = gpirt_sampler_shape_order_enable(s, 1);
+    if (!rc && loo) rc = gpirt_sampler_loo_enable(s, cr->draws, (int)run.loo->tail, 1);
 
     if (replay) {
         // R-stream replay is item-sequential and drains the stream every iteration anyway (the cursor comes back to the
@@ -2776,20 +2766,33 @@ int gpirt_chains_combine(gpirt_handle_t h, int chains, const void* const* d_stat
     return chains_combine(h, chains, d_states, signs, align, h_irfs, pooled, diag);
 }
 
-// gpirt_mcmc_chains and gpirt_mcmc_quantiles: the arguments checked as gpirt_mcmc_chains checks them, C chains one after
-// another on one handle (chain c: seed gpirt_chain_seed(seed, c), column c of h_theta0; rs != NULL: R's stream, one chain),
-// each state keeping pooled->parts | extra (with DIAG planned for S), then gpirt_chains_combine with align and, with q,
-// gpirt_summary_quantiles of the same states.  One loop, so the quantiles' chains are gpirt_mcmc_chains's chains.
+// gpirt_mcmc_chains (run == NULL) and gpirt_mcmc_run: the arguments checked as gpirt_mcmc_chains checks them, then run's
+// structs; C chains one after another on one handle (chain c: seed gpirt_chain_seed(seed, c), column c of h_theta0;
+// run->rs != NULL: R's stream, one chain), each state keeping pooled->parts (with DIAG planned for S; with the quantiles also
+// THETA_HIST | IRF_BAND) and accumulating the run's analyses; then gpirt_chains_combine with align and every analysis's
+// combine over the same states.  One loop, so every analysis's chains are gpirt_mcmc_chains's chains.
 static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, int extra, gpirt_rstream_t rs,
-                      gpirt_quantiles* q, gpirt_ppc* ppc = nullptr, gpirt_ranks* ranks = nullptr,
-                      const double* h_y_new = nullptr, int64_t n_new = 0, gpirt_score* score = nullptr,
-                      gpirt_score_predict* predict = nullptr, gpirt_ppc_pairs* pairs = nullptr, gpirt_ppc_bins* bins = nullptr,
-                      gpirt_shape* shape = nullptr, gpirt_sumscore* sumscore = nullptr, gpirt_ppc_dif* dif = nullptr,
-                      gpirt_equate* equate = nullptr, gpirt_loo* loo = nullptr, gpirt_shape_order* order = nullptr)
+                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, const gpirt_run* run)
 {
+    const gpirt_run none{};
+    if (!run) run = &none;
+    gpirt_quantiles* const q = run->quantiles;
+    gpirt_ppc* const ppc = run->ppc;
+    gpirt_ranks* const ranks = run->ranks;
+    const double* const h_y_new = run->h_y_new;
+    const int64_t n_new = run->n_new;
+    gpirt_score* const score = run->score;
+    gpirt_score_predict* const predict = run->predict;
+    gpirt_ppc_pairs* const pairs = run->pairs;
+    gpirt_ppc_bins* const bins = run->bins;
+    gpirt_shape* const shape = run->shape;
+    gpirt_sumscore* const sumscore = run->sumscore;
+    gpirt_ppc_dif* const dif = run->dif;
+    gpirt_equate* const equate = run->equate;
+    gpirt_loo* const loo = run->loo;
+    gpirt_shape_order* const order = run->order;
     GP_ARG(h_y && h_theta0 && h_pm && h_ps && h_step && opts && pooled);
     GP_ARG(n > 0 && m > 0 && chains >= 1 && S_it >= 1 && B_it >= 0);
     // the pooled outputs are checked now, before any chain runs (the combine checks them again against the states)
@@ -2801,18 +2804,18 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(!((pooled->h_f_mean || pooled->h_f_var) && !(parts & GPIRT_SUM_F)));
     }
     if (diag) {
-        GP_ARG(diag->reserved[0] == 0 && diag->reserved[1] == 0 && diag->reserved[2] == 0 && diag->reserved[3] == 0);
+        GP_ARG(all_zero(diag->reserved));
         GP_ARG((parts & GPIRT_SUM_F) || !(diag->h_f_rhat || diag->h_f_ess || diag->h_f_mcse));
     }
     if (q) {
-        GP_ARG(q->reserved0 == 0 && q->reserved[0] == 0 && q->reserved[1] == 0 && q->reserved[2] == 0 && q->reserved[3] == 0);
+        GP_ARG(q->reserved0 == 0 && all_zero(q->reserved));
         GP_ARG(q->nprobs >= 0 && (q->nprobs == 0 || q->probs));
         for (int p = 0; p < q->nprobs; ++p) GP_ARG(q->probs[p] >= 0.0 && q->probs[p] <= 1.0);
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
     }
-    if (ppc) GP_ARG(ppc->reserved[0] == 0 && ppc->reserved[1] == 0 && ppc->reserved[2] == 0 && ppc->reserved[3] == 0);
+    if (ppc) GP_ARG(all_zero(ppc->reserved));
     if (ranks) {
-        GP_ARG(ranks->reserved0 == 0 && ranks->reserved[0] == 0 && ranks->reserved[1] == 0 && ranks->reserved[2] == 0 && ranks->reserved[3] == 0);
+        GP_ARG(ranks->reserved0 == 0 && all_zero(ranks->reserved));
         GP_ARG(ranks->nprobs >= 0 && (ranks->nprobs == 0 || ranks->probs));
         for (int p = 0; p < ranks->nprobs; ++p) GP_ARG(ranks->probs[p] >= 0.0 && ranks->probs[p] <= 1.0);
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
@@ -2829,7 +2832,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_ARG(!(ranks->lt && !ranks->pairwise));
     }
     if (score) {
-        GP_ARG(score->reserved0 == 0 && score->reserved[0] == 0 && score->reserved[1] == 0 && score->reserved[2] == 0 && score->reserved[3] == 0);
+        GP_ARG(score->reserved0 == 0 && all_zero(score->reserved));
         GP_ARG(score->nprobs >= 0 && (score->nprobs == 0 || score->probs));
         for (int p = 0; p < score->nprobs; ++p) GP_ARG(score->probs[p] >= 0.0 && score->probs[p] <= 1.0);
         if (!h_y_new || n_new < 1 || n_new > GPIRT_SCORE_MAX_N) {
@@ -2843,7 +2846,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     }
     if (predict) {
         GP_ARG(score);
-        GP_ARG(predict->reserved0 == 0 && predict->reserved[0] == 0 && predict->reserved[1] == 0 && predict->reserved[2] == 0 && predict->reserved[3] == 0);
+        GP_ARG(predict->reserved0 == 0 && all_zero(predict->reserved));
         if (predict->top < 1 || predict->top > GPIRT_PREDICT_MAX_TOP) {
             set_error("prediction: top = %d is outside 1..%d", predict->top, GPIRT_PREDICT_MAX_TOP);
             return GPIRT_E_ARG;
@@ -2851,7 +2854,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     }
     if (pairs) {
         GP_ARG(ppc);
-        GP_ARG(pairs->reserved0 == 0 && pairs->reserved[0] == 0 && pairs->reserved[1] == 0 && pairs->reserved[2] == 0 && pairs->reserved[3] == 0);
+        GP_ARG(pairs->reserved0 == 0 && all_zero(pairs->reserved));
         if (pairs->top < 1 || pairs->top > GPIRT_PAIRS_MAX_TOP) {
             set_error("pairwise PPC: top = %d is outside 1..%d", pairs->top, GPIRT_PAIRS_MAX_TOP);
             return GPIRT_E_ARG;
@@ -2860,7 +2863,7 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
     }
     if (bins) {
         GP_ARG(ppc);
-        GP_ARG(bins->reserved[0] == 0 && bins->reserved[1] == 0 && bins->reserved[2] == 0 && bins->reserved[3] == 0);
+        GP_ARG(all_zero(bins->reserved));
         if (bins->top < 1 || bins->top > GPIRT_BINS_MAX_TOP) {
             set_error("theta-binned PPC: top = %d is outside 1..%d", bins->top, GPIRT_BINS_MAX_TOP);
             return GPIRT_E_ARG;
@@ -2868,17 +2871,17 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_TRY(bin_check_cuts(bins->h, bins->cuts));
     }
     if (shape) {
-        GP_ARG(shape->reserved[0] == 0 && shape->reserved[1] == 0 && shape->reserved[2] == 0 && shape->reserved[3] == 0);
+        GP_ARG(all_zero(shape->reserved));
         GP_ARG((int64_t)chains * S_it < ((int64_t)1 << 32));
         GP_TRY(shape_check(shape->k_half, shape->tols, shape->n_tols));
     }
     if (sumscore) {
-        GP_ARG(sumscore->reserved[0] == 0 && sumscore->reserved[1] == 0 && sumscore->reserved[2] == 0 && sumscore->reserved[3] == 0);
+        GP_ARG(all_zero(sumscore->reserved));
         GP_TRY(sumscore_check(m, sumscore->items, nullptr));
     }
     if (dif) {
         GP_ARG(ppc);
-        GP_ARG(dif->reserved0 == 0 && dif->reserved[0] == 0 && dif->reserved[1] == 0 && dif->reserved[2] == 0 && dif->reserved[3] == 0);
+        GP_ARG(dif->reserved0 == 0 && all_zero(dif->reserved));
         if (dif->top < 1 || dif->top > GPIRT_DIF_MAX_TOP) {
             set_error("group-wise PPC: top = %d is outside 1..%d", dif->top, GPIRT_DIF_MAX_TOP);
             return GPIRT_E_ARG;
@@ -2887,13 +2890,13 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
         GP_TRY(bin_check_cuts(dif->h, dif->cuts));
     }
     if (equate) {
-        GP_ARG(equate->reserved[0] == 0 && equate->reserved[1] == 0 && equate->reserved[2] == 0 && equate->reserved[3] == 0);
+        GP_ARG(all_zero(equate->reserved));
         GP_TRY(equate_check(m, equate->x, equate->y, nullptr, nullptr));
     }
     if (order) {
-        GP_ARG(order->reserved[0] == 0 && order->reserved[1] == 0 && order->reserved[2] == 0 && order->reserved[3] == 0);
+        GP_ARG(all_zero(order->reserved));
         if (!shape) {
-            set_error("gpirt_mcmc_order: the order posteriors need the shape posteriors (shape is NULL)");
+            set_error("gpirt_mcmc_run: the order posteriors need the shape posteriors (shape is NULL)");
             return GPIRT_E_ARG;
         }
         if (m < 2 || m > GPIRT_ORDER_MAX_M) {
@@ -2901,118 +2904,88 @@ static int chains_run(const double* h_y, int64_t n, int64_t m, const double* h_t
             return GPIRT_E_ARG;
         }
         if (order->top < 1 || order->top > GPIRT_ORDER_MAX_TOP) {
-            set_error("gpirt_mcmc_order: top = %d is outside 1..%d", order->top, GPIRT_ORDER_MAX_TOP);
+            set_error("gpirt_mcmc_run: top = %d is outside 1..%d", order->top, GPIRT_ORDER_MAX_TOP);
             return GPIRT_E_ARG;
         }
     }
     int64_t loo_M = 0;
     if (loo) {
-        GP_ARG(loo->reserved[0] == 0 && loo->reserved[1] == 0 && loo->reserved[2] == 0 && loo->reserved[3] == 0);
+        GP_ARG(all_zero(loo->reserved));
         GP_ARG(loo->top >= 1 && loo->top <= GPIRT_LOO_MAX_TOP && loo->tail >= 0 && loo->tail <= GPIRT_LOO_MAX_TAIL);
         GP_TRY(loo_tail_length((int64_t)chains * S_it, (int)loo->tail, &loo_M));
     }
-    const gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};    // the combine overwrites h / cuts
-    const gpirt_ppc_dif dif_in = dif ? *dif : gpirt_ppc_dif{};
-    const gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
+    // what the chains read: the run with its in/out structs as they are now (the combines overwrite pivots / n_pivots, h /
+    // cuts, k_half / tols)
+    gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};
+    gpirt_ppc_bins bins_in = bins ? *bins : gpirt_ppc_bins{};
+    gpirt_ppc_dif dif_in = dif ? *dif : gpirt_ppc_dif{};
+    gpirt_shape shape_in = shape ? *shape : gpirt_shape{};
+    gpirt_run in = *run;
+    if (ranks) in.ranks = &ranks_in;
+    if (bins) in.bins = &bins_in;
+    if (dif) in.dif = &dif_in;
+    if (shape) in.shape = &shape_in;
     gpirt_handle_t h = nullptr;
     GP_TRY(gpirt_create_own_stream(&h, opts->device));
     { const long long trip = gpirt_debug_take_mcmc_trip(); if (trip > 0) h->trip_guard_at = trip; }
-    std::vector<SummaryState> keep((size_t)chains);
-    std::vector<PpcState> keep_ppc(ppc ? (size_t)chains : 0);
-    std::vector<RankState> keep_rank(ranks ? (size_t)chains : 0);
-    std::vector<ScoreState> keep_score(score ? (size_t)chains : 0);
-    std::vector<ShapeState> keep_shape(shape ? (size_t)chains : 0);
-    std::vector<SumscoreState> keep_sumscore(sumscore ? (size_t)chains : 0);
-    std::vector<EquateState> keep_equate(equate ? (size_t)chains : 0);
-    LooState loo_pool, loo_chain;                                      // the pooled state and the chain that just finished
-    const gpirt_ranks ranks_in = ranks ? *ranks : gpirt_ranks{};       // the combine overwrites pivots / n_pivots
+    std::vector<ChainKeep> keep((size_t)chains);
+    LooState& loo_pool = keep[0].loo;                                  // the pooled state: chain 0's, the others merged in
     const int total = S_it + B_it;
     int rc = 0;
     for (int c = 0; c < chains && !rc; ++c) {
         gpirt_options o = *opts;
         o.seed = gpirt_chain_seed(opts->seed, c);
         gpirt_summary sm{};
-        sm.parts = parts | extra;
-        const ChainRun cr{ h, &keep[(size_t)c], c * total, chains * total, ppc ? &keep_ppc[(size_t)c] : nullptr,
-                           ranks ? &keep_rank[(size_t)c] : nullptr, &ranks_in,
-                           score ? &keep_score[(size_t)c] : nullptr, h_y_new, n_new, predict != nullptr, pairs != nullptr,
-                           bins ? &bins_in : nullptr, shape ? &keep_shape[(size_t)c] : nullptr, &shape_in,
-                           sumscore ? &keep_sumscore[(size_t)c] : nullptr, sumscore, dif ? &dif_in : nullptr,
-                           equate ? &keep_equate[(size_t)c] : nullptr, equate,
-                           loo ? (c == 0 ? &loo_pool : &loo_chain) : nullptr, (int64_t)chains * S_it, loo ? (int)loo->tail : 0,
-                           order != nullptr };
+        sm.parts = parts | (q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0);
+        ChainKeep& k = keep[(size_t)c];
+        const ChainRun cr{ h, c * total, chains * total, (int64_t)chains * S_it, &in, &k };
         std::vector<double> irf_c((size_t)GPIRT_NGRID * (size_t)m);
-        rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, rs, tick, tick_ctx,
+        rc = mcmc_run(h_y, n, m, h_theta0 + (int64_t)c * n, S_it, B_it, h_pm, h_ps, h_step, &o, run->rs, tick, tick_ctx,
                       h_theta_draws ? h_theta_draws + (int64_t)c * (S_it + 1) * n : nullptr,
                       h_beta_draws ? h_beta_draws + (int64_t)c * 2 * m * (S_it + 1) : nullptr,
                       h_f_draws ? h_f_draws + (int64_t)c * n * m * (S_it + 1) : nullptr, irf_c.data(), &sm, &cr);
         if (loo && c > 0) {                                  // pooled in chain order; the chain's state goes at once
-            if (!rc && loo_chain.block) rc = launch_loo_merge(h->stream, loo_pool.block, loo_chain.block, n, m, loo_M);
+            if (!rc && k.loo.block) rc = launch_loo_merge(h->stream, loo_pool.block, k.loo.block, n, m, loo_M);
             if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) { set_error("LOO merge: the stream failed"); rc = GPIRT_E_HIP; }
-            loo_free(&loo_chain);
+            loo_free(&k.loo);
         }
     }
     std::vector<const void*> st((size_t)chains);
-    for (int c = 0; c < chains; ++c) st[(size_t)c] = keep[(size_t)c].block;
     std::vector<int> sg((size_t)chains, 1);
-    if (!rc) rc = chains_combine(h, chains, st.data(), nullptr, align, h_irfs, pooled, diag, sg.data());
+    // st[] := the block that `block` picks from every chain's kept states, then `combine` on them
+    auto pool = [&](auto block, auto combine) -> int {
+        for (int c = 0; c < chains; ++c) st[(size_t)c] = block(keep[(size_t)c]);
+        return combine(st.data());
+    };
+    using K = const ChainKeep&;
+    using St = const void* const*;
+    if (!rc) rc = pool([](K k) { return k.sum.block; }, [&](St s) { return chains_combine(h, chains, s, nullptr, align, h_irfs, pooled, diag, sg.data()); });
     if (!rc && q) rc = summary_quantiles(h, chains, st.data(), nullptr, align, q);
-    if (!rc && ppc) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].block;
-        rc = ppc_combine(h, chains, st.data(), ppc);
-    }
-    if (!rc && pairs) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].pairs.block;
-        rc = pair_combine(h, chains, st.data(), pairs);
-    }
-    if (!rc && bins) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].bins.block;
-        rc = bin_combine(h, chains, st.data(), sg.data(), bins);
-    }
-    if (!rc && dif) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_ppc[(size_t)c].dif.block;
-        rc = dif_combine(h, chains, st.data(), sg.data(), dif);
-    }
-    for (auto& k : keep) summary_free(&k);
-    if (!rc && ranks) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_rank[(size_t)c].block;
-        rc = rank_combine(h, chains, st.data(), sg.data(), ranks);
-    }
-    if (!rc && score) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].block;
-        rc = score_combine(h, chains, st.data(), sg.data(), score);
-    }
-    if (!rc && predict) {                                    // (no signs: both sums run over the whole grid)
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_score[(size_t)c].pred.block;
-        rc = pred_combine(h, chains, st.data(), predict);
-    }
-    if (!rc && shape) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].block;
-        rc = shape_combine(h, chains, st.data(), sg.data(), shape);
-    }
-    if (!rc && order) {                                    // no signs: the pair block is the same under theta -> -theta
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_shape[(size_t)c].order.block;
-        rc = order_combine(h, chains, st.data(), order);
-    }
-    if (!rc && sumscore) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_sumscore[(size_t)c].block;
-        rc = sumscore_combine(h, chains, st.data(), sg.data(), sumscore);
-    }
-    for (auto& k : keep_shape) shape_free(&k);
-    if (!rc && equate) {
-        for (int c = 0; c < chains; ++c) st[(size_t)c] = keep_equate[(size_t)c].block;
-        rc = equate_combine(h, chains, st.data(), equate);
-    }
+    if (!rc && ppc) rc = pool([](K k) { return k.ppc.block; }, [&](St s) { return ppc_combine(h, chains, s, ppc); });
+    if (!rc && pairs) rc = pool([](K k) { return k.ppc.pairs.block; }, [&](St s) { return pair_combine(h, chains, s, pairs); });
+    if (!rc && bins) rc = pool([](K k) { return k.ppc.bins.block; }, [&](St s) { return bin_combine(h, chains, s, sg.data(), bins); });
+    if (!rc && dif) rc = pool([](K k) { return k.ppc.dif.block; }, [&](St s) { return dif_combine(h, chains, s, sg.data(), dif); });
+    for (auto& k : keep) summary_free(&k.sum);
+    if (!rc && ranks) rc = pool([](K k) { return k.rank.block; }, [&](St s) { return rank_combine(h, chains, s, sg.data(), ranks); });
+    if (!rc && score) rc = pool([](K k) { return k.score.block; }, [&](St s) { return score_combine(h, chains, s, sg.data(), score); });
+    // (no signs: both sums of the prediction run over the whole grid)
+    if (!rc && predict) rc = pool([](K k) { return k.score.pred.block; }, [&](St s) { return pred_combine(h, chains, s, predict); });
+    if (!rc && shape) rc = pool([](K k) { return k.shape.block; }, [&](St s) { return shape_combine(h, chains, s, sg.data(), shape); });
+    // (no signs: the pair block is the same under theta -> -theta)
+    if (!rc && order) rc = pool([](K k) { return k.shape.order.block; }, [&](St s) { return order_combine(h, chains, s, order); });
+    if (!rc && sumscore) rc = pool([](K k) { return k.sumscore.block; }, [&](St s) { return sumscore_combine(h, chains, s, sg.data(), sumscore); });
+    for (auto& k : keep) shape_free(&k.shape);
+    if (!rc && equate) rc = pool([](K k) { return k.equate.block; }, [&](St s) { return equate_combine(h, chains, s, equate); });
     if (!rc && loo) {
         const void* one = loo_pool.block;
         rc = loo_combine(h, 1, &one, loo);
     }
     loo_free(&loo_pool);
-    for (auto& k : keep_sumscore) sumscore_free(&k);
-    for (auto& k : keep_equate) equate_free(&k);
-    for (auto& k : keep_ppc) ppc_free(&k);
-    for (auto& k : keep_rank) rank_free(&k);
-    for (auto& k : keep_score) score_free(&k);
+    for (auto& k : keep) sumscore_free(&k.sumscore);
+    for (auto& k : keep) equate_free(&k.equate);
+    for (auto& k : keep) ppc_free(&k.ppc);
+    for (auto& k : keep) rank_free(&k.rank);
+    for (auto& k : keep) score_free(&k.score);
     gpirt_destroy(h);
     return rc;
 }
@@ -3028,7 +3001,7 @@ int gpirt_mcmc_chains(const double* h_y, int64_t n, int64_t m, const double* h_t
         return GPIRT_E_ARG;
     }
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, 0, nullptr, nullptr);
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, nullptr);
 }
 
 // ---- quantiles --------------------------------------------------------------------------------------------------------
@@ -3045,237 +3018,20 @@ int gpirt_summary_quantiles(gpirt_handle_t h, int chains, const void* const* d_s
     return summary_quantiles(h, chains, d_states, signs, align, q);
 }
 
-int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                         const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                         gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                         double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q)
-{
-    GP_ARG(opts && q);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_quantiles needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND, rs, q);
-}
-
-// ---- posterior predictive checks ------------------------------------------------------------------------------------
-int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
+// ---- the chains with any of the analyses ------------------------------------------------------------------------------
+int gpirt_mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
                    const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                   gpirt_ppc* ppc)
+                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_run* run)
 {
-    GP_ARG(opts && ppc);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_ppc needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
+    GP_ARG(opts && run);
+    GP_ARG(all_zero(run->reserved));
+    if (run->rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
+        set_error("gpirt_mcmc_run needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
         return GPIRT_E_ARG;
     }
     return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc);
-}
-
-// ---- rank posteriors ------------------------------------------------------------------------------------------------------
-int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                     gpirt_ppc* ppc, gpirt_ranks* ranks)
-{
-    GP_ARG(opts && ranks);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_ranks needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks);
-}
-
-// ---- scoring new respondents ------------------------------------------------------------------------------------------------
-int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score)
-{
-    GP_ARG(opts && score);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_score needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score);
-}
-
-// ---- predicting the new respondents' unseen answers ----------------------------------------------------------------------------
-int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                       const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                       double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                       gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                       gpirt_score_predict* predict)
-{
-    GP_ARG(opts && score && predict);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_predict needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict);
-}
-
-// ---- the pairwise item checks ---------------------------------------------------------------------------------------------------
-int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs)
-{
-    GP_ARG(opts && ppc && pairs);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_pairs needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs);
-}
-
-// ---- the theta-binned item fit ---------------------------------------------------------------------------------------------------
-int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                    const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                    double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                    gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                    gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins)
-{
-    GP_ARG(opts && ppc && bins);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_bins needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins);
-}
-
-// ---- the IRF shape posteriors ---------------------------------------------------------------------------------------------------
-int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape)
-{
-    GP_ARG(opts && shape);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_shape needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape);
-}
-
-// ---- the sum-score posteriors -----------------------------------------------------------------------------------------------------
-int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                        const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                        gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                        double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                        gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                        gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
-                        gpirt_sumscore* sumscore)
-{
-    GP_ARG(opts && sumscore);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_sumscore needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore);
-}
-
-// ---- the group-wise item fit --------------------------------------------------------------------------------------------------------
-int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                   const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                   gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                   gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
-                   gpirt_sumscore* sumscore, gpirt_ppc_dif* dif)
-{
-    GP_ARG(opts && ppc && dif);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_dif needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif);
-}
-
-// ---- the two-form score equating ------------------------------------------------------------------------------------------------------
-int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                      const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                      double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                      gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                      gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
-                      gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate)
-{
-    GP_ARG(opts && equate);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_equate needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate);
-}
-
-// ---- PSIS-LOO -------------------------------------------------------------------------------------------------------------------------
-int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                   const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                   gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                   gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
-                   gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo)
-{
-    GP_ARG(opts && loo);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_loo needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate, loo);
-}
-
-// ---- the item-pair order posteriors -------------------------------------------------------------------------------------------------
-int gpirt_mcmc_order(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains, int S_it, int B_it,
-                     const double* h_pm, const double* h_ps, const double* h_step, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
-                     double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_rstream_t rs, gpirt_quantiles* q,
-                     gpirt_ppc* ppc, gpirt_ranks* ranks, const double* h_y_new, int64_t n_new, gpirt_score* score,
-                     gpirt_score_predict* predict, gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape,
-                     gpirt_sumscore* sumscore, gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo,
-                     gpirt_shape_order* order)
-{
-    GP_ARG(opts && order);
-    if (rs ? (opts->rng_kind != GPIRT_RNG_RSTREAM || chains != 1) : opts->rng_kind != GPIRT_RNG_ITEM) {
-        set_error("gpirt_mcmc_order needs GPIRT_RNG_ITEM, or GPIRT_RNG_RSTREAM with rs and one chain");
-        return GPIRT_E_ARG;
-    }
-    return chains_run(h_y, n, m, h_theta0, chains, S_it, B_it, h_pm, h_ps, h_step, opts, align, tick, tick_ctx, h_theta_draws,
-                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, q ? GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND : 0, rs, q,
-                      ppc, ranks, h_y_new, n_new, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order);
+                      h_beta_draws, h_f_draws, h_irfs, pooled, diag, run);
 }
 
 }  // extern "C"

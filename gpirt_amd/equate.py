@@ -1,7 +1,7 @@
 """Two forms at once, without stored draws: the joint distribution of the sum scores on two disjoint forms X and Y, the
 equipercentile equivalents of each form's scores on the other's scale (IRT observed-score equating), the concordance tables, the
 correlation of the two scores and the agreement of pass / fail decisions (include/gpirt_hip.h, "Two-form score equating":
-gpirt_sampler_equate_*, gpirt_equate_combine, gpirt_mcmc_equate; csrc/equate.hip).
+gpirt_sampler_equate_*, gpirt_equate_combine, gpirt_run.equate; csrc/equate.hip).
 
 Per draw the device runs the sum-score recursion once per form and contracts the two score tables over the grid in one fp64
 matrix-core product: J[s, t] = sum_k (w_k A_X[k, s]) A_Y[k, t].  It keeps the JOINT and normalises once at the end, so pooling
@@ -94,7 +94,7 @@ def _raw_shape(name, m, Mx, My):
 # ------------------------------------------------------------------------------------------------------ the device ---
 def struct(m: int, Mx: int, My: int, mask_x=None, mask_y=None):
     """A gpirt_equate asking for every raw array, and the host arrays behind it (kept alive by the caller).  The masks (m bytes
-    each) are read by gpirt_mcmc_equate; gpirt_equate_combine ignores them."""
+    each) are read by gpirt_mcmc_run; gpirt_equate_combine ignores them."""
     r = _lib.Equate()
     arrays = {}
     for k, (name, dt) in enumerate(EQUATE_RAW):

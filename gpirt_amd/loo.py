@@ -1,6 +1,6 @@
 """PSIS-LOO without stored draws: leave-one-out cross-validation by Pareto-smoothed importance sampling for every observed cell,
 its Pareto k diagnostic and the comparison of two models (include/gpirt_hip.h, "PSIS-LOO": gpirt_sampler_loo_*,
-gpirt_loo_combine, gpirt_mcmc_loo; csrc/loo.hip).
+gpirt_loo_combine, gpirt_run.loo; csrc/loo.hip).
 
 Per draw the device keeps, per cell, the K = M + 1 largest keys kappa = -y (f + mu) in a min-heap and the sums of the importance
 ratios of everything else; at the end one wave per cell sorts the kept keys and fits the generalised Pareto tail.  `struct` /

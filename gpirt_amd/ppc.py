@@ -1,5 +1,5 @@
 """Posterior predictive checks of items, respondents and the whole matrix without stored draws (include/gpirt_hip.h,
-"posterior predictive checks": gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc; csrc/ppc.hip).
+"posterior predictive checks": gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_run.ppc; csrc/ppc.hip).
 
 For every sampling draw the device replicates the response matrix -- yrep_ij = +1 if u_ij < plogis(f_ij + mu_ij), else -1,
 u_ij the item-RNG uniform of (seed, iter, ST_PPC, item0 + j, i) -- and compares, per item, per respondent and overall, the
@@ -781,7 +781,7 @@ def _dif_shape(kind, m, G, B):
 
 
 def dif_struct(m: int, G: int, cuts=DEFAULT_CUTS, top=DEFAULT_DIF_TOP, groups=None):
-    """A gpirt_ppc_dif with the cuts (and the group codes, for gpirt_mcmc_dif) and host arrays for every output, and those
+    """A gpirt_ppc_dif with the cuts (and the group codes, for gpirt_mcmc_run) and host arrays for every output, and those
     arrays (kept alive by the caller)."""
     cuts = check_cuts(cuts)
     B = 2 * len(cuts) + 1

@@ -1,5 +1,5 @@
 """Quantiles of long chains without their draws (include/gpirt_hip.h GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND,
-gpirt_summary_quantiles, gpirt_mcmc_quantiles).
+gpirt_summary_quantiles, gpirt_run.quantiles).
 
 Every theta draw is a point of the fixed grid theta* = -5 + 0.01 k, k = 0..1000, so a count per (respondent, grid point)
 is the exact posterior of theta in n x 1001 counts however long the chain: exact quantiles, the median, the mode, exact

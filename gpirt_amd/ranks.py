@@ -1,5 +1,5 @@
 """Rank posteriors without stored draws: rank intervals, pivots, pairwise order (include/gpirt_hip.h, "rank posteriors":
-gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks; csrc/ranks.hip).
+gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_run.ranks; csrc/ranks.hip).
 
 Every sampled theta is a grid point -5 + 0.01 k, so a draw's ranks follow from a 1001-bin count and a prefix sum:
 less_i = #{k_j < k_i}, eq_i = #{k_j = k_i}, R2_i = 2 less_i + eq_i + 1 (twice the mid-rank).  The device accumulates, per
@@ -57,7 +57,7 @@ def close_pivots(n: int, pivots="median"):
 # ------------------------------------------------------------------------------------------------------ the device ---
 def struct(n: int, pivots="median", probs=DEFAULT_PROBS, pairwise=False, closed=None):
     """A gpirt_ranks asking for every output (lt with pairwise), and the host arrays behind it (kept alive by the
-    caller).  The struct's pivots are the ones given: gpirt_mcmc_ranks reads them; gpirt_rank_combine ignores them.
+    caller).  The struct's pivots are the ones given: gpirt_mcmc_run reads them; gpirt_rank_combine ignores them.
     closed: the closed set of a state block as it is (up to 32 positions), for gpirt_rank_combine: the arrays are sized
     by it and no positions are given."""
     if closed is not None:

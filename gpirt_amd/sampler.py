@@ -40,6 +40,16 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
     return o
 
 
+def _call_options(rng, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device) -> Options:
+    """The options of a whole call: the library's fast preset with this call's seed and device, or the keywords'."""
+    if preset == "fast":
+        o = _lib.fast_options()
+        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        o.device = -1 if device is None else int(device)
+        return o
+    return _options(rng, seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
+
+
 def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_prior_means=None,
               beta_prior_sds=None, beta_proposal_sds=None, theta_init=None, *, rng="reference",
               seed=1, rstream=None, theta_stabilise=False, fstar_fused=False, kstar_rank=0, device=None,
@@ -68,23 +78,23 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       (and with "f" in summaries, f) value, their per-block scalars and the chains reflected by the theta -> -theta
       alignment (align=False: none).  theta_init may be (C, n); by default chain 0 starts at RStream(seed).rnorm(n) as
       today and chain c at RStream(chain_seed(seed, c) & 0xFFFFFFFF).rnorm(n).  chains=None: one chain, as before.
-    quantiles: probabilities, e.g. (0.025, 0.5, 0.975) (gpirt_mcmc_quantiles, gpirt_amd.quantiles): every chain also
+    quantiles: probabilities, e.g. (0.025, 0.5, 0.975) (gpirt_run.quantiles, gpirt_amd.quantiles): every chain also
       keeps theta histograms and IRF bands on the device (and the DIAG accumulators), for chains=None too; rng="reference"
       runs one chain, the chain gpirt_mcmc_summary runs.  The result gains "summary" and "diagnostics" as with chains and
       "quantiles": probs, theta (len(probs) x n, exact), theta_median, theta_mode, theta_hist, theta_rhat (the
       rank-normalised bulk / tail / max), irf (len(probs) x 1001 x m, in probability, within 1/256), irf_p_mean (E[P]),
       reflected and scalars.  Memory: the band is 1001 x m x 256 x 4 bytes per chain on the device (1.05 GB at
       m = 1024), theta's histograms 3 x 1001 x n x 4 bytes.  quantiles=None leaves every other path as it is.
-    ppc: True adds posterior predictive checks (gpirt_mcmc_ppc, gpirt_amd.ppc): after every sampling iteration the
+    ppc: True adds posterior predictive checks (gpirt_run.ppc, gpirt_amd.ppc): after every sampling iteration the
       device replicates the response matrix from that draw and compares the yes count and the deviance of the replicate
       with the data's, per item, per respondent and overall, in O(n + m) memory.  The result gains "ppc": "item" and
       "respondent" (dicts of arrays: n_obs, obs_yes, rep_yes_mean, rep_yes_var, yes_ge, yes_gt, dev_obs_mean,
       dev_rep_mean, dev_ge, correct_mean, nonfinite, draws and the derived ppp_yes, ppp_yes_mid, ppp_dev) and "totals",
-      and -- the call runs gpirt_mcmc_chains's or gpirt_mcmc_quantiles's chains -- "summary" and "diagnostics" as with
+      and -- the call runs gpirt_mcmc_chains's chains -- "summary" and "diagnostics" as with
       chains (draws stacked per chain only with chains given).  The chain itself is untouched: the replicate draws from
       the counter-based generator under both RNG contracts and consumes nothing of R's stream.  ppc=None leaves every
       other path as it is.
-      ppc=dict(pairs=True, top=20) also checks every PAIR of items (gpirt_mcmc_pairs): "ppc" gains "pairs" with, per
+      ppc=dict(pairs=True, top=20) also checks every PAIR of items (gpirt_run.pairs): "ppc" gains "pairs" with, per
       ordered pair (a, b) as m x m arrays, the observed 2 x 2 table over the co-observed respondents (n_co, obs_n11,
       obs_n10, obs_n01, obs_n00), the replicates' (rep_n11_mean, rep_n11_var, rep_n10_mean, rep_n01_mean, rep_n00_mean),
       agree_obs / agree_rep_mean, log_or_obs and the posterior predictive p-values ppp_n11, ppp_agree, ppp_or with their
@@ -94,14 +104,14 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       device (71 MB at m = 1024) plus the int8 operands; n <= 65534.  ppc=True is exactly as without it.
       ppc=dict(bins=True, bins_top=20) (or bins=(d_1, ..., d_h), the positive cut points as hundredths of theta or theta
       values; True = gpirt_amd.ppc.DEFAULT_CUTS, nine bins of equal N(0, 1) probability) also checks every item's
-      response curve along theta (gpirt_mcmc_bins): each draw groups the respondents by the bin of their theta, and "ppc"
+      response curve along theta (gpirt_run.bins): each draw groups the respondents by the bin of their theta, and "ppc"
       gains "bins" with, per (bin, item) as B x m arrays, obs_rate (the empirical IRF), rep_rate, exp_rate, z_mean,
       ppp_cell, ppp_cell_mid and n_mean; per item ppp_chi2, ppp_chi2_mid, chi2_obs_mean and chi2_rep_mean (the binned
       chi-square of the data against the replicates'); per bin occupancy, bin_lo, bin_hi; "worst" lists the `bins_top`
       (1..64) items with the smallest ppp_chi2_mid -- the items whose curve the data contradict; bin_draws, bin_skipped (a
       draw with a theta off the grid or a non-finite g in an observed cell is skipped whole) and the raw sums and counts.
       pairs and bins may be asked for together.
-      ppc=dict(dif=groups) or dif=dict(groups=g, cuts=None, top=20) also checks measurement invariance (gpirt_mcmc_dif):
+      ppc=dict(dif=groups) or dif=dict(groups=g, cuts=None, top=20) also checks measurement invariance (gpirt_run.dif):
       groups holds one code per row of the prepared data (-1 = left out, 0 = the reference group, 1..G-1 the focal groups,
       G <= 4).  Each draw stratifies the respondents by the bin of their theta (cuts as for bins; None = DEFAULT_CUTS), and
       "ppc" gains "dif" with the group-wise empirical IRFs obs_rate, rep_rate, exp_rate (G x B x m) and occupancy (G x B);
@@ -111,7 +121,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       std_obs_mean, std_rep_mean; "flagged" lists the `top` (1..64) (item, focal group) pairs whose ppp_mh_mid lies farthest
       from 0.5; dif_draws, dif_skipped, group_size and the raw sums and counts.  n <= 65534.  It composes with pairs and bins.
     ranks: True, or dict(pivots="median", pairwise=False, probs=(0.025, 0.5, 0.975)), adds the rank posteriors
-      (gpirt_mcmc_ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
+      (gpirt_run.ranks, gpirt_amd.ranks): after every sampling iteration the device ranks that draw's theta (rank 1 =
       the smallest; ties take the mid-rank) and accumulates, in "ranks": rank_mean, rank_var, rank_quantiles
       (len(probs) x n, a rank-histogram bin's upper edge; exact for n <= 512), rank_bin_width, order (argsort of
       rank_mean), pivots (the positions asked for -- "median" and / or positions in 1..n, at most 16 --, closed under
@@ -122,7 +132,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       untouched under both RNG contracts.  "summary" and "diagnostics" come as with ppc.  ranks=None leaves every other
       path as it is.
     score: y_new (n_new x m), or dict(data=y_new, probs=(0.025, 0.5, 0.975)), scores respondents who are NOT in the fit
-      (gpirt_mcmc_score, gpirt_amd.score): y_new is coded +1 / -1 / NaN over the prepared data's m item columns (after
+      (gpirt_run.score, gpirt_amd.score): y_new is coded +1 / -1 / NaN over the prepared data's m item columns (after
       unanimous items were dropped; another width is a ValueError), 1 <= n_new <= 16384.  After every sampling iteration
       the device forms, from that draw's f*, each new respondent's normalised posterior over the theta grid and the log
       marginal likelihood of their answers, and accumulates them; "score" holds grid_post (n_new x 1001), theta_mean,
@@ -132,14 +142,14 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       pooled with the reflection "diagnostics" reports.  Nothing is drawn: the chain is untouched under both RNG contracts.
       "summary" and "diagnostics" come as with ranks.  score=None leaves every other path as it is.
       dict(data=y_new, predict=True, top=5) also predicts the answers those respondents have NOT given
-      (gpirt_mcmc_predict): "score" gains "predict" with p_yes (n_new x m: P(y_rj = +1 | y_new[r, :]), for every item),
+      (gpirt_run.predict): "score" gains "predict" with p_yes (n_new x m: P(y_rj = +1 | y_new[r, :]), for every item),
       info (n_new x m: the expected information, in nats, that the answer to item j carries about theta_r -- the mutual
       information under each draw, averaged over the draws; valid for non-monotone items), next_items and next_info
       (n_new x top: each respondent's UNANSWERED items by decreasing info, padded with -1 / NaN; 1 <= top <= 16), pred_draws,
       pred_skipped (a draw whose f* holds a NaN cell is skipped whole for the prediction) and the raw pred_sum, info_sum.
       Without predict the score= argument behaves exactly as before, and the scores themselves do not depend on it.
     shape: True, or dict(window=3.0, tols=(0.0, 0.25, 1.0), probs=(0.025, 0.5, 0.975), top=20), adds the shape posteriors of
-      the item response curves (gpirt_mcmc_shape, gpirt_amd.shape): after every sampling iteration the device reads that
+      the item response curves (gpirt_run.shape, gpirt_amd.shape): after every sampling iteration the device reads that
       draw's smooth curve g = k*^T S^-1 f + mu* (what draw_fstar draws f* around) and accumulates, per item, inside
       |theta| <= window (0.01..5.0): p_nonmonotone, p_increasing, p_decreasing, p_flat (len(tols) x m: the draw's largest fall
       and rise against each tolerance, in logits; at most 4), peak_quantiles and valley_quantiles (len(probs) x m, theta of
@@ -151,12 +161,12 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       Memory at m = 1024: 24 MB of accumulators per chain plus 8 MB each for the curve and the draw's information.  Nothing is
       drawn: the chain is untouched under both RNG contracts.  Reflected chains are reflected exactly on their accumulators.
       shape=None leaves every other path as it is.  Two more keys, order=True and order_top=20 (1..64), add the item-pair order
-      posteriors as out["shape"]["order"] (gpirt_mcmc_order, gpirt_amd.shape.order_finish): per tolerance and ordered pair of
+      posteriors as out["shape"]["order"] (gpirt_run.order, gpirt_amd.shape.order_finish): per tolerance and ordered pair of
       items p_above, p_cross, p_tied (curve a above b on the whole window, crossing it, neither), p_easier, depth_mean,
       easiness_mean / _sd, rank_mean, order, cross_items_mean, p_iio, cross_pairs_mean / _sd, worst (the order_top pairs that
       cross most often at the largest tolerance), draws, skipped and the raw arrays; 2 <= m <= 4096, 46 MB per chain at m = 1024.
     sumscore: True, or dict(items=None, probs=(0.025, 0.5, 0.975)), adds the posteriors of the SUM SCORE S = number of yes
-      answers on a form of items (gpirt_mcmc_sumscore, gpirt_amd.sumscore): after every sampling iteration the device runs
+      answers on a form of items (gpirt_run.sumscore, gpirt_amd.sumscore): after every sampling iteration the device runs
       the Lord-Wingersky recursion over the form's items at every grid point of that draw's f*.  items: None (all items),
       column indices or a boolean mask over the PREPARED data's columns (after unanimous items were dropped); at most 4096
       items; a wrong index or an empty form is a ValueError.  "sumscore" holds score_dist, score_dist_sd, score_cdf (M + 1: the
@@ -170,7 +180,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       33 MB per chain.  Nothing is drawn: the chain is untouched under both RNG contracts.  sumscore=None leaves every other
       path as it is.
     equate: dict(x=items_x, y=items_y, probs=(0.025, 0.5, 0.975), cuts=((cx, cy), ...)) relates the sum scores on TWO disjoint
-      forms (gpirt_mcmc_equate, gpirt_amd.equate): after every sampling iteration the device runs the sum-score recursion once
+      forms (gpirt_run.equate, gpirt_amd.equate): after every sampling iteration the device runs the sum-score recursion once
       per form and contracts the two score tables over the grid in one fp64 matrix-core product, the draw's joint distribution
       of (S_X, S_Y) for a N(0, 1) population.  x, y: column indices or boolean masks over the PREPARED data's columns, each
       non-empty, at most 2048 items, no column in both; cuts: up to 8 pairs of pass marks (a score >= the cut passes).  "equate"
@@ -182,7 +192,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
       f* holds a NaN in a column of either form is skipped whole), corr_draws, corr_skipped, eq_clamped, x_items, y_items and
       the raw accumulators.  Memory at M_X = M_Y = 1024: 75 MB per chain.  Nothing is drawn: the chain is untouched under both
       RNG contracts.  equate=None leaves every other path as it is.
-    loo: True or dict(tail=None, top=20) adds PSIS-LOO (gpirt_mcmc_loo, gpirt_amd.loo): after every sampling iteration the device
+    loo: True or dict(tail=None, top=20) adds PSIS-LOO (gpirt_run.loo, gpirt_amd.loo): after every sampling iteration the device
       enters each observed cell's key -y (f + mu) into the cell's heap of the M + 1 largest keys, T = chains x sample_iterations,
       M = min(T // 5, ceil(3 sqrt(T))) or `tail` (5 .. 1024); at the end one wave per cell fits the generalised Pareto tail.
       "loo" holds the totals elpd_loo, se_elpd_loo, p_loo, looic, se_looic, n_obs, lppd, k_threshold, k_good, k_bad, k_very_bad,
@@ -280,9 +290,10 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
         ppc = True
     if (quantiles is not None or ppc or ranks is not None or score is not None or shape is not None or sumscore is not None
             or equate is not None or loo is not None):
-        return _mcmc_quantiles(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream,
-                               preset, theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws,
-                               align, quantiles, bool(ppc), ranks, score, pairs, bins, shape, sumscore, dif, equate, loo)
+        return _mcmc_run(y, chains, sample_iterations, burn_iterations, pm, ps, st, theta_init, rng, seed, rstream, preset,
+                         theta_stabilise, fstar_fused, kstar_rank, device, progress, summaries, store_draws, align,
+                         dict(quantiles=quantiles, ppc=bool(ppc), ranks=ranks, score=score, pairs=pairs, bins=bins, shape=shape,
+                              sumscore=sumscore, dif=dif, equate=equate, loo=loo))
     if chains is not None:
         if rng == "reference":
             raise ValueError("chains need the item RNG (rng='item' or preset='fast')")
@@ -305,12 +316,7 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
     ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
     irf = np.empty((NGRID, m), order="F")
-    if preset == "fast":
-        o = _lib.fast_options()
-        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        o.device = -1 if device is None else int(device)
-    else:
-        o = _options(rng, seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
+    o = _call_options(rng, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device)
 
     def _tick(ctx, it, total):                                       # src/gpirtMCMC.cpp:64-66
         if progress:
@@ -354,87 +360,103 @@ def _keep(store_draws) -> set:
     return keep
 
 
-def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device,
-                 progress, summaries, store_draws, align):
-    """gpirtMCMC(chains=C): gpirt_mcmc_chains (include/gpirt_hip.h)."""
+def _chains_setup(y, nc, S, theta_init, rs, one, seed, summaries, store_draws, progress):
+    """What gpirt_mcmc_chains and gpirt_mcmc_run take alike, as one namespace: th0 (theta_init as nc columns), the draw
+    arrays th, be, ff (one: gpirt_mcmc's layout; else chain-major blocks of it), irf, the pooled summary's struct sm with its
+    `arrays` and `parts`, the diagnostics' struct d with its arrays darr, and the tick cb."""
+    from types import SimpleNamespace
     from . import chains as CH
-    lib = _lib.load()
     n, m = y.shape
-    S, B = int(S), int(B)
-    if nc < 1:
-        raise ValueError("chains must be >= 1")
     if theta_init is None:
-        th0 = CH.default_inits(n, nc, seed)
+        th0 = rs.rnorm(n)[None, :] if rs is not None else CH.default_inits(n, nc, seed)
     else:
         t = np.asarray(theta_init, dtype=np.float64)
         th0 = np.broadcast_to(t, (nc, n)) if t.shape == (n,) else t
         if th0.shape != (nc, n):
             raise ValueError("theta_init must be (n,) or (chains, n)")
-    th0 = np.ascontiguousarray(th0)                                  # n x C column-major: chain c's column at c n
+    p = SimpleNamespace(one=one, progress=progress)
+    p.th0 = np.ascontiguousarray(th0)                                # n x C column-major: chain c's column at c n
     keep = _keep(store_draws)
-    # chain-major blocks, each in gpirt_mcmc's layout; the returned arrays are views with the chain first
-    th = np.empty((nc, n, S + 1)) if "theta" in keep else None
-    be = np.empty((nc, S + 1, m, 2)) if "beta" in keep else None
-    ff = np.empty((nc, S + 1, m, n)) if "f" in keep else None
-    irf = np.empty((NGRID, m), order="F")
-    if preset == "fast":
-        o = _lib.fast_options()
-        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        o.device = -1 if device is None else int(device)
-    else:
-        o = _options("item", seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
-    parts = _lib.summary_parts(summaries if summaries is not None else 0) | _lib.SUM_THETA_BETA
-    sm = _lib.Summary()
-    sm.parts = parts
-    arrays = _summary_arrays(parts, n, m)
-    for k, a in arrays.items():
-        setattr(sm, "h_" + k, _ptr(a))
-    d, darr = CH.diag_struct(parts, n, m, nc)
+    if one:
+        p.th = np.empty((S + 1, n), order="F") if "theta" in keep else None
+        p.be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
+        p.ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
+    else:     # chain-major blocks, each in gpirt_mcmc's layout; the returned arrays are views with the chain first
+        p.th = np.empty((nc, n, S + 1)) if "theta" in keep else None
+        p.be = np.empty((nc, S + 1, m, 2)) if "beta" in keep else None
+        p.ff = np.empty((nc, S + 1, m, n)) if "f" in keep else None
+    p.irf = np.empty((NGRID, m), order="F")
+    p.parts = _lib.summary_parts(summaries if summaries is not None else 0) | _lib.SUM_THETA_BETA
+    p.sm = _lib.Summary()
+    p.sm.parts = p.parts
+    p.arrays = _summary_arrays(p.parts, n, m)
+    for k, a in p.arrays.items():
+        setattr(p.sm, "h_" + k, _ptr(a))
+    p.d, p.darr = CH.diag_struct(p.parts, n, m, nc)
 
     def _tick(ctx, it, total):
         if progress:
             print("\r%6.3f %% complete" % (100.0 * it / max(total, 1)), end="", flush=True)
         return 0
 
-    cb = _lib.TICK_FN(_tick)
+    p.cb = _lib.TICK_FN(_tick)
+    return p
+
+
+def _chains_args(y, p, nc, S, B, pm, ps, st, o, align):
+    """gpirt_mcmc_chains's twenty arguments (gpirt_mcmc_run's first twenty) from _chains_setup's namespace."""
     opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    rc = lib.gpirt_mcmc_chains(_ptr(y), n, m, _ptr(th0), nc, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                               int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d))
-    if progress:
+    return (_ptr(y), y.shape[0], y.shape[1], _ptr(p.th0), nc, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
+            int(bool(align)), p.cb, None, opt(p.th), opt(p.be), opt(p.ff), _ptr(p.irf), C.byref(p.sm), C.byref(p.d))
+
+
+def _chains_result(rc, p) -> dict:
+    """The call's return code checked; the draws (the chain first unless p.one), the IRFs, the pooled summary and the
+    diagnostics as gpirtMCMC returns them."""
+    from . import chains as CH
+    if p.progress:
         print("\r100.000 % complete")
     if rc > 0:
         raise RuntimeError("chol(): decomposition failed")
     check(rc)
-    summary = dict(arrays)
-    if parts & _lib.SUM_WAIC:
-        summary["totals"] = _totals(sm.totals)
-    return dict(theta=th.transpose(0, 2, 1) if th is not None else None,
-                beta=be.transpose(0, 3, 2, 1) if be is not None else None,
-                f=ff.transpose(0, 3, 2, 1) if ff is not None else None,
-                IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr))
+    summary = dict(p.arrays)
+    if p.parts & _lib.SUM_WAIC:
+        summary["totals"] = _totals(p.sm.totals)
+    th, be, ff = p.th, p.be, p.ff
+    if not p.one:
+        th = th.transpose(0, 2, 1) if th is not None else None
+        be = be.transpose(0, 3, 2, 1) if be is not None else None
+        ff = ff.transpose(0, 3, 2, 1) if ff is not None else None
+    return dict(theta=th, beta=be, f=ff, IRFs=p.irf, summary=summary, diagnostics=CH.diag_result(p.d, p.darr))
 
 
-def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
-                    kstar_rank, device, progress, summaries, store_draws, align, probs, with_ppc=False, ranks=None,
-                    score=None, pairs=None, bins=None, shape=None, sumscore=None, dif=None, equate=None, loo=None):
-    """gpirtMCMC(quantiles=...): gpirt_mcmc_quantiles (include/gpirt_hip.h).  chains=None: one chain, its draws in
-    gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  with_ppc: gpirt_mcmc_ppc, the same chains
-    with the posterior predictive checks (probs may then be None: no quantiles).  ranks (a dict): gpirt_mcmc_ranks, the
-    same chains with the rank posteriors (with or without the checks).  score (dict(data, probs)): gpirt_mcmc_score, the
-    same chains scoring the new respondents `data` (with or without the checks and the ranks).  pairs (dict(top)):
-    gpirt_mcmc_pairs, the same chains with the pairwise item checks inside the PPC (with or without everything else).  bins
-    (dict(cuts, top)): gpirt_mcmc_bins, the same chains with the theta-binned item fit inside the PPC (with or without the
-    pairs and everything else).  shape (gpirt_amd.shape.parse's dict): gpirt_mcmc_shape, the same chains with the shape
-    posteriors of the item response curves (with or without everything else).  sumscore (gpirt_amd.sumscore.parse's dict):
-    gpirt_mcmc_sumscore, the same chains with the sum-score posteriors (with or without everything else).  dif
-    (dict(groups, G, cuts, top)): gpirt_mcmc_dif, the same chains with the group-wise item fit inside the PPC (with or without
-    everything else).  equate (gpirt_amd.equate.parse's dict): gpirt_mcmc_equate, the same chains with the two-form score equating
-    (with or without everything else).  loo (gpirt_amd.loo.parse's dict): gpirt_mcmc_loo, the same chains with PSIS-LOO (with or
-    without everything else)."""
-    from . import chains as CH
-    from . import ranks as RK
+def _mcmc_chains(y, nc, S, B, pm, ps, st, theta_init, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device,
+                 progress, summaries, store_draws, align):
+    """gpirtMCMC(chains=C): gpirt_mcmc_chains (include/gpirt_hip.h)."""
+    lib = _lib.load()
+    S, B = int(S), int(B)
+    if nc < 1:
+        raise ValueError("chains must be >= 1")
+    p = _chains_setup(y, nc, S, theta_init, None, False, seed, summaries, store_draws, progress)
+    o = _call_options("item", seed, preset, theta_stabilise, fstar_fused, kstar_rank, device)
+    return _chains_result(lib.gpirt_mcmc_chains(*_chains_args(y, p, nc, S, B, pm, ps, st, o, align)), p)
+
+
+def _mcmc_run(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, preset, theta_stabilise, fstar_fused,
+              kstar_rank, device, progress, summaries, store_draws, align, want):
+    """gpirtMCMC with any of the analyses: gpirt_mcmc_run (include/gpirt_hip.h).  chains=None: one chain, its draws in
+    gpirt_mcmc's layout; else stacked per chain as _mcmc_chains returns them.  `want` holds what gpirtMCMC parsed, None (ppc:
+    False) for what is not asked for: quantiles (the probabilities), ppc (a bool), ranks (a dict), score (dict(data, probs,
+    predict, top)), pairs (dict(top)), bins (dict(cuts, top)), dif (dict(groups, G, cuts, top)) -- those three need ppc --,
+    shape, sumscore, equate and loo (the dicts of their modules' parse).  Every combination runs the same chains."""
+    from . import equate as EQ
+    from . import loo as LO
     from . import ppc as P
     from . import quantiles as Q
+    from . import ranks as RK
+    from . import score as SC
+    from . import shape as SH
+    from . import sumscore as SS
     from .ops import RStream
     lib = _lib.load()
     n, m = y.shape
@@ -448,188 +470,76 @@ def _mcmc_quantiles(y, nc, S, B, pm, ps, st, theta_init, rng, seed, rstream, pre
         if C_ != 1:
             raise ValueError("rng='reference' runs one chain; several chains need the item RNG")
         rs = rstream if rstream is not None else RStream(seed)
-    if theta_init is None:
-        th0 = rs.rnorm(n)[None, :] if rs is not None else CH.default_inits(n, C_, seed)
-    else:
-        t = np.asarray(theta_init, dtype=np.float64)
-        th0 = np.broadcast_to(t, (C_, n)) if t.shape == (n,) else t
-        if th0.shape != (C_, n):
-            raise ValueError("theta_init must be (n,) or (chains, n)")
-    th0 = np.ascontiguousarray(th0)
-    keep = _keep(store_draws)
-    if one:
-        th = np.empty((S + 1, n), order="F") if "theta" in keep else None
-        be = np.empty((2, m, S + 1), order="F") if "beta" in keep else None
-        ff = np.empty((n, m, S + 1), order="F") if "f" in keep else None
-    else:
-        th = np.empty((C_, n, S + 1)) if "theta" in keep else None
-        be = np.empty((C_, S + 1, m, 2)) if "beta" in keep else None
-        ff = np.empty((C_, S + 1, m, n)) if "f" in keep else None
-    irf = np.empty((NGRID, m), order="F")
-    if preset == "fast":
-        o = _lib.fast_options()
-        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        o.device = -1 if device is None else int(device)
-    else:
-        o = _options(rng, seed, theta_stabilise, fstar_fused, device, kstar_rank=kstar_rank)
-    parts = _lib.summary_parts(summaries if summaries is not None else 0) | _lib.SUM_THETA_BETA
-    sm = _lib.Summary()
-    sm.parts = parts
-    arrays = _summary_arrays(parts, n, m)
-    for k, a in arrays.items():
-        setattr(sm, "h_" + k, _ptr(a))
-    d, darr = CH.diag_struct(parts, n, m, C_)
-    q, qarr = Q.quantiles_struct(probs, n, m, C_) if probs is not None else (None, None)
-    if with_ppc:
-        pp, parr = P.struct(n, m)
+    p = _chains_setup(y, C_, S, theta_init, rs, one, seed, summaries, store_draws, progress)
+    o = _call_options(rng, seed, preset, theta_stabilise, fstar_fused, kstar_rank, device)
+    probs, ranks, score, pairs, bins, dif = (want[k] for k in ("quantiles", "ranks", "score", "pairs", "bins", "dif"))
+    shape, sumscore, equate, loo = (want[k] for k in ("shape", "sumscore", "equate", "loo"))
+    order = shape is not None and shape["order"]
+    predict = score is not None and score["predict"]
+    # name -> (the struct, its arrays), for what is wanted; the arrays live until the results are read
+    made = {}
+    if probs is not None:
+        made["quantiles"] = Q.quantiles_struct(probs, n, m, C_)
+    if want["ppc"]:
+        made["ppc"] = P.struct(n, m)
     if ranks is not None:
-        rk, rkarr = RK.struct(n, ranks.get("pivots", "median"), ranks.get("probs", RK.DEFAULT_PROBS),
-                              bool(ranks.get("pairwise", False)))
-
-    def _tick(ctx, it, total):
-        if progress:
-            print("\r%6.3f %% complete" % (100.0 * it / max(total, 1)), end="", flush=True)
-        return 0
-
-    cb = _lib.TICK_FN(_tick)
-    opt = lambda a: _ptr(a) if a is not None else None               # noqa: E731
-    if shape is not None or sumscore is not None or dif is not None or equate is not None or loo is not None:
-        from . import shape as SH
-        from . import score as SC
-        sh = ss = None
-        if shape is not None:
-            sh, sharr = SH.struct(m, shape["k_half"], shape["tols"])
-        if sumscore is not None:
-            from . import sumscore as SS
-            ss, ssarr = SS.struct(m, int(sumscore["mask"].sum()), sumscore["mask"])
-        pq = bq = sc = pr = None
-        if pairs is not None:
-            pq, pqarr = P.pairs_struct(m, pairs["top"])
-        if bins is not None:
-            bq, bqarr = P.bins_struct(m, bins["cuts"], bins["top"])
-        if score is not None:
-            sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
-            if score.get("predict"):
-                pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
-        ref = lambda x: C.byref(x) if x is not None else None            # noqa: E731
-        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                rs.ptr if rs is not None else None, ref(q), C.byref(pp) if with_ppc else None,
-                C.byref(rk) if ranks is not None else None,
-                _ptr(score["data"]) if score is not None else None,
-                score["data"].shape[0] if score is not None else 0, ref(sc), ref(pr), ref(pq), ref(bq))
-        df = None
-        if dif is not None:
-            df, dfarr = P.dif_struct(m, dif["G"], dif["cuts"], dif["top"], groups=dif["groups"])
-        eq = None
-        if equate is not None:
-            from . import equate as EQ
-            eq, eqarr = EQ.struct(m, int(equate["mask_x"].sum()), int(equate["mask_y"].sum()), equate["mask_x"], equate["mask_y"])
-        lo = None
-        if loo is not None:
-            from . import loo as LO
-            lo, loarr = LO.struct(n, m, LO.tail_length(C_ * S, loo["tail"]), loo["top"], loo["tail"])
-        if shape is not None and shape["order"]:
-            od, odarr = SH.order_struct(m, len(shape["tols"]), shape["order_top"])
-            rc = lib.gpirt_mcmc_order(*args, ref(sh), ref(ss), ref(df), ref(eq), ref(lo), C.byref(od))
-        elif loo is not None:
-            rc = lib.gpirt_mcmc_loo(*args, ref(sh), ref(ss), ref(df), ref(eq), C.byref(lo))
-        elif equate is not None:
-            rc = lib.gpirt_mcmc_equate(*args, ref(sh), ref(ss), ref(df), C.byref(eq))
-        elif dif is not None:
-            rc = lib.gpirt_mcmc_dif(*args, ref(sh), ref(ss), C.byref(df))
-        elif ss is not None:
-            rc = lib.gpirt_mcmc_sumscore(*args, ref(sh), C.byref(ss))
-        else:
-            rc = lib.gpirt_mcmc_shape(*args, C.byref(sh))
-    elif pairs is not None or bins is not None:
-        pq = bq = None
-        if pairs is not None:
-            pq, pqarr = P.pairs_struct(m, pairs["top"])
-        if bins is not None:
-            bq, bqarr = P.bins_struct(m, bins["cuts"], bins["top"])
-        sc = pr = None
-        if score is not None:
-            from . import score as SC
-            sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
-            if score.get("predict"):
-                pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
-        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp),
-                C.byref(rk) if ranks is not None else None,
-                _ptr(score["data"]) if score is not None else None,
-                score["data"].shape[0] if score is not None else 0,
-                C.byref(sc) if sc is not None else None, C.byref(pr) if pr is not None else None)
-        if bq is not None:
-            rc = lib.gpirt_mcmc_bins(*args, C.byref(pq) if pq is not None else None, C.byref(bq))
-        else:
-            rc = lib.gpirt_mcmc_pairs(*args, C.byref(pq))
-    elif score is not None:
-        from . import score as SC
-        sc, scarr = SC.struct(score["data"].shape[0], score["probs"])
-        args = (_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
-                C.byref(pp) if with_ppc else None, C.byref(rk) if ranks is not None else None,
-                _ptr(score["data"]), score["data"].shape[0], C.byref(sc))
-        if score.get("predict"):
-            pr, prarr = SC.predict_struct(score["data"].shape[0], m, score["top"])
-            rc = lib.gpirt_mcmc_predict(*args, C.byref(pr))
-        else:
-            rc = lib.gpirt_mcmc_score(*args)
-    elif ranks is not None:
-        rc = lib.gpirt_mcmc_ranks(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                  int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                  rs.ptr if rs is not None else None, C.byref(q) if q is not None else None,
-                                  C.byref(pp) if with_ppc else None, C.byref(rk))
-    elif with_ppc:
-        rc = lib.gpirt_mcmc_ppc(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm), C.byref(d),
-                                rs.ptr if rs is not None else None, C.byref(q) if q is not None else None, C.byref(pp))
-    else:
-        rc = lib.gpirt_mcmc_quantiles(_ptr(y), n, m, _ptr(th0), C_, S, B, _ptr(pm), _ptr(ps), _ptr(st), C.byref(o),
-                                      int(bool(align)), cb, None, opt(th), opt(be), opt(ff), _ptr(irf), C.byref(sm),
-                                      C.byref(d), rs.ptr if rs is not None else None, C.byref(q))
-    if progress:
-        print("\r100.000 % complete")
-    if rc > 0:
-        raise RuntimeError("chol(): decomposition failed")
-    check(rc)
-    summary = dict(arrays)
-    if parts & _lib.SUM_WAIC:
-        summary["totals"] = _totals(sm.totals)
-    if not one:
-        th = th.transpose(0, 2, 1) if th is not None else None
-        be = be.transpose(0, 3, 2, 1) if be is not None else None
-        ff = ff.transpose(0, 3, 2, 1) if ff is not None else None
-    out = dict(theta=th, beta=be, f=ff, IRFs=irf, summary=summary, diagnostics=CH.diag_result(d, darr))
-    if q is not None:
-        out["quantiles"] = Q.quantiles_result(q, qarr)
-    if with_ppc:
-        out["ppc"] = P.result(pp, parr)
-        if pairs is not None:
-            out["ppc"]["pairs"] = P.pairs_result(pq, pqarr)
-        if bins is not None:
-            out["ppc"]["bins"] = P.bins_result(bq, bqarr)
-        if dif is not None:
-            out["ppc"]["dif"] = P.dif_result(df, dfarr)
-    if ranks is not None:
-        out["ranks"] = RK.result(rk, rkarr)
+        made["ranks"] = RK.struct(n, ranks.get("pivots", "median"), ranks.get("probs", RK.DEFAULT_PROBS),
+                                  bool(ranks.get("pairwise", False)))
     if score is not None:
-        out["score"] = SC.result(sc, scarr)
-        if score.get("predict"):
-            out["score"]["predict"] = SC.predict_result(pr, prarr)
+        made["score"] = SC.struct(score["data"].shape[0], score["probs"])
+    if predict:
+        made["predict"] = SC.predict_struct(score["data"].shape[0], m, score["top"])
+    if pairs is not None:
+        made["pairs"] = P.pairs_struct(m, pairs["top"])
+    if bins is not None:
+        made["bins"] = P.bins_struct(m, bins["cuts"], bins["top"])
     if shape is not None:
-        out["shape"] = SH.result(sh, sharr, shape["probs"], shape["top"])
-        if shape["order"]:
-            out["shape"]["order"] = SH.order_result(od, odarr)
+        made["shape"] = SH.struct(m, shape["k_half"], shape["tols"])
     if sumscore is not None:
-        out["sumscore"] = SS.result(ss, ssarr, sumscore["probs"], y)
+        made["sumscore"] = SS.struct(m, int(sumscore["mask"].sum()), sumscore["mask"])
+    if dif is not None:
+        made["dif"] = P.dif_struct(m, dif["G"], dif["cuts"], dif["top"], groups=dif["groups"])
     if equate is not None:
-        out["equate"] = EQ.result(eq, eqarr, equate["probs"], equate["cuts"])
+        made["equate"] = EQ.struct(m, int(equate["mask_x"].sum()), int(equate["mask_y"].sum()), equate["mask_x"],
+                                   equate["mask_y"])
     if loo is not None:
-        out["loo"] = LO.result(lo, loarr)
+        made["loo"] = LO.struct(n, m, LO.tail_length(C_ * S, loo["tail"]), loo["top"], loo["tail"])
+    if order:
+        made["order"] = SH.order_struct(m, len(shape["tols"]), shape["order_top"])
+    run = _lib.Run()
+    run.rs = rs.ptr if rs is not None else None
+    for name, (struct, _) in made.items():
+        setattr(run, name, C.pointer(struct))
+    if score is not None:
+        run.h_y_new, run.n_new = _ptr(score["data"]), score["data"].shape[0]
+    rc = lib.gpirt_mcmc_run(*_chains_args(y, p, C_, S, B, pm, ps, st, o, align), C.byref(run))
+    out = _chains_result(rc, p)
+    if probs is not None:
+        out["quantiles"] = Q.quantiles_result(*made["quantiles"])
+    if want["ppc"]:
+        out["ppc"] = P.result(*made["ppc"])
+        if pairs is not None:
+            out["ppc"]["pairs"] = P.pairs_result(*made["pairs"])
+        if bins is not None:
+            out["ppc"]["bins"] = P.bins_result(*made["bins"])
+        if dif is not None:
+            out["ppc"]["dif"] = P.dif_result(*made["dif"])
+    if ranks is not None:
+        out["ranks"] = RK.result(*made["ranks"])
+    if score is not None:
+        out["score"] = SC.result(*made["score"])
+        if predict:
+            out["score"]["predict"] = SC.predict_result(*made["predict"])
+    if shape is not None:
+        out["shape"] = SH.result(*made["shape"], shape["probs"], shape["top"])
+        if order:
+            out["shape"]["order"] = SH.order_result(*made["order"])
+    if sumscore is not None:
+        out["sumscore"] = SS.result(*made["sumscore"], sumscore["probs"], y)
+    if equate is not None:
+        out["equate"] = EQ.result(*made["equate"], equate["probs"], equate["cuts"])
+    if loo is not None:
+        out["loo"] = LO.result(*made["loo"])
     return out
 
 

@@ -1,5 +1,5 @@
 """Scoring respondents who were not in the fit: the posterior of their theta and the predictive density of their answers
-(include/gpirt_hip.h, "scoring new respondents": gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score;
+(include/gpirt_hip.h, "scoring new respondents": gpirt_sampler_score_*, gpirt_score_combine, gpirt_run.score;
 csrc/score.hip).
 
 For every counted draw of f* (1001 x m, it carries mu*) and every new respondent r the device forms

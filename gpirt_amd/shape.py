@@ -1,5 +1,5 @@
 """Shape posteriors of the item response curves without stored draws: monotonicity, peaks, crossings, slopes, information
-(include/gpirt_hip.h, "IRF shape posteriors": gpirt_sampler_shape_*, gpirt_shape_combine, gpirt_mcmc_shape; csrc/shape.hip),
+(include/gpirt_hip.h, "IRF shape posteriors": gpirt_sampler_shape_*, gpirt_shape_combine, gpirt_run.shape; csrc/shape.hip),
 and on top of them the item-pair order posteriors (gpirt_sampler_shape_order_*, csrc/order.hip; the order_* functions below).
 
 The curve of a draw is g = k*^T S^-1 f + mu*, the conditional mean draw_fstar forms (the sampler array "gbar"); the stored f* is
@@ -115,7 +115,7 @@ def grid_weights():
 # ------------------------------------------------------------------------------------------------------ the device ---
 def struct(m: int, k_half=None, tols=None):
     """A gpirt_shape asking for every raw array, and the host arrays behind it (kept alive by the caller).  k_half and tols
-    are read by gpirt_mcmc_shape; gpirt_shape_combine ignores them."""
+    are read by gpirt_mcmc_run; gpirt_shape_combine ignores them."""
     r = _lib.Shape()
     arrays = {}
     for k, (name, dt) in enumerate(SHAPE_RAW):

@@ -1,6 +1,6 @@
 """Posteriors of the sum score S = number of yes answers on a form of items, without stored draws: the score distribution, the
 score-to-theta conversion table, the test characteristic curve (TCC), the conditional standard error and the reliability of the
-score (include/gpirt_hip.h, "Sum-score posteriors": gpirt_sampler_sumscore_*, gpirt_sumscore_combine, gpirt_mcmc_sumscore;
+score (include/gpirt_hip.h, "Sum-score posteriors": gpirt_sampler_sumscore_*, gpirt_sumscore_combine, gpirt_run.sumscore;
 csrc/sumscore.hip).
 
 Per draw the device runs the Lord-Wingersky recursion over the form's items at every grid point, from the draw's f*:
@@ -96,7 +96,7 @@ def _raw_shape(name, m, M):
 # ------------------------------------------------------------------------------------------------------ the device ---
 def struct(m: int, M: int, mask=None):
     """A gpirt_sumscore asking for every raw array, and the host arrays behind it (kept alive by the caller).  mask (m bytes)
-    is read by gpirt_mcmc_sumscore; gpirt_sumscore_combine ignores it."""
+    is read by gpirt_mcmc_run; gpirt_sumscore_combine ignores it."""
     r = _lib.Sumscore()
     arrays = {}
     for k, (name, dt) in enumerate(SUMSCORE_RAW):

@@ -61,7 +61,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine, gpirt_mcmc_predict); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine, gpirt_mcmc_score); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine, gpirt_mcmc_ranks); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine, gpirt_mcmc_ppc); 106: quantiles (gpirt_summary_quantiles, gpirt_mcmc_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -461,7 +461,7 @@ int gpirt_irf_band_edges(double* out);
 #define GPIRT_QNT_IRF_COUNT_MIN  6   /* the least and the most draws a pooled f* cell holds (bins + NaN): T both when */
 #define GPIRT_QNT_IRF_COUNT_MAX  7   /* no draw was lost or counted twice */
 #define GPIRT_QNT_NSCALARS       8
-/* What gpirt_summary_quantiles / gpirt_mcmc_quantiles return: a HOST pointer per output (NULL: not wanted; an output
+/* What gpirt_summary_quantiles / gpirt_mcmc_run return: a HOST pointer per output (NULL: not wanted; an output
  * whose part the states lack is refused).  T = C S pooled draws, a reflected chain entering with its grid index
  * reversed (k -> 1000 - k, for theta and for f*'s grid axis).
  * theta_q (nprobs x n): the ceil(q T)-th smallest pooled draw (1-based; q = 0: the smallest; q T, here and below, is
@@ -499,16 +499,6 @@ typedef struct gpirt_quantiles {
  * align.  C S must be < 2^32.  No atomics: bit-identical from run to run. */
 int gpirt_summary_quantiles(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, int align,
                             gpirt_quantiles* q);
-/* gpirt_mcmc_chains with the quantiles (library version 106): every chain also keeps GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND (and
- * GPIRT_SUM_DIAG with S planned); draws, IRFs, pooled and diag are bit-identical to gpirt_mcmc_chains's.  rs != NULL
- * (GPIRT_RNG_RSTREAM, chains = 1): the chain is gpirt_mcmc_summary's -- draws, IRFs and R's stream position bit-identical
- * -- with the quantiles of its one state.  q is required; pooled->parts as gpirt_mcmc_chains's. */
-int gpirt_mcmc_quantiles(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                         int sample_iterations, int burn_iterations, const double* h_prior_means,
-                         const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                         gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                         double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                         gpirt_rstream_t rs, gpirt_quantiles* q);
 
 /* ------------------------------------------------------ posterior predictive checks: items, respondents, the whole matrix --- */
 /* Does the model fit these items and these respondents?  For sampling draw s, the state after that iteration's step gives
@@ -581,16 +571,6 @@ int gpirt_sampler_ppc_get(gpirt_sampler_t s, const char* name, double* h_out, in
 int gpirt_sampler_ppc_totals(gpirt_sampler_t s, double* h_totals);
 int gpirt_sampler_ppc_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc* out);
-/* gpirt_mcmc_quantiles with the checks (library version 107): the same chains -- draws, IRFs, pooled, diag, the
- * quantiles and R's stream position bit-identical --, each accumulating the PPC after every sampling iteration's
- * summaries, pooled into ppc (required).  q may be NULL: the chains are then gpirt_mcmc_chains's (no histograms, no bands),
- * and rs != NULL with chains = 1 runs gpirt_mcmc_summary's chain. */
-int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                   int sample_iterations, int burn_iterations, const double* h_prior_means,
-                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc);
 
 /* ------------------------------------------------------ rank posteriors: rank intervals, pivots, pairwise order --------- */
 /* Who is where in the order?  Joint functionals of one theta draw, accumulated without storing it (library version 108).
@@ -626,9 +606,9 @@ int gpirt_mcmc_ppc(const double* h_y, int64_t n, int64_t m, const double* h_thet
 typedef struct gpirt_ranks {
     const double* probs;          /* in: nprobs probabilities in [0, 1] for rank_q */
     int       nprobs;
-    int       n_pivots;           /* in (gpirt_mcmc_ranks): the positions given in pivots[], 0 = the median; out: P */
+    int       n_pivots;           /* in (gpirt_mcmc_run): the positions given in pivots[], 0 = the median; out: P */
     int64_t   pivots[GPIRT_RANK_MAX_PIVOTS_CLOSED];     /* in: the first n_pivots; out: the closed set, sorted */
-    int       pairwise;           /* in (gpirt_mcmc_ranks): keep lt */
+    int       pairwise;           /* in (gpirt_mcmc_run): keep lt */
     int       reserved0;          /* must be 0 */
     double*   rank_mean;          /* n */
     double*   rank_var;           /* n */
@@ -661,16 +641,6 @@ int gpirt_sampler_rank_accumulate(gpirt_sampler_t s);
 int gpirt_sampler_rank_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_rank_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_rank_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ranks* out);
-/* gpirt_mcmc_ppc with the rank posteriors: the same chains -- draws, IRFs, pooled, diag, the quantiles, the PPC and R's
- * stream position bit-identical --, each accumulating its theta after every sampling iteration's summaries (under the item
- * RNG from the verified checkpoint, so a hang-guard rollback counts no draw twice), pooled into ranks (required) with the
- * signs gpirt_chains_combine decided (align = 0 or one chain: none).  q and ppc may be NULL. */
-int gpirt_mcmc_ranks(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                     int sample_iterations, int burn_iterations, const double* h_prior_means,
-                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks);
 
 /* ------------------------------------------------------ scoring new respondents: theta posterior and predictive density -- */
 /* What does the fitted model say about a respondent who was NOT in the fit (library version 109)?  y_new is n_new x m,
@@ -740,18 +710,6 @@ int gpirt_sampler_score_accumulate(gpirt_sampler_t s);
 int gpirt_sampler_score_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_score_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out);
-/* gpirt_mcmc_ranks with scoring: the same chains -- draws, IRFs, pooled, diag, the quantiles, the PPC, the ranks and R's
- * stream position bit-identical --, each accumulating its f* after every sampling iteration's summaries (under the item RNG
- * from the verified checkpoint, so a hang-guard rollback counts no draw twice; under R's stream from the live state), pooled
- * into score (required) with the signs gpirt_chains_combine decided (align = 0 or one chain: none).  q, ppc and ranks may
- * be NULL. */
-int gpirt_mcmc_score(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                     int sample_iterations, int burn_iterations, const double* h_prior_means,
-                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                     const double* h_y_new, int64_t n_new, gpirt_score* score);
 
 /* ---------------------------------------------- predicting new respondents' unseen answers and ranking the next item to ask -- */
 /* How would a respondent who was NOT in the fit answer item j, and which unanswered item is expected to say most about their
@@ -817,16 +775,6 @@ int gpirt_sampler_score_predict_enable(gpirt_sampler_t s, int on);
 int gpirt_sampler_score_predict_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_score_predict_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_score_predict_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_score_predict* out);
-/* gpirt_mcmc_score with prediction (predict is required): the same chains and the same score, every chain also accumulating
- * the prediction inside its score_accumulate -- under the item RNG from the verified checkpoint, so a hang-guard rollback
- * counts no draw twice --, pooled into predict. */
-int gpirt_mcmc_predict(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                       int sample_iterations, int burn_iterations, const double* h_prior_means,
-                       const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                       gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                       double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                       gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                       const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict);
 
 /* ------------------------------------------------------------- pairwise item checks: joint counts and odds ratios of item pairs -- */
 /* Does the model's one latent dimension hold (library version 111)?  Given theta, answers to different items are independent;
@@ -926,18 +874,6 @@ int gpirt_sampler_ppc_pairs_enable(gpirt_sampler_t s, int on);
 int gpirt_sampler_ppc_pairs_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_ppc_pairs_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_pairs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_pairs* out);
-/* gpirt_mcmc_predict with the pairwise checks (ppc and pairs are required; score and predict may be NULL, with y_new NULL and
- * n_new 0; predict needs score): the same chains and the same PPC, every chain also accumulating the pairs inside its
- * ppc_accumulate -- under the item RNG from the verified checkpoint, so a hang-guard rollback counts no draw twice --, pooled
- * into pairs. */
-int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                     int sample_iterations, int burn_iterations, const double* h_prior_means,
-                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                     gpirt_ppc_pairs* pairs);
 
 /* ------------------------------------------------------------- theta-binned item fit: empirical IRFs and chi-square per item -- */
 /* Does an item's response function have the right SHAPE along theta (library version 112)?  An item's yes count is reproduced by
@@ -1010,8 +946,8 @@ int gpirt_mcmc_pairs(const double* h_y, int64_t n, int64_t m, const double* h_th
 /* HOST pointers (NULL: not wanted). */
 typedef struct gpirt_ppc_bins {
     int        top;                            /* in: 1..GPIRT_BINS_MAX_TOP */
-    int        h;                              /* in (gpirt_mcmc_bins): the number of cuts; out: the states' */
-    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_bins) / out: d_1 .. d_h, the rest 0 */
+    int        h;                              /* in (gpirt_mcmc_run): the number of cuts; out: the states' */
+    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_run) / out: d_1 .. d_h, the rest 0 */
     double*    cell[GPIRT_BINS_CELL_NFIELDS];  /* B x m each */
     double*    item[GPIRT_BINS_ITEM_NFIELDS];  /* m each */
     double*    bin[GPIRT_BINS_BIN_NFIELDS];    /* B each */
@@ -1047,17 +983,6 @@ int gpirt_sampler_ppc_bins_enable(gpirt_sampler_t s, int h, const int* cuts, int
 int gpirt_sampler_ppc_bins_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_ppc_bins_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_bins_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_bins* out);
-/* gpirt_mcmc_pairs with the theta-binned item fit (ppc and bins are required, bins->h and bins->cuts given; pairs may be NULL):
- * every chain also accumulates the bins inside its ppc_accumulate -- under the item RNG from the verified checkpoint, as the
- * pairs do --, pooled into bins with the reflection signs that the chains' alignment decides. */
-int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                    int sample_iterations, int burn_iterations, const double* h_prior_means,
-                    const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                    gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                    double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                    gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                    const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                    gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins);
 
 /* ------------------------------------------------------ IRF shape posteriors: monotonicity, peaks, information --------- */
 /* The posterior mean curve and its pointwise bands do not say what SHAPE an item's response curve has: whether it is monotone,
@@ -1126,9 +1051,9 @@ int gpirt_mcmc_bins(const double* h_y, int64_t n, int64_t m, const double* h_the
 #define GPIRT_SHAPE_NARRAYS           13
 /* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
 typedef struct gpirt_shape {
-    int        k_half;                         /* in (gpirt_mcmc_shape): 1..500; out: the states' */
-    int        n_tols;                         /* in (gpirt_mcmc_shape): 1..GPIRT_SHAPE_MAX_TOLS; out: the states' */
-    double     tols[GPIRT_SHAPE_MAX_TOLS];     /* in (gpirt_mcmc_shape) / out: the first n_tols, each >= 0 and finite */
+    int        k_half;                         /* in (gpirt_mcmc_run): 1..500; out: the states' */
+    int        n_tols;                         /* in (gpirt_mcmc_run): 1..GPIRT_SHAPE_MAX_TOLS; out: the states' */
+    double     tols[GPIRT_SHAPE_MAX_TOLS];     /* in (gpirt_mcmc_run) / out: the first n_tols, each >= 0 and finite */
     void*      raw[GPIRT_SHAPE_NARRAYS];
     int64_t    n, m;                           /* out */
     int64_t    info_draws, info_skipped;       /* out */
@@ -1152,18 +1077,6 @@ int gpirt_sampler_shape_get(gpirt_sampler_t s, const char* name, void* h_out, in
 int gpirt_sampler_shape_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_shape_state_bytes(int64_t m, int64_t* bytes);
 int gpirt_shape_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_shape* out);
-/* gpirt_mcmc_bins with the shape posteriors (shape is required, k_half, n_tols and tols given; everything from q on may be
- * NULL, pairs and bins need ppc as before): every chain also accumulates its curves after each sampling iteration -- under the
- * item RNG from the verified checkpoint, which then carries gbar --, pooled into shape with the reflection signs that the
- * chains' alignment decides. */
-int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                     int sample_iterations, int burn_iterations, const double* h_prior_means,
-                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                     gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape);
 
 /* ------------------------------------------------------ Sum-score posteriors: score table, TCC, reliability ------------ */
 /* Everything above looks at one item, a pair of items or one respondent with a known answer pattern.  The statistic an IRT user
@@ -1226,7 +1139,7 @@ int gpirt_mcmc_shape(const double* h_y, int64_t n, int64_t m, const double* h_th
 #define GPIRT_SUMSCORE_NARRAYS        11
 /* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
 typedef struct gpirt_sumscore {
-    const unsigned char* items;                /* in (gpirt_mcmc_sumscore): m bytes, non-zero = in the form; NULL: all m items */
+    const unsigned char* items;                /* in (gpirt_mcmc_run): m bytes, non-zero = in the form; NULL: all m items */
     void*      raw[GPIRT_SUMSCORE_NARRAYS];
     int64_t    m, M;                           /* out */
     int64_t    draws, skipped, rel_draws, rel_skipped;   /* out */
@@ -1249,18 +1162,6 @@ int gpirt_sampler_sumscore_state(gpirt_sampler_t s, void** d_state, int64_t* byt
 int gpirt_sumscore_state_bytes(int64_t m, int64_t M, int64_t* bytes);
 int gpirt_sumscore_grid_weights(double* h_w);
 int gpirt_sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_sumscore* out);
-/* gpirt_mcmc_shape with the sum-score posteriors (sumscore is required, items given or NULL; everything from q on, shape
- * included, may be NULL; pairs and bins need ppc as before): every chain also accumulates its f* after each sampling iteration
- * -- under the item RNG from the verified checkpoint's f*, under R's stream right after the step --, pooled into sumscore with
- * the reflection signs that the chains' alignment decides. */
-int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                        int sample_iterations, int burn_iterations, const double* h_prior_means,
-                        const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                        gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                        double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                        gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                        const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                        gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore);
 
 /* ------------------------------------------------------------- group-wise item fit (DIF): Mantel-Haenszel per item ------------ */
 /* Given theta, does an answer still depend on WHO the respondent is (library version 115)?  Differential item functioning: the
@@ -1322,11 +1223,11 @@ int gpirt_mcmc_sumscore(const double* h_y, int64_t n, int64_t m, const double* h
 /* HOST pointers (NULL: not wanted). */
 typedef struct gpirt_ppc_dif {
     int        top;                            /* in: 1..GPIRT_DIF_MAX_TOP */
-    int        G;                              /* in (gpirt_mcmc_dif): the number of groups; out: the states' */
-    int        h;                              /* in (gpirt_mcmc_dif): the number of cuts; out: the states' */
-    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_dif) / out: d_1 .. d_h, the rest 0 */
+    int        G;                              /* in (gpirt_mcmc_run): the number of groups; out: the states' */
+    int        h;                              /* in (gpirt_mcmc_run): the number of cuts; out: the states' */
+    int        cuts[GPIRT_BINS_MAX_H + 1];     /* in (gpirt_mcmc_run) / out: d_1 .. d_h, the rest 0 */
     int        reserved0;                      /* must be 0 */
-    const int32_t* groups;                     /* in (gpirt_mcmc_dif): n codes in -1 .. G - 1 */
+    const int32_t* groups;                     /* in (gpirt_mcmc_run): n codes in -1 .. G - 1 */
     double*    cell[GPIRT_DIF_CELL_NFIELDS];   /* G x B x m each */
     double*    occupancy;                      /* G x B */
     double*    group[GPIRT_DIF_GROUP_NFIELDS]; /* G x m each */
@@ -1355,18 +1256,6 @@ int gpirt_sampler_ppc_dif_enable(gpirt_sampler_t s, int G, const int32_t* groups
 int gpirt_sampler_ppc_dif_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_ppc_dif_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out);
-/* gpirt_mcmc_sumscore with the group-wise item fit (ppc and dif are required, dif->G, groups, h and cuts given; everything else from
- * q on may be NULL): every chain also accumulates the block inside its ppc_accumulate -- under the item RNG from the verified
- * checkpoint, as the pairs and the bins do --, pooled into dif with the reflection signs that the chains' alignment decides. */
-int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                   int sample_iterations, int burn_iterations, const double* h_prior_means,
-                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                   const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                   gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
-                   gpirt_ppc_dif* dif);
 
 /* ------------------------------------------------------ Two-form score equating: joint table, concordance ------------- */
 /* The sum-score section answers every question about ONE form's score.  This one is about TWO forms at once: how scores on
@@ -1440,8 +1329,8 @@ int gpirt_mcmc_dif(const double* h_y, int64_t n, int64_t m, const double* h_thet
 #define GPIRT_EQUATE_NARRAYS          19
 /* HOST pointers (NULL: not wanted): the pooled raw arrays, each of the size and type named above. */
 typedef struct gpirt_equate {
-    const unsigned char* x;                    /* in (gpirt_mcmc_equate): m bytes, non-zero = in form X */
-    const unsigned char* y;                    /* in (gpirt_mcmc_equate): m bytes, non-zero = in form Y */
+    const unsigned char* x;                    /* in (gpirt_mcmc_run): m bytes, non-zero = in form X */
+    const unsigned char* y;                    /* in (gpirt_mcmc_run): m bytes, non-zero = in form Y */
     void*      raw[GPIRT_EQUATE_NARRAYS];
     int64_t    m, Mx, My;                      /* out */
     int64_t    draws, skipped, corr_draws, corr_skipped, eq_clamped;   /* out */
@@ -1462,19 +1351,6 @@ int gpirt_sampler_equate_get(gpirt_sampler_t s, const char* name, void* h_out, i
 int gpirt_sampler_equate_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_equate_state_bytes(int64_t m, int64_t Mx, int64_t My, int64_t* bytes);
 int gpirt_equate_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_equate* out);
-/* gpirt_mcmc_dif with the score equating (equate is required, both masks given; everything from q on, dif included, may be NULL;
- * pairs, bins and dif need ppc as before): every chain also accumulates its f* after each sampling iteration -- under the item
- * RNG from the verified checkpoint's f*, under R's stream right after the step --, pooled into equate in chain order (no signs:
- * see REFLECTION above). */
-int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                      int sample_iterations, int burn_iterations, const double* h_prior_means,
-                      const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                      gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                      double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                      gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                      const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                      gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
-                      gpirt_ppc_dif* dif, gpirt_equate* equate);
 
 /* ------------------------------------------------------ PSIS-LOO: pointwise elpd, Pareto k, model comparison ----------- */
 /* Leave-one-out cross-validation by Pareto-smoothed importance sampling (Vehtari, Gelman and Gabry 2017; Vehtari, Simpson,
@@ -1564,7 +1440,7 @@ int gpirt_mcmc_equate(const double* h_y, int64_t n, int64_t m, const double* h_t
 #define GPIRT_LOO_NTOTALS             14
 /* HOST pointers (NULL: not wanted). */
 typedef struct gpirt_loo {
-    int64_t    tail;                           /* in (gpirt_mcmc_loo): 0 = the rule, else 5 .. GPIRT_LOO_MAX_TAIL */
+    int64_t    tail;                           /* in (gpirt_mcmc_run): 0 = the rule, else 5 .. GPIRT_LOO_MAX_TAIL */
     int64_t    top;                            /* in: 1 .. GPIRT_LOO_MAX_TOP, the length of worst_index / worst_k */
     void*      raw[GPIRT_LOO_NARRAYS];         /* the pooled raw arrays, each of the size and type named above */
     double*    pointwise[GPIRT_LOO_NPOINTWISE];
@@ -1591,19 +1467,6 @@ int gpirt_sampler_loo_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_loo_tail_length(int64_t T, int tail, int64_t* M);
 int gpirt_loo_state_bytes(int64_t n, int64_t m, int64_t M, int64_t* bytes);
 int gpirt_loo_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_loo* out);
-/* gpirt_mcmc_equate with PSIS-LOO (loo is required; everything from q on, equate included, may be NULL; pairs, bins and dif need
- * ppc as before): T = chains x sample_iterations; every chain also enters its f + mu after each sampling iteration -- under the
- * item RNG from the verified checkpoint's f and mu, under R's stream right after the step --; each finished chain is merged into
- * the pooled state and freed (at most two states are alive), then the pooled state is finished into loo. */
-int gpirt_mcmc_loo(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                   int sample_iterations, int burn_iterations, const double* h_prior_means,
-                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                   double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                   gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                   const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                   gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
-                   gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo);
 
 /* ------------------------------------------------------ Item-pair IRF order posteriors: dominance and crossings -------- */
 /* The shape posteriors say, item by item, whether a curve is monotone.  Whether the curves of two items INTERSECT -- whether the
@@ -1664,19 +1527,55 @@ int gpirt_sampler_shape_order_get(gpirt_sampler_t s, const char* name, void* h_o
 int gpirt_sampler_shape_order_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_shape_order_state_bytes(int64_t m, int n_tols, int64_t* bytes);
 int gpirt_shape_order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out);
-/* gpirt_mcmc_loo with the order posteriors (order and shape are required; everything else from q on may be NULL as before):
- * every chain's shape accumulation also runs the order kernels -- under the item RNG from the verified checkpoint's gbar --,
- * pooled into order without signs.  The chain, the IRFs, R's stream position and every other block's state, the shape block
- * included, are bit for bit what they are without. */
-int gpirt_mcmc_order(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
-                     int sample_iterations, int burn_iterations, const double* h_prior_means,
-                     const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
-                     gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws,
-                     double* h_f_draws, double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag,
-                     gpirt_rstream_t rs, gpirt_quantiles* q, gpirt_ppc* ppc, gpirt_ranks* ranks,
-                     const double* h_y_new, int64_t n_new, gpirt_score* score, gpirt_score_predict* predict,
-                     gpirt_ppc_pairs* pairs, gpirt_ppc_bins* bins, gpirt_shape* shape, gpirt_sumscore* sumscore,
-                     gpirt_ppc_dif* dif, gpirt_equate* equate, gpirt_loo* loo, gpirt_shape_order* order);
+
+/* ------------------------------------------------------ the chains with any of the analyses above, in one call -------- */
+/* What gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs: one struct per analysis, each NULL when not wanted, each
+ * filled as its section above describes.  The chains are gpirt_mcmc_chains's whatever is asked for -- draws, IRFs, pooled, diag
+ * and R's stream position bit-identical; no analysis consumes anything of the chain's random numbers, and each leaves every
+ * other one's results bit for bit what they are without it.  Every chain accumulates after each sampling iteration's
+ * summaries: under the item RNG from the verified checkpoint (so a hang-guard rollback counts no draw twice), under R's
+ * stream from the live state right after the step.  The states are pooled with the reflection signs that
+ * gpirt_chains_combine decided for the same chains (align = 0 or one chain: none) where the analysis's combine takes signs. */
+typedef struct gpirt_run {
+    gpirt_rstream_t rs;            /* NULL: item RNG (GPIRT_RNG_ITEM); else R's stream (GPIRT_RNG_RSTREAM, chains = 1): the
+                                    * chain is gpirt_mcmc_summary's -- draws, IRFs and R's stream position bit-identical */
+    gpirt_quantiles* quantiles;    /* every chain also keeps GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND; gpirt_summary_quantiles
+                                    * of the chains' states.  NULL: no histograms, no bands.  chains x S < 2^32 */
+    gpirt_ppc* ppc;                /* the posterior predictive checks, pooled by gpirt_ppc_combine */
+    gpirt_ranks* ranks;            /* the rank posteriors of every chain's theta: pivots, n_pivots and pairwise given; n <=
+                                    * GPIRT_RANK_MAX_N, chains x S < 2^32 */
+    const double* h_y_new;         /* scoring: n_new x m on the host, +1 / -1 / NaN; NULL and 0 without score */
+    int64_t n_new;                 /* 1..GPIRT_SCORE_MAX_N */
+    gpirt_score* score;            /* scoring y_new against every chain's f* */
+    gpirt_score_predict* predict;  /* needs score: the prediction of y_new's unseen answers, accumulated inside the score's
+                                    * accumulate; top in 1..GPIRT_PREDICT_MAX_TOP */
+    gpirt_ppc_pairs* pairs;        /* needs ppc: the pairwise item checks, accumulated inside the PPC's accumulate; top in
+                                    * 1..GPIRT_PAIRS_MAX_TOP, n <= GPIRT_PAIRS_MAX_N */
+    gpirt_ppc_bins* bins;          /* needs ppc: the theta-binned item fit, h and cuts given; inside the PPC's accumulate as the
+                                    * pairs; top in 1..GPIRT_BINS_MAX_TOP */
+    gpirt_shape* shape;            /* the IRF shape posteriors, k_half, n_tols and tols given: every chain's curves gbar (which
+                                    * the checkpoint then carries); chains x S < 2^32 */
+    gpirt_sumscore* sumscore;      /* the sum-score posteriors of every chain's f*; items given or NULL (all m) */
+    gpirt_ppc_dif* dif;            /* needs ppc: the group-wise item fit, G, groups, h and cuts given; inside the PPC's
+                                    * accumulate as the pairs and the bins; top in 1..GPIRT_DIF_MAX_TOP */
+    gpirt_equate* equate;          /* the two-form score equating of every chain's f*, both masks given; pooled in chain
+                                    * order (no signs: see REFLECTION above) */
+    gpirt_loo* loo;                /* PSIS-LOO of every chain's f + mu with T = chains x sample_iterations; each finished chain
+                                    * is merged into the pooled state and freed (at most two states are alive), then the pooled
+                                    * state is finished into loo */
+    gpirt_shape_order* order;      /* needs shape: the item-pair order posteriors; every chain's shape accumulation also runs
+                                    * the order kernels, pooled without signs; the shape block is bit for bit what it is
+                                    * without; m in 2..GPIRT_ORDER_MAX_M, top in 1..GPIRT_ORDER_MAX_TOP */
+    void* reserved[8];             /* must be NULL: the next analyses go here */
+} gpirt_run;
+/* gpirt_mcmc_chains with the analyses that run names (library version 119; run == NULL, a non-NULL reserved slot and a
+ * dependant without its base are GPIRT_E_ARG).  With run->rs it needs GPIRT_RNG_RSTREAM and chains = 1, without it
+ * GPIRT_RNG_ITEM.  A run with every analysis NULL and no rs is gpirt_mcmc_chains. */
+int gpirt_mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_theta0, int chains,
+                   int sample_iterations, int burn_iterations, const double* h_prior_means,
+                   const double* h_prior_sds, const double* h_step_sizes, const gpirt_options* opts, int align,
+                   gpirt_tick_fn tick, void* tick_ctx, double* h_theta_draws, double* h_beta_draws, double* h_f_draws,
+                   double* h_irfs, gpirt_summary* pooled, gpirt_diag* diag, gpirt_run* run);
 
 /* Stage-level sampler for hosts that drive the loop themselves (bench.py, multi-GPU hosts that
  * put a collective between stages).  State lives on the device.  h_y holds +1, -1 or NaN (a missing response); any

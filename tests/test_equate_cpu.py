@@ -175,9 +175,9 @@ def test_c_abi_of_version_116():
     p = _lib.Equate()
     assert C.sizeof(p) == 8 * 2 + 8 * 19 + 8 * 3 + 8 * 5 + 8 * 4 and len(_lib.EQUATE_RAW) == 19
     for name in ("gpirt_sampler_equate_enable", "gpirt_sampler_equate_accumulate", "gpirt_sampler_equate_get",
-                 "gpirt_sampler_equate_state", "gpirt_equate_state_bytes", "gpirt_equate_combine", "gpirt_mcmc_equate"):
+                 "gpirt_sampler_equate_state", "gpirt_equate_state_bytes", "gpirt_equate_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert len(_lib.SIGNATURES["gpirt_mcmc_equate"][1]) == len(_lib.SIGNATURES["gpirt_mcmc_dif"][1]) + 1
+    assert _lib.Run.equate.offset == _lib.Run.dif.offset + 8              # gpirt_run: equate follows dif
     # argument errors come back before any device is touched
     assert lib.gpirt_equate_combine(None, 1, None, C.byref(p)) == _lib.E_ARG
     assert lib.gpirt_sampler_equate_enable(None, None, None, 1) == _lib.E_ARG

@@ -360,3 +360,82 @@ def test_multi_block_size_with_f():
     check_pooled(res["summary"], y, th, be, ff, signs)
     check_diag(res["diagnostics"], th, be, ff, signs, True)
     check_irfs(res["IRFs"], irfs, signs)
+
+
+def _same(a, b, what):
+    """Two results of the same chains: every array bit for bit (NaN where the other has NaN), every scalar equal."""
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            _same(a[k], b[k], f"{what}.{k}")
+    elif a is None:
+        assert b is None, what
+    else:
+        assert np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True), what
+
+
+def _mcmc_run_empty(y, inits, S, B, seed, priors, chains):
+    """gpirt_mcmc_run through ctypes with an empty gpirt_run, the fast preset and every pooled part: the stored draws chain-major
+    in gpirt_mcmc's layout, the IRFs, the pooled arrays by name, the totals and the diagnostics."""
+    import ctypes as C
+    from gpirt_amd import _lib
+    from gpirt_amd import chains as CH
+    lib = _lib.load()
+    dp = C.POINTER(C.c_double)
+    a = lambda x: x.ctypes.data_as(dp)                                           # noqa: E731
+    n, m = y.shape
+    yf, th0 = np.asfortranarray(y), np.ascontiguousarray(inits)
+    pm, ps, st = (np.asfortranarray(p, dtype=np.float64) for p in priors)
+    th, be, ff = np.empty((chains, n, S + 1)), np.empty((chains, S + 1, m, 2)), np.empty((chains, S + 1, m, n))
+    irf = np.empty((_lib.NGRID, m), order="F")
+    o = _lib.fast_options()
+    o.seed = seed
+    sm = _lib.Summary()
+    sm.parts = _lib.summary_parts(ALL) | _lib.SUM_THETA_BETA
+    shapes = dict(theta_mean=(n,), theta_var=(n,), beta_mean=(2, m), beta_var=(2, m))
+    pooled = {k: np.empty(shapes.get(k, (n, m)), order="F") for k in ("theta_mean", "theta_var", "beta_mean", "beta_var", "p_yes",
+                                                                      "lppd", "p_waic", "f_mean", "f_var")}
+    for k, v in pooled.items():
+        setattr(sm, "h_" + k, a(v))
+    d, darr = CH.diag_struct(sm.parts, n, m, chains)
+    run = _lib.Run()
+    _lib.check(lib.gpirt_mcmc_run(a(yf), n, m, a(th0), chains, S, B, a(pm), a(ps), a(st), C.byref(o), 1, _lib.TICK_FN(0), None,
+                                  a(th), a(be), a(ff), a(irf), C.byref(sm), C.byref(d), C.byref(run)))
+    return dict(theta=th.transpose(0, 2, 1), beta=be.transpose(0, 3, 2, 1), f=ff.transpose(0, 3, 2, 1), IRFs=irf, pooled=pooled,
+                totals=list(sm.totals), diagnostics=CH.diag_result(d, darr))
+
+
+def test_mcmc_run_is_mcmc_chains_and_the_analyses_leave_the_chains_alone():
+    """gpirt_mcmc_run with an empty gpirt_run against gpirt_mcmc_chains -- draws, IRFs, pooled summary and diagnostics bit for
+    bit, as two calls with one seed are everywhere in this file --; then with ppc, ranks, shape and loo all set: the same
+    draws, IRFs and pooled summary, ranks over chains x S draws, and PSIS-LOO over one chain (chain 0's state alone, no
+    merge) and over two (chain 1 merged into it)."""
+    from gpirt_amd import _lib, gpirtMCMC
+    n, m, C_, S, B = 8, 3, 2, 4, 1
+    y = np.array([[1, -1, 1], [-1, 1, 1], [1, 1, -1], [-1, -1, 1], [1, np.nan, -1], [1, 1, 1], [-1, 1, -1], [1, -1, -1]],
+                 dtype=np.float64)
+    inits = np.round(np.random.default_rng(3).normal(size=(C_, n)), 2)
+    priors = (np.zeros((2, m)), np.full((2, m), 3.0), np.full((2, m), 0.1))
+    kw = dict(vote_codes=CODES, beta_prior_means=priors[0], beta_prior_sds=priors[1], beta_proposal_sds=priors[2], preset="fast",
+              seed=17, summaries=ALL)
+    ref = gpirtMCMC(y, S, B, theta_init=inits, chains=C_, **kw)
+    empty = _mcmc_run_empty(y, inits, S, B, 17, priors, C_)
+    for k in ("theta", "beta", "f", "IRFs", "diagnostics"):
+        _same(empty[k], ref[k], "empty run: " + k)
+    _same(empty["pooled"], {k: v for k, v in ref["summary"].items() if k != "totals"}, "empty run: summary")
+    assert dict(zip(_lib.SUM_TOTALS, empty["totals"])) == ref["summary"]["totals"]
+    every = dict(ppc=True, ranks=True, shape=True, loo=True)
+    full = gpirtMCMC(y, S, B, theta_init=inits, chains=C_, **every, **kw)
+    for k in ("theta", "beta", "f", "IRFs", "summary"):
+        _same(full[k], ref[k], k)
+    assert full["ranks"]["draws"] == C_ * S and full["ranks"]["skipped_draws"] == 0
+    assert full["ppc"]["totals"]["draws"] == C_ * S and (full["shape"]["draws"] == C_ * S).all()
+    lo = full["loo"]
+    assert (lo["T"], lo["M"], lo["draws"], lo["chains"], lo["cells_incomplete"]) == (C_ * S, 1, C_ * S, C_, 0)
+    assert lo["n_obs"] == 23 and (lo["raw"]["count"][~np.isnan(y)] == C_ * S).all()
+    one = gpirtMCMC(y, S, B, theta_init=inits[:1], chains=1, **every, **kw)
+    for k in ("theta", "beta", "f"):
+        _same(one[k][0], ref[k][0], k + " of chain 0")
+    lo = one["loo"]
+    assert (lo["T"], lo["M"], lo["draws"], lo["chains"], lo["cells_incomplete"]) == (S, 0, S, 1, 0)
+    assert lo["n_obs"] == 23 and (lo["raw"]["count"][~np.isnan(y)] == S).all() and one["ranks"]["draws"] == S

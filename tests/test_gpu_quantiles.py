@@ -1,5 +1,5 @@
 """Quantiles on the device (include/gpirt_hip.h GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND, gpirt_summary_quantiles,
-gpirt_mcmc_quantiles) against NumPy over the stored draws: exact histograms and theta quantiles, the band interpolation
+gpirt_mcmc_run) against NumPy over the stored draws: exact histograms and theta quantiles, the band interpolation
 and its 1/256 bound, E[P], the rank-normalised R-hat; several chains with the reflection; the R-stream chain; the new parts
 leaving every existing output alone; a hang-guard rollback; the metric size."""
 import math

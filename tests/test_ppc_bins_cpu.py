@@ -240,7 +240,7 @@ def test_c_abi_of_version_112():
     p = _lib.PpcBins()
     assert C.sizeof(p) == 8 + 4 * 16 + 8 * (7 + 4 + 3 + 5 + 3 + 2 + 2 + 1 + 3) + 8 * 9
     for name in ("gpirt_sampler_ppc_bins_enable", "gpirt_sampler_ppc_bins_get", "gpirt_sampler_ppc_bins_state",
-                 "gpirt_ppc_bins_combine", "gpirt_mcmc_bins"):
+                 "gpirt_ppc_bins_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     # argument errors come back before any device is touched
     p.top = 20

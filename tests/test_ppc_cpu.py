@@ -177,14 +177,14 @@ def test_result_derives_the_p_values():
 def test_abi_version_symbols_and_struct(lib):
     assert lib.gpirt_version() >= 107
     for name in ("gpirt_sampler_ppc_enable", "gpirt_sampler_ppc_accumulate", "gpirt_sampler_ppc_get", "gpirt_sampler_ppc_totals",
-                 "gpirt_sampler_ppc_state", "gpirt_ppc_combine", "gpirt_mcmc_ppc"):
+                 "gpirt_sampler_ppc_state", "gpirt_ppc_combine", "gpirt_mcmc_run"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES, name
     nf = len(_lib.PPC_FIELDS)
     assert nf == 15 and C.sizeof(_lib.Ppc) == 8 * (3 * nf + 4)
     assert _lib.Ppc.reserved.offset == 8 * 3 * nf
 
 
-def _mcmc_ppc_args(pp, q=None, reserved_ok=True):
+def _mcmc_ppc_args(pp, run=True):
     dp = C.POINTER(C.c_double)
     y = np.ones((4, 2), order="F")
     th = np.zeros(4)
@@ -192,10 +192,12 @@ def _mcmc_ppc_args(pp, q=None, reserved_ok=True):
     irf = np.zeros((1001, 2), order="F")
     o = _lib.fast_options()
     sm = _lib.Summary()
-    keep = (y, th, p, irf, o, sm)
+    r = _lib.Run()
+    r.ppc = C.pointer(pp)
+    keep = (y, th, p, irf, o, sm, r)
     a = lambda x: x.ctypes.data_as(dp)          # noqa: E731
     return keep, (a(y), 4, 2, a(th), 1, 1, 0, a(p), a(p), a(p), C.byref(o), 1, _lib.TICK_FN(0), None, None, None, None,
-                  a(irf), C.byref(sm), None, None, q, C.byref(pp))
+                  a(irf), C.byref(sm), None, C.byref(r) if run else None)
 
 
 def test_mcmc_ppc_without_a_gpu_and_argument_errors(lib):
@@ -203,14 +205,17 @@ def test_mcmc_ppc_without_a_gpu_and_argument_errors(lib):
     pp = _lib.Ppc()
     pp.reserved[2] = 1
     keep, args = _mcmc_ppc_args(pp)
-    assert lib.gpirt_mcmc_ppc(*args) == _lib.E_ARG           # refused before any device is touched
+    assert lib.gpirt_mcmc_run(*args) == _lib.E_ARG           # refused before any device is touched
+    assert "bad argument" in _lib.last_error()
+    keep, args = _mcmc_ppc_args(_lib.Ppc(), run=False)
+    assert lib.gpirt_mcmc_run(*args) == _lib.E_ARG           # run is required
     assert "bad argument" in _lib.last_error()
     assert lib.gpirt_ppc_combine(None, 1, None, C.byref(pp)) == _lib.E_ARG
     if torch.cuda.is_available():
         return
     pp = _lib.Ppc()
     keep, args = _mcmc_ppc_args(pp)
-    assert lib.gpirt_mcmc_ppc(*args) == _lib.E_NODEVICE
+    assert lib.gpirt_mcmc_run(*args) == _lib.E_NODEVICE
     assert "no CPU fallback" in _lib.last_error()
     from gpirt_amd import gpirtMCMC
     with pytest.raises(_lib.GpirtError):

@@ -215,7 +215,7 @@ def test_c_abi_of_version_115():
     assert C.sizeof(p) == 4 * 3 + 4 * 16 + 4 + 8 + 8 * (3 + 1 + 6 + 9) + 8 * 19 + 8 * 3 + 8 * 5 + 8 * 4 + 8 * 4
     assert len(_lib.DIF_RAW) == 19 and len(_lib.DIF_FOCAL_FIELDS) == 9
     for name in ("gpirt_sampler_ppc_dif_enable", "gpirt_sampler_ppc_dif_get", "gpirt_sampler_ppc_dif_state",
-                 "gpirt_ppc_dif_combine", "gpirt_mcmc_dif"):
+                 "gpirt_ppc_dif_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     # argument errors come back before any device is touched
     assert lib.gpirt_ppc_dif_combine(None, 1, None, None, C.byref(p)) == _lib.E_ARG

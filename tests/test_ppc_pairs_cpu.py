@@ -175,7 +175,7 @@ def test_c_abi_of_version_111():
     p = _lib.PpcPairs()
     assert C.sizeof(p) == 8 + 8 * (19 + 3 + 6 + 3) + 8 * 8
     for name in ("gpirt_sampler_ppc_pairs_enable", "gpirt_sampler_ppc_pairs_get", "gpirt_sampler_ppc_pairs_state",
-                 "gpirt_ppc_pairs_combine", "gpirt_mcmc_pairs"):
+                 "gpirt_ppc_pairs_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     # argument errors come back before any device is touched
     assert lib.gpirt_ppc_pairs_combine(None, 1, None, C.byref(p)) == _lib.E_ARG

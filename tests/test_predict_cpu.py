@@ -20,7 +20,7 @@ from _score_bounds import EPS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 1001
 NEW = ("gpirt_sampler_score_predict_enable", "gpirt_sampler_score_predict_get", "gpirt_sampler_score_predict_state",
-       "gpirt_score_predict_combine", "gpirt_mcmc_predict")
+       "gpirt_score_predict_combine", "gpirt_mcmc_run")
 
 
 def _fstar(S, m, seed=3):
@@ -165,7 +165,7 @@ def test_abi_of_version_110():
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
     assert re.search(r"#define GPIRT_PREDICT_MAX_TOP\s+%d\b" % _lib.PREDICT_MAX_TOP, hdr)
-    assert len(_lib.SIGNATURES["gpirt_mcmc_predict"][1]) == len(_lib.SIGNATURES["gpirt_mcmc_score"][1]) + 1
+    assert _lib.Run.predict.offset == _lib.Run.score.offset + 8          # gpirt_run: predict follows score
 
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs a C compiler")

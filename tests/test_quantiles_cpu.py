@@ -1,4 +1,4 @@
-"""Quantiles (include/gpirt_hip.h GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND, gpirt_summary_quantiles, gpirt_mcmc_quantiles)
+"""Quantiles (include/gpirt_hip.h GPIRT_SUM_THETA_HIST, GPIRT_SUM_IRF_BAND, gpirt_summary_quantiles, gpirt_mcmc_run)
 on a machine without a GPU: the entry points are exported and bound, the state block grows by exactly the new arrays, the
 band edges, the argument checks, and the two NumPy routes -- over stored draws (scipy's ranks) and over the histograms
 alone -- agree, with ties, odd S, 1..4 chains, reflection, constant chains and draws off the grid, and on a hand-worked
@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("gpirt_irf_band_edges", "gpirt_summary_quantiles", "gpirt_mcmc_quantiles")
+NEW = ("gpirt_irf_band_edges", "gpirt_summary_quantiles", "gpirt_mcmc_run")
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +87,7 @@ def test_band_edges(lib):
         assert abs(got - want) <= 4 * math.ulp(want), (b, got, want)
 
 
-def _mcmc_q(lib, chains=2, rng_item=True, rs=None, q=None, pooled_parts=None, probs=(0.1, 0.9)):
+def _mcmc_q(lib, chains=2, rng_item=True, rs=None, q=None, pooled_parts=None, probs=(0.1, 0.9), no_run=False):
     from gpirt_amd import _lib
     dp = C.POINTER(C.c_double)
     n, m = 4, 2
@@ -106,9 +106,12 @@ def _mcmc_q(lib, chains=2, rng_item=True, rs=None, q=None, pooled_parts=None, pr
         q = _lib.Quantiles()
         q.nprobs = pr.size
         q.probs = pr.ctypes.data_as(dp)
-    return lib.gpirt_mcmc_quantiles(y.ctypes.data_as(dp), n, m, th.ctypes.data_as(dp), chains, 4, 1, p.ctypes.data_as(dp),
-                                    p.ctypes.data_as(dp), p.ctypes.data_as(dp), C.byref(o), 1, _lib.TICK_FN(0), None, None,
-                                    None, None, irf.ctypes.data_as(dp), C.byref(sm), None, rs, C.byref(q) if q else None)
+    run = _lib.Run()
+    run.rs = rs
+    run.quantiles = C.pointer(q)
+    return lib.gpirt_mcmc_run(y.ctypes.data_as(dp), n, m, th.ctypes.data_as(dp), chains, 4, 1, p.ctypes.data_as(dp),
+                              p.ctypes.data_as(dp), p.ctypes.data_as(dp), C.byref(o), 1, _lib.TICK_FN(0), None, None,
+                              None, None, irf.ctypes.data_as(dp), C.byref(sm), None, None if no_run else C.byref(run))
 
 
 def test_argument_errors_and_no_device(lib):
@@ -118,7 +121,8 @@ def test_argument_errors_and_no_device(lib):
     assert lib.gpirt_summary_quantiles(None, 1, None, None, 1, None) == _lib.E_ARG
     q = _lib.Quantiles()
     assert lib.gpirt_summary_quantiles(None, 1, None, None, 1, C.byref(q)) == _lib.E_ARG
-    assert _mcmc_q(lib, q=False) == _lib.E_ARG                                  # q is required
+    assert _mcmc_q(lib, no_run=True) == _lib.E_ARG                              # run is required
+    assert "bad argument" in _lib.last_error()
     assert _mcmc_q(lib, probs=(0.5, 1.5)) == _lib.E_ARG                         # a probability outside [0, 1]
     assert _mcmc_q(lib, probs=(float("nan"),)) == _lib.E_ARG
     assert _mcmc_q(lib, pooled_parts=_lib.SUM_WAIC | _lib.SUM_THETA_HIST) == _lib.E_ARG     # not a pooled part

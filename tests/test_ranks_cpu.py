@@ -253,7 +253,7 @@ def test_abi_of_version_108():
     lib = _lib.load()
     assert lib.gpirt_version() >= 108
     for name in ("gpirt_sampler_rank_enable", "gpirt_sampler_rank_accumulate", "gpirt_sampler_rank_get",
-                 "gpirt_sampler_rank_state", "gpirt_rank_combine", "gpirt_mcmc_ranks"):
+                 "gpirt_sampler_rank_state", "gpirt_rank_combine", "gpirt_mcmc_run"):
         assert hasattr(lib, name)
     # 8 + 4 + 4 + 32 * 8 + 4 + 4 + 10 pointers + 4 int64 + a double + 4 int64
     assert C.sizeof(_lib.Ranks) == 8 + 8 + 256 + 8 + 80 + 32 + 8 + 32

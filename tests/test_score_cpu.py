@@ -117,7 +117,7 @@ def test_abi_of_version_109():
     lib = _lib.load()
     assert lib.gpirt_version() >= 109
     for name in ("gpirt_sampler_score_enable", "gpirt_sampler_score_accumulate", "gpirt_sampler_score_get",
-                 "gpirt_sampler_score_state", "gpirt_score_combine", "gpirt_mcmc_score"):
+                 "gpirt_sampler_score_state", "gpirt_score_combine", "gpirt_mcmc_run"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
     r, arrays = SC.struct(3, (0.1, 0.9))
     assert r.nprobs == 2 and arrays["grid_post"].shape == (3, N) and arrays["theta_quantiles"].shape == (2, 3)

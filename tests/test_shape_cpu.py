@@ -147,7 +147,7 @@ def test_c_abi_of_version_113():
     p = _lib.Shape()
     assert C.sizeof(p) == 8 + 8 * 4 + 8 * 13 + 8 * 4 + 8 * 4 and len(_lib.SHAPE_RAW) == 13
     for name in ("gpirt_sampler_shape_enable", "gpirt_sampler_shape_accumulate", "gpirt_sampler_shape_get",
-                 "gpirt_sampler_shape_state", "gpirt_shape_state_bytes", "gpirt_shape_combine", "gpirt_mcmc_shape"):
+                 "gpirt_sampler_shape_state", "gpirt_shape_state_bytes", "gpirt_shape_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     # argument errors come back before any device is touched
     assert lib.gpirt_shape_combine(None, 1, None, None, C.byref(p)) == _lib.E_ARG

@@ -193,7 +193,7 @@ def test_c_abi_of_version_114():
     assert C.sizeof(p) == 8 + 8 * 11 + 8 * 2 + 8 * 4 + 8 * 4 and len(_lib.SUMSCORE_RAW) == 11
     for name in ("gpirt_sampler_sumscore_enable", "gpirt_sampler_sumscore_accumulate", "gpirt_sampler_sumscore_get",
                  "gpirt_sampler_sumscore_state", "gpirt_sumscore_state_bytes", "gpirt_sumscore_grid_weights",
-                 "gpirt_sumscore_combine", "gpirt_mcmc_sumscore"):
+                 "gpirt_sumscore_combine", "gpirt_mcmc_run"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     # argument errors come back before any device is touched
     assert lib.gpirt_sumscore_combine(None, 1, None, None, C.byref(p)) == _lib.E_ARG
