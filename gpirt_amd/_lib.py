@@ -181,6 +181,41 @@ class PpcDif(C.Structure):
                 ("group_size", C.c_int64 * DIF_MAX_G), ("reserved", C.c_int64 * 4)]
 
 
+# score-based checks (include/gpirt_hip.h GPIRT_SCORES_*): the finished fields per score (m + 1), of the spread (3), per item and
+# per (group, item), in order; the raw arrays of the state block with their dtypes and shapes ("h": m + 1, "s": 4 x m, "v": 2,
+# "1": 1, "i": m, "c": K x m), the constants first
+SCORES_HIST_FIELDS = ("score_hist_obs", "score_hist_rep_mean", "score_hist_rep_sd", "ppp_hist", "ppp_hist_mid", "ppp_cdf",
+                      "ppp_cdf_mid")
+SCORES_VAR_FIELDS = ("score_var_obs", "score_var_rep_mean", "ppp_var")
+SCORES_ITEM_FIELDS = ("r_rep_mean", "r_rep_sd", "ppp_r", "ppp_r_mid", "r_undefined", "ppp_chi2", "ppp_chi2_mid", "chi2_obs_mean",
+                      "chi2_rep_mean")
+SCORES_CELL_FIELDS = ("obs_rate", "rep_rate", "exp_rate", "ppp_cell", "ppp_cell_mid")
+SCORES_CONST = (("hist_obs", "i8", "h"), ("sums_obs", "i8", "s"), ("var_obs", "i8", "v"), ("r_obs", "f8", "i"), ("tNo", "u4", "c"),
+                ("tT", "u4", "c"))
+SCORES_RAW = SCORES_CONST + (
+    ("hist_sum", "u8", "h"), ("hist_sumsq", "u8", "h"), ("hist_ge", "u4", "h"), ("hist_gt", "u4", "h"), ("cdf_ge", "u4", "h"),
+    ("cdf_gt", "u4", "h"), ("var_ge", "u4", "1"), ("var_gt", "u4", "1"), ("var_rep_sum", "u8", "1"),
+    ("r_ge", "u4", "i"), ("r_gt", "u4", "i"), ("r_undefined_count", "u4", "i"), ("r_rep_sum", "f8", "i"), ("r_rep_sumsq", "f8", "i"),
+    ("cell_ge", "u4", "c"), ("cell_gt", "u4", "c"), ("cell_empty", "u4", "c"), ("sum_nr", "u8", "c"), ("sum_r", "u8", "c"),
+    ("sum_eo", "f8", "c"), ("sum_er", "f8", "c"),
+    ("chi_ge", "u4", "i"), ("chi_gt", "u4", "i"), ("chi_obs_sum", "f8", "i"), ("chi_rep_sum", "f8", "i"))
+# the last counted draw's arrays of gpirt_sampler_ppc_scores_get
+SCORES_LAST = (("xr", "i4", "n"), ("hist", "i8", "h"), ("sums", "i8", "s"), ("r", "f8", "i"), ("tNr", "u4", "c"), ("tR", "u4", "c"),
+               ("tEo", "i8", "c"), ("tVo", "i8", "c"), ("tEr", "i8", "c"), ("tVr", "i8", "c"), ("chi", "f8", "x"))
+SCORES_MAX_M, SCORES_MAX_N, SCORES_MAX_K, SCORES_MAX_TOP, SCORES_TAG = 4096, 65534, 16, 64, 0x31524353
+
+
+class PpcScores(C.Structure):
+    """gpirt_ppc_scores (include/gpirt_hip.h): top, the cuts, host pointers per output (NULL: not wanted), counters."""
+    _fields_ = [("top", C.c_int), ("K", C.c_int), ("cuts", C.c_int * SCORES_MAX_K),
+                ("hist", C.POINTER(C.c_double) * len(SCORES_HIST_FIELDS)), ("var", C.POINTER(C.c_double)),
+                ("item", C.POINTER(C.c_double) * len(SCORES_ITEM_FIELDS)), ("cell", C.POINTER(C.c_double) * len(SCORES_CELL_FIELDS)),
+                ("raw", C.c_void_p * len(SCORES_RAW)), ("group_lo", C.POINTER(C.c_int64)), ("group_hi", C.POINTER(C.c_int64)),
+                ("worst_items", C.POINTER(C.c_int64)), ("worst_ppp_chi2_mid", C.POINTER(C.c_double)),
+                ("n", C.c_int64), ("m", C.c_int64), ("score_draws", C.c_int64), ("score_skipped", C.c_int64),
+                ("n_scored", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -455,6 +490,11 @@ SIGNATURES = {
     "gpirt_sampler_ppc_dif_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_dif_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_dif_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(PpcDif)]),
+    "gpirt_ppc_scores_check": (_i32, [_i64, _i64, _i32, C.POINTER(C.c_int)]),
+    "gpirt_sampler_ppc_scores_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int), _i32]),
+    "gpirt_sampler_ppc_scores_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_scores_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_scores_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcScores)]),
     "gpirt_sampler_equate_enable": (_i32, [_vp, _vp, _vp, _i32]),
     "gpirt_sampler_equate_accumulate": (_i32, [_vp]),
     "gpirt_sampler_equate_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),

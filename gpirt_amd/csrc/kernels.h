@@ -473,6 +473,55 @@ int64_t dif_state_words(const DifState* p);
 int dif_get(hipStream_t stream, DifState* p, const char* name, void* h_out, int64_t bytes);
 int dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out);
 
+// ppc_scores.hip: the score-based checks (gpirt_sampler_ppc_scores_*), an add-on to a PPC state.  Its accumulators are ONE device
+// block of 8-byte words of their own: a header of PPS_HEADER_WORDS int64 (PPS_TAG, layout version, n, m, K, score_draws,
+// score_skipped, 0 -- the two counters are kept by pps_update_kernel), PPS_CUT_WORDS int64 with the cuts, then the arrays of
+// PpsLayout (the constants first), (k, j) at [k m + j], every array padded to 16 bytes.  Beside it: the replicate's bit plane
+// repw[j][W] (W = ceil(n / 64) words per item), the strips' row partials (rep count | observed << 16), X and the last counted
+// draw's Xr, the respondents with an observed cell, this draw's histogram, the control word ctl[0] = a non-finite g in an observed
+// cell, this draw's tables [5][K][m] (Nr | R << 32, Er, Vr, Eo, Vo in units of 2^-44) and item sums [4][m] (A, B, Cq, D) --
+// zero between draws: pps_update_kernel clears what it has read --, and the last counted draw's tables and statistics.
+constexpr int PPS_LAYOUT_VERSION = 1;
+constexpr int PPS_HEADER_WORDS = 8;
+constexpr int PPS_CUT_WORDS = 16;
+constexpr int64_t PPS_TAG = 0x31524353;             // "SCR1"
+enum { PPS_HIST_OBS, PPS_SUMS_OBS, PPS_VAR_OBS, PPS_R_OBS, PPS_TNO, PPS_TT,                                     // the constants
+       PPS_HIST_SUM, PPS_HIST_SUMSQ, PPS_HIST_GE, PPS_HIST_GT, PPS_CDF_GE, PPS_CDF_GT,                          // m + 1
+       PPS_VAR_GE, PPS_VAR_GT, PPS_VAR_REP_SUM,                                                              // 1
+       PPS_R_GE, PPS_R_GT, PPS_R_UNDEF, PPS_R_REP_SUM, PPS_R_REP_SUMSQ,                                        // m
+       PPS_CELL_GE, PPS_CELL_GT, PPS_CELL_EMPTY, PPS_SUM_NR, PPS_SUM_R, PPS_SUM_EO, PPS_SUM_ER,                  // K x m
+       PPS_CHI_GE, PPS_CHI_GT, PPS_CHI_OBS, PPS_CHI_REP,                                                      // m
+       PPS_NARRAYS };
+static_assert(PPS_NARRAYS == GPIRT_SCORES_NRAW, "gpirt_ppc_scores::raw");
+struct PpsLayout { int64_t off[PPS_NARRAYS]; int64_t words; };      // offsets in 8-byte words from the start of the block
+PpsLayout pps_layout(int64_t m, int64_t K);
+struct PpsState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0, W = 0;
+    int K = 0, strips = 0;
+    int cuts[GPIRT_SCORES_MAX_K] = {};
+    uint64_t* block = nullptr;
+    uint64_t* repw = nullptr;                                         // [m][W]
+    uint32_t* xpart = nullptr;                                        // [strips][n]
+    int32_t *x_obs = nullptr, *xr = nullptr;                          // [n]
+    unsigned char* live = nullptr;                                    // [n]
+    uint32_t* hist_cur = nullptr; int64_t* hist_last = nullptr;       // [m + 1]
+    int* ctl = nullptr;
+    uint64_t *tab = nullptr, *tab_last = nullptr;                     // [5][K][m]
+    uint64_t *isum = nullptr, *isum_last = nullptr;                   // [4][m]
+    double *r_last = nullptr, *chi_last = nullptr;                    // [m], [2][m]
+    std::vector<void*> allocs;
+};
+int pps_check(int64_t n, int64_t m, int K, const int* cuts);       // GPIRT_E_ARG with the message
+int pps_alloc(hipStream_t stream, PpsState* p, int64_t n, int64_t m, int64_t item0, const double* y, int K, const int* cuts);
+void pps_free(PpsState* p);
+// one draw: the replicate's bit plane and row scores, the columns' tables, then the statistics and the accumulators
+int launch_pps_accumulate(hipStream_t stream, PpsState* p, const double* f, const double* mu, const double* y, uint64_t seed,
+                            uint32_t iter);
+int64_t pps_state_words(const PpsState* p);
+int pps_get(hipStream_t stream, PpsState* p, const char* name, void* h_out, int64_t bytes);
+int pps_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_scores* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -484,6 +533,7 @@ struct PpcState {
     PairState pairs;                                  // the pairwise item checks (ppc_pairs.hip; on == false: off)
     BinState bins;                                    // the theta-binned item fit (ppc_bins.hip; on == false: off)
     DifState dif;                                     // the group-wise item fit (ppc_dif.hip; on == false: off)
+    PpsState scores;                                  // the score-based checks (ppc_scores.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written

@@ -360,6 +360,7 @@ void ppc_free(PpcState* s)
     pair_free(&s->pairs);
     bin_free(&s->bins);
     dif_free(&s->dif);
+    pps_free(&s->scores);
     for (void* p : s->allocs) hipFree(p);
     *s = PpcState{};
 }
@@ -402,6 +403,7 @@ int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const do
     if (s->pairs.on) GP_TRY(launch_pair_accumulate(st, &s->pairs));
     if (bins) GP_TRY(launch_bin_update(st, &s->bins));
     if (s->dif.on) GP_TRY(launch_dif_accumulate(st, &s->dif, f, mu, y, seed, iter, theta));     // (ppc_dif.hip: launches of its own)
+    if (s->scores.on) GP_TRY(launch_pps_accumulate(st, &s->scores, f, mu, y, seed, iter));       // (ppc_scores.hip: likewise)
     return 0;
 }
 

@@ -1716,6 +1716,54 @@ int gpirt_ppc_dif_combine(gpirt_handle_t h, int chains, const void* const* d_sta
     return dif_combine(h, chains, d_states, signs, out);
 }
 
+// ---- score-based checks (ppc_scores.hip): an add-on to the PPC state ---------------------------------------------------------
+static int scores_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.scores.on) return 0;
+    set_error("the score-based checks are not enabled (gpirt_sampler_ppc_scores_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_ppc_scores_check(int64_t n, int64_t m, int K, const int* cuts) { return pps_check(n, m, K, cuts); }
+
+int gpirt_sampler_ppc_scores_enable(gpirt_sampler_t s, int K, const int* cuts, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    pps_free(&s->ppc.scores);
+    if (!on) return 0;
+    GP_TRY(ppc_needs_on(s));
+    if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
+        set_error("the score-based checks are not offered for item shards (a respondent's score runs over all items)");
+        return GPIRT_E_ARG;
+    }
+    const int rc = pps_alloc(s->h->stream, &s->ppc.scores, s->n, s->m, s->opt.item0, s->y, K, cuts);
+    if (rc) pps_free(&s->ppc.scores);
+    return rc;
+}
+
+int gpirt_sampler_ppc_scores_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(scores_needs_on(s));
+    return pps_get(s->h->stream, &s->ppc.scores, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_scores_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(scores_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.scores.block;
+    *bytes = pps_state_words(&s->ppc.scores) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_scores_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_scores* out)
+{
+    return pps_combine(h, chains, d_states, out);
+}
+
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
 static int rank_needs_on(gpirt_sampler_t s)
 {

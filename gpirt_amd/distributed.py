@@ -258,6 +258,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the group-wise item fit is not offered for item shards "
                          "(it is an add-on to the posterior predictive checks, which are not offered either)")
 
+    def ppc_scores_enable(self, cuts=None, groups=9, top=20, on=True):
+        raise ValueError("ShardedSampler: the score-based checks are not offered for item shards "
+                         "(a respondent's score runs over all items, and each rank holds its own columns)")
+
     # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         self.engine.rank_enable(on, pivots, pairwise)

@@ -16,8 +16,8 @@ The theta-binned item fit ("theta-binned item fit" in the header; csrc/ppc_bins.
 reflection signs, `bins_from_rep` is the NumPy statement of the header over stored theta, g and replicates (integers exact,
 E, V and X2 in np.longdouble, the chi-square decisions as (lo, hi) brackets from `bins_bounds`) and `bins_from_draws` builds
 the replicates from stored g draws.
-The group-wise item fit ("group-wise item fit" in the header; csrc/ppc_dif.hip) is the third add-on: see the section at the end
-of this module.
+The group-wise item fit ("group-wise item fit" in the header; csrc/ppc_dif.hip) is the third add-on and the score-based checks
+("score-based PPC" in the header; csrc/ppc_scores.hip) the fourth: see their sections at the end of this module.
 ShardedSampler is not covered: the respondents' statistics would need one all-reduce per draw.  The keying of the
 uniforms by the global item index keeps that possible.
 """
@@ -1072,3 +1072,404 @@ def dif_from_draws(y, theta_draws, g_draws, seed, iters, groups, cuts=DEFAULT_CU
         reps.append(obs & (u < p))
     rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
     return dif_from_rep(y, theta_draws, g_draws, rep, groups, cuts, top, signs), gap
+
+
+# ------------------------------------------------------------------------------------------------ score-based checks ---
+# ("score-based PPC" in the header; csrc/ppc_scores.hip) the fourth add-on, on the MANIFEST score: `check_score_cuts` /
+# `default_score_cuts`, `scores_struct` / `scores_result` wrap gpirt_ppc_scores, `scores_combine` pools chains' state blocks,
+# `scores_observed` / `scores_tables` / `scores_draw_stats` / `scores_from_tables` are the NumPy statement of the header --
+# integer tables, then fp64 operations in the header's order, so the same tables give the same bits --, `scores_from_rep` runs it
+# over stored g and replicates, `scores_from_draws` builds the replicates with this module's Philox.
+DEFAULT_SCORES_TOP = 20
+DEFAULT_SCORE_GROUPS = 9
+SCORES_FIX = 2.0 ** 44
+_SC_DTYPES = {"u8": np.uint64, "f8": np.float64, "u4": np.uint32, "i8": np.int64, "i4": np.int32}
+
+
+def check_scores_top(top) -> int:
+    t = int(top)
+    if t != top or not 1 <= t <= _lib.SCORES_MAX_TOP:
+        raise ValueError(f"scores: top must be an integer in 1..{_lib.SCORES_MAX_TOP}")
+    return t
+
+
+def check_score_cuts(cuts, m: int, n: int = 1) -> tuple:
+    """The cuts as a tuple of ints: ascending c_1 < ... < c_{K-1} in 1 .. m - 1, 2 <= K <= 16 groups; 2 <= m <= 4096 items and
+    n <= 65534 respondents.  Anything else is a ValueError that says which."""
+    if not 2 <= int(m) <= _lib.SCORES_MAX_M:
+        raise ValueError(f"scores: m = {m} is outside 2..{_lib.SCORES_MAX_M} items")
+    if n > _lib.SCORES_MAX_N:
+        raise ValueError(f"scores: n = {n} is beyond {_lib.SCORES_MAX_N} respondents")
+    try:
+        c = tuple(int(x) for x in cuts)
+        whole = all(float(a) == float(b) for a, b in zip(c, cuts))
+    except (TypeError, ValueError):
+        raise ValueError("scores: the cuts must be a sequence of integers") from None
+    if not whole:
+        raise ValueError("scores: the cuts must be integers")
+    if not 2 <= len(c) + 1 <= _lib.SCORES_MAX_K:
+        raise ValueError(f"scores: {len(c)} cuts make {len(c) + 1} score groups, 2..{_lib.SCORES_MAX_K} groups are taken")
+    if any(not 1 <= x <= m - 1 for x in c) or any(b <= a for a, b in zip(c, c[1:])):
+        raise ValueError(f"scores: the cuts must be increasing integers in 1..{m - 1}, got {c}")
+    return c
+
+
+def default_score_cuts(y, groups: int = DEFAULT_SCORE_GROUPS) -> tuple:
+    """Up to `groups` score groups from the quantiles of the data's total scores (raw counts over each respondent's own observed
+    items, the respondents without an observed cell left out): the sorted scores at the positions k n_s // groups, k = 1 ..
+    groups - 1, those outside 1 .. m - 1 and duplicates dropped.  Fewer than two groups is a ValueError that says so."""
+    y = np.asarray(y, dtype=np.float64)
+    g = int(groups)
+    if g != groups or not 2 <= g <= _lib.SCORES_MAX_K:
+        raise ValueError(f"scores: groups must be an integer in 2..{_lib.SCORES_MAX_K}")
+    ob = ~np.isnan(y)
+    x = np.sort((ob & (y > 0)).sum(axis=1)[ob.any(axis=1)])
+    m = y.shape[1]
+    c = sorted({int(x[k * len(x) // g]) for k in range(1, g)} & set(range(1, m))) if len(x) else []
+    if not c:
+        raise ValueError("scores: the data's total scores give fewer than two score groups (no quantile lies in 1 .. m - 1); "
+                         "pass cuts")
+    return tuple(c)
+
+
+def _scores_shape(kind, n, m, K):
+    return {"h": (m + 1,), "s": (4, m), "v": (2,), "1": (1,), "i": (m,), "c": (K, m), "n": (n,), "x": (2, m)}[kind]
+
+
+def scores_field(name: str, n: int, m: int, K: int):
+    """(shape, dtype) of the array gpirt_sampler_ppc_scores_get copies for `name`: a finished field (SCORES_HIST_FIELDS: m + 1;
+    SCORES_VAR_FIELDS: 0-d; SCORES_ITEM_FIELDS: m; SCORES_CELL_FIELDS: K x m), a raw array or constant of SCORES_RAW, group_lo,
+    group_hi, cuts, counts, x_obs or an array of SCORES_LAST.  An unknown name is a ValueError that says so."""
+    named = {r[0]: r for r in _lib.SCORES_RAW + _lib.SCORES_LAST}
+    fixed = {"counts": ((2,), np.int64), "cuts": ((K - 1,), np.int64), "group_lo": ((K,), np.int64), "group_hi": ((K,), np.int64),
+             "x_obs": ((n,), np.int32)}
+    if name in fixed:
+        return fixed[name]
+    if name in named:
+        _, dt, kind = named[name]
+        return _scores_shape(kind, n, m, K), _SC_DTYPES[dt]
+    for names, shape in ((_lib.SCORES_HIST_FIELDS, (m + 1,)), (_lib.SCORES_VAR_FIELDS, ()), (_lib.SCORES_ITEM_FIELDS, (m,)),
+                         (_lib.SCORES_CELL_FIELDS, (K, m))):
+        if name in names:
+            return shape, np.float64
+    raise ValueError(f"scores: unknown field {name!r}")
+
+
+def scores_struct(m: int, K: int, top=DEFAULT_SCORES_TOP):
+    """A gpirt_ppc_scores with host arrays for every output, and those arrays (kept alive by the caller)."""
+    p = _lib.PpcScores()
+    p.top = check_scores_top(top)
+    arr = {}
+    for grp, names, shape in (("hist", _lib.SCORES_HIST_FIELDS, (m + 1,)), ("item", _lib.SCORES_ITEM_FIELDS, (m,)),
+                              ("cell", _lib.SCORES_CELL_FIELDS, (K, m))):
+        for k, name in enumerate(names):
+            arr[name] = np.empty(shape)
+            getattr(p, grp)[k] = arr[name].ctypes.data_as(_dp)
+    arr["_var"] = np.empty(3)
+    p.var = arr["_var"].ctypes.data_as(_dp)
+    for k, (name, dt, kind) in enumerate(_lib.SCORES_RAW):
+        arr[name] = np.empty(_scores_shape(kind, 0, m, K), dtype=_SC_DTYPES[dt])
+        p.raw[k] = arr[name].ctypes.data
+    for name in ("group_lo", "group_hi"):
+        arr[name] = np.empty(K, dtype=np.int64)
+        setattr(p, name, arr[name].ctypes.data_as(C.POINTER(C.c_int64)))
+    arr["worst_items"] = np.empty(p.top, dtype=np.int64)
+    p.worst_items = arr["worst_items"].ctypes.data_as(C.POINTER(C.c_int64))
+    arr["worst_ppp_chi2_mid"] = np.empty(p.top)
+    p.worst_ppp_chi2_mid = arr["worst_ppp_chi2_mid"].ctypes.data_as(_dp)
+    return p, arr
+
+
+def scores_result(p, arr) -> dict:
+    """The dict of Sampler.ppc_scores() and scores_combine(): every array of the header by name (cell (k, j) at [k, j]), the
+    three values of the spread as floats, "cuts", "worst" (dict: items, ppp_chi2_mid) and the counters."""
+    out = {k: v for k, v in arr.items() if not k.startswith("worst_") and not k.startswith("_")}
+    for k, name in enumerate(_lib.SCORES_VAR_FIELDS):
+        out[name] = float(arr["_var"][k])
+    out["worst"] = dict(items=arr["worst_items"], ppp_chi2_mid=arr["worst_ppp_chi2_mid"])
+    out["cuts"] = np.array([p.cuts[q] for q in range(p.K - 1)], dtype=np.int64)
+    out.update(n=int(p.n), m=int(p.m), K=int(p.K), score_draws=int(p.score_draws), score_skipped=int(p.score_skipped),
+               n_scored=int(p.n_scored))
+    return out
+
+
+def scores_state_header(state) -> dict:
+    """The header of a score-based state block (a device tensor): its 8 int64 words and the cuts."""
+    w = state[:24].cpu().numpy().view(np.int64)
+    K = int(w[4])
+    return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), K=K, score_draws=int(w[5]), score_skipped=int(w[6]),
+                cuts=tuple(int(x) for x in w[8:8 + max(min(K, 16) - 1, 0)]))
+
+
+def scores_combine(handle, states, top=DEFAULT_SCORES_TOP) -> dict:
+    """gpirt_ppc_scores_combine over the score-based state blocks `states` (device tensors, or Samplers with ppc_scores_enable()
+    on, all on handle's device): the integers added, the doubles added in chain order; no signs (theta -> -theta leaves f + mu
+    as it is).  Blocks with another n, m, K, cuts or response matrix are refused."""
+    lib = _lib.load()
+    tensors = [s.ppc_scores_state() if hasattr(s, "ppc_scores_state") else s for s in states]
+    hdr = scores_state_header(tensors[0])
+    if hdr["tag"] != _lib.SCORES_TAG or not 2 <= hdr["K"] <= _lib.SCORES_MAX_K or not 2 <= hdr["m"] <= _lib.SCORES_MAX_M:
+        raise ValueError("scores_combine: the first state is not a score-based PPC state block")
+    p, arr = scores_struct(hdr["m"], hdr["K"], top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    check(lib.gpirt_ppc_scores_combine(handle.ptr, nc, ptrs, C.byref(p)))
+    return scores_result(p, arr)
+
+
+def _score_r(N, sums):
+    """r = (double)NUM / sqrt((double)VA (double)VC) per item from the integer sums (4 x m: A, B, Cq, D); NaN when VA or VC is 0"""
+    N = np.asarray(N, dtype=np.int64)
+    A, B, Cq, D = (np.asarray(a, dtype=np.int64) for a in sums)
+    NUM, VA, VC = N * D - A * B, N * A - A * A, N * Cq - B * B
+    ok = (VA != 0) & (VC != 0)
+    den = np.sqrt(np.where(ok, VA, 1).astype(np.float64) * np.where(ok, VC, 1).astype(np.float64))
+    return np.where(ok, NUM.astype(np.float64) / den, np.nan)
+
+
+def _score_group(w, cuts):
+    """the group of a rest score: #{k : c_k <= w}"""
+    return np.searchsorted(np.asarray(cuts, dtype=np.int64), w, side="right")
+
+
+def _score_sums(ob, bit, x):
+    """(sums (4 x m int64: A, B, Cq, D), the rest scores n x m) of the plane `bit` with the scores x, over the cells ob"""
+    W = x.astype(np.int64)[:, None] - bit.astype(np.int64)
+    Wo = np.where(ob, W, 0)
+    return np.stack([bit.sum(axis=0), Wo.sum(axis=0), (Wo * Wo).sum(axis=0), np.where(bit, Wo, 0).sum(axis=0)]).astype(np.int64), W
+
+
+def _score_by_group(grp, ob, K, *terms):
+    """per term the K x m sums over the cells ob of group k"""
+    out = [np.zeros((K, ob.shape[1]), dtype=np.int64) for _ in terms]
+    for k in range(K):
+        mask = ob & (grp == k)
+        for o, t in zip(out, terms):
+            o[k] = np.where(mask, t, 0).sum(axis=0)
+    return out
+
+
+def _score_moments(hist):
+    """(Vn = n_s S2 - S1^2, n_s) of a histogram of scores, as Python ints"""
+    h = [int(v) for v in hist]
+    ns, s1, s2 = sum(h), sum(s * v for s, v in enumerate(h)), sum(s * s * v for s, v in enumerate(h))
+    return ns * s2 - s1 * s1, ns
+
+
+def scores_observed(y, cuts) -> dict:
+    """The constants of the header from the data: x (int32, n), live (the respondents with an observed cell), hist (m + 1),
+    sums (4 x m: A, B, Cq, D), n_item, No, T (K x m), var = (Vn, n_s), r (NaN where undefined), with cuts, K, n, m."""
+    y = np.asarray(y, dtype=np.float64)
+    n, m = y.shape
+    cuts = check_score_cuts(cuts, m, n)
+    K = len(cuts) + 1
+    ob = ~np.isnan(y)
+    Y = ob & (y > 0)
+    x, live = Y.sum(axis=1), ob.any(axis=1)
+    hist = np.bincount(x[live], minlength=m + 1).astype(np.int64)
+    sums, W = _score_sums(ob, Y, x)
+    No, T = _score_by_group(_score_group(W, cuts), ob, K, 1, Y)
+    n_item = ob.sum(axis=0).astype(np.int64)
+    return dict(cuts=cuts, K=K, n=n, m=m, x=x.astype(np.int32), live=live, hist=hist, sums=sums, n_item=n_item, No=No, T=T,
+                var=_score_moments(hist), r=_score_r(n_item, sums), W=W)
+
+
+def scores_observed_from_arrays(cuts, hist_obs, sums_obs, tNo, tT, x_obs=None) -> dict:
+    """scores_observed's dict from the constants of a state block (gpirt_sampler_ppc_scores_get): what scores_draw_stats and
+    scores_from_tables read of it."""
+    tNo, tT = np.asarray(tNo, dtype=np.int64), np.asarray(tT, dtype=np.int64)
+    K, m = tNo.shape
+    hist = np.asarray(hist_obs, dtype=np.int64)
+    sums = np.asarray(sums_obs, dtype=np.int64).reshape(4, m)
+    n_item = tNo.sum(axis=0)
+    return dict(cuts=tuple(int(c) for c in cuts), K=K, n=None if x_obs is None else len(x_obs), m=m, x=x_obs, hist=hist, sums=sums,
+                n_item=n_item, No=tNo, T=tT, var=_score_moments(hist), r=_score_r(n_item, sums))
+
+
+def scores_tables(y, g, rep, obs) -> dict:
+    """One draw's integer tables: xr (int32, n), hist (m + 1), sums (4 x m), Nr, R (K x m) and the fixed-point Eo, Vo, Er, Vr
+    (int64, K x m), with "obs" = scores_observed's dict; g must be finite in the observed cells."""
+    y = np.asarray(y, dtype=np.float64)
+    m, K, cuts = obs["m"], obs["K"], obs["cuts"]
+    ob = ~np.isnan(y)
+    bit = ob & (np.asarray(rep) != 0)
+    xr = bit.sum(axis=1)
+    hist = np.bincount(xr[obs["live"]], minlength=m + 1).astype(np.int64)
+    sums, Wr = _score_sums(ob, bit, xr)
+    gz = np.where(ob, g, 0.0)
+    p, e = _plogis(gz)
+    q = np.where(gz >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+    ef, vf = np.rint(p * SCORES_FIX).astype(np.int64), np.rint(p * q * SCORES_FIX).astype(np.int64)
+    Nr, R, Er, Vr = _score_by_group(_score_group(Wr, cuts), ob, K, 1, bit, ef, vf)
+    Eo, Vo = _score_by_group(_score_group(obs["W"], cuts), ob, K, ef, vf)
+    return dict(obs=obs, xr=xr.astype(np.int32), hist=hist, sums=sums, Nr=Nr, R=R, Eo=Eo, Vo=Vo, Er=Er, Vr=Vr)
+
+
+def _score_x2(Cn, E, V):
+    """X2 = sum over k ascending with V > 0 of d d / v, d = (double)(C 2^44 - E) 2^-44, v = (double)V 2^-44"""
+    K, m = np.asarray(V).shape
+    x = np.zeros(m)
+    un = 1.0 / SCORES_FIX
+    for k in range(K):
+        pos = np.asarray(V[k]) > 0
+        d = ((np.asarray(Cn[k], dtype=np.int64) << 44) - np.asarray(E[k], dtype=np.int64)).astype(np.float64) * un
+        v = np.where(pos, np.asarray(V[k], dtype=np.int64).astype(np.float64) * un, 1.0)
+        x = x + np.where(pos, d * d / v, 0.0)
+    return x
+
+
+def scores_draw_stats(tables) -> dict:
+    """The header's statistics and decisions of one draw from its tables (scores_tables' dict, or the same arrays read from the
+    device): r (m; NaN where VA or VC is 0), chi (2 x m: X2(T), X2(R)), Vn, and the bool decisions hist_ge, hist_gt, cdf_ge,
+    cdf_gt (m + 1), var_ge, var_gt, r_def, r_ge, r_gt, chi_ge, chi_gt (m), cell_ge, cell_gt, cell_empty (K x m)."""
+    obs = tables["obs"]
+    r, r0 = _score_r(obs["n_item"], tables["sums"]), obs["r"]
+    with np.errstate(invalid="ignore"):
+        r_def = ~np.isnan(r) & ~np.isnan(r0)
+        out = dict(r=r, r_def=r_def, r_ge=r_def & (r >= r0), r_gt=r_def & (r > r0))
+    No, T = np.asarray(obs["No"], dtype=np.int64), np.asarray(obs["T"], dtype=np.int64)
+    Nr, R = np.asarray(tables["Nr"], dtype=np.int64), np.asarray(tables["R"], dtype=np.int64)
+    both = (Nr > 0) & (No > 0)
+    out.update(cell_ge=both & (R * No >= T * Nr), cell_gt=both & (R * No > T * Nr), cell_empty=~both)
+    x2T, x2R = _score_x2(T, tables["Eo"], tables["Vo"]), _score_x2(R, tables["Er"], tables["Vr"])
+    out.update(chi=np.stack([x2T, x2R]), chi_ge=x2R >= x2T, chi_gt=x2R > x2T)
+    H, Ho = np.asarray(tables["hist"], dtype=np.int64), np.asarray(obs["hist"], dtype=np.int64)
+    out.update(hist_ge=H >= Ho, hist_gt=H > Ho, cdf_ge=np.cumsum(H) >= np.cumsum(Ho), cdf_gt=np.cumsum(H) > np.cumsum(Ho))
+    Vn, _ = _score_moments(H)
+    out.update(Vn=Vn, var_ge=Vn >= obs["var"][0], var_gt=Vn > obs["var"][0])
+    return out
+
+
+def scores_worst(ppp_chi2_mid, top=DEFAULT_SCORES_TOP) -> dict:
+    """The `top` items with the smallest ppp_chi2_mid, ties to the lowest j, NaN never listed; padded with -1 / NaN."""
+    top = check_scores_top(top)
+    mid = np.asarray(ppp_chi2_mid, dtype=np.float64)
+    at = np.flatnonzero(~np.isnan(mid))
+    order = at[np.argsort(mid[at], kind="stable")][:top]
+    w = dict(items=np.full(top, -1, dtype=np.int64), ppp_chi2_mid=np.full(top, np.nan))
+    w["items"][:len(order)] = order
+    w["ppp_chi2_mid"][:len(order)] = mid[order]
+    return w
+
+
+def scores_from_tables(draws, top=DEFAULT_SCORES_TOP, skipped=0, obs=None) -> dict:
+    """The header's accumulators and finished fields from the COUNTED draws' tables (a list of scores_tables' dicts, in draw
+    order; obs: the constants, needed only when the list is empty).  Returns scores_result's dict and "last" (the last draw's
+    arrays under the getter's names)."""
+    S = len(draws)
+    obs = draws[0]["obs"] if draws else obs
+    m, K = obs["m"], obs["K"]
+    kinds = {name: (dt, kind) for name, dt, kind in _lib.SCORES_RAW}
+    acc = {name: np.zeros(_scores_shape(kind, 0, m, K), dtype=np.float64 if dt == "f8" else object)
+           for name, (dt, kind) in kinds.items() if (name, dt, kind) not in _lib.SCORES_CONST}
+    un = 1.0 / SCORES_FIX
+    last = None
+    for d in draws:
+        st = scores_draw_stats(d)
+        H = np.array([int(v) for v in d["hist"]], dtype=object)
+        acc["hist_sum"] += H; acc["hist_sumsq"] += H * H
+        for k in ("hist_ge", "hist_gt", "cdf_ge", "cdf_gt", "r_ge", "r_gt", "cell_ge", "cell_gt", "cell_empty", "chi_ge", "chi_gt"):
+            acc[k] += st[k].astype(np.int64)
+        acc["var_ge"] += int(st["var_ge"]); acc["var_gt"] += int(st["var_gt"]); acc["var_rep_sum"] += st["Vn"]
+        acc["r_undefined_count"] += (~st["r_def"]).astype(np.int64)
+        rz = np.where(st["r_def"], st["r"], 0.0)
+        acc["r_rep_sum"] = acc["r_rep_sum"] + rz
+        acc["r_rep_sumsq"] = acc["r_rep_sumsq"] + rz * rz
+        acc["sum_nr"] += np.asarray(d["Nr"], dtype=np.int64); acc["sum_r"] += np.asarray(d["R"], dtype=np.int64)
+        acc["sum_eo"] = acc["sum_eo"] + np.asarray(d["Eo"], dtype=np.int64).astype(np.float64) * un
+        acc["sum_er"] = acc["sum_er"] + np.asarray(d["Er"], dtype=np.int64).astype(np.float64) * un
+        acc["chi_obs_sum"] = acc["chi_obs_sum"] + st["chi"][0]
+        acc["chi_rep_sum"] = acc["chi_rep_sum"] + st["chi"][1]
+        last = dict(xr=d.get("xr"), hist=np.asarray(d["hist"], dtype=np.int64), sums=np.asarray(d["sums"], dtype=np.int64), r=st["r"],
+                    tNr=np.asarray(d["Nr"], dtype=np.uint32), tR=np.asarray(d["R"], dtype=np.uint32),
+                    tEo=np.asarray(d["Eo"], dtype=np.int64), tVo=np.asarray(d["Vo"], dtype=np.int64),
+                    tEr=np.asarray(d["Er"], dtype=np.int64), tVr=np.asarray(d["Vr"], dtype=np.int64), chi=st["chi"])
+    ints = {k: np.array([int(v) for v in np.ravel(a)], dtype=object).reshape(np.shape(a)) for k, a in acc.items() if a.dtype == object}
+    out = {k: (ints[k].astype(_SC_DTYPES[kinds[k][0]]) if k in ints else a) for k, a in acc.items()}
+    out.update(hist_obs=np.asarray(obs["hist"], dtype=np.int64), sums_obs=np.asarray(obs["sums"], dtype=np.int64),
+               var_obs=np.array(obs["var"], dtype=np.int64), r_obs=obs["r"], tNo=np.asarray(obs["No"], dtype=np.uint32),
+               tT=np.asarray(obs["T"], dtype=np.uint32))
+    nan = float("nan")
+    fS = float(S)
+    pp = lambda a: np.asarray(a, dtype=np.float64) / fS if S >= 1 else np.full(np.shape(a), nan)         # noqa: E731
+    mid = lambda a, b: (a.astype(np.float64) + b.astype(np.float64)) / (2.0 * fS) if S >= 1 else np.full(np.shape(a), nan)   # noqa: E731
+    out["score_hist_obs"] = out["hist_obs"].astype(np.float64)
+    out["score_hist_rep_mean"] = np.array([float(v) / fS if S >= 1 else nan for v in ints["hist_sum"]])
+    out["score_hist_rep_sd"] = np.array([np.sqrt(float(S * q - v * v) / (fS * float(S - 1))) if S >= 2 else nan
+                                         for v, q in zip(ints["hist_sum"], ints["hist_sumsq"])])
+    out["ppp_hist"], out["ppp_hist_mid"] = pp(out["hist_ge"]), mid(out["hist_ge"], out["hist_gt"])
+    out["ppp_cdf"], out["ppp_cdf_mid"] = pp(out["cdf_ge"]), mid(out["cdf_ge"], out["cdf_gt"])
+    Vn_obs, ns = obs["var"]
+    n2 = float(ns) * float(ns)
+    out["score_var_obs"] = float(Vn_obs) / n2 if ns >= 1 else nan
+    out["score_var_rep_mean"] = float(int(ints["var_rep_sum"][0])) / (fS * n2) if ns >= 1 and S >= 1 else nan
+    out["ppp_var"] = float(int(ints["var_ge"][0])) / fS if ns >= 1 and S >= 1 else nan
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Sr = S - out["r_undefined_count"].astype(np.int64)
+        fr = np.where(Sr >= 1, Sr, 1).astype(np.float64)
+        mean = out["r_rep_sum"] / fr
+        out["r_rep_mean"] = np.where(Sr >= 1, mean, nan)
+        v = (out["r_rep_sumsq"] - out["r_rep_sum"] * mean) / np.where(Sr >= 2, Sr - 1, 1).astype(np.float64)
+        out["r_rep_sd"] = np.where(Sr >= 2, np.where(v > 0.0, np.sqrt(np.where(v > 0.0, v, 0.0)), 0.0), nan)
+        out["ppp_r"] = np.where(Sr >= 1, out["r_ge"].astype(np.float64) / fr, nan)
+        out["ppp_r_mid"] = np.where(Sr >= 1, (out["r_ge"].astype(np.float64) + out["r_gt"].astype(np.float64)) / (2.0 * fr), nan)
+        out["r_undefined"] = out["r_undefined_count"].astype(np.float64)
+        out["ppp_chi2"], out["ppp_chi2_mid"] = pp(out["chi_ge"]), mid(out["chi_ge"], out["chi_gt"])
+        out["chi2_obs_mean"], out["chi2_rep_mean"] = pp(out["chi_obs_sum"]), pp(out["chi_rep_sum"])
+        No = out["tNo"].astype(np.float64)
+        out["obs_rate"] = np.where(No > 0, out["tT"].astype(np.float64) / np.where(No > 0, No, 1.0), nan)
+        sn = out["sum_nr"].astype(np.float64)
+        out["rep_rate"] = np.where(sn > 0, out["sum_r"].astype(np.float64) / np.where(sn > 0, sn, 1.0), nan)
+        out["exp_rate"] = np.where((No > 0) & (S >= 1), out["sum_eo"] / np.where(No > 0, fS * No, 1.0), nan) if S >= 1 else np.full((K, m), nan)
+        Sc = S - out["cell_empty"].astype(np.int64)
+        fc = np.where(Sc >= 1, Sc, 1).astype(np.float64)
+        out["ppp_cell"] = np.where(Sc >= 1, out["cell_ge"].astype(np.float64) / fc, nan)
+        out["ppp_cell_mid"] = np.where(Sc >= 1, (out["cell_ge"].astype(np.float64) + out["cell_gt"].astype(np.float64)) / (2.0 * fc), nan)
+    cuts = obs["cuts"]
+    out["cuts"] = np.array(cuts, dtype=np.int64)
+    out["group_lo"] = np.array((0,) + tuple(cuts), dtype=np.int64)
+    out["group_hi"] = np.array(tuple(c - 1 for c in cuts) + (m - 1,), dtype=np.int64)
+    out["worst"] = scores_worst(out["ppp_chi2_mid"], top)
+    out.update(n=obs["n"], m=m, K=K, score_draws=S, score_skipped=int(skipped), n_scored=int(ns), last=last)
+    return out
+
+
+def scores_from_rep(y, g_draws, rep_draws, cuts=None, top=DEFAULT_SCORES_TOP) -> dict:
+    """The header's score-based checks from stored draws: y (n x m; NaN = missing), g_draws (S, n, m) the draws of g = f + mu,
+    rep_draws (S, n, m) with rep != 0 where yrep = +1; cuts None: default_score_cuts(y).  A draw with a non-finite g in an
+    observed cell is skipped.  Returns scores_from_tables' dict."""
+    y = np.asarray(y, dtype=np.float64)
+    obs = scores_observed(y, default_score_cuts(y) if cuts is None else cuts)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    S = g_draws.shape[0]
+    assert g_draws.shape == (S,) + y.shape and np.asarray(rep_draws).shape == (S,) + y.shape
+    ob = ~np.isnan(y)
+    draws, skipped = [], 0
+    for s in range(S):
+        if not np.isfinite(g_draws[s][ob]).all():
+            skipped += 1
+            continue
+        draws.append(scores_tables(y, g_draws[s], rep_draws[s], obs))
+    return scores_from_tables(draws, top, skipped, obs)
+
+
+def scores_from_draws(y, g_draws, seed, iters, cuts=None, top=DEFAULT_SCORES_TOP, item0=0):
+    """scores_from_rep over the replicates of stored draws, built as dif_from_draws builds them: rep = [u < plogis(g)] with
+    replicate_uniforms' u at the completed-iteration counters `iters`.  Returns (result, min |u - p| over the observed cells
+    of the draws with finite g): a cell that close to its uniform may replicate either way under another evaluation of
+    plogis."""
+    y = np.asarray(y, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    n, m = y.shape
+    ob = ~np.isnan(y)
+    reps, gap = [], np.inf
+    for s, it in enumerate(iters):
+        with np.errstate(invalid="ignore"):
+            fin = ob & np.isfinite(g_draws[s])
+        p, _ = _plogis(np.where(fin, g_draws[s], 0.0))
+        u = replicate_uniforms(seed, int(it), n, m, item0)
+        if fin.any():
+            gap = min(gap, float(np.abs(u - p)[fin].min()))
+        reps.append(ob & (u < p))
+    rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
+    return scores_from_rep(y, g_draws, rep, cuts, top), gap

@@ -1049,6 +1049,58 @@ class Sampler:
         return P.dif_combine(self.handle, [self], signs=[sign],
                              top=getattr(self, "_dif_top", P.DEFAULT_DIF_TOP) if top is None else top)
 
+    # -- score-based checks inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_scores_*, gpirt_amd.ppc)
+    def ppc_scores_enable(self, cuts=None, groups=9, top=20, on=True):
+        """Allocate and zero the score-based accumulators on a sampler whose ppc_enable is on, and count the data's constants on
+        the device: from then on every ppc_accumulate also adds the replicate's score distribution, every item's correlation
+        with the rest score and the item fit within groups of the rest score.  Scores are raw counts over each respondent's own
+        observed items.  cuts: ascending integers in 1 .. m - 1 (K - 1 of them, 2 <= K <= 16 groups; the group of a rest score w
+        is #{k : c_k <= w}); None: up to `groups` groups from the quantiles of the data's total scores
+        (gpirt_amd.ppc.default_score_cuts).  top (1..64): how many items ppc_scores() lists as worst.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_scores_enable(self._s, 0, None, 0))
+            self._scores_K = None
+            return
+        from . import ppc as P
+        self._scores_top = P.check_scores_top(top)
+        cuts = P.check_score_cuts(P.default_score_cuts(self.get("y"), groups) if cuts is None else cuts, self.m, self.n)
+        check(self.lib.gpirt_sampler_ppc_scores_enable(self._s, len(cuts) + 1, (C.c_int * len(cuts))(*cuts), 1))
+        self._scores_K = len(cuts) + 1
+
+    def ppc_scores_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.SCORES_HIST_FIELDS: float64 m + 1; SCORES_VAR_FIELDS: a 0-d float64;
+        SCORES_ITEM_FIELDS: m; SCORES_CELL_FIELDS: K x m), a raw array or constant of _lib.SCORES_RAW, group_lo, group_hi (int64,
+        K), cuts (int64, K - 1), counts (int64: score_draws, score_skipped), x_obs (int32, n) and, of the last counted draw,
+        the arrays of _lib.SCORES_LAST.  An unknown name is a ValueError."""
+        from . import ppc as P
+        n, m = self.n, self.m
+        K = getattr(self, "_scores_K", None) or 2                    # (not enabled: the library refuses the call)
+        shape, dtype = P.scores_field(name, n, m, K)
+        out = np.empty(shape, dtype=dtype)
+        check(self.lib.gpirt_sampler_ppc_scores_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def ppc_scores_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the score-based accumulators: what
+        gpirt_amd.ppc.scores_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_scores_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_scores(self, top=None) -> dict:
+        """Every finished output of this sampler's score-based accumulators (gpirt_amd.ppc.scores_result's shape):
+        gpirt_ppc_scores_combine over its own state; top defaults to ppc_scores_enable's."""
+        from . import ppc as P
+        return P.scores_combine(self.handle, [self], top=getattr(self, "_scores_top", P.DEFAULT_SCORES_TOP) if top is None else top)
+
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         """Allocate and zero the rank accumulators for `pivots` ("median" and / or positions in 1..n, at most 16; the

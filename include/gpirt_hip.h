@@ -1257,6 +1257,115 @@ int gpirt_sampler_ppc_dif_get(gpirt_sampler_t s, const char* name, void* h_out, 
 int gpirt_sampler_ppc_dif_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_dif_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_ppc_dif* out);
 
+/* ------------------------------------------------- score-based PPC: score distribution, item-rest fit by score group --------- */
+/* The three discrepancies Sinharay, Johnson and Stern (2006) name first for a one-dimensional model, on the MANIFEST score
+ * (library version 120): the observed-score distribution, every item's correlation with the rest of the test, and the item fit
+ * within groups of the rest score (the grouping of Orlando and Thissen's S-X2; the theta-binned fit above groups on each draw's
+ * latent theta instead, which is what makes it conservative).  A fourth add-on to the PPC: enabled on a sampler whose ppc_enable
+ * is on, accumulated inside the same ppc_accumulate call by passes of its own that form the PPC's replicate again, bit for bit
+ * (the same expression for p, the same item_uniform(seed, iter, GPIRT_ST_PPC, item0 + j, i)); nothing is drawn.  Stage API only:
+ * gpirt_run has no field for it yet.
+ * n respondents, m items, 2 <= m <= GPIRT_SCORES_MAX_M = 4096, n <= GPIRT_SCORES_MAX_N = 65534, 2 <= K <= GPIRT_SCORES_MAX_K = 16
+ * score groups; item shards are refused.  O = the observed cells, Y = [y = +1] and rep = [yrep = +1] on O.
+ * Scores are raw counts over each respondent's own observed items: X_i = sum_j Y_ij (constant, counted on the device at enable),
+ * Xr_i = sum_j rep_ij per draw; the rest scores of a cell W_ij = X_i - Y_ij and Wr_ij = Xr_i - rep_ij.  Respondents without an
+ * observed cell are left out of everything; n_s is the number of the others.
+ * Cuts: ascending integers c_1 < ... < c_{K-1} in 1 .. m - 1; the group of a rest score w is #{k : c_k <= w}, so group k holds
+ * the rest scores group_lo[k] = c_k (0 for k = 0) to group_hi[k] = c_{k+1} - 1 (m - 1 for k = K - 1).
+ * A draw with a non-finite g = f + mu in an observed cell is skipped whole -- score_skipped += 1 and nothing else changes, which
+ * is decided before any accumulator is touched; a NaN in a missing cell is ignored.  Every other draw adds 1 to score_draws.
+ * 1. Score distribution.  H[s] = #{i : score_i = s}, s = 0 .. m, over the n_s respondents, for the data (hist_obs) and per draw
+ *    for the replicate; C[s] = H[0] + ... + H[s].  Per counted draw and s: hist_sum += H_rep, hist_sumsq += H_rep^2 (uint64),
+ *    hist_ge / hist_gt += [H_rep >= / > H_obs], cdf_ge / cdf_gt += [C_rep >= / > C_obs] (uint32).  The spread of the scores
+ *    Vn = n_s S2 - S1^2 with S1 = sum_i X_i, S2 = sum_i X_i^2: an exact int64 (S2 <= 65534 x 4096^2 < 2^41, both terms < 2^57);
+ *    var_obs = (Vn_obs, n_s); var_ge / var_gt += [Vn_rep >= / > Vn_obs], var_rep_sum += Vn_rep (uint64).
+ * 2. Item-rest correlation.  Per item j over i in O_j: N = #O_j, A = sum Y, B = sum W, Cq = sum W^2, D = sum Y W -- integers,
+ *    B <= 65534 x 4096 < 2^28, Cq < 2^40 -- and NUM = N D - A B, VA = N A - A^2, VC = N Cq - B^2 exactly in int64 (every product
+ *    is below 2^57).  r = (double)NUM / sqrt((double)VA * (double)VC): each conversion rounded once, sqrt and the division
+ *    IEEE.  r_obs at enable (NaN when VA = 0 or VC = 0); r_rep per draw from rep and Wr.  When VA = 0 or VC = 0 in the replicate,
+ *    or r_obs is NaN, the draw counts in r_undefined_count[j] and enters nothing else of item j's correlation; otherwise
+ *    r_ge / r_gt += [r_rep >= / > r_obs], r_rep_sum += r_rep, r_rep_sumsq += r_rep r_rep (doubles, in draw order).
+ * 3. Item fit by rest-score group.  Per (group k, item j): the data's cells are grouped by W_ij -- constant, so tNo[k, j] = #cells
+ *    and tT[k, j] = #{Y = 1} are counted at enable --, the replicate's cells by Wr_ij, which gives Nr and R per draw.  Given theta
+ *    item j's answer is independent of the REST score, so E = sum p is the expectation within a group (it would not be under a
+ *    grouping by the total score).  Both groupings get E = sum rint(p 2^44) and V = sum rint(p q 2^44) over their cells (Eo, Vo
+ *    and Er, Vr; int64, below 2^60): every term rounded once, the sums exact and independent of the order of summation.
+ *    Per counted draw: sum_nr += Nr, sum_r += R (uint64), sum_eo += (double)Eo 2^-44, sum_er += (double)Er 2^-44 (in draw order);
+ *    when Nr > 0 and No > 0 cell_ge / cell_gt += [R No >= / > T Nr] (integer cross-multiplication), otherwise cell_empty += 1.
+ *    Item statistic for C = T with (Eo, Vo) and for C = R with (Er, Vr): d = (double)(C 2^44 - E) 2^-44, v = (double)V 2^-44,
+ *    X2 = sum over k ascending with V > 0 of d d / v (no contraction).  chi_ge / chi_gt += [X2(R) >= / > X2(T)], chi_obs_sum +=
+ *    X2(T), chi_rep_sum += X2(R).
+ * Finished on the host with S = score_draws (NaN where a denominator is 0; a mean over zero draws is NaN):
+ *   m + 1 values each (GPIRT_SCORES_HIST_*): score_hist_obs, score_hist_rep_mean = hist_sum / S, score_hist_rep_sd =
+ *   sqrt((S hist_sumsq - hist_sum^2) / (S (S - 1))) (the numerator exact in 128 bits), ppp_hist = hist_ge / S, ppp_hist_mid =
+ *   (hist_ge + hist_gt) / 2S, ppp_cdf, ppp_cdf_mid;
+ *   3 values (var): score_var_obs = Vn_obs / n_s^2, score_var_rep_mean = var_rep_sum / (S n_s^2), ppp_var = var_ge / S;
+ *   m values each (GPIRT_SCORES_ITEM_*), with S' = S - r_undefined_count: r_rep_mean = r_rep_sum / S', r_rep_sd =
+ *   sqrt(max((r_rep_sumsq - r_rep_sum r_rep_mean) / (S' - 1), 0)) for S' >= 2, ppp_r = r_ge / S', ppp_r_mid, r_undefined,
+ *   ppp_chi2 = chi_ge / S, ppp_chi2_mid, chi2_obs_mean, chi2_rep_mean;
+ *   K x m values each, cell (k, j) at [k m + j] (GPIRT_SCORES_CELL_*): obs_rate = tT / tNo, rep_rate = sum_r / sum_nr, exp_rate =
+ *   sum_eo / (S tNo), and with S" = S - cell_empty: ppp_cell = cell_ge / S", ppp_cell_mid;
+ *   group_lo, group_hi (int64, K); worst: the `top` (1..GPIRT_SCORES_MAX_TOP, the Python default is 20) items with the smallest
+ *   ppp_chi2_mid, ties to the lowest j, NaN never listed, padded with -1 / NaN.
+ * Determinism: no floating-point atomics anywhere; the only atomics add integers.  Two runs give a byte-identical state block.
+ * Pooling C chains (gpirt_ppc_scores_combine) adds the integers and adds the doubles in chain order.  It takes no signs: theta ->
+ * -theta leaves f + mu of every cell as it is.  Blocks with another n, m, K, cuts or response matrix (the constants differ) than
+ * state 0 are refused.  With the block on, the chain, the IRFs and the PPC, pairs, bins and dif state blocks are bit for bit what
+ * they are without.
+ * The raw arrays (GPIRT_SCORES_NRAW, in the state block's order).  Constants: int64 hist_obs (m + 1), int64 sums_obs (4 x m: A, B,
+ * Cq, D), int64 var_obs (2), double r_obs (m), uint32 tNo, tT (K m).  Accumulators: uint64 hist_sum, hist_sumsq, uint32 hist_ge,
+ * hist_gt, cdf_ge, cdf_gt (m + 1); uint32 var_ge, var_gt, uint64 var_rep_sum (1); uint32 r_ge, r_gt, r_undefined_count, double
+ * r_rep_sum, r_rep_sumsq (m); uint32 cell_ge, cell_gt, cell_empty, uint64 sum_nr, sum_r, double sum_eo, sum_er (K m); uint32
+ * chi_ge, chi_gt, double chi_obs_sum, chi_rep_sum (m). */
+#define GPIRT_SCORES_MAX_M       4096
+#define GPIRT_SCORES_MAX_N       65534
+#define GPIRT_SCORES_MAX_K       16
+#define GPIRT_SCORES_MAX_TOP     64
+#define GPIRT_SCORES_HIST_NFIELDS  7    /* score_hist_obs, score_hist_rep_mean, score_hist_rep_sd, ppp_hist, ppp_hist_mid, ppp_cdf,
+                                           ppp_cdf_mid */
+#define GPIRT_SCORES_ITEM_NFIELDS  9    /* r_rep_mean, r_rep_sd, ppp_r, ppp_r_mid, r_undefined, ppp_chi2, ppp_chi2_mid,
+                                           chi2_obs_mean, chi2_rep_mean */
+#define GPIRT_SCORES_CELL_NFIELDS  5    /* obs_rate, rep_rate, exp_rate, ppp_cell, ppp_cell_mid */
+#define GPIRT_SCORES_NRAW          31
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_ppc_scores {
+    int        top;                              /* in: 1..GPIRT_SCORES_MAX_TOP */
+    int        K;                                /* out: the states' number of groups */
+    int        cuts[GPIRT_SCORES_MAX_K];         /* out: c_1 .. c_{K-1}, the rest 0 */
+    double*    hist[GPIRT_SCORES_HIST_NFIELDS];  /* m + 1 each */
+    double*    var;                              /* 3: score_var_obs, score_var_rep_mean, ppp_var */
+    double*    item[GPIRT_SCORES_ITEM_NFIELDS];  /* m each */
+    double*    cell[GPIRT_SCORES_CELL_NFIELDS];  /* K x m each */
+    void*      raw[GPIRT_SCORES_NRAW];           /* the raw arrays, in the order and with the types above */
+    int64_t*   group_lo;                         /* K */
+    int64_t*   group_hi;                         /* K */
+    int64_t*   worst_items;                      /* top */
+    double*    worst_ppp_chi2_mid;               /* top */
+    int64_t    n, m;                             /* out */
+    int64_t    score_draws, score_skipped;       /* out */
+    int64_t    n_scored;                         /* out: n_s, the respondents with an observed cell */
+    int64_t    reserved[4];                      /* must be 0 */
+} gpirt_ppc_scores;
+/* Stage API.  ppc_scores_enable(K, cuts, on != 0) allocates and zeroes the state on a sampler with ppc_enable on and counts the
+ * constants on the device (GPIRT_E_ARG, with a message, without ppc_enable, on an item shard, for m outside 2..4096, n > 65534, K
+ * outside 2..16 and for cuts that are not K - 1 ascending integers in 1 .. m - 1; on = 0 frees it, cuts may then be NULL;
+ * ppc_enable called again frees it too).  From then on every ppc_accumulate also adds the draw to the block.  ppc_scores_get
+ * copies one array by name to the host, `bytes` its exact size: every finished array by the lower-case name above (double), the
+ * raw arrays by theirs, "group_lo", "group_hi" (int64, K), "counts" (int64: score_draws, score_skipped), "cuts" (int64, K - 1),
+ * "x_obs" (int32, n) and, of the last COUNTED draw, "xr" (int32, n), "hist" (int64, m + 1), "sums" (int64, 4 x m: A, B, Cq, D
+ * of the replicate), "r" (double, m; NaN where VA = 0 or VC = 0), "tNr", "tR" (uint32, K x m), "tEo", "tVo", "tEr", "tVr" (the
+ * fixed-point int64 sums, K x m) and "chi" (double, 2 x m: X2(T), X2(R)).
+ * ppc_scores_state returns the ONE device block of its own: a header of 8 int64 -- the tag 0x31524353 ("SCR1"), the layout
+ * version (1), n, m, K, score_draws, score_skipped, 0 --, 16 int64 with the cuts c_1 .. c_{K-1} (the rest 0), then the raw arrays in
+ * the order above; every array starts on a 16-byte boundary.
+ * gpirt_ppc_scores_check is ppc_scores_enable's argument check alone (0, or GPIRT_E_ARG with the message): nothing is allocated and
+ * no device is touched. */
+int gpirt_ppc_scores_check(int64_t n, int64_t m, int K, const int* cuts);
+int gpirt_sampler_ppc_scores_enable(gpirt_sampler_t s, int K, const int* cuts, int on);
+int gpirt_sampler_ppc_scores_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_scores_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_scores_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_scores* out);
+
 /* ------------------------------------------------------ Two-form score equating: joint table, concordance ------------- */
 /* The sum-score section answers every question about ONE form's score.  This one is about TWO forms at once: how scores on
  * form X and form Y relate (IRT observed-score equating), what somebody who scored s on X scores on Y (the concordance table),
