@@ -216,6 +216,35 @@ class PpcScores(C.Structure):
                 ("n_scored", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# person fit (include/gpirt_hip.h GPIRT_PERSON_*): the finished fields per respondent (n) and per (group, respondent), in order;
+# the raw arrays of the state block with their dtypes and shapes ("n": n, "c": K x n), the constants first
+PERSON_RESP_FIELDS = ("guttman_obs", "guttman_norm_obs", "guttman_rep_mean", "guttman_norm_rep_mean", "ppp_guttman", "ppp_guttman_mid",
+                      "guttman_undefined", "lz_obs_mean", "lz_rep_mean", "lz_rep_sd", "lz_undefined", "ppp_chi2", "ppp_chi2_mid",
+                      "chi2_obs_mean", "chi2_rep_mean")
+PERSON_CELL_FIELDS = ("obs_rate", "rep_rate", "exp_rate", "ppp_cell", "ppp_cell_mid")
+PERSON_CONST = (("x_obs", "i8", "n"), ("g_obs", "i8", "n"), ("q_obs", "i8", "n"), ("tN", "u4", "c"), ("tT", "u4", "c"))
+PERSON_RAW = PERSON_CONST + (
+    ("g_ge", "u4", "n"), ("g_gt", "u4", "n"), ("g_undefined_count", "u4", "n"), ("g_rep_sum", "u8", "n"), ("gn_rep_sum", "f8", "n"),
+    ("lz_undefined_count", "u4", "n"), ("lz_obs_sum", "f8", "n"), ("lz_rep_sum", "f8", "n"), ("lz_rep_sumsq", "f8", "n"),
+    ("sum_r", "u8", "c"), ("sum_e", "f8", "c"), ("cell_ge", "u4", "c"), ("cell_gt", "u4", "c"),
+    ("chi_ge", "u4", "n"), ("chi_gt", "u4", "n"), ("chi_obs_sum", "f8", "n"), ("chi_rep_sum", "f8", "n"))
+# the last counted draw's arrays of gpirt_sampler_ppc_person_get ("3": 3 x n, "2": 2 x n)
+PERSON_LAST = (("xr", "i8", "n"), ("gr", "i8", "n"), ("qr", "i8", "n"), ("tR", "u4", "c"), ("tE", "i8", "c"), ("tV", "i8", "c"),
+               ("lz", "f8", "3"), ("chi", "f8", "2"))
+PERSON_MAX_M, PERSON_MAX_N, PERSON_MAX_K, PERSON_MAX_TOP, PERSON_TAG = 4096, 65534, 16, 64, 0x31535250
+
+
+class PpcPerson(C.Structure):
+    """gpirt_ppc_person (include/gpirt_hip.h): top, the cuts, host pointers per output (NULL: not wanted), counters."""
+    _fields_ = [("top", C.c_int), ("K", C.c_int), ("cuts", C.c_int * PERSON_MAX_K),
+                ("resp", C.POINTER(C.c_double) * len(PERSON_RESP_FIELDS)), ("cell", C.POINTER(C.c_double) * len(PERSON_CELL_FIELDS)),
+                ("raw", C.c_void_p * len(PERSON_RAW)), ("group_lo", C.POINTER(C.c_int64)), ("group_hi", C.POINTER(C.c_int64)),
+                ("group_items", C.POINTER(C.c_int32)),
+                ("worst_respondents", C.POINTER(C.c_int64)), ("worst_ppp_guttman_mid", C.POINTER(C.c_double)),
+                ("n", C.c_int64), ("m", C.c_int64), ("person_draws", C.c_int64), ("person_skipped", C.c_int64),
+                ("n_scored", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -495,6 +524,11 @@ SIGNATURES = {
     "gpirt_sampler_ppc_scores_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_scores_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_scores_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcScores)]),
+    "gpirt_ppc_person_check": (_i32, [_i64, _i64, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "gpirt_sampler_ppc_person_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int), _i32]),
+    "gpirt_sampler_ppc_person_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_person_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_person_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcPerson)]),
     "gpirt_sampler_equate_enable": (_i32, [_vp, _vp, _vp, _i32]),
     "gpirt_sampler_equate_accumulate": (_i32, [_vp]),
     "gpirt_sampler_equate_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),

@@ -522,6 +522,60 @@ int64_t pps_state_words(const PpsState* p);
 int pps_get(hipStream_t stream, PpsState* p, const char* name, void* h_out, int64_t bytes);
 int pps_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_scores* out);
 
+// ppc_person.hip: the person fit (gpirt_sampler_ppc_person_*), an add-on to a PPC state.  Its accumulators are ONE device block of
+// 8-byte words of their own: a header of PRS_HEADER_WORDS int64 (PRS_TAG, layout version, n, m, K, person_draws, person_skipped,
+// 0 -- the two counters are kept by prs_finish_kernel), PRS_CUT_WORDS int64 with the cuts, the order as m int32, then the arrays
+// of PrsLayout (the constants first), (k, i) at [k n + i], every array padded to 16 bytes.  Beside it: the order once more (the
+// kernels' copy), the strips' partials per (strip, respondent) -- the packed counts ones | observed << 8 | G_s << 16, E and V in
+// units of 2^-44 and the three lz sums --, the control word ctl[0] = a non-finite g in an observed cell, and the last counted
+// draw's tables and statistics.
+constexpr int PRS_LAYOUT_VERSION = 1;
+constexpr int PRS_HEADER_WORDS = 8;
+constexpr int PRS_CUT_WORDS = 16;
+constexpr int64_t PRS_TAG = 0x31535250;             // "PRS1"
+constexpr int PRS_STRIP = 32;                       // positions per strip at the most
+constexpr int PRS_MAX_STRIPS = GPIRT_PERSON_MAX_M / PRS_STRIP + GPIRT_PERSON_MAX_K;
+enum { PRS_X_OBS, PRS_G_OBS, PRS_Q_OBS, PRS_TN, PRS_TT,                                                    // the constants
+       PRS_G_GE, PRS_G_GT, PRS_G_UNDEF, PRS_G_REP_SUM, PRS_GN_REP_SUM,                                        // n
+       PRS_LZ_UNDEF, PRS_LZ_OBS_SUM, PRS_LZ_REP_SUM, PRS_LZ_REP_SUMSQ,                                         // n
+       PRS_SUM_R, PRS_SUM_E, PRS_CELL_GE, PRS_CELL_GT,                                                       // K x n
+       PRS_CHI_GE, PRS_CHI_GT, PRS_CHI_OBS, PRS_CHI_REP,                                                      // n
+       PRS_NARRAYS };
+static_assert(PRS_NARRAYS == GPIRT_PERSON_NRAW, "gpirt_ppc_person::raw");
+struct PrsLayout { int64_t order; int64_t off[PRS_NARRAYS]; int64_t words; };      // offsets in 8-byte words from the block's start
+PrsLayout prs_layout(int64_t n, int64_t m, int64_t K);
+// the strips of the header: strip s holds the positions lo[s] .. lo[s] + len[s] - 1 of ONE group; group k's strips are first[k] ..
+// first[k + 1] - 1
+struct PrsStrips { int ns; int first[GPIRT_PERSON_MAX_K + 1]; uint16_t lo[PRS_MAX_STRIPS]; uint8_t len[PRS_MAX_STRIPS]; };
+struct PrsState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0;
+    int K = 0;
+    int cuts[GPIRT_PERSON_MAX_K] = {};
+    PrsStrips strips{};
+    uint64_t* block = nullptr;
+    int32_t* order = nullptr;                                         // [m]
+    uint32_t* part_c = nullptr;                                       // [strips][n]
+    int64_t* part_ev = nullptr;                                       // [strips][2][n]
+    double* part_lz = nullptr;                                        // [strips][3][n]
+    int* ctl = nullptr;
+    int64_t* xgq_last = nullptr;                                      // [3][n]: X, G, Q of the replicate
+    uint32_t* tr_last = nullptr;                                      // [K][n]
+    int64_t* tev_last = nullptr;                                      // [2][K][n]
+    double *lz_last = nullptr, *chi_last = nullptr;                   // [3][n], [2][n]
+    std::vector<void*> allocs;
+};
+int prs_check(int64_t n, int64_t m, int K, const int32_t* order, const int* cuts);      // GPIRT_E_ARG with the message
+int prs_alloc(hipStream_t stream, PrsState* p, int64_t n, int64_t m, int64_t item0, const double* y, int K, const int32_t* order,
+              const int* cuts);
+void prs_free(PrsState* p);
+// one draw: the strips' partials from f, mu, y and the PPC's uniforms, then one thread per respondent finishes and decides
+int launch_prs_accumulate(hipStream_t stream, PrsState* p, const double* f, const double* mu, const double* y, uint64_t seed,
+                          uint32_t iter);
+int64_t prs_state_words(const PrsState* p);
+int prs_get(hipStream_t stream, PrsState* p, const char* name, void* h_out, int64_t bytes);
+int prs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_person* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -534,6 +588,7 @@ struct PpcState {
     BinState bins;                                    // the theta-binned item fit (ppc_bins.hip; on == false: off)
     DifState dif;                                     // the group-wise item fit (ppc_dif.hip; on == false: off)
     PpsState scores;                                  // the score-based checks (ppc_scores.hip; on == false: off)
+    PrsState person;                                  // the person fit (ppc_person.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written

@@ -1764,6 +1764,57 @@ int gpirt_ppc_scores_combine(gpirt_handle_t h, int chains, const void* const* d_
     return pps_combine(h, chains, d_states, out);
 }
 
+// ---- person fit (ppc_person.hip): an add-on to the PPC state -----------------------------------------------------------------
+static int person_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.person.on) return 0;
+    set_error("the person fit is not enabled (gpirt_sampler_ppc_person_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_ppc_person_check(int64_t n, int64_t m, int K, const int32_t* order, const int* cuts)
+{
+    return prs_check(n, m, K, order, cuts);
+}
+
+int gpirt_sampler_ppc_person_enable(gpirt_sampler_t s, int K, const int32_t* order, const int* cuts, int on)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    prs_free(&s->ppc.person);
+    if (!on) return 0;
+    GP_TRY(ppc_needs_on(s));
+    if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
+        set_error("the person fit is not offered for item shards (a respondent's pattern runs over all items)");
+        return GPIRT_E_ARG;
+    }
+    const int rc = prs_alloc(s->h->stream, &s->ppc.person, s->n, s->m, s->opt.item0, s->y, K, order, cuts);
+    if (rc) prs_free(&s->ppc.person);
+    return rc;
+}
+
+int gpirt_sampler_ppc_person_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(person_needs_on(s));
+    return prs_get(s->h->stream, &s->ppc.person, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_person_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(person_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.person.block;
+    *bytes = prs_state_words(&s->ppc.person) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_person_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_person* out)
+{
+    return prs_combine(h, chains, d_states, out);
+}
+
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
 static int rank_needs_on(gpirt_sampler_t s)
 {

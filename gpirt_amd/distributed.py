@@ -262,6 +262,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the score-based checks are not offered for item shards "
                          "(a respondent's score runs over all items, and each rank holds its own columns)")
 
+    def ppc_person_enable(self, order=None, cuts=None, groups=5, top=20, on=True):
+        raise ValueError("ShardedSampler: the person fit is not offered for item shards "
+                         "(a respondent's pattern runs over all items, and each rank holds its own columns)")
+
     # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         self.engine.rank_enable(on, pivots, pairwise)

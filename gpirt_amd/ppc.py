@@ -17,7 +17,8 @@ reflection signs, `bins_from_rep` is the NumPy statement of the header over stor
 E, V and X2 in np.longdouble, the chi-square decisions as (lo, hi) brackets from `bins_bounds`) and `bins_from_draws` builds
 the replicates from stored g draws.
 The group-wise item fit ("group-wise item fit" in the header; csrc/ppc_dif.hip) is the third add-on and the score-based checks
-("score-based PPC" in the header; csrc/ppc_scores.hip) the fourth: see their sections at the end of this module.
+("score-based PPC" in the header; csrc/ppc_scores.hip) the fourth, the person fit ("person fit in the PPC"; csrc/ppc_person.hip)
+the fifth: see their sections at the end of this module.
 ShardedSampler is not covered: the respondents' statistics would need one all-reduce per draw.  The keying of the
 uniforms by the global item index keeps that possible.
 """
@@ -1473,3 +1474,390 @@ def scores_from_draws(y, g_draws, seed, iters, cuts=None, top=DEFAULT_SCORES_TOP
         reps.append(ob & (u < p))
     rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
     return scores_from_rep(y, g_draws, rep, cuts, top), gap
+
+
+# ------------------------------------------------------------------------------------------------------- person fit ---
+# ("person fit in the PPC" in the header; csrc/ppc_person.hip) the fifth add-on, the score-based checks transposed: every
+# respondent's Guttman errors, lz and person response function within groups of the items' easiness.  `default_item_order` /
+# `default_item_cuts` / `check_person_args`, `person_struct` / `person_result` wrap gpirt_ppc_person, `person_combine` pools chains'
+# state blocks, `person_observed` / `person_tables` / `person_draw_stats` / `person_from_tables` are the NumPy statement of the
+# header -- integer tables (G by the O(m^2) pair definition) and the lz sums in long double, then fp64 operations in the header's
+# order, so the same tables give the same bits --, `person_from_rep` runs it over stored g and replicates, `person_from_draws`
+# builds the replicates with this module's Philox.
+DEFAULT_PERSON_TOP = 20
+DEFAULT_PERSON_GROUPS = 5
+
+
+def check_person_top(top) -> int:
+    t = int(top)
+    if t != top or not 1 <= t <= _lib.PERSON_MAX_TOP:
+        raise ValueError(f"person: top must be an integer in 1..{_lib.PERSON_MAX_TOP}")
+    return t
+
+
+def default_item_order(y) -> np.ndarray:
+    """The items by the data's yes rate T_j / N_j, descending (the easiest first), ties to the lowest j, the items without an
+    observed cell last: a permutation of 0 .. m - 1 (int32)."""
+    y = np.asarray(y, dtype=np.float64)
+    ob = ~np.isnan(y)
+    N, T = ob.sum(axis=0), (ob & (y > 0)).sum(axis=0)
+    rate = np.where(N > 0, T / np.maximum(N, 1), -np.inf)
+    return np.argsort(-rate, kind="stable").astype(np.int32)
+
+
+def default_item_cuts(m: int, groups: int = DEFAULT_PERSON_GROUPS) -> tuple:
+    """`groups` groups of near-equal position counts: the cuts k m // groups, k = 1 .. groups - 1, those outside 1 .. m - 1 and
+    duplicates dropped (fewer groups where m < groups)."""
+    g = int(groups)
+    if g != groups or not 2 <= g <= _lib.PERSON_MAX_K:
+        raise ValueError(f"person: groups must be an integer in 2..{_lib.PERSON_MAX_K}")
+    return tuple(sorted({(k * int(m)) // g for k in range(1, g)} & set(range(1, int(m)))))
+
+
+def check_person_args(order, cuts, m: int, n: int = 1):
+    """(order as an int32 array, the cuts as a tuple of ints): order a permutation of 0 .. m - 1, the cuts ascending c_1 < ... <
+    c_{K-1} in 1 .. m - 1, 2 <= K <= 16 groups; 2 <= m <= 4096 items and n <= 65534 respondents.  Anything else is a ValueError
+    that says which."""
+    if not 2 <= int(m) <= _lib.PERSON_MAX_M:
+        raise ValueError(f"person: m = {m} is outside 2..{_lib.PERSON_MAX_M} items")
+    if n > _lib.PERSON_MAX_N:
+        raise ValueError(f"person: n = {n} is beyond {_lib.PERSON_MAX_N} respondents")
+    try:
+        o = np.asarray(order)
+        oi = o.astype(np.int64)
+        whole_o = o.ndim == 1 and bool(np.all(oi == o))
+    except (TypeError, ValueError):
+        raise ValueError("person: the order must be a sequence of integers") from None
+    if not whole_o or len(oi) != m:
+        raise ValueError(f"person: the order must hold {m} integers, a permutation of 0..{m - 1}")
+    seen = np.zeros(m, dtype=bool)
+    for t, j in enumerate(oi):
+        if not 0 <= j < m or seen[j]:
+            raise ValueError(f"person: the order is not a permutation of 0..{m - 1} (entry {t} is {int(j)})")
+        seen[j] = True
+    try:
+        c = tuple(int(x) for x in cuts)
+        whole = all(float(a) == float(b) for a, b in zip(c, cuts))
+    except (TypeError, ValueError):
+        raise ValueError("person: the cuts must be a sequence of integers") from None
+    if not whole:
+        raise ValueError("person: the cuts must be integers")
+    if not 2 <= len(c) + 1 <= _lib.PERSON_MAX_K:
+        raise ValueError(f"person: {len(c)} cuts make {len(c) + 1} item groups, 2..{_lib.PERSON_MAX_K} groups are taken")
+    if any(not 1 <= x <= m - 1 for x in c) or any(b <= a for a, b in zip(c, c[1:])):
+        raise ValueError(f"person: the cuts must be increasing integers in 1..{m - 1}, got {c}")
+    return oi.astype(np.int32), c
+
+
+def _person_shape(kind, n, m, K):
+    return {"n": (n,), "c": (K, n), "3": (3, n), "2": (2, n)}[kind]
+
+
+def person_field(name: str, n: int, m: int, K: int):
+    """(shape, dtype) of the array gpirt_sampler_ppc_person_get copies for `name`: a finished field (PERSON_RESP_FIELDS: n;
+    PERSON_CELL_FIELDS: K x n), a raw array or constant of PERSON_RAW, group_lo, group_hi, group_items, order, cuts, counts or an
+    array of PERSON_LAST.  An unknown name is a ValueError that says so."""
+    named = {r[0]: r for r in _lib.PERSON_RAW + _lib.PERSON_LAST}
+    fixed = {"counts": ((2,), np.int64), "cuts": ((K - 1,), np.int64), "group_lo": ((K,), np.int64), "group_hi": ((K,), np.int64),
+             "group_items": ((m,), np.int32), "order": ((m,), np.int32)}
+    if name in fixed:
+        return fixed[name]
+    if name in named:
+        _, dt, kind = named[name]
+        return _person_shape(kind, n, m, K), _SC_DTYPES[dt]
+    for names, shape in ((_lib.PERSON_RESP_FIELDS, (n,)), (_lib.PERSON_CELL_FIELDS, (K, n))):
+        if name in names:
+            return shape, np.float64
+    raise ValueError(f"person: unknown field {name!r}")
+
+
+def person_struct(n: int, m: int, K: int, top=DEFAULT_PERSON_TOP):
+    """A gpirt_ppc_person with host arrays for every output, and those arrays (kept alive by the caller)."""
+    p = _lib.PpcPerson()
+    p.top = check_person_top(top)
+    arr = {}
+    for grp, names, shape in (("resp", _lib.PERSON_RESP_FIELDS, (n,)), ("cell", _lib.PERSON_CELL_FIELDS, (K, n))):
+        for k, name in enumerate(names):
+            arr[name] = np.empty(shape)
+            getattr(p, grp)[k] = arr[name].ctypes.data_as(_dp)
+    for k, (name, dt, kind) in enumerate(_lib.PERSON_RAW):
+        arr[name] = np.empty(_person_shape(kind, n, m, K), dtype=_SC_DTYPES[dt])
+        p.raw[k] = arr[name].ctypes.data
+    for name in ("group_lo", "group_hi"):
+        arr[name] = np.empty(K, dtype=np.int64)
+        setattr(p, name, arr[name].ctypes.data_as(C.POINTER(C.c_int64)))
+    arr["group_items"] = np.empty(m, dtype=np.int32)
+    p.group_items = arr["group_items"].ctypes.data_as(C.POINTER(C.c_int32))
+    arr["worst_respondents"] = np.empty(p.top, dtype=np.int64)
+    p.worst_respondents = arr["worst_respondents"].ctypes.data_as(C.POINTER(C.c_int64))
+    arr["worst_ppp_guttman_mid"] = np.empty(p.top)
+    p.worst_ppp_guttman_mid = arr["worst_ppp_guttman_mid"].ctypes.data_as(_dp)
+    return p, arr
+
+
+def person_result(p, arr) -> dict:
+    """The dict of Sampler.ppc_person() and person_combine(): every array of the header by name (cell (k, i) at [k, i]), "cuts",
+    "worst" (dict: respondents, ppp_guttman_mid) and the counters."""
+    out = {k: v for k, v in arr.items() if not k.startswith("worst_")}
+    out["worst"] = dict(respondents=arr["worst_respondents"], ppp_guttman_mid=arr["worst_ppp_guttman_mid"])
+    out["cuts"] = np.array([p.cuts[q] for q in range(p.K - 1)], dtype=np.int64)
+    out.update(n=int(p.n), m=int(p.m), K=int(p.K), person_draws=int(p.person_draws), person_skipped=int(p.person_skipped),
+               n_scored=int(p.n_scored))
+    return out
+
+
+def person_state_header(state) -> dict:
+    """The header of a person-fit state block (a device tensor): its 8 int64 words and the cuts."""
+    w = state[:24].cpu().numpy().view(np.int64)
+    K = int(w[4])
+    return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), K=K, person_draws=int(w[5]), person_skipped=int(w[6]),
+                cuts=tuple(int(x) for x in w[8:8 + max(min(K, 16) - 1, 0)]))
+
+
+def person_combine(handle, states, top=DEFAULT_PERSON_TOP) -> dict:
+    """gpirt_ppc_person_combine over the person-fit state blocks `states` (device tensors, or Samplers with ppc_person_enable()
+    on, all on handle's device): the integers added, the doubles added in chain order; no signs (theta -> -theta leaves f + mu
+    as it is).  Blocks with another n, m, K, order, cuts or response matrix are refused."""
+    lib = _lib.load()
+    tensors = [s.ppc_person_state() if hasattr(s, "ppc_person_state") else s for s in states]
+    hdr = person_state_header(tensors[0])
+    if (hdr["tag"] != _lib.PERSON_TAG or not 2 <= hdr["K"] <= _lib.PERSON_MAX_K or not 2 <= hdr["m"] <= _lib.PERSON_MAX_M
+            or not 1 <= hdr["n"] <= _lib.PERSON_MAX_N):
+        raise ValueError("person_combine: the first state is not a person-fit state block")
+    p, arr = person_struct(hdr["n"], hdr["m"], hdr["K"], top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    check(lib.gpirt_ppc_person_combine(handle.ptr, nc, ptrs, C.byref(p)))
+    return person_result(p, arr)
+
+
+def _person_groups(m, cuts):
+    """the group of every position: #{k : c_k <= t}"""
+    return np.searchsorted(np.asarray(cuts, dtype=np.int64), np.arange(m), side="right")
+
+
+def person_guttman(ob, bit) -> np.ndarray:
+    """G per respondent by the pair definition: #{positions s < t, both observed : z_s = 0, z_t = 1}; ob and bit are n x m in
+    POSITION order.  Every pair is looked at: O(m^2) per respondent."""
+    ob = np.asarray(ob, dtype=bool)
+    one = ob & (np.asarray(bit) != 0)
+    zero = ob & ~one
+    G = np.zeros(ob.shape[0], dtype=np.int64)
+    for s in range(ob.shape[1] - 1):
+        G += (zero[:, s:s + 1] & one[:, s + 1:]).sum(axis=1)
+    return G
+
+
+def _person_cells(grp, K, *terms):
+    """per term the K x n sums over the positions of group k (terms n x m in position order, zero off the observed cells)"""
+    return [np.stack([t[:, grp == k].sum(axis=1) for k in range(K)]).astype(np.int64) for t in terms]
+
+
+def person_observed(y, order, cuts) -> dict:
+    """The constants of the header from the data: N, x, g, q (int64, n), tN, tT (int64, K x n), live (the respondents with an
+    observed cell), with order, cuts, grp (the group of every position), K, n, m."""
+    y = np.asarray(y, dtype=np.float64)
+    n, m = y.shape
+    order, cuts = check_person_args(order, cuts, m, n)
+    K = len(cuts) + 1
+    yp = y[:, order]
+    ob = ~np.isnan(yp)
+    Y = ob & (yp > 0)
+    grp = _person_groups(m, cuts)
+    N, x = ob.sum(axis=1).astype(np.int64), Y.sum(axis=1).astype(np.int64)
+    tN, tT = _person_cells(grp, K, ob, Y)
+    return dict(order=order, cuts=cuts, grp=grp, K=K, n=n, m=m, N=N, live=N > 0, x=x, g=person_guttman(ob, Y), q=x * (N - x), tN=tN, tT=tT)
+
+
+def person_observed_from_arrays(order, cuts, x_obs, g_obs, q_obs, tN, tT) -> dict:
+    """person_observed's dict from the constants of a state block (gpirt_sampler_ppc_person_get): what person_draw_stats and
+    person_from_tables read of it."""
+    tN, tT = np.asarray(tN, dtype=np.int64), np.asarray(tT, dtype=np.int64)
+    K, n = tN.shape
+    order = np.asarray(order, dtype=np.int32)
+    N = tN.sum(axis=0)
+    return dict(order=order, cuts=tuple(int(c) for c in cuts), grp=_person_groups(len(order), cuts), K=K, n=n, m=len(order), N=N,
+                live=N > 0, x=np.asarray(x_obs, dtype=np.int64), g=np.asarray(g_obs, dtype=np.int64), q=np.asarray(q_obs, dtype=np.int64),
+                tN=tN, tT=tT)
+
+
+def person_tables(y, g, rep, obs) -> dict:
+    """One draw's tables: xr, gr, qr (int64, n), tR and the fixed-point tE, tV (int64, K x n), lz (3 x n LONG DOUBLE: Wo, Wr, Vl,
+    with p and the sums in long double), with "obs" = person_observed's dict; g must be finite in the observed cells."""
+    y = np.asarray(y, dtype=np.float64)
+    order, K, grp = obs["order"], obs["K"], obs["grp"]
+    yp = y[:, order]
+    ob = ~np.isnan(yp)
+    Y = ob & (yp > 0)
+    bit = ob & (np.asarray(rep)[:, order] != 0)
+    gz = np.where(ob, np.asarray(g, dtype=np.float64)[:, order], 0.0)
+    p, e = _plogis(gz)
+    q = np.where(gz >= 0, e / (1.0 + e), 1.0 / (1.0 + e))
+    ef = np.where(ob, np.rint(p * SCORES_FIX), 0.0).astype(np.int64)
+    vf = np.where(ob, np.rint((p * q) * SCORES_FIX), 0.0).astype(np.int64)
+    tR, tE, tV = _person_cells(grp, K, bit, ef, vf)
+    xr = bit.sum(axis=1).astype(np.int64)
+    ld = np.longdouble
+    gl = gz.astype(ld)
+    el = np.exp(-np.abs(gl))
+    pl = np.where(gl >= 0, 1 / (1 + el), el / (1 + el))
+    ql = np.where(gl >= 0, el / (1 + el), 1 / (1 + el))
+    zero = ld(0)
+    lz = np.stack([np.where(ob, (Y.astype(ld) - pl) * gl, zero).sum(axis=1), np.where(ob, (bit.astype(ld) - pl) * gl, zero).sum(axis=1),
+                   np.where(ob, pl * ql * gl * gl, zero).sum(axis=1)])
+    return dict(obs=obs, xr=xr, gr=person_guttman(ob, bit), qr=xr * (obs["N"] - xr), tR=tR, tE=tE, tV=tV, lz=lz)
+
+
+def person_draw_stats(tables) -> dict:
+    """The header's statistics and decisions of one draw from its tables (person_tables' dict, or the same arrays read from the
+    device; lz is taken as fp64): gn (n: G_rep / Q_rep, 0 where undefined), lz_obs, lz_rep (n; 0 where undefined), chi (2 x n:
+    X2(tT), X2(R)) and the bool decisions g_def, g_ge, g_gt, lz_def, chi_ge, chi_gt (n), cell_ge, cell_gt (K x n).  Nothing of a
+    respondent without an observed cell is set."""
+    obs = tables["obs"]
+    live = obs["live"]
+    Go, Qo = obs["g"], obs["q"]
+    Gr, Qr = np.asarray(tables["gr"], dtype=np.int64), np.asarray(tables["qr"], dtype=np.int64)
+    g_def = live & (Qo != 0) & (Qr != 0)
+    out = dict(g_def=g_def, g_ge=g_def & (Gr * Qo >= Go * Qr), g_gt=g_def & (Gr * Qo > Go * Qr),
+               gn=np.where(g_def, Gr.astype(np.float64) / np.where(g_def, Qr, 1).astype(np.float64), 0.0))
+    Wo, Wr, Vl = (np.asarray(a).astype(np.float64) for a in tables["lz"])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lz_def = live & np.isfinite(Vl) & (Vl > 0.0) & np.isfinite(Wo) & np.isfinite(Wr)
+        sd = np.sqrt(np.where(lz_def, Vl, 1.0))
+        out.update(lz_def=lz_def, lz_obs=np.where(lz_def, Wo / sd, 0.0), lz_rep=np.where(lz_def, Wr / sd, 0.0))
+    tN, T, R = obs["tN"], obs["tT"], np.asarray(tables["tR"], dtype=np.int64)
+    has = tN > 0
+    out.update(cell_ge=has & (R >= T), cell_gt=has & (R > T))
+    x2T, x2R = _score_x2(T, tables["tE"], tables["tV"]), _score_x2(R, tables["tE"], tables["tV"])
+    out.update(chi=np.stack([x2T, x2R]), chi_ge=live & (x2R >= x2T), chi_gt=live & (x2R > x2T))
+    return out
+
+
+def person_worst(ppp_guttman_mid, top=DEFAULT_PERSON_TOP) -> dict:
+    """The `top` respondents with the smallest ppp_guttman_mid, ties to the lowest i, NaN never listed; padded with -1 / NaN."""
+    top = check_person_top(top)
+    mid = np.asarray(ppp_guttman_mid, dtype=np.float64)
+    at = np.flatnonzero(~np.isnan(mid))
+    order = at[np.argsort(mid[at], kind="stable")][:top]
+    w = dict(respondents=np.full(top, -1, dtype=np.int64), ppp_guttman_mid=np.full(top, np.nan))
+    w["respondents"][:len(order)] = order
+    w["ppp_guttman_mid"][:len(order)] = mid[order]
+    return w
+
+
+def person_from_tables(draws, top=DEFAULT_PERSON_TOP, skipped=0, obs=None) -> dict:
+    """The header's accumulators and finished fields from the COUNTED draws' tables (a list of person_tables' dicts, in draw
+    order; obs: the constants, needed only when the list is empty).  Returns person_result's dict and "last" (the last draw's
+    arrays under the getter's names, lz as fp64)."""
+    S = len(draws)
+    obs = draws[0]["obs"] if draws else obs
+    n, m, K, live = obs["n"], obs["m"], obs["K"], obs["live"]
+    kinds = {name: (dt, kind) for name, dt, kind in _lib.PERSON_RAW}
+    acc = {name: np.zeros(_person_shape(kind, n, m, K), dtype=np.float64 if dt == "f8" else np.int64)
+           for name, (dt, kind) in kinds.items() if (name, dt, kind) not in _lib.PERSON_CONST}
+    un = 1.0 / SCORES_FIX
+    has = obs["tN"] > 0
+    last = None
+    for d in draws:
+        st = person_draw_stats(d)
+        for k in ("g_ge", "g_gt", "cell_ge", "cell_gt", "chi_ge", "chi_gt"):
+            acc[k] += st[k].astype(np.int64)
+        acc["g_undefined_count"] += (live & ~st["g_def"]).astype(np.int64)
+        acc["g_rep_sum"] += np.where(st["g_def"], np.asarray(d["gr"], dtype=np.int64), 0)
+        acc["gn_rep_sum"] = acc["gn_rep_sum"] + st["gn"]
+        acc["lz_undefined_count"] += (live & ~st["lz_def"]).astype(np.int64)
+        acc["lz_obs_sum"] = acc["lz_obs_sum"] + st["lz_obs"]
+        acc["lz_rep_sum"] = acc["lz_rep_sum"] + st["lz_rep"]
+        acc["lz_rep_sumsq"] = acc["lz_rep_sumsq"] + st["lz_rep"] * st["lz_rep"]
+        acc["sum_r"] += np.where(has, np.asarray(d["tR"], dtype=np.int64), 0)
+        acc["sum_e"] = acc["sum_e"] + np.where(has, np.asarray(d["tE"], dtype=np.int64).astype(np.float64) * un, 0.0)
+        acc["chi_obs_sum"] = acc["chi_obs_sum"] + np.where(live, st["chi"][0], 0.0)
+        acc["chi_rep_sum"] = acc["chi_rep_sum"] + np.where(live, st["chi"][1], 0.0)
+        last = dict(xr=np.asarray(d["xr"], dtype=np.int64), gr=np.asarray(d["gr"], dtype=np.int64), qr=np.asarray(d["qr"], dtype=np.int64),
+                    tR=np.asarray(d["tR"], dtype=np.uint32), tE=np.asarray(d["tE"], dtype=np.int64), tV=np.asarray(d["tV"], dtype=np.int64),
+                    lz=np.stack([np.asarray(a).astype(np.float64) for a in d["lz"]]), chi=st["chi"])
+    out = {k: (a if a.dtype == np.float64 else a.astype(_SC_DTYPES[kinds[k][0]])) for k, a in acc.items()}
+    out.update(x_obs=obs["x"].astype(np.int64), g_obs=obs["g"].astype(np.int64), q_obs=obs["q"].astype(np.int64),
+               tN=obs["tN"].astype(np.uint32), tT=obs["tT"].astype(np.uint32))
+    nan = float("nan")
+    fS = float(S)
+    f8 = lambda a: np.asarray(a).astype(np.float64)                                                       # noqa: E731
+    with np.errstate(invalid="ignore", divide="ignore"):
+        def over(num, cnt, least=1):
+            """num / cnt where cnt >= least and the respondent has an observed cell, NaN elsewhere"""
+            ok = live & (cnt >= least)
+            return np.where(ok, f8(num) / np.where(ok, cnt, 1).astype(np.float64), nan)
+
+        Sg, Sl = S - acc["g_undefined_count"], S - acc["lz_undefined_count"]
+        Sall = np.full(n, S, dtype=np.int64)
+        Qo = obs["q"]
+        out["guttman_obs"] = np.where(live, f8(obs["g"]), nan)
+        out["guttman_norm_obs"] = np.where(live & (Qo > 0), f8(obs["g"]) / np.where(Qo > 0, Qo, 1).astype(np.float64), nan)
+        out["guttman_rep_mean"], out["guttman_norm_rep_mean"] = over(out["g_rep_sum"], Sg), over(out["gn_rep_sum"], Sg)
+        out["ppp_guttman"] = over(out["g_ge"], Sg)
+        out["ppp_guttman_mid"] = over(f8(out["g_ge"]) + f8(out["g_gt"]), 2 * Sg, 2)
+        out["guttman_undefined"] = np.where(live, f8(out["g_undefined_count"]), nan)
+        out["lz_obs_mean"], out["lz_rep_mean"] = over(out["lz_obs_sum"], Sl), over(out["lz_rep_sum"], Sl)
+        mean = out["lz_rep_sum"] / np.where(Sl >= 1, Sl, 1).astype(np.float64)
+        v = (out["lz_rep_sumsq"] - out["lz_rep_sum"] * mean) / np.where(Sl >= 2, Sl - 1, 1).astype(np.float64)
+        out["lz_rep_sd"] = np.where(live & (Sl >= 2), np.where(v > 0.0, np.sqrt(np.where(v > 0.0, v, 0.0)), 0.0), nan)
+        out["lz_undefined"] = np.where(live, f8(out["lz_undefined_count"]), nan)
+        out["ppp_chi2"] = over(out["chi_ge"], Sall)
+        out["ppp_chi2_mid"] = over(f8(out["chi_ge"]) + f8(out["chi_gt"]), 2 * Sall, 2)
+        out["chi2_obs_mean"], out["chi2_rep_mean"] = over(out["chi_obs_sum"], Sall), over(out["chi_rep_sum"], Sall)
+        tNf = np.where(has, obs["tN"], 1).astype(np.float64)
+        out["obs_rate"] = np.where(has, f8(obs["tT"]) / tNf, nan)
+        ok = has & (S >= 1)
+        out["rep_rate"] = np.where(ok, f8(out["sum_r"]) / (fS * tNf), nan)
+        out["exp_rate"] = np.where(ok, out["sum_e"] / (fS * tNf), nan)
+        out["ppp_cell"] = np.where(ok, f8(out["cell_ge"]) / (fS if S else 1.0), nan)
+        out["ppp_cell_mid"] = np.where(ok, (f8(out["cell_ge"]) + f8(out["cell_gt"])) / (2.0 * fS if S else 1.0), nan)
+    cuts = obs["cuts"]
+    out["cuts"] = np.array(cuts, dtype=np.int64)
+    out["group_lo"] = np.array((0,) + tuple(cuts), dtype=np.int64)
+    out["group_hi"] = np.array(tuple(c - 1 for c in cuts) + (m - 1,), dtype=np.int64)
+    out["group_items"] = np.asarray(obs["order"], dtype=np.int32)
+    out["worst"] = person_worst(out["ppp_guttman_mid"], top)
+    out.update(n=n, m=m, K=K, person_draws=S, person_skipped=int(skipped), n_scored=int(live.sum()), last=last)
+    return out
+
+
+def person_from_rep(y, g_draws, rep_draws, order=None, cuts=None, top=DEFAULT_PERSON_TOP) -> dict:
+    """The header's person fit from stored draws: y (n x m; NaN = missing), g_draws (S, n, m) the draws of g = f + mu, rep_draws
+    (S, n, m) with rep != 0 where yrep = +1; order None: default_item_order(y), cuts None: default_item_cuts(m).  A draw with a
+    non-finite g in an observed cell is skipped.  Returns person_from_tables' dict."""
+    y = np.asarray(y, dtype=np.float64)
+    obs = person_observed(y, default_item_order(y) if order is None else order, default_item_cuts(y.shape[1]) if cuts is None else cuts)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    S = g_draws.shape[0]
+    assert g_draws.shape == (S,) + y.shape and np.asarray(rep_draws).shape == (S,) + y.shape
+    ob = ~np.isnan(y)
+    draws, skipped = [], 0
+    for s in range(S):
+        if not np.isfinite(g_draws[s][ob]).all():
+            skipped += 1
+            continue
+        draws.append(person_tables(y, g_draws[s], rep_draws[s], obs))
+    return person_from_tables(draws, top, skipped, obs)
+
+
+def person_from_draws(y, g_draws, seed, iters, order=None, cuts=None, top=DEFAULT_PERSON_TOP, item0=0):
+    """person_from_rep over the replicates of stored draws, built as scores_from_draws builds them: rep = [u < plogis(g)] with
+    replicate_uniforms' u at the completed-iteration counters `iters`.  Returns (result, min |u - p| over the observed cells
+    of the draws with finite g): a cell that close to its uniform may replicate either way under another evaluation of
+    plogis."""
+    y = np.asarray(y, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    n, m = y.shape
+    ob = ~np.isnan(y)
+    reps, gap = [], np.inf
+    for s, it in enumerate(iters):
+        with np.errstate(invalid="ignore"):
+            fin = ob & np.isfinite(g_draws[s])
+        p, _ = _plogis(np.where(fin, g_draws[s], 0.0))
+        u = replicate_uniforms(seed, int(it), n, m, item0)
+        if fin.any():
+            gap = min(gap, float(np.abs(u - p)[fin].min()))
+        reps.append(ob & (u < p))
+    rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
+    return person_from_rep(y, g_draws, rep, order, cuts, top), gap

@@ -1101,6 +1101,60 @@ class Sampler:
         from . import ppc as P
         return P.scores_combine(self.handle, [self], top=getattr(self, "_scores_top", P.DEFAULT_SCORES_TOP) if top is None else top)
 
+    # -- person fit inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_person_*, gpirt_amd.ppc)
+    def ppc_person_enable(self, order=None, cuts=None, groups=5, top=20, on=True):
+        """Allocate and zero the person-fit accumulators on a sampler whose ppc_enable is on, and count the data's constants on
+        the device: from then on every ppc_accumulate also adds every respondent's Guttman errors, lz and person response
+        function (the yes rate within groups of the items' easiness) of the replicate.  order: a permutation of 0 .. m - 1, the
+        easiest item first; None: by the data's yes rate (gpirt_amd.ppc.default_item_order).  cuts: ascending integers in 1 .. m -
+        1 that act on the POSITIONS in that order (K - 1 of them, 2 <= K <= 16 groups; position t lies in group #{k : c_k <=
+        t}); None: `groups` groups of near-equal size (gpirt_amd.ppc.default_item_cuts).  top (1..64): how many respondents
+        ppc_person() lists as worst.  on=False frees the state.  Stage API only: gpirtMCMC has no keyword for it."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_person_enable(self._s, 0, None, None, 0))
+            self._person_K = None
+            return
+        from . import ppc as P
+        self._person_top = P.check_person_top(top)
+        order, cuts = P.check_person_args(P.default_item_order(self.get("y")) if order is None else order,
+                                          P.default_item_cuts(self.m, groups) if cuts is None else cuts, self.m, self.n)
+        check(self.lib.gpirt_sampler_ppc_person_enable(self._s, len(cuts) + 1, order.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       (C.c_int * len(cuts))(*cuts), 1))
+        self._person_K = len(cuts) + 1
+
+    def ppc_person_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.PERSON_RESP_FIELDS: float64 n; PERSON_CELL_FIELDS: K x n), a raw array or
+        constant of _lib.PERSON_RAW, group_lo, group_hi (int64, K), group_items, order (int32, m), cuts (int64, K - 1), counts
+        (int64: person_draws, person_skipped) and, of the last counted draw, the arrays of _lib.PERSON_LAST.  An unknown name is
+        a ValueError."""
+        from . import ppc as P
+        K = getattr(self, "_person_K", None) or 2                    # (not enabled: the library refuses the call)
+        shape, dtype = P.person_field(name, self.n, self.m, K)
+        out = np.empty(shape, dtype=dtype)
+        check(self.lib.gpirt_sampler_ppc_person_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out
+
+    def ppc_person_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the person-fit accumulators: what
+        gpirt_amd.ppc.person_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_person_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_person(self, top=None) -> dict:
+        """Every finished output of this sampler's person-fit accumulators (gpirt_amd.ppc.person_result's shape):
+        gpirt_ppc_person_combine over its own state; top defaults to ppc_person_enable's."""
+        from . import ppc as P
+        return P.person_combine(self.handle, [self], top=getattr(self, "_person_top", P.DEFAULT_PERSON_TOP) if top is None else top)
+
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         """Allocate and zero the rank accumulators for `pivots` ("median" and / or positions in 1..n, at most 16; the

@@ -1366,6 +1366,119 @@ int gpirt_sampler_ppc_scores_get(gpirt_sampler_t s, const char* name, void* h_ou
 int gpirt_sampler_ppc_scores_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_scores_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_scores* out);
 
+/* ------------------------------------------------- person fit in the PPC: Guttman errors, lz, person response function ------- */
+/* The checks above judge an ITEM; for a RESPONDENT the PPC has the yes count and one deviance p-value (respondent_ppp_dev).  A
+ * respondent who misses the easy items and answers the hard ones can replicate both: what goes wrong is WHICH items were answered
+ * yes, in the order of their easiness.  This section adds the three standard person-fit tools in their posterior predictive form
+ * (Glas and Meijer 2003): the number of Guttman errors (Meijer 1994), the standardised log-likelihood lz (Drasgow, Levine and
+ * Williams 1985) and the person response function, the yes rate by item-easiness group (Sijtsma and Meijer 2001).  For a GP-IRT
+ * model the curves need not be monotone, so the model does not imply a Guttman pattern: only the replicate of each draw says how
+ * many errors a respondent is expected to make.  It is the score-based section transposed: respondent fit within groups of the
+ * items' easiness.  A fifth add-on to the PPC (library version 121): enabled on a sampler whose ppc_enable is on, accumulated
+ * inside the same ppc_accumulate call by a pass of its own that forms the PPC's replicate again, bit for bit (the same expression
+ * for p, the same item_uniform(seed, iter, GPIRT_ST_PPC, item0 + j, i)); nothing is drawn.  Stage API only: gpirt_run,
+ * gpirt_mcmc_run and gpirtMCMC have no field for it and stay exactly as they are.
+ * n respondents, m items, column-major (cell (i, j) at i + j n), 2 <= m <= GPIRT_PERSON_MAX_M = 4096, n <= GPIRT_PERSON_MAX_N =
+ * 65534, 2 <= K <= GPIRT_PERSON_MAX_K = 16 item groups; item shards are refused.  O = the observed cells, Y = [y = +1] and rep =
+ * [yrep = +1] on O.  A respondent without an observed cell is left out of everything: no accumulator of its moves and every
+ * finished value of its is NaN.
+ * Item order and groups, given by the caller and constant for the state: `order` is a permutation of 0 .. m - 1, the easiest item
+ * first; position t holds item order[t].  The cuts c_1 < ... < c_{K-1}, integers in 1 .. m - 1, act on POSITIONS: position t lies
+ * in group #{k : c_k <= t}, so group k holds the positions group_lo[k] = c_k (0 for k = 0) to group_hi[k] = c_{k+1} - 1 (m - 1
+ * for k = K - 1).  The STRIPS: each group's positions are cut, from the group's first position on, into runs of 32 (the last run
+ * of a group may be shorter); the strips are numbered in ascending position.  They fix the order of the floating-point sums.
+ * A draw with a non-finite g = f + mu in an observed cell is skipped whole -- person_skipped += 1 and nothing else changes, which
+ * is decided before any accumulator is touched; a NaN in a missing cell is ignored.  Every other draw adds 1 to person_draws.
+ * Per respondent i, over i's observed cells in position order (N = #O_i):
+ * 1. Guttman errors.  For z in {Y, rep}: X(z) = sum z, G(z) = #{positions s < t, both observed : z_s = 0, z_t = 1}, Q(z) =
+ *    X (N - X), the largest G that score allows.  x_obs, g_obs, q_obs are constants (int64), counted on the device at enable.
+ *    Per counted draw: if Q_obs = 0 or Q_rep = 0, g_undefined_count += 1 and the draw enters nothing else of the Guttman check;
+ *    otherwise g_ge / g_gt += [G_rep Q_obs >= / > G_obs Q_rep] (an integer cross-multiplication, every product below 2^46),
+ *    g_rep_sum += G_rep (uint64) and gn_rep_sum += (double)G_rep / (double)Q_rep (in draw order).  A small p-value says that the
+ *    data hold more errors than the model replicates.
+ * 2. lz.  With g the cell's f + mu, e = exp(-|g|), p = 1 / (1 + e) for g >= 0 and e / (1 + e) otherwise, q the other of the two:
+ *    l(z) - E[l] = sum (z - p) g exactly and Var[l] = sum p q g^2, so no logarithm is needed.  Per draw Wo = sum (Y - p) g, Wr =
+ *    sum (rep - p) g, Vl = sum ((p q) g) g, every term in fp64 as written (Y and rep as 0.0 / 1.0, no contraction), the observed
+ *    cells of a strip added in ascending position to 0.0, the strips' sums added in ascending strip to 0.0.  No floating-point
+ *    atomics.  If Vl is not finite or not > 0, or Wo or Wr is not finite, lz_undefined_count += 1; otherwise, with sd =
+ *    sqrt(Vl), lz_obs_sum += Wo / sd, lz_rep_sum += Wr / sd, lz_rep_sumsq += (Wr / sd) (Wr / sd).  The p-value of lz is the PPC's
+ *    own respondent_ppp_dev -- l(rep) <= l(y) exactly when D(rep) >= D(y) -- and is not stored twice.
+ * 3. Person response function.  Per (group k, respondent i): tN = #observed cells and tT = #{Y = 1} (constants, uint32, counted
+ *    at enable); per draw R = #{rep = 1}, E = sum rint(p 2^44) and V = sum rint((p q) 2^44) as int64 (the score-based section's
+ *    fixed point: every term rounded once, the sums exact in any order).  Per counted draw and cell with tN > 0: sum_r += R
+ *    (uint64), sum_e += (double)E 2^-44, cell_ge / cell_gt += [R >= / > tT] (the same cells on both sides, so no
+ *    cross-multiplication).  X2(C) = sum over k ascending with V > 0 of d d / v, d = (double)(C 2^44 - E) 2^-44, v = (double)V
+ *    2^-44 (no contraction); chi_ge / chi_gt += [X2(R) >= / > X2(tT)], chi_obs_sum += X2(tT), chi_rep_sum += X2(R).
+ * Finished on the host with S = person_draws (NaN where a denominator is 0 and for a respondent without an observed cell):
+ *   n values each (GPIRT_PERSON_RESP_*), with S' = S - g_undefined_count and S" = S - lz_undefined_count: guttman_obs = G_obs,
+ *   guttman_norm_obs = G_obs / Q_obs, guttman_rep_mean = g_rep_sum / S', guttman_norm_rep_mean = gn_rep_sum / S', ppp_guttman =
+ *   g_ge / S', ppp_guttman_mid = (g_ge + g_gt) / 2S', guttman_undefined; lz_obs_mean = lz_obs_sum / S", lz_rep_mean, lz_rep_sd =
+ *   sqrt(max((lz_rep_sumsq - lz_rep_sum lz_rep_mean) / (S" - 1), 0)) for S" >= 2, lz_undefined; ppp_chi2 = chi_ge / S,
+ *   ppp_chi2_mid, chi2_obs_mean, chi2_rep_mean;
+ *   K x n values each, cell (k, i) at [k n + i] (GPIRT_PERSON_CELL_*; NaN where tN = 0): obs_rate = tT / tN, rep_rate = sum_r /
+ *   (S tN), exp_rate = sum_e / (S tN), ppp_cell = cell_ge / S, ppp_cell_mid;
+ *   group_lo, group_hi (int64, K; positions), group_items (int32, m: the order itself); worst: the `top` (1 ..
+ *   GPIRT_PERSON_MAX_TOP, the Python default is 20) respondents with the smallest ppp_guttman_mid, ties to the lowest i, NaN never
+ *   listed, padded with -1 / NaN.
+ * Determinism: every accumulator of a respondent is owned by one thread and there is no atomic at all; two runs give a
+ * byte-identical state block.  Pooling C chains (gpirt_ppc_person_combine) adds the integers and adds the doubles in chain order.
+ * It takes no signs: theta -> -theta leaves f + mu of every cell as it is.  Blocks whose n, m, K, order, cuts or constants differ
+ * from state 0 are refused.  With the block on, the chain, the IRFs and the PPC, pairs, bins, dif and scores state blocks are bit
+ * for bit what they are without.
+ * The raw arrays (GPIRT_PERSON_NRAW, in the state block's order).  Constants: int64 x_obs, g_obs, q_obs (n), uint32 tN, tT (K n).
+ * Accumulators: uint32 g_ge, g_gt, g_undefined_count, uint64 g_rep_sum, double gn_rep_sum (n); uint32 lz_undefined_count, double
+ * lz_obs_sum, lz_rep_sum, lz_rep_sumsq (n); uint64 sum_r, double sum_e, uint32 cell_ge, cell_gt (K n); uint32 chi_ge, chi_gt,
+ * double chi_obs_sum, chi_rep_sum (n).
+ * Device memory per state at 8192 x 1024 with 16 groups: the block 5.0 MB (104 bytes per respondent and 32 per cell), the
+ * strips' partials 17 MB at the most (44 bytes per strip and respondent, 32 to 47 strips), the last draw's arrays 3.0 MB. */
+#define GPIRT_PERSON_MAX_M       4096
+#define GPIRT_PERSON_MAX_N       65534
+#define GPIRT_PERSON_MAX_K       16
+#define GPIRT_PERSON_MAX_TOP     64
+#define GPIRT_PERSON_RESP_NFIELDS  15   /* guttman_obs, guttman_norm_obs, guttman_rep_mean, guttman_norm_rep_mean, ppp_guttman,
+                                           ppp_guttman_mid, guttman_undefined, lz_obs_mean, lz_rep_mean, lz_rep_sd, lz_undefined,
+                                           ppp_chi2, ppp_chi2_mid, chi2_obs_mean, chi2_rep_mean */
+#define GPIRT_PERSON_CELL_NFIELDS  5    /* obs_rate, rep_rate, exp_rate, ppp_cell, ppp_cell_mid */
+#define GPIRT_PERSON_NRAW          22
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_ppc_person {
+    int        top;                              /* in: 1..GPIRT_PERSON_MAX_TOP */
+    int        K;                                /* out: the states' number of groups */
+    int        cuts[GPIRT_PERSON_MAX_K];         /* out: c_1 .. c_{K-1}, the rest 0 */
+    double*    resp[GPIRT_PERSON_RESP_NFIELDS];  /* n each */
+    double*    cell[GPIRT_PERSON_CELL_NFIELDS];  /* K x n each */
+    void*      raw[GPIRT_PERSON_NRAW];           /* the raw arrays, in the order and with the types above */
+    int64_t*   group_lo;                         /* K */
+    int64_t*   group_hi;                         /* K */
+    int32_t*   group_items;                      /* m: the order */
+    int64_t*   worst_respondents;                /* top */
+    double*    worst_ppp_guttman_mid;            /* top */
+    int64_t    n, m;                             /* out */
+    int64_t    person_draws, person_skipped;     /* out */
+    int64_t    n_scored;                         /* out: the respondents with an observed cell */
+    int64_t    reserved[4];                      /* must be 0 */
+} gpirt_ppc_person;
+/* Stage API.  ppc_person_enable(K, order, cuts, on != 0) allocates and zeroes the state on a sampler with ppc_enable on and counts
+ * the constants on the device (GPIRT_E_ARG, with a message that names the fault, without ppc_enable, on an item shard, for m
+ * outside 2..4096, n > 65534, K outside 2..16, for an order that is not a permutation of 0 .. m - 1 -- the first offending entry is
+ * named -- and for cuts that are not K - 1 ascending integers in 1 .. m - 1; on = 0 frees it, order and cuts may then be NULL;
+ * ppc_enable called again frees it too).  From then on every ppc_accumulate also adds the draw to the block.  ppc_person_get
+ * copies one array by name to the host, `bytes` its exact size: every finished array by the lower-case name above (double), the
+ * raw arrays by theirs, "group_lo", "group_hi" (int64, K), "group_items" and "order" (int32, m), "counts" (int64: person_draws,
+ * person_skipped), "cuts" (int64, K - 1) and, of the last COUNTED draw, "xr", "gr", "qr" (int64, n: X, G, Q of the replicate),
+ * "tR" (uint32, K x n), "tE", "tV" (the fixed-point int64 sums, K x n), "lz" (double, 3 x n: Wo, Wr, Vl) and "chi" (double, 2 x
+ * n: X2(tT), X2(R)).
+ * ppc_person_state returns the ONE device block of its own: a header of 8 int64 -- the tag 0x31535250 ("PRS1"), the layout
+ * version (1), n, m, K, person_draws, person_skipped, 0 --, 16 int64 with the cuts c_1 .. c_{K-1} (the rest 0), the order as m
+ * int32, then the raw arrays in the order above; every array starts on a 16-byte boundary.
+ * gpirt_ppc_person_check is ppc_person_enable's argument check alone (0, or GPIRT_E_ARG with the message): nothing is allocated
+ * and no device is touched. */
+int gpirt_ppc_person_check(int64_t n, int64_t m, int K, const int32_t* order, const int* cuts);
+int gpirt_sampler_ppc_person_enable(gpirt_sampler_t s, int K, const int32_t* order, const int* cuts, int on);
+int gpirt_sampler_ppc_person_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_person_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_person_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_person* out);
+
 /* ------------------------------------------------------ Two-form score equating: joint table, concordance ------------- */
 /* The sum-score section answers every question about ONE form's score.  This one is about TWO forms at once: how scores on
  * form X and form Y relate (IRT observed-score equating), what somebody who scored s on X scores on Y (the concordance table),
