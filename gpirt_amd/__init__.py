@@ -6,8 +6,8 @@ Layout:
   _lib.py          ctypes binding of that C ABI (fails loudly when the library / GPU is missing)
   ops.py           operator-level host API (K, chol, trmm, trsm, draw_f, draw_fstar, ...)
   sampler.py       gpirtMCMC() mirror of the reference's R entry point, and the stage-driven Sampler
-  chains.py ... loo.py        host side of the on-device posterior functionals (chains, quantiles, ppc, ranks, score,
-                   shape, sumscore, equate, loo): the C structs, the pooling of chains and the NumPy statement each is tested against
+  chains.py ... acf.py        host side of the on-device posterior functionals (chains, quantiles, ppc, ranks, score,
+                   shape, sumscore, equate, loo, acf): the C structs, the pooling of chains and the NumPy statement each is tested against
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

@@ -368,6 +368,29 @@ class ShapeOrder(C.Structure):
                 ("n", C.c_int64), ("m", C.c_int64), ("draws", C.c_int64), ("skipped", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# autocorrelation ESS (include/gpirt_hip.h GPIRT_ACF_*): the series' bits, the raw arrays of a state block in order, the outputs
+ACF_THETA, ACF_BETA, ACF_LL = 1, 2, 4
+ACF_PARTS = {"theta": ACF_THETA, "beta": ACF_BETA, "ll": ACF_LL}
+ACF_MAX_LAG, ACF_DEFAULT_LAG, ACF_MAX_TOP, ACF_TAG = 1024, 256, 64, 0x31464341
+ACF_RAW = ("s", "sum", "head", "tail", "centre", "nonfinite", "ring")
+ACF_VALUES = ("ess", "tau", "mcse", "rhat", "rho1", "mean", "sd")
+ACF_FLAGS = ("lag_used", "truncated", "nonfinite", "constant")
+ACF_BLOCKS = ("theta", "beta", "item_ll", "resp_ll", "total_ll")
+ACF_BLOCK_STATS = ("min_ess", "max_tau", "max_rhat")
+ACF_BLOCK_COUNTS = ("n_truncated", "n_nan")
+
+
+class Acf(C.Structure):
+    """gpirt_acf (include/gpirt_hip.h): top (in), a host pointer per output (NULL: not wanted), the block folds, the counters."""
+    _fields_ = [("top", C.c_int64), ("value", C.POINTER(C.c_double) * len(ACF_VALUES)),
+                ("flag", C.POINTER(C.c_int64) * len(ACF_FLAGS)), ("acf", C.POINTER(C.c_double)),
+                ("worst_block", C.POINTER(C.c_int64)), ("worst_index", C.POINTER(C.c_int64)), ("worst_ess", C.POINTER(C.c_double)),
+                ("block_stat", C.c_double * (len(ACF_BLOCKS) * len(ACF_BLOCK_STATS))),
+                ("block_count", C.c_int64 * (len(ACF_BLOCKS) * len(ACF_BLOCK_COUNTS))),
+                ("n", C.c_int64), ("m", C.c_int64), ("parts", C.c_int64), ("S", C.c_int64), ("H", C.c_int64), ("L", C.c_int64),
+                ("P", C.c_int64), ("chains", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 class Run(C.Structure):
     """gpirt_run (include/gpirt_hip.h): what gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs -- R's stream (NULL: the
     item RNG) and one pointer per analysis (NULL: not wanted)."""
@@ -524,6 +547,12 @@ SIGNATURES = {
     "gpirt_sampler_ppc_scores_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_scores_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_scores_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcScores)]),
+    "gpirt_acf_check": (_i32, [_i64, _i64, _i32, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gpirt_sampler_acf_enable": (_i32, [_vp, _i32, _i64, _i64, _i32]),
+    "gpirt_sampler_acf_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_acf_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_acf_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_acf_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Acf)]),
     "gpirt_ppc_person_check": (_i32, [_i64, _i64, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "gpirt_sampler_ppc_person_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int), _i32]),
     "gpirt_sampler_ppc_person_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),

@@ -842,6 +842,32 @@ int launch_loo_merge(hipStream_t stream, uint64_t* into, const uint64_t* from, i
 int loo_get(hipStream_t stream, LooState* s, const char* name, void* h_out, int64_t bytes);
 int loo_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_loo* out);
 
+// acf.hip: autocorrelation ESS without stored draws (gpirt_sampler_acf_*, gpirt_acf_combine; include/gpirt_hip.h,
+// "autocorrelation ESS").  The state is ONE device block of 8-byte words: a header of ACF_HEADER_WORDS int64 (tag, layout version,
+// n, m, parts, S, H, L, P, draws, 0 ... -- draws is kept by the kernels), then the GPIRT_ACF_* arrays in order, each on a 16-byte
+// boundary.  `last` (the draw's P values as read), cpart and rpart (the log-likelihood pass's partials) are scratch beside it.
+constexpr int ACF_LAYOUT_VERSION = 1;
+constexpr int ACF_HEADER_WORDS = 16;
+constexpr int64_t ACF_TAG = 0x31464341;               // "ACF1"
+struct AcfLayout { int64_t off[GPIRT_ACF_NARRAYS]; int64_t words; };
+AcfLayout acf_layout(int64_t P, int64_t L);
+struct AcfState {
+    bool on = false;
+    int64_t n = 0, m = 0, S = 0, H = 0, L = 0, P = 0, draws = 0;
+    int parts = 0;
+    uint64_t* block = nullptr;
+    double *last = nullptr, *cpart = nullptr, *rpart = nullptr;
+};
+// the argument check of gpirt_acf_check: L from max_lag (0: the default), P from the parts
+int acf_check(int64_t n, int64_t m, int parts, int64_t planned, int64_t max_lag, int64_t* L_out, int64_t* P_out);
+int acf_alloc(hipStream_t stream, AcfState* s, int64_t n, int64_t m, int parts, int64_t planned, int64_t L);
+void acf_free(AcfState* s);
+// the sampler's theta (n), beta (2 x m), f, mu and y (n x m) on the device; refuses a draw beyond the planned ones
+int launch_acf_accumulate(hipStream_t stream, AcfState* s, const double* theta, const double* beta, const double* f, const double* mu,
+                          const double* y);
+int acf_get(hipStream_t stream, AcfState* s, const char* name, void* h_out, int64_t bytes);
+int acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

@@ -147,6 +147,7 @@ struct gpirt_sampler_s {
     SumscoreState sumscore;           // sum-score posteriors (gpirt_sampler_sumscore_enable; on == false: off)
     EquateState equate;               // two-form score equating (gpirt_sampler_equate_enable; on == false: off)
     LooState loo;                     // PSIS-LOO (gpirt_sampler_loo_enable; on == false: off)
+    AcfState acf;                     // autocorrelation ESS (gpirt_sampler_acf_enable; on == false: off)
 };
 
 namespace {
@@ -1223,6 +1224,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     sumscore_free(&s->sumscore);
     equate_free(&s->equate);
     loo_free(&s->loo);
+    acf_free(&s->acf);
     score_free(&s->score);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -2157,6 +2159,62 @@ int gpirt_shape_order_state_bytes(int64_t m, int n_tols, int64_t* bytes)
 int gpirt_shape_order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out)
 {
     return order_combine(h, chains, d_states, out);
+}
+
+// ---- autocorrelation ESS (acf.hip) on the stage API -------------------------------------------------------------------------
+static int acf_needs_on(gpirt_sampler_t s)
+{
+    if (s->acf.on) return 0;
+    set_error("the autocorrelation ESS is not enabled (gpirt_sampler_acf_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_acf_check(int64_t n, int64_t m, int parts, int64_t planned_draws, int64_t max_lag, int64_t* L_out, int64_t* P_out)
+{
+    return acf_check(n, m, parts, planned_draws, max_lag, L_out, P_out);
+}
+
+int gpirt_sampler_acf_enable(gpirt_sampler_t s, int parts, int64_t planned_draws, int64_t max_lag, int on)
+{
+    GP_ARG(s && s->initialised);
+    int64_t L = 0;
+    if (on) GP_TRY(acf_check(s->n, s->m, parts, planned_draws, max_lag, &L, nullptr));   // refused before the old state goes
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // a kernel still running on the old accumulators
+    acf_free(&s->acf);
+    if (!on) return 0;
+    const int rc = acf_alloc(s->h->stream, &s->acf, s->n, s->m, parts, planned_draws, L);
+    if (rc) acf_free(&s->acf);
+    return rc;
+}
+
+int gpirt_sampler_acf_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(acf_needs_on(s));
+    GP_TRY(beta_sync(s));                     // draw_beta (beta, mu) may still be deferred to the sampler's own stream
+    return launch_acf_accumulate(s->h->stream, &s->acf, s->theta, s->beta, s->f, s->mu, s->y);
+}
+
+int gpirt_sampler_acf_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(acf_needs_on(s));
+    return acf_get(s->h->stream, &s->acf, name, h_out, bytes);
+}
+
+int gpirt_sampler_acf_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(acf_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));                 // the header's draw count is the kernels'
+    *d_state = s->acf.block;
+    *bytes = acf_layout(s->acf.P, s->acf.L).words * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out)
+{
+    return acf_combine(h, chains, d_states, signs, out);
 }
 
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------

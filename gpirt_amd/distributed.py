@@ -301,6 +301,12 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the item-pair order posteriors are not offered for item shards (a pair's two curves "
                          "may live on two ranks, and the shape posteriors they sit on are not offered either)")
 
+    # -- autocorrelation ESS (gpirt_amd.acf): beta's and the items' series are local to a shard, but the respondents' and the
+    # total log-likelihood run over all items and are not pooled across ranks here
+    def acf_enable(self, parts="all", planned_draws=None, max_lag=None, on=True):
+        raise ValueError("ShardedSampler: the autocorrelation ESS is not offered for item shards (the respondents' and the "
+                         "total log-likelihood series run over all items; each rank holds its own columns)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

@@ -4,8 +4,9 @@ gpirt_summary_quantiles, gpirt_run.quantiles).
 Every theta draw is a point of the fixed grid theta* = -5 + 0.01 k, k = 0..1000, so a count per (respondent, grid point)
 is the exact posterior of theta in n x 1001 counts however long the chain: exact quantiles, the median, the mode, exact
 pooling over chains (an integer sum; the reflection theta -> -theta reverses the grid index) and -- from the counts of
-DIAG's two halves -- the rank-normalised split-R-hat of Vehtari et al. (2021), bulk and tail, exactly.  The bulk-ESS and
-tail-ESS need the autocorrelation, the order of the draws, and are not offered.
+DIAG's two halves -- the rank-normalised split-R-hat of Vehtari et al. (2021), bulk and tail, exactly.  The rank-normalised
+bulk-ESS and tail-ESS are not offered: the ranks are not known until the end of the chain.  The autocorrelation ESS of the values
+themselves is (gpirt_amd.acf).
 
 f* is not on a grid; each cell (grid point k, item j) keeps a histogram of 256 bins that cut the probability scale evenly
 (edges e_b = logit(b / 256) on the f* scale, gpirt_irf_band_edges) and the sum of plogis(f*).  A band quantile is

@@ -1478,6 +1478,64 @@ class Sampler:
         from . import loo as LO
         return LO.combine(self.handle, [self], top=top)
 
+    # -- autocorrelation ESS (include/gpirt_hip.h gpirt_sampler_acf_*, gpirt_amd.acf)
+    def acf_enable(self, parts="all", planned_draws=None, max_lag=None, on=True):
+        """Allocate and zero the autocorrelation state for this chain's `planned_draws` draws (S, fixed now, as DIAG's) and the
+        series `parts` (GPIRT_ACF_* bits, names of ("theta", "beta", "ll") or "all").  max_lag: L, 1 .. min(S // 2 - 1, 1024);
+        None: min(S // 2 - 1, 256).  No planned draws, halves of fewer than 4 draws and a lag window the halves cannot fill are
+        ValueErrors.  on=False frees the state.  Stage API only: gpirtMCMC has no keyword for it (gpirt_amd.acf.run is the
+        one-call way in)."""
+        if not on:
+            check(self.lib.gpirt_sampler_acf_enable(self._s, 0, 0, 0, 0))
+            self._acf = None
+            return
+        from . import acf as AC
+        mask = AC.parts_mask(parts)
+        L = AC.lag_window(planned_draws, max_lag)
+        check(self.lib.gpirt_sampler_acf_enable(self._s, mask, int(planned_draws), 0 if max_lag is None else int(max_lag), 1))
+        self._acf = (mask, L, AC.n_values(self.n, self.m, mask))
+
+    def acf_accumulate(self):
+        """Enter the current theta, beta and f + mu (after a sampling iteration's step) as the chain's next draw; one beyond
+        the planned draws is an error.  The chain is untouched."""
+        self._call("gpirt_sampler_acf_accumulate")
+
+    def acf_get(self, name: str) -> np.ndarray:
+        """One array by name: s, head, tail (2 x (L + 1) x P), sum (2 x P), ring ((L + 1) x P), centre, last (P; float64),
+        nonfinite (int64, P) -- theta's integer columns come back as float64, exactly -- and counts (int64: n, m, parts, S, H, L,
+        P, draws)."""
+        from . import acf as AC
+        mask, L, P = getattr(self, "_acf", None) or (0, 0, 1)           # (not enabled: the library refuses the call)
+        if name == "counts":
+            out = np.empty(8, dtype=np.int64)
+        else:
+            out = np.empty(AC.raw_shape(name, P, L), dtype=np.int64)
+        check(self.lib.gpirt_sampler_acf_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        if name == "counts":
+            return out
+        return AC.decode_raw(name, out, 0 if name == "last" or not mask & _lib.ACF_THETA else self.n)
+
+    def acf_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the autocorrelation state: what gpirt_amd.acf.combine
+        finishes."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_acf_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def acf(self, top=20, sign=1) -> dict:
+        """Every finished output of this sampler's state alone (gpirt_amd.acf.result's dict): gpirt_acf_combine over it with
+        `sign` (+1, or -1 for the reflected chain)."""
+        from . import acf as AC
+        return AC.combine(self.handle, [self], signs=[sign], top=top)
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

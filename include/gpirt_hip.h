@@ -1750,6 +1750,120 @@ int gpirt_sampler_shape_order_state(gpirt_sampler_t s, void** d_state, int64_t* 
 int gpirt_shape_order_state_bytes(int64_t m, int n_tols, int64_t* bytes);
 int gpirt_shape_order_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_shape_order* out);
 
+/* ------------------------------------------------------ autocorrelation ESS: lag sums, Geyer tau, MCSE ---------------- */
+/* The lag-window estimate of the effective sample size (Geyer's 1992 initial monotone sequence over split chains, the rule
+ * Stan, `posterior` and ArviZ users know as ESS) for tracked scalar series of the chain, without stored draws: only the last
+ * L + 1 draws of each value are kept, in a ring.  Library version 122.  Stage API only: gpirt_run has no field for it yet.
+ * SERIES, chosen by the bit mask `parts`, in this order (P values in all):
+ *   GPIRT_ACF_THETA   n values, the INTEGER section: a theta draw is a grid point -5 + 0.01 k;
+ *   GPIRT_ACF_BETA    2m values in the order of the array beta (value 2j + r is row r of item j; r = 1 is the slope);
+ *   GPIRT_ACF_LL      m + n + 1 values: item_ll[j], resp_ll[i], total_ll, from the sampler's own f, mu and y.
+ * LOG-LIKELIHOOD.  For an observed cell g = f + mu (one fp64 add) and cell = -(log1p(exp(-|g|)) + fmax(-y g, 0)), WAIC's
+ * expression; a missing cell and a row past n enter as 0.0.  Work-group (b, q) owns rows 256 b .. 256 b + 255 and columns
+ * 32 q .. 32 q + 31.  Its lane of row i adds the cells of its columns in ascending j: R[q][i].  For each column the 256 rows
+ * are summed by a fixed tree: in each wave of 64 rows v[l] += v[l + o] for o = 32, 16, 8, 4, 2, 1, then (w0 + w1) + (w2 + w3)
+ * over the four waves: C[b][j].  resp_ll[i] = sum over q ascending of R[q][i]; item_ll[j] = sum over b ascending of C[b][j];
+ * total_ll = sum over j ascending of item_ll[j].  No atomics.
+ * HALVES.  S = the chain's planned draws, H = floor(S / 2); half 1 is draws 1 .. H, half 2 the last H draws; with S odd the
+ * middle draw enters nothing.  Each half is a series of its own with t = 1 .. H; the ring restarts at half 2's first draw.
+ * 4 <= H, 1 <= L <= min(H - 1, GPIRT_ACF_MAX_LAG); max_lag = 0 asks for L = min(H - 1, GPIRT_ACF_DEFAULT_LAG).
+ * RAW ARRAYS, for half h, lag k = 0 .. L and value p (value fastest): d_t = x_t - centre[p]; for theta d_t = k_t - 500 as an
+ * integer (centre 0) and every theta array but `centre` is int64; for the others centre[p] is the value at the chain's first
+ * draw (0 if that is not finite) and d_t is one fp64 subtraction.  A non-finite value -- for theta also one off the grid, by
+ * the rule of GPIRT_SUM_THETA_HIST: k = rint((x + 5) 100) outside 0 .. 1000 or -5 + 0.01 k != x -- adds 1 to nonfinite[p] and
+ * enters as d_t = 0.
+ *   s[h][k][p]    = sum_{t = k+1 .. H} d_t d_{t-k}, one product and one add per term, added in ascending t;
+ *   sum[h][p]     = sum_t d_t in ascending t;
+ *   head[h][k][p] = the running sum after the first k draws;
+ *   tail[h][k][p] = d_H + d_{H-1} + ... + d_{H-k+1}, added in that order (written from the ring at the half's last draw);
+ *   centre[p], nonfinite[p] (int64).
+ * Every cell has one owner and no sum is contracted, so a sequential NumPy loop reproduces the arrays bit for bit.
+ * FINISH (gpirt_acf_combine), in fp64, one thread per value, over the 2C half-chains c in the order chain 0 half 1, chain 0
+ * half 2, chain 1 half 1, ...: dbar = sum / H,
+ *   gamma_{k,c} = [s_k - dbar ((sum - tail_k) + (sum - head_k)) + (H - k) dbar^2] / H,
+ *   W = mean_c gamma_{0,c} H / (H - 1),  var+ = W (H - 1) / H + var(centre + dbar over c, ddof 1),
+ *   rho_0 = 1, rho_k = 1 - (W - mean_c gamma_{k,c}) / var+.
+ * Geyer's pairs P_j = rho_{2j} + rho_{2j+1}, 2j + 1 <= L: stop at the first P_j <= 0, else P_j <- min(P_j, P_{j-1}); tau = -1 +
+ * 2 sum P_j; lag_used = 2j + 1 of the last pair that entered (0: none); truncated = 1 when the lags ran out with P_j > 0;
+ * tau <- max(tau, 1 / log10 N), N = 2 C H; ess = N / tau, mcse = sqrt(var+ / ess), rhat = sqrt(var+ / W), rho1 = rho_1,
+ * mean = the mean over c of centre + dbar, sd = sqrt(var+).  constant = 1 when W = 0 or var+ = 0 or either is not finite:
+ * ess, tau, mcse, rhat and rho1 are then NaN, lag_used and truncated 0 and the value's acf column NaN.  acf[k][p] = rho_k.
+ * BLOCKS theta, beta, item_ll, resp_ll, total_ll: min_ess, max_tau, max_rhat over the values that are not NaN (NaN if none),
+ * n_truncated, n_nan (values whose ess is NaN).  worst: the `top` values with the smallest ess, ties to the lowest p; block -1
+ * and ess NaN where fewer values have an ess.
+ * REFLECTION.  A chain with sign -1 enters with theta's sum, head and tail negated, the beta slopes' sum, head, tail and centre
+ * negated; s and the log-likelihood series are untouched.  That is exactly the chain with every draw negated.
+ * Nothing is drawn: with the block on, the chain, the IRFs, R's stream position and every other block's state are bit for bit
+ * what they are without.  Device memory per state: 8 bytes x (7 (L + 1) P + 4 P), plus 8 (ceil(n / 256) m + ceil(m / 32) n). */
+#define GPIRT_ACF_THETA               1
+#define GPIRT_ACF_BETA                2
+#define GPIRT_ACF_LL                  4
+#define GPIRT_ACF_MAX_LAG             1024
+#define GPIRT_ACF_DEFAULT_LAG         256
+#define GPIRT_ACF_MAX_TOP             64
+/* the raw arrays of a state block, in the block's order (8-byte elements; the theta columns of the first four are int64) */
+#define GPIRT_ACF_S                   0       /* [2][L + 1][P] */
+#define GPIRT_ACF_SUM                 1       /* [2][P] */
+#define GPIRT_ACF_HEAD                2       /* [2][L + 1][P] */
+#define GPIRT_ACF_TAIL                3       /* [2][L + 1][P] */
+#define GPIRT_ACF_CENTRE              4       /* double [P] */
+#define GPIRT_ACF_NONFINITE           5       /* int64 [P] */
+#define GPIRT_ACF_RING                6       /* [L + 1][P]: d_t at slot (t - 1) mod (L + 1); theta's as int64 */
+#define GPIRT_ACF_NARRAYS             7
+/* per value */
+#define GPIRT_ACF_V_ESS               0
+#define GPIRT_ACF_V_TAU               1
+#define GPIRT_ACF_V_MCSE              2
+#define GPIRT_ACF_V_RHAT              3
+#define GPIRT_ACF_V_RHO1              4
+#define GPIRT_ACF_V_MEAN              5
+#define GPIRT_ACF_V_SD                6
+#define GPIRT_ACF_NVALUE              7
+#define GPIRT_ACF_F_LAG_USED          0
+#define GPIRT_ACF_F_TRUNCATED         1
+#define GPIRT_ACF_F_NONFINITE         2       /* summed over the chains */
+#define GPIRT_ACF_F_CONSTANT          3
+#define GPIRT_ACF_NFLAG               4
+/* per block */
+#define GPIRT_ACF_NBLOCK              5       /* theta, beta, item_ll, resp_ll, total_ll */
+#define GPIRT_ACF_B_MIN_ESS           0
+#define GPIRT_ACF_B_MAX_TAU           1
+#define GPIRT_ACF_B_MAX_RHAT          2
+#define GPIRT_ACF_NBSTAT              3
+#define GPIRT_ACF_C_TRUNCATED         0
+#define GPIRT_ACF_C_NAN               1
+#define GPIRT_ACF_NBCOUNT             2
+/* HOST pointers (NULL: not wanted). */
+typedef struct gpirt_acf {
+    int64_t    top;                            /* in: 1 .. GPIRT_ACF_MAX_TOP, the length of the worst_* arrays */
+    double*    value[GPIRT_ACF_NVALUE];        /* P each */
+    int64_t*   flag[GPIRT_ACF_NFLAG];          /* P each */
+    double*    acf;                            /* (L + 1) x P, value fastest */
+    int64_t*   worst_block;                    /* top: 0 theta, 1 beta, 2 item_ll, 3 resp_ll, 4 total_ll */
+    int64_t*   worst_index;                    /* top: the index inside the block */
+    double*    worst_ess;                      /* top */
+    double     block_stat[GPIRT_ACF_NBLOCK * GPIRT_ACF_NBSTAT];     /* out: [block][stat]; NaN for a block that is not tracked */
+    int64_t    block_count[GPIRT_ACF_NBLOCK * GPIRT_ACF_NBCOUNT];   /* out: [block][count] */
+    int64_t    n, m, parts, S, H, L, P, chains;                     /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_acf;
+/* gpirt_acf_check is the argument check alone (no device is touched): parts a non-empty subset of the three bits, H >= 4,
+ * max_lag 0 or 1 .. min(H - 1, GPIRT_ACF_MAX_LAG); each refusal says which.  L_out, P_out: may be NULL.
+ * Stage API.  acf_enable(parts, planned_draws, max_lag, on != 0) allocates and zeroes the state (a refused argument keeps the
+ * old state); on = 0 frees it.  acf_accumulate enters the CURRENT theta, beta, f and mu as the chain's next draw; one beyond
+ * the planned draws is GPIRT_E_ARG and says so.  acf_get copies one array by name to the host, `bytes` its exact size: "s",
+ * "sum", "head", "tail", "centre", "nonfinite", "ring", "counts" (int64: n, m, parts, S, H, L, P, draws) and "last" (double [P]:
+ * the values x_t of the last accumulate as they were read, before centring; what the log-likelihood pass is tested by).  acf_state returns the ONE device block (valid until acf_enable is called again or the sampler
+ * goes): a header of 16 int64 -- the tag 0x31464341 ("ACF1"), the layout version (1), n, m, parts, S, H, L, P, draws, 0 ... --
+ * then the raw arrays in the order above, each on a 16-byte boundary.  gpirt_acf_combine finishes `chains` such blocks of the
+ * same n, m, parts, S and L, each with all S draws in, on the device; signs: NULL (all +1) or `chains` values of +1 / -1. */
+int gpirt_acf_check(int64_t n, int64_t m, int parts, int64_t planned_draws, int64_t max_lag, int64_t* L_out, int64_t* P_out);
+int gpirt_sampler_acf_enable(gpirt_sampler_t s, int parts, int64_t planned_draws, int64_t max_lag, int on);
+int gpirt_sampler_acf_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_acf_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_acf_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out);
+
 /* ------------------------------------------------------ the chains with any of the analyses above, in one call -------- */
 /* What gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs: one struct per analysis, each NULL when not wanted, each
  * filled as its section above describes.  The chains are gpirt_mcmc_chains's whatever is asked for -- draws, IRFs, pooled, diag
