@@ -245,6 +245,34 @@ class PpcPerson(C.Structure):
                 ("n_scored", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# residual correlations (include/gpirt_hip.h GPIRT_RESID_*): the finished fields per pair (m x m), per item (m) and the scalars, in
+# order; the raw arrays of the state block with their dtypes and shapes ("p": m x m, "i": m, "g": 16 words); the last counted
+# draw's arrays of gpirt_sampler_ppc_resid_get ("c": n x m column-major, "d": 9 x n x m, "s": 8)
+RESID_PAIR_FIELDS = ("n_co", "rc_obs_mean", "rc_rep_mean", "rc_rep_sd", "ppp_rc", "ppp_rc_mid", "undefined")
+RESID_ITEM_FIELDS = ("infit_obs_mean", "infit_rep_mean", "infit_rep_sd", "ppp_infit", "ppp_infit_mid", "ss_obs_mean", "ss_rep_mean",
+                     "ppp_ss", "ppp_ss_mid")
+RESID_SCALARS = ("frob_obs_mean", "frob_rep_mean", "frob_rep_sd", "ppp_frob", "ppp_frob_mid", "max_obs_mean", "max_rep_mean", "ppp_max",
+                 "ppp_max_mid", "absmax_obs_mean", "absmax_rep_mean", "ppp_absmax", "ppp_absmax_mid")
+RESID_RAW = (("n_co_int", "i8", "p"), ("undefined_count", "u4", "p"), ("rc_ge", "u4", "p"), ("rc_gt", "u4", "p"),
+             ("rc_obs_sum", "f8", "p"), ("rc_rep_sum", "f8", "p"), ("rc_rep_sumsq", "f8", "p"),
+             ("ss_undefined", "u4", "i"), ("ss_ge", "u4", "i"), ("ss_gt", "u4", "i"), ("ss_obs_sum", "f8", "i"), ("ss_rep_sum", "f8", "i"),
+             ("global", "u8", "g"))
+RESID_LAST = (("d_obs", "i4", "c"), ("d_rep", "i4", "c"), ("w", "i4", "c"), ("digits", "i1", "d"), ("s_obs", "i8", "p"), ("s_rep", "i8", "p"),
+              ("v", "i8", "p"), ("r_obs", "f8", "p"), ("r_rep", "f8", "p"), ("stats", "f8", "s"))
+RESID_MAX_M, RESID_MAX_N, RESID_MAX_TOP, RESID_TAG = 4096, 65534, 64, 0x31445352
+
+
+class PpcResid(C.Structure):
+    """gpirt_ppc_resid (include/gpirt_hip.h): top, host pointers per output (NULL: not wanted), the scalars and the counters."""
+    _fields_ = [("top", C.c_int), ("reserved0", C.c_int), ("pair", C.POINTER(C.c_double) * len(RESID_PAIR_FIELDS)),
+                ("item", C.POINTER(C.c_double) * len(RESID_ITEM_FIELDS)), ("raw", C.c_void_p * len(RESID_RAW)),
+                ("worst_pairs", C.POINTER(C.c_int64)), ("worst_ppp_rc_mid", C.POINTER(C.c_double)),
+                ("worst_rc_obs_mean", C.POINTER(C.c_double)), ("worst_items", C.POINTER(C.c_int64)),
+                ("worst_ppp_ss_mid", C.POINTER(C.c_double)), ("scalar", C.c_double * len(RESID_SCALARS)),
+                ("n", C.c_int64), ("m", C.c_int64), ("resid_draws", C.c_int64), ("resid_skipped", C.c_int64),
+                ("global_undefined", C.c_int64), ("reserved", C.c_int64 * 4)]
+
+
 # rank posteriors (include/gpirt_hip.h gpirt_ranks)
 RANK_MAX_PIVOTS, RANK_MAX_PIVOTS_CLOSED, RANK_MAX_N = 16, 32, 16384
 
@@ -558,6 +586,10 @@ SIGNATURES = {
     "gpirt_sampler_ppc_person_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ppc_person_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_ppc_person_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcPerson)]),
+    "gpirt_sampler_ppc_resid_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ppc_resid_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ppc_resid_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ppc_resid_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(PpcResid)]),
     "gpirt_sampler_equate_enable": (_i32, [_vp, _vp, _vp, _i32]),
     "gpirt_sampler_equate_accumulate": (_i32, [_vp]),
     "gpirt_sampler_equate_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),

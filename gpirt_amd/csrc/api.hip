@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 122; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 123; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -199,6 +199,8 @@ int gpirt_version(void) { return 122; }     // 101: gpirt_options names kernel_f
                                             // 121: person fit of the PPC (ppc_person.hip: gpirt_sampler_ppc_person_*,
                                             //      gpirt_ppc_person_check, gpirt_ppc_person_combine)
                                             // 122: autocorrelation ESS (acf.hip: gpirt_acf_check, gpirt_sampler_acf_*, gpirt_acf_combine)
+                                            // 123: residual correlations of the PPC (ppc_resid.hip: gpirt_sampler_ppc_resid_*,
+                                            //      gpirt_ppc_resid_combine)
 
 const char* gpirt_last_error(void) { return g_err; }
 

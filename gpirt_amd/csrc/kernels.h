@@ -576,6 +576,46 @@ int64_t prs_state_words(const PrsState* p);
 int prs_get(hipStream_t stream, PrsState* p, const char* name, void* h_out, int64_t bytes);
 int prs_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_person* out);
 
+// ppc_resid.hip: the residual correlations (gpirt_sampler_ppc_resid_*), an add-on to a PPC state.  Its accumulators are ONE device
+// block of 8-byte words of their own: a header of RSD_HEADER_WORDS int64 (n, m, layout version, resid_draws, resid_skipped, item0,
+// 0, RSD_TAG -- the two counters are kept by resid_update_kernel), then the arrays of RsdLayout, pair (a, b) at [a m + b], every
+// array padded to 16 bytes.  Beside it: the 0 / 1 plane O8 (built once), two sets of the nine int8 digit planes (ctl[0] names
+// the set of the last counted draw; the terms kernel writes the other one), the per-draw tables S_obs, S_rep, V, r_obs, r_rep, the
+// items' partial sums, the last draw's global statistics and the control words ctl[0] = set, ctl[1] = this draw holds a NaN g.
+constexpr int RSD_LAYOUT_VERSION = 1;
+constexpr int RSD_HEADER_WORDS = 8;
+constexpr int64_t RSD_TAG = 0x31445352;               // "RSD1"
+constexpr int RSD_GLOBAL_WORDS = 16;
+constexpr int RSD_ITEM_PARTS = 10;                    // per item and draw: t, u, M+, M for the data and the replicate, both counts
+enum { RSD_N_CO, RSD_UNDEF, RSD_RC_GE, RSD_RC_GT, RSD_RC_OBS_SUM, RSD_RC_REP_SUM, RSD_RC_REP_SUMSQ,                     // m x m
+       RSD_SS_UNDEF, RSD_SS_GE, RSD_SS_GT, RSD_SS_OBS_SUM, RSD_SS_REP_SUM,                                                // m
+       RSD_GLOBAL, RSD_NARRAYS };
+static_assert(RSD_NARRAYS == GPIRT_RESID_NRAW, "gpirt_ppc_resid::raw");
+struct RsdLayout { int64_t off[RSD_NARRAYS]; int64_t bytes[RSD_NARRAYS]; int64_t words; };      // offsets in 8-byte words
+RsdLayout rsd_layout(int64_t m);
+struct RsdState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0;
+    int64_t iblocks = 0, ksteps = 0, plane = 0;       // the operands: item blocks of 32, k-steps of 32 respondents, bytes of one
+    uint64_t* block = nullptr;
+    signed char* O8 = nullptr;
+    signed char* dig = nullptr;                       // [set][d_obs, d_rep, w][digit] planes
+    int64_t *s_obs = nullptr, *s_rep = nullptr, *v = nullptr;          // 2 x m x m (two halves of the depth), m x m
+    double *r_obs = nullptr, *r_rep = nullptr;                         // m x m
+    double* item_part = nullptr;                                       // [RSD_ITEM_PARTS][m]
+    double* stats = nullptr;                                           // [8]
+    int* ctl = nullptr;
+    std::vector<void*> allocs;
+};
+int64_t rsd_state_words(int64_t m);
+int rsd_alloc(hipStream_t stream, RsdState* p, int64_t n, int64_t m, int64_t item0, const double* y);      // refusals: with a message
+void rsd_free(RsdState* p);
+// one draw: the digit planes from f, mu, y and the PPC's uniforms, the int8 products, then the decisions and the reductions
+int launch_rsd_accumulate(hipStream_t stream, RsdState* p, const double* f, const double* mu, const double* y, uint64_t seed,
+                          uint32_t iter);
+int rsd_get(hipStream_t stream, RsdState* p, const char* name, void* h_out, int64_t bytes);
+int rsd_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_resid* out);
+
 struct PpcState {
     bool on = false;
     int64_t n = 0, m = 0, item0 = 0, draws = 0, stride = 0;
@@ -589,6 +629,7 @@ struct PpcState {
     DifState dif;                                     // the group-wise item fit (ppc_dif.hip; on == false: off)
     PpsState scores;                                  // the score-based checks (ppc_scores.hip; on == false: off)
     PrsState person;                                  // the person fit (ppc_person.hip; on == false: off)
+    RsdState resid;                                   // the residual correlations (ppc_resid.hip; on == false: off)
     std::vector<void*> allocs;
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written

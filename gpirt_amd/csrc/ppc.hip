@@ -362,6 +362,7 @@ void ppc_free(PpcState* s)
     dif_free(&s->dif);
     pps_free(&s->scores);
     prs_free(&s->person);
+    rsd_free(&s->resid);
     for (void* p : s->allocs) hipFree(p);
     *s = PpcState{};
 }
@@ -406,6 +407,7 @@ int launch_ppc_accumulate(hipStream_t st, PpcState* s, const double* f, const do
     if (s->dif.on) GP_TRY(launch_dif_accumulate(st, &s->dif, f, mu, y, seed, iter, theta));     // (ppc_dif.hip: launches of its own)
     if (s->scores.on) GP_TRY(launch_pps_accumulate(st, &s->scores, f, mu, y, seed, iter));       // (ppc_scores.hip: likewise)
     if (s->person.on) GP_TRY(launch_prs_accumulate(st, &s->person, f, mu, y, seed, iter));       // (ppc_person.hip: likewise)
+    if (s->resid.on) GP_TRY(launch_rsd_accumulate(st, &s->resid, f, mu, y, seed, iter));         // (ppc_resid.hip: likewise)
     return 0;
 }
 

@@ -1817,6 +1817,56 @@ int gpirt_ppc_person_combine(gpirt_handle_t h, int chains, const void* const* d_
     return prs_combine(h, chains, d_states, out);
 }
 
+// ---- residual correlations (ppc_resid.hip): an add-on to the PPC state ---------------------------------------------------------
+static int resid_needs_on(gpirt_sampler_t s)
+{
+    if (s->ppc.on && s->ppc.resid.on) return 0;
+    set_error("the residual correlations are not enabled (gpirt_sampler_ppc_resid_enable)");
+    return GPIRT_E_ARG;
+}
+
+int gpirt_sampler_ppc_resid_enable(gpirt_sampler_t s, int top)
+{
+    GP_ARG(s && s->initialised);
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // a kernel still running on the old accumulators
+    rsd_free(&s->ppc.resid);
+    if (top == 0) return 0;
+    GP_TRY(ppc_needs_on(s));
+    if (top < 1 || top > GPIRT_RESID_MAX_TOP) {
+        set_error("residual PPC: top = %d is outside 1..%d", top, GPIRT_RESID_MAX_TOP);
+        return GPIRT_E_ARG;
+    }
+    if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
+        set_error("the residual correlations are not offered for item shards (a pair's items may lie on two ranks)");
+        return GPIRT_E_ARG;
+    }
+    const int rc = rsd_alloc(s->h->stream, &s->ppc.resid, s->n, s->m, s->opt.item0, s->y);
+    if (rc) rsd_free(&s->ppc.resid);
+    return rc;
+}
+
+int gpirt_sampler_ppc_resid_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    GP_TRY(resid_needs_on(s));
+    return rsd_get(s->h->stream, &s->ppc.resid, name, h_out, bytes);
+}
+
+int gpirt_sampler_ppc_resid_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    GP_TRY(resid_needs_on(s));
+    GP_HIP(hipStreamSynchronize(s->h->stream));        // the counters in the header are the kernel's
+    *d_state = s->ppc.resid.block;
+    *bytes = rsd_state_words(s->m) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ppc_resid_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_resid* out)
+{
+    return rsd_combine(h, chains, d_states, out);
+}
+
 // ---- rank posteriors (ranks.hip) on the stage API -----------------------------------------------------------------------
 static int rank_needs_on(gpirt_sampler_t s)
 {

@@ -266,6 +266,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the person fit is not offered for item shards "
                          "(a respondent's pattern runs over all items, and each rank holds its own columns)")
 
+    def ppc_resid_enable(self, top=20, on=True):
+        raise ValueError("ShardedSampler: the residual correlations are not offered for item shards "
+                         "(a pair's items may lie on two ranks, and each rank holds its own columns)")
+
     # -- rank posteriors (gpirt_amd.ranks): theta is replicated on every rank, so each rank's engine holds the same ranks
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         self.engine.rank_enable(on, pivots, pairwise)

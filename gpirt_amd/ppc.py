@@ -18,7 +18,8 @@ E, V and X2 in np.longdouble, the chi-square decisions as (lo, hi) brackets from
 the replicates from stored g draws.
 The group-wise item fit ("group-wise item fit" in the header; csrc/ppc_dif.hip) is the third add-on and the score-based checks
 ("score-based PPC" in the header; csrc/ppc_scores.hip) the fourth, the person fit ("person fit in the PPC"; csrc/ppc_person.hip)
-the fifth: see their sections at the end of this module.
+the fifth, the residual correlations ("residual correlations in the PPC"; csrc/ppc_resid.hip) the sixth: see their sections at the
+end of this module.
 ShardedSampler is not covered: the respondents' statistics would need one all-reduce per draw.  The keying of the
 uniforms by the global item index keeps that possible.
 """
@@ -1861,3 +1862,344 @@ def person_from_draws(y, g_draws, seed, iters, order=None, cuts=None, top=DEFAUL
         reps.append(ob & (u < p))
     rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
     return person_from_rep(y, g_draws, rep, order, cuts, top), gap
+
+
+# ---------------------------------------------------------------------------------- residual correlations: device ---
+DEFAULT_RESID_TOP = 20
+RESID_UNIT = 4194304.0          # 2^22: the terms are integers in units of 2^-22
+_RS_DTYPES = {"u8": np.uint64, "f8": np.float64, "u4": np.uint32, "i8": np.int64, "i4": np.int32, "i1": np.int8}
+
+
+def check_resid_top(top) -> int:
+    t = int(top)
+    if t != top or not 1 <= t <= _lib.RESID_MAX_TOP:
+        raise ValueError(f"resid: top must be an integer in 1..{_lib.RESID_MAX_TOP}")
+    return t
+
+
+def _resid_shape(kind, n, m):
+    return {"p": (m, m), "i": (m,), "g": (16,), "c": (n, m), "d": (9, m, n), "s": (8,)}[kind]
+
+
+def resid_field(name: str, n: int, m: int):
+    """(shape, dtype, memory order) of the array gpirt_sampler_ppc_resid_get returns for `name` ("digits" comes as 9 x m x n and is
+    transposed by the caller); an unknown name gets the library's refusal through a 1-element buffer."""
+    if name in _lib.RESID_PAIR_FIELDS:
+        return (m, m), np.float64, "C"
+    if name in _lib.RESID_ITEM_FIELDS:
+        return (m,), np.float64, "C"
+    if name == "scalars":
+        return (len(_lib.RESID_SCALARS),), np.float64, "C"
+    if name == "counts":
+        return (3,), np.int64, "C"
+    for nm, dt, kind in _lib.RESID_RAW + _lib.RESID_LAST:
+        if nm == name:
+            return _resid_shape(kind, n, m), _RS_DTYPES[dt], "F" if kind == "c" else "C"
+    return (1,), np.float64, "C"
+
+
+def resid_struct(m: int, top=DEFAULT_RESID_TOP):
+    """A gpirt_ppc_resid with host arrays for every output, and those arrays (kept alive by the caller)."""
+    p = _lib.PpcResid()
+    p.top = check_resid_top(top)
+    arr = {}
+    for k, name in enumerate(_lib.RESID_PAIR_FIELDS):
+        arr[name] = np.empty((m, m))
+        p.pair[k] = arr[name].ctypes.data_as(_dp)
+    for k, name in enumerate(_lib.RESID_ITEM_FIELDS):
+        arr[name] = np.empty(m)
+        p.item[k] = arr[name].ctypes.data_as(_dp)
+    for k, (name, dt, kind) in enumerate(_lib.RESID_RAW):
+        arr[name] = np.empty(_resid_shape(kind, 0, m), dtype=_RS_DTYPES[dt])
+        p.raw[k] = arr[name].ctypes.data
+    arr["worst_pairs"] = np.empty((p.top, 2), dtype=np.int64)
+    p.worst_pairs = arr["worst_pairs"].ctypes.data_as(C.POINTER(C.c_int64))
+    arr["worst_items"] = np.empty(p.top, dtype=np.int64)
+    p.worst_items = arr["worst_items"].ctypes.data_as(C.POINTER(C.c_int64))
+    for name in ("worst_ppp_rc_mid", "worst_rc_obs_mean", "worst_ppp_ss_mid"):
+        arr[name] = np.empty(p.top)
+        setattr(p, name, arr[name].ctypes.data_as(_dp))
+    return p, arr
+
+
+def resid_result(p, arr) -> dict:
+    """The dict of Sampler.ppc_resid() and resid_combine(): every pair array (m x m, pair (a, b) at [a, b]), item array (m) and
+    raw array of the header by name, the scalars as floats, "worst" (dict: pairs (top x 2), ppp_rc_mid, rc_obs_mean), "worst_items"
+    (dict: items, ppp_ss_mid) and the counters."""
+    out = {k: v for k, v in arr.items() if not k.startswith("worst_")}
+    out.update({k: float(p.scalar[i]) for i, k in enumerate(_lib.RESID_SCALARS)})
+    out["worst"] = dict(pairs=arr["worst_pairs"], ppp_rc_mid=arr["worst_ppp_rc_mid"], rc_obs_mean=arr["worst_rc_obs_mean"])
+    out["worst_items"] = dict(items=arr["worst_items"], ppp_ss_mid=arr["worst_ppp_ss_mid"])
+    out.update(n=int(p.n), m=int(p.m), resid_draws=int(p.resid_draws), resid_skipped=int(p.resid_skipped),
+               global_undefined=int(p.global_undefined))
+    return out
+
+
+def resid_state_header(state) -> dict:
+    """The 8 int64 header words of a residual-correlation state block (a device tensor)."""
+    w = state[:8].cpu().numpy().view(np.int64)
+    return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), resid_draws=int(w[3]), resid_skipped=int(w[4]), item0=int(w[5]),
+                tag=int(w[7]))
+
+
+def resid_combine(handle, states, top=DEFAULT_RESID_TOP) -> dict:
+    """gpirt_ppc_resid_combine over the state blocks `states` (device tensors, or Samplers with ppc_resid_enable() on, all on
+    handle's device): the integers added, the double sums added in chain order.  Blocks with another n, m, item0 or n_co are
+    refused."""
+    lib = _lib.load()
+    tensors = [s.ppc_resid_state() if hasattr(s, "ppc_resid_state") else s for s in states]
+    m = resid_state_header(tensors[0])["m"]
+    p, arr = resid_struct(m if 2 <= m <= _lib.RESID_MAX_M else 2, top)
+    nc = len(tensors)
+    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+    check(lib.gpirt_ppc_resid_combine(handle.ptr, nc, ptrs, C.byref(p)))
+    return resid_result(p, arr)
+
+
+# ----------------------------------------------------------------------------------- residual correlations: NumPy ---
+def resid_digits(x):
+    """x (integers in [-2^22, 2^22]) as three balanced base-256 digits: x = d0 + 256 d1 + 65536 d2, d0 and d1 in [-128, 127],
+    |d2| <= 64 -- the int8 planes of the device."""
+    x = np.asarray(x, dtype=np.int64)
+    d0 = ((x + 128) & 255) - 128
+    x1 = (x - d0) >> 8
+    d1 = ((x1 + 128) & 255) - 128
+    return d0, d1, (x1 - d1) >> 8
+
+
+def resid_join(d0, d1, d2):
+    return np.asarray(d0, dtype=np.int64) + 256 * np.asarray(d1, dtype=np.int64) + 65536 * np.asarray(d2, dtype=np.int64)
+
+
+def resid_terms(y, g, rep):
+    """(dt_obs, dt_rep, wt), int64 n x m in units of 2^-22, from y (NaN = missing), g = f + mu of one draw and the replicate
+    (rep != 0 where yrep = +1): d = +q where the answer is +1, -p where it is -1, w = p q, each rounded once by rint; 0 in the
+    unobserved cells, whatever g holds there.  p and q by the PPC's arithmetic (g = +-inf gives exactly 0 and 1)."""
+    y = np.asarray(y, dtype=np.float64)
+    obs = ~np.isnan(y)
+    g = np.where(obs, np.asarray(g, dtype=np.float64), 0.0)
+    e = np.exp(-np.abs(g))
+    big, small = 1.0 / (1.0 + e), e / (1.0 + e)
+    p, q = np.where(g >= 0, big, small), np.where(g >= 0, small, big)
+    fix = lambda v: np.where(obs, np.rint(v * RESID_UNIT), 0.0).astype(np.int64)            # noqa: E731
+    return fix(np.where(y > 0, q, -p)), fix(np.where(np.asarray(rep) != 0, q, -p)), fix(p * q)
+
+
+def resid_tables(dt_obs, dt_rep, wt, O):
+    """The exact tables of one draw: S_obs = dt_obs^T dt_obs, S_rep = dt_rep^T dt_rep (units of 2^-44), V = wt^T O (units of
+    2^-22), int64 m x m."""
+    a, b, w, O = (np.asarray(x, dtype=np.int64) for x in (dt_obs, dt_rep, wt, O))
+    return dict(s_obs=a.T @ a, s_rep=b.T @ b, v=w.T @ O)
+
+
+def resid_lane_sum(x):
+    """The sum over the last axis of non-negative terms in the device's order: lane l of 64 adds the entries l, l + 64, ... in
+    ascending order, then the 64 lane sums are added in lane order (np.cumsum adds strictly in order)."""
+    x = np.asarray(x, dtype=np.float64)
+    pad = (-x.shape[-1]) % 64
+    x = np.concatenate([x, np.zeros(x.shape[:-1] + (pad,))], axis=-1).reshape(x.shape[:-1] + (-1, 64))
+    return np.cumsum(np.cumsum(x, axis=-2)[..., -1, :], axis=-1)[..., -1]
+
+
+def resid_draw_stats(tables, n_co) -> dict:
+    """One draw's statistics from its integer tables, in the header's arithmetic: r_obs, r_rep (m x m: the correlations, the infit
+    on the diagonal, NaN where n_co = 0 or V[a, b] V[b, a] = 0), the integer decisions ge, gt (S_rep >= / > S_obs), live and
+    defined (bool m x m), t_obs, t_rep, t_count per item and stats = (Q, M+, M of the data, Q, M+, M of the replicate, the defined
+    pairs a < b, 0)."""
+    So, Sr, V = (np.asarray(tables[k], dtype=np.int64) for k in ("s_obs", "s_rep", "v"))
+    m = So.shape[0]
+    eye = np.eye(m, dtype=bool)
+    live = np.asarray(n_co) > 0
+    defined = live & (V != 0) & (V.T != 0)
+    Vd = V.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        den = np.where(eye, Vd * RESID_UNIT, np.sqrt(Vd * Vd.T) * RESID_UNIT)
+        r_obs = np.where(defined, So.astype(np.float64) / den, np.nan)
+        r_rep = np.where(defined, Sr.astype(np.float64) / den, np.nan)
+    off = defined & ~eye
+    up = off & np.triu(np.ones((m, m), dtype=bool), 1)
+    sq = lambda r, mask: np.where(mask, r * r, 0.0)            # noqa: E731
+    t_obs, t_rep = resid_lane_sum(sq(r_obs, off)), resid_lane_sum(sq(r_rep, off))
+    Q_obs, Q_rep = resid_lane_sum(resid_lane_sum(sq(r_obs, up))), resid_lane_sum(resid_lane_sum(sq(r_rep, up)))
+    big = lambda r: float(np.max(r[up])) if up.any() else -np.inf            # noqa: E731
+    stats = np.array([Q_obs, big(r_obs), big(np.abs(r_obs)), Q_rep, big(r_rep), big(np.abs(r_rep)), float(up.sum()), 0.0])
+    return dict(r_obs=r_obs, r_rep=r_rep, ge=defined & (Sr >= So), gt=defined & (Sr > So), live=live, defined=defined,
+                t_obs=t_obs, t_rep=t_rep, t_count=off.sum(axis=1), stats=stats)
+
+
+def _resid_finish(so, sr, sq, ge, gt, D):
+    """obs_mean, rep_mean, rep_sd, ppp, ppp_mid from the sums and counts over D draws, in the host code's arithmetic"""
+    so, sr, sq, ge, gt = (np.asarray(x, dtype=np.float64) for x in (so, sr, sq, ge, gt))
+    D = np.asarray(D, dtype=np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dD = np.where(D >= 1, D, 1).astype(np.float64)
+        ok = D >= 1
+        mean = sr / dD
+        var = (sq - sr * mean) / np.where(D >= 2, D - 1, 1).astype(np.float64)
+        sd = np.where(var > 0.0, np.sqrt(np.where(var > 0.0, var, 0.0)), 0.0)
+        nanif = lambda v, good: np.where(good, v, np.nan)            # noqa: E731
+        return (nanif(so / dD, ok), nanif(mean, ok), nanif(sd, D >= 2), nanif(ge / dD, ok), nanif((ge + gt) / (2.0 * dD), ok))
+
+
+def resid_worst(ppp_rc_mid, rc_obs_mean, top=DEFAULT_RESID_TOP) -> dict:
+    """The `top` pairs a < b with the smallest ppp_rc_mid, ties to the lowest (a, b), NaN never listed; padded with -1 / NaN."""
+    m = ppp_rc_mid.shape[0]
+    ia, ib = np.triu_indices(m, 1)
+    mid = ppp_rc_mid[ia, ib]
+    ok = ~np.isnan(mid)
+    ia, ib, mid = ia[ok], ib[ok], mid[ok]
+    order = np.argsort(mid, kind="stable")[:top]
+    w = dict(pairs=np.full((top, 2), -1, dtype=np.int64), ppp_rc_mid=np.full(top, np.nan), rc_obs_mean=np.full(top, np.nan))
+    w["pairs"][:len(order), 0], w["pairs"][:len(order), 1] = ia[order], ib[order]
+    w["ppp_rc_mid"][:len(order)] = mid[order]
+    w["rc_obs_mean"][:len(order)] = rc_obs_mean[ia[order], ib[order]]
+    return w
+
+
+def resid_worst_items(ppp_ss_mid, top=DEFAULT_RESID_TOP) -> dict:
+    """The `top` items with the smallest ppp_ss_mid, ties to the lowest index, NaN never listed; padded with -1 / NaN."""
+    idx = np.flatnonzero(~np.isnan(ppp_ss_mid))
+    order = idx[np.argsort(ppp_ss_mid[idx], kind="stable")[:top]]
+    w = dict(items=np.full(top, -1, dtype=np.int64), ppp_ss_mid=np.full(top, np.nan))
+    w["items"][:len(order)] = order
+    w["ppp_ss_mid"][:len(order)] = ppp_ss_mid[order]
+    return w
+
+
+def resid_from_tables(draws, n_co, top=DEFAULT_RESID_TOP, skipped=0, n=0, chains=None) -> dict:
+    """resid_result's dict from the integer tables of the COUNTED draws (a list of dicts s_obs, s_rep, v: resid_tables' or the
+    device's own) and n_co = O^T O: every accumulator grows draw by draw as the device's does, every finished value by the host
+    code's arithmetic.  chains: the number of draws of each pooled chain, in chain order (None: one chain); the chains' sums are
+    formed apart and added in chain order, as gpirt_ppc_resid_combine adds them."""
+    top = check_resid_top(top)
+    n_co = np.asarray(n_co, dtype=np.int64)
+    m = n_co.shape[0]
+    chains = [len(draws)] if chains is None else list(chains)
+    assert sum(chains) == len(draws)
+    zf = lambda *s: np.zeros(s)            # noqa: E731
+    zi = lambda *s: np.zeros(s, dtype=np.int64)            # noqa: E731
+    tot = None
+    at = 0
+    for count in chains:
+        a = dict(undefined_count=zi(m, m), rc_ge=zi(m, m), rc_gt=zi(m, m), rc_obs_sum=zf(m, m), rc_rep_sum=zf(m, m),
+                 rc_rep_sumsq=zf(m, m), ss_undefined=zi(m), ss_ge=zi(m), ss_gt=zi(m), ss_obs_sum=zf(m), ss_rep_sum=zf(m),
+                 gd=zf(7), gi=zi(7))
+        for tables in draws[at:at + count]:
+            d = resid_draw_stats(tables, n_co)
+            df = d["defined"]
+            a["undefined_count"] += d["live"] & ~df
+            a["rc_ge"] += d["ge"]
+            a["rc_gt"] += d["gt"]
+            a["rc_obs_sum"] = np.where(df, a["rc_obs_sum"] + np.where(df, d["r_obs"], 0.0), a["rc_obs_sum"])
+            a["rc_rep_sum"] = np.where(df, a["rc_rep_sum"] + np.where(df, d["r_rep"], 0.0), a["rc_rep_sum"])
+            a["rc_rep_sumsq"] = np.where(df, a["rc_rep_sumsq"] + np.where(df, d["r_rep"] * d["r_rep"], 0.0), a["rc_rep_sumsq"])
+            has = d["t_count"] > 0
+            a["ss_undefined"] += ~has
+            a["ss_obs_sum"] = np.where(has, a["ss_obs_sum"] + d["t_obs"], a["ss_obs_sum"])
+            a["ss_rep_sum"] = np.where(has, a["ss_rep_sum"] + d["t_rep"], a["ss_rep_sum"])
+            a["ss_ge"] += has & (d["t_rep"] >= d["t_obs"])
+            a["ss_gt"] += has & (d["t_rep"] > d["t_obs"])
+            st = d["stats"]
+            if st[6] == 0:
+                a["gi"][6] += 1
+                continue
+            a["gd"] += np.array([st[0], st[3], st[3] * st[3], st[1], st[4], st[2], st[5]])
+            for k in range(3):
+                a["gi"][2 * k] += st[3 + k] >= st[k]
+                a["gi"][2 * k + 1] += st[3 + k] > st[k]
+        at += count
+        tot = a if tot is None else {k: tot[k] + a[k] for k in a}
+    S = len(draws)
+    eye = np.eye(m, dtype=bool)
+    live = n_co > 0
+    cell = _resid_finish(tot["rc_obs_sum"], tot["rc_rep_sum"], tot["rc_rep_sumsq"], tot["rc_ge"], tot["rc_gt"], S - tot["undefined_count"])
+    pair_ok = live & ~eye
+    out = {"n_co": n_co.astype(np.float64)}
+    for k, v in zip(("rc_obs_mean", "rc_rep_mean", "rc_rep_sd", "ppp_rc", "ppp_rc_mid"), cell):
+        out[k] = np.where(pair_ok, v, np.nan)
+    out["undefined"] = np.where(pair_ok, tot["undefined_count"], np.nan).astype(np.float64)
+    item_ok = np.diag(live)
+    for k, v in zip(("infit_obs_mean", "infit_rep_mean", "infit_rep_sd", "ppp_infit", "ppp_infit_mid"), cell):
+        out[k] = np.where(item_ok, np.diag(v), np.nan)
+    ss = _resid_finish(tot["ss_obs_sum"], tot["ss_rep_sum"], 0.0 * tot["ss_rep_sum"], tot["ss_ge"], tot["ss_gt"], S - tot["ss_undefined"])
+    for k, v in zip(("ss_obs_mean", "ss_rep_mean", None, "ppp_ss", "ppp_ss_mid"), ss):
+        if k:
+            out[k] = np.where(item_ok, v, np.nan)
+    gd, gi = tot["gd"], tot["gi"]
+    D = S - int(gi[6])
+    fr = _resid_finish(gd[0], gd[1], gd[2], gi[0], gi[1], D)
+    mx = _resid_finish(gd[3], gd[4], 0.0, gi[2], gi[3], D)
+    am = _resid_finish(gd[5], gd[6], 0.0, gi[4], gi[5], D)
+    sc = (fr[0], fr[1], fr[2], fr[3], fr[4], mx[0], mx[1], mx[3], mx[4], am[0], am[1], am[3], am[4])
+    out.update({k: float(v) for k, v in zip(_lib.RESID_SCALARS, sc)})
+    out["n_co_int"] = n_co.copy()
+    for name, dt, _ in _lib.RESID_RAW[1:-1]:
+        out[name] = tot[name].astype(_RS_DTYPES[dt])
+    glob = np.zeros(16, dtype=np.uint64)
+    glob[:7] = gd.view(np.uint64)
+    glob[7:14] = gi.astype(np.uint64)
+    out["global"] = glob
+    out["worst"] = resid_worst(out["ppp_rc_mid"], out["rc_obs_mean"], top)
+    out["worst_items"] = resid_worst_items(out["ppp_ss_mid"], top)
+    out.update(n=int(n), m=m, resid_draws=S, resid_skipped=int(skipped), global_undefined=int(gi[6]))
+    return out
+
+
+def resid_from_rep(y, g_draws, rep_draws, top=DEFAULT_RESID_TOP) -> dict:
+    """The header's residual correlations from stored draws: y (n x m; NaN = missing), g_draws (S, n, m) the draws of g = f +
+    mu, rep_draws (S, n, m) with rep != 0 where yrep = +1.  A draw with a NaN g in an observed cell is skipped whole
+    (resid_skipped).  Steps: resid_terms, resid_tables (int64 matrix products), resid_draw_stats, resid_from_tables."""
+    y = np.asarray(y, dtype=np.float64)
+    n, m = y.shape
+    obs = ~np.isnan(y)
+    O = obs.astype(np.int64)
+    draws, skipped = [], 0
+    for g, rep in zip(np.asarray(g_draws, dtype=np.float64), np.asarray(rep_draws)):
+        if np.isnan(g[obs]).any():
+            skipped += 1
+            continue
+        draws.append(resid_tables(*resid_terms(y, g, rep), O))
+    return resid_from_tables(draws, O.T @ O, top, skipped, n)
+
+
+def resid_from_draws(y, g_draws, seed, iters, top=DEFAULT_RESID_TOP, item0=0):
+    """resid_from_rep over the replicates of stored draws: rep = [u < plogis(g)] with replicate_uniforms' u at the
+    completed-iteration counters `iters`.  Returns (result, min |u - p| over the observed cells): a cell that close to its uniform
+    may replicate either way under another evaluation of plogis."""
+    y = np.asarray(y, dtype=np.float64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    n, m = y.shape
+    obs = ~np.isnan(y)
+    reps, gap = [], np.inf
+    for s, it in enumerate(iters):
+        with np.errstate(invalid="ignore"):
+            p, _ = _plogis(np.where(obs, g_draws[s], 0.0))
+        u = replicate_uniforms(seed, int(it), n, m, item0)
+        if obs.any() and not np.isnan(p[obs]).any():
+            gap = min(gap, float(np.abs(u - p)[obs].min()))
+        reps.append(obs & (u < p))
+    rep = np.stack(reps) if reps else np.zeros((0, n, m), dtype=bool)
+    return resid_from_rep(y, g_draws, rep, top), gap
+
+
+def resid_contrasts(result, k=5) -> dict:
+    """The PCAR first-contrast view of a residual-correlation result (host only): the k largest eigenvalues and their vectors
+    of rc_obs_mean with the diagonal set to 1, by numpy.linalg.eigh.  Items whose row holds a NaN off the diagonal are dropped one
+    at a time, the item with the most NaNs first (ties to the highest index), and reported.  Returns dict(values (k,), vectors
+    (kept x k), items (the kept items' indices), dropped).  Descriptive only: it has NO p-value -- the posterior predictive tests
+    of the same matrix are ppp_frob_mid, ppp_max_mid and ppp_absmax_mid."""
+    R = np.array(result["rc_obs_mean"], dtype=np.float64)
+    m = R.shape[0]
+    np.fill_diagonal(R, 1.0)
+    keep = np.arange(m)
+    while keep.size:
+        bad = np.isnan(R[np.ix_(keep, keep)]).sum(axis=1)
+        if not bad.any():
+            break
+        keep = np.delete(keep, np.flatnonzero(bad == bad.max())[-1])
+    dropped = np.setdiff1d(np.arange(m), keep)
+    k = int(min(k, keep.size))
+    if k < 1:
+        return dict(values=np.zeros(0), vectors=np.zeros((0, 0)), items=keep, dropped=dropped)
+    w, v = np.linalg.eigh(R[np.ix_(keep, keep)])
+    return dict(values=w[::-1][:k].copy(), vectors=v[:, ::-1][:, :k].copy(), items=keep, dropped=dropped)

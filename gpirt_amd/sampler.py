@@ -1155,6 +1155,51 @@ class Sampler:
         from . import ppc as P
         return P.person_combine(self.handle, [self], top=getattr(self, "_person_top", P.DEFAULT_PERSON_TOP) if top is None else top)
 
+    # -- residual correlations inside the PPC (include/gpirt_hip.h gpirt_sampler_ppc_resid_*, gpirt_amd.ppc)
+    def ppc_resid_enable(self, top=20, on=True):
+        """Allocate and zero the residual-correlation accumulators on a sampler whose ppc_enable is on and form O and n_co: from
+        then on every ppc_accumulate also adds that draw's residual correlations of every item pair, every item's infit and
+        share in the dependence, and the global statistics Q, M+ and M, for the data and the replicate.  top (1..64): how many
+        pairs and items ppc_resid() lists as worst.  on=False frees the state.  Stage API only: gpirtMCMC has no keyword for it."""
+        if not on:
+            check(self.lib.gpirt_sampler_ppc_resid_enable(self._s, 0))
+            return
+        top = int(top) if int(top) == top and top != 0 else -1          # (0 frees the state in C; the library names the fault)
+        check(self.lib.gpirt_sampler_ppc_resid_enable(self._s, top))
+        self._resid_top = top
+
+    def ppc_resid_get(self, name: str) -> np.ndarray:
+        """One array by name: a finished field (_lib.RESID_PAIR_FIELDS: float64 m x m; RESID_ITEM_FIELDS: m), "scalars" (float64,
+        13, in _lib.RESID_SCALARS' order), a raw array of _lib.RESID_RAW, counts (int64: resid_draws, resid_skipped,
+        global_undefined) and, of the last counted draw, the arrays of _lib.RESID_LAST.  Pair (a, b) is at [a, b]; d_obs, d_rep
+        and w are n x m, digits is 9 x n x m.  An unknown name is refused by the library."""
+        from . import ppc as P
+        shape, dtype, order = P.resid_field(name, self.n, self.m)
+        out = np.empty(shape, dtype=dtype, order=order)
+        check(self.lib.gpirt_sampler_ppc_resid_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        return out.transpose(0, 2, 1) if name == "digits" else out
+
+    def ppc_resid_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the residual-correlation accumulators: what
+        gpirt_amd.ppc.resid_combine pools; copy it anywhere to combine it there."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(self.lib.gpirt_sampler_ppc_resid_state(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def ppc_resid(self, top=None) -> dict:
+        """Every finished output of this sampler's residual-correlation accumulators (gpirt_amd.ppc.resid_result's shape):
+        gpirt_ppc_resid_combine over its own state; top defaults to ppc_resid_enable's."""
+        from . import ppc as P
+        return P.resid_combine(self.handle, [self], top=getattr(self, "_resid_top", P.DEFAULT_RESID_TOP) if top is None else top)
+
     # -- rank posteriors accumulated on the device (include/gpirt_hip.h gpirt_sampler_rank_*, gpirt_amd.ranks)
     def rank_enable(self, on=True, pivots="median", pairwise=False):
         """Allocate and zero the rank accumulators for `pivots` ("median" and / or positions in 1..n, at most 16; the

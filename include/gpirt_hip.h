@@ -1479,6 +1479,134 @@ int gpirt_sampler_ppc_person_get(gpirt_sampler_t s, const char* name, void* h_ou
 int gpirt_sampler_ppc_person_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_ppc_person_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_person* out);
 
+/* ------------------------------------------------- residual correlations in the PPC: local dependence, infit, global tests ------- */
+/* Is one dimension enough, as a single test (library version 123)?  The pairs section returns m (m - 1) / 2 p-values and nothing
+ * that sums them up, and its odds ratio weighs every co-observed respondent alike.  This sixth add-on forms, per draw, the
+ * residual correlation of every item pair (Yen's Q3 with the model variance as the scale), the infit mean square of every item
+ * (the diagonal of the same products), each item's share t_a in the dependence and three global statistics -- the sum of squared
+ * residual correlations Q, the largest correlation M+ and the largest absolute one M -- for the data and for that draw's
+ * replicate, and accumulates the comparisons.  Enabled on a sampler whose ppc_enable is on; it accumulates inside the same
+ * ppc_accumulate call.  2 <= m <= GPIRT_RESID_MAX_M = 4096, n <= GPIRT_RESID_MAX_N = 65534; item shards stay refused.
+ * Per draw, with g = f + mu, over the observed cells (O = the 0 / 1 observed matrix; an unobserved cell is 0 in all three terms):
+ *   e = exp(-|g|);  p = 1 / (1 + e), q = e / (1 + e) for g >= 0, p = e / (1 + e), q = 1 / (1 + e) for g < 0 (the PPC's own
+ *   arithmetic: p is 1 / (1 + exp(-g)) and q is 1 / (1 + exp(+g)), each formed on its own; +-inf gives exactly 0 and 1)
+ *   d_obs = +q where y = +1, -p where y = -1;   d_rep = the same with yrep = +1 if u < p, else -1, u the PPC's uniform
+ *   item_uniform(seed, iter, GPIRT_ST_PPC, item0 + j, i): the PPC's replicate bit for bit, nothing else is drawn (at g = +-inf,
+ *   where the PPC itself counts the item's draw out, the same rule gives yrep = +-1);   w = p q
+ *   dt = rint(d 2^22) in [-2^22, 2^22], wt = rint(w 2^22) in [0, 2^20]: every term rounded ONCE, to units of 2^-22.
+ * Each term is split in three balanced base-256 digits (d0, d1 in [-128, 127], |d2| <= 64) held as int8 planes in the operand
+ * layout of the pairs section; the nine digit-plane products per statistic run on the int8 matrix cores (a product is below
+ * 65534 x 128 x 128 < 2^31) and are joined with the weights 256^(u + v) into exact int64 (|S| <= 65534 x 2^44 < 2^61):
+ *   S_obs[a, b] = sum_i dt_obs[i, a] dt_obs[i, b],  S_rep likewise (symmetric, units of 2^-44),
+ *   V[a, b] = sum_i wt[i, a] O[i, b] (NOT symmetric, units of 2^-22),  n_co = O^T O once at enable.
+ * Per COUNTED draw and ordered pair (a, b), a != b, with n_co > 0 (pair (a, b) at [a m + b]):
+ *   V[a, b] V[b, a] = 0: undefined_count += 1 and the pair is left out of every sum of this draw, data and replicate alike;
+ *   otherwise r = (double)S / (sqrt((double)V[a, b] * (double)V[b, a]) * 4194304.0) for S_obs and S_rep (conversion, product,
+ *   square root, product, division: in this order),  rc_obs_sum += r_obs, rc_rep_sum += r_rep, rc_rep_sumsq += r_rep r_rep,
+ *   rc_ge / rc_gt += [S_rep >= / > S_obs]: both share the positive denominator, so the comparison is made on the integers.
+ * The DIAGONAL cell (a, a) of the same seven arrays holds item a's infit: undefined when V[a, a] = 0, otherwise
+ *   infit = (double)S[a, a] / ((double)V[a, a] * 4194304.0) in place of r, the comparison again on S[a, a].
+ * Per item a: t_a = sum over b != a, in ascending b, of r[a, b]^2 over the pairs defined in this draw; an item without one adds
+ * 1 to ss_undefined, otherwise ss_obs_sum += t_obs, ss_rep_sum += t_rep, ss_ge / ss_gt += [t_rep >= / > t_obs] in fp64.
+ * Global: u_a = sum over b > a, ascending, of r[a, b]^2; Q = sum over a, ascending, of u_a; M+ = max r, M = max |r| over the
+ * defined pairs a < b.  A draw without a defined pair adds 1 to global_undefined; otherwise the 16 words `global` take
+ *   [0..6] doubles frob_obs_sum, frob_rep_sum, frob_rep_sumsq, max_obs_sum, max_rep_sum, absmax_obs_sum, absmax_rep_sum,
+ *   [7..12] uint64 frob_ge, frob_gt, max_ge, max_gt, absmax_ge, absmax_gt (rep >= / > obs in fp64), [13] global_undefined.
+ * Every fp64 sum has one owning thread and the order stated above; there are no atomics, so two runs leave a byte-identical
+ * state block and NumPy reproduces it bit for bit from the integer tables (gpirt_amd.ppc.resid_*).
+ * A draw with a NaN g in an observed cell is skipped whole: resid_skipped += 1 and nothing else changes, decided on the device
+ * before anything is touched.  A NaN in an unobserved cell is ignored.  Otherwise resid_draws += 1.
+ * Finished on the host, S = resid_draws.  Pair arrays (m x m; NaN on the diagonal and where n_co = 0, except n_co itself), with
+ * D = S - undefined_count:  n_co;  rc_obs_mean = rc_obs_sum / D, rc_rep_mean (NaN for D < 1);  rc_rep_sd = sqrt(max(0,
+ * (rc_rep_sumsq - rc_rep_sum (rc_rep_sum / D)) / (D - 1))) (NaN for D < 2);  ppp_rc = rc_ge / D, ppp_rc_mid = (rc_ge + rc_gt) /
+ * 2D;  undefined = undefined_count.  Item arrays (m): infit_obs_mean, infit_rep_mean, infit_rep_sd, ppp_infit, ppp_infit_mid by
+ * the same formulas from the diagonal cells;  ss_obs_mean, ss_rep_mean, ppp_ss, ppp_ss_mid with D = S - ss_undefined.  Scalars,
+ * D = S - global_undefined: frob_obs_mean, frob_rep_mean, frob_rep_sd, ppp_frob, ppp_frob_mid; max_obs_mean, max_rep_mean,
+ * ppp_max, ppp_max_mid; absmax_obs_mean, absmax_rep_mean, ppp_absmax, ppp_absmax_mid.
+ *   worst: the `top` (1..GPIRT_RESID_MAX_TOP, the Python default is 20) pairs a < b with the smallest ppp_rc_mid -- the data more
+ *   correlated than the replicates: positive local dependence --, ties to the lowest (a, b), NaN never listed: their indices,
+ *   ppp_rc_mid and rc_obs_mean, padded with -1 / NaN.  worst_items: the `top` items with the smallest ppp_ss_mid, ties to the
+ *   lowest a.
+ * Pooling C chains (gpirt_ppc_resid_combine) adds the integers and adds the doubles in chain order; blocks with another n, m or
+ * item0, or another n_co, are refused.  theta -> -theta leaves f + mu as it is, so there are no signs.  Nothing is drawn: with
+ * the block on, the chain, the IRFs, R's stream position and the PPC, pairs, bins, dif, scores and person state blocks are bit
+ * for bit what they are without it.
+ * Device memory per state: 44 bytes per ordered pair of accumulators and constants and 56 of per-draw tables (105 MB at m =
+ * 1024), and 19 int8 planes of n x m padded to 256 respondents and 128 items (160 MB at 8192 x 1024). */
+#define GPIRT_RESID_MAX_TOP  64
+#define GPIRT_RESID_MAX_N    65534
+#define GPIRT_RESID_MAX_M    4096
+#define GPIRT_RESID_P_N_CO          0
+#define GPIRT_RESID_P_RC_OBS_MEAN   1
+#define GPIRT_RESID_P_RC_REP_MEAN   2
+#define GPIRT_RESID_P_RC_REP_SD     3
+#define GPIRT_RESID_P_PPP_RC        4
+#define GPIRT_RESID_P_PPP_RC_MID    5
+#define GPIRT_RESID_P_UNDEFINED     6
+#define GPIRT_RESID_NPAIR           7
+#define GPIRT_RESID_I_INFIT_OBS_MEAN  0
+#define GPIRT_RESID_I_INFIT_REP_MEAN  1
+#define GPIRT_RESID_I_INFIT_REP_SD    2
+#define GPIRT_RESID_I_PPP_INFIT       3
+#define GPIRT_RESID_I_PPP_INFIT_MID   4
+#define GPIRT_RESID_I_SS_OBS_MEAN     5
+#define GPIRT_RESID_I_SS_REP_MEAN     6
+#define GPIRT_RESID_I_PPP_SS          7
+#define GPIRT_RESID_I_PPP_SS_MID      8
+#define GPIRT_RESID_NITEM             9
+#define GPIRT_RESID_S_FROB_OBS_MEAN    0
+#define GPIRT_RESID_S_FROB_REP_MEAN    1
+#define GPIRT_RESID_S_FROB_REP_SD      2
+#define GPIRT_RESID_S_PPP_FROB         3
+#define GPIRT_RESID_S_PPP_FROB_MID     4
+#define GPIRT_RESID_S_MAX_OBS_MEAN     5
+#define GPIRT_RESID_S_MAX_REP_MEAN     6
+#define GPIRT_RESID_S_PPP_MAX          7
+#define GPIRT_RESID_S_PPP_MAX_MID      8
+#define GPIRT_RESID_S_ABSMAX_OBS_MEAN  9
+#define GPIRT_RESID_S_ABSMAX_REP_MEAN  10
+#define GPIRT_RESID_S_PPP_ABSMAX       11
+#define GPIRT_RESID_S_PPP_ABSMAX_MID   12
+#define GPIRT_RESID_NSCALAR            13
+/* the raw arrays of the state block, in its order: n_co (int64, m x m); undefined_count, rc_ge, rc_gt (uint32, m x m);
+ * rc_obs_sum, rc_rep_sum, rc_rep_sumsq (double, m x m); ss_undefined, ss_ge, ss_gt (uint32, m); ss_obs_sum, ss_rep_sum (double,
+ * m); global (16 words of 8 bytes) */
+#define GPIRT_RESID_NRAW     13
+/* HOST pointers (NULL: not wanted); every m x m array holds the pair (a, b) at [a m + b]. */
+typedef struct gpirt_ppc_resid {
+    int        top;                            /* in: 1..GPIRT_RESID_MAX_TOP */
+    int        reserved0;                      /* must be 0 */
+    double*    pair[GPIRT_RESID_NPAIR];        /* m x m each */
+    double*    item[GPIRT_RESID_NITEM];        /* m each */
+    void*      raw[GPIRT_RESID_NRAW];          /* the raw arrays, by their own types */
+    int64_t*   worst_pairs;                    /* top x 2: a, b */
+    double*    worst_ppp_rc_mid;               /* top */
+    double*    worst_rc_obs_mean;              /* top */
+    int64_t*   worst_items;                    /* top */
+    double*    worst_ppp_ss_mid;               /* top */
+    double     scalar[GPIRT_RESID_NSCALAR];    /* out */
+    int64_t    n, m;                           /* out */
+    int64_t    resid_draws, resid_skipped, global_undefined;     /* out */
+    int64_t    reserved[4];                    /* must be 0 */
+} gpirt_ppc_resid;
+/* Stage API.  ppc_resid_enable(top in 1..GPIRT_RESID_MAX_TOP; 0 frees the state) allocates and zeroes the state on a sampler
+ * with ppc_enable on and forms O and n_co (GPIRT_E_ARG, with a message that names the fault, without ppc_enable, on an item
+ * shard, for top outside 0..64, m outside 2..4096 and n > 65534; ppc_enable called again frees it too).  From then on every
+ * ppc_accumulate also adds the draw to the block.  ppc_resid_get copies one array by name to the host, `bytes` its exact size:
+ * every finished pair or item array by the lower-case name above (double), "scalars" (double, 13), the raw arrays by theirs,
+ * "counts" (int64: resid_draws, resid_skipped, global_undefined) and, of the last COUNTED draw, "d_obs", "d_rep", "w" (int32, n x
+ * m, column-major as y is, rejoined from the digit planes), "digits" (int8, 9 x n x m: the planes of d_obs, d_rep, w, the low
+ * digit first), "s_obs", "s_rep", "v" (int64, m x m), "r_obs", "r_rep" (double, m x m: the correlations, the infit on the
+ * diagonal, NaN where undefined) and "stats" (double, 8: Q, M+, M of the data, Q, M+, M of the replicate, the defined pairs a <
+ * b, 0).
+ * ppc_resid_state returns the ONE device block of its own: a header of 8 int64 -- n, m, the layout version (1), resid_draws,
+ * resid_skipped, item0, 0, the tag 0x31445352 ("RSD1") --, then the raw arrays in the order above; every array starts on a
+ * 16-byte boundary. */
+int gpirt_sampler_ppc_resid_enable(gpirt_sampler_t s, int top);
+int gpirt_sampler_ppc_resid_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ppc_resid_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ppc_resid_combine(gpirt_handle_t h, int chains, const void* const* d_states, gpirt_ppc_resid* out);
+
 /* ------------------------------------------------------ Two-form score equating: joint table, concordance ------------- */
 /* The sum-score section answers every question about ONE form's score.  This one is about TWO forms at once: how scores on
  * form X and form Y relate (IRT observed-score equating), what somebody who scored s on X scores on Y (the concordance table),
