@@ -690,6 +690,19 @@ def check(rc: int) -> int:
     return rc
 
 
+def state_ptrs(states, method: str):
+    """What every combine starts from: the states as device tensors (a Sampler gives its `method`(), e.g. "rank_state"; a
+    tensor is taken as it is), their count and their device pointers as a C array of void*."""
+    tensors = [getattr(s, method)() if hasattr(s, method) else s for s in states]
+    nc = len(tensors)
+    return tensors, nc, (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
+
+
+def header_words(state, words: int = 8) -> np.ndarray:
+    """The first `words` 8-byte words of a state block (a torch tensor on the device, int64 or float64) as int64 on the host."""
+    return state[:words].detach().cpu().numpy().view(np.int64)
+
+
 def default_options() -> Options:
     o = Options()
     load().gpirt_default_options(C.byref(o))

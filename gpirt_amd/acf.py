@@ -158,7 +158,7 @@ def result(r, arrays) -> dict:
 
 def state_header(state) -> dict:
     """The header of an ACF state block (a device tensor of int64)."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     names = ("tag", "version", "n", "m", "parts", "S", "H", "L", "P", "draws")
     return {k: int(w[i]) for i, k in enumerate(names)}
 
@@ -168,13 +168,11 @@ def combine(handle, states, signs=None, top=DEFAULT_TOP) -> dict:
     device), each with all of its planned draws in.  signs: None, or one +1 / -1 per chain (-1: the chain enters reflected,
     theta -> -theta with the beta slopes; `1 - 2 * diagnostics["reflected"]` of gpirt_amd.chains.combine)."""
     lib = _lib.load()
-    tensors = [s.acf_state() if hasattr(s, "acf_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "acf_state")
     hdr = state_header(tensors[0])
     if hdr["tag"] != _lib.ACF_TAG:
         raise ValueError("acf.combine: state 0 is not an ACF state block")
     r, arrays = struct(hdr["P"], hdr["L"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = None
     if signs is not None:
         if len(signs) != nc:

@@ -31,8 +31,7 @@ def _ptr(a):
 
 def state_header(state) -> dict:
     """The header of a state block (a torch tensor on the device, as Sampler.summary_state() returns)."""
-    import torch
-    h = state[:8].detach().to("cpu").contiguous().view(torch.int64).numpy()
+    h = _lib.header_words(state)
     return dict(n=int(h[0]), m=int(h[1]), parts=int(h[2]), planned=int(h[3]), draws=int(h[4]), layout=int(h[5]))
 
 
@@ -68,7 +67,7 @@ def combine(handle, states, align=True, signs=None, summaries=None) -> dict:
     summaries: the pooled parts to return (default: every part the states carry)."""
     from .sampler import _summary_arrays, _totals
     lib = _lib.load()
-    tensors = [s.summary_state() if hasattr(s, "summary_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "summary_state")
     hdr = state_header(tensors[0])
     n, m, parts = hdr["n"], hdr["m"], hdr["parts"]
     want = (parts & _lib.SUM_POOLED) if summaries is None else _lib.summary_parts(summaries) | _lib.SUM_THETA_BETA
@@ -77,8 +76,6 @@ def combine(handle, states, align=True, signs=None, summaries=None) -> dict:
     arrays = _summary_arrays(want, n, m)
     for k, a in arrays.items():
         setattr(sm, "h_" + k, _ptr(a))
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = None
     if signs is not None:
         sg = (C.c_int * nc)(*[int(x) for x in signs])

@@ -372,6 +372,7 @@ struct PairState {
     std::vector<void*> allocs;
 };
 int64_t pair_state_words(int64_t m);
+inline int64_t pair_state_words(const PairState* p) { return pair_state_words(p->m); }
 int pair_alloc(hipStream_t stream, PairState* p, int64_t n, int64_t m, int64_t item0, const double* y);
 void pair_free(PairState* p);
 // after the replicate pass has left this draw's bytes and its non-finite word: the products, then the decisions
@@ -414,6 +415,7 @@ struct BinState {
     std::vector<void*> allocs;
 };
 int64_t bin_state_words(int64_t m, int64_t B);
+inline int64_t bin_state_words(const BinState* p) { return bin_state_words(p->m, p->B); }
 int bin_check_cuts(int h, const int* cuts);          // GPIRT_E_ARG (with the message) unless 1 <= d_1 < ... < d_h <= 499, 1 <= h <= 15
 int bin_alloc(hipStream_t stream, BinState* p, int64_t n, int64_t m, int64_t item0, int rblocks, int h, const int* cuts);
 void bin_free(BinState* p);
@@ -608,6 +610,7 @@ struct RsdState {
     std::vector<void*> allocs;
 };
 int64_t rsd_state_words(int64_t m);
+inline int64_t rsd_state_words(const RsdState* p) { return rsd_state_words(p->m); }
 int rsd_alloc(hipStream_t stream, RsdState* p, int64_t n, int64_t m, int64_t item0, const double* y);      // refusals: with a message
 void rsd_free(RsdState* p);
 // one draw: the digit planes from f, mu, y and the PPC's uniforms, the int8 products, then the decisions and the reductions
@@ -634,6 +637,7 @@ struct PpcState {
 };
 // zeroed accumulators; n_obs and obs_yes from y (device, n x m) on `stream`; the header is written
 int ppc_alloc(hipStream_t stream, PpcState* s, int64_t n, int64_t m, int64_t item0, const double* y);
+inline int64_t ppc_state_words(const PpcState* s) { return ppc_state_words(s->n, s->m); }
 void ppc_free(PpcState* s);
 // adds the replicate of one draw: f, mu, y n x m on the device; iter = the completed-iteration counter of that state;
 // theta (n, on the device) is read only with the bins or the group-wise fit on
@@ -733,6 +737,7 @@ int score_get(hipStream_t stream, ScoreState* s, const char* name, void* h_out, 
 int score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_score* out);
 // predict.hip
 int64_t pred_state_words(int64_t n_new, int64_t m);
+inline int64_t pred_state_words(const ScoreState* s) { return pred_state_words(s->pred.n, s->pred.m); }     // of s->pred
 int pred_alloc(hipStream_t stream, ScoreState* s);    // needs s->on; the block's header and mask are written
 void pred_free(PredState* p);
 // after score_accumulate_kernel has stored this draw's weights and go-flag: the operands, the contraction, the epilogue
@@ -782,6 +787,9 @@ struct ShapeState {
 };
 // refuses k_half outside 1..500, n_tols outside 1..GPIRT_SHAPE_MAX_TOLS and a negative or non-finite tolerance, with a message
 int shape_check(int k_half, const double* tols, int n_tols);
+// the sizes of the shape block and of its pair block (s->order), in 8-byte words
+inline int64_t shape_state_words(const ShapeState* s) { return shape_layout(s->m).words; }
+inline int64_t order_state_words(const ShapeState* s) { return order_layout(s->m, s->n_tols).words; }
 int shape_alloc(hipStream_t stream, ShapeState* s, int64_t n, int64_t m, int k_half, const double* tols, int n_tols);
 void shape_free(ShapeState* s);
 int launch_shape_accumulate(hipStream_t stream, ShapeState* s, const double* gbar);   // gbar: N x m (ld N) on the device
@@ -815,6 +823,7 @@ struct SumscoreState {
 };
 // mask: m bytes (non-zero: the item is in the form) or NULL (all m); refuses an empty form and M > GPIRT_SUMSCORE_MAX_ITEMS
 int sumscore_check(int64_t m, const unsigned char* mask, int64_t* M_out);
+inline int64_t sumscore_state_words(const SumscoreState* s) { return sumscore_layout(s->m, s->M).words; }
 void sumscore_grid_weights(double* w);                // 1001 doubles (host)
 int sumscore_alloc(hipStream_t stream, SumscoreState* s, int64_t m, const unsigned char* mask);
 void sumscore_free(SumscoreState* s);
@@ -853,6 +862,7 @@ struct EquateState {
 // both masks: m bytes; refuses a missing mask, an overlap (naming the first shared column), an empty form and more than
 // GPIRT_EQUATE_MAX_ITEMS items in a form
 int equate_check(int64_t m, const unsigned char* mask_x, const unsigned char* mask_y, int64_t* Mx_out, int64_t* My_out);
+inline int64_t equate_state_words(const EquateState* s) { return equate_layout(s->m, s->Mx, s->My).words; }
 int equate_alloc(hipStream_t stream, EquateState* s, int64_t m, const unsigned char* mask_x, const unsigned char* mask_y);
 void equate_free(EquateState* s);
 int launch_equate_accumulate(gpirt_handle_t h, hipStream_t stream, EquateState* s, const double* fstar);   // fstar: N x m (ld N)
@@ -875,6 +885,7 @@ struct LooState {
 };
 // M from T and `tail` (0: the rule); refuses a tail outside 5 .. GPIRT_LOO_MAX_TAIL, M > GPIRT_LOO_MAX_TAIL and M >= T
 int loo_tail_length(int64_t T, int tail, int64_t* M_out);
+inline int64_t loo_state_words(const LooState* s) { return loo_layout(s->n, s->m, s->M).words; }
 int loo_alloc(hipStream_t stream, LooState* s, int64_t n, int64_t m, int64_t T, int64_t M, const double* d_y);   // d_y: n x m
 void loo_free(LooState* s);
 int launch_loo_accumulate(hipStream_t stream, LooState* s, const double* f, const double* mu);    // f, mu: n x m on the device
@@ -901,6 +912,7 @@ struct AcfState {
 };
 // the argument check of gpirt_acf_check: L from max_lag (0: the default), P from the parts
 int acf_check(int64_t n, int64_t m, int parts, int64_t planned, int64_t max_lag, int64_t* L_out, int64_t* P_out);
+inline int64_t acf_state_words(const AcfState* s) { return acf_layout(s->P, s->L).words; }
 int acf_alloc(hipStream_t stream, AcfState* s, int64_t n, int64_t m, int parts, int64_t planned, int64_t L);
 void acf_free(AcfState* s);
 // the sampler's theta (n), beta (2 x m), f, mu and y (n x m) on the device; refuses a draw beyond the planned ones

@@ -115,7 +115,7 @@ def result(r, arrays, probs=DEFAULT_PROBS, cuts=None) -> dict:
 
 def state_header(state) -> dict:
     """The header of an equating state block (a device tensor of int64)."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     return dict(tag=int(w[0]), version=int(w[1]), m=int(w[2]), Mx=int(w[3]), My=int(w[4]), N=int(w[5]), draws=int(w[6]),
                 skipped=int(w[7]), corr_draws=int(w[8]), corr_skipped=int(w[9]), eq_clamped=int(w[10]))
 
@@ -126,13 +126,11 @@ def combine(handle, states, probs=DEFAULT_PROBS, cuts=None) -> dict:
     or other grid weights are refused."""
     lib = _lib.load()
     probs = check_probs(probs)
-    tensors = [s.equate_state() if hasattr(s, "equate_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "equate_state")
     hdr = state_header(tensors[0])
     if hdr["tag"] != _lib.EQUATE_TAG:
         raise ValueError("equate.combine: state 0 is not an equating state block")
     r, arrays = struct(hdr["m"], hdr["Mx"], hdr["My"])
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_equate_combine(handle.ptr, nc, ptrs, C.byref(r)))
     return result(r, arrays, probs, cuts)
 

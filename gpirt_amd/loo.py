@@ -128,7 +128,7 @@ def result(r, arrays) -> dict:
 
 def state_header(state) -> dict:
     """The header of a LOO state block (a device tensor of int64)."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), T=int(w[4]), M=int(w[5]), draws=int(w[6]),
                 chains=int(w[7]))
 
@@ -138,13 +138,11 @@ def combine(handle, states, top=DEFAULT_TOP) -> dict:
     device): pooled on the device in chain order (no signs: theta -> -theta does not change g), then finished.  States of
     another n, m, T, M or y are refused."""
     lib = _lib.load()
-    tensors = [s.loo_state() if hasattr(s, "loo_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "loo_state")
     hdr = state_header(tensors[0])
     if hdr["tag"] != _lib.LOO_TAG:
         raise ValueError("loo.combine: state 0 is not a LOO state block")
     r, arrays = struct(hdr["n"], hdr["m"], hdr["M"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_loo_combine(handle.ptr, nc, ptrs, C.byref(r)))
     return result(r, arrays)
 

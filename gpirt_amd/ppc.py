@@ -84,18 +84,16 @@ def combine(handle, states) -> dict:
     handle's device): the integer sums and counts added, the double sums added in chain order.  The theta -> -theta
     reflection changes no PPC output, so there are no signs and no alignment."""
     lib = _lib.load()
-    tensors = [s.ppc_state() if hasattr(s, "ppc_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_state")
     hdr = state_header(tensors[0])
     p, arrays = struct(hdr["n"], hdr["m"])
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_ppc_combine(handle.ptr, nc, ptrs, C.byref(p)))
     return result(p, arrays)
 
 
 def state_header(state) -> dict:
     """The 8 int64 header words of a PPC state block (a device tensor): n, m, draws, layout version, item0."""
-    w = state[:8].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state)
     return dict(n=int(w[0]), m=int(w[1]), draws=int(w[2]), version=int(w[3]), item0=int(w[4]))
 
 
@@ -145,18 +143,16 @@ def pairs_combine(handle, states, top=DEFAULT_PAIRS_TOP) -> dict:
     """gpirt_ppc_pairs_combine over the pairwise state blocks `states` (device tensors, or Samplers with ppc_pairs_enable()
     on, all on handle's device): every array and both counters added.  Blocks with another n, m or n_co are refused."""
     lib = _lib.load()
-    tensors = [s.ppc_pairs_state() if hasattr(s, "ppc_pairs_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_pairs_state")
     m = pairs_state_header(tensors[0])["m"]
     p, arr = pairs_struct(m, top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_ppc_pairs_combine(handle.ptr, nc, ptrs, C.byref(p)))
     return pairs_result(p, arr)
 
 
 def pairs_state_header(state) -> dict:
     """The 8 int64 header words of a pairwise state block (a device tensor)."""
-    w = state[:8].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state)
     return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), pair_draws=int(w[3]), pair_skipped=int(w[4]), item0=int(w[5]),
                 tag=int(w[7]))
 
@@ -383,7 +379,7 @@ def bins_result(p, arr) -> dict:
 
 def bins_state_header(state) -> dict:
     """The header of a theta-binned state block (a device tensor): its 8 int64 words and the cuts."""
-    w = state[:24].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 24)
     B = int(w[6])
     return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), bin_draws=int(w[3]), bin_skipped=int(w[4]), item0=int(w[5]),
                 B=B, tag=int(w[7]), cuts=tuple(int(x) for x in w[8:8 + max((B - 1) // 2, 0)]))
@@ -394,13 +390,11 @@ def bins_combine(handle, states, signs=None, top=DEFAULT_BINS_TOP) -> dict:
     on, all on handle's device): the integers added, the doubles added in chain order; a chain whose sign is -1 enters with
     its bin axis reversed.  Blocks with another n, m, item0 or cuts are refused."""
     lib = _lib.load()
-    tensors = [s.ppc_bins_state() if hasattr(s, "ppc_bins_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_bins_state")
     hdr = bins_state_header(tensors[0])
     if hdr["tag"] != _lib.BINS_TAG:
         raise ValueError("bins_combine: the first state is not a theta-binned PPC state block")
     p, arr = bins_struct(hdr["m"], hdr["cuts"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = None
     if signs is not None:
         if len(signs) != nc:
@@ -828,7 +822,7 @@ def dif_result(p, arr) -> dict:
 
 def dif_state_header(state) -> dict:
     """The header of a group-wise state block (a device tensor): its 8 int64 words, the cuts, G and the groups' sizes."""
-    w = state[:32].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 32)
     B, G = int(w[6]), int(w[24])
     return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), dif_draws=int(w[3]), dif_skipped=int(w[4]), item0=int(w[5]),
                 B=B, tag=int(w[7]), cuts=tuple(int(x) for x in w[8:8 + max((B - 1) // 2, 0)]), G=G,
@@ -840,13 +834,11 @@ def dif_combine(handle, states, signs=None, top=DEFAULT_DIF_TOP) -> dict:
     all on handle's device): the integers added, the doubles added in chain order; a chain whose sign is -1 enters with the bin
     axis of its tables reversed.  Blocks with another n, m, item0, groups or cuts are refused."""
     lib = _lib.load()
-    tensors = [s.ppc_dif_state() if hasattr(s, "ppc_dif_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_dif_state")
     hdr = dif_state_header(tensors[0])
     if hdr["tag"] != _lib.DIF_TAG or not 2 <= hdr["G"] <= _lib.DIF_MAX_G:
         raise ValueError("dif_combine: the first state is not a group-wise PPC state block")
     p, arr = dif_struct(hdr["m"], hdr["G"], hdr["cuts"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = None
     if signs is not None:
         if len(signs) != nc:
@@ -1197,7 +1189,7 @@ def scores_result(p, arr) -> dict:
 
 def scores_state_header(state) -> dict:
     """The header of a score-based state block (a device tensor): its 8 int64 words and the cuts."""
-    w = state[:24].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 24)
     K = int(w[4])
     return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), K=K, score_draws=int(w[5]), score_skipped=int(w[6]),
                 cuts=tuple(int(x) for x in w[8:8 + max(min(K, 16) - 1, 0)]))
@@ -1208,13 +1200,11 @@ def scores_combine(handle, states, top=DEFAULT_SCORES_TOP) -> dict:
     on, all on handle's device): the integers added, the doubles added in chain order; no signs (theta -> -theta leaves f + mu
     as it is).  Blocks with another n, m, K, cuts or response matrix are refused."""
     lib = _lib.load()
-    tensors = [s.ppc_scores_state() if hasattr(s, "ppc_scores_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_scores_state")
     hdr = scores_state_header(tensors[0])
     if hdr["tag"] != _lib.SCORES_TAG or not 2 <= hdr["K"] <= _lib.SCORES_MAX_K or not 2 <= hdr["m"] <= _lib.SCORES_MAX_M:
         raise ValueError("scores_combine: the first state is not a score-based PPC state block")
     p, arr = scores_struct(hdr["m"], hdr["K"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_ppc_scores_combine(handle.ptr, nc, ptrs, C.byref(p)))
     return scores_result(p, arr)
 
@@ -1609,7 +1599,7 @@ def person_result(p, arr) -> dict:
 
 def person_state_header(state) -> dict:
     """The header of a person-fit state block (a device tensor): its 8 int64 words and the cuts."""
-    w = state[:24].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 24)
     K = int(w[4])
     return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), K=K, person_draws=int(w[5]), person_skipped=int(w[6]),
                 cuts=tuple(int(x) for x in w[8:8 + max(min(K, 16) - 1, 0)]))
@@ -1620,14 +1610,12 @@ def person_combine(handle, states, top=DEFAULT_PERSON_TOP) -> dict:
     on, all on handle's device): the integers added, the doubles added in chain order; no signs (theta -> -theta leaves f + mu
     as it is).  Blocks with another n, m, K, order, cuts or response matrix are refused."""
     lib = _lib.load()
-    tensors = [s.ppc_person_state() if hasattr(s, "ppc_person_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_person_state")
     hdr = person_state_header(tensors[0])
     if (hdr["tag"] != _lib.PERSON_TAG or not 2 <= hdr["K"] <= _lib.PERSON_MAX_K or not 2 <= hdr["m"] <= _lib.PERSON_MAX_M
             or not 1 <= hdr["n"] <= _lib.PERSON_MAX_N):
         raise ValueError("person_combine: the first state is not a person-fit state block")
     p, arr = person_struct(hdr["n"], hdr["m"], hdr["K"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_ppc_person_combine(handle.ptr, nc, ptrs, C.byref(p)))
     return person_result(p, arr)
 
@@ -1937,7 +1925,7 @@ def resid_result(p, arr) -> dict:
 
 def resid_state_header(state) -> dict:
     """The 8 int64 header words of a residual-correlation state block (a device tensor)."""
-    w = state[:8].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state)
     return dict(n=int(w[0]), m=int(w[1]), version=int(w[2]), resid_draws=int(w[3]), resid_skipped=int(w[4]), item0=int(w[5]),
                 tag=int(w[7]))
 
@@ -1947,11 +1935,9 @@ def resid_combine(handle, states, top=DEFAULT_RESID_TOP) -> dict:
     handle's device): the integers added, the double sums added in chain order.  Blocks with another n, m, item0 or n_co are
     refused."""
     lib = _lib.load()
-    tensors = [s.ppc_resid_state() if hasattr(s, "ppc_resid_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ppc_resid_state")
     m = resid_state_header(tensors[0])["m"]
     p, arr = resid_struct(m if 2 <= m <= _lib.RESID_MAX_M else 2, top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_ppc_resid_combine(handle.ptr, nc, ptrs, C.byref(p)))
     return resid_result(p, arr)
 

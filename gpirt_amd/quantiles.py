@@ -100,14 +100,12 @@ def from_states(handle, states, probs, signs=None, align=True) -> dict:
     handle's device): every output the states' parts allow.  The reflection is chains.combine's for the same arguments."""
     from .chains import state_header
     lib = _lib.load()
-    tensors = [s.summary_state() if hasattr(s, "summary_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "summary_state")
     hdr = state_header(tensors[0])
     n, m, parts = hdr["n"], hdr["m"], hdr["parts"]
     th = bool(parts & _lib.SUM_THETA_HIST)
     q, arrays = quantiles_struct(probs, n, m, len(tensors), theta=th, rhat=th and bool(parts & _lib.SUM_DIAG),
                                  irf=bool(parts & _lib.SUM_IRF_BAND))
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = (C.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
     check(lib.gpirt_summary_quantiles(handle.ptr, nc, ptrs, sg, int(bool(align)), C.byref(q)))
     return quantiles_result(q, arrays)

@@ -110,11 +110,9 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS) -> dict:
     handle's device): the integers added, the shares added in chain order, a chain with sign -1 reflected exactly first
     (signs=None: nothing is reflected).  p_less comes with it when every state holds the pairwise counters."""
     lib = _lib.load()
-    tensors = [s.rank_state() if hasattr(s, "rank_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "rank_state")
     hdrs = [state_header(t) for t in tensors]
     r, arrays = struct(hdrs[0]["n"], None, probs, all(h["pairwise"] for h in hdrs), closed=hdrs[0]["pivots"])
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = (C.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
     check(lib.gpirt_rank_combine(handle.ptr, nc, ptrs, sg, C.byref(r)))
     return result(r, arrays)
@@ -123,7 +121,7 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS) -> dict:
 def state_header(state) -> dict:
     """The header of a rank state block (a device tensor of int64): n, draws (counted), skipped, version, B, w, the closed
     pivots and the pairwise flag."""
-    w = state[:40].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 40)
     return dict(n=int(w[0]), draws=int(w[1]), skipped=int(w[2]), version=int(w[3]), B=int(w[4]), w=int(w[5]),
                 pivots=[int(x) for x in w[8:8 + int(w[6])]], pairwise=bool(w[7]))
 

@@ -615,6 +615,24 @@ class Sampler:
             raise RuntimeError("chol(): decomposition failed (leading minor %d)" % rc)
         check(rc)
 
+    def _state(self, entry, typestr="<i8"):
+        """Torch view (on the device) of the ONE block that the stage entry `entry` (gpirt_sampler_*_state) hands out."""
+        import torch
+        p = C.c_void_p()
+        nb = C.c_int64()
+        check(getattr(self.lib, entry)(self._s, C.byref(p), C.byref(nb)))
+
+        class _Wrap:
+            pass
+
+        w = _Wrap()
+        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": typestr, "data": (p.value, False), "version": 2}
+        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+
+    def _get_into(self, entry, name, out):
+        """The array `name` of the stage entry `entry` (gpirt_sampler_*_get with a byte count) into the host array `out`."""
+        check(getattr(self.lib, entry)(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+
     def init(self): self._call("gpirt_sampler_init")
     def step(self): self._call("gpirt_sampler_step")
     def draw_f(self): self._call("gpirt_sampler_draw_f")
@@ -767,17 +785,7 @@ class Sampler:
     def summary_state(self):
         """Torch view (float64, on the device) of the ONE block that holds every accumulator of the summaries, its header
         and the IRF sum refreshed: what gpirt_amd.chains.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_summary_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<f8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_summary_state", "<f8")
 
     def summary_accumulate(self):
         """Add the current state (after a sampling iteration's step) as one draw."""
@@ -830,17 +838,7 @@ class Sampler:
     def ppc_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the PPC accumulators, its header refreshed: what
         gpirt_amd.ppc.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_state")
 
     def ppc(self) -> dict:
         """Every field of the items and the respondents, the derived ppp_* values and "totals" (gpirt_amd.ppc.result's shape)."""
@@ -882,23 +880,13 @@ class Sampler:
             out = np.empty((m, m), dtype=np.uint32)
         else:
             out = np.empty((m, m))
-        check(self.lib.gpirt_sampler_ppc_pairs_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_pairs_get", name, out)
         return out
 
     def ppc_pairs_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the pairwise accumulators: what
         gpirt_amd.ppc.pairs_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_pairs_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_pairs_state")
 
     def ppc_pairs(self, top=None) -> dict:
         """Every finished output of this sampler's pairwise accumulators (gpirt_amd.ppc.pairs_result's shape):
@@ -946,23 +934,13 @@ class Sampler:
             out = np.empty(B)
         else:
             out = np.empty((B, m))
-        check(self.lib.gpirt_sampler_ppc_bins_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_bins_get", name, out)
         return out
 
     def ppc_bins_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the theta-binned accumulators: what
         gpirt_amd.ppc.bins_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_bins_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_bins_state")
 
     def ppc_bins(self, top=None, sign=1) -> dict:
         """Every finished output of this sampler's theta-binned accumulators (gpirt_amd.ppc.bins_result's shape):
@@ -1024,23 +1002,13 @@ class Sampler:
             out = np.empty((G, B))
         else:
             out = np.empty((G, m))
-        check(self.lib.gpirt_sampler_ppc_dif_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_dif_get", name, out)
         return out
 
     def ppc_dif_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the group-wise accumulators: what
         gpirt_amd.ppc.dif_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_dif_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_dif_state")
 
     def ppc_dif(self, top=None, sign=1) -> dict:
         """Every finished output of this sampler's group-wise accumulators (gpirt_amd.ppc.dif_result's shape):
@@ -1077,23 +1045,13 @@ class Sampler:
         K = getattr(self, "_scores_K", None) or 2                    # (not enabled: the library refuses the call)
         shape, dtype = P.scores_field(name, n, m, K)
         out = np.empty(shape, dtype=dtype)
-        check(self.lib.gpirt_sampler_ppc_scores_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_scores_get", name, out)
         return out
 
     def ppc_scores_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the score-based accumulators: what
         gpirt_amd.ppc.scores_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_scores_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_scores_state")
 
     def ppc_scores(self, top=None) -> dict:
         """Every finished output of this sampler's score-based accumulators (gpirt_amd.ppc.scores_result's shape):
@@ -1131,23 +1089,13 @@ class Sampler:
         K = getattr(self, "_person_K", None) or 2                    # (not enabled: the library refuses the call)
         shape, dtype = P.person_field(name, self.n, self.m, K)
         out = np.empty(shape, dtype=dtype)
-        check(self.lib.gpirt_sampler_ppc_person_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_person_get", name, out)
         return out
 
     def ppc_person_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the person-fit accumulators: what
         gpirt_amd.ppc.person_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_person_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_person_state")
 
     def ppc_person(self, top=None) -> dict:
         """Every finished output of this sampler's person-fit accumulators (gpirt_amd.ppc.person_result's shape):
@@ -1176,23 +1124,13 @@ class Sampler:
         from . import ppc as P
         shape, dtype, order = P.resid_field(name, self.n, self.m)
         out = np.empty(shape, dtype=dtype, order=order)
-        check(self.lib.gpirt_sampler_ppc_resid_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_ppc_resid_get", name, out)
         return out.transpose(0, 2, 1) if name == "digits" else out
 
     def ppc_resid_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the residual-correlation accumulators: what
         gpirt_amd.ppc.resid_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_ppc_resid_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_ppc_resid_state")
 
     def ppc_resid(self, top=None) -> dict:
         """Every finished output of this sampler's residual-correlation accumulators (gpirt_amd.ppc.resid_result's shape):
@@ -1221,7 +1159,7 @@ class Sampler:
         pivot_share, p_pivot (P x n), rank_mean, rank_var (n), pivots (int64, P), lt (uint32, n x n),
         counts (int64: draws, skipped, B, w, P)."""
         c = np.zeros(5, dtype=np.int64)
-        check(self.lib.gpirt_sampler_rank_get(self._s, b"counts", c.ctypes.data, c.nbytes))     # the header alone
+        self._get_into("gpirt_sampler_rank_get", "counts", c)                                    # the header alone
         n, B, P = self.n, int(c[2]), int(c[4])
         shapes = dict(counts=((5,), np.int64), rank2_sum=((n,), np.uint64), rank2_sumsq=((n,), np.uint64),
                       rank_hist=((n, B), np.uint32), pivot_cover=((P, n), np.uint32), pivot_share=((P, n), np.float64),
@@ -1231,23 +1169,13 @@ class Sampler:
             return c
         shape, dt = shapes.get(name, ((0,), np.float64))
         out = np.empty(shape, dtype=dt)
-        check(self.lib.gpirt_sampler_rank_get(self._s, name.encode(), out.ctypes.data, out.nbytes))
+        self._get_into("gpirt_sampler_rank_get", name, out)
         return out
 
     def rank_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the rank accumulators: what
         gpirt_amd.ranks.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_rank_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_rank_state")
 
     def ranks(self, probs=(0.025, 0.5, 0.975)) -> dict:
         """Every finished output of this sampler's accumulators (gpirt_amd.ranks.result's shape): gpirt_rank_combine
@@ -1287,7 +1215,7 @@ class Sampler:
             out = np.empty(2, dtype=np.int64)
         else:
             out = np.empty({"tols": (_lib.SHAPE_MAX_TOLS,), "info": (m, NGRID), "ti": (NGRID,)}.get(name, (0,)))
-        check(self.lib.gpirt_sampler_shape_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_shape_get", name, out)
         if name == "tols":
             return out[:nt]
         return out.T if name == "info" else SH._public(name, out, nt)
@@ -1312,7 +1240,7 @@ class Sampler:
             out = np.empty(2 if name == "counts" else _lib.SHAPE_MAX_TOLS, dtype=np.int64)
         else:
             out = np.empty({"u": (m, m), "e": (m,)}.get(name, (0,)))
-        check(self.lib.gpirt_sampler_shape_order_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_shape_order_get", name, out)
         if name == "ncross":
             return out[:nt]
         return out[:, :nt] if name == "set_counts" else out
@@ -1320,17 +1248,7 @@ class Sampler:
     def shape_order_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the order accumulators: what
         gpirt_amd.shape.order_combine pools."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_shape_order_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_shape_order_state")
 
     def shape_order(self, top=20) -> dict:
         """Every finished output of this sampler's order block (gpirt_amd.shape.order_finish's dict)."""
@@ -1340,17 +1258,7 @@ class Sampler:
     def shape_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the shape accumulators: what
         gpirt_amd.shape.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_shape_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_shape_state")
 
     def shape(self, probs=(0.025, 0.5, 0.975), top=20, sign=1) -> dict:
         """Every finished output of this sampler's accumulators (gpirt_amd.shape.finish's dict): gpirt_shape_combine over
@@ -1388,23 +1296,13 @@ class Sampler:
             out = np.empty(4, dtype=np.int64)
         else:
             out = np.empty({"tcc": (NGRID,), "var": (NGRID,)}.get(name, (0,)))
-        check(self.lib.gpirt_sampler_sumscore_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_sumscore_get", name, out)
         return out
 
     def sumscore_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the sum-score accumulators: what
         gpirt_amd.sumscore.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_sumscore_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_sumscore_state")
 
     def sumscore(self, probs=(0.025, 0.5, 0.975), sign=1, y=None) -> dict:
         """Every finished output of this sampler's accumulators (gpirt_amd.sumscore.finish's dict): gpirt_sumscore_combine
@@ -1442,23 +1340,13 @@ class Sampler:
             out = np.empty(5, dtype=np.int64)
         else:
             out = np.empty(0)
-        check(self.lib.gpirt_sampler_equate_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_equate_get", name, out)
         return out
 
     def equate_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the equating accumulators: what
         gpirt_amd.equate.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_equate_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_equate_state")
 
     def equate(self, probs=(0.025, 0.5, 0.975), cuts=None) -> dict:
         """Every finished output of this sampler's accumulators (gpirt_amd.equate.finish's dict): gpirt_equate_combine over
@@ -1499,24 +1387,14 @@ class Sampler:
             out = np.empty(6, dtype=np.int64)
         else:
             out = np.empty(0)
-        check(self.lib.gpirt_sampler_loo_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_loo_get", name, out)
         if name == "keys":
             return out.transpose(0, 2, 1)
         return out.T if name in dts else out
 
     def loo_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the LOO state: what gpirt_amd.loo.combine pools."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_loo_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_loo_state")
 
     def loo(self, top=20) -> dict:
         """Every finished output of this sampler's state (gpirt_amd.loo.result's dict): gpirt_loo_combine over it alone."""
@@ -1555,7 +1433,7 @@ class Sampler:
             out = np.empty(8, dtype=np.int64)
         else:
             out = np.empty(AC.raw_shape(name, P, L), dtype=np.int64)
-        check(self.lib.gpirt_sampler_acf_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_acf_get", name, out)
         if name == "counts":
             return out
         return AC.decode_raw(name, out, 0 if name == "last" or not mask & _lib.ACF_THETA else self.n)
@@ -1563,17 +1441,7 @@ class Sampler:
     def acf_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the autocorrelation state: what gpirt_amd.acf.combine
         finishes."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_acf_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_acf_state")
 
     def acf(self, top=20, sign=1) -> dict:
         """Every finished output of this sampler's state alone (gpirt_amd.acf.result's dict): gpirt_acf_combine over it with
@@ -1612,23 +1480,13 @@ class Sampler:
             out = np.empty((NGRID, n), order="F")
         else:
             out = np.empty(n)
-        check(self.lib.gpirt_sampler_score_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_score_get", name, out)
         return out
 
     def score_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the score accumulators: what
         gpirt_amd.score.combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_score_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_score_state")
 
     def score(self, probs=(0.025, 0.5, 0.975)) -> dict:
         """Every finished output of this sampler's accumulators (gpirt_amd.score.result's shape): gpirt_score_combine over
@@ -1658,23 +1516,13 @@ class Sampler:
             out = np.empty((NGRID, n), order="F")
         else:
             out = np.empty((n, self.m), order="F")
-        check(self.lib.gpirt_sampler_score_predict_get(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
+        self._get_into("gpirt_sampler_score_predict_get", name, out)
         return out
 
     def score_predict_state(self):
         """Torch view (int64, on the device) of the ONE block that holds the prediction accumulators: what
         gpirt_amd.score.predict_combine pools; copy it anywhere to combine it there."""
-        import torch
-        p = C.c_void_p()
-        nb = C.c_int64()
-        check(self.lib.gpirt_sampler_score_predict_state(self._s, C.byref(p), C.byref(nb)))
-
-        class _Wrap:
-            pass
-
-        w = _Wrap()
-        w.__cuda_array_interface__ = {"shape": (nb.value // 8,), "typestr": "<i8", "data": (p.value, False), "version": 2}
-        return torch.as_tensor(w, device=f"cuda:{self.handle.device}")
+        return self._state("gpirt_sampler_score_predict_state")
 
     def score_predict(self, top=None) -> dict:
         """Every finished output of this sampler's prediction accumulators (gpirt_amd.score.predict_result's shape):

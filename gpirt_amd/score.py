@@ -96,7 +96,7 @@ def result(r, arrays) -> dict:
 
 def state_header(state) -> dict:
     """The header of a score state block (a device tensor of int64): n_new, m, version, N."""
-    w = state[:8].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state)
     return dict(n_new=int(w[0]), m=int(w[1]), version=int(w[2]), N=int(w[3]))
 
 
@@ -105,10 +105,8 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS) -> dict:
     on handle's device): the counters added, post_sum and ll_sum added and lpd_acc combined by logaddexp in chain order, a
     chain with sign -1 entering with post_sum[r][k] <-> post_sum[r][1000 - k] (signs=None: nothing is reflected)."""
     lib = _lib.load()
-    tensors = [s.score_state() if hasattr(s, "score_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "score_state")
     r, arrays = struct(state_header(tensors[0])["n_new"], probs)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = (C.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
     check(lib.gpirt_score_combine(handle.ptr, nc, ptrs, sg, C.byref(r)))
     return result(r, arrays)
@@ -267,7 +265,7 @@ def predict_result(r, arrays) -> dict:
 
 def predict_state_header(state) -> dict:
     """The header of a predict state block (a device tensor of int64): n_new, m, version, N, pred_draws, pred_skipped."""
-    w = state[:8].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state)
     return dict(n_new=int(w[0]), m=int(w[1]), version=int(w[2]), N=int(w[3]), pred_draws=int(w[4]), pred_skipped=int(w[5]))
 
 
@@ -277,11 +275,9 @@ def predict_combine(handle, states, top=DEFAULT_TOP) -> dict:
     blocks with another n_new, m or answered-mask are refused.  Nothing is reflected: both sums run over the whole grid."""
     lib = _lib.load()
     top = check_top(top)
-    tensors = [s.score_predict_state() if hasattr(s, "score_predict_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "score_predict_state")
     hdr = predict_state_header(tensors[0])
     r, arrays = predict_struct(hdr["n_new"], hdr["m"], top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_score_predict_combine(handle.ptr, nc, ptrs, C.byref(r)))
     return predict_result(r, arrays)
 

@@ -143,11 +143,9 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS, top=DEFAULT_TOP) ->
     (signs=None: nothing is reflected)."""
     lib = _lib.load()
     probs, top = check_probs(probs), check_top(top)
-    tensors = [s.shape_state() if hasattr(s, "shape_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "shape_state")
     m = state_header(tensors[0])["m"]
     r, arrays = struct(m)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = (C.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
     check(lib.gpirt_shape_combine(handle.ptr, nc, ptrs, sg, C.byref(r)))
     return result(r, arrays, probs, top)
@@ -155,7 +153,7 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS, top=DEFAULT_TOP) ->
 
 def state_header(state) -> dict:
     """The header of a shape state block (a device tensor of int64): tag, version, n, m, k_half, the tolerances, the counters."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     n_tols = int(w[5])
     return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), k_half=int(w[4]),
                 tols=[float(x) for x in w[6:6 + n_tols].view(np.float64)], info_draws=int(w[10]), info_skipped=int(w[11]))
@@ -367,18 +365,16 @@ def order_combine(handle, states, top=DEFAULT_ORDER_TOP) -> dict:
     on): the integers added, the doubles added in chain order.  No signs: theta -> -theta changes nothing in this block."""
     lib = _lib.load()
     top = check_order_top(top)
-    tensors = [s.shape_order_state() if hasattr(s, "shape_order_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "shape_order_state")
     hd = order_state_header(tensors[0])
     r, arrays = order_struct(hd["m"], len(hd["tols"]), top)
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     check(lib.gpirt_shape_order_combine(handle.ptr, nc, ptrs, C.byref(r)))
     return order_result(r, arrays)
 
 
 def order_state_header(state) -> dict:
     """The header of an order state block (a device tensor of int64): tag, version, n, m, k_half, the tolerances, the counters."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     n_tols = int(w[5])
     return dict(tag=int(w[0]), version=int(w[1]), n=int(w[2]), m=int(w[3]), k_half=int(w[4]),
                 tols=[float(x) for x in w[6:6 + n_tols].view(np.float64)], draws=int(w[10]), skipped=int(w[11]))

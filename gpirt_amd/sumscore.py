@@ -116,7 +116,7 @@ def result(r, arrays, probs=DEFAULT_PROBS, y=None) -> dict:
 
 def state_header(state) -> dict:
     """The header of a sum-score state block (a device tensor of int64)."""
-    w = state[:16].cpu().numpy().view(np.int64)
+    w = _lib.header_words(state, 16)
     return dict(tag=int(w[0]), version=int(w[1]), m=int(w[2]), M=int(w[3]), N=int(w[4]), draws=int(w[5]), skipped=int(w[6]),
                 rel_draws=int(w[7]), rel_skipped=int(w[8]))
 
@@ -128,13 +128,11 @@ def combine(handle, states, signs=None, probs=DEFAULT_PROBS, y=None) -> dict:
     histogram over the respondents who answered every item of the form."""
     lib = _lib.load()
     probs = check_probs(probs)
-    tensors = [s.sumscore_state() if hasattr(s, "sumscore_state") else s for s in states]
+    tensors, nc, ptrs = _lib.state_ptrs(states, "sumscore_state")
     hdr = state_header(tensors[0])
     if hdr["tag"] != _lib.SUMSCORE_TAG:
         raise ValueError("sumscore.combine: state 0 is not a sum-score state block")
     r, arrays = struct(hdr["m"], hdr["M"])
-    nc = len(tensors)
-    ptrs = (C.c_void_p * nc)(*[t.data_ptr() for t in tensors])
     sg = (C.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
     check(lib.gpirt_sumscore_combine(handle.ptr, nc, ptrs, sg, C.byref(r)))
     return result(r, arrays, probs, y)
