@@ -739,6 +739,7 @@ static int theta_logpost(gpirt_handle_t h, const double* d_y, const double* d_fs
     }
     GP_TRY(launch_loglik_terms(h->stream, d_fstar, N, m, Gpm, Np, only_if));
     GP_TRY(launch_gemm(h, h->stream, false, true, TRI_NONE, N, n, 2 * m, 1.0, Gpm, Np, Ypm, n, 0.0, lp, N, Np, only_if));
+    GP_TRY(launch_theta_nan_fix(h->stream, Gpm, Np, Ypm, n, m, lp, N, N, only_if));
     *lp_out = lp;
     if (overflow_out) *overflow_out = only_if;
     return 0;

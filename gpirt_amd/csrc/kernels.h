@@ -224,6 +224,9 @@ int launch_fstar_epilogue(hipStream_t stream, const FstarEpiArgs& a);
 int launch_indicators(hipStream_t stream, const double* y, int64_t n, int64_t m, double* Ypm /* n x 2m */);
 int launch_loglik_terms(hipStream_t stream, const double* fstar, int64_t N, int64_t m, double* Gpm /* ldg x 2m */, int64_t ldg,
                         const int* run_if = nullptr);
+// behind the fp64 product (lp = Gpm Ypm^T, N x n): entries that came out NaN are summed again over the observed cells alone
+int launch_theta_nan_fix(hipStream_t stream, const double* Gpm, int64_t ldg, const double* Ypm /* n x 2m */, int64_t n, int64_t m,
+                         double* lp, int64_t N, int64_t ldlp, const int* run_if = nullptr);
 // theta_fixed.hip: the same product in exact fixed point on the int8 matrix cores
 struct TfDims { int64_t mp, ksteps, iblocks, gblocks; };
 TfDims tf_dims(int64_t n, int64_t m, int64_t N);

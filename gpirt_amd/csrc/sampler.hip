@@ -711,7 +711,8 @@ int do_theta_partial(gpirt_sampler_s* s)
         only_if = tf_overflow(s->tf_aux, s->tfd);
     }
     GP_TRY(launch_loglik_terms(st, s->fstar, N, m, s->Gpm, Np, only_if));
-    return launch_gemm(s->h, st, false, true, TRI_NONE, N, n, 2 * m, 1.0, s->Gpm, Np, s->Ypm, n, 0.0, s->logpost, N, Np, only_if);
+    GP_TRY(launch_gemm(s->h, st, false, true, TRI_NONE, N, n, 2 * m, 1.0, s->Gpm, Np, s->Ypm, n, 0.0, s->logpost, N, Np, only_if));
+    return launch_theta_nan_fix(st, s->Gpm, Np, s->Ypm, n, m, s->logpost, N, N, only_if);   // (a missing answer over a NaN f*)
 }
 
 int do_theta_finish(gpirt_sampler_s* s)
@@ -746,6 +747,7 @@ int do_theta_block(gpirt_sampler_s* s)
     GP_TRY(launch_loglik_terms(st, s->fstar_full, N, mt, s->Gpm_full, Np, only_if));
     GP_TRY(launch_gemm(s->h, st, false, true, TRI_NONE, N, nb, 2 * mt, 1.0, s->Gpm_full, Np, s->Ypm_blk, nb, 0.0,
                        s->logpost_blk, N, Np, only_if));
+    GP_TRY(launch_theta_nan_fix(st, s->Gpm_full, Np, s->Ypm_blk, nb, mt, s->logpost_blk, N, N, only_if));
     ThetaArgs a{};
     a.logpost = s->logpost_blk; a.N = N; a.n = nb; a.i0 = s->blk_i0; a.stabilise = s->opt.theta_stabilise;
     a.seed = s->opt.seed; a.iter = (uint32_t)(s->iter + 1);

@@ -151,6 +151,28 @@ __global__ void loglik_terms_kernel(const double* __restrict__ fstar, int64_t N,
     }
 }
 
+// The fp64 product forms 0 * NaN = NaN for a respondent whose answer to the item with the NaN f* is missing; the reference
+// skips that cell (isnan(y), src/log-likelihood.cpp:16).  Behind the product, every NaN entry of the log-posterior is summed
+// again over the observed cells alone, in item order: it stays NaN exactly where an observed cell holds one.
+__global__ void theta_nan_fix_kernel(const double* __restrict__ Gpm, int64_t ldg, const double* __restrict__ Ypm, int64_t n,
+                                     int64_t m, double* __restrict__ lp, int64_t N, int64_t ldlp, const int* __restrict__ run_if)
+{
+    if (run_if != nullptr && *run_if == 0) return;
+    const int64_t total = N * n;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total;
+         g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = g % N, i = g / N;
+        double* out = lp + k + i * ldlp;
+        if (*out == *out) continue;
+        double acc = 0.0;
+        for (int64_t j = 0; j < m; ++j) {
+            if (Ypm[i + j * n] != 0.0) acc += Gpm[k + j * ldg];
+            if (Ypm[i + (m + j) * n] != 0.0) acc += Gpm[k + (m + j) * ldg];
+        }
+        *out = acc;
+    }
+}
+
 // one work-group per respondent; 256 threads x 4 consecutive grid points cover N <= 1024
 __global__ __launch_bounds__(256) void theta_sample_kernel(ThetaArgs a)
 {
@@ -179,6 +201,9 @@ __global__ __launch_bounds__(256) void theta_sample_kernel(ThetaArgs a)
         __syncthreads();
         mx = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
         __syncthreads();
+        // every row at or below the product's stand-in for -inf (loglik_terms_kernel): the reference has -inf - (-inf) = NaN
+        // on the whole grid, a degenerate draw -- not the flat posterior that -1e300 - (-1e300) = 0 would make of it
+        if (mx <= -1e300) mx = __builtin_nan("");
 #pragma unroll
         for (int e = 0; e < 4; ++e) P[e] -= mx;
     }
@@ -378,6 +403,16 @@ int launch_loglik_terms(hipStream_t stream, const double* fstar, int64_t N, int6
     // (a conditional launch almost never runs: a small grid keeps what it costs to find that out at a couple of microseconds)
     const unsigned blocks = run_if ? (grid_for(N * m) < 256u ? grid_for(N * m) : 256u) : grid_for(N * m);
     hipLaunchKernelGGL(loglik_terms_kernel, dim3(blocks), dim3(256), 0, stream, fstar, N, m, Gpm, ldg, run_if);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_theta_nan_fix(hipStream_t stream, const double* Gpm, int64_t ldg, const double* Ypm, int64_t n, int64_t m,
+                         double* lp, int64_t N, int64_t ldlp, const int* run_if)
+{
+    if (N * n <= 0) return 0;
+    const unsigned blocks = run_if ? (grid_for(N * n) < 256u ? grid_for(N * n) : 256u) : grid_for(N * n);   // (as launch_loglik_terms)
+    hipLaunchKernelGGL(theta_nan_fix_kernel, dim3(blocks), dim3(256), 0, stream, Gpm, ldg, Ypm, n, m, lp, N, ldlp, run_if);
     GP_HIP(hipGetLastError());
     return 0;
 }

@@ -543,6 +543,10 @@ int summary_alloc(SummaryState* s, int64_t n, int64_t m, int parts, int64_t plan
     GP_TRY(get(&s->out, cells > tb ? cells : tb));
     GP_TRY(get(&s->part, (size_t)SUM_TOTAL_BLOCKS * 4));
     GP_TRY(get(&s->tot, GPIRT_SUM_NTOTALS));
+    // the clears above are the null stream's, which is not ordered against a hipStreamNonBlocking stream (the handle
+    // gpirt_mcmc makes for itself): drained here, or the first kernel that writes s->out on such a stream can have its
+    // last blocks cleared under it (seen once: the tail of the pooled lppd read back as zeros)
+    GP_HIP(hipStreamSynchronize(nullptr));
     return 0;
 }
 

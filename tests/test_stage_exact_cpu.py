@@ -137,3 +137,130 @@ def test_constructed_columns_are_what_they_claim(n):
     wrk, _ = X.draw_f_reference(n, 1000.0, "written")
     ov = wrk[0]["overflow"]
     assert not ov[-1] and sum(ov) >= 3
+
+
+# ------------------------------------------------------------------ draw_theta and draw_beta on constructed states ----
+THETA_CASES = ("one_item_finite", "one_item_fallback", "dense_smooth", "dense_nan_cell", "dense_nan_row", "dense_pm800",
+               "dense_overflow_item")
+
+
+def test_theta_and_beta_randoms_equal_the_oracle(oracle):
+    u = X.theta_uniforms(X.THETA_SEED, X.THETA_IT, 140)
+    assert np.array_equal(u, [oracle.item_uniform(X.THETA_SEED, X.THETA_IT, X.ST_THETA, i, 0) for i in range(140)])
+    z, v = X.beta_randoms(9, X.BETA_IT, 25)
+    for j in range(25):
+        raw = [oracle.item_uniform(9, X.BETA_IT, X.ST_BETA, j, ix) for ix in range(4)]
+        assert np.array_equal(v[:, j], [raw[1], raw[3]])
+        assert np.array_equal(z[:, j], [oracle.qnorm(raw[0]), oracle.qnorm(raw[2])])
+
+
+@pytest.mark.parametrize("name", THETA_CASES)
+def test_constructed_draw_theta_cases_decide_every_respondent(oracle, name):
+    """The conditions tests/test_gpu_draw_theta_constructed.py rests on: under both products' bounds and with and without
+    stabilisation no respondent is undecided; every kind is what draw_theta_cases() says it is; the near-ties lie within
+    1e-5 of a step of the CDF (the tight ones at 1e-11, at least four bounds away from it); and the CPU oracle draws the
+    reference's rows wherever its own sequential fp64 sums are decided."""
+    c = X.draw_theta_cases()[name]
+    y, kinds, k0 = c["y"], np.array(c["kinds"]), c["k0"]
+    n = y.shape[0]
+    for stabilise in (False, True):
+        idx = None
+        for product in ("fixed", "gemm"):
+            r = X.draw_theta_reference(name, stabilise, product)
+            assert r["undecided"].sum() == 0, (name, stabilise, product, np.flatnonzero(r["undecided"])[:8])
+            assert idx is None or np.array_equal(idx, r["index"])
+            idx = r["index"]
+            tie = kinds == "tie"
+            if tie.any():
+                delta = np.array(X.TIE_DELTAS)[k0[tie]]
+                assert (r["margin"][tie] <= 1e-5).all()
+                assert (np.abs(r["margin"][tie] / np.abs(delta) - 1) < 0.05).all(), r["margin"][tie] / np.abs(delta)
+                assert (4 * r["bound"][tie] < np.abs(delta)).all(), (r["bound"][tie].max(), product)
+                assert np.array_equal(idx[tie], np.where(delta > 0, X.TIE_ROWS[0], X.TIE_ROWS[1]))
+                assert set(np.abs(delta)) == {1e-6, 1e-9, 1e-11} and (delta > 0).any() and (delta < 0).any()
+                print(f"MEASURED {name} stabilise={stabilise} {product}: largest bound at a near-tie {r['bound'][tie].max():.2e}")
+        fin = np.isfinite(r["bound"])
+        print(f"MEASURED {name} stabilise={stabilise}: degenerate {r['degenerate']}, smallest margin {r['margin'].min():.2e}, "
+              f"largest bound {r['bound'][fin].max():.2e}")
+        if name.startswith("one_item"):
+            for kind in ("point", "last_row"):
+                assert np.array_equal(idx[kinds == kind], k0[kinds == kind]) and (kinds == kind).any()
+            assert (idx[kinds == "last_row"] == X.NGRID - 1).all()
+            assert (idx[kinds == "row_0"] == -1).all() and (kinds == "row_0").any()
+            assert (idx[kinds == "flat"] > 0).all() and (kinds == "flat").any()
+            assert ((idx[kinds == "peaked"] >= 0) == stabilise).all() and (kinds == "peaked").any()
+            assert (idx[kinds == "overflow"] == -1).all()
+            assert (kinds == "overflow").any() == (name == "one_item_fallback") == X.theta_hands_over(c["fstar"])
+            assert kinds[128] == "tie" and kinds[129] == "point"          # the ragged tile's respondents are not idle ones
+        else:
+            smooth = X.draw_theta_reference("dense_smooth", stabilise, "gemm")["index"]
+            sees = ~np.isnan(y[:, X.DENSE_J0]) if name == "dense_nan_cell" else ~np.isnan(y).all(axis=1)
+            if name in ("dense_nan_cell", "dense_nan_row"):
+                assert (idx[sees] < X.DENSE_K0).all() and sees.any() and (~sees).any()
+                assert np.array_equal(idx[~sees], smooth[~sees])            # a missing answer hides the NaN
+                assert (smooth[sees] >= X.DENSE_K0).any()                   # ... and for some who see it the draw moves
+                if name == "dense_nan_cell":
+                    assert (idx[~sees] >= X.DENSE_K0).any()                 # where 0 * NaN = NaN would have moved it
+            if name == "dense_overflow_item":
+                assert r["degenerate"] == int((y[:, 11] == -1.0).sum()) > 0 and (idx[y[:, 11] == -1.0] == -1).all()
+            if name in ("dense_smooth", "dense_pm800"):
+                assert r["degenerate"] == 0
+            assert 0.04 < np.isnan(y[1:]).mean() < 0.10
+        ro = X.draw_theta_reference(name, stabilise, "oracle")
+        th, deg = oracle.draw_theta(oracle.ItemStream(X.THETA_SEED), y, c["fstar"], it=X.THETA_IT, stabilise=stabilise)
+        rows = np.where(np.isnan(th), -1, np.rint((th + 5.0) / 0.01)).astype(np.int64)
+        ok = ~ro["undecided"]
+        assert ok.sum() >= n - 2 and np.array_equal(rows[ok], ro["index"][ok]) and deg == ro["degenerate"]
+
+
+@pytest.mark.parametrize("n", X.BETA_ORDERS)
+def test_constructed_draw_beta_cases_decide_every_step(oracle, n):
+    """The conditions tests/test_gpu_draw_beta_constructed.py rests on: no decision is undecided; the near-ties lie within 1e-5
+    of log u, on the side their name says; both branches of the kept log-likelihood occur, and each overflow branch; and
+    the CPU oracle's beta is the reference's."""
+    c = X.draw_beta_cases(n)
+    ref = X.draw_beta_reference(n)
+    col = {nm: j for j, nm in enumerate(c["names"])}
+    for nm, r in zip(c["names"], ref):
+        assert r["undecided"] == 0, (n, nm, r["margin"], r["bound"])
+    for nm, k, delta in X.BETA_TIES:
+        r = ref[col[nm]]
+        assert r["margin"][k] <= 1e-5 and abs(r["margin"][k] / abs(delta) - 1) < 0.05 and 4 * r["bound"][k] < abs(delta)
+        assert r["accept"][k] == (delta > 0)
+        if k == 1:
+            # behind a forced step 0, whose two sums differ by far more than the tie's margin: a kept sum from the wrong
+            # branch moves r by that difference and flips one tie of the pair
+            assert r["accept"][0] == (abs(delta) == 1e-6) and r["margin"][0] > 0.9
+            j = col[nm]
+            th, yy, ff = c["theta"], c["y"][:, j], c["f"][:, j]
+            lls = [-np.nansum(np.log1p(np.exp(-yy * (ff + b0 + th * c["beta"][1, j])))) for b0 in (c["beta"][0, j], r["proposal"][0])]
+            assert abs(lls[1] - lls[0]) > 1e3 * abs(delta), (nm, lls)
+        if n == 257:
+            # without row 256 (the one a loop that stops at 256 rows misses) r moves by far more than the tie's margin
+            j = col[nm]
+            y2 = c["y"][:, j].copy()
+            assert not np.isnan(y2[256])
+            y2[256] = np.nan
+            z, u = X.beta_randoms(c["seed"], c["it"], len(c["names"]))
+            r2 = X.beta_exact(c["beta"][:, j], c["theta"], y2, c["f"][:, j], c["pm"][:, j], c["ps"][:, j], c["step"][:, j], z[:, j], u[:, j])
+            assert abs(float(r2["r"][k] - r["r"][k])) > 1e3 * abs(delta), (nm, float(r2["r"][k] - r["r"][k]))
+    for nm in ("step0_zero", "step1_zero", "both_zero"):
+        r = ref[col[nm]]
+        assert all(r["accept"][k] and r["r"][k] == 0 for k in range(2) if c["step"][k, col[nm]] == 0.0)
+    a, b = ref[col["accept_then_decide"]], ref[col["reject_then_decide"]]
+    assert a["accept"][0] and not b["accept"][0] and a["margin"][0] > 0.9 and b["margin"][0] > 0.9
+    assert min(a["margin"][1], b["margin"][1]) > 1e-3
+    r = ref[col["both_overflow"]]
+    assert r["overflow"] == [(True, True), (True, True)] and r["accept"] == [False, False] and np.isnan(r["r"][0])
+    r = ref[col["proposal_overflow"]]
+    assert r["overflow"][0] == (True, False) and not r["accept"][0] and r["r"][0] == -np.inf
+    r = ref[col["current_overflow"]]
+    assert r["overflow"][0] == (False, True) and r["accept"][0] and r["r"][0] == np.inf and r["overflow"][1] == (False, False)
+    r = ref[col["proposal_overflow_s1"]]
+    assert r["overflow"][1] == (True, False) and not r["accept"][1]
+    assert not np.isnan(c["y"][:min(n, 2), [j for nm, j in col.items() if nm not in ("no_observed_row", "single_observed_row")]]).any()
+    assert np.isnan(c["y"][:, col["no_observed_row"]]).all() and (~np.isnan(c["y"][:, col["single_observed_row"]])).sum() == 1
+    worst = max(bd / mg for r in ref for bd, mg in zip(r["bound"], r["margin"]) if np.isfinite(mg))
+    print(f"MEASURED n={n}: worst bound / margin {worst:.3f}")
+    o = oracle.draw_beta(oracle.ItemStream(c["seed"]), c["beta"], c["theta"], c["y"], c["f"], c["pm"], c["ps"], c["step"], it=c["it"])
+    assert np.abs(o - np.stack([r["beta"] for r in ref], axis=1)).max() <= 1e-12
