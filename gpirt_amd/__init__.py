@@ -8,6 +8,8 @@ Layout:
   sampler.py       gpirtMCMC() mirror of the reference's R entry point, and the stage-driven Sampler
   chains.py ... acf.py        host side of the on-device posterior functionals (chains, quantiles, ppc, ranks, score,
                    shape, sumscore, equate, loo, acf): the C structs, the pooling of chains and the NumPy statement each is tested against
+  kernel.py        the covariance kernel of a handle (length scale, Matern 5/2 and 3/2): the NumPy statement, the rank
+                   certificate, one run per kernel and their comparison by elpd_loo
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

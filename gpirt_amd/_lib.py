@@ -447,6 +447,15 @@ class Options(C.Structure):
     ]
 
 
+class Kernel(C.Structure):
+    """gpirt_kernel: the covariance kernel of a handle (include/gpirt_hip.h, "the covariance kernel")"""
+    _fields_ = [("family", C.c_int), ("reserved0", C.c_int), ("length_scale", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
+KERNEL_SE, KERNEL_MATERN52, KERNEL_MATERN32 = 0, 1, 2
+KERNEL_FAMILIES = {"se": KERNEL_SE, "matern52": KERNEL_MATERN52, "matern32": KERNEL_MATERN32}
+LENGTH_SCALE_MIN, LENGTH_SCALE_MAX = 0.01, 1000.0
+
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _vp, _i64, _i32, _u64, _u32, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_double
@@ -472,6 +481,10 @@ SIGNATURES = {
     "gpirt_debug_poison_allocs": (_i32, [_vp, _i32]),
     "gpirt_debug_rs_trace": (_i32, [_vp, _i32]),
     "gpirt_debug_last_mcmc_fallbacks": (_i32, []),
+    "gpirt_kernel_default": (None, [C.POINTER(Kernel)]),
+    "gpirt_kernel_check": (_i32, [C.POINTER(Kernel), _i32, _dp, C.POINTER(_i32)]),
+    "gpirt_kernel_set": (_i32, [_vp, C.POINTER(Kernel)]),
+    "gpirt_kernel_get": (_i32, [_vp, C.POINTER(Kernel)]),
     "gpirt_se_kernel": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _dbl]),
     "gpirt_potrf_lower": (_i32, [_vp, _vp, _i64, _i64]),
     "gpirt_factor": (_i32, [_vp, _vp, _i64, _vp, _i64]),

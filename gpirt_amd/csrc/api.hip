@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 123; }     // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 124; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -201,6 +201,9 @@ int gpirt_version(void) { return 123; }     // 101: gpirt_options names kernel_f
                                             // 122: autocorrelation ESS (acf.hip: gpirt_acf_check, gpirt_sampler_acf_*, gpirt_acf_combine)
                                             // 123: residual correlations of the PPC (ppc_resid.hip: gpirt_sampler_ppc_resid_*,
                                             //      gpirt_ppc_resid_combine)
+                                            // 124: the covariance kernel per handle -- squared exponential with a length scale, Matern
+                                            //      5/2 and 3/2 (se_kernel.hip: gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set,
+                                            //      gpirt_kernel_get); gpirt_options, gpirt_run and the gpirt_mcmc* entries are unchanged
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -358,6 +361,49 @@ int gpirt_config_set(gpirt_handle_t h, const char* name, int value)
     return 0;
 }
 
+// The covariance kernel (include/gpirt_hip.h, "the covariance kernel"; device code and certificate: se_kernel.hip)
+void gpirt_kernel_default(gpirt_kernel* k)
+{
+    if (!k) return;
+    memset(k, 0, sizeof(*k));
+    k->family = GPIRT_KERNEL_SE;
+    k->length_scale = 1.0;
+}
+
+int gpirt_kernel_check(const gpirt_kernel* k, int kstar_rank, double* cert_out, int* min_rank_out)
+{
+    if (cert_out) *cert_out = 0.0;
+    if (min_rank_out) *min_rank_out = 0;
+    KernelSpec spec;
+    GP_TRY(kernel_spec_from(k, &spec));
+    return kernel_rank_check(spec, kstar_rank, cert_out, min_rank_out);
+}
+
+int gpirt_kernel_set(gpirt_handle_t h, const gpirt_kernel* k)
+{
+    GP_ARG(h != nullptr);
+    KernelSpec spec;
+    GP_TRY(kernel_spec_from(k, &spec));
+    if (h->live_samplers > 0) {
+        set_error("gpirt_kernel_set: %d sampler(s) created on this handle are alive; a sampler keeps the kernel it was created "
+                  "under -- destroy them first", h->live_samplers);
+        return GPIRT_E_ARG;
+    }
+    GP_HIP(hipStreamSynchronize(h->stream));
+    h->kern = spec;
+    if (h->aux) h->aux->kern = spec;
+    return 0;
+}
+
+int gpirt_kernel_get(gpirt_handle_t h, gpirt_kernel* k)
+{
+    GP_ARG(h && k);
+    gpirt_kernel_default(k);
+    k->family = h->kern.family;
+    k->length_scale = h->kern.length_scale;
+    return 0;
+}
+
 int gpirt_set_stream(gpirt_handle_t h, void* stream)
 {
     GP_ARG(h != nullptr);
@@ -407,7 +453,7 @@ int gpirt_se_kernel(gpirt_handle_t h, const double* d_x1, int64_t n1, const doub
                     double* d_out, int64_t ld, double jitter)
 {
     GP_ARG(h && d_x1 && d_x2 && d_out && n1 >= 0 && n2 >= 0 && ld >= n1);
-    return launch_se_kernel(h->stream, d_x1, n1, d_x2, n2, d_out, ld, jitter);
+    return launch_se_kernel(h->stream, h->kern, d_x1, n1, d_x2, n2, d_out, ld, jitter);
 }
 
 int gpirt_potrf_lower(gpirt_handle_t h, double* d_A, int64_t n, int64_t lda)
@@ -420,7 +466,7 @@ int gpirt_potrf_lower(gpirt_handle_t h, double* d_A, int64_t n, int64_t lda)
 int gpirt_factor(gpirt_handle_t h, const double* d_theta, int64_t n, double* d_L, int64_t ldl)
 {
     GP_ARG(h && d_theta && d_L && n >= 0 && ldl >= n);
-    GP_TRY(launch_se_kernel(h->stream, d_theta, n, d_theta, n, d_L, ldl, GPIRT_JITTER));
+    GP_TRY(launch_se_kernel(h->stream, h->kern, d_theta, n, d_theta, n, d_L, ldl, GPIRT_JITTER));
     GP_TRY(launch_potrf_lower(h, h->stream, d_L, n, ldl, true));
     GP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 8 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     GP_HIP(hipStreamSynchronize(h->stream));
@@ -431,7 +477,7 @@ int gpirt_factor(gpirt_handle_t h, const double* d_theta, int64_t n, double* d_L
         GP_TRY(potrf_guard_reset(h, h->stream));
         const int saved = h->cfg.panel;
         h->cfg.panel = 2;
-        int rc = launch_se_kernel(h->stream, d_theta, n, d_theta, n, d_L, ldl, GPIRT_JITTER);
+        int rc = launch_se_kernel(h->stream, h->kern, d_theta, n, d_theta, n, d_L, ldl, GPIRT_JITTER);
         if (!rc) rc = launch_potrf_lower(h, h->stream, d_L, n, ldl, true);
         h->cfg.panel = saved;
         GP_TRY(rc);
@@ -690,7 +736,7 @@ int gpirt_draw_fstar(gpirt_handle_t h, const double* d_f, const double* d_theta,
     for (int i = 0; i < GPIRT_NGRID; ++i) ts[i] = -5.0 + (double)i * 0.01;
     GP_HIP(hipMemcpyAsync(tstar, ts, sizeof(ts), hipMemcpyHostToDevice, h->stream));
     GP_HIP(hipStreamSynchronize(h->stream));   // ts is a stack buffer
-    GP_TRY(launch_se_kernel(h->stream, d_theta, n, tstar, N, kstar, n, 0.0));              // :17
+    GP_TRY(launch_se_kernel(h->stream, h->kern, d_theta, n, tstar, N, kstar, n, 0.0));              // :17
     GP_HIP(hipMemcpyAsync(rhs, kstar, sizeof(double) * (size_t)n * N, hipMemcpyDeviceToDevice, h->stream));
     GP_HIP(hipMemcpyAsync(rhs + (size_t)n * N, d_f, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToDevice, h->stream));
     GP_TRY(launch_trsm_lower(h, h->stream, d_L, n, ldl, rhs, N + m, n, false));             // :19 and :7 inner

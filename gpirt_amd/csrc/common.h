@@ -84,11 +84,21 @@ struct Config {
 };
 const Config& env_config();
 
+// The covariance kernel as the launches take it (se_kernel.hip), by value: gpirt_kernel with 1 / length_scale formed once on
+// the host.  is_default(): the reference's exp(-d^2 / 2), which keeps its own instantiation of the device code.
+struct KernelSpec {
+    int    family = GPIRT_KERNEL_SE;
+    double length_scale = 1.0;
+    double inv_ell = 1.0;
+    bool is_default() const { return family == GPIRT_KERNEL_SE && length_scale == 1.0; }
+};
+
 }  // namespace gpirt
 
 struct gpirt_handle_s {
     int          device = 0;
     gpirt::Config cfg;
+    gpirt::KernelSpec kern;              // gpirt_kernel_set; read by the operators and copied by gpirt_sampler_create
     hipStream_t  stream = nullptr;
     bool         own_stream = false;
     // small persistent workspace

@@ -35,11 +35,17 @@ int launch_gemm_splitk(hipStream_t stream, bool ta, bool tb, int64_t M, int64_t 
                        int64_t strideC, int nsplit, double* Cout, int64_t ldout, double beta_out);
 
 // se_kernel.hip
-int launch_se_kernel(hipStream_t stream, const double* x1, int64_t n1, const double* x2, int64_t n2,
+int launch_se_kernel(hipStream_t stream, KernelSpec kern, const double* x1, int64_t n1, const double* x2, int64_t n2,
                      double* out, int64_t ld, double jitter);
-// lower-triangular blocks only (upper blocks are left untouched): the potrf input
-int launch_se_kernel_lower(hipStream_t stream, const double* x, int64_t n, double* out, int64_t ld,
+// lower-triangular blocks only (upper blocks are left untouched): the potrf input.  fp32 (config C5): the default kernel only
+int launch_se_kernel_lower(hipStream_t stream, KernelSpec kern, const double* x, int64_t n, double* out, int64_t ld,
                            double jitter, bool fp32 = false);
+// host only (gpirt_kernel_check): the argument checks, and the rank certificate of include/gpirt_hip.h
+int kernel_spec_from(const gpirt_kernel* k, KernelSpec* out);       // GPIRT_E_ARG with the message
+int kernel_rank_check(const KernelSpec& kern, int kstar_rank, double* cert_out, int* min_rank_out);
+// the r first-kind Chebyshev nodes on [-5, 5] rounded to fp64 and the barycentric Lagrange basis at the GPIRT_NGRID grid points
+// (V[j + k N], evaluated in long double, rounded to fp64): what the rank-r draw_fstar holds on the device
+void cheb_nodes_basis(int r, std::vector<double>& nodes, std::vector<double>& V);
 
 // potrf.hip
 int launch_potrf_lower(gpirt_handle_t h, hipStream_t stream, double* A, int64_t n, int64_t lda,

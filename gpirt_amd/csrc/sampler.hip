@@ -37,6 +37,8 @@ struct gpirt_sampler_s {
     gpirt_handle_t h = nullptr;
     int64_t n = 0, m = 0, N = GPIRT_NGRID;
     gpirt_options opt{};
+    KernelSpec kern;                  // the handle's covariance kernel when the sampler was created (gpirt_kernel_set is
+                                      // refused while the sampler lives, so the two cannot part)
     RStream* rs = nullptr;            // borrowed (R-stream mode)
     // device state
     double *y = nullptr, *Ypm = nullptr, *theta = nullptr, *theta_new = nullptr, *f = nullptr,
@@ -646,7 +648,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
             if (!s->prep_valid) { GP_TRY(fstar_prep(s, h)); s->prep_valid = true; }   // (rows rebuilt above if they were stale)
             else if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
         } else {
-            GP_TRY(launch_se_kernel(st, s->theta, n, s->knodes, r, Bu, n, 0.0));
+            GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->knodes, r, Bu, n, 0.0));
             GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, Bu, r, n, false));
             GP_HIP(hipMemcpyAsync(Cu, Bu, sizeof(double) * (size_t)n * r, hipMemcpyDeviceToDevice, st));
             GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, Cu, r, n, true, true));
@@ -669,14 +671,14 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
     if (s->ext_grid) {
         // tmp = L^-1 k* came out of the bordered factorisation as the rows below L (N x n): one transpose puts it
         // where the solve used to leave it; only the m item columns are still solved for                      :19
-        if (!fused) GP_TRY(launch_se_kernel(st, s->theta, n, s->tstar, N, s->kstar, n, 0.0));  // :17 (for :25)
+        if (!fused) GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->tstar, N, s->kstar, n, 0.0));  // :17 (for :25)
         GP_TRY(launch_transpose(st, s->L + n, N, n, s->ldl, tmp, n));
         GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, W, m, n, false));                    // :7 inner
     } else {
         if (fused) {
-            GP_TRY(launch_se_kernel(st, s->theta, n, s->tstar, N, tmp, n, 0.0));               // :17
+            GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->tstar, N, tmp, n, 0.0));               // :17
         } else {
-            GP_TRY(launch_se_kernel(st, s->theta, n, s->tstar, N, s->kstar, n, 0.0));
+            GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->tstar, N, s->kstar, n, 0.0));
             GP_HIP(hipMemcpyAsync(tmp, s->kstar, sizeof(double) * (size_t)n * N, hipMemcpyDeviceToDevice, st));
         }
         GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, s->rhs, N + m, n, false));                // :19, :7 inner
@@ -814,9 +816,9 @@ int aux_join(gpirt_sampler_s* s, bool beta_too = true, bool z_too = true)
 int build_cov(gpirt_sampler_s* s)
 {
     hipStream_t st = s->h->stream;
-    GP_TRY(launch_se_kernel_lower(st, s->theta, s->n, s->L, s->ldl, GPIRT_JITTER, s->opt.kernel_fp32 != 0));
-    if (s->ext > 0 && !s->ext_grid) GP_TRY(launch_se_kernel(st, s->knodes, s->ext, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
-    if (s->ext_grid) GP_TRY(launch_se_kernel(st, s->tstar, s->N, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
+    GP_TRY(launch_se_kernel_lower(st, s->kern, s->theta, s->n, s->L, s->ldl, GPIRT_JITTER, s->opt.kernel_fp32 != 0));
+    if (s->ext > 0 && !s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->knodes, s->ext, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
+    if (s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->tstar, s->N, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
     return 0;
 }
 
@@ -827,7 +829,7 @@ int rebuild_rows(gpirt_sampler_s* s)
     hipStream_t st = s->h->stream;
     const int64_t n = s->n, cols = s->ext_grid ? s->N : s->kr;
     double* Bu = s->rhs;
-    GP_TRY(launch_se_kernel(st, s->theta, n, s->ext_grid ? s->tstar : s->knodes, cols, Bu, n, 0.0));
+    GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->ext_grid ? s->tstar : s->knodes, cols, Bu, n, 0.0));
     GP_TRY(launch_trsm_lower(s->h, st, s->L, n, s->ldl, Bu, cols, n, false));
     GP_TRY(launch_transpose(st, Bu, n, cols, n, s->L + n, s->ldl));
     s->rows_valid = true;
@@ -1164,6 +1166,22 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     s->h = h; s->n = n; s->m = m; s->N = GPIRT_NGRID;
     if (opts) s->opt = *opts; else gpirt_default_options(&s->opt);
     if (s->opt.m_total <= 0) s->opt.m_total = m;
+    s->kern = h->kern;
+    if (!s->kern.is_default()) {
+        // the single-precision build is the default kernel's (config C5); the rank form must pass the kernel's certificate
+        // (gpirt_kernel_check: under the default kernel every allowed rank is taken as before, r = 16 and 32 included)
+        if (s->opt.kernel_fp32) {
+            set_error("kernel_fp32 needs the default kernel (squared exponential, length_scale 1): the handle's kernel is family %d, "
+                      "length_scale %g", s->kern.family, s->kern.length_scale);
+            delete s;
+            return GPIRT_E_ARG;
+        }
+        if (s->opt.kstar_rank != 0 && s->opt.fstar_fused && s->opt.kstar_rank >= 16 && s->opt.kstar_rank <= 128 &&
+            (s->opt.kstar_rank % 16) == 0) {           // (any other value is refused below, with the message it always had)
+            const int rc_k = kernel_rank_check(s->kern, s->opt.kstar_rank, nullptr, nullptr);
+            if (rc_k) { delete s; return rc_k; }
+        }
+    }
     if (stream_mode(s)) {
         if (!rs) { set_error("GPIRT_RNG_RSTREAM needs an R stream state"); delete s; return GPIRT_E_ARG; }
         if (s->opt.item0 != 0 || s->opt.m_total != m) {
@@ -1270,8 +1288,11 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
             GP_A(s->rs_unitsP, unitsP.size());
             hipMemcpyAsync(s->rs_unitsP, unitsP.data(), unitsP.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st);
             // the structured form of the predictor's pass (rs_lr.hip): from 4096 rows on (below, a pass over L is a few MB anyway: 2048 x 256 runs at 270 it/s with it, 298 without),
-            // not with the single-precision kernel build (S then is not the kernel the basis represents, to 6e-8)
-            s->lr_on = h->cfg.rs_lr != 2 && n >= 4096 && !s->opt.kernel_fp32;
+            // not with the single-precision kernel build (S then is not the kernel the basis represents, to 6e-8),
+            // and only under the default kernel: rs_lr.hip builds its rank-64 basis from the unit squared exponential
+            // (rs_lr_nodes' K(c, c), the setup kernel's K(theta, c)), which says nothing about any other S.  With another kernel the
+            // dense predictor runs -- it reads only the fp32 copy of L.  The draws are the same either way: phase B verifies.
+            s->lr_on = h->cfg.rs_lr != 2 && n >= 4096 && !s->opt.kernel_fp32 && s->kern.is_default();
             std::vector<uint32_t> unitsL;
             if (s->lr_on) {
                 std::vector<double> nodes, wts, Mn;
@@ -1332,32 +1353,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         // Chebyshev points c_k, evaluated at the 1001 grid points in long double.  The integrand is entire and
         // the interval is 10 length-scales wide: r = 56 already reaches 1.3e-15 max-abs error (Lebesgue
         // constant 3.6), so K*^T (n x 1001) is replaced by its exact rank-r factorisation U V^T, U = K(theta, c).
+        // Neither the nodes nor V depend on the kernel; the error does (a shorter length scale needs a higher rank, a Matern
+        // kernel has no such form): gpirt_kernel_check's certificate, applied above, is computed from this same V.
         const int r = s->kr;
-        const long double pi = 3.141592653589793238462643383279502884L;
-        std::vector<long double> c((size_t)r), w((size_t)r);
-        nodes.resize((size_t)r); V.assign((size_t)(N * r), 0.0);
-        for (int k = 0; k < r; ++k) {
-            const long double a = (2 * k + 1) * pi / (2 * r);
-            c[(size_t)k] = 5.0L * cosl(a);
-            w[(size_t)k] = ((k & 1) ? -1.0L : 1.0L) * sinl(a);
-            nodes[(size_t)k] = (double)c[(size_t)k];
-        }
-        for (int64_t j = 0; j < N; ++j) {
-            const long double t = (long double)ts[(size_t)j];
-            int hit = -1;
-            long double den = 0.0L;
-            for (int k = 0; k < r; ++k) {
-                const long double d = t - (long double)nodes[(size_t)k];     // the nodes as the device will see them
-                if (d == 0.0L) { hit = k; break; }
-                den += w[(size_t)k] / d;
-            }
-            for (int k = 0; k < r; ++k) {
-                long double v;
-                if (hit >= 0) v = (k == hit) ? 1.0L : 0.0L;
-                else v = (w[(size_t)k] / (t - (long double)nodes[(size_t)k])) / den;
-                V[(size_t)(j + k * N)] = (double)v;
-            }
-        }
+        cheb_nodes_basis(r, nodes, V);                                     // (se_kernel.hip)
         hipMemcpyAsync(s->knodes, nodes.data(), sizeof(double) * (size_t)r, hipMemcpyHostToDevice, st);
         hipMemcpyAsync(s->kV, V.data(), sizeof(double) * (size_t)(N * r), hipMemcpyHostToDevice, st);
     }

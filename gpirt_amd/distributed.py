@@ -56,6 +56,16 @@ class ShardedSampler:
         sl = slice(self.lo, self.hi)
         self.engine = engine_factory(y[:, sl], np.asarray(theta_init, dtype=np.float64), pm[:, sl], ps[:, sl],
                                      step[:, sl], self.lo, m)
+        # The sharded path is checked against the CPU oracle (tests/test_distributed_cpu.py), which knows the reference's
+        # kernel alone: an engine on a handle with another kernel (Handle.set_kernel) is refused, not run unchecked.
+        eh = getattr(self.engine, "handle", None)
+        if eh is not None and hasattr(eh, "kernel"):
+            from . import kernel as K
+            if not K.is_default(eh.kernel()):
+                used = eh.kernel()
+                self.engine.close()
+                raise ValueError(f"ShardedSampler runs the default kernel only (squared exponential, length_scale 1); the "
+                                 f"engine's handle is set to {used}")
         self.chol = chol
         if chol not in ("replicated", "bcast", "distributed"):
             raise ValueError("chol must be 'replicated', 'bcast' or 'distributed'")

@@ -64,9 +64,10 @@ def _p(t):
 
 
 class Handle:
-    """gpirt_handle_t bound to a device and (by default) torch's current stream."""
+    """gpirt_handle_t bound to a device and (by default) torch's current stream.
+    kernel: the covariance kernel of the handle (set_kernel); None = the reference's, the squared exponential at length scale 1."""
 
-    def __init__(self, device: int | None = None, stream: torch.cuda.Stream | None = None):
+    def __init__(self, device: int | None = None, stream: torch.cuda.Stream | None = None, kernel=None):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.GpirtError(_lib.E_NODEVICE, "no GPU visible: the HIP path has no CPU fallback")
@@ -79,6 +80,24 @@ class Handle:
             check(self.lib.gpirt_create(C.byref(h), device, C.c_void_p(self.stream.cuda_stream)))
         self._h = h
         self._samplers = []                # weak references to the samplers created on this handle
+        if kernel is not None:
+            self.set_kernel(kernel)
+
+    # ---------------------------------------------------------------- the covariance kernel
+    def set_kernel(self, kernel):
+        """The handle's covariance kernel (gpirt_kernel_set): "se" | "matern52" | "matern32" (length scale 1), or
+        dict(family=..., length_scale=...); None = the default.  K(a, b) = k(|a - b| / length_scale), k(0) = 1.  se_kernel,
+        factor, draw_fstar and every Sampler created on the handle afterwards use it; refused while Samplers of the handle are
+        alive (close them first).  gpirt_amd.kernel has the NumPy statement and the one-call runs."""
+        from . import kernel as K
+        check(self.lib.gpirt_kernel_set(self._h, C.byref(K.struct(kernel))))
+
+    def kernel(self) -> dict:
+        """dict(family=<name>, length_scale=<float>) of the handle's kernel (gpirt_kernel_get)."""
+        from . import kernel as K
+        k = _lib.Kernel()
+        check(self.lib.gpirt_kernel_get(self._h, C.byref(k)))
+        return dict(family=K.family_name(k.family), length_scale=float(k.length_scale))
 
     @property
     def ptr(self):
@@ -151,7 +170,7 @@ class Handle:
 
     # ---------------------------------------------------------------- operators
     def se_kernel(self, x1: torch.Tensor, x2: torch.Tensor, jitter: float = 0.0) -> torch.Tensor:
-        """K(x1, x2): src/covariance-function.cpp:3-14 (+ jitter on i == j)."""
+        """K(x1, x2) under the handle's kernel: src/covariance-function.cpp:3-14 by default (+ jitter on i == j)."""
         out = colmajor(x1.shape[0], x2.shape[0], x1.device)
         check(self.lib.gpirt_se_kernel(self._h, _p(x1), x1.shape[0], _p(x2), x2.shape[0], _p(out), _ld(out), jitter))
         return out

@@ -61,7 +61,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -108,10 +108,55 @@ int         gpirt_debug_last_mcmc_fallbacks(void);
  * (TFLOP/s); used to calibrate the roofline. */
 int         gpirt_calibrate_mfma_f64(gpirt_handle_t h, double* tflops);
 
+/* ---------------------------------------------------------------- the covariance kernel -- */
+/* K(a, b) = k(|a - b| / length_scale) with k(0) = 1 for every family, S = K(theta, theta) + GPIRT_JITTER I:
+ *   GPIRT_KERNEL_SE        k(r) = exp(-r^2 / 2)                          (the reference's, at length_scale = 1)
+ *   GPIRT_KERNEL_MATERN52  k(r) = (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r
+ *   GPIRT_KERNEL_MATERN32  k(r) = (1 + a) exp(-a),           a = sqrt(3) r
+ * length_scale is finite, GPIRT_LENGTH_SCALE_MIN (the spacing of the theta grid) <= length_scale <= GPIRT_LENGTH_SCALE_MAX.
+ * There is NO signal variance: draw_fstar's standard deviation is the reference's s = 1 - sqrt(q) (src/draw-fstar.cpp:20),
+ * which is a statement about a prior with k(0) = 1 and means nothing for any other k(0).
+ *
+ * The kernel is a property of the HANDLE (like the switches of gpirt_config_set); gpirt_options and gpirt_run do not know it.
+ * gpirt_se_kernel, gpirt_factor and gpirt_draw_fstar read the handle's kernel, and so does every sampler created on the handle
+ * afterwards (a sampler keeps the kernel it was created under).  gpirt_mcmc, gpirt_mcmc_summary, gpirt_mcmc_chains and
+ * gpirt_mcmc_run create a handle of their own: they run the default kernel.  A handle that was never set, or was set to
+ * (GPIRT_KERNEL_SE, 1.0), computes bit for bit what it did before version 124.
+ *
+ * gpirt_kernel_check touches no device.  It validates k (GPIRT_E_ARG with a message: family outside 0..2, length_scale not
+ * finite or outside its range, a non-zero reserved word, kstar_rank not 0 or a multiple of 16 in 16..128) and decides whether
+ * gpirt_options.kstar_rank = kstar_rank may be used with it.  The Chebyshev nodes c and the basis V of the rank form do not
+ * depend on the kernel; the interpolation error does.  The certificate is max |K(theta, c) V^T - K(theta, theta*)| over theta
+ * and theta* on the whole grid, in long double with V rounded to fp64 as the device holds it (*cert_out; 0 for
+ * kstar_rank = 0).  A rank is accepted exactly when its certificate is no larger than that of (GPIRT_KERNEL_SE, 1.0, r = 48)
+ * from the same routine -- the line gpirt_options.kstar_rank draws for "exact to rounding".  A refusal is GPIRT_E_ARG, its
+ * message names the certificate and the smallest allowed rank that passes, which is also *min_rank_out (0: none does).  The
+ * Matern kernels are not analytic at r = 0 (the interpolation converges algebraically only): every kstar_rank > 0 is refused
+ * for them, *min_rank_out = 0.  cert_out and min_rank_out may be NULL.
+ * gpirt_sampler_create applies the same check to a handle whose kernel is not the default (under the default kernel every
+ * allowed rank is accepted, as before: r = 16 and r = 32 are the documented approximations); and kernel_fp32 needs the
+ * default kernel (GPIRT_E_ARG otherwise).
+ * gpirt_kernel_set drains the handle's stream; it is refused (GPIRT_E_ARG) while samplers created on the handle are alive. */
+#define GPIRT_KERNEL_SE        0
+#define GPIRT_KERNEL_MATERN52  1
+#define GPIRT_KERNEL_MATERN32  2
+#define GPIRT_LENGTH_SCALE_MIN 0.01
+#define GPIRT_LENGTH_SCALE_MAX 1000.0
+typedef struct gpirt_kernel {
+    int      family;          /* GPIRT_KERNEL_* */
+    int      reserved0;       /* must be 0 */
+    double   length_scale;
+    int64_t  reserved[4];     /* must be 0 */
+} gpirt_kernel;
+void gpirt_kernel_default(gpirt_kernel* k);                   /* GPIRT_KERNEL_SE, 1.0 */
+int  gpirt_kernel_check(const gpirt_kernel* k, int kstar_rank, double* cert_out, int* min_rank_out);
+int  gpirt_kernel_set(gpirt_handle_t h, const gpirt_kernel* k);
+int  gpirt_kernel_get(gpirt_handle_t h, gpirt_kernel* k);
+
 /* ---------------------------------------------------------------- operators ------------- */
-/* K(): src/covariance-function.cpp:3-14.  d_out (n1 x n2, leading dimension ld) =
- * exp(-0.5 (x1_i - x2_j)^2); `jitter` is added where i == j (src/gpirtMCMC.cpp:16; pass 0 for
- * K(theta, theta_star), src/draw-fstar.cpp:17). */
+/* K(): src/covariance-function.cpp:3-14 under the handle's kernel (above).  d_out (n1 x n2, leading dimension ld) =
+ * k(|x1_i - x2_j| / length_scale), by default exp(-0.5 (x1_i - x2_j)^2); `jitter` is added where i == j
+ * (src/gpirtMCMC.cpp:16; pass 0 for K(theta, theta_star), src/draw-fstar.cpp:17). */
 int gpirt_se_kernel(gpirt_handle_t h, const double* d_x1, int64_t n1, const double* d_x2,
                     int64_t n2, double* d_out, int64_t ld, double jitter);
 
