@@ -10,6 +10,8 @@ Layout:
                    shape, sumscore, equate, loo, acf): the C structs, the pooling of chains and the NumPy statement each is tested against
   kernel.py        the covariance kernel of a handle (length scale, Matern 5/2 and 3/2): the NumPy statement, the rank
                    certificate, one run per kernel and their comparison by elpd_loo
+  ell.py           the kernel's length scale as a parameter of the chain (a whitened Metropolis update on a grid): the
+                   NumPy statement of one update, the exact conditional posterior, the one-call run
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

@@ -19,6 +19,7 @@ NGRID = 1001
 RNG_RSTREAM, RNG_ITEM = 0, 1
 ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3, 4, 5, 6, 7
 ST_PPC = 8                        # the replicate of the posterior predictive checks (gpirt_amd.ppc)
+ST_ELL = 9                        # the two uniforms of a length-scale update (gpirt_amd.ell)
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
@@ -456,6 +457,19 @@ KERNEL_SE, KERNEL_MATERN52, KERNEL_MATERN32 = 0, 1, 2
 KERNEL_FAMILIES = {"se": KERNEL_SE, "matern52": KERNEL_MATERN52, "matern32": KERNEL_MATERN32}
 LENGTH_SCALE_MIN, LENGTH_SCALE_MAX = 0.01, 1000.0
 
+# the length scale as a parameter of the chain (include/gpirt_hip.h gpirt_ell; gpirt_amd.ell)
+ELL_MAX_POINTS = 1025
+ELL_COUNTS = ("updates", "accepted", "out_of_range", "failed")
+ELL_PARTS = ("copies", "solve", "factor", "product", "delta", "decide", "commit", "restore")     # "times" of ell_get, ms
+ELL_LAST = {-1: None, 0: "rejected", 1: "accepted", 2: "out_of_range", 3: "failed"}
+
+
+class Ell(C.Structure):
+    """gpirt_ell (include/gpirt_hip.h): the grid's size, the width, the index, the counters and the last update."""
+    _fields_ = [(k, C.c_int64) for k in ("points", "width", "index") + ELL_COUNTS + ("last", "last_proposed", "factorisations")] + [
+        (k, C.c_double) for k in ("length_scale", "lo", "hi", "last_u0", "last_u1")] + [("reserved", C.c_int64 * 4)]
+
+
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _vp, _i64, _i32, _u64, _u32, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_double
@@ -664,6 +678,13 @@ SIGNATURES = {
     "gpirt_prof_syrk": (_i32, [_vp, _i32, _i32, _dp, C.POINTER(_i64), _dp]),
     "gpirt_prof_syrk_bytes": (_i32, [_vp, _i32, _dp]),
     "gpirt_sampler_set_iteration": (_i32, [_vp, _i32]),
+    "gpirt_ell_grid": (_i32, [_dbl, _dbl, _i32, _dp]),
+    "gpirt_ell_check": (_i32, [_dbl, _dbl, _i32, _dp, _i32, _i32, C.POINTER(Kernel), C.POINTER(Options), _i64]),
+    "gpirt_sampler_ell_enable": (_i32, [_vp, _dbl, _dbl, _i32, _dp, _i32, _i32, _i32]),
+    "gpirt_sampler_draw_ell": (_i32, [_vp]),
+    "gpirt_sampler_ell_width": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ell_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ell_stats": (_i32, [_vp, C.POINTER(Ell)]),
 }
 
 _lib = None

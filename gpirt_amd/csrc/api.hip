@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 124; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 125; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -204,6 +204,8 @@ int gpirt_version(void) { return 124; }    // 101: gpirt_options names kernel_fp
                                             // 124: the covariance kernel per handle -- squared exponential with a length scale, Matern
                                             //      5/2 and 3/2 (se_kernel.hip: gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set,
                                             //      gpirt_kernel_get); gpirt_options, gpirt_run and the gpirt_mcmc* entries are unchanged
+                                            // 125: the length scale as a parameter of the chain (ell.hip, sampler.hip: gpirt_ell_grid,
+                                            //      gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -47,6 +47,17 @@ int kernel_rank_check(const KernelSpec& kern, int kstar_rank, double* cert_out, 
 // (V[j + k N], evaluated in long double, rounded to fp64): what the rank-r draw_fstar holds on the device
 void cheb_nodes_basis(int r, std::vector<double>& nodes, std::vector<double>& V);
 
+// ell.hip: the length-scale update's own kernels (gpirt_sampler_draw_ell) and the grid on the host
+// delta[j] = sum over item j's observed rows of t(y (f + mu)) - t(y (f' + mu)), nonfin[j] = its rows with a non-finite f'
+int launch_ell_delta(hipStream_t st, const double* f, const double* fp, const double* mu, const double* y, int64_t n, int64_t m,
+                     double* delta, int* nonfin);
+// rec = {dll, log_ratio, log_u, accept, nonfinite}, flag = 0 rejected / 1 accepted / 2 failed / 3 hang guard (info: the factor's two words)
+int launch_ell_decide(hipStream_t st, const double* delta, const int* nonfin, int64_t m, double lp_diff, double log_u,
+                      const int* info, double* rec, int* flag);
+int launch_ell_commit(hipStream_t st, const int* flag, double* f, const double* fp, int64_t count);     // f <- f' iff *flag == 1
+int ell_grid_check(double lo, double hi, int P);                      // GPIRT_E_ARG with the message
+void ell_grid_fill(double lo, double hi, int P, double* out);         // long double, rounded to fp64, the end points exact
+
 // potrf.hip
 int launch_potrf_lower(gpirt_handle_t h, hipStream_t stream, double* A, int64_t n, int64_t lda,
                        bool zero_upper, bool reset_info = true, int64_t extra_rows = 0);

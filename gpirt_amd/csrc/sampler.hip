@@ -33,6 +33,27 @@ const char* const kStageNames[ST_COUNT] = { "draw_f", "draw_fstar", "theta_gemm"
 
 }  // namespace
 
+// The length scale as a parameter of the chain (gpirt_sampler_ell_enable / gpirt_sampler_draw_ell; include/gpirt_hip.h).  The
+// index k is host state: every decision is read back once per update.
+struct EllState {
+    bool on = false;
+    int P = 0, w = 0, k = 0;
+    std::vector<double> grid, log_prior;
+    int64_t updates = 0, accepted = 0, out_of_range = 0, failed = 0, factorisations = 0;
+    int64_t last = -1, last_proposed = 0;
+    double last_u0 = 0.0, last_u1 = 0.0;
+    uint32_t t = 0;                   // draw_ell calls so far
+    double *Lsave = nullptr, *fprop = nullptr, *delta = nullptr, *rec = nullptr;    // device: ldl x n, n x m, m, 8
+    int *nonfin = nullptr, *flag = nullptr;                                         // device: m, 1
+    int* h_flag = nullptr;            // pinned
+    hipEvent_t ev = nullptr;          // the sampler's own stream has finished whatever still reads L
+    // with gpirt_sampler_enable_timing on: the device time of the last update's parts ("times" of gpirt_sampler_ell_get) --
+    // the copies (f -> nu's buffer, the factor buffer saved), the solve, the build and factorisation, the product, the three
+    // kernels, the copy back after a rejection
+    hipEvent_t tev[GPIRT_ELL_PARTS + 2] = {};
+    double part_ms[GPIRT_ELL_PARTS] = {};
+};
+
 struct gpirt_sampler_s {
     gpirt_handle_t h = nullptr;
     int64_t n = 0, m = 0, N = GPIRT_NGRID;
@@ -150,6 +171,7 @@ struct gpirt_sampler_s {
     EquateState equate;               // two-form score equating (gpirt_sampler_equate_enable; on == false: off)
     LooState loo;                     // PSIS-LOO (gpirt_sampler_loo_enable; on == false: off)
     AcfState acf;                     // autocorrelation ESS (gpirt_sampler_acf_enable; on == false: off)
+    EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
 };
 
 namespace {
@@ -836,15 +858,22 @@ int rebuild_rows(gpirt_sampler_s* s)
     return 0;
 }
 
+// S under the sampler's kernel, built and factored in place on the main stream -- do_factor without its side work (the early
+// block inverses, the Z prefill, a held-back draw_beta).  Whoever calls it has made sure nothing still reads the old factor.
+int factor_core(gpirt_sampler_s* s)
+{
+    invalidate_factor_products(s);
+    GP_TRY(build_cov(s));                                                                                  // :76-77
+    s->rows_valid = true;
+    return launch_potrf_lower(s->h, s->h->stream, s->L, s->n, s->ldl, false, !s->sticky_info, s->ext);     // :78
+}
+
 int do_factor(gpirt_sampler_s* s)
 {
     hipStream_t st = s->h->stream;
     GP_TRY(aux_join(s, false, true));     // nothing of the old factor may still be read when it is overwritten (a held-back
                                           // draw_beta does not read it: it is launched below, behind the factorisation)
-    invalidate_factor_products(s);
-    GP_TRY(build_cov(s));                                                                                  // :76-77
-    s->rows_valid = true;
-    GP_TRY(launch_potrf_lower(s->h, st, s->L, s->n, s->ldl, false, !s->sticky_info, s->ext)); // :78
+    GP_TRY(factor_core(s));
     // The low-rank draw_fstar's transposed solve (fstar_prep) goes through the inverses of L's 1024 x 1024 diagonal blocks:
     // ~5 GFLOP to build at n = 8192, and they only need the DIAGONAL blocks, final panel by panel.  Those of every outer
     // panel but the last are built on the sampler's own stream while the last outer panel is factored (16 + 8 whole-CU
@@ -920,6 +949,169 @@ int factor_guard_sync(gpirt_sampler_s* s)
     GP_HIP(hipStreamSynchronize(h->stream));
     if (h->h_info[1] != 0 && s->factor_fresh && h->cfg.panel != 2) GP_TRY(recover_factor(s));
     return 0;
+}
+
+// ---- the length scale as a parameter of the chain (include/gpirt_hip.h; the kernels are ell.hip's) ------------------------------
+void ell_free(EllState* e)
+{
+    for (void* p : { (void*)e->Lsave, (void*)e->fprop, (void*)e->delta, (void*)e->rec, (void*)e->nonfin, (void*)e->flag })
+        if (p) hipFree(p);
+    if (e->h_flag) hipHostFree(e->h_flag);
+    if (e->ev) hipEventDestroy(e->ev);
+    for (hipEvent_t t : e->tev) if (t) hipEventDestroy(t);
+    const uint32_t calls = e->t;          // t counts the sampler's draw_ell calls: enabling again does not replay their uniforms
+    *e = EllState();
+    e->t = calls;
+}
+
+// The main stream waits for whatever the sampler's own stream still has in flight -- the early block inverses read L, a
+// deferred draw_beta writes beta and mu -- WITHOUT dropping a prefilled Z, which aux_join's z_too would: the update touches
+// neither Z nor the iteration it is keyed by.
+int ell_join(gpirt_sampler_s* s)
+{
+    GP_TRY(aux_join(s, true, false));
+    if (s->haux) {
+        GP_HIP(hipEventRecord(s->ell.ev, s->haux->stream));
+        GP_HIP(hipStreamWaitEvent(s->h->stream, s->ell.ev, 0));
+    }
+    return 0;
+}
+
+void ell_set_kernel(gpirt_sampler_s* s, double ell)
+{
+    s->kern.length_scale = ell;
+    s->kern.inv_ell = 1.0 / ell;
+}
+
+// a factor nobody has looked at yet: its info words would be lost under the next factorisation's
+int ell_settle_factor(gpirt_sampler_s* s)
+{
+    if (!s->factor_fresh) return 0;
+    gpirt_handle_t h = s->h;
+    hipStream_t st = h->stream;
+    GP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    if (h->h_info[1] != 0) {
+        // a hang-guard expiry nothing has consumed: repaired in place, and the words read again, as gpirt_sampler_check does
+        if (h->cfg.panel == 2) return report_panel_guard(h, h->h_info, st);
+        GP_TRY(recover_factor(s));
+        GP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
+        GP_HIP(hipStreamSynchronize(st));
+        if (h->h_info[1] != 0) return report_panel_guard(h, h->h_info, st);
+    }
+    if (*h->h_info > 0) {
+        set_error("chol(): decomposition failed (leading minor of order %d is not positive definite)", *h->h_info);
+        return *h->h_info;
+    }
+    return 0;
+}
+
+int do_draw_ell(gpirt_sampler_s* s)
+{
+    EllState& e = s->ell;
+    gpirt_handle_t h = s->h;
+    hipStream_t st = h->stream;
+    const int64_t n = s->n, m = s->m;
+    GP_TRY(ell_settle_factor(s));
+    // the call is counted, and its pair of uniforms consumed, when it ends in one of the four outcomes: an update that returns
+    // an error has not happened (updates = accepted + rejected + out_of_range + failed at all times)
+    const uint32_t t = e.t + 1;
+    const double u0 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, 0, 0), u1 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, 0, 1);
+    auto counted = [&]() { e.t = t; e.updates += 1; e.last_u0 = u0; e.last_u1 = u1; };
+    const int w = e.w;
+    int j = (int)floor(u0 * (double)(2 * w));
+    if (j > 2 * w - 1) j = 2 * w - 1;
+    const int kp = e.k + (j < w ? j - w : j - w + 1);
+    if (kp < 0 || kp >= e.P) { counted(); e.last_proposed = kp; e.out_of_range += 1; e.last = 2; return 0; }      // (the proposal is symmetric: nothing else runs)
+    GP_TRY(ell_join(s));
+    s->factor_fresh = false;
+    const bool timed = s->timing;
+    if (timed)
+        for (hipEvent_t& t : e.tev) if (!t) GP_HIP(hipEventCreate(&t));
+    auto tick = [&](int i) { if (timed) hipEventRecord(e.tev[i], st); };
+    const KernelSpec kern_before = s->kern;
+    const bool rows_before = s->rows_valid;
+    const size_t fbytes = sizeof(double) * (size_t)(n * m), lbytes = sizeof(double) * (size_t)(s->ldl * n);
+    // everything back as it was: the saved buffer holds the factor AND the rows below it
+    auto restore = [&]() -> int {
+        s->kern = kern_before;
+        s->rows_valid = rows_before;
+        invalidate_factor_products(s);
+        GP_HIP(hipMemcpyAsync(s->L, e.Lsave, lbytes, hipMemcpyDeviceToDevice, st));
+        return 0;
+    };
+    // nu = L^-1 f (NU is free between steps), then the proposal's factor in place of the saved one
+    tick(0);
+    GP_HIP(hipMemcpyAsync(s->NU, s->f, fbytes, hipMemcpyDeviceToDevice, st));
+    GP_HIP(hipMemcpyAsync(e.Lsave, s->L, lbytes, hipMemcpyDeviceToDevice, st));
+    tick(1);
+    GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, s->NU, m, n, false));
+    tick(2);
+    ell_set_kernel(s, e.grid[(size_t)kp]);
+    int rc = factor_core(s);
+    e.factorisations += 1;
+    tick(3);
+    const double lp_diff = e.log_prior[(size_t)kp] - e.log_prior[(size_t)e.k], log_u = log(u1);
+    for (int attempt = 0; !rc; ++attempt) {
+        rc = launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->NU, n, 0.0, e.fprop, n);
+        tick(4);
+        if (!rc) rc = launch_ell_delta(st, s->f, e.fprop, s->mu, s->y, n, m, e.delta, e.nonfin);
+        tick(5);
+        if (!rc) rc = launch_ell_decide(st, e.delta, e.nonfin, m, lp_diff, log_u, h->d_info, e.rec, e.flag);
+        tick(6);
+        if (!rc) rc = launch_ell_commit(st, e.flag, s->f, e.fprop, n * m);
+        tick(7);
+        if (rc) break;
+        // the decision: 4 bytes and a stream synchronisation, as gpirt_sampler_check's
+        if (hipMemcpyAsync(e.h_flag, e.flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) {
+            set_error("length-scale update: reading the decision failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = GPIRT_E_HIP;
+            break;
+        }
+        if (*e.h_flag != 3) break;
+        // a hang-guard expiry in the proposal's factor (nothing was committed): once more with the launch-per-step panel
+        if (attempt > 0 || h->cfg.panel == 2) {
+            hipMemcpyAsync(h->h_info, h->d_info, 8 * sizeof(int), hipMemcpyDeviceToHost, st);
+            hipStreamSynchronize(st);
+            rc = report_panel_guard(h, h->h_info, st);
+            break;
+        }
+        s->factor_fresh = true;
+        rc = recover_factor(s);
+        s->factor_fresh = false;
+        e.factorisations += 1;
+    }
+    if (rc) { restore(); return rc; }
+    // the parts' device time, once the stream has passed the last event (timing on: one more synchronisation)
+    auto times = [&](bool restored) -> int {
+        if (!timed) return 0;
+        tick(9);
+        GP_HIP(hipEventSynchronize(e.tev[9]));
+        for (int i = 0; i < GPIRT_ELL_PARTS; ++i) {
+            float ms = 0.f;
+            if (i < 7) hipEventElapsedTime(&ms, e.tev[i], e.tev[i + 1]);
+            else if (restored) hipEventElapsedTime(&ms, e.tev[8], e.tev[9]);
+            e.part_ms[i] = ms;
+        }
+        return 0;
+    };
+    counted();
+    e.last_proposed = kp;
+    if (*e.h_flag == 1) {
+        e.k = kp; e.accepted += 1; e.last = 1;
+        invalidate_factor_products(s);        // (the solve for nu may have left block inverses of the OLD factor behind)
+        return times(false);
+    }
+    if (*e.h_flag == 2) {
+        e.failed += 1; e.last = 3;
+        GP_HIP(hipMemsetAsync(h->d_info, 0, sizeof(int), st));       // a non-positive minor of the PROPOSAL is not the chain's
+    } else {
+        e.last = 0;
+    }
+    tick(8);                                  // (the copy back alone: from here to the last event)
+    GP_TRY(restore());
+    return times(true);
 }
 
 // draw_theta's CDF came out 0/0 for some respondents: the reference reads theta_star[N] out of bounds there
@@ -1428,6 +1620,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     loo_free(&s->loo);
     acf_free(&s->acf);
     score_free(&s->score);
+    ell_free(&s->ell);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -2242,6 +2435,122 @@ int gpirt_score_predict_combine(gpirt_handle_t h, int chains, const void* const*
     return pred_combine(h, chains, d_states, out);
 }
 
+// ---- the length scale as a parameter of the chain -------------------------------------------------------------------------
+int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, const double* log_prior, int width, int k0, int on)
+{
+    GP_ARG(s != nullptr);
+    EllState& e = s->ell;
+    if (!on) {
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        ell_free(&e);
+        return 0;
+    }
+    if (!s->initialised) { set_error("gpirt_sampler_ell_enable needs an initialised sampler (gpirt_sampler_init)"); return GPIRT_E_ARG; }
+    gpirt_kernel kk;
+    gpirt_kernel_default(&kk);
+    kk.family = s->kern.family; kk.length_scale = s->kern.length_scale;
+    GP_TRY(gpirt_ell_check(lo, hi, P, log_prior, width, k0, &kk, &s->opt, s->m));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    ell_free(&e);
+    const int64_t n = s->n, m = s->m;
+    auto fail = [&](int rc, const char* what) { set_error("length scale: %s failed", what); ell_free(&e); return rc; };
+    if (hipMalloc((void**)&e.Lsave, sizeof(double) * (size_t)(s->ldl * n)) != hipSuccess ||
+        hipMalloc((void**)&e.fprop, sizeof(double) * (size_t)(n * m)) != hipSuccess ||
+        hipMalloc((void**)&e.delta, sizeof(double) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&e.rec, sizeof(double) * 8) != hipSuccess ||
+        hipMalloc((void**)&e.nonfin, sizeof(int) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&e.flag, sizeof(int)) != hipSuccess) return fail(GPIRT_E_ALLOC, "hipMalloc");
+    if (hipHostMalloc((void**)&e.h_flag, sizeof(int), hipHostMallocDefault) != hipSuccess) return fail(GPIRT_E_ALLOC, "the pinned allocation");
+    if (hipEventCreateWithFlags(&e.ev, hipEventDisableTiming) != hipSuccess) return fail(GPIRT_E_HIP, "hipEventCreate");
+    hipStream_t st = s->h->stream;
+    if (hipMemsetAsync(e.fprop, 0, sizeof(double) * (size_t)(n * m), st) != hipSuccess ||
+        hipMemsetAsync(e.delta, 0, sizeof(double) * (size_t)m, st) != hipSuccess ||
+        hipMemsetAsync(e.rec, 0, sizeof(double) * 8, st) != hipSuccess ||
+        hipMemsetAsync(e.nonfin, 0, sizeof(int) * (size_t)m, st) != hipSuccess ||
+        hipMemsetAsync(e.flag, 0, sizeof(int), st) != hipSuccess) return fail(GPIRT_E_HIP, "hipMemsetAsync");
+    e.P = P; e.w = width;
+    e.grid.resize((size_t)P); e.log_prior.resize((size_t)P);
+    ell_grid_fill(lo, hi, P, e.grid.data());
+    for (int k = 0; k < P; ++k) {
+        const long double l = logl((long double)e.grid[(size_t)k]);
+        e.log_prior[(size_t)k] = log_prior ? log_prior[k] : (double)(-(l * l) / 2.0L);
+        if (k0 < 0 && e.grid[(size_t)k] == s->kern.length_scale) k0 = k;
+    }
+    e.k = k0;
+    e.on = true;
+    if (e.grid[(size_t)k0] != s->kern.length_scale) {
+        // the chain starts at ell_k0: its factor, through the same core as every other
+        int rc = ell_settle_factor(s);
+        if (!rc) rc = ell_join(s);
+        if (!rc) {
+            ell_set_kernel(s, e.grid[(size_t)k0]);
+            rc = factor_core(s);
+            s->factor_fresh = true;
+        }
+        if (rc) { ell_free(&e); return rc; }
+    }
+    return 0;
+}
+
+int gpirt_sampler_draw_ell(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    return do_draw_ell(s);
+}
+
+int gpirt_sampler_ell_width(gpirt_sampler_t s, int w)
+{
+    GP_ARG(s != nullptr);
+    GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    if (w < 1 || w > s->ell.P - 1) {
+        set_error("length scale: width = %d, it must lie in 1 .. P - 1 = %d", w, s->ell.P - 1);
+        return GPIRT_E_ARG;
+    }
+    s->ell.w = w;
+    return 0;
+}
+
+int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    EllState& e = s->ell;
+    GP_TRY(needs(e.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    const int64_t nm = s->n * s->m;
+    const int64_t counts[4] = { e.updates, e.accepted, e.out_of_range, e.failed };
+    const int64_t index = e.k;
+    const void* host = nullptr; const void* dev = nullptr; int64_t want = 0;
+    if (strcmp(name, "grid") == 0) { host = e.grid.data(); want = 8 * (int64_t)e.P; }
+    else if (strcmp(name, "log_prior") == 0) { host = e.log_prior.data(); want = 8 * (int64_t)e.P; }
+    else if (strcmp(name, "index") == 0) { host = &index; want = 8; }
+    else if (strcmp(name, "counts") == 0) { host = counts; want = 32; }
+    else if (strcmp(name, "nu") == 0) { dev = s->NU; want = 8 * nm; }
+    else if (strcmp(name, "f_prop") == 0) { dev = e.fprop; want = 8 * nm; }
+    else if (strcmp(name, "delta") == 0) { dev = e.delta; want = 8 * s->m; }
+    else if (strcmp(name, "record") == 0) { dev = e.rec; want = 40; }
+    else if (strcmp(name, "times") == 0) { host = e.part_ms; want = 8 * GPIRT_ELL_PARTS; }
+    else { set_error("unknown length-scale array '%s'", name); return GPIRT_E_ARG; }
+    if (bytes != want) { set_error("length scale: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    if (host) { memcpy(h_out, host, (size_t)want); return 0; }
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out)
+{
+    GP_ARG(s && out);
+    const EllState& e = s->ell;
+    GP_TRY(needs(e.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    memset(out, 0, sizeof(*out));
+    out->points = e.P; out->width = e.w; out->index = e.k;
+    out->updates = e.updates; out->accepted = e.accepted; out->out_of_range = e.out_of_range; out->failed = e.failed;
+    out->last = e.last; out->last_proposed = e.last_proposed; out->factorisations = e.factorisations;
+    out->length_scale = e.grid[(size_t)e.k]; out->lo = e.grid.front(); out->hi = e.grid.back();
+    out->last_u0 = e.last_u0; out->last_u1 = e.last_u1;
+    return 0;
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -2372,6 +2681,15 @@ int gpirt_sampler_panel_copy_part(gpirt_sampler_t s, int64_t p, int half, double
 int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
 {
     GP_ARG(dst && src && dst->initialised && src->initialised && dst->n == src->n && dst->m == src->m && dst->h == src->h);
+    if (dst->ell.on || src->ell.on) {
+        set_error("gpirt_sampler_copy_state is not defined while the length-scale update is on (the index and its tables are not copied)");
+        return GPIRT_E_ARG;
+    }
+    if (dst->kern.family != src->kern.family || dst->kern.length_scale != src->kern.length_scale) {
+        // (only a length-scale update can part two samplers of one handle: the copied factor would not be dst's kernel's)
+        set_error("gpirt_sampler_copy_state: the samplers' kernels differ (length_scale %g and %g)", dst->kern.length_scale, src->kern.length_scale);
+        return GPIRT_E_ARG;
+    }
     hipStream_t st = dst->h->stream;
     const int64_t n = dst->n, m = dst->m, N = dst->N;
     GP_TRY(aux_join(dst)); GP_TRY(aux_join(src));

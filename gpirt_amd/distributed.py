@@ -321,6 +321,16 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the autocorrelation ESS is not offered for item shards (the respondents' and the "
                          "total log-likelihood series run over all items; each rank holds its own columns)")
 
+    # -- the length scale in the chain (gpirt_amd.ell): the likelihood change of an update runs over ALL items and the factor is
+    # the ranks' common one
+    def ell_enable(self, lo=0.25, hi=4.0, points=129, log_prior=None, width=4, k0=None, on=True):
+        raise ValueError("ShardedSampler: the length-scale update is not offered for item shards (its likelihood change runs "
+                         "over all items, and each rank holds its own columns of f)")
+
+    def draw_ell(self):
+        raise ValueError("ShardedSampler: the length-scale update is not offered for item shards (its likelihood change runs "
+                         "over all items, and each rank holds its own columns of f)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

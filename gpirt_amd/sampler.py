@@ -1449,6 +1449,60 @@ class Sampler:
         from . import acf as AC
         return AC.combine(self.handle, [self], signs=[sign], top=top)
 
+    # -- the kernel's length scale as a parameter of the chain (include/gpirt_hip.h gpirt_sampler_ell_*, gpirt_amd.ell)
+    def ell_enable(self, lo=0.25, hi=4.0, points=129, log_prior=None, width=4, k0=None, on=True):
+        """Put the length scale on the logarithmic grid ell_k = lo (hi / lo)^(k / (points - 1)) with the prior mass log_prior
+        (`points` finite values; None: -(ln ell_k)^2 / 2) and the proposal width `width` (1 .. points - 1), start the chain
+        at index k0 (None: the index of the length scale the sampler has) and factor under ell_k0.  After init().  Refused
+        with the reason: rng="reference", kernel_fp32, an item shard, a length scale that is not on the grid, a kstar_rank
+        whose certificate fails at lo.  on=False frees the state (the arguments are not looked at); a sampler it was never
+        switched on for computes what it always did.  The handle's kernel (Handle.kernel()) is not touched."""
+        if not on:
+            check(self.lib.gpirt_sampler_ell_enable(self._s, 0.0, 0.0, 0, None, 0, 0, 0))
+            self._ell_points = 0
+            return
+        lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float64)
+        if lp is not None and lp.shape != (int(points),):
+            raise ValueError(f"ell_enable: log_prior must hold points = {int(points)} values")
+        check(self.lib.gpirt_sampler_ell_enable(self._s, float(lo), float(hi), int(points), None if lp is None else _ptr(lp),
+                                                int(width), -1 if k0 is None else int(k0), 1))
+        self._ell_points = int(points)
+
+    def draw_ell(self):
+        """One prior-whitened Metropolis update of the length scale (nu = L^-1 f held fixed): see gpirt_amd.ell.step_exact."""
+        self._call("gpirt_sampler_draw_ell")
+
+    def ell_width(self, w: int):
+        """The proposal width from the next update on (1 .. points - 1)."""
+        check(self.lib.gpirt_sampler_ell_width(self._s, int(w)))
+
+    def ell_get(self, name: str) -> np.ndarray:
+        """One array by name: grid, log_prior (points), index (int64, 1), counts (int64: updates, accepted, out_of_range, failed)
+        and, of the last update that reached the device, nu, f_prop (n x m), delta (m), record (dll, log_ratio, log_u, accept,
+        nonfinite) and times (ms of device time with enable_timing() on: copies, solve, factor, product, delta, decide, commit,
+        restore)."""
+        P = getattr(self, "_ell_points", 0)
+        if name in ("index", "counts"):
+            out = np.empty(1 if name == "index" else 4, dtype=np.int64)
+        elif name in ("nu", "f_prop"):
+            out = np.empty((self.n, self.m), order="F")
+        else:
+            out = np.empty({"delta": self.m, "record": 5, "times": len(_lib.ELL_PARTS)}.get(name, P))
+        self._get_into("gpirt_sampler_ell_get", name, out)
+        return out
+
+    def ell(self) -> dict:
+        """The length scale's state (gpirt_sampler_ell_stats): index, length_scale, points, width, lo, hi, the counters
+        (updates, accepted, out_of_range, failed), accept_rate, factorisations, and of the last update `last` ("accepted",
+        "rejected", "out_of_range", "failed" or None), last_proposed and its two uniforms."""
+        e = _lib.Ell()
+        check(self.lib.gpirt_sampler_ell_stats(self._s, C.byref(e)))
+        out = {k: int(getattr(e, k)) for k in ("index", "points", "width", "last_proposed", "factorisations") + _lib.ELL_COUNTS}
+        out.update({k: float(getattr(e, k)) for k in ("length_scale", "lo", "hi", "last_u0", "last_u1")})
+        out["last"] = _lib.ELL_LAST[int(e.last)]
+        out["accept_rate"] = out["accepted"] / out["updates"] if out["updates"] else float("nan")
+        return out
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

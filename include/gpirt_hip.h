@@ -54,14 +54,15 @@ enum { GPIRT_RNG_RSTREAM = 0, GPIRT_RNG_ITEM = 1 };
 enum {
     GPIRT_ST_INIT_F = 1, GPIRT_ST_INIT_BETA = 2, GPIRT_ST_F_Z = 3, GPIRT_ST_F_ESS = 4,
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
-    GPIRT_ST_PPC = 8      /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
+    GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
+    GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update (gpirt_sampler_draw_ell); nothing else draws from it */
 };
 
 typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2037,6 +2038,77 @@ int gpirt_sampler_acf_get(gpirt_sampler_t s, const char* name, void* h_out, int6
 int gpirt_sampler_acf_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
 int gpirt_acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out);
 
+/* ------------------------------------------------------ the kernel's length scale as a parameter of the chain ---------- */
+/* Library version 125.  One length scale ell, shared by all items, is updated INSIDE the chain so that theta, the IRFs and
+ * every analysis block average over it; the family stays the handle's, there is still no signal variance.  Stage API only:
+ * gpirt_sampler_step, gpirt_mcmc_run and the whole-call entries do not know it, and a sampler on which
+ * gpirt_sampler_ell_enable was never called (or was called with on = 0) computes bit for bit what it did before.
+ *
+ * ell lives on a fixed logarithmic grid, ell_k = lo (hi / lo)^(k / (P - 1)), k = 0 .. P - 1, 2 <= P <= GPIRT_ELL_MAX_POINTS,
+ * GPIRT_LENGTH_SCALE_MIN <= lo < hi <= GPIRT_LENGTH_SCALE_MAX: computed once on the host in long double, rounded to fp64, the
+ * end points exact (gpirt_ell_grid; a grid that is not strictly increasing in fp64 is refused).  The chain's state is the
+ * index k.  log_prior[k] (P finite doubles) is a mass on the grid, i.e. a density with respect to log ell; NULL: the default
+ * -(ln ell_k)^2 / 2, a log-normal with median 1 and log-sd 1.
+ *
+ * gpirt_sampler_draw_ell is the prior-whitened Metropolis step of Murray & Adams (2010, section 2.2): nu = L(ell_k)^-1 f is
+ * held fixed, not f; theta, beta and mu are held fixed; L is the sampler's current factor of K(theta, theta; ell_k) + jitter.
+ *   t        the number of draw_ell calls on this sampler so far, counted from 1
+ *   u0, u1   item_uniform(seed, t, GPIRT_ST_ELL, 0, 0) and (.., 0, 1): what gpirt_item_uniforms(h, seed, t, 9, 0, 1, 2, .) writes
+ *   j = min(floor(u0 2w), 2w - 1), d = j - w for j < w, else j - w + 1; k' = k + d (width 1 <= w <= P - 1).  k' outside
+ *   0 .. P - 1: rejected and counted in out_of_range, nothing else runs (the proposal is symmetric).
+ *   nu = L^-1 f (all n x m values); S under ell_k' is built and factored (ONE factorisation per update); f' = L' nu.
+ *   dll = sum over observed cells of [t(y (f + mu)) - t(y (f' + mu))], t(a) = log(1 + exp(-a)) in the form of csrc/ll_fast.h,
+ *   formed cell by cell as a difference of terms; per item in a fixed order (256 threads over ascending rows, a fixed tree),
+ *   then over the items in ascending order: deterministic.  Cells with NaN y are skipped.
+ *   accepted iff log(u1) < dll + log_prior[k'] - log_prior[k].
+ *   Accepted: f <- f', k <- k', the sampler's kernel is ell_k'; L, the rows below it and the cached products are bit for bit
+ *   what gpirt_sampler_factor leaves for (theta, ell_k').  Rejected, out of range or failed: f, L, the rows below it, theta,
+ *   beta, mu and the sampler's kernel are byte-identical to before the call; only the counters move.  A proposal whose factor
+ *   reports a non-positive minor, or whose f' or dll is not finite, is rejected and counted in `failed`: not an error.
+ * A call that returns an error (a HIP error, a hang-guard expiry that could not be repaired) has not happened: it is not
+ * counted, t does not advance, and updates = accepted + rejected + out_of_range + failed always.  A factor nobody has checked
+ * yet (gpirt_sampler_step directly before) is checked first, a hang-guard expiry in it repaired as gpirt_sampler_check does.
+ * The host reads the decision once per update (4 bytes and a stream synchronisation).  The handle's kernel
+ * (gpirt_kernel_get) is not touched: it stays what new samplers of the handle start from.
+ *
+ * gpirt_ell_check touches no device: every refusal of gpirt_sampler_ell_enable (GPIRT_E_ARG, the message names the reason) --
+ * the grid, a non-finite log_prior, width outside 1 .. P - 1, k0 outside -1 .. P - 1 (-1: the index of the handle's length
+ * scale); with opts: GPIRT_RNG_RSTREAM (R's stream has no such draw), kernel_fp32, an item shard (item0 != 0 or
+ * m_total != m); with kern: a length_scale that is not a point of the grid, and a kstar_rank > 0 whose gpirt_kernel_check
+ * certificate fails at ell_0 = lo (the certificate grows as the length scale shrinks; a Matern family needs kstar_rank = 0).
+ * kern and opts may be NULL (those checks are skipped).
+ *
+ * gpirt_sampler_ell_enable (after gpirt_sampler_init) applies that check to the sampler's own kernel and options, keeps the
+ * tables, zeroes the counters (not t: the call count runs over the sampler's life, so enabling again never replays a pair of
+ * uniforms), sets the sampler's kernel to ell_k0 and factors (nothing is factored when ell_k0 is the
+ * length scale it already has).  on = 0 frees the state and leaves the sampler's kernel as it is.
+ * gpirt_sampler_ell_get, by name: "grid", "log_prior" (P doubles), "index" (1 int64), "counts" (4 int64: updates, accepted,
+ * out_of_range, failed) and, of the last update that reached the device, "nu", "f_prop" (n x m doubles), "delta" (m doubles)
+ * and "record" (5 doubles: dll, log_ratio, log_u, accept, nonfinite); "times" (GPIRT_ELL_PARTS doubles, milliseconds of device
+ * time of that update's parts with gpirt_sampler_enable_timing on, else 0: the copies f -> nu's buffer and factor buffer ->
+ * saved buffer, the solve, the build and factorisation, the product, the delta, decide and commit kernels, the copy back after
+ * a rejection). */
+#define GPIRT_ELL_MAX_POINTS 1025
+#define GPIRT_ELL_PARTS 8
+typedef struct gpirt_ell {
+    int64_t  points, width, index;          /* P, w, k */
+    int64_t  updates, accepted, out_of_range, failed;
+    int64_t  last;                          /* the last update: 0 rejected, 1 accepted, 2 out of range, 3 failed, -1 none yet */
+    int64_t  last_proposed;                 /* its k' (may lie outside the grid) */
+    int64_t  factorisations;                /* factorisations enqueued by the updates so far (one per update that reached the device) */
+    double   length_scale, lo, hi;          /* ell_k and the grid's end points */
+    double   last_u0, last_u1;
+    int64_t  reserved[4];
+} gpirt_ell;
+int gpirt_ell_grid(double lo, double hi, int P, double* out);
+int gpirt_ell_check(double lo, double hi, int P, const double* log_prior, int width, int k0, const gpirt_kernel* kern,
+                    const gpirt_options* opts, int64_t m);
+int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, const double* log_prior, int width, int k0, int on);
+int gpirt_sampler_draw_ell(gpirt_sampler_t s);
+int gpirt_sampler_ell_width(gpirt_sampler_t s, int w);
+int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out);
+
 /* ------------------------------------------------------ the chains with any of the analyses above, in one call -------- */
 /* What gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs: one struct per analysis, each NULL when not wanted, each
  * filled as its section above describes.  The chains are gpirt_mcmc_chains's whatever is asked for -- draws, IRFs, pooled, diag
@@ -2158,7 +2230,9 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
  * factorisation.
  * gpirt_sampler_get / _set("L") always move the n x n factor. */
 int gpirt_sampler_ldl(gpirt_sampler_t s, int64_t* ldl);
-/* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m. */
+/* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m.  The kernel
+ * is not part of the state: refused (GPIRT_E_ARG) when the two samplers' kernels differ, or while the length-scale update
+ * (gpirt_sampler_ell_enable) is on for either -- its index and tables are not copied. */
 int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src);
 int gpirt_sampler_get(gpirt_sampler_t s, const char* name, double* h_out, int64_t count);
 int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, int64_t count);
