@@ -19,7 +19,7 @@ NGRID = 1001
 RNG_RSTREAM, RNG_ITEM = 0, 1
 ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3, 4, 5, 6, 7
 ST_PPC = 8                        # the replicate of the posterior predictive checks (gpirt_amd.ppc)
-ST_ELL = 9                        # the two uniforms of a length-scale update (gpirt_amd.ell)
+ST_ELL = 9                        # the two uniforms of a length-scale update (gpirt_amd.ell): item index 0 whitened, 1 centred
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
@@ -462,12 +462,20 @@ ELL_MAX_POINTS = 1025
 ELL_COUNTS = ("updates", "accepted", "out_of_range", "failed")
 ELL_PARTS = ("copies", "solve", "factor", "product", "delta", "decide", "commit", "restore")     # "times" of ell_get, ms
 ELL_LAST = {-1: None, 0: "rejected", 1: "accepted", 2: "out_of_range", 3: "failed"}
+ELL_KINDS = ("whitened", "centred")       # the two updates; a kind's index is the item index of its uniforms
+ELL_PARTS_CENTRED = ("copies", "solve", "factor", "solve_prop", "quad", "logdet", "decide", "restore")   # "times_centred", ms
 
 
 class Ell(C.Structure):
     """gpirt_ell (include/gpirt_hip.h): the grid's size, the width, the index, the counters and the last update."""
     _fields_ = [(k, C.c_int64) for k in ("points", "width", "index") + ELL_COUNTS + ("last", "last_proposed", "factorisations")] + [
         (k, C.c_double) for k in ("length_scale", "lo", "hi", "last_u0", "last_u1")] + [("reserved", C.c_int64 * 4)]
+
+
+class EllCentred(C.Structure):
+    """gpirt_ell_centred (include/gpirt_hip.h): the centred update's width, counters and last update."""
+    _fields_ = [(k, C.c_int64) for k in ("width",) + ELL_COUNTS + ("last", "last_proposed", "factorisations")] + [
+        (k, C.c_double) for k in ("last_u0", "last_u1")] + [("reserved", C.c_int64 * 6)]
 
 
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
@@ -685,6 +693,9 @@ SIGNATURES = {
     "gpirt_sampler_ell_width": (_i32, [_vp, _i32]),
     "gpirt_sampler_ell_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ell_stats": (_i32, [_vp, C.POINTER(Ell)]),
+    "gpirt_sampler_draw_ell_centred": (_i32, [_vp]),
+    "gpirt_sampler_ell_width_centred": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ell_centred_stats": (_i32, [_vp, C.POINTER(EllCentred)]),
 }
 
 _lib = None

@@ -1,6 +1,8 @@
 // ell.hip -- the kernel's length scale as a parameter of the chain (gpirt_sampler_draw_ell, sampler.hip): the grid and its
 // checks on the host, and the three kernels that decide and commit one prior-whitened Metropolis update (Murray & Adams 2010,
-// section 2.2: nu = L(ell)^-1 f is held fixed, f' = L(ell') nu is what the likelihood sees).
+// section 2.2: nu = L(ell)^-1 f is held fixed, f' = L(ell') nu is what the likelihood sees).  Below them the three kernels of
+// the centred update (gpirt_sampler_draw_ell_centred: f is held fixed and the GP prior N(f_j; 0, S(ell)) decides): the
+// quadratic-form difference per item, the log-determinant difference, the decision.
 //
 // The log-likelihood term t(a) = log(1 + exp(-a)) is ll_term_fast (ll_fast.h): max(-a, 0) + log1p(exp(-|a|)) with the
 // logarithm as 2 atanh(s).  Against the exact value it is within 2 ulp of the term (tests/test_ll_fast.py), i.e. at most
@@ -98,6 +100,110 @@ __global__ __launch_bounds__(ELL_THREADS) void ell_commit_kernel(const int* __re
     for (int64_t i = (int64_t)blockIdx.x * ELL_THREADS + threadIdx.x; i < count; i += stride) f[i] = fp[i];
 }
 
+// ---- the centred update: log p(f | ell') - log p(f | ell) = -0.5 sum_j (|nu'_j|^2 - |nu_j|^2) - m (log det L' - log det L) ----
+// One work-group per item j, ell_delta_kernel's order: dq[j] = sum_i (nu'_ij - nu_ij) (nu'_ij + nu_ij), each cell that product
+// (never a difference of two sums of squares); nonfin[j] = the rows whose nu' is not finite.  One writer each.
+__global__ __launch_bounds__(ELL_THREADS) void ell_quad_kernel(const double* __restrict__ nu, const double* __restrict__ nup,
+                                                               int64_t n, double* __restrict__ dq, int* __restrict__ nonfin)
+{
+    __shared__ double sd[ELL_THREADS];
+    __shared__ int sc[ELL_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * n;
+    const double* aj = nu + base;
+    const double* pj = nup + base;
+    double acc = 0.0;
+    int bad = 0;
+    auto cell = [&](double av, double pv) {
+        if (!(fabs(pv) <= 1.79769313486231570815e308)) ++bad;             // NaN or infinite
+        acc += (pv - av) * (pv + av);
+    };
+    int64_t i = tid;
+    for (; i + 3 * ELL_THREADS < n; i += 4 * ELL_THREADS) {               // four rows' loads in flight, added in row order
+        const int64_t i1 = i + ELL_THREADS, i2 = i + 2 * ELL_THREADS, i3 = i + 3 * ELL_THREADS;
+        const double a0 = aj[i], a1 = aj[i1], a2 = aj[i2], a3 = aj[i3];
+        const double p0 = pj[i], p1 = pj[i1], p2 = pj[i2], p3 = pj[i3];
+        cell(a0, p0); cell(a1, p1); cell(a2, p2); cell(a3, p3);
+    }
+    for (; i < n; i += ELL_THREADS) cell(aj[i], pj[i]);
+    sd[tid] = acc; sc[tid] = bad;
+    __syncthreads();
+#pragma unroll
+    for (int s = ELL_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) { sd[tid] += sd[tid + s]; sc[tid] += sc[tid + s]; }
+        __syncthreads();
+    }
+    if (tid == 0) { dq[blockIdx.x] = sd[0]; nonfin[blockIdx.x] = sc[0]; }
+}
+
+// One work-group: out[0] = dld = sum_i (log L'_ii - log L_ii), the diagonals at stride ldl + 1 (L: the saved buffer, L': the
+// factor buffer); thread t takes its rows i = t, t + 256, ... ascending, four loads in flight, then the fixed tree.
+// out[1] = the diagonal entries of either factor that are non-positive or non-finite (their terms are left out of the sum).
+__global__ __launch_bounds__(ELL_THREADS) void ell_logdet_kernel(const double* __restrict__ Lold, const double* __restrict__ Lnew,
+                                                                 int64_t n, int64_t ldl, double* __restrict__ out)
+{
+    __shared__ double sd[ELL_THREADS];
+    __shared__ int sc[ELL_THREADS];
+    const int tid = threadIdx.x;
+    const int64_t step = ldl + 1;
+    double acc = 0.0;
+    int bad = 0;
+    auto row = [&](double lo, double ln) {
+        const bool ok_o = lo > 0.0 && lo <= 1.79769313486231570815e308, ok_n = ln > 0.0 && ln <= 1.79769313486231570815e308;
+        if (ok_o && ok_n) acc += log(ln) - log(lo);
+        else bad += (ok_o ? 0 : 1) + (ok_n ? 0 : 1);
+    };
+    int64_t i = tid;
+    for (; i + 3 * ELL_THREADS < n; i += 4 * ELL_THREADS) {
+        const int64_t i1 = i + ELL_THREADS, i2 = i + 2 * ELL_THREADS, i3 = i + 3 * ELL_THREADS;
+        const double o0 = Lold[i * step], o1 = Lold[i1 * step], o2 = Lold[i2 * step], o3 = Lold[i3 * step];
+        const double n0 = Lnew[i * step], n1 = Lnew[i1 * step], n2 = Lnew[i2 * step], n3 = Lnew[i3 * step];
+        row(o0, n0); row(o1, n1); row(o2, n2); row(o3, n3);
+    }
+    for (; i < n; i += ELL_THREADS) row(Lold[i * step], Lnew[i * step]);
+    sd[tid] = acc; sc[tid] = bad;
+    __syncthreads();
+#pragma unroll
+    for (int s = ELL_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) { sd[tid] += sd[tid + s]; sc[tid] += sc[tid + s]; }
+        __syncthreads();
+    }
+    if (tid == 0) { out[0] = sd[0]; out[1] = (double)sc[0]; }
+}
+
+// One work-group, one deciding thread, as ell_decide_kernel: dq = dq[0] + ... + dq[m - 1] in ascending j, log_ratio =
+// (-0.5 dq - m dld) + lp_diff with every product and sum rounded on its own, accept iff log_u < log_ratio.  Failed, never
+// accepted: a factor that reported a non-positive minor or a hang-guard expiry, a non-finite nu', diagonal entry, dq or dld.
+// rec = {dq, dld, log_ratio, log_u, accept, nonfinite}; flag as ell_decide_kernel's.
+__global__ __launch_bounds__(ELL_THREADS) void ell_decide_centred_kernel(const double* __restrict__ dqj, const int* __restrict__ nonfin,
+                                                                         int64_t m, const double* __restrict__ ld, double lp_diff,
+                                                                         double log_u, const int* __restrict__ info,
+                                                                         double* __restrict__ rec, int* __restrict__ flag)
+{
+    __shared__ double sd[4 * ELL_THREADS];
+    __shared__ int sc[4 * ELL_THREADS];
+    double dq = 0.0;
+    long long bad = 0;
+    for (int64_t j0 = 0; j0 < m; j0 += 4 * ELL_THREADS) {
+        const int cnt = (int)(m - j0 < 4 * ELL_THREADS ? m - j0 : 4 * ELL_THREADS);
+        for (int q = threadIdx.x; q < cnt; q += ELL_THREADS) { sd[q] = dqj[j0 + q]; sc[q] = nonfin[j0 + q]; }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int q = 0; q < cnt; ++q) { dq += sd[q]; bad += sc[q]; }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double dld = ld[0];
+    bad += (long long)ld[1];
+    const double half = __dmul_rn(-0.5, dq), dets = __dmul_rn((double)m, dld);
+    const double ratio = __dadd_rn(__dsub_rn(half, dets), lp_diff);
+    const bool failed = info[0] != 0 || info[1] != 0 || bad != 0 || !(fabs(dq) <= 1.79769313486231570815e308) ||
+                        !(fabs(dld) <= 1.79769313486231570815e308);
+    const bool accept = !failed && log_u < ratio;
+    rec[0] = dq; rec[1] = dld; rec[2] = ratio; rec[3] = log_u; rec[4] = accept ? 1.0 : 0.0; rec[5] = (double)bad;
+    *flag = info[1] != 0 ? 3 : failed ? 2 : (accept ? 1 : 0);
+}
+
 }  // namespace
 
 int launch_ell_delta(hipStream_t st, const double* f, const double* fp, const double* mu, const double* y, int64_t n, int64_t m,
@@ -121,6 +227,28 @@ int launch_ell_commit(hipStream_t st, const int* flag, double* f, const double* 
     int64_t blocks = (count + ELL_THREADS - 1) / ELL_THREADS;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(ell_commit_kernel, dim3((unsigned)blocks), dim3(ELL_THREADS), 0, st, flag, f, fp, count);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ell_quad(hipStream_t st, const double* nu, const double* nup, int64_t n, int64_t m, double* dq, int* nonfin)
+{
+    hipLaunchKernelGGL(ell_quad_kernel, dim3((unsigned)m), dim3(ELL_THREADS), 0, st, nu, nup, n, dq, nonfin);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ell_logdet(hipStream_t st, const double* Lold, const double* Lnew, int64_t n, int64_t ldl, double* out)
+{
+    hipLaunchKernelGGL(ell_logdet_kernel, dim3(1), dim3(ELL_THREADS), 0, st, Lold, Lnew, n, ldl, out);
+    GP_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ell_decide_centred(hipStream_t st, const double* dq, const int* nonfin, int64_t m, const double* ld, double lp_diff,
+                              double log_u, const int* info, double* rec, int* flag)
+{
+    hipLaunchKernelGGL(ell_decide_centred_kernel, dim3(1), dim3(ELL_THREADS), 0, st, dq, nonfin, m, ld, lp_diff, log_u, info, rec, flag);
     GP_HIP(hipGetLastError());
     return 0;
 }

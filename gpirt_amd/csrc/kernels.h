@@ -55,7 +55,14 @@ int launch_ell_delta(hipStream_t st, const double* f, const double* fp, const do
 int launch_ell_decide(hipStream_t st, const double* delta, const int* nonfin, int64_t m, double lp_diff, double log_u,
                       const int* info, double* rec, int* flag);
 int launch_ell_commit(hipStream_t st, const int* flag, double* f, const double* fp, int64_t count);     // f <- f' iff *flag == 1
-int ell_grid_check(double lo, double hi, int P);                      // GPIRT_E_ARG with the message
+// the centred update (gpirt_sampler_draw_ell_centred): dq[j] = sum_i (nu' - nu)(nu' + nu), nonfin[j] = item j's non-finite nu';
+// out = {sum_i log L'_ii - log L_ii, the diagonal entries that are non-positive or non-finite};
+// rec = {dq, dld, log_ratio, log_u, accept, nonfinite}, flag as launch_ell_decide's
+int launch_ell_quad(hipStream_t st, const double* nu, const double* nup, int64_t n, int64_t m, double* dq, int* nonfin);
+int launch_ell_logdet(hipStream_t st, const double* Lold, const double* Lnew, int64_t n, int64_t ldl, double* out);
+int launch_ell_decide_centred(hipStream_t st, const double* dq, const int* nonfin, int64_t m, const double* ld, double lp_diff,
+                              double log_u, const int* info, double* rec, int* flag);
+int ell_grid_check(double lo, double hi, int P);                    // GPIRT_E_ARG with the message
 void ell_grid_fill(double lo, double hi, int P, double* out);         // long double, rounded to fp64, the end points exact
 
 // potrf.hip

@@ -34,24 +34,32 @@ const char* const kStageNames[ST_COUNT] = { "draw_f", "draw_fstar", "theta_gemm"
 }  // namespace
 
 // The length scale as a parameter of the chain (gpirt_sampler_ell_enable / gpirt_sampler_draw_ell; include/gpirt_hip.h).  The
-// index k is host state: every decision is read back once per update.
-struct EllState {
-    bool on = false;
-    int P = 0, w = 0, k = 0;
-    std::vector<double> grid, log_prior;
+// index k is host state: every decision is read back once per update.  Two updates move it, each with its own width, call
+// count, uniforms and counters: the whitened one (gpirt_sampler_draw_ell) and the centred one (gpirt_sampler_draw_ell_centred).
+enum { ELL_WHITENED = 0, ELL_CENTRED = 1 };
+struct EllUpdate {
+    int w = 0;
     int64_t updates = 0, accepted = 0, out_of_range = 0, failed = 0, factorisations = 0;
     int64_t last = -1, last_proposed = 0;
     double last_u0 = 0.0, last_u1 = 0.0;
-    uint32_t t = 0;                   // draw_ell calls so far
+    uint32_t t = 0;                   // calls of this update so far
+    double part_ms[GPIRT_ELL_PARTS] = {};
+};
+struct EllState {
+    bool on = false;
+    int P = 0, k = 0;
+    std::vector<double> grid, log_prior;
+    EllUpdate up[2];                  // ELL_WHITENED, ELL_CENTRED
     double *Lsave = nullptr, *fprop = nullptr, *delta = nullptr, *rec = nullptr;    // device: ldl x n, n x m, m, 8
+    double *nuprop = nullptr, *dq = nullptr, *ld = nullptr, *rec_c = nullptr;       // the centred update's: n x m, m, 2, 8
     int *nonfin = nullptr, *flag = nullptr;                                         // device: m, 1
     int* h_flag = nullptr;            // pinned
     hipEvent_t ev = nullptr;          // the sampler's own stream has finished whatever still reads L
     // with gpirt_sampler_enable_timing on: the device time of the last update's parts ("times" of gpirt_sampler_ell_get) --
     // the copies (f -> nu's buffer, the factor buffer saved), the solve, the build and factorisation, the product, the three
-    // kernels, the copy back after a rejection
+    // kernels, the copy back after a rejection (the centred update: the copies, the first solve, the build and factorisation,
+    // the second solve, the quad, logdet and decide kernels, the copy back)
     hipEvent_t tev[GPIRT_ELL_PARTS + 2] = {};
-    double part_ms[GPIRT_ELL_PARTS] = {};
 };
 
 struct gpirt_sampler_s {
@@ -954,14 +962,16 @@ int factor_guard_sync(gpirt_sampler_s* s)
 // ---- the length scale as a parameter of the chain (include/gpirt_hip.h; the kernels are ell.hip's) ------------------------------
 void ell_free(EllState* e)
 {
-    for (void* p : { (void*)e->Lsave, (void*)e->fprop, (void*)e->delta, (void*)e->rec, (void*)e->nonfin, (void*)e->flag })
+    for (void* p : { (void*)e->Lsave, (void*)e->fprop, (void*)e->delta, (void*)e->rec, (void*)e->nuprop, (void*)e->dq, (void*)e->ld,
+                     (void*)e->rec_c, (void*)e->nonfin, (void*)e->flag })
         if (p) hipFree(p);
     if (e->h_flag) hipHostFree(e->h_flag);
     if (e->ev) hipEventDestroy(e->ev);
     for (hipEvent_t t : e->tev) if (t) hipEventDestroy(t);
-    const uint32_t calls = e->t;          // t counts the sampler's draw_ell calls: enabling again does not replay their uniforms
+    // t counts the sampler's calls of each update: enabling again does not replay their uniforms
+    const uint32_t calls[2] = { e->up[ELL_WHITENED].t, e->up[ELL_CENTRED].t };
     *e = EllState();
-    e->t = calls;
+    e->up[ELL_WHITENED].t = calls[0]; e->up[ELL_CENTRED].t = calls[1];
 }
 
 // The main stream waits for whatever the sampler's own stream still has in flight -- the early block inverses read L, a
@@ -1006,23 +1016,30 @@ int ell_settle_factor(gpirt_sampler_s* s)
     return 0;
 }
 
-int do_draw_ell(gpirt_sampler_s* s)
+// One update of the index, whitened or centred.  What the two share is here: the factor settled, the call counted only when it
+// ends in one of the four outcomes, the proposal, the join, f -> nu's buffer and the factor buffer saved, nu = L^-1 f, the
+// proposal's factor, the decision read back, a hang-guard expiry repaired once, everything put back unless accepted, the timing.
+// They differ in their uniforms' item index, their width and counters, and in what is enqueued between the proposal's factor and
+// the read of the decision.
+int do_draw_ell(gpirt_sampler_s* s, int kind)
 {
     EllState& e = s->ell;
+    EllUpdate& c = e.up[kind];
     gpirt_handle_t h = s->h;
     hipStream_t st = h->stream;
     const int64_t n = s->n, m = s->m;
     GP_TRY(ell_settle_factor(s));
     // the call is counted, and its pair of uniforms consumed, when it ends in one of the four outcomes: an update that returns
     // an error has not happened (updates = accepted + rejected + out_of_range + failed at all times)
-    const uint32_t t = e.t + 1;
-    const double u0 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, 0, 0), u1 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, 0, 1);
-    auto counted = [&]() { e.t = t; e.updates += 1; e.last_u0 = u0; e.last_u1 = u1; };
-    const int w = e.w;
+    const uint32_t t = c.t + 1;
+    const double u0 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, (uint32_t)kind, 0),        // (item index 0: whitened, 1: centred)
+                 u1 = item_uniform(s->opt.seed, t, GPIRT_ST_ELL, (uint32_t)kind, 1);
+    auto counted = [&]() { c.t = t; c.updates += 1; c.last_u0 = u0; c.last_u1 = u1; };
+    const int w = c.w;
     int j = (int)floor(u0 * (double)(2 * w));
     if (j > 2 * w - 1) j = 2 * w - 1;
     const int kp = e.k + (j < w ? j - w : j - w + 1);
-    if (kp < 0 || kp >= e.P) { counted(); e.last_proposed = kp; e.out_of_range += 1; e.last = 2; return 0; }      // (the proposal is symmetric: nothing else runs)
+    if (kp < 0 || kp >= e.P) { counted(); c.last_proposed = kp; c.out_of_range += 1; c.last = 2; return 0; }      // (the proposal is symmetric: nothing else runs)
     GP_TRY(ell_join(s));
     s->factor_fresh = false;
     const bool timed = s->timing;
@@ -1043,24 +1060,42 @@ int do_draw_ell(gpirt_sampler_s* s)
     // nu = L^-1 f (NU is free between steps), then the proposal's factor in place of the saved one
     tick(0);
     GP_HIP(hipMemcpyAsync(s->NU, s->f, fbytes, hipMemcpyDeviceToDevice, st));
+    if (kind == ELL_CENTRED) GP_HIP(hipMemcpyAsync(e.nuprop, s->f, fbytes, hipMemcpyDeviceToDevice, st));
     GP_HIP(hipMemcpyAsync(e.Lsave, s->L, lbytes, hipMemcpyDeviceToDevice, st));
     tick(1);
     GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, s->NU, m, n, false));
     tick(2);
     ell_set_kernel(s, e.grid[(size_t)kp]);
     int rc = factor_core(s);
-    e.factorisations += 1;
+    c.factorisations += 1;
     tick(3);
     const double lp_diff = e.log_prior[(size_t)kp] - e.log_prior[(size_t)e.k], log_u = log(u1);
     for (int attempt = 0; !rc; ++attempt) {
-        rc = launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->NU, n, 0.0, e.fprop, n);
-        tick(4);
-        if (!rc) rc = launch_ell_delta(st, s->f, e.fprop, s->mu, s->y, n, m, e.delta, e.nonfin);
-        tick(5);
-        if (!rc) rc = launch_ell_decide(st, e.delta, e.nonfin, m, lp_diff, log_u, h->d_info, e.rec, e.flag);
-        tick(6);
-        if (!rc) rc = launch_ell_commit(st, e.flag, s->f, e.fprop, n * m);
-        tick(7);
+        if (kind == ELL_WHITENED) {
+            // f' = L' nu, the likelihood's change, the decision, f <- f' behind it
+            rc = launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->NU, n, 0.0, e.fprop, n);
+            tick(4);
+            if (!rc) rc = launch_ell_delta(st, s->f, e.fprop, s->mu, s->y, n, m, e.delta, e.nonfin);
+            tick(5);
+            if (!rc) rc = launch_ell_decide(st, e.delta, e.nonfin, m, lp_diff, log_u, h->d_info, e.rec, e.flag);
+            tick(6);
+            if (!rc) rc = launch_ell_commit(st, e.flag, s->f, e.fprop, n * m);
+            tick(7);
+        } else {
+            // nu' = L'^-1 f (f does not move: no product, no commit), the prior's change in its two parts, the decision
+            if (attempt > 0 && hipMemcpyAsync(e.nuprop, s->f, fbytes, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+                set_error("length-scale update: copying f failed: %s", hipGetErrorString(hipGetLastError()));
+                rc = GPIRT_E_HIP;
+            }
+            if (!rc) rc = launch_trsm_lower(h, st, s->L, n, s->ldl, e.nuprop, m, n, false);
+            tick(4);
+            if (!rc) rc = launch_ell_quad(st, s->NU, e.nuprop, n, m, e.dq, e.nonfin);
+            tick(5);
+            if (!rc) rc = launch_ell_logdet(st, e.Lsave, s->L, n, s->ldl, e.ld);
+            tick(6);
+            if (!rc) rc = launch_ell_decide_centred(st, e.dq, e.nonfin, m, e.ld, lp_diff, log_u, h->d_info, e.rec_c, e.flag);
+            tick(7);
+        }
         if (rc) break;
         // the decision: 4 bytes and a stream synchronisation, as gpirt_sampler_check's
         if (hipMemcpyAsync(e.h_flag, e.flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -1080,7 +1115,7 @@ int do_draw_ell(gpirt_sampler_s* s)
         s->factor_fresh = true;
         rc = recover_factor(s);
         s->factor_fresh = false;
-        e.factorisations += 1;
+        c.factorisations += 1;
     }
     if (rc) { restore(); return rc; }
     // the parts' device time, once the stream has passed the last event (timing on: one more synchronisation)
@@ -1092,22 +1127,22 @@ int do_draw_ell(gpirt_sampler_s* s)
             float ms = 0.f;
             if (i < 7) hipEventElapsedTime(&ms, e.tev[i], e.tev[i + 1]);
             else if (restored) hipEventElapsedTime(&ms, e.tev[8], e.tev[9]);
-            e.part_ms[i] = ms;
+            c.part_ms[i] = ms;
         }
         return 0;
     };
     counted();
-    e.last_proposed = kp;
+    c.last_proposed = kp;
     if (*e.h_flag == 1) {
-        e.k = kp; e.accepted += 1; e.last = 1;
+        e.k = kp; c.accepted += 1; c.last = 1;
         invalidate_factor_products(s);        // (the solve for nu may have left block inverses of the OLD factor behind)
         return times(false);
     }
     if (*e.h_flag == 2) {
-        e.failed += 1; e.last = 3;
+        c.failed += 1; c.last = 3;
         GP_HIP(hipMemsetAsync(h->d_info, 0, sizeof(int), st));       // a non-positive minor of the PROPOSAL is not the chain's
     } else {
-        e.last = 0;
+        c.last = 0;
     }
     tick(8);                                  // (the copy back alone: from here to the last event)
     GP_TRY(restore());
@@ -2458,6 +2493,10 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
         hipMalloc((void**)&e.fprop, sizeof(double) * (size_t)(n * m)) != hipSuccess ||
         hipMalloc((void**)&e.delta, sizeof(double) * (size_t)m) != hipSuccess ||
         hipMalloc((void**)&e.rec, sizeof(double) * 8) != hipSuccess ||
+        hipMalloc((void**)&e.nuprop, sizeof(double) * (size_t)(n * m)) != hipSuccess ||
+        hipMalloc((void**)&e.dq, sizeof(double) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&e.ld, sizeof(double) * 2) != hipSuccess ||
+        hipMalloc((void**)&e.rec_c, sizeof(double) * 8) != hipSuccess ||
         hipMalloc((void**)&e.nonfin, sizeof(int) * (size_t)m) != hipSuccess ||
         hipMalloc((void**)&e.flag, sizeof(int)) != hipSuccess) return fail(GPIRT_E_ALLOC, "hipMalloc");
     if (hipHostMalloc((void**)&e.h_flag, sizeof(int), hipHostMallocDefault) != hipSuccess) return fail(GPIRT_E_ALLOC, "the pinned allocation");
@@ -2466,9 +2505,13 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
     if (hipMemsetAsync(e.fprop, 0, sizeof(double) * (size_t)(n * m), st) != hipSuccess ||
         hipMemsetAsync(e.delta, 0, sizeof(double) * (size_t)m, st) != hipSuccess ||
         hipMemsetAsync(e.rec, 0, sizeof(double) * 8, st) != hipSuccess ||
+        hipMemsetAsync(e.nuprop, 0, sizeof(double) * (size_t)(n * m), st) != hipSuccess ||
+        hipMemsetAsync(e.dq, 0, sizeof(double) * (size_t)m, st) != hipSuccess ||
+        hipMemsetAsync(e.ld, 0, sizeof(double) * 2, st) != hipSuccess ||
+        hipMemsetAsync(e.rec_c, 0, sizeof(double) * 8, st) != hipSuccess ||
         hipMemsetAsync(e.nonfin, 0, sizeof(int) * (size_t)m, st) != hipSuccess ||
         hipMemsetAsync(e.flag, 0, sizeof(int), st) != hipSuccess) return fail(GPIRT_E_HIP, "hipMemsetAsync");
-    e.P = P; e.w = width;
+    e.P = P; e.up[ELL_WHITENED].w = e.up[ELL_CENTRED].w = width;
     e.grid.resize((size_t)P); e.log_prior.resize((size_t)P);
     ell_grid_fill(lo, hi, P, e.grid.data());
     for (int k = 0; k < P; ++k) {
@@ -2496,10 +2539,17 @@ int gpirt_sampler_draw_ell(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised);
     GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
-    return do_draw_ell(s);
+    return do_draw_ell(s, ELL_WHITENED);
 }
 
-int gpirt_sampler_ell_width(gpirt_sampler_t s, int w)
+int gpirt_sampler_draw_ell_centred(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    return do_draw_ell(s, ELL_CENTRED);
+}
+
+static int ell_set_width(gpirt_sampler_t s, int w, int kind)
 {
     GP_ARG(s != nullptr);
     GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
@@ -2507,8 +2557,18 @@ int gpirt_sampler_ell_width(gpirt_sampler_t s, int w)
         set_error("length scale: width = %d, it must lie in 1 .. P - 1 = %d", w, s->ell.P - 1);
         return GPIRT_E_ARG;
     }
-    s->ell.w = w;
+    s->ell.up[kind].w = w;
     return 0;
+}
+
+int gpirt_sampler_ell_width(gpirt_sampler_t s, int w)
+{
+    return ell_set_width(s, w, ELL_WHITENED);
+}
+
+int gpirt_sampler_ell_width_centred(gpirt_sampler_t s, int w)
+{
+    return ell_set_width(s, w, ELL_CENTRED);
 }
 
 int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
@@ -2517,7 +2577,9 @@ int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int6
     EllState& e = s->ell;
     GP_TRY(needs(e.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
     const int64_t nm = s->n * s->m;
-    const int64_t counts[4] = { e.updates, e.accepted, e.out_of_range, e.failed };
+    const EllUpdate &wh = e.up[ELL_WHITENED], &ce = e.up[ELL_CENTRED];
+    const int64_t counts[4] = { wh.updates, wh.accepted, wh.out_of_range, wh.failed };
+    const int64_t counts_c[4] = { ce.updates, ce.accepted, ce.out_of_range, ce.failed };
     const int64_t index = e.k;
     const void* host = nullptr; const void* dev = nullptr; int64_t want = 0;
     if (strcmp(name, "grid") == 0) { host = e.grid.data(); want = 8 * (int64_t)e.P; }
@@ -2528,7 +2590,12 @@ int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int6
     else if (strcmp(name, "f_prop") == 0) { dev = e.fprop; want = 8 * nm; }
     else if (strcmp(name, "delta") == 0) { dev = e.delta; want = 8 * s->m; }
     else if (strcmp(name, "record") == 0) { dev = e.rec; want = 40; }
-    else if (strcmp(name, "times") == 0) { host = e.part_ms; want = 8 * GPIRT_ELL_PARTS; }
+    else if (strcmp(name, "times") == 0) { host = wh.part_ms; want = 8 * GPIRT_ELL_PARTS; }
+    else if (strcmp(name, "nu_prop") == 0) { dev = e.nuprop; want = 8 * nm; }
+    else if (strcmp(name, "dq") == 0) { dev = e.dq; want = 8 * s->m; }
+    else if (strcmp(name, "record_centred") == 0) { dev = e.rec_c; want = 48; }
+    else if (strcmp(name, "counts_centred") == 0) { host = counts_c; want = 32; }
+    else if (strcmp(name, "times_centred") == 0) { host = ce.part_ms; want = 8 * GPIRT_ELL_PARTS; }
     else { set_error("unknown length-scale array '%s'", name); return GPIRT_E_ARG; }
     if (bytes != want) { set_error("length scale: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
     if (host) { memcpy(h_out, host, (size_t)want); return 0; }
@@ -2542,12 +2609,27 @@ int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out)
     GP_ARG(s && out);
     const EllState& e = s->ell;
     GP_TRY(needs(e.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    const EllUpdate& c = e.up[ELL_WHITENED];
     memset(out, 0, sizeof(*out));
-    out->points = e.P; out->width = e.w; out->index = e.k;
-    out->updates = e.updates; out->accepted = e.accepted; out->out_of_range = e.out_of_range; out->failed = e.failed;
-    out->last = e.last; out->last_proposed = e.last_proposed; out->factorisations = e.factorisations;
+    out->points = e.P; out->width = c.w; out->index = e.k;
+    out->updates = c.updates; out->accepted = c.accepted; out->out_of_range = c.out_of_range; out->failed = c.failed;
+    out->last = c.last; out->last_proposed = c.last_proposed; out->factorisations = c.factorisations;
     out->length_scale = e.grid[(size_t)e.k]; out->lo = e.grid.front(); out->hi = e.grid.back();
-    out->last_u0 = e.last_u0; out->last_u1 = e.last_u1;
+    out->last_u0 = c.last_u0; out->last_u1 = c.last_u1;
+    return 0;
+}
+
+int gpirt_sampler_ell_centred_stats(gpirt_sampler_t s, gpirt_ell_centred* out)
+{
+    GP_ARG(s && out);
+    const EllState& e = s->ell;
+    GP_TRY(needs(e.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    const EllUpdate& c = e.up[ELL_CENTRED];
+    memset(out, 0, sizeof(*out));
+    out->width = c.w;
+    out->updates = c.updates; out->accepted = c.accepted; out->out_of_range = c.out_of_range; out->failed = c.failed;
+    out->last = c.last; out->last_proposed = c.last_proposed; out->factorisations = c.factorisations;
+    out->last_u0 = c.last_u0; out->last_u1 = c.last_u1;
     return 0;
 }
 

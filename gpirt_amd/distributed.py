@@ -327,7 +327,7 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the length-scale update is not offered for item shards (its likelihood change runs "
                          "over all items, and each rank holds its own columns of f)")
 
-    def draw_ell(self):
+    def draw_ell(self, kind="whitened"):
         raise ValueError("ShardedSampler: the length-scale update is not offered for item shards (its likelihood change runs "
                          "over all items, and each rank holds its own columns of f)")
 

@@ -10,6 +10,11 @@ hyperparameters of latent Gaussian models", section 2.2): nu = L(ell)^-1 f is he
 `run` is the one-call way in: gpirt_amd.kernel.run's stage loop with Sampler.draw_ell() after every `every`-th step().
 `step_exact` is the NumPy statement of one update (Cholesky in fp64 on gpirt_amd.kernel.kernel_matrix, everything after it in
 long double), `conditional_posterior` the exact discrete p(k | nu, theta, mu, y) by direct summation.
+
+Beside it stands the centred update of the same paper (section 2.1; gpirt_sampler_draw_ell_centred, Sampler.draw_ell("centred")):
+f is held fixed and the GP prior decides, p(k | f, theta) proportional to prod_j N(f_j; 0, S_k) exp(log_prior[k]).  It has its
+own width, call count, uniforms (item index 1 of GPIRT_ST_ELL) and counters.  `step_exact_centred` is its NumPy statement,
+`conditional_posterior_centred` its stationary distribution, and run(update="centred" | "both") drives it.
 """
 from __future__ import annotations
 
@@ -54,10 +59,11 @@ def check_args(lo, hi, points, log_prior=None, width=4, k0=None, kernel=None, op
                                       None if options is None else C.byref(options), int(m)))
 
 
-def uniforms(seed, t) -> tuple:
-    """(u0, u1) of the t-th draw_ell call of a sampler (t counted from 1): item_uniform(seed, t, GPIRT_ST_ELL, 0, 0 / 1)."""
+def uniforms(seed, t, kind="whitened") -> tuple:
+    """(u0, u1) of the t-th draw_ell call of that kind on a sampler (t counted from 1, per kind): item_uniform(seed, t,
+    GPIRT_ST_ELL, item, 0 / 1) with item 0 for "whitened" and 1 for "centred"."""
     from .ppc import item_uniform
-    u = item_uniform(seed, int(t), ST_ELL, 0, np.arange(2, dtype=np.uint64))
+    u = item_uniform(seed, int(t), ST_ELL, _lib.ELL_KINDS.index(kind), np.arange(2, dtype=np.uint64))
     return float(u[0]), float(u[1])
 
 
@@ -162,6 +168,56 @@ def conditional_posterior(nu, theta, mu, y, ell_grid, log_prior, family="se") ->
     return (w / w.sum()).astype(np.float64)
 
 
+def step_exact_centred(theta, f, k, u0, u1, ell_grid, log_prior, width, family="se", cache=None) -> dict:
+    """One update as gpirt_sampler_draw_ell_centred states it: f (n x m) is held fixed and
+    log_ratio = sum_j [log N(f_j; 0, S_k') - log N(f_j; 0, S_k)] + log_prior[k'] - log_prior[k]
+              = -0.5 sum_j dq_j - m dld + log_prior[k'] - log_prior[k],
+    dq_j = sum_i (nu'_ij - nu_ij)(nu'_ij + nu_ij) with nu = L_k^-1 f and nu' = L_k'^-1 f, dld = sum_i (log L'_ii - log L_ii).
+    Cholesky in fp64, everything after it in long double; cache as step_exact's.  Returns dict(status ("accepted", "rejected",
+    "out_of_range", "failed"), k (the index afterwards), k_prop, and for an update that got that far nu, nu_prop (long double),
+    dq (m), dld, log_ratio, log_u)."""
+    ell_grid = np.asarray(ell_grid, dtype=np.float64)
+    lp = np.asarray(log_prior, dtype=np.float64)
+    f = np.asarray(f, dtype=np.float64)
+    kp = int(k) + proposal(u0, width)
+    out = dict(status="out_of_range", k=int(k), k_prop=kp)
+    if kp < 0 or kp >= ell_grid.shape[0]:
+        return out
+    out["status"] = "failed"
+    try:
+        L = _factor_of(cache, theta, family, ell_grid, int(k))
+        Lp = _factor_of(cache, theta, family, ell_grid, kp)
+    except np.linalg.LinAlgError:
+        return out
+    nu, nup = solve_lower(L, f), solve_lower(Lp, f)
+    dq = ((nup - nu) * (nup + nu)).sum(axis=0)
+    dld = (np.log(np.diagonal(Lp)) - np.log(np.diagonal(L))).sum()
+    log_ratio = LD(-0.5) * dq.sum() - LD(f.shape[1]) * dld + (LD(lp[kp]) - LD(lp[int(k)]))
+    log_u = np.log(LD(u1))
+    out.update(nu=nu, nu_prop=nup, dq=dq, dld=dld, log_ratio=log_ratio, log_u=log_u)
+    if not (np.isfinite(nup).all() and np.isfinite(dq).all() and np.isfinite(dld)):
+        return out
+    if log_u < log_ratio:
+        out.update(status="accepted", k=kp)
+    else:
+        out["status"] = "rejected"
+    return out
+
+
+def conditional_posterior_centred(f, theta, ell_grid, log_prior, family="se") -> np.ndarray:
+    """p(k | f, theta) on the grid by direct summation: proportional to exp(log_prior[k] - 0.5 sum_j |L_k^-1 f_j|^2 -
+    m sum_i log (L_k)_ii), in long double (the stationary distribution of the centred update with f held fixed)."""
+    ell_grid = np.asarray(ell_grid, dtype=np.float64)
+    f = np.asarray(f, dtype=np.float64)
+    lw = np.empty(ell_grid.shape[0], dtype=LD)
+    for k in range(ell_grid.shape[0]):
+        L = factor(theta, family, ell_grid[k])
+        nu = solve_lower(L, f)
+        lw[k] = LD(log_prior[k]) - (nu * nu).sum() / LD(2) - LD(f.shape[1]) * np.log(np.diagonal(L)).sum()
+    w = np.exp(lw - lw.max())
+    return (w / w.sum()).astype(np.float64)
+
+
 # ------------------------------------------------------------------------------------------------------- summaries ---
 def retune(width, accept_rate, points) -> int:
     """The burn-in's rule: halve the width below an acceptance of 0.2, double it above 0.5, within 1 .. points - 1."""
@@ -195,7 +251,7 @@ def summarise(index, ell_grid, probs=(0.025, 0.25, 0.5, 0.75, 0.975)) -> dict:
 # ------------------------------------------------------------------------------------------------ one call per run ---
 def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo=0.25, hi=4.0, points=129, width=4,
         log_prior=None, every=1, adapt=True, loo=False, preset="fast", store_draws=True, theta_init=None, k0=None, *,
-        handle=None, **sampler_kw) -> dict:
+        handle=None, update="whitened", width_centred=None, **sampler_kw) -> dict:
     """gpirt_amd.kernel.run's stage loop with the length scale in the chain: `chains` chains of the stage-driven Sampler, one
     after the other, each with Sampler.draw_ell() after every `every`-th step().  y: n x m of +1 / -1 / NaN.
 
@@ -206,7 +262,13 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
     phase runs a fixed kernel.  Returns what kernel.run returns -- theta, beta, f, IRFs, summary, diagnostics, loo, kernel (the
     handle's), kstar_rank, chains -- plus ell: index and length_scale per kept draw (chains x S; S for one chain), hist, mean, sd,
     exact quantiles, mode, rhat and ess of log ell (`summarise`), accept_rate and width per chain (of the sampling phase),
-    counts per chain, grid and log_prior."""
+    counts per chain, grid and log_prior.
+
+    update: which update follows every `every`-th step() -- "whitened" (the default: exactly what this function returned before
+    the keyword existed), "centred" (Sampler.draw_ell("centred"), width `width_centred`, None: `width`), or "both": the whitened
+    update and then the centred one, in that fixed order.  The burn-in retunes each kind's width from that kind's own
+    acceptance.  ell["update"] names the mode; with "centred" or "both", ell's accept_rate, width and counts are dicts with one
+    entry per kind that ran ("whitened", "centred"), each what the default mode holds for its one kind."""
     from . import chains as CH
     from . import kernel as K
     from . import loo as LO
@@ -217,10 +279,15 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
     S, B, nc, every = int(sample_iterations), int(burn_iterations), int(chains), int(every)
     if nc < 1 or S < 1 or B < 0 or every < 1:
         raise ValueError("ell.run: chains >= 1, sample_iterations >= 1, burn_iterations >= 0 and every >= 1 are needed")
+    kinds = {"whitened": ("whitened",), "centred": ("centred",), "both": _lib.ELL_KINDS}.get(update)
+    if kinds is None:
+        raise ValueError(f"ell.run: update must be 'whitened', 'centred' or 'both', not {update!r}")
+    width0 = {"whitened": int(width), "centred": int(width if width_centred is None else width_centred)}
     g = grid(lo, hi, points)
     if k0 is None:
         k0 = int(np.argmin(np.abs(np.log(g))))
     check_args(lo, hi, points, log_prior, width, k0)
+    check_args(lo, hi, points, log_prior, width0["centred"], k0)
     want_loo = None
     if loo is not None and loo is not False:
         want_loo = LO.parse(loo)
@@ -252,7 +319,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
         be = np.empty((nc, 2, m, S + 1)) if "beta" in keep else None
         ff = np.empty((nc, n, m, S + 1)) if "f" in keep else None
         index = np.empty((nc, S), dtype=np.int64)
-        rates, widths, counts = [], [], []
+        rates, widths, counts = ({kd: [] for kd in kinds} for _ in range(3))
 
         def store(c, slot, s):
             if th is not None:
@@ -273,20 +340,25 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
             s.summary_enable(_lib.SUM_THETA_BETA | _lib.SUM_DIAG, planned_draws=S)
             if want_loo is not None:
                 s.loo_enable(nc * S, want_loo["tail"])
-            w, seen, start = int(width), (0, 0), (0, 0)
+            if "centred" in kinds:
+                s.ell_width(width0["centred"], "centred")
+            of = lambda e, kd: e if kd == "whitened" else e["centred"]                   # noqa: E731
+            w, seen, start = dict(width0), {kd: (0, 0) for kd in kinds}, {kd: (0, 0) for kd in kinds}
             for it in range(S + B):
                 s.step()
                 if (it + 1) % every == 0:
-                    s.draw_ell()
-                    if adapt and it < B:
-                        e = s.ell()
-                        if e["updates"] - seen[0] >= ADAPT_EVERY:
-                            w = retune(w, (e["accepted"] - seen[1]) / (e["updates"] - seen[0]), points)
-                            s.ell_width(w)
-                            seen = (e["updates"], e["accepted"])
+                    for kd in kinds:
+                        s.draw_ell(kd)
+                        if adapt and it < B:
+                            e = of(s.ell(), kd)
+                            if e["updates"] - seen[kd][0] >= ADAPT_EVERY:
+                                w[kd] = retune(w[kd], (e["accepted"] - seen[kd][1]) / (e["updates"] - seen[kd][0]), points)
+                                s.ell_width(w[kd], kd)
+                                seen[kd] = (e["updates"], e["accepted"])
                 if it == B - 1:
-                    e = s.ell()
-                    start = (e["updates"], e["accepted"])
+                    for kd in kinds:
+                        e = of(s.ell(), kd)
+                        start[kd] = (e["updates"], e["accepted"])
                 if it >= B:
                     s.accumulate_irf()
                     store(c, it - B + 1, s)
@@ -295,16 +367,19 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
                     if want_loo is not None:
                         s.loo_accumulate()
             s.check()
-            e = s.ell()
-            done = e["updates"] - start[0]
-            rates.append((e["accepted"] - start[1]) / done if done else float("nan"))
-            widths.append(e["width"])
-            counts.append({k: e[k] for k in _lib.ELL_COUNTS})
+            for kd in kinds:
+                e = of(s.ell(), kd)
+                done = e["updates"] - start[kd][0]
+                rates[kd].append((e["accepted"] - start[kd][1]) / done if done else float("nan"))
+                widths[kd].append(e["width"])
+                counts[kd].append({k: e[k] for k in _lib.ELL_COUNTS})
             if nc == 1:
                 irf_one = s.finish_irfs(S)
         pooled = CH.combine(h, samplers)
         ell = summarise(index, g)
-        ell.update(index=index if nc > 1 else index[0], length_scale=g[index] if nc > 1 else g[index[0]], accept_rate=rates,
+        if update == "whitened":
+            rates, widths, counts = rates["whitened"], widths["whitened"], counts["whitened"]
+        ell.update(update=update, index=index if nc > 1 else index[0], length_scale=g[index] if nc > 1 else g[index[0]], accept_rate=rates,
                    width=widths, counts=counts, grid=g, log_prior=samplers[0].ell_get("log_prior"), every=every)
         out = dict(theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
                    diagnostics=pooled["diagnostics"], kernel=used, kstar_rank=rank, chains=nc, ell=ell,

@@ -349,6 +349,13 @@ def gpirtMCMC(data, sample_iterations, burn_iterations, vote_codes=None, beta_pr
     return out
 
 
+def _ell_entry(kind, entry) -> str:
+    """the library entry of a length-scale call for one of the two updates (_lib.ELL_KINDS)"""
+    if kind not in _lib.ELL_KINDS:
+        raise ValueError(f"ell: kind must be one of {_lib.ELL_KINDS}, not {kind!r}")
+    return entry + ("_centred" if kind == "centred" else "")
+
+
 def _keep(store_draws) -> set:
     if store_draws is True:
         return {"theta", "beta", "f"}
@@ -1468,39 +1475,52 @@ class Sampler:
                                                 int(width), -1 if k0 is None else int(k0), 1))
         self._ell_points = int(points)
 
-    def draw_ell(self):
-        """One prior-whitened Metropolis update of the length scale (nu = L^-1 f held fixed): see gpirt_amd.ell.step_exact."""
-        self._call("gpirt_sampler_draw_ell")
+    def draw_ell(self, kind="whitened"):
+        """One Metropolis update of the length scale.  kind="whitened": the prior-whitened one (nu = L^-1 f held fixed), see
+        gpirt_amd.ell.step_exact; kind="centred": f held fixed and the GP prior decides, see gpirt_amd.ell.step_exact_centred.
+        Each kind has its own width, call count, uniforms and counters."""
+        self._call(_ell_entry(kind, "gpirt_sampler_draw_ell"))
 
-    def ell_width(self, w: int):
-        """The proposal width from the next update on (1 .. points - 1)."""
-        check(self.lib.gpirt_sampler_ell_width(self._s, int(w)))
+    def ell_width(self, w: int, kind="whitened"):
+        """The proposal width of that kind's updates from the next one on (1 .. points - 1)."""
+        check(getattr(self.lib, _ell_entry(kind, "gpirt_sampler_ell_width"))(self._s, int(w)))
 
     def ell_get(self, name: str) -> np.ndarray:
         """One array by name: grid, log_prior (points), index (int64, 1), counts (int64: updates, accepted, out_of_range, failed)
         and, of the last update that reached the device, nu, f_prop (n x m), delta (m), record (dll, log_ratio, log_u, accept,
         nonfinite) and times (ms of device time with enable_timing() on: copies, solve, factor, product, delta, decide, commit,
-        restore)."""
+        restore).  Of the last centred update that reached the device: nu_prop (n x m), dq (m), record_centred (dq, dld,
+        log_ratio, log_u, accept, nonfinite), and counts_centred (int64, as counts), times_centred (_lib.ELL_PARTS_CENTRED).
+        nu is that of whichever update ran last."""
         P = getattr(self, "_ell_points", 0)
-        if name in ("index", "counts"):
+        if name in ("index", "counts", "counts_centred"):
             out = np.empty(1 if name == "index" else 4, dtype=np.int64)
-        elif name in ("nu", "f_prop"):
+        elif name in ("nu", "f_prop", "nu_prop"):
             out = np.empty((self.n, self.m), order="F")
         else:
-            out = np.empty({"delta": self.m, "record": 5, "times": len(_lib.ELL_PARTS)}.get(name, P))
+            out = np.empty({"delta": self.m, "record": 5, "times": len(_lib.ELL_PARTS), "dq": self.m, "record_centred": 6,
+                            "times_centred": len(_lib.ELL_PARTS_CENTRED)}.get(name, P))
         self._get_into("gpirt_sampler_ell_get", name, out)
         return out
 
     def ell(self) -> dict:
         """The length scale's state (gpirt_sampler_ell_stats): index, length_scale, points, width, lo, hi, the counters
         (updates, accepted, out_of_range, failed), accept_rate, factorisations, and of the last update `last` ("accepted",
-        "rejected", "out_of_range", "failed" or None), last_proposed and its two uniforms."""
+        "rejected", "out_of_range", "failed" or None), last_proposed and its two uniforms -- all of the whitened update; under
+        "centred" (gpirt_sampler_ell_centred_stats) the centred update's width, counters, accept_rate, factorisations, last,
+        last_proposed and uniforms."""
         e = _lib.Ell()
         check(self.lib.gpirt_sampler_ell_stats(self._s, C.byref(e)))
         out = {k: int(getattr(e, k)) for k in ("index", "points", "width", "last_proposed", "factorisations") + _lib.ELL_COUNTS}
         out.update({k: float(getattr(e, k)) for k in ("length_scale", "lo", "hi", "last_u0", "last_u1")})
         out["last"] = _lib.ELL_LAST[int(e.last)]
         out["accept_rate"] = out["accepted"] / out["updates"] if out["updates"] else float("nan")
+        c = _lib.EllCentred()
+        check(self.lib.gpirt_sampler_ell_centred_stats(self._s, C.byref(c)))
+        cen = {k: int(getattr(c, k)) for k in ("width", "last_proposed", "factorisations") + _lib.ELL_COUNTS}
+        cen.update(last_u0=float(c.last_u0), last_u1=float(c.last_u1), last=_lib.ELL_LAST[int(c.last)])
+        cen["accept_rate"] = cen["accepted"] / cen["updates"] if cen["updates"] else float("nan")
+        out["centred"] = cen
         return out
 
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)

@@ -55,14 +55,14 @@ enum {
     GPIRT_ST_INIT_F = 1, GPIRT_ST_INIT_BETA = 2, GPIRT_ST_F_Z = 3, GPIRT_ST_F_ESS = 4,
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
-    GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update (gpirt_sampler_draw_ell); nothing else draws from it */
+    GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
 
 typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2087,7 +2087,41 @@ int gpirt_acf_combine(gpirt_handle_t h, int chains, const void* const* d_states,
  * and "record" (5 doubles: dll, log_ratio, log_u, accept, nonfinite); "times" (GPIRT_ELL_PARTS doubles, milliseconds of device
  * time of that update's parts with gpirt_sampler_enable_timing on, else 0: the copies f -> nu's buffer and factor buffer ->
  * saved buffer, the solve, the build and factorisation, the product, the delta, decide and commit kernels, the copy back after
- * a rejection). */
+ * a rejection).
+ *
+ * Library version 126: gpirt_sampler_draw_ell_centred, the companion move of the same paper (section 2.1): f is held fixed, not
+ * nu, and the GP prior decides -- p(k | f, theta) is proportional to prod_j N(f_j; 0, S_k) exp(log_prior[k]); the likelihood
+ * does not enter, since f does not move.  It needs gpirt_sampler_ell_enable, takes the same refusals and is held to the same
+ * contract as gpirt_sampler_draw_ell; gpirt_sampler_draw_ell itself, its uniforms, decisions and counters are untouched by it,
+ * and a sampler that never calls it computes bit for bit what it did under version 125.
+ *   t_c      the number of draw_ell_centred calls on this sampler so far, counted from 1: a counter of its own, which
+ *            survives gpirt_sampler_ell_enable as t does
+ *   u0, u1   item_uniform(seed, t_c, GPIRT_ST_ELL, 1, 0) and (.., 1, 1): item index 1 where the whitened update has 0, so the two
+ *            never share a uniform and calling one never shifts the other's stream
+ *   k' = k + d by the rule above with the centred update's own width w_c: the width given to gpirt_sampler_ell_enable until
+ *   gpirt_sampler_ell_width_centred sets another (gpirt_sampler_ell_width sets the whitened update's alone).  k' outside
+ *   0 .. P - 1: rejected and counted in out_of_range, nothing else runs.
+ *   nu = L^-1 f; S under ell_k' is built and factored (ONE factorisation and TWO solves per update that reaches the device);
+ *   nu' = L'^-1 f.  There is no product and no commit copy: f does not move.
+ *   dq_j = sum over ALL n rows of (nu'_ij - nu_ij) (nu'_ij + nu_ij), formed cell by cell as that product, never as a difference
+ *   of two sums of squares; per item in the order of delta above (256 threads over ascending rows, a fixed tree); dq = the sum
+ *   of dq_j over the items in ascending order.
+ *   dld = sum_i (log L'_ii - log L_ii), each term that difference of two fp64 logarithms; one work-group, 256 threads over
+ *   ascending rows, the same tree.  A diagonal entry that is non-positive or not finite counts as non-finite.
+ *   log_ratio = (-0.5 dq - m dld) + (log_prior[k'] - log_prior[k]), each product and sum rounded on its own;
+ *   accepted iff log(u1) < log_ratio.
+ *   Accepted: k <- k', the sampler's kernel is ell_k'; f is byte-identical to before; L, the rows below it and the cached
+ *   products are bit for bit what gpirt_sampler_factor leaves for (theta, ell_k').  Rejected, out of range or failed (a
+ *   non-positive minor of the proposal's factor, a non-finite nu', diagonal entry, dq or dld): f, L, the rows below it, theta,
+ *   beta, mu and the sampler's kernel are byte-identical to before the call; only the centred counters move.  Not an error.
+ * A call that returns an error has not happened: not counted, t_c does not advance, and for the centred counters too
+ * updates = accepted + rejected + out_of_range + failed always.  A hang-guard expiry in the proposal's factor is repaired once
+ * (the factor again on the launch-per-step panel, then the solve, the kernels and the decision again), as above.
+ * gpirt_ell's counters stay the whitened update's alone; gpirt_sampler_ell_centred_stats fills gpirt_ell_centred with the
+ * centred update's.  gpirt_sampler_ell_get gains "nu_prop" (n x m doubles: nu'), "dq" (m doubles), "record_centred" (6 doubles:
+ * dq, dld, log_ratio, log_u, accept, nonfinite), "counts_centred" (4 int64, as "counts") and "times_centred" (GPIRT_ELL_PARTS
+ * doubles: the copies, the first solve, the build and factorisation, the second solve, the quad, logdet and decide kernels, the
+ * copy back after a rejection).  "nu" is that of whichever update ran last. */
 #define GPIRT_ELL_MAX_POINTS 1025
 #define GPIRT_ELL_PARTS 8
 typedef struct gpirt_ell {
@@ -2100,6 +2134,15 @@ typedef struct gpirt_ell {
     double   last_u0, last_u1;
     int64_t  reserved[4];
 } gpirt_ell;
+typedef struct gpirt_ell_centred {
+    int64_t  width;                         /* w_c */
+    int64_t  updates, accepted, out_of_range, failed;
+    int64_t  last;                          /* the last centred update: 0 rejected, 1 accepted, 2 out of range, 3 failed, -1 none yet */
+    int64_t  last_proposed;                 /* its k' (may lie outside the grid) */
+    int64_t  factorisations;                /* factorisations enqueued by the centred updates so far */
+    double   last_u0, last_u1;
+    int64_t  reserved[6];
+} gpirt_ell_centred;
 int gpirt_ell_grid(double lo, double hi, int P, double* out);
 int gpirt_ell_check(double lo, double hi, int P, const double* log_prior, int width, int k0, const gpirt_kernel* kern,
                     const gpirt_options* opts, int64_t m);
@@ -2108,6 +2151,9 @@ int gpirt_sampler_draw_ell(gpirt_sampler_t s);
 int gpirt_sampler_ell_width(gpirt_sampler_t s, int w);
 int gpirt_sampler_ell_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out);
+int gpirt_sampler_draw_ell_centred(gpirt_sampler_t s);
+int gpirt_sampler_ell_width_centred(gpirt_sampler_t s, int w);
+int gpirt_sampler_ell_centred_stats(gpirt_sampler_t s, gpirt_ell_centred* out);
 
 /* ------------------------------------------------------ the chains with any of the analyses above, in one call -------- */
 /* What gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs: one struct per analysis, each NULL when not wanted, each

@@ -17,6 +17,11 @@
       (4) the launch counts: factorisations enqueued by the updates against the updates that reached the device.
       (5) the acceptance rate at the default width 4 on the default grid (0.25 .. 4, 129 points; kstar_rank as
           gpirt_amd.kernel.fast_rank at 0.25 gives it) over --accept-updates updates after --burn steps, one update per step.
+      (6) the centred update (Sampler.draw_ell("centred")), a section of its own ("centred") in the record: on the sampler of
+          (1) to (4), after them, the parts of --updates centred updates after a step each and, in the same loop, of a whitened
+          update after a step of its own, so that the two are timed side by side; the same parts by outcome under the rising prior
+          table; the quad kernel against the delta kernel and logdet + decide against the whitened decide of that run; then, as
+          (5), the centred update's acceptance on the default grid in a run of its own.
   python tools/ell_cost.py --out profiles/ell_cost.json --readme README.md
       also rewrites the paragraph between the two "ell_cost" marker comments of README.md from the record
   python tools/ell_cost.py --from profiles/ell_cost.json --readme README.md
@@ -34,6 +39,7 @@ sys.path.insert(0, ROOT)
 
 
 BEGIN, END = "<!-- ell_cost: written by tools/ell_cost.py -->", "<!-- /ell_cost -->"
+BEGIN_C, END_C = "<!-- ell_cost_centred: written by tools/ell_cost.py -->", "<!-- /ell_cost_centred -->"
 
 
 def paragraph(r) -> str:
@@ -67,11 +73,44 @@ def paragraph(r) -> str:
     return "\n".join(textwrap.wrap(txt, 124))
 
 
+def paragraph_centred(r) -> str:
+    """the README's paragraph on the centred update's cost from a record's "centred" section"""
+    import textwrap
+    c = r["centred"]
+    p, w, a, d = c["update_parts_ms"], c["whitened_parts_ms"], c["by_outcome"], c["default_grid"]
+    acc, rej = a["accepted"], a["rejected"]
+    txt = (f"The centred update in the same run (`tools/ell_cost.py`, section `centred` of `profiles/ell_cost.json`; the same "
+           f"sampler, grid and options), one centred and one whitened update after a step each, medians of "
+           f"{c['launches']['reached_the_device']} centred updates that reached the device "
+           f"({c['outcomes'].get('accepted', 0)} accepted): {c['update_device_ms']:.2f} ms of device time and "
+           f"{c['update_wall_ms']:.2f} ms by the host's clock, beside {c['whitened_device_ms']:.2f} ms for the whitened update "
+           f"timed in that loop. Its parts: the save copies {p['copies']:.2f} ms, the first solve {p['solve']:.2f} ms, the build "
+           f"and factorisation {p['factor']:.2f} ms, the second solve {p['solve_prop']:.2f} ms (the whitened update's product in "
+           f"its place: {w['product']:.2f} ms), `ell_quad_kernel` {p['quad']:.3f} ms -- {c['quad_kernel']['bytes'] / 1e6:.0f} MB "
+           f"read, {c['quad_kernel']['tb_per_s']:.1f} TB/s; `ell_delta_kernel` in the same loop {w['delta']:.3f} ms --, "
+           f"`ell_logdet_kernel` {p['logdet']:.3f} ms and `ell_decide_centred_kernel` {p['decide']:.3f} ms (`ell_decide_kernel` "
+           f"with the commit behind it: {w['decide'] + w['commit']:.3f} ms). By outcome under the rising prior table "
+           f"({acc['count']} accepted, {rej['count']} rejected, no step between them): {acc['device_ms']:.2f} ms of device time "
+           f"for an accepted update, {rej['device_ms']:.2f} ms for a rejected one, of which the copy back "
+           f"{rej['parts_ms']['restore']:.2f} ms. {c['launches']['factorisations']} factorisations for "
+           f"{c['launches']['reached_the_device']} updates that reached the device. On `make_responses({r['n']}, {r['m']})` with "
+           f"the documented defaults (grid {d['lo']} .. {d['hi']}, {d['points']} points, width {d['width']}, `kstar_rank` = "
+           f"{d['kstar_rank']}) the centred update's acceptance rate is {d['accept_rate']:.2f} over {d['updates']} updates after "
+           f"{r['burn']} steps, one update per step, the index travelling from {d['index_first']} to {d['index_last']} (`ell` "
+           f"{d['length_scale_first']:.2f} to {d['length_scale_last']:.2f}); the whitened update's figure above is from a run of "
+           f"its own under the same conditions.")
+    return "\n".join(textwrap.wrap(txt, 124))
+
+
 def write_readme(path, r):
     src = open(path).read()
     i, j = src.index(BEGIN), src.index(END)
+    src = src[:i + len(BEGIN)] + "\n" + paragraph(r) + "\n" + src[j:]
+    if "centred" in r:
+        i, j = src.index(BEGIN_C), src.index(END_C)
+        src = src[:i + len(BEGIN_C)] + "\n" + paragraph_centred(r) + "\n" + src[j:]
     with open(path, "w") as fh:
-        fh.write(src[:i + len(BEGIN)] + "\n" + paragraph(r) + "\n" + src[j:])
+        fh.write(src)
 
 
 def main():
@@ -183,6 +222,64 @@ def main():
                launches=dict(updates=after["updates"] - before["updates"], reached_the_device=reached,
                              factorisations=after["factorisations"] - before["factorisations"]),
                outcomes={o: outcomes.count(o) for o in set(outcomes)}, accept_rate_this_grid=after["accept_rate"])
+    # (6) the centred update on the same sampler: a centred and a whitened update side by side, a step before each
+    s.ell_enable(lo, hi, points, None, width, k0)
+    s.check()
+    s.enable_timing(True)
+    PC = _lib.ELL_PARTS_CENTRED
+    cparts, wparts, cwall, coutcomes = {k: [] for k in PC}, {k: [] for k in _lib.ELL_PARTS}, [], []
+    cbefore = s.ell()["centred"]
+    for _ in range(args.updates):
+        s.step()
+        s.check()
+        t0 = time.perf_counter()
+        s.draw_ell("centred")
+        cwall.append((time.perf_counter() - t0) * 1e3)
+        o = s.ell()["centred"]["last"]
+        coutcomes.append(o)
+        if o != "out_of_range":
+            for k, v in zip(PC, s.ell_get("times_centred")):
+                cparts[k].append(float(v))
+        s.step()
+        s.check()
+        s.draw_ell()
+        if s.ell()["last"] != "out_of_range":
+            for k, v in zip(_lib.ELL_PARTS, s.ell_get("times")):
+                wparts[k].append(float(v))
+    cafter = s.ell()["centred"]
+    s.ell_enable(lo, hi, points, 1e6 * np.arange(points), width, 0)
+    s.check()
+    cby = {o: dict(parts={k: [] for k in PC}, count=0) for o in ("accepted", "rejected")}
+    for _ in range(args.updates):
+        s.draw_ell("centred")
+        o = s.ell()["centred"]["last"]
+        if o in cby:
+            cby[o]["count"] += 1
+            for k, v in zip(PC, s.ell_get("times_centred")):
+                cby[o]["parts"][k].append(float(v))
+    s.enable_timing(False)
+    s.check()
+    cby_outcome = {}
+    for o, rec_o in cby.items():
+        pm = {k: statistics.median(v) if v else 0.0 for k, v in rec_o["parts"].items()}
+        cby_outcome[o] = dict(count=rec_o["count"], parts_ms=pm, device_ms=sum(pm.values()))
+    creached = [o for o in coutcomes if o != "out_of_range"]
+    cmed = {k: statistics.median(v) if v else 0.0 for k, v in cparts.items()}
+    crestore = [v for v, o in zip(cparts["restore"], creached) if o != "accepted"]
+    cmed["restore"] = statistics.median(crestore) if crestore else 0.0
+    wmed = {k: statistics.median(v) if v else 0.0 for k, v in wparts.items()}
+    cwall_reached = [w for w, o in zip(cwall, coutcomes) if o != "out_of_range"]
+    quad_bytes = 2.0 * 8.0 * n * m
+    rec["centred"] = dict(
+        update_parts_ms=cmed, update_device_ms=sum(v for k, v in cmed.items() if k != "restore"),
+        update_wall_ms=statistics.median(cwall_reached) if cwall_reached else None,
+        whitened_parts_ms=wmed, whitened_device_ms=sum(v for k, v in wmed.items() if k != "restore"), by_outcome=cby_outcome,
+        quad_kernel=dict(bytes=quad_bytes, ms=cmed["quad"], tb_per_s=quad_bytes / (cmed["quad"] * 1e-3) / 1e12 if cmed["quad"] else None),
+        conditions=dict(quad_not_slower_than_delta=bool(cmed["quad"] <= wmed["delta"]), quad_ms=cmed["quad"], delta_ms=wmed["delta"],
+                        logdet_plus_decide_ms=cmed["logdet"] + cmed["decide"], whitened_decide_ms=wmed["decide"]),
+        launches=dict(updates=cafter["updates"] - cbefore["updates"], reached_the_device=len(creached),
+                      factorisations=cafter["factorisations"] - cbefore["factorisations"]),
+        outcomes={o: coutcomes.count(o) for o in set(coutcomes)})
     s.close()
     h.close()
     # (5) the documented defaults
@@ -208,6 +305,28 @@ def main():
                                out_of_range=e["out_of_range"], failed=e["failed"], index_first=idx[0], index_last=idx[-1],
                                index_min=min(idx), index_max=max(idx), length_scale_first=float(gd[idx[0]]),
                                length_scale_last=e["length_scale"])
+    s.close()
+    h.close()
+    # (6) the centred update's acceptance under the same conditions, in a run of its own
+    h = Handle(0, kernel=dict(family="se", length_scale=float(gd[kd])))
+    s = Sampler(h, y, th0, seed=1, rng="item", theta_stabilise=True, fstar_fused=True, kstar_rank=rank)
+    s.init()
+    s.ell_enable()
+    idx = []
+    for it in range(args.burn + args.accept_updates):
+        s.step()
+        if it == args.burn:
+            start = s.ell()["centred"]
+        s.draw_ell("centred")
+        idx.append(s.ell()["index"])
+    s.check()
+    e = s.ell()
+    done = e["centred"]["updates"] - start["updates"]
+    rec["centred"]["default_grid"] = dict(lo=0.25, hi=4.0, points=129, width=4, kstar_rank=rank, updates=done,
+                                          accept_rate=(e["centred"]["accepted"] - start["accepted"]) / done,
+                                          out_of_range=e["centred"]["out_of_range"], failed=e["centred"]["failed"],
+                                          index_first=idx[0], index_last=idx[-1], index_min=min(idx), index_max=max(idx),
+                                          length_scale_first=float(gd[idx[0]]), length_scale_last=e["length_scale"])
     s.close()
     h.close()
     txt = json.dumps(rec, indent=1, default=float)
