@@ -6,8 +6,8 @@ Layout:
   _lib.py          ctypes binding of that C ABI (fails loudly when the library / GPU is missing)
   ops.py           operator-level host API (K, chol, trmm, trsm, draw_f, draw_fstar, ...)
   sampler.py       gpirtMCMC() mirror of the reference's R entry point, and the stage-driven Sampler
-  chains.py ... acf.py        host side of the on-device posterior functionals (chains, quantiles, ppc, ranks, score,
-                   shape, sumscore, equate, loo, acf): the C structs, the pooling of chains and the NumPy statement each is tested against
+  chains.py ... groups.py     host side of the on-device posterior functionals (chains, quantiles, ppc, ranks, score,
+                   shape, sumscore, equate, loo, acf, groups): the C structs, the pooling of chains and the NumPy statement each is tested against
   kernel.py        the covariance kernel of a handle (length scale, Matern 5/2 and 3/2): the NumPy statement, the rank
                    certificate, one run per kernel and their comparison by elpd_loo
   ell.py           the kernel's length scale as a parameter of the chain (a whitened Metropolis update on a grid): the

@@ -420,6 +420,34 @@ class Acf(C.Structure):
                 ("P", C.c_int64), ("chains", C.c_int64), ("reserved", C.c_int64 * 4)]
 
 
+# group posteriors (include/gpirt_hip.h GPIRT_GROUPS_*): the arrays of a state block in order, each (name, dtype, shape key) --
+# the shape keys are those of gpirt_amd.groups.raw_shape
+GROUPS_MAX_G, GROUPS_MAX_N, GROUPS_MAX_M, GROUPS_MAX_TOP, GROUPS_MED_BINS, GROUPS_TAG = 8, 65534, 4096, 64, 2001, 0x31505247
+GROUPS_RAW = (("dens_sum", "u8", "g1k"), ("dens_sq", "u8", "g1k"), ("medhist", "u4", "g1m"), ("order", "u4", "6p"),
+              ("ov_sum", "u8", "p"), ("d_undefined", "u4", "p"), ("mean_sum", "f8", "g1"), ("mean_sq", "f8", "g1"),
+              ("sd_sum", "f8", "g1"), ("sd_sq", "f8", "g1"), ("a_sum", "f8", "p"), ("a_sq", "f8", "p"), ("ovl_sum", "f8", "p"),
+              ("ovl_sq", "f8", "p"), ("d_sum", "f8", "p"), ("d_sq", "f8", "p"), ("median_cover", "u4", "n"),
+              ("median_share", "f8", "n"), ("split_count", "u4", "pm"), ("nsplit_sum", "u8", "p"), ("nsplit_sq", "u8", "p"),
+              ("support_sum", "f8", "gm"), ("support_sq", "f8", "gm"), ("rice_sum", "f8", "gm"), ("rice_sq", "f8", "gm"),
+              ("gap_sum", "f8", "pm"), ("gap_sq", "f8", "pm"), ("loy_sum", "f8", "n"), ("loy_sq", "f8", "n"),
+              ("loy_undefined", "u4", "g"), ("obs_with_sum", "u8", "n"), ("obs_n_sum", "u8", "n"))
+# the last counted draw's tables of gpirt_sampler_groups_get, and the constants
+GROUPS_LAST = (("hist", "u4", "g1k"), ("c1", "i8", "g1"), ("c2", "i8", "g1"), ("med2", "i8", "g1"), ("w", "i8", "p"), ("ov", "i8", "p"),
+               ("latent_stats", "f8", "stats"), ("e", "u8", "gm"), ("side", "i1", "gm"), ("split", "u1", "pm"), ("contested", "u1", "m"),
+               ("n_split", "i8", "p"), ("c_g", "i8", "g"), ("loy", "u8", "n"), ("obs_with", "u4", "n"), ("obs_n", "u4", "n"),
+               ("counts", "i8", "4"), ("group_size", "i8", "9"), ("groups", "i1", "n"))
+
+
+class Groups(C.Structure):
+    """gpirt_groups (include/gpirt_hip.h): top (in), a host pointer per pooled array and list (NULL: not wanted), the counters."""
+    _fields_ = [("top", C.c_int64), ("raw", C.c_void_p * len(GROUPS_RAW)), ("most_split_items", C.POINTER(C.c_int64)),
+                ("most_split_p", C.POINTER(C.c_double)), ("least_loyal", C.POINTER(C.c_int64)),
+                ("least_loyal_loyalty", C.POINTER(C.c_double)), ("n", C.c_int64), ("m", C.c_int64), ("G", C.c_int64),
+                ("pairs", C.c_int64), ("included", C.c_int64), ("chains", C.c_int64), ("latent_draws", C.c_int64),
+                ("latent_skipped", C.c_int64), ("votes_draws", C.c_int64), ("votes_skipped", C.c_int64),
+                ("group_size", C.c_int64 * (GROUPS_MAX_G + 1)), ("reserved", C.c_int64 * 4)]
+
+
 class Run(C.Structure):
     """gpirt_run (include/gpirt_hip.h): what gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs -- R's stream (NULL: the
     item RNG) and one pointer per analysis (NULL: not wanted)."""
@@ -616,6 +644,12 @@ SIGNATURES = {
     "gpirt_sampler_acf_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_acf_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
     "gpirt_acf_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Acf)]),
+    "gpirt_groups_check": (_i32, [_i64, _i64, _i32, C.POINTER(C.c_int32), _i32, C.POINTER(_i64)]),
+    "gpirt_sampler_groups_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), _i32, _i32]),
+    "gpirt_sampler_groups_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_groups_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_groups_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_groups_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(C.c_int), C.POINTER(Groups)]),
     "gpirt_ppc_person_check": (_i32, [_i64, _i64, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
     "gpirt_sampler_ppc_person_enable": (_i32, [_vp, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int), _i32]),
     "gpirt_sampler_ppc_person_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),

@@ -162,7 +162,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 126; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 127; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -206,6 +206,8 @@ int gpirt_version(void) { return 126; }    // 101: gpirt_options names kernel_fp
                                             //      gpirt_kernel_get); gpirt_options, gpirt_run and the gpirt_mcmc* entries are unchanged
                                             // 125: the length scale as a parameter of the chain (ell.hip, sampler.hip: gpirt_ell_grid,
                                             //      gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); stage API only
+                                            // 127: group posteriors (groups.hip: gpirt_groups_check, gpirt_sampler_groups_*,
+                                            //      gpirt_groups_combine); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -948,6 +948,46 @@ int launch_acf_accumulate(hipStream_t stream, AcfState* s, const double* theta, 
 int acf_get(hipStream_t stream, AcfState* s, const char* name, void* h_out, int64_t bytes);
 int acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out);
 
+// groups.hip: group posteriors (gpirt_sampler_groups_*, gpirt_groups_combine; include/gpirt_hip.h, "group posteriors").  The
+// state is ONE device block of 8-byte words: GRP_HEADER_WORDS int64 (tag, layout version, n, m, G, latent_draws, latent_skipped,
+// votes_draws, votes_skipped, 0 ... -- the counters are kept by the kernels), GRP_SIZE_WORDS int64 of group sizes (index G: the
+// included respondents), the codes as n int8, then the GPIRT_GROUPS_* arrays in order, each on a 16-byte boundary.  Everything
+// else is the draw's scratch and the last counted draw's tables.
+constexpr int GRP_LAYOUT_VERSION = 1;
+constexpr int GRP_HEADER_WORDS = 16;
+constexpr int GRP_SIZE_WORDS = 16;
+constexpr int64_t GRP_TAG = 0x31505247;               // "GRP1"
+struct GrpLayout { int64_t groups; int64_t off[GPIRT_GROUPS_NARRAYS]; int64_t words; };
+GrpLayout grp_layout(int64_t n, int64_t m, int64_t G);
+struct GroupsState {
+    bool on = false;
+    int64_t n = 0, m = 0;
+    int G = 0, top = 0;
+    int64_t sizes[GPIRT_GROUPS_MAX_G + 1] = {};
+    uint64_t* block = nullptr;
+    // the draw's scratch: ctl[0] a theta off the grid, ctl[1] a NaN g; hist and e are zeroed before each draw
+    int* ctl = nullptr;
+    uint32_t *hist = nullptr, *less = nullptr, *cnt = nullptr, *obs = nullptr;    // cnt: n_split[P], then c_g[G]
+    uint64_t *e = nullptr, *loy = nullptr;
+    // the last counted draw's tables
+    uint32_t *hist_last = nullptr, *obs_last = nullptr;
+    int64_t *lat_last = nullptr, *cnt_last = nullptr;
+    double* stat_last = nullptr;
+    uint64_t *e_last = nullptr, *loy_last = nullptr;
+    signed char* side_last = nullptr;                 // side [G][m], then split [P][m], then contested [m]
+    std::vector<void*> allocs;
+};
+// the argument check of gpirt_groups_check; sizes: GPIRT_GROUPS_MAX_G + 1 words or NULL
+int groups_check(int64_t n, int64_t m, int G, const int32_t* groups, int top, int64_t* sizes);
+int64_t groups_state_words(const GroupsState* s);
+int groups_alloc(hipStream_t stream, GroupsState* s, int64_t n, int64_t m, int G, const int32_t* groups, int top);
+void groups_free(GroupsState* s);
+// the sampler's theta (n), f, mu and y (n x m) on the device
+int launch_groups_accumulate(hipStream_t stream, GroupsState* s, const double* theta, const double* f, const double* mu,
+                             const double* y);
+int groups_get(hipStream_t stream, GroupsState* s, const char* name, void* h_out, int64_t bytes);
+int groups_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_groups* out);
+
 // misc
 // out (cols x rows, ldo) = in^T, in is rows x cols with leading dimension ldi
 int launch_transpose(hipStream_t stream, const double* in, int64_t rows, int64_t cols, int64_t ldi, double* out, int64_t ldo);

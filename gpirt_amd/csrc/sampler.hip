@@ -179,6 +179,7 @@ struct gpirt_sampler_s {
     EquateState equate;               // two-form score equating (gpirt_sampler_equate_enable; on == false: off)
     LooState loo;                     // PSIS-LOO (gpirt_sampler_loo_enable; on == false: off)
     AcfState acf;                     // autocorrelation ESS (gpirt_sampler_acf_enable; on == false: off)
+    GroupsState groups;               // group posteriors (gpirt_sampler_groups_enable; on == false: off)
     EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
 };
 
@@ -1261,6 +1262,11 @@ Block<AcfState> blk_acf(gpirt_sampler_t s)
     return { &s->acf, s->acf.block, s->acf.on,
              "the autocorrelation ESS is", "gpirt_sampler_acf_enable" };
 }
+Block<GroupsState> blk_groups(gpirt_sampler_t s)
+{
+    return { &s->groups, s->groups.block, s->groups.on,
+             "the group posteriors are", "gpirt_sampler_groups_enable" };
+}
 Block<ScoreState> blk_score(gpirt_sampler_t s)
 {
     return { &s->score, s->score.block, s->score.on,
@@ -1329,8 +1335,9 @@ int acc_sumscore(gpirt_sampler_t s, const DrawView& v) { return launch_sumscore_
 int acc_equate(gpirt_sampler_t s, const DrawView& v) { return launch_equate_accumulate(s->h, s->h->stream, &s->equate, v.fstar); }
 int acc_loo(gpirt_sampler_t s, const DrawView& v) { return launch_loo_accumulate(s->h->stream, &s->loo, v.f, v.mu); }
 int acc_acf(gpirt_sampler_t s, const DrawView& v) { return launch_acf_accumulate(s->h->stream, &s->acf, v.theta, v.beta, v.f, v.mu, s->y); }
+int acc_groups(gpirt_sampler_t s, const DrawView& v) { return launch_groups_accumulate(s->h->stream, &s->groups, v.theta, v.f, v.mu, s->y); }
 
-// mcmc_run's draw: every block that is on (what the run named, enabled before the loop; the ACF is stage-only), in this
+// mcmc_run's draw: every block that is on (what the run named, enabled before the loop; the ACF and the groups are stage-only), in this
 // order on the stream.  A live view needs beta_sync first (the summaries and the PPC read beta and mu).
 int accumulate_run(gpirt_sampler_t s, const DrawView& v)
 {
@@ -1654,6 +1661,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     equate_free(&s->equate);
     loo_free(&s->loo);
     acf_free(&s->acf);
+    groups_free(&s->groups);
     score_free(&s->score);
     ell_free(&s->ell);
     if (s->hU) hipHostFree(s->hU);
@@ -2409,6 +2417,43 @@ int gpirt_sampler_acf_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
 int gpirt_acf_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_acf* out)
 {
     return acf_combine(h, chains, d_states, signs, out);
+}
+
+// ---- group posteriors (groups.hip) on the stage API --------------------------------------------------------------------------
+int gpirt_groups_check(int64_t n, int64_t m, int G, const int32_t* groups, int top, int64_t* sizes_out)
+{
+    return groups_check(n, m, G, groups, top, sizes_out);
+}
+
+int gpirt_sampler_groups_enable(gpirt_sampler_t s, int G, const int32_t* groups, int top, int on)
+{
+    GP_ARG(s && s->initialised);
+    if (on) {                                         // refused before the old state goes
+        if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
+            set_error("groups: not offered for an item shard (the vote part runs over all items)");
+            return GPIRT_E_ARG;
+        }
+        GP_TRY(groups_check(s->n, s->m, G, groups, top, nullptr));
+    }
+    return stage_enable(s, &s->groups, groups_free, on,
+                        [&] { return groups_alloc(s->h->stream, &s->groups, s->n, s->m, G, groups, top); });
+}
+
+int gpirt_sampler_groups_accumulate(gpirt_sampler_t s) { return stage_accumulate(s, blk_groups, acc_groups, true); }
+
+int gpirt_sampler_groups_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    return stage_get(s, blk_groups, groups_get, name, h_out, bytes);
+}
+
+int gpirt_sampler_groups_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    return stage_state(s, blk_groups, groups_state_words, d_state, bytes);
+}
+
+int gpirt_groups_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_groups* out)
+{
+    return groups_combine(h, chains, d_states, signs, out);
 }
 
 // ---- scoring new respondents (score.hip) on the stage API ----------------------------------------------------------------

@@ -321,6 +321,11 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the autocorrelation ESS is not offered for item shards (the respondents' and the "
                          "total log-likelihood series run over all items; each rank holds its own columns)")
 
+    # -- group posteriors (gpirt_amd.groups): the vote part (sides, contested items, loyalty) runs over ALL items
+    def groups_enable(self, groups=None, top=20, on=True):
+        raise ValueError("ShardedSampler: the group posteriors are not offered for item shards (the vote part -- the contested "
+                         "items and every respondent's loyalty -- runs over all items; each rank holds its own columns)")
+
     # -- the length scale in the chain (gpirt_amd.ell): the likelihood change of an update runs over ALL items and the factor is
     # the ranks' common one
     def ell_enable(self, lo=0.25, hi=4.0, points=129, log_prior=None, width=4, k0=None, on=True):

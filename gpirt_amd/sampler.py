@@ -1456,6 +1456,57 @@ class Sampler:
         from . import acf as AC
         return AC.combine(self.handle, [self], signs=[sign], top=top)
 
+    # -- group posteriors (include/gpirt_hip.h gpirt_sampler_groups_*, gpirt_amd.groups)
+    def groups_enable(self, groups=None, top=20, on=True):
+        """Allocate and zero the group posterior state: from then on every groups_accumulate() enters the current theta and
+        f + mu as a draw of the groups' separation, overlap, medians, party-line votes and loyalty.  groups: one code per
+        respondent (-1 = left out, 0 .. G - 1; 2 <= G <= 8, every group with a member); top (1..64): the length of the two lists
+        groups() gives.  Refusals are ValueErrors that say which.  on=False frees the state.  Stage API only: gpirtMCMC has no
+        keyword for it (gpirt_amd.groups.run is the one-call way in)."""
+        if not on:
+            check(self.lib.gpirt_sampler_groups_enable(self._s, 0, None, 0, 0))
+            self._groups = None
+            return
+        from . import groups as GR
+        codes, G = GR.check_groups(groups, self.n, self.m)
+        top = GR.check_top(top)
+        check(self.lib.gpirt_sampler_groups_enable(self._s, G, codes.ctypes.data_as(C.POINTER(C.c_int32)), top, 1))
+        self._groups = (codes, G, top)
+
+    def groups_accumulate(self):
+        """Enter the current theta and f + mu (after a sampling iteration's step) as the next draw.  Nothing is drawn and the
+        chain is untouched; a draw with an included theta off the grid is skipped for the latent part, one with a NaN f + mu
+        for the vote part."""
+        self._call("gpirt_sampler_groups_accumulate")
+
+    def groups_get(self, name: str) -> np.ndarray:
+        """One array by name: an accumulator of _lib.GROUPS_RAW, a constant (counts: int64 latent_draws, latent_skipped,
+        votes_draws, votes_skipped; group_size: int64, 9; groups: int8, n) or a table of the last counted draw
+        (_lib.GROUPS_LAST: hist, c1, c2, med2, w, ov, latent_stats, e, side, split, contested, n_split, c_g, loy, obs_with,
+        obs_n)."""
+        from . import groups as GR
+        _, G, _ = getattr(self, "_groups", None) or (None, 2, 1)        # (not enabled: the library refuses the call)
+        for nm, dt, key in _lib.GROUPS_RAW + _lib.GROUPS_LAST:
+            if nm == name:
+                out = np.empty(GR.raw_shape(key, self.n, self.m, G), dtype=GR._DT[dt])
+                break
+        else:
+            raise ValueError(f"groups_get: unknown array '{name}'")
+        self._get_into("gpirt_sampler_groups_get", name, out)
+        return out
+
+    def groups_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the group posterior state: what
+        gpirt_amd.groups.combine pools."""
+        return self._state("gpirt_sampler_groups_state")
+
+    def groups(self, sign=1, top=None) -> dict:
+        """Every finished output of this sampler's state alone (gpirt_amd.groups.finish's dict): gpirt_groups_combine over it
+        with `sign` (+1, or -1 for the reflected chain)."""
+        from . import groups as GR
+        g = getattr(self, "_groups", None)
+        return GR.combine(self.handle, [self], signs=[sign], top=(g[2] if g else 20) if top is None else top)
+
     # -- the kernel's length scale as a parameter of the chain (include/gpirt_hip.h gpirt_sampler_ell_*, gpirt_amd.ell)
     def ell_enable(self, lo=0.25, hi=4.0, points=129, log_prior=None, width=4, k0=None, on=True):
         """Put the length scale on the logarithmic grid ell_k = lo (hi / lo)^(k / (points - 1)) with the prior mass log_prior

@@ -62,7 +62,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2154,6 +2154,121 @@ int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out);
 int gpirt_sampler_draw_ell_centred(gpirt_sampler_t s);
 int gpirt_sampler_ell_width_centred(gpirt_sampler_t s, int w);
 int gpirt_sampler_ell_centred_stats(gpirt_sampler_t s, gpirt_ell_centred* out);
+
+/* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
+/* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
+ * functionals of the groups and accumulates them, so that no f draw is ever stored.  Stage API only: gpirt_run is unchanged,
+ * nothing is drawn, and a sampler on which gpirt_sampler_groups_enable was never called computes bit for bit what it did.
+ *
+ * GROUP CODES.  One int32 per respondent: -1 = left out, 0 .. G - 1 the groups; 2 <= G <= GPIRT_GROUPS_MAX_G, every group has a
+ * member, n <= GPIRT_GROUPS_MAX_N, m <= GPIRT_GROUPS_MAX_M, top in 1 .. GPIRT_GROUPS_MAX_TOP.  gpirt_groups_check is that
+ * check alone (no device is touched; sizes_out: GPIRT_GROUPS_MAX_G + 1 words, the group sizes n_g and at index G the number of
+ * included respondents; may be NULL).  A left-out respondent takes part in nothing: its theta, f, mu and y are never looked at.
+ * Row G of every per-group array of part A is the group of ALL included respondents.  The P = G (G - 1) / 2 pairs (g, h),
+ * g < h, are indexed in lexicographic order.
+ *
+ * PART A, LATENT (theta alone; every per-draw quantity but the fp64 statistics is an integer).  k_i is theta_i's grid index
+ * (theta_i bit for bit -5 + 0.01 k_i, else the respondent is off the grid), t_i = k_i - 500.  A draw with any included
+ * respondent off the grid is skipped whole (latent_skipped), decided before anything is touched; else latent_draws counts it:
+ *   hist[g][k]   uint32 (G + 1) x 1001: the group's respondents at grid point k
+ *   c1[g], c2[g] int64: sum of t and of t^2
+ *   med2[g]      k at position (n_g + 1) / 2 plus k at position n_g / 2 + 1 of the sorted group (positions from 1; integer
+ *                divisions), 0 .. 2000
+ *   w[p]         U2 - n_g n_h, U2 = sum_k H_g[k] (2 less_h[k] + H_h[k]), less_h[k] = sum_{k' < k} H_h[k']: twice the Mann-Whitney
+ *                count of theta_g > theta_h with ties as a half
+ *   ov[p]        sum_k min(H_g[k] n_h, H_h[k] n_g)
+ *   the order of the means: c1[g] n_h against c1[h] n_g in int64; the order of the medians: med2[g] against med2[h]
+ *   in fp64, each operation rounded on its own (-ffp-contract=off):
+ *     mean_g = c1 / n_g;  var_g = (n_g c2 - c1 c1) / (n_g n_g) (numerator and denominator exact integers, converted, one
+ *     division);  sd_g = sqrt(var_g);  a[p] = w / (n_g n_h);  overlap[p] = ov / (n_g n_h);
+ *     d[p] = (mean_g - mean_h) / sqrt((n_g var_g + n_h var_h) / (n_g + n_h)), each n converted, products before the sum; a
+ *     pooled variance of 0 counts in d_undefined and adds nothing
+ *   per included respondent, within its own group: less = less_g[k_i], eq = H_g[k_i]; it covers a median position q when
+ *   less < q <= less + eq, q1 = (n_g + 1) / 2, q2 = n_g / 2 + 1; c = [covers q1] + [covers q2]; median_cover += (c > 0),
+ *   median_share += c / (2 eq) in fp64.
+ * PART B, VOTES (the n x m pass).  Per cell of an included respondent, observed or not, g = f + mu, e = exp(-|g|),
+ * p = g >= 0 ? 1 / (1 + e) : e / (1 + e), q = g >= 0 ? e / (1 + e) : 1 / (1 + e) (the PPC's expression).  A draw with a NaN g
+ * in any such cell is skipped whole (votes_skipped), decided before anything is touched; +-inf is taken (p is 0 or 1); else
+ * votes_draws counts it.  The two parts skip independently.
+ *   e[g][j]      uint64: sum over the group's members of rint(p 2^44)
+ *   side[g][j]   the sign of 2 e - n_g 2^44 (integers); pair p is split on j when side_g side_h = -1; j is contested when any
+ *                pair splits on it; n_split[p] = its split items; c_g = the contested items with side_g != 0
+ *   support s = (double)e / ((double)n_g 2^44), rice = |2 s - 1|, gap[p][j] = s_g - s_h
+ *   loy[i]       uint64: sum over the contested items j with side_g != 0 of rint(x 2^44), x = p for side_g = +1, q for -1; the
+ *                draw's loyalty is (double)loy / ((double)c_g 2^44); c_g = 0 counts in loy_undefined[g] and adds nothing
+ *   obs_with[i], obs_n[i]: over the same items, the observed cells whose answer is on the group's side, and their number.
+ * ACCUMULATORS (the arrays GPIRT_GROUPS_* of the state block, in this order; every fp64 cell has one owner and is added to
+ * once per counted draw, the value and then its square, in draw order; no floating-point atomics anywhere).
+ * POOLING (gpirt_groups_combine): integers add, fp64 sums add in chain order.  A chain with sign -1 enters part A reflected:
+ * dens_sum, dens_sq and medhist reversed along their grid axis, mean_sum, a_sum and d_sum negated, the > and < order counts
+ * swapped; everything else is even in theta and kept; part B takes no signs.  The struct gets the pooled arrays, the counters,
+ * most_split (per pair the `top` items by split count, ties to the lowest j; -1 beyond m) with p_split = count / votes_draws,
+ * and least_loyal (the `top` included respondents by loy_sum / (votes_draws - loy_undefined[g]) ascending, ties to the
+ * lowest i, respondents without a defined draw left out; -1 and NaN beyond them).
+ * gpirt_sampler_groups_get, by name: every array below in lower case ("dens_sum" ...), "counts" (4 int64: latent_draws,
+ * latent_skipped, votes_draws, votes_skipped), "group_size" (GPIRT_GROUPS_MAX_G + 1 int64), "groups" (n int8) and, of the last
+ * counted draw of its part: "hist" (uint32), "c1", "c2", "med2", "w", "ov" (int64), "latent_stats" (fp64: mean, var, sd of the
+ * G + 1 rows, then a, overlap, d of the P pairs, d NaN where undefined), "e" (uint64 G x m), "side" (int8 G x m), "split" (uint8
+ * P x m), "contested" (uint8 m), "n_split" (int64 P), "c_g" (int64 G), "loy" (uint64 n), "obs_with", "obs_n" (uint32 n).
+ * gpirt_sampler_groups_state returns the ONE device block: 16 int64 (the tag 0x31505247 "GRP1", the layout version 1, n, m, G,
+ * latent_draws, latent_skipped, votes_draws, votes_skipped, 0 ...), 16 int64 of group sizes, the codes as n int8, then the
+ * arrays in order, each on a 16-byte boundary. */
+#define GPIRT_GROUPS_MAX_G            8
+#define GPIRT_GROUPS_MAX_N            65534
+#define GPIRT_GROUPS_MAX_M            4096
+#define GPIRT_GROUPS_MAX_TOP          64
+#define GPIRT_GROUPS_MED_BINS         2001
+#define GPIRT_GROUPS_DENS_SUM         0       /* uint64 [G + 1][1001]: sum of H */
+#define GPIRT_GROUPS_DENS_SQ          1       /* uint64 [G + 1][1001]: sum of H^2 */
+#define GPIRT_GROUPS_MEDHIST          2       /* uint32 [G + 1][2001] */
+#define GPIRT_GROUPS_ORDER            3       /* uint32 [6][P]: mean >, =, <, median >, =, < */
+#define GPIRT_GROUPS_OV_SUM           4       /* uint64 [P] */
+#define GPIRT_GROUPS_D_UNDEFINED      5       /* uint32 [P] */
+#define GPIRT_GROUPS_MEAN_SUM         6       /* double [G + 1] */
+#define GPIRT_GROUPS_MEAN_SQ          7
+#define GPIRT_GROUPS_SD_SUM           8       /* double [G + 1] */
+#define GPIRT_GROUPS_SD_SQ            9
+#define GPIRT_GROUPS_A_SUM            10      /* double [P] */
+#define GPIRT_GROUPS_A_SQ             11
+#define GPIRT_GROUPS_OVL_SUM          12      /* double [P] */
+#define GPIRT_GROUPS_OVL_SQ           13
+#define GPIRT_GROUPS_D_SUM            14      /* double [P] */
+#define GPIRT_GROUPS_D_SQ             15
+#define GPIRT_GROUPS_MEDIAN_COVER     16      /* uint32 [n] */
+#define GPIRT_GROUPS_MEDIAN_SHARE     17      /* double [n] */
+#define GPIRT_GROUPS_SPLIT_COUNT      18      /* uint32 [P][m] */
+#define GPIRT_GROUPS_NSPLIT_SUM       19      /* uint64 [P] */
+#define GPIRT_GROUPS_NSPLIT_SQ        20      /* uint64 [P] */
+#define GPIRT_GROUPS_SUPPORT_SUM      21      /* double [G][m] */
+#define GPIRT_GROUPS_SUPPORT_SQ       22
+#define GPIRT_GROUPS_RICE_SUM         23      /* double [G][m] */
+#define GPIRT_GROUPS_RICE_SQ          24
+#define GPIRT_GROUPS_GAP_SUM          25      /* double [P][m] */
+#define GPIRT_GROUPS_GAP_SQ           26
+#define GPIRT_GROUPS_LOY_SUM          27      /* double [n] */
+#define GPIRT_GROUPS_LOY_SQ           28
+#define GPIRT_GROUPS_LOY_UNDEFINED    29      /* uint32 [G] */
+#define GPIRT_GROUPS_OBS_WITH_SUM     30      /* uint64 [n] */
+#define GPIRT_GROUPS_OBS_N_SUM        31      /* uint64 [n] */
+#define GPIRT_GROUPS_NARRAYS          32
+typedef struct gpirt_groups {
+    int64_t    top;                                  /* in: 1 .. GPIRT_GROUPS_MAX_TOP */
+    void*      raw[GPIRT_GROUPS_NARRAYS];            /* the pooled arrays, on the host, sized as above; NULL: not wanted */
+    int64_t*   most_split_items;                     /* P x top */
+    double*    most_split_p;                         /* P x top */
+    int64_t*   least_loyal;                          /* top */
+    double*    least_loyal_loyalty;                  /* top */
+    int64_t    n, m, G, pairs, included, chains;     /* out */
+    int64_t    latent_draws, latent_skipped, votes_draws, votes_skipped;
+    int64_t    group_size[GPIRT_GROUPS_MAX_G + 1];   /* n_g; at index G the included respondents */
+    int64_t    reserved[4];                          /* zero */
+} gpirt_groups;
+int gpirt_groups_check(int64_t n, int64_t m, int G, const int32_t* groups, int top, int64_t* sizes_out);
+int gpirt_sampler_groups_enable(gpirt_sampler_t s, int G, const int32_t* groups, int top, int on);
+int gpirt_sampler_groups_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_groups_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_groups_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_groups_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, gpirt_groups* out);
 
 /* ------------------------------------------------------ the chains with any of the analyses above, in one call -------- */
 /* What gpirt_mcmc_run computes beside gpirt_mcmc_chains's outputs: one struct per analysis, each NULL when not wanted, each
