@@ -705,6 +705,8 @@ SIGNATURES = {
     "gpirt_sampler_panel_update_part": (_i32, [_vp, _i64, _i64, _i32]),
     "gpirt_sampler_panel_copy_part": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32]),
     "gpirt_sampler_ldl": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_nu_lr_draws": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_nu_lr_rows": (_i32, [_vp, _vp, _i64]),
     "gpirt_sampler_copy_state": (_i32, [_vp, _vp]),
     "gpirt_sampler_accumulate_irf": (_i32, [_vp]),
     "gpirt_sampler_iteration": (_i32, [_vp, C.POINTER(_i32)]),

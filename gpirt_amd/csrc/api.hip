@@ -37,6 +37,7 @@ const Config& env_config()
         d.guard_verbose = env_value("GPIRT_GUARD_VERBOSE", d.guard_verbose);
         d.rs_predict = env_value("GPIRT_RS_PREDICT", d.rs_predict);
         d.rs_lr = env_value("GPIRT_RS_LR", d.rs_lr);
+        d.nu_lr = env_value("GPIRT_NU_LR", d.nu_lr);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -162,7 +163,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 127; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 128; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -208,6 +209,9 @@ int gpirt_version(void) { return 127; }    // 101: gpirt_options names kernel_fp
                                             //      gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); stage API only
                                             // 127: group posteriors (groups.hip: gpirt_groups_check, gpirt_sampler_groups_*,
                                             //      gpirt_groups_combine); stage API only
+                                            // 128: draw_f's nu = L z from L's diagonal parts and 64 node rows below the factor (nu_lr.hip:
+                                            //      GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; every bordered layout
+                                            //      carries the node rows, gpirt_sampler_ldl)
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -337,6 +341,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_EARLY_INV", &h->cfg.early_inv, false }, { "GPIRT_PREP_EARLY", &h->cfg.prep_early, false },
         { "GPIRT_RS_PREDICT", &h->cfg.rs_predict, false },
         { "GPIRT_RS_LR", &h->cfg.rs_lr, false },
+        { "GPIRT_NU_LR", &h->cfg.nu_lr, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }

@@ -76,9 +76,12 @@ struct Config {
     int  theta_fixed = 1;         // GPIRT_THETA_FIXED: 2 = draw_theta's log-posterior product as an fp64 GEMM (theta_fixed.hip)
     int  ess_screen = 1;          // GPIRT_ESS_SCREEN: 2 = every trial point of the slice kernel is evaluated in full precision
     int  bordered = 1;            // GPIRT_BORDERED: 2 = draw_fstar solves for L^-1 K(theta, c) / L^-1 k* explicitly
+                                  //   (the 64 node rows of draw_f's structured product are carried either way)
     int  early_inv = 1;           // GPIRT_EARLY_INV: 2 = no side work beside the factorisation's last outer panel
     int  prep_early = 1;          // GPIRT_PREP_EARLY: 2 = the factor-only part of the rank-r draw_fstar waits for nu = L z
     int  rs_lr = 1;               // GPIRT_RS_LR: 2 = the predictor's every pass reads all of L as floats (no structured form, rs_lr.hip)
+    int  nu_lr = 1;               // GPIRT_NU_LR: draw_f's nu = L z from L's diagonal parts and the 64 node rows (nu_lr.hip): 1 = from n = 2048 on,
+                                  //   2 = always the dense product, 3 = at every eligible n
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)
     int  guard_verbose = 0;       // GPIRT_GUARD_VERBOSE: 1 = a hang-guard fallback prints the guard record to stderr
 };

@@ -219,6 +219,21 @@ void rs_lr_nodes(std::vector<double>& nodes, std::vector<double>& wts, std::vect
 void rs_lr_unit_table(int64_t n, std::vector<uint32_t>& units);
 int launch_rs_lr_setup(hipStream_t stream, const RsLrSetup& q);
 int launch_rs_lr_apply(hipStream_t stream, const Rs3Args& a);
+// nu_lr.hip: draw_f's nu = L z (item-keyed RNG) from L's 512-column diagonal parts and the 64 node rows below the factor
+constexpr int NU_LR_RANK = 64;       // the nodes of cheb_nodes_basis(64)
+constexpr int NU_LR_PART = 512;      // columns per part
+struct NuLrArgs {
+    const double* L; int64_t ldl;     // the dense factor
+    const double* Bt;                 // its node rows, K(c, theta) L^-T (64 x n, leading dimension ldl)
+    const double* V;                  // n x 64 (leading dimension n): the Lagrange basis at theta
+    const double* Z; double* NU;      // n x m each
+    double* T;                        // nu_lr_slabs(n) records of 64 x m
+    int64_t n, m;
+};
+void nu_lr_nodes(std::vector<double>& nodes, std::vector<double>& wts);
+int64_t nu_lr_slabs(int64_t n);
+int launch_nu_lr_basis(hipStream_t stream, const double* theta, int64_t n, const double* nodes, const double* wts, double* V);
+int launch_nu_lr(hipStream_t stream, const NuLrArgs& a, double* flops, double* bytes);
 int launch_rs3p_products(hipStream_t stream, const Rs3Args& a);
 int launch_rs3p_decide(hipStream_t stream, const Rs3Args& a);
 int launch_rs_pred_start(hipStream_t stream, const uint64_t* anchor, uint64_t* anchorP, const int* k_last, int64_t m);

@@ -18,6 +18,7 @@
 // A pass then is:  the predictor's products kernel on the DIAGONAL parts only (32 rows x the 512-column part that holds the
 // row group's diagonal: 16 MB instead of 134) plus 2 x parts units that apply C (as two more "row groups" of tiles) to the
 // part's normals: y_J = C_J z_J;  rs_lr_apply_kernel: nu[rows of part I] += V (sum_{J < I} y_J);  the decide kernel as before.
+// (nu_lr.hip is the fp64 form of the same structure with the factor's own node rows: draw_f's product under the item-keyed RNG.)
 #include "common.h"
 #include "kernels.h"
 #include <utility>

@@ -85,8 +85,23 @@ struct gpirt_sampler_s {
     // rows) and come out as (L^-1 k*)^T -- the 1001-column forward solve of src/draw-fstar.cpp:19 rides through the
     // factorisation the same way.  rows_valid: the rows belong to the current (theta, L); cleared when either is set
     // from outside, rebuilt by an explicit solve on demand (rebuild_rows).
-    int64_t ext = 0, ldl = 0;
-    bool ext_grid = false, rows_valid = false;
+    // Every bordered layout also carries the 64 NODE rows K(c_64, theta) -> K(c_64, theta) L^-T that draw_f's structured product
+    // reads (nu_lr.hip): with kr == 64 they ARE draw_fstar's rows (carried once, shared); with another rank r the node rows
+    // come first and the r rank rows behind them (ext = 64 + r); with the grid rows they sit behind the 1024 (ext = 1088);
+    // a sampler with neither (kr == 0, n < 1024) carries them alone (ext = 64).  node_off / rank_off: first row of each
+    // below row n (node_off < 0: none).
+    // Under GPIRT_BORDERED=2 draw_fstar's rows are not carried (it solves for them: fstar_rows == false, also with kr == 64),
+    // the node rows still are (ext = 64): draw_f's product, and with it f, does not depend on that switch.
+    int64_t ext = 0, ldl = 0, node_off = -1, rank_off = 0;
+    bool ext_grid = false, rows_valid = false, fstar_rows = false;
+    // draw_f's structured product: nodes and weights, the basis at theta (n x 64), the parts' records.  nu_kern_ok: the handle's
+    // kernel passes the rank-64 certificate (under a length-scale update: at the grid's smallest ell); theta_ok: every theta
+    // is finite and inside [-5, 5] -- a HOST-side fact, checked on the host arrays that arrive (create, set) and true by
+    // construction after a draw_theta; theta_alone: theta was set from outside and no factor has followed it, so L need
+    // not be the factor of K(theta, theta); nu_lr_draws: draws that ran the structured product so far
+    double *nu_nodes = nullptr, *nu_wts = nullptr, *nuV = nullptr, *nuT = nullptr;
+    bool nu_kern_ok = false, theta_ok = false, theta_alone = false;
+    int64_t nu_lr_draws = 0;
     // Work that needs only L (not this iteration's f) runs on a stream of the sampler's own, beside draw_f's elliptical
     // slice kernel: the part of the low-rank draw_fstar that depends on the factor alone (C = L^-T B, G = B^T B).
     // haux is the main handle's side handle (h->aux, shared by the samplers of that handle, not owned) on that stream (its own trsm / split-K workspaces: several
@@ -403,6 +418,15 @@ int launch_trmv_lower(hipStream_t st, const double* L, int64_t n, int64_t ldl, c
     return 0;
 }
 
+// does the kernel have the rank-64 form draw_f's structured product rests on (gpirt_kernel_check's certificate)?  The default
+// kernel does (as every rank >= 48 is taken for it at creation); a refusal's message is not an error here
+bool nu_kernel_ok(const KernelSpec& kern)
+{
+    if (kern.is_default()) return true;
+    if (kern.family != GPIRT_KERNEL_SE) return false;          // (a Matern kernel has no such form)
+    return kernel_rank_check(kern, NU_LR_RANK, nullptr, nullptr) == 0;
+}
+
 int fstar_prep(gpirt_sampler_s* s, gpirt_handle_t hh);
 int report_degenerate_theta(gpirt_sampler_s* s, int count);
 int rebuild_rows(gpirt_sampler_s* s);
@@ -426,7 +450,14 @@ int do_draw_f(gpirt_sampler_s* s)
     GP_TRY(beta_sync(s));                     // mu of the previous iteration's draw_beta
     s->factor_fresh = false;
     if (!stream_mode(s)) {
-        const bool prep = s->haux && s->ext > 0 && !s->ext_grid && s->rows_valid && !s->prep_valid;
+        // The structured product (nu_lr.hip) reads the node rows below L: it runs when they are carried and belong to this
+        // (theta, L) -- rebuilt here by the explicit solve if they were left stale --, the kernel has the rank-64 form, K was
+        // built in fp64, every theta lies in the nodes' interval and L is the factor of K(theta, theta) as far as the sampler
+        // can know; from n = 2048 on (GPIRT_NU_LR=3: at every n; =2: never).  Otherwise the dense product, as before.
+        const bool nu_lr = s->node_off >= 0 && s->nuV && h->cfg.nu_lr != 2 && (h->cfg.nu_lr == 3 || n >= 2048) &&
+                           s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && !s->theta_alone;
+        if (nu_lr) GP_TRY(rebuild_rows(s));
+        const bool prep = s->haux && s->kr > 0 && s->fstar_rows && s->rows_valid && !s->prep_valid;
         // The side work (what the low-rank draw_fstar needs from L alone: the last range of block inverses and the
         // 64-column transposed solve, ~0.6 ms of small DEPENDENT launches) starts at once, beside the fill and the product
         // nu = L z.  Until the end of round 3 it waited for the product with all 1024 columns ("its 256 work-groups would
@@ -447,8 +478,20 @@ int do_draw_f(gpirt_sampler_s* s)
         {
             ProfPair pp;                                          // (bench.py's roofline: class 3, n^2 m flops)
             GP_TRY(prof_pair_begin(h, st, pp));
-            GP_TRY(launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->Z, n, 0.0, s->NU, n));
-            GP_TRY(prof_pair_end(h, st, pp, 3, (double)n * (double)n * (double)m, 8.0 * (0.5 * (double)n * (double)n + 2.0 * (double)n * (double)m)));
+            if (nu_lr) {
+                // (class 3 with what actually ran: the diagonal parts' triangles and the rank-64 products)
+                double flops = 0.0, bytes = 0.0;
+                NuLrArgs q{};
+                q.L = s->L; q.ldl = s->ldl; q.Bt = s->L + n + s->node_off; q.V = s->nuV; q.Z = s->Z; q.NU = s->NU; q.T = s->nuT;
+                q.n = n; q.m = m;
+                GP_TRY(launch_nu_lr_basis(st, s->theta, n, s->nu_nodes, s->nu_wts, s->nuV));
+                GP_TRY(launch_nu_lr(st, q, &flops, &bytes));
+                GP_TRY(prof_pair_end(h, st, pp, 3, flops, bytes));
+                s->nu_lr_draws += 1;
+            } else {
+                GP_TRY(launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->Z, n, 0.0, s->NU, n));
+                GP_TRY(prof_pair_end(h, st, pp, 3, (double)n * (double)n * (double)m, 8.0 * (0.5 * (double)n * (double)n + 2.0 * (double)n * (double)m)));
+            }
         }
         if (prep && !early) GP_HIP(hipEventRecord(s->ev_trmm, st));
         EssArgs a{};
@@ -635,7 +678,7 @@ int fstar_prep(gpirt_sampler_s* s, gpirt_handle_t hh)
     const int64_t n = s->n;
     const int r = s->kr;
     double* Cu = s->rhs + (size_t)n * r;
-    const double* Bt = s->L + n;
+    const double* Bt = s->L + n + s->rank_off;
     GP_TRY(launch_transpose(st, Bt, r, n, s->ldl, Cu, n));
     if (hh == s->haux && hh->inv_partial_L == s->L && hh->inv_partial_pairs > 0 && hh->trsm_winv_L != s->L) {
         // most of the block inverses were built while the last outer panel was being factored (do_factor): the rest now.
@@ -672,7 +715,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
         const int r = s->kr;
         double* Bu = s->rhs;                                  // n x r : U, then B
         double* Cu = s->rhs + (size_t)n * r;                  // n x r : B, then C
-        const bool bordered = s->ext > 0;
+        const bool bordered = s->fstar_rows;
         if (bordered) {
             // C = L^-T B and G = B^T B depend on the factor alone: usually already under way on the sampler's own
             // stream since draw_f's product finished (do_draw_f); otherwise computed here
@@ -758,6 +801,7 @@ int do_theta_finish(gpirt_sampler_s* s)
     if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; }
     GP_TRY(launch_theta_sample(st, a));
     if (stream_mode(s)) GP_TRY(launch_advance_pos(st, s->pos, (uint64_t)s->n));
+    s->theta_ok = true;                   // grid values
     return 0;
 }
 
@@ -848,8 +892,11 @@ int build_cov(gpirt_sampler_s* s)
 {
     hipStream_t st = s->h->stream;
     GP_TRY(launch_se_kernel_lower(st, s->kern, s->theta, s->n, s->L, s->ldl, GPIRT_JITTER, s->opt.kernel_fp32 != 0));
-    if (s->ext > 0 && !s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->knodes, s->ext, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
+    if (s->fstar_rows && s->kr > 0) GP_TRY(launch_se_kernel(st, s->kern, s->knodes, s->kr, s->theta, s->n, s->L + s->n + s->rank_off, s->ldl, 0.0));
     if (s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->tstar, s->N, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
+    // the node rows of draw_f's structured product (nu_lr.hip); with kr == 64 they are the rows just written
+    if (s->node_off >= 0 && !(s->fstar_rows && s->kr == NU_LR_RANK))
+        GP_TRY(launch_se_kernel(st, s->kern, s->nu_nodes, NU_LR_RANK, s->theta, s->n, s->L + s->n + s->node_off, s->ldl, 0.0));
     return 0;
 }
 
@@ -858,11 +905,19 @@ int rebuild_rows(gpirt_sampler_s* s)
 {
     if (s->ext == 0 || s->rows_valid) return 0;
     hipStream_t st = s->h->stream;
-    const int64_t n = s->n, cols = s->ext_grid ? s->N : s->kr;
+    const int64_t n = s->n, cols = s->ext_grid ? s->N : (s->fstar_rows ? s->kr : 0);
     double* Bu = s->rhs;
-    GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->ext_grid ? s->tstar : s->knodes, cols, Bu, n, 0.0));
-    GP_TRY(launch_trsm_lower(s->h, st, s->L, n, s->ldl, Bu, cols, n, false));
-    GP_TRY(launch_transpose(st, Bu, n, cols, n, s->L + n, s->ldl));
+    if (cols > 0) {
+        GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->ext_grid ? s->tstar : s->knodes, cols, Bu, n, 0.0));
+        GP_TRY(launch_trsm_lower(s->h, st, s->L, n, s->ldl, Bu, cols, n, false));
+        GP_TRY(launch_transpose(st, Bu, n, cols, n, s->L + n + (s->ext_grid ? 0 : s->rank_off), s->ldl));
+    }
+    if (s->node_off >= 0 && !(s->fstar_rows && s->kr == NU_LR_RANK)) {
+        // the node rows: a 64-column solve of their own in every layout (the same arithmetic whatever rides beside them)
+        GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->nu_nodes, NU_LR_RANK, Bu, n, 0.0));
+        GP_TRY(launch_trsm_lower(s->h, st, s->L, n, s->ldl, Bu, NU_LR_RANK, n, false));
+        GP_TRY(launch_transpose(st, Bu, n, NU_LR_RANK, n, s->L + n + s->node_off, s->ldl));
+    }
     s->rows_valid = true;
     return 0;
 }
@@ -874,6 +929,7 @@ int factor_core(gpirt_sampler_s* s)
     invalidate_factor_products(s);
     GP_TRY(build_cov(s));                                                                                  // :76-77
     s->rows_valid = true;
+    s->theta_alone = false;
     return launch_potrf_lower(s->h, s->h->stream, s->L, s->n, s->ldl, false, !s->sticky_info, s->ext);     // :78
 }
 
@@ -888,7 +944,7 @@ int do_factor(gpirt_sampler_s* s)
     // panel but the last are built on the sampler's own stream while the last outer panel is factored (16 + 8 whole-CU
     // work-groups and small updates: most of the chip is idle then); only the last block and the solve are left behind.
     const bool early_inv = s->h->cfg.early_inv != 2;
-    if (early_inv && s->haux && s->kr > 0 && s->ext > 0 && !s->ext_grid && !stream_mode(s) && s->h->prelast_cols >= 2048) {
+    if (early_inv && s->haux && s->kr > 0 && s->fstar_rows && !stream_mode(s) && s->h->prelast_cols >= 2048) {
         const int64_t p1 = (s->h->prelast_cols / 512) & ~(int64_t)1;
         hipStream_t ax = s->haux->stream;
         GP_HIP(hipStreamWaitEvent(ax, s->h->ev_prelast, 0));
@@ -946,6 +1002,7 @@ int recover_factor(gpirt_sampler_s* s)
     h->cfg.panel = saved;
     GP_TRY(rc);
     s->rows_valid = true;
+    s->theta_alone = false;
     s->factor_fresh = true;
     return 0;
 }
@@ -1442,12 +1499,20 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         return GPIRT_E_ARG;
     }
     const bool bordered_ok = (n % 64) == 0 && h->cfg.bordered != 2;
-    s->ext = (s->kr > 0 && bordered_ok) ? s->kr : 0;
-    if (s->kr == 0 && bordered_ok && n >= 1024) {
-        s->ext = (N + 63) / 64 * 64;          // 1001 grid rows + 23 rows that stay zero
-        s->ext_grid = true;
-    }
+    if (bordered_ok) {
+        // (the node rows of nu_lr.hip in every bordered layout: see node_off)
+        if (s->kr == NU_LR_RANK) { s->ext = s->kr; s->node_off = 0; s->rank_off = 0; s->fstar_rows = true; }
+        else if (s->kr > 0) { s->ext = NU_LR_RANK + s->kr; s->node_off = 0; s->rank_off = NU_LR_RANK; s->fstar_rows = true; }
+        else if (n >= 1024) {
+            s->node_off = (N + 63) / 64 * 64;     // 1001 grid rows + 23 rows that stay zero, then the node rows
+            s->ext = s->node_off + NU_LR_RANK;
+            s->ext_grid = true; s->fstar_rows = true;
+        } else { s->ext = NU_LR_RANK; s->node_off = 0; }
+    } else if ((n % 64) == 0) { s->ext = NU_LR_RANK; s->node_off = 0; }      // GPIRT_BORDERED=2: the node rows alone
     s->ldl = n + s->ext;
+    s->theta_ok = true;
+    for (int64_t i = 0; i < n; ++i) s->theta_ok = s->theta_ok && h_theta0[i] >= -5.0 && h_theta0[i] <= 5.0;
+    s->nu_kern_ok = nu_kernel_ok(s->kern);
     GP_A(s->mu, n * m);      GP_A(s->mu_star, N * m + 1); GP_A(s->fstar, N * m + 1); GP_A(s->L, s->ldl * n);
     GP_A(s->tstar, N + 1);   GP_A(s->rhs, n * (N + m) + 2); GP_A(s->mean, N * m + 1); GP_A(s->s, N + 1);
     GP_A(s->Gpm, ((N + 127) / 128 * 128) * 2 * m + 2); GP_A(s->logpost, N * n + 2); GP_A(s->irf_sum, N * m + 1);
@@ -1459,6 +1524,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     GP_A(s->pm, 2 * m);      GP_A(s->ps, 2 * m);       GP_A(s->step, 2 * m);
     GP_A(s->ess_k, m);       GP_A(s->flags, 4);
     if (!s->opt.fstar_fused) GP_A(s->kstar, n * N + 2);
+    if (s->node_off >= 0) {
+        GP_A(s->nu_nodes, NU_LR_RANK); GP_A(s->nu_wts, NU_LR_RANK);
+        if (!stream_mode(s)) { GP_A(s->nuV, n * NU_LR_RANK); GP_A(s->nuT, nu_lr_slabs(n) * NU_LR_RANK * m); }
+    }
     if (s->kr != 0) {
         GP_A(s->knodes, s->kr); GP_A(s->kV, N * s->kr);
         GP_A(s->kparts, (size_t)KSPLIT * s->kr * (s->kr + m)); GP_A(s->kP, (size_t)s->kr * (s->kr + m));
@@ -1593,6 +1662,13 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         cheb_nodes_basis(r, nodes, V);                                     // (se_kernel.hip)
         hipMemcpyAsync(s->knodes, nodes.data(), sizeof(double) * (size_t)r, hipMemcpyHostToDevice, st);
         hipMemcpyAsync(s->kV, V.data(), sizeof(double) * (size_t)(N * r), hipMemcpyHostToDevice, st);
+    }
+    if (s->node_off >= 0) {
+        std::vector<double> nnodes, wts;
+        nu_lr_nodes(nnodes, wts);                                           // (cheb_nodes_basis(64): with kr == 64, knodes' values)
+        hipMemcpyAsync(s->nu_nodes, nnodes.data(), sizeof(double) * NU_LR_RANK, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(s->nu_wts, wts.data(), sizeof(double) * NU_LR_RANK, hipMemcpyHostToDevice, st);
+        hipStreamSynchronize(st);                                          // (nnodes, wts leave scope)
     }
     hipMemsetAsync(s->L, 0, sizeof(double) * (size_t)(s->ldl * n), st);    // strict upper stays zero
     hipMemsetAsync(s->irf_sum, 0, sizeof(double) * (size_t)(N * m), st);   // :42
@@ -1820,6 +1896,7 @@ int gpirt_sampler_theta_commit(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised && s->theta_stage);
     GP_HIP(hipMemcpyAsync(s->theta, s->theta_stage, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, s->h->stream));
+    s->theta_ok = true;                   // the ranks' blocks of grid values, summed
     return 0;
 }
 int gpirt_sampler_draw_beta(gpirt_sampler_t s) { GP_ARG(s && s->initialised); return do_draw_beta(s); }
@@ -1853,6 +1930,7 @@ int gpirt_sampler_adopt_factor(gpirt_sampler_t s, int rows_with_L)
     invalidate_factor_products(s);
     s->factor_fresh = false;             // (nothing here could rebuild a factor that arrived from elsewhere)
     s->rows_valid = rows_with_L != 0;
+    s->theta_alone = false;
     s->iter += 1;
     return 0;
 }
@@ -2523,6 +2601,7 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
     if (!on) {
         GP_HIP(hipStreamSynchronize(s->h->stream));
         ell_free(&e);
+        s->nu_kern_ok = nu_kernel_ok(s->kern);
         return 0;
     }
     if (!s->initialised) { set_error("gpirt_sampler_ell_enable needs an initialised sampler (gpirt_sampler_init)"); return GPIRT_E_ARG; }
@@ -2566,6 +2645,12 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
     }
     e.k = k0;
     e.on = true;
+    {
+        // draw_f's structured product under a moving length scale: the certificate at the grid's smallest ell covers the grid
+        KernelSpec at_lo = s->kern;
+        at_lo.length_scale = lo; at_lo.inv_ell = 1.0 / lo;
+        s->nu_kern_ok = nu_kernel_ok(at_lo);
+    }
     if (e.grid[(size_t)k0] != s->kern.length_scale) {
         // the chain starts at ell_k0: its factor, through the same core as every other
         int rc = ell_settle_factor(s);
@@ -2784,6 +2869,25 @@ int gpirt_sampler_panel_rows(gpirt_sampler_t s, int64_t* rows)
     return 0;
 }
 
+// draw_f's structured product (nu_lr.hip): how many draws have run it so far, and the 64 node rows below the factor as they
+// stand (64 x n, column-major; GPIRT_E_ARG when the layout carries none)
+int gpirt_sampler_nu_lr_draws(gpirt_sampler_t s, int64_t* draws)
+{
+    GP_ARG(s && draws);
+    *draws = s->nu_lr_draws;
+    return 0;
+}
+
+int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count)
+{
+    GP_ARG(s && h_out && s->node_off >= 0 && count == (int64_t)NU_LR_RANK * s->n);
+    GP_TRY(aux_join(s));
+    GP_HIP(hipMemcpy2DAsync(h_out, (size_t)NU_LR_RANK * 8, s->L + s->n + s->node_off, (size_t)s->ldl * 8, (size_t)NU_LR_RANK * 8, (size_t)s->n,
+                            hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
 // ... and by halves of an outer panel (first sub-panel / the rest), for a host that pipelines the broadcasts
 int gpirt_sampler_panel_factor_part(gpirt_sampler_t s, int64_t p, int half)
 {
@@ -2831,6 +2935,7 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     GP_HIP(hipMemcpy2DAsync(dst->L, (size_t)dst->ldl * 8, src->L, (size_t)src->ldl * 8, (size_t)n * 8, (size_t)n,
                             hipMemcpyDeviceToDevice, st));
     dst->rows_valid = false;
+    dst->theta_ok = src->theta_ok; dst->theta_alone = src->theta_alone;
     GP_TRY(rebuild_rows(dst));            // the rows below L for the copied (theta, L)
     dst->iter = src->iter;
     return 0;
@@ -2864,6 +2969,12 @@ int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, i
     GP_TRY(aux_join(s));
     invalidate_factor_products(s);
     if (strcmp(name, "L") == 0 || strcmp(name, "theta") == 0) s->rows_valid = false;
+    if (strcmp(name, "L") == 0) s->theta_alone = false;          // (taken as the factor of K(theta, theta) for the theta in place)
+    if (strcmp(name, "theta") == 0) {
+        s->theta_alone = true;
+        s->theta_ok = count == s->n;
+        for (int64_t i = 0; i < count; ++i) s->theta_ok = s->theta_ok && h_in[i] >= -5.0 && h_in[i] <= 5.0;
+    }
     if (strcmp(name, "L") == 0 && s->ldl != s->n) {
         GP_ARG(count == s->n * s->n);
         GP_HIP(hipMemcpy2DAsync(p, (size_t)s->ldl * 8, h_in, (size_t)s->n * 8, (size_t)s->n * 8, (size_t)s->n,

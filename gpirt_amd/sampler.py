@@ -712,6 +712,19 @@ class Sampler:
         check(self.lib.gpirt_debug_streams_busy(self.handle.ptr, C.byref(b)))
         return b.value
 
+    @property
+    def nu_lr_draws(self) -> int:
+        """draws of draw_f that formed nu = L z from L's diagonal parts and the 64 node rows (csrc/nu_lr.hip)"""
+        r = C.c_int64()
+        check(self.lib.gpirt_sampler_nu_lr_draws(self._s, C.byref(r)))
+        return r.value
+
+    def nu_lr_rows(self) -> np.ndarray:
+        """the 64 node rows below the factor as they stand, 64 x n"""
+        out = np.empty((64, self.n), order="F")
+        check(self.lib.gpirt_sampler_nu_lr_rows(self._s, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
     def copy_state_from(self, other: "Sampler"):
         check(self.lib.gpirt_sampler_copy_state(self._s, other._s))
 

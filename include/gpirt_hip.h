@@ -62,7 +62,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2389,8 +2389,30 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
  * the factorisation as K(c, theta) (rank-r K*, e = r) or K(theta*, theta) (e = 1024: the 1001 grid points, n >= 1024)
  * and leave it as (L^-1 K(theta, .))^T -- draw_fstar's forward solve (src/draw-fstar.cpp:19) comes out of a bordered
  * factorisation.
- * gpirt_sampler_get / _set("L") always move the n x n factor. */
+ * gpirt_sampler_get / _set("L") always move the n x n factor.
+ * Every such layout also carries 64 NODE rows, K(c_64, theta) for the 64 Chebyshev nodes of the rank-64 form, which leave
+ * the factorisation as K(c_64, theta) L^-T: with r = 64 they are draw_fstar's rows (e = 64); with another rank r they come
+ * first and the r rows behind them (e = 64 + r); with the grid rows they follow the 1024 (e = 1088); a sampler with
+ * neither (rank 0, n < 1024) carries them alone (e = 64), and so does every sampler under GPIRT_BORDERED=2, which switches
+ * off draw_fstar's rows only (f does not depend on that switch).
+ *
+ * draw_f of a sampler under GPIRT_RNG_ITEM forms nu = L z from them (csrc/nu_lr.hip): below a block P of 512 columns
+ * L[i, P] = V[i, :] Bt[:, P] with V the Lagrange basis of the nodes at theta_i and Bt the node rows, so
+ *   nu[P, :] = L[P, P] Z[P, :] + V[P, :] sum_{Q < P} Bt[:, Q] Z[Q, :]
+ * -- about a tenth of the n^2 m flops.  nu then equals L z TO ROUNDING, not bit for bit: measured on the device max |nu - L z| <= 1e-11 with max |nu| = 3 (n = 8192; 2.3e-12 at n = 1088), against the 1e-9 every oracle comparison of f uses.  It does not
+ * depend on the draw_fstar form, on m or on item0 (an item shard's f is bit-identical to the same columns of the full problem).
+ * It runs when n % 64 == 0, n >= 2048, the handle's kernel passes gpirt_kernel_check(kernel,
+ * 64) (under gpirt_sampler_ell_enable: at the grid's smallest length scale), kernel_fp32 == 0, every theta is finite and
+ * inside [-5, 5] (theta_init and gpirt_sampler_set("theta") are looked at on the host; draw_theta's values are grid values),
+ * and L is the factor of K(theta, theta): a gpirt_sampler_set("theta") that no factorisation, adopted factor or
+ * gpirt_sampler_set("L") has followed takes the dense product, and a caller who sets both sets a matching pair.
+ * Otherwise the dense product runs, as before.  GPIRT_NU_LR (gpirt_config_set): 1 this rule, 2 always dense, 3 at every
+ * eligible n.  The operators gpirt_draw_f / gpirt_trmm_lz are given L, not theta, and keep the dense product.
+ * gpirt_sampler_nu_lr_draws: how many draws of this sampler have run the structured product; gpirt_sampler_nu_lr_rows:
+ * the node rows as they stand (64 x n, column-major, count = 64 n; GPIRT_E_ARG when the layout carries none). */
 int gpirt_sampler_ldl(gpirt_sampler_t s, int64_t* ldl);
+int gpirt_sampler_nu_lr_draws(gpirt_sampler_t s, int64_t* draws);
+int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count);
 /* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m.  The kernel
  * is not part of the state: refused (GPIRT_E_ARG) when the two samplers' kernels differ, or while the length-scale update
  * (gpirt_sampler_ell_enable) is on for either -- its index and tables are not copied. */
