@@ -12,6 +12,8 @@ Layout:
                    certificate, one run per kernel and their comparison by elpd_loo
   ell.py           the kernel's length scale as a parameter of the chain (a whitened Metropolis update on a grid): the
                    NumPy statement of one update, the exact conditional posterior, the one-call run
+  amp.py           per-item GP amplitudes, fixed or sampled in the chain (one launch updates every item on a grid): the
+                   NumPy statement of one update, the exact conditional posterior per item, the one-call run
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

@@ -20,6 +20,7 @@ RNG_RSTREAM, RNG_ITEM = 0, 1
 ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3, 4, 5, 6, 7
 ST_PPC = 8                        # the replicate of the posterior predictive checks (gpirt_amd.ppc)
 ST_ELL = 9                        # the two uniforms of a length-scale update (gpirt_amd.ell): item index 0 whitened, 1 centred
+ST_AMP = 10                       # the two uniforms per item of an amplitude update (gpirt_amd.amp): item index item0 + j
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
@@ -506,6 +507,21 @@ class EllCentred(C.Structure):
         (k, C.c_double) for k in ("last_u0", "last_u1")] + [("reserved", C.c_int64 * 6)]
 
 
+# per-item GP amplitudes (include/gpirt_hip.h gpirt_amp; gpirt_amd.amp)
+AMP_MAX_POINTS = 1025
+AMP_MIN, AMP_MAX = 0.01, 1000.0
+AMP_COUNTS = ("updates", "accepted", "out_of_range", "failed")             # the rows of amp_get("counts")
+AMP_RECORD = ("dll", "log_ratio", "log_u", "status", "nonfinite")          # the rows of amp_get("record")
+AMP_STATUS = ("rejected", "accepted", "out_of_range", "failed")            # a record's status by its code
+AMP_MODES = (None, "fixed", "sampled")
+
+
+class Amp(C.Structure):
+    """gpirt_amp (include/gpirt_hip.h): the mode, the grid's size, the totals over the items and the pooled acceptance."""
+    _fields_ = [(k, C.c_int64) for k in ("on", "points", "m", "calls") + AMP_COUNTS + ("planned_draws", "recorded")] + [
+        (k, C.c_double) for k in ("accept_rate", "lo", "hi", "min_amplitude", "max_amplitude")] + [("reserved", C.c_int64 * 4)]
+
+
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _vp, _i64, _i32, _u64, _u32, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_double
@@ -732,6 +748,14 @@ SIGNATURES = {
     "gpirt_sampler_draw_ell_centred": (_i32, [_vp]),
     "gpirt_sampler_ell_width_centred": (_i32, [_vp, _i32]),
     "gpirt_sampler_ell_centred_stats": (_i32, [_vp, C.POINTER(EllCentred)]),
+    "gpirt_amp_check": (_i32, [_dbl, _dbl, _i32, _dp, _i32, C.POINTER(_i32), _i64, C.POINTER(Options)]),
+    "gpirt_sampler_amp_set": (_i32, [_vp, _dp]),
+    "gpirt_sampler_amp_enable": (_i32, [_vp, _dbl, _dbl, _i32, _dp, _i32, C.POINTER(_i32), _i64, _i32]),
+    "gpirt_sampler_draw_amp": (_i32, [_vp]),
+    "gpirt_sampler_amp_width": (_i32, [_vp, C.POINTER(_i32)]),
+    "gpirt_sampler_amp_record": (_i32, [_vp]),
+    "gpirt_sampler_amp_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_amp_stats": (_i32, [_vp, C.POINTER(Amp)]),
 }
 
 _lib = None

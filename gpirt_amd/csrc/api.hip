@@ -163,7 +163,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 128; }    // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 129; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -212,6 +212,8 @@ int gpirt_version(void) { return 128; }    // 101: gpirt_options names kernel_fp
                                             // 128: draw_f's nu = L z from L's diagonal parts and 64 node rows below the factor (nu_lr.hip:
                                             //      GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; every bordered layout
                                             //      carries the node rows, gpirt_sampler_ldl)
+                                            // 129: per-item GP amplitudes, fixed or sampled in the chain (amp.hip, sampler.hip:
+                                            //      gpirt_amp_check, gpirt_sampler_amp_*, gpirt_sampler_draw_amp); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -62,6 +62,20 @@ int launch_ell_quad(hipStream_t st, const double* nu, const double* nup, int64_t
 int launch_ell_logdet(hipStream_t st, const double* Lold, const double* Lnew, int64_t n, int64_t ldl, double* out);
 int launch_ell_decide_centred(hipStream_t st, const double* dq, const int* nonfin, int64_t m, const double* ld, double lp_diff,
                               double log_u, const int* info, double* rec, int* flag);
+// amp.hip: per-item GP amplitudes (gpirt_sampler_amp_*)
+int launch_amp_scale(hipStream_t st, double* nu, const double* amp, int64_t n, int64_t m);              // nu_ij <- a_j nu_ij
+struct AmpUpdateArgs {
+    double* f; const double* mu; const double* y; int64_t n, m;
+    const double* grid; const double* log_prior; int P;                 // device tables of P values
+    int* idx; const int* width; double* amp;                            // m each
+    long long* counts; double* rec;                                     // 4 x m, 5 x m, row-major (item j's values at stride m)
+    uint64_t seed; uint32_t t; uint32_t item0;
+};
+// one update of every item's amplitude: one work-group per item, f rewritten in place where the item accepts
+int launch_amp_update(hipStream_t st, const AmpUpdateArgs& a);
+// draws[slot, j] = idx[j] (planned x m, row-major), hist[idx[j], j] += 1 (P x m, row-major)
+int launch_amp_record(hipStream_t st, const int* idx, int64_t m, int P, int64_t slot, uint32_t* hist, int32_t* draws);
+int amp_nearest_one(const double* grid, int P);                     // the grid point nearest 1 in log a (the first of a tie)
 int ell_grid_check(double lo, double hi, int P);                    // GPIRT_E_ARG with the message
 void ell_grid_fill(double lo, double hi, int P, double* out);         // long double, rounded to fp64, the end points exact
 
@@ -256,6 +270,7 @@ struct FstarEpiArgs {
     const double* U; uint64_t* pos; uint64_t cap; int* err;   // R-stream replay when U != null
     double* mean_out;     // optional copy of mean + mu_star
     int* off_scratch;     // N + 1 ints of device scratch for the R-stream consumption offsets
+    const double* amp;    // optional per-item amplitudes (m): sd = amp[j] * s[i]; null: sd = s[i]
 };
 int launch_fstar_epilogue(hipStream_t stream, const FstarEpiArgs& a);
 

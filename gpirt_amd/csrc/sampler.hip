@@ -62,6 +62,25 @@ struct EllState {
     hipEvent_t tev[GPIRT_ELL_PARTS + 2] = {};
 };
 
+// Per-item GP amplitudes (gpirt_sampler_amp_set / gpirt_sampler_amp_enable; include/gpirt_hip.h, amp.hip).  mode 0: off (draw_f
+// and draw_fstar are the unit model's), 1: fixed, 2: on the grid.  The indices, widths, counters and records live on the device:
+// an update is one launch and no host read.
+struct AmpState {
+    int mode = 0;
+    int P = 0;
+    int64_t planned = 0, recorded = 0;
+    uint32_t t = 0;                   // draw_amp calls so far (it survives enabling again: no pair of uniforms is replayed)
+    std::vector<double> grid, log_prior;
+    double *amp = nullptr, *d_grid = nullptr, *d_log_prior = nullptr, *rec = nullptr;      // device: m, P, P, 5 x m
+    int *idx = nullptr, *width = nullptr;                                                  // device: m, m
+    long long* counts = nullptr;                                                           // device: 4 x m
+    uint32_t* hist = nullptr;                                                              // device: P x m
+    int32_t* draws = nullptr;                                                              // device: planned x m
+    // with gpirt_sampler_enable_timing on: the device time of the last update's one launch ("time" of gpirt_sampler_amp_get)
+    hipEvent_t tev[2] = {};
+    double last_ms = 0.0;
+};
+
 struct gpirt_sampler_s {
     gpirt_handle_t h = nullptr;
     int64_t n = 0, m = 0, N = GPIRT_NGRID;
@@ -196,6 +215,7 @@ struct gpirt_sampler_s {
     AcfState acf;                     // autocorrelation ESS (gpirt_sampler_acf_enable; on == false: off)
     GroupsState groups;               // group posteriors (gpirt_sampler_groups_enable; on == false: off)
     EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
+    AmpState amp;                     // per-item GP amplitudes (gpirt_sampler_amp_set, gpirt_sampler_amp_enable; mode == 0: off)
 };
 
 namespace {
@@ -493,6 +513,7 @@ int do_draw_f(gpirt_sampler_s* s)
                 GP_TRY(prof_pair_end(h, st, pp, 3, (double)n * (double)n * (double)m, 8.0 * (0.5 * (double)n * (double)n + 2.0 * (double)n * (double)m)));
             }
         }
+        if (s->amp.mode) GP_TRY(launch_amp_scale(st, s->NU, s->amp.amp, n, m));       // nu_j = a_j (L z_j)
         if (prep && !early) GP_HIP(hipEventRecord(s->ev_trmm, st));
         EssArgs a{};
         a.f = s->f; a.nu = s->NU; a.y = s->y; a.mu = s->mu; a.n = n; a.m = m; a.k_out = s->ess_k;
@@ -739,6 +760,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
         a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0; a.err = s->flags;
         if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; a.off_scratch = s->fstar_off; }
         if (s->shape.on) a.mean_out = s->shape.gbar;          // the draw's smooth curve, for the shape posteriors
+        if (s->amp.mode) a.amp = s->amp.amp;
         return launch_fstar_epilogue(st, a);
     }
     GP_HIP(hipMemcpyAsync(W, s->f, sizeof(double) * (size_t)n * m, hipMemcpyDeviceToDevice, st));
@@ -770,6 +792,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
     a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0; a.err = s->flags;
     if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; a.off_scratch = s->fstar_off; }
     if (s->shape.on) a.mean_out = s->shape.gbar;
+    if (s->amp.mode) a.amp = s->amp.amp;
     return launch_fstar_epilogue(st, a);                                                      // :26-28
 }
 
@@ -1030,6 +1053,18 @@ void ell_free(EllState* e)
     const uint32_t calls[2] = { e->up[ELL_WHITENED].t, e->up[ELL_CENTRED].t };
     *e = EllState();
     e->up[ELL_WHITENED].t = calls[0]; e->up[ELL_CENTRED].t = calls[1];
+}
+
+// ---- per-item GP amplitudes (include/gpirt_hip.h; the kernels are amp.hip's) ---------------------------------------------------
+void amp_free(AmpState* a)
+{
+    for (void* p : { (void*)a->amp, (void*)a->d_grid, (void*)a->d_log_prior, (void*)a->rec, (void*)a->idx, (void*)a->width,
+                     (void*)a->counts, (void*)a->hist, (void*)a->draws })
+        if (p) hipFree(p);
+    for (hipEvent_t t : a->tev) if (t) hipEventDestroy(t);
+    const uint32_t calls = a->t;      // the sampler's draw_amp calls: enabling again does not replay their uniforms
+    *a = AmpState();
+    a->t = calls;
 }
 
 // The main stream waits for whatever the sampler's own stream still has in flight -- the early block inverses read L, a
@@ -1740,6 +1775,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     groups_free(&s->groups);
     score_free(&s->score);
     ell_free(&s->ell);
+    amp_free(&s->amp);
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -2676,6 +2712,11 @@ int gpirt_sampler_draw_ell_centred(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised);
     GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
+    if (s->amp.mode) {
+        set_error("gpirt_sampler_draw_ell_centred is refused while per-item amplitudes are on: its quadratic form would need "
+                  "1 / a_j^2 per item (the whitened update does not contain a_j and runs)");
+        return GPIRT_E_ARG;
+    }
     return do_draw_ell(s, ELL_CENTRED);
 }
 
@@ -2760,6 +2801,227 @@ int gpirt_sampler_ell_centred_stats(gpirt_sampler_t s, gpirt_ell_centred* out)
     out->updates = c.updates; out->accepted = c.accepted; out->out_of_range = c.out_of_range; out->failed = c.failed;
     out->last = c.last; out->last_proposed = c.last_proposed; out->factorisations = c.factorisations;
     out->last_u0 = c.last_u0; out->last_u1 = c.last_u1;
+    return 0;
+}
+
+// ---- per-item GP amplitudes ---------------------------------------------------------------------------------------------------
+static int amp_refusals(gpirt_sampler_t s, const char* entry)
+{
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", entry); return GPIRT_E_ARG; }
+    return gpirt_amp_check(GPIRT_AMP_MIN, GPIRT_AMP_MAX, 2, nullptr, 1, nullptr, s->m, &s->opt);      // (the options' refusals)
+}
+
+int gpirt_sampler_amp_set(gpirt_sampler_t s, const double* a)
+{
+    GP_ARG(s != nullptr);
+    AmpState& A = s->amp;
+    if (!a) {
+        if (A.mode == 2) { set_error("gpirt_sampler_amp_set(NULL): the amplitudes are on the grid, gpirt_sampler_amp_enable(on = 0) turns them off"); return GPIRT_E_ARG; }
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        amp_free(&A);
+        return 0;
+    }
+    if (A.mode == 2) {
+        set_error("gpirt_sampler_amp_set after gpirt_sampler_amp_enable: turn the sampled amplitudes off first (on = 0)");
+        return GPIRT_E_ARG;
+    }
+    GP_TRY(amp_refusals(s, "gpirt_sampler_amp_set"));
+    const int64_t m = s->m;
+    for (int64_t j = 0; j < m; ++j)
+        if (!std::isfinite(a[j]) || !(a[j] >= GPIRT_AMP_MIN) || !(a[j] <= GPIRT_AMP_MAX)) {
+            set_error("amplitude: a[%lld] = %g, it must be finite and lie in %g .. %g", (long long)j, a[j], (double)GPIRT_AMP_MIN,
+                      (double)GPIRT_AMP_MAX);
+            return GPIRT_E_ARG;
+        }
+    hipStream_t st = s->h->stream;
+    if (!A.amp && hipMalloc((void**)&A.amp, sizeof(double) * (size_t)m) != hipSuccess) {
+        set_error("amplitude: hipMalloc failed");
+        return GPIRT_E_ALLOC;
+    }
+    GP_HIP(hipMemcpyAsync(A.amp, a, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, st));
+    GP_HIP(hipStreamSynchronize(st));
+    A.mode = 1;
+    return 0;
+}
+
+int gpirt_sampler_amp_enable(gpirt_sampler_t s, double lo, double hi, int P, const double* log_prior, int width, const int* k0,
+                             int64_t planned_draws, int on)
+{
+    GP_ARG(s != nullptr);
+    AmpState& A = s->amp;
+    if (!on) {
+        if (A.mode == 1) { set_error("gpirt_sampler_amp_enable(on = 0): the amplitudes are fixed, gpirt_sampler_amp_set(NULL) turns them off"); return GPIRT_E_ARG; }
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        amp_free(&A);
+        return 0;
+    }
+    if (A.mode == 1) {
+        set_error("gpirt_sampler_amp_enable after gpirt_sampler_amp_set: turn the fixed amplitudes off first (gpirt_sampler_amp_set(NULL))");
+        return GPIRT_E_ARG;
+    }
+    if (!s->initialised) { set_error("gpirt_sampler_amp_enable needs an initialised sampler (gpirt_sampler_init)"); return GPIRT_E_ARG; }
+    const int64_t m = s->m;
+    GP_TRY(gpirt_amp_check(lo, hi, P, log_prior, width, k0, m, &s->opt));
+    if (planned_draws < 0 || planned_draws > (int64_t)1 << 31) {
+        set_error("amplitude: planned_draws = %lld, it must lie in 0 .. 2^31", (long long)planned_draws);
+        return GPIRT_E_ARG;
+    }
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipStreamSynchronize(st));
+    amp_free(&A);
+    auto fail = [&](int rc, const char* what) { set_error("amplitude: %s failed", what); amp_free(&A); return rc; };
+    const size_t hist_bytes = sizeof(uint32_t) * (size_t)P * (size_t)m, draw_bytes = sizeof(int32_t) * (size_t)(planned_draws ? planned_draws : 1) * (size_t)m;
+    if (hipMalloc((void**)&A.amp, sizeof(double) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.d_grid, sizeof(double) * (size_t)P) != hipSuccess ||
+        hipMalloc((void**)&A.d_log_prior, sizeof(double) * (size_t)P) != hipSuccess ||
+        hipMalloc((void**)&A.rec, sizeof(double) * 5 * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.idx, sizeof(int) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.width, sizeof(int) * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.counts, sizeof(long long) * 4 * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.hist, hist_bytes) != hipSuccess ||
+        hipMalloc((void**)&A.draws, draw_bytes) != hipSuccess) return fail(GPIRT_E_ALLOC, "hipMalloc");
+    A.P = P; A.planned = planned_draws; A.recorded = 0;
+    A.grid.resize((size_t)P); A.log_prior.resize((size_t)P);
+    ell_grid_fill(lo, hi, P, A.grid.data());
+    for (int k = 0; k < P; ++k) {
+        const long double l = logl((long double)A.grid[(size_t)k]);
+        A.log_prior[(size_t)k] = log_prior ? log_prior[k] : (double)(-(l * l) / 2.0L);
+    }
+    const int near1 = amp_nearest_one(A.grid.data(), P);
+    std::vector<int> idx((size_t)m), wd((size_t)m, width);
+    std::vector<double> amp((size_t)m);
+    for (int64_t j = 0; j < m; ++j) {
+        idx[(size_t)j] = k0 ? k0[j] : near1;
+        amp[(size_t)j] = A.grid[(size_t)idx[(size_t)j]];
+    }
+    if (hipMemcpyAsync(A.d_grid, A.grid.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_log_prior, A.log_prior.data(), sizeof(double) * (size_t)P, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.amp, amp.data(), sizeof(double) * (size_t)m, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.idx, idx.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.width, wd.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(A.rec, 0, sizeof(double) * 5 * (size_t)m, st) != hipSuccess ||
+        hipMemsetAsync(A.counts, 0, sizeof(long long) * 4 * (size_t)m, st) != hipSuccess ||
+        hipMemsetAsync(A.hist, 0, hist_bytes, st) != hipSuccess ||
+        hipMemsetAsync(A.draws, 0, draw_bytes, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return fail(GPIRT_E_HIP, "the upload");      // (the host vectors go out of scope)
+    A.mode = 2;
+    return 0;
+}
+
+int gpirt_sampler_draw_amp(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    AmpState& A = s->amp;
+    GP_TRY(needs(A.mode == 2, "the amplitude update is", "gpirt_sampler_amp_enable"));
+    // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
+    GP_TRY(beta_sync(s));
+    AmpUpdateArgs a{};
+    a.f = s->f; a.mu = s->mu; a.y = s->y; a.n = s->n; a.m = s->m;
+    a.grid = A.d_grid; a.log_prior = A.d_log_prior; a.P = A.P;
+    a.idx = A.idx; a.width = A.width; a.amp = A.amp; a.counts = A.counts; a.rec = A.rec;
+    a.seed = s->opt.seed; a.t = A.t + 1; a.item0 = (uint32_t)s->opt.item0;
+    hipStream_t st = s->h->stream;
+    const bool timed = s->timing;
+    if (timed) {
+        for (hipEvent_t& t : A.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(A.tev[0], st));
+    }
+    GP_TRY(launch_amp_update(st, a));
+    A.t += 1;
+    if (timed) {                              // (timing on: one synchronisation, as the length-scale update's)
+        GP_HIP(hipEventRecord(A.tev[1], st));
+        GP_HIP(hipEventSynchronize(A.tev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, A.tev[0], A.tev[1]);
+        A.last_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_amp_width(gpirt_sampler_t s, const int* w)
+{
+    GP_ARG(s && w);
+    AmpState& A = s->amp;
+    GP_TRY(needs(A.mode == 2, "the amplitude update is", "gpirt_sampler_amp_enable"));
+    for (int64_t j = 0; j < s->m; ++j)
+        if (w[j] < 1 || w[j] > A.P - 1) {
+            set_error("amplitude: width[%lld] = %d, it must lie in 1 .. P - 1 = %d", (long long)j, w[j], A.P - 1);
+            return GPIRT_E_ARG;
+        }
+    GP_HIP(hipMemcpyAsync(A.width, w, sizeof(int) * (size_t)s->m, hipMemcpyHostToDevice, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_amp_record(gpirt_sampler_t s)
+{
+    GP_ARG(s != nullptr);
+    AmpState& A = s->amp;
+    GP_TRY(needs(A.mode == 2, "the amplitude update is", "gpirt_sampler_amp_enable"));
+    if (A.recorded >= A.planned) {
+        set_error("amplitude: all %lld planned draws are recorded", (long long)A.planned);
+        return GPIRT_E_ARG;
+    }
+    GP_TRY(launch_amp_record(s->h->stream, A.idx, s->m, A.P, A.recorded, A.hist, A.draws));
+    A.recorded += 1;
+    return 0;
+}
+
+int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    AmpState& A = s->amp;
+    GP_TRY(needs(A.mode != 0, "per-item amplitudes are", "gpirt_sampler_amp_set, gpirt_sampler_amp_enable"));
+    const int64_t m = s->m, P = A.P;
+    const void* host = nullptr; const void* dev = nullptr; int64_t want = 0;
+    if (strcmp(name, "amplitude") != 0) GP_TRY(needs(A.mode == 2, "the amplitude update is", "gpirt_sampler_amp_enable"));
+    if (strcmp(name, "amplitude") == 0) { dev = A.amp; want = 8 * m; }
+    else if (strcmp(name, "grid") == 0) { host = A.grid.data(); want = 8 * P; }
+    else if (strcmp(name, "log_prior") == 0) { host = A.log_prior.data(); want = 8 * P; }
+    else if (strcmp(name, "index") == 0) { dev = A.idx; want = 4 * m; }
+    else if (strcmp(name, "width") == 0) { dev = A.width; want = 4 * m; }
+    else if (strcmp(name, "counts") == 0) { dev = A.counts; want = 32 * m; }
+    else if (strcmp(name, "record") == 0) { dev = A.rec; want = 40 * m; }
+    else if (strcmp(name, "hist") == 0) { dev = A.hist; want = 4 * P * m; }
+    else if (strcmp(name, "draws") == 0) { dev = A.draws; want = 4 * A.recorded * m; }
+    else if (strcmp(name, "time") == 0) { host = &A.last_ms; want = 8; }
+    else { set_error("unknown amplitude array '%s'", name); return GPIRT_E_ARG; }
+    if (bytes != want) { set_error("amplitude: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    if (want == 0) return 0;
+    if (host) { memcpy(h_out, host, (size_t)want); return 0; }
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out)
+{
+    GP_ARG(s && out);
+    const AmpState& A = s->amp;
+    memset(out, 0, sizeof(*out));
+    out->on = A.mode; out->m = s->m; out->calls = A.t;
+    out->accept_rate = (double)NAN; out->lo = out->hi = out->min_amplitude = out->max_amplitude = (double)NAN;
+    if (A.mode == 0) return 0;
+    const int64_t m = s->m;
+    std::vector<double> amp((size_t)m);
+    std::vector<long long> cnt(A.mode == 2 ? 4 * (size_t)m : 0);
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(amp.data(), A.amp, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+    if (A.mode == 2) GP_HIP(hipMemcpyAsync(cnt.data(), A.counts, sizeof(long long) * 4 * (size_t)m, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    out->min_amplitude = out->max_amplitude = amp[0];
+    for (int64_t j = 1; j < m; ++j) {
+        if (amp[(size_t)j] < out->min_amplitude) out->min_amplitude = amp[(size_t)j];
+        if (amp[(size_t)j] > out->max_amplitude) out->max_amplitude = amp[(size_t)j];
+    }
+    if (A.mode != 2) return 0;
+    out->points = A.P; out->planned_draws = A.planned; out->recorded = A.recorded;
+    out->lo = A.grid.front(); out->hi = A.grid.back();
+    for (int64_t j = 0; j < m; ++j) {
+        out->updates += cnt[(size_t)j]; out->accepted += cnt[(size_t)(m + j)];
+        out->out_of_range += cnt[(size_t)(2 * m + j)]; out->failed += cnt[(size_t)(3 * m + j)];
+    }
+    if (out->updates) out->accept_rate = (double)out->accepted / (double)out->updates;
     return 0;
 }
 
@@ -2914,6 +3176,10 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     GP_ARG(dst && src && dst->initialised && src->initialised && dst->n == src->n && dst->m == src->m && dst->h == src->h);
     if (dst->ell.on || src->ell.on) {
         set_error("gpirt_sampler_copy_state is not defined while the length-scale update is on (the index and its tables are not copied)");
+        return GPIRT_E_ARG;
+    }
+    if (dst->amp.mode || src->amp.mode) {
+        set_error("gpirt_sampler_copy_state is not defined while per-item amplitudes are on (they are not copied)");
         return GPIRT_E_ARG;
     }
     if (dst->kern.family != src->kern.family || dst->kern.length_scale != src->kern.length_scale) {

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void fstar_epilogue_kernel(FstarEpiArgs a, con
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N) return;
     const double mean = a.mean[i + j * a.N] + a.mu_star[i + j * a.N];       // :25
-    const double sd = a.s[i];
+    const double sd = a.amp ? a.amp[j] * a.s[i] : a.s[i];                   // (per-item amplitudes: amp.hip)
     double z;
     if (a.U) {
         const uint64_t q = *a.pos + 2ull * ((uint64_t)j * (uint64_t)off[a.N] + (uint64_t)off[i]);

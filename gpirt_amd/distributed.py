@@ -336,6 +336,19 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the length-scale update is not offered for item shards (its likelihood change runs "
                          "over all items, and each rank holds its own columns of f)")
 
+    # -- per-item GP amplitudes (gpirt_amd.amp): the library keeps them for all items of one sampler
+    def amp_set(self, a):
+        raise ValueError("ShardedSampler: per-item amplitudes are not offered for item shards (the library keeps them for all "
+                         "items of one sampler)")
+
+    def amp_enable(self, lo=0.1, hi=10.0, points=129, log_prior=None, width=4, k0=None, planned_draws=0, on=True):
+        raise ValueError("ShardedSampler: per-item amplitudes are not offered for item shards (the library keeps them for all "
+                         "items of one sampler)")
+
+    def draw_amp(self):
+        raise ValueError("ShardedSampler: per-item amplitudes are not offered for item shards (the library keeps them for all "
+                         "items of one sampler)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

@@ -246,7 +246,11 @@ def compare(y, kernels, sample_iterations, burn_iterations, chains=4, seed=1, *,
     next kernel is set), every run with the same seed, inits and PSIS-LOO on, no draws stored.  Returns the rows sorted by
     elpd_loo, best first: dict(index (the entry's position in `kernels`), kernel, kstar_rank, elpd_loo, se_elpd_loo, p_loo,
     elpd_diff and se_diff against the best row (gpirt_amd.loo.compare; 0 for the best), k_bad (cells whose Pareto k is above
-    the threshold: their elpd is not to be trusted), max_rhat (theta and beta) and n_obs)."""
+    the threshold: their elpd is not to be trusted), max_rhat (theta and beta) and n_obs).
+
+    A dict entry may also carry amplitude= (a scalar or m values): that candidate runs under fixed per-item GP amplitudes
+    (gpirt_amd.amp.run with fixed=amplitude, Sampler.amp_set) and its row gains `amplitude`."""
+    from . import amp as AM
     from . import loo as LO
     from .ops import Handle
     if loo is None or loo is False:
@@ -254,14 +258,22 @@ def compare(y, kernels, sample_iterations, burn_iterations, chains=4, seed=1, *,
     kernels = list(kernels)
     if not kernels:
         raise ValueError("kernel.compare: no kernels")
+    amps = [k.get("amplitude") if isinstance(k, dict) else None for k in kernels]
+    kernels = [{q: v for q, v in k.items() if q != "amplitude"} if isinstance(k, dict) else k for k in kernels]
     for k in kernels:
         spec(k)
+
+    def one(k, a):
+        kw = dict(chains=chains, seed=seed, kernel=as_dict(k), loo=loo, preset=preset, theta_init=theta_init, store_draws=False,
+                  handle=h, **sampler_kw)
+        if a is None:
+            return run(y, sample_iterations, burn_iterations, **kw)
+        return AM.run(y, sample_iterations, burn_iterations, fixed=a, **kw)
     own = handle is None
     h = Handle() if own else handle
     before = h.kernel()
     try:
-        runs = [run(y, sample_iterations, burn_iterations, chains=chains, seed=seed, kernel=as_dict(k), loo=loo, preset=preset,
-                    theta_init=theta_init, store_draws=False, handle=h, **sampler_kw) for k in kernels]
+        runs = [one(k, a) for k, a in zip(kernels, amps)]
     finally:
         if own:
             h.close()
@@ -277,4 +289,6 @@ def compare(y, kernels, sample_iterations, burn_iterations, chains=4, seed=1, *,
                          se_elpd_loo=r["loo"]["se_elpd_loo"], p_loo=r["loo"]["p_loo"], elpd_diff=d["elpd_diff"],
                          se_diff=d["se_diff"], k_bad=r["loo"]["k_bad"] + r["loo"]["k_very_bad"],
                          max_rhat=max_rhat(r["diagnostics"]), n_obs=d["n_obs"]))
+        if amps[i] is not None:
+            rows[-1]["amplitude"] = r["amp"]["amplitude"]
     return rows

@@ -1587,6 +1587,82 @@ class Sampler:
         out["centred"] = cen
         return out
 
+    # -- per-item GP amplitudes, fixed or sampled in the chain (include/gpirt_hip.h gpirt_sampler_amp_*, gpirt_amd.amp)
+    def amp_set(self, a):
+        """Fixed amplitudes: m values, each finite and in [0.01, 1000]; item j's prior is f_j ~ N(0, a_j^2 (K + 0.001 I)), so
+        draw_f's prior draw is a_j L z_j and draw_fstar's standard deviation a_j s.  None turns amplitudes off.  After init(); f
+        is not rescaled.  Refused with the reason: rng="reference", kernel_fp32, an item shard, and while amp_enable is on."""
+        if a is None:
+            check(self.lib.gpirt_sampler_amp_set(self._s, None))
+            return
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.m,)))
+        check(self.lib.gpirt_sampler_amp_set(self._s, _ptr(a)))
+
+    def amp_enable(self, lo=0.1, hi=10.0, points=129, log_prior=None, width=4, k0=None, planned_draws=0, on=True):
+        """Put every item's amplitude on the logarithmic grid a_k = lo (hi / lo)^(k / (points - 1)) with the prior mass log_prior
+        (`points` finite values; None: -(ln a_k)^2 / 2, a choice), every item's proposal width `width` (1 .. points - 1) and the
+        starting indices k0 (m values, or one for all; None: the grid point nearest 1).  planned_draws: how many amp_record()
+        calls the draw buffer holds.  After init().  Refused with the reason: rng="reference", kernel_fp32, an item shard, and
+        while amp_set is on.  on=False frees the state and turns amplitudes off."""
+        if not on:
+            check(self.lib.gpirt_sampler_amp_enable(self._s, 0.0, 0.0, 0, None, 0, None, 0, 0))
+            self._amp_points = 0
+            return
+        lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float64)
+        if lp is not None and lp.shape != (int(points),):
+            raise ValueError(f"amp_enable: log_prior must hold points = {int(points)} values")
+        kk = None if k0 is None else np.ascontiguousarray(np.broadcast_to(np.asarray(k0, dtype=np.int32), (self.m,)))
+        check(self.lib.gpirt_sampler_amp_enable(self._s, float(lo), float(hi), int(points), None if lp is None else _ptr(lp),
+                                                int(width), None if kk is None else kk.ctypes.data_as(C.POINTER(C.c_int)),
+                                                int(planned_draws), 1))
+        self._amp_points = int(points)
+
+    def draw_amp(self):
+        """One prior-whitened Metropolis update of every item's amplitude in one launch (gpirt_amd.amp.step_exact is its NumPy
+        statement): nothing is read back."""
+        self._call("gpirt_sampler_draw_amp")
+
+    def amp_width(self, w):
+        """The proposal widths from the next update on: m values (or one for all), each in 1 .. points - 1."""
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), (self.m,)))
+        check(self.lib.gpirt_sampler_amp_width(self._s, w.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def amp_record(self):
+        """Append the current indices to the draw buffer and add 1 to hist[k_j, j], on the device."""
+        self._call("gpirt_sampler_amp_record")
+
+    def amp_get(self, name: str) -> np.ndarray:
+        """One array by name: grid, log_prior (points), amplitude (m), index, width (int32, m), counts (int64, 4 x m: updates,
+        accepted, out_of_range, failed), record (5 x m of the last update: dll, log_ratio, log_u, status, nonfinite; status as
+        _lib.AMP_STATUS), hist (uint32, points x m), draws (int32, recorded x m), time (1: ms of device time of the last update
+        with enable_timing() on)."""
+        P, m = getattr(self, "_amp_points", 0), self.m
+        if name in ("index", "width"):
+            out = np.empty(m, dtype=np.int32)
+        elif name == "counts":
+            out = np.empty((4, m), dtype=np.int64)
+        elif name == "record":
+            out = np.empty((5, m))
+        elif name == "hist":
+            out = np.empty((P, m), dtype=np.uint32)
+        elif name == "draws":
+            out = np.empty((self.amp()["recorded"], m), dtype=np.int32)
+        else:
+            out = np.empty({"amplitude": m, "time": 1}.get(name, P))
+        self._get_into("gpirt_sampler_amp_get", name, out)
+        return out
+
+    def amp(self) -> dict:
+        """The amplitudes' state (gpirt_sampler_amp_stats): mode (None, "fixed" or "sampled"), points, m, calls, the counters
+        summed over the items (updates, accepted, out_of_range, failed), the pooled accept_rate, planned_draws, recorded, lo, hi,
+        min_amplitude and max_amplitude."""
+        a = _lib.Amp()
+        check(self.lib.gpirt_sampler_amp_stats(self._s, C.byref(a)))
+        out = {k: int(getattr(a, k)) for k in ("points", "m", "calls", "planned_draws", "recorded") + _lib.AMP_COUNTS}
+        out.update({k: float(getattr(a, k)) for k in ("accept_rate", "lo", "hi", "min_amplitude", "max_amplitude")})
+        out["mode"] = _lib.AMP_MODES[int(a.on)]
+        return out
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

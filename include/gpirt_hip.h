@@ -55,6 +55,7 @@ enum {
     GPIRT_ST_INIT_F = 1, GPIRT_ST_INIT_BETA = 2, GPIRT_ST_F_Z = 3, GPIRT_ST_F_ESS = 4,
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
+    GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
 
@@ -2154,6 +2155,84 @@ int gpirt_sampler_ell_stats(gpirt_sampler_t s, gpirt_ell* out);
 int gpirt_sampler_draw_ell_centred(gpirt_sampler_t s);
 int gpirt_sampler_ell_width_centred(gpirt_sampler_t s, int w);
 int gpirt_sampler_ell_centred_stats(gpirt_sampler_t s, gpirt_ell_centred* out);
+
+/* ------------------------------------------------------ per-item GP amplitudes: fixed or sampled in the chain ---------- */
+/* Library version 129.  Item j has an amplitude a_j > 0 and the prior f_j ~ N(0, a_j^2 (K(theta, theta) + 0.001 I)): the
+ * amplitude multiplies the WHOLE prior, jitter included, so item j's model is exactly a_j times the unit model.  The factor L is
+ * shared by all items as before and nothing is factored for an amplitude.  Where a_j enters, and nowhere else:
+ *   draw_f       the prior draw of the elliptical slice is nu_j = a_j (L z_j): the product as before, then one multiplication
+ *                per value;
+ *   draw_fstar   the conditional mean is unchanged (a_j cancels in k*^T S^-1 f), the standard deviation is a_j s_i with the
+ *                reference's s_i = 1 - sqrt(q_i) (quirk Q2) as before;
+ *   gpirt_sampler_draw_ell (whitened) runs unchanged: f' = L' L^-1 f does not contain a_j;
+ *   gpirt_sampler_draw_ell_centred returns GPIRT_E_ARG while amplitudes are on: its quadratic form would need 1 / a_j^2 per item.
+ * Stage API only: gpirt_options, gpirt_run, gpirt_mcmc* and gpirt_sampler_step keep their layout and behaviour.  A sampler on
+ * which neither gpirt_sampler_amp_set nor gpirt_sampler_amp_enable was called computes bit for bit what it did; multiplying by
+ * 1.0 is exact, so a sampler whose amplitudes are all 1.0 does too.
+ *
+ * gpirt_sampler_amp_set(s, a): m fixed amplitudes, each finite and in [GPIRT_AMP_MIN, GPIRT_AMP_MAX]; a = NULL turns amplitudes
+ * off.  After gpirt_sampler_init.  f is not rescaled: any f is a valid state under any amplitude.
+ *
+ * gpirt_sampler_amp_enable puts the amplitudes on the logarithmic grid of gpirt_ell_grid, a_k = lo (hi / lo)^(k / (P - 1)),
+ * 2 <= P <= GPIRT_AMP_MAX_POINTS, GPIRT_AMP_MIN <= lo < hi <= GPIRT_AMP_MAX, the end points exact, with a_j = a_{k0[j]}
+ * (k0 = NULL: the grid point nearest 1 in log a for every item).  log_prior: P finite values, a mass on the grid, i.e. a
+ * density with respect to log a; NULL: -(ln a_k)^2 / 2, a log-normal with median 1 and log-sd 1 -- a choice, not a measurement.
+ * Every item's proposal width starts at `width` (1 .. P - 1; gpirt_sampler_amp_width sets m widths).  It allocates per item the
+ * index, the width, four int64 counters and the last update's record, a P x m uint32 histogram and a planned_draws x m int32
+ * buffer of recorded indices, all zeroed; the call count t runs over the sampler's life.  on = 0 frees the state and turns
+ * amplitudes off.  gpirt_amp_check is the argument check alone and touches no device: the grid, a non-finite log_prior, width,
+ * k0 (m indices in 0 .. P - 1 or NULL); with opts: GPIRT_RNG_RSTREAM (R's stream has no such draw), kernel_fp32, an item shard
+ * (item0 != 0 or m_total != m).  gpirt_sampler_amp_enable after gpirt_sampler_amp_set without turning it off, and the
+ * converse, are refused.
+ *
+ * gpirt_sampler_draw_amp: one update of every item in ONE launch, with no host read.  It is a prior-whitened Metropolis step
+ * (Murray & Adams 2010, section 2.2) per item: nu_j = L^-1 f_j / a_j is held fixed, so a proposal moves f_j' = (a_k' / a_k) f_j
+ * and the likelihood decides.  theta, beta, mu and L are not touched.  For item j (one work-group of 256 threads):
+ *   t        the number of draw_amp calls on this sampler so far, counted from 1
+ *   u0, u1   item_uniform(seed, t, GPIRT_ST_AMP, item0 + j, 0) and (.., 1)
+ *   q = min(floor(u0 2w_j), 2w_j - 1), d = q - w_j for q < w_j, else q - w_j + 1; k' = k_j + d.  k' outside 0 .. P - 1: rejected
+ *   and counted in out_of_range[j], nothing else runs for the item.
+ *   c = grid[k'] / grid[k_j] (one fp64 division), f'_i = c f_ij (one fp64 multiplication)
+ *   dll_j = sum over observed rows of [t(y (f + mu)) - t(y (f' + mu))], t(a) = log(1 + exp(-a)) in the form of csrc/ll_fast.h,
+ *   formed cell by cell as a difference of terms; thread t takes rows t, t + 256, ... in ascending order, then a fixed tree:
+ *   deterministic.  Rows whose f' is not finite are counted, observed or not.
+ *   accepted iff log(u1) < dll_j + (log_prior[k'] - log_prior[k_j]).  A non-finite f' or dll_j: `failed`, never accepted, not
+ *   an error.
+ *   Accepted: f_ij <- c f_ij (the same expression), k_j <- k', a_j <- grid[k'].  Otherwise item j's column of f is
+ *   byte-identical to before; only its counters and record move.
+ * Items are independent: no grid-wide barrier, no atomic, one writer per value; two runs give a byte-identical state.
+ *
+ * gpirt_sampler_amp_record appends the current indices to the draw buffer (GPIRT_E_ARG once planned_draws are in) and adds 1 to
+ * hist[k_j, j], on the device with no host synchronisation.  gpirt_sampler_amp_get, by name: "grid", "log_prior" (P doubles),
+ * "amplitude" (m doubles; the one name a sampler with gpirt_sampler_amp_set knows), "index", "width" (m int32), "counts" (4 x m
+ * int64, row-major: updates, accepted, out_of_range, failed), "record" (5 x m doubles, row-major, of the last update: dll,
+ * log_ratio, log_u, status, nonfinite; status 0 rejected, 1 accepted, 2 out of range -- the three figures are NaN --, 3 failed),
+ * "hist" (P x m uint32, row-major), "draws" (recorded x m int32, row-major: bytes = 4 m times the records so far), "time" (1 double: milliseconds of device time of
+ * the last update's launch with gpirt_sampler_enable_timing on -- one synchronisation per update then --, else 0).
+ * gpirt_sampler_amp_stats: totals over the items and the pooled acceptance. */
+#define GPIRT_AMP_MAX_POINTS 1025
+#define GPIRT_AMP_MIN 0.01
+#define GPIRT_AMP_MAX 1000.0
+typedef struct gpirt_amp {
+    int64_t  on;                            /* 0 off, 1 fixed (gpirt_sampler_amp_set), 2 on the grid (gpirt_sampler_amp_enable) */
+    int64_t  points, m;                     /* P (0 when fixed), the items */
+    int64_t  calls;                         /* t: gpirt_sampler_draw_amp calls over the sampler's life */
+    int64_t  updates, accepted, out_of_range, failed;   /* summed over the items, since gpirt_sampler_amp_enable */
+    int64_t  planned_draws, recorded;
+    double   accept_rate;                   /* accepted / updates, NaN before the first update */
+    double   lo, hi, min_amplitude, max_amplitude;
+    int64_t  reserved[4];
+} gpirt_amp;
+int gpirt_amp_check(double lo, double hi, int P, const double* log_prior, int width, const int* k0, int64_t m,
+                    const gpirt_options* opts);
+int gpirt_sampler_amp_set(gpirt_sampler_t s, const double* a);
+int gpirt_sampler_amp_enable(gpirt_sampler_t s, double lo, double hi, int P, const double* log_prior, int width, const int* k0,
+                             int64_t planned_draws, int on);
+int gpirt_sampler_draw_amp(gpirt_sampler_t s);
+int gpirt_sampler_amp_width(gpirt_sampler_t s, const int* w);
+int gpirt_sampler_amp_record(gpirt_sampler_t s);
+int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out);
 
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
