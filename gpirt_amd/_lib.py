@@ -723,6 +723,7 @@ SIGNATURES = {
     "gpirt_sampler_ldl": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_nu_lr_draws": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_nu_lr_rows": (_i32, [_vp, _vp, _i64]),
+    "gpirt_sampler_fstar_free_draws": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_copy_state": (_i32, [_vp, _vp]),
     "gpirt_sampler_accumulate_irf": (_i32, [_vp]),
     "gpirt_sampler_iteration": (_i32, [_vp, C.POINTER(_i32)]),

@@ -82,6 +82,8 @@ struct Config {
     int  rs_lr = 1;               // GPIRT_RS_LR: 2 = the predictor's every pass reads all of L as floats (no structured form, rs_lr.hip)
     int  nu_lr = 1;               // GPIRT_NU_LR: draw_f's nu = L z from L's diagonal parts and the 64 node rows (nu_lr.hip): 1 = from n = 2048 on,
                                   //   2 = always the dense product, 3 = at every eligible n
+    int  fstar_free = 1;          // GPIRT_FSTAR_FREE: the rank-64 draw_fstar's C = S^-1 U from theta alone (fstar_free.hip): 1 = from n = 2048 on
+                                  //   where the sampler is eligible, 2 = always the solve through L, 3 = at every eligible n
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)
     int  guard_verbose = 0;       // GPIRT_GUARD_VERBOSE: 1 = a hang-guard fallback prints the guard record to stderr
 };

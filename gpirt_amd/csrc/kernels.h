@@ -248,6 +248,11 @@ void nu_lr_nodes(std::vector<double>& nodes, std::vector<double>& wts);
 int64_t nu_lr_slabs(int64_t n);
 int launch_nu_lr_basis(hipStream_t stream, const double* theta, int64_t n, const double* nodes, const double* wts, double* V);
 int launch_nu_lr(hipStream_t stream, const NuLrArgs& a, double* flops, double* bytes);
+// fstar_free.hip: the rank-64 draw_fstar's C = S^-1 K(theta, c) = V M from theta alone (V: launch_nu_lr_basis' n x 64)
+constexpr int FSTAR_FREE_RANK = NU_LR_RANK;
+void fstar_free_factor(const KernelSpec& kern, std::vector<double>& F);        // host: F (64 x 64) with K(c, c) = F F^T
+int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const double* F, double eps, double* work, double* parts,
+                      int nsplit, double* Cu, int* err);                        // work: 2 x 64 x 64, parts: nsplit x 64 x 64
 int launch_rs3p_products(hipStream_t stream, const Rs3Args& a);
 int launch_rs3p_decide(hipStream_t stream, const Rs3Args& a);
 int launch_rs_pred_start(hipStream_t stream, const uint64_t* anchor, uint64_t* anchorP, const int* k_last, int64_t m);

@@ -17,6 +17,7 @@
 
 #include <stdlib.h>
 #include <new>
+#include <mutex>
 #include <type_traits>
 #include <string>
 #include <vector>
@@ -129,6 +130,14 @@ struct gpirt_sampler_s {
     gpirt_handle_t haux = nullptr;
     hipEvent_t ev_trmm = nullptr, ev_prep = nullptr;
     bool prep_valid = false, prep_pending = false;
+    // C from theta alone (fstar_free.hip): C = V M with V = nuV and M from V^T V and F, K(c, c) = F F^T -- no solve through L.
+    // ffF: F on the device (64 x 64) for the kernel with length scale ff_ell (ff_have; rebuilt wherever the host replaces
+    // `kern`); ffW: V^T V and M; prep_free: the C in place (prep_valid) came from that chain, which READS nuV -- whoever
+    // rewrites nuV while it is pending joins it first; fstar_free_draws: draw_fstar calls that used such a C so far
+    double *ffF = nullptr, *ffW = nullptr;
+    bool ff_have = false, prep_free = false;
+    double ff_ell = 0.0;
+    int64_t fstar_free_draws = 0;
     // the N(0,1) draws of the NEXT draw_f depend on (seed, iteration, item, index) only: filled on the sampler's own stream
     // while the last outer panel is factored; z_filled_iter = the iteration they belong to (0: none), ev_zfill fires when done
     uint32_t z_filled_iter = 0;
@@ -448,6 +457,56 @@ bool nu_kernel_ok(const KernelSpec& kern)
 }
 
 int fstar_prep(gpirt_sampler_s* s, gpirt_handle_t hh);
+
+// F for the sampler's kernel on the device (fstar_free.hip): at creation and wherever the host replaces s->kern for good.  The
+// decomposition is a property of the kernel alone: the last one is kept per process.  Drains the handle's stream.
+int fstar_free_setup(gpirt_sampler_s* s)
+{
+    s->ff_have = false;
+    if (!s->ffF || s->kern.family != GPIRT_KERNEL_SE) return 0;
+    static std::mutex mu;
+    static double cached_ell = 0.0;
+    static std::vector<double> cached;
+    std::vector<double> F;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        if (cached.empty() || cached_ell != s->kern.length_scale) {
+            fstar_free_factor(s->kern, cached);
+            cached_ell = s->kern.length_scale;
+        }
+        F = cached;
+    }
+    GP_HIP(hipMemcpyAsync(s->ffF, F.data(), sizeof(double) * F.size(), hipMemcpyHostToDevice, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));                // (F leaves scope)
+    s->ff_have = true; s->ff_ell = s->kern.length_scale;
+    return 0;
+}
+
+// Does the rank-64 draw_fstar take C from theta alone?  What the structured nu = L z asks (the node rows carried, the kernel's
+// rank-64 certificate, K built in fp64, every theta inside the nodes' interval, L the factor of K(theta, theta) as far as
+// the sampler can know), and: kstar_rank = 64 in the bordered layout, the item-keyed RNG, F in place for the kernel as it
+// stands, no length-scale update (F for a moving kernel is not kept).  From n = 2048 on (GPIRT_FSTAR_FREE=3: at every n;
+// =2: never).  Otherwise the chain through L (fstar_prep).
+bool fstar_free_ok(const gpirt_sampler_s* s)
+{
+    const int mode = s->h->cfg.fstar_free;
+    return mode != 2 && (mode == 3 || s->n >= 2048) && s->kr == NU_LR_RANK && s->fstar_rows && s->node_off >= 0 && s->nuV &&
+           !stream_mode(s) && s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && !s->theta_alone && !s->ell.on &&
+           s->ffF && s->ff_have && s->kern.family == GPIRT_KERNEL_SE && s->ff_ell == s->kern.length_scale;
+}
+
+// ... and that chain on `st`: [the basis at theta,] V^T V, M in one work-group, C = V M into draw_fstar's Cu; G = B^T B from
+// the node rows as fstar_prep forms it (the same launches: the same bits)
+int fstar_prep_free(gpirt_sampler_s* s, hipStream_t st, bool basis)
+{
+    const int64_t n = s->n;
+    const int r = s->kr;
+    const double* Bt = s->L + n + s->rank_off;
+    if (basis) GP_TRY(launch_nu_lr_basis(st, s->theta, n, s->nu_nodes, s->nu_wts, s->nuV));
+    GP_TRY(launch_fstar_free(st, s->nuV, n, s->ffF, GPIRT_JITTER, s->ffW, s->kparts, KSPLIT, s->rhs + (size_t)n * r, s->flags));
+    return launch_gemm_splitk(st, false, true, r, r, n, 1.0, Bt, s->ldl, Bt, s->ldl, s->kparts, r, (int64_t)r * r, KSPLIT,
+                              s->kP, r, 0.0);
+}
 int report_degenerate_theta(gpirt_sampler_s* s, int count);
 int rebuild_rows(gpirt_sampler_s* s);
 int beta_sync(gpirt_sampler_s* s);
@@ -486,8 +545,15 @@ int do_draw_f(gpirt_sampler_s* s)
         // the 256-register form of that leaf (trsm.hip, slim_leaf) and the chain is done before the slice kernel is:
         // draw_fstar no longer waits 0.33 ms for it (7.12 -> 6.88 ms per iteration; the product slows by 0.1 ms).
         // GPIRT_PREP_EARLY=2 puts it back behind the product.
-        const bool early = prep && !(h->cfg.prep_early == 2 && m > 128);
-        if (early) GP_HIP(hipEventRecord(s->ev_trmm, st));
+        // With C from theta alone (fstar_free.hip) the side work does not wait for anything of the factor but the node rows
+        // (G): four small launches behind the basis at theta, no block inverses, no solve.
+        const bool free = prep && fstar_free_ok(s);
+        const bool early = prep && !free && !(h->cfg.prep_early == 2 && m > 128);
+        if (early || (free && !nu_lr)) GP_HIP(hipEventRecord(s->ev_trmm, st));
+        if (nu_lr && s->prep_pending && s->prep_free) {           // (a chain of an earlier draw may still be reading the basis)
+            GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0));
+            s->prep_pending = false;
+        }
         if (s->z_filled_iter == iter && s->ev_zfill) {
             GP_HIP(hipStreamWaitEvent(st, s->ev_zfill, 0));       // filled behind the previous factorisation (do_factor)
             s->z_filled_iter = 0;
@@ -505,6 +571,7 @@ int do_draw_f(gpirt_sampler_s* s)
                 q.L = s->L; q.ldl = s->ldl; q.Bt = s->L + n + s->node_off; q.V = s->nuV; q.Z = s->Z; q.NU = s->NU; q.T = s->nuT;
                 q.n = n; q.m = m;
                 GP_TRY(launch_nu_lr_basis(st, s->theta, n, s->nu_nodes, s->nu_wts, s->nuV));
+                if (free) GP_HIP(hipEventRecord(s->ev_trmm, st));       // (the side chain shares this basis)
                 GP_TRY(launch_nu_lr(st, q, &flops, &bytes));
                 GP_TRY(prof_pair_end(h, st, pp, 3, flops, bytes));
                 s->nu_lr_draws += 1;
@@ -514,7 +581,7 @@ int do_draw_f(gpirt_sampler_s* s)
             }
         }
         if (s->amp.mode) GP_TRY(launch_amp_scale(st, s->NU, s->amp.amp, n, m));       // nu_j = a_j (L z_j)
-        if (prep && !early) GP_HIP(hipEventRecord(s->ev_trmm, st));
+        if (prep && !early && !free) GP_HIP(hipEventRecord(s->ev_trmm, st));
         EssArgs a{};
         a.f = s->f; a.nu = s->NU; a.y = s->y; a.mu = s->mu; a.n = n; a.m = m; a.k_out = s->ess_k;
         a.err = s->flags; a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0;
@@ -525,12 +592,16 @@ int do_draw_f(gpirt_sampler_s* s)
             // what the low-rank draw_fstar needs from L alone, on the sampler's own stream (see `early` above)
             hipStream_t ax = s->haux->stream;
             GP_HIP(hipStreamWaitEvent(ax, s->ev_trmm, 0));
-            s->haux->slim_leaf = early;
-            const int rc_prep = fstar_prep(s, s->haux);
-            s->haux->slim_leaf = false;
-            GP_TRY(rc_prep);
+            if (free) {
+                GP_TRY(fstar_prep_free(s, ax, !nu_lr));
+            } else {
+                s->haux->slim_leaf = early;
+                const int rc_prep = fstar_prep(s, s->haux);
+                s->haux->slim_leaf = false;
+                GP_TRY(rc_prep);
+            }
             GP_HIP(hipEventRecord(s->ev_prep, ax));
-            s->prep_valid = true; s->prep_pending = true;
+            s->prep_valid = true; s->prep_pending = true; s->prep_free = free;
         }
         return 0;
     }
@@ -740,8 +811,15 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
         if (bordered) {
             // C = L^-T B and G = B^T B depend on the factor alone: usually already under way on the sampler's own
             // stream since draw_f's product finished (do_draw_f); otherwise computed here
-            if (!s->prep_valid) { GP_TRY(fstar_prep(s, h)); s->prep_valid = true; }   // (rows rebuilt above if they were stale)
+            if (!s->prep_valid) {                                 // (rows rebuilt above if they were stale)
+                if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
+                s->prep_free = fstar_free_ok(s);
+                if (s->prep_free) GP_TRY(fstar_prep_free(s, st, true));
+                else GP_TRY(fstar_prep(s, h));
+                s->prep_valid = true;
+            }
             else if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
+            if (s->prep_free) s->fstar_free_draws += 1;
         } else {
             GP_TRY(launch_se_kernel(st, s->kern, s->theta, n, s->knodes, r, Bu, n, 0.0));
             GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, Bu, r, n, false));
@@ -967,7 +1045,8 @@ int do_factor(gpirt_sampler_s* s)
     // panel but the last are built on the sampler's own stream while the last outer panel is factored (16 + 8 whole-CU
     // work-groups and small updates: most of the chip is idle then); only the last block and the solve are left behind.
     const bool early_inv = s->h->cfg.early_inv != 2;
-    if (early_inv && s->haux && s->kr > 0 && s->fstar_rows && !stream_mode(s) && s->h->prelast_cols >= 2048) {
+    // Not when the next draw_fstar takes C from theta alone (fstar_free.hip): nobody would read them.
+    if (early_inv && s->haux && s->kr > 0 && s->fstar_rows && !stream_mode(s) && s->h->prelast_cols >= 2048 && !fstar_free_ok(s)) {
         const int64_t p1 = (s->h->prelast_cols / 512) & ~(int64_t)1;
         hipStream_t ax = s->haux->stream;
         GP_HIP(hipStreamWaitEvent(ax, s->h->ev_prelast, 0));
@@ -1562,6 +1641,9 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     if (s->node_off >= 0) {
         GP_A(s->nu_nodes, NU_LR_RANK); GP_A(s->nu_wts, NU_LR_RANK);
         if (!stream_mode(s)) { GP_A(s->nuV, n * NU_LR_RANK); GP_A(s->nuT, nu_lr_slabs(n) * NU_LR_RANK * m); }
+        if (!stream_mode(s) && s->kr == NU_LR_RANK && s->fstar_rows) {
+            GP_A(s->ffF, FSTAR_FREE_RANK * FSTAR_FREE_RANK); GP_A(s->ffW, 2 * FSTAR_FREE_RANK * FSTAR_FREE_RANK);
+        }
     }
     if (s->kr != 0) {
         GP_A(s->knodes, s->kr); GP_A(s->kV, N * s->kr);
@@ -1714,6 +1796,7 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
         set_error("sampler upload failed"); gpirt_sampler_destroy(s); return GPIRT_E_HIP;
     }
+    if (fstar_free_setup(s) != 0) { gpirt_sampler_destroy(s); return GPIRT_E_HIP; }
     if (!stream_mode(s)) {
         if (!h->aux) {
             if (create_side_handle(&h->aux, h->device) != 0) { gpirt_sampler_destroy(s); return GPIRT_E_HIP; }
@@ -2638,7 +2721,7 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
         GP_HIP(hipStreamSynchronize(s->h->stream));
         ell_free(&e);
         s->nu_kern_ok = nu_kernel_ok(s->kern);
-        return 0;
+        return fstar_free_setup(s);          // (the kernel stays where the chain left it)
     }
     if (!s->initialised) { set_error("gpirt_sampler_ell_enable needs an initialised sampler (gpirt_sampler_init)"); return GPIRT_E_ARG; }
     gpirt_kernel kk;
@@ -3137,6 +3220,14 @@ int gpirt_sampler_nu_lr_draws(gpirt_sampler_t s, int64_t* draws)
 {
     GP_ARG(s && draws);
     *draws = s->nu_lr_draws;
+    return 0;
+}
+
+// draw_fstar calls of this sampler that took C = S^-1 U from theta alone (fstar_free.hip) so far
+int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws)
+{
+    GP_ARG(s && draws);
+    *draws = s->fstar_free_draws;
     return 0;
 }
 

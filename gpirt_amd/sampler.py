@@ -719,6 +719,13 @@ class Sampler:
         check(self.lib.gpirt_sampler_nu_lr_draws(self._s, C.byref(r)))
         return r.value
 
+    @property
+    def fstar_free_draws(self) -> int:
+        """draw_fstar calls that took C = S^-1 K(theta, c) from theta alone, without the solve through L (csrc/fstar_free.hip)"""
+        r = C.c_int64()
+        check(self.lib.gpirt_sampler_fstar_free_draws(self._s, C.byref(r)))
+        return r.value
+
     def nu_lr_rows(self) -> np.ndarray:
         """the 64 node rows below the factor as they stand, 64 x n"""
         out = np.empty((64, self.n), order="F")

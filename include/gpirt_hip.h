@@ -2492,6 +2492,20 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
 int gpirt_sampler_ldl(gpirt_sampler_t s, int64_t* ldl);
 int gpirt_sampler_nu_lr_draws(gpirt_sampler_t s, int64_t* draws);
 int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count);
+/* Library version 130.  The rank-64 draw_fstar (kstar_rank = 64, bordered layout) needs C = S^-1 U, U = K(theta, c_64).  With
+ * the same basis V and Kcc = K(c_64, c_64) = F F^T (F from a long-double Jacobi eigendecomposition on the host, once per
+ * kernel) S = (V F)(V F)^T + 0.001 I, so
+ *   C = V M,   M = F (F^T (V^T V) F + 0.001 I)^-1 F^T   (64 x 64)
+ * -- a 64 x 64 x n Gram product, one 64 x 64 factorisation and solve in a single work-group, an n x 64 x 64 product: nothing
+ * of L, where the transposed solve through L's block inverses could not start before the factorisation's last pivot block
+ * (csrc/fstar_free.hip).  G = B^T B stays the product over the node rows: s is unchanged bit for bit;
+ * mean and f* change to rounding (measured in DESIGN.md section 38, inside 1e-9 max(1, max|f*|) for a theta that is not
+ * degenerate; for a theta on one or two points the forward error of S x = f, 8 n u cond(S), is the bound).  It does not depend
+ * on m or item0.  It runs under the conditions of the structured nu = L z above and, besides: kstar_rank = 64 in the bordered
+ * layout, GPIRT_RNG_ITEM, no length-scale update (gpirt_sampler_ell_enable) in force.  Otherwise the chain through L, as
+ * before.  GPIRT_FSTAR_FREE (gpirt_config_set): 1 this rule, 2 always through L, 3 at every eligible n.
+ * gpirt_sampler_fstar_free_draws: how many draw_fstar calls of this sampler have used such a C. */
+int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws);
 /* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m.  The kernel
  * is not part of the state: refused (GPIRT_E_ARG) when the two samplers' kernels differ, or while the length-scale update
  * (gpirt_sampler_ell_enable) is on for either -- its index and tables are not copied. */
