@@ -473,7 +473,8 @@ class Options(C.Structure):
         ("reserved1", C.c_int),
         ("kernel_fp32", C.c_int),
         ("kstar_rank", C.c_int),
-        ("reserved", C.c_int * 5),
+        ("reserved", C.c_int * 4),
+        ("factor_structured", C.c_int),
     ]
 
 
@@ -724,6 +725,10 @@ SIGNATURES = {
     "gpirt_sampler_nu_lr_draws": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_nu_lr_rows": (_i32, [_vp, _vp, _i64]),
     "gpirt_sampler_fstar_free_draws": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_factor_lr_count": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_dense_factor_count": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_dense_factor": (_i32, [_vp]),
+    "gpirt_sampler_factor_lr_parts": (_i32, [_vp, _vp, _i64]),
     "gpirt_sampler_copy_state": (_i32, [_vp, _vp]),
     "gpirt_sampler_accumulate_irf": (_i32, [_vp]),
     "gpirt_sampler_iteration": (_i32, [_vp, C.POINTER(_i32)]),

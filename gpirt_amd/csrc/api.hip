@@ -39,6 +39,7 @@ const Config& env_config()
         d.rs_lr = env_value("GPIRT_RS_LR", d.rs_lr);
         d.nu_lr = env_value("GPIRT_NU_LR", d.nu_lr);
         d.fstar_free = env_value("GPIRT_FSTAR_FREE", d.fstar_free);
+        d.factor_lr = env_value("GPIRT_FACTOR_LR", d.factor_lr);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -164,7 +165,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 130; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 131; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -217,6 +218,9 @@ int gpirt_version(void) { return 130; }   // 101: gpirt_options names kernel_fp3
                                             //      gpirt_amp_check, gpirt_sampler_amp_*, gpirt_sampler_draw_amp); stage API only
                                             // 130: the rank-64 draw_fstar's C = S^-1 U from theta alone, without the solve through L
                                             //      (fstar_free.hip: GPIRT_FSTAR_FREE, gpirt_sampler_fstar_free_draws)
+                                            // 131: gpirt_options.factor_structured (gpirt_fast_options sets it): L's diagonal parts and node
+                                            //      rows alone, from theta (factor_lr.hip: GPIRT_FACTOR_LR, gpirt_sampler_factor_lr_count,
+                                            //      gpirt_sampler_dense_factor_count, gpirt_sampler_dense_factor, gpirt_sampler_factor_lr_parts)
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -348,6 +352,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_RS_LR", &h->cfg.rs_lr, false },
         { "GPIRT_NU_LR", &h->cfg.nu_lr, false },
         { "GPIRT_FSTAR_FREE", &h->cfg.fstar_free, false },
+        { "GPIRT_FACTOR_LR", &h->cfg.factor_lr, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }
@@ -1001,6 +1006,7 @@ void gpirt_fast_options(gpirt_options* o)
     o->theta_stabilise = 1;
     o->fstar_fused = 1;
     o->kstar_rank = 64;
+    o->factor_structured = 1;
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "potf2.h"
+#include "solve64.h"
 
 namespace gpirt {
 
@@ -162,6 +164,63 @@ __global__ __launch_bounds__(256) void fstar_free_small_kernel(const double* __r
         for (int ii = 0; ii < 4; ++ii) M[(4 * ti + ii) + FR * (4 * tj + jj)] = acc[ii][jj];
 }
 
+// Xh = R^-1 F^T with R R^T = F^T Gv F + eps I for `gridDim.x` matrices Gv 64 x 64 apart, one work-group each (factor_lr.hip:
+// a part's X-hat; the first half of the kernel above, which it leaves as it is).  The two products as above; A is then
+// factored in LDS by the factorisation's own 64 x 64 Cholesky (potf2.h) and each wavefront solves R x = f for 16 rows f of F
+// with its substitution core (solve64.h): x is column i of Xh for row i of F.
+// A pivot that is not positive raises *err (the sampler's numeric error word).
+constexpr size_t FX_LDS = sizeof(double) * (3 * FR * FLD + 2 * 4 * FR);
+static_assert(FR * S64_LS <= 2 * FR * FLD, "the staged factor takes the place of Gv and Gv F");
+__global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
+                                                              double* __restrict__ Xh, int* __restrict__ err)
+{
+    extern __shared__ __attribute__((aligned(16))) double ff_lds[];
+    __shared__ int sfail, sinfo;
+    double* Q = ff_lds;                      // F
+    double* P = ff_lds + FR * FLD;           // Gv
+    double* W = ff_lds + 2 * FR * FLD;       // Gv F
+    double* sM = P;                          // A, then R, with solve64.h's stride (over P and W, both dead by then)
+    double* sP = ff_lds + 3 * FR * FLD;      // potf2_64_body's two panels
+    const int t = threadIdx.x, ti = t & 15, tj = t >> 4;
+    const int lane = t & 63, wave = t >> 6, i = lane & 15, g = lane >> 4;
+    Gv += (int64_t)blockIdx.x * FR * FR;
+    Xh += (int64_t)blockIdx.x * FR * FR;
+    for (int e = t; e < FR * FR; e += 256) {
+        const int r = e & (FR - 1), c = e >> 6;
+        P[r + FLD * c] = Gv[e];
+        Q[r + FLD * c] = F[e];
+    }
+    if (t == 0) sinfo = 0;
+    __syncthreads();
+    double acc[4][4], a[4][4];
+    mm64<false, false>(P, Q, ti, tj, acc);                   // W = Gv F
+    put64(W, ti, tj, acc);
+    __syncthreads();
+    mm64<true, false>(Q, W, ti, tj, a);                      // A = F^T (Gv F) + eps I
+    __syncthreads();                                         // (every thread has read P and W: A goes over them)
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const int r = 4 * ti + ii, c = 4 * tj + jj;
+            sM[c * S64_LS + r] = r >= c ? a[ii][jj] + (r == c ? eps : 0.0) : 0.0;
+        }
+    d4 X[4];                                                 // this lane's row of F
+#pragma unroll
+    for (int J = 0; J < 4; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) X[J][r] = Q[(wave * 16 + i) + FLD * (16 * J + 4 * g + r)];
+    __syncthreads();
+    potf2_64_body(sM, S64_LS, FR, 0, &sinfo, sP, &sfail);
+    if (t == 0 && sfail != 0x7fffffff && err) atomicCAS(err, 0, (int)GPIRT_E_NUMERIC);
+    invert_diag16(sM);
+    solve64_lower_inv(X, sM);
+#pragma unroll
+    for (int J = 0; J < 4; ++J)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Xh[(16 * J + 4 * g + r) + FR * (wave * 16 + i)] = X[J][r];
+}
+
 }  // namespace
 
 // F (64 x 64, column-major) with K(c, c) = F F^T for the handle's kernel at the nodes of nu_lr_nodes: Kcc in long double, a
@@ -228,6 +287,17 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
     GP_HIP(hipGetLastError());
     // an un-split 64-tile product: an element of Cu depends on its row of V and on M alone
     return launch_gemm_batched(stream, false, false, TRI_NONE, n, FR, FR, 1.0, V, n, 0, M, FR, 0, 0.0, Cu, n, 0, 1);
+}
+
+// Xh[q] = R_q^-1 F^T with R_q R_q^T = F^T Gv[q] F + eps I for `batch` matrices Gv[q] (64 x 64 each, 4096 doubles apart), one
+// work-group per matrix
+int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err)
+{
+    if (batch <= 0) return 0;
+    GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fstar_free_xhat_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
+    hipLaunchKernelGGL(fstar_free_xhat_kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, err);
+    GP_HIP(hipGetLastError());
+    return 0;
 }
 
 }  // namespace gpirt

@@ -685,13 +685,15 @@ static int launch_gemm_t(hipStream_t stream, bool ta, bool tb, GemmParams p, int
     return 0;
 }
 
-// `batch` independent products of one shape (TRI_NONE / TRI_A_* only), operands `stride*` elements apart
+// `batch` independent products of one shape (TRI_NONE / TRI_A_*, or TRI_SYRK_LOWER with M >= N: the tiles on and below the
+// block diagonal, masked above the diagonal -- factor_lr.hip), operands `stride*` elements apart
 int launch_gemm_batched(hipStream_t stream, bool ta, bool tb, int tri, int64_t M, int64_t N, int64_t K, double alpha,
                         const double* A, int64_t lda, int64_t strideA, const double* B, int64_t ldb, int64_t strideB,
                         double beta, double* C, int64_t ldc, int64_t strideC, int batch)
 {
     if (M <= 0 || N <= 0 || batch <= 0) return 0;
-    if (tri == TRI_SYRK_LOWER || tri == TRI_SYRK_LOWER_TRAILING || tri == TRI_SYRK_LOWER_BACKGROUND) { set_error("batched gemm: no syrk mode"); return GPIRT_E_ARG; }
+    if (tri == TRI_SYRK_LOWER_TRAILING || tri == TRI_SYRK_LOWER_BACKGROUND) { set_error("batched gemm: no trailing-update mode"); return GPIRT_E_ARG; }
+    if (tri == TRI_SYRK_LOWER && M < N) { set_error("batched gemm: syrk mode needs M >= N"); return GPIRT_E_ARG; }
     GemmParams p;
     p.A = A; p.B = B; p.C = C;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc;

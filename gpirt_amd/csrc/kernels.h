@@ -253,6 +253,23 @@ constexpr int FSTAR_FREE_RANK = NU_LR_RANK;
 void fstar_free_factor(const KernelSpec& kern, std::vector<double>& F);        // host: F (64 x 64) with K(c, c) = F F^T
 int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const double* F, double eps, double* work, double* parts,
                       int nsplit, double* Cu, int* err);                        // work: 2 x 64 x 64, parts: nsplit x 64 x 64
+// Xh[q] = R_q^-1 F^T, R_q R_q^T = F^T Gv[q] F + eps I, for `batch` 64 x 64 matrices Gv[q] (one work-group each)
+int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err);
+// factor_lr.hip: L's diagonal parts and the 64 node rows from theta alone -- nothing below the parts is computed
+struct FactorLrArgs {
+    const double* theta; int64_t n;
+    const double *nodes, *wts;        // nu_lr_nodes on the device
+    double* V;                        // n x 64 (leading dimension n): rewritten with the basis at theta
+    const double* F; double eps;      // fstar_free_factor's F on the device; the jitter
+    double *G, *Xh;                   // factor_lr_parts(n) x 64 x 64 each: the Grams in front of the parts; R_P^-1 F^T
+    double* X;                        // 64 x n: the parts' borders
+    double* D;                        // factor_lr_parts(n) x 8 x 64 x 64: the pivot blocks' factors until the last round is through
+    double* L; int64_t ldl;           // the factor's buffer: the diagonal parts are written
+    double* Bt;                       // its node rows (64 x n, leading dimension ldl): written
+    int* err;                         // the sampler's numeric error word
+};
+int64_t factor_lr_parts(int64_t n);
+int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a);
 int launch_rs3p_products(hipStream_t stream, const Rs3Args& a);
 int launch_rs3p_decide(hipStream_t stream, const Rs3Args& a);
 int launch_rs_pred_start(hipStream_t stream, const uint64_t* anchor, uint64_t* anchorP, const int* k_last, int64_t m);

@@ -138,6 +138,15 @@ struct gpirt_sampler_s {
     bool ff_have = false, prep_free = false;
     double ff_ell = 0.0;
     int64_t fstar_free_draws = 0;
+    // The structured factor (factor_lr.hip; opt.factor_structured): where the sampler's next readers are draw_f's structured
+    // product and the rank-64 draw_fstar with C from theta alone, only L's diagonal parts and the node rows are built, from
+    // theta.  L_structured: that is what `L` holds -- the triangle below the parts is NOT the factor's; theta_L: the theta it
+    // belongs to (ensure_dense_factor builds the dense factor from it for whoever reads more of L); flrG / flrXh / flrX: the
+    // workspaces of launch_factor_lr; ev_flr: recorded where the structured factor starts (the side work waits for it)
+    double *theta_L = nullptr, *flrG = nullptr, *flrXh = nullptr, *flrX = nullptr, *flrD = nullptr;
+    bool L_structured = false;
+    hipEvent_t ev_flr = nullptr;
+    int64_t factor_lr_count = 0, dense_factor_count = 0;      // structured factors / dense factorisations this sampler enqueued
     // the N(0,1) draws of the NEXT draw_f depend on (seed, iteration, item, index) only: filled on the sampler's own stream
     // while the last outer panel is factored; z_filled_iter = the iteration they belong to (0: none), ev_zfill fires when done
     uint32_t z_filled_iter = 0;
@@ -487,12 +496,23 @@ int fstar_free_setup(gpirt_sampler_s* s)
 // the sampler can know), and: kstar_rank = 64 in the bordered layout, the item-keyed RNG, F in place for the kernel as it
 // stands, no length-scale update (F for a moving kernel is not kept).  From n = 2048 on (GPIRT_FSTAR_FREE=3: at every n;
 // =2: never).  Otherwise the chain through L (fstar_prep).
-bool fstar_free_ok(const gpirt_sampler_s* s)
+// (state_only: without "L is the factor of K(theta, theta)" -- what a factorisation about to run asks, factor_lr_ok)
+bool fstar_free_ok(const gpirt_sampler_s* s, bool state_only = false)
 {
     const int mode = s->h->cfg.fstar_free;
     return mode != 2 && (mode == 3 || s->n >= 2048) && s->kr == NU_LR_RANK && s->fstar_rows && s->node_off >= 0 && s->nuV &&
-           !stream_mode(s) && s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && !s->theta_alone && !s->ell.on &&
+           !stream_mode(s) && s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && (state_only || !s->theta_alone) && !s->ell.on &&
            s->ffF && s->ff_have && s->kern.family == GPIRT_KERNEL_SE && s->ff_ell == s->kern.length_scale;
+}
+
+// Does the factorisation build L's diagonal parts and node rows alone, from theta (factor_lr.hip)?  Only where nothing of the
+// steady iteration reads more: the option set, and what draw_f's structured product and the rank-64 draw_fstar with C from
+// theta alone ask, their own switches included.  From n = 2048 on (GPIRT_FACTOR_LR=3: at every eligible n; =2: never).
+bool factor_lr_ok(const gpirt_sampler_s* s)
+{
+    const Config& c = s->h->cfg;
+    return s->opt.factor_structured && s->theta_L && c.factor_lr != 2 && (c.factor_lr == 3 || s->n >= 2048) &&
+           c.nu_lr != 2 && (c.nu_lr == 3 || s->n >= 2048) && fstar_free_ok(s, true);
 }
 
 // ... and that chain on `st`: [the basis at theta,] V^T V, M in one work-group, C = V M into draw_fstar's Cu; G = B^T B from
@@ -510,6 +530,7 @@ int fstar_prep_free(gpirt_sampler_s* s, hipStream_t st, bool basis)
 int report_degenerate_theta(gpirt_sampler_s* s, int count);
 int rebuild_rows(gpirt_sampler_s* s);
 int beta_sync(gpirt_sampler_s* s);
+int ensure_dense_factor(gpirt_sampler_s* s);
 
 // Z may still be being filled on the sampler's own stream (do_factor's prefill of the NEXT draw_f's normals): whoever reads or
 // rewrites Z, or changes the iteration the prefill was keyed by, joins it first and drops it
@@ -535,6 +556,7 @@ int do_draw_f(gpirt_sampler_s* s)
         // can know; from n = 2048 on (GPIRT_NU_LR=3: at every n; =2: never).  Otherwise the dense product, as before.
         const bool nu_lr = s->node_off >= 0 && s->nuV && h->cfg.nu_lr != 2 && (h->cfg.nu_lr == 3 || n >= 2048) &&
                            s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && !s->theta_alone;
+        if (!nu_lr) GP_TRY(ensure_dense_factor(s));               // (the dense product reads all of L)
         if (nu_lr) GP_TRY(rebuild_rows(s));
         const bool prep = s->haux && s->kr > 0 && s->fstar_rows && s->rows_valid && !s->prep_valid;
         // The side work (what the low-rank draw_fstar needs from L alone: the last range of block inverses and the
@@ -548,6 +570,7 @@ int do_draw_f(gpirt_sampler_s* s)
         // With C from theta alone (fstar_free.hip) the side work does not wait for anything of the factor but the node rows
         // (G): four small launches behind the basis at theta, no block inverses, no solve.
         const bool free = prep && fstar_free_ok(s);
+        if (prep && !free) GP_TRY(ensure_dense_factor(s));        // (fstar_prep solves through L)
         const bool early = prep && !free && !(h->cfg.prep_early == 2 && m > 128);
         if (early || (free && !nu_lr)) GP_HIP(hipEventRecord(s->ev_trmm, st));
         if (nu_lr && s->prep_pending && s->prep_free) {           // (a chain of an earlier draw may still be reading the basis)
@@ -815,7 +838,7 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
                 if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
                 s->prep_free = fstar_free_ok(s);
                 if (s->prep_free) GP_TRY(fstar_prep_free(s, st, true));
-                else GP_TRY(fstar_prep(s, h));
+                else { GP_TRY(ensure_dense_factor(s)); GP_TRY(fstar_prep(s, h)); }
                 s->prep_valid = true;
             }
             else if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
@@ -989,15 +1012,18 @@ int aux_join(gpirt_sampler_s* s, bool beta_too = true, bool z_too = true)
 }
 
 // S = K(theta, theta) + jitter into the lower blocks of L; with the bordered layout also K(c, theta) into the rows below
-int build_cov(gpirt_sampler_s* s)
+// (theta: the sampler's, or the saved theta a structured factor belongs to -- ensure_dense_factor)
+int build_cov(gpirt_sampler_s* s, const double* theta = nullptr)
 {
     hipStream_t st = s->h->stream;
-    GP_TRY(launch_se_kernel_lower(st, s->kern, s->theta, s->n, s->L, s->ldl, GPIRT_JITTER, s->opt.kernel_fp32 != 0));
-    if (s->fstar_rows && s->kr > 0) GP_TRY(launch_se_kernel(st, s->kern, s->knodes, s->kr, s->theta, s->n, s->L + s->n + s->rank_off, s->ldl, 0.0));
-    if (s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->tstar, s->N, s->theta, s->n, s->L + s->n, s->ldl, 0.0));
+    if (!theta) theta = s->theta;
+    s->L_structured = false;              // (whatever L held is being overwritten)
+    GP_TRY(launch_se_kernel_lower(st, s->kern, theta, s->n, s->L, s->ldl, GPIRT_JITTER, s->opt.kernel_fp32 != 0));
+    if (s->fstar_rows && s->kr > 0) GP_TRY(launch_se_kernel(st, s->kern, s->knodes, s->kr, theta, s->n, s->L + s->n + s->rank_off, s->ldl, 0.0));
+    if (s->ext_grid) GP_TRY(launch_se_kernel(st, s->kern, s->tstar, s->N, theta, s->n, s->L + s->n, s->ldl, 0.0));
     // the node rows of draw_f's structured product (nu_lr.hip); with kr == 64 they are the rows just written
     if (s->node_off >= 0 && !(s->fstar_rows && s->kr == NU_LR_RANK))
-        GP_TRY(launch_se_kernel(st, s->kern, s->nu_nodes, NU_LR_RANK, s->theta, s->n, s->L + s->n + s->node_off, s->ldl, 0.0));
+        GP_TRY(launch_se_kernel(st, s->kern, s->nu_nodes, NU_LR_RANK, theta, s->n, s->L + s->n + s->node_off, s->ldl, 0.0));
     return 0;
 }
 
@@ -1005,6 +1031,7 @@ int build_cov(gpirt_sampler_s* s)
 int rebuild_rows(gpirt_sampler_s* s)
 {
     if (s->ext == 0 || s->rows_valid) return 0;
+    GP_TRY(ensure_dense_factor(s));       // (the solves below go through all of L)
     hipStream_t st = s->h->stream;
     const int64_t n = s->n, cols = s->ext_grid ? s->N : (s->fstar_rows ? s->kr : 0);
     double* Bu = s->rhs;
@@ -1025,13 +1052,46 @@ int rebuild_rows(gpirt_sampler_s* s)
 
 // S under the sampler's kernel, built and factored in place on the main stream -- do_factor without its side work (the early
 // block inverses, the Z prefill, a held-back draw_beta).  Whoever calls it has made sure nothing still reads the old factor.
+// With factor_lr_ok (not for gpirt_sampler_init, whose f = L z is the dense product): the diagonal parts and the node rows
+// alone, from theta (factor_lr.hip) -- theta is kept in theta_L for whoever asks for the rest of L later.
 int factor_core(gpirt_sampler_s* s)
 {
+    hipStream_t st = s->h->stream;
     invalidate_factor_products(s);
+    if (!s->in_init && factor_lr_ok(s)) {
+        if (s->ev_flr) GP_HIP(hipEventRecord(s->ev_flr, st));          // (the side work of do_factor starts here)
+        if (!s->sticky_info) GP_HIP(hipMemsetAsync(s->h->d_info, 0, sizeof(int), st));
+        GP_HIP(hipMemcpyAsync(s->theta_L, s->theta, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, st));
+        FactorLrArgs a{};
+        a.theta = s->theta; a.n = s->n; a.nodes = s->nu_nodes; a.wts = s->nu_wts; a.V = s->nuV; a.F = s->ffF; a.eps = GPIRT_JITTER;
+        a.G = s->flrG; a.Xh = s->flrXh; a.X = s->flrX; a.D = s->flrD; a.L = s->L; a.ldl = s->ldl; a.Bt = s->L + s->n + s->node_off; a.err = s->flags;
+        GP_TRY(launch_factor_lr(s->h, st, a));
+        s->L_structured = true;
+        s->rows_valid = true;
+        s->theta_alone = false;
+        s->factor_lr_count += 1;
+        return 0;
+    }
     GP_TRY(build_cov(s));                                                                                  // :76-77
     s->rows_valid = true;
     s->theta_alone = false;
-    return launch_potrf_lower(s->h, s->h->stream, s->L, s->n, s->ldl, false, !s->sticky_info, s->ext);     // :78
+    s->dense_factor_count += 1;
+    return launch_potrf_lower(s->h, st, s->L, s->n, s->ldl, false, !s->sticky_info, s->ext);               // :78
+}
+
+// Whoever reads more of L than its diagonal parts and node rows calls this first: a structured factor (factor_lr.hip) is
+// replaced by the dense factorisation of K(theta_L, theta_L) -- the existing build and factorisation, on the main stream --
+// and everything derived from the factor is dropped.  The rows below L then belong to theta_L as before: rows_valid stands.
+int ensure_dense_factor(gpirt_sampler_s* s)
+{
+    if (!s->L_structured) return 0;
+    hipStream_t st = s->h->stream;
+    if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }      // (G = B^T B may still read the rows)
+    invalidate_factor_products(s);
+    GP_TRY(build_cov(s, s->theta_L));
+    s->dense_factor_count += 1;
+    s->factor_fresh = false;              // (a hang-guard expiry here is reported, not repaired: theta may have moved on)
+    return launch_potrf_lower(s->h, st, s->L, s->n, s->ldl, false, false, s->ext);
 }
 
 int do_factor(gpirt_sampler_s* s)
@@ -1045,8 +1105,14 @@ int do_factor(gpirt_sampler_s* s)
     // panel but the last are built on the sampler's own stream while the last outer panel is factored (16 + 8 whole-CU
     // work-groups and small updates: most of the chip is idle then); only the last block and the solve are left behind.
     const bool early_inv = s->h->cfg.early_inv != 2;
+    // Behind a structured factor (factor_lr.hip) there is no last outer panel: its batched 64-column rounds leave most of the
+    // chip idle from the start, so the Z prefill and the held-back draw_beta wait for the event recorded where it began
+    // (prelast_cols says nothing about it), and no block inverses are built (nobody reads them).
+    const bool lr = s->L_structured && s->ev_flr;
+    hipEvent_t ev_side = lr ? s->ev_flr : s->h->ev_prelast;
+    const bool side_phase = lr || s->h->prelast_cols >= 2048;
     // Not when the next draw_fstar takes C from theta alone (fstar_free.hip): nobody would read them.
-    if (early_inv && s->haux && s->kr > 0 && s->fstar_rows && !stream_mode(s) && s->h->prelast_cols >= 2048 && !fstar_free_ok(s)) {
+    if (early_inv && !s->L_structured && s->haux && s->kr > 0 && s->fstar_rows && !stream_mode(s) && s->h->prelast_cols >= 2048 && !fstar_free_ok(s)) {
         const int64_t p1 = (s->h->prelast_cols / 512) & ~(int64_t)1;
         hipStream_t ax = s->haux->stream;
         GP_HIP(hipStreamWaitEvent(ax, s->h->ev_prelast, 0));
@@ -1055,13 +1121,13 @@ int do_factor(gpirt_sampler_s* s)
         GP_TRY(trsm_inverses_build(s->haux, ax, s->L, s->n, s->ldl, true, 0, p1));
         s->haux->inv_partial_L = s->L; s->haux->inv_partial_pairs = p1;
     }
-    if (early_inv && s->initialised && !s->in_init && s->haux && s->ev_zfill && !stream_mode(s) && s->h->prelast_cols >= 2048) {
+    if (early_inv && s->initialised && !s->in_init && s->haux && s->ev_zfill && !stream_mode(s) && side_phase) {
         // (not from gpirt_sampler_init, first or repeated: it fills Z itself for the initial f right behind its factorisation)
         // ... and the next draw_f's N(0,1) draws (the factorisation closes iteration s->iter + 1; the next draw_f is
         // iteration s->iter + 2).  Z was last read by this iteration's nu = L z, long finished on the main stream.
         hipStream_t ax = s->haux->stream;
         const uint32_t next_iter = (uint32_t)(s->iter + 2);
-        GP_HIP(hipStreamWaitEvent(ax, s->h->ev_prelast, 0));
+        GP_HIP(hipStreamWaitEvent(ax, ev_side, 0));
         GP_TRY(launch_item_uniforms(ax, s->opt.seed, next_iter, GPIRT_ST_F_Z, (uint32_t)s->opt.item0, s->m, s->n, s->Z, true));
         GP_HIP(hipEventRecord(s->ev_zfill, ax));
         s->z_filled_iter = next_iter;
@@ -1070,9 +1136,9 @@ int do_factor(gpirt_sampler_s* s)
         // draw_beta of THIS iteration (do_draw_beta held it back): beside the last outer panel on the sampler's stream
         // when there is such a phase, otherwise right here on the main stream
         s->beta_deferred = false;
-        if (s->haux && s->h->prelast_cols >= 2048) {
+        if (s->haux && side_phase) {
             hipStream_t ax = s->haux->stream;
-            GP_HIP(hipStreamWaitEvent(ax, s->h->ev_prelast, 0));       // (causally behind theta and f on the main stream)
+            GP_HIP(hipStreamWaitEvent(ax, ev_side, 0));                // (causally behind theta and f on the main stream)
             GP_TRY(launch_beta_on(s, ax));
             GP_HIP(hipEventRecord(s->ev_beta, ax));
             s->beta_pending = true;
@@ -1080,7 +1146,8 @@ int do_factor(gpirt_sampler_s* s)
             GP_TRY(launch_beta_on(s, st));
         }
     }
-    s->factor_fresh = true;               // nothing has read this L yet: a hang-guard expiry in it can still be repaired in place
+    // nothing has read this L yet: a hang-guard expiry in it can still be repaired in place (a structured factor has no guard)
+    s->factor_fresh = !s->L_structured;
     return 0;
 }
 
@@ -1101,6 +1168,7 @@ int recover_factor(gpirt_sampler_s* s)
     h->cfg.panel = 2;
     int rc = build_cov(s);
     if (!rc) rc = launch_potrf_lower(h, st, s->L, s->n, s->ldl, false, true, s->ext);
+    s->dense_factor_count += 1;
     h->cfg.panel = saved;
     GP_TRY(rc);
     s->rows_valid = true;
@@ -1213,6 +1281,7 @@ int do_draw_ell(gpirt_sampler_s* s, int kind)
     const int kp = e.k + (j < w ? j - w : j - w + 1);
     if (kp < 0 || kp >= e.P) { counted(); c.last_proposed = kp; c.out_of_range += 1; c.last = 2; return 0; }      // (the proposal is symmetric: nothing else runs)
     GP_TRY(ell_join(s));
+    GP_TRY(ensure_dense_factor(s));       // (the update saves, solves through and multiplies by all of L)
     s->factor_fresh = false;
     const bool timed = s->timing;
     if (timed)
@@ -1612,6 +1681,11 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         gpirt_sampler_destroy(s);
         return GPIRT_E_ARG;
     }
+    if (s->opt.factor_structured != 0 && s->opt.factor_structured != 1) {
+        set_error("factor_structured must be 0 or 1");
+        gpirt_sampler_destroy(s);
+        return GPIRT_E_ARG;
+    }
     const bool bordered_ok = (n % 64) == 0 && h->cfg.bordered != 2;
     if (bordered_ok) {
         // (the node rows of nu_lr.hip in every bordered layout: see node_off)
@@ -1643,6 +1717,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         if (!stream_mode(s)) { GP_A(s->nuV, n * NU_LR_RANK); GP_A(s->nuT, nu_lr_slabs(n) * NU_LR_RANK * m); }
         if (!stream_mode(s) && s->kr == NU_LR_RANK && s->fstar_rows) {
             GP_A(s->ffF, FSTAR_FREE_RANK * FSTAR_FREE_RANK); GP_A(s->ffW, 2 * FSTAR_FREE_RANK * FSTAR_FREE_RANK);
+            if (s->opt.factor_structured) {       // (the structured factor's: only where the rank-64 chain from theta can run)
+                const int64_t fp = factor_lr_parts(n) * NU_LR_RANK * NU_LR_RANK;
+                GP_A(s->theta_L, n); GP_A(s->flrG, fp); GP_A(s->flrXh, fp); GP_A(s->flrX, NU_LR_RANK * n); GP_A(s->flrD, fp * (NU_LR_PART / 64));
+            }
         }
     }
     if (s->kr != 0) {
@@ -1808,6 +1886,7 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
             hipEventCreateWithFlags(&s->ev_trmm, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s->ev_prep, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s->ev_zfill, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&s->ev_flr, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&s->ev_beta, hipEventDisableTiming) != hipSuccess) {
             gpirt_sampler_destroy(s);
             return GPIRT_E_HIP;
@@ -1845,6 +1924,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     if (s->ev_trmm) hipEventDestroy(s->ev_trmm);
     if (s->ev_prep) hipEventDestroy(s->ev_prep);
     if (s->ev_zfill) hipEventDestroy(s->ev_zfill);
+    if (s->ev_flr) hipEventDestroy(s->ev_flr);
     if (s->ev_beta) hipEventDestroy(s->ev_beta);
     for (void* p : s->allocs) hipFree(p);
     summary_free(&s->sum);
@@ -2047,6 +2127,7 @@ int gpirt_sampler_adopt_factor(gpirt_sampler_t s, int rows_with_L)
     GP_ARG(s && s->initialised);
     GP_TRY(beta_sync(s));                // a held-back draw_beta belongs to the iteration that closes here
     invalidate_factor_products(s);
+    s->L_structured = false;             // (L was overwritten from outside)
     s->factor_fresh = false;             // (nothing here could rebuild a factor that arrived from elsewhere)
     s->rows_valid = rows_with_L != 0;
     s->theta_alone = false;
@@ -2728,6 +2809,7 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
     gpirt_kernel_default(&kk);
     kk.family = s->kern.family; kk.length_scale = s->kern.length_scale;
     GP_TRY(gpirt_ell_check(lo, hi, P, log_prior, width, k0, &kk, &s->opt, s->m));
+    GP_TRY(ensure_dense_factor(s));       // (the updates read all of L; from here on every factor is dense)
     GP_HIP(hipStreamSynchronize(s->h->stream));
     ell_free(&e);
     const int64_t n = s->n, m = s->m;
@@ -3177,7 +3259,12 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
 {
     GP_ARG(s && name && d_ptr && count);
     GP_TRY(lookup(s, name, d_ptr, count));
-    if (strcmp(name, "L") == 0) *count = s->ldl * s->n;     // the whole buffer (leading dimension gpirt_sampler_ldl)
+    if (strcmp(name, "L") == 0) {
+        *count = s->ldl * s->n;           // the whole buffer (leading dimension gpirt_sampler_ldl)
+        // the caller may read or overwrite any of it: the dense factor now, and a structured factor that follows is not seen
+        // through this pointer until gpirt_sampler_dense_factor (or another call that needs all of L) has run
+        GP_TRY(ensure_dense_factor(s));
+    }
     return 0;
 }
 
@@ -3192,18 +3279,21 @@ int gpirt_sampler_ldl(gpirt_sampler_t s, int64_t* ldl)
 int gpirt_sampler_panel_factor(gpirt_sampler_t s, int64_t p)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_factor(s->h, s->h->stream, s->L, s->n, s->ldl, p, s->ext);
 }
 
 int gpirt_sampler_panel_update(gpirt_sampler_t s, int64_t p, int64_t c)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_update(s->h, s->h->stream, s->L, s->n, s->ldl, p, c, s->ext);
 }
 
 int gpirt_sampler_panel_copy(gpirt_sampler_t s, int64_t p, double* d_buf, int to_buf)
 {
     GP_ARG(s && s->initialised && d_buf);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_copy(s->h->stream, s->L, s->n, s->ldl, p, d_buf, to_buf != 0, s->ext);
 }
 
@@ -3231,6 +3321,43 @@ int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws)
     return 0;
 }
 
+// the structured factor (factor_lr.hip): how many factorisations of this sampler built the diagonal parts and node rows alone,
+// how many dense factorisations it enqueued (those of ensure_dense_factor included), the dense factor on demand, and the
+// diagonal parts as they stand (no dense factor is formed for them)
+int gpirt_sampler_factor_lr_count(gpirt_sampler_t s, int64_t* count)
+{
+    GP_ARG(s && count);
+    *count = s->factor_lr_count;
+    return 0;
+}
+
+int gpirt_sampler_dense_factor_count(gpirt_sampler_t s, int64_t* count)
+{
+    GP_ARG(s && count);
+    *count = s->dense_factor_count;
+    return 0;
+}
+
+int gpirt_sampler_dense_factor(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    return ensure_dense_factor(s);
+}
+
+int gpirt_sampler_factor_lr_parts(gpirt_sampler_t s, double* h_out, int64_t count)
+{
+    GP_ARG(s && h_out && count == (int64_t)NU_LR_PART * s->n);
+    GP_TRY(aux_join(s));
+    memset(h_out, 0, sizeof(double) * (size_t)count);
+    for (int64_t p = 0; p < s->n; p += NU_LR_PART) {
+        const int64_t w = s->n - p < NU_LR_PART ? s->n - p : NU_LR_PART;
+        GP_HIP(hipMemcpy2DAsync(h_out + p * NU_LR_PART, (size_t)NU_LR_PART * 8, s->L + p * (s->ldl + 1), (size_t)s->ldl * 8, (size_t)w * 8, (size_t)w,
+                                hipMemcpyDeviceToHost, s->h->stream));
+    }
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
 int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count)
 {
     GP_ARG(s && h_out && s->node_off >= 0 && count == (int64_t)NU_LR_RANK * s->n);
@@ -3245,18 +3372,21 @@ int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count)
 int gpirt_sampler_panel_factor_part(gpirt_sampler_t s, int64_t p, int half)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_factor(s->h, s->h->stream, s->L, s->n, s->ldl, p, s->ext, half);
 }
 
 int gpirt_sampler_panel_update_part(gpirt_sampler_t s, int64_t p, int64_t c, int part)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_update(s->h, s->h->stream, s->L, s->n, s->ldl, p, c, s->ext, part);
 }
 
 int gpirt_sampler_panel_copy_part(gpirt_sampler_t s, int64_t p, int half, double* d_buf, int64_t buf_doubles, int to_buf)
 {
     GP_ARG(s && s->initialised && d_buf && buf_doubles >= 0);
+    GP_TRY(ensure_dense_factor(s));       // (the pieces work on, and hand out, the dense factor)
     return potrf_panel_copy(s->h->stream, s->L, s->n, s->ldl, p, d_buf, to_buf != 0, s->ext, half, buf_doubles);
 }
 
@@ -3281,6 +3411,8 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     hipStream_t st = dst->h->stream;
     const int64_t n = dst->n, m = dst->m, N = dst->N;
     GP_TRY(aux_join(dst)); GP_TRY(aux_join(src));
+    GP_TRY(ensure_dense_factor(src));     // (dst gets the whole factor)
+    dst->L_structured = false;
     src->factor_fresh = false;
     invalidate_factor_products(dst);
     GP_HIP(hipMemcpyAsync(dst->theta, src->theta, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
@@ -3306,6 +3438,7 @@ int gpirt_sampler_get(gpirt_sampler_t s, const char* name, double* h_out, int64_
     GP_ARG(count <= c);
     const size_t esz = strcmp(name, "ess_k") == 0 ? sizeof(int) : sizeof(double);
     GP_TRY(aux_join(s));
+    if (strcmp(name, "L") == 0) GP_TRY(ensure_dense_factor(s));
     if (strcmp(name, "L") == 0 && s->ldl != s->n) {       // n x n out of the (n + ext) x n buffer
         GP_ARG(count == s->n * s->n);
         GP_HIP(hipMemcpy2DAsync(h_out, (size_t)s->n * 8, p, (size_t)s->ldl * 8, (size_t)s->n * 8, (size_t)s->n,
@@ -3327,6 +3460,11 @@ int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, i
     invalidate_factor_products(s);
     if (strcmp(name, "L") == 0 || strcmp(name, "theta") == 0) s->rows_valid = false;
     if (strcmp(name, "L") == 0) s->theta_alone = false;          // (taken as the factor of K(theta, theta) for the theta in place)
+    if (strcmp(name, "L") == 0) {
+        // (a partial write lands in the dense factor; a whole one replaces whatever L held)
+        if (count < c) GP_TRY(ensure_dense_factor(s));
+        s->L_structured = false;
+    }
     if (strcmp(name, "theta") == 0) {
         s->theta_alone = true;
         s->theta_ok = count == s->n;

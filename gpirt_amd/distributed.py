@@ -204,6 +204,8 @@ class ShardedSampler:
         else:
             if self.rank == 0:
                 self.engine.factor()
+                if hasattr(self.engine, "dense_factor"):
+                    self.engine.dense_factor()      # (the "L" view is a kept pointer: a structured factor is made dense before it travels)
             else:
                 self.engine.adopt_factor(True)      # the "L" view is the WHOLE ldl x n buffer: the bordered rows travel too
             self.dist.broadcast(self._view("L"), src=0)

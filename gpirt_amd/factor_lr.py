@@ -1,0 +1,65 @@
+"""The fast preset's structured factor (csrc/factor_lr.hip): the NumPy statement.
+
+What a steady iteration of the fast preset reads of the factor L of S = K(theta, theta) + eps I is only its 512-column
+diagonal parts L[P, P] (draw_f's structured nu = L z, gpirt_amd/csrc/nu_lr.hip) and the 64 node rows Bt = K(c, theta) L^-T
+below it (nu_lr's records and draw_fstar's G = B^T B).  Both follow from theta alone by the rank-64 form
+K(theta, theta) = V Kcc V^T, Kcc = F F^T (fstar_free.py): for the part P = [p, p + w) with G_P = V[<p]^T V[<p] the Gram of
+the basis rows in front of it (G_0 = 0)
+
+    H_P  = F^T G_P F,   A_P = H_P + eps I = R_P R_P^T,   Xh_P = R_P^-1 F^T        (64 x 64)
+    X_P  = Xh_P V[P]^T                                                             (64 x w)
+    S_PP = eps (I + X_P^T X_P)       the Schur complement of S in front of P, formed without a subtraction
+    L_PP = chol(S_PP)                every pivot >= sqrt(eps)
+    Bt[:, P] = eps Xh_P^T (X_P L_PP^-T)
+
+(Woodbury on the leading block: Kcc - sum_{Q < P} Bt_Q Bt_Q^T = eps F (H_P + eps I)^-1 F^T.)  The parts depend on each other
+through the running Gram alone.  The triangle of L below the parts is never formed.
+"""
+from __future__ import annotations
+
+import numpy as np
+from scipy.linalg import solve_triangular
+
+from .fstar_free import JITTER, RANK, basis, kernel_factor
+
+PART = 512
+
+
+def structured_factor(theta, family="se", length_scale=1.0, eps: float = JITTER, part: int = PART, F=None):
+    """(parts, Bt, V): the lower-triangular diagonal parts L[P, P] in part order, the node rows (64 x n) and the basis at theta"""
+    V = basis(theta)
+    n = V.shape[0]
+    if F is None:
+        F = kernel_factor(family, length_scale)
+    I = np.eye(RANK)
+    G = np.zeros((RANK, RANK))
+    parts, Bt = [], np.empty((RANK, n))
+    for p in range(0, n, part):
+        Vp = V[p:p + part]
+        A = F.T @ (G @ F) + eps * I
+        R = np.linalg.cholesky(np.tril(A) + np.tril(A, -1).T)
+        Xh = solve_triangular(R, F.T, lower=True)
+        X = Xh @ Vp.T
+        Lpp = np.linalg.cholesky(eps * (np.eye(Vp.shape[0]) + X.T @ X))
+        Y = solve_triangular(Lpp, X.T, lower=True).T                 # X L_PP^-T
+        parts.append(Lpp)
+        Bt[:, p:p + part] = eps * (Xh.T @ Y)
+        G = G + Vp.T @ Vp
+    return parts, Bt, V
+
+
+def nu(parts, Bt, V, Z, part: int = PART) -> np.ndarray:
+    """nu = L Z from the parts and the node rows alone (csrc/nu_lr.hip): L[P, P] Z[P] + V[P] sum_{Q < P} Bt[:, Q] Z[Q]"""
+    out = np.empty_like(Z)
+    T = np.zeros((RANK, Z.shape[1]))
+    for q, Lpp in enumerate(parts):
+        p = q * part
+        out[p:p + part] = Lpp @ Z[p:p + part] + V[p:p + part] @ T
+        T = T + Bt[:, p:p + part] @ Z[p:p + part]
+    return out
+
+
+def s_grid(Bt, Vstar) -> np.ndarray:
+    """draw_fstar's s = 1 - sqrt(v^T G v) at the rows v of Vstar, G = B^T B the product over the node rows"""
+    G = Bt @ Bt.T
+    return 1.0 - np.sqrt(np.maximum(np.einsum("jk,kl,jl->j", Vstar, G, Vstar), 0.0))

@@ -26,7 +26,7 @@ def _ptr(a):
 
 
 def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0, kernel_fp32=False,
-             kstar_rank=0) -> Options:
+             kstar_rank=0, factor_structured=False) -> Options:
     o = _lib.default_options()
     o.rng_kind = RNG_RSTREAM if rng == "reference" else RNG_ITEM
     o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -37,6 +37,7 @@ def _options(rng, seed, theta_stabilise, fstar_fused, device, item0=0, m_total=0
     o.m_total = int(m_total)
     o.kernel_fp32 = int(bool(kernel_fp32))
     o.kstar_rank = int(kstar_rank)
+    o.factor_structured = int(bool(factor_structured))
     return o
 
 
@@ -572,11 +573,14 @@ def _totals(raw) -> dict:
 class Sampler:
     """Stage-driven sampler (gpirt_sampler_*): device-resident state, one iteration per step().
     preset="fast": the options are gpirt_fast_options() (what bench.py's headline is timed with) with this call's seed,
-    item0 / m_total and kernel_fp32; rng, theta_stabilise, fstar_fused and kstar_rank are then the preset's."""
+    item0 / m_total and kernel_fp32; rng, theta_stabilise, fstar_fused, kstar_rank and factor_structured are then the preset's.
+    factor_structured: where the steady iteration reads nothing else of the factor, a factorisation builds only L's diagonal
+    parts and node rows, from theta (csrc/factor_lr.hip, gpirt_amd/factor_lr.py); get("L") and every other reader of the
+    whole factor get the dense one, formed on demand."""
 
     def __init__(self, handle, y, theta_init, beta_prior_means=None, beta_prior_sds=None,
                  beta_proposal_sds=None, *, rng="item", seed=1, rstream=None, theta_stabilise=True,
-                 fstar_fused=False, item0=0, m_total=0, kernel_fp32=False, kstar_rank=0, preset=None):
+                 fstar_fused=False, item0=0, m_total=0, kernel_fp32=False, kstar_rank=0, factor_structured=False, preset=None):
         self.lib = _lib.load()
         self.handle = handle
         y = _f64(y)
@@ -593,7 +597,8 @@ class Sampler:
             o.device = -1 if handle.device is None else int(handle.device)
             o.item0, o.m_total, o.kernel_fp32 = int(item0), int(m_total), int(bool(kernel_fp32))
         elif preset is None:
-            o = _options(rng, seed, theta_stabilise, fstar_fused, handle.device, item0, m_total, kernel_fp32, kstar_rank)
+            o = _options(rng, seed, theta_stabilise, fstar_fused, handle.device, item0, m_total, kernel_fp32, kstar_rank,
+                         factor_structured)
         else:
             raise ValueError(f"unknown preset {preset!r}")
         s = C.c_void_p()
@@ -725,6 +730,30 @@ class Sampler:
         r = C.c_int64()
         check(self.lib.gpirt_sampler_fstar_free_draws(self._s, C.byref(r)))
         return r.value
+
+    @property
+    def factor_lr_count(self) -> int:
+        """factorisations that built only L's diagonal parts and node rows, from theta (csrc/factor_lr.hip)"""
+        r = C.c_int64()
+        check(self.lib.gpirt_sampler_factor_lr_count(self._s, C.byref(r)))
+        return int(r.value)
+
+    @property
+    def dense_factor_count(self) -> int:
+        """dense factorisations this sampler has enqueued, those formed on demand behind a structured factor included"""
+        r = C.c_int64()
+        check(self.lib.gpirt_sampler_dense_factor_count(self._s, C.byref(r)))
+        return int(r.value)
+
+    def dense_factor(self):
+        """the dense factor now, if L holds a structured one: for a caller who reads L through a device pointer it kept"""
+        self._call("gpirt_sampler_dense_factor")
+
+    def factor_lr_parts(self) -> list:
+        """L's 512-column diagonal parts as they stand, in part order (w x w arrays), without forming the dense factor"""
+        out = np.empty((self.n, 512), dtype=np.float64)
+        check(self.lib.gpirt_sampler_factor_lr_parts(self._s, C.c_void_p(out.ctypes.data), out.size))
+        return [out[p:p + 512, :min(512, self.n - p)].T.copy() for p in range(0, self.n, 512)]
 
     def nu_lr_rows(self) -> np.ndarray:
         """the 64 node rows below the factor as they stand, 64 x n"""

@@ -321,8 +321,13 @@ typedef struct gpirt_options {
                                * r = 48 on the form is exact to rounding.  At r = 16 the error lifts ||L^-1 k*|| above 1 at
                                * about a fifth of the grid points: s = 1 - sqrt(q) < 0 there and R::rnorm's rule makes f* NaN
                                * (tests/test_gpu_fstar_ranks.py): r = 16 is not usable for a chain */
-    int      reserved[5];     /* must be 0.  (Up to version 100 kernel_fp32 and kstar_rank were the unnamed slots
+    int      reserved[4];     /* must be 0.  (Up to version 100 kernel_fp32 and kstar_rank were the unnamed slots
                                * reserved[1] and reserved[2] of an int reserved[8] at this offset: same layout, same size.) */
+    int      factor_structured; /* 0 or 1 (version 131; up to 130 the last slot of an int reserved[5]: same layout, same size).
+                               * 1: where the sampler's steady iteration reads nothing else of the factor (the conditions of
+                               * gpirt_sampler_factor_lr_count below) a factorisation builds only L's 512-column diagonal parts
+                               * and the 64 node rows, from theta; the dense factor is formed on demand.  0: every
+                               * factorisation is the dense one, bit for bit as before. */
 } gpirt_options;
 
 /* The reference's contract: GPIRT_RNG_RSTREAM (draw-for-draw replay of R's stream), draw_theta and draw_fstar as
@@ -331,7 +336,9 @@ typedef struct gpirt_options {
  * a host without R's RNG state sets rng_kind = GPIRT_RNG_ITEM (and a seed) explicitly. */
 void gpirt_default_options(gpirt_options* o);
 /* The throughput preset -- what bench.py times as its headline and what BASELINE.json's metric is quoted on: the item-keyed
- * RNG (seed = 1: set your own), theta_stabilise = 1, fstar_fused = 1, kstar_rank = 64.  Same sampler, every form
+ * RNG (seed = 1: set your own), theta_stabilise = 1, fstar_fused = 1, kstar_rank = 64, factor_structured = 1 (from n = 2048
+ * on a factorisation then builds L's diagonal parts and node rows alone, from theta: f within 1e-10 max(1, max|f|) and f* within
+ * 1e-9 max|f*| of the dense factor's, theta and beta the same draws).  Same sampler, every form
  * algebraically identical to the reference's (DESIGN.md sections 4-5: f* within 1e-9 of the as-written form relative to
  * max|f*| at 8192 x 1024, checked in every bench.py run); draws are NOT those of R's stream (gpirt_default_options is
  * that contract).  One call away from the drop-in: the R shim selects it with options(gpirt.hip.preset = "fast"). */
@@ -2506,6 +2513,30 @@ int gpirt_sampler_nu_lr_rows(gpirt_sampler_t s, double* h_out, int64_t count);
  * before.  GPIRT_FSTAR_FREE (gpirt_config_set): 1 this rule, 2 always through L, 3 at every eligible n.
  * gpirt_sampler_fstar_free_draws: how many draw_fstar calls of this sampler have used such a C. */
 int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws);
+/* Library version 131.  With both of the above in force a steady iteration reads of L only its 512-column diagonal parts
+ * L[P, P] and the 64 node rows.  A sampler created with gpirt_options.factor_structured = 1 then builds exactly those, from
+ * theta (csrc/factor_lr.hip): with G_P = V[<p]^T V[<p] the Gram of the basis rows in front of part P,
+ *   A_P = F^T G_P F + 0.001 I = R_P R_P^T,  Xh_P = R_P^-1 F^T,  X_P = Xh_P V[P]^T,
+ *   L[P, P] = chol(0.001 (I + X_P^T X_P)),  Bt[:, P] = 0.001 Xh_P^T (X_P L[P, P]^-T)
+ * -- 1.5e9 flop at n = 8192 instead of n^3 / 3 = 1.8e11; every pivot is >= sqrt(0.001).  The triangle of L below the parts is
+ * NOT written.  Parts and rows equal the dense factor's to rounding (measured in DESIGN.md section 39); they do not depend on
+ * m or item0 (an item shard's are bit-identical).  It runs where the structured nu = L z and C from theta alone both would
+ * (their switches included), gpirt_sampler_init excepted.  GPIRT_FACTOR_LR (gpirt_config_set): 1 this rule from n = 2048,
+ * 2 always the dense factor, 3 at every eligible n.
+ * Whatever reads more of L first replaces it by the dense factor of K(theta_L, theta_L), theta_L the theta the structured
+ * factor was built from (a gpirt_sampler_set("theta") in between does not change which matrix is factored): the dense nu = L z,
+ * the solves of the other draw_fstar forms, the length-scale update, gpirt_sampler_get("L"), gpirt_sampler_devptr("L"),
+ * gpirt_sampler_copy_state (on src), the factorisation in pieces.  A caller who keeps the pointer of gpirt_sampler_devptr("L")
+ * across factorisations calls gpirt_sampler_dense_factor before reading through it.
+ * gpirt_sampler_factor_lr_count: factorisations of this sampler that built the parts and rows alone;
+ * gpirt_sampler_dense_factor_count: dense factorisations it enqueued, those on demand included;
+ * gpirt_sampler_dense_factor: the dense factor now, if L holds a structured one (otherwise nothing);
+ * gpirt_sampler_factor_lr_parts: the diagonal parts as they stand, WITHOUT forming the dense factor: 512 x n column-major,
+ * column j holding L[p + i, j], i = 0 .. w - 1, for its part [p, p + w) (zero behind a shorter last part); count = 512 n. */
+int gpirt_sampler_factor_lr_count(gpirt_sampler_t s, int64_t* count);
+int gpirt_sampler_dense_factor_count(gpirt_sampler_t s, int64_t* count);
+int gpirt_sampler_dense_factor(gpirt_sampler_t s);
+int gpirt_sampler_factor_lr_parts(gpirt_sampler_t s, double* h_out, int64_t count);
 /* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m.  The kernel
  * is not part of the state: refused (GPIRT_E_ARG) when the two samplers' kernels differ, or while the length-scale update
  * (gpirt_sampler_ell_enable) is on for either -- its index and tables are not copied. */

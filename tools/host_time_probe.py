@@ -8,7 +8,7 @@ from gpirt_amd.synthetic import make_responses
 n, m = 8192, 1024
 y, th0 = make_responses(n, m, seed=7)
 h = Handle()
-s = Sampler(h, y, th0, rng="item", seed=11, theta_stabilise=True, fstar_fused=True, kstar_rank=64)
+s = Sampler(h, y, th0, preset="fast", seed=11)      # gpirt_fast_options: what bench.py times as its headline
 s.init()
 for _ in range(3): s.step()
 torch.cuda.synchronize()
