@@ -40,6 +40,7 @@ const Config& env_config()
         d.nu_lr = env_value("GPIRT_NU_LR", d.nu_lr);
         d.fstar_free = env_value("GPIRT_FSTAR_FREE", d.fstar_free);
         d.factor_lr = env_value("GPIRT_FACTOR_LR", d.factor_lr);
+        d.flr_fuse = env_value("GPIRT_FLR_FUSE", d.flr_fuse);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -165,7 +166,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 131; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 132; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -221,6 +222,8 @@ int gpirt_version(void) { return 131; }   // 101: gpirt_options names kernel_fp3
                                             // 131: gpirt_options.factor_structured (gpirt_fast_options sets it): L's diagonal parts and node
                                             //      rows alone, from theta (factor_lr.hip: GPIRT_FACTOR_LR, gpirt_sampler_factor_lr_count,
                                             //      gpirt_sampler_dense_factor_count, gpirt_sampler_dense_factor, gpirt_sampler_factor_lr_parts)
+                                            // 132: the structured factor runs one launch per 64-column round (factor_lr.hip: GPIRT_FLR_FUSE; 2 = the
+                                            //      launches of version 131); the same bits, no change to the interface
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -353,6 +356,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_NU_LR", &h->cfg.nu_lr, false },
         { "GPIRT_FSTAR_FREE", &h->cfg.fstar_free, false },
         { "GPIRT_FACTOR_LR", &h->cfg.factor_lr, false },
+        { "GPIRT_FLR_FUSE", &h->cfg.flr_fuse, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }

@@ -86,6 +86,8 @@ struct Config {
                                   //   where the sampler is eligible, 2 = always the solve through L, 3 = at every eligible n
     int  factor_lr = 1;           // GPIRT_FACTOR_LR: a sampler with gpirt_options.factor_structured builds L's diagonal parts and node rows alone,
                                   //   from theta (factor_lr.hip): 1 = from n = 2048 on where it is eligible, 2 = always the dense factor, 3 = at every eligible n
+    int  flr_fuse = 1;            // GPIRT_FLR_FUSE: the structured factor's rounds (factor_lr.hip): 1 = one launch per 64-column round (each round's update
+                                  //   rides in the next round's launch), 2 = a panel launch and two product launches per round, the diagonal placed at the end
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)
     int  guard_verbose = 0;       // GPIRT_GUARD_VERBOSE: 1 = a hang-guard fallback prints the guard record to stderr
 };

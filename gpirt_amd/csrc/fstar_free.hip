@@ -169,10 +169,12 @@ __global__ __launch_bounds__(256) void fstar_free_small_kernel(const double* __r
 // factored in LDS by the factorisation's own 64 x 64 Cholesky (potf2.h) and each wavefront solves R x = f for 16 rows f of F
 // with its substitution core (solve64.h): x is column i of Xh for row i of F.
 // A pivot that is not positive raises *err (the sampler's numeric error word).
+// prefix: the slots of Gv hold the parts' own Grams and work-group P first adds those of slots 1 .. P itself, element by
+// element in slot order from zero -- flr_scan_kernel's sums, so its bits, without its launch (slot 0 is not read: G_0 = 0).
 constexpr size_t FX_LDS = sizeof(double) * (3 * FR * FLD + 2 * 4 * FR);
 static_assert(FR * S64_LS <= 2 * FR * FLD, "the staged factor takes the place of Gv and Gv F");
-__global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
-                                                              double* __restrict__ Xh, int* __restrict__ err)
+__device__ __forceinline__ void fstar_free_xhat_body(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
+                                                     double* __restrict__ Xh, int* __restrict__ err, const bool prefix)
 {
     extern __shared__ __attribute__((aligned(16))) double ff_lds[];
     __shared__ int sfail, sinfo;
@@ -183,11 +185,19 @@ __global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __re
     double* sP = ff_lds + 3 * FR * FLD;      // potf2_64_body's two panels
     const int t = threadIdx.x, ti = t & 15, tj = t >> 4;
     const int lane = t & 63, wave = t >> 6, i = lane & 15, g = lane >> 4;
-    Gv += (int64_t)blockIdx.x * FR * FR;
+    // (a link of the fused structured factor's chain, 16 work-groups that share their SIMDs with draw_beta's waves: ahead of them at issue)
+    if (prefix) __builtin_amdgcn_s_setprio(3);
     Xh += (int64_t)blockIdx.x * FR * FR;
     for (int e = t; e < FR * FR; e += 256) {
         const int r = e & (FR - 1), c = e >> 6;
-        P[r + FLD * c] = Gv[e];
+        double gv;
+        if (prefix) {
+            gv = 0.0;
+            for (int q = 1; q <= (int)blockIdx.x; ++q) gv += Gv[(int64_t)q * FR * FR + e];
+        } else {
+            gv = Gv[(int64_t)blockIdx.x * FR * FR + e];
+        }
+        P[r + FLD * c] = gv;
         Q[r + FLD * c] = F[e];
     }
     if (t == 0) sinfo = 0;
@@ -219,6 +229,22 @@ __global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __re
     for (int J = 0; J < 4; ++J)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Xh[(16 * J + 4 * g + r) + FR * (wave * 16 + i)] = X[J][r];
+}
+
+__global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
+                                                              double* __restrict__ Xh, int* __restrict__ err)
+{
+    fstar_free_xhat_body(Gv, F, eps, Xh, err, false);
+}
+
+// The prefix form runs on the fused structured factor's chain while the sampler's side stream fills the chip with
+// draw_beta_kernel (stages.hip: 104 registers, four waves on every SIMD, which leaves 96 of a SIMD's 512 registers free).
+// Held to 96 registers (five waves a SIMD; the rest spills to scratch) its 16 work-groups start beside those waves; with
+// the 146 it would otherwise take they wait until the first draw_beta work-groups retire, 0.15 ms later.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void fstar_free_xhat_prefix_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps, double* __restrict__ Xh, int* __restrict__ err)
+{
+    fstar_free_xhat_body(Gv, F, eps, Xh, err, true);
 }
 
 }  // namespace
@@ -290,12 +316,13 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
 }
 
 // Xh[q] = R_q^-1 F^T with R_q R_q^T = F^T Gv[q] F + eps I for `batch` matrices Gv[q] (64 x 64 each, 4096 doubles apart), one
-// work-group per matrix
-int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err)
+// work-group per matrix.  prefix: matrix q is the sum of the slots 1 .. q of Gv, formed by its work-group (see the kernel)
+int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err, bool prefix)
 {
     if (batch <= 0) return 0;
-    GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fstar_free_xhat_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
-    hipLaunchKernelGGL(fstar_free_xhat_kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, err);
+    auto* kernel = prefix ? fstar_free_xhat_prefix_kernel : fstar_free_xhat_kernel;
+    GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, err);
     GP_HIP(hipGetLastError());
     return 0;
 }

@@ -253,8 +253,10 @@ constexpr int FSTAR_FREE_RANK = NU_LR_RANK;
 void fstar_free_factor(const KernelSpec& kern, std::vector<double>& F);        // host: F (64 x 64) with K(c, c) = F F^T
 int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const double* F, double eps, double* work, double* parts,
                       int nsplit, double* Cu, int* err);                        // work: 2 x 64 x 64, parts: nsplit x 64 x 64
-// Xh[q] = R_q^-1 F^T, R_q R_q^T = F^T Gv[q] F + eps I, for `batch` 64 x 64 matrices Gv[q] (one work-group each)
-int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err);
+// Xh[q] = R_q^-1 F^T, R_q R_q^T = F^T Gv[q] F + eps I, for `batch` 64 x 64 matrices Gv[q] (one work-group each); prefix: matrix q
+// is Gv[1] + ... + Gv[q], added by its own work-group in slot order (Gv[0] is not read)
+int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err,
+                           bool prefix = false);
 // factor_lr.hip: L's diagonal parts and the 64 node rows from theta alone -- nothing below the parts is computed
 struct FactorLrArgs {
     const double* theta; int64_t n;

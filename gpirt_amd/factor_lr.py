@@ -48,6 +48,67 @@ def structured_factor(theta, family="se", length_scale=1.0, eps: float = JITTER,
     return parts, Bt, V
 
 
+def structured_factor_fused(theta, family="se", length_scale=1.0, eps: float = JITTER, part: int = PART, F=None, block: int = 64):
+    """The same three results by the schedule of csrc/factor_lr.hip's flr_round_kernel: a part is
+    factored in rounds of `block` columns, one "launch" a round, its 64 border rows X_P riding along.
+
+    Launch k reads only what the launches before it wrote (`old` below) and every tile is written by one item:
+      * lazy update: each tile (i, j), k <= j <= i, and each border block j >= k first takes panel k - 1 off itself,
+        C(i, j) -= L(i, k - 1) L(j, k - 1)^T and X(:, j) -= X(:, k - 1) L(j, k - 1)^T; in launch 0 the tile is formed as
+        eps X_i^T X_j from X_b = Xh V[P_b]^T instead, and the border blocks are written;
+      * ownerless pivot tile: tile (k, k) is written by nobody in launch k -- every item of block column k reads it, applies
+        the same update, adds eps on the diagonal, factors it and solves its own rows against the factor;
+      * late placement: the pivot's factor waits in a workspace and goes into tile (k, k) in launch k + 1, when nobody reads
+        the tile any more (the last pivot's behind the last launch)."""
+    V = basis(theta)
+    n = V.shape[0]
+    if F is None:
+        F = kernel_factor(family, length_scale)
+    I = np.eye(RANK)
+    G = np.zeros((RANK, RANK))
+    parts, Bt = [], np.empty((RANK, n))
+    for p in range(0, n, part):
+        Vp = V[p:p + part]
+        w = Vp.shape[0]
+        if w % block:
+            raise ValueError("a part is a whole number of blocks")
+        nb = w // block
+        A = F.T @ (G @ F) + eps * I
+        R = np.linalg.cholesky(np.tril(A) + np.tril(A, -1).T)
+        Xh = solve_triangular(R, F.T, lower=True)
+        b = lambda j: slice(block * j, block * (j + 1))
+        xblock = lambda j: Xh @ Vp[b(j)].T
+        C = np.full((w, w), np.nan)              # the part of L: tiles on and below the block diagonal
+        X = np.full((RANK, w), np.nan)           # the border
+        Dw = [None] * nb                         # the pivots' factors until they are placed
+        for k in range(nb):
+            old, Xold = C.copy(), X.copy()
+            if k == 0:
+                tile = lambda i, j: eps * (xblock(i).T @ xblock(j))
+                border = xblock
+            else:
+                tile = lambda i, j: old[b(i), b(j)] - old[b(i), b(k - 1)] @ old[b(j), b(k - 1)].T
+                border = lambda j: Xold[:, b(j)] - Xold[:, b(k - 1)] @ old[b(j), b(k - 1)].T
+            # every item of block column k forms the pivot block itself; nobody writes tile (k, k) in this launch
+            D = np.tril(tile(k, k)) + eps * np.eye(block)
+            Lkk = np.linalg.cholesky(D + np.tril(D, -1).T)
+            for i in range(k + 1, nb):
+                C[b(i), b(k)] = solve_triangular(Lkk, tile(i, k).T, lower=True).T
+            X[:, b(k)] = solve_triangular(Lkk, border(k).T, lower=True).T
+            Dw[k] = Lkk
+            for j in range(k + 1, nb):
+                X[:, b(j)] = border(j)
+                for i in range(j, nb):
+                    C[b(i), b(j)] = np.tril(tile(i, j)) if i == j else tile(i, j)
+            if k >= 1:
+                C[b(k - 1), b(k - 1)] = Dw[k - 1]
+        C[b(nb - 1), b(nb - 1)] = Dw[nb - 1]
+        parts.append(np.tril(C))
+        Bt[:, p:p + part] = eps * (Xh.T @ X)
+        G = G + Vp.T @ Vp
+    return parts, Bt, V
+
+
 def nu(parts, Bt, V, Z, part: int = PART) -> np.ndarray:
     """nu = L Z from the parts and the node rows alone (csrc/nu_lr.hip): L[P, P] Z[P] + V[P] sum_{Q < P} Bt[:, Q] Z[Q]"""
     out = np.empty_like(Z)

@@ -2532,7 +2532,10 @@ int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws);
  * gpirt_sampler_dense_factor_count: dense factorisations it enqueued, those on demand included;
  * gpirt_sampler_dense_factor: the dense factor now, if L holds a structured one (otherwise nothing);
  * gpirt_sampler_factor_lr_parts: the diagonal parts as they stand, WITHOUT forming the dense factor: 512 x n column-major,
- * column j holding L[p + i, j], i = 0 .. w - 1, for its part [p, p + w) (zero behind a shorter last part); count = 512 n. */
+ * column j holding L[p + i, j], i = 0 .. w - 1, for its part [p, p + w) (zero behind a shorter last part); count = 512 n.
+ * Library version 132: the structured factor runs one launch per 64-column round (12 launches at n = 8192 instead of 29;
+ * DESIGN.md section 40).  The same sums in the same order: parts and rows are bit for bit those of version 131.
+ * GPIRT_FLR_FUSE (gpirt_config_set): 1 these launches (the default), 2 the launches of version 131.  No change to this interface. */
 int gpirt_sampler_factor_lr_count(gpirt_sampler_t s, int64_t* count);
 int gpirt_sampler_dense_factor_count(gpirt_sampler_t s, int64_t* count);
 int gpirt_sampler_dense_factor(gpirt_sampler_t s);
