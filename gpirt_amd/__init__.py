@@ -14,6 +14,8 @@ Layout:
                    NumPy statement of one update, the exact conditional posterior, the one-call run
   amp.py           per-item GP amplitudes, fixed or sampled in the chain (one launch updates every item on a grid): the
                    NumPy statement of one update, the exact conditional posterior per item, the one-call run
+  consistent.py    the consistent step beside the reference's (f carried to the new theta plus the model's nugget) and the
+                   prior check: the NumPy statement of the carry, the device's normals, the exact prior quadratic form
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

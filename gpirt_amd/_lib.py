@@ -21,6 +21,7 @@ ST_INIT_F, ST_INIT_BETA, ST_F_Z, ST_F_ESS, ST_FSTAR, ST_THETA, ST_BETA = 1, 2, 3
 ST_PPC = 8                        # the replicate of the posterior predictive checks (gpirt_amd.ppc)
 ST_ELL = 9                        # the two uniforms of a length-scale update (gpirt_amd.ell): item index 0 whitened, 1 centred
 ST_AMP = 10                       # the two uniforms per item of an amplitude update (gpirt_amd.amp): item index item0 + j
+ST_CARRY = 11                     # the nugget of the consistent step's carry (gpirt_amd.consistent): item index item0 + j, index i
 
 E_ARG, E_HIP, E_NODEVICE, E_ALLOC, E_RNG, E_INTERRUPT, E_NUMERIC = -1, -2, -3, -4, -5, -6, -7
 
@@ -523,6 +524,15 @@ class Amp(C.Structure):
         (k, C.c_double) for k in ("accept_rate", "lo", "hi", "min_amplitude", "max_amplitude")] + [("reserved", C.c_int64 * 4)]
 
 
+# the consistent step's carry (include/gpirt_hip.h gpirt_carry; gpirt_amd.consistent)
+CARRY_COUNTS = ("calls", "off_grid", "nonfinite", "total_off_grid", "total_nonfinite")
+
+
+class Carry(C.Structure):
+    """gpirt_carry (include/gpirt_hip.h): the carries so far, the last call's two counters, their sums, the last call's time."""
+    _fields_ = [(k, C.c_int64) for k in CARRY_COUNTS] + [("last_ms", C.c_double), ("reserved", C.c_int64 * 4)]
+
+
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _vp, _i64, _i32, _u64, _u32, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_double
@@ -762,6 +772,10 @@ SIGNATURES = {
     "gpirt_sampler_amp_record": (_i32, [_vp]),
     "gpirt_sampler_amp_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_amp_stats": (_i32, [_vp, C.POINTER(Amp)]),
+    "gpirt_sampler_carry_f": (_i32, [_vp, _i32]),
+    "gpirt_sampler_step_consistent": (_i32, [_vp, _i32]),
+    "gpirt_sampler_carry_stats": (_i32, [_vp, C.POINTER(Carry)]),
+    "gpirt_sampler_prior_quad": (_i32, [_vp, _dp]),
 }
 
 _lib = None

@@ -425,11 +425,12 @@ def from_draws(theta_draws, beta_draws, g_draws, y, planned=None, max_lag=None, 
 
 # ------------------------------------------------------------------------------------------------ one call for C chains ---
 def run(y, sample_iterations, burn_iterations, chains=1, seed=1, *, parts="all", max_lag=None, top=DEFAULT_TOP, align=True,
-        theta_init=None, preset="fast", handle=None, **sampler_kw) -> dict:
+        theta_init=None, preset="fast", handle=None, consistent=False, **sampler_kw) -> dict:
     """`chains` chains of the stage-driven Sampler, one after the other, each with the autocorrelation block and the DIAG
     summaries on; chain c runs with the seed chain_seed(seed, c) from gpirtMCMC(chains=...)'s default init.  The signs are the
     ones gpirt_amd.chains.combine decides for the same chains (align=False: none).  Returns combine()'s dict with
-    "diagnostics" (the batch-means ones of the same chains) and "reflected" beside it."""
+    "diagnostics" (the batch-means ones of the same chains) and "reflected" beside it.  consistent=True: every iteration is Sampler.step(consistent=True)
+    (gpirt_amd.consistent); "consistent" in the result names it."""
     from . import chains as CH
     from .ops import Handle
     from .sampler import Sampler
@@ -449,7 +450,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, *, parts="all",
             s.summary_enable(_lib.SUM_THETA_BETA | _lib.SUM_DIAG, planned_draws=S)
             s.acf_enable(mask, S, max_lag)
             for it in range(S + B):
-                s.step()
+                s.step(consistent=consistent)
                 if it >= B:
                     s.accumulate_irf()
                     s.summary_accumulate()
@@ -458,7 +459,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, *, parts="all",
         pooled = CH.combine(h, samplers, align=align)
         refl = pooled["diagnostics"]["reflected"]
         out = combine(h, samplers, signs=[-1 if r else 1 for r in refl], top=top)
-        out.update(diagnostics=pooled["diagnostics"], reflected=refl)
+        out.update(diagnostics=pooled["diagnostics"], reflected=refl, consistent=bool(consistent))
         return out
     finally:
         for s in samplers:

@@ -198,7 +198,7 @@ def summarise(draws, hist, amp_grid, probs=(0.025, 0.25, 0.5, 0.75, 0.975)) -> d
 # ------------------------------------------------------------------------------------------------ one call per run ---
 def run(y, sample_iterations, burn_iterations, chains=1, seed=1, lo=0.1, hi=10.0, points=129, width=4, every=1, adapt=True,
         kernel=None, fixed=None, top=20, log_prior=None, k0=None, loo=False, preset="fast", store_draws=True, theta_init=None, *,
-        handle=None, **sampler_kw) -> dict:
+        handle=None, consistent=False, **sampler_kw) -> dict:
     """gpirt_amd.kernel.run's stage loop with per-item amplitudes: `chains` chains of the stage-driven Sampler under `kernel`, one
     after the other, each with Sampler.draw_amp() after every `every`-th step() and Sampler.amp_record() per kept draw.  y: n x m
     of +1 / -1 / NaN.  Every item starts at index k0 (None: the grid point nearest 1).  adapt=True: during the burn-in, and nowhere
@@ -211,7 +211,10 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, lo=0.1, hi=10.0
     mode ("sampled"), draws (the recorded indices, chains x S x m; S x m for one chain) and amplitude (grid[draws]); hist
     (P x m, pooled over the chains), mean, sd, quantiles, mode_amplitude, p_below, rhat and ess of log a_j (`summarise`);
     accept_rate and width per chain and item (of the sampling phase), counts per chain (4 x m), grid, log_prior, every;
-    smallest and largest: the `top` items with the smallest and with the largest posterior mean amplitude (item, mean, sd)."""
+    smallest and largest: the `top` items with the smallest and with the largest posterior mean amplitude (item, mean, sd).
+
+    consistent=True: every iteration is Sampler.step(consistent=True) -- f is carried to the new theta with the model's nugget,
+    whose sd carries a_j (gpirt_amd.consistent); the result's "consistent" names it."""
     from . import chains as CH
     from . import kernel as K
     from . import loo as LO
@@ -294,7 +297,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, lo=0.1, hi=10.0
             start = np.zeros((4, m), dtype=np.int64)
             done = 0
             for it in range(S + B):
-                s.step()
+                s.step(consistent=consistent)
                 if sampled and (it + 1) % every == 0:
                     s.draw_amp()
                     done += 1
@@ -338,7 +341,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, lo=0.1, hi=10.0
                        smallest=[row(j) for j in order[:tp]], largest=[row(j) for j in order[::-1][:tp]])
         else:
             amp = dict(mode="fixed", amplitude=fixed.copy())
-        out = dict(theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
+        out = dict(consistent=bool(consistent), theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
                    diagnostics=pooled["diagnostics"], kernel=used, kstar_rank=rank, chains=nc, amp=amp,
                    loo=LO.combine(h, samplers, top=want_loo["top"]) if want_loo is not None else None)
         if nc == 1:

@@ -166,7 +166,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 132; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 133; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -224,6 +224,10 @@ int gpirt_version(void) { return 132; }   // 101: gpirt_options names kernel_fp3
                                             //      gpirt_sampler_dense_factor_count, gpirt_sampler_dense_factor, gpirt_sampler_factor_lr_parts)
                                             // 132: the structured factor runs one launch per 64-column round (factor_lr.hip: GPIRT_FLR_FUSE; 2 = the
                                             //      launches of version 131); the same bits, no change to the interface
+                                            // 133: a consistent step beside the reference's: f carried to the new theta plus the model's
+                                            //      nugget, and the prior check (carry.hip, sampler.hip: GPIRT_ST_CARRY, gpirt_sampler_carry_f,
+                                            //      gpirt_sampler_step_consistent, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); stage
+                                            //      API only, gpirt_sampler_step and every existing stage's uniforms are unchanged
 
 const char* gpirt_last_error(void) { return g_err; }
 

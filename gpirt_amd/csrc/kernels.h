@@ -76,6 +76,19 @@ int launch_amp_update(hipStream_t st, const AmpUpdateArgs& a);
 // draws[slot, j] = idx[j] (planned x m, row-major), hist[idx[j], j] += 1 (P x m, row-major)
 int launch_amp_record(hipStream_t st, const int* idx, int64_t m, int P, int64_t slot, uint32_t* hist, int32_t* draws);
 int amp_nearest_one(const double* grid, int P);                     // the grid point nearest 1 in log a (the first of a tie)
+// carry.hip: the consistent step's carry stage (gpirt_sampler_carry_f) and the prior check's reduction (gpirt_sampler_prior_quad)
+struct CarryArgs {
+    double* f; const double* theta; const double* fstar; const double* mu_star; int64_t n, m, N;       // f: n x m; fstar, mu_star: N x m
+    const double* amp;                                                  // m amplitudes, or nullptr: 1.0
+    // 6 words, {off_grid, nonfinite} three times: [0, 1] the sampler's life, [2 + 2 slot, ..] this call's, and the third pair is
+    // zeroed by this launch for the next call (slot alternates 0 / 1 from call to call; all six start at zero)
+    unsigned long long* counters; int slot;
+    uint64_t seed; uint32_t iter; uint32_t item0; int nugget;
+};
+// f_ij <- fstar[k_i, j] - mu_star[k_i, j] (+ sd_j z_ij with nugget) for every row whose theta is a grid point: one launch
+int launch_carry_f(hipStream_t st, const CarryArgs& a);
+// q[j] = sum_i nu_ij^2 (nu: n x m, column-major), ell_quad_kernel's order
+int launch_prior_quad(hipStream_t st, const double* nu, int64_t n, int64_t m, double* q);
 int ell_grid_check(double lo, double hi, int P);                    // GPIRT_E_ARG with the message
 void ell_grid_fill(double lo, double hi, int P, double* out);         // long double, rounded to fp64, the end points exact
 

@@ -82,6 +82,16 @@ struct AmpState {
     double last_ms = 0.0;
 };
 
+// The consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad; include/gpirt_hip.h,
+// carry.hip).  Both buffers are allocated by the first call that needs them: a sampler that never calls either has neither.
+struct CarryState {
+    int64_t calls = 0;
+    unsigned long long* counters = nullptr;   // device, 6: off_grid, nonfinite of the sampler's life, of the even calls, of the odd calls
+    double* quad = nullptr;                   // device, m: the prior check's q_j
+    hipEvent_t tev[2] = {};                   // with gpirt_sampler_enable_timing on: around the carry's launch
+    double last_ms = 0.0;
+};
+
 struct gpirt_sampler_s {
     gpirt_handle_t h = nullptr;
     int64_t n = 0, m = 0, N = GPIRT_NGRID;
@@ -234,6 +244,7 @@ struct gpirt_sampler_s {
     GroupsState groups;               // group posteriors (gpirt_sampler_groups_enable; on == false: off)
     EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
     AmpState amp;                     // per-item GP amplitudes (gpirt_sampler_amp_set, gpirt_sampler_amp_enable; mode == 0: off)
+    CarryState carry;                 // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
 };
 
 namespace {
@@ -989,6 +1000,49 @@ int do_draw_beta(gpirt_sampler_s* s)
     GP_TRY(beta_sync(s));
     if (defer) { s->beta_deferred = true; return 0; }     // do_factor launches it behind the factorisation's last outer panel
     return launch_beta_on(s, s->h->stream);
+}
+
+// ---- the consistent step's carry (include/gpirt_hip.h; the kernel is carry.hip's) ---------------------------------------------
+// the refusals of gpirt_sampler_carry_f and gpirt_sampler_step_consistent, each with its reason
+int carry_refusals(gpirt_sampler_s* s, int nugget, const char* entry)
+{
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", entry); return GPIRT_E_ARG; }
+    if (stream_mode(s)) {
+        set_error("carry: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw");
+        return GPIRT_E_ARG;
+    }
+    if (nugget != 0 && nugget != 1) { set_error("carry: nugget = %d, it must be 0 or 1", nugget); return GPIRT_E_ARG; }
+    return 0;
+}
+
+// f <- the curve at the new theta (+ the nugget), on the main stream: behind theta_finish / theta_commit, in front of draw_beta.
+// mu_star is the one this iteration's draw_fstar added (draw_beta, which rewrites it, has not run yet).  timed: the launch
+// between the carry's own two events (the caller reads them once the stream has passed the second).
+int do_carry_f(gpirt_sampler_s* s, int nugget, bool timed)
+{
+    CarryState& c = s->carry;
+    hipStream_t st = s->h->stream;
+    // a draw_beta still held back or running on the sampler's own stream reads the f this stage rewrites (inside a step: none)
+    GP_TRY(beta_sync(s));
+    if (!c.counters) {
+        GP_TRY(dalloc(s, &c.counters, 6));
+        GP_HIP(hipMemsetAsync(c.counters, 0, 6 * sizeof(unsigned long long), st));
+    }
+    CarryArgs a{};
+    a.slot = (int)(c.calls & 1);              // (the launch adds to this call's pair and zeroes the other for the next call)
+    a.f = s->f; a.theta = s->theta; a.fstar = s->fstar; a.mu_star = s->mu_star; a.n = s->n; a.m = s->m; a.N = s->N;
+    a.amp = s->amp.mode ? s->amp.amp : nullptr;
+    a.counters = c.counters;
+    a.seed = s->opt.seed; a.iter = (uint32_t)(s->iter + 1); a.item0 = (uint32_t)s->opt.item0; a.nugget = nugget;
+    if (timed) {
+        for (hipEvent_t& t : c.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(c.tev[0], st));
+    }
+    GP_TRY(launch_carry_f(st, a));
+    if (timed) GP_HIP(hipEventRecord(c.tev[1], st));
+    c.calls += 1;
+    c.last_ms = 0.0;
+    return 0;
 }
 
 // everything derived from the factor (C, G, cached block inverses on either handle) is stale once L changes
@@ -1939,6 +1993,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     score_free(&s->score);
     ell_free(&s->ell);
     amp_free(&s->amp);
+    for (hipEvent_t t : s->carry.tev) if (t) hipEventDestroy(t);      // (its two buffers are in `allocs`)
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -2158,6 +2213,89 @@ int gpirt_sampler_step(gpirt_sampler_t s)
             s->stage_ms[i] = ms;
         }
     }
+    return 0;
+}
+
+// ---- the consistent step (include/gpirt_hip.h, "a consistent step"; carry.hip) -------------------------------------------------
+int gpirt_sampler_carry_f(gpirt_sampler_t s, int nugget)
+{
+    GP_ARG(s != nullptr);
+    GP_TRY(carry_refusals(s, nugget, "gpirt_sampler_carry_f"));
+    const bool timed = s->timing;
+    GP_TRY(do_carry_f(s, nugget, timed));
+    if (timed) {                              // (timing on: one synchronisation, as the amplitude update's)
+        GP_HIP(hipEventSynchronize(s->carry.tev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->carry.tev[0], s->carry.tev[1]);
+        s->carry.last_ms = ms;
+    }
+    return 0;
+}
+
+// gpirt_sampler_step with the carry between theta_finish and draw_beta: the same marks, the carry between its own two events
+int gpirt_sampler_step_consistent(gpirt_sampler_t s, int nugget)
+{
+    GP_ARG(s != nullptr);
+    GP_TRY(carry_refusals(s, nugget, "gpirt_sampler_step_consistent"));
+    mark(s, 0);
+    GP_TRY(do_draw_f(s));            mark(s, 1);
+    GP_TRY(do_draw_fstar(s, (uint32_t)(s->iter + 1))); mark(s, 2);
+    GP_TRY(do_theta_partial(s));     mark(s, 3);
+    GP_TRY(do_theta_finish(s));      mark(s, 4);
+    GP_TRY(do_carry_f(s, nugget, s->timing));
+    GP_TRY(do_draw_beta(s));         mark(s, 5);
+    GP_TRY(do_factor(s));            mark(s, 6);
+    s->iter += 1;
+    if (s->timing) {
+        GP_HIP(hipEventSynchronize(s->ev[ST_COUNT]));
+        for (int i = 0; i < ST_COUNT; ++i) {
+            float ms = 0.f;
+            // (draw_beta's time starts behind the carry, whose own is the seventh: gpirt_carry.last_ms)
+            hipEventElapsedTime(&ms, i == ST_BETA ? s->carry.tev[1] : s->ev[i], s->ev[i + 1]);
+            s->stage_ms[i] = ms;
+        }
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->carry.tev[0], s->carry.tev[1]);
+        s->carry.last_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_carry_stats(gpirt_sampler_t s, gpirt_carry* out)
+{
+    GP_ARG(s && out);
+    const CarryState& c = s->carry;
+    memset(out, 0, sizeof(*out));
+    out->calls = c.calls; out->last_ms = c.last_ms;
+    if (!c.counters) return 0;
+    unsigned long long w[6];
+    GP_HIP(hipMemcpyAsync(w, c.counters, sizeof(w), hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    const int last = 2 + 2 * (int)((c.calls - 1) & 1);
+    out->total_off_grid = (int64_t)w[0]; out->total_nonfinite = (int64_t)w[1];
+    out->off_grid = (int64_t)w[last]; out->nonfinite = (int64_t)w[last + 1];
+    return 0;
+}
+
+// q_j = || L^-1 f_j ||^2: the forward solve of the centred length-scale update's first half into NU (free between steps), then
+// one reduction.  Nothing of the chain moves; a structured factor is replaced by the dense one first.
+int gpirt_sampler_prior_quad(gpirt_sampler_t s, double* h_q)
+{
+    GP_ARG(s && h_q);
+    if (!s->initialised) { set_error("gpirt_sampler_prior_quad needs an initialised sampler (gpirt_sampler_init)"); return GPIRT_E_ARG; }
+    gpirt_handle_t h = s->h;
+    hipStream_t st = h->stream;
+    const int64_t n = s->n, m = s->m;
+    GP_TRY(ell_settle_factor(s));             // (a factor nobody has looked at yet: its info words read, an expired guard repaired)
+    GP_TRY(aux_join(s, true, false));         // (a held-back draw_beta runs now; a prefilled Z is kept: nothing here touches it)
+    GP_TRY(ensure_dense_factor(s));           // (the solve goes through all of L)
+    s->factor_fresh = false;
+    if (!s->carry.quad) GP_TRY(dalloc(s, &s->carry.quad, (size_t)m));
+    GP_HIP(hipMemcpyAsync(s->NU, s->f, sizeof(double) * (size_t)(n * m), hipMemcpyDeviceToDevice, st));
+    GP_TRY(launch_trsm_lower(h, st, s->L, n, s->ldl, s->NU, m, n, false));
+    GP_TRY(launch_prior_quad(st, s->NU, n, m, s->carry.quad));
+    GP_HIP(hipMemcpyAsync(h_q, s->carry.quad, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -251,7 +251,7 @@ def summarise(index, ell_grid, probs=(0.025, 0.25, 0.5, 0.75, 0.975)) -> dict:
 # ------------------------------------------------------------------------------------------------ one call per run ---
 def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo=0.25, hi=4.0, points=129, width=4,
         log_prior=None, every=1, adapt=True, loo=False, preset="fast", store_draws=True, theta_init=None, k0=None, *,
-        handle=None, update="whitened", width_centred=None, **sampler_kw) -> dict:
+        handle=None, update="whitened", width_centred=None, consistent=False, **sampler_kw) -> dict:
     """gpirt_amd.kernel.run's stage loop with the length scale in the chain: `chains` chains of the stage-driven Sampler, one
     after the other, each with Sampler.draw_ell() after every `every`-th step().  y: n x m of +1 / -1 / NaN.
 
@@ -268,7 +268,10 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
     the keyword existed), "centred" (Sampler.draw_ell("centred"), width `width_centred`, None: `width`), or "both": the whitened
     update and then the centred one, in that fixed order.  The burn-in retunes each kind's width from that kind's own
     acceptance.  ell["update"] names the mode; with "centred" or "both", ell's accept_rate, width and counts are dicts with one
-    entry per kind that ran ("whitened", "centred"), each what the default mode holds for its one kind."""
+    entry per kind that ran ("whitened", "centred"), each what the default mode holds for its one kind.
+
+    consistent=True: every iteration is Sampler.step(consistent=True) -- f is carried to the new theta with the model's nugget
+    (gpirt_amd.consistent), the state the centred update's prior density assumes; the result's "consistent" names it."""
     from . import chains as CH
     from . import kernel as K
     from . import loo as LO
@@ -345,7 +348,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
             of = lambda e, kd: e if kd == "whitened" else e["centred"]                   # noqa: E731
             w, seen, start = dict(width0), {kd: (0, 0) for kd in kinds}, {kd: (0, 0) for kd in kinds}
             for it in range(S + B):
-                s.step()
+                s.step(consistent=consistent)
                 if (it + 1) % every == 0:
                     for kd in kinds:
                         s.draw_ell(kd)
@@ -381,7 +384,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, family="se", lo
             rates, widths, counts = rates["whitened"], widths["whitened"], counts["whitened"]
         ell.update(update=update, index=index if nc > 1 else index[0], length_scale=g[index] if nc > 1 else g[index[0]], accept_rate=rates,
                    width=widths, counts=counts, grid=g, log_prior=samplers[0].ell_get("log_prior"), every=every)
-        out = dict(theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
+        out = dict(consistent=bool(consistent), theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
                    diagnostics=pooled["diagnostics"], kernel=used, kstar_rank=rank, chains=nc, ell=ell,
                    loo=LO.combine(h, samplers, top=want_loo["top"]) if want_loo is not None else None)
         if nc == 1:

@@ -134,7 +134,7 @@ def fast_rank(kernel) -> int:
 
 # ------------------------------------------------------------------------------------------------ one call per kernel ---
 def run(y, sample_iterations, burn_iterations, chains=1, seed=1, kernel=None, loo=True, preset="fast", theta_init=None,
-        store_draws=True, *, handle=None, **sampler_kw) -> dict:
+        store_draws=True, *, handle=None, consistent=False, **sampler_kw) -> dict:
     """`chains` chains of the stage-driven Sampler under `kernel`, one after the other -- the stage loop of gpirt_amd.acf.run:
     chain c runs with the seed chain_seed(seed, c) from gpirtMCMC(chains=...)'s default init, with the DIAG summaries and
     (loo=True, or dict(tail=..., top=...)) PSIS-LOO on.  y: n x m of +1 / -1 / NaN.
@@ -147,7 +147,9 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, kernel=None, lo
     after init; stacked with a leading chain axis for chains > 1; None where store_draws leaves a draw out), IRFs (1001 x m,
     pooled over the chains), summary and diagnostics (gpirt_amd.chains.combine), loo (gpirt_amd.loo's dict, or None),
     kernel (dict(family, length_scale)) and kstar_rank, the rank used.  With kernel=None and the defaults the draws are
-    gpirtMCMC(y, S, B, preset="fast", seed=seed)'s."""
+    gpirtMCMC(y, S, B, preset="fast", seed=seed)'s.
+    consistent=True: every iteration is Sampler.step(consistent=True) -- f is carried to the new theta with the model's nugget
+    (gpirt_amd.consistent); the result's "consistent" names it."""
     from . import chains as CH
     from . import loo as LO
     from .ops import Handle
@@ -207,7 +209,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, kernel=None, lo
             if want_loo is not None:
                 s.loo_enable(nc * S, want_loo["tail"])
             for it in range(S + B):
-                s.step()
+                s.step(consistent=consistent)
                 if it >= B:
                     s.accumulate_irf()
                     store(c, it - B + 1, s)
@@ -218,7 +220,7 @@ def run(y, sample_iterations, burn_iterations, chains=1, seed=1, kernel=None, lo
             if nc == 1:
                 irf_one = s.finish_irfs(S)
         pooled = CH.combine(h, samplers)
-        out = dict(theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
+        out = dict(consistent=bool(consistent), theta=th, beta=be, f=ff, IRFs=irf_one if nc == 1 else pooled["IRFs"], summary=pooled["summary"],
                    diagnostics=pooled["diagnostics"], kernel=used, kstar_rank=rank, chains=nc,
                    loo=LO.combine(h, samplers, top=want_loo["top"]) if want_loo is not None else None)
         if nc == 1:

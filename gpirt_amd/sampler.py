@@ -646,7 +646,51 @@ class Sampler:
         check(getattr(self.lib, entry)(self._s, name.encode(), C.c_void_p(out.ctypes.data), out.nbytes))
 
     def init(self): self._call("gpirt_sampler_init")
-    def step(self): self._call("gpirt_sampler_step")
+
+    def step(self, consistent=False, nugget=True):
+        """One iteration.  The default is the reference's (gpirt_sampler_step): theta moves and f stays at the old theta.
+        consistent=True: gpirt_sampler_step_consistent -- the same stages with carry_f(nugget) between theta_finish and
+        draw_beta, so that f belongs to the new theta (gpirt_amd.consistent)."""
+        if not consistent:
+            self._last_step_consistent = False
+            self._call("gpirt_sampler_step")
+            return
+        rc = self.lib.gpirt_sampler_step_consistent(self._s, int(nugget))
+        if rc > 0:
+            raise RuntimeError("chol(): decomposition failed (leading minor %d)" % rc)
+        check(rc)
+        self._last_step_consistent = True
+
+    def carry_f(self, nugget=True):
+        """The carry stage, behind theta_finish (or theta_commit) and in front of draw_beta: f[i, :] becomes the curve
+        fstar - mu_star at respondent i's new grid point, plus the model's nugget sd_j z_ij with nugget=True (gpirt_sampler_carry_f;
+        gpirt_amd.consistent.carry_exact is its NumPy statement).  Refused with the reason under rng="reference" and before
+        init()."""
+        check(self.lib.gpirt_sampler_carry_f(self._s, int(nugget)))
+
+    def carry_stats(self) -> dict:
+        """calls, and off_grid / nonfinite of the last carry and summed over the sampler's life (total_*): rows whose theta is
+        no grid point (their f stays) and non-finite fstar cells carried; time_ms: the last carry's device time with
+        enable_timing() on."""
+        c = _lib.Carry()
+        check(self.lib.gpirt_sampler_carry_stats(self._s, C.byref(c)))
+        out = {k: int(getattr(c, k)) for k in _lib.CARRY_COUNTS}
+        out["time_ms"] = float(c.last_ms)
+        return out
+
+    def prior_quad(self) -> np.ndarray:
+        """The prior check, m values: || L^-1 f_j ||^2 / (n a_j^2) for the sampler's current factor and f (a_j: the item's
+        amplitude, 1 when amplitudes are off).  Near 1 says f_j looks like a draw from its prior at the current theta, which is
+        what an update that reads the prior density assumes; after the reference's step() it is in the hundreds.  Nothing of
+        the chain moves; a structured factor is replaced by the dense one first (dense_factor_count moves by one)."""
+        q = np.empty(self.m)
+        rc = self.lib.gpirt_sampler_prior_quad(self._s, _ptr(q))
+        if rc > 0:
+            raise RuntimeError("chol(): decomposition failed (leading minor %d)" % rc)
+        check(rc)
+        a = self.amp_get("amplitude") if self.amp()["mode"] else 1.0
+        return q / (float(self.n) * a * a)
+
     def draw_f(self): self._call("gpirt_sampler_draw_f")
     def draw_fstar(self): self._call("gpirt_sampler_draw_fstar")
     def theta_partial(self): self._call("gpirt_sampler_theta_partial")
@@ -1788,4 +1832,7 @@ class Sampler:
         k = C.c_int()
         check(self.lib.gpirt_sampler_stage_times(self._s, ms, 16, C.byref(k), None))
         names = ["draw_f", "draw_fstar", "theta_gemm", "theta_sample", "draw_beta", "factor"]
-        return {names[i]: ms[i] for i in range(k.value)}
+        out = {names[i]: ms[i] for i in range(k.value)}
+        if getattr(self, "_last_step_consistent", False):       # the seventh stage of step(consistent=True)
+            out["carry"] = self.carry_stats()["time_ms"]
+        return out

@@ -56,6 +56,7 @@ enum {
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
+    GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
     GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
 
@@ -63,7 +64,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 133: a consistent step beside the reference's -- f carried to the new theta plus the model's nugget, and the prior check (GPIRT_ST_CARRY, gpirt_sampler_carry_f, gpirt_sampler_step_consistent, gpirt_carry, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2240,6 +2241,64 @@ int gpirt_sampler_amp_width(gpirt_sampler_t s, const int* w);
 int gpirt_sampler_amp_record(gpirt_sampler_t s);
 int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out);
+
+/* ------------------------------------------------------ a consistent step: f carried to the new theta, a prior check ---- */
+/* Library version 133.  The reference's iteration moves theta and keeps f (quirk Q3 of SURVEY.md): behind gpirt_sampler_step
+ * f[i, :] is the GP's value at respondent i's OLD position while mu, L and everything built on them belong to the new one, and
+ * the prior quadratic form f_j^T S(theta)^-1 f_j / n, which is near 1 for a draw from the prior, sits two orders of magnitude
+ * above it (README, "a consistent step").  Whatever reads the prior density of f after such a step reads that mismatch as
+ * roughness.  The entries below are an opt-in BESIDE the reference's step: gpirt_sampler_step, gpirt_options, gpirt_run,
+ * gpirt_mcmc* and every existing stage's uniforms are unchanged, and a sampler that never calls them computes bit for bit
+ * what it did.
+ *
+ * gpirt_sampler_carry_f(s, nugget): the carry stage, behind gpirt_sampler_theta_finish (or gpirt_sampler_theta_commit) and in
+ * front of gpirt_sampler_draw_beta; one launch over the n x m cells on the handle's stream (csrc/carry.hip).  Per respondent i,
+ * with k_i the k for which theta_i is bit for bit -5 + 0.01 k (else -1):
+ *   k_i < 0 (NaN, a starting value off the grid): the row of f stays byte for byte and is counted in off_grid;
+ *   otherwise, for every local item j,
+ *     g    = fstar[k_i, j] - mu_star[k_i, j]      one fp64 subtraction; mu_star is the one draw_fstar added, still in place
+ *     f_ij = g                                    nugget = 0
+ *     f_ij = g + sd_j z_ij                        nugget = 1: one multiplication, one addition, no FMA
+ *   sd_j = a_j 0.031622776601683794 (the correctly rounded sqrt(GPIRT_JITTER); a_j the item's amplitude, 1.0 exactly when
+ *   amplitudes are off), z_ij = qnorm(item_uniform(seed, iter + 1, GPIRT_ST_CARRY, item0 + j, i)) with iter the completed
+ *   iterations: what gpirt_item_normals(h, seed, iter + 1, 11, item0, m, n, .) writes at [i + j n].
+ * All respondents are carried, moved or not.  A non-finite fstar cell is carried as draw_fstar left it and counted in
+ * nonfinite.  One writer per cell, integer atomics for the two counters alone: two runs give a byte-identical f.  Given the
+ * curve on the grid, theta's draw is the reference's own; f becomes that curve at the new theta plus the model's nugget.  Exact
+ * up to two named approximations: f* is the reference's conditional mean plus independent noise of sd s = 1 - sqrt(q), about
+ * 1e-6 (quirk Q2), not a joint draw; and the nugget is redrawn from its prior (sd 0.03 logits), not tilted by the likelihood.
+ * The next draw_f is an exact update of f | theta, y.  nugget = 0 leaves a smooth f WITHOUT the jitter's share: its quadratic
+ * form is some 30 times too small; it is there for measurements, not as a step to run.
+ * Refused (GPIRT_E_ARG, the reason in gpirt_last_error): before gpirt_sampler_init; GPIRT_RNG_RSTREAM (R's stream has no such
+ * draw); nugget other than 0 or 1.  Item shards are NOT refused: the normals are keyed by the global item and a shard holds its
+ * own columns of fstar, so a shard's columns come out bit for bit as the whole sampler's.
+ *
+ * gpirt_sampler_step_consistent(s, nugget): gpirt_sampler_step with the carry between theta_finish and draw_beta -- draw_f,
+ * draw_fstar, theta_partial, theta_finish, carry, draw_beta, factor -- bit for bit those seven stage calls.  The carry runs on
+ * the main stream in front of the (possibly held-back) draw_beta, which reads the carried f; L and theta are not touched, so
+ * nothing cached from the factor goes stale, and the structured paths (which read f at draw_f and draw_fstar only) run as under
+ * gpirt_sampler_step.  With gpirt_sampler_enable_timing on, gpirt_sampler_stage_times reports its six stages as before and the
+ * carry's device time is gpirt_carry.last_ms, the seventh.
+ *
+ * gpirt_sampler_carry_stats: the counters (one 32-byte read and a stream synchronisation).
+ *
+ * gpirt_sampler_prior_quad(s, h_q): m doubles, q_j = || L^-1 f_j ||^2 for the sampler's current L and f -- the prior check.
+ * q_j / (n a_j^2) near 1 says that f_j looks like a draw from its prior N(0, a_j^2 S) at the theta L belongs to.  It settles
+ * the factor as the length-scale update does, replaces a structured factor by the dense one (gpirt_sampler_dense_factor_count
+ * moves by one then, and later structured products read the dense factor's parts: equal to rounding, not bit for bit), copies f
+ * to scratch, runs the forward solve there and one reduction (thread t of 256 takes rows t, t + 256, ... ascending, then a fixed
+ * tree: no atomics).  f, theta, beta and the iteration counter are untouched and nothing is drawn. */
+typedef struct gpirt_carry {
+    int64_t  calls;                         /* carries over the sampler's life (stage calls and consistent steps) */
+    int64_t  off_grid, nonfinite;           /* of the last call: rows kept (theta not a grid point), non-finite fstar cells carried */
+    int64_t  total_off_grid, total_nonfinite;   /* the same summed over the sampler's life */
+    double   last_ms;                       /* device time of the last carry with gpirt_sampler_enable_timing on, else 0 */
+    int64_t  reserved[4];
+} gpirt_carry;
+int gpirt_sampler_carry_f(gpirt_sampler_t s, int nugget);
+int gpirt_sampler_step_consistent(gpirt_sampler_t s, int nugget);
+int gpirt_sampler_carry_stats(gpirt_sampler_t s, gpirt_carry* out);
+int gpirt_sampler_prior_quad(gpirt_sampler_t s, double* h_q);
 
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint

@@ -13,6 +13,11 @@ DESIGN.md section 34.)
       update, 600 times, for the whitened and the centred update each from the grid's middle.  step() reuses f after theta has
       moved (the reference's quirk Q3), so f is not the GP's value at the current theta; with theta fixed it is.
       Per kind: the index at the start, after a third of the run and at the end, its range over the last third, the acceptance.
+  python tools/ell_mix.py --consistent --out profiles/ell_mix_consistent.json
+      the three modes again with ell.run(consistent=True): every iteration is Sampler.step(consistent=True), which carries f to
+      the new theta with the model's nugget (gpirt_amd.consistent) -- the state the centred update's prior density assumes.
+      Per mode also Q: one more chain of the same configuration (the first chain's seed, the starting width, no retuning)
+      driven by hand, with the mean over items of Sampler.prior_quad() every 50 steps and the index beside it.
 """
 import argparse
 import json
@@ -22,6 +27,32 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def q_probe(args, y, rank, mode, every=50):
+    """Q = prior_quad().mean() and the index every `every` steps of one hand-driven chain of ell.run's configuration"""
+    import numpy as np
+    from gpirt_amd import Sampler, _lib, chains as CH, ell as E
+    from gpirt_amd.ops import Handle
+    g = E.grid(args.lo, args.hi, args.points)
+    k0 = int(np.argmin(np.abs(np.log(g))))
+    h = Handle(0, kernel=dict(family="se", length_scale=float(g[k0])))
+    s = Sampler(h, y, CH.default_inits(args.n, 1, args.seed)[0], seed=args.seed, rng="item", theta_stabilise=True, fstar_fused=True,
+                kstar_rank=rank)
+    s.init()
+    s.ell_enable(args.lo, args.hi, args.points, None, args.width, k0)
+    kinds = {"whitened": ("whitened",), "centred": ("centred",), "both": _lib.ELL_KINDS}[mode]
+    out = []
+    for it in range(1, args.burn + args.samples + 1):
+        s.step(consistent=args.consistent)
+        for kd in kinds:
+            s.draw_ell(kd)
+        if it % every == 0:
+            out.append(dict(step=it, Q=float(s.prior_quad().mean()), index=int(s.ell()["index"])))
+    s.check()
+    s.close()
+    h.close()
+    return out
 
 
 def main():
@@ -38,6 +69,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--modes", default="whitened,centred,both")
     ap.add_argument("--fixed-theta", type=int, default=0)
+    ap.add_argument("--consistent", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -47,7 +79,7 @@ def main():
     y, _ = make_responses(args.n, args.m, seed=20240)
     rank = K.fast_rank(dict(family="se", length_scale=args.lo))
     rec = dict(n=args.n, m=args.m, grid=dict(lo=args.lo, hi=args.hi, points=args.points), width_start=args.width, chains=args.chains,
-               samples=args.samples, burn=args.burn, seed=args.seed, kstar_rank=rank, modes={})
+               samples=args.samples, burn=args.burn, seed=args.seed, kstar_rank=rank, consistent=bool(args.consistent), modes={})
     if args.fixed_theta:
         from gpirt_amd import Sampler
         from gpirt_amd.ops import Handle
@@ -79,7 +111,7 @@ def main():
     for mode in [v for v in args.modes.split(",") if v]:
         t0 = time.perf_counter()
         res = E.run(y, args.samples, args.burn, chains=args.chains, seed=args.seed, lo=args.lo, hi=args.hi, points=args.points,
-                    width=args.width, update=mode, store_draws=False)
+                    width=args.width, update=mode, store_draws=False, consistent=args.consistent)
         wall = time.perf_counter() - t0
         e = res["ell"]
         per_kind = (lambda v: {"whitened": v}) if mode == "whitened" else (lambda v: v)
@@ -90,6 +122,8 @@ def main():
                                   index_first=[int(v) for v in idx[:, 0]], index_last=[int(v) for v in idx[:, -1]],
                                   index_min=int(idx.min()), index_max=int(idx.max()), distinct_indices=int(np.unique(idx).size),
                                   wall_s=wall, ess_per_s=e["ess"] / wall if np.isfinite(e["ess"]) else None)
+        if args.consistent:
+            rec["modes"][mode]["prior_quad"] = q_probe(args, y, rank, mode)
         print(mode, json.dumps(rec["modes"][mode], default=float), flush=True)
     txt = json.dumps(rec, indent=1, default=float)
     if args.out:
