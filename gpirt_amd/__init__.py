@@ -16,6 +16,8 @@ Layout:
                    NumPy statement of one update, the exact conditional posterior per item, the one-call run
   consistent.py    the consistent step beside the reference's (f carried to the new theta plus the model's nugget) and the
                    prior check: the NumPy statement of the carry, the device's normals, the exact prior quadratic form
+  pop.py           a population prior for theta, a table per group, fixed or with the groups' means and sds sampled by exact
+                   Gibbs on two grids: the NumPy statement of one update, the exact conditional masses, the one-call run
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

@@ -533,6 +533,21 @@ class Carry(C.Structure):
     _fields_ = [(k, C.c_int64) for k in CARRY_COUNTS] + [("last_ms", C.c_double), ("reserved", C.c_int64 * 4)]
 
 
+# the population prior for theta (include/gpirt_hip.h gpirt_pop; gpirt_amd.pop)
+ST_POP = 12                       # the two uniforms per group of a population-prior update: item index g, index 0 (mu) / 1 (sd)
+POP_MAX_GROUPS, POP_MAX_POINTS = 8, 1024
+POP_SD_MIN, POP_SD_MAX = 0.05, 10.0
+POP_COUNTS = ("updates", "updated", "skipped", "failed")                   # the rows of pop_get("counts")
+POP_MODES = (None, "fixed", "sampled")
+
+
+class Pop(C.Structure):
+    """gpirt_pop (include/gpirt_hip.h): the mode, the sizes, the totals over the groups and the last call's off-grid members."""
+    _fields_ = [(k, C.c_int64) for k in ("on", "groups", "n", "points_mu", "points_sd", "calls") + POP_COUNTS + (
+        "off_grid", "planned_draws", "recorded")] + [(k, C.c_double) for k in ("mu_hi", "sd_lo", "sd_hi", "last_ms")] + [
+        ("reserved", C.c_int64 * 4)]
+
+
 TICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _vp, _i64, _i32, _u64, _u32, _dbl = C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_double
@@ -772,6 +787,19 @@ SIGNATURES = {
     "gpirt_sampler_amp_record": (_i32, [_vp]),
     "gpirt_sampler_amp_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_amp_stats": (_i32, [_vp, C.POINTER(Amp)]),
+    "gpirt_pop_check": (_i32, [C.POINTER(C.c_int32), _i64, _i32, _dp, _i64, _i32, _dbl, _i32, _dbl, _dbl, _i32, _dp, _dp,
+                               C.POINTER(_i32), C.POINTER(_i32), C.POINTER(Options)]),
+    "gpirt_pop_default_row": (_i32, [_dp]),
+    "gpirt_pop_normal_row": (_i32, [_dbl, _dbl, _dp]),
+    "gpirt_pop_grids": (_i32, [_dbl, _i32, _dbl, _dbl, _i32, _dp, _dp]),
+    "gpirt_pop_lse": (_i32, [_dp, _i32, _dp, _i32, _dp]),
+    "gpirt_sampler_pop_set": (_i32, [_vp, C.POINTER(C.c_int32), _i32, _dp]),
+    "gpirt_sampler_pop_enable": (_i32, [_vp, C.POINTER(C.c_int32), _i32, _dp, _dbl, _i32, _dbl, _dbl, _i32, _dp, _dp,
+                                        C.POINTER(_i32), C.POINTER(_i32), _i64, _i32]),
+    "gpirt_sampler_draw_pop": (_i32, [_vp]),
+    "gpirt_sampler_pop_record": (_i32, [_vp]),
+    "gpirt_sampler_pop_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_pop_stats": (_i32, [_vp, C.POINTER(Pop)]),
     "gpirt_sampler_carry_f": (_i32, [_vp, _i32]),
     "gpirt_sampler_step_consistent": (_i32, [_vp, _i32]),
     "gpirt_sampler_carry_stats": (_i32, [_vp, C.POINTER(Carry)]),

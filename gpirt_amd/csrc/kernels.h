@@ -76,6 +76,29 @@ int launch_amp_update(hipStream_t st, const AmpUpdateArgs& a);
 // draws[slot, j] = idx[j] (planned x m, row-major), hist[idx[j], j] += 1 (P x m, row-major)
 int launch_amp_record(hipStream_t st, const int* idx, int64_t m, int P, int64_t slot, uint32_t* hist, int32_t* draws);
 int amp_nearest_one(const double* grid, int P);                     // the grid point nearest 1 in log a (the first of a tie)
+// pop.hip: the population prior for theta (gpirt_sampler_pop_*): group means and sds on two grids, and the host tables
+struct PopUpdateArgs {
+    const long long* stats;                                             // 4 x G, row-major: n_g, S1, S2, off_grid of this call
+    const double* mu; const double* sd; int P_mu, P_sd;                 // the grids
+    const double* hyper_mu; const double* hyper_sd; const double* lse;  // P_mu, P_sd, P_mu x P_sd (row-major)
+    int* idx;                                                           // 2 x G: (a_g, b_g) pairs; group 0's are -1
+    double* lp_mu; double* lp_sd;                                       // G x P_mu, G x P_sd: the last call's rows
+    double* log_prior;                                                  // G x N: row g rebuilt
+    long long* counts;                                                  // 4 x G, row-major: calls, updated, skipped, failed
+    int G, N;
+    uint64_t seed; uint32_t t;
+};
+// stats[0 .. 4G) (zeroed here) from theta's grid indices: integer atomics alone, so any order gives the same bits
+int launch_pop_stats(hipStream_t st, const double* theta, const int32_t* codes, int64_t n, int G, long long* stats);
+// one exact Gibbs update of (mu_g, sd_g) for every group g >= 1: one work-group of 256 threads per group
+int launch_pop_update(hipStream_t st, const PopUpdateArgs& a);
+// draws[slot, g] = (a_g, b_g) (planned x 2G int32), hist_mu[a_g, g] += 1 (P_mu x G), hist_sd[b_g, g] += 1 (P_sd x G)
+int launch_pop_record(hipStream_t st, const int* idx, int G, int P_mu, int P_sd, int64_t slot, uint32_t* hist_mu, uint32_t* hist_sd,
+                      int32_t* draws);
+void pop_default_row(double* row);                                  // the N(0, 1) row as theta_sample_kernel forms it: its bits
+void pop_normal_row(double mu, double sd, double* row);             // -(0.5 z z), z = (t_k - mu) / sd: the update kernel's bits
+void pop_grids_fill(double mu_hi, int P_mu, double sd_lo, double sd_hi, int P_sd, double* mu, double* sd);
+void pop_lse_fill(const double* mu, int P_mu, const double* sd, int P_sd, double* lse);     // long double, rounded once
 // carry.hip: the consistent step's carry stage (gpirt_sampler_carry_f) and the prior check's reduction (gpirt_sampler_prior_quad)
 struct CarryArgs {
     double* f; const double* theta; const double* fstar; const double* mu_star; int64_t n, m, N;       // f: n x m; fstar, mu_star: N x m
@@ -340,6 +363,8 @@ struct ThetaArgs {
     uint64_t seed; uint32_t iter;
     const double* U; uint64_t* pos; uint64_t cap;  // R-stream replay when U != null
     double* theta_out; int* degenerate; int* err;
+    // the population prior (pop.hip): a G x N table of log masses and one code per respondent; both null: N(0, 1) as before
+    const double* log_prior; const int32_t* codes;
 };
 int launch_theta_sample(hipStream_t stream, const ThetaArgs& a);
 

@@ -82,6 +82,27 @@ struct AmpState {
     double last_ms = 0.0;
 };
 
+// The population prior for theta (gpirt_sampler_pop_set / gpirt_sampler_pop_enable; include/gpirt_hip.h, pop.hip).  mode 0: off
+// (draw_theta adds N(0, 1) in the kernel it always ran), 1: a fixed table, 2: the groups' means and sds on two grids.  The
+// indices, statistics, counters and rows live on the device: an update is two launches and no host read.
+struct PopState {
+    int mode = 0;
+    int G = 0, P_mu = 0, P_sd = 0;
+    int64_t planned = 0, recorded = 0;
+    uint32_t t = 0;                   // draw_pop calls so far (it survives enabling again: no pair of uniforms is replayed)
+    double mu_hi = 0.0, sd_lo = 0.0, sd_hi = 0.0;
+    std::vector<double> mu, sd, lse, hyper_mu, hyper_sd;
+    int32_t* codes = nullptr;                                                              // device: n
+    double *log_prior = nullptr, *d_mu = nullptr, *d_sd = nullptr, *d_lse = nullptr, *d_hyper_mu = nullptr, *d_hyper_sd = nullptr,
+           *lp_mu = nullptr, *lp_sd = nullptr;                    // device: G x N, P_mu, P_sd, P_mu x P_sd, P_mu, P_sd, G x P_mu, G x P_sd
+    int* idx = nullptr;                                                                    // device: G x 2
+    long long *stats = nullptr, *counts = nullptr;                                         // device: 4 x G each
+    uint32_t *hist_mu = nullptr, *hist_sd = nullptr;                                       // device: P_mu x G, P_sd x G
+    int32_t* draws = nullptr;                                                              // device: planned x G x 2
+    hipEvent_t tev[2] = {};           // with gpirt_sampler_enable_timing on: around the two launches of the last draw_pop
+    double last_ms = 0.0;
+};
+
 // The consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad; include/gpirt_hip.h,
 // carry.hip).  Both buffers are allocated by the first call that needs them: a sampler that never calls either has neither.
 struct CarryState {
@@ -244,7 +265,8 @@ struct gpirt_sampler_s {
     GroupsState groups;               // group posteriors (gpirt_sampler_groups_enable; on == false: off)
     EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
     AmpState amp;                     // per-item GP amplitudes (gpirt_sampler_amp_set, gpirt_sampler_amp_enable; mode == 0: off)
-    CarryState carry;                 // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
+    PopState pop;                     // the population prior for theta (gpirt_sampler_pop_set, gpirt_sampler_pop_enable; mode == 0: off)
+    CarryState carry;               // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
 };
 
 namespace {
@@ -934,6 +956,7 @@ int do_theta_finish(gpirt_sampler_s* s)
     a.seed = s->opt.seed; a.iter = (uint32_t)(s->iter + 1);
     a.theta_out = s->theta; a.degenerate = s->flags + 1; a.err = s->flags;
     if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.cap = s->U_cap; }
+    if (s->pop.mode) { a.log_prior = s->pop.log_prior; a.codes = s->pop.codes; }           // (the group's row in place of N(0, 1))
     GP_TRY(launch_theta_sample(st, a));
     if (stream_mode(s)) GP_TRY(launch_advance_pos(st, s->pos, (uint64_t)s->n));
     s->theta_ok = true;                   // grid values
@@ -1266,6 +1289,19 @@ void amp_free(AmpState* a)
     const uint32_t calls = a->t;      // the sampler's draw_amp calls: enabling again does not replay their uniforms
     *a = AmpState();
     a->t = calls;
+}
+
+// ---- the population prior for theta (include/gpirt_hip.h; the kernels are pop.hip's) -------------------------------------------
+void pop_free(PopState* p)
+{
+    for (void* q : { (void*)p->codes, (void*)p->log_prior, (void*)p->d_mu, (void*)p->d_sd, (void*)p->d_lse, (void*)p->d_hyper_mu,
+                     (void*)p->d_hyper_sd, (void*)p->lp_mu, (void*)p->lp_sd, (void*)p->idx, (void*)p->stats, (void*)p->counts,
+                     (void*)p->hist_mu, (void*)p->hist_sd, (void*)p->draws })
+        if (q) hipFree(q);
+    for (hipEvent_t t : p->tev) if (t) hipEventDestroy(t);
+    const uint32_t calls = p->t;      // the sampler's draw_pop calls: enabling again does not replay their uniforms
+    *p = PopState();
+    p->t = calls;
 }
 
 // The main stream waits for whatever the sampler's own stream still has in flight -- the early block inverses read L, a
@@ -1993,6 +2029,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     score_free(&s->score);
     ell_free(&s->ell);
     amp_free(&s->amp);
+    pop_free(&s->pop);
     for (hipEvent_t t : s->carry.tev) if (t) hipEventDestroy(t);      // (its two buffers are in `allocs`)
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
@@ -2113,6 +2150,10 @@ int gpirt_sampler_set_theta_block(gpirt_sampler_t s, const double* y_block, int6
     GP_ARG(s && (y_block || n_block == 0) && i0 >= 0 && n_block >= 0 && i0 + n_block <= s->n && m_total >= s->m);
     if (stream_mode(s)) { set_error("the R-stream replay cannot be sharded"); return GPIRT_E_ARG; }
     if (s->fstar_full) { set_error("the theta block is already set"); return GPIRT_E_ARG; }
+    if (s->pop.mode) {
+        set_error("gpirt_sampler_set_theta_block is refused while a population prior is on: the block path would need the codes of its respondents");
+        return GPIRT_E_ARG;
+    }
     const int64_t N = s->N, Np = (N + 127) / 128 * 128;
     int rc = 0;
     double* yb = nullptr;
@@ -3328,6 +3369,246 @@ int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out)
     return 0;
 }
 
+// ---- the population prior for theta --------------------------------------------------------------------------------------------
+static int pop_refusals(gpirt_sampler_t s, const char* entry)
+{
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", entry); return GPIRT_E_ARG; }
+    if (s->fstar_full) {
+        set_error("%s is refused while gpirt_sampler_set_theta_block is in use: the block path would need the codes of its respondents", entry);
+        return GPIRT_E_ARG;
+    }
+    if (s->opt.m_total > 0 && s->opt.m_total != s->m) {
+        set_error("population prior: an item shard (item0 = %lld, m_total = %lld) is refused, the respondent-block theta path "
+                  "would need the codes of its respondents", (long long)s->opt.item0, (long long)s->opt.m_total);
+        return GPIRT_E_ARG;
+    }
+    return 0;
+}
+
+int gpirt_sampler_pop_set(gpirt_sampler_t s, const int32_t* codes, int G, const double* log_prior)
+{
+    GP_ARG(s != nullptr);
+    PopState& A = s->pop;
+    if (!codes) {
+        if (A.mode == 2) { set_error("gpirt_sampler_pop_set(NULL): the population prior is sampled, gpirt_sampler_pop_enable(on = 0) turns it off"); return GPIRT_E_ARG; }
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        pop_free(&A);
+        return 0;
+    }
+    if (A.mode == 2) {
+        set_error("gpirt_sampler_pop_set after gpirt_sampler_pop_enable: turn the sampled population prior off first (on = 0)");
+        return GPIRT_E_ARG;
+    }
+    GP_ARG(log_prior != nullptr);
+    GP_TRY(pop_refusals(s, "gpirt_sampler_pop_set"));
+    const int64_t n = s->n, N = s->N;
+    GP_TRY(gpirt_pop_check(codes, n, G, log_prior, G, 0, 0.0, 0, 0.0, 0.0, 0, nullptr, nullptr, nullptr, nullptr, &s->opt));
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipStreamSynchronize(st));
+    pop_free(&A);
+    if (hipMalloc((void**)&A.codes, sizeof(int32_t) * (size_t)n) != hipSuccess ||
+        hipMalloc((void**)&A.log_prior, sizeof(double) * (size_t)G * (size_t)N) != hipSuccess) {
+        set_error("population prior: hipMalloc failed");
+        pop_free(&A);
+        return GPIRT_E_ALLOC;
+    }
+    if (hipMemcpyAsync(A.codes, codes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.log_prior, log_prior, sizeof(double) * (size_t)G * (size_t)N, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        set_error("population prior: the upload failed");
+        pop_free(&A);
+        return GPIRT_E_HIP;
+    }
+    A.G = G;
+    A.mode = 1;
+    return 0;
+}
+
+int gpirt_sampler_pop_enable(gpirt_sampler_t s, const int32_t* codes, int G, const double* anchor_row, double mu_hi, int P_mu,
+                             double sd_lo, double sd_hi, int P_sd, const double* log_hyper_mu, const double* log_hyper_sd,
+                             const int* a0, const int* b0, int64_t planned_draws, int on)
+{
+    GP_ARG(s != nullptr);
+    PopState& A = s->pop;
+    if (!on) {
+        if (A.mode == 1) { set_error("gpirt_sampler_pop_enable(on = 0): the population prior is fixed, gpirt_sampler_pop_set(NULL) turns it off"); return GPIRT_E_ARG; }
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        pop_free(&A);
+        return 0;
+    }
+    if (A.mode == 1) {
+        set_error("gpirt_sampler_pop_enable after gpirt_sampler_pop_set: turn the fixed population prior off first (gpirt_sampler_pop_set(NULL))");
+        return GPIRT_E_ARG;
+    }
+    GP_ARG(codes != nullptr);
+    GP_TRY(pop_refusals(s, "gpirt_sampler_pop_enable"));
+    const int64_t n = s->n, N = s->N;
+    GP_TRY(gpirt_pop_check(codes, n, G, anchor_row, anchor_row ? 1 : 0, 1, mu_hi, P_mu, sd_lo, sd_hi, P_sd, log_hyper_mu, log_hyper_sd,
+                           a0, b0, &s->opt));
+    if (planned_draws < 0 || planned_draws > (int64_t)1 << 31) {
+        set_error("population prior: planned_draws = %lld, it must lie in 0 .. 2^31", (long long)planned_draws);
+        return GPIRT_E_ARG;
+    }
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipStreamSynchronize(st));
+    pop_free(&A);
+    auto fail = [&](int rc, const char* what) { set_error("population prior: %s failed", what); pop_free(&A); return rc; };
+    const size_t Gs = (size_t)G, Pm = (size_t)P_mu, Ps = (size_t)P_sd;
+    const size_t draw_bytes = sizeof(int32_t) * (size_t)(planned_draws ? planned_draws : 1) * 2 * Gs;
+    if (hipMalloc((void**)&A.codes, sizeof(int32_t) * (size_t)n) != hipSuccess ||
+        hipMalloc((void**)&A.log_prior, sizeof(double) * Gs * (size_t)N) != hipSuccess ||
+        hipMalloc((void**)&A.d_mu, sizeof(double) * Pm) != hipSuccess ||
+        hipMalloc((void**)&A.d_sd, sizeof(double) * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.d_lse, sizeof(double) * Pm * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.d_hyper_mu, sizeof(double) * Pm) != hipSuccess ||
+        hipMalloc((void**)&A.d_hyper_sd, sizeof(double) * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.lp_mu, sizeof(double) * Gs * Pm) != hipSuccess ||
+        hipMalloc((void**)&A.lp_sd, sizeof(double) * Gs * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.idx, sizeof(int) * 2 * Gs) != hipSuccess ||
+        hipMalloc((void**)&A.stats, sizeof(long long) * 4 * Gs) != hipSuccess ||
+        hipMalloc((void**)&A.counts, sizeof(long long) * 4 * Gs) != hipSuccess ||
+        hipMalloc((void**)&A.hist_mu, sizeof(uint32_t) * Pm * Gs) != hipSuccess ||
+        hipMalloc((void**)&A.hist_sd, sizeof(uint32_t) * Ps * Gs) != hipSuccess ||
+        hipMalloc((void**)&A.draws, draw_bytes) != hipSuccess) return fail(GPIRT_E_ALLOC, "hipMalloc");
+    A.G = G; A.P_mu = P_mu; A.P_sd = P_sd; A.planned = planned_draws; A.recorded = 0;
+    A.mu_hi = mu_hi; A.sd_lo = sd_lo; A.sd_hi = sd_hi;
+    A.mu.resize(Pm); A.sd.resize(Ps); A.lse.resize(Pm * Ps);
+    A.hyper_mu.assign(Pm, 0.0); A.hyper_sd.assign(Ps, 0.0);
+    pop_grids_fill(mu_hi, P_mu, sd_lo, sd_hi, P_sd, A.mu.data(), A.sd.data());
+    pop_lse_fill(A.mu.data(), P_mu, A.sd.data(), P_sd, A.lse.data());
+    if (log_hyper_mu) A.hyper_mu.assign(log_hyper_mu, log_hyper_mu + Pm);
+    if (log_hyper_sd) A.hyper_sd.assign(log_hyper_sd, log_hyper_sd + Ps);
+    const int near1 = amp_nearest_one(A.sd.data(), P_sd);
+    std::vector<int> idx(2 * Gs, -1);
+    std::vector<double> table(Gs * (size_t)N);
+    if (anchor_row) memcpy(table.data(), anchor_row, sizeof(double) * (size_t)N);
+    else pop_default_row(table.data());
+    for (int g = 1; g < G; ++g) {
+        const int a = a0 ? a0[g] : (P_mu - 1) / 2, b = b0 ? b0[g] : near1;
+        idx[2 * (size_t)g] = a; idx[2 * (size_t)g + 1] = b;
+        pop_normal_row(A.mu[(size_t)a], A.sd[(size_t)b], table.data() + (size_t)g * (size_t)N);
+    }
+    if (hipMemcpyAsync(A.codes, codes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.log_prior, table.data(), sizeof(double) * Gs * (size_t)N, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_mu, A.mu.data(), sizeof(double) * Pm, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_sd, A.sd.data(), sizeof(double) * Ps, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_lse, A.lse.data(), sizeof(double) * Pm * Ps, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_hyper_mu, A.hyper_mu.data(), sizeof(double) * Pm, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_hyper_sd, A.hyper_sd.data(), sizeof(double) * Ps, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.idx, idx.data(), sizeof(int) * 2 * Gs, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(A.lp_mu, 0, sizeof(double) * Gs * Pm, st) != hipSuccess ||
+        hipMemsetAsync(A.lp_sd, 0, sizeof(double) * Gs * Ps, st) != hipSuccess ||
+        hipMemsetAsync(A.stats, 0, sizeof(long long) * 4 * Gs, st) != hipSuccess ||
+        hipMemsetAsync(A.counts, 0, sizeof(long long) * 4 * Gs, st) != hipSuccess ||
+        hipMemsetAsync(A.hist_mu, 0, sizeof(uint32_t) * Pm * Gs, st) != hipSuccess ||
+        hipMemsetAsync(A.hist_sd, 0, sizeof(uint32_t) * Ps * Gs, st) != hipSuccess ||
+        hipMemsetAsync(A.draws, 0, draw_bytes, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return fail(GPIRT_E_HIP, "the upload");      // (the host vectors go out of scope)
+    A.mode = 2;
+    return 0;
+}
+
+int gpirt_sampler_draw_pop(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    PopState& A = s->pop;
+    GP_TRY(needs(A.mode == 2, "the population prior's update is", "gpirt_sampler_pop_enable"));
+    PopUpdateArgs a{};
+    a.stats = A.stats; a.mu = A.d_mu; a.sd = A.d_sd; a.P_mu = A.P_mu; a.P_sd = A.P_sd;
+    a.hyper_mu = A.d_hyper_mu; a.hyper_sd = A.d_hyper_sd; a.lse = A.d_lse;
+    a.idx = A.idx; a.lp_mu = A.lp_mu; a.lp_sd = A.lp_sd; a.log_prior = A.log_prior; a.counts = A.counts;
+    a.G = A.G; a.N = (int)s->N; a.seed = s->opt.seed; a.t = A.t + 1;
+    hipStream_t st = s->h->stream;              // (theta is written on this stream alone; nothing else writes the table)
+    const bool timed = s->timing;
+    if (timed) {
+        for (hipEvent_t& t : A.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(A.tev[0], st));
+    }
+    GP_TRY(launch_pop_stats(st, s->theta, A.codes, s->n, A.G, A.stats));
+    GP_TRY(launch_pop_update(st, a));
+    A.t += 1;
+    if (timed) {                              // (timing on: one synchronisation, as the amplitude update's)
+        GP_HIP(hipEventRecord(A.tev[1], st));
+        GP_HIP(hipEventSynchronize(A.tev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, A.tev[0], A.tev[1]);
+        A.last_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_pop_record(gpirt_sampler_t s)
+{
+    GP_ARG(s != nullptr);
+    PopState& A = s->pop;
+    GP_TRY(needs(A.mode == 2, "the population prior's update is", "gpirt_sampler_pop_enable"));
+    if (A.recorded >= A.planned) {
+        set_error("population prior: all %lld planned draws are recorded", (long long)A.planned);
+        return GPIRT_E_ARG;
+    }
+    GP_TRY(launch_pop_record(s->h->stream, A.idx, A.G, A.P_mu, A.P_sd, A.recorded, A.hist_mu, A.hist_sd, A.draws));
+    A.recorded += 1;
+    return 0;
+}
+
+int gpirt_sampler_pop_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    PopState& A = s->pop;
+    GP_TRY(needs(A.mode != 0, "a population prior is", "gpirt_sampler_pop_set, gpirt_sampler_pop_enable"));
+    const int64_t n = s->n, N = s->N, G = A.G, Pm = A.P_mu, Ps = A.P_sd;
+    const void* host = nullptr; const void* dev = nullptr; int64_t want = 0;
+    const bool both = strcmp(name, "codes") == 0 || strcmp(name, "log_prior") == 0;
+    if (!both) GP_TRY(needs(A.mode == 2, "the population prior's update is", "gpirt_sampler_pop_enable"));
+    if (strcmp(name, "codes") == 0) { dev = A.codes; want = 4 * n; }
+    else if (strcmp(name, "log_prior") == 0) { dev = A.log_prior; want = 8 * G * N; }
+    else if (strcmp(name, "mu_grid") == 0) { host = A.mu.data(); want = 8 * Pm; }
+    else if (strcmp(name, "sd_grid") == 0) { host = A.sd.data(); want = 8 * Ps; }
+    else if (strcmp(name, "lse") == 0) { host = A.lse.data(); want = 8 * Pm * Ps; }
+    else if (strcmp(name, "log_hyper_mu") == 0) { host = A.hyper_mu.data(); want = 8 * Pm; }
+    else if (strcmp(name, "log_hyper_sd") == 0) { host = A.hyper_sd.data(); want = 8 * Ps; }
+    else if (strcmp(name, "index") == 0) { dev = A.idx; want = 8 * G; }
+    else if (strcmp(name, "stats") == 0) { dev = A.stats; want = 24 * G; }
+    else if (strcmp(name, "off_grid") == 0) { dev = A.stats + 3 * G; want = 8 * G; }
+    else if (strcmp(name, "lp_mu") == 0) { dev = A.lp_mu; want = 8 * G * Pm; }
+    else if (strcmp(name, "lp_sd") == 0) { dev = A.lp_sd; want = 8 * G * Ps; }
+    else if (strcmp(name, "counts") == 0) { dev = A.counts; want = 32 * G; }
+    else if (strcmp(name, "hist_mu") == 0) { dev = A.hist_mu; want = 4 * Pm * G; }
+    else if (strcmp(name, "hist_sd") == 0) { dev = A.hist_sd; want = 4 * Ps * G; }
+    else if (strcmp(name, "draws") == 0) { dev = A.draws; want = 8 * A.recorded * G; }
+    else if (strcmp(name, "time") == 0) { host = &A.last_ms; want = 8; }
+    else { set_error("unknown population-prior array '%s'", name); return GPIRT_E_ARG; }
+    if (bytes != want) { set_error("population prior: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    if (want == 0) return 0;
+    if (host) { memcpy(h_out, host, (size_t)want); return 0; }
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_pop_stats(gpirt_sampler_t s, gpirt_pop* out)
+{
+    GP_ARG(s && out);
+    const PopState& A = s->pop;
+    memset(out, 0, sizeof(*out));
+    out->on = A.mode; out->groups = A.G; out->n = s->n; out->calls = A.t;
+    out->mu_hi = out->sd_lo = out->sd_hi = (double)NAN;
+    if (A.mode != 2) return 0;
+    const size_t G = (size_t)A.G;
+    std::vector<long long> cnt(4 * G), stats(4 * G);
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(cnt.data(), A.counts, sizeof(long long) * 4 * G, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipMemcpyAsync(stats.data(), A.stats, sizeof(long long) * 4 * G, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    out->points_mu = A.P_mu; out->points_sd = A.P_sd; out->planned_draws = A.planned; out->recorded = A.recorded;
+    out->mu_hi = A.mu_hi; out->sd_lo = A.sd_lo; out->sd_hi = A.sd_hi; out->last_ms = A.last_ms;
+    for (size_t g = 0; g < G; ++g) {
+        out->updates += cnt[g]; out->updated += cnt[G + g]; out->skipped += cnt[2 * G + g]; out->failed += cnt[3 * G + g];
+        out->off_grid += stats[3 * G + g];
+    }
+    return 0;
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -3539,6 +3820,10 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     }
     if (dst->amp.mode || src->amp.mode) {
         set_error("gpirt_sampler_copy_state is not defined while per-item amplitudes are on (they are not copied)");
+        return GPIRT_E_ARG;
+    }
+    if (dst->pop.mode || src->pop.mode) {
+        set_error("gpirt_sampler_copy_state is not defined while a population prior is on (it is not copied)");
         return GPIRT_E_ARG;
     }
     if (dst->kern.family != src->kern.family || dst->kern.length_scale != src->kern.length_scale) {

@@ -174,6 +174,8 @@ __global__ void theta_nan_fix_kernel(const double* __restrict__ Gpm, int64_t ldg
 }
 
 // one work-group per respondent; 256 threads x 4 consecutive grid points cover N <= 1024
+// POP: the prior is row codes[i] of the table log_prior (pop.hip) in place of N(0, 1); everything behind that line is shared
+template <bool POP>
 __global__ __launch_bounds__(256) void theta_sample_kernel(ThetaArgs a)
 {
     __shared__ double red[8];
@@ -184,13 +186,19 @@ __global__ __launch_bounds__(256) void theta_sample_kernel(ThetaArgs a)
     const double* lp = a.logpost + ib * a.N;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int N = (int)a.N;
+    const double* prior = nullptr;
+    if (POP) prior = a.log_prior + (int64_t)a.codes[i] * a.N;
     double P[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int k = t * 4 + e;
         if (k < N) {
-            const double ts = -5.0 + (double)k * 0.01;
-            P[e] = r_dnorm_log(ts, 0.0, 1.0) + lp[k];                      // draw-theta.cpp:18
+            if (POP) {
+                P[e] = prior[k] + lp[k];                                    // the group's row: one addition
+            } else {
+                const double ts = -5.0 + (double)k * 0.01;
+                P[e] = r_dnorm_log(ts, 0.0, 1.0) + lp[k];                  // draw-theta.cpp:18
+            }
         } else P[e] = -INFINITY;
     }
     if (a.stabilise) {
@@ -421,7 +429,8 @@ int launch_theta_sample(hipStream_t stream, const ThetaArgs& a)
 {
     if (a.n <= 0) return 0;
     if (a.N > 1024) { set_error("theta grid larger than 1024 points is not supported"); return GPIRT_E_ARG; }
-    hipLaunchKernelGGL(theta_sample_kernel, dim3((unsigned)a.n), dim3(256), 0, stream, a);
+    if (a.log_prior && a.codes) hipLaunchKernelGGL(theta_sample_kernel<true>, dim3((unsigned)a.n), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(theta_sample_kernel<false>, dim3((unsigned)a.n), dim3(256), 0, stream, a);
     GP_HIP(hipGetLastError());
     return 0;
 }

@@ -351,6 +351,19 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: per-item amplitudes are not offered for item shards (the library keeps them for all "
                          "items of one sampler)")
 
+    # -- the population prior for theta (gpirt_amd.pop): the respondent-block theta path would need the codes of its block
+    def pop_set(self, codes, log_prior=None):
+        raise ValueError("ShardedSampler: a population prior is not offered for item shards (the respondent-block theta path "
+                         "would need the codes of its respondents)")
+
+    def pop_enable(self, codes=None, groups=None, **kw):
+        raise ValueError("ShardedSampler: a population prior is not offered for item shards (the respondent-block theta path "
+                         "would need the codes of its respondents)")
+
+    def draw_pop(self):
+        raise ValueError("ShardedSampler: a population prior is not offered for item shards (the respondent-block theta path "
+                         "would need the codes of its respondents)")
+
     # -- scoring new respondents (gpirt_amd.score): the product of a new respondent runs over ALL items
     def score_enable(self, y_new):
         raise ValueError("ShardedSampler: scoring new respondents is not offered for item shards (a new respondent's "

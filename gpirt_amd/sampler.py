@@ -1743,6 +1743,110 @@ class Sampler:
         out["mode"] = _lib.AMP_MODES[int(a.on)]
         return out
 
+    # -- the population prior for theta, fixed or sampled in the chain (include/gpirt_hip.h gpirt_sampler_pop_*, gpirt_amd.pop)
+    def pop_set(self, codes, log_prior=None):
+        """A fixed population prior: one code per respondent in 0 .. G - 1 (every group with a member) and a G x 1001 table of
+        finite log masses on the theta grid (log_prior[g] is group g's prior; it need not be normalised; None: the default
+        N(0, 1) row for every group).  draw_theta adds row codes[i] in place of N(0, 1).  codes=None turns it off.  After init();
+        works under both RNG contracts.  Refused with the reason: an item shard, theta_block in use, while pop_enable is on."""
+        if codes is None:
+            check(self.lib.gpirt_sampler_pop_set(self._s, None, 0, None))
+            self._pop = (0, 0, 0)
+            return
+        from . import pop as PO
+        cd = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+        if cd.shape != (self.n,):
+            raise ValueError(f"pop_set: codes must hold n = {self.n} values")
+        if log_prior is None:
+            G = int(cd.max()) + 1 if cd.size else 1
+            log_prior = np.tile(PO.default_row(), (max(G, 1), 1))
+        lp = np.ascontiguousarray(log_prior, dtype=np.float64)
+        if lp.ndim != 2 or lp.shape[1] != NGRID:
+            raise ValueError(f"pop_set: log_prior must be G x {NGRID}")
+        check(self.lib.gpirt_sampler_pop_set(self._s, cd.ctypes.data_as(C.POINTER(C.c_int32)), lp.shape[0], _ptr(lp)))
+        self._pop = (lp.shape[0], 0, 0)
+
+    def pop_enable(self, codes=None, groups=None, anchor_row=None, mu_hi=3.0, points_mu=121, sd_lo=0.2, sd_hi=5.0, points_sd=65,
+                   log_hyper_mu=None, log_hyper_sd=None, a0=None, b0=None, planned_draws=0, on=True):
+        """A sampled population prior: group 0 is the anchor and keeps anchor_row (1001 finite values; None: the N(0, 1) row),
+        every group g >= 1 has (mu_g, sd_g) on gpirt_amd.pop.grids(mu_hi, points_mu, sd_lo, sd_hi, points_sd) with the
+        hyperprior masses log_hyper_mu / log_hyper_sd (None: flat in mu, flat in log sd) and the start indices a0, b0 (G values
+        each, or one for all; None: mu = 0's point and the sd point nearest 1).  groups: G (None: max(codes) + 1).
+        planned_draws: how many pop_record() calls the draw buffer holds.  After init().  Refused with the reason:
+        rng="reference", an item shard, theta_block in use, while pop_set is on.  on=False frees the state."""
+        if not on:
+            check(self.lib.gpirt_sampler_pop_enable(self._s, None, 0, None, 0.0, 0, 0.0, 0.0, 0, None, None, None, None, 0, 0))
+            self._pop = (0, 0, 0)
+            return
+        cd = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+        if cd.shape != (self.n,):
+            raise ValueError(f"pop_enable: codes must hold n = {self.n} values")
+        G = int(groups) if groups is not None else (int(cd.max()) + 1 if cd.size else 1)
+        Pm, Ps = int(points_mu), int(points_sd)
+
+        def vec(v, size, what):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != (size,):
+                raise ValueError(f"pop_enable: {what} must hold {size} values")
+            return v
+
+        def ints(v):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32), (max(G, 1),)))
+        ar, hm, hs = vec(anchor_row, NGRID, "anchor_row"), vec(log_hyper_mu, Pm, "log_hyper_mu"), vec(log_hyper_sd, Ps, "log_hyper_sd")
+        ia, ib = ints(a0), ints(b0)
+        ip = lambda v: None if v is None else v.ctypes.data_as(C.POINTER(C.c_int))          # noqa: E731
+        dp = lambda v: None if v is None else _ptr(v)                                        # noqa: E731
+        check(self.lib.gpirt_sampler_pop_enable(self._s, cd.ctypes.data_as(C.POINTER(C.c_int32)), G, dp(ar), float(mu_hi), Pm,
+                                                float(sd_lo), float(sd_hi), Ps, dp(hm), dp(hs), ip(ia), ip(ib),
+                                                int(planned_draws), 1))
+        self._pop = (G, Pm, Ps)
+
+    def draw_pop(self):
+        """One exact Gibbs update of every group's (mu_g, sd_g), g >= 1, on the grids and the rebuild of the groups' rows: two
+        launches, nothing is read back (gpirt_amd.pop.step_exact is its NumPy statement)."""
+        self._call("gpirt_sampler_draw_pop")
+
+    def pop_record(self):
+        """Append the current (a_g, b_g) to the draw buffer and add 1 to hist_mu[a_g, g] and hist_sd[b_g, g], on the device."""
+        self._call("gpirt_sampler_pop_record")
+
+    def pop_get(self, name: str) -> np.ndarray:
+        """One array by name: codes (int32, n), log_prior (G x 1001) -- the two a fixed prior knows --, mu_grid, log_hyper_mu
+        (points_mu), sd_grid, log_hyper_sd (points_sd), lse (points_mu x points_sd), index (int32, G x 2: (a_g, b_g), group 0's
+        -1), stats (int64, 3 x G: n_g, S1, S2 of the last draw_pop), off_grid (int64, G), lp_mu (G x points_mu), lp_sd
+        (G x points_sd: the last draw_pop's rows), counts (int64, 4 x G: updates, updated, skipped, failed), hist_mu (uint32,
+        points_mu x G), hist_sd (uint32, points_sd x G), draws (int32, recorded x G x 2), time (1: ms of device time of the last
+        draw_pop with enable_timing() on)."""
+        G, Pm, Ps = getattr(self, "_pop", (0, 0, 0))
+        shapes = {"codes": ((self.n,), np.int32), "log_prior": ((G, NGRID), np.float64), "mu_grid": ((Pm,), np.float64),
+                  "sd_grid": ((Ps,), np.float64), "log_hyper_mu": ((Pm,), np.float64), "log_hyper_sd": ((Ps,), np.float64),
+                  "lse": ((Pm, Ps), np.float64), "index": ((G, 2), np.int32), "stats": ((3, G), np.int64),
+                  "off_grid": ((G,), np.int64), "lp_mu": ((G, Pm), np.float64), "lp_sd": ((G, Ps), np.float64),
+                  "counts": ((4, G), np.int64), "hist_mu": ((Pm, G), np.uint32), "hist_sd": ((Ps, G), np.uint32),
+                  "time": ((1,), np.float64)}
+        if name == "draws":
+            out = np.empty((self.pop_stats()["recorded"], G, 2), dtype=np.int32)
+        else:
+            shape, dt = shapes.get(name, ((0,), np.float64))
+            out = np.empty(shape, dtype=dt)
+        self._get_into("gpirt_sampler_pop_get", name, out)
+        return out
+
+    def pop_stats(self) -> dict:
+        """The population prior's state (gpirt_sampler_pop_stats): mode (None, "fixed" or "sampled"), groups, n, points_mu,
+        points_sd, calls, the counters summed over the groups (updates, updated, skipped, failed), off_grid (members off the grid
+        in the last draw_pop), planned_draws, recorded, mu_hi, sd_lo, sd_hi, time_ms."""
+        p = _lib.Pop()
+        check(self.lib.gpirt_sampler_pop_stats(self._s, C.byref(p)))
+        out = {k: int(getattr(p, k)) for k in ("groups", "n", "points_mu", "points_sd", "calls", "off_grid", "planned_draws",
+                                               "recorded") + _lib.POP_COUNTS}
+        out.update({k: float(getattr(p, k)) for k in ("mu_hi", "sd_lo", "sd_hi")})
+        out["time_ms"] = float(p.last_ms)
+        out["mode"] = _lib.POP_MODES[int(p.on)]
+        return out
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

@@ -56,6 +56,7 @@ enum {
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
+    GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
     GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
@@ -2299,6 +2300,110 @@ int gpirt_sampler_carry_f(gpirt_sampler_t s, int nugget);
 int gpirt_sampler_step_consistent(gpirt_sampler_t s, int nugget);
 int gpirt_sampler_carry_stats(gpirt_sampler_t s, gpirt_carry* out);
 int gpirt_sampler_prior_quad(gpirt_sampler_t s, double* h_q);
+
+/* ------------------------------------------------------ a population prior for theta: group means and sds ------------------ */
+/* Library version 134.  The reference's prior on theta is N(0, 1) for everyone (src/draw-theta.cpp:18).  Here respondent i
+ * carries a group code g_i in 0 .. G - 1, 1 <= G <= GPIRT_POP_MAX_GROUPS, every group has a member and -1 is not allowed, and
+ * group g's prior is a mass on the theta grid t_k = -5 + 0.01 k: row g of a G x GPIRT_NGRID table log_prior (row-major) of finite
+ * doubles.  The table need not be normalised: the constant cancels in :25.  draw_theta becomes
+ *   P[k] = log_prior[g_i, k] + logpost[k, i]            one fp64 addition
+ * and everything behind that line -- the stabilising maximum, exp, the scan, the CDF, the draw, the degenerate count, the one
+ * uniform per respondent -- is as it was (csrc/stages.hip theta_sample_kernel<true>).  A sampler on which neither entry below
+ * was called runs the kernel it ran (theta_sample_kernel<false>), and a sampler whose rows are all the default row
+ * (gpirt_pop_default_row: -(ln sqrt(2 pi) + 0.5 z z), z = |t_k|, the built-in prior's own bits) draws the same bits.
+ * Stage API only: gpirt_options, gpirt_run, gpirt_mcmc* and gpirt_sampler_step keep their layout and behaviour.
+ * WHAT KEEPS READING N(0, 1): score, predict, sumscore and shape's reliability weights read N(0, 1) for new respondents and for
+ * the marginal weights -- group 0's default population.
+ *
+ * gpirt_sampler_pop_set(s, codes, G, log_prior): FIXED.  n codes and a G x GPIRT_NGRID table, any finite table -- a normal per
+ * group (gpirt_pop_normal_row), a mixture, a flat row.  codes = NULL turns it off.  It works under both RNG contracts: theta
+ * consumes the same one uniform per respondent, so R's stream position is unchanged.
+ *
+ * gpirt_sampler_pop_enable: SAMPLED.  Group 0 is the anchor and keeps a fixed row (anchor_row: GPIRT_NGRID finite values; NULL:
+ * the default row), which is what fixes location and scale.  Each group g >= 1 has (mu_g, sd_g) on two grids,
+ *   mu_a = mu_hi (2a - (P_mu - 1)) / (P_mu - 1)            long double, rounded once: antisymmetric bit for bit, so that a
+ *                                                           mirror-mode chain maps index a to P_mu - 1 - a; 0 < mu_hi <= 5
+ *   sd_b = gpirt_ell_grid(sd_lo, sd_hi, P_sd)[b]           logarithmic, the end points exact;
+ *                                                           GPIRT_POP_SD_MIN <= sd_lo < sd_hi <= GPIRT_POP_SD_MAX
+ * with 2 <= P_mu, P_sd <= GPIRT_POP_MAX_POINTS, and its row is log_prior[g, k] = -(0.5 z z), z = (t_k - mu_g) / sd_g, with
+ * t_k = -5.0 + (double)k * 0.01: each of the two products, the sum, the difference, the quotient, 0.5 z and (0.5 z) z rounded on
+ * its own, no contraction and no transcendental.  log_hyper_mu (P_mu finite values) and log_hyper_sd (P_sd) are masses on the
+ * grids; NULL: zeros, i.e. flat in mu and flat in log sd.  a0, b0: G start indices each (entry 0 is not read); NULL: a = (P_mu -
+ * 1) / 2 and the sd point nearest 1 in log sd.  planned_draws sizes the record buffer.  The P_mu x P_sd table
+ *   lse[a, b] = log sum_k exp(-(t_k - mu_a)^2 / (2 sd_b^2))
+ * the grid's normaliser, is formed once on the host in long double (k ascending) and rounded once (gpirt_pop_lse); it is what
+ * makes the update exact for the truncated, discrete prior that draw_theta actually uses.  At P_mu = P_sd = 1024 this is 10^9
+ * long-double exponentials, tens of seconds on one core.  on = 0 frees the state and turns the prior off.
+ *
+ * gpirt_sampler_draw_pop: every group g >= 1 by EXACT GIBBS ON THE GRIDS, with no host read: a reduction launch, then one
+ * launch with one work-group of 256 threads per group.  t counts the draw_pop calls over the sampler's life, from 1.
+ *   1. n_g, S1_g = sum (k_i - 500), S2_g = sum (k_i - 500)^2 over the group's members, int64, from the grid index k_i of theta_i
+ *      (theta_i bit for bit -5 + 0.01 k_i); integer atomics, so the bits do not depend on the order.  A member whose theta is no
+ *      grid point (NaN, a start value before the first draw) is counted in off_grid and left out of n_g; its group is not updated
+ *      in this call and keeps its indices, its row and its lp rows byte for byte.
+ *   2. mu given sd_b (b the group's current sd index), for a = 0 .. P_mu - 1, with c = 0.01, n = (double)n_g, S1, S2 converted
+ *      likewise, m = mu_a, s = sd_b, each operation one fp64 rounding in this order:
+ *        A = (S2 c) c      B = ((2 m) S1) c      C = (n m) m      Q = (A - B) + C      den = 2 (s s)
+ *        lp[a] = (log_hyper_mu[a] - Q / den) - n lse[a, b]
+ *      Then the maximum is subtracted, exp, the inclusive scan in theta_sample_kernel's layout (256 threads by 4 consecutive
+ *      points: 3 additions in a thread, the Hillis-Steele scan of the thread totals, 1 base addition), and the new index is the
+ *      first a with (C_a - C_0) / (C_last - C_0) > u0.  As in draw_theta, index 0 of a grid is therefore never drawn: the update
+ *      is exact Gibbs for the masses on the points 1 .. P - 1.
+ *   3. sd given the new mu: the same form over b with Q at the new m, lp[b] = (log_hyper_sd[b] - Q / den_b) - n lse[a, b], u1.
+ *   4. the group's row, as stated above.
+ *   u0, u1 = item_uniform(seed, t, GPIRT_ST_POP, g, 0) and (.., 1): what gpirt_item_uniforms(h, seed, t, 12, g, 1, 2, .) writes.
+ *   Nothing else draws from stage 12 and stage 12 draws from nothing else, so every existing stage keeps its uniforms.
+ * A draw that finds no index (C_last = C_0) is counted in failed and leaves the group as it was.  Each value has one writer and
+ * there is no floating-point atomic: two runs give a byte-identical state.
+ *
+ * gpirt_sampler_pop_record appends the (a_g, b_g) pairs (group 0's are -1) to the draw buffer (GPIRT_E_ARG once planned_draws are
+ * in) and adds 1 to hist_mu[a_g, g] and hist_sd[b_g, g], on the device.  gpirt_sampler_pop_get, by name: "codes" (n int32),
+ * "log_prior" (G x GPIRT_NGRID doubles) -- the two names a sampler with gpirt_sampler_pop_set knows --, "mu_grid" (P_mu), "sd_grid"
+ * (P_sd), "lse" (P_mu x P_sd, row-major), "log_hyper_mu", "log_hyper_sd", "index" (G x 2 int32), "stats" (3 x G int64, row-major:
+ * n_g, S1, S2 of the last call), "off_grid" (G int64, of the last call), "lp_mu" (G x P_mu), "lp_sd" (G x P_sd: the last call's
+ * rows, row 0 unused), "counts" (4 x G int64, row-major: calls, updated, skipped, failed), "hist_mu" (P_mu x G uint32), "hist_sd"
+ * (P_sd x G uint32), "draws" (recorded x G x 2 int32), "time" (1 double: milliseconds of device time of the last draw_pop's
+ * launches with gpirt_sampler_enable_timing on -- one synchronisation per call then --, else 0).  gpirt_sampler_pop_stats: totals.
+ *
+ * gpirt_pop_check is the argument check alone and touches no device (codes, log_prior, the hyperpriors, a0, b0 may be NULL: not
+ * checked then; rows: the rows of log_prior to check; the grids are checked with sampled != 0).  Refused, GPIRT_E_ARG with the
+ * reason: the sampled mode under GPIRT_RNG_RSTREAM (R's stream has no such draw); an item shard (item0 != 0 or m_total != m) or
+ * gpirt_sampler_set_theta_block in use (the block path would need the codes of its respondents; and
+ * gpirt_sampler_set_theta_block is refused while a population prior is on); before gpirt_sampler_init; gpirt_sampler_pop_enable
+ * after gpirt_sampler_pop_set without turning it off, and the converse; a non-finite table entry; a code outside 0 .. G - 1; a
+ * group without a member; G or a grid size out of range; mu_hi outside (0, 5]; sd_lo not in [GPIRT_POP_SD_MIN, sd_hi) or sd_hi
+ * above GPIRT_POP_SD_MAX.  gpirt_sampler_copy_state is refused while a population prior is on (it is not copied). */
+#define GPIRT_POP_MAX_GROUPS 8
+#define GPIRT_POP_MAX_POINTS 1024
+#define GPIRT_POP_SD_MIN 0.05
+#define GPIRT_POP_SD_MAX 10.0
+typedef struct gpirt_pop {
+    int64_t  on;                            /* 0 off, 1 fixed (gpirt_sampler_pop_set), 2 sampled (gpirt_sampler_pop_enable) */
+    int64_t  groups, n;                     /* G, the respondents */
+    int64_t  points_mu, points_sd;          /* 0 when fixed */
+    int64_t  calls;                         /* t: gpirt_sampler_draw_pop calls over the sampler's life */
+    int64_t  updates, updated, skipped, failed;   /* summed over the groups g >= 1, since gpirt_sampler_pop_enable */
+    int64_t  off_grid;                      /* members off the grid in the last call, summed over all groups */
+    int64_t  planned_draws, recorded;
+    double   mu_hi, sd_lo, sd_hi;
+    double   last_ms;
+    int64_t  reserved[4];
+} gpirt_pop;
+int gpirt_pop_check(const int32_t* codes, int64_t n, int G, const double* log_prior, int64_t rows, int sampled, double mu_hi,
+                    int P_mu, double sd_lo, double sd_hi, int P_sd, const double* log_hyper_mu, const double* log_hyper_sd,
+                    const int* a0, const int* b0, const gpirt_options* opts);
+int gpirt_pop_default_row(double* row);                             /* GPIRT_NGRID doubles */
+int gpirt_pop_normal_row(double mu, double sd, double* row);        /* GPIRT_NGRID doubles: -(0.5 z z), the update's expression */
+int gpirt_pop_grids(double mu_hi, int P_mu, double sd_lo, double sd_hi, int P_sd, double* mu, double* sd);
+int gpirt_pop_lse(const double* mu, int P_mu, const double* sd, int P_sd, double* lse);   /* P_mu x P_sd, row-major */
+int gpirt_sampler_pop_set(gpirt_sampler_t s, const int32_t* codes, int G, const double* log_prior);
+int gpirt_sampler_pop_enable(gpirt_sampler_t s, const int32_t* codes, int G, const double* anchor_row, double mu_hi, int P_mu,
+                             double sd_lo, double sd_hi, int P_sd, const double* log_hyper_mu, const double* log_hyper_sd,
+                             const int* a0, const int* b0, int64_t planned_draws, int on);
+int gpirt_sampler_draw_pop(gpirt_sampler_t s);
+int gpirt_sampler_pop_record(gpirt_sampler_t s);
+int gpirt_sampler_pop_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_pop_stats(gpirt_sampler_t s, gpirt_pop* out);
 
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
