@@ -516,6 +516,18 @@ AMP_COUNTS = ("updates", "accepted", "out_of_range", "failed")             # the
 AMP_RECORD = ("dll", "log_ratio", "log_u", "status", "nonfinite")          # the rows of amp_get("record")
 AMP_STATUS = ("rejected", "accepted", "out_of_range", "failed")            # a record's status by its code
 AMP_MODES = (None, "fixed", "sampled")
+# the centred amplitude update (include/gpirt_hip.h gpirt_amp_centred; gpirt_amd.amp.centred_*)
+ST_AMP_CENTRED = 13               # item index item0 + j: index 0 .. 63 the augmentation's normals, 64 / 65 the two uniforms
+AMP_CENTRED_RANK = 64
+AMP_CENTRED_COUNTS = ("updates", "accepted", "same", "failed")             # the rows of amp_get("counts_centred")
+AMP_CENTRED_RECORD = ("Q", "k_prop", "dll", "log_u", "status")             # the rows of amp_get("record_centred")
+AMP_CENTRED_STATUS = ("rejected", "accepted", "same", "failed")            # a record's status by its code
+
+
+class AmpCentred(C.Structure):
+    """gpirt_amp_centred (include/gpirt_hip.h): the calls, the rank, the totals over the items and the acceptance of the decided."""
+    _fields_ = [(k, C.c_int64) for k in ("calls", "rank") + AMP_CENTRED_COUNTS] + [
+        (k, C.c_double) for k in ("accept_rate", "last_ms")] + [("reserved", C.c_int64 * 6)]
 
 
 class Amp(C.Structure):
@@ -787,6 +799,8 @@ SIGNATURES = {
     "gpirt_sampler_amp_record": (_i32, [_vp]),
     "gpirt_sampler_amp_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_amp_stats": (_i32, [_vp, C.POINTER(Amp)]),
+    "gpirt_sampler_draw_amp_centred": (_i32, [_vp]),
+    "gpirt_sampler_amp_centred_stats": (_i32, [_vp, C.POINTER(AmpCentred)]),
     "gpirt_pop_check": (_i32, [C.POINTER(C.c_int32), _i64, _i32, _dp, _i64, _i32, _dbl, _i32, _dbl, _dbl, _i32, _dp, _dp,
                                C.POINTER(_i32), C.POINTER(_i32), C.POINTER(Options)]),
     "gpirt_pop_default_row": (_i32, [_dp]),

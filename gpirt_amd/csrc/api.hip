@@ -166,7 +166,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 134; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 135; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -231,6 +231,9 @@ int gpirt_version(void) { return 134; }   // 101: gpirt_options names kernel_fp3
                                             // 134: a population prior for theta: a table of log masses per group, fixed or with the groups'
                                             //      means and sds sampled by exact Gibbs on two grids (pop.hip, sampler.hip: GPIRT_ST_POP,
                                             //      gpirt_pop_check, gpirt_sampler_pop_*, gpirt_sampler_draw_pop); stage API only
+                                            // 135: a centred amplitude update on the GP's rank-64 smooth part beside the whitened one
+                                            //      (amp_centred.hip, sampler.hip: GPIRT_ST_AMP_CENTRED, gpirt_sampler_draw_amp_centred,
+                                            //      gpirt_sampler_amp_centred_stats, new names of gpirt_sampler_amp_get); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

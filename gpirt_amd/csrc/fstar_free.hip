@@ -171,10 +171,13 @@ __global__ __launch_bounds__(256) void fstar_free_small_kernel(const double* __r
 // A pivot that is not positive raises *err (the sampler's numeric error word).
 // prefix: the slots of Gv hold the parts' own Grams and work-group P first adds those of slots 1 .. P itself, element by
 // element in slot order from zero -- flr_scan_kernel's sums, so its bits, without its launch (slot 0 is not read: G_0 = 0).
+// Rout (the centred amplitude update, amp_centred.hip; nullptr for everybody else, whose code it leaves as it was): R itself,
+// 64 x 64 column-major with zeros above the diagonal, stored before its diagonal blocks are inverted in place.
 constexpr size_t FX_LDS = sizeof(double) * (3 * FR * FLD + 2 * 4 * FR);
 static_assert(FR * S64_LS <= 2 * FR * FLD, "the staged factor takes the place of Gv and Gv F");
 __device__ __forceinline__ void fstar_free_xhat_body(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
-                                                     double* __restrict__ Xh, int* __restrict__ err, const bool prefix)
+                                                     double* __restrict__ Xh, int* __restrict__ err, const bool prefix,
+                                                     double* __restrict__ Rout = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) double ff_lds[];
     __shared__ int sfail, sinfo;
@@ -223,6 +226,11 @@ __device__ __forceinline__ void fstar_free_xhat_body(const double* __restrict__ 
     __syncthreads();
     potf2_64_body(sM, S64_LS, FR, 0, &sinfo, sP, &sfail);
     if (t == 0 && sfail != 0x7fffffff && err) atomicCAS(err, 0, (int)GPIRT_E_NUMERIC);
+    if (Rout) {
+        Rout += (int64_t)blockIdx.x * FR * FR;
+        for (int e = t; e < FR * FR; e += 256) Rout[e] = sM[(e >> 6) * S64_LS + (e & (FR - 1))];
+        __syncthreads();                                     // (read before wave 0 inverts the diagonal blocks)
+    }
     invert_diag16(sM);
     solve64_lower_inv(X, sM);
 #pragma unroll
@@ -235,6 +243,12 @@ __global__ __launch_bounds__(256) void fstar_free_xhat_kernel(const double* __re
                                                               double* __restrict__ Xh, int* __restrict__ err)
 {
     fstar_free_xhat_body(Gv, F, eps, Xh, err, false);
+}
+
+__global__ __launch_bounds__(256) void fstar_free_xhat_r_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
+                                                                double* __restrict__ Xh, double* __restrict__ R, int* __restrict__ err)
+{
+    fstar_free_xhat_body(Gv, F, eps, Xh, err, false, R);
 }
 
 // The prefix form runs on the fused structured factor's chain while the sampler's side stream fills the chip with
@@ -317,9 +331,17 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
 
 // Xh[q] = R_q^-1 F^T with R_q R_q^T = F^T Gv[q] F + eps I for `batch` matrices Gv[q] (64 x 64 each, 4096 doubles apart), one
 // work-group per matrix.  prefix: matrix q is the sum of the slots 1 .. q of Gv, formed by its work-group (see the kernel)
-int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err, bool prefix)
+int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err, bool prefix,
+                           double* R)
 {
     if (batch <= 0) return 0;
+    if (R) {
+        if (prefix) { set_error("fstar_free_xhat: R is not kept in the prefix form"); return GPIRT_E_ARG; }
+        GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fstar_free_xhat_r_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
+        hipLaunchKernelGGL(fstar_free_xhat_r_kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, R, err);
+        GP_HIP(hipGetLastError());
+        return 0;
+    }
     auto* kernel = prefix ? fstar_free_xhat_prefix_kernel : fstar_free_xhat_kernel;
     GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
     hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, err);

@@ -76,6 +76,25 @@ int launch_amp_update(hipStream_t st, const AmpUpdateArgs& a);
 // draws[slot, j] = idx[j] (planned x m, row-major), hist[idx[j], j] += 1 (P x m, row-major)
 int launch_amp_record(hipStream_t st, const int* idx, int64_t m, int P, int64_t slot, uint32_t* hist, int32_t* draws);
 int amp_nearest_one(const double* grid, int P);                     // the grid point nearest 1 in log a (the first of a tie)
+// amp_centred.hip: the centred amplitude update on the GP's rank-64 smooth part (gpirt_sampler_draw_amp_centred)
+constexpr int AMP_CENTRED_RANK = 64;
+struct AmpCentredArgs {
+    double* f; const double* mu; const double* y; int64_t n, m;
+    const double* theta; const double* nodes; const double* wts;        // the basis' inputs (launch_nu_lr_basis)
+    const double* F; double eps;                                        // F with Kcc = F F^T, its dead columns zero; the jitter
+    uint64_t live; int r;                                               // bit k: column k of F is live; r = their count
+    double *V, *Gv, *parts; int nsplit;                                 // n x 64; 64 x 64; nsplit x 64 x max(64, m)
+    double *Xh, *R;                                                     // 64 x 64 each: R^-1 F^T and R, R R^T = F^T V^T V F + eps I
+    double *T, *Z, *W, *Xi, *Gc, *Q;                                    // 64 x m each (column j: item j), Q: m
+    double* H;                                                          // n x m (ld n): h_j = V g_j
+    const double *grid, *log_prior, *ln_a, *half_inv_a2; int P;         // device tables of P values
+    int* idx; double* amp;                                              // m each, shared with the whitened update
+    long long* counts; double* rec;                                     // 4 x m (updates, accepted, same, failed), 5 x m, row-major
+    uint64_t seed; uint32_t t; uint32_t item0;
+    int* err;                                                           // the sampler's numeric error word
+};
+// one centred update of every item's amplitude: the basis, V^T V, the small kernel, T = V^T f, the coefficients, H = V Gc, the update
+int launch_amp_centred(hipStream_t st, const AmpCentredArgs& a);
 // pop.hip: the population prior for theta (gpirt_sampler_pop_*): group means and sds on two grids, and the host tables
 struct PopUpdateArgs {
     const long long* stats;                                             // 4 x G, row-major: n_g, S1, S2, off_grid of this call
@@ -292,7 +311,7 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
 // Xh[q] = R_q^-1 F^T, R_q R_q^T = F^T Gv[q] F + eps I, for `batch` 64 x 64 matrices Gv[q] (one work-group each); prefix: matrix q
 // is Gv[1] + ... + Gv[q], added by its own work-group in slot order (Gv[0] is not read)
 int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err,
-                           bool prefix = false);
+                           bool prefix = false, double* R = nullptr);     // R: also R itself, 64 x 64 per matrix (not with prefix)
 // factor_lr.hip: L's diagonal parts and the 64 node rows from theta alone -- nothing below the parts is computed
 struct FactorLrArgs {
     const double* theta; int64_t n;

@@ -80,6 +80,16 @@ struct AmpState {
     // with gpirt_sampler_enable_timing on: the device time of the last update's one launch ("time" of gpirt_sampler_amp_get)
     hipEvent_t tev[2] = {};
     double last_ms = 0.0;
+    // The centred update (gpirt_sampler_draw_amp_centred; amp_centred.hip).  Its buffers are one allocation made by its first
+    // call after an enable: a sampler that never calls it has none.  F_ell: the length scale `F` (dead columns zeroed, `live`
+    // their mask, r the live count) was built for.
+    uint32_t ct = 0;                  // draw_amp_centred calls so far (it survives enabling again, as t)
+    double* cbuf = nullptr;
+    AmpCentredArgs ca{};              // the device pointers into cbuf, the tables, the mask
+    bool cF_have = false;
+    double cF_ell = 0.0;
+    hipEvent_t ctev[2] = {};
+    double clast_ms = 0.0;
 };
 
 // The population prior for theta (gpirt_sampler_pop_set / gpirt_sampler_pop_enable; include/gpirt_hip.h, pop.hip).  mode 0: off
@@ -1283,12 +1293,13 @@ void ell_free(EllState* e)
 void amp_free(AmpState* a)
 {
     for (void* p : { (void*)a->amp, (void*)a->d_grid, (void*)a->d_log_prior, (void*)a->rec, (void*)a->idx, (void*)a->width,
-                     (void*)a->counts, (void*)a->hist, (void*)a->draws })
+                     (void*)a->counts, (void*)a->hist, (void*)a->draws, (void*)a->cbuf })
         if (p) hipFree(p);
     for (hipEvent_t t : a->tev) if (t) hipEventDestroy(t);
-    const uint32_t calls = a->t;      // the sampler's draw_amp calls: enabling again does not replay their uniforms
+    for (hipEvent_t t : a->ctev) if (t) hipEventDestroy(t);
+    const uint32_t calls = a->t, ccalls = a->ct;      // the sampler's draw_amp / draw_amp_centred calls: enabling again does not replay their uniforms
     *a = AmpState();
-    a->t = calls;
+    a->t = calls; a->ct = ccalls;
 }
 
 // ---- the population prior for theta (include/gpirt_hip.h; the kernels are pop.hip's) -------------------------------------------
@@ -3329,6 +3340,36 @@ int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int6
     else if (strcmp(name, "hist") == 0) { dev = A.hist; want = 4 * P * m; }
     else if (strcmp(name, "draws") == 0) { dev = A.draws; want = 4 * A.recorded * m; }
     else if (strcmp(name, "time") == 0) { host = &A.last_ms; want = 8; }
+    else if (strcmp(name, "time_centred") == 0) { host = &A.clast_ms; want = 8; }
+    else if (strstr(name, "centred") != nullptr || strcmp(name, "rank") == 0 || strcmp(name, "live") == 0) {
+        // the centred update's (gpirt_sampler_draw_amp_centred): they exist from its first call on
+        GP_TRY(needs(A.cbuf != nullptr && A.cF_have, "the centred amplitude update's arrays are", "one gpirt_sampler_draw_amp_centred call"));
+        const AmpCentredArgs& c = A.ca;
+        const int64_t R = AMP_CENTRED_RANK;
+        int32_t small[AMP_CENTRED_RANK];
+        if (strcmp(name, "rank") == 0 || strcmp(name, "live") == 0) {
+            const bool one = name[0] == 'r';
+            want = one ? 4 : 4 * R;
+            if (bytes != want) { set_error("amplitude: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+            if (one) small[0] = c.r;
+            else for (int k = 0; k < R; ++k) small[k] = (int32_t)((c.live >> k) & 1ull);
+            memcpy(h_out, small, (size_t)want);
+            return 0;
+        }
+        if (strcmp(name, "counts_centred") == 0) { dev = c.counts; want = 32 * m; }
+        else if (strcmp(name, "record_centred") == 0) { dev = c.rec; want = 40 * m; }
+        else if (strcmp(name, "centred_T") == 0) { dev = c.T; want = 8 * R * m; }
+        else if (strcmp(name, "centred_z") == 0) { dev = c.Z; want = 8 * R * m; }
+        else if (strcmp(name, "centred_w") == 0) { dev = c.W; want = 8 * R * m; }
+        else if (strcmp(name, "centred_xi") == 0) { dev = c.Xi; want = 8 * R * m; }
+        else if (strcmp(name, "centred_g") == 0) { dev = c.Gc; want = 8 * R * m; }
+        else if (strcmp(name, "centred_Q") == 0) { dev = c.Q; want = 8 * m; }
+        else if (strcmp(name, "centred_H") == 0) { dev = s->NU; want = 8 * s->n * m; }
+        else if (strcmp(name, "centred_Xh") == 0) { dev = c.Xh; want = 8 * R * R; }
+        else if (strcmp(name, "centred_R") == 0) { dev = c.R; want = 8 * R * R; }
+        else if (strcmp(name, "centred_F") == 0) { dev = c.F; want = 8 * R * R; }
+        else { set_error("unknown amplitude array '%s'", name); return GPIRT_E_ARG; }
+    }
     else { set_error("unknown amplitude array '%s'", name); return GPIRT_E_ARG; }
     if (bytes != want) { set_error("amplitude: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
     if (want == 0) return 0;
@@ -3366,6 +3407,163 @@ int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out)
         out->out_of_range += cnt[(size_t)(2 * m + j)]; out->failed += cnt[(size_t)(3 * m + j)];
     }
     if (out->updates) out->accept_rate = (double)out->accepted / (double)out->updates;
+    return 0;
+}
+
+// ---- the centred amplitude update (amp_centred.hip) ----------------------------------------------------------------------------
+// the buffers of the first call after an enable: one allocation, the two tables of the proposal (long double on the host, rounded
+// once), the nodes and weights of the basis; counters and record zeroed.  Drains the handle's stream.
+static int amp_centred_alloc(gpirt_sampler_t s)
+{
+    AmpState& A = s->amp;
+    if (A.cbuf) return 0;
+    const size_t n = (size_t)s->n, m = (size_t)s->m, P = (size_t)A.P, R = AMP_CENTRED_RANK, RR = R * R;
+    const size_t wide = m > R ? m : R;
+    const size_t sizes[] = { RR, n * R, RR, (size_t)KSPLIT * R * wide, RR, RR, R * m, R * m, R * m, R * m, R * m, m, P, P, 5 * m, 4 * m, R, R };
+    size_t total = 0;
+    for (size_t sz : sizes) total += sz;
+    if (hipMalloc((void**)&A.cbuf, sizeof(double) * total) != hipSuccess) { A.cbuf = nullptr; set_error("amplitude (centred): hipMalloc failed"); return GPIRT_E_ALLOC; }
+    double* p = A.cbuf;
+    auto take = [&](size_t sz) { double* q = p; p += sz; return q; };
+    AmpCentredArgs& c = A.ca;
+    c = AmpCentredArgs();
+    double* F = take(sizes[0]); c.F = F;
+    c.V = take(sizes[1]); c.Gv = take(sizes[2]); c.parts = take(sizes[3]); c.Xh = take(sizes[4]); c.R = take(sizes[5]);
+    c.T = take(sizes[6]); c.Z = take(sizes[7]); c.W = take(sizes[8]); c.Xi = take(sizes[9]); c.Gc = take(sizes[10]); c.Q = take(sizes[11]);
+    double* ln_a = take(sizes[12]); double* hia = take(sizes[13]);
+    c.ln_a = ln_a; c.half_inv_a2 = hia;
+    c.rec = take(sizes[14]);
+    c.counts = reinterpret_cast<long long*>(take(sizes[15]));
+    double* nodes = take(sizes[16]); double* wts = take(sizes[17]);
+    c.nodes = nodes; c.wts = wts;
+    c.nsplit = KSPLIT;
+    std::vector<double> tab(2 * P), hn, hw;
+    for (size_t k = 0; k < P; ++k) {
+        const long double a = (long double)A.grid[k];
+        tab[k] = (double)logl(a);
+        tab[P + k] = (double)(0.5L / (a * a));
+    }
+    nu_lr_nodes(hn, hw);
+    hipStream_t st = s->h->stream;
+    if (hipMemsetAsync(A.cbuf, 0, sizeof(double) * total, st) != hipSuccess ||
+        hipMemcpyAsync(ln_a, tab.data(), sizeof(double) * 2 * P, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(nodes, hn.data(), sizeof(double) * R, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(wts, hw.data(), sizeof(double) * R, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        hipFree(A.cbuf); A.cbuf = nullptr;
+        set_error("amplitude (centred): the upload failed");
+        return GPIRT_E_HIP;
+    }
+    A.cF_have = false;
+    return 0;
+}
+
+// F for the sampler's current length scale with its dead columns zeroed, the live mask and r (host; cached until the length
+// scale moves).  Drains the handle's stream when it rebuilds.
+static int amp_centred_factor(gpirt_sampler_t s)
+{
+    AmpState& A = s->amp;
+    if (A.cF_have && A.cF_ell == s->kern.length_scale) return 0;
+    constexpr int R = AMP_CENTRED_RANK;
+    std::vector<double> F;
+    fstar_free_factor(s->kern, F);
+    uint64_t live = 0;
+    int r = 0;
+    for (int k = 0; k < R; ++k) {
+        long double sq = 0.0L;
+        for (int i = 0; i < R; ++i) sq += (long double)F[(size_t)(i + R * k)] * (long double)F[(size_t)(i + R * k)];
+        if (sq <= 1e-13L) { for (int i = 0; i < R; ++i) F[(size_t)(i + R * k)] = 0.0; }
+        else { live |= 1ull << k; r += 1; }
+    }
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(const_cast<double*>(A.ca.F), F.data(), sizeof(double) * F.size(), hipMemcpyHostToDevice, st));
+    GP_HIP(hipStreamSynchronize(st));                          // (F leaves scope)
+    A.ca.live = live; A.ca.r = r;
+    A.cF_have = true; A.cF_ell = s->kern.length_scale;
+    return 0;
+}
+
+int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_draw_amp_centred";
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    if (stream_mode(s)) { set_error("%s: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw", me); return GPIRT_E_ARG; }
+    if (s->opt.kernel_fp32) { set_error("%s: kernel_fp32 is refused, the single-precision build is the default kernel's alone", me); return GPIRT_E_ARG; }
+    if (s->opt.item0 != 0 || (s->opt.m_total > 0 && s->opt.m_total != s->m)) {
+        set_error("%s: an item shard (item0 = %lld, m_total = %lld) is refused, the amplitudes are kept for all items of one sampler", me,
+                  (long long)s->opt.item0, (long long)s->opt.m_total);
+        return GPIRT_E_ARG;
+    }
+    AmpState& A = s->amp;
+    if (A.mode != 2) {
+        set_error("%s: the amplitudes are not in the sampled mode (gpirt_sampler_amp_enable): %s", me,
+                  A.mode == 1 ? "they are fixed" : "they are off");
+        return GPIRT_E_ARG;
+    }
+    if (!s->nu_kern_ok) {
+        if (s->kern.family != GPIRT_KERNEL_SE) {
+            set_error("%s: the handle's kernel is not a squared exponential, it has no rank-64 form (gpirt_kernel_check(kernel, 64))", me);
+            return GPIRT_E_ARG;
+        }
+        const int rc = kernel_rank_check(s->kern, AMP_CENTRED_RANK, nullptr, nullptr);      // (its message names the length scale)
+        if (rc) return rc;
+        set_error("%s: the length-scale grid's smallest value fails gpirt_kernel_check(kernel, 64)", me);
+        return GPIRT_E_ARG;
+    }
+    if (!s->theta_ok) {
+        set_error("%s: a theta is not finite or lies outside [-5, 5], the rank-64 basis does not hold there", me);
+        return GPIRT_E_ARG;
+    }
+    // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
+    GP_TRY(beta_sync(s));
+    GP_TRY(amp_centred_alloc(s));
+    GP_TRY(amp_centred_factor(s));
+    AmpCentredArgs a = A.ca;
+    a.f = s->f; a.mu = s->mu; a.y = s->y; a.n = s->n; a.m = s->m;
+    a.theta = s->theta; a.eps = GPIRT_JITTER;
+    a.H = s->NU;                                  // draw_f's prior draw: free between steps
+    a.grid = A.d_grid; a.log_prior = A.d_log_prior; a.P = A.P;
+    a.idx = A.idx; a.amp = A.amp;
+    a.seed = s->opt.seed; a.t = A.ct + 1; a.item0 = (uint32_t)s->opt.item0;
+    a.err = s->flags;
+    hipStream_t st = s->h->stream;
+    const bool timed = s->timing;
+    if (timed) {
+        for (hipEvent_t& t : A.ctev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(A.ctev[0], st));
+    }
+    GP_TRY(launch_amp_centred(st, a));
+    A.ct += 1;
+    if (timed) {                              // (timing on: one synchronisation, as the whitened update's)
+        GP_HIP(hipEventRecord(A.ctev[1], st));
+        GP_HIP(hipEventSynchronize(A.ctev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, A.ctev[0], A.ctev[1]);
+        A.clast_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_amp_centred_stats(gpirt_sampler_t s, gpirt_amp_centred* out)
+{
+    GP_ARG(s && out);
+    const AmpState& A = s->amp;
+    memset(out, 0, sizeof(*out));
+    out->calls = A.ct; out->accept_rate = (double)NAN; out->last_ms = A.clast_ms;
+    if (A.mode != 2 || !A.cbuf) return 0;
+    out->rank = A.cF_have ? A.ca.r : 0;
+    const int64_t m = s->m;
+    std::vector<long long> cnt(4 * (size_t)m);
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(cnt.data(), A.ca.counts, sizeof(long long) * 4 * (size_t)m, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < m; ++j) {
+        out->updates += cnt[(size_t)j]; out->accepted += cnt[(size_t)(m + j)];
+        out->same += cnt[(size_t)(2 * m + j)]; out->failed += cnt[(size_t)(3 * m + j)];
+    }
+    const int64_t decided = out->updates - out->same - out->failed;
+    if (decided > 0) out->accept_rate = (double)out->accepted / (double)decided;
     return 0;
 }
 

@@ -1702,6 +1702,21 @@ class Sampler:
         statement): nothing is read back."""
         self._call("gpirt_sampler_draw_amp")
 
+    def draw_amp_centred(self):
+        """One centred update of every item's amplitude on the GP's rank-64 smooth part (gpirt_sampler_draw_amp_centred;
+        gpirt_amd.amp.centred_exact_coef and centred_exact_update are its NumPy statement): nothing is read back.  It reads the
+        prior density of f, so it belongs behind step(consistent=True)."""
+        self._call("gpirt_sampler_draw_amp_centred")
+
+    def amp_centred(self) -> dict:
+        """The centred update's totals (gpirt_sampler_amp_centred_stats): calls, rank, updates, accepted, same, failed, accept_rate
+        (of the decided updates) and last_ms."""
+        a = _lib.AmpCentred()
+        check(self.lib.gpirt_sampler_amp_centred_stats(self._s, C.byref(a)))
+        out = {k: int(getattr(a, k)) for k in ("calls", "rank") + _lib.AMP_CENTRED_COUNTS}
+        out.update(accept_rate=float(a.accept_rate), last_ms=float(a.last_ms))
+        return out
+
     def amp_width(self, w):
         """The proposal widths from the next update on: m values (or one for all), each in 1 .. points - 1."""
         w = np.ascontiguousarray(np.broadcast_to(np.asarray(w, dtype=np.int32), (self.m,)))
@@ -1715,9 +1730,31 @@ class Sampler:
         """One array by name: grid, log_prior (points), amplitude (m), index, width (int32, m), counts (int64, 4 x m: updates,
         accepted, out_of_range, failed), record (5 x m of the last update: dll, log_ratio, log_u, status, nonfinite; status as
         _lib.AMP_STATUS), hist (uint32, points x m), draws (int32, recorded x m), time (1: ms of device time of the last update
-        with enable_timing() on)."""
+        with enable_timing() on).  Of the centred update, from its first call on: counts_centred (int64, 4 x m: updates, accepted,
+        same, failed), record_centred (5 x m: Q, k', dll, log u1, status as _lib.AMP_CENTRED_STATUS), rank (int), live (int32, 64),
+        the last call's centred_T, centred_z, centred_w, centred_xi, centred_g (64 x m), centred_Q (m), centred_H (n x m, valid
+        until the next draw_f), centred_Xh, centred_R, centred_F (64 x 64), time_centred."""
         P, m = getattr(self, "_amp_points", 0), self.m
-        if name in ("index", "width"):
+        R = _lib.AMP_CENTRED_RANK
+        if name == "rank":
+            out = np.empty(1, dtype=np.int32)
+            self._get_into("gpirt_sampler_amp_get", name, out)
+            return int(out[0])
+        if name == "live":
+            out = np.empty(R, dtype=np.int32)
+        elif name == "counts_centred":
+            out = np.empty((4, m), dtype=np.int64)
+        elif name == "record_centred":
+            out = np.empty((5, m))
+        elif name in ("centred_T", "centred_z", "centred_w", "centred_xi", "centred_g"):
+            out = np.empty((R, m), order="F")
+        elif name in ("centred_Xh", "centred_R", "centred_F"):
+            out = np.empty((R, R), order="F")
+        elif name == "centred_H":
+            out = np.empty((self.n, m), order="F")
+        elif name in ("centred_Q", "time_centred"):
+            out = np.empty(m if name == "centred_Q" else 1)
+        elif name in ("index", "width"):
             out = np.empty(m, dtype=np.int32)
         elif name == "counts":
             out = np.empty((4, m), dtype=np.int64)

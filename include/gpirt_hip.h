@@ -55,6 +55,7 @@ enum {
     GPIRT_ST_INIT_F = 1, GPIRT_ST_INIT_BETA = 2, GPIRT_ST_F_Z = 3, GPIRT_ST_F_ESS = 4,
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
+    GPIRT_ST_AMP_CENTRED = 13,  /* the centred amplitude update (gpirt_sampler_draw_amp_centred): item index item0 + j, index 0 .. 63 the normals of the augmentation, 64 / 65 the two uniforms; nothing else draws from it */
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
@@ -2242,6 +2243,67 @@ int gpirt_sampler_amp_width(gpirt_sampler_t s, const int* w);
 int gpirt_sampler_amp_record(gpirt_sampler_t s);
 int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_amp_stats(gpirt_sampler_t s, gpirt_amp* out);
+
+/* ------------------------------------------------------ a centred amplitude update on the rank-64 smooth part ---------- */
+/* Library version 135.  gpirt_sampler_draw_amp holds nu_j = L^-1 f_j / a_j fixed; with thousands of answers per item the
+ * likelihood pins f_j down and a_j moves only as fast as draw_f changes |nu_j|.  gpirt_sampler_draw_amp_centred is the centred
+ * move Murray & Adams (2010) pair it with.  It reads the prior density of f, so it belongs behind gpirt_sampler_step_consistent
+ * (after the reference's step f sits at the old theta, quirk Q3).  It needs no factor, dense or structured: only the rank-64
+ * identity K(theta, theta) = V Kcc V^T (V the Lagrange basis at theta on the 64 Chebyshev nodes, Kcc = F F^T the kernel at the
+ * nodes) on which the structured draw_f and draw_fstar rest.  Stage API only: gpirt_options, gpirt_run, gpirt_mcmc*,
+ * gpirt_sampler_step* and gpirt_sampler_draw_amp keep their layout and behaviour, every existing stage keeps its numbers, and a
+ * sampler on which the entry is never called computes bit for bit what it did.
+ *
+ * Exact MCMC by augmentation.  Phi = V F (n x 64), eps = GPIRT_JITTER.  The columns of F whose squared norm (the eigenvalue of
+ * Kcc) is <= 1e-13 are DEAD: zeroed on the host, they take no part; r is the count of live ones (32 at the default kernel).  The
+ * model f_j ~ N(0, a_j^2 (K + eps I)) is the marginal of
+ *     xi_j ~ N(0, a_j^2 I_r),   e_j ~ N(0, eps I_n),   f_j = Phi xi_j + a_j e_j
+ * (its covariance a^2 (Phi Phi^T + eps I) differs from a^2 S by the rank identity's 1e-13; the move leaves that model's posterior
+ * exactly invariant).  One update of item j, t the count of gpirt_sampler_draw_amp_centred calls from 1:
+ *   1. augment   A = Phi^T Phi + eps I = R R^T (one work-group; a bad pivot raises the sampler's numeric error word as the
+ *                theta-alone draw_fstar does), T = V^T f, t_j = (R^-1 F^T) T_j, z_j[k] = qnorm(item_uniform(seed, t,
+ *                GPIRT_ST_AMP_CENTRED, item0 + j, k)), k = 0 .. 63 (dead k are drawn and ignored: the keying does not depend on
+ *                r), w_j = t_j + (a_j sqrt(eps)) z_j, xi_j = R^-T w_j by back-substitution, Q_j = sum of xi^2 over live k in
+ *                ascending k, g_j = F xi_j, h_j = V g_j.  csrc/amp_centred.hip fixes the order of every sum.
+ *   2. propose   lq[k] = (log_prior[k] - r ln a_k) - Q_j / (2 a_k^2) with the two tables formed at enable on the host in long
+ *                double; the maximum, exp and an inclusive scan C; u0 = item_uniform(.., item0 + j, 64); k' = the FIRST k with
+ *                C_k > u0 C_last (not draw_theta's (C - C_0) rule: index 0 keeps its mass).  k' == k_j: counted in `same`,
+ *                nothing is touched.
+ *   3. move      c = grid[k'] / grid[k_j] (one division), f'_i = h_i + c (f_i - h_i) (three roundings, no FMA): the nugget's
+ *                whitened coordinates are held fixed.
+ *   4. accept    iff log(u1) < dll_j, u1 = item_uniform(.., item0 + j, 65), dll_j the sum over observed rows of
+ *                t(y (f + mu)) - t(y (f' + mu)) cell by cell in gpirt_sampler_draw_amp's order.  The proposal carries the prior
+ *                and the centred term, so only the likelihood ratio is left; the nugget is 0.03 a logits and acceptance is near
+ *                1.  A non-finite f', h, Q_j or dll_j: `failed`, never accepted, not an error.  Accepted: the same work-group
+ *                rewrites the column with the same expression and sets k_j, a_j; otherwise the column is byte-identical.
+ * No atomics, one writer per value, items independent behind the shared 64 x 64 factorisation: two runs give a byte-identical
+ * state.  The call joins a held-back draw_beta, rebuilds V from the current theta and uses the n x m scratch of draw_f's prior
+ * draw for H (free between steps).  F is cached per sampler and rebuilt only when a sampled length scale's index moved.
+ * On a coarse grid the move hardly moves: given xi, a has relative sd 1 / sqrt(2 r), about 0.12, so a useful grid has steps
+ * under about 10 % (the default 129 points on 0.1 .. 10: 3.7 %).
+ *
+ * It shares grid, log_prior, index, amplitude, histogram and draw buffer with the whitened update and has its own counters and
+ * last record, by name through gpirt_sampler_amp_get: "counts_centred" (4 x m int64, row-major: updates, accepted, same,
+ * failed), "record_centred" (5 x m doubles, row-major: Q_j, k', dll, log u1, status; status 0 rejected, 1 accepted, 2 same --
+ * dll and log u1 NaN --, 3 failed; k' = -1 where no draw could be made), "rank" (1 int32: r), "live" (64 int32: 1 live, 0
+ * dead), and the last call's intermediates "centred_T", "centred_z", "centred_w", "centred_xi", "centred_g" (64 x m doubles,
+ * column j item j), "centred_Q" (m doubles), "centred_H" (n x m doubles, valid until the next draw_f), "centred_Xh",
+ * "centred_R", "centred_F" (64 x 64; F with its dead columns zeroed), "time_centred" (1 double, as "time").  All of them need one gpirt_sampler_draw_amp_centred first.
+ * gpirt_sampler_amp_centred_stats: the totals.
+ *
+ * Refused with GPIRT_E_ARG, each with its reason: before gpirt_sampler_init; amplitudes not in the sampled mode;
+ * GPIRT_RNG_RSTREAM; an item shard; kernel_fp32; a handle kernel that fails gpirt_kernel_check(kernel, 64) (Matern, too short
+ * a length scale); a theta the sampler does not vouch for (not finite or outside [-5, 5]). */
+typedef struct gpirt_amp_centred {
+    int64_t  calls;                         /* t: gpirt_sampler_draw_amp_centred calls over the sampler's life */
+    int64_t  rank;                          /* r of the last call (0 before the first) */
+    int64_t  updates, accepted, same, failed;   /* summed over the items, since gpirt_sampler_amp_enable */
+    double   accept_rate;                   /* accepted / (updates - same - failed), NaN while that is 0 */
+    double   last_ms;                       /* device time of the last call with gpirt_sampler_enable_timing on, else 0 */
+    int64_t  reserved[6];
+} gpirt_amp_centred;
+int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s);
+int gpirt_sampler_amp_centred_stats(gpirt_sampler_t s, gpirt_amp_centred* out);
 
 /* ------------------------------------------------------ a consistent step: f carried to the new theta, a prior check ---- */
 /* Library version 133.  The reference's iteration moves theta and keeps f (quirk Q3 of SURVEY.md): behind gpirt_sampler_step

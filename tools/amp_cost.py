@@ -19,6 +19,14 @@
       also rewrites the paragraph between the two "amp_cost" marker comments of README.md from the record
   python tools/amp_cost.py --from profiles/amp_cost.json --readme README.md
       rewrites that paragraph from an earlier record; no device is touched
+  python tools/amp_cost.py --centred --out profiles/amp_cost.json [--kernel-stats DIR/..._kernel_stats.csv]
+      the centred update (csrc/amp_centred.hip) ADDED to the record at --out under "centred", everything
+      else of it left as it is: one gpirt_sampler_draw_amp_centred after a consistent step each, median of --updates by the
+      sampler's event timing, beside the whitened update in the same run; the step loop with both updates against the whitened
+      one alone, --rounds alternating rounds of --steps consistent steps in one process.  --kernel-stats: a rocprofv3
+      --kernel-trace --stats table of such a run (python tools/amp_cost.py --centred-profile under rocprofv3), from which the
+      call's split by kernel is taken, with the update kernel's bytes (four arrays read, accepted columns read and written once
+      more) and TB/s beside ell_delta_kernel's of the record.
 """
 import argparse
 import json
@@ -79,6 +87,98 @@ def verdict(rej, acc, d) -> str:
     return first + second
 
 
+CENTRED_KERNELS = ("nu_basis_kernel", "gemm_f64_kernel", "sum_parts_kernel", "fstar_free_xhat_r_kernel", "amp_centred_coef_kernel",
+                   "amp_centred_update_kernel")
+
+
+def centred(args):
+    """--centred / --centred-profile (the module docstring)"""
+    import csv
+    import numpy as np
+    from gpirt_amd import Sampler
+    from gpirt_amd.ops import Handle
+    from gpirt_amd.synthetic import make_responses
+    n, m = args.n, args.m
+    y, th0 = make_responses(n, m, seed=20240)
+    h = Handle(0)
+    s = Sampler(h, y, th0, seed=1, preset="fast")
+    s.init()
+    s.amp_enable(0.1, 10.0, 129, None, 4)
+    for _ in range(args.warmup):
+        s.step(consistent=True)
+        s.draw_amp()
+        s.draw_amp_centred()
+    s.check()
+    if args.centred_profile:                       # under rocprofv3: the calls alone, so that the table's calls are theirs
+        for _ in range(args.updates):
+            s.draw_amp_centred()
+        s.check()
+        s.close()
+        h.close()
+        return
+    s.enable_timing(True)
+    ms, ms_w, acc, same = [], [], [], []
+    for _ in range(args.updates):
+        s.step(consistent=True)
+        s.check()
+        s.draw_amp()
+        ms_w.append(float(s.amp_get("time")[0]))
+        before = s.amp_centred()
+        s.draw_amp_centred()
+        ms.append(float(s.amp_get("time_centred")[0]))
+        after = s.amp_centred()
+        acc.append((after["accepted"] - before["accepted"]) / m)
+        same.append((after["same"] - before["same"]) / m)
+    s.enable_timing(False)
+    rates = {"both": [], "whitened": []}
+    for _ in range(args.rounds):
+        for name in ("both", "whitened"):
+            s.check()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                s.step(consistent=True)
+                s.draw_amp()
+                if name == "both":
+                    s.draw_amp_centred()
+            s.check()
+            rates[name].append(args.steps / (time.perf_counter() - t0))
+    st = s.amp_centred()
+    s.close()
+    h.close()
+    rec = dict(n=n, m=m, rank=st["rank"], updates=args.updates, ms=statistics.median(ms), ms_min=min(ms), ms_max=max(ms),
+               whitened_ms=statistics.median(ms_w), accepted_share=float(np.mean(acc)), same_share=float(np.mean(same)),
+               failed=st["failed"], steps=args.steps, rounds=args.rounds, iterations_per_s=rates,
+               median_iterations_per_s={k: statistics.median(v) for k, v in rates.items()})
+    if args.kernel_stats:
+        rows = {}
+        for r in csv.DictReader(open(args.kernel_stats)):
+            for k in CENTRED_KERNELS:
+                if k in r["Name"]:
+                    d = rows.setdefault(k, dict(calls=0, total_ns=0.0))
+                    d["calls"] += int(r["Calls"])
+                    d["total_ns"] += float(r["TotalDurationNs"])
+        calls = rows.get("amp_centred_update_kernel", {}).get("calls", 0)
+        if calls:
+            for k, d in rows.items():
+                d["us_per_call_of_draw"] = d["total_ns"] / calls / 1e3
+            up = rows["amp_centred_update_kernel"]
+            moved = (4.0 + 3.0 * rec["accepted_share"]) * 8.0 * n * m
+            up.update(bytes=moved, tb_per_s=moved / (up["total_ns"] / calls * 1e-9) / 1e12)
+        rec["kernels"] = rows
+    full = json.load(open(args.out)) if args.out and os.path.exists(args.out) else {}
+    if "ell_delta_kernel" in full:
+        rec["ell_delta_kernel_tb_per_s"] = full["ell_delta_kernel"]["tb_per_s"]
+    if args.headline_this and args.headline_parent:
+        rec["headline"] = dict(this=[float(v) for v in args.headline_this.split(",")],
+                               parent=[float(v) for v in args.headline_parent.split(",")])
+    full["centred"] = rec
+    txt = json.dumps(full, indent=1, default=float)
+    print(json.dumps(rec, indent=1, default=float))
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(txt + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--readme", default=None)
@@ -92,7 +192,13 @@ def main():
     ap.add_argument("--headline-this", default=None)
     ap.add_argument("--headline-parent", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--centred", action="store_true")
+    ap.add_argument("--centred-profile", action="store_true")
+    ap.add_argument("--kernel-stats", default=None)
     args = ap.parse_args()
+    if args.centred or args.centred_profile:
+        centred(args)
+        return
     if args.record:
         write_readme(args.readme, json.load(open(args.record)))
         return

@@ -9,6 +9,10 @@ DESIGN.md section 37.)
       item (pooled over the chains: mean, min, max), the adapted widths, R-hat and ESS of log a_j (quartiles and the worst), the
       posterior mean amplitude of the two halves (mean, quartiles), how often a bumped item's posterior mean exceeds a linear
       item's (the AUC of the posterior mean as a classifier of the halves) and the same for P(a_j <= 1), the wall time.
+  python tools/amp_mix.py --consistent --update both --out profiles/amp_mix_centred.json
+      the same with every iteration a consistent step and the centred update beside the whitened one (--update whitened, centred
+      or both): the record also names the mode and carries the centred update's counters and acceptance.
+      The defaults (--update whitened, no --consistent) reproduce the first run.
 """
 import argparse
 import json
@@ -50,6 +54,8 @@ def main():
     ap.add_argument("--samples", type=int, default=600)
     ap.add_argument("--burn", type=int, default=400)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--update", default="whitened", choices=("whitened", "centred", "both"))
+    ap.add_argument("--consistent", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -57,7 +63,8 @@ def main():
     from gpirt_amd import amp as A
     y, bumped = make(args.n, args.m, args.bump, 20240)
     t0 = time.perf_counter()
-    res = A.run(y, args.samples, args.burn, chains=args.chains, seed=args.seed, store_draws=False)
+    res = A.run(y, args.samples, args.burn, chains=args.chains, seed=args.seed, store_draws=False, update=args.update,
+                consistent=args.consistent)
     wall = time.perf_counter() - t0
     e = res["amp"]
     g = e["grid"]
@@ -79,6 +86,13 @@ def main():
                                bumped_among_top_half=int(bumped[np.argsort(-e["mean"])[: args.m // 2]].sum())),
                counts_total={k: int(e["counts"][:, i].sum()) for i, k in enumerate(("updates", "accepted", "out_of_range", "failed"))},
                smallest=e["smallest"][:5], largest=e["largest"][:5])
+    if args.update != "whitened" or args.consistent:
+        rec.update(update=args.update, consistent=bool(args.consistent))
+    if args.update != "whitened":
+        cc = e["counts_centred"]
+        rec.update(rank=int(e["rank"]), accept_rate_centred=dict(mean=float(np.nanmean(e["accept_rate_centred"])),
+                                                               quantiles=q(e["accept_rate_centred"])),
+                   counts_centred_total={k: int(cc[:, i].sum()) for i, k in enumerate(("updates", "accepted", "same", "failed"))})
     txt = json.dumps(rec, indent=1, default=float)
     print(txt)
     if args.out:
