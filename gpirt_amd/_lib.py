@@ -530,6 +530,18 @@ class AmpCentred(C.Structure):
         (k, C.c_double) for k in ("accept_rate", "last_ms")] + [("reserved", C.c_int64 * 6)]
 
 
+# the centred beta update (include/gpirt_hip.h gpirt_beta_centred; gpirt_amd.beta)
+ST_BETA_CENTRED = 14              # item index item0 + j: index 0 / 1 the two normals
+BETA_CENTRED_RANK = 64
+BETA_CENTRED_COUNTS = ("updates", "failed")                                # the rows of beta_centred_get("counts")
+BETA_CENTRED_STATUS = {0: "updated", 3: "failed"}                          # a record's status by its code
+
+
+class BetaCentred(C.Structure):
+    """gpirt_beta_centred (include/gpirt_hip.h): the calls, the rank and the totals over the items."""
+    _fields_ = [(k, C.c_int64) for k in ("calls", "rank") + BETA_CENTRED_COUNTS] + [("last_ms", C.c_double), ("reserved", C.c_int64 * 6)]
+
+
 class Amp(C.Structure):
     """gpirt_amp (include/gpirt_hip.h): the mode, the grid's size, the totals over the items and the pooled acceptance."""
     _fields_ = [(k, C.c_int64) for k in ("on", "points", "m", "calls") + AMP_COUNTS + ("planned_draws", "recorded")] + [
@@ -801,6 +813,9 @@ SIGNATURES = {
     "gpirt_sampler_amp_stats": (_i32, [_vp, C.POINTER(Amp)]),
     "gpirt_sampler_draw_amp_centred": (_i32, [_vp]),
     "gpirt_sampler_amp_centred_stats": (_i32, [_vp, C.POINTER(AmpCentred)]),
+    "gpirt_sampler_draw_beta_centred": (_i32, [_vp]),
+    "gpirt_sampler_beta_centred_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_beta_centred_stats": (_i32, [_vp, C.POINTER(BetaCentred)]),
     "gpirt_pop_check": (_i32, [C.POINTER(C.c_int32), _i64, _i32, _dp, _i64, _i32, _dbl, _i32, _dbl, _dbl, _i32, _dp, _dp,
                                C.POINTER(_i32), C.POINTER(_i32), C.POINTER(Options)]),
     "gpirt_pop_default_row": (_i32, [_dp]),

@@ -166,7 +166,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 135; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 136; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -234,6 +234,9 @@ int gpirt_version(void) { return 135; }   // 101: gpirt_options names kernel_fp3
                                             // 135: a centred amplitude update on the GP's rank-64 smooth part beside the whitened one
                                             //      (amp_centred.hip, sampler.hip: GPIRT_ST_AMP_CENTRED, gpirt_sampler_draw_amp_centred,
                                             //      gpirt_sampler_amp_centred_stats, new names of gpirt_sampler_amp_get); stage API only
+                                            // 136: a centred beta update, exact Gibbs for the mean's coefficients with f + mu held fixed
+                                            //      (beta_centred.hip, sampler.hip: GPIRT_ST_BETA_CENTRED, gpirt_sampler_draw_beta_centred,
+                                            //      gpirt_sampler_beta_centred_get, gpirt_sampler_beta_centred_stats); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -95,6 +95,27 @@ struct AmpCentredArgs {
 };
 // one centred update of every item's amplitude: the basis, V^T V, the small kernel, T = V^T f, the coefficients, H = V Gc, the update
 int launch_amp_centred(hipStream_t st, const AmpCentredArgs& a);
+// beta_centred.hip: the centred update of the mean function's coefficients, exact Gibbs with f + mu fixed (gpirt_sampler_draw_beta_centred)
+constexpr int BETA_CENTRED_RANK = 64;
+constexpr int64_t BETA_CENTRED_LDS_ROWS = 8192;                         // an item's f column stays in LDS up to this n (64 KB)
+struct BetaCentredArgs {
+    double *f, *beta, *mu, *mu_star; int64_t n, m, N;                   // the state it rewrites: n x m, 2 x m, n x m, N x m
+    const double *theta, *tstar;                                        // n, N
+    const double *pm, *ps;                                              // the prior's means and sds, 2 x m each
+    const double* amp;                                                  // m, or nullptr: every a_j is 1.0
+    const double* nodes; const double* wts;                             // the basis' inputs (launch_nu_lr_basis)
+    const double* F; double eps;                                        // F with Kcc = F F^T, its dead columns zero; the jitter
+    double *V, *Gv, *parts; int nsplit;                                 // n x 64; 64 x 64; nsplit x 64 x 64
+    double *Xh, *R;                                                     // 64 x 64 each: R^-1 F^T and R, R R^T = F^T V^T V F + eps I
+    double *P, *Gx, *W, *B;                                             // 64 x 2, 64 x 2, n x 2 (column-major), 4
+    double *T, *Z, *mean, *beta_old, *beta_new, *chol, *rec;            // 2 x m each (column j: item j), chol 3 x m, rec m
+    long long* counts;                                                  // 2 x m row-major: updates, failed
+    uint64_t seed; uint32_t t; uint32_t item0;
+    int* err;                                                           // the sampler's numeric error word
+    hipEvent_t kev[2];                                                  // with timing on: recorded around the per-item kernel, else null
+};
+// one centred update of every item's coefficients: the basis, V^T V, the small kernel, P, Gx, W, B, the per-item kernel
+int launch_beta_centred(hipStream_t st, const BetaCentredArgs& a);
 // pop.hip: the population prior for theta (gpirt_sampler_pop_*): group means and sds on two grids, and the host tables
 struct PopUpdateArgs {
     const long long* stats;                                             // 4 x G, row-major: n_g, S1, S2, off_grid of this call

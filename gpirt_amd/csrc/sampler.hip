@@ -81,13 +81,11 @@ struct AmpState {
     hipEvent_t tev[2] = {};
     double last_ms = 0.0;
     // The centred update (gpirt_sampler_draw_amp_centred; amp_centred.hip).  Its buffers are one allocation made by its first
-    // call after an enable: a sampler that never calls it has none.  F_ell: the length scale `F` (dead columns zeroed, `live`
-    // their mask, r the live count) was built for.
+    // call after an enable: a sampler that never calls it has none.  F, its live mask and r are the sampler's SmoothF (below),
+    // shared with the centred beta update.
     uint32_t ct = 0;                  // draw_amp_centred calls so far (it survives enabling again, as t)
     double* cbuf = nullptr;
-    AmpCentredArgs ca{};              // the device pointers into cbuf, the tables, the mask
-    bool cF_have = false;
-    double cF_ell = 0.0;
+    AmpCentredArgs ca{};              // the device pointers into cbuf, the tables
     hipEvent_t ctev[2] = {};
     double clast_ms = 0.0;
 };
@@ -111,6 +109,29 @@ struct PopState {
     int32_t* draws = nullptr;                                                              // device: planned x G x 2
     hipEvent_t tev[2] = {};           // with gpirt_sampler_enable_timing on: around the two launches of the last draw_pop
     double last_ms = 0.0;
+};
+
+// F of the rank-64 smooth part, Kcc = F F^T (fstar_free_factor) with its DEAD columns (squared norm <= 1e-13) zeroed on the host,
+// `live` their mask and r the live count, on the device for the kernel with length scale `ell`.  One per sampler, shared by the
+// centred amplitude update and the centred beta update; built by the first call of either and rebuilt only when a sampled length
+// scale's index moved (smooth_factor).
+struct SmoothF {
+    double* F = nullptr;              // device, 64 x 64 (in `allocs`)
+    uint64_t live = 0;
+    int r = 0;
+    bool have = false;
+    double ell = 0.0;
+};
+
+// The centred beta update (gpirt_sampler_draw_beta_centred; include/gpirt_hip.h, beta_centred.hip).  Its buffers are one
+// allocation made by its first call: a sampler that never calls it has none.
+struct BetaCentredState {
+    uint32_t t = 0;                   // draw_beta_centred calls so far
+    double* buf = nullptr;            // device (in `allocs`)
+    BetaCentredArgs a{};              // the device pointers into buf
+    int prior_ok = -1;                // the prior sds are finite and > 0 (host_tmp): -1 not looked at yet
+    hipEvent_t tev[4] = {};           // with timing on: around the call, around its per-item kernel
+    double last_ms = 0.0, item_ms = 0.0;
 };
 
 // The consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad; include/gpirt_hip.h,
@@ -277,6 +298,8 @@ struct gpirt_sampler_s {
     AmpState amp;                     // per-item GP amplitudes (gpirt_sampler_amp_set, gpirt_sampler_amp_enable; mode == 0: off)
     PopState pop;                     // the population prior for theta (gpirt_sampler_pop_set, gpirt_sampler_pop_enable; mode == 0: off)
     CarryState carry;               // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
+    SmoothF sf;                       // F of the rank-64 smooth part with its dead columns zeroed (the two centred updates below)
+    BetaCentredState bc;              // the centred beta update (gpirt_sampler_draw_beta_centred)
 };
 
 namespace {
@@ -2042,6 +2065,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     amp_free(&s->amp);
     pop_free(&s->pop);
     for (hipEvent_t t : s->carry.tev) if (t) hipEventDestroy(t);      // (its two buffers are in `allocs`)
+    for (hipEvent_t t : s->bc.tev) if (t) hipEventDestroy(t);         // (its buffer and the smooth part's F are in `allocs`)
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -3343,7 +3367,7 @@ int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int6
     else if (strcmp(name, "time_centred") == 0) { host = &A.clast_ms; want = 8; }
     else if (strstr(name, "centred") != nullptr || strcmp(name, "rank") == 0 || strcmp(name, "live") == 0) {
         // the centred update's (gpirt_sampler_draw_amp_centred): they exist from its first call on
-        GP_TRY(needs(A.cbuf != nullptr && A.cF_have, "the centred amplitude update's arrays are", "one gpirt_sampler_draw_amp_centred call"));
+        GP_TRY(needs(A.cbuf != nullptr && s->sf.have, "the centred amplitude update's arrays are", "one gpirt_sampler_draw_amp_centred call"));
         const AmpCentredArgs& c = A.ca;
         const int64_t R = AMP_CENTRED_RANK;
         int32_t small[AMP_CENTRED_RANK];
@@ -3351,8 +3375,8 @@ int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int6
             const bool one = name[0] == 'r';
             want = one ? 4 : 4 * R;
             if (bytes != want) { set_error("amplitude: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
-            if (one) small[0] = c.r;
-            else for (int k = 0; k < R; ++k) small[k] = (int32_t)((c.live >> k) & 1ull);
+            if (one) small[0] = s->sf.r;
+            else for (int k = 0; k < R; ++k) small[k] = (int32_t)((s->sf.live >> k) & 1ull);
             memcpy(h_out, small, (size_t)want);
             return 0;
         }
@@ -3367,7 +3391,7 @@ int gpirt_sampler_amp_get(gpirt_sampler_t s, const char* name, void* h_out, int6
         else if (strcmp(name, "centred_H") == 0) { dev = s->NU; want = 8 * s->n * m; }
         else if (strcmp(name, "centred_Xh") == 0) { dev = c.Xh; want = 8 * R * R; }
         else if (strcmp(name, "centred_R") == 0) { dev = c.R; want = 8 * R * R; }
-        else if (strcmp(name, "centred_F") == 0) { dev = c.F; want = 8 * R * R; }
+        else if (strcmp(name, "centred_F") == 0) { dev = s->sf.F; want = 8 * R * R; }
         else { set_error("unknown amplitude array '%s'", name); return GPIRT_E_ARG; }
     }
     else { set_error("unknown amplitude array '%s'", name); return GPIRT_E_ARG; }
@@ -3419,7 +3443,7 @@ static int amp_centred_alloc(gpirt_sampler_t s)
     if (A.cbuf) return 0;
     const size_t n = (size_t)s->n, m = (size_t)s->m, P = (size_t)A.P, R = AMP_CENTRED_RANK, RR = R * R;
     const size_t wide = m > R ? m : R;
-    const size_t sizes[] = { RR, n * R, RR, (size_t)KSPLIT * R * wide, RR, RR, R * m, R * m, R * m, R * m, R * m, m, P, P, 5 * m, 4 * m, R, R };
+    const size_t sizes[] = { n * R, RR, (size_t)KSPLIT * R * wide, RR, RR, R * m, R * m, R * m, R * m, R * m, m, P, P, 5 * m, 4 * m, R, R };
     size_t total = 0;
     for (size_t sz : sizes) total += sz;
     if (hipMalloc((void**)&A.cbuf, sizeof(double) * total) != hipSuccess) { A.cbuf = nullptr; set_error("amplitude (centred): hipMalloc failed"); return GPIRT_E_ALLOC; }
@@ -3427,14 +3451,13 @@ static int amp_centred_alloc(gpirt_sampler_t s)
     auto take = [&](size_t sz) { double* q = p; p += sz; return q; };
     AmpCentredArgs& c = A.ca;
     c = AmpCentredArgs();
-    double* F = take(sizes[0]); c.F = F;
-    c.V = take(sizes[1]); c.Gv = take(sizes[2]); c.parts = take(sizes[3]); c.Xh = take(sizes[4]); c.R = take(sizes[5]);
-    c.T = take(sizes[6]); c.Z = take(sizes[7]); c.W = take(sizes[8]); c.Xi = take(sizes[9]); c.Gc = take(sizes[10]); c.Q = take(sizes[11]);
-    double* ln_a = take(sizes[12]); double* hia = take(sizes[13]);
+    c.V = take(sizes[0]); c.Gv = take(sizes[1]); c.parts = take(sizes[2]); c.Xh = take(sizes[3]); c.R = take(sizes[4]);
+    c.T = take(sizes[5]); c.Z = take(sizes[6]); c.W = take(sizes[7]); c.Xi = take(sizes[8]); c.Gc = take(sizes[9]); c.Q = take(sizes[10]);
+    double* ln_a = take(sizes[11]); double* hia = take(sizes[12]);
     c.ln_a = ln_a; c.half_inv_a2 = hia;
-    c.rec = take(sizes[14]);
-    c.counts = reinterpret_cast<long long*>(take(sizes[15]));
-    double* nodes = take(sizes[16]); double* wts = take(sizes[17]);
+    c.rec = take(sizes[13]);
+    c.counts = reinterpret_cast<long long*>(take(sizes[14]));
+    double* nodes = take(sizes[15]); double* wts = take(sizes[16]);
     c.nodes = nodes; c.wts = wts;
     c.nsplit = KSPLIT;
     std::vector<double> tab(2 * P), hn, hw;
@@ -3454,17 +3477,17 @@ static int amp_centred_alloc(gpirt_sampler_t s)
         set_error("amplitude (centred): the upload failed");
         return GPIRT_E_HIP;
     }
-    A.cF_have = false;
     return 0;
 }
 
-// F for the sampler's current length scale with its dead columns zeroed, the live mask and r (host; cached until the length
-// scale moves).  Drains the handle's stream when it rebuilds.
-static int amp_centred_factor(gpirt_sampler_t s)
+// F for the sampler's current length scale with its dead columns zeroed, the live mask and r (host; cached per sampler until the
+// length scale moves; the two centred updates share it).  Drains the handle's stream when it rebuilds.
+static int smooth_factor(gpirt_sampler_t s)
 {
-    AmpState& A = s->amp;
-    if (A.cF_have && A.cF_ell == s->kern.length_scale) return 0;
+    SmoothF& S = s->sf;
+    if (S.have && S.ell == s->kern.length_scale) return 0;
     constexpr int R = AMP_CENTRED_RANK;
+    if (!S.F) GP_TRY(dalloc(s, &S.F, (size_t)R * R, false));
     std::vector<double> F;
     fstar_free_factor(s->kern, F);
     uint64_t live = 0;
@@ -3476,10 +3499,11 @@ static int amp_centred_factor(gpirt_sampler_t s)
         else { live |= 1ull << k; r += 1; }
     }
     hipStream_t st = s->h->stream;
-    GP_HIP(hipMemcpyAsync(const_cast<double*>(A.ca.F), F.data(), sizeof(double) * F.size(), hipMemcpyHostToDevice, st));
+    S.have = false;
+    GP_HIP(hipMemcpyAsync(S.F, F.data(), sizeof(double) * F.size(), hipMemcpyHostToDevice, st));
     GP_HIP(hipStreamSynchronize(st));                          // (F leaves scope)
-    A.ca.live = live; A.ca.r = r;
-    A.cF_have = true; A.cF_ell = s->kern.length_scale;
+    S.live = live; S.r = r;
+    S.have = true; S.ell = s->kern.length_scale;
     return 0;
 }
 
@@ -3518,8 +3542,9 @@ int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s)
     // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
     GP_TRY(beta_sync(s));
     GP_TRY(amp_centred_alloc(s));
-    GP_TRY(amp_centred_factor(s));
+    GP_TRY(smooth_factor(s));
     AmpCentredArgs a = A.ca;
+    a.F = s->sf.F; a.live = s->sf.live; a.r = s->sf.r;
     a.f = s->f; a.mu = s->mu; a.y = s->y; a.n = s->n; a.m = s->m;
     a.theta = s->theta; a.eps = GPIRT_JITTER;
     a.H = s->NU;                                  // draw_f's prior draw: free between steps
@@ -3552,7 +3577,7 @@ int gpirt_sampler_amp_centred_stats(gpirt_sampler_t s, gpirt_amp_centred* out)
     memset(out, 0, sizeof(*out));
     out->calls = A.ct; out->accept_rate = (double)NAN; out->last_ms = A.clast_ms;
     if (A.mode != 2 || !A.cbuf) return 0;
-    out->rank = A.cF_have ? A.ca.r : 0;
+    out->rank = s->sf.have ? s->sf.r : 0;
     const int64_t m = s->m;
     std::vector<long long> cnt(4 * (size_t)m);
     hipStream_t st = s->h->stream;
@@ -3564,6 +3589,165 @@ int gpirt_sampler_amp_centred_stats(gpirt_sampler_t s, gpirt_amp_centred* out)
     }
     const int64_t decided = out->updates - out->same - out->failed;
     if (decided > 0) out->accept_rate = (double)out->accepted / (double)decided;
+    return 0;
+}
+
+// ---- the centred beta update (beta_centred.hip) ----------------------------------------------------------------------------------
+// the buffers of the first call: one allocation, zeroed (counters and record too), the nodes and weights of the basis.  Drains
+// the handle's stream.
+static int beta_centred_alloc(gpirt_sampler_t s)
+{
+    BetaCentredState& Bc = s->bc;
+    if (Bc.buf) return 0;
+    const size_t n = (size_t)s->n, m = (size_t)s->m, R = BETA_CENTRED_RANK, RR = R * R;
+    const size_t sizes[] = { n * R, RR, (size_t)KSPLIT * RR, RR, RR, 2 * R, 2 * R, 2 * n, 4, 2 * m, 2 * m, 2 * m, 2 * m, 2 * m, 3 * m, m, 2 * m, R, R };
+    size_t total = 0;
+    for (size_t sz : sizes) total += sz;
+    double* buf = nullptr;
+    GP_TRY(dalloc(s, &buf, total, false));
+    double* p = buf;
+    auto take = [&](size_t sz) { double* q = p; p += sz; return q; };
+    BetaCentredArgs& c = Bc.a;
+    c = BetaCentredArgs();
+    c.V = take(sizes[0]); c.Gv = take(sizes[1]); c.parts = take(sizes[2]); c.Xh = take(sizes[3]); c.R = take(sizes[4]);
+    c.P = take(sizes[5]); c.Gx = take(sizes[6]); c.W = take(sizes[7]); c.B = take(sizes[8]);
+    c.T = take(sizes[9]); c.Z = take(sizes[10]); c.mean = take(sizes[11]); c.beta_old = take(sizes[12]); c.beta_new = take(sizes[13]);
+    c.chol = take(sizes[14]); c.rec = take(sizes[15]);
+    c.counts = reinterpret_cast<long long*>(take(sizes[16]));
+    double* nodes = take(sizes[17]); double* wts = take(sizes[18]);
+    c.nodes = nodes; c.wts = wts;
+    c.nsplit = KSPLIT;
+    std::vector<double> hn, hw;
+    nu_lr_nodes(hn, hw);
+    hipStream_t st = s->h->stream;
+    if (hipMemsetAsync(buf, 0, sizeof(double) * total, st) != hipSuccess ||
+        hipMemcpyAsync(nodes, hn.data(), sizeof(double) * R, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(wts, hw.data(), sizeof(double) * R, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        set_error("beta (centred): the upload failed");              // (the buffer stays in `allocs`; the next call tries again)
+        return GPIRT_E_HIP;
+    }
+    Bc.buf = buf;
+    return 0;
+}
+
+int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_draw_beta_centred";
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    if (stream_mode(s)) { set_error("%s: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw", me); return GPIRT_E_ARG; }
+    if (s->opt.kernel_fp32) { set_error("%s: kernel_fp32 is refused, the single-precision build is the default kernel's alone", me); return GPIRT_E_ARG; }
+    if (s->opt.item0 != 0 || (s->opt.m_total > 0 && s->opt.m_total != s->m)) {
+        set_error("%s: an item shard (item0 = %lld, m_total = %lld) is refused, the shared 2 x 2 matrix is built for all items of one sampler", me,
+                  (long long)s->opt.item0, (long long)s->opt.m_total);
+        return GPIRT_E_ARG;
+    }
+    if (!s->nu_kern_ok) {
+        if (s->kern.family != GPIRT_KERNEL_SE) {
+            set_error("%s: the handle's kernel is not a squared exponential, it has no rank-64 form (gpirt_kernel_check(kernel, 64))", me);
+            return GPIRT_E_ARG;
+        }
+        const int rc = kernel_rank_check(s->kern, BETA_CENTRED_RANK, nullptr, nullptr);     // (its message names the length scale)
+        if (rc) return rc;
+        set_error("%s: the length-scale grid's smallest value fails gpirt_kernel_check(kernel, 64)", me);
+        return GPIRT_E_ARG;
+    }
+    if (!s->theta_ok) {
+        set_error("%s: a theta is not finite or lies outside [-5, 5], the rank-64 basis does not hold there", me);
+        return GPIRT_E_ARG;
+    }
+    BetaCentredState& Bc = s->bc;
+    if (Bc.prior_ok < 0) {                        // (the prior is the sampler's for life: looked at once)
+        Bc.prior_ok = 1;
+        const double* ps = s->host_tmp.data() + 2 * s->m;
+        for (int64_t e = 0; e < 2 * s->m; ++e)
+            if (!(ps[e] > 0.0) || !(ps[e] <= 1.79769313486231570815e308)) Bc.prior_ok = 0;
+    }
+    if (!Bc.prior_ok) {
+        set_error("%s: a prior sd of beta is not finite and > 0, the conditional has no precision to add", me);
+        return GPIRT_E_ARG;
+    }
+    // a held-back draw_beta writes beta, mu and mu_star, and nothing on the sampler's own stream may still read what this rewrites
+    GP_TRY(beta_sync(s));
+    GP_TRY(beta_centred_alloc(s));
+    GP_TRY(smooth_factor(s));
+    BetaCentredArgs a = Bc.a;
+    a.f = s->f; a.beta = s->beta; a.mu = s->mu; a.mu_star = s->mu_star; a.n = s->n; a.m = s->m; a.N = s->N;
+    a.theta = s->theta; a.tstar = s->tstar; a.pm = s->pm; a.ps = s->ps;
+    a.amp = s->amp.mode ? s->amp.amp : nullptr;
+    a.F = s->sf.F; a.eps = GPIRT_JITTER;
+    a.seed = s->opt.seed; a.t = Bc.t + 1; a.item0 = (uint32_t)s->opt.item0;
+    a.err = s->flags;
+    hipStream_t st = s->h->stream;
+    const bool timed = s->timing;
+    if (timed) {
+        for (hipEvent_t& t : Bc.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(Bc.tev[0], st));
+        a.kev[0] = Bc.tev[2]; a.kev[1] = Bc.tev[3];
+    }
+    GP_TRY(launch_beta_centred(st, a));
+    Bc.t += 1;
+    if (timed) {                              // (timing on: one synchronisation, as the amplitude updates')
+        GP_HIP(hipEventRecord(Bc.tev[1], st));
+        GP_HIP(hipEventSynchronize(Bc.tev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, Bc.tev[0], Bc.tev[1]);
+        Bc.last_ms = ms;
+        hipEventElapsedTime(&ms, Bc.tev[2], Bc.tev[3]);
+        Bc.item_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_beta_centred_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out);
+    BetaCentredState& Bc = s->bc;
+    if (strcmp(name, "time") == 0 || strcmp(name, "time_item") == 0) {
+        if (bytes != 8) { set_error("beta (centred): '%s' holds 8 bytes, %lld were asked for", name, (long long)bytes); return GPIRT_E_ARG; }
+        memcpy(h_out, name[4] ? &Bc.item_ms : &Bc.last_ms, 8);
+        return 0;
+    }
+    GP_TRY(needs(Bc.buf != nullptr && Bc.t > 0, "the centred beta update's arrays are", "one gpirt_sampler_draw_beta_centred call"));
+    const BetaCentredArgs& c = Bc.a;
+    const int64_t n = s->n, m = s->m, R = BETA_CENTRED_RANK;
+    const void* dev = nullptr;
+    int64_t want = 0;
+    if (strcmp(name, "W") == 0) { dev = c.W; want = 8 * 2 * n; }
+    else if (strcmp(name, "B") == 0) { dev = c.B; want = 8 * 4; }
+    else if (strcmp(name, "P") == 0) { dev = c.P; want = 8 * 2 * R; }
+    else if (strcmp(name, "Gx") == 0) { dev = c.Gx; want = 8 * 2 * R; }
+    else if (strcmp(name, "T") == 0) { dev = c.T; want = 8 * 2 * m; }
+    else if (strcmp(name, "z") == 0) { dev = c.Z; want = 8 * 2 * m; }
+    else if (strcmp(name, "mean") == 0) { dev = c.mean; want = 8 * 2 * m; }
+    else if (strcmp(name, "beta_old") == 0) { dev = c.beta_old; want = 8 * 2 * m; }
+    else if (strcmp(name, "beta_new") == 0) { dev = c.beta_new; want = 8 * 2 * m; }
+    else if (strcmp(name, "chol") == 0) { dev = c.chol; want = 8 * 3 * m; }
+    else if (strcmp(name, "record") == 0) { dev = c.rec; want = 8 * m; }
+    else if (strcmp(name, "counts") == 0) { dev = c.counts; want = 8 * 2 * m; }
+    else { set_error("unknown centred beta array '%s'", name); return GPIRT_E_ARG; }
+    if (bytes != want) { set_error("beta (centred): '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int gpirt_sampler_beta_centred_stats(gpirt_sampler_t s, gpirt_beta_centred* out)
+{
+    GP_ARG(s && out);
+    const BetaCentredState& Bc = s->bc;
+    memset(out, 0, sizeof(*out));
+    out->calls = Bc.t; out->last_ms = Bc.last_ms;
+    if (!Bc.buf) return 0;
+    out->rank = s->sf.have ? s->sf.r : 0;
+    const int64_t m = s->m;
+    std::vector<long long> cnt(2 * (size_t)m);
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(cnt.data(), Bc.a.counts, sizeof(long long) * 2 * (size_t)m, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < m; ++j) { out->updates += cnt[(size_t)j]; out->failed += cnt[(size_t)(m + j)]; }
     return 0;
 }
 

@@ -355,6 +355,10 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: per-item amplitudes are not offered for item shards (the library keeps them for all "
                          "items of one sampler)")
 
+    def draw_beta_centred(self):
+        raise ValueError("ShardedSampler: the centred beta update is not offered for item shards (the library refuses an item "
+                         "shard: its shared 2 x 2 matrix is built for all items of one sampler)")
+
     # -- the population prior for theta (gpirt_amd.pop): the respondent-block theta path would need the codes of its block
     def pop_set(self, codes, log_prior=None):
         raise ValueError("ShardedSampler: a population prior is not offered for item shards (the respondent-block theta path "

@@ -1780,6 +1780,49 @@ class Sampler:
         out["mode"] = _lib.AMP_MODES[int(a.on)]
         return out
 
+    # -- the centred beta update: exact Gibbs for the mean's coefficients with f + mu held fixed (gpirt_sampler_draw_beta_centred)
+    def draw_beta_centred(self):
+        """One centred update of every item's beta (gpirt_sampler_draw_beta_centred; gpirt_amd.beta.centred_shared and
+        centred_exact_update are its NumPy statement): beta_j and f_j move together with f_j + mu_j held fixed, so the likelihood
+        does not change and nothing is accepted or rejected.  Nothing is read back.  It reads the prior density of f, so it
+        belongs behind step(consistent=True)."""
+        self._call("gpirt_sampler_draw_beta_centred")
+
+    def beta_centred(self) -> dict:
+        """The centred beta update's totals (gpirt_sampler_beta_centred_stats): calls, rank, updates, failed and last_ms."""
+        a = _lib.BetaCentred()
+        check(self.lib.gpirt_sampler_beta_centred_stats(self._s, C.byref(a)))
+        out = {k: int(getattr(a, k)) for k in ("calls", "rank") + _lib.BETA_CENTRED_COUNTS}
+        out.update(last_ms=float(a.last_ms))
+        return out
+
+    def beta_centred_get(self, name: str) -> np.ndarray:
+        """One array of the last draw_beta_centred() by name: W (n x 2), B (2 x 2), P, Gx (64 x 2), T, z, mean, beta_old, beta_new
+        (2 x m, as beta), chol (3 x m: c00, c10, c11), record (m: status, 0 updated, 3 failed), counts (int64, 2 x m: updates,
+        failed), time (1: ms of device time of the last call with enable_timing() on), time_item (1: of that, the per-item
+        kernel's)."""
+        m, R = self.m, _lib.BETA_CENTRED_RANK
+        if name == "W":
+            out = np.empty((self.n, 2), order="F")
+        elif name == "B":
+            out = np.empty((2, 2), order="F")
+        elif name in ("P", "Gx"):
+            out = np.empty((R, 2), order="F")
+        elif name in ("T", "z", "mean", "beta_old", "beta_new"):
+            out = np.empty((2, m), order="F")
+        elif name == "chol":
+            out = np.empty((3, m), order="F")
+        elif name == "counts":
+            out = np.empty((2, m), dtype=np.int64)
+        elif name == "record":
+            out = np.empty(m)
+        elif name in ("time", "time_item"):
+            out = np.empty(1)
+        else:
+            raise ValueError(f"unknown centred beta array {name!r}")
+        self._get_into("gpirt_sampler_beta_centred_get", name, out)
+        return out
+
     # -- the population prior for theta, fixed or sampled in the chain (include/gpirt_hip.h gpirt_sampler_pop_*, gpirt_amd.pop)
     def pop_set(self, codes, log_prior=None):
         """A fixed population prior: one code per respondent in 0 .. G - 1 (every group with a member) and a G x 1001 table of

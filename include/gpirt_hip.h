@@ -56,6 +56,7 @@ enum {
     GPIRT_ST_FSTAR = 5, GPIRT_ST_THETA = 6, GPIRT_ST_BETA = 7,
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
     GPIRT_ST_AMP_CENTRED = 13,  /* the centred amplitude update (gpirt_sampler_draw_amp_centred): item index item0 + j, index 0 .. 63 the normals of the augmentation, 64 / 65 the two uniforms; nothing else draws from it */
+    GPIRT_ST_BETA_CENTRED = 14, /* the two normals per item of the centred beta update (gpirt_sampler_draw_beta_centred): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
@@ -2304,6 +2305,80 @@ typedef struct gpirt_amp_centred {
 } gpirt_amp_centred;
 int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s);
 int gpirt_sampler_amp_centred_stats(gpirt_sampler_t s, gpirt_amp_centred* out);
+
+/* ------------------------------------------------------ a centred beta update: exact Gibbs with f + mu held fixed ------ */
+/* Library version 136.  gpirt_sampler_draw_beta is the reference's: one random-walk Metropolis step per coefficient of
+ * mu_j = beta_0j + beta_1j theta with f_j held fixed, at step sizes the caller gives.  The likelihood reads only g_j = f_j + mu_j
+ * and with thousands of answers per item pins it down, so a step that moves mu_j under a fixed f_j is accepted only when tiny, and
+ * the linear trend wanders between f_j and mu_j as slowly as draw_f lets it.  gpirt_sampler_draw_beta_centred is the centred move
+ * Murray & Adams (2010) and Yu & Meng (2011) pair such an update with, as gpirt_sampler_draw_ell_centred and
+ * gpirt_sampler_draw_amp_centred do for their parameters: beta_j and f_j move together with g_j held fixed.  The likelihood does
+ * not change at all, there is no accept step, and the conditional of beta_j is Gaussian in closed form.  It reads the prior
+ * density of f, so it belongs behind gpirt_sampler_step_consistent (after the reference's step f sits at the old theta, quirk
+ * Q3); it is not refused behind a plain step, which measurements need.  It needs no factor, dense or structured: only the rank-64
+ * identity K(theta, theta) = Phi Phi^T, Phi = V F, which gpirt_sampler_draw_amp_centred builds (V the Lagrange basis at theta on
+ * the 64 Chebyshev nodes, Kcc = F F^T with its dead columns zeroed).  Stage API only: gpirt_options, gpirt_run, gpirt_mcmc*,
+ * gpirt_sampler_step* and gpirt_sampler_draw_beta keep their layout and behaviour, every existing stage keeps its uniforms, and a
+ * sampler on which the entry is never called computes bit for bit what it did.
+ *
+ * With X = [1, theta] (n x 2), S = K(theta, theta) + eps I, eps = GPIRT_JITTER, the amplitude a_j (1.0 exactly when amplitudes
+ * are off; fixed and sampled amplitudes are both taken) and the independent priors beta_kj ~ N(m0_kj, s0_kj^2) of the sampler:
+ *     f_j = g_j - X beta_j ~ N(0, a_j^2 S)   =>   beta_j | g_j, theta, a_j ~ N(Lam_j^-1 b_j, Lam_j^-1)
+ *     Lam_j = B / a_j^2 + diag(1 / s0_kj^2),   B = X^T S^-1 X (2 x 2, shared by all items),   W = S^-1 X (n x 2, shared)
+ *     b_j   = X^T S^-1 g_j / a_j^2 + m0_j / s0_j^2 = (W^T f_j + B beta_j) / a_j^2 + m0_j / s0_j^2
+ *     f_j'  = f_j + X (beta_j - beta_j'),   mu_j' = X beta_j',   g_j' = g_j.
+ * One call updates every item once; t is the count of gpirt_sampler_draw_beta_centred calls over the sampler's life from 1.
+ * ROW ORDER below means ell_delta_kernel's: thread t of 256 takes the rows t, t + 256, ... ascending into one accumulator
+ * that starts at 0, then the fixed LDS tree s = 128, 64, .., 1 with acc[t] += acc[t + s].  The library is built without
+ * contraction: fma where written, nothing else fused.
+ *   1. shared    (from theta alone) the call joins a held-back draw_beta, builds V from the current theta and Gv = V^T V by the
+ *                split-K product in index order, Xh = R^-1 F^T and R with A = Phi^T Phi + eps I = R R^T in one work-group (a bad
+ *                pivot raises the sampler's numeric error word as the theta-alone draw_fstar does).  F and its live mask are the
+ *                ones gpirt_sampler_draw_amp_centred caches per sampler, rebuilt only when a sampled length scale's index moved.
+ *                P = V^T X (64 x 2): P[c, 0] = sum_i V[i, c] by plain sums, P[c, 1] by fma(V[i, c], theta_i, .), both in row
+ *                order.  u = Xh P: u[k, q] = fma(Xh(k, i), P[i, q], .) over i ascending.  Gx = Xh^T u (= F A^-1 Phi^T X):
+ *                Gx[c, q] = fma(Xh(k, c), u[k, q], .) over k ascending.  W[i, q] = (X[i, q] - sum_c V[i, c] Gx[c, q]) / eps, the
+ *                sum over c ascending by fma from 0, then one subtraction and one division.  B00 = sum_i W[i, 0] (plain sums),
+ *                B01 = B10 = fma(W[i, 0], theta_i, .), B11 = fma(W[i, 1], theta_i, .), each in row order.
+ *   2. per item  (one work-group per item) T_j[k] = fma(W[i, k], f[i, j], .) in row order; ia = 1 / (a_j a_j); p_k =
+ *                1 / (s0_kj s0_kj); b_k = (T_j[k] + (B_k0 beta_0j + B_k1 beta_1j)) ia + m0_kj p_k; Lam00 = B00 ia + p_0,
+ *                Lam10 = B10 ia, Lam11 = B11 ia + p_1; c00 = sqrt(Lam00), c10 = Lam10 / c00, c11 = sqrt(Lam11 - c10 c10);
+ *                y0 = b_0 / c00, y1 = (b_1 - c10 y0) / c11, mean_1 = y1 / c11, mean_0 = (y0 - c10 mean_1) / c00;
+ *                z_k = qnorm_as241(item_uniform(seed, t, GPIRT_ST_BETA_CENTRED, item0 + j, k)), k = 0, 1; x1 = z_1 / c11,
+ *                x0 = (z_0 - c10 x1) / c00; beta'_k = mean_k + x_k.
+ *                A non-finite T, Lam, pivot, mean or beta', or a pivot (Lam00, Lam11 - c10 c10) that is not > 0: `failed`;
+ *                the item's f column, beta, mu and mu_star then stay byte for byte.  It is not an error.
+ *   3. rewrite   (the same work-group) mo_i = beta_0j + theta_i beta_1j, the bits mu[i, j] holds behind draw_beta;
+ *                mu[i, j] = beta'_0 + theta_i beta'_1 and mu_star[i, j] = beta'_0 + theta*_i beta'_1, the bits the linear mean
+ *                of gpirt_sampler_draw_beta gives for beta', so the state is what draw_beta would have left; f'_i = f_i +
+ *                (mo_i - mu[i, j]): two products and four sums, no FMA.  The shift is the difference of the two ROUNDED means
+ *                and not d_0 + theta_i d_1 with d = beta - beta': that form rounds theta_i beta_1 apart from mu's own rounding,
+ *                and where beta_0 and theta_i beta_1 cancel g'_i - g_i would exceed 4 u (|f| + |mu| + |mu'|).  As it is,
+ *                |g'_i - g_i| <= u |mo_i - mu_i| + u |f'_i|, within that bound in every cell.  The column of f stays in LDS
+ *                between the reduction and the rewrite up to n = 8192 and is read again above.
+ * No floating-point atomic, one writer per value: two runs give a byte-identical state.
+ *
+ * gpirt_sampler_beta_centred_get, by name, all of the last call (they need one gpirt_sampler_draw_beta_centred first, "time"
+ * excepted): "W" (n x 2 doubles, column-major), "B" (4 doubles: B00, B10, B01, B11), "P", "Gx" (64 x 2, column-major), "T", "z",
+ * "mean", "beta_old", "beta_new" (2 x m doubles, column j item j, as beta; beta_new of a failed item is beta_old), "chol" (3 x m:
+ * c00, c10, c11 of item j in column j), "record" (m doubles: status 0 updated, 3 failed), "counts" (2 x m int64, row-major:
+ * updates, failed), "time" (1 double: ms of device time of the last call with gpirt_sampler_enable_timing on, else 0),
+ * "time_item" (1 double: of that, the per-item kernel's).
+ * gpirt_sampler_beta_centred_stats: the totals.
+ *
+ * Refused with GPIRT_E_ARG, each with its reason: before gpirt_sampler_init; GPIRT_RNG_RSTREAM; an item shard; kernel_fp32; a
+ * handle kernel that fails gpirt_kernel_check(kernel, 64) (Matern, too short a length scale); a theta the sampler does not vouch
+ * for (not finite or outside [-5, 5]); a prior sd that is not finite and > 0. */
+typedef struct gpirt_beta_centred {
+    int64_t  calls;                         /* t: gpirt_sampler_draw_beta_centred calls over the sampler's life */
+    int64_t  rank;                          /* the live columns of F at the last call (0 before the first) */
+    int64_t  updates, failed;               /* summed over the items: every item of every call, and those that failed */
+    double   last_ms;                       /* device time of the last call with gpirt_sampler_enable_timing on, else 0 */
+    int64_t  reserved[6];
+} gpirt_beta_centred;
+int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s);
+int gpirt_sampler_beta_centred_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_beta_centred_stats(gpirt_sampler_t s, gpirt_beta_centred* out);
 
 /* ------------------------------------------------------ a consistent step: f carried to the new theta, a prior check ---- */
 /* Library version 133.  The reference's iteration moves theta and keeps f (quirk Q3 of SURVEY.md): behind gpirt_sampler_step
