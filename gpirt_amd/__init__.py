@@ -18,6 +18,8 @@ Layout:
                    prior check: the NumPy statement of the carry, the device's normals, the exact prior quadratic form
   pop.py           a population prior for theta, a table per group, fixed or with the groups' means and sds sampled by exact
                    Gibbs on two grids: the NumPy statement of one update, the exact conditional masses, the one-call run
+  scale.py         the collapsed scale and shift move on the linear mean with theta summed out: the NumPy statement of one
+                   call, the collapsed target, the one-call run
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

@@ -542,6 +542,21 @@ class BetaCentred(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("calls", "rank") + BETA_CENTRED_COUNTS] + [("last_ms", C.c_double), ("reserved", C.c_int64 * 6)]
 
 
+# the collapsed scale and shift move (include/gpirt_hip.h gpirt_scale; gpirt_amd.scale)
+ST_SCALE = 15                      # item index the kind (0 scale, 1 shift): index 0 the normal's uniform, 1 the decision's
+SCALE_KINDS = ("scale", "shift")
+SCALE_RECORD = ("kind", "z", "step", "c", "D", "Q", "J", "log_r", "u", "log_u", "status", "bad", "t", "width", "_14", "_15")
+SCALE_STATUS = {0: "rejected", 1: "accepted", 2: "failed"}
+SCALE_COUNTS = ("calls", "accepted", "failed")                              # the rows of scale_get("counts"), a column per kind
+SCALE_TIMES = ("whole", "curve", "product", "logz", "decide", "commits")
+
+
+class Scale(C.Structure):
+    """gpirt_scale (include/gpirt_hip.h): per kind the calls, the accepted and failed ones, the width and the last call's time."""
+    _fields_ = [("on", C.c_int64), ("calls", C.c_int64 * 2), ("accepted", C.c_int64 * 2), ("failed", C.c_int64 * 2),
+                ("width", C.c_double * 2), ("last_ms", C.c_double * 2), ("reserved", C.c_int64 * 5)]
+
+
 class Amp(C.Structure):
     """gpirt_amp (include/gpirt_hip.h): the mode, the grid's size, the totals over the items and the pooled acceptance."""
     _fields_ = [(k, C.c_int64) for k in ("on", "points", "m", "calls") + AMP_COUNTS + ("planned_draws", "recorded")] + [
@@ -816,6 +831,12 @@ SIGNATURES = {
     "gpirt_sampler_draw_beta_centred": (_i32, [_vp]),
     "gpirt_sampler_beta_centred_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_beta_centred_stats": (_i32, [_vp, C.POINTER(BetaCentred)]),
+    "gpirt_sampler_scale_enable": (_i32, [_vp, _dbl, _dbl]),
+    "gpirt_sampler_scale_width": (_i32, [_vp, _i32, _dbl]),
+    "gpirt_sampler_draw_scale": (_i32, [_vp, _i32]),
+    "gpirt_sampler_scale_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_scale_stats": (_i32, [_vp, C.POINTER(Scale)]),
+    "gpirt_sampler_step_consistent_scale": (_i32, [_vp, _i32, _i32]),
     "gpirt_pop_check": (_i32, [C.POINTER(C.c_int32), _i64, _i32, _dp, _i64, _i32, _dbl, _i32, _dbl, _dbl, _i32, _dp, _dp,
                                C.POINTER(_i32), C.POINTER(_i32), C.POINTER(Options)]),
     "gpirt_pop_default_row": (_i32, [_dp]),

@@ -166,7 +166,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 136; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 137; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -237,6 +237,9 @@ int gpirt_version(void) { return 136; }   // 101: gpirt_options names kernel_fp3
                                             // 136: a centred beta update, exact Gibbs for the mean's coefficients with f + mu held fixed
                                             //      (beta_centred.hip, sampler.hip: GPIRT_ST_BETA_CENTRED, gpirt_sampler_draw_beta_centred,
                                             //      gpirt_sampler_beta_centred_get, gpirt_sampler_beta_centred_stats); stage API only
+                                            // 137: a collapsed scale and shift move on the linear mean with theta summed out (scale.hip,
+                                            //      sampler.hip: GPIRT_ST_SCALE, gpirt_sampler_scale_enable, gpirt_sampler_draw_scale,
+                                            //      gpirt_sampler_scale_width / _get / _stats, gpirt_sampler_step_consistent_scale); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -116,6 +116,24 @@ struct BetaCentredArgs {
 };
 // one centred update of every item's coefficients: the basis, V^T V, the small kernel, P, Gx, W, B, the per-item kernel
 int launch_beta_centred(hipStream_t st, const BetaCentredArgs& a);
+// scale.hip: the collapsed scale and shift move, the linear mean's coefficients with theta summed out (gpirt_sampler_draw_scale)
+enum { SCALE_REC_KIND = 0, SCALE_REC_Z, SCALE_REC_STEP, SCALE_REC_C, SCALE_REC_D, SCALE_REC_Q, SCALE_REC_J, SCALE_REC_LOGR,
+       SCALE_REC_U, SCALE_REC_LOGU, SCALE_REC_STATUS, SCALE_REC_BAD, SCALE_REC_T, SCALE_REC_WIDTH, SCALE_REC_COUNT = 16 };
+struct ScaleArgs {
+    double *beta, *mu, *mu_star, *fstar, *logpost, *gbar; int64_t n, m, N;   // the state an accepted move rewrites (gbar: or nullptr)
+    const double* theta;                                                // n
+    const double *pm, *ps;                                              // the prior's means and sds, 2 x m each
+    const double* log_prior; const int* codes;                          // the population prior's table and codes, or nullptr
+    double *beta_prop, *mu2, *fstar2, *logpost2;                        // the proposal: 2 x m, N x m, N x m, N x n
+    double *lz, *lz_prop, *dlz; int* bad;                               // n each
+    double* rec;                                                        // SCALE_REC_COUNT doubles
+    long long* counts;                                                  // 3 x 2 row-major: calls, accepted, failed of kind 0 / 1
+    int kind; double width;
+    uint64_t seed; uint32_t t;
+    hipEvent_t kev[4];                                                  // with timing on: around logz, decide, the commits; else null
+};
+int launch_scale_curve(hipStream_t st, const ScaleArgs& a);             // z, the step, beta', mu2, fstar2
+int launch_scale_decide(hipStream_t st, const ScaleArgs& a);            // lz, lz', the decision and the conditional commits
 // pop.hip: the population prior for theta (gpirt_sampler_pop_*): group means and sds on two grids, and the host tables
 struct PopUpdateArgs {
     const long long* stats;                                             // 4 x G, row-major: n_g, S1, S2, off_grid of this call

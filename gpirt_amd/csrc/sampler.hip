@@ -134,6 +134,20 @@ struct BetaCentredState {
     double last_ms = 0.0, item_ms = 0.0;
 };
 
+// The collapsed scale and shift move (gpirt_sampler_scale_enable, gpirt_sampler_draw_scale; include/gpirt_hip.h, scale.hip).
+// Its buffers are allocated by gpirt_sampler_scale_enable through `allocs`: a sampler that never enables it has none.
+struct ScaleState {
+    bool on = false;
+    uint32_t t[2] = {};               // draw_scale calls so far, per kind
+    double width[2] = {};             // the proposal's sd: of eps (scale), of delta (shift)
+    ScaleArgs a{};                    // the device pointers of the proposal's buffers, the vectors, the record, the counters
+    int last_kind = -1;
+    int prior_ok = -1;                // the prior sds are finite and > 0 (host_tmp): -1 not looked at yet
+    hipEvent_t tev[7] = {};           // with timing on: the call's start, behind the curve, behind the product, logz, decide, commits
+    double last_ms[2] = {};
+    double times[6] = {};             // of the last timed call: whole, curve, product, logz, decide, commits
+};
+
 // The consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad; include/gpirt_hip.h,
 // carry.hip).  Both buffers are allocated by the first call that needs them: a sampler that never calls either has neither.
 struct CarryState {
@@ -300,6 +314,10 @@ struct gpirt_sampler_s {
     CarryState carry;               // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
     SmoothF sf;                       // F of the rank-64 smooth part with its dead columns zeroed (the two centred updates below)
     BetaCentredState bc;              // the centred beta update (gpirt_sampler_draw_beta_centred)
+    ScaleState sc;                    // the collapsed scale and shift move (gpirt_sampler_scale_enable; on == false: off)
+    // logpost (N x n) is theta_partial's product for the fstar, beta and population prior in place: set by theta_partial, kept
+    // by gpirt_sampler_draw_scale, cleared by every writer of fstar, beta, f, theta or the population prior's table
+    bool lp_current = false;
 };
 
 namespace {
@@ -609,6 +627,7 @@ int z_sync(gpirt_sampler_s* s)
 
 int do_draw_f(gpirt_sampler_s* s)
 {
+    s->lp_current = false;
     gpirt_handle_t h = s->h;
     hipStream_t st = h->stream;
     const int64_t n = s->n, m = s->m;
@@ -878,6 +897,7 @@ int fstar_prep(gpirt_sampler_s* s, gpirt_handle_t hh)
 
 int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
 {
+    s->lp_current = false;
     gpirt_handle_t h = s->h;
     hipStream_t st = h->stream;
     const int64_t n = s->n, m = s->m, N = s->N;
@@ -963,7 +983,10 @@ int do_draw_fstar(gpirt_sampler_s* s, uint32_t iter)
     return launch_fstar_epilogue(st, a);                                                      // :26-28
 }
 
-int do_theta_partial(gpirt_sampler_s* s)
+// logpost_out (N x n) from the curve fstar_in (N x m) through the sampler's scratch (tfd, tf_gq, tf_aux, Gpm): what
+// theta_partial launches, also for the proposal's curve of gpirt_sampler_draw_scale (the scratch is free again once the first
+// product has finished on the stream)
+int theta_product(gpirt_sampler_s* s, const double* fstar_in, double* logpost_out)
 {
     hipStream_t st = s->h->stream;
     const int64_t n = s->n, m = s->m, N = s->N;
@@ -973,12 +996,19 @@ int do_theta_partial(gpirt_sampler_s* s)
     // could not be scaled (|f*| beyond exp()'s range, non-finite), or instead of it with GPIRT_THETA_FIXED=2
     const int* only_if = nullptr;
     if (s->h->cfg.theta_fixed == 1) {
-        GP_TRY(launch_theta_fixed(st, s->fstar, N, n, m, s->tfd, s->tf_y8, s->tf_gq, s->tf_aux, s->logpost, N, false, s->h));
+        GP_TRY(launch_theta_fixed(st, fstar_in, N, n, m, s->tfd, s->tf_y8, s->tf_gq, s->tf_aux, logpost_out, N, false, s->h));
         only_if = tf_overflow(s->tf_aux, s->tfd);
     }
-    GP_TRY(launch_loglik_terms(st, s->fstar, N, m, s->Gpm, Np, only_if));
-    GP_TRY(launch_gemm(s->h, st, false, true, TRI_NONE, N, n, 2 * m, 1.0, s->Gpm, Np, s->Ypm, n, 0.0, s->logpost, N, Np, only_if));
-    return launch_theta_nan_fix(st, s->Gpm, Np, s->Ypm, n, m, s->logpost, N, N, only_if);   // (a missing answer over a NaN f*)
+    GP_TRY(launch_loglik_terms(st, fstar_in, N, m, s->Gpm, Np, only_if));
+    GP_TRY(launch_gemm(s->h, st, false, true, TRI_NONE, N, n, 2 * m, 1.0, s->Gpm, Np, s->Ypm, n, 0.0, logpost_out, N, Np, only_if));
+    return launch_theta_nan_fix(st, s->Gpm, Np, s->Ypm, n, m, logpost_out, N, N, only_if);   // (a missing answer over a NaN f*)
+}
+
+int do_theta_partial(gpirt_sampler_s* s)
+{
+    GP_TRY(theta_product(s, s->fstar, s->logpost));
+    s->lp_current = true;
+    return 0;
 }
 
 int do_theta_finish(gpirt_sampler_s* s)
@@ -992,6 +1022,7 @@ int do_theta_finish(gpirt_sampler_s* s)
     if (s->pop.mode) { a.log_prior = s->pop.log_prior; a.codes = s->pop.codes; }           // (the group's row in place of N(0, 1))
     GP_TRY(launch_theta_sample(st, a));
     if (stream_mode(s)) GP_TRY(launch_advance_pos(st, s->pos, (uint64_t)s->n));
+    s->lp_current = false;
     s->theta_ok = true;                   // grid values
     return 0;
 }
@@ -1025,6 +1056,7 @@ int do_theta_block(gpirt_sampler_s* s)
 
 int launch_beta_on(gpirt_sampler_s* s, hipStream_t st)
 {
+    s->lp_current = false;
     BetaArgs a{};
     a.beta = s->beta; a.theta = s->theta; a.y = s->y; a.f = s->f; a.pm = s->pm; a.ps = s->ps;
     a.step = s->step; a.n = s->n; a.m = s->m; a.N = s->N; a.mu = s->mu; a.mu_star = s->mu_star;
@@ -1080,6 +1112,7 @@ int do_carry_f(gpirt_sampler_s* s, int nugget, bool timed)
     hipStream_t st = s->h->stream;
     // a draw_beta still held back or running on the sampler's own stream reads the f this stage rewrites (inside a step: none)
     GP_TRY(beta_sync(s));
+    s->lp_current = false;
     if (!c.counters) {
         GP_TRY(dalloc(s, &c.counters, 6));
         GP_HIP(hipMemsetAsync(c.counters, 0, 6 * sizeof(unsigned long long), st));
@@ -1393,6 +1426,7 @@ int do_draw_ell(gpirt_sampler_s* s, int kind)
     hipStream_t st = h->stream;
     const int64_t n = s->n, m = s->m;
     GP_TRY(ell_settle_factor(s));
+    s->lp_current = false;
     // the call is counted, and its pair of uniforms consumed, when it ends in one of the four outcomes: an update that returns
     // an error has not happened (updates = accepted + rejected + out_of_range + failed at all times)
     const uint32_t t = c.t + 1;
@@ -2066,6 +2100,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     pop_free(&s->pop);
     for (hipEvent_t t : s->carry.tev) if (t) hipEventDestroy(t);      // (its two buffers are in `allocs`)
     for (hipEvent_t t : s->bc.tev) if (t) hipEventDestroy(t);         // (its buffer and the smooth part's F are in `allocs`)
+    for (hipEvent_t t : s->sc.tev) if (t) hipEventDestroy(t);         // (the scale move's buffers are in `allocs`)
     if (s->hU) hipHostFree(s->hU);
     if (s->h_pos) hipHostFree(s->h_pos);
     if (s->h_flags) hipHostFree(s->h_flags);
@@ -2226,6 +2261,7 @@ int gpirt_sampler_theta_commit(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised && s->theta_stage);
     GP_HIP(hipMemcpyAsync(s->theta, s->theta_stage, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, s->h->stream));
+    s->lp_current = false;
     s->theta_ok = true;                   // the ranks' blocks of grid values, summed
     return 0;
 }
@@ -3541,6 +3577,7 @@ int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s)
     }
     // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
     GP_TRY(beta_sync(s));
+    s->lp_current = false;
     GP_TRY(amp_centred_alloc(s));
     GP_TRY(smooth_factor(s));
     AmpCentredArgs a = A.ca;
@@ -3670,6 +3707,7 @@ int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s)
     }
     // a held-back draw_beta writes beta, mu and mu_star, and nothing on the sampler's own stream may still read what this rewrites
     GP_TRY(beta_sync(s));
+    s->lp_current = false;
     GP_TRY(beta_centred_alloc(s));
     GP_TRY(smooth_factor(s));
     BetaCentredArgs a = Bc.a;
@@ -3751,6 +3789,238 @@ int gpirt_sampler_beta_centred_stats(gpirt_sampler_t s, gpirt_beta_centred* out)
     return 0;
 }
 
+// ---- the collapsed scale and shift move (scale.hip) ------------------------------------------------------------------------------
+static const char* const SCALE_KIND_NAME[2] = { "scale", "shift" };
+
+static int scale_width_check(const char* me, int kind, double w)
+{
+    if (!(w >= 0.0) || !(w <= 1.79769313486231570815e308)) {
+        set_error("%s: the %s width = %g, it must be finite and >= 0", me, SCALE_KIND_NAME[kind], w);
+        return GPIRT_E_ARG;
+    }
+    return 0;
+}
+
+// what gpirt_sampler_scale_enable and gpirt_sampler_draw_scale both refuse, each with its reason
+static int scale_refusals(gpirt_sampler_t s, const char* me)
+{
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    if (stream_mode(s)) { set_error("%s: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw", me); return GPIRT_E_ARG; }
+    if (s->opt.item0 != 0 || (s->opt.m_total > 0 && s->opt.m_total != s->m)) {
+        set_error("%s: an item shard (item0 = %lld, m_total = %lld) is refused, logpost then holds only part of the items", me,
+                  (long long)s->opt.item0, (long long)s->opt.m_total);
+        return GPIRT_E_ARG;
+    }
+    if (s->fstar_full) {
+        set_error("%s is refused while gpirt_sampler_set_theta_block is in use: logpost then holds only part of the items", me);
+        return GPIRT_E_ARG;
+    }
+    ScaleState& Sc = s->sc;
+    if (Sc.prior_ok < 0) {                        // (the prior is the sampler's for life: looked at once)
+        Sc.prior_ok = 1;
+        const double* ps = s->host_tmp.data() + 2 * s->m;
+        for (int64_t e = 0; e < 2 * s->m; ++e)
+            if (!(ps[e] > 0.0) || !(ps[e] <= 1.79769313486231570815e308)) Sc.prior_ok = 0;
+    }
+    if (!Sc.prior_ok) {
+        set_error("%s: a prior sd of beta is not finite and > 0, the move's prior ratio is not defined", me);
+        return GPIRT_E_ARG;
+    }
+    return 0;
+}
+
+int gpirt_sampler_scale_enable(gpirt_sampler_t s, double w_scale, double w_shift)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_scale_enable";
+    GP_TRY(scale_refusals(s, me));
+    // the defaults: a choice, not a measurement (the sum of n respondents' dlz has a curvature of order n)
+    const double dflt = 1.0 / sqrt((double)s->n);
+    if (w_scale != w_scale) w_scale = dflt;
+    if (w_shift != w_shift) w_shift = dflt;
+    GP_TRY(scale_width_check(me, 0, w_scale));
+    GP_TRY(scale_width_check(me, 1, w_shift));
+    ScaleState& Sc = s->sc;
+    if (!Sc.on) {
+        const size_t n = (size_t)s->n, m = (size_t)s->m, N = (size_t)s->N;
+        ScaleArgs& a = Sc.a;
+        a = ScaleArgs();
+        GP_TRY(dalloc(s, &a.fstar2, N * m + 2));
+        GP_TRY(dalloc(s, &a.mu2, N * m + 2));
+        GP_TRY(dalloc(s, &a.logpost2, N * n + 2));
+        GP_TRY(dalloc(s, &a.beta_prop, 2 * m));
+        double* vec = nullptr;
+        GP_TRY(dalloc(s, &vec, 3 * n + SCALE_REC_COUNT, false));
+        a.lz = vec; a.lz_prop = vec + n; a.dlz = vec + 2 * n; a.rec = vec + 3 * n;
+        GP_TRY(dalloc(s, &a.bad, n));
+        GP_TRY(dalloc(s, &a.counts, 6));
+        hipStream_t st = s->h->stream;
+        GP_HIP(hipMemsetAsync(vec, 0, sizeof(double) * (3 * n + SCALE_REC_COUNT), st));
+        GP_HIP(hipMemsetAsync(a.bad, 0, sizeof(int) * n, st));
+        GP_HIP(hipMemsetAsync(a.counts, 0, sizeof(long long) * 6, st));
+        Sc.on = true;
+    }
+    Sc.width[0] = w_scale; Sc.width[1] = w_shift;
+    return 0;
+}
+
+int gpirt_sampler_scale_width(gpirt_sampler_t s, int kind, double w)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_scale_width";
+    GP_TRY(needs(s->sc.on, "the scale and shift move is", "gpirt_sampler_scale_enable"));
+    if (kind != 0 && kind != 1) { set_error("%s: kind = %d, it must be 0 (scale) or 1 (shift)", me, kind); return GPIRT_E_ARG; }
+    GP_TRY(scale_width_check(me, kind, w));
+    s->sc.width[kind] = w;
+    return 0;
+}
+
+// one proposal of the kind on the main stream; nothing is read back.  timed: its events are recorded, the caller reads them
+static int do_draw_scale(gpirt_sampler_t s, int kind, const char* me, bool timed)
+{
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    GP_TRY(needs(s->sc.on, "the scale and shift move is", "gpirt_sampler_scale_enable"));
+    GP_TRY(scale_refusals(s, me));
+    if (kind != 0 && kind != 1) { set_error("%s: kind = %d, it must be 0 (scale) or 1 (shift)", me, kind); return GPIRT_E_ARG; }
+    // a held-back draw_beta writes beta, mu and mu_star (and with them makes logpost stale): it runs first
+    GP_TRY(beta_sync(s));
+    if (!s->lp_current) {
+        set_error("%s: logpost is not current, the move belongs between gpirt_sampler_theta_partial and gpirt_sampler_theta_finish "
+                  "(a stage that writes fstar, beta, f, theta or the population prior ran since the last theta_partial)", me);
+        return GPIRT_E_ARG;
+    }
+    ScaleState& Sc = s->sc;
+    ScaleArgs a = Sc.a;
+    a.beta = s->beta; a.mu = s->mu; a.mu_star = s->mu_star; a.fstar = s->fstar; a.logpost = s->logpost;
+    a.gbar = s->shape.on ? s->shape.gbar : nullptr;
+    a.n = s->n; a.m = s->m; a.N = s->N; a.theta = s->theta; a.pm = s->pm; a.ps = s->ps;
+    if (s->pop.mode) { a.log_prior = s->pop.log_prior; a.codes = s->pop.codes; }
+    a.kind = kind; a.width = Sc.width[kind]; a.seed = s->opt.seed; a.t = Sc.t[kind] + 1;
+    hipStream_t st = s->h->stream;
+    if (timed) {
+        for (hipEvent_t& t : Sc.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(Sc.tev[0], st));
+        for (int k = 0; k < 4; ++k) a.kev[k] = Sc.tev[3 + k];
+    }
+    GP_TRY(launch_scale_curve(st, a));
+    if (timed) GP_HIP(hipEventRecord(Sc.tev[1], st));
+    GP_TRY(theta_product(s, a.fstar2, a.logpost2));
+    if (timed) GP_HIP(hipEventRecord(Sc.tev[2], st));
+    GP_TRY(launch_scale_decide(st, a));
+    Sc.t[kind] += 1;
+    Sc.last_kind = kind;
+    return 0;                                     // (lp_current stays: logpost is the standing curve's either way)
+}
+
+static int scale_read_times(gpirt_sampler_t s)
+{
+    ScaleState& Sc = s->sc;
+    GP_HIP(hipEventSynchronize(Sc.tev[6]));
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, Sc.tev[0], Sc.tev[6]); Sc.times[0] = ms;
+    hipEventElapsedTime(&ms, Sc.tev[0], Sc.tev[1]); Sc.times[1] = ms;
+    hipEventElapsedTime(&ms, Sc.tev[1], Sc.tev[2]); Sc.times[2] = ms;
+    for (int k = 0; k < 3; ++k) { hipEventElapsedTime(&ms, Sc.tev[3 + k], Sc.tev[4 + k]); Sc.times[3 + k] = ms; }
+    Sc.last_ms[Sc.last_kind] = Sc.times[0];
+    return 0;
+}
+
+int gpirt_sampler_draw_scale(gpirt_sampler_t s, int kind)
+{
+    GP_ARG(s != nullptr);
+    const bool timed = s->timing;
+    GP_TRY(do_draw_scale(s, kind, "gpirt_sampler_draw_scale", timed));
+    if (timed) GP_TRY(scale_read_times(s));      // (timing on: one synchronisation, as the centred updates')
+    return 0;
+}
+
+// gpirt_sampler_step_consistent with the asked-for kinds between theta_partial and theta_finish (kinds: bit 0 scale, bit 1 shift,
+// the scale first)
+int gpirt_sampler_step_consistent_scale(gpirt_sampler_t s, int nugget, int kinds)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_step_consistent_scale";
+    GP_TRY(carry_refusals(s, nugget, me));
+    if (kinds < 0 || kinds > 3) { set_error("%s: kinds = %d, it is a mask of 1 (scale) and 2 (shift)", me, kinds); return GPIRT_E_ARG; }
+    if (kinds) {
+        GP_TRY(needs(s->sc.on, "the scale and shift move is", "gpirt_sampler_scale_enable"));
+        GP_TRY(scale_refusals(s, me));
+    }
+    mark(s, 0);
+    GP_TRY(do_draw_f(s));            mark(s, 1);
+    GP_TRY(do_draw_fstar(s, (uint32_t)(s->iter + 1))); mark(s, 2);
+    GP_TRY(do_theta_partial(s));
+    for (int kind = 0; kind < 2; ++kind)
+        if (kinds & (1 << kind)) GP_TRY(do_draw_scale(s, kind, me, false));
+    mark(s, 3);
+    GP_TRY(do_theta_finish(s));      mark(s, 4);
+    GP_TRY(do_carry_f(s, nugget, s->timing));
+    GP_TRY(do_draw_beta(s));         mark(s, 5);
+    GP_TRY(do_factor(s));            mark(s, 6);
+    s->iter += 1;
+    if (s->timing) {
+        GP_HIP(hipEventSynchronize(s->ev[ST_COUNT]));
+        for (int i = 0; i < ST_COUNT; ++i) {
+            float ms = 0.f;
+            hipEventElapsedTime(&ms, i == ST_BETA ? s->carry.tev[1] : s->ev[i], s->ev[i + 1]);
+            s->stage_ms[i] = ms;                  // (the moves' time is inside theta_partial's)
+        }
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, s->carry.tev[0], s->carry.tev[1]);
+        s->carry.last_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_scale_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out);
+    ScaleState& Sc = s->sc;
+    GP_TRY(needs(Sc.on, "the scale and shift move's arrays are", "gpirt_sampler_scale_enable"));
+    const ScaleArgs& c = Sc.a;
+    const int64_t n = s->n, m = s->m, N = s->N;
+    const void* dev = nullptr;
+    const void* host = nullptr;
+    int64_t want = 0;
+    if (strcmp(name, "times") == 0) { host = Sc.times; want = 8 * 6; }
+    else if (strcmp(name, "counts") == 0) { dev = c.counts; want = 8 * 6; }
+    else if (strcmp(name, "logpost") == 0) { dev = s->logpost; want = 8 * N * n; }
+    else {
+        GP_TRY(needs(Sc.last_kind >= 0, "the scale and shift move's arrays are", "one gpirt_sampler_draw_scale call"));
+        if (strcmp(name, "record") == 0) { dev = c.rec; want = 8 * SCALE_REC_COUNT; }
+        else if (strcmp(name, "lz") == 0) { dev = c.lz; want = 8 * n; }
+        else if (strcmp(name, "lz_prop") == 0) { dev = c.lz_prop; want = 8 * n; }
+        else if (strcmp(name, "dlz") == 0) { dev = c.dlz; want = 8 * n; }
+        else if (strcmp(name, "beta_prop") == 0) { dev = c.beta_prop; want = 8 * 2 * m; }
+        else if (strcmp(name, "mu_prop") == 0) { dev = c.mu2; want = 8 * N * m; }
+        else if (strcmp(name, "fstar_prop") == 0) { dev = c.fstar2; want = 8 * N * m; }
+        else if (strcmp(name, "logpost_prop") == 0) { dev = c.logpost2; want = 8 * N * n; }
+        else { set_error("unknown scale array '%s'", name); return GPIRT_E_ARG; }
+    }
+    if (bytes != want) { set_error("scale: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    if (host) { memcpy(h_out, host, (size_t)want); return 0; }
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+int gpirt_sampler_scale_stats(gpirt_sampler_t s, gpirt_scale* out)
+{
+    GP_ARG(s && out);
+    const ScaleState& Sc = s->sc;
+    memset(out, 0, sizeof(*out));
+    out->on = Sc.on ? 1 : 0;
+    for (int k = 0; k < 2; ++k) { out->calls[k] = Sc.t[k]; out->width[k] = Sc.width[k]; out->last_ms[k] = Sc.last_ms[k]; }
+    if (!Sc.on) return 0;
+    long long cnt[6];
+    hipStream_t st = s->h->stream;
+    GP_HIP(hipMemcpyAsync(cnt, Sc.a.counts, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; ++k) { out->accepted[k] = cnt[2 + k]; out->failed[k] = cnt[4 + k]; }
+    return 0;
+}
+
 // ---- the population prior for theta --------------------------------------------------------------------------------------------
 static int pop_refusals(gpirt_sampler_t s, const char* entry)
 {
@@ -3771,6 +4041,7 @@ int gpirt_sampler_pop_set(gpirt_sampler_t s, const int32_t* codes, int G, const 
 {
     GP_ARG(s != nullptr);
     PopState& A = s->pop;
+    s->lp_current = false;
     if (!codes) {
         if (A.mode == 2) { set_error("gpirt_sampler_pop_set(NULL): the population prior is sampled, gpirt_sampler_pop_enable(on = 0) turns it off"); return GPIRT_E_ARG; }
         GP_HIP(hipStreamSynchronize(s->h->stream));
@@ -3812,6 +4083,7 @@ int gpirt_sampler_pop_enable(gpirt_sampler_t s, const int32_t* codes, int G, con
 {
     GP_ARG(s != nullptr);
     PopState& A = s->pop;
+    s->lp_current = false;
     if (!on) {
         if (A.mode == 1) { set_error("gpirt_sampler_pop_enable(on = 0): the population prior is fixed, gpirt_sampler_pop_set(NULL) turns it off"); return GPIRT_E_ARG; }
         GP_HIP(hipStreamSynchronize(s->h->stream));
@@ -3895,6 +4167,7 @@ int gpirt_sampler_draw_pop(gpirt_sampler_t s)
     GP_ARG(s && s->initialised);
     PopState& A = s->pop;
     GP_TRY(needs(A.mode == 2, "the population prior's update is", "gpirt_sampler_pop_enable"));
+    s->lp_current = false;
     PopUpdateArgs a{};
     a.stats = A.stats; a.mu = A.d_mu; a.sd = A.d_sd; a.P_mu = A.P_mu; a.P_sd = A.P_sd;
     a.hyper_mu = A.d_hyper_mu; a.hyper_sd = A.d_hyper_sd; a.lse = A.d_lse;
@@ -4218,6 +4491,7 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     GP_TRY(aux_join(dst)); GP_TRY(aux_join(src));
     GP_TRY(ensure_dense_factor(src));     // (dst gets the whole factor)
     dst->L_structured = false;
+    dst->lp_current = false;
     src->factor_fresh = false;
     invalidate_factor_products(dst);
     GP_HIP(hipMemcpyAsync(dst->theta, src->theta, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
@@ -4263,6 +4537,7 @@ int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, i
     GP_ARG(count <= c && strcmp(name, "ess_k") != 0);
     GP_TRY(aux_join(s));
     invalidate_factor_products(s);
+    s->lp_current = false;
     if (strcmp(name, "L") == 0 || strcmp(name, "theta") == 0) s->rows_valid = false;
     if (strcmp(name, "L") == 0) s->theta_alone = false;          // (taken as the factor of K(theta, theta) for the theta in place)
     if (strcmp(name, "L") == 0) {

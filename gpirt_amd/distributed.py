@@ -359,6 +359,13 @@ class ShardedSampler:
         raise ValueError("ShardedSampler: the centred beta update is not offered for item shards (the library refuses an item "
                          "shard: its shared 2 x 2 matrix is built for all items of one sampler)")
 
+    def scale_enable(self, w_scale=None, w_shift=None):
+        raise ValueError("ShardedSampler: the collapsed scale and shift move is not offered for item shards (the library refuses an "
+                         "item shard: logpost then holds only part of the items)")
+
+    def draw_scale(self, kind):
+        self.scale_enable()
+
     # -- the population prior for theta (gpirt_amd.pop): the respondent-block theta path would need the codes of its block
     def pop_set(self, codes, log_prior=None):
         raise ValueError("ShardedSampler: a population prior is not offered for item shards (the respondent-block theta path "

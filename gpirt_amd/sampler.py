@@ -647,10 +647,24 @@ class Sampler:
 
     def init(self): self._call("gpirt_sampler_init")
 
-    def step(self, consistent=False, nugget=True):
+    def step(self, consistent=False, nugget=True, scale=None):
         """One iteration.  The default is the reference's (gpirt_sampler_step): theta moves and f stays at the old theta.
         consistent=True: gpirt_sampler_step_consistent -- the same stages with carry_f(nugget) between theta_finish and
-        draw_beta, so that f belongs to the new theta (gpirt_amd.consistent)."""
+        draw_beta, so that f belongs to the new theta (gpirt_amd.consistent).  scale: the kinds of the collapsed move ("scale",
+        "shift" or a tuple of them) proposed between theta_partial and theta_finish of a consistent step
+        (gpirt_sampler_step_consistent_scale, after scale_enable()); None makes the calls it made before."""
+        if scale is not None:
+            if not consistent:
+                raise ValueError("step: scale = ... needs consistent=True (the move is part of the consistent step)")
+            kinds = 0
+            for k in ((scale,) if isinstance(scale, str) else tuple(scale)):
+                kinds |= 1 << self._scale_kind(k)
+            rc = self.lib.gpirt_sampler_step_consistent_scale(self._s, int(nugget), kinds)
+            if rc > 0:
+                raise RuntimeError("chol(): decomposition failed (leading minor %d)" % rc)
+            check(rc)
+            self._last_step_consistent = True
+            return
         if not consistent:
             self._last_step_consistent = False
             self._call("gpirt_sampler_step")
@@ -1821,6 +1835,74 @@ class Sampler:
         else:
             raise ValueError(f"unknown centred beta array {name!r}")
         self._get_into("gpirt_sampler_beta_centred_get", name, out)
+        return out
+
+    # -- the collapsed scale and shift move: the linear mean with theta summed out (gpirt_sampler_draw_scale, gpirt_amd.scale)
+    @staticmethod
+    def _scale_kind(kind) -> int:
+        if kind in _lib.SCALE_KINDS:
+            return _lib.SCALE_KINDS.index(kind)
+        if isinstance(kind, (int, np.integer)) and not isinstance(kind, bool):
+            return int(kind)                      # (the library refuses anything but 0 and 1, with its reason)
+        raise ValueError(f"scale: kind = {kind!r}, it is \"scale\" or \"shift\"")
+
+    def scale_enable(self, w_scale=None, w_shift=None):
+        """Allocate the move's buffers and set the proposal widths, the sds of eps (scale) and delta (shift)
+        (gpirt_sampler_scale_enable).  None is the default 1 / sqrt(n), a choice and not a measurement; 0 proposes the state
+        itself.  Calling it again only sets the widths."""
+        nan = float("nan")
+        check(self.lib.gpirt_sampler_scale_enable(self._s, nan if w_scale is None else float(w_scale),
+                                                  nan if w_shift is None else float(w_shift)))
+
+    def draw_scale(self, kind):
+        """One proposal of kind "scale" (every slope times exp(-eps)) or "shift" (the linear mean at x + delta), decided on the
+        likelihood with every theta summed out; legal between theta_partial() and theta_finish() (gpirt_sampler_draw_scale;
+        gpirt_amd.scale.step_exact is its NumPy statement).  Nothing is read back."""
+        check(self.lib.gpirt_sampler_draw_scale(self._s, self._scale_kind(kind)))
+
+    def scale_width(self, kind, w):
+        """Set one kind's proposal width (gpirt_sampler_scale_width)."""
+        check(self.lib.gpirt_sampler_scale_width(self._s, self._scale_kind(kind), float(w)))
+
+    def scale(self) -> dict:
+        """The move's totals (gpirt_sampler_scale_stats): on, and per kind a dict(calls, accepted, failed, width, last_ms)."""
+        a = _lib.Scale()
+        check(self.lib.gpirt_sampler_scale_stats(self._s, C.byref(a)))
+        out = dict(on=bool(a.on))
+        for k, name in enumerate(_lib.SCALE_KINDS):
+            out[name] = dict(calls=int(a.calls[k]), accepted=int(a.accepted[k]), failed=int(a.failed[k]), width=float(a.width[k]),
+                             last_ms=float(a.last_ms[k]))
+        return out
+
+    def scale_get(self, name: str):
+        """One array of the move by name: record (a dict by _lib.SCALE_RECORD's names, status as its word), lz, lz_prop, dlz (n),
+        beta_prop (2 x m), mu_prop, fstar_prop (N x m), logpost, logpost_prop (N x n), counts (int64 3 x 2: calls, accepted, failed
+        by kind), times (a dict by _lib.SCALE_TIMES' names, ms of the last call with enable_timing() on)."""
+        N, n, m = _lib.NGRID, self.n, self.m
+        if name == "record":
+            raw = np.empty(len(_lib.SCALE_RECORD))
+            self._get_into("gpirt_sampler_scale_get", name, raw)
+            out = {k: float(v) for k, v in zip(_lib.SCALE_RECORD, raw) if not k.startswith("_")}
+            out["kind"] = _lib.SCALE_KINDS[int(out["kind"])]
+            out["status"] = _lib.SCALE_STATUS[int(out["status"])]
+            return out
+        if name == "times":
+            raw = np.empty(len(_lib.SCALE_TIMES))
+            self._get_into("gpirt_sampler_scale_get", name, raw)
+            return dict(zip(_lib.SCALE_TIMES, map(float, raw)))
+        if name in ("lz", "lz_prop", "dlz"):
+            out = np.empty(n)
+        elif name == "beta_prop":
+            out = np.empty((2, m), order="F")
+        elif name in ("mu_prop", "fstar_prop"):
+            out = np.empty((N, m), order="F")
+        elif name in ("logpost", "logpost_prop"):
+            out = np.empty((N, n), order="F")
+        elif name == "counts":
+            out = np.empty((3, 2), dtype=np.int64)
+        else:
+            raise ValueError(f"unknown scale array {name!r}")
+        self._get_into("gpirt_sampler_scale_get", name, out)
         return out
 
     # -- the population prior for theta, fixed or sampled in the chain (include/gpirt_hip.h gpirt_sampler_pop_*, gpirt_amd.pop)

@@ -57,6 +57,7 @@ enum {
     GPIRT_ST_PPC = 8,     /* the replicate of the posterior predictive checks (below); no stage of the chain draws from it */
     GPIRT_ST_AMP_CENTRED = 13,  /* the centred amplitude update (gpirt_sampler_draw_amp_centred): item index item0 + j, index 0 .. 63 the normals of the augmentation, 64 / 65 the two uniforms; nothing else draws from it */
     GPIRT_ST_BETA_CENTRED = 14, /* the two normals per item of the centred beta update (gpirt_sampler_draw_beta_centred): item index item0 + j, index 0 / 1; nothing else draws from it */
+    GPIRT_ST_SCALE = 15,  /* the collapsed scale and shift move (gpirt_sampler_draw_scale): item index the kind (0 scale, 1 shift), index 0 the normal's uniform, 1 the decision's; nothing else draws from it */
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
@@ -2379,6 +2380,89 @@ typedef struct gpirt_beta_centred {
 int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s);
 int gpirt_sampler_beta_centred_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_beta_centred_stats(gpirt_sampler_t s, gpirt_beta_centred* out);
+
+/* ------------------------------------------------------ a collapsed scale and shift move: the slopes with theta summed out -- */
+/* Library version 137.  theta_finish draws theta given the curves on the grid and every update of beta is given theta, so a
+ * change of theta's scale (or location) needs all n respondents and all m slopes (intercepts) to move together, and no
+ * conditional update does that: each chain sits at its own scale.  Between gpirt_sampler_theta_partial and
+ * gpirt_sampler_theta_finish the sampler holds logpost (N x n), from which theta is summed out in closed form.
+ * gpirt_sampler_draw_scale makes ONE Metropolis proposal that moves the linear mean of every item at once and is decided on
+ * prod_i Z_i, the likelihood with every theta_i summed out; the theta_finish that follows redraws every theta under whichever
+ * curve stands.  That is a partially collapsed Gibbs pair in the right order: no rounding of theta, no factorisation, no new
+ * model assumption.  Stage API only: gpirt_options, gpirt_run, gpirt_mcmc*, gpirt_sampler_step, gpirt_sampler_step_consistent
+ * and every existing stage keep their layout, behaviour and uniforms, and a sampler that never calls
+ * gpirt_sampler_scale_enable computes bit for bit what it did.
+ *
+ * At the call fstar[k, j] = hstar[k, j] + mu_star[k, j] with mu_star[k, j] = b0_j + x_k b1_j, x_k = -5 + 0.01 k, and
+ * logpost[k, i] is the log-likelihood of respondent i's answers at fstar[k, :].  theta_finish draws theta_i from masses
+ * proportional to exp(P_i[k]) on k = 1 .. N - 1 (index 0 is never drawn: the CDF there is (C - C_0) / (C_last - C_0)), with
+ * P_i[k] = lprior_i[k] + logpost[k, i] and lprior_i the N(0, 1) log density at x_k or row codes[i] of the population prior's
+ * table.  So   lz_i = M_i + log sum_{k=1}^{N-1} exp(P_i[k] - M_i),  M_i = max_{k >= 1} P_i[k]   is the log normaliser of
+ * exactly the law theta_finish draws from.  hstar is held fixed and only the linear mean moves; t is the count of calls of
+ * the kind over the sampler's life from 1, z = qnorm_as241(item_uniform(seed, t, GPIRT_ST_SCALE, kind, 0)), u =
+ * item_uniform(seed, t, GPIRT_ST_SCALE, kind, 1):
+ *   kind 0, scale   eps = w_scale z;    b1_j' = b1_j c, c = exp(-eps) (the device's exp; the record holds c); b0 unchanged;
+ *                   log r = sum_i (lz'_i - lz_i) + sum_j [ldn(b1_j'; pm_1j, ps_1j) - ldn(b1_j; pm_1j, ps_1j)] - m eps.
+ *                   -m eps is the log Jacobian of the m slopes; without it the move does not leave the prior invariant.
+ *   kind 1, shift   delta = w_shift z;  b0_j' = b0_j + b1_j delta (one product, one sum); b1 unchanged: the linear mean at
+ *                   x + delta, Jacobian 1;  log r = sum_i (lz'_i - lz_i) + sum_j [ldn(b0_j'; pm_0j, ps_0j) - ldn(b0_j; ..)].
+ * ldn is R's dnorm(., log = TRUE) as draw_beta forms it, -(ln sqrt(2 pi) + 0.5 z^2 + log(sd)) with z = |(x - mean) / sd|.
+ * Accepted iff log(u) < log r.  The library is built without contraction: no operation below is fused.
+ *   the curve    mu2[k, j] = b0_j' + x_k b1_j' with x_k = -5.0 + (double)k 0.01, draw_beta's expression, so an accepted mu_star
+ *                holds the bits draw_beta would write for beta'.  fstar2 = fstar + (mu2 - mu_star): the difference of the two
+ *                ROUNDED means; carry_f's fstar - mu_star moves by two roundings per cell.
+ *   logpost2     from fstar2 through the very launches gpirt_sampler_theta_partial makes, into its own buffer, through the
+ *                same scratch: a width of 0 gives a logpost2 byte-equal to logpost.
+ *   lz, lz'      one work-group per respondent in theta_sample_kernel's layout: thread t of 256 holds k = 4 t + e, e = 0 .. 3;
+ *                k = 0 and k >= N are left out.  M = the maximum by fmax (a NaN is skipped there and caught by the sum).
+ *                s_t = ((0 + exp(P[4t] - M)) + exp(P[4t + 1] - M)) + .., e ascending, a left-out k adding exactly 0.0.
+ *                S = the adjacent-pair tree over s_0 .. s_255: for d = 1, 2, .., 128, s[t] += s[t - d] at every t with
+ *                (t + 1) % (2 d) == 0, S = s[255] -- what the last entry of theta_sample_kernel's scan holds; in NumPy,
+ *                s = s[0::2] + s[1::2] eight times.  lz = M + log(S); dlz = lz' - lz.
+ *   the sums     D = sum_i dlz_i: thread t of 256 takes i = t, t + 256, .. ascending into an accumulator that starts at 0,
+ *                then the fixed tree s = 128, 64, .., 1 with acc[t] += acc[t + s] (ell_delta_kernel's).  Q = the prior's sum
+ *                in ascending j from 0, each term the difference of the two ldn.  J = (double)m eps (scale) or 0.0 (shift).
+ *                log r = (D + Q) - J.
+ * A call is FAILED, never accepted and counted in `failed`, when an lz_i or lz'_i is not finite, a respondent's column is
+ * degenerate (M not > -1e300, theta_sample_kernel's rule), a beta' is not finite, or D, Q or log r is not finite.
+ * On ACCEPT the device decides and the host reads nothing: beta, mu_star, fstar and logpost take the proposal's values, mu is
+ * rewritten as b0_j' + theta_i b1_j' at the theta in place (mu = X beta as stored holds between stages), and the shape block's
+ * gbar, when on, moves by the same mu2 - mu_star.  On REJECT or a failed call every array of the chain is byte for byte as
+ * before; only the counters, the record and the proposal's buffers move.  No floating-point atomic, one writer per value: two
+ * runs give a byte-identical state.  The call keeps the sampler's note that logpost belongs to the fstar and beta in place,
+ * which gpirt_sampler_theta_partial sets and every writer of fstar, beta, f, theta or the population prior clears.
+ *
+ * gpirt_sampler_scale_enable(s, w_scale, w_shift) allocates the proposal's buffers (2 N m + N n + 3 n doubles) and sets the
+ * widths, the sds of eps and delta.  NaN asks for the default 1 / sqrt(n) -- a choice, not a measurement: the sum over n
+ * respondents has a curvature of order n m, so this is generous and gpirt_amd.scale.run retunes it.  A width of 0 is allowed
+ * and proposes the state itself.  Calling it again only sets the widths.  gpirt_sampler_scale_width sets one.
+ * gpirt_sampler_scale_get, by name: "record" (GPIRT_SCALE_RECORD doubles: kind, z, the step eps or delta, c, D, Q, J, log r, u,
+ * log u, status (0 rejected, 1 accepted, 2 failed), the count of bad respondents and coefficients, t, the width, 0, 0), "lz",
+ * "lz_prop", "dlz" (n doubles), "beta_prop" (2 x m), "mu_prop", "fstar_prop" (N x m), "logpost", "logpost_prop" (N x n, column i
+ * respondent i), "counts" (6 int64, row-major 3 x 2: calls, accepted, failed of kind 0 / 1), "times" (6 doubles, ms of the last
+ * call with gpirt_sampler_enable_timing on: whole, curve, product, logz, decide, commits).
+ * gpirt_sampler_step_consistent_scale(s, nugget, kinds): gpirt_sampler_step_consistent with the asked-for kinds (bit 0 the
+ * scale, bit 1 the shift, the scale first) between theta_partial and theta_finish; kinds = 0 is that step bit for bit.
+ *
+ * Refused with GPIRT_E_ARG, each with its reason: before gpirt_sampler_init or gpirt_sampler_scale_enable; GPIRT_RNG_RSTREAM; an
+ * item shard or gpirt_sampler_set_theta_block in use (logpost then holds only part of the items); logpost not current; a kind
+ * other than 0 or 1; a width that is not finite or < 0; a prior sd that is not finite and > 0.  Behind a plain
+ * gpirt_sampler_step's stages it is not refused, which measurements need, but there f sits at the old theta (quirk Q3) and the
+ * chain it is part of is not the model's. */
+#define GPIRT_SCALE_RECORD 16
+typedef struct gpirt_scale {
+    int64_t  on;
+    int64_t  calls[2], accepted[2], failed[2];  /* per kind (0 scale, 1 shift) over the sampler's life */
+    double   width[2];                          /* the sds of eps and delta */
+    double   last_ms[2];                        /* device time of the kind's last call with gpirt_sampler_enable_timing on, else 0 */
+    int64_t  reserved[5];
+} gpirt_scale;
+int gpirt_sampler_scale_enable(gpirt_sampler_t s, double w_scale, double w_shift);
+int gpirt_sampler_scale_width(gpirt_sampler_t s, int kind, double w);
+int gpirt_sampler_draw_scale(gpirt_sampler_t s, int kind);
+int gpirt_sampler_scale_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_scale_stats(gpirt_sampler_t s, gpirt_scale* out);
+int gpirt_sampler_step_consistent_scale(gpirt_sampler_t s, int nugget, int kinds);
 
 /* ------------------------------------------------------ a consistent step: f carried to the new theta, a prior check ---- */
 /* Library version 133.  The reference's iteration moves theta and keeps f (quirk Q3 of SURVEY.md): behind gpirt_sampler_step
