@@ -38,6 +38,7 @@ const Config& env_config()
         d.rs_predict = env_value("GPIRT_RS_PREDICT", d.rs_predict);
         d.rs_lr = env_value("GPIRT_RS_LR", d.rs_lr);
         d.nu_lr = env_value("GPIRT_NU_LR", d.nu_lr);
+        d.nu_sub = env_value("GPIRT_NU_SUB", NU_LR_SUB);
         d.fstar_free = env_value("GPIRT_FSTAR_FREE", d.fstar_free);
         d.factor_lr = env_value("GPIRT_FACTOR_LR", d.factor_lr);
         d.flr_fuse = env_value("GPIRT_FLR_FUSE", d.flr_fuse);
@@ -166,7 +167,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 137; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 138; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -240,6 +241,9 @@ int gpirt_version(void) { return 137; }   // 101: gpirt_options names kernel_fp3
                                             // 137: a collapsed scale and shift move on the linear mean with theta summed out (scale.hip,
                                             //      sampler.hip: GPIRT_ST_SCALE, gpirt_sampler_scale_enable, gpirt_sampler_draw_scale,
                                             //      gpirt_sampler_scale_width / _get / _stats, gpirt_sampler_step_consistent_scale); stage API only
+                                            // 138: draw_f's structured product in parts of its own width, narrower than the factor's 512, with
+                                            //      the rank-64 term accumulated in the launch of the diagonal parts (nu_lr.hip, gemm_f64.hip:
+                                            //      GPIRT_NU_SUB = 64, 128, 256 or 512); nu changes in rounding only, no change to the interface
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -370,6 +374,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_RS_PREDICT", &h->cfg.rs_predict, false },
         { "GPIRT_RS_LR", &h->cfg.rs_lr, false },
         { "GPIRT_NU_LR", &h->cfg.nu_lr, false },
+        { "GPIRT_NU_SUB", &h->cfg.nu_sub, false },
         { "GPIRT_FSTAR_FREE", &h->cfg.fstar_free, false },
         { "GPIRT_FACTOR_LR", &h->cfg.factor_lr, false },
         { "GPIRT_FLR_FUSE", &h->cfg.flr_fuse, false },
@@ -395,6 +400,7 @@ int gpirt_config_set(gpirt_handle_t h, const char* name, int value)
     int* p = config_slot(h, name, &ro);
     if (!p) { set_error("unknown switch '%s'", name); return GPIRT_E_ARG; }
     if (ro) { set_error("%s is fixed per process (set it in the environment before the library is loaded)", name); return GPIRT_E_ARG; }
+    if (p == &h->cfg.nu_sub && !nu_lr_sub_ok(value)) { set_error("GPIRT_NU_SUB must be 64, 128, 256 or 512 (got %d)", value); return GPIRT_E_ARG; }
     GP_HIP(hipStreamSynchronize(h->stream));
     *p = value;
     if (h->aux) *config_slot(h->aux, name, nullptr) = value;

@@ -82,6 +82,8 @@ struct Config {
     int  rs_lr = 1;               // GPIRT_RS_LR: 2 = the predictor's every pass reads all of L as floats (no structured form, rs_lr.hip)
     int  nu_lr = 1;               // GPIRT_NU_LR: draw_f's nu = L z from L's diagonal parts and the 64 node rows (nu_lr.hip): 1 = from n = 2048 on,
                                   //   2 = always the dense product, 3 = at every eligible n
+    int  nu_sub = 0;              // GPIRT_NU_SUB: the part width of that product, 64, 128, 256 or 512 (the factor's parts stay 512 wide; env_config()
+                                  //   fills in kernels.h's NU_LR_SUB); anything else is an argument error
     int  fstar_free = 1;          // GPIRT_FSTAR_FREE: the rank-64 draw_fstar's C = S^-1 U from theta alone (fstar_free.hip): 1 = from n = 2048 on
                                   //   where the sampler is eligible, 2 = always the solve through L, 3 = at every eligible n
     int  factor_lr = 1;           // GPIRT_FACTOR_LR: a sampler with gpirt_options.factor_structured builds L's diagonal parts and node rows alone,

@@ -58,6 +58,11 @@ struct GemmParams {
     // fused epilogue (FUSE kernels only): work-group 0 factors this 64 x 64 block after its tile
     double* fz_A; int64_t fz_lda; int fz_nb; int fz_k0; int* fz_info;
     const int* run_if = nullptr;   // when set: the launch does nothing unless *run_if != 0 (a fallback product kept behind a device-side flag)
+    // optional second operand pair (DUAL kernels only): after the K range of A and B the tile's main loop runs once more,
+    // acc += op(A2)[tile rows, 0 : K2] op(B2)[0 : K2, tile cols], into the same accumulator, then the epilogue
+    const double* A2 = nullptr; const double* B2 = nullptr;
+    int64_t lda2 = 0, ldb2 = 0, sA2 = 0, sB2 = 0;
+    int K2 = 0, fastA2 = 0, fastB2 = 0;
 };
 
 template <bool KCONTIG, int T>
@@ -440,7 +445,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, const int bi,
     }
 }
 
-template <bool TA, bool TB, int T>
+template <bool TA, bool TB, int T, bool DUAL = false>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int bi, const int bj, double* smem)
 {
     constexpr int NT = Cfg<T>::NT;
@@ -466,6 +471,17 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int bi, con
                       kend > kbeg && ((kend - kbeg) % BK) == 0;
     if (fast) gemm_mainloop_fast<TA, TB, T>(p, bi, bj, smem, kbeg, (kend - kbeg) / BK, acc);
     else gemm_mainloop<TA, TB, T>(p, bi, bj, smem, kbeg, kend, acc);
+    if constexpr (DUAL) {
+        // the second operand pair, all of its K2, behind the first in the same accumulator (both main loops leave the LDS
+        // tiles behind a barrier with nothing of them still to be read, so the second starts as the first did)
+        if (p.K2 > 0) {
+            GemmParams q = p;
+            q.A = p.A2; q.B = p.B2; q.lda = p.lda2; q.ldb = p.ldb2; q.K = p.K2; q.fastA = p.fastA2; q.fastB = p.fastB2;
+            const bool fast2 = q.fastA && q.fastB && (bi * T + T <= p.M) && (bj * T + T <= p.N) && (p.K2 % BK) == 0;
+            if (fast2) gemm_mainloop_fast<TA, TB, T>(q, bi, bj, smem, 0, p.K2 / BK, acc);
+            else gemm_mainloop<TA, TB, T>(q, bi, bj, smem, 0, p.K2, acc);
+        }
+    }
     gemm_epilogue<T>(p, bi, bj, acc);
 }
 
@@ -473,7 +489,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int bi, con
 // FUSE: the work-group that owns work item 0 (the tile holding the next diagonal block of the Cholesky
 // panel) factors that block right after producing it -- the potf2 launch and its kernel boundary
 // disappear from the panel chain (potrf.hip).
-template <bool TA, bool TB, int T, int PAD = 0, bool FUSE = false>
+// DUAL: the tile's main loop runs a second time on GemmParams' second operand pair (launch_gemm_batched_dual).
+template <bool TA, bool TB, int T, int PAD = 0, bool FUSE = false, bool DUAL = false>
 __global__ __launch_bounds__(256, (T == 64 ? 3 : 2)) void gemm_f64_kernel(GemmParams p)
 {
     __shared__ __attribute__((aligned(16))) double smem[4 * Cfg<T>::TILE + PAD];
@@ -481,6 +498,10 @@ __global__ __launch_bounds__(256, (T == 64 ? 3 : 2)) void gemm_f64_kernel(GemmPa
     p.A += (int64_t)blockIdx.y * p.sA;
     p.B += (int64_t)blockIdx.y * p.sB;
     p.C += (int64_t)blockIdx.y * p.sC;
+    if constexpr (DUAL) {
+        p.A2 += (int64_t)blockIdx.y * p.sA2;
+        p.B2 += (int64_t)blockIdx.y * p.sB2;
+    }
     int bi, bj;
     if (p.tri == TRI_SYRK_LOWER) {
         // Lower trapezoid (M >= N): block columns bj = 0..nblocks-1, each holding block rows bj..mblocks-1.
@@ -524,14 +545,14 @@ __global__ __launch_bounds__(256, (T == 64 ? 3 : 2)) void gemm_f64_kernel(GemmPa
         const int q = blockIdx.x % half;
         bj = blockIdx.x / half;
         bi = p.mblocks - 1 - q;
-        gemm_tile<TA, TB, T>(p, bi, bj, smem);
+        gemm_tile<TA, TB, T, DUAL>(p, bi, bj, smem);
         if (q == bi) return;
         bi = q;
     } else {
         bi = blockIdx.x % p.mblocks;
         bj = blockIdx.x / p.mblocks;
     }
-    gemm_tile<TA, TB, T>(p, bi, bj, smem);
+    gemm_tile<TA, TB, T, DUAL>(p, bi, bj, smem);
     if (FUSE) {
         __shared__ int sfail;
         if (blockIdx.x == 0 && p.fz_A != nullptr) {
@@ -705,6 +726,39 @@ int launch_gemm_batched(hipStream_t stream, bool ta, bool tb, int tri, int64_t M
     p.fastA = (((uintptr_t)A & 15) == 0) && (lda % 2 == 0) && (strideA % 2 == 0);
     p.fastB = (((uintptr_t)B & 15) == 0) && (ldb % 2 == 0) && (strideB % 2 == 0);
     return launch_gemm_t<64>(stream, ta, tb, p, batch);
+}
+
+// `batch` products  C = A B + A2 B2  of one shape in 64-tiles, both pairs NN (A, A2: M x K / M x K2, B, B2: K x N / K2 x N;
+// TRI_NONE or TRI_A_LOWER, which is about A alone).  One accumulator per tile takes the K range of the first pair in
+// ascending order, then the K2 terms of the second in ascending order, and C is written once: nothing is read back and
+// nothing of the order depends on N, the batch or the grid (nu_lr.hip's consumer).
+int launch_gemm_batched_dual(hipStream_t stream, int tri, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                             int64_t strideA, const double* B, int64_t ldb, int64_t strideB, int64_t K2, const double* A2,
+                             int64_t lda2, int64_t strideA2, const double* B2, int64_t ldb2, int64_t strideB2, double* C,
+                             int64_t ldc, int64_t strideC, int batch)
+{
+    if (M <= 0 || N <= 0 || batch <= 0) return 0;
+    if (tri != TRI_NONE && tri != TRI_A_LOWER) { set_error("dual batched gemm: plain or lower-triangular A only"); return GPIRT_E_ARG; }
+    if (K2 <= 0 || !A2 || !B2) { set_error("dual batched gemm: the second operand pair is missing"); return GPIRT_E_ARG; }
+    constexpr int T = 64;
+    GemmParams p;
+    p.A = A; p.B = B; p.C = C;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.M = (int)M; p.N = (int)N; p.K = (int)K; p.Mr = 0;
+    p.alpha = 1.0; p.beta = 0.0; p.tri = tri;
+    p.fz_A = nullptr; p.fz_lda = 0; p.fz_nb = 0; p.fz_k0 = 0; p.fz_info = nullptr;
+    p.sA = strideA; p.sB = strideB; p.sC = strideC; p.ksplit = 0;
+    p.fastA = (((uintptr_t)A & 15) == 0) && (lda % 2 == 0) && (strideA % 2 == 0);
+    p.fastB = (((uintptr_t)B & 15) == 0) && (ldb % 2 == 0) && (strideB % 2 == 0);
+    p.A2 = A2; p.B2 = B2; p.lda2 = lda2; p.ldb2 = ldb2; p.sA2 = strideA2; p.sB2 = strideB2; p.K2 = (int)K2;
+    p.fastA2 = (((uintptr_t)A2 & 15) == 0) && (lda2 % 2 == 0) && (strideA2 % 2 == 0);
+    p.fastB2 = (((uintptr_t)B2 & 15) == 0) && (ldb2 % 2 == 0) && (strideB2 % 2 == 0);
+    p.mblocks = (p.M + T - 1) / T;
+    p.nblocks = (p.N + T - 1) / T;
+    const int64_t grid = (tri == TRI_A_LOWER) ? (int64_t)((p.mblocks + 1) / 2) * p.nblocks : (int64_t)p.mblocks * p.nblocks;
+    hipLaunchKernelGGL((gemm_f64_kernel<false, false, T, 0, false, true>), dim3((unsigned)grid, (unsigned)batch), dim3(256), 0, stream, p);
+    GP_HIP(hipGetLastError());
+    return 0;
 }
 
 // Split-K: C_q = alpha * op(A)[:, Kq] op(B)[Kq, :] for the `nsplit` consecutive K ranges Kq, written to

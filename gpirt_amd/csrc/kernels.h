@@ -22,6 +22,12 @@ int launch_gemm(gpirt_handle_t h, hipStream_t stream, bool ta, bool tb, int tri,
 int launch_gemm_batched(hipStream_t stream, bool ta, bool tb, int tri, int64_t M, int64_t N, int64_t K, double alpha,
                         const double* A, int64_t lda, int64_t strideA, const double* B, int64_t ldb, int64_t strideB,
                         double beta, double* C, int64_t ldc, int64_t strideC, int batch);
+// ... and C = A B + A2 B2 (both NN, TRI_NONE or TRI_A_LOWER on A) in one accumulator per 64-tile: A B's K range ascending, then
+// the K2 terms of A2 B2 ascending; C is written once
+int launch_gemm_batched_dual(hipStream_t stream, int tri, int64_t M, int64_t N, int64_t K, const double* A, int64_t lda,
+                             int64_t strideA, const double* B, int64_t ldb, int64_t strideB, int64_t K2, const double* A2,
+                             int64_t lda2, int64_t strideA2, const double* B2, int64_t ldb2, int64_t strideB2, double* C,
+                             int64_t ldc, int64_t strideC, int batch);
 
 // nparts consecutive trailing updates of one block column (panel q = columns [q * kpart, (q + 1) * kpart) of A / B) as one
 // launch + an in-order application: bit-identical to nparts separate launches (work: nparts * M * N doubles)
@@ -327,16 +333,20 @@ void rs_lr_nodes(std::vector<double>& nodes, std::vector<double>& wts, std::vect
 void rs_lr_unit_table(int64_t n, std::vector<uint32_t>& units);
 int launch_rs_lr_setup(hipStream_t stream, const RsLrSetup& q);
 int launch_rs_lr_apply(hipStream_t stream, const Rs3Args& a);
-// nu_lr.hip: draw_f's nu = L z (item-keyed RNG) from L's 512-column diagonal parts and the 64 node rows below the factor
+// nu_lr.hip: draw_f's nu = L z (item-keyed RNG) from L's diagonal parts and the 64 node rows below the factor
 constexpr int NU_LR_RANK = 64;       // the nodes of cheb_nodes_basis(64)
-constexpr int NU_LR_PART = 512;      // columns per part
+constexpr int NU_LR_PART = 512;      // columns per part of the FACTOR (factor_lr.hip, gpirt_sampler_factor_lr_parts)
+constexpr int NU_LR_SUB = 128;       // columns per part of the PRODUCT (GPIRT_NU_SUB: 64, 128, 256 or 512), measured
+constexpr int NU_LR_SUB_MIN = 64;    // the narrowest width: what the workspace is sized for
+inline bool nu_lr_sub_ok(int w) { return w == 64 || w == 128 || w == 256 || w == 512; }
 struct NuLrArgs {
     const double* L; int64_t ldl;     // the dense factor
     const double* Bt;                 // its node rows, K(c, theta) L^-T (64 x n, leading dimension ldl)
     const double* V;                  // n x 64 (leading dimension n): the Lagrange basis at theta
     const double* Z; double* NU;      // n x m each
-    double* T;                        // nu_lr_slabs(n) records of 64 x m
+    double* T;                        // nu_lr_slabs(n) slabs of 64 x m; slab 0 is zero and stays zero
     int64_t n, m;
+    int sub;                          // the product's part width (0: NU_LR_SUB)
 };
 void nu_lr_nodes(std::vector<double>& nodes, std::vector<double>& wts);
 int64_t nu_lr_slabs(int64_t n);

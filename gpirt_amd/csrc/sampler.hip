@@ -677,7 +677,7 @@ int do_draw_f(gpirt_sampler_s* s)
                 double flops = 0.0, bytes = 0.0;
                 NuLrArgs q{};
                 q.L = s->L; q.ldl = s->ldl; q.Bt = s->L + n + s->node_off; q.V = s->nuV; q.Z = s->Z; q.NU = s->NU; q.T = s->nuT;
-                q.n = n; q.m = m;
+                q.n = n; q.m = m; q.sub = h->cfg.nu_sub;
                 GP_TRY(launch_nu_lr_basis(st, s->theta, n, s->nu_nodes, s->nu_wts, s->nuV));
                 if (free) GP_HIP(hipEventRecord(s->ev_trmm, st));       // (the side chain shares this basis)
                 GP_TRY(launch_nu_lr(st, q, &flops, &bytes));
@@ -1872,7 +1872,14 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     if (!s->opt.fstar_fused) GP_A(s->kstar, n * N + 2);
     if (s->node_off >= 0) {
         GP_A(s->nu_nodes, NU_LR_RANK); GP_A(s->nu_wts, NU_LR_RANK);
-        if (!stream_mode(s)) { GP_A(s->nuV, n * NU_LR_RANK); GP_A(s->nuT, nu_lr_slabs(n) * NU_LR_RANK * m); }
+        if (!stream_mode(s)) {
+            GP_A(s->nuV, n * NU_LR_RANK); GP_A(s->nuT, nu_lr_slabs(n) * NU_LR_RANK * m);
+            // slab 0 of the product's workspace is the zero prefix of its first part: cleared once, behind any poison fill on the
+            // same stream, and never written again (nu_lr.hip)
+            if (hipMemsetAsync(s->nuT, 0, sizeof(double) * (size_t)(NU_LR_RANK * m), st) != hipSuccess) {
+                set_error("hipMemsetAsync(nuT) failed"); gpirt_sampler_destroy(s); return GPIRT_E_HIP;
+            }
+        }
         if (!stream_mode(s) && s->kr == NU_LR_RANK && s->fstar_rows) {
             GP_A(s->ffF, FSTAR_FREE_RANK * FSTAR_FREE_RANK); GP_A(s->ffW, 2 * FSTAR_FREE_RANK * FSTAR_FREE_RANK);
             if (s->opt.factor_structured) {       // (the structured factor's: only where the rank-64 chain from theta can run)

@@ -109,6 +109,18 @@ def structured_factor_fused(theta, family="se", length_scale=1.0, eps: float = J
     return parts, Bt, V
 
 
+SUB_WIDTHS = (64, 128, 256, 512)        # GPIRT_NU_SUB: the part widths of draw_f's product (the factor's parts stay PART wide)
+
+
+def sub_parts(parts, width: int, part: int = PART):
+    """The `width`-wide diagonal blocks of L that lie inside its `part`-wide diagonal parts, in order: what csrc/nu_lr.hip
+    reads of the factor at GPIRT_NU_SUB = width (nu(sub_parts(parts, w), Bt, V, Z, part=w)).  The last block of a ragged last
+    part is whatever is left of it."""
+    if width not in SUB_WIDTHS or part % width:
+        raise ValueError("the product's part width is 64, 128, 256 or 512 and divides the factor's")
+    return [Lpp[q:q + width, q:q + width] for Lpp in parts for q in range(0, Lpp.shape[0], width)]
+
+
 def nu(parts, Bt, V, Z, part: int = PART) -> np.ndarray:
     """nu = L Z from the parts and the node rows alone (csrc/nu_lr.hip): L[P, P] Z[P] + V[P] sum_{Q < P} Bt[:, Q] Z[Q]"""
     out = np.empty_like(Z)

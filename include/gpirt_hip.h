@@ -68,7 +68,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 133: a consistent step beside the reference's -- f carried to the new theta plus the model's nugget, and the prior check (GPIRT_ST_CARRY, gpirt_sampler_carry_f, gpirt_sampler_step_consistent, gpirt_carry, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 138: draw_f's structured product in parts of its own width with the rank-64 term accumulated in the launch of the diagonal parts (GPIRT_NU_SUB; nu changes in rounding only, no change to the interface); 133: a consistent step beside the reference's -- f carried to the new theta plus the model's nugget, and the prior check (GPIRT_ST_CARRY, gpirt_sampler_carry_f, gpirt_sampler_step_consistent, gpirt_carry, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2878,7 +2878,10 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
  * and L is the factor of K(theta, theta): a gpirt_sampler_set("theta") that no factorisation, adopted factor or
  * gpirt_sampler_set("L") has followed takes the dense product, and a caller who sets both sets a matching pair.
  * Otherwise the dense product runs, as before.  GPIRT_NU_LR (gpirt_config_set): 1 this rule, 2 always dense, 3 at every
- * eligible n.  The operators gpirt_draw_f / gpirt_trmm_lz are given L, not theta, and keep the dense product.
+ * eligible n.  GPIRT_NU_SUB (library version 138): the width of the product's blocks P, 64, 128 (the default), 256 or 512 --
+ * any cut into multiples of 64 satisfies the identity, the factor's own parts stay 512 wide, and a value outside the four is
+ * GPIRT_E_ARG; the width changes nu in rounding only and can be changed between draws.
+ * The operators gpirt_draw_f / gpirt_trmm_lz are given L, not theta, and keep the dense product.
  * gpirt_sampler_nu_lr_draws: how many draws of this sampler have run the structured product; gpirt_sampler_nu_lr_rows:
  * the node rows as they stand (64 x n, column-major, count = 64 n; GPIRT_E_ARG when the layout carries none). */
 int gpirt_sampler_ldl(gpirt_sampler_t s, int64_t* ldl);
