@@ -20,6 +20,8 @@ Layout:
                    Gibbs on two grids: the NumPy statement of one update, the exact conditional masses, the one-call run
   scale.py         the collapsed scale and shift move on the linear mean with theta summed out: the NumPy statement of one
                    call, the collapsed target, the one-call run
+  ordinal.py       ordinal (graded) responses under the cumulative-logit model, the thresholds sampled by exact Gibbs on a grid
+                   inside a random window: the NumPy statement of every swapped stage in long double, the one-call run
   distributed.py   item-column sharding over torch.distributed (RCCL), one process per GPU
   response_matrix.py, synthetic.py   host-side data preparation
 """

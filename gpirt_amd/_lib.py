@@ -580,6 +580,18 @@ POP_COUNTS = ("updates", "updated", "skipped", "failed")                   # the
 POP_MODES = (None, "fixed", "sampled")
 
 
+# ordinal (graded) responses (include/gpirt_hip.h gpirt_ordinal; gpirt_amd.ordinal)
+ST_ORD = 16                       # the two uniforms per threshold of a threshold update: item index item0 + j, index 2 (c - 1) / 2 (c - 1) + 1
+ORD_MAX_C, ORD_MIN_POINTS, ORD_MAX_POINTS, ORD_MAX_WIDTH, ORD_MAX_N = 8, 9, 1001, 64, 16384
+
+
+class Ordinal(C.Structure):
+    """gpirt_ordinal (include/gpirt_hip.h): the sizes, the counters since enable and the records."""
+    _fields_ = [(k, C.c_int64) for k in ("on", "n", "m", "categories", "points", "width", "calls", "pinned", "failed", "updates",
+                                         "planned_draws", "recorded", "irf_draws")] + [
+        ("hi", C.c_double), ("last_ms", C.c_double), ("lp_width", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
 class Pop(C.Structure):
     """gpirt_pop (include/gpirt_hip.h): the mode, the sizes, the totals over the groups and the last call's off-grid members."""
     _fields_ = [(k, C.c_int64) for k in ("on", "groups", "n", "points_mu", "points_sd", "calls") + POP_COUNTS + (
@@ -850,6 +862,16 @@ SIGNATURES = {
     "gpirt_sampler_pop_record": (_i32, [_vp]),
     "gpirt_sampler_pop_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_pop_stats": (_i32, [_vp, C.POINTER(Pop)]),
+    "gpirt_ordinal_check": (_i32, [C.POINTER(C.c_int8), _dp, _i64, _i64, _i32, _dbl, _i32, _dp, C.POINTER(C.c_int32), _i32,
+                                   C.POINTER(Options)]),
+    "gpirt_ordinal_grid": (_i32, [_dbl, _i32, _dp]),
+    "gpirt_sampler_ordinal_enable": (_i32, [_vp, C.POINTER(C.c_int8), _i32, _dbl, _i32, _dp, C.POINTER(C.c_int32), _i32, _i64]),
+    "gpirt_sampler_draw_thresholds": (_i32, [_vp]),
+    "gpirt_sampler_ordinal_width": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ordinal_record": (_i32, [_vp]),
+    "gpirt_sampler_ordinal_accumulate_irf": (_i32, [_vp]),
+    "gpirt_sampler_ordinal_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ordinal_stats": (_i32, [_vp, C.POINTER(Ordinal)]),
     "gpirt_sampler_carry_f": (_i32, [_vp, _i32]),
     "gpirt_sampler_step_consistent": (_i32, [_vp, _i32]),
     "gpirt_sampler_carry_stats": (_i32, [_vp, C.POINTER(Carry)]),

@@ -167,7 +167,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 138; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 139; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -244,6 +244,10 @@ int gpirt_version(void) { return 138; }   // 101: gpirt_options names kernel_fp3
                                             // 138: draw_f's structured product in parts of its own width, narrower than the factor's 512, with
                                             //      the rank-64 term accumulated in the launch of the diagonal parts (nu_lr.hip, gemm_f64.hip:
                                             //      GPIRT_NU_SUB = 64, 128, 256 or 512); nu changes in rounding only, no change to the interface
+                                            // 139: ordinal (graded) responses under the cumulative-logit model, the thresholds sampled on a grid
+                                            //      (ordinal.hip, sampler.hip: GPIRT_ST_ORD, gpirt_ordinal_check, gpirt_ordinal_grid,
+                                            //      gpirt_sampler_ordinal_enable / _width / _record / _accumulate_irf / _get / _stats,
+                                            //      gpirt_sampler_draw_thresholds); stage API only
 
 const char* gpirt_last_error(void) { return g_err; }
 

@@ -163,6 +163,41 @@ void pop_default_row(double* row);                                  // the N(0, 
 void pop_normal_row(double mu, double sd, double* row);             // -(0.5 z z), z = (t_k - mu) / sd: the update kernel's bits
 void pop_grids_fill(double mu_hi, int P_mu, double sd_lo, double sd_hi, int P_sd, double* mu, double* sd);
 void pop_lse_fill(const double* mu, int P_mu, const double* sd, int P_sd, double* lse);     // long double, rounded once
+// ordinal.hip: ordinal (graded) responses under the cumulative-logit model (gpirt_sampler_ordinal_*).  cat: n x m int8,
+// column-major, 0 = missing; thr: m x (C - 1) threshold values, thr[j (C - 1) + c - 1] = b_{j,c}; counts: m x C int64 observed cells
+struct EssOrdArgs {
+    double* f; const double* nu; const double* mu; const int8_t* cat; const double* thr; const long long* counts;
+    int C; int64_t n, m;
+    int* k_out; int* err;                                               // as EssArgs
+    uint64_t seed; uint32_t iter; uint32_t item0;
+    int screen;
+};
+int launch_ess_ord(hipStream_t stream, const EssOrdArgs& a);          // the slice for f, item-keyed RNG only, n <= GPIRT_ORD_MAX_N
+int launch_ord_indicators(hipStream_t stream, const int8_t* cat, int64_t n, int64_t m, int C, double* Y);      // Y: n x C m one-hot
+int launch_ord_counts(hipStream_t stream, const int8_t* cat, int64_t n, int64_t m, int C, long long* counts);
+// G[k, (c - 1) m + j] = -ll(b_c - f*) [c < C] - ll(f* - b_{c-1}) [c > 1] (N x C m, leading dimension ldg >= N)
+int launch_ord_loglik_terms(hipStream_t stream, const double* fstar, int64_t N, int64_t m, int C, const double* thr, double* G, int64_t ldg);
+int launch_ord_nan_fix(hipStream_t stream, const double* G, int64_t ldg, const int8_t* cat, int64_t n, int64_t m, double* lp, int64_t N,
+                       int64_t ldlp);
+struct BetaOrdArgs {
+    double* beta; const double* theta; const int8_t* cat; const double* f; const double* thr;
+    const double* pm; const double* ps; const double* step;
+    int C; int64_t n, m, N; double* mu; double* mu_star;
+    uint64_t seed; uint32_t iter; uint32_t item0;
+};
+int launch_draw_beta_ord(hipStream_t stream, const BetaOrdArgs& a);   // the slope's MH step; beta[0, :] is read and never written
+struct OrdThrArgs {
+    const double* f; const double* mu; const int8_t* cat; const long long* counts; int64_t n, m;
+    const double* grid; const double* log_prior; int C, P, W;
+    int* idx; double* thr;                                              // m x (C - 1): the state
+    double* lp; int* window;                                            // m x (C - 1) x W, m x (C - 1): the last update's masses and windows
+    long long* stat;                                                    // pinned, failed, updates
+    uint64_t seed; uint32_t t; uint32_t item0;
+};
+int launch_ord_thresholds(hipStream_t stream, const OrdThrArgs& a);   // one window update of every threshold, one work-group per item
+int launch_ord_irf(hipStream_t stream, const double* fstar, int64_t N, int64_t m, int C, const double* thr, double* cum);
+int launch_ord_record(hipStream_t stream, const int* idx, int64_t m, int C, int P, int64_t slot, uint32_t* hist, int32_t* draws);
+void ord_grid_fill(double hi, int P, double* out);                    // long double, rounded once: the centre exactly 0
 // carry.hip: the consistent step's carry stage (gpirt_sampler_carry_f) and the prior check's reduction (gpirt_sampler_prior_quad)
 struct CarryArgs {
     double* f; const double* theta; const double* fstar; const double* mu_star; int64_t n, m, N;       // f: n x m; fstar, mu_star: N x m

@@ -111,6 +111,27 @@ struct PopState {
     double last_ms = 0.0;
 };
 
+// Ordinal responses (gpirt_sampler_ordinal_enable; include/gpirt_hip.h, ordinal.hip).  on == false: the binary chain, launch for
+// launch what it was.  The indices, thresholds, counters and records live on the device: an update is one launch and no host read.
+struct OrdState {
+    bool on = false;
+    int C = 0, P = 0, W = 16;
+    int lp_W = 16;                    // the width the last update wrote "lp" with (enable: W), the stride gpirt_sampler_ordinal_get reads it by
+    double hi = 0.0;
+    int64_t planned = 0, recorded = 0, irf_draws = 0;
+    uint32_t t = 0;                   // draw_thresholds calls so far (it survives enabling again: no pair of uniforms is replayed)
+    std::vector<double> grid, log_prior;
+    int8_t* cat = nullptr;                                                                 // device: n x m
+    double *d_grid = nullptr, *d_log_prior = nullptr, *thr = nullptr, *lp = nullptr, *cum = nullptr, *Y = nullptr, *G = nullptr;
+                                      // device: P, P, m x (C - 1), m x (C - 1) x GPIRT_ORD_MAX_WIDTH, m x (C - 1) x N, n x C m, Np x C m
+    int *idx = nullptr, *window = nullptr;                                                 // device: m x (C - 1) each
+    long long *counts = nullptr, *stat = nullptr;                                          // device: m x C; pinned, failed, updates
+    uint32_t* hist = nullptr;                                                              // device: m x (C - 1) x P
+    int32_t* draws = nullptr;                                                              // device: planned x m x (C - 1)
+    hipEvent_t tev[2] = {};
+    double last_ms = 0.0;
+};
+
 // F of the rank-64 smooth part, Kcc = F F^T (fstar_free_factor) with its DEAD columns (squared norm <= 1e-13) zeroed on the host,
 // `live` their mask and r the live count, on the device for the kernel with length scale `ell`.  One per sampler, shared by the
 // centred amplitude update and the centred beta update; built by the first call of either and rebuilt only when a sampled length
@@ -310,6 +331,7 @@ struct gpirt_sampler_s {
     GroupsState groups;               // group posteriors (gpirt_sampler_groups_enable; on == false: off)
     EllState ell;                     // the length scale in the chain (gpirt_sampler_ell_enable; on == false: off)
     AmpState amp;                     // per-item GP amplitudes (gpirt_sampler_amp_set, gpirt_sampler_amp_enable; mode == 0: off)
+    OrdState ord;                     // ordinal responses (gpirt_sampler_ordinal_enable; on == false: the binary chain)
     PopState pop;                     // the population prior for theta (gpirt_sampler_pop_set, gpirt_sampler_pop_enable; mode == 0: off)
     CarryState carry;               // the consistent step's carry and the prior check (gpirt_sampler_carry_f, gpirt_sampler_prior_quad)
     SmoothF sf;                       // F of the rank-64 smooth part with its dead columns zeroed (the two centred updates below)
@@ -690,12 +712,21 @@ int do_draw_f(gpirt_sampler_s* s)
         }
         if (s->amp.mode) GP_TRY(launch_amp_scale(st, s->NU, s->amp.amp, n, m));       // nu_j = a_j (L z_j)
         if (prep && !early && !free) GP_HIP(hipEventRecord(s->ev_trmm, st));
+        if (s->ord.on) {                                          // (the ordinal slice: ordinal.hip; y is not read)
+            EssOrdArgs a{};
+            a.f = s->f; a.nu = s->NU; a.mu = s->mu; a.cat = s->ord.cat; a.thr = s->ord.thr; a.counts = s->ord.counts;
+            a.C = s->ord.C; a.n = n; a.m = m; a.k_out = s->ess_k; a.err = s->flags;
+            a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0;
+            a.screen = h->cfg.ess_screen == 1;
+            GP_TRY(launch_ess_ord(st, a));
+        } else {
         EssArgs a{};
         a.f = s->f; a.nu = s->NU; a.y = s->y; a.mu = s->mu; a.n = n; a.m = m; a.k_out = s->ess_k;
         a.err = s->flags; a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0;
         a.ll_exact = h->cfg.ll_exact;
         a.screen = h->cfg.ess_screen == 1;
         GP_TRY(launch_ess(st, a));
+        }
         if (prep) {
             // what the low-rank draw_fstar needs from L alone, on the sampler's own stream (see `early` above)
             hipStream_t ax = s->haux->stream;
@@ -1004,8 +1035,26 @@ int theta_product(gpirt_sampler_s* s, const double* fstar_in, double* logpost_ou
     return launch_theta_nan_fix(st, s->Gpm, Np, s->Ypm, n, m, logpost_out, N, N, only_if);   // (a missing answer over a NaN f*)
 }
 
+// the ordinal counterpart (ordinal.hip): the fp64 product of the N x C m table with the one-hot indicators, K = C m, and the NaN
+// fix behind it -- the int8 fixed-point product is not extended to one-hot operands
+int theta_product_ord(gpirt_sampler_s* s, const double* fstar_in, double* logpost_out)
+{
+    hipStream_t st = s->h->stream;
+    const OrdState& A = s->ord;
+    const int64_t n = s->n, m = s->m, N = s->N;
+    const int64_t Np = (N + 127) / 128 * 128;
+    GP_TRY(launch_ord_loglik_terms(st, fstar_in, N, m, A.C, A.thr, A.G, Np));
+    GP_TRY(launch_gemm(s->h, st, false, true, TRI_NONE, N, n, (int64_t)A.C * m, 1.0, A.G, Np, A.Y, n, 0.0, logpost_out, N, Np));
+    return launch_ord_nan_fix(st, A.G, Np, A.cat, n, m, logpost_out, N, N);
+}
+
 int do_theta_partial(gpirt_sampler_s* s)
 {
+    if (s->ord.on) {
+        GP_TRY(theta_product_ord(s, s->fstar, s->logpost));
+        s->lp_current = true;
+        return 0;
+    }
     GP_TRY(theta_product(s, s->fstar, s->logpost));
     s->lp_current = true;
     return 0;
@@ -1057,6 +1106,13 @@ int do_theta_block(gpirt_sampler_s* s)
 int launch_beta_on(gpirt_sampler_s* s, hipStream_t st)
 {
     s->lp_current = false;
+    if (s->ord.on) {                                              // (the slope alone: the intercept is pinned at 0)
+        BetaOrdArgs a{};
+        a.beta = s->beta; a.theta = s->theta; a.cat = s->ord.cat; a.f = s->f; a.thr = s->ord.thr; a.pm = s->pm; a.ps = s->ps;
+        a.step = s->step; a.C = s->ord.C; a.n = s->n; a.m = s->m; a.N = s->N; a.mu = s->mu; a.mu_star = s->mu_star;
+        a.seed = s->opt.seed; a.iter = (uint32_t)(s->iter + 1); a.item0 = (uint32_t)s->opt.item0;
+        return launch_draw_beta_ord(st, a);
+    }
     BetaArgs a{};
     a.beta = s->beta; a.theta = s->theta; a.y = s->y; a.f = s->f; a.pm = s->pm; a.ps = s->ps;
     a.step = s->step; a.n = s->n; a.m = s->m; a.N = s->N; a.mu = s->mu; a.mu_star = s->mu_star;
@@ -1357,6 +1413,27 @@ void amp_free(AmpState* a)
     *a = AmpState();
     a->t = calls; a->ct = ccalls;
 }
+
+// ---- ordinal responses (include/gpirt_hip.h; the kernels are ordinal.hip's) -----------------------------------------------------
+void ord_free(OrdState* p)
+{
+    const uint32_t calls = p->t;      // the sampler's draw_thresholds calls: enabling again does not replay their uniforms
+    for (void* q : { (void*)p->cat, (void*)p->d_grid, (void*)p->d_log_prior, (void*)p->thr, (void*)p->lp, (void*)p->cum, (void*)p->Y,
+                     (void*)p->G, (void*)p->idx, (void*)p->window, (void*)p->counts, (void*)p->stat, (void*)p->hist, (void*)p->draws })
+        if (q) hipFree(q);
+    for (hipEvent_t t : p->tev) if (t) hipEventDestroy(t);
+    *p = OrdState{};
+    p->t = calls;
+}
+
+// "<entry> is refused while ordinal responses are on: <why>"
+int ord_refuse(const gpirt_sampler_s* s, const char* entry, const char* why)
+{
+    if (!s->ord.on) return 0;
+    set_error("%s is refused while ordinal responses are on: %s", entry, why);
+    return GPIRT_E_ARG;
+}
+#define ORD_BINARY "it evaluates the binary likelihood of y"
 
 // ---- the population prior for theta (include/gpirt_hip.h; the kernels are pop.hip's) -------------------------------------------
 void pop_free(PopState* p)
@@ -2105,6 +2182,7 @@ int gpirt_sampler_destroy(gpirt_sampler_t s)
     ell_free(&s->ell);
     amp_free(&s->amp);
     pop_free(&s->pop);
+    ord_free(&s->ord);
     for (hipEvent_t t : s->carry.tev) if (t) hipEventDestroy(t);      // (its two buffers are in `allocs`)
     for (hipEvent_t t : s->bc.tev) if (t) hipEventDestroy(t);         // (its buffer and the smooth part's F are in `allocs`)
     for (hipEvent_t t : s->sc.tev) if (t) hipEventDestroy(t);         // (the scale move's buffers are in `allocs`)
@@ -2227,6 +2305,7 @@ int gpirt_sampler_set_theta_block(gpirt_sampler_t s, const double* y_block, int6
     GP_ARG(s && (y_block || n_block == 0) && i0 >= 0 && n_block >= 0 && i0 + n_block <= s->n && m_total >= s->m);
     if (stream_mode(s)) { set_error("the R-stream replay cannot be sharded"); return GPIRT_E_ARG; }
     if (s->fstar_full) { set_error("the theta block is already set"); return GPIRT_E_ARG; }
+    GP_TRY(ord_refuse(s, "gpirt_sampler_set_theta_block", "the respondent-block theta path has no one-hot product"));
     if (s->pop.mode) {
         set_error("gpirt_sampler_set_theta_block is refused while a population prior is on: the block path would need the codes of its respondents");
         return GPIRT_E_ARG;
@@ -2436,6 +2515,7 @@ int gpirt_sampler_summary_enable(gpirt_sampler_t s, int parts)
 int gpirt_sampler_summary_enable_planned(gpirt_sampler_t s, int parts, int64_t planned_draws)
 {
     GP_ARG(s && s->initialised);
+    if (parts & (GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) GP_TRY(ord_refuse(s, "gpirt_sampler_summary_enable_planned", "its WAIC and pred parts evaluate the binary likelihood of y"));
     GP_ARG((parts & ~(GPIRT_SUM_THETA_BETA | GPIRT_SUM_F | GPIRT_SUM_PRED | GPIRT_SUM_WAIC | GPIRT_SUM_DIAG |
                       GPIRT_SUM_THETA_HIST | GPIRT_SUM_IRF_BAND)) == 0);
     GP_ARG(planned_draws >= 0 && (!(parts & GPIRT_SUM_DIAG) || planned_draws >= 1));
@@ -2503,6 +2583,7 @@ int gpirt_sampler_summary_totals(gpirt_sampler_t s, double* h_totals)
 int gpirt_sampler_ppc_enable(gpirt_sampler_t s, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc, ppc_free, on, [&] { return ppc_alloc(s->h->stream, &s->ppc, s->n, s->m, s->opt.item0, s->y); });
 }
 
@@ -2546,6 +2627,7 @@ int gpirt_ppc_combine(gpirt_handle_t h, int chains, const void* const* d_states,
 int gpirt_sampler_ppc_pairs_enable(gpirt_sampler_t s, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_pairs_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.pairs, pair_free, on, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         return pair_alloc(s->h->stream, &s->ppc.pairs, s->n, s->m, s->opt.item0, s->y);
@@ -2571,6 +2653,7 @@ int gpirt_ppc_pairs_combine(gpirt_handle_t h, int chains, const void* const* d_s
 int gpirt_sampler_ppc_bins_enable(gpirt_sampler_t s, int h, const int* cuts, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_bins_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.bins, bin_free, on, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         return bin_alloc(s->h->stream, &s->ppc.bins, s->n, s->m, s->opt.item0, s->ppc.rblocks, h, cuts);
@@ -2596,6 +2679,7 @@ int gpirt_ppc_bins_combine(gpirt_handle_t h, int chains, const void* const* d_st
 int gpirt_sampler_ppc_dif_enable(gpirt_sampler_t s, int G, const int32_t* groups, int h, const int* cuts, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_dif_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.dif, dif_free, on, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         return dif_alloc(s->h->stream, &s->ppc.dif, s->n, s->m, s->opt.item0, G, groups, h, cuts);
@@ -2623,6 +2707,7 @@ int gpirt_ppc_scores_check(int64_t n, int64_t m, int K, const int* cuts) { retur
 int gpirt_sampler_ppc_scores_enable(gpirt_sampler_t s, int K, const int* cuts, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_scores_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.scores, pps_free, on, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
@@ -2657,6 +2742,7 @@ int gpirt_ppc_person_check(int64_t n, int64_t m, int K, const int32_t* order, co
 int gpirt_sampler_ppc_person_enable(gpirt_sampler_t s, int K, const int32_t* order, const int* cuts, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_person_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.person, prs_free, on, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
@@ -2686,6 +2772,7 @@ int gpirt_ppc_person_combine(gpirt_handle_t h, int chains, const void* const* d_
 int gpirt_sampler_ppc_resid_enable(gpirt_sampler_t s, int top)
 {
     GP_ARG(s && s->initialised);
+    if (top != 0) GP_TRY(ord_refuse(s, "gpirt_sampler_ppc_resid_enable", ORD_BINARY));
     return stage_enable(s, &s->ppc.resid, rsd_free, top != 0, [&]() -> int {
         GP_TRY(needs(blk_ppc(s)));
         GP_TRY(check_top("residual PPC", top, GPIRT_RESID_MAX_TOP));
@@ -2774,6 +2861,7 @@ int gpirt_shape_combine(gpirt_handle_t h, int chains, const void* const* d_state
 int gpirt_sampler_sumscore_enable(gpirt_sampler_t s, const unsigned char* items_mask, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_sumscore_enable", "its scores are sums of binary answers"));
     if (on) GP_TRY(sumscore_check(s->m, items_mask, nullptr));   // refused before the old state goes
     return stage_enable(s, &s->sumscore, sumscore_free, on,
                         [&] { return sumscore_alloc(s->h->stream, &s->sumscore, s->m, items_mask); });
@@ -2814,6 +2902,7 @@ int gpirt_sumscore_combine(gpirt_handle_t h, int chains, const void* const* d_st
 int gpirt_sampler_equate_enable(gpirt_sampler_t s, const unsigned char* mask_x, const unsigned char* mask_y, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_equate_enable", "its scores are sums of binary answers"));
     if (on) GP_TRY(equate_check(s->m, mask_x, mask_y, nullptr, nullptr));   // refused before the old state goes
     return stage_enable(s, &s->equate, equate_free, on,
                         [&] { return equate_alloc(s->h->stream, &s->equate, s->m, mask_x, mask_y); });
@@ -2847,6 +2936,7 @@ int gpirt_equate_combine(gpirt_handle_t h, int chains, const void* const* d_stat
 int gpirt_sampler_loo_enable(gpirt_sampler_t s, int64_t planned_total_draws, int tail, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_loo_enable", ORD_BINARY));
     int64_t M = 0;
     if (on) GP_TRY(loo_tail_length(planned_total_draws, tail, &M));   // refused before the old state goes
     return stage_enable(s, &s->loo, loo_free, on,
@@ -2931,6 +3021,7 @@ int gpirt_acf_check(int64_t n, int64_t m, int parts, int64_t planned_draws, int6
 int gpirt_sampler_acf_enable(gpirt_sampler_t s, int parts, int64_t planned_draws, int64_t max_lag, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on && (parts & GPIRT_ACF_LL)) GP_TRY(ord_refuse(s, "gpirt_sampler_acf_enable", "its log-likelihood series evaluates the binary likelihood of y"));
     int64_t L = 0;
     if (on) GP_TRY(acf_check(s->n, s->m, parts, planned_draws, max_lag, &L, nullptr));   // refused before the old state goes
     return stage_enable(s, &s->acf, acf_free, on,
@@ -2963,6 +3054,7 @@ int gpirt_groups_check(int64_t n, int64_t m, int G, const int32_t* groups, int t
 int gpirt_sampler_groups_enable(gpirt_sampler_t s, int G, const int32_t* groups, int top, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_groups_enable", "its vote part evaluates the binary likelihood of y"));
     if (on) {                                         // refused before the old state goes
         if (s->opt.item0 != 0 || s->opt.m_total != s->m) {
             set_error("groups: not offered for an item shard (the vote part runs over all items)");
@@ -2995,6 +3087,7 @@ int gpirt_groups_combine(gpirt_handle_t h, int chains, const void* const* d_stat
 int gpirt_sampler_score_enable(gpirt_sampler_t s, const double* h_y_new, int64_t n_new)
 {
     GP_ARG(s && s->initialised);
+    if (h_y_new && n_new != 0) GP_TRY(ord_refuse(s, "gpirt_sampler_score_enable", ORD_BINARY));
     const bool on = h_y_new && n_new != 0;
     if (on) {                                           // every refusal before the old state is touched
         if (n_new < 1 || n_new > GPIRT_SCORE_MAX_N) {
@@ -3031,6 +3124,7 @@ int gpirt_score_combine(gpirt_handle_t h, int chains, const void* const* d_state
 int gpirt_sampler_score_predict_enable(gpirt_sampler_t s, int on)
 {
     GP_ARG(s && s->initialised);
+    if (on) GP_TRY(ord_refuse(s, "gpirt_sampler_score_predict_enable", ORD_BINARY));
     if (on) GP_TRY(needs(blk_score(s)));
     return stage_enable(s, &s->score.pred, pred_free, on, [&] { return pred_alloc(s->h->stream, &s->score); });
 }
@@ -3126,6 +3220,7 @@ int gpirt_sampler_ell_enable(gpirt_sampler_t s, double lo, double hi, int P, con
 int gpirt_sampler_draw_ell(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ord_refuse(s, "gpirt_sampler_draw_ell", ORD_BINARY));
     GP_TRY(needs(s->ell.on, "the length-scale update is", "gpirt_sampler_ell_enable"));
     return do_draw_ell(s, ELL_WHITENED);
 }
@@ -3333,6 +3428,7 @@ int gpirt_sampler_amp_enable(gpirt_sampler_t s, double lo, double hi, int P, con
 int gpirt_sampler_draw_amp(gpirt_sampler_t s)
 {
     GP_ARG(s && s->initialised);
+    GP_TRY(ord_refuse(s, "gpirt_sampler_draw_amp", ORD_BINARY));
     AmpState& A = s->amp;
     GP_TRY(needs(A.mode == 2, "the amplitude update is", "gpirt_sampler_amp_enable"));
     // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
@@ -3554,6 +3650,7 @@ int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s)
 {
     GP_ARG(s != nullptr);
     const char* me = "gpirt_sampler_draw_amp_centred";
+    GP_TRY(ord_refuse(s, "gpirt_sampler_draw_amp_centred", ORD_BINARY));
     if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
     if (stream_mode(s)) { set_error("%s: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw", me); return GPIRT_E_ARG; }
     if (s->opt.kernel_fp32) { set_error("%s: kernel_fp32 is refused, the single-precision build is the default kernel's alone", me); return GPIRT_E_ARG; }
@@ -3679,6 +3776,7 @@ int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s)
 {
     GP_ARG(s != nullptr);
     const char* me = "gpirt_sampler_draw_beta_centred";
+    GP_TRY(ord_refuse(s, "gpirt_sampler_draw_beta_centred", "it moves the intercept, which ordinal responses pin at 0"));
     if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
     if (stream_mode(s)) { set_error("%s: rng = reference (GPIRT_RNG_RSTREAM) is refused, R's stream has no such draw", me); return GPIRT_E_ARG; }
     if (s->opt.kernel_fp32) { set_error("%s: kernel_fp32 is refused, the single-precision build is the default kernel's alone", me); return GPIRT_E_ARG; }
@@ -3935,6 +4033,7 @@ static int scale_read_times(gpirt_sampler_t s)
 int gpirt_sampler_draw_scale(gpirt_sampler_t s, int kind)
 {
     GP_ARG(s != nullptr);
+    GP_TRY(ord_refuse(s, "gpirt_sampler_draw_scale", ORD_BINARY));
     const bool timed = s->timing;
     GP_TRY(do_draw_scale(s, kind, "gpirt_sampler_draw_scale", timed));
     if (timed) GP_TRY(scale_read_times(s));      // (timing on: one synchronisation, as the centred updates')
@@ -3946,6 +4045,7 @@ int gpirt_sampler_draw_scale(gpirt_sampler_t s, int kind)
 int gpirt_sampler_step_consistent_scale(gpirt_sampler_t s, int nugget, int kinds)
 {
     GP_ARG(s != nullptr);
+    if (kinds) GP_TRY(ord_refuse(s, "gpirt_sampler_step_consistent_scale", ORD_BINARY));
     const char* me = "gpirt_sampler_step_consistent_scale";
     GP_TRY(carry_refusals(s, nugget, me));
     if (kinds < 0 || kinds > 3) { set_error("%s: kinds = %d, it is a mask of 1 (scale) and 2 (shift)", me, kinds); return GPIRT_E_ARG; }
@@ -4271,6 +4371,220 @@ int gpirt_sampler_pop_stats(gpirt_sampler_t s, gpirt_pop* out)
     return 0;
 }
 
+// ---- ordinal responses ------------------------------------------------------------------------------------------------------------
+int gpirt_sampler_ordinal_enable(gpirt_sampler_t s, const int8_t* cat, int C, double hi, int P, const double* log_prior,
+                                 const int32_t* K0, int W, int64_t planned_draws)
+{
+    GP_ARG(s != nullptr);
+    OrdState& A = s->ord;
+    const char* me = "gpirt_sampler_ordinal_enable";
+    if (!cat) {
+        GP_HIP(hipStreamSynchronize(s->h->stream));
+        s->lp_current = false;
+        ord_free(&A);
+        return 0;
+    }
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    if (s->fstar_full) {
+        set_error("%s is refused while gpirt_sampler_set_theta_block is in use: the respondent-block theta path has no one-hot product", me);
+        return GPIRT_E_ARG;
+    }
+    if (s->opt.m_total > 0 && s->opt.m_total != s->m) {
+        set_error("ordinal: an item shard (item0 = %lld, m_total = %lld) is refused, the respondent-block theta path has no one-hot product",
+                  (long long)s->opt.item0, (long long)s->opt.m_total);
+        return GPIRT_E_ARG;
+    }
+    if (s->h->cfg.ll_exact == 1) {
+        set_error("%s is refused under GPIRT_LL_EXACT=1: the ordinal kernels have the fast term alone", me);
+        return GPIRT_E_ARG;
+    }
+    // the analysis blocks that evaluate the binary likelihood: none may be on
+    const char* blk = nullptr;
+    if (s->sum.parts & (GPIRT_SUM_PRED | GPIRT_SUM_WAIC)) blk = "the summaries' WAIC / pred parts (gpirt_sampler_summary_enable)";
+    else if (s->ppc.on) blk = "the posterior predictive checks (gpirt_sampler_ppc_enable)";
+    else if (s->loo.on) blk = "PSIS-LOO (gpirt_sampler_loo_enable)";
+    else if (s->score.on) blk = "scoring (gpirt_sampler_score_enable)";
+    else if (s->sumscore.on) blk = "the sum-score posteriors (gpirt_sampler_sumscore_enable)";
+    else if (s->equate.on) blk = "the score equating (gpirt_sampler_equate_enable)";
+    else if (s->groups.on) blk = "the group posteriors (gpirt_sampler_groups_enable)";
+    else if (s->acf.on && (s->acf.parts & GPIRT_ACF_LL)) blk = "the ACF's log-likelihood series (gpirt_sampler_acf_enable)";
+    if (blk) { set_error("%s is refused while %s are on: they evaluate the binary likelihood of y", me, blk); return GPIRT_E_ARG; }
+    const int64_t n = s->n, m = s->m, N = s->N, Np = (N + 127) / 128 * 128;
+    if (planned_draws < 0 || planned_draws > (int64_t)1 << 31) {
+        set_error("ordinal: planned_draws = %lld, it must lie in 0 .. 2^31", (long long)planned_draws);
+        return GPIRT_E_ARG;
+    }
+    hipStream_t st = s->h->stream;
+    GP_TRY(beta_sync(s));                     // (a held-back draw_beta writes beta, mu and mu_star)
+    std::vector<double> hy((size_t)(n * m));
+    GP_HIP(hipMemcpyAsync(hy.data(), s->y, sizeof(double) * (size_t)(n * m), hipMemcpyDeviceToHost, st));
+    GP_HIP(hipStreamSynchronize(st));
+    GP_TRY(gpirt_ordinal_check(cat, hy.data(), n, m, C, hi, P, log_prior, K0, W, &s->opt));
+    s->lp_current = false;
+    ord_free(&A);
+    auto fail = [&](int rc, const char* what) { set_error("ordinal: %s failed", what); ord_free(&A); return rc; };
+    const size_t rows = (size_t)m * (size_t)(C - 1), Ps = (size_t)P;
+    const size_t draw_bytes = sizeof(int32_t) * (size_t)(planned_draws ? planned_draws : 1) * rows;
+    if (hipMalloc((void**)&A.cat, (size_t)(n * m)) != hipSuccess ||
+        hipMalloc((void**)&A.d_grid, sizeof(double) * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.d_log_prior, sizeof(double) * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.thr, sizeof(double) * rows) != hipSuccess ||
+        hipMalloc((void**)&A.lp, sizeof(double) * rows * GPIRT_ORD_MAX_WIDTH) != hipSuccess ||
+        hipMalloc((void**)&A.cum, sizeof(double) * rows * (size_t)N) != hipSuccess ||
+        hipMalloc((void**)&A.Y, sizeof(double) * (size_t)n * (size_t)C * (size_t)m) != hipSuccess ||
+        hipMalloc((void**)&A.G, sizeof(double) * ((size_t)Np * (size_t)C * (size_t)m + 2)) != hipSuccess ||
+        hipMalloc((void**)&A.idx, sizeof(int) * rows) != hipSuccess ||
+        hipMalloc((void**)&A.window, sizeof(int) * rows) != hipSuccess ||
+        hipMalloc((void**)&A.counts, sizeof(long long) * (size_t)m * (size_t)C) != hipSuccess ||
+        hipMalloc((void**)&A.stat, sizeof(long long) * 4) != hipSuccess ||
+        hipMalloc((void**)&A.hist, sizeof(uint32_t) * rows * Ps) != hipSuccess ||
+        hipMalloc((void**)&A.draws, draw_bytes) != hipSuccess) return fail(GPIRT_E_ALLOC, "hipMalloc");
+    A.C = C; A.P = P; A.W = W; A.lp_W = W; A.hi = hi; A.planned = planned_draws; A.recorded = 0; A.irf_draws = 0;
+    A.grid.resize(Ps); A.log_prior.resize(Ps);
+    ord_grid_fill(hi, P, A.grid.data());
+    for (int k = 0; k < P; ++k) A.log_prior[(size_t)k] = log_prior ? log_prior[k] : -(A.grid[(size_t)k] * A.grid[(size_t)k]) / 18.0;
+    std::vector<int> idx(rows);
+    std::vector<double> thr(rows);
+    for (int64_t j = 0; j < m; ++j)
+        for (int c = 1; c < C; ++c) {
+            const size_t r = (size_t)j * (size_t)(C - 1) + (size_t)(c - 1);
+            idx[r] = K0 ? K0[r] : (2 * (P - 1) * c + C) / (2 * C);
+            thr[r] = A.grid[(size_t)idx[r]];
+        }
+    if (hipMemcpyAsync(A.cat, cat, (size_t)(n * m), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_grid, A.grid.data(), sizeof(double) * Ps, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.d_log_prior, A.log_prior.data(), sizeof(double) * Ps, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.idx, idx.data(), sizeof(int) * rows, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(A.thr, thr.data(), sizeof(double) * rows, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(A.lp, 0, sizeof(double) * rows * GPIRT_ORD_MAX_WIDTH, st) != hipSuccess ||
+        hipMemsetAsync(A.cum, 0, sizeof(double) * rows * (size_t)N, st) != hipSuccess ||
+        hipMemsetAsync(A.G, 0, sizeof(double) * ((size_t)Np * (size_t)C * (size_t)m + 2), st) != hipSuccess ||
+        hipMemsetAsync(A.window, 0, sizeof(int) * rows, st) != hipSuccess ||
+        hipMemsetAsync(A.stat, 0, sizeof(long long) * 4, st) != hipSuccess ||
+        hipMemsetAsync(A.hist, 0, sizeof(uint32_t) * rows * Ps, st) != hipSuccess ||
+        hipMemsetAsync(A.draws, 0, draw_bytes, st) != hipSuccess) return fail(GPIRT_E_HIP, "the upload");
+    if (launch_ord_indicators(st, A.cat, n, m, C, A.Y) != 0 || launch_ord_counts(st, A.cat, n, m, C, A.counts) != 0)
+        return fail(GPIRT_E_HIP, "the indicator launch");
+    // the pinned intercept: beta[0, :] = 0, mu and mu_star refreshed with draw_beta's expression
+    std::vector<double> hb((size_t)(2 * m));
+    if (hipMemcpyAsync(hb.data(), s->beta, sizeof(double) * (size_t)(2 * m), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return fail(GPIRT_E_HIP, "reading beta");
+    for (int64_t j = 0; j < m; ++j) hb[(size_t)(2 * j)] = 0.0;
+    if (hipMemcpyAsync(s->beta, hb.data(), sizeof(double) * (size_t)(2 * m), hipMemcpyHostToDevice, st) != hipSuccess ||
+        launch_linear_mean(st, s->theta, n, s->beta, m, s->mu) != 0 ||
+        launch_linear_mean(st, s->tstar, N, s->beta, m, s->mu_star) != 0 ||
+        hipStreamSynchronize(st) != hipSuccess) return fail(GPIRT_E_HIP, "pinning the intercept");      // (the host vectors go out of scope)
+    A.on = true;
+    return 0;
+}
+
+int gpirt_sampler_draw_thresholds(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    GP_TRY(beta_sync(s));                     // mu of a held-back draw_beta
+    s->lp_current = false;
+    OrdThrArgs a{};
+    a.f = s->f; a.mu = s->mu; a.cat = A.cat; a.counts = A.counts; a.n = s->n; a.m = s->m;
+    a.grid = A.d_grid; a.log_prior = A.d_log_prior; a.C = A.C; a.P = A.P; a.W = A.W;
+    a.idx = A.idx; a.thr = A.thr; a.lp = A.lp; a.window = A.window; a.stat = A.stat;
+    a.seed = s->opt.seed; a.t = A.t + 1; a.item0 = (uint32_t)s->opt.item0;
+    hipStream_t st = s->h->stream;
+    const bool timed = s->timing;
+    if (timed) {
+        for (hipEvent_t& t : A.tev) if (!t) GP_HIP(hipEventCreate(&t));
+        GP_HIP(hipEventRecord(A.tev[0], st));
+    }
+    GP_TRY(launch_ord_thresholds(st, a));
+    A.t += 1;
+    A.lp_W = A.W;
+    if (timed) {                              // (timing on: one synchronisation, as the amplitude update's)
+        GP_HIP(hipEventRecord(A.tev[1], st));
+        GP_HIP(hipEventSynchronize(A.tev[1]));
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, A.tev[0], A.tev[1]);
+        A.last_ms = ms;
+    }
+    return 0;
+}
+
+int gpirt_sampler_ordinal_width(gpirt_sampler_t s, int W)
+{
+    GP_ARG(s != nullptr);
+    GP_TRY(needs(s->ord.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    if (W < 1 || W > GPIRT_ORD_MAX_WIDTH) { set_error("ordinal: window width W = %d, it must lie in 1 .. %d", W, GPIRT_ORD_MAX_WIDTH); return GPIRT_E_ARG; }
+    s->ord.W = W;                             // (from the next update on; "lp" keeps the last update's width, lp_W, until then)
+    return 0;
+}
+
+int gpirt_sampler_ordinal_record(gpirt_sampler_t s)
+{
+    GP_ARG(s != nullptr);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    if (A.recorded >= A.planned) { set_error("ordinal: all %lld planned draws are recorded", (long long)A.planned); return GPIRT_E_ARG; }
+    GP_TRY(launch_ord_record(s->h->stream, A.idx, s->m, A.C, A.P, A.recorded, A.hist, A.draws));
+    A.recorded += 1;
+    return 0;
+}
+
+int gpirt_sampler_ordinal_accumulate_irf(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    GP_TRY(launch_ord_irf(s->h->stream, s->fstar, s->N, s->m, A.C, A.thr, A.cum));
+    A.irf_draws += 1;
+    return 0;
+}
+
+int gpirt_sampler_ordinal_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    const int64_t n = s->n, m = s->m, N = s->N, rows = m * (A.C - 1), P = A.P;
+    const void* host = nullptr; const void* dev = nullptr; int64_t want = 0;
+    if (strcmp(name, "cat") == 0) { dev = A.cat; want = n * m; }
+    else if (strcmp(name, "grid") == 0) { host = A.grid.data(); want = 8 * P; }
+    else if (strcmp(name, "log_prior") == 0) { host = A.log_prior.data(); want = 8 * P; }
+    else if (strcmp(name, "index") == 0) { dev = A.idx; want = 4 * rows; }
+    else if (strcmp(name, "thresholds") == 0) { dev = A.thr; want = 8 * rows; }
+    else if (strcmp(name, "counts") == 0) { dev = A.counts; want = 8 * m * A.C; }
+    else if (strcmp(name, "lp") == 0) { dev = A.lp; want = 8 * rows * A.lp_W; }
+    else if (strcmp(name, "window") == 0) { dev = A.window; want = 4 * rows; }
+    else if (strcmp(name, "hist") == 0) { dev = A.hist; want = 4 * rows * P; }
+    else if (strcmp(name, "draws") == 0) { dev = A.draws; want = 4 * A.recorded * rows; }
+    else if (strcmp(name, "cum") == 0) { dev = A.cum; want = 8 * rows * N; }
+    else if (strcmp(name, "pinned") == 0) { dev = A.stat; want = 8; }
+    else if (strcmp(name, "failed") == 0) { dev = A.stat + 1; want = 8; }
+    else if (strcmp(name, "updates") == 0) { dev = A.stat + 2; want = 8; }
+    else { set_error("unknown ordinal array '%s'", name); return GPIRT_E_ARG; }
+    if (bytes != want) { set_error("ordinal: '%s' holds %lld bytes, %lld were asked for", name, (long long)want, (long long)bytes); return GPIRT_E_ARG; }
+    if (want == 0) return 0;
+    if (host) { memcpy(h_out, host, (size_t)want); return 0; }
+    GP_HIP(hipMemcpyAsync(h_out, dev, (size_t)want, hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+int gpirt_sampler_ordinal_stats(gpirt_sampler_t s, gpirt_ordinal* out)
+{
+    GP_ARG(s && out);
+    const OrdState& A = s->ord;
+    memset(out, 0, sizeof(*out));
+    out->on = A.on ? 1 : 0; out->n = s->n; out->m = s->m; out->calls = A.t; out->hi = (double)NAN;
+    if (!A.on) return 0;
+    long long st3[3];
+    GP_HIP(hipMemcpyAsync(st3, A.stat, sizeof(st3), hipMemcpyDeviceToHost, s->h->stream));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    out->categories = A.C; out->points = A.P; out->width = A.W; out->lp_width = A.lp_W; out->hi = A.hi; out->last_ms = A.last_ms;
+    out->pinned = st3[0]; out->failed = st3[1]; out->updates = st3[2];
+    out->planned_draws = A.planned; out->recorded = A.recorded; out->irf_draws = A.irf_draws;
+    return 0;
+}
+
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)
 {
     GP_ARG(s && iter);
@@ -4476,6 +4790,10 @@ int gpirt_sampler_panel_copy_part(gpirt_sampler_t s, int64_t p, int half, double
 int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
 {
     GP_ARG(dst && src && dst->initialised && src->initialised && dst->n == src->n && dst->m == src->m && dst->h == src->h);
+    if (dst->ord.on || src->ord.on) {
+        set_error("gpirt_sampler_copy_state is refused while ordinal responses are on: the categories, thresholds and records are not copied");
+        return GPIRT_E_ARG;
+    }
     if (dst->ell.on || src->ell.on) {
         set_error("gpirt_sampler_copy_state is not defined while the length-scale update is on (the index and its tables are not copied)");
         return GPIRT_E_ARG;
@@ -4542,6 +4860,11 @@ int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, i
     void* p; int64_t c;
     GP_TRY(lookup(s, name, &p, &c));
     GP_ARG(count <= c && strcmp(name, "ess_k") != 0);
+    if (s->ord.on && strcmp(name, "y") == 0)
+        GP_TRY(ord_refuse(s, "gpirt_sampler_set(\"y\")", "the categories were checked against y's missing cells at enable"));
+    if (s->ord.on && strcmp(name, "beta") == 0)
+        for (int64_t q = 0; q < count; q += 2)
+            if (h_in[q] != 0.0) GP_TRY(ord_refuse(s, "gpirt_sampler_set(\"beta\") with a non-zero intercept", "the intercept is pinned at 0"));
     GP_TRY(aux_join(s));
     invalidate_factor_products(s);
     s->lp_current = false;

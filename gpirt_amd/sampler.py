@@ -2009,6 +2009,99 @@ class Sampler:
         out["mode"] = _lib.POP_MODES[int(p.on)]
         return out
 
+    # -- ordinal (graded) responses, the thresholds sampled in the chain (include/gpirt_hip.h gpirt_sampler_ordinal_*, gpirt_amd.ordinal)
+    def ordinal_enable(self, cat, C=None, hi=6.0, points=241, log_prior=None, K0=None, width=16, planned_draws=0):
+        """Turn the chain into the cumulative-logit model on the categories cat (n x m, 0 = missing, 1 .. C; C: the number
+        of categories, None: cat.max()).  The sampler must have been created on gpirt_amd.ordinal.dichotomise(cat).  The thresholds live on
+        gpirt_amd.ordinal.grid(hi, points) with the log masses log_prior (None: -t^2 / 18) and start at the indices K0 (m x (C - 1),
+        strictly increasing; None: the library's equally spaced start -- gpirt_amd.ordinal.init_thresholds gives the data's).
+        beta[0, :] is set to 0 and stays there.  From then on step() runs the ordinal kernels and draw_thresholds() updates the
+        thresholds; width: the window W of that update.  After init().  cat=None turns ordinal off.  Refused with the reason:
+        rng="reference", an item shard, theta_block in use, n > 16384, an analysis block that reads y already on."""
+        import ctypes as ct                   # (the keyword C is the issue's name for the number of categories)
+        if cat is None:
+            check(self.lib.gpirt_sampler_ordinal_enable(self._s, None, 0, 0.0, 0, None, None, 0, 0))
+            self._ord = (0, 0, 0)
+            return
+        c8 = np.asfortranarray(np.asarray(cat, dtype=np.int8))
+        if c8.shape != (self.n, self.m):
+            raise ValueError(f"ordinal_enable: cat must be {self.n} x {self.m}")
+        Cn = int(C) if C is not None else int(c8.max())
+        P = int(points)
+        lp = None if log_prior is None else np.ascontiguousarray(log_prior, dtype=np.float64).reshape(-1)
+        if lp is not None and lp.shape != (P,):
+            raise ValueError(f"ordinal_enable: log_prior must hold points = {P} values")
+        k0 = None if K0 is None else np.ascontiguousarray(K0, dtype=np.int32)
+        if k0 is not None and k0.shape != (self.m, max(Cn - 1, 0)):
+            raise ValueError(f"ordinal_enable: K0 must be m x (C - 1) = {self.m} x {Cn - 1}")
+        check(self.lib.gpirt_sampler_ordinal_enable(
+            self._s, c8.ctypes.data_as(ct.POINTER(ct.c_int8)), Cn, float(hi), P, None if lp is None else _ptr(lp),
+            None if k0 is None else k0.ctypes.data_as(ct.POINTER(ct.c_int32)), int(width), int(planned_draws)))
+        self._ord = (Cn, P, int(width))
+
+    def draw_thresholds(self):
+        """One exact Gibbs update of every threshold on the grid inside a randomly placed window: one launch, nothing is read
+        back (gpirt_amd.ordinal.thresholds_exact is its NumPy statement).  A call of its own after step(), as draw_pop is."""
+        self._call("gpirt_sampler_draw_thresholds")
+
+    def ordinal_width(self, width):
+        """The window W of draw_thresholds from the next update on, 1 .. 64.  ordinal_get("lp") keeps the layout of the update
+        that wrote it (ordinal_stats()["lp_width"]) until then."""
+        check(self.lib.gpirt_sampler_ordinal_width(self._s, int(width)))
+        Cn, P, _ = getattr(self, "_ord", (0, 0, 0))
+        self._ord = (Cn, P, int(width))
+
+    def ordinal_record(self):
+        """Append the current threshold indices to the draw buffer and add 1 to their histogram cells, on the device."""
+        self._call("gpirt_sampler_ordinal_record")
+
+    def ordinal_accumulate_irf(self):
+        """cum[j, c, k] += sigma(f*[k, j] - b_{j,c}) = P(y > c | theta_k) under the current draw (gpirt_amd.ordinal.curves)."""
+        self._call("gpirt_sampler_ordinal_accumulate_irf")
+
+    def ordinal_get(self, name: str) -> np.ndarray:
+        """One array by name: cat (int8, n x m), grid, log_prior (points), index (int32, m x (C - 1)), thresholds (m x (C - 1)),
+        counts (int64, m x C: observed cells per category), lp (m x (C - 1) x W: the last update's masses by window slot, -inf
+        outside the candidates; W is that update's width), window (int32, m x (C - 1): the last windows' first index), hist (uint32, m x (C - 1) x points),
+        draws (int32, recorded x m x (C - 1)), cum (m x (C - 1) x 1001), pinned, failed, updates (int64 scalars)."""
+        Cn, P, W = getattr(self, "_ord", (0, 0, 0))
+        if name == "lp":
+            W = self.ordinal_stats()["lp_width"]      # the width of the update that wrote it, whatever ordinal_width set since
+        m, R = self.m, max(Cn - 1, 0)
+        shapes = {"grid": ((P,), np.float64), "log_prior": ((P,), np.float64), "index": ((m, R), np.int32),
+                  "thresholds": ((m, R), np.float64), "counts": ((m, Cn), np.int64), "lp": ((m, R, W), np.float64),
+                  "window": ((m, R), np.int32), "hist": ((m, R, P), np.uint32), "cum": ((m, R, NGRID), np.float64),
+                  "pinned": ((1,), np.int64), "failed": ((1,), np.int64), "updates": ((1,), np.int64)}
+        if name == "cat":
+            out = np.empty((self.n, m), dtype=np.int8, order="F")
+        elif name == "draws":
+            out = np.empty((self.ordinal_stats()["recorded"], m, R), dtype=np.int32)
+        else:
+            shape, dt = shapes.get(name, ((0,), np.float64))
+            out = np.empty(shape, dtype=dt)
+        self._get_into("gpirt_sampler_ordinal_get", name, out)
+        return int(out[0]) if name in ("pinned", "failed", "updates") else out
+
+    def ordinal_stats(self) -> dict:
+        """gpirt_sampler_ordinal_stats: on, n, m, categories, points, width, calls, pinned, failed, updates, planned_draws,
+        recorded, irf_draws, lp_width (the W of the last update: the slots per row of "lp"), hi, time_ms."""
+        p = _lib.Ordinal()
+        check(self.lib.gpirt_sampler_ordinal_stats(self._s, C.byref(p)))
+        out = {k: int(getattr(p, k)) for k in ("n", "m", "categories", "points", "width", "calls", "pinned", "failed", "updates",
+                                               "planned_draws", "recorded", "irf_draws", "lp_width")}
+        out.update(on=bool(p.on), hi=float(p.hi), time_ms=float(p.last_ms))
+        return out
+
+    def ordinal(self, probs=(0.025, 0.5, 0.975)) -> dict:
+        """The recorded thresholds summarised and the accumulated curves finished (gpirt_amd.ordinal.summarise and curves)."""
+        from . import ordinal as OR
+        st = self.ordinal_stats()
+        out = OR.summarise(self.ordinal_get("draws"), self.ordinal_get("grid"), probs=probs)
+        out.update(hist=self.ordinal_get("hist"), counters={k: st[k] for k in ("pinned", "failed", "updates")})
+        if st["irf_draws"]:
+            out["curves"] = OR.curves(self.ordinal_get("cum"), st["irf_draws"])
+        return out
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

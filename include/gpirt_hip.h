@@ -61,6 +61,7 @@ enum {
     GPIRT_ST_AMP = 10,    /* the two uniforms per item of an amplitude update (gpirt_sampler_draw_amp): item index item0 + j, index 0 / 1; nothing else draws from it */
     GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
+    GPIRT_ST_ORD = 16,    /* the two uniforms per threshold of an ordinal threshold update (gpirt_sampler_draw_thresholds): item index item0 + j, index 2 (c - 1) the window's placement, 2 (c - 1) + 1 the draw; nothing else draws from it */
     GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
 
@@ -2625,6 +2626,78 @@ int gpirt_sampler_draw_pop(gpirt_sampler_t s);
 int gpirt_sampler_pop_record(gpirt_sampler_t s);
 int gpirt_sampler_pop_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_pop_stats(gpirt_sampler_t s, gpirt_pop* out);
+
+/* ------------------------------------------------------ ordinal (graded) responses: thresholds sampled in the chain --- */
+/* Library version 139.  The cumulative-logit (graded response) model on the same f: with g = f + mu and an item's thresholds
+ * b_1 < ... < b_{C-1} (b_0 = -inf, b_C = +inf),
+ *   P(y = c | g, b) = sigma(b_c - g) - sigma(b_{c-1} - g) = sigma(b_c - g) sigma(g - b_{c-1}) (1 - e^-(b_c - b_{c-1}))
+ *   log P = -ll(b_c - g) [c < C] - ll(g - b_{c-1}) [c > 1] + w(b_c - b_{c-1}) [1 < c < C],  ll(a) = log(1 + e^-a), w(d) = log1p(-e^-d)
+ * Stage API only: gpirt_run, gpirt_mcmc* and gpirt_options are unchanged, and a sampler on which gpirt_sampler_ordinal_enable was
+ * never called launches exactly the kernels it launched before.
+ *
+ * cat is n x m int8, column-major: 0 = missing, 1 .. C a category, 2 <= C <= GPIRT_ORD_MAX_C, the same C for every item (an item
+ * need not use every category).  The sampler is created on the dichotomised matrix (gpirt_amd.ordinal.dichotomise); enable
+ * refuses unless its y is NaN exactly where cat is 0, and while ordinal is on nothing of the chain reads y.  The thresholds live on
+ * the grid t_k = hi (2k - (P - 1)) / (P - 1) (gpirt_ordinal_grid: long double, rounded once; P odd, the centre exactly 0, the end
+ * points exact; GPIRT_ORD_MIN_POINTS <= P <= GPIRT_ORD_MAX_POINTS, 0 < hi <= 20); the state is the int32 index K[j, c], c = 1 ..
+ * C - 1, strictly increasing in c (row-major m x (C - 1)).  log_prior: P finite log masses (NULL: -t^2 / 18, sd 3).  K0: the start
+ * (NULL: k_c = ((2 (P - 1) c + C) / (2 C), integer division -- for C = 2 the centre; gpirt_amd.ordinal.init_thresholds starts from the data).
+ * The intercept is pinned: enable sets beta[0, :] = 0 and refreshes mu and mu_star; location is the thresholds'.
+ *
+ * While ordinal is on, gpirt_sampler_step (and _step_consistent) run draw_f with the ordinal slice kernel (the same uniforms of
+ * GPIRT_ST_F_ESS, bracket rule, trial cap and failure behaviour; with C = 2 and the one threshold at the centre it is the binary
+ * kernel bit for bit), draw_fstar unchanged, theta_partial as the fp64 product of the N x C m table
+ *   G[k, (c - 1) m + j] = -ll(b_c - f*_kj) [c < C] - ll(f*_kj - b_{c-1}) [c > 1]
+ * with the one-hot n x C m indicators (the int8 fixed-point product is not extended), theta_finish unchanged (the population prior
+ * composes), and draw_beta as the reference's MH step for the SLOPE alone (GPIRT_ST_BETA indices 2 and 3, the binary kernel's).
+ * gpirt_sampler_draw_thresholds is a call of its own after the step: exact Gibbs for each threshold on the grid points of a
+ * randomly placed window [a, a + W), a = k - (int)(u0 W), that lie strictly between the neighbouring thresholds -- a set that does
+ * not depend on k, so the move leaves the posterior invariant.  csrc/ordinal.hip states the order of every operation.
+ * gpirt_sampler_ordinal_record appends K to the draw buffer (planned_draws x m x (C - 1) int32) and adds to the histogram
+ * (m x (C - 1) x P uint32); gpirt_sampler_ordinal_accumulate_irf adds sigma(f*[k, j] - b_{j,c}) = P(y > c | theta_k) to cum
+ * (m x (C - 1) x GPIRT_NGRID doubles, k fastest).
+ * gpirt_sampler_ordinal_get, by name: "cat" (n x m int8), "grid", "log_prior" (P doubles), "index" (m x (C - 1) int32),
+ * "thresholds" (m x (C - 1) doubles), "counts" (m x C int64: observed cells per category), "lp" (m x (C - 1) x W doubles: the last
+ * update's masses by window slot, -inf outside the candidates; W is that update's width, gpirt_ordinal.lp_width -- a
+ * gpirt_sampler_ordinal_width since then does not change how it is read), "window" (m x (C - 1) int32: the last windows' a), "hist", "draws"
+ * (recorded x m x (C - 1)), "cum", "pinned", "failed", "updates" (1 int64 each).
+ *
+ * Refused while ordinal is on, GPIRT_E_ARG with the reason: every entry that evaluates the binary likelihood or reads y (the
+ * summaries' WAIC / pred parts, the PPC and its add-ons, LOO, score and predict, sumscore, equate, groups, the ACF's
+ * log-likelihood series, the whitened draw_ell, both draw_amp updates, draw_scale), draw_beta_centred (it moves the pinned
+ * intercept), gpirt_sampler_set_theta_block, gpirt_sampler_copy_state, gpirt_sampler_set of "y" (its missing cells were checked
+ * against cat) and of "beta" with a non-zero intercept; and gpirt_sampler_ordinal_enable itself after any of
+ * those blocks, under GPIRT_RNG_RSTREAM, on an item shard, with theta_block in use, with GPIRT_LL_EXACT=1 (the ordinal kernels have
+ * the fast term alone), before gpirt_sampler_init, for n > GPIRT_ORD_MAX_N, and for every bad argument gpirt_ordinal_check names
+ * (it is the argument check alone and touches no device; NULL pointers are not checked).  cat = NULL turns ordinal off and
+ * frees its state; beta and the chain's state stay as they are. */
+#define GPIRT_ORD_MAX_C 8
+#define GPIRT_ORD_MIN_POINTS 9
+#define GPIRT_ORD_MAX_POINTS 1001
+#define GPIRT_ORD_MAX_WIDTH 64
+#define GPIRT_ORD_MAX_N 16384
+typedef struct gpirt_ordinal {
+    int64_t  on;                            /* 0 off, 1 on */
+    int64_t  n, m, categories, points, width;
+    int64_t  calls;                         /* t: gpirt_sampler_draw_thresholds calls over the sampler's life */
+    int64_t  pinned, failed, updates;       /* thresholds with one candidate / a non-finite mass / drawn, since enable */
+    int64_t  planned_draws, recorded, irf_draws;
+    double   hi;
+    double   last_ms;                       /* device time of the last draw_thresholds with gpirt_sampler_enable_timing on, else 0 */
+    int64_t  lp_width;                      /* the W of the last update: the slots per row of "lp" (the enable's W before the first) */
+    int64_t  reserved[3];
+} gpirt_ordinal;
+int gpirt_ordinal_check(const int8_t* cat, const double* y, int64_t n, int64_t m, int C, double hi, int P, const double* log_prior,
+                        const int32_t* K0, int W, const gpirt_options* opts);
+int gpirt_ordinal_grid(double hi, int P, double* out);
+int gpirt_sampler_ordinal_enable(gpirt_sampler_t s, const int8_t* cat, int C, double hi, int P, const double* log_prior,
+                                 const int32_t* K0, int W, int64_t planned_draws);
+int gpirt_sampler_draw_thresholds(gpirt_sampler_t s);
+int gpirt_sampler_ordinal_width(gpirt_sampler_t s, int W);
+int gpirt_sampler_ordinal_record(gpirt_sampler_t s);
+int gpirt_sampler_ordinal_accumulate_irf(gpirt_sampler_t s);
+int gpirt_sampler_ordinal_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ordinal_stats(gpirt_sampler_t s, gpirt_ordinal* out);
 
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
