@@ -805,6 +805,8 @@ SIGNATURES = {
     "gpirt_sampler_dense_factor_count": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_dense_factor": (_i32, [_vp]),
     "gpirt_sampler_factor_lr_parts": (_i32, [_vp, _vp, _i64]),
+    "gpirt_sampler_factor_lr_width": (_i32, [_vp, C.POINTER(_i32)]),
+    "gpirt_sampler_factor_lr_blocks": (_i32, [_vp, _vp, _i64]),
     "gpirt_sampler_copy_state": (_i32, [_vp, _vp]),
     "gpirt_sampler_accumulate_irf": (_i32, [_vp]),
     "gpirt_sampler_iteration": (_i32, [_vp, C.POINTER(_i32)]),

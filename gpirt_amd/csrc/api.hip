@@ -42,6 +42,7 @@ const Config& env_config()
         d.fstar_free = env_value("GPIRT_FSTAR_FREE", d.fstar_free);
         d.factor_lr = env_value("GPIRT_FACTOR_LR", d.factor_lr);
         d.flr_fuse = env_value("GPIRT_FLR_FUSE", d.flr_fuse);
+        d.flr_narrow = env_value("GPIRT_FLR_NARROW", d.flr_narrow);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -167,7 +168,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 139; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 140; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -248,6 +249,9 @@ int gpirt_version(void) { return 139; }   // 101: gpirt_options names kernel_fp3
                                             //      (ordinal.hip, sampler.hip: GPIRT_ST_ORD, gpirt_ordinal_check, gpirt_ordinal_grid,
                                             //      gpirt_sampler_ordinal_enable / _width / _record / _accumulate_irf / _get / _stats,
                                             //      gpirt_sampler_draw_thresholds); stage API only
+                                            // 140: the structured factor's parts as narrow as draw_f's product reads them, part / 64 rounds instead
+                                            //      of eight (factor_lr.hip: GPIRT_FLR_NARROW, gpirt_sampler_factor_lr_width,
+                                            //      gpirt_sampler_factor_lr_blocks); the parts and node rows change in rounding only
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -382,6 +386,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_FSTAR_FREE", &h->cfg.fstar_free, false },
         { "GPIRT_FACTOR_LR", &h->cfg.factor_lr, false },
         { "GPIRT_FLR_FUSE", &h->cfg.flr_fuse, false },
+        { "GPIRT_FLR_NARROW", &h->cfg.flr_narrow, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }

@@ -82,7 +82,7 @@ struct Config {
     int  rs_lr = 1;               // GPIRT_RS_LR: 2 = the predictor's every pass reads all of L as floats (no structured form, rs_lr.hip)
     int  nu_lr = 1;               // GPIRT_NU_LR: draw_f's nu = L z from L's diagonal parts and the 64 node rows (nu_lr.hip): 1 = from n = 2048 on,
                                   //   2 = always the dense product, 3 = at every eligible n
-    int  nu_sub = 0;              // GPIRT_NU_SUB: the part width of that product, 64, 128, 256 or 512 (the factor's parts stay 512 wide; env_config()
+    int  nu_sub = 0;              // GPIRT_NU_SUB: the part width of that product, 64, 128, 256 or 512 (the factor's parts follow it: GPIRT_FLR_NARROW; env_config()
                                   //   fills in kernels.h's NU_LR_SUB); anything else is an argument error
     int  fstar_free = 1;          // GPIRT_FSTAR_FREE: the rank-64 draw_fstar's C = S^-1 U from theta alone (fstar_free.hip): 1 = from n = 2048 on
                                   //   where the sampler is eligible, 2 = always the solve through L, 3 = at every eligible n
@@ -90,6 +90,8 @@ struct Config {
                                   //   from theta (factor_lr.hip): 1 = from n = 2048 on where it is eligible, 2 = always the dense factor, 3 = at every eligible n
     int  flr_fuse = 1;            // GPIRT_FLR_FUSE: the structured factor's rounds (factor_lr.hip): 1 = one launch per 64-column round (each round's update
                                   //   rides in the next round's launch), 2 = a panel launch and two product launches per round, the diagonal placed at the end
+    int  flr_narrow = 1;          // GPIRT_FLR_NARROW: the structured factor's part width: 1 = from n = 2048 on the parts are as wide as draw_f's product
+                                  //   reads them (GPIRT_NU_SUB), 2 = always 512 wide, 3 = GPIRT_NU_SUB wide at every eligible n
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)
     int  guard_verbose = 0;       // GPIRT_GUARD_VERBOSE: 1 = a hang-guard fallback prints the guard record to stderr
 };

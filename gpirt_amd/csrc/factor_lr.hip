@@ -21,6 +21,11 @@
 //
 // Two schedules of the same sums (GPIRT_FLR_FUSE): 1, the default, one launch per round
 // (flr_round_kernel: 12 launches at n = 8192); 2, a panel launch and two product launches per round (29 launches).
+//
+// The identities hold for any cut into multiples of 64, and the steady iteration reads no more of L than diagonal parts as
+// wide as draw_f's product takes them (GPIRT_NU_SUB, 128 by default): FactorLrArgs::part = 64, 128, 256 or 512 is the width
+// of the parts built here (GPIRT_FLR_NARROW), part / 64 rounds instead of eight -- 7 launches at
+// n = 8192 and part = 128.  At 512 every launch is what it was; below it the prefix over the Grams is flr_scan2_kernel's.
 #include "common.h"
 #include "kernels.h"
 #include "potf2.h"
@@ -31,8 +36,9 @@ namespace gpirt {
 namespace {
 
 constexpr int NR = NU_LR_RANK;
-constexpr int64_t PC = NU_LR_PART;
-constexpr int NBLK = (int)(PC / 64);                 // 64-column rounds of a full part
+// The part width PC and NBLK = PC / 64, the 64-column rounds of a full part, are launch arguments (`part`: 64, 128, 256 or
+// NU_LR_PART = 512, FactorLrArgs::part): whoever reads no more of L than w-wide diagonal parts is given w-wide parts,
+// part / 64 rounds instead of eight.
 static_assert(NR == 64, "potf2.h and solve64.h are written for 64 x 64");
 
 // G[0] <- 0, G[q] <- g[1] + ... + g[q] for the Grams g[q] found in slot q (q = 1 .. nslot - 1), in slot order, element by
@@ -46,16 +52,57 @@ __global__ __launch_bounds__(256) void flr_scan_kernel(double* __restrict__ G, i
     for (int q = 1; q < nslot; ++q) { run += G[(int64_t)q * NR * NR + e]; G[(int64_t)q * NR * NR + e] = run; }
 }
 
+// The same prefix for parts narrower than 512 columns, where the slots are many (n / part: 64 at n = 8192 and part = 128) and a
+// serial sum per element is a chain of that many dependent adds behind as many loads.  Two levels in a fixed order, no atomics:
+// with c = 512 / part slots a group (the parts of one 512-column stretch), g[p] the Gram of part p (found in slot p + 1),
+//       H_j = g[j c] + ... + g[j c + c - 1]          (from zero, ascending: the Gram of stretch j)
+//       G_P = (H_0 + ... + H_{J-1}) + (g[J c] + ... + g[P - 1]),   J = P / c        (both sums from zero, ascending)
+// A work-group holds 256 / ng elements of all groups, thread (element, group): it loads its group's c Grams (all loads in
+// flight together), leaves H_j in LDS, and behind the barrier -- every slot has been read by then: slot j c + c belongs to the
+// next group's thread -- adds the groups in front and writes its c slots.  ng: the groups' count rounded up to a power of two.
+constexpr int FLR_SCAN_THREADS = 256;
+constexpr int FLR_SCAN_CMAX = NU_LR_PART / NU_LR_SUB_MIN;        // 8 slots a group at the narrowest width
+__global__ __launch_bounds__(FLR_SCAN_THREADS) void flr_scan2_kernel(double* __restrict__ G, int nslot, int c, int ng)
+{
+    extern __shared__ double sH[];                               // [group][element of the work-group]
+    const int el_per = FLR_SCAN_THREADS / ng;
+    const int el = threadIdx.x % el_per, j = threadIdx.x / el_per;
+    const int e = blockIdx.x * el_per + el;                      // (NR * NR is a multiple of el_per: no element is left over)
+    double g[FLR_SCAN_CMAX];
+    double h = 0.0;
+#pragma unroll
+    for (int r = 0; r < FLR_SCAN_CMAX; ++r) {
+        const int slot = j * c + r + 1;                          // g[j c + r]
+        g[r] = (r < c && slot < nslot) ? G[(int64_t)slot * NR * NR + e] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < FLR_SCAN_CMAX; ++r)
+        if (r < c) h += g[r];
+    sH[j * el_per + el] = h;
+    __syncthreads();
+    double run = 0.0;
+    for (int jj = 0; jj < j; ++jj) run += sH[jj * el_per + el];
+    double tail = 0.0;
+#pragma unroll
+    for (int r = 0; r < FLR_SCAN_CMAX; ++r) {
+        const int slot = j * c + r;                              // G_P for P = j c + r
+        if (r < c && slot < nslot) G[(int64_t)slot * NR * NR + e] = run + tail;
+        tail += g[r];
+    }
+}
+
 // Round k of the parts' factorisation, all parts side by side.  Work-group (rb, q) belongs to part q, whose pivot block D is
-// the 64 x 64 block at column c0 = 512 q + 64 k of L's diagonal.  EVERY work-group of the part factors D itself, in LDS
+// the 64 x 64 block at column c0 = part q + 64 k of L's diagonal.  EVERY work-group of the part factors D itself, in LDS
 // (potf2.h; eps is added to its diagonal here: the product in front wrote eps X^T X) -- nothing passes between work-groups,
 // and nobody writes D in this launch -- and then solves its own 64 rows B <- B D^-T with the substitution core of the
 // factorisation's panels (solve64.h, 16 rows a wavefront):  rb == 0: the border, the 64 rows of X at the pivot's columns (and
 // it keeps D's factor in Dw, which flr_diag_kernel puts in place behind the last round);  rb >= 1: rows c0 + 64 rb of the part.
 // A pivot that is not positive raises *err (the sampler's numeric error word).
 __global__ __launch_bounds__(256) void flr_panel_kernel(double* __restrict__ L, int64_t ldl, int64_t n, double* __restrict__ X,
-                                                        double* __restrict__ Dw, int k, double eps, int* __restrict__ err)
+                                                        double* __restrict__ Dw, int k, double eps, int* __restrict__ err, int part)
 {
+    const int64_t PC = part;
+    const int NBLK = part / 64;
     __shared__ __attribute__((aligned(16))) double sM[NR * S64_LS];
     __shared__ __attribute__((aligned(16))) double sP[2 * 4 * NR];
     __shared__ int sfail, sinfo;
@@ -102,8 +149,10 @@ __global__ __launch_bounds__(256) void flr_panel_kernel(double* __restrict__ L, 
 }
 
 // the pivot blocks' factors from Dw into L's diagonal (the strict upper triangle inside a block: zero)
-__global__ __launch_bounds__(256) void flr_diag_kernel(double* __restrict__ L, int64_t ldl, int64_t n, const double* __restrict__ Dw)
+__global__ __launch_bounds__(256) void flr_diag_kernel(double* __restrict__ L, int64_t ldl, int64_t n, const double* __restrict__ Dw, int part)
 {
+    const int64_t PC = part;
+    const int NBLK = part / 64;
     const int k = (int)blockIdx.x;
     const int64_t c0 = (int64_t)blockIdx.y * PC + 64 * (int64_t)k;
     if (c0 >= n) return;
@@ -228,8 +277,10 @@ __device__ __forceinline__ void flr_axpby(d4 (&acc)[2][2], double alpha, double 
 template <bool FIRST>
 __global__ __launch_bounds__(256) void flr_round_kernel(double* __restrict__ L, int64_t ldl, int64_t n, double* __restrict__ X,
                                                         double* __restrict__ Dw, const double* __restrict__ Xh, const double* __restrict__ V,
-                                                        int k, double eps, int* __restrict__ err)
+                                                        int k, double eps, int* __restrict__ err, int part)
 {
+    const int64_t PC = part;
+    const int NBLK = part / 64;
     extern __shared__ __attribute__((aligned(16))) double flr_lds[];
     __shared__ int sfail, sinfo;
     double* tA = flr_lds;                    // operand image A[k][m]
@@ -408,11 +459,11 @@ __global__ __launch_bounds__(256) void flr_round_kernel(double* __restrict__ L, 
 
 }  // namespace
 
-int64_t factor_lr_parts(int64_t n) { return (n + PC - 1) / PC; }
+int64_t factor_lr_parts(int64_t n, int part) { const int64_t PC = part ? part : NU_LR_PART; return (n + PC - 1) / PC; }
 
 // The diagonal parts into a.L (lower triangles; the strict upper triangle inside a part is zero, nothing below the parts is
-// written) and the node rows into a.Bt.  V: n x 64 (ld n), rewritten with the basis at theta; G, Xh: factor_lr_parts(n) x
-// 64 x 64; X: 64 x n; D: factor_lr_parts(n) x 8 x 64 x 64.  n a multiple of 64; the last part may be shorter than 512.
+// written) and the node rows into a.Bt.  V: n x 64 (ld n), rewritten with the basis at theta; G, Xh: factor_lr_parts(n, part)
+// x 64 x 64; X: 64 x n; D: n / 64 x 64 x 64.  n a multiple of 64; the last part may be shorter than a.part.
 // h (may be null): the handle whose profiler books the syrk-lower launches -- S_PP under class 1, the in-part updates
 // under class 2 (the fused rounds: round 0 under class 1, the rounds behind it under class 2, each with the flops and bytes
 // of the syrk-lower it contains) -- and whose GPIRT_FLR_FUSE picks the schedule (null: the fused rounds).
@@ -421,6 +472,10 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
     const int64_t n = a.n, ldl = a.ldl;
     if (n <= 0) return 0;
     if ((n % 64) != 0) { set_error("factor_lr: n must be a multiple of 64"); return GPIRT_E_ARG; }
+    const int part = a.part ? a.part : NU_LR_PART;
+    if (part != 64 && part != 128 && part != 256 && part != 512) { set_error("factor_lr: the part width must be 64, 128, 256 or 512 (got %d)", a.part); return GPIRT_E_ARG; }
+    const int64_t PC = part;
+    const int NBLK = part / 64;
     const int64_t full = n / PC, rem = n % PC;
     const int parts = (int)(full + (rem ? 1 : 0));
     const int64_t sG = (int64_t)NR * NR, sX = (int64_t)NR * PC, sL = PC * (ldl + 1);
@@ -440,10 +495,23 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
     if (parts > 1)
         GP_TRY(launch_gemm_batched(stream, true, false, TRI_NONE, NR, NR, PC, 1.0, a.V, n, PC, a.V, n, PC, 0.0, a.G + sG, NR, sG, parts - 1));
     const int rounds = full > 0 ? NBLK : (int)(rem / 64);
+    // the prefix over the Grams: parts narrower than 512 take the two-level order of flr_scan2_kernel in both schedules
+    const bool narrow = part < NU_LR_PART;
+    if (narrow) {                                         // (a single part too: slot 0 <- 0, which nobody else writes)
+        const int c = NU_LR_PART / part;
+        const int64_t groups = (parts + c - 1) / c;
+        if (groups > FLR_SCAN_THREADS) { set_error("factor_lr: n = %lld is too large for parts %d wide", (long long)n, part); return GPIRT_E_ARG; }
+        int ng = 1;
+        while (ng < groups) ng *= 2;
+        const int el_per = FLR_SCAN_THREADS / ng;
+        hipLaunchKernelGGL(flr_scan2_kernel, dim3((unsigned)(NR * NR / el_per)), dim3(FLR_SCAN_THREADS), sizeof(double) * FLR_SCAN_THREADS, stream, a.G, parts, c, ng);
+        GP_HIP(hipGetLastError());
+    }
     if (fuse) {
         // One launch per round (flr_round_kernel): the prefix over the Grams rides in the X-hat kernel, X_P, eps X_P^T X_P and
         // each round's update in the round kernels, the diagonal is placed as the rounds go.  The same sums in the same order.
-        GP_TRY(launch_fstar_free_xhat(stream, a.G, a.F, a.eps, a.Xh, parts, a.err, true));
+        // (behind flr_scan2_kernel the slots already hold the prefix: the same kernel without its own sum)
+        GP_TRY(launch_fstar_free_xhat(stream, a.G, a.F, a.eps, a.Xh, parts, a.err, !narrow, nullptr, narrow));
         GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(flr_round_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLR_LDS));
         GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(flr_round_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FLR_LDS));
         for (int k = 0; k < rounds; ++k) {
@@ -460,8 +528,8 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
             }
             ProfPair pp;
             if (h) GP_TRY(prof_pair_begin(h, stream, pp));
-            if (k == 0) hipLaunchKernelGGL(flr_round_kernel<true>, dim3((unsigned)parts, items), dim3(256), FLR_LDS, stream, a.L, ldl, n, a.X, a.D, a.Xh, a.V, k, a.eps, a.err);
-            else        hipLaunchKernelGGL(flr_round_kernel<false>, dim3((unsigned)parts, items), dim3(256), FLR_LDS, stream, a.L, ldl, n, a.X, a.D, a.Xh, a.V, k, a.eps, a.err);
+            if (k == 0) hipLaunchKernelGGL(flr_round_kernel<true>, dim3((unsigned)parts, items), dim3(256), FLR_LDS, stream, a.L, ldl, n, a.X, a.D, a.Xh, a.V, k, a.eps, a.err, part);
+            else        hipLaunchKernelGGL(flr_round_kernel<false>, dim3((unsigned)parts, items), dim3(256), FLR_LDS, stream, a.L, ldl, n, a.X, a.D, a.Xh, a.V, k, a.eps, a.err, part);
             GP_HIP(hipGetLastError());
             if (h) GP_TRY(prof_pair_end(h, stream, pp, k == 0 ? 1 : 2, flops, bytes));
         }
@@ -472,8 +540,10 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
         return 0;
     }
     // GPIRT_FLR_FUSE = 2: a panel launch and two product launches per round (library version 131)
-    hipLaunchKernelGGL(flr_scan_kernel, dim3((unsigned)((NR * NR + 255) / 256)), dim3(256), 0, stream, a.G, parts);
-    GP_HIP(hipGetLastError());
+    if (!narrow) {
+        hipLaunchKernelGGL(flr_scan_kernel, dim3((unsigned)((NR * NR + 255) / 256)), dim3(256), 0, stream, a.G, parts);
+        GP_HIP(hipGetLastError());
+    }
     GP_TRY(launch_fstar_free_xhat(stream, a.G, a.F, a.eps, a.Xh, parts, a.err));
     // X_P = Xh_P V[P]^T, then eps X_P^T X_P into the parts of L (flr_panel_kernel adds eps I)
     if (full > 0) GP_TRY(launch_gemm_batched(stream, false, true, TRI_NONE, NR, PC, NR, 1.0, a.Xh, NR, sG, a.V, n, PC, 0.0, a.X, NR, sX, (int)full));
@@ -483,7 +553,7 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
     // the parts' factorisation with X_P as the border: a round factors the pivot blocks and solves the rows below them, then
     // takes the new columns' products off what lies to their right (the part's trailing triangle, the border's columns)
     for (int k = 0; k < rounds; ++k) {
-        hipLaunchKernelGGL(flr_panel_kernel, dim3((unsigned)(rounds - k), (unsigned)parts), dim3(256), 0, stream, a.L, ldl, n, a.X, a.D, k, a.eps, a.err);
+        hipLaunchKernelGGL(flr_panel_kernel, dim3((unsigned)(rounds - k), (unsigned)parts), dim3(256), 0, stream, a.L, ldl, n, a.X, a.D, k, a.eps, a.err, part);
         GP_HIP(hipGetLastError());
         const int64_t c = 64 * (int64_t)k, c1 = c + 64;
         auto update = [&](int64_t w, int64_t part0, int batch) -> int {
@@ -498,7 +568,7 @@ int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a
         GP_TRY(update(PC, 0, (int)full));
         GP_TRY(update(rem, full, 1));
     }
-    hipLaunchKernelGGL(flr_diag_kernel, dim3((unsigned)rounds, (unsigned)parts), dim3(256), 0, stream, a.L, ldl, n, a.D);
+    hipLaunchKernelGGL(flr_diag_kernel, dim3((unsigned)rounds, (unsigned)parts), dim3(256), 0, stream, a.L, ldl, n, a.D, part);
     GP_HIP(hipGetLastError());
     // Bt[:, P] = eps Xh_P^T (X_P L_PP^-T)
     if (full > 0) GP_TRY(launch_gemm_batched(stream, true, false, TRI_NONE, NR, PC, NR, a.eps, a.Xh, NR, sG, a.X, NR, sX, 0.0, a.Bt, ldl, PC * ldl, (int)full));

@@ -177,7 +177,7 @@ constexpr size_t FX_LDS = sizeof(double) * (3 * FR * FLD + 2 * 4 * FR);
 static_assert(FR * S64_LS <= 2 * FR * FLD, "the staged factor takes the place of Gv and Gv F");
 __device__ __forceinline__ void fstar_free_xhat_body(const double* __restrict__ Gv, const double* __restrict__ F, double eps,
                                                      double* __restrict__ Xh, int* __restrict__ err, const bool prefix,
-                                                     double* __restrict__ Rout = nullptr)
+                                                     double* __restrict__ Rout = nullptr, const bool chain = false)
 {
     extern __shared__ __attribute__((aligned(16))) double ff_lds[];
     __shared__ int sfail, sinfo;
@@ -189,7 +189,7 @@ __device__ __forceinline__ void fstar_free_xhat_body(const double* __restrict__ 
     const int t = threadIdx.x, ti = t & 15, tj = t >> 4;
     const int lane = t & 63, wave = t >> 6, i = lane & 15, g = lane >> 4;
     // (a link of the fused structured factor's chain, 16 work-groups that share their SIMDs with draw_beta's waves: ahead of them at issue)
-    if (prefix) __builtin_amdgcn_s_setprio(3);
+    if (prefix || chain) __builtin_amdgcn_s_setprio(3);
     Xh += (int64_t)blockIdx.x * FR * FR;
     for (int e = t; e < FR * FR; e += 256) {
         const int r = e & (FR - 1), c = e >> 6;
@@ -261,6 +261,14 @@ void fstar_free_xhat_prefix_kernel(const double* __restrict__ Gv, const double* 
     fstar_free_xhat_body(Gv, F, eps, Xh, err, true);
 }
 
+// the prefix form's place on the chain -- its register cap, its priority -- for slots that already hold the prefix (factor_lr.hip's
+// two-level sum for parts narrower than 512)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 5)))
+void fstar_free_xhat_chain_kernel(const double* __restrict__ Gv, const double* __restrict__ F, double eps, double* __restrict__ Xh, int* __restrict__ err)
+{
+    fstar_free_xhat_body(Gv, F, eps, Xh, err, false, nullptr, true);
+}
+
 }  // namespace
 
 // F (64 x 64, column-major) with K(c, c) = F F^T for the handle's kernel at the nodes of nu_lr_nodes: Kcc in long double, a
@@ -330,11 +338,13 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
 }
 
 // Xh[q] = R_q^-1 F^T with R_q R_q^T = F^T Gv[q] F + eps I for `batch` matrices Gv[q] (64 x 64 each, 4096 doubles apart), one
-// work-group per matrix.  prefix: matrix q is the sum of the slots 1 .. q of Gv, formed by its work-group (see the kernel)
+// work-group per matrix.  prefix: matrix q is the sum of the slots 1 .. q of Gv, formed by its work-group (see the kernel);
+// chain: the prefix form's register cap and priority without its sum
 int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err, bool prefix,
-                           double* R)
+                           double* R, bool chain)
 {
     if (batch <= 0) return 0;
+    if (chain && (prefix || R)) { set_error("fstar_free_xhat: the chain form takes the slots as they stand and keeps no R"); return GPIRT_E_ARG; }
     if (R) {
         if (prefix) { set_error("fstar_free_xhat: R is not kept in the prefix form"); return GPIRT_E_ARG; }
         GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fstar_free_xhat_r_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
@@ -342,7 +352,7 @@ int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F
         GP_HIP(hipGetLastError());
         return 0;
     }
-    auto* kernel = prefix ? fstar_free_xhat_prefix_kernel : fstar_free_xhat_kernel;
+    auto* kernel = prefix ? fstar_free_xhat_prefix_kernel : chain ? fstar_free_xhat_chain_kernel : fstar_free_xhat_kernel;
     GP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FX_LDS));
     hipLaunchKernelGGL(kernel, dim3((unsigned)batch), dim3(256), FX_LDS, stream, Gv, F, eps, Xh, err);
     GP_HIP(hipGetLastError());

@@ -370,7 +370,7 @@ int launch_rs_lr_setup(hipStream_t stream, const RsLrSetup& q);
 int launch_rs_lr_apply(hipStream_t stream, const Rs3Args& a);
 // nu_lr.hip: draw_f's nu = L z (item-keyed RNG) from L's diagonal parts and the 64 node rows below the factor
 constexpr int NU_LR_RANK = 64;       // the nodes of cheb_nodes_basis(64)
-constexpr int NU_LR_PART = 512;      // columns per part of the FACTOR (factor_lr.hip, gpirt_sampler_factor_lr_parts)
+constexpr int NU_LR_PART = 512;      // columns per part of the FACTOR at its widest (factor_lr.hip, gpirt_sampler_factor_lr_parts)
 constexpr int NU_LR_SUB = 128;       // columns per part of the PRODUCT (GPIRT_NU_SUB: 64, 128, 256 or 512), measured
 constexpr int NU_LR_SUB_MIN = 64;    // the narrowest width: what the workspace is sized for
 inline bool nu_lr_sub_ok(int w) { return w == 64 || w == 128 || w == 256 || w == 512; }
@@ -395,21 +395,23 @@ int launch_fstar_free(hipStream_t stream, const double* V, int64_t n, const doub
 // Xh[q] = R_q^-1 F^T, R_q R_q^T = F^T Gv[q] F + eps I, for `batch` 64 x 64 matrices Gv[q] (one work-group each); prefix: matrix q
 // is Gv[1] + ... + Gv[q], added by its own work-group in slot order (Gv[0] is not read)
 int launch_fstar_free_xhat(hipStream_t stream, const double* Gv, const double* F, double eps, double* Xh, int batch, int* err,
-                           bool prefix = false, double* R = nullptr);     // R: also R itself, 64 x 64 per matrix (not with prefix)
+                           bool prefix = false, double* R = nullptr,      // R: also R itself, 64 x 64 per matrix (not with prefix)
+                           bool chain = false);                           // chain: the prefix form's kernel without its sum
 // factor_lr.hip: L's diagonal parts and the 64 node rows from theta alone -- nothing below the parts is computed
 struct FactorLrArgs {
     const double* theta; int64_t n;
     const double *nodes, *wts;        // nu_lr_nodes on the device
     double* V;                        // n x 64 (leading dimension n): rewritten with the basis at theta
     const double* F; double eps;      // fstar_free_factor's F on the device; the jitter
-    double *G, *Xh;                   // factor_lr_parts(n) x 64 x 64 each: the Grams in front of the parts; R_P^-1 F^T
+    double *G, *Xh;                   // factor_lr_parts(n, part) x 64 x 64 each: the Grams in front of the parts; R_P^-1 F^T
     double* X;                        // 64 x n: the parts' borders
-    double* D;                        // factor_lr_parts(n) x 8 x 64 x 64: the pivot blocks' factors until the last round is through
+    double* D;                        // n / 64 x 64 x 64: the pivot blocks' factors until the last round is through
     double* L; int64_t ldl;           // the factor's buffer: the diagonal parts are written
     double* Bt;                       // its node rows (64 x n, leading dimension ldl): written
     int* err;                         // the sampler's numeric error word
+    int part;                         // the parts' width: 64, 128, 256 or 512 (0: NU_LR_PART); anything else is an argument error
 };
-int64_t factor_lr_parts(int64_t n);
+int64_t factor_lr_parts(int64_t n, int part = 0);
 int launch_factor_lr(gpirt_handle_t h, hipStream_t stream, const FactorLrArgs& a);
 int launch_rs3p_products(hipStream_t stream, const Rs3Args& a);
 int launch_rs3p_decide(hipStream_t stream, const Rs3Args& a);

@@ -7,8 +7,8 @@
 //       K(theta_i, .) = sum_k V[i][k] K(c_k, .)      =>      L[i, P] = V[i, :] Bt[:, P],    Bt = K(c, theta) L^-T   (64 x n).
 // Bt is what the bordered factorisation leaves in the 64 node rows below L (sampler.hip: node_off), for free.  The identity
 // holds for every row block strictly below every column block, so the n columns may be cut into parts P of any multiple of
-// 64: w = 64, 128, 256 or 512 (GPIRT_NU_SUB, default NU_LR_SUB; the FACTOR's parts stay NU_LR_PART = 512 wide, and the
-// w-wide diagonal blocks lie inside them):
+// 64: w = 64, 128, 256 or 512 (GPIRT_NU_SUB, default NU_LR_SUB; the structured FACTOR's parts are at least as wide, up to
+// NU_LR_PART = 512, and the w-wide diagonal blocks lie inside them):
 //       nu[P, :] = L[P, P] Z[P, :]  +  V[P, :] sum_{Q < P} Bt[:, Q] Z[Q, :]
 // -- the dense w x w lower-triangular diagonal parts and two rank-64 products, n m (w + 256) flop: 3.2e9 at 8192 x 1024 and
 // w = 128 (6.4e9 at 512) instead of n^2 m = 6.9e10.  Four launches:

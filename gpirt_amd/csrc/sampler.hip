@@ -242,6 +242,7 @@ struct gpirt_sampler_s {
     // workspaces of launch_factor_lr; ev_flr: recorded where the structured factor starts (the side work waits for it)
     double *theta_L = nullptr, *flrG = nullptr, *flrXh = nullptr, *flrX = nullptr, *flrD = nullptr;
     bool L_structured = false;
+    int L_part_width = 0;                 // the width of the diagonal parts a structured L holds (factor_width(): 0 for a dense L)
     hipEvent_t ev_flr = nullptr;
     int64_t factor_lr_count = 0, dense_factor_count = 0;      // structured factors / dense factorisations this sampler enqueued
     // the N(0,1) draws of the NEXT draw_f depend on (seed, iteration, item, index) only: filled on the sampler's own stream
@@ -637,6 +638,7 @@ int report_degenerate_theta(gpirt_sampler_s* s, int count);
 int rebuild_rows(gpirt_sampler_s* s);
 int beta_sync(gpirt_sampler_s* s);
 int ensure_dense_factor(gpirt_sampler_s* s);
+int ensure_factor_width(gpirt_sampler_s* s, int need);
 
 // Z may still be being filled on the sampler's own stream (do_factor's prefill of the NEXT draw_f's normals): whoever reads or
 // rewrites Z, or changes the iteration the prefill was keyed by, joins it first and drops it
@@ -665,6 +667,7 @@ int do_draw_f(gpirt_sampler_s* s)
                            s->nu_kern_ok && !s->opt.kernel_fp32 && s->theta_ok && !s->theta_alone;
         if (!nu_lr) GP_TRY(ensure_dense_factor(s));               // (the dense product reads all of L)
         if (nu_lr) GP_TRY(rebuild_rows(s));
+        if (nu_lr) GP_TRY(ensure_factor_width(s, h->cfg.nu_sub));  // (GPIRT_NU_SUB raised behind a factor in narrower parts)
         const bool prep = s->haux && s->kr > 0 && s->fstar_rows && s->rows_valid && !s->prep_valid;
         // The side work (what the low-rank draw_fstar needs from L alone: the last range of block inverses and the
         // 64-column transposed solve, ~0.6 ms of small DEPENDENT launches) starts at once, beside the fill and the product
@@ -1253,6 +1256,42 @@ int rebuild_rows(gpirt_sampler_s* s)
 // block inverses, the Z prefill, a held-back draw_beta).  Whoever calls it has made sure nothing still reads the old factor.
 // With factor_lr_ok (not for gpirt_sampler_init, whose f = L z is the dense product): the diagonal parts and the node rows
 // alone, from theta (factor_lr.hip) -- theta is kept in theta_L for whoever asks for the rest of L later.
+// the structured factor of K(theta, theta) in parts `part` wide on the main stream: the diagonal parts into L, the node rows below
+int launch_structured_factor(gpirt_sampler_s* s, const double* theta, int part)
+{
+    FactorLrArgs a{};
+    a.theta = theta; a.n = s->n; a.nodes = s->nu_nodes; a.wts = s->nu_wts; a.V = s->nuV; a.F = s->ffF; a.eps = GPIRT_JITTER;
+    a.G = s->flrG; a.Xh = s->flrXh; a.X = s->flrX; a.D = s->flrD; a.L = s->L; a.ldl = s->ldl; a.Bt = s->L + s->n + s->node_off; a.err = s->flags;
+    a.part = part;
+    GP_TRY(launch_factor_lr(s->h, s->h->stream, a));
+    s->L_part_width = part;
+    return 0;
+}
+
+// The width of the structured factor's parts: nobody in the steady iteration reads more of L than the diagonal parts of draw_f's
+// product, GPIRT_NU_SUB wide, so that is how wide they are factored, part / 64 rounds instead of eight -- from n = 2048 on
+// (GPIRT_FLR_NARROW=3: at every eligible n; =2: always 512).  Whoever reads wider parts later asks ensure_factor_width first.
+int factor_lr_width(const gpirt_sampler_s* s)
+{
+    const Config& c = s->h->cfg;
+    return (c.flr_narrow != 2 && (c.flr_narrow == 3 || s->n >= 2048)) ? c.nu_sub : NU_LR_PART;
+}
+
+// the width of the diagonal parts L holds; 0: L is dense
+int factor_width(const gpirt_sampler_s* s) { return s->L_structured ? s->L_part_width : 0; }
+
+// Whoever reads diagonal parts `need` wide calls this first: a structured factor in narrower parts is replaced by the structured
+// factor of K(theta_L, theta_L) in 512-wide parts, on the main stream behind whatever still reads the node rows or the basis,
+// and everything derived from the factor is dropped.  Counted neither as a structured nor as a dense factorisation.
+int ensure_factor_width(gpirt_sampler_s* s, int need)
+{
+    if (!s->L_structured || s->L_part_width >= need) return 0;
+    hipStream_t st = s->h->stream;
+    if (s->prep_pending) { GP_HIP(hipStreamWaitEvent(st, s->ev_prep, 0)); s->prep_pending = false; }
+    invalidate_factor_products(s);
+    return launch_structured_factor(s, s->theta_L, NU_LR_PART);
+}
+
 int factor_core(gpirt_sampler_s* s)
 {
     hipStream_t st = s->h->stream;
@@ -1261,10 +1300,7 @@ int factor_core(gpirt_sampler_s* s)
         if (s->ev_flr) GP_HIP(hipEventRecord(s->ev_flr, st));          // (the side work of do_factor starts here)
         if (!s->sticky_info) GP_HIP(hipMemsetAsync(s->h->d_info, 0, sizeof(int), st));
         GP_HIP(hipMemcpyAsync(s->theta_L, s->theta, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, st));
-        FactorLrArgs a{};
-        a.theta = s->theta; a.n = s->n; a.nodes = s->nu_nodes; a.wts = s->nu_wts; a.V = s->nuV; a.F = s->ffF; a.eps = GPIRT_JITTER;
-        a.G = s->flrG; a.Xh = s->flrXh; a.X = s->flrX; a.D = s->flrD; a.L = s->L; a.ldl = s->ldl; a.Bt = s->L + s->n + s->node_off; a.err = s->flags;
-        GP_TRY(launch_factor_lr(s->h, st, a));
+        GP_TRY(launch_structured_factor(s, s->theta, factor_lr_width(s)));
         s->L_structured = true;
         s->rows_valid = true;
         s->theta_alone = false;
@@ -1960,8 +1996,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
         if (!stream_mode(s) && s->kr == NU_LR_RANK && s->fstar_rows) {
             GP_A(s->ffF, FSTAR_FREE_RANK * FSTAR_FREE_RANK); GP_A(s->ffW, 2 * FSTAR_FREE_RANK * FSTAR_FREE_RANK);
             if (s->opt.factor_structured) {       // (the structured factor's: only where the rank-64 chain from theta can run)
-                const int64_t fp = factor_lr_parts(n) * NU_LR_RANK * NU_LR_RANK;
-                GP_A(s->theta_L, n); GP_A(s->flrG, fp); GP_A(s->flrXh, fp); GP_A(s->flrX, NU_LR_RANK * n); GP_A(s->flrD, fp * (NU_LR_PART / 64));
+                // one 64 x 64 slot per part of the narrowest width (G, Xh) and per pivot block (D: NU_LR_SUB_MIN = 64 columns each)
+                const int64_t fp = factor_lr_parts(n, NU_LR_SUB_MIN) * NU_LR_RANK * NU_LR_RANK;
+                GP_A(s->theta_L, n); GP_A(s->flrG, fp); GP_A(s->flrXh, fp); GP_A(s->flrX, NU_LR_RANK * n);
+                GP_A(s->flrD, factor_lr_parts(n) * (NU_LR_PART / 64) * NU_LR_RANK * NU_LR_RANK);
             }
         }
     }
@@ -4743,10 +4781,37 @@ int gpirt_sampler_factor_lr_parts(gpirt_sampler_t s, double* h_out, int64_t coun
 {
     GP_ARG(s && h_out && count == (int64_t)NU_LR_PART * s->n);
     GP_TRY(aux_join(s));
+    GP_TRY(ensure_factor_width(s, NU_LR_PART));       // (behind a factor in narrower parts: the structured factor at 512 first)
     memset(h_out, 0, sizeof(double) * (size_t)count);
     for (int64_t p = 0; p < s->n; p += NU_LR_PART) {
         const int64_t w = s->n - p < NU_LR_PART ? s->n - p : NU_LR_PART;
         GP_HIP(hipMemcpy2DAsync(h_out + p * NU_LR_PART, (size_t)NU_LR_PART * 8, s->L + p * (s->ldl + 1), (size_t)s->ldl * 8, (size_t)w * 8, (size_t)w,
+                                hipMemcpyDeviceToHost, s->h->stream));
+    }
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    return 0;
+}
+
+// the width of the diagonal parts a structured L holds (0: L is dense), and those parts as they lie: part p, w x w with w the
+// width (the last may be shorter), at h_out + p * w * w with leading dimension w; count = width * n.  Nothing is factored for it.
+int gpirt_sampler_factor_lr_width(gpirt_sampler_t s, int* width)
+{
+    GP_ARG(s && width);
+    *width = factor_width(s);
+    return 0;
+}
+
+int gpirt_sampler_factor_lr_blocks(gpirt_sampler_t s, double* h_out, int64_t count)
+{
+    GP_ARG(s && h_out);
+    const int64_t W = factor_width(s);
+    if (W == 0) { set_error("factor_lr_blocks: L holds the dense factor, not diagonal parts"); return GPIRT_E_ARG; }
+    GP_ARG(count == W * s->n);
+    GP_TRY(aux_join(s));
+    memset(h_out, 0, sizeof(double) * (size_t)count);
+    for (int64_t p = 0; p < s->n; p += W) {
+        const int64_t w = s->n - p < W ? s->n - p : W;
+        GP_HIP(hipMemcpy2DAsync(h_out + p * W, (size_t)W * 8, s->L + p * (s->ldl + 1), (size_t)s->ldl * 8, (size_t)w * 8, (size_t)w,
                                 hipMemcpyDeviceToHost, s->h->stream));
     }
     GP_HIP(hipStreamSynchronize(s->h->stream));

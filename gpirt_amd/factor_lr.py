@@ -14,6 +14,11 @@ the basis rows in front of it (G_0 = 0)
 
 (Woodbury on the leading block: Kcc - sum_{Q < P} Bt_Q Bt_Q^T = eps F (H_P + eps I)^-1 F^T.)  The parts depend on each other
 through the running Gram alone.  The triangle of L below the parts is never formed.
+
+All of it holds for any cut into multiples of 64: `part` is 512 or, since library version 140, the width draw_f's product
+reads the parts at (GPIRT_FLR_NARROW; tests/test_factor_lr_narrow_cpu.py).  Below 512 the device adds
+the running Gram in two levels (whole 512-column stretches, then the parts inside the last one) where this statement adds part
+by part: the same sum to rounding.
 """
 from __future__ import annotations
 

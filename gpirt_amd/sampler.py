@@ -813,6 +813,20 @@ class Sampler:
         check(self.lib.gpirt_sampler_factor_lr_parts(self._s, C.c_void_p(out.ctypes.data), out.size))
         return [out[p:p + 512, :min(512, self.n - p)].T.copy() for p in range(0, self.n, 512)]
 
+    @property
+    def factor_lr_width(self) -> int:
+        """the width of the diagonal parts a structured L holds (GPIRT_FLR_NARROW); 0: L is dense"""
+        r = C.c_int()
+        check(self.lib.gpirt_sampler_factor_lr_width(self._s, C.byref(r)))
+        return int(r.value)
+
+    def factor_lr_blocks(self) -> list:
+        """L's diagonal parts at the width it holds them, in part order (w x w arrays), as they lie: nothing is factored for it"""
+        W = self.factor_lr_width
+        out = np.empty((self.n, max(W, 1)), dtype=np.float64)
+        check(self.lib.gpirt_sampler_factor_lr_blocks(self._s, C.c_void_p(out.ctypes.data), self.n * W))
+        return [out[p:p + W, :min(W, self.n - p)].T.copy() for p in range(0, self.n, W)]
+
     def nu_lr_rows(self) -> np.ndarray:
         """the 64 node rows below the factor as they stand, 64 x n"""
         out = np.empty((64, self.n), order="F")

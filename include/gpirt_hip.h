@@ -2996,11 +2996,22 @@ int gpirt_sampler_fstar_free_draws(gpirt_sampler_t s, int64_t* draws);
  * column j holding L[p + i, j], i = 0 .. w - 1, for its part [p, p + w) (zero behind a shorter last part); count = 512 n.
  * Library version 132: the structured factor runs one launch per 64-column round (12 launches at n = 8192 instead of 29;
  * DESIGN.md section 40).  The same sums in the same order: parts and rows are bit for bit those of version 131.
- * GPIRT_FLR_FUSE (gpirt_config_set): 1 these launches (the default), 2 the launches of version 131.  No change to this interface. */
+ * GPIRT_FLR_FUSE (gpirt_config_set): 1 these launches (the default), 2 the launches of version 131.  No change to this interface.
+ * Library version 140: draw_f's product reads diagonal parts GPIRT_NU_SUB wide and nothing else reads the parts, so the
+ * structured factor builds parts of that width, width / 64 rounds instead of eight (the identities above
+ * hold for any cut into multiples of 64).  GPIRT_FLR_NARROW (gpirt_config_set): 1 this from n = 2048 on (the default), 2 always
+ * 512-wide parts (version 139, bit for bit), 3 at every eligible n.  Parts and node rows change in rounding only.  Whoever reads
+ * wider parts than L holds -- draw_f after GPIRT_NU_SUB was raised on a live sampler, gpirt_sampler_factor_lr_parts -- first
+ * replaces the factor by the structured factor of K(theta_L, theta_L) in 512-wide parts; that counts in neither counter.
+ * gpirt_sampler_factor_lr_width: the width of the parts L holds, 0 for a dense L;
+ * gpirt_sampler_factor_lr_blocks: those parts as they lie, nothing factored for it: width x n column-major, column j holding
+ * L[p + i, j], i = 0 .. w - 1, for its part [p, p + w) (zero behind a shorter last part); count = width n; GPIRT_E_ARG when L is dense. */
 int gpirt_sampler_factor_lr_count(gpirt_sampler_t s, int64_t* count);
 int gpirt_sampler_dense_factor_count(gpirt_sampler_t s, int64_t* count);
 int gpirt_sampler_dense_factor(gpirt_sampler_t s);
 int gpirt_sampler_factor_lr_parts(gpirt_sampler_t s, double* h_out, int64_t count);
+int gpirt_sampler_factor_lr_width(gpirt_sampler_t s, int* width);
+int gpirt_sampler_factor_lr_blocks(gpirt_sampler_t s, double* h_out, int64_t count);
 /* dst's chain state := src's (theta, f, beta, mu, mu_star, fstar, L, iteration counter); same handle, same n and m.  The kernel
  * is not part of the state: refused (GPIRT_E_ARG) when the two samplers' kernels differ, or while the length-scale update
  * (gpirt_sampler_ell_enable) is on for either -- its index and tables are not copied. */
