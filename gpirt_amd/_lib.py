@@ -654,6 +654,7 @@ SIGNATURES = {
     "gpirt_draw_fstar": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp]),
     "gpirt_draw_theta": (_i32, [_vp, _vp, _vp, _i64, _i64, _u64, _u32, _i32, _vp, _vp]),
     "gpirt_draw_beta": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _u32]),
+    "gpirt_draw_beta_paths": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _u32, _vp]),
     "gpirt_item_uniforms": (_i32, [_vp, _u64, _u32, _u32, _u32, _i64, _i64, _vp]),
     "gpirt_item_normals": (_i32, [_vp, _u64, _u32, _u32, _u32, _i64, _i64, _vp]),
     "gpirt_rstream_create": (_i32, [C.POINTER(_vp), _u32]),

@@ -43,6 +43,8 @@ const Config& env_config()
         d.factor_lr = env_value("GPIRT_FACTOR_LR", d.factor_lr);
         d.flr_fuse = env_value("GPIRT_FLR_FUSE", d.flr_fuse);
         d.flr_narrow = env_value("GPIRT_FLR_NARROW", d.flr_narrow);
+        d.beta_screen = env_value("GPIRT_BETA_SCREEN", d.beta_screen);
+        d.zfill_compact = env_value("GPIRT_ZFILL_COMPACT", d.zfill_compact);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -168,7 +170,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 140; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 141; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -387,6 +389,8 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_FACTOR_LR", &h->cfg.factor_lr, false },
         { "GPIRT_FLR_FUSE", &h->cfg.flr_fuse, false },
         { "GPIRT_FLR_NARROW", &h->cfg.flr_narrow, false },
+        { "GPIRT_BETA_SCREEN", &h->cfg.beta_screen, false },
+        { "GPIRT_ZFILL_COMPACT", &h->cfg.zfill_compact, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }
@@ -740,7 +744,7 @@ int gpirt_item_normals(gpirt_handle_t h, uint64_t seed, uint32_t iter, uint32_t 
                        uint32_t item0, int64_t n_items, int64_t n_index, double* d_out)
 {
     GP_ARG(h && d_out && n_items >= 0 && n_index >= 0);
-    return launch_item_uniforms(h->stream, seed, iter, stage, item0, n_items, n_index, d_out, true);
+    return launch_item_uniforms(h->stream, seed, iter, stage, item0, n_items, n_index, d_out, true, h->cfg.zfill_compact == 1);
 }
 
 int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double* d_L, int64_t ldl,
@@ -760,7 +764,7 @@ int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double*
     GP_HIP(hipMemcpyAsync(h->h_info, err + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     GP_HIP(hipStreamSynchronize(h->stream));
     if (*h->h_info != 0) { set_error("draw_f: y must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
-    GP_TRY(launch_item_uniforms(h->stream, seed, iter, GPIRT_ST_F_Z, 0, m, n, Z, true));
+    GP_TRY(launch_item_uniforms(h->stream, seed, iter, GPIRT_ST_F_Z, 0, m, n, Z, true, h->cfg.zfill_compact == 1));
     GP_TRY(launch_gemm(h, h->stream, false, false, TRI_A_LOWER, n, m, n, 1.0, d_L, ldl, Z, n, 0.0, NU, n));
     EssArgs a{};
     a.f = d_f; a.nu = NU; a.y = d_y; a.mu = d_mu; a.n = n; a.m = m; a.k_out = d_k_out; a.err = err;
@@ -889,16 +893,42 @@ int gpirt_debug_theta_clock(gpirt_handle_t h, const double* d_y, const double* d
     return 0;
 }
 
-int gpirt_draw_beta(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
-                    const double* d_f, const double* d_pm, const double* d_ps, const double* d_step,
-                    int64_t n, int64_t m, uint64_t seed, uint32_t iter)
+// draw_beta for callers outside a sampler.  Nobody has checked this y: the register kernel (GPIRT_BETA_SCREEN=1) folds it into
+// two bit masks and is only taken when every entry is +1, -1 or NaN; anything else goes to draw_beta_kernel, which multiplies.
+static int draw_beta_op(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
+                        const double* d_f, const double* d_pm, const double* d_ps, const double* d_step,
+                        int64_t n, int64_t m, uint64_t seed, uint32_t iter, int* d_path)
 {
     GP_ARG(h && d_beta && d_theta && d_y && d_f && d_pm && d_ps && d_step && n >= 0 && m >= 0);
     BetaArgs a{};
     a.beta = d_beta; a.theta = d_theta; a.y = d_y; a.f = d_f; a.pm = d_pm; a.ps = d_ps; a.step = d_step;
     a.n = n; a.m = m; a.N = GPIRT_NGRID; a.mu = nullptr; a.mu_star = nullptr;
-    a.seed = seed; a.iter = iter; a.item0 = 0; a.U = nullptr;
+    a.seed = seed; a.iter = iter; a.item0 = 0; a.U = nullptr; a.path = d_path;
+    if (h->cfg.beta_screen == 1 && n <= 8192 && n * m > 0) {
+        GP_TRY(ensure_work(h, 8 * sizeof(double)));
+        int* bad = reinterpret_cast<int*>(h->d_work);
+        GP_HIP(hipMemsetAsync(bad, 0, sizeof(int), h->stream));
+        GP_TRY(launch_check_y(h->stream, d_y, n * m, bad));
+        GP_HIP(hipMemcpyAsync(h->h_info, bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        GP_HIP(hipStreamSynchronize(h->stream));
+        a.screen = *h->h_info == 0;
+    }
     return launch_draw_beta(h->stream, a);
+}
+
+int gpirt_draw_beta(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
+                    const double* d_f, const double* d_pm, const double* d_ps, const double* d_step,
+                    int64_t n, int64_t m, uint64_t seed, uint32_t iter)
+{
+    return draw_beta_op(h, d_beta, d_theta, d_y, d_f, d_pm, d_ps, d_step, n, m, seed, iter, nullptr);
+}
+
+int gpirt_draw_beta_paths(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
+                          const double* d_f, const double* d_pm, const double* d_ps, const double* d_step,
+                          int64_t n, int64_t m, uint64_t seed, uint32_t iter, int* d_path)
+{
+    GP_ARG(d_path != nullptr);
+    return draw_beta_op(h, d_beta, d_theta, d_y, d_f, d_pm, d_ps, d_step, n, m, seed, iter, d_path);
 }
 
 int gpirt_prof_enable(gpirt_handle_t h, int on)

@@ -92,6 +92,10 @@ struct Config {
                                   //   rides in the next round's launch), 2 = a panel launch and two product launches per round, the diagonal placed at the end
     int  flr_narrow = 1;          // GPIRT_FLR_NARROW: the structured factor's part width: 1 = from n = 2048 on the parts are as wide as draw_f's product
                                   //   reads them (GPIRT_NU_SUB), 2 = always 512 wide, 3 = GPIRT_NU_SUB wide at every eligible n
+    int  beta_screen = 1;         // GPIRT_BETA_SCREEN: 1 = draw_beta from registers, its accept tests decided by the single-precision screen where
+                                  //   that is safe (stages.hip draw_beta_reg_kernel; item RNG, n <= 8192), 2 = always draw_beta_kernel
+    int  zfill_compact = 1;       // GPIRT_ZFILL_COMPACT: 1 = the normal fills evaluate AS241's tail branch on a compacted list (rng_ess.hip
+                                  //   item_fill_normal_kernel), 2 = item_fill_kernel
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)
     int  guard_verbose = 0;       // GPIRT_GUARD_VERBOSE: 1 = a hang-guard fallback prints the guard record to stderr
 };
@@ -224,22 +228,27 @@ __host__ __device__ inline double item_uniform(uint64_t seed, uint32_t iter, uin
     return ((double)v + 0.5) * 2.220446049250313e-16;
 }
 
-// R's qnorm(p, 0, 1, lower, !log): Wichura AS241 PPND16, evaluated in R's Horner order
-__host__ __device__ inline double qnorm_as241(double p)
+// R's qnorm(p, 0, 1, lower, !log): Wichura AS241 PPND16, evaluated in R's Horner order -- in two halves, so that a fill can
+// run the central branch on every lane and the tail branch on a compacted list (rng_ess.hip item_fill_normal_kernel)
+// the central branch, |q| <= 0.425, q = p - 0.5
+__host__ __device__ inline double qnorm_as241_central(double q)
 {
-    double q = p - 0.5, r, val;
-    if (fabs(q) <= 0.425) {
-        r = 0.180625 - q * q;
-        val = q * (((((((r * 2509.0809287301226727 + 33430.575583588128105) * r
-                        + 67265.770927008700853) * r + 45921.953931549871457) * r
-                      + 13731.693765509461125) * r + 1971.5909503065514427) * r
-                    + 133.14166789178437745) * r + 3.387132872796366608)
-              / (((((((r * 5226.495278852545925 + 28729.085735721942674) * r
-                      + 39307.89580009271061) * r + 21213.794301586595867) * r
-                    + 5394.1960214247511077) * r + 687.1870074920579083) * r
-                  + 42.313330701600911252) * r + 1.0);
-        return val;
-    }
+    const double r = 0.180625 - q * q;
+    return q * (((((((r * 2509.0809287301226727 + 33430.575583588128105) * r
+                     + 67265.770927008700853) * r + 45921.953931549871457) * r
+                   + 13731.693765509461125) * r + 1971.5909503065514427) * r
+                 + 133.14166789178437745) * r + 3.387132872796366608)
+           / (((((((r * 5226.495278852545925 + 28729.085735721942674) * r
+                   + 39307.89580009271061) * r + 21213.794301586595867) * r
+                 + 5394.1960214247511077) * r + 687.1870074920579083) * r
+               + 42.313330701600911252) * r + 1.0);
+}
+
+// the tails, |p - 0.5| > 0.425
+__host__ __device__ inline double qnorm_as241_tail(double p)
+{
+    const double q = p - 0.5;
+    double r, val;
     r = (q < 0) ? p : 1.0 - p;
     r = sqrt(-log(r));
     if (r <= 5.0) {
@@ -265,6 +274,13 @@ __host__ __device__ inline double qnorm_as241(double p)
     }
     if (q < 0.0) val = -val;
     return val;
+}
+
+__host__ __device__ inline double qnorm_as241(double p)
+{
+    const double q = p - 0.5;
+    if (fabs(q) <= 0.425) return qnorm_as241_central(q);
+    return qnorm_as241_tail(p);
 }
 
 // R's norm_rand() under INVERSION from two consecutive stream uniforms

@@ -252,7 +252,7 @@ void trsm_inverses_mark(gpirt_handle_t h, const double* L, int64_t n, int64_t ld
 
 // rng.hip
 int launch_item_uniforms(hipStream_t stream, uint64_t seed, uint32_t iter, uint32_t stage,
-                         uint32_t item0, int64_t n_items, int64_t n_index, double* out, bool normal);
+                         uint32_t item0, int64_t n_items, int64_t n_index, double* out, bool normal, bool compact = false);
 // z (n x m) from the R stream: column j, row i <- rnorm from U[pos0 + j*stride + 2i], U[.. + 1]
 int launch_rstream_normals(hipStream_t stream, const double* U, const uint64_t* d_pos,
                            int64_t col_stride, int64_t n, int64_t m, double* out);
@@ -481,6 +481,8 @@ struct BetaArgs {
     double* mu; double* mu_star;      // refreshed with the new beta (may be null)
     uint64_t seed; uint32_t iter; uint32_t item0;
     const double* U; uint64_t* pos; const uint64_t* item_off; uint64_t cap; int* err;  // R stream
+    int screen;                       // 1: draw_beta_reg_kernel where it is eligible (GPIRT_BETA_SCREEN; y must be +1, -1 or NaN)
+    int* path;                        // 2 x m, tests only (null in production): path[k + 2j] = 0 the screen decided step k, 1 full precision
 };
 int launch_draw_beta(hipStream_t stream, const BetaArgs& a);
 int launch_linear_mean(hipStream_t stream, const double* x, int64_t n, const double* beta, int64_t m, double* mu);

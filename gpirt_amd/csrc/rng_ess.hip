@@ -38,6 +38,61 @@ __global__ void item_fill_kernel(uint64_t seed, uint32_t iter, uint32_t stage, u
     }
 }
 
+// The normal fill.  item_fill_kernel is bound by vector issue, not by its stores: AS241's tail branch (the library's log and
+// sqrt, two degree-7 polynomials, a division: ~220 of the loop's ~355 instructions) is needed by 15 % of the elements, so
+// every wavefront holds one and runs it with most lanes masked off.  Here a work-group owns ZF_TILE consecutive elements:
+// every lane runs the central branch for its own elements and leaves the others' slots on a list in LDS (an LDS counter
+// hands out the places: the order of the list changes no value); behind one barrier the listed elements' tails run
+// on whole wavefronts.  Results pass through a tile in LDS (a tail element's slot carries its uniform in between) and leave
+// in one coalesced sweep.  Every value is qnorm_as241(item_uniform(...)) of its own index: item_fill_kernel's bits.
+constexpr int ZF_TILE = 1024;
+__global__ __launch_bounds__(256) void item_fill_normal_kernel(uint64_t seed, uint32_t iter, uint32_t stage, uint32_t item0,
+                                                               int64_t n_items, int64_t n_index, double* __restrict__ out)
+{
+    __shared__ double tile[ZF_TILE];
+    __shared__ unsigned short list[ZF_TILE];
+    __shared__ int count;
+    const int64_t total = n_items * n_index;
+    const int64_t ntiles = (total + ZF_TILE - 1) / ZF_TILE;
+    const int t = threadIdx.x;
+    for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+        const int64_t base = tl * ZF_TILE;
+        const int64_t it0 = base / n_index, ix0 = base - it0 * n_index;    // (work-group uniform)
+        const bool one_item = ix0 + ZF_TILE <= n_index;                    // the tile lies inside one item: no division per element
+        if (t == 0) count = 0;
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < ZF_TILE / 256; ++e) {
+            const int slot = t + 256 * e;
+            const int64_t g = base + slot;
+            if (g < total) {
+                int64_t it = it0, ix = ix0 + slot;
+                if (!one_item) { it = g / n_index; ix = g - it * n_index; }
+                const double u = item_uniform(seed, iter, stage, item0 + (uint32_t)it, (uint32_t)ix);
+                const double q = u - 0.5;
+                if (fabs(q) <= 0.425) {
+                    tile[slot] = qnorm_as241_central(q);
+                } else {
+                    tile[slot] = u;
+                    list[atomicAdd(&count, 1)] = (unsigned short)slot;
+                }
+            }
+        }
+        __syncthreads();
+        const int c = count;
+        for (int k = t; k < c; k += 256) {
+            const int slot = list[k];
+            tile[slot] = qnorm_as241_tail(tile[slot]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < ZF_TILE / 256; ++e) {
+            const int64_t g = base + t + 256 * e;
+            if (g < total) out[g] = tile[t + 256 * e];
+        }
+    }
+}
+
 __global__ void rstream_normals_kernel(const double* __restrict__ U, const uint64_t* __restrict__ pos,
                                        int64_t col_stride, int64_t n, int64_t m,
                                        double* __restrict__ out)
@@ -920,10 +975,18 @@ __global__ void check_y_kernel(const double* __restrict__ y, int64_t total, int*
 }  // namespace
 
 int launch_item_uniforms(hipStream_t stream, uint64_t seed, uint32_t iter, uint32_t stage,
-                         uint32_t item0, int64_t n_items, int64_t n_index, double* out, bool normal)
+                         uint32_t item0, int64_t n_items, int64_t n_index, double* out, bool normal, bool compact)
 {
     const int64_t total = n_items * n_index;
     if (total <= 0) return 0;
+    if (normal && compact) {                                   // GPIRT_ZFILL_COMPACT=1
+        int64_t tiles = (total + ZF_TILE - 1) / ZF_TILE;
+        if (tiles > 8192) tiles = 8192;
+        hipLaunchKernelGGL(item_fill_normal_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, seed, iter,
+                           stage, item0, n_items, n_index, out);
+        GP_HIP(hipGetLastError());
+        return 0;
+    }
     int64_t blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(item_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, seed, iter,

@@ -692,7 +692,7 @@ int do_draw_f(gpirt_sampler_s* s)
             s->z_filled_iter = 0;
         } else {
             GP_TRY(z_sync(s));                                    // a prefill for ANOTHER iteration may still be writing Z
-            GP_TRY(launch_item_uniforms(st, s->opt.seed, iter, GPIRT_ST_F_Z, (uint32_t)s->opt.item0, m, n, s->Z, true));
+            GP_TRY(launch_item_uniforms(st, s->opt.seed, iter, GPIRT_ST_F_Z, (uint32_t)s->opt.item0, m, n, s->Z, true, s->h->cfg.zfill_compact == 1));
         }
         {
             ProfPair pp;                                          // (bench.py's roofline: class 3, n^2 m flops)
@@ -1121,6 +1121,7 @@ int launch_beta_on(gpirt_sampler_s* s, hipStream_t st)
     a.step = s->step; a.n = s->n; a.m = s->m; a.N = s->N; a.mu = s->mu; a.mu_star = s->mu_star;
     a.seed = s->opt.seed; a.iter = (uint32_t)(s->iter + 1); a.item0 = (uint32_t)s->opt.item0;
     a.err = s->flags;
+    a.screen = s->h->cfg.beta_screen == 1;           // (y was checked at creation: +1, -1 or NaN)
     if (stream_mode(s)) { a.U = s->U; a.pos = s->pos; a.item_off = s->beta_off; a.cap = s->U_cap; }
     GP_TRY(launch_draw_beta(st, a));
     if (stream_mode(s)) GP_TRY(launch_advance_pos(st, s->pos, s->beta_total));
@@ -1363,7 +1364,7 @@ int do_factor(gpirt_sampler_s* s)
         hipStream_t ax = s->haux->stream;
         const uint32_t next_iter = (uint32_t)(s->iter + 2);
         GP_HIP(hipStreamWaitEvent(ax, ev_side, 0));
-        GP_TRY(launch_item_uniforms(ax, s->opt.seed, next_iter, GPIRT_ST_F_Z, (uint32_t)s->opt.item0, s->m, s->n, s->Z, true));
+        GP_TRY(launch_item_uniforms(ax, s->opt.seed, next_iter, GPIRT_ST_F_Z, (uint32_t)s->opt.item0, s->m, s->n, s->Z, true, s->h->cfg.zfill_compact == 1));
         GP_HIP(hipEventRecord(s->ev_zfill, ax));
         s->z_filled_iter = next_iter;
     }
@@ -2256,7 +2257,7 @@ int gpirt_sampler_init(gpirt_sampler_t s)
     GP_TRY(rc_f);
     GP_TRY(factor_guard_sync(s));         // (init drains the stream below anyway)
     if (!stream_mode(s)) {
-        GP_TRY(launch_item_uniforms(st, s->opt.seed, 0, GPIRT_ST_INIT_F, (uint32_t)s->opt.item0, m, n, s->Z, true));
+        GP_TRY(launch_item_uniforms(st, s->opt.seed, 0, GPIRT_ST_INIT_F, (uint32_t)s->opt.item0, m, n, s->Z, true, s->h->cfg.zfill_compact == 1));
         GP_TRY(launch_gemm(h, st, false, false, TRI_A_LOWER, n, m, n, 1.0, s->L, s->ldl, s->Z, n, 0.0, s->f, n)); // :18-21
         // beta(p, j) = R::rnorm(prior_mean, prior_sd), index = p                    :22-27
         std::vector<double> b((size_t)(2 * m));

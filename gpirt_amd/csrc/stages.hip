@@ -8,6 +8,7 @@
 // respondent), coalesced along the contiguous column, fixed-tree block reductions.
 #include "common.h"
 #include "kernels.h"
+#include "ll_fast.h"
 
 namespace gpirt {
 
@@ -339,6 +340,160 @@ __global__ __launch_bounds__(256) void draw_beta_kernel(BetaArgs a)
             a.mu_star[i + j * a.N] = cv[0] + (-5.0 + (double)i * 0.01) * cv[1];
 }
 
+// Register-resident form for the item-keyed RNG and 1 <= n <= 256 * EPT (GPIRT_BETA_SCREEN=1): thread t keeps f and theta of
+// its rows t + 256 e in registers and y as two bit masks (observed, negative; y is +1, -1 or NaN, so y (f + mu) = +-(f + mu)
+// exactly), so the column is read once.  Each of the two accept tests needs only the sign of log u - r: it is taken from
+// the single-precision sums of ll_term_screen (ll_fast.h), r_s = (pv_prior - cv_prior) - S_p + S_c, wherever r_s is further
+// from log u than both sums' error bands together (band = LL_SCREEN_ERR n each), and from the expression of
+// draw_beta_kernel otherwise -- same terms, same assignment of rows to threads, same order, same tree, hence the same bits
+// of r.  So every decision is draw_beta_kernel's.  The screen does not decide when an observed row's argument, the
+// proposal's or the current state's, lies below -709: the written term is +inf from -709.78 on and the screen's stays
+// finite (seen on the screened term, which is at least -a: a term above 709 sends the step to the full path).  A NaN in
+// any comparison fails both of them and lands in the full path as well.
+// The masks act on bits, not on lanes: the sign of the argument is flipped by an exclusive or, and the term of a row that
+// does not count is cleared to +0.0 by an and.  The sums start at +0.0 and their terms are never negative, so no partial
+// sum is -0.0 and x + 0.0 is x bit for bit: adding the cleared term is skipping the row, without a branch or a lane mask
+// per row (32 of those each were 360 spilled scalar registers).
+// DB_COEF: the coefficients and masks of one pass behind an empty asm, so that every pass forms its arguments and its rows'
+// masks anew.  Without it the compiler keeps the arguments (and theta_i b1) of the screened passes alive for the
+// full-precision pass that rarely follows, and every row's two masks from the first pass to the last: 8 registers per row.
+// (Macros, not lambdas over the arrays: rng_ess.hip, ess_kernel_reg.)
+#define DB_COEF(v) double b0 = (v)[0], b1 = (v)[1]; uint32_t lv = live, ng = neg; asm volatile("" : "+v"(b0), "+v"(b1), "+v"(lv), "+v"(ng))
+#define DB_KEEP(e) (0ull - (uint64_t)((lv >> (e)) & 1u))                                    /* all ones: the row counts */
+#define DB_ARG(e) __longlong_as_double(__double_as_longlong(F[e] + (b0 + T[e] * b1)) ^ (long long)((uint64_t)((ng >> (e)) & 1u) << 63))
+#define DB_TERM(e, fn) __longlong_as_double(__double_as_longlong(fn(DB_ARG(e))) & (long long)DB_KEEP(e))
+// acc, tmax <- the screened sum of this thread's rows under coefficients v, and the largest of its terms
+#define DB_SCREEN_PASS(v)                                                    \
+    {                                                                        \
+        DB_COEF(v);                                                          \
+        acc = 0.0;                                                           \
+        tmax = 0.0;                                                          \
+        _Pragma("unroll") for (int e = 0; e < EPT; ++e) {                    \
+            const double term = DB_TERM(e, ll_term_screen);                  \
+            acc += term;                                                     \
+            tmax = fmax(tmax, term);                                         \
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);             \
+        }                                                                    \
+    }
+// acc <- the full-precision sum: draw_beta_kernel's terms in its order
+#define DB_FULL_PASS(v)                                                      \
+    {                                                                        \
+        DB_COEF(v);                                                          \
+        acc = 0.0;                                                           \
+        _Pragma("unroll") for (int e = 0; e < EPT; ++e) {                    \
+            acc += DB_TERM(e, ll_term);                                      \
+            __builtin_amdgcn_sched_barrier(0);                               \
+        }                                                                    \
+    }
+// a value every lane holds alike, moved to scalar registers: the kernel's vector registers go to the rows
+__device__ __forceinline__ double db_uniform(double v)
+{
+    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+template <int EPT>
+__global__ __launch_bounds__(256) void draw_beta_reg_kernel(BetaArgs a)
+{
+    static_assert(EPT <= 32, "one bit per row in the masks");
+    __shared__ double red[4];
+    const int64_t j = blockIdx.x;
+    const int n = (int)a.n;
+    const int t = threadIdx.x;
+    const double* __restrict__ fj = a.f + j * a.n;
+    const double* __restrict__ yj = a.y + j * a.n;
+    const double* __restrict__ th = a.theta;
+    const uint32_t item = a.item0 + (uint32_t)j;
+    double F[EPT], T[EPT];
+    uint32_t live = 0, neg = 0;
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) {
+        const int i = t + 256 * e;
+        const int ic = i < n ? i : n - 1;                      // (a row past the end reads the last one and is masked out)
+        const double yy = yj[ic];
+        F[e] = fj[ic];
+        T[e] = th[ic];
+        live |= (uint32_t)(i < n && yy == yy) << e;
+        neg |= (uint32_t)(yy < 0.0) << e;
+        // (eight rows' loads at a time: y's registers are dead as soon as its two bits are taken)
+        if ((e & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+    }
+    double cv[2] = { a.beta[0 + 2 * j], a.beta[1 + 2 * j] };
+    double pv[2] = { cv[0], cv[1] };
+    const double band = LL_SCREEN_ERR * (double)n;
+    double kept_ll = 0.0;                 // ll(y | current beta) in full precision, where the last step formed it
+    bool have_kept = false;
+    double kept_s = 0.0;                  // the screened sum of the current state, and whether one of its rows overflows
+    int kept_ovf = 0;
+    double acc, tmax;
+    for (int k = 0; k < 2; ++k) {               // (one copy of the passes' code: not unrolled)
+        const double step = a.step[k + 2 * j];
+        const double z = qnorm_as241(item_uniform(a.seed, a.iter, GPIRT_ST_BETA, item, (uint32_t)(2 * k)));
+        bool consumes;
+        pv[k] = db_uniform(r_rnorm(cv[k], step, z, consumes));              // draw-beta.cpp:22
+        const double pm = a.pm[k + 2 * j], ps = a.ps[k + 2 * j];
+        const double pv_prior = db_uniform(r_dnorm_log(pv[k], pm, ps));     // :25
+        const double cv_prior = db_uniform(r_dnorm_log(cv[k], pm, ps));     // :26
+        DB_SCREEN_PASS(pv);
+        const double s_p = db_uniform(block_sum_256(acc, red));
+        const int ovf_p = __syncthreads_or(tmax > 709.0);
+        double s_c = kept_s;              // (k = 1: whichever screened sum step 0 kept)
+        int ovf_c = kept_ovf;
+        if (k == 0) {
+            DB_SCREEN_PASS(cv);
+            s_c = db_uniform(block_sum_256(acc, red));
+            ovf_c = __syncthreads_or(tmax > 709.0);
+        }
+        const double u = item_uniform(a.seed, a.iter, GPIRT_ST_BETA, item, (uint32_t)(2 * k + 1));
+        const double log_u = db_uniform(log(u));
+        const double r_s = (pv_prior - cv_prior) - s_p + s_c;
+        int verdict = 0;                                                    // +1 accept, -1 reject, 0: full precision decides
+        if (r_s - 2.0 * band > log_u) verdict = 1;
+        else if (r_s + 2.0 * band < log_u) verdict = -1;
+        if (ovf_p | ovf_c) verdict = 0;
+        const bool full = verdict == 0;                                     // (work-group uniform: sums, u and flags are)
+        double pv_ll = 0.0, cv_ll = 0.0;
+        if (full) {
+            DB_FULL_PASS(pv);                                               // :27
+            pv_ll = db_uniform(-block_sum_256(acc, red));
+            if (k == 1 && have_kept) {
+                cv_ll = kept_ll;
+            } else {
+                // (at k = 1 behind a screened step 0: the sum draw_beta_kernel kept, formed now -- same expression, same bits)
+                DB_FULL_PASS(cv);                                           // :28
+                cv_ll = db_uniform(-block_sum_256(acc, red));
+            }
+            const double r = pv_prior + pv_ll - cv_prior - cv_ll;           // :29
+            verdict = (log_u < r) ? 1 : -1;
+        }
+        if (a.path && t == 0) a.path[k + 2 * j] = full ? 1 : 0;
+        if (verdict > 0) { cv[k] = pv[k]; kept_ll = pv_ll; kept_s = s_p; kept_ovf = ovf_p; }   // :30-35
+        else { pv[k] = cv[k]; kept_ll = cv_ll; kept_s = s_c; kept_ovf = ovf_c; }
+        have_kept = full;
+    }
+    if (t == 0) { a.beta[0 + 2 * j] = cv[0]; a.beta[1 + 2 * j] = cv[1]; }
+    if (a.mu) {
+        double* __restrict__ mj = a.mu + j * a.n;
+        int t2 = t;                                            // (the rows' indices formed anew, not carried from the loads)
+        asm volatile("" : "+v"(t2));
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
+            const int i = t2 + 256 * e;
+            if (i < n) mj[i] = cv[0] + T[e] * cv[1];
+            if ((e & 7) == 7) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if (a.mu_star)
+        for (int64_t i = t; i < a.N; i += 256)
+            a.mu_star[i + j * a.N] = cv[0] + (-5.0 + (double)i * 0.01) * cv[1];
+}
+#undef DB_COEF
+#undef DB_KEEP
+#undef DB_ARG
+#undef DB_TERM
+#undef DB_SCREEN_PASS
+#undef DB_FULL_PASS
+
 __global__ void linear_mean_kernel(const double* __restrict__ x, int64_t n, const double* __restrict__ beta,
                                    int64_t m, double* __restrict__ mu)
 {
@@ -438,7 +593,12 @@ int launch_theta_sample(hipStream_t stream, const ThetaArgs& a)
 int launch_draw_beta(hipStream_t stream, const BetaArgs& a)
 {
     if (a.m <= 0) return 0;
-    hipLaunchKernelGGL(draw_beta_kernel, dim3((unsigned)a.m), dim3(256), 0, stream, a);
+    // the register kernel: item-keyed RNG, a column within 32 rows per thread, y known to be +1, -1 or NaN (the caller's word)
+    const bool reg = a.screen == 1 && a.U == nullptr && a.n >= 1 && a.n <= 256 * 32;
+    if (reg && a.n <= 256 * 8) hipLaunchKernelGGL(draw_beta_reg_kernel<8>, dim3((unsigned)a.m), dim3(256), 0, stream, a);
+    else if (reg && a.n <= 256 * 16) hipLaunchKernelGGL(draw_beta_reg_kernel<16>, dim3((unsigned)a.m), dim3(256), 0, stream, a);
+    else if (reg) hipLaunchKernelGGL(draw_beta_reg_kernel<32>, dim3((unsigned)a.m), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(draw_beta_kernel, dim3((unsigned)a.m), dim3(256), 0, stream, a);
     GP_HIP(hipGetLastError());
     return 0;
 }

@@ -314,12 +314,19 @@ class Handle:
         check(self.lib.gpirt_debug_theta_logpost(self._h, _p(y), _p(fstar), n, m, _p(out), C.byref(fb)))
         return out, fb.value
 
-    def draw_beta(self, beta, theta, y, f, pm, ps, step, seed: int, it: int):
-        """draw_beta(): src/draw-beta.cpp:3-41 (item RNG).  In place on beta (2 x m)."""
+    def draw_beta(self, beta, theta, y, f, pm, ps, step, seed: int, it: int, paths: bool = False):
+        """draw_beta(): src/draw-beta.cpp:3-41 (item RNG).  In place on beta (2 x m).  paths=True (tests): returns (beta, path),
+        path 2 x m int32 -- 0 where the single-precision screen decided the step, 1 where full precision did, and the -1 it was
+        filled with where the kernel without a screen ran (GPIRT_BETA_SCREEN=2, n > 8192, a y that is not +1 / -1 / NaN)."""
         n, m = y.shape
-        check(self.lib.gpirt_draw_beta(self._h, _p(beta), _p(theta), _p(y), _p(f), _p(pm), _p(ps), _p(step),
-                                       n, m, seed, it))
-        return beta
+        if not paths:
+            check(self.lib.gpirt_draw_beta(self._h, _p(beta), _p(theta), _p(y), _p(f), _p(pm), _p(ps), _p(step),
+                                           n, m, seed, it))
+            return beta
+        path = torch.full((m, 2), -1, dtype=torch.int32, device=y.device)
+        check(self.lib.gpirt_draw_beta_paths(self._h, _p(beta), _p(theta), _p(y), _p(f), _p(pm), _p(ps), _p(step),
+                                             n, m, seed, it, _p(path)))
+        return beta, path.t()
 
     # ---------------------------------------------------------------- profiling
     def prof_enable(self, on: bool):

@@ -281,6 +281,22 @@ int gpirt_draw_theta(gpirt_handle_t h, const double* d_y, const double* d_fstar,
 int gpirt_draw_beta(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
                     const double* d_f, const double* d_prior_means, const double* d_prior_sds,
                     const double* d_step_sizes, int64_t n, int64_t m, uint64_t seed, uint32_t iter);
+/* Library version 141: the same draws from two leaner kernels.  draw_beta under the item RNG at n <= 8192
+ * keeps an item's f and theta in registers and decides each accept test by a single-precision screen of the two log-likelihood
+ * sums wherever their difference is further from log u than the screen's error band (4e-6 n per sum); inside the band, with an
+ * observed row's argument below -709, or with a NaN in the comparison, the test is the full-precision expression of version 140,
+ * same sums in the same order.  beta, mu and mu_star are bit for bit those of version 140.  GPIRT_BETA_SCREEN (gpirt_config_set):
+ * 1 this (the default), 2 always the kernel of version 140.  gpirt_draw_beta first checks that y holds +1, -1 and NaN only (one
+ * small launch and a stream synchronisation) and takes the kernel of version 140 when it does not.
+ * gpirt_draw_beta_paths, for tests: gpirt_draw_beta that also records which path took each decision.  d_path (2 x m ints, device):
+ * entry k + 2 j = 0 when the screen decided coefficient k of item j, 1 when full precision did; the kernel of version 140
+ * leaves d_path as it was.
+ * The normal fills (gpirt_item_normals, draw_f's N(0,1) draws) evaluate the tail branch of AS241 (|u - 0.5| > 0.425) on a
+ * compacted list per 1024 elements instead of under a mask in every wavefront; every value is bit for bit that of version 140.
+ * GPIRT_ZFILL_COMPACT (gpirt_config_set): 1 this (the default), 2 the kernel of version 140. */
+int gpirt_draw_beta_paths(gpirt_handle_t h, double* d_beta, const double* d_theta, const double* d_y,
+                          const double* d_f, const double* d_prior_means, const double* d_prior_sds,
+                          const double* d_step_sizes, int64_t n, int64_t m, uint64_t seed, uint32_t iter, int* d_path);
 
 /* The item-RNG primitives, exported so hosts and tests can address the same sub-streams. */
 int gpirt_item_uniforms(gpirt_handle_t h, uint64_t seed, uint32_t iter, uint32_t stage,
