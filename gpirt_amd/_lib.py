@@ -592,6 +592,22 @@ class Ordinal(C.Structure):
         ("hi", C.c_double), ("last_ms", C.c_double), ("lp_width", C.c_int64), ("reserved", C.c_int64 * 3)]
 
 
+# ordinal model fit (include/gpirt_hip.h gpirt_ordinal_fit; gpirt_amd.ordinal.fit_*)
+ST_ORD_PPC = 17                   # the replicate of the ordinal PPC: item index item0 + j, index i
+OFIT_WAIC, OFIT_PRED, OFIT_PPC = 1, 2, 4
+OFIT_PARTS = {"waic": OFIT_WAIC, "pred": OFIT_PRED, "ppc": OFIT_PPC}
+OFIT_UNIT_FIELDS = ("n_obs", "obs_score", "score_ge", "score_gt", "rep_score_sum", "rep_score_sumsq", "agree_sum", "dev_ge",
+                    "nonfinite", "dev_obs_sum", "dev_rep_sum")       # uint64 but for the last two (doubles)
+OFIT_CAT_FIELDS = ("obs_count", "rep_count_sum", "rep_count_sumsq", "count_ge", "count_gt")
+OFIT_TOTALS = ("lppd", "p_waic", "elpd_waic", "waic", "se_elpd_waic")
+
+
+class OrdinalFit(C.Structure):
+    """gpirt_ordinal_fit (include/gpirt_hip.h): the sizes, the draws and the WAIC totals of a fit state block."""
+    _fields_ = [(k, C.c_int64) for k in ("n", "m", "categories", "parts", "draws", "n_obs")] + [
+        (k, C.c_double) for k in OFIT_TOTALS] + [("reserved", C.c_int64 * 5)]
+
+
 class Pop(C.Structure):
     """gpirt_pop (include/gpirt_hip.h): the mode, the sizes, the totals over the groups and the last call's off-grid members."""
     _fields_ = [(k, C.c_int64) for k in ("on", "groups", "n", "points_mu", "points_sd", "calls") + POP_COUNTS + (
@@ -875,6 +891,14 @@ SIGNATURES = {
     "gpirt_sampler_ordinal_accumulate_irf": (_i32, [_vp]),
     "gpirt_sampler_ordinal_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
     "gpirt_sampler_ordinal_stats": (_i32, [_vp, C.POINTER(Ordinal)]),
+    "gpirt_sampler_ordinal_fit_enable": (_i32, [_vp, _i32]),
+    "gpirt_sampler_ordinal_fit_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_ordinal_fit_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ordinal_fit_totals": (_i32, [_vp, C.POINTER(OrdinalFit)]),
+    "gpirt_sampler_ordinal_fit_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ordinal_fit_combine": (_i32, [_vp, C.POINTER(_vp), _i32, _vp]),
+    "gpirt_ordinal_fit_get": (_i32, [_vp, _vp, C.c_char_p, _vp, _i64]),
+    "gpirt_ordinal_fit_totals": (_i32, [_vp, _vp, C.POINTER(OrdinalFit)]),
     "gpirt_sampler_carry_f": (_i32, [_vp, _i32]),
     "gpirt_sampler_step_consistent": (_i32, [_vp, _i32]),
     "gpirt_sampler_carry_stats": (_i32, [_vp, C.POINTER(Carry)]),

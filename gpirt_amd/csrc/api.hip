@@ -170,7 +170,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 141; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 142; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)

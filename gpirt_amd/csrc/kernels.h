@@ -198,6 +198,42 @@ int launch_ord_thresholds(hipStream_t stream, const OrdThrArgs& a);   // one win
 int launch_ord_irf(hipStream_t stream, const double* fstar, int64_t N, int64_t m, int C, const double* thr, double* cum);
 int launch_ord_record(hipStream_t stream, const int* idx, int64_t m, int C, int P, int64_t slot, uint32_t* hist, int32_t* draws);
 void ord_grid_fill(double hi, int P, double* out);                    // long double, rounded once: the centre exactly 0
+// ordinal_fit.hip: fit output of the ordinal model accumulated one draw at a time (gpirt_sampler_ordinal_fit_*).  The state is ONE
+// device block of 8-byte words: a header of OFIT_HEADER_WORDS int64 (the tag "OFIT", the layout version, n, m, C, parts, draws,
+// item0), then the enabled parts' arrays in this order -- WAIC: double lse, ll_mean, ll_m2 [n x m] (a missing cell's ll_m2 is -1
+// and its words are never touched); PRED: double [C - 1][n x m]; PPC: [OFIT_NUNIT][stride] (units: the m items, the n respondents,
+// the whole matrix; stride = n + m + 1 rounded up to even; uint64 but for the two deviance sums) and uint64 [OFIT_NCAT][m][C].
+constexpr int OFIT_HEADER_WORDS = 16;
+constexpr int OFIT_LAYOUT_VERSION = 1;
+enum { OFIT_U_N_OBS = 0, OFIT_U_OBS_SCORE, OFIT_U_SCORE_GE, OFIT_U_SCORE_GT, OFIT_U_REP_SUM, OFIT_U_REP_SUMSQ, OFIT_U_AGREE,
+       OFIT_U_DEV_GE, OFIT_U_NONFINITE, OFIT_U_DEV_OBS, OFIT_U_DEV_REP, OFIT_NUNIT };
+enum { OFIT_K_OBS = 0, OFIT_K_REP_SUM, OFIT_K_REP_SUMSQ, OFIT_K_GE, OFIT_K_GT, OFIT_NCAT };
+struct OfitLayout { int64_t lse, mean, m2, pred, units, cats, words, cells, stride; };       // offsets in words, -1: not there
+OfitLayout ofit_layout(int64_t n, int64_t m, int C, int parts);
+struct OfitState {
+    bool on = false;
+    int64_t n = 0, m = 0, item0 = 0, draws = 0;
+    int C = 0, parts = 0, strips = 0, rblocks = 0;
+    OfitLayout L{};
+    uint64_t* block = nullptr;
+    double *rowd = nullptr, *cold = nullptr;          // a draw's partials: [strip][3][n], [row block][3][m]
+    uint32_t *rowi = nullptr, *coli = nullptr, *colc = nullptr;       //   ... their packed counts; [row block][m][8] category counts
+    double* unit_d = nullptr; uint64_t* unit_i = nullptr;             // the items' sums of a draw ([3][m]), for the total
+    int8_t* rep = nullptr;                            // the last draw: the replicate (n x m), Delta and the score of every unit,
+    double* last_delta = nullptr; int64_t *last_score = nullptr, *last_counts = nullptr;      //   the replicate's counts (m x C)
+    std::vector<void*> allocs;
+};
+int64_t ofit_state_words(const OfitState* p);
+int ofit_alloc(hipStream_t stream, OfitState* p, int64_t n, int64_t m, int C, int parts, int64_t item0, const int8_t* cat);
+void ofit_free(OfitState* p);
+int ofit_seal(hipStream_t stream, OfitState* p);      // refreshes the header (synchronises)
+// one draw: f, mu (n x m doubles), cat (n x m int8) and thr (m x (C - 1)) on the device; iter = the completed-iteration counter
+int launch_ofit_accumulate(hipStream_t stream, OfitState* p, const double* f, const double* mu, const int8_t* cat, const double* thr,
+                           uint64_t seed, uint32_t iter);
+int ofit_block_get(hipStream_t stream, const void* d_block, const char* name, void* h_out, int64_t bytes);
+int ofit_last_get(hipStream_t stream, OfitState* p, const char* name, void* h_out, int64_t bytes);   // 1: not a last-draw name
+int ofit_block_totals(hipStream_t stream, const void* d_block, gpirt_ordinal_fit* out);
+int ofit_combine(gpirt_handle_t h, const void* const* d_states, int chains, void* d_out);
 // carry.hip: the consistent step's carry stage (gpirt_sampler_carry_f) and the prior check's reduction (gpirt_sampler_prior_quad)
 struct CarryArgs {
     double* f; const double* theta; const double* fstar; const double* mu_star; int64_t n, m, N;       // f: n x m; fstar, mu_star: N x m

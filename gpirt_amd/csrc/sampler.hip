@@ -130,6 +130,7 @@ struct OrdState {
     int32_t* draws = nullptr;                                                              // device: planned x m x (C - 1)
     hipEvent_t tev[2] = {};
     double last_ms = 0.0;
+    OfitState fit;                    // the fit output (gpirt_sampler_ordinal_fit_enable, ordinal_fit.hip; on == false: off)
 };
 
 // F of the rank-64 smooth part, Kcc = F F^T (fstar_free_factor) with its DEAD columns (squared norm <= 1e-13) zeroed on the host,
@@ -1455,6 +1456,7 @@ void amp_free(AmpState* a)
 void ord_free(OrdState* p)
 {
     const uint32_t calls = p->t;      // the sampler's draw_thresholds calls: enabling again does not replay their uniforms
+    ofit_free(&p->fit);
     for (void* q : { (void*)p->cat, (void*)p->d_grid, (void*)p->d_log_prior, (void*)p->thr, (void*)p->lp, (void*)p->cum, (void*)p->Y,
                      (void*)p->G, (void*)p->idx, (void*)p->window, (void*)p->counts, (void*)p->stat, (void*)p->hist, (void*)p->draws })
         if (q) hipFree(q);
@@ -4622,6 +4624,81 @@ int gpirt_sampler_ordinal_stats(gpirt_sampler_t s, gpirt_ordinal* out)
     out->pinned = st3[0]; out->failed = st3[1]; out->updates = st3[2];
     out->planned_draws = A.planned; out->recorded = A.recorded; out->irf_draws = A.irf_draws;
     return 0;
+}
+
+// ---- ordinal model fit (ordinal_fit.hip) --------------------------------------------------------------------------------------------
+int gpirt_sampler_ordinal_fit_enable(gpirt_sampler_t s, int parts)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_ordinal_fit_enable";
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    OrdState& A = s->ord;
+    if (parts == 0)
+        return stage_enable(s, &A.fit, ofit_free, false, [] { return 0; });
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    if (parts < 0 || (parts & ~GPIRT_OFIT_ALL)) {
+        set_error("%s: parts = %d has bits outside GPIRT_OFIT_WAIC | GPIRT_OFIT_PRED | GPIRT_OFIT_PPC", me, parts);
+        return GPIRT_E_ARG;
+    }
+    return stage_enable(s, &A.fit, ofit_free, true,
+                        [&] { return ofit_alloc(s->h->stream, &A.fit, s->n, s->m, A.C, parts, s->opt.item0, A.cat); });
+}
+
+int gpirt_sampler_ordinal_fit_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on && A.fit.on, "the ordinal fit block is", "gpirt_sampler_ordinal_fit_enable"));
+    GP_TRY(beta_sync(s));                     // mu of a held-back draw_beta
+    return launch_ofit_accumulate(s->h->stream, &A.fit, s->f, s->mu, A.cat, A.thr, s->opt.seed, (uint32_t)s->iter);
+}
+
+int gpirt_sampler_ordinal_fit_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on && A.fit.on, "the ordinal fit block is", "gpirt_sampler_ordinal_fit_enable"));
+    const int rc = ofit_last_get(s->h->stream, &A.fit, name, h_out, bytes);
+    if (rc != 1) return rc;
+    GP_TRY(ofit_seal(s->h->stream, &A.fit));
+    return ofit_block_get(s->h->stream, A.fit.block, name, h_out, bytes);
+}
+
+int gpirt_sampler_ordinal_fit_totals(gpirt_sampler_t s, gpirt_ordinal_fit* out)
+{
+    GP_ARG(s && out);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on && A.fit.on, "the ordinal fit block is", "gpirt_sampler_ordinal_fit_enable"));
+    GP_TRY(ofit_seal(s->h->stream, &A.fit));
+    return ofit_block_totals(s->h->stream, A.fit.block, out);
+}
+
+int gpirt_sampler_ordinal_fit_state(gpirt_sampler_t s, void** d_block, int64_t* bytes)
+{
+    GP_ARG(s && d_block && bytes);
+    OrdState& A = s->ord;
+    GP_TRY(needs(A.on && A.fit.on, "the ordinal fit block is", "gpirt_sampler_ordinal_fit_enable"));
+    GP_TRY(ofit_seal(s->h->stream, &A.fit));
+    *d_block = A.fit.block;
+    *bytes = ofit_state_words(&A.fit) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ordinal_fit_combine(gpirt_handle_t h, const void* const* d_states, int chains, void* d_out)
+{
+    return ofit_combine(h, d_states, chains, d_out);
+}
+
+int gpirt_ordinal_fit_get(gpirt_handle_t h, const void* d_block, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(h && d_block && name && h_out && bytes >= 0);
+    return ofit_block_get(h->stream, d_block, name, h_out, bytes);
+}
+
+int gpirt_ordinal_fit_totals(gpirt_handle_t h, const void* d_block, gpirt_ordinal_fit* out)
+{
+    GP_ARG(h && d_block && out);
+    return ofit_block_totals(h->stream, d_block, out);
 }
 
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)

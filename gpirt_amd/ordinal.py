@@ -20,7 +20,7 @@ import ctypes as ct
 import numpy as np
 
 from . import _lib
-from ._lib import NGRID, ST_ORD, check
+from ._lib import NGRID, OFIT_CAT_FIELDS, OFIT_PARTS, OFIT_TOTALS, OFIT_UNIT_FIELDS, ST_ORD, ST_ORD_PPC, check
 
 LD = np.longdouble
 ST_F_ESS, ST_BETA = 4, 7
@@ -417,9 +417,361 @@ def make_graded(n, m, C, seed=20240, na_frac=0.1, slopes=None, thresholds=None) 
     return dict(cat=np.asfortranarray(cat), theta=theta, slopes=a, thresholds=B)
 
 
+# ------------------------------------------------------------------------------------------------------ model fit ----
+# (include/gpirt_hip.h "ordinal model fit", csrc/ordinal_fit.hip; library version 142) pointwise WAIC, per-cell
+# category predictions and the first-order posterior predictive check, accumulated on the device one draw at a time.
+# `fit_result` finishes the raw accumulators on the host, `fit_combine` pools chains' state blocks, `fit_from_draws` is the NumPy
+# statement over stored draws.
+FIT_INT_UNIT = OFIT_UNIT_FIELDS[:9]
+FIT_U_TOL = 1e-13         # |u - e_c| at or below: the cell's replicate is undecided
+FIT_D_TOL = 1e-10         # 0 < |Delta| <= FIT_D_TOL sum_changed (|logP(cat)| + |logP(rep)|): the deviance comparison is undecided
+
+
+def fit_parts(parts) -> int:
+    """The GPIRT_OFIT_* bits of a tuple of part names ("waic", "pred", "ppc"); an int is passed through, None / () / False is 0,
+    True is every part."""
+    if parts is True:
+        return 7
+    if parts is None or parts is False:
+        return 0
+    if isinstance(parts, (int, np.integer)):
+        return int(parts)
+    bits = 0
+    for k in ((parts,) if isinstance(parts, str) else tuple(parts)):
+        if k not in OFIT_PARTS:
+            raise ValueError(f"ordinal fit: unknown part {k!r}; the parts are {tuple(OFIT_PARTS)}")
+        bits |= OFIT_PARTS[k]
+    return bits
+
+
+def fit_array(name, n, m, C) -> np.ndarray:
+    """An empty host array of the shape and type the fit block's array `name` has (gpirt_sampler_ordinal_fit_get)."""
+    if name == "draws":
+        return np.empty(1, dtype=np.int64)
+    if name in ("lse", "ll_mean", "ll_m2"):
+        return np.empty((n, m), order="F")
+    if name == "pred_sum":
+        return np.empty((C - 1, m, n)).transpose(0, 2, 1)           # C - 1 planes of column-major n x m
+    if name == "rep":
+        return np.empty((n, m), dtype=np.int8, order="F")
+    if name == "delta":
+        return np.empty(m + n + 1)
+    if name == "score":
+        return np.empty(m + n + 1, dtype=np.int64)
+    if name == "counts_rep":
+        return np.empty((m, C), dtype=np.int64)
+    for pre, size in (("item_", m), ("respondent_", n), ("total_", 1)):
+        if name.startswith(pre):
+            fld = name[len(pre):]
+            return np.empty(size, dtype=np.float64 if fld in ("dev_obs_sum", "dev_rep_sum") else np.uint64)
+    if name.startswith("cat_"):
+        return np.empty((m, C), dtype=np.uint64)
+    return np.empty(0)
+
+
+def _fit_get_into(entry, first, name, out):
+    base = out.base if out.base is not None and name == "pred_sum" else out
+    check(entry(*first, name.encode(), ct.c_void_p(base.ctypes.data), base.nbytes))
+    return out
+
+
+def fit_block_header(state) -> dict:
+    """The header of a fit state block (a device tensor): n, m, categories, parts, draws, item0, layout version."""
+    w = _lib.header_words(state, 8)
+    return dict(version=int(w[1]), n=int(w[2]), m=int(w[3]), categories=int(w[4]), parts=int(w[5]), draws=int(w[6]), item0=int(w[7]))
+
+
+def fit_block_get(handle, state, name) -> np.ndarray:
+    """gpirt_ordinal_fit_get: one raw accumulator of a fit state block, one chain's or a pooled one."""
+    h = fit_block_header(state)
+    out = fit_array(name, h["n"], h["m"], h["categories"])
+    return _fit_get_into(_lib.load().gpirt_ordinal_fit_get, (handle.ptr, ct.c_void_p(state.data_ptr())), name, out)
+
+
+def _fit_totals_dict(t) -> dict:
+    out = {k: int(getattr(t, k)) for k in ("n", "m", "categories", "parts", "draws", "n_obs")}
+    out.update({k: float(getattr(t, k)) for k in OFIT_TOTALS})
+    return out
+
+
+def fit_block_totals(handle, state) -> dict:
+    """gpirt_ordinal_fit_totals of a fit state block."""
+    t = _lib.OrdinalFit()
+    check(_lib.load().gpirt_ordinal_fit_totals(handle.ptr, ct.c_void_p(state.data_ptr()), ct.byref(t)))
+    return _fit_totals_dict(t)
+
+
+def _exact_var(S, s1, s2):
+    """(S sum R^2 - (sum R)^2) / (S (S - 1)): the numerator in exact integers, rounded once"""
+    S, s1, s2 = (np.asarray(x).reshape(-1) for x in (S, s1, s2))
+    out = np.full(S.size, np.nan)
+    for k in range(S.size):
+        Sk = int(S[k])
+        if Sk >= 2:
+            out[k] = float(Sk * int(s2[k]) - int(s1[k]) ** 2) / (float(Sk) * float(Sk - 1))
+    return out
+
+
+def fit_derive_units(d, draws) -> dict:
+    """The derived fields of one kind of unit from its raw sums (ppc.derive's conventions): S = draws - nonfinite, NaN where
+    S = 0 or the unit has no observed cell; ppp_score = score_ge / S, ppp_score_mid = (score_ge + score_gt) / 2S, rep_score_mean,
+    rep_score_var (from the exact integer sums), ppp_dev = dev_ge / S, dev_obs_mean, dev_rep_mean, agree_mean."""
+    f = lambda k: np.asarray(d[k]).astype(np.float64)       # noqa: E731
+    nobs = np.asarray(d["n_obs"])
+    Si = int(draws) - np.asarray(d["nonfinite"]).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S = np.where((Si > 0) & (nobs > 0), Si, np.nan).astype(np.float64)
+        d["ppp_score"] = f("score_ge") / S
+        d["ppp_score_mid"] = (f("score_ge") + f("score_gt")) / (2.0 * S)
+        d["rep_score_mean"] = f("rep_score_sum") / S
+        d["rep_score_var"] = np.where(nobs > 0, _exact_var(Si, d["rep_score_sum"], d["rep_score_sumsq"]).reshape(nobs.shape), np.nan)
+        d["ppp_dev"] = f("dev_ge") / S
+        d["dev_obs_mean"] = f("dev_obs_sum") / S
+        d["dev_rep_mean"] = f("dev_rep_sum") / S
+        d["agree_mean"] = f("agree_sum") / S
+    d["draws"] = int(draws)
+    return d
+
+
+def fit_derive_categories(d, item, draws) -> dict:
+    """ppp_count = count_ge / S, ppp_count_mid = (count_ge + count_gt) / 2S and rep_count_mean = rep_count_sum / S per (item,
+    category), S the item's draws - nonfinite (NaN for an item without an observed cell)."""
+    Si = int(draws) - np.asarray(item["nonfinite"]).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S = np.where((Si > 0) & (np.asarray(item["n_obs"]) > 0), Si, np.nan).astype(np.float64)[:, None]
+        ge, gt = np.asarray(d["count_ge"]).astype(np.float64), np.asarray(d["count_gt"]).astype(np.float64)
+        d["ppp_count"] = ge / S
+        d["ppp_count_mid"] = (ge + gt) / (2.0 * S)
+        d["rep_count_mean"] = np.asarray(d["rep_count_sum"]).astype(np.float64) / S
+    return d
+
+
+def fit_pred(pred_sum, draws, cat=None) -> dict:
+    """From the sums of e_c = P(y > c) ((C - 1) x n x m) and the draws, as `curves` does for the grid: exceed (n x m x (C - 1)),
+    probs (n x m x C, by difference of the means), expected (the expected category) and, with cat, p_observed (the mean
+    probability of the category that was seen; NaN for a missing cell)."""
+    ex = np.moveaxis(np.asarray(pred_sum, dtype=np.float64), 0, 2) / float(draws)
+    n, m, R = ex.shape
+    full = np.concatenate([np.ones((n, m, 1)), ex, np.zeros((n, m, 1))], axis=2)
+    probs = full[:, :, :-1] - full[:, :, 1:]
+    out = dict(exceed=ex, probs=probs, expected=(probs * np.arange(1, R + 2)[None, None, :]).sum(axis=2))
+    if cat is not None:
+        cat = np.asarray(cat).astype(np.int64)
+        po = np.take_along_axis(probs, np.clip(cat - 1, 0, R)[:, :, None], axis=2)[:, :, 0]
+        out["p_observed"] = np.where(cat > 0, po, np.nan)
+    return out
+
+
+def fit_result(get, totals, cat=None) -> dict:
+    """The finished fit output from a getter of raw arrays (name -> array) and the totals dict: "waic" (lse, ll_mean, ll_m2, lppd,
+    p_waic, elpd per cell; NaN for a missing one), "pred" (`fit_pred`), "item", "respondent" (raw sums and `fit_derive_units`),
+    "categories" (`fit_derive_categories`) and "totals" (the WAIC totals and the whole matrix's PPC fields); a part that is not
+    enabled is None."""
+    parts, S = totals["parts"], totals["draws"]
+    out = dict(waic=None, pred=None, item=None, respondent=None, categories=None, totals=dict(totals))
+    if parts & OFIT_PARTS["waic"]:
+        lse, mean, m2 = get("lse"), get("ll_mean"), get("ll_m2")
+        miss = m2 == -1.0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lppd = np.where(miss, np.nan, lse - np.log(float(S))) if S >= 1 else np.full(lse.shape, np.nan)
+            pw = np.where(miss, np.nan, m2 / float(S - 1)) if S >= 2 else np.full(lse.shape, np.nan)
+        out["waic"] = dict(lse=lse, ll_mean=mean, ll_m2=m2, lppd=lppd, p_waic=pw, elpd=lppd - pw)
+    if parts & OFIT_PARTS["pred"]:
+        out["pred"] = fit_pred(get("pred_sum"), S, cat) if S >= 1 else None
+    if parts & OFIT_PARTS["ppc"]:
+        for unit in ("item", "respondent"):
+            out[unit] = fit_derive_units({k: get(f"{unit}_{k}") for k in OFIT_UNIT_FIELDS}, S)
+        tot = fit_derive_units({k: get(f"total_{k}") for k in OFIT_UNIT_FIELDS}, S)
+        out["totals"].update({k: (v if isinstance(v, int) else v.reshape(-1)[0].item()) for k, v in tot.items()})
+        out["categories"] = fit_derive_categories({k: get(f"cat_{k}") for k in OFIT_CAT_FIELDS}, out["item"], S)
+    return out
+
+
+def fit_combine(handle, states, cat=None) -> dict:
+    """gpirt_ordinal_fit_combine over the fit state blocks `states` (device tensors, or Samplers with ordinal_fit_enable on, all on
+    handle's device), in chain order: counts added, Chan's formula for the Welford pairs, a logaddexp for lse.  No signs: theta ->
+    -theta with the slope leaves f + mu and the thresholds as they are.  Returns `fit_result` of the pooled block and the block
+    itself as "state" (a device tensor that `fit_block_get` and `fit_block_totals` read as they read one chain's)."""
+    import torch
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ordinal_fit_state")
+    pooled = torch.empty_like(tensors[0])
+    check(_lib.load().gpirt_ordinal_fit_combine(handle.ptr, ptrs, nc, ct.c_void_p(pooled.data_ptr())))
+    out = fit_result(lambda name: fit_block_get(handle, pooled, name), fit_block_totals(handle, pooled), cat)
+    out["state"] = pooled
+    return out
+
+
+def _fit_terms(g, B):
+    """Per threshold c = 1 .. C - 1 (axis 0) of every cell, in float64 and the kernel's operations: e_c = P(y > c),
+    up_c = ll(b_c - g), lo_c = ll(g - b_c) with ll(a) = log1p(e^-|a|) + max(-a, 0) from ONE E_c = exp(-|g - b_c|)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = g[None, :, :] - B.T[:, None, :]
+        E = np.exp(-np.abs(d))
+        e = np.where(d >= 0, 1.0 / (1.0 + E), E / (1.0 + E))
+        l1 = np.log1p(E)
+        return e, l1 + np.maximum(d, 0.0), l1 + np.maximum(-d, 0.0)
+
+
+def _fit_logp(K, up, lo, W):
+    """logP(K) per cell (K: n x m categories 1 .. C) in the header's order: -up_K if K < C, then - lo_{K-1} if K > 1, then + w_K for
+    an interior K.  W: m x (C + 1), W[j, c] = w(b_c - b_{c-1}) for 1 < c < C and 0 elsewhere."""
+    R = up.shape[0]
+    Cn = R + 1
+    with np.errstate(invalid="ignore"):
+        v = np.zeros(K.shape)
+        iu = np.clip(K - 1, 0, R - 1)[None]
+        il = np.clip(K - 2, 0, R - 1)[None]
+        v = np.where(K < Cn, -np.take_along_axis(up, iu, axis=0)[0], v)
+        v = np.where(K > 1, v - np.take_along_axis(lo, il, axis=0)[0], v)
+        wk = np.take_along_axis(W, np.clip(K, 0, Cn).T, axis=1).T
+        v = np.where((K > 1) & (K < Cn), v + wk, v)
+    return v
+
+
+def fit_from_draws(cat, g_draws, threshold_draws, seed, iters, item0=0, stage=ST_ORD_PPC) -> dict:
+    """What the device accumulates, from stored draws: cat (n x m; 0 = missing), g_draws (S, n, m) the draws of g = f + mu,
+    threshold_draws (S, m, C - 1) the threshold VALUES of each draw, `iters` the S completed-iteration counters.  It follows
+    ppc.from_draws' convention: every integer field of "item", "respondent", "totals" and "categories" is a pair (lo, hi) of int64
+    arrays -- a cell with |u - e_c| <= 1e-13 for some c may replicate either way, a deviance comparison with such a cell in it, or
+    with 0 < |Delta| <= 1e-10 sum_changed (|logP(cat)| + |logP(rep)|), may go either way.  The double fields (dev_obs_sum,
+    dev_rep_sum, "pred_sum") are float64 with the undecided cells at rep = 1 + #{c : u < e_c}; "waic" is the long-double reference
+    (lse, ll_mean, ll_m2, lppd, p_waic, ll_absmax = max_s |logP_s| per cell and the totals).  "rep": the S replicates (0: missing or non-finite); "undecided"
+    counts cells and comparisons, "comparisons" every deviance comparison made."""
+    from .ppc import item_uniform
+    cat = np.asarray(cat).astype(np.int64)
+    g_draws = np.asarray(g_draws, dtype=np.float64)
+    B_draws = np.asarray(threshold_draws, dtype=np.float64)
+    n, m = cat.shape
+    S = g_draws.shape[0]
+    R = B_draws.shape[2]
+    Cn = R + 1
+    iters = [int(x) for x in iters]
+    assert g_draws.shape == (S, n, m) and B_draws.shape == (S, m, R) and len(iters) == S
+    obs = cat > 0
+    units = (("item", 0, m), ("respondent", 1, n), ("totals", None, 1))
+
+    def usum(a, axis):
+        return a.sum(axis=axis) if axis is not None else np.array([a.sum()])
+
+    acc = {}
+    zi = lambda size: np.zeros(size, dtype=np.int64)      # noqa: E731
+    for name, axis, size in units:
+        acc[name] = dict(n_obs=usum(obs, axis).astype(np.int64), obs_score=usum(cat, axis).astype(np.int64), nonfinite=zi(size),
+                         dev_obs_sum=np.zeros(size), dev_rep_sum=np.zeros(size),
+                         **{f"{k}_{b}": zi(size) for k in ("score_ge", "score_gt", "rep_score_sum", "rep_score_sumsq", "agree_sum",
+                                                           "dev_ge") for b in ("lo", "hi")})
+    obs_count = np.stack([(cat == c).sum(axis=0) for c in range(1, Cn + 1)], axis=1).astype(np.int64)
+    kacc = {f"{k}_{b}": np.zeros((m, Cn), dtype=np.int64) for k in ("rep_count_sum", "rep_count_sumsq", "count_ge", "count_gt")
+            for b in ("lo", "hi")}
+    pred_sum = np.zeros((R, n, m))
+    reps = np.zeros((S, n, m), dtype=np.int8)
+    lp_ld = np.zeros((S, n, m), dtype=LD)
+    und_cells = und_cmp = n_cmp = 0
+    items = (np.arange(m, dtype=np.uint64) + np.uint64(item0))[None, :]
+    rows = np.arange(n, dtype=np.uint64)[:, None]
+    for s in range(S):
+        g, B = g_draws[s], B_draws[s]
+        W = np.zeros((m, Cn + 1))
+        if Cn > 2:
+            with np.errstate(divide="ignore"):
+                W[:, 2:Cn] = np.log1p(-np.exp(-(B[:, 1:] - B[:, :-1])))
+        e, up, lo = _fit_terms(g, B)
+        pred_sum += e
+        for j in range(m):
+            lp_ld[s, :, j] = loglik(cat[:, j], g[:, j].astype(LD), B[j], True, LD)
+        with np.errstate(invalid="ignore"):
+            bad = obs & ~np.isfinite(g)
+            live = obs & ~bad
+            u = item_uniform(seed, iters[s], int(stage), items, rows)
+            below = u[None] < e
+            undc = (np.abs(u[None] - e) <= FIT_U_TOL)
+            rep = 1 + below.sum(axis=0)
+            rep_lo = 1 + (below & ~undc).sum(axis=0)
+            rep_hi = 1 + (below | undc).sum(axis=0)
+            und = live & undc.any(axis=0)
+            Kc = np.where(obs, cat, 1)
+            lpc = _fit_logp(Kc, up, lo, W)
+            lpr = _fit_logp(rep, up, lo, W)
+            changed = live & (rep != cat)
+            d_obs = np.where(live, -2.0 * lpc, 0.0)
+            d_rep = np.where(live, -2.0 * np.where(rep == cat, lpc, lpr), 0.0)
+            delta = np.where(changed, lpc - lpr, 0.0)
+            absd = np.where(changed, np.abs(lpc) + np.abs(lpr), 0.0)
+        reps[s] = np.where(live, rep, 0)
+        und_cells += int(und.sum())
+        agree_lo = live & ~und & (rep == cat)
+        agree_hi = live & np.where(und, (rep_lo <= cat) & (cat <= rep_hi), rep == cat)
+        nf_item = None
+        for name, axis, size in units:
+            a = acc[name]
+            nf = usum(bad, axis) > 0
+            if name == "item":
+                nf_item = nf
+            on = ~nf & (a["n_obs"] > 0)
+            a["nonfinite"] += nf
+            nu = usum(und, axis)
+            R_lo = usum(np.where(live, rep_lo, 0), axis).astype(np.int64)
+            R_hi = usum(np.where(live, rep_hi, 0), axis).astype(np.int64)
+            T = a["obs_score"]
+            a["rep_score_sum_lo"] += np.where(on, R_lo, 0); a["rep_score_sum_hi"] += np.where(on, R_hi, 0)
+            a["rep_score_sumsq_lo"] += np.where(on, R_lo * R_lo, 0); a["rep_score_sumsq_hi"] += np.where(on, R_hi * R_hi, 0)
+            a["score_ge_lo"] += on & (R_lo >= T); a["score_ge_hi"] += on & (R_hi >= T)
+            a["score_gt_lo"] += on & (R_lo > T); a["score_gt_hi"] += on & (R_hi > T)
+            a["agree_sum_lo"] += np.where(on, usum(agree_lo, axis), 0); a["agree_sum_hi"] += np.where(on, usum(agree_hi, axis), 0)
+            with np.errstate(invalid="ignore"):
+                D = usum(delta, axis)
+                open_ = (nu > 0) | ((D != 0) & (np.abs(D) <= FIT_D_TOL * usum(absd, axis)))
+                ge = D >= 0
+            a["dev_ge_lo"] += on & ~open_ & ge; a["dev_ge_hi"] += on & (open_ | ge)
+            und_cmp += int((on & open_).sum())
+            n_cmp += int(on.sum())
+            with np.errstate(invalid="ignore"):
+                a["dev_obs_sum"] += np.where(on, usum(d_obs, axis), 0.0)
+                a["dev_rep_sum"] += np.where(on, usum(d_rep, axis), 0.0)
+        on_item = (~nf_item & (acc["item"]["n_obs"] > 0))[:, None]
+        c_lo = np.stack([(live & ~und & (rep == c)).sum(axis=0) for c in range(1, Cn + 1)], axis=1).astype(np.int64)
+        c_hi = c_lo + np.stack([(und & (rep_lo <= c) & (c <= rep_hi)).sum(axis=0) for c in range(1, Cn + 1)], axis=1)
+        for b, cnt in (("lo", c_lo), ("hi", c_hi)):
+            kacc[f"rep_count_sum_{b}"] += np.where(on_item, cnt, 0)
+            kacc[f"rep_count_sumsq_{b}"] += np.where(on_item, cnt * cnt, 0)
+            kacc[f"count_ge_{b}"] += on_item & (cnt >= obs_count)
+            kacc[f"count_gt_{b}"] += on_item & (cnt > obs_count)
+    out = {}
+    pair = lambda x: (x.copy(), x.copy())       # noqa: E731
+    for name, axis, size in units:
+        a = acc[name]
+        d = dict(n_obs=pair(a["n_obs"]), obs_score=pair(a["obs_score"]), nonfinite=pair(a["nonfinite"]),
+                 dev_obs_sum=a["dev_obs_sum"], dev_rep_sum=a["dev_rep_sum"], draws=S)
+        for k in ("score_ge", "score_gt", "rep_score_sum", "rep_score_sumsq", "agree_sum", "dev_ge"):
+            d[k] = (a[f"{k}_lo"], a[f"{k}_hi"])
+        out[name] = d
+    out["categories"] = dict(obs_count=pair(obs_count), **{k: (kacc[f"{k}_lo"], kacc[f"{k}_hi"])
+                                                           for k in ("rep_count_sum", "rep_count_sumsq", "count_ge", "count_gt")})
+    # the WAIC reference in long double: the logaddexp over the draws, the mean and the sum of squared deviations
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        mx = lp_ld.max(axis=0)
+        safe = np.where(np.isfinite(mx), mx, LD(0))
+        lse = np.where(np.isfinite(mx), safe + np.log(np.exp(lp_ld - safe).sum(axis=0)), lp_ld.sum(axis=0))
+        mean = lp_ld.sum(axis=0) / LD(S)
+        m2 = ((lp_ld - mean) ** 2).sum(axis=0)
+        lppd = lse - np.log(LD(S))
+        pw = m2 / LD(S - 1) if S >= 2 else np.full((n, m), np.nan, dtype=LD)
+        elpd = lppd - pw
+        nobs = int(obs.sum())
+        tl, tp = lppd[obs].sum(), pw[obs].sum()
+        se = np.sqrt(LD(nobs) * (((elpd[obs] - elpd[obs].mean()) ** 2).sum() / LD(nobs - 1))) if nobs >= 2 else LD(np.nan)
+    out["waic"] = dict(lse=lse, ll_mean=mean, ll_m2=m2, lppd=lppd, p_waic=pw, observed=obs, ll_absmax=np.abs(lp_ld).max(axis=0),
+                       totals=dict(lppd=tl, p_waic=tp, elpd_waic=tl - tp, waic=LD(-2) * (tl - tp), se_elpd_waic=se, n_obs=nobs, draws=S))
+    out["pred_sum"] = pred_sum
+    out["rep"] = reps
+    out["undecided"] = dict(cells=und_cells, comparisons=und_cmp)
+    out["comparisons"] = n_cmp
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ one call per run ---
 def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width=16, consistent=False, hi=6.0, points=241,
-        log_prior=None, K0=None, theta_init=None, preset="fast", probs=(0.025, 0.25, 0.5, 0.75, 0.975), *, handle=None,
+        log_prior=None, K0=None, theta_init=None, preset="fast", probs=(0.025, 0.25, 0.5, 0.75, 0.975), *, handle=None, fit=None,
         **sampler_kw) -> dict:
     """`chains` chains of the stage-driven Sampler under the ordinal model, one after the other: per iteration step() then
     draw_thresholds(), per kept draw ordinal_record() and ordinal_accumulate_irf().  Chain c runs with the seed
@@ -428,7 +780,9 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
     Returns theta (chains x S x n; S x n for one chain), beta (.. x 2 x m; row 0 is the pinned 0), threshold_draws (indices,
     .. x m x (C - 1)), thresholds (`summarise` over all chains: mean, sd, quantiles per item and threshold, on each chain's own
     latent scale -- chains are not sign-aligned), hist (pooled), curves (`curves` of the pooled accumulators), counters (pinned,
-    failed, updates per chain), grid, categories, chains, consistent."""
+    failed, updates per chain), grid, categories, chains, consistent.  fit=True, or a tuple of parts ("waic", "pred", "ppc"):
+    ordinal_fit_accumulate() after every kept draw and "fit", `fit_combine` over the chains (without its "state"); the default
+    makes the calls and returns the keys it did before."""
     from . import chains as CH
     from .ops import Handle
     from .sampler import Sampler, _options
@@ -438,6 +792,7 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
     if nc < 1 or S < 1 or B < 0:
         raise ValueError("ordinal.run: chains >= 1, sample_iterations >= 1 and burn_iterations >= 0 are needed")
     Cn = categories(cat, C)
+    fit_bits = fit_parts(fit)
     y = dichotomise(cat)
     o = _options(sampler_kw.get("rng", "item"), seed, True, True, None, sampler_kw.get("item0", 0), sampler_kw.get("m_total", 0),
                  sampler_kw.get("kernel_fp32", False), 0)
@@ -461,12 +816,16 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
             s.init()
             s.check()
             s.ordinal_enable(cat, Cn, hi, points, log_prior, k0, width, planned_draws=S)
+            if fit_bits:
+                s.ordinal_fit_enable(fit_bits)
             for it in range(S + B):
                 s.step(consistent=consistent)
                 s.draw_thresholds()
                 if it >= B:
                     s.ordinal_record()
                     s.ordinal_accumulate_irf()
+                    if fit_bits:
+                        s.ordinal_fit_accumulate()
                     th[c, it - B] = s.get("theta")
                     be[c, it - B] = s.get("beta")
             s.check()
@@ -476,7 +835,11 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
             st = s.ordinal_stats()
             counters.append({k: st[k] for k in ("pinned", "failed", "updates")})
         one = nc == 1
-        return dict(theta=th[0] if one else th, beta=be[0] if one else be, threshold_draws=dr[0] if one else dr,
+        extra = {}
+        if fit_bits:
+            extra["fit"] = fit_combine(h, samplers, cat)
+            del extra["fit"]["state"]
+        return dict(**extra, theta=th[0] if one else th, beta=be[0] if one else be, threshold_draws=dr[0] if one else dr,
                     thresholds=summarise(dr, t, probs), hist=hist, curves=curves(cum, nc * S), counters=counters, grid=t,
                     categories=Cn, chains=nc, consistent=bool(consistent))
     finally:
@@ -488,4 +851,6 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
 
 __all__ = ["grid", "default_log_prior", "dichotomise", "init_thresholds", "check_args", "uniforms", "ll", "w", "loglik",
            "category_logprobs", "n_terms", "slice_exact", "theta_logpost_exact", "beta_exact", "window", "candidates",
-           "threshold_conditional", "grid_draw", "thresholds_exact", "transition_matrix", "summarise", "curves", "make_graded", "run"]
+           "threshold_conditional", "grid_draw", "thresholds_exact", "transition_matrix", "summarise", "curves", "make_graded", "run",
+           "fit_parts", "fit_array", "fit_block_header", "fit_block_get", "fit_block_totals", "fit_derive_units",
+           "fit_derive_categories", "fit_pred", "fit_result", "fit_combine", "fit_from_draws"]

@@ -2116,6 +2116,47 @@ class Sampler:
             out["curves"] = OR.curves(self.ordinal_get("cum"), st["irf_draws"])
         return out
 
+    # -- ordinal model fit accumulated on the device (include/gpirt_hip.h gpirt_sampler_ordinal_fit_*, gpirt_amd.ordinal.fit_*)
+    def ordinal_fit_enable(self, parts=("waic", "pred", "ppc")):
+        """Allocate and zero the fit accumulators of the ordinal model for any subset of "waic" (pointwise WAIC, 24 bytes per cell),
+        "pred" (the sums of P(y > c) per cell, missing ones included, 8 (C - 1) bytes per cell) and "ppc" (the first-order
+        posterior predictive check per item, respondent, (item, category) and for the whole matrix).  After ordinal_enable.
+        parts=None (or ()) frees the block."""
+        from . import ordinal as OR
+        bits = OR.fit_parts(parts)
+        check(self.lib.gpirt_sampler_ordinal_fit_enable(self._s, bits))
+        self._ofit = bits
+
+    def ordinal_fit_accumulate(self):
+        """Add the current state (after step() and draw_thresholds()) as one draw, with the sampler's current thresholds; the
+        chain is untouched (the replicate draws from a stage of its own)."""
+        self._call("gpirt_sampler_ordinal_fit_accumulate")
+
+    def ordinal_fit_get(self, name: str) -> np.ndarray:
+        """One raw array by name: draws; lse, ll_mean, ll_m2 (n x m; a missing cell: 0, 0, -1); pred_sum ((C - 1) x n x m);
+        item_<f>, respondent_<f>, total_<f> for f in _lib.OFIT_UNIT_FIELDS; cat_<f> (m x C) for f in _lib.OFIT_CAT_FIELDS; and of
+        the last counted draw rep (int8, n x m), delta, score (m + n + 1: items, respondents, the whole matrix), counts_rep (m x C)."""
+        from . import ordinal as OR
+        out = OR.fit_array(name, self.n, self.m, getattr(self, "_ord", (0, 0, 0))[0])
+        return OR._fit_get_into(self.lib.gpirt_sampler_ordinal_fit_get, (self._s,), name, out)
+
+    def ordinal_fit_totals(self) -> dict:
+        """gpirt_sampler_ordinal_fit_totals: n, m, categories, parts, draws, n_obs, lppd, p_waic, elpd_waic, waic, se_elpd_waic."""
+        from . import ordinal as OR
+        t = _lib.OrdinalFit()
+        check(self.lib.gpirt_sampler_ordinal_fit_totals(self._s, C.byref(t)))
+        return OR._fit_totals_dict(t)
+
+    def ordinal_fit_state(self):
+        """Torch view (int64, on the device) of the ONE block that holds the fit accumulators, its header refreshed: what
+        gpirt_amd.ordinal.fit_combine pools."""
+        return self._state("gpirt_sampler_ordinal_fit_state")
+
+    def ordinal_fit(self) -> dict:
+        """The finished fit output (gpirt_amd.ordinal.fit_result): waic, pred, item, respondent, totals and categories."""
+        from . import ordinal as OR
+        return OR.fit_result(self.ordinal_fit_get, self.ordinal_fit_totals(), self.ordinal_get("cat"))
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

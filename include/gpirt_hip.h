@@ -62,6 +62,7 @@ enum {
     GPIRT_ST_POP = 12,    /* the two uniforms per group of a population-prior update (gpirt_sampler_draw_pop): item index g, index 0 (mu) / 1 (sd); nothing else draws from it */
     GPIRT_ST_CARRY = 11,  /* the nugget of the consistent step's carry (gpirt_sampler_carry_f): item index item0 + j, index i; nothing else draws from it */
     GPIRT_ST_ORD = 16,    /* the two uniforms per threshold of an ordinal threshold update (gpirt_sampler_draw_thresholds): item index item0 + j, index 2 (c - 1) the window's placement, 2 (c - 1) + 1 the draw; nothing else draws from it */
+    GPIRT_ST_ORD_PPC = 17, /* the replicate of the ordinal model's posterior predictive check (gpirt_sampler_ordinal_fit_accumulate): item index item0 + j, index i; nothing else draws from it */
     GPIRT_ST_ELL = 9      /* the two uniforms of a length-scale update: item index 0 the whitened one's (gpirt_sampler_draw_ell), item index 1 the centred one's (gpirt_sampler_draw_ell_centred); nothing else draws from it */
 };
 
@@ -69,7 +70,7 @@ typedef struct gpirt_handle_s*  gpirt_handle_t;
 typedef struct gpirt_sampler_s* gpirt_sampler_t;
 
 /* ---------------------------------------------------------------- library / handle ------ */
-int         gpirt_version(void);    /* 138: draw_f's structured product in parts of its own width with the rank-64 term accumulated in the launch of the diagonal parts (GPIRT_NU_SUB; nu changes in rounding only, no change to the interface); 133: a consistent step beside the reference's -- f carried to the new theta plus the model's nugget, and the prior check (GPIRT_ST_CARRY, gpirt_sampler_carry_f, gpirt_sampler_step_consistent, gpirt_carry, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
+int         gpirt_version(void);    /* 142: fit output for the ordinal model accumulated on the device -- pointwise WAIC, category predictions, the first-order PPC (GPIRT_ST_ORD_PPC, gpirt_ordinal_fit, gpirt_sampler_ordinal_fit_*, gpirt_ordinal_fit_get, gpirt_ordinal_fit_totals, gpirt_ordinal_fit_combine); 138: draw_f's structured product in parts of its own width with the rank-64 term accumulated in the launch of the diagonal parts (GPIRT_NU_SUB; nu changes in rounding only, no change to the interface); 133: a consistent step beside the reference's -- f carried to the new theta plus the model's nugget, and the prior check (GPIRT_ST_CARRY, gpirt_sampler_carry_f, gpirt_sampler_step_consistent, gpirt_carry, gpirt_sampler_carry_stats, gpirt_sampler_prior_quad); 128: draw_f's nu = L z from L's diagonal parts and 64 node rows (GPIRT_NU_LR, gpirt_sampler_nu_lr_draws, gpirt_sampler_nu_lr_rows; gpirt_sampler_ldl has the layouts); 127: group posteriors -- separation, overlap, party-line votes (gpirt_groups, gpirt_groups_check, gpirt_sampler_groups_*, gpirt_groups_combine); 126: a centred length-scale update beside the whitened one (gpirt_sampler_draw_ell_centred, gpirt_sampler_ell_width_centred, gpirt_ell_centred, gpirt_sampler_ell_centred_stats); 125: the kernel's length scale as a parameter of the chain (GPIRT_ST_ELL, gpirt_ell_grid, gpirt_ell_check, gpirt_sampler_ell_*, gpirt_sampler_draw_ell); 124: the covariance kernel is a property of the handle -- squared exponential with a length scale, Matern 5/2, Matern 3/2 (gpirt_kernel, gpirt_kernel_default, gpirt_kernel_check, gpirt_kernel_set, gpirt_kernel_get); 119: gpirt_mcmc_run and gpirt_run replace the thirteen whole-call entries that versions 106 to 118 added one per analysis, each the one before with one more parameter (in that order: quantiles, ppc, ranks, score, predict, pairs, bins, shape, sumscore, dif, equate, loo, order -- the fields of gpirt_run); gpirt_mcmc, gpirt_mcmc_summary and gpirt_mcmc_chains are unchanged; 110: predicting new respondents' unseen answers, next-item information (gpirt_sampler_score_predict_*, gpirt_score_predict_combine); 109: scoring new respondents (gpirt_sampler_score_*, gpirt_score_combine); 108: rank posteriors (gpirt_sampler_rank_*, gpirt_rank_combine); 107: posterior predictive checks (gpirt_sampler_ppc_*, gpirt_ppc_combine); 106: quantiles (gpirt_summary_quantiles); 105: several chains, split-R-hat / ESS / MCSE (GPIRT_SUM_DIAG, gpirt_chains_combine, gpirt_mcmc_chains); 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary); 103: gpirt_debug_poison_allocs, y outside {+1, -1, NaN} refused; 102: gpirt_potrf_subpanel_width(n) takes the order of the matrix; 101: named gpirt_options fields, gpirt_fast_options */
 const char* gpirt_last_error(void);
 int         gpirt_device_count(int* count);
 /* device < 0: current device.  stream is a hipStream_t; NULL is HIP's default (null) stream. */
@@ -2714,6 +2715,60 @@ int gpirt_sampler_ordinal_record(gpirt_sampler_t s);
 int gpirt_sampler_ordinal_accumulate_irf(gpirt_sampler_t s);
 int gpirt_sampler_ordinal_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
 int gpirt_sampler_ordinal_stats(gpirt_sampler_t s, gpirt_ordinal* out);
+
+/* ------------------------------------------------------ ordinal model fit: WAIC, category predictions, PPC ------------ */
+/* Library version 142.  Fit output for the ordinal model above, accumulated on the device one draw at a time so that no f draw is
+ * ever stored.  Stage API only: gpirt_run, gpirt_mcmc* and gpirt_options are unchanged, every refusal above stays (the binary
+ * summaries and PPC are still refused while ordinal is on), nothing is drawn from the chain's streams and a sampler that never
+ * calls gpirt_sampler_ordinal_fit_enable launches exactly what it launched before.
+ *
+ * Per cell and draw, g = f + mu, d_c = g - b_c with the sampler's CURRENT thresholds (an accumulate after
+ * gpirt_sampler_draw_thresholds sees that iteration's), E_c = exp(-|d_c|):
+ *   e_c = P(y > c) = d_c >= 0 ? 1 / (1 + E_c) : E_c / (1 + E_c),     ll(a) = log1p(e^-|a|) + max(-a, 0)
+ *   logP(c) = -ll(b_c - g) [c < C] - ll(g - b_{c-1}) [c > 1] + w(b_c - b_{c-1}) [1 < c < C], added in that order
+ * (csrc/ordinal_fit.hip states the order of every sum; gpirt_amd.ordinal.fit_from_draws is the NumPy statement).
+ *
+ * parts, any subset: GPIRT_OFIT_WAIC -- per observed cell the running lse (a logaddexp, the first draw sets it) and the Welford
+ * mean and M2 of logP(cat), 24 bytes per cell; a cell with a NaN draw is NaN.  GPIRT_OFIT_PRED -- per cell, missing ones
+ * included, the sums of e_c, 8 (C - 1) bytes per cell (for a missing cell its held-out prediction).  GPIRT_OFIT_PPC -- each
+ * observed cell replicated from one uniform, rep = 1 + #{c : u < e_c}, u = item_uniform(seed, iteration, GPIRT_ST_ORD_PPC,
+ * item0 + j, i), iteration the completed-iteration counter; per item, per respondent and for the whole matrix over the observed
+ * cells: n_obs, obs_score (T, the sum of cat), score_ge / score_gt (#{R >= T}, #{R > T} of the replicate's score R),
+ * rep_score_sum, rep_score_sumsq, agree_sum (cells with rep == cat), dev_obs_sum, dev_rep_sum (D = -2 sum logP), dev_ge (Delta >= 0,
+ * Delta = the sum over the cells with rep != cat of logP(cat) - logP(rep): exactly 0, and counted, when nothing changed), nonfinite;
+ * per (item, category): obs_count, rep_count_sum, rep_count_sumsq, count_ge, count_gt.  A unit with a non-finite g in an observed
+ * cell in a draw counts that draw in nonfinite and leaves it out of its sums (the item's category counts included).
+ *
+ * gpirt_sampler_ordinal_fit_enable: after gpirt_sampler_ordinal_enable; parts = 0 turns the block off and frees it, as does
+ * gpirt_sampler_ordinal_enable(cat = NULL).  Refused, GPIRT_E_ARG with the reason: before gpirt_sampler_init, without ordinal on,
+ * parts with unknown bits; gpirt_sampler_ordinal_fit_accumulate without enable; a _get of a part that is not enabled.
+ * gpirt_sampler_ordinal_fit_state: ONE device block (header of 16 int64: the tag "OFIT", layout version, n, m, C, parts, draws,
+ * item0; then the enabled parts' arrays).  gpirt_ordinal_fit_combine pools `chains` such blocks into d_out (as large as one of
+ * them; it may be d_states[0]) in chain order: counts added, Chan's formula for the Welford pairs, a logaddexp for lse.  It takes no
+ * signs: theta -> -theta with the slope leaves f + mu and the thresholds as they are.  gpirt_ordinal_fit_get and
+ * gpirt_ordinal_fit_totals read any such block, one chain's or a pooled one; the sampler's entries read its own.
+ * _get, by name: "draws" (1 int64); "lse", "ll_mean", "ll_m2" (n x m doubles, column-major; a missing cell: 0, 0, -1);
+ * "pred_sum" ((C - 1) planes of n x m doubles); "item_<f>" (m), "respondent_<f>" (n), "total_<f>" (1) for the unit fields <f> above
+ * (uint64; dev_obs_sum and dev_rep_sum doubles); "cat_<f>" (m x C uint64, row-major) for the category fields; and through the
+ * sampler's entry alone, of the last counted draw: "rep" (n x m int8; 0 = missing or non-finite), "delta" and "score" (m + n + 1
+ * doubles / int64: items, respondents, the whole matrix), "counts_rep" (m x C int64).
+ * Limits are the ordinal model's: n <= GPIRT_ORD_MAX_N, C <= GPIRT_ORD_MAX_C, GPIRT_RNG_ITEM, no item shard. */
+enum { GPIRT_OFIT_WAIC = 1, GPIRT_OFIT_PRED = 2, GPIRT_OFIT_PPC = 4, GPIRT_OFIT_ALL = 7 };
+typedef struct gpirt_ordinal_fit {
+    int64_t  n, m, categories, parts;
+    int64_t  draws;                         /* accumulated draws (pooled: of all chains) */
+    int64_t  n_obs;                         /* observed cells (0 with GPIRT_OFIT_PRED alone) */
+    double   lppd, p_waic, elpd_waic, waic, se_elpd_waic;      /* NaN without GPIRT_OFIT_WAIC; se: sqrt(n_obs var(elpd_ij)), ddof 1 */
+    int64_t  reserved[5];                   /* in: 0 */
+} gpirt_ordinal_fit;
+int gpirt_sampler_ordinal_fit_enable(gpirt_sampler_t s, int parts);
+int gpirt_sampler_ordinal_fit_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_ordinal_fit_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ordinal_fit_totals(gpirt_sampler_t s, gpirt_ordinal_fit* out);
+int gpirt_sampler_ordinal_fit_state(gpirt_sampler_t s, void** d_block, int64_t* bytes);
+int gpirt_ordinal_fit_combine(gpirt_handle_t h, const void* const* d_states, int chains, void* d_out);
+int gpirt_ordinal_fit_get(gpirt_handle_t h, const void* d_block, const char* name, void* h_out, int64_t bytes);
+int gpirt_ordinal_fit_totals(gpirt_handle_t h, const void* d_block, gpirt_ordinal_fit* out);
 
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
