@@ -667,6 +667,7 @@ SIGNATURES = {
     "gpirt_gemm": (_i32, [_vp, _i32, _i32, _i64, _i64, _i64, _dbl, _vp, _i64, _vp, _i64, _dbl, _vp, _i64]),
     "gpirt_ll_bar": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     "gpirt_draw_f": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u64, _u32, _vp]),
+    "gpirt_draw_f_linear": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _u64, _u32, _vp]),
     "gpirt_draw_fstar": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _u64, _u32, _i32, _vp, _vp, _vp]),
     "gpirt_draw_theta": (_i32, [_vp, _vp, _vp, _i64, _i64, _u64, _u32, _i32, _vp, _vp]),
     "gpirt_draw_beta": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _u64, _u32]),
@@ -816,6 +817,7 @@ SIGNATURES = {
     "gpirt_sampler_panel_copy_part": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32]),
     "gpirt_sampler_ldl": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_nu_lr_draws": (_i32, [_vp, C.POINTER(_i64)]),
+    "gpirt_sampler_ess_pack_draws": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_nu_lr_rows": (_i32, [_vp, _vp, _i64]),
     "gpirt_sampler_fstar_free_draws": (_i32, [_vp, C.POINTER(_i64)]),
     "gpirt_sampler_factor_lr_count": (_i32, [_vp, C.POINTER(_i64)]),

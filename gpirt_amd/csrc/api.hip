@@ -45,6 +45,7 @@ const Config& env_config()
         d.flr_narrow = env_value("GPIRT_FLR_NARROW", d.flr_narrow);
         d.beta_screen = env_value("GPIRT_BETA_SCREEN", d.beta_screen);
         d.zfill_compact = env_value("GPIRT_ZFILL_COMPACT", d.zfill_compact);
+        d.ess_pack = env_value("GPIRT_ESS_PACK", d.ess_pack);
         if (d.nbo < 64) d.nbo = 1024;
         if (d.nbp != 0 && d.nbp < 64) d.nbp = 512;          // (0 = by size: potrf_subpanel_width)
         return d;
@@ -170,7 +171,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 142; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 143; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -254,6 +255,8 @@ int gpirt_version(void) { return 142; }   // 101: gpirt_options names kernel_fp3
                                             // 140: the structured factor's parts as narrow as draw_f's product reads them, part / 64 rounds instead
                                             //      of eight (factor_lr.hip: GPIRT_FLR_NARROW, gpirt_sampler_factor_lr_width,
                                             //      gpirt_sampler_factor_lr_blocks); the parts and node rows change in rounding only
+                                            // 143: draw_f's slice kernel of 2048 < n <= 8192 with y packed and mu formed again from theta and
+                                            //      beta (ess_lin.hip: GPIRT_ESS_PACK, gpirt_draw_f_linear, gpirt_sampler_ess_pack_draws); bit for bit
 
 const char* gpirt_last_error(void) { return g_err; }
 
@@ -391,6 +394,7 @@ static int* config_slot(gpirt_handle_t h, const char* name, bool* read_only)
         { "GPIRT_FLR_NARROW", &h->cfg.flr_narrow, false },
         { "GPIRT_BETA_SCREEN", &h->cfg.beta_screen, false },
         { "GPIRT_ZFILL_COMPACT", &h->cfg.zfill_compact, false },
+        { "GPIRT_ESS_PACK", &h->cfg.ess_pack, false },
     };
     for (auto& e : tab)
         if (strcmp(e.k, name) == 0) { if (read_only) *read_only = e.ro; return e.p; }
@@ -774,6 +778,42 @@ int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double*
     GP_HIP(hipMemcpyAsync(h->h_info, err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     GP_HIP(hipStreamSynchronize(h->stream));
     if (*h->h_info != 0) { set_error("draw_f: elliptical slice sampler did not terminate"); return GPIRT_E_NUMERIC; }
+    return 0;
+}
+
+// gpirt_draw_f with mu = b0 + theta b1 given by its parts: y is packed and the slice kernel forms mu itself (ess_lin.hip).
+// Same Z, same product, same draws as gpirt_draw_f on mu[i + j n] = beta[2 j] + theta[i] * beta[2 j + 1], bit for bit.
+int gpirt_draw_f_linear(gpirt_handle_t h, double* d_f, const double* d_y, const double* d_L, int64_t ldl,
+                        const double* d_theta, const double* d_beta, int64_t n, int64_t m, uint64_t seed, uint32_t iter,
+                        int* d_k_out)
+{
+    GP_ARG(h && d_f && d_y && d_L && d_theta && d_beta && m >= 0 && ldl >= n);
+    if (!ess_pack_eligible(n)) { set_error("draw_f_linear: n = %lld, the packed slice kernel takes 2048 < n <= 8192", (long long)n); return GPIRT_E_ARG; }
+    // workspace: Z (n x m) | NU (n x m) | err, bad y | the packed y (512 m words)
+    const size_t nm = (size_t)n * (size_t)m;
+    GP_TRY(ensure_work(h, (2 * nm + 8) * sizeof(double) + 512 * (size_t)m * sizeof(uint32_t)));
+    double* Z = h->d_work;
+    double* NU = Z + nm;
+    int* err = reinterpret_cast<int*>(NU + nm);
+    uint32_t* ypk = reinterpret_cast<uint32_t*>(NU + nm + 8);
+    GP_HIP(hipMemsetAsync(err, 0, 2 * sizeof(int), h->stream));
+    GP_TRY(launch_check_y(h->stream, d_y, (int64_t)nm, err + 1));
+    GP_HIP(hipMemcpyAsync(h->h_info, err + 1, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GP_HIP(hipStreamSynchronize(h->stream));
+    if (*h->h_info != 0) { set_error("draw_f_linear: y must be +1, -1 or NaN (a missing response)"); return GPIRT_E_ARG; }
+    GP_TRY(launch_ess_pack(h->stream, d_y, n, m, ypk));
+    GP_TRY(launch_item_uniforms(h->stream, seed, iter, GPIRT_ST_F_Z, 0, m, n, Z, true, h->cfg.zfill_compact == 1));
+    GP_TRY(launch_gemm(h, h->stream, false, false, TRI_A_LOWER, n, m, n, 1.0, d_L, ldl, Z, n, 0.0, NU, n));
+    EssArgs a{};
+    a.f = d_f; a.nu = NU; a.n = n; a.m = m; a.k_out = d_k_out; a.err = err;
+    a.seed = seed; a.iter = iter; a.item0 = 0;
+    a.ll_exact = h->cfg.ll_exact; a.screen = h->cfg.ess_screen == 1;
+    a.ypk = ypk; a.theta = d_theta; a.beta = d_beta;
+    a.grid = h->cfg.ess_pack == 3 ? 2 * h->n_cu : 0;
+    GP_TRY(launch_ess(h->stream, a));
+    GP_HIP(hipMemcpyAsync(h->h_info, err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    GP_HIP(hipStreamSynchronize(h->stream));
+    if (*h->h_info != 0) { set_error("draw_f_linear: elliptical slice sampler did not terminate"); return GPIRT_E_NUMERIC; }
     return 0;
 }
 

@@ -94,6 +94,9 @@ struct Config {
                                   //   reads them (GPIRT_NU_SUB), 2 = always 512 wide, 3 = GPIRT_NU_SUB wide at every eligible n
     int  beta_screen = 1;         // GPIRT_BETA_SCREEN: 1 = draw_beta from registers, its accept tests decided by the single-precision screen where
                                   //   that is safe (stages.hip draw_beta_reg_kernel; item RNG, n <= 8192), 2 = always draw_beta_kernel
+    int  ess_pack = 1;            // GPIRT_ESS_PACK: 1 = draw_f's slice kernel of 2048 < n <= 8192 reads y as one packed word per lane and forms mu
+                                  //   again from theta and beta where the sampler knows mu = b0 + theta b1 (ess_lin.hip), one work-group per item;
+                                  //   3 = the same kernel, two work-groups per CU striding over the items; 2 = always the kernel that reads y and mu
     int  zfill_compact = 1;       // GPIRT_ZFILL_COMPACT: 1 = the normal fills evaluate AS241's tail branch on a compacted list (rng_ess.hip
                                   //   item_fill_normal_kernel), 2 = item_fill_kernel
     int  rs_predict = 1;          // GPIRT_RS_PREDICT: 2 = the R-stream replay's draw_f runs every pass over L in fp64 (one phase, rng_ess.hip)

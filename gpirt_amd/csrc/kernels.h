@@ -305,8 +305,19 @@ struct EssArgs {
     const double* U; uint64_t* pos; uint64_t cap;
     int ll_exact;         // 1: log(1 + exp(-a)) through the library's exp and log, as written (GPIRT_LL_EXACT)
     int screen;           // 1: the register kernels decide a trial point by the single-precision screen where it can (ll_fast.h)
+    // packed y and mu = b0 + theta b1 recomputed (ypk != null; item RNG, 2048 < n <= 8192: ess_kernel_lin).
+    // y and mu are then not read; any other n or an R-stream replay is an argument error
+    const uint32_t* ypk;  // launch_ess_pack's words, 512 per item
+    const double* theta;  // [n]
+    const double* beta;   // [2 m]: b0, b1 of item j at 2 j
+    int grid;             // work-groups of that kernel, each striding over the items (<= 0 or > m: one per item)
 };
 int launch_ess(hipStream_t stream, const EssArgs& a);
+// y (n x m, +1 / -1 / NaN) as ess_kernel_lin reads it: one word per (item, lane of 512), bit e = row lane + 512 e is observed,
+// bit 16 + e = it is negative; rows >= n are not observed.  512 m words.  ess_pack_eligible: the n the packed kernel takes.
+inline bool ess_pack_eligible(int64_t n) { return n > 2048 && n <= 8192; }
+int launch_ess_pack(hipStream_t stream, const double* y, int64_t n, int64_t m, uint32_t* out);
+int launch_ess_lin(hipStream_t stream, const EssArgs& a);     // (launch_ess calls it where a.ypk is set)
 // R-stream replay of draw_f, three items per pass over L (rng_ess.hip; sampler.hip, do_draw_f)
 constexpr int RS_KC = 512;           // columns of L per part of a candidate product (one work-group: four waves x 128 columns)
 constexpr int RS_ROWS = 32;          // rows of L per work-group of a candidate product

@@ -1022,6 +1022,7 @@ int launch_ess(hipStream_t stream, const EssArgs& a)
     if (a.m <= 0) return 0;
     // a.ll_exact (GPIRT_LL_EXACT=1): log(1 + exp(-a)) through the library in every mode
     const bool fast = a.U == nullptr && a.ll_exact != 1;
+    if (a.ypk) return launch_ess_lin(stream, a);              // (ess_lin.hip)
     if (a.U == nullptr && a.n <= 256 * 8) {
         if (fast) hipLaunchKernelGGL((ess_kernel_reg<8, 256, true>), dim3((unsigned)a.m), dim3(256), 0, stream, a);
         else      hipLaunchKernelGGL((ess_kernel_reg<8, 256, false>), dim3((unsigned)a.m), dim3(256), 0, stream, a);

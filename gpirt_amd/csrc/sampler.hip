@@ -342,6 +342,14 @@ struct gpirt_sampler_s {
     // logpost (N x n) is theta_partial's product for the fstar, beta and population prior in place: set by theta_partial, kept
     // by gpirt_sampler_draw_scale, cleared by every writer of fstar, beta, f, theta or the population prior's table
     bool lp_current = false;
+    // mu_linear: mu was last written as b0 + theta b1 (one multiply, one add) from the theta and beta that are still in place, so
+    // the slice kernel may form it again instead of reading it (ess_lin.hip; DESIGN.md section 51 lists who sets and who clears
+    // it).  ess_ypk: y as that kernel reads it (launch_ess_pack), built at creation and again behind a caller's write to y;
+    // ess_pack_draws: draws that took that kernel so far
+    bool mu_linear = false;
+    uint32_t* ess_ypk = nullptr;
+    bool ess_ypk_valid = false;
+    int64_t ess_pack_draws = 0;
 };
 
 namespace {
@@ -729,6 +737,14 @@ int do_draw_f(gpirt_sampler_s* s)
         a.err = s->flags; a.seed = s->opt.seed; a.iter = iter; a.item0 = (uint32_t)s->opt.item0;
         a.ll_exact = h->cfg.ll_exact;
         a.screen = h->cfg.ess_screen == 1;
+        // y packed and mu formed again from theta and beta (ess_lin.hip) where mu is known to be b0 + theta b1 of the theta and
+        // beta in place; GPIRT_ESS_PACK=2, kernel_fp32 or any other n: the kernel that reads mu and y
+        if (h->cfg.ess_pack != 2 && s->mu_linear && s->ess_ypk && !s->opt.kernel_fp32 && ess_pack_eligible(n)) {
+            if (!s->ess_ypk_valid) { GP_TRY(launch_ess_pack(st, s->y, n, m, s->ess_ypk)); s->ess_ypk_valid = true; }
+            a.ypk = s->ess_ypk; a.theta = s->theta; a.beta = s->beta;
+            a.grid = h->cfg.ess_pack == 3 ? 2 * h->n_cu : 0;      // (3: two work-groups per CU stride over the items)
+            s->ess_pack_draws += 1;
+        }
         GP_TRY(launch_ess(st, a));
         }
         if (prep) {
@@ -1076,6 +1092,7 @@ int do_theta_finish(gpirt_sampler_s* s)
     GP_TRY(launch_theta_sample(st, a));
     if (stream_mode(s)) GP_TRY(launch_advance_pos(st, s->pos, (uint64_t)s->n));
     s->lp_current = false;
+    s->mu_linear = false;                 // (theta moved: mu is the old theta's until draw_beta has run)
     s->theta_ok = true;                   // grid values
     return 0;
 }
@@ -1110,6 +1127,7 @@ int do_theta_block(gpirt_sampler_s* s)
 int launch_beta_on(gpirt_sampler_s* s, hipStream_t st)
 {
     s->lp_current = false;
+    s->mu_linear = !s->ord.on;                                    // (draw_beta_kernel and draw_beta_reg_kernel store mu = b0 + theta_i b1)
     if (s->ord.on) {                                              // (the slope alone: the intercept is pinned at 0)
         BetaOrdArgs a{};
         a.beta = s->beta; a.theta = s->theta; a.cat = s->ord.cat; a.f = s->f; a.thr = s->ord.thr; a.pm = s->pm; a.ps = s->ps;
@@ -1174,6 +1192,7 @@ int do_carry_f(gpirt_sampler_s* s, int nugget, bool timed)
     // a draw_beta still held back or running on the sampler's own stream reads the f this stage rewrites (inside a step: none)
     GP_TRY(beta_sync(s));
     s->lp_current = false;
+    s->mu_linear = false;
     if (!c.counters) {
         GP_TRY(dalloc(s, &c.counters, 6));
         GP_HIP(hipMemsetAsync(c.counters, 0, 6 * sizeof(unsigned long long), st));
@@ -1985,6 +2004,10 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     }
     GP_A(s->pm, 2 * m);      GP_A(s->ps, 2 * m);       GP_A(s->step, 2 * m);
     GP_A(s->ess_k, m);       GP_A(s->flags, 4);
+    if (!stream_mode(s) && ess_pack_eligible(n)) {       // (y as ess_kernel_lin reads it: 512 words per item)
+        rc = dalloc(s, &s->ess_ypk, (size_t)(512 * m), false);
+        if (rc) { gpirt_sampler_destroy(s); return rc; }
+    }
     if (!s->opt.fstar_fused) GP_A(s->kstar, n * N + 2);
     if (s->node_off >= 0) {
         GP_A(s->nu_nodes, NU_LR_RANK); GP_A(s->nu_wts, NU_LR_RANK);
@@ -2154,6 +2177,7 @@ int gpirt_sampler_create(gpirt_sampler_t* out, gpirt_handle_t h, const double* h
     hipMemsetAsync(s->ess_k, 0, sizeof(int) * (size_t)m, st);
     launch_indicators(st, s->y, n, m, s->Ypm);
     launch_tf_indicators(st, s->y, n, n, m, s->tfd, s->tf_y8);
+    if (s->ess_ypk) { launch_ess_pack(st, s->y, n, m, s->ess_ypk); s->ess_ypk_valid = true; }
     if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
         set_error("sampler upload failed"); gpirt_sampler_destroy(s); return GPIRT_E_HIP;
     }
@@ -2308,6 +2332,7 @@ int gpirt_sampler_init(gpirt_sampler_t s)
         GP_HIP(hipStreamSynchronize(st));
     }
     GP_TRY(launch_linear_mean(st, s->theta, n, s->beta, m, s->mu));               // :30-33
+    s->mu_linear = true;
     GP_TRY(launch_linear_mean(st, s->tstar, N, s->beta, m, s->mu_star));          // :37-40
     GP_TRY(do_draw_fstar(s, 0));                                                  // :41
     if (stream_mode(s)) {
@@ -2389,6 +2414,7 @@ int gpirt_sampler_theta_commit(gpirt_sampler_t s)
     GP_ARG(s && s->initialised && s->theta_stage);
     GP_HIP(hipMemcpyAsync(s->theta, s->theta_stage, sizeof(double) * (size_t)s->n, hipMemcpyDeviceToDevice, s->h->stream));
     s->lp_current = false;
+    s->mu_linear = false;
     s->theta_ok = true;                   // the ranks' blocks of grid values, summed
     return 0;
 }
@@ -3723,6 +3749,7 @@ int gpirt_sampler_draw_amp_centred(gpirt_sampler_t s)
     // mu of a held-back draw_beta, and nothing on the sampler's own stream may still read the f this update rewrites in place
     GP_TRY(beta_sync(s));
     s->lp_current = false;
+    s->mu_linear = false;
     GP_TRY(amp_centred_alloc(s));
     GP_TRY(smooth_factor(s));
     AmpCentredArgs a = A.ca;
@@ -3854,6 +3881,7 @@ int gpirt_sampler_draw_beta_centred(gpirt_sampler_t s)
     // a held-back draw_beta writes beta, mu and mu_star, and nothing on the sampler's own stream may still read what this rewrites
     GP_TRY(beta_sync(s));
     s->lp_current = false;
+    s->mu_linear = false;
     GP_TRY(beta_centred_alloc(s));
     GP_TRY(smooth_factor(s));
     BetaCentredArgs a = Bc.a;
@@ -4048,6 +4076,7 @@ static int do_draw_scale(gpirt_sampler_t s, int kind, const char* me, bool timed
         GP_HIP(hipEventRecord(Sc.tev[0], st));
         for (int k = 0; k < 4; ++k) a.kev[k] = Sc.tev[3 + k];
     }
+    s->mu_linear = false;                         // (an accepted move rewrites beta and mu on the device: the host cannot know)
     GP_TRY(launch_scale_curve(st, a));
     if (timed) GP_HIP(hipEventRecord(Sc.tev[1], st));
     GP_TRY(theta_product(s, a.fstar2, a.logpost2));
@@ -4190,6 +4219,7 @@ int gpirt_sampler_pop_set(gpirt_sampler_t s, const int32_t* codes, int G, const 
     GP_ARG(s != nullptr);
     PopState& A = s->pop;
     s->lp_current = false;
+    s->mu_linear = false;
     if (!codes) {
         if (A.mode == 2) { set_error("gpirt_sampler_pop_set(NULL): the population prior is sampled, gpirt_sampler_pop_enable(on = 0) turns it off"); return GPIRT_E_ARG; }
         GP_HIP(hipStreamSynchronize(s->h->stream));
@@ -4232,6 +4262,7 @@ int gpirt_sampler_pop_enable(gpirt_sampler_t s, const int32_t* codes, int G, con
     GP_ARG(s != nullptr);
     PopState& A = s->pop;
     s->lp_current = false;
+    s->mu_linear = false;
     if (!on) {
         if (A.mode == 1) { set_error("gpirt_sampler_pop_enable(on = 0): the population prior is fixed, gpirt_sampler_pop_set(NULL) turns it off"); return GPIRT_E_ARG; }
         GP_HIP(hipStreamSynchronize(s->h->stream));
@@ -4316,6 +4347,7 @@ int gpirt_sampler_draw_pop(gpirt_sampler_t s)
     PopState& A = s->pop;
     GP_TRY(needs(A.mode == 2, "the population prior's update is", "gpirt_sampler_pop_enable"));
     s->lp_current = false;
+    s->mu_linear = false;
     PopUpdateArgs a{};
     a.stats = A.stats; a.mu = A.d_mu; a.sd = A.d_sd; a.P_mu = A.P_mu; a.P_sd = A.P_sd;
     a.hyper_mu = A.d_hyper_mu; a.hyper_sd = A.d_hyper_sd; a.lse = A.d_lse;
@@ -4770,6 +4802,10 @@ int gpirt_sampler_devptr(gpirt_sampler_t s, const char* name, void** d_ptr, int6
 {
     GP_ARG(s && name && d_ptr && count);
     GP_TRY(lookup(s, name, d_ptr, count));
+    // the caller may write through the pointer: what is derived from these arrays is taken as stale from here on (a caller
+    // who writes theta, beta or mu after a later draw_beta asks for the pointer again, or uses gpirt_sampler_set)
+    if (strcmp(name, "theta") == 0 || strcmp(name, "beta") == 0 || strcmp(name, "mu") == 0) s->mu_linear = false;
+    if (strcmp(name, "y") == 0) s->ess_ypk_valid = false;
     if (strcmp(name, "L") == 0) {
         *count = s->ldl * s->n;           // the whole buffer (leading dimension gpirt_sampler_ldl)
         // the caller may read or overwrite any of it: the dense factor now, and a structured factor that follows is not seen
@@ -4817,6 +4853,13 @@ int gpirt_sampler_panel_rows(gpirt_sampler_t s, int64_t* rows)
 
 // draw_f's structured product (nu_lr.hip): how many draws have run it so far, and the 64 node rows below the factor as they
 // stand (64 x n, column-major; GPIRT_E_ARG when the layout carries none)
+int gpirt_sampler_ess_pack_draws(gpirt_sampler_t s, int64_t* draws)
+{
+    GP_ARG(s && draws);
+    *draws = s->ess_pack_draws;
+    return 0;
+}
+
 int gpirt_sampler_nu_lr_draws(gpirt_sampler_t s, int64_t* draws)
 {
     GP_ARG(s && draws);
@@ -4960,6 +5003,7 @@ int gpirt_sampler_copy_state(gpirt_sampler_t dst, gpirt_sampler_t src)
     GP_TRY(ensure_dense_factor(src));     // (dst gets the whole factor)
     dst->L_structured = false;
     dst->lp_current = false;
+    dst->mu_linear = false;
     src->factor_fresh = false;
     invalidate_factor_products(dst);
     GP_HIP(hipMemcpyAsync(dst->theta, src->theta, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
@@ -5011,6 +5055,8 @@ int gpirt_sampler_set(gpirt_sampler_t s, const char* name, const double* h_in, i
     GP_TRY(aux_join(s));
     invalidate_factor_products(s);
     s->lp_current = false;
+    if (strcmp(name, "theta") == 0 || strcmp(name, "beta") == 0 || strcmp(name, "mu") == 0) s->mu_linear = false;
+    if (strcmp(name, "y") == 0) s->ess_ypk_valid = false;       // (packed again by the next draw_f that reads it)
     if (strcmp(name, "L") == 0 || strcmp(name, "theta") == 0) s->rows_valid = false;
     if (strcmp(name, "L") == 0) s->theta_alone = false;          // (taken as the factor of K(theta, theta) for the theta in place)
     if (strcmp(name, "L") == 0) {
@@ -5328,6 +5374,7 @@ static int mcmc_run(const double* h_y, int64_t n, int64_t m, const double* h_the
             d += even(pt.cnt);
         }
         if (hipMemsetAsync(s->flags, 0, 4 * sizeof(int), st) != hipSuccess) return fail_hip("rollback");
+        s->mu_linear = false;
         s->iter = k;
         return recover_factor(s);
     };

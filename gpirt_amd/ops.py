@@ -287,6 +287,14 @@ class Handle:
         check(self.lib.gpirt_draw_f(self._h, _p(f), _p(y), _p(L), _ld(L), _p(mu), n, m, seed, it, _p(k)))
         return f, k
 
+    def draw_f_linear(self, f, y, L, theta, beta, seed: int, it: int):
+        """draw_f() on mu = beta[0, j] + theta * beta[1, j], given by its parts: y packed, mu formed inside the slice kernel
+        (csrc/ess_lin.hip; 2048 < n <= 8192).  beta: 2 x m, column-major.  In place on f; returns (f, rejections)."""
+        n, m = f.shape
+        k = torch.zeros(m, dtype=torch.int32, device=f.device)
+        check(self.lib.gpirt_draw_f_linear(self._h, _p(f), _p(y), _p(L), _ld(L), _p(theta), _p(beta), n, m, seed, it, _p(k)))
+        return f, k
+
     def draw_fstar(self, f, theta, L, mu_star, seed: int, it: int, fused: bool = False):
         """draw_fstar(): src/draw-fstar.cpp:10-31 (item RNG).  Returns (fstar, s, mean)."""
         n, m = f.shape

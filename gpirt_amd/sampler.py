@@ -783,6 +783,13 @@ class Sampler:
         return r.value
 
     @property
+    def ess_pack_draws(self) -> int:
+        """draws of draw_f whose slice kernel read the packed y and formed mu from theta and beta (csrc/ess_lin.hip)"""
+        r = C.c_int64()
+        check(self.lib.gpirt_sampler_ess_pack_draws(self._s, C.byref(r)))
+        return r.value
+
+    @property
     def fstar_free_draws(self) -> int:
         """draw_fstar calls that took C = S^-1 K(theta, c) from theta alone, without the solve through L (csrc/fstar_free.hip)"""
         r = C.c_int64()

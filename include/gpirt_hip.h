@@ -264,6 +264,19 @@ int gpirt_draw_f(gpirt_handle_t h, double* d_f, const double* d_y, const double*
                  const double* d_mu, int64_t n, int64_t m, uint64_t seed, uint32_t iter,
                  int* d_k_out);
 
+/* Library version 143.  gpirt_draw_f for a linear mean given by its parts: mu[i + j n] = d_beta[2 j] + d_theta[i] * d_beta[2 j + 1]
+ * (one multiply, one add).  y is packed to two bits a cell and the slice kernel forms mu itself (csrc/ess_lin.hip, DESIGN.md
+ * section 51); f, the rejection counts and the error code are gpirt_draw_f's on that mu, bit for bit.  2048 < n <= 8192, any
+ * other n is GPIRT_E_ARG.  Inside a sampler the same kernel runs under GPIRT_ESS_PACK (gpirt_config_set): 1 (the default)
+ * where the sampler knows that mu is b0 + theta b1 of the theta and beta in place (written last by draw_beta or at
+ * initialisation; any entry that writes theta, beta or mu another way sends the next draw_f to the kernel that reads mu and
+ * y), one work-group per item; 3 the same with two work-groups per CU striding over the items; 2 never.
+ * gpirt_sampler_ess_pack_draws: how many draws of this sampler took the packed kernel. */
+int gpirt_draw_f_linear(gpirt_handle_t h, double* d_f, const double* d_y, const double* d_L, int64_t ldl,
+                        const double* d_theta, const double* d_beta, int64_t n, int64_t m, uint64_t seed,
+                        uint32_t iter, int* d_k_out);
+int gpirt_sampler_ess_pack_draws(gpirt_sampler_t s, int64_t* draws);
+
 /* draw_fstar(): src/draw-fstar.cpp:10-31 under GPIRT_RNG_ITEM.  d_out (N x m), N = GPIRT_NGRID.
  * fused = 0: alpha = L^-T L^-1 f as in the reference (double_solve, :3-8);
  * fused = 1: mean = (L^-1 kstar)^T (L^-1 f), algebraically identical, one trsm fewer.
