@@ -901,6 +901,13 @@ SIGNATURES = {
     "gpirt_ordinal_fit_combine": (_i32, [_vp, C.POINTER(_vp), _i32, _vp]),
     "gpirt_ordinal_fit_get": (_i32, [_vp, _vp, C.c_char_p, _vp, _i64]),
     "gpirt_ordinal_fit_totals": (_i32, [_vp, _vp, C.POINTER(OrdinalFit)]),
+    "gpirt_sampler_ordinal_score_enable": (_i32, [_vp, C.POINTER(C.c_int8), _i64, _i32, _i32]),
+    "gpirt_sampler_ordinal_score_accumulate": (_i32, [_vp]),
+    "gpirt_sampler_ordinal_score_get": (_i32, [_vp, C.c_char_p, _vp, _i64]),
+    "gpirt_sampler_ordinal_score_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_sampler_ordinal_score_predict_state": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "gpirt_ordinal_score_combine": (_i32, [_vp, _i32, C.POINTER(_vp), C.POINTER(_i32), _vp, _i64]),
+    "gpirt_ordinal_score_predict_combine": (_i32, [_vp, _i32, C.POINTER(_vp), _vp, _i64]),
     "gpirt_sampler_carry_f": (_i32, [_vp, _i32]),
     "gpirt_sampler_step_consistent": (_i32, [_vp, _i32]),
     "gpirt_sampler_carry_stats": (_i32, [_vp, C.POINTER(Carry)]),

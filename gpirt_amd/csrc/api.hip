@@ -171,7 +171,7 @@ int prof_pair_end(gpirt_handle_t h, hipStream_t stream, ProfPair& pp, int cls, d
 
 extern "C" {
 
-int gpirt_version(void) { return 143; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
+int gpirt_version(void) { return 144; }   // 101: gpirt_options names kernel_fp32 / kstar_rank, gpirt_fast_options;
                                             // 102: gpirt_potrf_subpanel_width takes the order of the matrix, gpirt_debug_theta_*
                                             // 103: gpirt_debug_poison_allocs; draw_f and the sampler refuse y outside {+1, -1, NaN}
                                             // 104: posterior summaries (gpirt_sampler_summary_*, gpirt_mcmc_summary, summary.hip)
@@ -257,6 +257,10 @@ int gpirt_version(void) { return 143; }   // 101: gpirt_options names kernel_fp3
                                             //      gpirt_sampler_factor_lr_blocks); the parts and node rows change in rounding only
                                             // 143: draw_f's slice kernel of 2048 < n <= 8192 with y packed and mu formed again from theta and
                                             //      beta (ess_lin.hip: GPIRT_ESS_PACK, gpirt_draw_f_linear, gpirt_sampler_ess_pack_draws); bit for bit
+                                            // 144: scoring new respondents under ordinal responses: theta posterior, lpd, category predictions and
+                                            //      the next item (ordinal_score.hip, sampler.hip: gpirt_sampler_ordinal_score_enable / _accumulate /
+                                            //      _get / _state / _predict_state, gpirt_ordinal_score_combine, gpirt_ordinal_score_predict_combine);
+                                            //      stage API only, every existing kernel's output is unchanged
 
 const char* gpirt_last_error(void) { return g_err; }
 

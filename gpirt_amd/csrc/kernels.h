@@ -234,6 +234,44 @@ int ofit_block_get(hipStream_t stream, const void* d_block, const char* name, vo
 int ofit_last_get(hipStream_t stream, OfitState* p, const char* name, void* h_out, int64_t bytes);   // 1: not a last-draw name
 int ofit_block_totals(hipStream_t stream, const void* d_block, gpirt_ordinal_fit* out);
 int ofit_combine(gpirt_handle_t h, const void* const* d_states, int chains, void* d_out);
+// ordinal_score.hip: scoring respondents who were not in the fit under ordinal responses, and their category predictions
+// (gpirt_sampler_ordinal_score_*).  Two device blocks of 8-byte words, each with a header of OSCORE_HEADER_WORDS int64.
+//   score:    (OSCORE_TAG, layout version, n_new, m, C, N, 0, 0), int64 draws[n_new], nonfinite[n_new], n_obs[n_new], double
+//             lpd_acc[n_new] (starts at -inf), ll_sum[n_new], post_sum[n_new][N] (k fastest)
+//   predict:  (OSPRED_TAG, layout version, n_new, m, C, N, pred_draws, pred_skipped -- the two counters are the epilogue kernel's),
+//             the answered-mask of cat_new packed 64 cells a word (cell g = r + j n_new), double prob_sum[C][m][n_new] and
+//             info_sum[m][n_new] (r fastest)
+// Beside them: the one-hot Y (n_new x C m), the block's OWN table G (Np x C m, Np = 1024), the product T (N x n_new), the cleaned
+// f*, the w table (m x C) and Wc (n_new) of the last draw; with predict the weights W (Np x n_new), the operand table
+// B = [P_1 | ... | P_C | Hc] (Np x (C + 1) m) and the product W^T B (n_new x (C + 1) m).
+constexpr int OSCORE_LAYOUT_VERSION = 1;
+constexpr int OSCORE_HEADER_WORDS = 8;
+constexpr int64_t OSCORE_TAG = 0x5243534F;            // "OSCR"
+constexpr int64_t OSPRED_TAG = 0x5250534F;            // "OSPR"
+struct OscoreState {
+    bool on = false, pred_on = false;
+    int64_t n = 0, m = 0;
+    int C = 0;
+    uint64_t *block = nullptr, *pblock = nullptr;
+    int8_t* cat = nullptr;                            // device: n_new x m
+    double *Y = nullptr, *G = nullptr, *T = nullptr, *fclean = nullptr, *logprior = nullptr, *wtab = nullptr, *Wc = nullptr;
+    double *W = nullptr, *B = nullptr, *Cm = nullptr; // predict only
+    int* flags = nullptr;                             // [0] a NaN in this draw's f*, [1 + j] in item j, [1 + m + r] r answered one
+    int* go = nullptr;                                // predict: 1 when this draw's f* holds no NaN
+    double lse_prior = 0.0;
+    std::vector<void*> allocs;
+};
+int64_t oscore_state_words(const OscoreState* s);
+int64_t oscore_pred_state_words(const OscoreState* s);
+// refuses n_new outside 1..GPIRT_SCORE_MAX_N and a value outside 0..C before anything is allocated; h_cat_new: n_new x m, column-major
+int oscore_alloc(hipStream_t stream, OscoreState* s, const int8_t* h_cat_new, int64_t n_new, int64_t m, int C, bool predict);
+void oscore_free(OscoreState* s);
+// one draw: fstar (N x m) and thr (m x (C - 1)) on the device
+int launch_oscore_accumulate(gpirt_handle_t h, hipStream_t stream, OscoreState* s, const double* fstar, const double* thr);
+int oscore_get(hipStream_t stream, OscoreState* s, const char* name, void* h_out, int64_t bytes);
+// pools `chains` blocks into the host block h_out (the same layout; bytes: its size); signs (score only): -1 reverses the grid axis
+int oscore_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, void* h_out, int64_t bytes);
+int oscore_pred_combine(gpirt_handle_t h, int chains, const void* const* d_states, void* h_out, int64_t bytes);
 // carry.hip: the consistent step's carry stage (gpirt_sampler_carry_f) and the prior check's reduction (gpirt_sampler_prior_quad)
 struct CarryArgs {
     double* f; const double* theta; const double* fstar; const double* mu_star; int64_t n, m, N;       // f: n x m; fstar, mu_star: N x m

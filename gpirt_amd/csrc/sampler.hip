@@ -131,6 +131,7 @@ struct OrdState {
     hipEvent_t tev[2] = {};
     double last_ms = 0.0;
     OfitState fit;                    // the fit output (gpirt_sampler_ordinal_fit_enable, ordinal_fit.hip; on == false: off)
+    OscoreState score;                // scoring new respondents (gpirt_sampler_ordinal_score_enable, ordinal_score.hip; on == false: off)
 };
 
 // F of the rank-64 smooth part, Kcc = F F^T (fstar_free_factor) with its DEAD columns (squared norm <= 1e-13) zeroed on the host,
@@ -1476,6 +1477,7 @@ void ord_free(OrdState* p)
 {
     const uint32_t calls = p->t;      // the sampler's draw_thresholds calls: enabling again does not replay their uniforms
     ofit_free(&p->fit);
+    oscore_free(&p->score);
     for (void* q : { (void*)p->cat, (void*)p->d_grid, (void*)p->d_log_prior, (void*)p->thr, (void*)p->lp, (void*)p->cum, (void*)p->Y,
                      (void*)p->G, (void*)p->idx, (void*)p->window, (void*)p->counts, (void*)p->stat, (void*)p->hist, (void*)p->draws })
         if (q) hipFree(q);
@@ -4731,6 +4733,82 @@ int gpirt_ordinal_fit_totals(gpirt_handle_t h, const void* d_block, gpirt_ordina
 {
     GP_ARG(h && d_block && out);
     return ofit_block_totals(h->stream, d_block, out);
+}
+
+// ---- scoring new respondents under ordinal responses (ordinal_score.hip) ----------------------------------------------------------
+int gpirt_sampler_ordinal_score_enable(gpirt_sampler_t s, const int8_t* cat_new, int64_t n_new, int predict, int top)
+{
+    GP_ARG(s != nullptr);
+    const char* me = "gpirt_sampler_ordinal_score_enable";
+    if (!s->initialised) { set_error("%s needs an initialised sampler (gpirt_sampler_init)", me); return GPIRT_E_ARG; }
+    OrdState& A = s->ord;
+    if (!cat_new || n_new == 0)
+        return stage_enable(s, &A.score, oscore_free, false, [] { return 0; });
+    GP_TRY(needs(A.on, "ordinal responses are", "gpirt_sampler_ordinal_enable"));
+    if (n_new < 1 || n_new > GPIRT_SCORE_MAX_N) {        // refused before the old state goes, as every refusal here
+        set_error("ordinal scoring: n_new = %lld is outside 1..%d", (long long)n_new, GPIRT_SCORE_MAX_N);
+        return GPIRT_E_ARG;
+    }
+    if (predict) GP_TRY(check_top("ordinal scoring", top, GPIRT_PREDICT_MAX_TOP));
+    for (int64_t g = 0; g < n_new * s->m; ++g)
+        if (cat_new[g] < 0 || cat_new[g] > A.C) {
+            set_error("ordinal scoring: cat_new[%lld, %lld] = %d, it must lie in 0 .. C = %d (0 = missing)", (long long)(g % n_new),
+                      (long long)(g / n_new), (int)cat_new[g], A.C);
+            return GPIRT_E_ARG;
+        }
+    return stage_enable(s, &A.score, oscore_free, true,
+                        [&] { return oscore_alloc(s->h->stream, &A.score, cat_new, n_new, s->m, A.C, predict != 0); });
+}
+
+#define OSCORE_NEEDS(A) needs((A).on && (A).score.on, "ordinal scoring is", "gpirt_sampler_ordinal_score_enable")
+
+int gpirt_sampler_ordinal_score_accumulate(gpirt_sampler_t s)
+{
+    GP_ARG(s && s->initialised);
+    OrdState& A = s->ord;
+    GP_TRY(OSCORE_NEEDS(A));
+    return launch_oscore_accumulate(s->h, s->h->stream, &A.score, s->fstar, A.thr);
+}
+
+int gpirt_sampler_ordinal_score_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes)
+{
+    GP_ARG(s && name && h_out && bytes >= 0);
+    OrdState& A = s->ord;
+    GP_TRY(OSCORE_NEEDS(A));
+    return oscore_get(s->h->stream, &A.score, name, h_out, bytes);
+}
+
+int gpirt_sampler_ordinal_score_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    OrdState& A = s->ord;
+    GP_TRY(OSCORE_NEEDS(A));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    *d_state = A.score.block;
+    *bytes = oscore_state_words(&A.score) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_sampler_ordinal_score_predict_state(gpirt_sampler_t s, void** d_state, int64_t* bytes)
+{
+    GP_ARG(s && d_state && bytes);
+    OrdState& A = s->ord;
+    GP_TRY(OSCORE_NEEDS(A));
+    GP_TRY(needs(A.score.pred_on, "ordinal prediction is", "gpirt_sampler_ordinal_score_enable with predict = 1"));
+    GP_HIP(hipStreamSynchronize(s->h->stream));
+    *d_state = A.score.pblock;
+    *bytes = oscore_pred_state_words(&A.score) * (int64_t)sizeof(uint64_t);
+    return 0;
+}
+
+int gpirt_ordinal_score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, void* h_out, int64_t bytes)
+{
+    return oscore_combine(h, chains, d_states, signs, h_out, bytes);
+}
+
+int gpirt_ordinal_score_predict_combine(gpirt_handle_t h, int chains, const void* const* d_states, void* h_out, int64_t bytes)
+{
+    return oscore_pred_combine(h, chains, d_states, h_out, bytes);
 }
 
 int gpirt_sampler_iteration(gpirt_sampler_t s, int* iter)

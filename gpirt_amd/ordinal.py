@@ -769,10 +769,328 @@ def fit_from_draws(cat, g_draws, threshold_draws, seed, iters, item0=0, stage=ST
     return out
 
 
+# --------------------------------------------------------------------------------------- scoring new respondents ----
+# (include/gpirt_hip.h "scoring new respondents under ordinal responses", csrc/ordinal_score.hip; library
+# version 144) the theta posterior, the predictive density, the category predictions and the next item of respondents who were not
+# in the fit.  `score_from_draws` / `predict_from_draws` are the NumPy statement over stored f* and threshold draws,
+# `score_combine` / `score_predict_combine` pool chains' state blocks and finish them with gpirt_amd.score's functions.
+SCORE_TAG, SCORE_PREDICT_TAG = 0x5243534F, 0x5250534F          # "OSCR", "OSPR"
+SCORE_HELD = 1e300        # the finite value a term of -inf is held at (csrc/ordinal.hip ord_loglik_terms_kernel)
+
+
+def check_cat_new(cat_new, m=None, C=None) -> np.ndarray:
+    """cat_new as an (n_new, m) int8 array; ValueError for a size outside 1..16384, another width than m or (with C) a value
+    outside 0 .. C."""
+    from .score import SCORE_MAX_N
+    c = np.asarray(cat_new)
+    if c.ndim == 1:
+        c = c[None, :]
+    if c.ndim != 2:
+        raise ValueError("cat_new must be n_new x m")
+    if not 1 <= c.shape[0] <= SCORE_MAX_N:
+        raise ValueError(f"n_new = {c.shape[0]} is outside 1..{SCORE_MAX_N}")
+    if m is not None and c.shape[1] != int(m):
+        raise ValueError(f"cat_new has {c.shape[1]} item columns, the sampler has {int(m)}: cat_new must be coded over the "
+                         "sampler's items")
+    ci = np.asarray(c, dtype=np.int64)
+    if C is not None and not np.all((ci >= 0) & (ci <= int(C))):
+        raise ValueError(f"cat_new must lie in 0 .. C = {int(C)} (0 = missing)")
+    return ci.clip(-128, 127).astype(np.int8)
+
+
+def score_product(cat_new, fstar, B) -> np.ndarray:
+    """T (1001, n_new) of one f* draw (1001, m) and its thresholds B (m x (C - 1) values): per (k, r) the sum over r's observed
+    cells of `theta_logpost_exact`'s terms in long double, rounded once.  A term of -inf (f* = +-inf) is held at -1e300, as the
+    device's table holds it; NaN only where r answered an item whose cell is NaN."""
+    cat = np.asarray(cat_new)
+    fs = np.asarray(fstar, dtype=np.float64).astype(LD)
+    B = np.asarray(B, dtype=np.float64)
+    N, m = fs.shape
+    Cn = B.shape[1] + 1
+    T = np.zeros((N, cat.shape[0]), dtype=LD)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for j in range(m):
+            for c in range(1, Cn + 1):
+                who = cat[:, j] == c
+                if who.any():
+                    col = loglik(np.full(N, c), fs[:, j], B[j], False, LD)
+                    col = np.where(col == -np.inf, LD(-SCORE_HELD), col)
+                    T[:, who] += col[:, None]
+    return T.astype(np.float64)
+
+
+def score_w(cat_new, B) -> np.ndarray:
+    """Wc (n_new): per respondent the sum over the observed cells with 1 < c < C of w(b_c - b_{c-1}), in long double, rounded once."""
+    cat = np.asarray(cat_new)
+    Bl = np.asarray(B, dtype=np.float64).astype(LD)
+    Cn = Bl.shape[1] + 1
+    out = np.zeros(cat.shape[0], dtype=LD)
+    for c in range(2, Cn):
+        wc = w(Bl[:, c - 1] - Bl[:, c - 2])
+        out += ((cat == c) * wc[None, :]).sum(axis=1)
+    return out.astype(np.float64)
+
+
+def score_accumulate(cat_new, fstar_draws, threshold_draws, return_products=False, with_w=True) -> dict:
+    """One chain's accumulators from its f* draws (S, 1001, m) and threshold VALUES (S, m, C - 1): draws, nonfinite, n_obs (int64),
+    lpd_acc, ll_sum, post_sum (n_new, 1001) -- the state block's arrays.  with_w=False leaves Wc out of l (what is wrong
+    without it)."""
+    from . import score as SC
+    cat = check_cat_new(cat_new)
+    f = np.asarray(fstar_draws, dtype=np.float64)
+    Bd = np.asarray(threshold_draws, dtype=np.float64)
+    n = cat.shape[0]
+    lp0, lse0 = SC.logprior(), SC.logprior_lse()
+    acc = dict(draws=np.zeros(n, dtype=np.int64), nonfinite=np.zeros(n, dtype=np.int64),
+               n_obs=(cat != 0).sum(axis=1).astype(np.int64), lpd_acc=np.full(n, -np.inf), ll_sum=np.zeros(n),
+               post_sum=np.zeros((n, NGRID)))
+    if return_products:
+        acc.update(products=[], wc=[])
+    for fd, B in zip(f, Bd):
+        T = score_product(cat, fd, B)
+        Wc = score_w(cat, B) if with_w else np.zeros(n)
+        if return_products:
+            acc["products"].append(T); acc["wc"].append(Wc)
+        lp = lp0[:, None] + T
+        ok = np.isfinite(lp).all(axis=0)
+        acc["nonfinite"] += ~ok
+        for r in np.flatnonzero(ok):
+            M = lp[:, r].max()
+            e = np.exp(lp[:, r] - M)
+            Z = e.sum()
+            ell = M + np.log(Z) - lse0 + Wc[r]
+            acc["post_sum"][r] += e / Z
+            acc["lpd_acc"][r] = np.logaddexp(acc["lpd_acc"][r], ell)
+            acc["ll_sum"][r] += ell
+            acc["draws"][r] += 1
+    return acc
+
+
+def _chain_axis(fstar_draws, threshold_draws):
+    f = np.asarray(fstar_draws, dtype=np.float64)
+    Bd = np.asarray(threshold_draws, dtype=np.float64)
+    if f.ndim == 3:
+        f, Bd = f[None], Bd[None]
+    if f.ndim != 4 or f.shape[2] != NGRID or Bd.ndim != 4 or Bd.shape[:2] != f.shape[:2] or Bd.shape[2] != f.shape[3]:
+        raise ValueError("fstar_draws must be (C, S, 1001, m) or (S, 1001, m), threshold_draws (C, S, m, C - 1) or (S, m, C - 1)")
+    return f, Bd
+
+
+def score_from_draws(cat_new, fstar_draws, threshold_draws, probs=(0.025, 0.5, 0.975), signs=None, return_products=False,
+                     with_w=True) -> dict:
+    """What the device accumulates and `score_combine` reports, from stored draws: fstar_draws (chains, S, 1001, m) or (S, 1001, m),
+    threshold_draws the threshold VALUES of each draw ((chains,) S, m, C - 1).  Each chain accumulated on its own, pooled and
+    finished by gpirt_amd.score.pool and .finish (signs[c] = -1 reverses that chain's grid axis of post_sum).  With
+    return_products, "products" and "wc": per chain the list of T and Wc per draw."""
+    from . import score as SC
+    f, Bd = _chain_axis(fstar_draws, threshold_draws)
+    cat = check_cat_new(cat_new, f.shape[3], Bd.shape[3] + 1)
+    chains = [score_accumulate(cat, fc, bc, return_products, with_w) for fc, bc in zip(f, Bd)]
+    out = SC.finish(SC.pool([{k: v for k, v in c.items() if k != "wc"} for c in chains], signs), probs)
+    if return_products:
+        out["products"] = [c["products"] for c in chains]
+        out["wc"] = [c["wc"] for c in chains]
+    return out
+
+
+def category_tables(fstar, B) -> tuple:
+    """(P, Hc) of one f* draw in float64 and the kernel's operations: P (C, 1001, m) with P_c = exp(logP_c), logP_c = -up_c [c < C]
+    - lo_{c-1} [c > 1] + w_c [1 < c < C] from ONE E_c = exp(-|f* - b_c|) per threshold (`_fit_terms`), and Hc (1001, m) =
+    -sum_c P_c logP_c in ascending c, a term with P_c = 0 left out."""
+    g = np.asarray(fstar, dtype=np.float64)
+    B = np.asarray(B, dtype=np.float64)
+    R = B.shape[1]
+    Cn = R + 1
+    _, up, lo = _fit_terms(g, B)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        P = np.empty((Cn,) + g.shape)
+        H = np.zeros(g.shape)
+        for c in range(1, Cn + 1):
+            lp = np.zeros(g.shape)
+            if c < Cn:
+                lp = -up[c - 1]
+            if c > 1:
+                lp = lp - lo[c - 2]
+            if 1 < c < Cn:
+                lp = lp + np.log1p(-np.exp(-(B[:, c - 1] - B[:, c - 2])))[None, :]
+            P[c - 1] = np.exp(lp)
+            H = np.where(P[c - 1] > 0.0, H - P[c - 1] * np.where(P[c - 1] > 0.0, lp, 0.0), H)
+    return P, H
+
+
+def category_entropy(q) -> np.ndarray:
+    """h(q) = -sum_c q_c log q_c over axis 0, q_c clamped to <= 1, 0 log 0 = 0, ascending c."""
+    q = np.asarray(q, dtype=np.float64)
+    h = np.zeros(q.shape[1:])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for qc in q:
+            qq = np.minimum(qc, 1.0)
+            h = np.where(qq > 0.0, h - qq * np.log(np.where(qq > 0.0, qq, 1.0)), h)
+    return h
+
+
+def predict_accumulate(cat_new, fstar_draws, threshold_draws, return_draws=False) -> dict:
+    """One chain's prediction accumulators: prob_sum (C, n_new, m), info_sum (n_new, m), pred_draws, pred_skipped.  Per counted
+    draw the contractions q_c = W^T P_c and Hbar = W^T Hc run in long double and are rounded once; a draw whose f* holds a NaN is
+    skipped whole.  With return_draws, "q", "Hbar", "weights", "products" list them per counted draw."""
+    from . import score as SC
+    cat = check_cat_new(cat_new)
+    f = np.asarray(fstar_draws, dtype=np.float64)
+    Bd = np.asarray(threshold_draws, dtype=np.float64)
+    n, m = cat.shape
+    Cn = Bd.shape[2] + 1
+    acc = dict(prob_sum=np.zeros((Cn, n, m)), info_sum=np.zeros((n, m)), pred_draws=0, pred_skipped=0)
+    if return_draws:
+        acc.update(q=[], Hbar=[], weights=[], products=[])
+    for fd, B in zip(f, Bd):
+        if np.isnan(fd).any():
+            acc["pred_skipped"] += 1
+            continue
+        T = score_product(cat, fd, B)
+        wts = SC.draw_weights(None, None, T)
+        P, H = category_tables(fd, B)
+        wl = wts.astype(LD).T
+        q = np.stack([SC._contract(wl, P[c]) for c in range(Cn)])
+        hbar = SC._contract(wl, H)
+        acc["prob_sum"] += q
+        acc["info_sum"] += category_entropy(q) - hbar
+        acc["pred_draws"] += 1
+        if return_draws:
+            acc["q"].append(q); acc["Hbar"].append(hbar); acc["weights"].append(wts); acc["products"].append(T)
+    return acc
+
+
+def predict_result(acc, cat_new, top=5) -> dict:
+    """The finished prediction from (pooled) sums: probs (n_new x m x C) = prob_sum / pred_draws, expected (the mean category, from
+    probs), info, and (top not None) next_items / next_info by gpirt_amd.score.next_items over the cells with cat_new = 0; NaN
+    without a counted draw.  acc: prob_sum (C, n_new, m), info_sum, and pred_draws / pred_skipped or "counts"."""
+    from . import score as SC
+    prob_sum, info_sum = np.asarray(acc["prob_sum"]), np.asarray(acc["info_sum"])
+    draws, skipped = (acc["counts"] if "counts" in acc else (acc["pred_draws"], acc["pred_skipped"]))
+    draws, skipped = int(draws), int(skipped)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        S = float(draws) if draws > 0 else np.nan
+        probs = np.moveaxis(prob_sum, 0, 2) / S
+        info = info_sum / S
+    out = dict(probs=probs, expected=(probs * np.arange(1, probs.shape[2] + 1)[None, None, :]).sum(axis=2), info=info,
+               prob_sum=prob_sum, info_sum=info_sum, pred_draws=draws, pred_skipped=skipped)
+    if top is not None:
+        y = np.where(np.asarray(cat_new) == 0, np.nan, 1.0)
+        out["next_items"], out["next_info"] = SC.next_items(info, y, top)
+    return out
+
+
+def predict_from_draws(cat_new, fstar_draws, threshold_draws, top=5, return_draws=False) -> dict:
+    """What the device accumulates and `score_predict_combine` reports, from stored draws (shapes as `score_from_draws`): each chain
+    accumulated on its own, the sums and counters added in chain order.  With return_draws, per chain the lists "q" (C, n_new, m),
+    "Hbar", "weights" and "products"."""
+    from . import score as SC
+    top = SC.check_top(top)
+    f, Bd = _chain_axis(fstar_draws, threshold_draws)
+    cat = check_cat_new(cat_new, f.shape[3], Bd.shape[3] + 1)
+    chains = [predict_accumulate(cat, fc, bc, return_draws) for fc, bc in zip(f, Bd)]
+    pooled = dict(prob_sum=np.array(chains[0]["prob_sum"]), info_sum=np.array(chains[0]["info_sum"]),
+                  pred_draws=sum(c["pred_draws"] for c in chains), pred_skipped=sum(c["pred_skipped"] for c in chains))
+    for c in chains[1:]:
+        pooled["prob_sum"] = pooled["prob_sum"] + c["prob_sum"]
+        pooled["info_sum"] = pooled["info_sum"] + c["info_sum"]
+    out = predict_result(pooled, cat, top)
+    if return_draws:
+        for k in ("q", "Hbar", "weights", "products"):
+            out[k] = [c[k] for c in chains]
+    return out
+
+
+def score_state_header(state) -> dict:
+    """The header of an ordinal score or predict state block (a device tensor, or a host array of int64 words): tag, version,
+    n_new, m, categories, N and, for a predict block, pred_draws and pred_skipped."""
+    wd = np.asarray(state[:8]).view(np.int64) if isinstance(state, np.ndarray) else _lib.header_words(state)
+    out = dict(tag=int(wd[0]), version=int(wd[1]), n_new=int(wd[2]), m=int(wd[3]), categories=int(wd[4]), N=int(wd[5]))
+    if out["tag"] == SCORE_PREDICT_TAG:
+        out.update(pred_draws=int(wd[6]), pred_skipped=int(wd[7]))
+    return out
+
+
+def score_block_arrays(words) -> dict:
+    """The arrays of a score block on the host (int64 words): draws, nonfinite, n_obs, lpd_acc, ll_sum, post_sum."""
+    wd = np.ascontiguousarray(words).view(np.int64)
+    n = int(wd[2])
+    at = 8
+    out = {}
+    for k in ("draws", "nonfinite", "n_obs"):
+        out[k] = wd[at:at + n].copy(); at += n
+    for k in ("lpd_acc", "ll_sum"):
+        out[k] = wd[at:at + n].view(np.float64).copy(); at += n
+    out["post_sum"] = wd[at:at + n * NGRID].view(np.float64).reshape(n, NGRID).copy()
+    return out
+
+
+def predict_block_arrays(words) -> dict:
+    """The arrays of a predict block on the host: answered (bool, n_new x m), prob_sum (C, n_new, m), info_sum (n_new, m), pred_draws,
+    pred_skipped."""
+    wd = np.ascontiguousarray(words).view(np.int64)
+    n, m, Cn = int(wd[2]), int(wd[3]), int(wd[4])
+    nm = (n * m + 63) // 64
+    bits = np.unpackbits(wd[8:8 + nm].view(np.uint8), bitorder="little")[:n * m]
+    at = 8 + nm
+    ps = wd[at:at + Cn * n * m].view(np.float64).reshape(Cn, m, n).transpose(0, 2, 1).copy(); at += Cn * n * m
+    return dict(answered=bits.reshape(m, n).T.astype(bool), prob_sum=ps,
+                info_sum=wd[at:at + n * m].view(np.float64).reshape(m, n).T.copy(), pred_draws=int(wd[6]), pred_skipped=int(wd[7]))
+
+
+def score_predict_combine(handle, states, top=5, return_state=False) -> dict:
+    """gpirt_ordinal_score_predict_combine over the predict state blocks `states` (device tensors, or Samplers with
+    ordinal_score_enable(predict=True) on): prob_sum, info_sum and the two counters added in chain order; blocks with another
+    n_new, m, C or answered-mask are refused.  Nothing is reflected: probs and info take no sign."""
+    from . import score as SC
+    top = SC.check_top(top)
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ordinal_score_predict_state")
+    pooled = np.empty(int(tensors[0].numel()), dtype=np.int64)
+    check(_lib.load().gpirt_ordinal_score_predict_combine(handle.ptr, nc, ptrs, ct.c_void_p(pooled.ctypes.data), pooled.nbytes))
+    arr = predict_block_arrays(pooled)
+    out = predict_result(arr, np.where(arr["answered"], 1, 0), top)
+    if return_state:
+        out["state"] = pooled
+    return out
+
+
+def score_combine(handle, states, signs=None, probs=(0.025, 0.5, 0.975), top=None, return_state=False) -> dict:
+    """gpirt_ordinal_score_combine over the score state blocks `states` (device tensors, or Samplers with ordinal_score_enable on,
+    all on handle's device), in chain order: the counters, post_sum and ll_sum added, lpd_acc combined by logaddexp, a chain with
+    sign -1 entering with post_sum[r][k] <-> post_sum[r][1000 - k] (signs=None: nothing is reflected; lpd takes no sign).  The
+    pooled block is finished by gpirt_amd.score.finish: its keys.  top (1..16): `states` are Samplers with predict on, and
+    "predict" holds `score_predict_combine` over their prediction blocks."""
+    from . import score as SC
+    tensors, nc, ptrs = _lib.state_ptrs(states, "ordinal_score_state")
+    sg = (ct.c_int * nc)(*[int(x) for x in signs]) if signs is not None else None
+    pooled = np.empty(int(tensors[0].numel()), dtype=np.int64)
+    check(_lib.load().gpirt_ordinal_score_combine(handle.ptr, nc, ptrs, sg, ct.c_void_p(pooled.ctypes.data), pooled.nbytes))
+    out = SC.finish(score_block_arrays(pooled), probs)
+    if top is not None:
+        out["predict"] = score_predict_combine(handle, states, top)
+    if return_state:
+        out["state"] = pooled
+    return out
+
+
+def _score_request(score, m, C):
+    """ordinal.run's score= as (cat_new, probs, predict, top), or None"""
+    from . import score as SC
+    if score is None:
+        return None
+    req = dict(score) if isinstance(score, dict) else dict(data=score)
+    unknown = set(req) - {"data", "probs", "predict", "top"}
+    if unknown or "data" not in req:
+        raise ValueError(f"ordinal.run: score= takes data, probs, predict and top; got {sorted(req)}")
+    predict = bool(req.get("predict", False))
+    top = SC.check_top(req.get("top", SC.DEFAULT_TOP))
+    return check_cat_new(req["data"], m, C), tuple(req.get("probs", SC.DEFAULT_PROBS)), predict, top
+
+
 # ------------------------------------------------------------------------------------------------ one call per run ---
 def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width=16, consistent=False, hi=6.0, points=241,
         log_prior=None, K0=None, theta_init=None, preset="fast", probs=(0.025, 0.25, 0.5, 0.75, 0.975), *, handle=None, fit=None,
-        **sampler_kw) -> dict:
+        score=None, **sampler_kw) -> dict:
     """`chains` chains of the stage-driven Sampler under the ordinal model, one after the other: per iteration step() then
     draw_thresholds(), per kept draw ordinal_record() and ordinal_accumulate_irf().  Chain c runs with the seed
     chain_seed(seed, c) from gpirtMCMC(chains=...)'s default init; K0=None starts at init_thresholds(cat, grid).
@@ -782,7 +1100,11 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
     latent scale -- chains are not sign-aligned), hist (pooled), curves (`curves` of the pooled accumulators), counters (pinned,
     failed, updates per chain), grid, categories, chains, consistent.  fit=True, or a tuple of parts ("waic", "pred", "ppc"):
     ordinal_fit_accumulate() after every kept draw and "fit", `fit_combine` over the chains (without its "state"); the default
-    makes the calls and returns the keys it did before."""
+    makes the calls and returns the keys it did before.  score=cat_new, or dict(data=cat_new, probs=, predict=, top=): the new
+    respondents cat_new (n_new x m, 0 = missing) are scored after every kept draw, after draw_thresholds
+    (ordinal_score_accumulate), and "score" holds `score_combine` over the chains -- with "predict" when asked -- and "signs":
+    chain c enters with the sign of the dot product of its theta means with chain 0's (the chains are not aligned otherwise).
+    The default makes no new call and returns the keys it returned before."""
     from . import chains as CH
     from .ops import Handle
     from .sampler import Sampler, _options
@@ -793,6 +1115,7 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
         raise ValueError("ordinal.run: chains >= 1, sample_iterations >= 1 and burn_iterations >= 0 are needed")
     Cn = categories(cat, C)
     fit_bits = fit_parts(fit)
+    sreq = _score_request(score, m, Cn)
     y = dichotomise(cat)
     o = _options(sampler_kw.get("rng", "item"), seed, True, True, None, sampler_kw.get("item0", 0), sampler_kw.get("m_total", 0),
                  sampler_kw.get("kernel_fp32", False), 0)
@@ -818,6 +1141,8 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
             s.ordinal_enable(cat, Cn, hi, points, log_prior, k0, width, planned_draws=S)
             if fit_bits:
                 s.ordinal_fit_enable(fit_bits)
+            if sreq:
+                s.ordinal_score_enable(sreq[0], predict=sreq[2], top=sreq[3])
             for it in range(S + B):
                 s.step(consistent=consistent)
                 s.draw_thresholds()
@@ -826,6 +1151,8 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
                     s.ordinal_accumulate_irf()
                     if fit_bits:
                         s.ordinal_fit_accumulate()
+                    if sreq:
+                        s.ordinal_score_accumulate()
                     th[c, it - B] = s.get("theta")
                     be[c, it - B] = s.get("beta")
             s.check()
@@ -839,6 +1166,11 @@ def run(cat, sample_iterations, burn_iterations, C=None, chains=1, seed=1, width
         if fit_bits:
             extra["fit"] = fit_combine(h, samplers, cat)
             del extra["fit"]["state"]
+        if sreq:
+            means = th.mean(axis=1)
+            signs = [1] + [(-1 if float(means[c] @ means[0]) < 0.0 else 1) for c in range(1, nc)]
+            extra["score"] = score_combine(h, samplers, signs, probs=sreq[1], top=sreq[3] if sreq[2] else None)
+            extra["score"]["signs"] = signs
         return dict(**extra, theta=th[0] if one else th, beta=be[0] if one else be, threshold_draws=dr[0] if one else dr,
                     thresholds=summarise(dr, t, probs), hist=hist, curves=curves(cum, nc * S), counters=counters, grid=t,
                     categories=Cn, chains=nc, consistent=bool(consistent))
@@ -853,4 +1185,7 @@ __all__ = ["grid", "default_log_prior", "dichotomise", "init_thresholds", "check
            "category_logprobs", "n_terms", "slice_exact", "theta_logpost_exact", "beta_exact", "window", "candidates",
            "threshold_conditional", "grid_draw", "thresholds_exact", "transition_matrix", "summarise", "curves", "make_graded", "run",
            "fit_parts", "fit_array", "fit_block_header", "fit_block_get", "fit_block_totals", "fit_derive_units",
-           "fit_derive_categories", "fit_pred", "fit_result", "fit_combine", "fit_from_draws"]
+           "fit_derive_categories", "fit_pred", "fit_result", "fit_combine", "fit_from_draws", "check_cat_new", "score_product", "score_w",
+           "score_accumulate", "score_from_draws", "category_tables", "category_entropy", "predict_accumulate", "predict_result",
+           "predict_from_draws", "score_state_header", "score_block_arrays", "predict_block_arrays", "score_combine",
+           "score_predict_combine"]

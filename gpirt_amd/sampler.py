@@ -2164,6 +2164,83 @@ class Sampler:
         from . import ordinal as OR
         return OR.fit_result(self.ordinal_fit_get, self.ordinal_fit_totals(), self.ordinal_get("cat"))
 
+    # -- scoring new respondents under ordinal responses (include/gpirt_hip.h gpirt_sampler_ordinal_score_*, gpirt_amd.ordinal.score_*)
+    def ordinal_score_enable(self, cat_new, predict=False, top=5):
+        """Upload cat_new (n_new x m over this sampler's items, 0 = missing, 1 .. C, 1 <= n_new <= 16384) and allocate the score
+        accumulators; predict=True adds the category predictions and the next-item information for every new respondent and item
+        (top, 1..16: how many unanswered items ordinal_score_predict() lists).  After ordinal_enable.  cat_new=None frees the block."""
+        import ctypes as ct
+        from . import ordinal as OR
+        if cat_new is None:
+            check(self.lib.gpirt_sampler_ordinal_score_enable(self._s, None, 0, 0, 0))
+            self._oscore = (0, False, 0)
+            return
+        c8 = np.asfortranarray(OR.check_cat_new(cat_new, self.m))
+        check(self.lib.gpirt_sampler_ordinal_score_enable(self._s, c8.ctypes.data_as(ct.POINTER(ct.c_int8)), c8.shape[0],
+                                                          int(bool(predict)), int(top)))
+        self._oscore = (c8.shape[0], bool(predict), int(top))
+        self._oscore_cat = c8
+
+    def ordinal_score_accumulate(self):
+        """Score the new respondents under the current f* and thresholds (after step() and draw_thresholds()) as one draw; the
+        chain is untouched."""
+        self._call("gpirt_sampler_ordinal_score_accumulate")
+
+    def ordinal_score_get(self, name: str) -> np.ndarray:
+        """One array by name.  Raw: draws, nonfinite, n_obs (int64, n_new), lpd_acc, ll_sum (n_new), post_sum (n_new x 1001); of the
+        last accumulate product (1001 x n_new, column-major), wc (n_new), w_table (m x C); with predict prob_sum (C x n_new x m),
+        info_sum (n_new x m), counts (int64: pred_draws, pred_skipped), weights (1001 x n_new) and operands (1001 x (C + 1) m,
+        both column-major) of the last counted draw.  Finished, from those sums (gpirt_amd.ordinal.score_result / predict_result):
+        grid_post, theta_mean, theta_sd, theta_map, lpd, loglik_mean; probs (n_new x m x C), expected, info (n_new x m)."""
+        from . import ordinal as OR
+        n = getattr(self, "_oscore", (0, False, 0))[0]
+        Cn, m = getattr(self, "_ord", (0, 0, 0))[0], self.m
+        if name in ("grid_post", "theta_mean", "theta_sd", "theta_map", "lpd", "loglik_mean"):
+            return self.ordinal_score()[name]
+        if name in ("probs", "expected", "info"):
+            return OR.predict_result({k: self.ordinal_score_get(k) for k in ("prob_sum", "info_sum", "counts")},
+                                     getattr(self, "_oscore_cat", None), top=None)[name]
+        if name in ("draws", "nonfinite", "n_obs", "counts"):
+            out = np.empty(2 if name == "counts" else n, dtype=np.int64)
+        elif name == "post_sum":
+            out = np.empty((n, NGRID))
+        elif name in ("product", "weights"):
+            out = np.empty((NGRID, n), order="F")
+        elif name == "operands":
+            out = np.empty((NGRID, (Cn + 1) * m), order="F")
+        elif name == "w_table":
+            out = np.empty((m, Cn))
+        elif name == "info_sum":
+            out = np.empty((n, m), order="F")
+        elif name == "prob_sum":
+            out = np.empty((Cn, m, n))
+            self._get_into("gpirt_sampler_ordinal_score_get", name, out)
+            return out.transpose(0, 2, 1)                  # C planes of column-major n_new x m
+        else:
+            out = np.empty(n)
+        self._get_into("gpirt_sampler_ordinal_score_get", name, out)
+        return out
+
+    def ordinal_score_state(self, predict=False):
+        """Torch view (int64, on the device) of the ONE block that holds the score accumulators (predict=True: the prediction
+        block): what gpirt_amd.ordinal.score_combine / score_predict_combine pool."""
+        return self._state("gpirt_sampler_ordinal_score_predict_state" if predict else "gpirt_sampler_ordinal_score_state")
+
+    def ordinal_score_predict_state(self):
+        return self.ordinal_score_state(predict=True)
+
+    def ordinal_score(self, probs=(0.025, 0.5, 0.975)) -> dict:
+        """Every finished output of this sampler's score accumulators (gpirt_amd.score.result's keys): grid_post, theta_mean,
+        theta_sd, theta_quantiles, theta_map, lpd, loglik_mean, lpd_total, se_lpd_total and the raw arrays."""
+        from . import ordinal as OR
+        return OR.score_combine(self.handle, [self], probs=probs)
+
+    def ordinal_score_predict(self, top=None) -> dict:
+        """Every finished output of the prediction part: probs (n_new x m x C), expected, info, next_items, next_info, prob_sum,
+        info_sum, pred_draws, pred_skipped; top defaults to ordinal_score_enable's."""
+        from . import ordinal as OR
+        return OR.score_predict_combine(self.handle, [self], top=getattr(self, "_oscore", (0, False, 5))[2] if top is None else top)
+
     # -- scoring new respondents on the device (include/gpirt_hip.h gpirt_sampler_score_*, gpirt_amd.score)
     def score_enable(self, y_new):
         """Pack y_new (n_new x m over this sampler's items, +1 / -1 / NaN, 1 <= n_new <= 16384) and allocate the

@@ -2783,6 +2783,67 @@ int gpirt_ordinal_fit_combine(gpirt_handle_t h, const void* const* d_states, int
 int gpirt_ordinal_fit_get(gpirt_handle_t h, const void* d_block, const char* name, void* h_out, int64_t bytes);
 int gpirt_ordinal_fit_totals(gpirt_handle_t h, const void* d_block, gpirt_ordinal_fit* out);
 
+/* ------------------------------------------------------ scoring new respondents under ordinal responses ---------------- */
+/* Library version 144.  What "scoring new respondents" and "predicting new respondents' unseen answers" do for the binary model,
+ * for the ordinal model above: the theta posterior and predictive density of respondents who were not in the fit, their category
+ * probabilities on every item and the item to ask next, accumulated on the device one draw at a time.  Stage API only: gpirt_run,
+ * gpirt_mcmc* and gpirt_options are unchanged, gpirt_sampler_score_enable and gpirt_sampler_score_predict_enable stay refused
+ * while ordinal is on, nothing is drawn and a sampler that never calls gpirt_sampler_ordinal_score_enable launches exactly what
+ * it launched before.
+ *
+ * cat_new: n_new x m int8, column-major, 0 = missing, 1 .. C a category, over the sampler's m items and its C; 1 <= n_new <=
+ * GPIRT_SCORE_MAX_N.  Per counted draw, with that draw's f* (N = 1001 x m; it carries mu*, the intercept is pinned at 0) and the
+ * sampler's CURRENT thresholds b_{j,c} (an accumulate after gpirt_sampler_draw_thresholds sees that iteration's):
+ *   T[k, r] = sum over r's observed cells of  -ll(b_c - f*[k,j]) [c < C]  - ll(f*[k,j] - b_{c-1}) [c > 1],   c = cat_new[r, j]
+ *   Wc[r]   = sum over r's observed cells with 1 < c < C of  log1p(-exp(-(b_c - b_{c-1}))),  ascending j
+ * T is the product draw_theta forms for the chain's respondents (the same launches, on the block's own one-hot operand and table).
+ * lp[k] = log dnorm(theta*_k) + T[k, r];  M = max_k lp[k],  Z = sum_k exp(lp[k] - M),  w_k = exp(lp[k] - M) / Z;
+ *   l = M + log Z - logsumexp_k log dnorm(theta*_k) + Wc[r]        (the log marginal likelihood of r's answers under the draw)
+ * post_sum[r][k] += w_k, lpd_acc[r] = logaddexp(lpd_acc[r], l), ll_sum[r] += l, draws[r] += 1.  Wc does not depend on theta, so the
+ * weights do not see it; it changes from draw to draw, so l may not drop it.  A NaN cell of f* skips the draw for the respondents
+ * who answered that item alone (nonfinite[r] += 1, nothing else of theirs is touched); +-inf terms are held at -1e300, which is
+ * finite.  A respondent with no answers gets the prior and l = 0.
+ *
+ * predict != 0 adds, per counted draw and for every respondent and item (answered ones included),
+ *   q_c[r, j] = sum_k w_k P_c[k, j],   P_c = exp(logP(c | f*[k,j], b_j)) with the w term (the stable log form above, one
+ *               exp(-|f* - b_c|) per threshold; never a difference of two sigmas)
+ *   info[r, j] = h(q) - sum_k w_k Hc[k, j],   h(q) = -sum_c q_c log q_c,   Hc = -sum_c P_c log P_c   (a term with P = 0 is 0)
+ * into prob_sum[c][j][r] and info_sum[j][r]: the mutual information between the unseen answer and theta_r.  A draw whose f* holds a
+ * NaN is skipped WHOLE for this part and counted in pred_skipped; +-inf cells are fine.  top (1..GPIRT_PREDICT_MAX_TOP) is checked
+ * here and used by the callers' next-item list (r's unanswered items by decreasing info, ties to the lowest j, padded with -1).
+ *
+ * gpirt_sampler_ordinal_score_enable: after gpirt_sampler_ordinal_enable; cat_new = NULL or n_new = 0 frees the block, as does
+ * gpirt_sampler_ordinal_enable(cat = NULL).  Refused, GPIRT_E_ARG with the reason: before gpirt_sampler_init, without ordinal on, a
+ * value outside 0 .. C, n_new outside 1..GPIRT_SCORE_MAX_N, top out of range; _accumulate or _get without enable; a predict name
+ * without predict.
+ * _get, by name: "draws", "nonfinite", "n_obs" (n_new int64), "lpd_acc", "ll_sum" (n_new), "post_sum" (n_new x N, k fastest); of the
+ * last accumulate "product" (T: N x n_new, k fastest), "wc" (n_new), "w_table" (m x C, row-major); with predict "prob_sum" (C planes
+ * of n_new x m, column-major), "info_sum" (n_new x m), "counts" (2 int64: pred_draws, pred_skipped), "weights" (N x n_new) and
+ * "operands" (N x (C + 1) m: [P_1 | ... | P_C | Hc]) of the last counted draw.  The finished values (grid_post = post_sum / draws,
+ * theta_mean, theta_sd, theta_quantiles, theta_map, lpd = lpd_acc - log draws, loglik_mean, probs, expected, info, next_items) are
+ * the binary scorer's functions of these sums (gpirt_amd.ordinal.score_result, predict_result).
+ *
+ * State blocks, ONE device block each, a header of 8 int64 then the arrays:
+ *   gpirt_sampler_ordinal_score_state          ("OSCR", layout version, n_new, m, C, N, 0, 0), draws, nonfinite, n_obs, lpd_acc,
+ *                                              ll_sum, post_sum
+ *   gpirt_sampler_ordinal_score_predict_state  ("OSPR", layout version, n_new, m, C, N, pred_draws, pred_skipped), the answered-mask
+ *                                              of cat_new packed 64 cells a word (cell g = r + j n_new), prob_sum, info_sum
+ * gpirt_ordinal_score_combine pools `chains` score blocks in chain order into the HOST block h_out (bytes: one block's size, the same
+ * layout): counters and sums added, lpd_acc by logaddexp, a chain with signs[c] = -1 entering with post_sum[r][k] <->
+ * post_sum[r][1000 - k] (exact: theta -> -theta with the slope leaves f + mu and the thresholds as they are; lpd takes no sign).
+ * gpirt_ordinal_score_predict_combine adds prob_sum, info_sum and the two counters; it takes no signs.  Blocks with another n_new, m,
+ * C or cat_new are refused.
+ * Device memory per state: 8 (n_new C m + 1024 C m + 2 * 1001 n_new + 1001 m) bytes for the one-hot operand, the table, the
+ * accumulators and the product; predict adds 16 (C + 1) n_new m bytes for its sums and product (about 2.4 GB at 16384 x 1024 with
+ * C = 8) and 8 * 1024 (n_new + (C + 1) m) for the weights and the operand table. */
+int gpirt_sampler_ordinal_score_enable(gpirt_sampler_t s, const int8_t* cat_new, int64_t n_new, int predict, int top);
+int gpirt_sampler_ordinal_score_accumulate(gpirt_sampler_t s);
+int gpirt_sampler_ordinal_score_get(gpirt_sampler_t s, const char* name, void* h_out, int64_t bytes);
+int gpirt_sampler_ordinal_score_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_sampler_ordinal_score_predict_state(gpirt_sampler_t s, void** d_state, int64_t* bytes);
+int gpirt_ordinal_score_combine(gpirt_handle_t h, int chains, const void* const* d_states, const int* signs, void* h_out, int64_t bytes);
+int gpirt_ordinal_score_predict_combine(gpirt_handle_t h, int chains, const void* const* d_states, void* h_out, int64_t bytes);
+
 /* ------------------------------------------------------ group posteriors: separation, overlap, party-line votes ------- */
 /* Library version 127.  The respondents come in groups (parties, cohorts, arms); per counted draw the device forms joint
  * functionals of the groups and accumulates them, so that no f draw is ever stored.  Stage API only: gpirt_run is unchanged,
